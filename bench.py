@@ -20,8 +20,19 @@ to it as `warm_cache`.
 
 Prints ONE JSON line on rank 0 (see the task contract): value = robots solved per second over all ranks;
 roofline = algorithmic bytes (488 B per robot: 388 B read + 100 B written) / average kernel time
-measured with HIP events on the launch stream; cpu_baseline = the C oracle (a port, not qpOASES) timed on the host
-cores on the same workload.
+measured with HIP events on the launch stream.
+
+A plain run does only what `value` needs: set up, warm up, time the K steps, print the line.  `--full` adds everything
+else the line used to carry, each measured in runs of its own after the headline's: the one-set replay (`warm_cache`),
+the same K steps after 2 s of idle (`from_idle`), cpu_baseline = the C oracle (a port, not qpOASES) timed on the host
+cores on the same workload, and at N = 1 the sweep of the other configs, ticks and dense forms (`other_configs`,
+`scaling_n1`), the host-boundary latencies and the batch-load probe; at N > 1 the whole batch on one GPU (`n1_reference`).
+`--no-sweep` / `--no-cpu-baseline` trim a `--full` run.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step computed - the arrays a caller of
+control_batch receives (grf_body, status, and joint_tau / active_set / the advanced gait phases where the workload has
+them) - as DIR/<name>.npy in float64 (with N > 1 ranks: DIR/<name>_rank<k>.npy, each rank its own shard).  At most
+64 MiB in all: a larger output is cut to a fixed, seeded sample of robots, whose indices go to DIR/sample_rows.npy.
 """
 from __future__ import annotations
 
@@ -63,6 +74,8 @@ GAIT_T_SWING, GAIT_T_STANCE = 0.18, 0.8  # mit_cheetah_config.yaml:17-18 = qc_se
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: 8.0 TB/s spec (6.3 TB/s achievable)
 ROTATE_BYTES = 512 << 20     # the rotating sets of the cold-cache protocol cover more than this
 CONFIG5_TOTAL = 2097152
+DUMP_BYTES = 64 << 20        # --dump-outputs writes at most this much (over all ranks)
+DUMP_SEED = 0x5EED00D0       # the fixed sample of robots a larger output is cut to
 
 CONFIG_N = {2: 4096, 3: 65536, 4: 262144, 5: 262144}  # robots per GPU (weak scaling / N = 1)
 TICK_DESC = {"fused": "; TICK: joint_q -> forward kinematics -> control() -> clamp(J^T f) -> joint_tau in the same launch (584 B/robot)",
@@ -220,10 +233,12 @@ def time_launches(launches, steps, warmup, dist=None, warm_all=False, warm_ms=0.
     return wall, ev0.elapsed_time(ev1) * 1e-3
 
 
-def run_config(ctl, q, cfg, n, start, steps, warmup, dist=None, device=0, fused=False, protocols=("cold", "warm"), warm_ms=0.0, from_idle_s=0.0):
+def run_config(ctl, q, cfg, n, start, steps, warmup, dist=None, device=0, fused=False, protocols=("cold", "warm"), warm_ms=0.0, from_idle_s=0.0,
+               keep_last=False):
     """Runs the workload under the cold-cache protocol (rotating sets) and/or as a replay of one resident set.
     Returns dict(cold=(wall, event_s), warm_cache=(wall, event_s), solved, n, sets, batch (host, set 0), warm) and, for the
-    clocked complete tick (fused == "full"), gait = what the gait clock did inside the cold timed region."""
+    clocked complete tick (fused == "full"), gait = what the gait clock did inside the cold timed region.  keep_last: also
+    last_step = dict(set, arrays) - host copies of what the last cold timed step wrote, taken before anything else runs."""
     import numpy as np
     import torch
 
@@ -290,6 +305,13 @@ def run_config(ctl, q, cfg, n, start, steps, warmup, dist=None, device=0, fused=
                 snap["phase"] = big["gait_phase"].clone()
 
         res["cold"] = time_launches(launches, steps, warmup, dist, warm_all=stateful, warm_ms=warm_ms, before_timed=before_timed)
+        if keep_last:  # the last timed step ran set (w + K - 1) mod sets; a caller of that launch receives these arrays
+            j = (snap["w"] + steps - 1) % sets
+            sl = slice(j * n, (j + 1) * n)
+            last = {k: v[sl] for k, v in out.items()}
+            if fused == "full":  # the gait clock advances the caller's phases in place
+                last["gait_phase"] = big["gait_phase"][sl]
+            res["last_step"] = {"set": j, "arrays": {k: v.cpu().numpy() for k, v in last.items()}}
         if fused == "full":
             per_set = [sum(1 for i in range(steps) if (snap["w"] + i) % sets == j) for j in range(sets)]
             edges, legs, r_edge, r_ticks, worst = count_gait_edges(snap["phase"], per_set, n, big["gait_phase"])
@@ -600,6 +622,31 @@ def rates(r, key, n, steps, bytes_per):
     return {"QPs_per_s": n * steps / wall, "avg_kernel_us": evs / steps * 1e6, "hbm_GBs": bytes_per * n * steps / evs / 1e9}
 
 
+def dump_outputs(dirname, arrays, start=0, rank=0, world=1, budget=DUMP_BYTES):
+    """--dump-outputs: `arrays` (name -> array with one row per robot, robots start ... start + n - 1) as float64 DIR/<name>.npy
+    (DIR/<name>_rank<k>.npy with N > 1 ranks).  A rank writes at most budget / N bytes: beyond that every array keeps the same
+    fixed, seeded sample of rows, and DIR/sample_rows<suffix>.npy holds their global robot indices.  Returns the file names."""
+    import numpy as np
+
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(a[:1].nbytes for a in arrays.values())
+    share = budget // world
+    suffix = "" if world == 1 else f"_rank{rank}"
+    os.makedirs(dirname, exist_ok=True)
+    files = []
+    if n * row_bytes > share:
+        m = max(1, share // (row_bytes + 8))  # (+ 8: the row's index)
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=m, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["sample_rows"] = (start + rows).astype(np.float64)
+    for k, a in arrays.items():
+        name = f"{k}{suffix}.npy"
+        np.save(os.path.join(dirname, name), a)
+        files.append(name)
+    return files
+
+
 def parse_rccl_log(text, world):
     """What RCCL said about the communicator it built (NCCL_DEBUG=INFO, subsystems INIT,GRAPH - set by main() for the group formation
     and its first all-reduce only): ranks, channels, and over WHAT each rank reaches its peers.  RCCL prints one line per channel and
@@ -659,14 +706,21 @@ def main():
                          "(Not '--n': torch.distributed.run's own parser would take that for an abbreviation of --nnodes.)")
     ap.add_argument("--scaling", choices=["auto", "strong", "weak"], default="auto",
                     help="N > 1: strong = config 5's fixed 2,097,152 robots sharded over the ranks (default); weak = --robots robots per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sweep", action="store_true", help="skip the informational runs of the other configs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else the line can carry (warm_cache, from_idle, cpu_baseline; at N = 1 the "
+                         "sweep of the other configs, host_boundary and the batch-load probe; at N > 1 n1_reference).  Off: set up, warm "
+                         "up, time the K steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (grf_body, status, ...) as DIR/<name>.npy, float64, "
+                         "at most 64 MiB in all (a larger output: a fixed, seeded sample of robots, indices in DIR/sample_rows.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-sweep", action="store_true", help="with --full: skip the informational runs of the other configs")
     ap.add_argument("--gather-results", action="store_true",
                     help="N > 1: after the timed region, all-gather the per-rank GRF blocks (result collection over xGMI, "
                          "SURVEY 8e) and report the collective's time separately")
     ap.add_argument("--probe-batch-load", action="store_true",
                     help="time the load -> assemble -> store phase alone (no solver iterations) on 2,097,152 robots "
-                         "(done by default together with the sweep)")
+                         "(done by --full together with the sweep)")
     ap.add_argument("--probe-only", action="store_true",
                     help="profiling (tools/profile_probe.sh): run ONLY the batch-load probe (--steps launches of it) and print its entry with the kernel-source hash")
     ap.add_argument("--tick", choices=["fused", "full", "full-frozen"], default=None,
@@ -796,14 +850,22 @@ def main():
 
     fused = {None: False, "fused": True, "full": "full", "full-frozen": "full-frozen"}[args.tick]
     res = run_config(ctl, q, cfg, n, start, args.steps, args.warmup, dist, device, fused=fused, warm_ms=args.device_warm_ms,
-                     from_idle_s=2.0 if args.device_warm_ms > 0 else 0.0)
+                     protocols=("cold", "warm") if args.full else ("cold",),
+                     from_idle_s=2.0 if args.full and args.device_warm_ms > 0 else 0.0, keep_last=bool(args.dump_outputs))
+    dumped = None
+    if args.dump_outputs:
+        last = res.pop("last_step")
+        dumped = {"dir": args.dump_outputs, "files": dump_outputs(args.dump_outputs, last["arrays"], start, rank, world), "set": last["set"],
+                  "robots": [start, start + n],
+                  "what": "what the last timed step computed (rotating set `set`, this rank's robots), float64"}
+        del last
 
     from quadruped_control_amd.sharding import reduce_counters
 
     on_gpu = dist is not None and dist.get_backend() == "nccl"
     rdev = f"cuda:{device}" if on_gpu else None
     wall, solved_total, total_robots = reduce_counters(dist, res["cold"][0], res["solved"], n, device=rdev)
-    wall_warm, _, _ = reduce_counters(dist, res["warm_cache"][0], 0, 0, device=rdev)
+    wall_warm = reduce_counters(dist, res["warm_cache"][0], 0, 0, device=rdev)[0] if "warm_cache" in res else None
     wall_idle = reduce_counters(dist, res["cold_from_idle"][0], 0, 0, device=rdev)[0] if "cold_from_idle" in res else None  # (max over ranks, like `wall`)
     from quadruped_control_amd.sharding import reduce_rank_stats
 
@@ -856,10 +918,11 @@ def main():
                                       "measured (their timed regions followed the host-side input generation); `value` is the device at its running clocks"}}
                if "cold_from_idle" in res else {}),
             "kernel_src_sha16": sha,
-            "warm_cache": {"value": total_robots * args.steps / wall_warm, "ms_per_step": wall_warm / args.steps * 1e3,
-                           "avg_kernel_us": res["warm_cache"][1] / args.steps * 1e6,
-                           "hbm_GBs": bytes_per * n * args.steps / res["warm_cache"][1] / 1e9,
-                           "what": "the same launch replayed on ONE resident set (inputs served by L2 / Infinity Cache)"},
+            **({"warm_cache": {"value": total_robots * args.steps / wall_warm, "ms_per_step": wall_warm / args.steps * 1e3,
+                               "avg_kernel_us": res["warm_cache"][1] / args.steps * 1e6,
+                               "hbm_GBs": bytes_per * n * args.steps / res["warm_cache"][1] / 1e9,
+                               "what": "the same launch replayed on ONE resident set (inputs served by L2 / Infinity Cache)"}}
+               if "warm_cache" in res else {}),
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": None,
                          "kernel": "qc::balance_kernel", "bytes_per_launch": bytes_per * n,
@@ -874,6 +937,8 @@ def main():
         if gather_s is not None:
             line["result_gather"] = {"bytes_per_rank": n * 96, "seconds": gather_s, "GBs_per_rank": n * 96 * (world - 1) / gather_s / 1e9,
                                      "what": "all-gather of the [n, 12] GRF blocks after the timed region (not part of value)"}
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         attach_pmc(line, cfg, n, sha, ctl.kernel_name, tick=args.tick, kernel_us=kernel_s * 1e6)
         if "gait" in res:
             line["gait_clock"] = res["gait"]
@@ -884,8 +949,8 @@ def main():
                              "allreduce_us": allreduce_s * 1e6, "backend": dist.get_backend(), "rccl": rccl_info,
                              "what": "slowest / fastest rank's average kernel time (HIP events); one 8-byte all-reduce of the kind that "
                                      "brackets the timed region (barrier + counter reduction are the only collectives: no data-path exchange)"}
-        if world > 1 and scaling == "strong":
-            # the N = 1 point of this strong-scaling curve, ALWAYS measured in the same run on rank 0's GPU while the other
+        if world > 1 and scaling == "strong" and args.full:
+            # the N = 1 point of this strong-scaling curve, measured by every --full run on rank 0's GPU while the other
             # ranks wait at the final barrier: the WHOLE batch on one device, so that the line explains itself
             del res
             torch.cuda.empty_cache()
@@ -896,17 +961,18 @@ def main():
             line["scaling_efficiency"] = line["value"] / (world * line["n1_reference"]["value"])
             line["scaling_note"] = ("strong scaling of BASELINE.json configs[4]: the same 2,097,152 robots on N GPUs; efficiency = value / "
                                     "(N x n1_reference.value).  A one-GPU line of `bench.py` without --config measures configs[1] (4096 robots) "
-                                    "and is NOT the N = 1 point of this curve; n1_reference (or other_configs.config5_n1 of that line) is.")
+                                    "and is NOT the N = 1 point of this curve; n1_reference (or other_configs.config5_n1 of that line with --full) is.")
             res = {"batch": None}
             del r1
-        if world == 1 and not args.no_cpu_baseline and not args.tick:
+        if world == 1 and args.full and not args.no_cpu_baseline and not args.tick:
             line["cpu_baseline"] = cpu_baseline(P, res["batch"])  # (configs 3 / 5: the first 4096 robots of the batch)
         del res
         torch.cuda.empty_cache()
-        if world == 1 and not args.no_sweep:
+        sweep = world == 1 and args.full and not args.no_sweep
+        if sweep:
             other = {}
             # the sweep's entries do not follow --steps: fifty steps each, whatever the headline was asked for, so that an entry reads the
-            # same from a default run and from the driver's 20-step run (the barrier + synchronize bracket costs ~30 us per timed region:
+            # same from a 200-step and from a 20-step --full run (the barrier + synchronize bracket costs ~30 us per timed region:
             # 1.5 us per step over 20 steps, 0.6 over 50 - DESIGN.md section 6 "Steps")
             k = SWEEP_STEPS
             for c in (2, 3, 4):
@@ -998,9 +1064,9 @@ def main():
                 torch.cuda.empty_cache()
             del dense
             line["other_configs"] = other
-        if world == 1 and not args.no_sweep:
+        if sweep:
             line["host_boundary"] = host_boundary(ctl, q)
-        if world == 1 and (args.probe_batch_load or not args.no_sweep):
+        if world == 1 and (args.probe_batch_load or sweep):
             line["batch_load_probe"] = batch_load_probe(q, P, device)
         # the driver keeps the contract's keys and the last 2 000 characters of this line, so the numbers a reader needs
         # from the long entries above come once more, compactly, as its LAST key (us = average kernel time by HIP events, cold-cache

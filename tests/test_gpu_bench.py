@@ -1,4 +1,4 @@
-"""-m gpu: bench.py keeps its contract (one JSON line on rank 0 with roofline + cpu_baseline at N = 1; `--gpus N`
+"""-m gpu: bench.py keeps its contract (one JSON line on rank 0 with roofline, + cpu_baseline at N = 1 with --full; `--gpus N`
 starts N ranks by itself or checks the launcher's WORLD_SIZE; N > 1 shards config 5's fixed batch and reduces the
 counters over the process group - RCCL when the box has the GPUs, gloo on one device otherwise)."""
 import json
@@ -31,7 +31,7 @@ def _free_port():
 
 
 def test_bench_line_single_gpu(built):
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "30", "--warmup", "5", "--no-sweep"], cwd=ROOT,
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "30", "--warmup", "5", "--full", "--no-sweep"], cwd=ROOT,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
@@ -53,10 +53,51 @@ def test_bench_line_single_gpu(built):
     assert len(d["kernel_src_sha16"]) == 16
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(built, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` does only what `value` needs (set-up, warm-up, K timed steps, the line) and
+    spends at most 30 s outside its steps; `--dump-outputs DIR` writes what the last timed step computed, which is the oracle's answer
+    for the inputs of the rotating set that step ran."""
+    import time
+
+    import numpy as np
+
+    import bench
+    import quadruped_control_amd as q
+    from oracle import c_oracle
+
+    steps, warmup = 40, 5
+    t0 = time.time()
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(tmp_path)],
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    elapsed = time.time() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _last_json(r.stdout)
+    for k in CONTRACT:
+        assert k in d, k
+    assert d["steps"] == steps and d["warmup"] == warmup and d["dtype"] == "f64" and d["higher_is_better"] is True and d["unit"] == "QPs/s"
+    assert abs(d["value"] - 4096 * steps / (d["ms_per_step"] * steps * 1e-3)) < 1e-6 * d["value"] and d["solved_fraction"] == 1.0
+    for k in ("cpu_baseline", "warm_cache", "from_idle", "other_configs", "scaling_n1", "host_boundary", "batch_load_probe"):
+        assert k not in d, k
+    assert elapsed - (steps + warmup) * d["ms_per_step"] * 1e-3 < 30.0, elapsed  # the whole run, less (K + W) steps
+    dm = d["dumped_outputs"]
+    assert sorted(dm["files"]) == ["grf_body.npy", "status.npy"] and dm["robots"] == [0, 4096]
+    assert sum(os.path.getsize(tmp_path / f) for f in dm["files"]) <= 64 << 20
+    grf, status = np.load(tmp_path / "grf_body.npy"), np.load(tmp_path / "status.npy")
+    assert grf.dtype == np.float64 and grf.shape == (4096, 12) and status.dtype == np.float64 and status.shape == (4096,)
+    assert (status == 0).all()
+    assert dm["set"] == (d["device_warmup"]["warmup_launches_done"] + steps - 1) % 269
+    batch, _ = bench.make_batch(2, 4096, 0, seed_shift=0x100 * dm["set"])
+    ref, ref_status, _ = c_oracle.control_batch(q.cheetah_params(mu=0.6), batch)
+    assert (ref_status == 0).all()
+    err = np.max(np.abs(grf - ref) / np.maximum(1.0, np.abs(ref).max(axis=1, keepdims=True)))
+    assert err < 1e-6, err
+
+
 def test_bench_driver_line_with_the_whole_sweep(built):
-    """The exact command the driver issues at round end (`bench.py --gpus 1 --steps 20 --warmup 5`, sweep included): one JSON
-    line whose informational entries are all there - a failure anywhere in the sweep would cost the round its bench record."""
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"], cwd=ROOT, capture_output=True, text=True, timeout=1500)
+    """The full one-GPU run (`bench.py --gpus 1 --steps 20 --warmup 5 --full`, sweep included): one JSON line whose informational
+    entries are all there - a failure anywhere in the sweep would cost the run its record."""
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"], cwd=ROOT, capture_output=True, text=True,
+                       timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _last_json(r.stdout)
     for k in CONTRACT + ("roofline", "cpu_baseline", "other_configs", "scaling_n1", "host_boundary", "batch_load_probe", "device_warmup", "warm_cache"):
@@ -150,7 +191,7 @@ def test_bench_two_ranks_torchrun(built):
     env = dict(os.environ, QC_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--steps", "10", "--warmup", "2", "--gather-results",
-           "--scaling", "strong", "--robots", "65536"]
+           "--scaling", "strong", "--robots", "65536", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _last_json(r.stdout)
@@ -162,8 +203,8 @@ def test_bench_self_launch_two_ranks(built):
     """`python bench.py --gpus 2` without a launcher starts its own two ranks (one-device hook on a 1-GPU box)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(QC_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "5", "--warmup", "1", "--scaling", "strong", "--robots", "32768"],
-                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "5", "--warmup", "1", "--scaling", "strong", "--robots", "32768",
+                        "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     _check_two_rank_line(_last_json(r.stdout), 65536)
 
@@ -176,7 +217,7 @@ def test_bench_eight_ranks_before_the_eight_gpus(built):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(QC_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0", QC_BENCH_TIMEOUT_S="120")
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "8", "--steps", "10", "--warmup", "2", "--scaling", "strong", "--robots", "16384",
-                        "--gather-results"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
+                        "--gather-results", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, (r.stderr + r.stdout)[-3000:]
     d = _last_json(r.stdout)
     for k in CONTRACT:
@@ -219,8 +260,8 @@ def test_bench_two_ranks_rccl_on_one_device(built):
     detected"); then this is a skip and test_bench_two_ranks_rccl (two devices) stays the armed test."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(QC_BENCH_ONE_DEVICE="1", QC_BENCH_ONE_DEVICE_BACKEND="nccl", QC_BENCH_TIMEOUT_S="60", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "5", "--warmup", "1", "--scaling", "strong", "--robots", "32768"],
-                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "5", "--warmup", "1", "--scaling", "strong", "--robots", "32768",
+                        "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     if r.returncode != 0:
         tail = (r.stderr + r.stdout)[-4000:]
         if "Duplicate GPU" in tail or "invalid usage" in tail.lower() or "did not form" in tail:
@@ -258,7 +299,7 @@ def test_bench_two_ranks_rccl(built):
         pytest.skip("needs two GPUs (RCCL)")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "QC_BENCH_ONE_DEVICE")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "10", "--warmup", "2", "--gather-results"],
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "10", "--warmup", "2", "--gather-results", "--full"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _last_json(r.stdout)

@@ -327,6 +327,43 @@ def test_bench_gpus_flag_is_not_ignored():
         assert r.returncode != 0 and "--gpus 2 but only" in (r.stderr + r.stdout)
 
 
+def test_bench_dump_outputs_writes_float64_within_its_budget(tmp_path):
+    """--dump-outputs: every array as float64 DIR/<name>.npy; past the budget the same fixed, seeded rows of every array (the same
+    in every run), their global robot indices in sample_rows.npy; with ranks, per-rank names and an equal share of the budget."""
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    import bench
+
+    r = subprocess.run([sys.executable, "bench.py", "--help"], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    rng = np.random.default_rng(1)
+    arrays = {"grf_body": rng.standard_normal((1000, 12)), "status": np.zeros(1000, dtype=np.int32)}
+    files = bench.dump_outputs(str(tmp_path / "all"), arrays, start=5000)
+    assert sorted(files) == ["grf_body.npy", "status.npy"]
+    g = np.load(tmp_path / "all" / "grf_body.npy")
+    s = np.load(tmp_path / "all" / "status.npy")
+    assert g.dtype == np.float64 and s.dtype == np.float64 and s.shape == (1000,)
+    np.testing.assert_array_equal(g, arrays["grf_body"])
+    budget = 40 * 1024
+    picks = []
+    for rep in range(2):
+        d = tmp_path / f"cut{rep}"
+        files = bench.dump_outputs(str(d), arrays, start=5000, budget=budget)
+        assert sorted(files) == ["grf_body.npy", "sample_rows.npy", "status.npy"]
+        assert sum(os.path.getsize(d / f) - 128 for f in files) <= budget  # (128 B: the .npy header)
+        rows = np.load(d / "sample_rows.npy")
+        assert rows.dtype == np.float64 and len(rows) == budget // (13 * 8 + 8) and np.all(np.diff(rows) > 0)
+        assert rows.min() >= 5000 and rows.max() < 6000
+        np.testing.assert_array_equal(np.load(d / "grf_body.npy"), arrays["grf_body"][rows.astype(np.int64) - 5000])
+        picks.append(rows)
+    np.testing.assert_array_equal(picks[0], picks[1])
+    files = bench.dump_outputs(str(tmp_path / "ranks"), arrays, start=1000, rank=1, world=2)
+    assert sorted(files) == ["grf_body_rank1.npy", "status_rank1.npy"]
+
+
 def test_bench_parses_rccl_transport_log():
     """`ranks.rccl` of an N > 1 bench line is parsed from RCCL's own INIT / GRAPH log.  No multi-GPU box has ever run it, so
     the parser is held here against lines in the format RCCL 2.26 prints (the one-rank log of the 1-GPU box has the INIT and Pattern lines;

@@ -3,8 +3,8 @@
 cd ${GRAFT_REPO_ROOT:-.}
 O=gpurun_out/r06_final; mkdir -p $O
 for i in 1 2; do echo "== run $i: python -m pytest tests -m gpu -q"; python -m pytest tests -m gpu -q 2>&1 | grep -v amdgpu.ids | tail -6; done > $O/pytest_gpu.log 2>&1
-python bench.py --gpus 1 --steps 20 --warmup 5 2> $O/bench_driver_flags.err | grep '^{' > $O/bench_driver_flags.json
-python bench.py 2> $O/bench_default.err | grep '^{' > $O/bench_default.json
+python bench.py --gpus 1 --steps 20 --warmup 5 --full 2> $O/bench_driver_flags.err | grep '^{' > $O/bench_driver_flags.json
+python bench.py --full 2> $O/bench_default.err | grep '^{' > $O/bench_default.json
 S=20260930
 {
 echo "== QC_FUZZ_SEED=$S"
