@@ -269,6 +269,53 @@ int qc_query_launch(qc_handle* h, size_t n, int kin, int warm, qc_launch_info* o
  * Calls that change device constants synchronise the device first.  Returns QC_ERR_INVALID for an unknown key. */
 int qc_set_tuning(qc_handle* h, const char* key, double value);
 
+/* Commander mode: the body of the reference's commander loop (commander_node.cpp:344-531) on the device.  Instead of a
+ * host-supplied desired COM state (qc_batch_in.Rwb_d / x_d / xdot_d / w_d), each robot carries a qc_commander_state that
+ * the tick itself advances, from the measured COM state and the user's body twist (cmd_vel, commander_node.cpp:191-202):
+ *   1. a fresh command overwrites Vb and sets cmd_pending;
+ *   2. standing latches once |x(2) - stand_height| < stand_tol (strict, math::almost_equal; never reset);
+ *   3. standing and gait_running already set: a pending command is applied - (Rwb_d, x_d) = integrate_twist_yaw((Rwb, x),
+ *      Vb, cmd_dt) (trajectory.cpp:29-69) with x_d(2) = stand_height, (xdot_d, w_d) = Ad_T(Rwb, x) Vb (rigid3d.cpp:259-271,
+ *      i.e. Rwb^T (v - x x w) and Rwb^T w) - and the gait clock, the contact rule and the foothold planner run as in
+ *      qc_control_batch; standing but not yet running: gait_running is set and nothing else happens this tick;
+ *   4. until the gait runs, the gait map is make_stance_gait(): all legs stance, the phases do not move, no planning.
+ * The QP and the stance J^T torques run every tick with the state's current desired values.  (stand_cmd_received is not
+ * modelled: calling qc_tick_batch for a robot stands for it.)  INTEGRATION.md names the two reference quirks kept here. */
+typedef struct qc_commander_state {
+  int32_t standing;     /* the stand height was reached (latched)                                 */
+  int32_t gait_running; /* the gait clock has been started                                        */
+  int32_t cmd_pending;  /* cmd_vel_received: a command waits to be applied                        */
+  int32_t reserved;
+  double Vb[6];         /* latest body twist (vx, vy, vz, wx, wy, wz)                             */
+  double Rwb_d[9];      /* desired state fed to the controller, row-major                         */
+  double x_d[3];
+  double xdot_d[3];
+  double w_d[3];
+} qc_commander_state;
+
+/* Per-call arguments of qc_tick_batch (DEVICE pointers). */
+typedef struct qc_command_in {
+  size_t struct_size;           /* = sizeof(qc_command_in); checked (a struct that grows carries its size)   */
+  const double* twist;          /* [n][6] commands; must be readable when `fresh` is given, used where fresh[i] != 0 */
+  const uint8_t* fresh;         /* [n] 1 = a command arrived for this robot since its previous tick; NULL = none    */
+  qc_commander_state* state;    /* [n] IN/OUT, initialise with qc_commander_state_init                     */
+  double stand_height;          /* x_stand(2), 0.26 (commander_node.cpp:355)                               */
+  double stand_tol;             /* 0.005 (commander_node.cpp:387)                                          */
+  double cmd_dt;                /* user command integration step, 0.001 (commander_node.cpp:344); not the tick period */
+} qc_command_in;
+
+/* The reference's values: struct_size set, no arrays, stand_height 0.26, stand_tol 0.005, cmd_dt 0.001. */
+void qc_default_command(qc_command_in* cmd);
+/* Host helper: the commander's initial state for n robots (commander_node.cpp:346-367): flags 0, Vb 0, Rwb_d = I,
+ * x_d = x_stand (NULL = (0, 0, 0.26)), xdot_d = w_d = 0. */
+void qc_commander_state_init(qc_commander_state* states, size_t n, const double x_stand[3]);
+/* The complete tick in commander mode: asynchronous on `stream`, no host synchronisation (graph-capturable).  `in` carries
+ * the measured state and the tick's arrays like qc_control_batch with joint_q, joint_qdot, gait_phase, gait_dt and
+ * swing_state given; its Rwb_d / x_d / xdot_d / w_d must be NULL (the desired state lives in cmd->state), stance,
+ * swing_pos and swing_vel must be NULL, and out->joint_tau is required.  QC_ERR_INVALID otherwise, nothing launched. */
+int qc_tick_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_command_in* cmd, const uint32_t* warm,
+                  const qc_batch_out* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,16 @@ class QcSwingState(C.Structure):
     _fields_ = [("leg_state", C.c_int32 * 4), ("has_traj", C.c_int32 * 4), ("p_start", C.c_double * 12), ("p_final", C.c_double * 12)]
 
 
+class QcCommanderState(C.Structure):
+    _fields_ = [("standing", C.c_int32), ("gait_running", C.c_int32), ("cmd_pending", C.c_int32), ("reserved", C.c_int32),
+                ("Vb", C.c_double * 6), ("Rwb_d", C.c_double * 9), ("x_d", C.c_double * 3), ("xdot_d", C.c_double * 3), ("w_d", C.c_double * 3)]
+
+
+class QcCommandIn(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("twist", C.c_void_p), ("fresh", C.c_void_p), ("state", C.c_void_p),
+                ("stand_height", C.c_double), ("stand_tol", C.c_double), ("cmd_dt", C.c_double)]
+
+
 class QcLaunchInfo(C.Structure):
     _fields_ = [("lanes_per_robot", C.c_int32), ("mode", C.c_int32), ("form", C.c_int32), ("strategies", C.c_int32),
                 ("chunk", C.c_int64), ("blocks", C.c_int64), ("resident_workgroups", C.c_int64), ("lds_bytes", C.c_int64)]
@@ -53,7 +63,7 @@ class QcLaunchInfo(C.Structure):
 
 EXPORTS = ("qc_create_abi", "qc_destroy", "qc_control_batch", "qc_control_batch_host", "qc_control",
            "qc_last_error", "qc_kernel_name", "qc_abi_version", "qc_default_kinematics", "qc_set_kinematics", "qc_set_gait", "qc_swing_state_init",
-           "qc_set_tuning", "qc_query_launch", "qc_check_abi")
+           "qc_set_tuning", "qc_query_launch", "qc_check_abi", "qc_default_command", "qc_commander_state_init", "qc_tick_batch")
 
 _lib = None
 
@@ -113,6 +123,13 @@ def load():
     lib.qc_query_launch.restype = C.c_int
     lib.qc_check_abi.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.c_size_t]
     lib.qc_check_abi.restype = C.c_int
+    lib.qc_default_command.argtypes = [C.POINTER(QcCommandIn)]
+    lib.qc_default_command.restype = None
+    lib.qc_commander_state_init.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.qc_commander_state_init.restype = None
+    lib.qc_tick_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcBatchIn), C.POINTER(QcCommandIn), C.c_void_p,
+                                  C.POINTER(QcBatchOut), C.c_void_p]
+    lib.qc_tick_batch.restype = C.c_int
     # the structures above are hand-written mirrors of the header: a library built from another revision is refused here,
     # before any of them crosses the boundary
     rc = lib.qc_check_abi(ABI_VERSION, C.sizeof(QcParams), C.sizeof(QcBatchIn), C.sizeof(QcBatchOut))

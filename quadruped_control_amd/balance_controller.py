@@ -23,6 +23,7 @@ import numpy as np
 from . import _lib
 from .gait import LEG_NAMES, LegState, make_stance_gait
 
+_DESIRED = ("Rwb_d", "x_d", "xdot_d", "w_d")  # host-supplied desired COM state; tick_batch() keeps it on the device instead
 _IN_FIELDS = (("Rwb", 9), ("Rwb_d", 9), ("x", 3), ("xdot", 3), ("w", 3), ("x_d", 3), ("xdot_d", 3),
               ("w_d", 3), ("feet", 12))
 
@@ -168,15 +169,21 @@ class BalanceController:
         return force_map
 
     # ------------------------------------------------------------------ batches
-    def _marshal(self, batch, warm, out, want_active_set, want_iterations, want_torques):
+    def _marshal(self, batch, warm, out, want_active_set, want_iterations, want_torques, commander=False):
         """Validate the arguments of control_batch() and build the C structs; allocates `out` when it is None.
-        Launches nothing.  Returns (n, bi, bo, warm_ptr, out)."""
+        Launches nothing.  Returns (n, bi, bo, warm_ptr, out).  commander=True: tick_batch() - the desired state
+        (Rwb_d, x_d, xdot_d, w_d) is not an input."""
         import torch
 
         n = batch["x"].shape[0]
         dev = torch.device("cuda", self.device)
         bi = _lib.QcBatchIn()
         fields = _IN_FIELDS + ((("joint_q", 12),) if batch.get("joint_q") is not None else ())
+        if commander:
+            given = [k for k in _DESIRED if batch.get(k) is not None]
+            if given:
+                raise ValueError(f"tick_batch: {', '.join(given)} must not be given: the desired state lives in the commander state")
+            fields = tuple(f for f in fields if f[0] not in _DESIRED)
         for name, k in fields:
             t = batch.get(name)
             if t is None and name == "feet" and batch.get("joint_q") is not None:
@@ -281,6 +288,66 @@ class BalanceController:
 
         return launch, out
 
+    # --------------------------------------------------------- commander mode
+    def _marshal_command(self, n, command):
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        c = _lib.QcCommandIn()
+        self._lib.qc_default_command(C.byref(c))
+        st = command.get("state")
+        if st is None or st.dtype != torch.uint8 or not st.is_contiguous() or st.numel() != n * COMMANDER_STATE_DTYPE.itemsize or st.device != dev:
+            raise ValueError(f"command['state']: need a contiguous uint8 tensor of n * {COMMANDER_STATE_DTYPE.itemsize} bytes on {dev} "
+                             "(new_commander_states)")
+        c.state = st.data_ptr()
+        fresh, twist = command.get("fresh"), command.get("twist")
+        if fresh is not None:
+            if fresh.dtype != torch.uint8 or not fresh.is_contiguous() or fresh.numel() != n or fresh.device != dev:
+                raise ValueError(f"command['fresh']: need contiguous uint8 [{n}] on {dev}")
+            if twist is None:
+                raise ValueError("command['fresh'] needs command['twist']")
+            c.fresh = fresh.data_ptr()
+        if twist is not None:
+            if twist.dtype != torch.float64 or not twist.is_contiguous() or twist.numel() != n * 6 or twist.device != dev:
+                raise ValueError(f"command['twist']: need contiguous float64 [{n},6] on {dev}")
+            c.twist = twist.data_ptr()
+        for name in ("stand_height", "stand_tol", "cmd_dt"):
+            if command.get(name) is not None:
+                setattr(c, name, float(command[name]))
+        return c
+
+    def plan_tick(self, batch, command, warm=None, out=None, want_active_set=False, want_iterations=False, stream=None):
+        """tick_batch() marshalled once: returns (launch, out), `launch()` being one qc_tick_batch call (graph-capturable).
+        Like plan_batch, planning launches nothing."""
+        import torch
+
+        n, bi, bo, warm_ptr, out = self._marshal(batch, warm, out, want_active_set, want_iterations, True, commander=True)
+        c = self._marshal_command(n, command)
+        self.query_launch(n, kin=True, warm=warm is not None)  # occupancy query done now, not inside a graph capture
+        s = stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.device))
+        fn, h, sp = self._lib.qc_tick_batch, self._h, C.c_void_p(s.cuda_stream)
+        bi_ref, c_ref, bo_ref = C.byref(bi), C.byref(c), C.byref(bo)
+        keep = (batch, command, warm, out, bi, c, bo)
+
+        def launch(_keep=keep):
+            rc = fn(h, n, bi_ref, c_ref, warm_ptr, bo_ref, sp)
+            if rc != _lib.QC_OK:
+                raise RuntimeError(f"qc_tick_batch failed ({rc}): {_lib.last_error()}")
+
+        return launch, out
+
+    def tick_batch(self, batch, command, warm=None, out=None, want_active_set=False, want_iterations=False, stream=None):
+        """The complete tick in commander mode (qc_tick_batch, include/qc_balance.h): the desired COM state is not an input but
+        the per-robot commander state (stand-up latch, gait start, body-twist integration; commander_node.cpp:372-531).
+        `batch`: device tensors as for control_batch() with joint_q, joint_qdot, gait_phase, gait_dt and swing_state, and no
+        Rwb_d / x_d / xdot_d / w_d / stance / swing_pos / swing_vel.  `command`: dict(state=uint8 tensor of n commander
+        records (new_commander_states, updated in place), twist=[n,6] float64 or None, fresh=[n] uint8 or None (1 = a command
+        arrived for this robot), and optionally stand_height / stand_tol / cmd_dt).  Asynchronous on `stream`; returns the
+        out dict of control_batch(..., want_torques=True)."""
+        launch, out = self.plan_tick(batch, command, warm, out, want_active_set, want_iterations, stream)
+        launch()
+        return out
+
     def control_batch_host(self, batch, warm=None, want_active_set=False, want_iterations=False, want_torques=False):
         """n robots, numpy (host) arrays in and out; PCIe-inclusive convenience path."""
         n = batch["x"].shape[0]
@@ -343,6 +410,21 @@ def new_swing_states(n):
     """Host array of n `qc_swing_state` records in the "nothing planned yet" state (qc_swing_state_init)."""
     s = np.zeros(n, dtype=SWING_STATE_DTYPE)
     _lib.load().qc_swing_state_init(s.ctypes.data_as(C.c_void_p), n)
+    return s
+
+
+COMMANDER_STATE_DTYPE = np.dtype([("standing", np.int32), ("gait_running", np.int32), ("cmd_pending", np.int32), ("reserved", np.int32),
+                                  ("Vb", np.float64, 6), ("Rwb_d", np.float64, 9), ("x_d", np.float64, 3), ("xdot_d", np.float64, 3),
+                                  ("w_d", np.float64, 3)])  # == qc_commander_state
+
+
+def new_commander_states(n, x_stand=(0.0, 0.0, 0.26)):
+    """Host array of n `qc_commander_state` records in the commander's initial state (qc_commander_state_init:
+    flags 0, Rwb_d = I, x_d = x_stand, zero velocities).  Move it to the device as a uint8 tensor for tick_batch:
+    torch.from_numpy(s.view(np.uint8)).cuda()."""
+    s = np.zeros(n, dtype=COMMANDER_STATE_DTYPE)
+    xs = np.ascontiguousarray(np.asarray(x_stand, dtype=np.float64).reshape(3))
+    _lib.load().qc_commander_state_init(s.ctypes.data_as(C.c_void_p), n, xs.ctypes.data_as(C.c_void_p))
     return s
 
 

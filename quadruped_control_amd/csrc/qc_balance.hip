@@ -439,19 +439,115 @@ QC_DEV uint32_t swing_plan(CParams& P, const BatchIn& in, long robot, int foot0,
   return has_bits;
 }
 
+// Commander mode (qc_tick_batch): one step of the reference's commander loop (commander_node.cpp:372-478) for this robot, run
+// where the robot is assembled - once per robot per launch (the hand-over paths re-read records, not inputs, and do not come
+// here).  Replaces the desired state in `S` when a held command is applied and returns whether the gait runs this tick (gait
+// clock, contact rule, planner).  Every member of a lane group computes the same values; member 0 stores what changed.
+QC_DEV bool commander_step(const BatchIn& in, long robot, int member, RawState& S, const TickExtra& X) {
+  int standing = X.flags[0], running = X.flags[1], pending = X.flags[2];
+  const bool fresh = X.fresh != 0;
+  double vb[6];
+#pragma unroll
+  for (int k = 0; k < 6; k++) vb[k] = fresh ? X.tw[k] : X.vb[k];  // cmdCallback, :191-202: the latest command wins
+  if (fresh) pending = 1;
+  if (!standing && fabs(S.x[2] - in.stand_height) < in.stand_tol) standing = 1;  // :386-391, almost_equal (strict)
+  bool run = false, applied = false;
+  if (standing) {
+    if (running) {
+      if (pending) {  // :397-428
+        // integrate_twist_yaw (trajectory.cpp:29-69): Rbb' from the angle-axis increment, the translation rotated by it
+        const double dt = in.cmd_dt;
+        const double d[3] = {vb[3] * dt, vb[4] * dt, vb[5] * dt};
+        const double th = __builtin_sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+        double Rb[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+        double t[3];
+        if (fabs(th) < 1.0e-12) {  // almost_equal(angle, 0.0)
+#pragma unroll
+          for (int k = 0; k < 3; k++) t[k] = vb[k] * dt;
+        } else {
+          const double a[3] = {d[0] / th, d[1] / th, d[2] / th};
+          double s, c;
+          sincos_joint(th, &s, &c);
+          const double oc = 1.0 - c;
+#pragma unroll
+          for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) Rb[3 * i + j] = oc * a[i] * a[j] + (i == j ? c : 0.0);
+          Rb[1] -= s * a[2]; Rb[3] += s * a[2];
+          Rb[2] += s * a[1]; Rb[6] -= s * a[1];
+          Rb[5] -= s * a[0]; Rb[7] += s * a[0];
+#pragma unroll
+          for (int i = 0; i < 3; i++) t[i] = (Rb[3 * i] * vb[0] + Rb[3 * i + 1] * vb[1] + Rb[3 * i + 2] * vb[2]) * dt;
+        }
+        // Rz(yaw of Rwb) without atan2 / sincos: yaw = atan2(R10, R00) away from pitch = +-pi/2.  At gimbal lock (h == 0, or a
+        // non-finite h) yaw 0 is taken: Drake's branch there is not pinned.
+        const double h = __builtin_sqrt(S.R[0] * S.R[0] + S.R[3] * S.R[3]);
+        const bool ok = h > 0.0 && h < 1.0e300;
+        const double cy = ok ? S.R[0] / h : 1.0, sy = ok ? S.R[3] / h : 0.0;
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+          S.Rd[j] = cy * Rb[j] - sy * Rb[3 + j];
+          S.Rd[3 + j] = sy * Rb[j] + cy * Rb[3 + j];
+          S.Rd[6 + j] = Rb[6 + j];
+        }
+        S.xd[0] = S.x[0] + (cy * t[0] - sy * t[1]);
+        S.xd[1] = S.x[1] + (sy * t[0] + cy * t[1]);
+        S.xd[2] = in.stand_height;  // "TODO: height drifts", :409
+        // Ad_T of the CURRENT pose (rigid3d.cpp:259-271): [R^T, -R^T [x]x; 0, R^T] Vb
+        const double u[3] = {vb[0] - (S.x[1] * vb[5] - S.x[2] * vb[4]), vb[1] - (S.x[2] * vb[3] - S.x[0] * vb[5]),
+                             vb[2] - (S.x[0] * vb[4] - S.x[1] * vb[3])};
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+          S.xdotd[k] = S.R[k] * u[0] + S.R[3 + k] * u[1] + S.R[6 + k] * u[2];
+          S.wd[k] = S.R[k] * vb[3] + S.R[3 + k] * vb[4] + S.R[6 + k] * vb[5];
+        }
+        pending = 0;
+        applied = true;
+      }
+      run = true;
+    } else {
+      running = 1;  // gait_scheduler.start(), :474-478: the first schedule() is next tick
+    }
+  }
+  if (member == 0) {
+    CmdState* C = in.cmd_state + robot;
+    if (standing != X.flags[0]) C->standing = standing;
+    if (running != X.flags[1]) C->gait_running = running;
+    if (pending != X.flags[2]) C->cmd_pending = pending;
+    if (fresh) {
+#pragma unroll
+      for (int k = 0; k < 6; k++) C->Vb[k] = vb[k];
+    }
+    if (applied) {
+#pragma unroll
+      for (int k = 0; k < 9; k++) C->Rwb_d[k] = S.Rd[k];
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        C->x_d[k] = S.xd[k];
+        C->xdot_d[k] = S.xdotd[k];
+        C->w_d[k] = S.wd[k];
+      }
+    }
+  }
+  return run;
+}
+
 // the assembly of one robot (or of this lane's feet of it): wrench target and lever arms, contact state, optional
 // gait clock and swing planning.  Returns the stance word (bits 0-3 LegState, bit 8 = non-finite input).
-// (`S`, `fp`: what fetch_state() read; `sw`: the robot's four LegState bytes if in.stance is given)
+// (`S`, `fp`: what fetch_state() read - in commander mode the step may replace its desired state; `sw`: the robot's four
+// LegState bytes if in.stance is given)
 template <bool KIN, int FPL, bool STR>
-QC_DEV uint32_t assemble_from_state(CParams& P, const BatchIn& in, long robot, int member, const RawState& S, const double (&fp)[3 * FPL], uint32_t sw,
+QC_DEV uint32_t assemble_from_state(CParams& P, const BatchIn& in, long robot, int member, RawState& S, const double (&fp)[3 * FPL], uint32_t sw,
                                     const TickExtra& X, Wrench<FPL>& W) {
   constexpr int GG = 4 / FPL;
   const int foot0 = member * FPL;
+  // commander mode: until the gait runs, make_stance_gait() with the phases held and no planning (commander_node.cpp:366, 480)
+  const bool run = !(KIN && in.cmd_state) || commander_step(in, robot, member, S, X);
   const double fin = wrench_from_state<FPL, KIN>(P, S, fp, foot0, W);
   uint32_t stance = 0xFu;  // make_stance_gait(), gait.cpp:24-34
   if (in.stance) {
     stance = ((sw & 0xFFu) ? 1u : 0u) | ((sw & 0xFF00u) ? 2u : 0u) | ((sw & 0xFF0000u) ? 4u : 0u) | ((sw & 0xFF000000u) ? 8u : 0u);
-  } else if (in.gait_phase) {
+  } else if (in.gait_phase && run) {
     // GaitScheduler::phase(), gait.cpp:125-134 (almost_equal = |a-b| < 1e-12, math/numerics.cpp:18-21)
     const double duty = in.gait_duty ? X.duty : P.stance_phase;
     stance = 0;
@@ -480,7 +576,7 @@ QC_DEV uint32_t assemble_from_state(CParams& P, const BatchIn& in, long robot, i
       stance |= (ge0 && le) ? (1u << i) : 0u;
     }
   }
-  if (KIN && in.swing_state)  // (bits 12-15: has_traj per leg, for the torque pass; only member 0's word reaches the stock: the group's bits are or-ed)
+  if (KIN && in.swing_state && run)  // (bits 12-15: has_traj per leg, for the torque pass; only member 0's word reaches the stock: the group's bits are or-ed)
     stance |= (uint32_t)group_or<GG, STR>((int)swing_plan<FPL, STR>(P, in, robot, foot0, stance, S, W, X)) << 12;
   // non-finite inputs poison b, r or R: report QC_NOT_PD instead of iterating on NaNs
   const bool bad = group_or<GG, STR>(!(fin == 0.0) ? 1 : 0) != 0;
@@ -1812,6 +1908,38 @@ __global__ __launch_bounds__(128, 2) void balance_pair_kernel(const DevParams* _
 // =============================================================== host / C ABI
 typedef void (*qc_kernel_fn)(const qc::DevParams*, long, qc::BatchIn, const uint32_t*, qc::BatchOut, long, int);
 
+// qc::BalanceKernelArgs is a hand-written mirror of balance_kernel's parameter list (the kernarg segment lays every argument at the
+// next multiple of its alignment); every instantiation is stored as a qc_kernel_fn, so that type IS the list.  Growing BatchIn or
+// BatchOut moves the members behind it: these asserts fail the build instead of letting kernarg_here read the wrong bytes.
+template <class... A>
+constexpr size_t kernarg_offset(int i) {
+  constexpr size_t sz[] = {sizeof(A)...}, al[] = {alignof(A)...};
+  size_t off = 0;
+  for (int k = 0; k < (int)sizeof...(A); k++) {
+    off = (off + al[k] - 1) / al[k] * al[k];
+    if (k == i) return off;
+    off += sz[k];
+  }
+  return off;
+}
+template <class F>
+struct KernargOf;
+template <class... A>
+struct KernargOf<void (*)(A...)> {
+  static constexpr int count = (int)sizeof...(A);
+  static constexpr size_t at(int i) { return kernarg_offset<A...>(i); }
+};
+using KernelArgList = KernargOf<qc_kernel_fn>;
+static_assert(KernelArgList::count == 7, "balance_kernel's parameter list changed: update qc::BalanceKernelArgs");
+static_assert(offsetof(qc::BalanceKernelArgs, Pg) == KernelArgList::at(0) && offsetof(qc::BalanceKernelArgs, n) == KernelArgList::at(1) &&
+                  offsetof(qc::BalanceKernelArgs, in) == KernelArgList::at(2) && offsetof(qc::BalanceKernelArgs, warm) == KernelArgList::at(3) &&
+                  offsetof(qc::BalanceKernelArgs, out) == KernelArgList::at(4) && offsetof(qc::BalanceKernelArgs, chunk) == KernelArgList::at(5) &&
+                  offsetof(qc::BalanceKernelArgs, refill_t) == KernelArgList::at(6),
+              "qc::BalanceKernelArgs no longer mirrors balance_kernel's kernarg layout");
+static_assert(sizeof(qc::CmdState) == sizeof(qc_commander_state) && offsetof(qc::CmdState, Vb) == offsetof(qc_commander_state, Vb) &&
+                  offsetof(qc::CmdState, Rwb_d) == offsetof(qc_commander_state, Rwb_d) && offsetof(qc::CmdState, w_d) == offsetof(qc_commander_state, w_d),
+              "qc::CmdState mirrors qc_commander_state");
+
 struct qc_handle {
   int device;
   int cus;                  // compute units of the device
@@ -2220,6 +2348,25 @@ void qc_swing_state_init(qc_swing_state* s, size_t n) {
     for (int l = 0; l < 4; l++) s[i].leg_state[l] = -1;
 }
 
+void qc_default_command(qc_command_in* c) {
+  if (!c) return;
+  std::memset(c, 0, sizeof(*c));
+  c->struct_size = sizeof(qc_command_in);
+  c->stand_height = 0.26;  // x_stand(2), commander_node.cpp:355
+  c->stand_tol = 0.005;    // commander_node.cpp:387
+  c->cmd_dt = 0.001;       // "User cmd integration step", commander_node.cpp:344
+}
+
+void qc_commander_state_init(qc_commander_state* s, size_t n, const double x_stand[3]) {
+  if (!s) return;
+  const double xs[3] = {x_stand ? x_stand[0] : 0.0, x_stand ? x_stand[1] : 0.0, x_stand ? x_stand[2] : 0.26};  // :354
+  std::memset(s, 0, n * sizeof(qc_commander_state));
+  for (size_t i = 0; i < n; i++) {
+    s[i].Rwb_d[0] = s[i].Rwb_d[4] = s[i].Rwb_d[8] = 1.0;  // Rwb_d = eye(3, 3), :347
+    for (int k = 0; k < 3; k++) s[i].x_d[k] = xs[k];      // x_d = x_stand, :364
+  }
+}
+
 int qc_set_kinematics(qc_handle* h, const qc_kinematics* kin) {
   if (!h) return fail(QC_ERR_INVALID, "qc_set_kinematics: null handle");
   qc_kinematics k;
@@ -2469,6 +2616,8 @@ void qc_destroy(qc_handle* h) {
   delete h;
 }
 
+static int launch_batch(qc_handle* h, size_t n, bool kin, const qc::BatchIn& bi, const uint32_t* warm, const qc::BatchOut& bo, void* stream);
+
 int qc_control_batch(qc_handle* h, size_t n, const qc_batch_in* in, const uint32_t* warm, const qc_batch_out* out, void* stream) {
   if (!h || !in || !out) return fail(QC_ERR_INVALID, "qc_control_batch: null argument");
   if (n == 0) return QC_OK;
@@ -2488,6 +2637,11 @@ int qc_control_batch(qc_handle* h, size_t n, const qc_batch_in* in, const uint32
                  in->gait_phase, in->gait_duty, in->swing_pos, in->swing_vel, in->joint_qdot,
                  reinterpret_cast<qc::SwingState*>(in->swing_state), in->gait_dt};
   qc::BatchOut bo{out->grf_body, out->status, out->active_set, out->iterations, out->joint_tau};
+  return launch_batch(h, n, kin, bi, warm, bo, stream);
+}
+
+// the one launch behind qc_control_batch and qc_tick_batch (arguments validated)
+static int launch_batch(qc_handle* h, size_t n, bool kin, const qc::BatchIn& bi, const uint32_t* warm, const qc::BatchOut& bo, void* stream) {
   qc_launch_plan lp;
   const int rc = plan_launch(h, (long)n, kin, warm != nullptr, &lp);
   if (rc != QC_OK) return rc;
@@ -2502,6 +2656,37 @@ int qc_control_batch(qc_handle* h, size_t n, const qc_batch_in* in, const uint32
   lp.fn<<<dim3(lp.blocks), dim3(64), lp.lds, (hipStream_t)stream>>>(h->d_params, (long)n, bi, warm, bo, lp.chunk, lp.refill_t);
   QC_HIP(hipGetLastError());
   return QC_OK;
+}
+
+int qc_tick_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_command_in* cmd, const uint32_t* warm, const qc_batch_out* out,
+                  void* stream) {
+  if (!h || !in || !cmd || !out) return fail(QC_ERR_INVALID, "qc_tick_batch: null argument");
+  if (cmd->struct_size != sizeof(qc_command_in)) {
+    char msg[160];
+    std::snprintf(msg, sizeof(msg), "qc_tick_batch: qc_command_in.struct_size is %zu, this library's qc_command_in has %zu B (qc_default_command sets it)",
+                  cmd->struct_size, sizeof(qc_command_in));
+    return fail(QC_ERR_INVALID, msg);
+  }
+  if (!in->Rwb || !in->x || !in->xdot || !in->w || !in->joint_q || !in->joint_qdot || !in->gait_phase || !in->gait_dt || !in->swing_state)
+    return fail(QC_ERR_INVALID, "qc_tick_batch: the complete tick needs Rwb, x, xdot, w, joint_q, joint_qdot, gait_phase, gait_dt and swing_state");
+  if (in->Rwb_d || in->x_d || in->xdot_d || in->w_d)
+    return fail(QC_ERR_INVALID, "qc_tick_batch: Rwb_d, x_d, xdot_d and w_d must be NULL (the desired state lives in qc_command_in.state)");
+  if (in->stance || in->swing_pos || in->swing_vel)
+    return fail(QC_ERR_INVALID, "qc_tick_batch: stance, swing_pos and swing_vel must be NULL (the gait clock and the planner make them)");
+  if (!out->grf_body || !out->status || !out->joint_tau) return fail(QC_ERR_INVALID, "qc_tick_batch: grf_body, status and joint_tau are required");
+  if (!cmd->state) return fail(QC_ERR_INVALID, "qc_tick_batch: qc_command_in.state is required");
+  if (cmd->fresh && !cmd->twist) return fail(QC_ERR_INVALID, "qc_tick_batch: qc_command_in.fresh needs twist");
+  if (!std::isfinite(cmd->stand_height) || !(cmd->stand_tol >= 0.0) || !std::isfinite(cmd->stand_tol) || !std::isfinite(cmd->cmd_dt))
+    return fail(QC_ERR_INVALID, "qc_tick_batch: stand_height, stand_tol (>= 0) and cmd_dt must be finite");
+  if (n == 0) return QC_OK;
+  QC_HIP(hipSetDevice(h->device));
+  qc::BatchIn bi{in->Rwb, nullptr, in->x, in->xdot, in->w, nullptr, nullptr, nullptr, in->feet, nullptr, in->joint_q,
+                 in->gait_phase, in->gait_duty, nullptr, nullptr, in->joint_qdot,
+                 reinterpret_cast<qc::SwingState*>(in->swing_state), in->gait_dt,
+                 reinterpret_cast<qc::CmdState*>(cmd->state), cmd->fresh ? cmd->twist : nullptr, cmd->fresh,
+                 cmd->stand_height, cmd->stand_tol, cmd->cmd_dt};
+  qc::BatchOut bo{out->grf_body, out->status, out->active_set, out->iterations, out->joint_tau};
+  return launch_batch(h, n, true, bi, warm, bo, stream);
 }
 
 // host-pointer variant.  Large batches: one device staging allocation, H2D copies, kernel, D2H copies, sync.

@@ -131,6 +131,12 @@ struct SwingState {
   double p_final[12];
 };
 
+// mirrors qc_commander_state (include/qc_balance.h)
+struct CmdState {
+  int32_t standing, gait_running, cmd_pending, reserved;
+  double Vb[6], Rwb_d[9], x_d[3], xdot_d[3], w_d[3];
+};
+
 struct BatchIn {
   const double *Rwb, *Rwb_d, *x, *xdot, *w, *x_d, *xdot_d, *w_d, *feet;
   const uint8_t* stance;
@@ -142,6 +148,12 @@ struct BatchIn {
   const double* joint_qdot;
   struct SwingState* swing_state;
   const double* gait_dt;
+  // commander mode (qc_tick_batch; cmd_state == NULL everywhere else): the desired state comes from cmd_state, not from
+  // Rwb_d / x_d / xdot_d / w_d (NULL then), and the robot's commander step gates the gait clock and the planner
+  struct CmdState* cmd_state;
+  const double* cmd_twist;
+  const uint8_t* cmd_fresh;
+  double stand_height, stand_tol, cmd_dt;
 };
 struct BatchOut {
   double* grf_body;
@@ -726,13 +738,25 @@ struct RawState {
 template <int FPL, bool KIN>
 QC_DEV void fetch_state(const BatchIn& in, long idx, int foot0, RawState& S, double (&fp)[3 * FPL]) {
   load9(in.Rwb, idx, S.R);
-  load9(in.Rwb_d, idx, S.Rd);
   load3(in.x, idx, S.x);
-  load3(in.x_d, idx, S.xd);
   load3(in.xdot, idx, S.xdot);
-  load3(in.xdot_d, idx, S.xdotd);
   load3(in.w, idx, S.w);
-  load3(in.w_d, idx, S.wd);
+  if (KIN && in.cmd_state) {  // commander mode: the desired state the robot's commander holds (the step may replace it)
+    const CmdState* C = in.cmd_state + idx;
+#pragma unroll
+    for (int k = 0; k < 9; k++) S.Rd[k] = C->Rwb_d[k];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      S.xd[k] = C->x_d[k];
+      S.xdotd[k] = C->xdot_d[k];
+      S.wd[k] = C->w_d[k];
+    }
+  } else {
+    load9(in.Rwb_d, idx, S.Rd);
+    load3(in.x_d, idx, S.xd);
+    load3(in.xdot_d, idx, S.xdotd);
+    load3(in.w_d, idx, S.wd);
+  }
   const double* q = (KIN ? in.joint_q : in.feet) + 12 * idx + 3 * foot0;
 #pragma unroll
   for (int k = 0; k < 3 * FPL; k++) fp[k] = q[k];
@@ -742,9 +766,27 @@ QC_DEV void fetch_state(const BatchIn& in, long idx, int foot0, RawState& S, dou
 struct TickExtra {
   double ph[4], duty, dt;
   int leg_state[4], has[4];
+  // commander mode: the flags and the held command of the robot's commander, and this tick's command (read whether or not it
+  // is fresh, with the other loads - a load behind the `fresh` byte would be one more dependent round trip)
+  int flags[3], fresh;
+  double vb[6], tw[6];
 };
 template <bool KIN>
 QC_DEV void fetch_extra(const BatchIn& in, long robot, TickExtra& X) {
+  if (KIN && in.cmd_state) {
+    const CmdState* C = in.cmd_state + robot;
+    X.flags[0] = C->standing;
+    X.flags[1] = C->gait_running;
+    X.flags[2] = C->cmd_pending;
+#pragma unroll
+    for (int k = 0; k < 6; k++) X.vb[k] = C->Vb[k];
+    X.fresh = 0;
+    if (in.cmd_fresh) {
+      X.fresh = in.cmd_fresh[robot];
+#pragma unroll
+      for (int k = 0; k < 6; k++) X.tw[k] = in.cmd_twist[6 * robot + k];
+    }
+  }
   if (!in.stance && in.gait_phase) {
 #pragma unroll
     for (int i = 0; i < 4; i++) X.ph[i] = in.gait_phase[4 * robot + i];

@@ -1,0 +1,334 @@
+"""-m gpu: commander mode (qc_tick_batch) - the stand-up latch, the gait start and the body-twist integration of the
+reference's commander loop (commander_node.cpp:372-531) run inside the complete tick, checked tick by tick against
+tests/commander_restatement.py for the commander and oracle.c_oracle for the rest of the tick."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+DESIRED = ("Rwb_d", "x_d", "xdot_d", "w_d")
+MEAS = ("Rwb", "x", "xdot", "w", "joint_q", "joint_qdot")
+
+# (n, tuning, lanes per robot, kernel mode, ticks): query_launch(n, kin=True) must report the instantiation the case claims.
+# (The paired-waves kernel, mode 3, serves QP-only batches: a tick with joint_q - which commander mode always is - never runs on it.)
+CASES = {
+    "4-lane": (600, {}, 4, None, 40),
+    "2-lane": (20000, {}, 2, None, 40),
+    "1-lane-one-fill": (140000, {}, 1, 1, 24),
+    "1-lane-big": (524288, {}, 1, 1, 4),
+    "dense-forced": (700, {"force_dense": 1}, 4, None, 30),
+    "dense-W": (40000, "dense_w", 1, None, 16),
+}
+
+
+@pytest.fixture(scope="module")
+def q(built):
+    import quadruped_control_amd as q
+
+    return q
+
+
+def _controller(q, tune):
+    P = q.cheetah_params(0.6)
+    if tune == "dense_w":
+        A = np.random.default_rng(3).normal(size=(12, 12))
+        P["W"] = P["W"] + 2e-6 * A @ A.T
+        tune = {}
+    ctl = q.BalanceController.from_params(P).set_tuning(**tune)
+    return P, ctl
+
+
+def _check_instantiation(ctl, n, lanes, mode, name):
+    info = ctl.query_launch(n, kin=True)
+    assert info["lanes_per_robot"] == lanes, (name, info)
+    if mode is not None:
+        assert info["mode"] == mode, (name, info)
+    if name.startswith("dense"):
+        assert ctl.kernel_name == "dense-12x12"
+
+
+def _base(n):
+    from tests.test_oracle_cpu import _planned_batch
+
+    b = _planned_batch(n, 0)
+    return {k: np.ascontiguousarray(v) for k, v in b.items()}
+
+
+def _heights(base_x2, tick, rng_params):
+    """COM heights rising from the workload's value toward 0.26 + e (e within the band for most robots, 0.02 above it for
+    some: those never stand), reaching it at robot-dependent ticks T (0 = from the start)."""
+    T, e = rng_params
+    goal = 0.26 + e
+    frac = np.where(T == 0, 1.0, np.minimum(1.0, tick / np.maximum(T, 1)))
+    return goal + (base_x2 - goal) * (1.0 - frac)
+
+
+def _to_dev(a):
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _state_host(q, d_state):
+    return d_state.cpu().numpy().view(q.COMMANDER_STATE_DTYPE)
+
+
+def _compare_tick(q, O, P, ctl, tick, n, dev, ref, tag):
+    """dev / ref: dict(out, state, phase, swing)."""
+    s, cmd = dev["state"], ref["cmd"]
+    got = np.stack([s["standing"], s["gait_running"], s["cmd_pending"]], axis=1)
+    assert np.array_equal(got, cmd.flags()), (tag, tick)
+    assert np.array_equal(s["Vb"], cmd.Vb), (tag, tick)
+    for k, v in cmd.desired().items():
+        assert np.max(np.abs(s[k] - v)) <= 1e-12, (tag, tick, k)
+    assert np.array_equal(dev["phase"], ref["phase"]), (tag, tick)
+    ds, rs = dev["swing"], ref["swing"]
+    assert np.array_equal(ds["leg_state"], rs["leg_state"]) and np.array_equal(ds["has_traj"], rs["has_traj"]), (tag, tick)
+    m = rs["has_traj"].repeat(3, axis=1) == 1
+    if m.any():
+        assert np.max(np.abs(ds["p_start"][m] - rs["p_start"][m])) < 1e-9, (tag, tick)
+        assert np.max(np.abs(ds["p_final"][m] - rs["p_final"][m])) < 1e-9, (tag, tick)
+    o, r = dev["out"], ref["out"]
+    assert np.array_equal(o["status"], r["status"]), (tag, tick)
+    scale = np.maximum(1.0, np.abs(r["grf_body"]).max(axis=1, keepdims=True))
+    assert np.max(np.abs(o["grf_body"] - r["grf_body"]) / scale) < 1e-6, (tag, tick)
+    assert np.max(np.abs(o["joint_tau"] - r["joint_tau"])) < 2e-5, (tag, tick)
+
+
+def _reference_tick(O, P, meas, cmd, ref_phase, ref_swing, dt, twist, fresh):
+    """One tick of the reference loop: commander step (restatement), then the gait clock + planned tick for running robots and
+    the stance-gait tick for the others (oracle)."""
+    n = meas["x"].shape[0]
+    run, applied = cmd.step(meas["Rwb"], meas["x"], twist, fresh)
+    des = cmd.desired()
+    full = dict(meas, **des)
+    grf, tau, status = np.zeros((n, 12)), np.zeros((n, 12)), np.zeros(n, np.int32)
+    ri, si = np.nonzero(run)[0], np.nonzero(~run)[0]
+    if ri.size:
+        ph = np.ascontiguousarray(ref_phase[ri])
+        O.gait_update(ph, np.ascontiguousarray(dt[ri]))
+        ref_phase[ri] = ph
+        sub = {k: np.ascontiguousarray(v[ri]) for k, v in full.items()}
+        sub["gait_phase"] = ph
+        st = np.ascontiguousarray(ref_swing[ri])
+        r = O.tick_planned_batch(P, sub, st, threads=16)
+        ref_swing[ri] = st
+        grf[ri], tau[ri], status[ri] = r["grf_body"], r["joint_tau"], r["status"]
+    if si.size:
+        sub = {k: np.ascontiguousarray(v[si]) for k, v in full.items()}
+        sub["stance"] = np.ones((si.size, 4), np.uint8)
+        r = O.tick_batch(P, sub, threads=16)
+        grf[si], tau[si], status[si] = r["grf_body"], r["joint_tau"], r["status"]
+    return run, applied, dict(grf_body=grf, joint_tau=tau, status=status)
+
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_closed_loop_commander_parity(q, case):
+    import torch
+
+    from oracle import c_oracle as O
+    from tests import commander_restatement as CR
+
+    n, tune, lanes, mode, ticks = CASES[case]
+    P, ctl = _controller(q, tune)
+    _check_instantiation(ctl, n, lanes, mode, case)
+    rng = np.random.default_rng(0xC0DE + n)
+    base = _base(n)
+    meas = {k: base[k] for k in MEAS}
+    T = rng.integers(0, max(2, ticks // 2), n)
+    e = np.where(rng.uniform(size=n) < 0.15, 0.02, rng.uniform(-0.003, 0.003, n))
+    dt = rng.uniform(0.002, 0.005, n)
+    cmd = CR.Commander(n)
+    ref_phase = base["gait_phase"].copy()
+    ref_swing = O.new_swing_states(n)
+    d_state = _to_dev(q.new_commander_states(n).view(np.uint8))
+    d_phase = _to_dev(base["gait_phase"])
+    d_swing = _to_dev(q.new_swing_states(n).view(np.uint8))
+    d_dt = _to_dev(dt)
+    d_meas = {k: _to_dev(v) for k, v in meas.items() if k != "x"}
+    ran = applied_any = 0
+    for tick in range(ticks):
+        x = meas["x"].copy()
+        x[:, 2] = _heights(base["x"][:, 2], tick, (T, e))
+        twist = np.stack([rng.uniform(-0.2, 0.2, n), rng.uniform(-0.1, 0.1, n), np.zeros(n),
+                          rng.uniform(-0.02, 0.02, n), rng.uniform(-0.02, 0.02, n), rng.uniform(-0.05, 0.05, n)], axis=1)
+        fresh = (rng.uniform(size=n) < 0.3).astype(np.uint8)
+        batch = dict(d_meas, x=_to_dev(x), gait_phase=d_phase, gait_dt=d_dt, swing_state=d_swing)
+        out = ctl.tick_batch(batch, dict(state=d_state, twist=_to_dev(twist), fresh=_to_dev(fresh)))
+        torch.cuda.synchronize()
+        m = dict(meas, x=x)
+        run, applied, r = _reference_tick(O, P, m, cmd, ref_phase, ref_swing, dt, twist, fresh)
+        dev = dict(out={k: v.cpu().numpy() for k, v in out.items()}, state=_state_host(q, d_state), phase=d_phase.cpu().numpy(),
+                   swing=d_swing.cpu().numpy().view(q.SWING_STATE_DTYPE))
+        _compare_tick(q, O, P, ctl, tick, n, dev, dict(cmd=cmd, out=r, phase=ref_phase, swing=ref_swing), case)
+        ran += int(run.sum())
+        applied_any += int(applied.sum())
+    # the run covered every branch: robots that never stood, robots that started the gait, and commands applied
+    assert ran > 0 and applied_any > 0
+    assert (cmd.standing == 0).any() and (cmd.gait_running == 1).any()
+    if ticks >= 16:
+        assert (ref_swing["has_traj"] == 1).any()
+
+
+def _standing_states(q, base, n):
+    s = q.new_commander_states(n)
+    s["standing"] = 1
+    s["gait_running"] = 1
+    for k in DESIRED:
+        s[k] = base[k]
+    return s
+
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_commander_step_changes_nothing_else(q, case):
+    """A running robot with no pending command: qc_tick_batch must give what qc_control_batch gives when fed the state's desired
+    values - bit for bit, over two ticks (the planner state carried) - and leave the commander state untouched."""
+    import torch
+
+    n, tune, lanes, mode, _ = CASES[case]
+    _, ctl = _controller(q, tune)
+    _check_instantiation(ctl, n, lanes, mode, case)
+    base = _base(n)
+    dt = _to_dev(np.full(n, 1.0 / 300.0))
+    st0 = _standing_states(q, base, n)
+    d_state = _to_dev(st0.view(np.uint8))
+    d_meas = {k: _to_dev(base[k]) for k in MEAS}
+    d_des = {k: _to_dev(base[k]) for k in DESIRED}
+    ph_a, ph_b = _to_dev(base["gait_phase"]), _to_dev(base["gait_phase"])
+    sw_a, sw_b = _to_dev(q.new_swing_states(n).view(np.uint8)), _to_dev(q.new_swing_states(n).view(np.uint8))
+    zeros = _to_dev(np.zeros(n, np.uint8))
+    junk = _to_dev(np.full((n, 6), 7.0))
+    for tick in range(2):
+        # (tick 1: a `fresh` array of zeros with a twist behind it changes nothing either)
+        command = dict(state=d_state) if tick == 0 else dict(state=d_state, fresh=zeros, twist=junk)
+        oa = ctl.tick_batch(dict(d_meas, gait_phase=ph_a, gait_dt=dt, swing_state=sw_a), command)
+        ob = ctl.control_batch(dict(d_meas, **d_des, gait_phase=ph_b, gait_dt=dt, swing_state=sw_b), want_torques=True)
+        torch.cuda.synchronize()
+        for k in ("grf_body", "status", "joint_tau"):
+            assert torch.equal(oa[k], ob[k]), (case, tick, k)
+        assert torch.equal(ph_a, ph_b) and torch.equal(sw_a, sw_b), (case, tick)
+        assert _state_host(q, d_state).tobytes() == st0.tobytes(), (case, tick)
+
+
+@pytest.mark.parametrize("n,lanes,mode", [(600, 4, None), (20000, 2, None), (140000, 1, 1)])
+def test_commander_step_runs_exactly_once(q, n, lanes, mode):
+    """Cold-started config-3 robots leave stragglers that the lane-group tails (re-packed records) finish: after
+    ONE launch every robot's commander, clock and planner have advanced exactly one step."""
+    import torch
+
+    from oracle import c_oracle as O
+    from tests import commander_restatement as CR
+
+    P, ctl = _controller(q, {})
+    _check_instantiation(ctl, n, lanes, mode, "exactly-once")
+    base = _base(n)
+    rng = np.random.default_rng(5)
+    x = base["x"].copy()
+    x[:, 2] = 0.26 + rng.uniform(-0.004, 0.004, n)  # every robot inside the band
+    kind = np.arange(n) % 4
+    s = q.new_commander_states(n)
+    s["standing"] = (kind >= 1).astype(np.int32)          # 0: stands up this tick
+    s["gait_running"] = (kind >= 2).astype(np.int32)      # 1: starts the gait this tick
+    s["cmd_pending"] = (kind == 3).astype(np.int32)       # 2: runs; 3: runs and applies its held command
+    s["Vb"] = rng.uniform(-0.1, 0.1, (n, 6))
+    cmd = CR.Commander(n)
+    cmd.standing[:], cmd.gait_running[:], cmd.cmd_pending[:] = s["standing"], s["gait_running"], s["cmd_pending"]
+    cmd.Vb[:] = s["Vb"]
+    dt = np.full(n, 1.0 / 300.0)
+    d_state = _to_dev(s.view(np.uint8))
+    d_phase = _to_dev(base["gait_phase"])
+    d_swing = _to_dev(q.new_swing_states(n).view(np.uint8))
+    meas = dict({k: base[k] for k in MEAS}, x=x)
+    out = ctl.tick_batch(dict({k: _to_dev(v) for k, v in meas.items()}, gait_phase=d_phase, gait_dt=_to_dev(dt), swing_state=d_swing),
+                         dict(state=d_state), want_iterations=True)
+    torch.cuda.synchronize()
+    it = out["iterations"].cpu().numpy()
+    assert it.max() > np.median(it) + 3  # stragglers: the hand-over paths ran
+    ref_phase, ref_swing = base["gait_phase"].copy(), O.new_swing_states(n)
+    run, applied, r = _reference_tick(O, P, meas, cmd, ref_phase, ref_swing, dt, None, None)
+    assert run.sum() == applied.sum() * 2 and (run == (kind >= 2)).all()
+    dev = dict(out={k: v.cpu().numpy() for k, v in out.items()}, state=_state_host(q, d_state), phase=d_phase.cpu().numpy(),
+               swing=d_swing.cpu().numpy().view(q.SWING_STATE_DTYPE))
+    _compare_tick(q, O, P, ctl, 0, n, dev, dict(cmd=cmd, out=r, phase=ref_phase, swing=ref_swing), f"once-{n}")
+
+
+def test_tick_batch_argument_validation(q):
+    """Every missing, extra or inconsistent pointer, a wrong struct_size and bad scalars: QC_ERR_INVALID with a message, nothing
+    launched (the outputs keep their fill, the state and the clock do not move)."""
+    import torch
+
+    from quadruped_control_amd import _lib
+
+    n = 8
+    _, ctl = _controller(q, {})
+    lib = _lib.load()
+    base = _base(n)
+    keep = {k: _to_dev(base[k]) for k in MEAS + DESIRED}
+    st0 = q.new_commander_states(n)
+    st0["standing"] = st0["gait_running"] = 1
+    d_state = _to_dev(st0.view(np.uint8))
+    d_phase = _to_dev(base["gait_phase"])
+    d_swing = _to_dev(q.new_swing_states(n).view(np.uint8))
+    d_dt = _to_dev(np.full(n, 0.01))
+    d_tw = _to_dev(np.zeros((n, 6)))
+    d_fr = _to_dev(np.ones(n, np.uint8))
+    d_st = _to_dev(np.ones((n, 4), np.uint8))
+    out = {"grf_body": _to_dev(np.full((n, 12), 5.0)), "status": _to_dev(np.full(n, -1, np.int32)), "joint_tau": _to_dev(np.full((n, 12), 5.0))}
+
+    def valid():
+        bi = _lib.QcBatchIn()
+        for k in MEAS:
+            setattr(bi, k, keep[k].data_ptr())
+        bi.gait_phase, bi.gait_dt, bi.swing_state = d_phase.data_ptr(), d_dt.data_ptr(), d_swing.data_ptr()
+        c = _lib.QcCommandIn()
+        lib.qc_default_command(C.byref(c))
+        c.state, c.twist, c.fresh = d_state.data_ptr(), d_tw.data_ptr(), d_fr.data_ptr()
+        bo = _lib.QcBatchOut()
+        for k, v in out.items():
+            setattr(bo, k, v.data_ptr())
+        return bi, c, bo
+
+    cases = []
+    for k in ("Rwb", "x", "xdot", "w", "joint_q", "joint_qdot", "gait_phase", "gait_dt", "swing_state"):
+        cases.append((f"missing {k}", lambda bi, c, bo, k=k: setattr(bi, k, None)))
+    for k in DESIRED:
+        cases.append((f"extra {k}", lambda bi, c, bo, k=k: setattr(bi, k, keep[k].data_ptr())))
+    for k in ("stance", "swing_pos", "swing_vel"):
+        cases.append((f"extra {k}", lambda bi, c, bo, k=k: setattr(bi, k, (d_st if k == "stance" else keep["joint_q"]).data_ptr())))
+    for k in ("grf_body", "status", "joint_tau"):
+        cases.append((f"missing out {k}", lambda bi, c, bo, k=k: setattr(bo, k, None)))
+    cases += [("missing state", lambda bi, c, bo: setattr(c, "state", None)),
+              ("fresh without twist", lambda bi, c, bo: setattr(c, "twist", None)),
+              ("struct_size small", lambda bi, c, bo: setattr(c, "struct_size", C.sizeof(c) - 8)),
+              ("struct_size zero", lambda bi, c, bo: setattr(c, "struct_size", 0)),
+              ("nan stand_height", lambda bi, c, bo: setattr(c, "stand_height", float("nan"))),
+              ("negative stand_tol", lambda bi, c, bo: setattr(c, "stand_tol", -1.0)),
+              ("inf cmd_dt", lambda bi, c, bo: setattr(c, "cmd_dt", float("inf")))]
+    torch.cuda.synchronize()
+    for name, spoil in cases:
+        bi, c, bo = valid()
+        spoil(bi, c, bo)
+        rc = lib.qc_tick_batch(ctl._h, n, C.byref(bi), C.byref(c), None, C.byref(bo), None)
+        assert rc == -1, name
+        msg = _lib.last_error()
+        assert msg.startswith("qc_tick_batch:") and len(msg) > 20, (name, msg)
+    for k, v in (("null in", (None, "c")), ("null cmd", ("bi", None)), ("null out", ("bi", "c"))):
+        bi, c, bo = valid()
+        args = [C.byref(bi) if v[0] else None, C.byref(c) if v[1] else None, C.byref(bo) if k != "null out" else None]
+        assert lib.qc_tick_batch(ctl._h, n, args[0], args[1], None, args[2], None) == -1, k
+    torch.cuda.synchronize()
+    assert (out["status"] == -1).all() and (out["grf_body"] == 5.0).all() and (out["joint_tau"] == 5.0).all()
+    assert _state_host(q, d_state).tobytes() == st0.tobytes()
+    assert np.array_equal(d_phase.cpu().numpy(), base["gait_phase"])
+    # and the valid call runs: the gait was running, so the command is applied in this very tick
+    bi, c, bo = valid()
+    assert lib.qc_tick_batch(ctl._h, n, C.byref(bi), C.byref(c), None, C.byref(bo), None) == 0, _lib.last_error()
+    torch.cuda.synchronize()
+    assert (out["status"] != -1).all() and not np.array_equal(d_phase.cpu().numpy(), base["gait_phase"])
+    s = _state_host(q, d_state)
+    assert (s["cmd_pending"] == 0).all() and (s["x_d"][:, 2] == 0.26).all()
+    # the Python layer refuses a desired state in the batch
+    with pytest.raises(ValueError, match="desired state"):
+        ctl.tick_batch(dict(keep, gait_phase=d_phase, gait_dt=d_dt, swing_state=d_swing), dict(state=d_state))
