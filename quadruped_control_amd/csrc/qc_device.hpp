@@ -396,7 +396,9 @@ struct LegTrig {
 // non-finite angles give NaN (the reference's libm would still return some value in [-1, 1] for the former: INTEGRATION.md).
 QC_DEV void sincos_joint(double x, double* __restrict__ sn, double* __restrict__ cs) {
   const bool ok = fabs(x) < 1073741824.0;                            // (false for NaN too)
-  const double fn = __builtin_rint(x * 6.36619772367581382433e-01);  // x * 2/pi
+  // (x * 2/pi + 0 and r z + 0: the same values, but a zero product comes out +0, so the reduction and the sine of x = -0 stay
+  // -0 - sin(-0) = -0 as in libm - at no cost: the FMA takes the place of the multiplication)
+  const double fn = __builtin_rint(__builtin_fma(x, 6.36619772367581382433e-01, 0.0));  // x * 2/pi
   double r = __builtin_fma(-fn, 1.57079632673412561417e+00, x);     // pi/2, first 33 bits
   r = __builtin_fma(-fn, 6.07710050650619224932e-11, r);            // pi/2 - that
   const int n = (int)(ok ? fn : 0.0);
@@ -405,7 +407,7 @@ QC_DEV void sincos_joint(double x, double* __restrict__ sn, double* __restrict__
                                   2.75573137070700676789e-06), -1.98412698298579493134e-04), 8.33333333332248946124e-03), -1.66666666666666324348e-01);
   const double pc = __builtin_fma(z, __builtin_fma(z, __builtin_fma(z, __builtin_fma(z, __builtin_fma(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09),
                                   -2.75573143513906633035e-07), 2.48015872894767294178e-05), -1.38888888888741095749e-03), 4.16666666666666019037e-02);
-  const double s = __builtin_fma(r * z, ps, r);
+  const double s = __builtin_fma(__builtin_fma(r, z, 0.0), ps, r);
   const double c = __builtin_fma(z * z, pc, __builtin_fma(-0.5, z, 1.0));
   const bool swap = n & 1;
   const double ss = swap ? c : s, cc = swap ? s : c;
@@ -469,14 +471,17 @@ QC_DEV void leg_jt_force(const LegGeom& g, const LegTrig& t, const double (&f)[3
   tau[2] = j02 * f[0] + j12 * f[1] + j22 * f[2];
 }
 
-// math/numerics.cpp:23-50
+// math/numerics.cpp:23-50, literally: kept out of FMA contraction (-ffp-contract=on would fuse `angle - q * 2 pi`, which the
+// reference's build does not), so the reference-shaped path rounds as the reference does (tests/test_gpu_device_math.py::test_wraps)
 QC_DEV double normalize_angle_2PI(double angle) {
+#pragma clang fp contract(off)
   const double two_pi = 2.0 * 3.14159265358979323846;
   angle -= floor(angle / two_pi) * two_pi;
   if (angle < 0.0) angle += two_pi;
   return angle;
 }
 QC_DEV double normalize_angle_PI(double rad) {
+#pragma clang fp contract(off)
   const double pi = 3.14159265358979323846, two_pi = 2.0 * pi;
   const double qf = floor((rad + pi) / two_pi);
   rad = (rad + pi) - qf * two_pi;
@@ -615,6 +620,14 @@ QC_DEV void swing_pd(CParams& P, const LegGeom& g, const LegTrig& t, const doubl
   }
 }
 
+// The numerator of the knee cosine d of legInverseKinematics (kinematics.cpp:127), rounded term by term as the reference's build
+// does: an FMA-contracted sum lands a few ulps of d elsewhere, and within a few ulps of d = 1 that decides whether the leg counts
+// as stretched (d clamped to 1, the pseudo-inverse) or not (tests/test_gpu_device_math.py::test_leg_swing_torque).
+QC_DEV double ik_knee_num(double x, double y, double z, double l1, double l2, double l3) {
+#pragma clang fp contract(off)
+  return x * x + y * y + z * z - l1 * l1 - l2 * l2 - l3 * l3;
+}
+
 // Swing-leg torque of one leg, commander_node.cpp:482-504 + joint_controller.cpp:21-39.
 // pb, vb: desired foot position / velocity in the frame the reference hands to IK.
 //
@@ -635,7 +648,7 @@ QC_DEV void leg_swing_torque(CParams& P, const LegGeom& g, const double (&pb)[3]
   const double l1 = fabs(g.L1), l2 = fabs(g.L2), l3 = fabs(g.L3);
   const bool right = g.L1 < 0.0;
   const double x = pb[0] - g.hx, y = pb[1] - g.hy, z = pb[2] - g.hz;
-  const double num = x * x + y * y + z * z - l1 * l1 - l2 * l2 - l3 * l3;
+  const double num = ik_knee_num(x, y, z, l1, l2, l3);
   double sc = y * y + z * z - l1 * l1;
   if (sc < 0.0) sc = 0.0;
   const double rho2 = y * y + z * z;

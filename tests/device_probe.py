@@ -1,0 +1,149 @@
+"""ctypes view of tests/hip/libqc_device_probe.so (tests/hip/device_math_probe.hip): one primitive of qc_device.hpp per
+thread over torch tensors on cuda:0.  Built by __graft_entry__.build_device_probe(); a missing library is an error."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+
+import numpy as np
+import torch
+
+LIB_PATH = os.environ.get("QC_DEVICE_PROBE_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "hip", "libqc_device_probe.so")  # (the env: development builds)
+LAUNCHERS = ("qcp_set_params", "qcp_sincos", "qcp_rsqrt_rcp", "qcp_angle_axis", "qcp_wraps", "qcp_leg", "qcp_pinv3", "qcp_swing_torque",
+             "qcp_swing_pd", "qcp_track_swing", "qcp_ldlt6", "qcp_ldlt12", "qcp_tag", "qcp_group")
+GROUP_VARIANTS = {(2, False): 0, (4, False): 1, (4, True): 2}
+
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise FileNotFoundError(f"{LIB_PATH} is not built (__graft_entry__.build_device_probe())")
+        _lib = C.CDLL(LIB_PATH)
+        for name in LAUNCHERS:
+            getattr(_lib, name).restype = C.c_int
+    return _lib
+
+
+def _dev(a, dtype):
+    return torch.as_tensor(np.ascontiguousarray(a, dtype=dtype)).to("cuda:0")
+
+
+def _empty(shape, dtype=torch.float64):
+    return torch.full(shape, float("nan"), dtype=dtype, device="cuda:0") if dtype.is_floating_point else torch.zeros(shape, dtype=dtype, device="cuda:0")
+
+
+def _call(name, *args):
+    st = C.c_void_p(torch.cuda.current_stream(0).cuda_stream)
+    conv = [C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in args]
+    err = getattr(lib(), name)(*conv, st)
+    if err != 0:
+        raise RuntimeError(f"{name}: hipError_t {err}")
+    torch.cuda.synchronize(0)
+
+
+def _host(t):
+    return t.cpu().numpy()
+
+
+def set_params(hip, links, jc_kff, jc_kp, jc_kd, traj_basis, t_swing, t_stance, swing_height):
+    arrs = [np.ascontiguousarray(a, np.float64) for a in (hip, links, jc_kff, jc_kp, jc_kd, traj_basis)]
+    for a, n in zip(arrs, (12, 12, 3, 3, 3, 21)):
+        assert a.size == n, (a.size, n)
+    ptrs = [a.ctypes.data_as(C.c_void_p) for a in arrs]
+    _call("qcp_set_params", *ptrs, C.c_double(t_swing), C.c_double(t_stance), C.c_double(swing_height))
+
+
+def sincos(x):
+    x = _dev(x, np.float64); n = x.numel(); s, c = _empty((n,)), _empty((n,))
+    _call("qcp_sincos", x, s, c, C.c_int(n))
+    return _host(s), _host(c)
+
+
+def rsqrt_rcp(x):
+    x = _dev(x, np.float64); n = x.numel(); rs, rc = _empty((n,)), _empty((n,))
+    _call("qcp_rsqrt_rcp", x, rs, rc, C.c_int(n))
+    return _host(rs), _host(rc)
+
+
+def angle_axis(m):
+    m = _dev(np.reshape(m, (-1, 9)), np.float64); n = m.shape[0]; out = _empty((n, 3))
+    _call("qcp_angle_axis", m, out, C.c_int(n))
+    return _host(out)
+
+
+def wraps(x):
+    """columns: wrap_2PI, wrap_PI, normalize_angle_2PI, normalize_angle_PI"""
+    x = _dev(x, np.float64); n = x.numel(); out = _empty((n, 4))
+    _call("qcp_wraps", x, out, C.c_int(n))
+    return _host(out)
+
+
+def leg(legs, q, f):
+    """-> trig [n, 6] (s1 c1 s2 c2 s23 c23), FK [n, 3], J^T f by the constant-leg and the LegGeom overloads [n, 3] each"""
+    legs = _dev(legs, np.int32); n = legs.numel()
+    q = _dev(np.reshape(q, (n, 3)), np.float64); f = _dev(np.reshape(f, (n, 3)), np.float64)
+    trig, p, tc, tg = _empty((n, 6)), _empty((n, 3)), _empty((n, 3)), _empty((n, 3))
+    _call("qcp_leg", legs, q, f, trig, p, tc, tg, C.c_int(n))
+    return _host(trig), _host(p), _host(tc), _host(tg)
+
+
+def pinv3(J, v):
+    J = _dev(np.reshape(J, (-1, 9)), np.float64); n = J.shape[0]; v = _dev(np.reshape(v, (n, 3)), np.float64); x = _empty((n, 3))
+    _call("qcp_pinv3", J, v, x, C.c_int(n))
+    return _host(x)
+
+
+def swing_torque(legs, pb, vb, q, qdot):
+    legs = _dev(legs, np.int32); n = legs.numel()
+    a = [_dev(np.reshape(v, (n, 3)), np.float64) for v in (pb, vb, q, qdot)]
+    tau = _empty((n, 3))
+    _call("qcp_swing_torque", legs, *a, tau, C.c_int(n))
+    return _host(tau)
+
+
+def swing_pd(legs, qr, q):
+    """(swing_pd<true>, swing_pd<false>) torques at vb = 0, qdot = 0"""
+    legs = _dev(legs, np.int32); n = legs.numel()
+    qr = _dev(np.reshape(qr, (n, 3)), np.float64); q = _dev(np.reshape(q, (n, 3)), np.float64)
+    tf, tr = _empty((n, 3)), _empty((n, 3))
+    _call("qcp_swing_pd", legs, qr, q, tf, tr, C.c_int(n))
+    return _host(tf), _host(tr)
+
+
+def track_swing(phase, p0, pf):
+    phase = _dev(phase, np.float64); n = phase.numel()
+    p0 = _dev(np.reshape(p0, (n, 3)), np.float64); pf = _dev(np.reshape(pf, (n, 3)), np.float64)
+    pos, vel = _empty((n, 3)), _empty((n, 3))
+    _call("qcp_track_swing", phase, p0, pf, pos, vel, C.c_int(n))
+    return _host(pos), _host(vel)
+
+
+def ldlt(Mpacked, b):
+    """Mpacked [n, N (N + 1) / 2] (row r, column c <= r at r (r + 1) / 2 + c), b [n, N] -> (x, ok)"""
+    b = np.asarray(b, np.float64); n, N = b.shape
+    assert N in (6, 12) and np.shape(Mpacked) == (n, N * (N + 1) // 2)
+    M = _dev(Mpacked, np.float64); x = _dev(b, np.float64); ok = _empty((n,), torch.int32)
+    _call("qcp_ldlt6" if N == 6 else "qcp_ldlt12", M, x, ok, C.c_int(n))
+    return _host(x), _host(ok).astype(bool)
+
+
+def tags(v, code, free_face, slack, nd):
+    """-> tag(v, code), tag_code of that, step_cand(free_face, slack, nd, code)"""
+    v = _dev(v, np.float64); n = v.numel()
+    code = _dev(code, np.int32); ff = _dev(free_face, np.int32); slack = _dev(slack, np.float64); nd = _dev(nd, np.float64)
+    tagged, back, cand = _empty((n,)), _empty((n,), torch.int32), _empty((n,))
+    _call("qcp_tag", v, code, ff, slack, nd, tagged, back, cand, C.c_int(n))
+    return _host(tagged), _host(back), _host(cand)
+
+
+def group(G, S, v, addend, bits):
+    """-> sum, sum_add, min, max [n] and or [n] (uint32) of the lane-group reductions; n a multiple of 64"""
+    v = _dev(v, np.float64); n = v.numel()
+    addend = _dev(addend, np.float64); bits = _dev(np.asarray(bits, np.uint32).view(np.int32), np.int32)
+    out = _empty((n, 5))
+    _call("qcp_group", C.c_int(GROUP_VARIANTS[(G, S)]), v, addend, bits, out, C.c_int(n))
+    o = _host(out)
+    return o[:, 0], o[:, 1], o[:, 2], o[:, 3], o[:, 4].copy().view(np.uint64).astype(np.uint32)

@@ -1,0 +1,218 @@
+// Device-math probe (test infrastructure, not the product): one primitive of quadruped_control_amd/csrc/qc_device.hpp per
+// thread over arrays, so tests/test_gpu_device_math.py can hold each hand-written primitive against a high-precision
+// reference.  The wrappers call the header's functions as they are; nothing here restates them.
+//
+// Every launcher takes device pointers (torch tensors), n and a stream and returns the hipError_t of its launch.  No
+// allocation and no copies: the constants the kinematic primitives read live in a __device__ DevParams that
+// qcp_set_params fills by a one-block kernel, and the kernels read it through QC_PARAMS_HERE as the product does.
+// Built by __graft_entry__.build_device_probe() with the product's own HIP_FLAGS (contraction and inlining as in the library).
+#include "../../quadruped_control_amd/csrc/qc_device.hpp"
+
+#include <cstring>
+
+using namespace qc;
+
+namespace {
+
+constexpr int kBlock = 64;
+__device__ DevParams g_params;
+
+inline dim3 grid_for(int n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
+__device__ __forceinline__ int tid() { return (int)(blockIdx.x * blockDim.x + threadIdx.x); }
+__device__ __forceinline__ CParams& params() { return *QC_PARAMS_HERE(&g_params); }
+
+__global__ void k_set_params(DevParams p) {
+  const double* src = reinterpret_cast<const double*>(&p);
+  double* dst = reinterpret_cast<double*>(&g_params);
+  constexpr int nd = (int)(sizeof(DevParams) / sizeof(double));
+  static_assert(sizeof(DevParams) % sizeof(double) == 0, "DevParams is a whole number of doubles");
+  for (int i = threadIdx.x; i < nd; i += blockDim.x) dst[i] = src[i];
+}
+
+__global__ void k_sincos(const double* x, double* s, double* c, int n) {
+  const int i = tid();
+  if (i < n) sincos_joint(x[i], &s[i], &c[i]);
+}
+__global__ void k_rsqrt_rcp(const double* x, double* rs, double* rc, int n) {
+  const int i = tid();
+  if (i < n) { rs[i] = rsqrt_nr(x[i]); rc[i] = rcp_nr(x[i]); }
+}
+__global__ void k_angle_axis(const double* m, double* out, int n) {
+  const int i = tid();
+  if (i >= n) return;
+  double a[9], o[3];
+  for (int k = 0; k < 9; k++) a[k] = m[9 * i + k];
+  angle_axis_total(a, o);
+  for (int k = 0; k < 3; k++) out[3 * i + k] = o[k];
+}
+// out[4 i ..]: wrap_2PI, wrap_PI, normalize_angle_2PI, normalize_angle_PI
+__global__ void k_wraps(const double* x, double* out, int n) {
+  const int i = tid();
+  if (i >= n) return;
+  out[4 * i] = wrap_2PI(x[i]);
+  out[4 * i + 1] = wrap_PI(x[i]);
+  out[4 * i + 2] = normalize_angle_2PI(x[i]);
+  out[4 * i + 3] = normalize_angle_PI(x[i]);
+}
+// trig[6 i ..]: s1 c1 s2 c2 s23 c23; p = FK; tau = J^T f through both leg_jt_force overloads
+__global__ void k_leg(const int* leg, const double* q, const double* f, double* trig, double* p, double* tau_c, double* tau_g, int n) {
+  const int i = tid();
+  if (i >= n) return;
+  const int l = leg[i];
+  if (l < 0 || l > 3) return;
+  const LegTrig t = leg_trig(q + 3 * i);
+  trig[6 * i] = t.s1; trig[6 * i + 1] = t.c1; trig[6 * i + 2] = t.s2; trig[6 * i + 3] = t.c2; trig[6 * i + 4] = t.s23; trig[6 * i + 5] = t.c23;
+  double pp[3], ff[3] = {f[3 * i], f[3 * i + 1], f[3 * i + 2]}, tc[3], tg[3];
+  leg_fk(params(), l, t, pp);
+  leg_jt_force(params(), l, t, ff, tc);
+  leg_jt_force(leg_geom(params(), l), t, ff, tg);
+  for (int k = 0; k < 3; k++) { p[3 * i + k] = pp[k]; tau_c[3 * i + k] = tc[k]; tau_g[3 * i + k] = tg[k]; }
+}
+__global__ void k_pinv3(const double* J, const double* v, double* x, int n) {
+  const int i = tid();
+  if (i >= n) return;
+  double a[9], b[3] = {v[3 * i], v[3 * i + 1], v[3 * i + 2]}, o[3];
+  for (int k = 0; k < 9; k++) a[k] = J[9 * i + k];
+  pinv3_apply(a, b, o);
+  for (int k = 0; k < 3; k++) x[3 * i + k] = o[k];
+}
+__global__ void k_swing_torque(const int* leg, const double* pb, const double* vb, const double* q, const double* qdot, double* tau, int n) {
+  const int i = tid();
+  if (i >= n) return;
+  const int l = leg[i];
+  if (l < 0 || l > 3) return;
+  const double p[3] = {pb[3 * i], pb[3 * i + 1], pb[3 * i + 2]}, v[3] = {vb[3 * i], vb[3 * i + 1], vb[3 * i + 2]};
+  double t[3];
+  leg_swing_torque(params(), leg_geom(params(), l), p, v, q + 3 * i, qdot + 3 * i, t);
+  for (int k = 0; k < 3; k++) tau[3 * i + k] = t[k];
+}
+// swing_pd<true> and <false> at the reference angles qr (J from leg_trig(qr)), vb = 0, qdot = 0: with kp = 1, kd = kff = 0 in
+// the constants the torques are the wrapped PD errors e of the two forms
+__global__ void k_swing_pd(const int* leg, const double* qr, const double* q, double* tau_fast, double* tau_ref, int n) {
+  const int i = tid();
+  if (i >= n) return;
+  const int l = leg[i];
+  if (l < 0 || l > 3) return;
+  const double r[3] = {qr[3 * i], qr[3 * i + 1], qr[3 * i + 2]}, vb[3] = {0.0, 0.0, 0.0}, qd[3] = {0.0, 0.0, 0.0};
+  const LegGeom g = leg_geom(params(), l);
+  const LegTrig t = leg_trig(r);
+  double tf[3], tr[3];
+  swing_pd<true>(params(), g, t, r, vb, q + 3 * i, qd, tf);
+  swing_pd<false>(params(), g, t, r, vb, q + 3 * i, qd, tr);
+  for (int k = 0; k < 3; k++) { tau_fast[3 * i + k] = tf[k]; tau_ref[3 * i + k] = tr[k]; }
+}
+__global__ void k_track_swing(const double* phase, const double* p0, const double* pf, double* pos, double* vel, int n) {
+  const int i = tid();
+  if (i >= n) return;
+  const double a[3] = {p0[3 * i], p0[3 * i + 1], p0[3 * i + 2]}, b[3] = {pf[3 * i], pf[3 * i + 1], pf[3 * i + 2]};
+  double ps[3], vl[3];
+  track_swing(params(), phase[i], a, b, ps, vl);
+  for (int k = 0; k < 3; k++) { pos[3 * i + k] = ps[k]; vel[3 * i + k] = vl[k]; }
+}
+// M: packed lower triangles (index r (r + 1) / 2 + c), x: right-hand sides in, solutions out
+template <int N>
+__global__ void k_ldlt(const double* M, double* x, int* ok, int n) {
+  const int i = tid();
+  if (i >= n) return;
+  constexpr int T = N * (N + 1) / 2;
+  double a[T], b[N];
+  for (int k = 0; k < T; k++) a[k] = M[(long)T * i + k];
+  for (int k = 0; k < N; k++) b[k] = x[(long)N * i + k];
+  ok[i] = ldlt_solve<N>(a, b) ? 1 : 0;
+  for (int k = 0; k < N; k++) x[(long)N * i + k] = b[k];
+}
+__global__ void k_tag(const double* v, const int* code, const int* free_face, const double* slack, const double* nd, double* tagged,
+                      int* code_back, double* cand, int n) {
+  const int i = tid();
+  if (i >= n) return;
+  const int c = code[i] & 31;
+  tagged[i] = tag(v[i], c);
+  code_back[i] = tag_code(tagged[i]);
+  cand[i] = step_cand(free_face[i] != 0, slack[i], nd[i], c);
+}
+// One value per lane of whole waves (n a multiple of 64, every lane active: the DPP / permlane / MFMA reductions read
+// their neighbours).  out[5 i ..]: group_sum, group_sum_add(v, addend[i]), group_min, group_max, and the bits of group_or.
+template <int G, bool S>
+__global__ void k_group(const double* v, const double* addend, const int* bits, double* out, int n) {
+  const int i = tid();
+  const bool in = i < n;  // (n is a multiple of the block: always true, kept so a short array cannot be overrun)
+  const double x = in ? v[i] : 0.0, a = in ? addend[i] : 0.0;
+  const int b = in ? bits[i] : 0;
+  const double s = group_sum<G, S>(x);
+  const double sa = group_sum_add<G, S>(x, a);
+  const double mn = group_min<G, S>(x);
+  const double mx = group_max<G, S>(x);
+  const int o = group_or<G, S>(b);
+  if (in) {
+    out[5 * i] = s; out[5 * i + 1] = sa; out[5 * i + 2] = mn; out[5 * i + 3] = mx;
+    out[5 * i + 4] = __longlong_as_double((long long)(unsigned)o);
+  }
+}
+
+template <class K, class... A>
+hipError_t launch(K kernel, int n, hipStream_t st, A... args) {
+  if (n < 0) return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(kernel, grid_for(n), dim3(kBlock), 0, st, args..., n);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" {
+
+// The constants of the kinematic primitives, from flat arrays; every other field of DevParams stays zero.
+hipError_t qcp_set_params(const double* hip, const double* links, const double* jc_kff, const double* jc_kp, const double* jc_kd,
+                          const double* traj_basis, double t_swing, double t_stance, double swing_height, hipStream_t st) {
+  DevParams p;
+  std::memset(&p, 0, sizeof(p));
+  std::memcpy(p.hip, hip, sizeof(p.hip));
+  std::memcpy(p.links, links, sizeof(p.links));
+  std::memcpy(p.jc_kff, jc_kff, sizeof(p.jc_kff));
+  std::memcpy(p.jc_kp, jc_kp, sizeof(p.jc_kp));
+  std::memcpy(p.jc_kd, jc_kd, sizeof(p.jc_kd));
+  std::memcpy(p.traj_basis, traj_basis, sizeof(p.traj_basis));
+  p.t_swing = t_swing;
+  p.t_stance = t_stance;
+  p.swing_height = swing_height;
+  hipLaunchKernelGGL(k_set_params, dim3(1), dim3(kBlock), 0, st, p);
+  return hipGetLastError();
+}
+
+hipError_t qcp_sincos(const double* x, double* s, double* c, int n, hipStream_t st) { return launch(k_sincos, n, st, x, s, c); }
+hipError_t qcp_rsqrt_rcp(const double* x, double* rs, double* rc, int n, hipStream_t st) { return launch(k_rsqrt_rcp, n, st, x, rs, rc); }
+hipError_t qcp_angle_axis(const double* m, double* out, int n, hipStream_t st) { return launch(k_angle_axis, n, st, m, out); }
+hipError_t qcp_wraps(const double* x, double* out, int n, hipStream_t st) { return launch(k_wraps, n, st, x, out); }
+hipError_t qcp_leg(const int* leg, const double* q, const double* f, double* trig, double* p, double* tau_c, double* tau_g, int n,
+                   hipStream_t st) {
+  return launch(k_leg, n, st, leg, q, f, trig, p, tau_c, tau_g);
+}
+hipError_t qcp_pinv3(const double* J, const double* v, double* x, int n, hipStream_t st) { return launch(k_pinv3, n, st, J, v, x); }
+hipError_t qcp_swing_torque(const int* leg, const double* pb, const double* vb, const double* q, const double* qdot, double* tau, int n,
+                            hipStream_t st) {
+  return launch(k_swing_torque, n, st, leg, pb, vb, q, qdot, tau);
+}
+hipError_t qcp_swing_pd(const int* leg, const double* qr, const double* q, double* tau_fast, double* tau_ref, int n, hipStream_t st) {
+  return launch(k_swing_pd, n, st, leg, qr, q, tau_fast, tau_ref);
+}
+hipError_t qcp_track_swing(const double* phase, const double* p0, const double* pf, double* pos, double* vel, int n, hipStream_t st) {
+  return launch(k_track_swing, n, st, phase, p0, pf, pos, vel);
+}
+hipError_t qcp_ldlt6(const double* M, double* x, int* ok, int n, hipStream_t st) { return launch(k_ldlt<6>, n, st, M, x, ok); }
+hipError_t qcp_ldlt12(const double* M, double* x, int* ok, int n, hipStream_t st) { return launch(k_ldlt<12>, n, st, M, x, ok); }
+hipError_t qcp_tag(const double* v, const int* code, const int* free_face, const double* slack, const double* nd, double* tagged, int* code_back,
+                   double* cand, int n, hipStream_t st) {
+  return launch(k_tag, n, st, v, code, free_face, slack, nd, tagged, code_back, cand);
+}
+// variant 0: (G, S) = (2, false), 1: (4, false), 2: (4, true)
+hipError_t qcp_group(int variant, const double* v, const double* addend, const int* bits, double* out, int n, hipStream_t st) {
+  if (n % kBlock != 0) return hipErrorInvalidValue;
+  switch (variant) {
+    case 0: return launch(k_group<2, false>, n, st, v, addend, bits, out);
+    case 1: return launch(k_group<4, false>, n, st, v, addend, bits, out);
+    case 2: return launch(k_group<4, true>, n, st, v, addend, bits, out);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+}  // extern "C"

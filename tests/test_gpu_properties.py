@@ -1068,3 +1068,49 @@ def test_paired_waves_kernel_full_size(q):
     assert int((ow["status"] != 0).sum()) == 0
     assert torch.equal(ow["iterations"], rw["iterations"])  # no race in a warm tail: the same walk robot by robot
     assert float((ow["grf_body"] - rw["grf_body"]).abs().max()) < 1e-9
+
+
+def test_fused_tick_against_the_reference_notebook(q):
+    """The notebook's printed kinematics (tests/golden/kinematics_notebook.json) through the fused tick kernels: every robot has
+    joint_q = the notebook's q on all four legs.  The fused tick's grf_body equals control_batch fed feet = FK(q) to 1e-8
+    relative, with FK(q) the device-math probe's leg_fk, whose RL / RR values are the notebook's (to 6e-9, the 8 printed
+    digits).  joint_tau equals clip(J_notebook^T grf_body) to half a unit of the 8th decimal per printed Jacobian entry,
+    5e-9 sum_i |f_i| per leg (a flat 6e-9 max|grf| is exceeded by the printing alone: 7.3e-9 with the oracle's own forces)."""
+    import json
+    import os
+
+    import __graft_entry__ as g
+    from quadruped_control_amd import workloads as W
+    from tests import device_math_reference as R
+    from tests import device_probe as D
+
+    g.build_device_probe()
+    _, basis = R.sextic_basis_mp()
+    D.set_params(R.HIP, R.LINKS, R.JC_KFF, R.JC_KP, R.JC_KD, basis, 0.18, 0.8, 0.08)
+    with open(os.path.join(os.path.dirname(__file__), "golden", "kinematics_notebook.json")) as fh:
+        nb = json.load(fh)
+    qn = np.array(nb["q"])
+    _, fk, _, _ = D.leg(np.arange(4), np.tile(qn, (4, 1)), np.zeros((4, 3)))
+    for leg, name in enumerate(R.LEG_NAMES):
+        if name in nb["fk"]:
+            np.testing.assert_allclose(fk[leg], nb["fk"][name], atol=6e-9)
+    P = q.cheetah_params(0.6)
+    ctl = q.BalanceController.from_params(P)
+    for n in (1000, 40000):  # four lanes per robot; one lane per robot
+        b = {k: v for k, v in W.config3(n).items() if k != "feet"}
+        b["joint_q"] = np.ascontiguousarray(np.tile(qn, (n, 4)))
+        o = ctl.control_batch_host(b, want_torques=True)
+        assert (o["status"] == 0).all()
+        b2 = {k: v for k, v in b.items() if k != "joint_q"}
+        b2["feet"] = np.ascontiguousarray(np.tile(fk.reshape(12), (n, 1)))
+        o2 = ctl.control_batch_host(b2)
+        scale = np.maximum(1.0, np.abs(o2["grf_body"]).max(axis=1, keepdims=True))
+        assert np.max(np.abs(o["grf_body"] - o2["grf_body"]) / scale) < 1e-8
+        grf = o["grf_body"].reshape(n, 4, 3)
+        for leg, name in enumerate(R.LEG_NAMES):
+            J = np.array(nb["jacobian"][name])
+            f = grf[:, leg]
+            st = b["stance"][:, leg].astype(bool)[:, None]
+            want = np.where(st, np.clip(f @ J, -20.0, 20.0), 0.0)  # (J^T f)_k = sum_i J_ik f_i
+            bar = 5e-9 * np.abs(f).sum(axis=1, keepdims=True) + 1e-12
+            assert (np.abs(o["joint_tau"][:, 3 * leg:3 * leg + 3] - want) <= bar).all(), name
