@@ -225,12 +225,12 @@ int qc_check_abi(int abi_version, size_t sizeof_params, size_t sizeof_batch_in, 
 #define QC_CHECK_ABI() qc_check_abi(QC_ABI_VERSION, sizeof(qc_params), sizeof(qc_batch_in), sizeof(qc_batch_out))
 
 /* ABI v4.  Which kernel instantiation a batch of n robots would run on (kin = joint_q given, warm = warm-start
- * words given): lanes per robot, kernel mode (0 persistent waves with lane refill, 1 one fill per wave, 2 one fill
+ * words given): lanes per robot, kernel mode (1 one fill per wave, 2 one fill
  * and one wave per SIMD with register-resident constants; batches that leave SIMDs idle even so race 2 or 4 pivoting
  * strategies per robot there, `strategies`; 3 paired waves - two one-lane waves per workgroup, the last to arrive
  * finishes both waves' stragglers: 6x6 forms from 524 288 robots on), form (0 uniform 6x6, 1 general 6x6, 2 dense 12x12),
  * robots per wave, grid size, and the workgroups of that kernel the device holds at once (the occupancy query the
- * heuristics use).  (Mode 0 is reported by development builds only: the default library runs every form as one-fill workgroups.) */
+ * heuristics use). */
 typedef struct qc_launch_info {
   int32_t lanes_per_robot;
   int32_t mode;
@@ -245,10 +245,9 @@ int qc_query_launch(qc_handle* h, size_t n, int kin, int warm, qc_launch_info* o
 
 /* ABI v4.  Development / test interface: explicit overrides of the launch heuristics and solver constants (the
  * library reads NO environment variables).  Keys: "group" (lanes per robot: 0 = heuristic, 1, 2, 4), "one_fill"
- * (-1 heuristic, 0 persistent waves, 1 one-fill workgroups; the persistent kernels exist only in development builds,
- * -DQC_PERSISTENT_6X6=1: elsewhere a launch with 0 fails with QC_ERR_INVALID), "chunk" (robots per wave, 0 = heuristic;
- * beyond one fill only where persistent kernels exist - QC_ERR_INVALID at launch otherwise),
- * "wave_slots" (resident workgroups assumed, 0 = occupancy query), "refill_t", "rounds_cold", "rounds_warm",
+ * (-1 heuristic or 1: every launch runs one-fill workgroups; 0 fails with QC_ERR_INVALID), "chunk" (robots per wave,
+ * 0 = heuristic; beyond one fill - 64 / lanes per robot - QC_ERR_INVALID at launch),
+ * "wave_slots" (resident workgroups assumed, 0 = occupancy query),
  * "race" (-1 heuristic; 0 or 1: one strategy per robot; 2, 4: at most that many racing in the 4-lane one-fill kernels.  With the
  * race on - the default for cold batches - a wave forks its last running robots onto idle lanes with a second drop rule, so a robot's
  * `iterations` (and, under a small max_iter, QC_SOLVED vs QC_MAX_ITER) depend on which robots share its wave, i.e. on the batch

@@ -31,18 +31,19 @@ namespace qc {
 // The QP is strictly convex (W > 0), so the KKT point is THE minimiser qpOASES
 // returns in the reference (BC.cpp:177-210).
 //
-// A wavefront owns a contiguous chunk of robots and walks through it: all
-// lanes execute the same working-set recalculation in lockstep (straight-line,
-// select-based code, no per-lane branches); a group whose robot has converged
-// pushes the result to the wave's output stock and, once `refill_t` lanes are
-// free, free groups pull the next robots from the wave's input stock.  This
-// keeps the lanes busy although robots need between 1 and ~20 recalculations.
+// A wavefront (one workgroup) fills once: its chunk of at most 64/G robots is
+// assembled into the wave's input stock, every lane executes the same
+// working-set recalculation in lockstep (straight-line, select-based code, no
+// per-lane branches) until the wave's slowest robot has converged, the results
+// go to the wave's output stock and a dense pass stores them.  Robots need
+// between 1 and ~20 recalculations; the stragglers of one- and two-lane waves
+// finish four lanes per robot (finish_on_four_lanes), and the hardware
+// scheduler refills the chip with the next workgroup.
 //
 // LDS stock planes (see "Dense phases around the divergent solve" below).
 // SP = plane stride in doubles = slots + 1 (odd), so that the lanes of one group (same
 // slot, planes 3*FPL apart) fall into different banks; the dense side
-// (plane[f][lane]) is conflict-free either way.  The stock is sized per kernel mode: a persistent wave
-// (MODE 0) restocks 64 robots at a time, a one-fill wave (MODE 1/2) only ever holds its 64/G robots, so its
+// (plane[f][lane]) is conflict-free either way.  A wave only ever holds its 64/G robots, so its
 // stock is 64/G slots - 9.2 KB instead of 18 KB at G = 2, which is what lets more than two workgroups per
 // SIMD share the CU's 160 KB (the 92-VGPR one-fill kernels are register-good for five).
 // "this robot still has its polish release" (Lane::iterate): bit 9 of the stance word in the hand-over records of a RUNNING robot
@@ -52,7 +53,7 @@ constexpr uint32_t QC_POLISH_ONE = 1u << 9;
 enum { IN_B = 0, IN_R = 6, IN_FLAGS = 18, IN_IDX = 19, IN_PLANES = 20,
        OUT_F = 0, OUT_STAT = 12, OUT_WORD = 13, OUT_IDX = 14, OUT_PLANES = 15,
        STOCK_PLANES = IN_PLANES + OUT_PLANES };
-constexpr int stock_slots(int G, int MODE) { return MODE == 0 ? 64 : 64 / G; }
+constexpr int stock_slots(int G) { return 64 / G; }
 constexpr int TASK_DOUBLES = 32;  // 256 one-byte (robot, leg) tasks of the torque pass, behind the planes
 constexpr int stock_doubles(int slots) { return ((STOCK_PLANES * (slots + 1) + TASK_DOUBLES + 63) / 64) * 64; }
 // QPARK - the one-lane one-fill joint_q kernels of the 6x6 forms (round 6).  The torque pass needs every robot's twelve joint angles a
@@ -85,7 +86,7 @@ struct Lane {
   int foot0;        // first foot of this lane
   int status, iters;
   double tol_s;  // relative multiplier tolerance of this robot (tol_d x Eqp::kTolScale), signed: + while it still has its polish release, - after
-  bool have_f;
+  bool have_f;  // (read only by a MIXED recalculation without RACE, which no kernel runs; yet dropping its stores reshuffles the registers of most kernels)
   int nclamp = 1;        // RACE: recalculations that clamp instead of stepping
   bool drop_all = false;  // RACE: drop every negative multiplier after a full step
 
@@ -145,10 +146,11 @@ struct Lane {
   }
 
   // one working-set recalculation; returns true when the robot is finished.
-  // PHASE: MIXED = fresh and running robots share the wave (persistent waves with lane refill: one straight-line
-  // body, the clamp of the fresh ones behind a wave-uniform branch); FIRST / STEADY = the one-fill modes, where
-  // every robot of the wave is fresh in the first recalculation and none afterwards, so the first is peeled and
-  // the steady body carries no clamp, no fresh/running selects and no ratio test for nothing.
+  // PHASE: FIRST / STEADY - every robot of a wave is fresh in its first recalculation and none afterwards, so the
+  // first is peeled and the steady body carries no clamp, no fresh/running selects and no ratio test for nothing.
+  // MIXED: fresh and running robots share the wave - the racing lanes, whose strategy takes its first `nclamp`
+  // recalculations as clamp steps (without RACE: until `have_f` is set) - in one straight-line body, the clamp
+  // behind a wave-uniform branch.
   // `live`: the lane's robot is still running.  The strided 4-lane kernels iterate every lane through a
   // wave-uniform loop (MFMA sums read all 64 lanes), finished robots included: a finished robot recomputes
   // the same f^ from the same working set (idempotent), so only what must not move once it has finished -
@@ -168,7 +170,7 @@ struct Lane {
   enum { MIXED = 0, FIRST = 1, STEADY = 2 };
   // `empty_set` (wave-uniform): every robot of the wave still has the EMPTY working set - the first recalculation of a cold
   // fill.  With no active face there is no multiplier to test (every candidate is +BIG), so the test is skipped.
-  template <int PHASE = MIXED, class PT>
+  template <int PHASE, class PT>
   QC_DEV bool iterate(const PT& P, Eqp& eqp, const bool live = true, const bool empty_set = false) {
     double fh[3 * FPL], g[3 * FPL];
     iters += live ? 1 : 0;
@@ -176,8 +178,8 @@ struct Lane {
     // RACE, MIXED: the lane's strategy decides (its first `nclamp` recalculations are clamp steps)
     const bool fresh = PHASE == FIRST ? true : (PHASE == STEADY ? false : (RACE ? iters <= nclamp : !have_f));
     have_f = true;
-    // (a) fresh robot: clamp f^ into the frusta.  In MIXED waves fresh robots exist only right
-    // after a (re)fill, so the whole block sits behind a wave-uniform branch.
+    // (a) fresh robot: clamp f^ into the frusta.  In MIXED recalculations the whole block sits behind a
+    // wave-uniform branch: once every strategy is past its clamp steps nobody takes it.
     double fc[3 * FPL];
     Cube<FPL> Cc;
     bool changed = false;
@@ -1029,10 +1031,9 @@ QC_DEV int repack_read(const DevParams* __restrict__ Pg, Lane4X& L4, Eqp4X& eqp4
 template <bool KIN, bool UNIFORM, int SP, bool HOLD = false, class LaneG>
 QC_DEV void finish_on_four_lanes(const DevParams* __restrict__ Pg, const LaneG& L, bool busy, unsigned long long bm, int slot, int member, int lane,
                                  double* __restrict__ sin, double* __restrict__ sout, const bool cold) {
-  using Eqp4 = EqpDiagW<UNIFORM, 4, !QC_NO_STRIDED>;
+  using Eqp4 = EqpDiagW<UNIFORM, 4>;
   using Lane4 = Lane<Eqp4, KIN>;
   using LaneR = Lane<Eqp4, KIN, true>;  // with a per-lane drop rule
-  constexpr bool STR4 = Eqp4::kStrided;
   constexpr int GS = LaneG::G;  // lanes per robot of the layout being left
   constexpr int RS = REPACK_RS;
   const int nb = __builtin_popcountll(bm) / GS;  // running robots
@@ -1043,10 +1044,10 @@ QC_DEV void finish_on_four_lanes(const DevParams* __restrict__ Pg, const LaneG& 
   __syncthreads();  // nobody reads the input stock any more
   if (busy) repack_write(L, sin + rank2 * RS, slot, member);
   __syncthreads();
-  const int g4 = lane_group<4, STR4>(lane), j4 = lane_member<4, STR4>(lane);
+  const int g4 = lane_group<4, true>(lane), j4 = lane_member<4, true>(lane);
   // (a warm-started robot that is not done after its first recalculation is a face or two away: nothing to race for;
   // measured neutral to +0.5 us on config 4's tick, tools/tail_race_scan.py)
-  const bool race = STR4 && cold && QC_PARAMS_HERE(Pg)->tail_race != 0;
+  const bool race = cold && QC_PARAMS_HERE(Pg)->tail_race != 0;
   int nrun = nb;  // robots the race stage starts with (the first re-pack's records if the classic stage is skipped)
   QC_CLK_TAIL_LOOP();
   Lane4 L4;
@@ -1056,9 +1057,9 @@ QC_DEV void finish_on_four_lanes(const DevParams* __restrict__ Pg, const LaneG& 
     Eqp4 eqp4(nullptr);
     bool busy4 = g4 < nb;
     // groups beyond the running robots shadow record 0: the strided layout keeps every lane in the loop (MFMA)
-    const int slot4 = repack_read(Pg, L4, eqp4, sin + (busy4 || !STR4 ? g4 : 0) * RS, j4);
+    const int slot4 = repack_read(Pg, L4, eqp4, sin + (busy4 ? g4 : 0) * RS, j4);
     const int stop = race ? 8 : 0;
-    if constexpr (STR4 && UNIFORM) {
+    if constexpr (UNIFORM) {
       // the tail has the registers to keep the recalculation's constants resident, as the mode-2 kernel does
       UConst uc = load_uconst(*QC_PARAMS_HERE(Pg));
       while (__builtin_popcountll(__builtin_amdgcn_ballot_w64(busy4) & 0xFFFFull) > stop) {
@@ -1067,14 +1068,12 @@ QC_DEV void finish_on_four_lanes(const DevParams* __restrict__ Pg, const LaneG& 
         const bool done = L4.template iterate<Lane4::STEADY>(uc, eqp4, busy4);
         busy4 = busy4 & !done;
       }
-    } else if constexpr (STR4) {
+    } else {
       while (__builtin_popcountll(__builtin_amdgcn_ballot_w64(busy4) & 0xFFFFull) > stop) {
         QC_CLK(7, 2);
         const bool done = L4.template iterate<Lane4::STEADY>(*QC_PARAMS_HERE(Pg), eqp4, busy4);
         busy4 = busy4 & !done;
       }
-    } else {
-      while (busy4) busy4 = !L4.template iterate<Lane4::STEADY>(*QC_PARAMS_HERE(Pg), eqp4);
     }
     if constexpr (HOLD) {
       held = g4 < nb && !busy4;
@@ -1098,42 +1097,39 @@ QC_DEV void finish_on_four_lanes(const DevParams* __restrict__ Pg, const LaneG& 
     if (busy4) repack_write(L4, sin + rank * RS, slot4, j4);
     __syncthreads();
   }
-  if constexpr (STR4) {
-    LaneR LR;
-    Eqp4 eqpR(nullptr);
-    const int r = g4 & 7, sid = g4 >> 3;  // robot, strategy of this group
-    bool busyR = r < nrun;
-    const int slotR = repack_read(Pg, LR, eqpR, sin + (busyR ? r : 0) * RS, j4);
-    LR.drop_all = sid == 1;
-    unsigned solved_mask = 0;  // strategies of this lane's robot that have reached the KKT point
-    auto after = [&](bool done) {
-      const int mine = (busyR & done & (LR.status == QC_SOLVED)) ? (1 << sid) : 0;
-      const int m = mine | __builtin_amdgcn_update_dpp(0, mine, 0x120 + 8, 0xF, 0xF, true);  // row_ror 8: the partner group
-      solved_mask |= (unsigned)m;
-      busyR = busyR & !done & (solved_mask == 0);
-    };
-    if constexpr (UNIFORM) {
-      UConst uc = load_uconst(*QC_PARAMS_HERE(Pg));
-      while (__builtin_amdgcn_ballot_w64(busyR) != 0) {
-        QC_CLK(7, 2);
-        pin_uconst(uc);
-        after(LR.template iterate<LaneR::STEADY>(uc, eqpR, busyR));
-      }
-    } else {
-      while (__builtin_amdgcn_ballot_w64(busyR) != 0) {
-        QC_CLK(7, 2);
-        after(LR.template iterate<LaneR::STEADY>(*QC_PARAMS_HERE(Pg), eqpR, busyR));
-      }
+  LaneR LR;
+  Eqp4 eqpR(nullptr);
+  const int r = g4 & 7, sid = g4 >> 3;  // robot, strategy of this group
+  bool busyR = r < nrun;
+  const int slotR = repack_read(Pg, LR, eqpR, sin + (busyR ? r : 0) * RS, j4);
+  LR.drop_all = sid == 1;
+  unsigned solved_mask = 0;  // strategies of this lane's robot that have reached the KKT point
+  auto after = [&](bool done) {
+    const int mine = (busyR & done & (LR.status == QC_SOLVED)) ? (1 << sid) : 0;
+    const int m = mine | __builtin_amdgcn_update_dpp(0, mine, 0x120 + 8, 0xF, 0xF, true);  // row_ror 8: the partner group
+    solved_mask |= (unsigned)m;
+    busyR = busyR & !done & (solved_mask == 0);
+  };
+  if constexpr (UNIFORM) {
+    UConst uc = load_uconst(*QC_PARAMS_HERE(Pg));
+    while (__builtin_amdgcn_ballot_w64(busyR) != 0) {
+      QC_CLK(7, 2);
+      pin_uconst(uc);
+      after(LR.template iterate<LaneR::STEADY>(uc, eqpR, busyR));
     }
-    QC_CLK_TAIL_END();
-    // the winner - the lower-numbered strategy if both got there in the same recalculation, strategy 0 with whatever
-    // status it has if none did - parks the result
-    const int win = solved_mask ? __builtin_ctz(solved_mask) : 0;
-    if constexpr (HOLD) __syncthreads();  // (the race stage's records have been read by every group)
-    if (r < nrun && sid == win) LR.template push_result<SP>(sout, slotR);
+  } else {
+    while (__builtin_amdgcn_ballot_w64(busyR) != 0) {
+      QC_CLK(7, 2);
+      after(LR.template iterate<LaneR::STEADY>(*QC_PARAMS_HERE(Pg), eqpR, busyR));
+    }
   }
+  QC_CLK_TAIL_END();
+  // the winner - the lower-numbered strategy if both got there in the same recalculation, strategy 0 with whatever
+  // status it has if none did - parks the result
+  const int win = solved_mask ? __builtin_ctz(solved_mask) : 0;
+  if constexpr (HOLD) __syncthreads();  // (the race stage's records have been read by every group)
+  if (r < nrun && sid == win) LR.template push_result<SP>(sout, slotR);
   if constexpr (HOLD) {
-    if constexpr (!STR4) __syncthreads();
     if (held) L4.template push_result<SP>(sout, slot_held);
   }
 }
@@ -1150,8 +1146,8 @@ QC_DEV int clamp_steps_for(CParams& P, const uint32_t* warm) {
   return tuned > 0 ? tuned : ((warm != nullptr || G == 4) ? 1 : 5);
 }
 
-// MODE 0: persistent waves (chunks of many fills, lane refill).  MODE 1: the launch gives every wave at most one
-// fill (chunk <= 64 / G).  MODE 2: one fill and the SIMD to itself, recalculation constants resident in VGPRs.
+// MODE 1: the launch gives every wave one fill (chunk <= 64 / G).  MODE 2: one fill and the SIMD to itself,
+// recalculation constants resident in VGPRs.
 // RACE (strided 4-lane one-fill kernels): strategies racing per robot, 1, 2 or 4; a wave then holds 16 / RACE robots (see Lane).
 
 // The kernel's argument block as the launch lays it out (kernarg segment), for re-deriving BatchIn / BatchOut AT THEIR USE in the
@@ -1166,7 +1162,6 @@ struct BalanceKernelArgs {
   const uint32_t* warm;
   BatchOut out;
   long chunk;
-  int refill_t;
 };
 template <class T>
 QC_DEV const T& kernarg_here(unsigned off) {
@@ -1176,11 +1171,11 @@ QC_DEV const T& kernarg_here(unsigned off) {
   return *(const T*)(const __attribute__((address_space(4))) T*)p;
 }
 
-template <class Eqp, bool KIN, int MIN_WAVES_PER_SIMD, int MODE = 0, int RACE = 1>
+template <class Eqp, bool KIN, int MIN_WAVES_PER_SIMD, int MODE, int RACE = 1>
 __global__ __launch_bounds__(64, MIN_WAVES_PER_SIMD) void balance_kernel(const DevParams* __restrict__ Pg, const long n, const BatchIn in_k,
-                                                                         const uint32_t* __restrict__ warm, const BatchOut out_k, const long chunk,
-                                                                         const int refill_t) {
-  static_assert(RACE == 1 || (MODE != 0 && Eqp::kStrided && Eqp::G == 4), "racing strategies exist for the strided one-fill kernels");
+                                                                         const uint32_t* __restrict__ warm, const BatchOut out_k, const long chunk) {
+  static_assert(MODE == 1 || MODE == 2, "one fill per wave (MODE 1), and the SIMD to itself (MODE 2)");
+  static_assert(RACE == 1 || (Eqp::kStrided && Eqp::G == 4), "racing strategies exist for the strided 4-lane kernels");
   constexpr int G = Eqp::G;
   // (KIN: re-read from the kernarg segment at every use, see BalanceKernelArgs; the QP-only kernels hold 14 pointers and keep them,
   // and so does the one-wave-per-SIMD kernel of chain-bound batches - a lone wave waits out every scalar-load round trip: the fused
@@ -1195,13 +1190,13 @@ __global__ __launch_bounds__(64, MIN_WAVES_PER_SIMD) void balance_kernel(const D
     else return out_k;
   };
   extern __shared__ __attribute__((aligned(16))) double qc_lds[];  // [stock planes][64] (+ the dense form's 78 Hessian planes)
-  constexpr int SP = stock_slots(G, MODE) + 1;  // plane stride of this mode's stock
+  constexpr int SP = stock_slots(G) + 1;  // plane stride of the stock
   // One-lane dense form as one-fill workgroups (round 5): the 78 Hessian planes (39 936 B) ARE the workgroup's LDS - four
   // workgroups per CU, one per SIMD.  With the stock in front of them (58.3 KB) a CU held two, i.e. every other SIMD idled
   // behind the 512-register kernel.  The input stock is not used on this path (one lane assembles and solves its robot),
   // Rwb is read again for the output transform instead of parked, and the output stock aliases the first Hessian planes
   // once every robot of the wave is finished.
-  constexpr bool HESS_ONLY = Eqp::kHessianInLds && MODE != 0;
+  constexpr bool HESS_ONLY = Eqp::kHessianInLds;
   static_assert(!HESS_ONLY || (OUT_PLANES * SP + TASK_DOUBLES <= 78 * 64), "the output stock fits the Hessian planes it aliases");
   // (see QPARK_* above: Rwb and the joint angles parked, the re-pack records under the output stock)
   constexpr bool QPARK = KIN && G == 1 && MODE == 1 && !Eqp::kHessianInLds;
@@ -1217,7 +1212,6 @@ __global__ __launch_bounds__(64, MIN_WAVES_PER_SIMD) void balance_kernel(const D
   // the batch to an XCD removes the same re-fetches but costs config 2 0.2 us, profiles/r05_ab_xcd_map.log: the spreading of
   // neighbouring groups over the XCDs is worth keeping.)  Waves of 16 robots or more share no line: identity.
   unsigned chunk_id = blockIdx.x;
-#ifndef QC_NO_XCD_MAP  // (development: -DQC_NO_XCD_MAP compiles the identity map for A/B runs)
   if constexpr (RACE > 1) {  // 16 / RACE robots per wave: RACE waves per aligned group (compile-time powers of two: shifts and masks only -
     // with run-time divisions the map cost the wave's first 0.1 us more than it saved)
     constexpr unsigned gw = (unsigned)RACE, super = 8u * gw;
@@ -1227,421 +1221,352 @@ __global__ __launch_bounds__(64, MIN_WAVES_PER_SIMD) void balance_kernel(const D
       chunk_id = (slot / gw) * super + xcd * gw + (slot % gw);
     }
   }
-#endif
   long cursor = (long)chunk_id * chunk;  // wave-uniform: next robot of this wave's chunk to assemble
   const long end = cursor + chunk < n ? cursor + chunk : n;
   const int lane = threadIdx.x;
-  constexpr bool STR = Eqp::kStrided;  // lane layout of a group (one-fill modes only)
-  static_assert(!STR || MODE != 0, "the refill bookkeeping of the persistent mode assumes adjacent lanes");
+  constexpr bool STR = Eqp::kStrided;  // lane layout of a group
   const int member = lane_member<G, STR>(lane);
-  int stock_n = 0, stock_next = 0;  // input stock: slots [stock_next, stock_n) hold assembled robots
-  int out_n = 0;                    // output stock: slots [0, out_n) hold finished results
+  int stock_n = 0;  // input stock: slots [0, stock_n) hold assembled robots
   // one-lane dense form, QP only: stragglers fork into idle lanes with the other drop rule.  (Not the joint_q kernel: with the results
   // parked in the lanes' own dead Hessian columns for the torque pass - tools/experiments/r06_dense_kin_twin.patch - the race bought its
   // tick nothing, 151.4 us with it, 151.4 with race = 0, 147.8 without the machinery: profiles/r06_dense_tick.log.  That kernel's time
   // is its fill and flush at one wave per SIMD, not its stragglers.)
-  constexpr bool TWIN = Eqp::kHessianInLds && MODE != 0 && !KIN;
+  constexpr bool TWIN = Eqp::kHessianInLds && !KIN;
   Lane<Eqp, KIN, (RACE > 1) || TWIN> L;
   L.idx = -1;
   L.foot0 = member * (4 / G);
-  Eqp eqp(qc_lds + (HESS_ONLY ? 0 : stock_doubles(stock_slots(G, MODE))) + lane);
+  Eqp eqp(qc_lds + (HESS_ONLY ? 0 : stock_doubles(stock_slots(G))) + lane);
   bool busy = false;  // group holds an unfinished robot
   QC_CLK_BEGIN();
-  if constexpr (MODE != 0) {
-    // One fill per wave: the persistent-wave machinery (refill, stock cursors, a result push after every
-    // recalculation) is dead weight on the serial chain that bounds such a batch.  One fill, a divergent solve
-    // loop, one push, one flush.
-    constexpr bool RESIDENT = MODE == 2;
-    if (cursor >= end) return;
-    UConst uc;  // RESIDENT: the recalculation's constants live in VGPRs (no scalar load + wait per recalculation)
-    if constexpr (RESIDENT) uc = load_uconst(*QC_PARAMS_HERE(Pg));
-    // One lane per robot: the lane that assembles a robot is the lane that solves it, so the robot goes straight from the
-    // assembly into the solver's registers - no input stock, no barrier - and its Rwb is parked in the first nine planes of
-    // the (otherwise idle) input-stock area for the output transform; the planes behind them serve as the re-pack area of the tail.
-    constexpr bool DIRECT = G == 1;
-    constexpr bool RPARK = DIRECT && !HESS_ONLY;  // Rwb parked in LDS for the output transform
-    constexpr int R_PLANES = RPARK ? 9 : 0;
-    static_assert(!DIRECT || QPARK || (R_PLANES * SP + 16 * REPACK_RS <= IN_PLANES * SP), "Rwb planes + re-pack records fit the input-stock area");
-    if constexpr (DIRECT) {
-      const long left = end - cursor;
-      stock_n = left < 64 ? (int)left : 64;
-      if (lane < stock_n) {
-        // Everything the fill reads from memory is issued back to back - the contact bytes and the warm-start word first
-        // (behind wave-uniform null tests), then the 48 doubles of the state - and nothing dependent sits in between: a
-        // wave's fill used to chain four to five vector-memory round trips (two batches of state, contact bytes, warm word,
-        // Rwb again: 2.5 us from kernel entry to "inputs landed" for a lone wave, profiles/r03_timeline.log).
-        const BatchIn& ia = IN();
-        const uint32_t* wp = warm;
-        const long robot = cursor + lane;
-        const uint32_t sw = ia.stance ? *reinterpret_cast<const uint32_t*>(ia.stance + 4 * robot) : 0u;
-        const uint32_t wv = wp ? wp[robot] : 0u;
-        RawState S;
-        TickExtra X;
-        double fp[12];
-        fetch_extra<KIN>(ia, robot, X);
-        fetch_state<4, KIN>(ia, robot, 0, S, fp);
-        asm volatile("" ::: "memory");  // (the loads above stay above)
-        CParams& P = *QC_PARAMS_HERE(Pg);
-        Wrench<4> W;
-        const uint32_t st = assemble_from_state<KIN, 4, false>(P, ia, robot, 0, S, fp, sw, X, W);
-        if constexpr (RPARK) {
+  // One fill per wave, a divergent solve loop, one push, one flush: nothing but recalculations on the serial chain that
+  // bounds such a batch.
+  constexpr bool RESIDENT = MODE == 2;
+  if (cursor >= end) return;
+  UConst uc;  // RESIDENT: the recalculation's constants live in VGPRs (no scalar load + wait per recalculation)
+  if constexpr (RESIDENT) uc = load_uconst(*QC_PARAMS_HERE(Pg));
+  // One lane per robot: the lane that assembles a robot is the lane that solves it, so the robot goes straight from the
+  // assembly into the solver's registers - no input stock, no barrier - and its Rwb is parked in the first nine planes of
+  // the (otherwise idle) input-stock area for the output transform; the planes behind them serve as the re-pack area of the tail.
+  constexpr bool DIRECT = G == 1;
+  constexpr bool RPARK = DIRECT && !HESS_ONLY;  // Rwb parked in LDS for the output transform
+  constexpr int R_PLANES = RPARK ? 9 : 0;
+  static_assert(!DIRECT || QPARK || (R_PLANES * SP + 16 * REPACK_RS <= IN_PLANES * SP), "Rwb planes + re-pack records fit the input-stock area");
+  if constexpr (DIRECT) {
+    const long left = end - cursor;
+    stock_n = left < 64 ? (int)left : 64;
+    if (lane < stock_n) {
+      // Everything the fill reads from memory is issued back to back - the contact bytes and the warm-start word first
+      // (behind wave-uniform null tests), then the 48 doubles of the state - and nothing dependent sits in between: a
+      // wave's fill used to chain four to five vector-memory round trips (two batches of state, contact bytes, warm word,
+      // Rwb again: 2.5 us from kernel entry to "inputs landed" for a lone wave, profiles/r03_timeline.log).
+      const BatchIn& ia = IN();
+      const uint32_t* wp = warm;
+      const long robot = cursor + lane;
+      const uint32_t sw = ia.stance ? *reinterpret_cast<const uint32_t*>(ia.stance + 4 * robot) : 0u;
+      const uint32_t wv = wp ? wp[robot] : 0u;
+      RawState S;
+      TickExtra X;
+      double fp[12];
+      fetch_extra<KIN>(ia, robot, X);
+      fetch_state<4, KIN>(ia, robot, 0, S, fp);
+      asm volatile("" ::: "memory");  // (the loads above stay above)
+      CParams& P = *QC_PARAMS_HERE(Pg);
+      Wrench<4> W;
+      const uint32_t st = assemble_from_state<KIN, 4, false>(P, ia, robot, 0, S, fp, sw, X, W);
+      if constexpr (RPARK) {
 #pragma unroll
-          for (int k = 0; k < 9; k++) sin[k * SP + lane] = S.R[k];
-        }
-        if constexpr (QPARK) {  // (fp = the twelve joint angles fetch_state read)
-#pragma unroll
-          for (int k = 0; k < 12; k++) sin[(QPARK_Q + k) * SP + lane] = fp[k];
-        }
-        L.load_direct(W, st, wv, robot, 0, P.tol_start);
-      } else if constexpr (TWIN) {
-        // The wave-uniform loops below run every lane through the recalculation body, the lanes beyond a ragged last fill
-        // included: they carry a defined robot - no wrench, no stance foot (every foot eliminated, nothing to iterate on) -
-        // instead of whatever the registers held.  They never store.  (Shadowing robot 0 of the wave, as the strided kernels'
-        // spare groups do, costs this 512-register kernel 12 B of scratch.)
-        Wrench<4> W;
-#pragma unroll
-        for (int k = 0; k < 6; k++) W.b[k] = 0.0;
-#pragma unroll
-        for (int i = 0; i < 4; i++) W.r[i][0] = W.r[i][1] = W.r[i][2] = 0.0;
-        L.load_direct(W, 0u, 0u, -1, 0, 0.0);
+        for (int k = 0; k < 9; k++) sin[k * SP + lane] = S.R[k];
       }
-    } else {
-      stock_n = restock<G, KIN, STR, SP>(Pg, IN(), warm, cursor, end, lane, member, sin);
+      if constexpr (QPARK) {  // (fp = the twelve joint angles fetch_state read)
+#pragma unroll
+        for (int k = 0; k < 12; k++) sin[(QPARK_Q + k) * SP + lane] = fp[k];
+      }
+      L.load_direct(W, st, wv, robot, 0, P.tol_start);
+    } else if constexpr (TWIN) {
+      // The wave-uniform loops below run every lane through the recalculation body, the lanes beyond a ragged last fill
+      // included: they carry a defined robot - no wrench, no stance foot (every foot eliminated, nothing to iterate on) -
+      // instead of whatever the registers held.  They never store.  (Shadowing robot 0 of the wave, as the strided kernels'
+      // spare groups do, costs this 512-register kernel 12 B of scratch.)
+      Wrench<4> W;
+#pragma unroll
+      for (int k = 0; k < 6; k++) W.b[k] = 0.0;
+#pragma unroll
+      for (int i = 0; i < 4; i++) W.r[i][0] = W.r[i][1] = W.r[i][2] = 0.0;
+      L.load_direct(W, 0u, 0u, -1, 0, 0.0);
     }
-    const int grp = lane_group<G, STR>(lane);
-    busy = grp < stock_n;
-    // measurement probe (qc_set_tuning "probe_batch_load"): load -> assemble -> store only, no recalculation
-    const bool probe = QC_PARAMS_HERE(Pg)->max_iter == 0;
-    using LaneT = Lane<Eqp, KIN, (RACE > 1) || TWIN>;
-    if constexpr (STR) {
-      // Strided layout: the group sums run on the matrix pipe, and an MFMA reads its operands from ALL 64 lanes
-      // whatever EXEC says - the all-ones A operand included, which the compiler materialises under the current
-      // EXEC.  So nothing here may run under a partial EXEC: every lane carries a robot (groups beyond the fill
-      // shadow robot 0) through a wave-uniform loop, and only the lanes of running robots commit what a
-      // recalculation produced.
-      // RACE > 1: the wave holds 16 / RACE robots; group grp solves robot grp % ROB with strategy sid
-      constexpr int ROB = 16 / RACE;
-      const int slot = grp & (ROB - 1);
-      const int sid = (grp / ROB) * (4 / RACE);  // 4 strategies: 0 .. 3; 2: {0, 2}
+  } else {
+    stock_n = restock<G, KIN, STR, SP>(Pg, IN(), warm, cursor, end, lane, member, sin);
+  }
+  const int grp = lane_group<G, STR>(lane);
+  busy = grp < stock_n;
+  // measurement probe (qc_set_tuning "probe_batch_load"): load -> assemble -> store only, no recalculation
+  const bool probe = QC_PARAMS_HERE(Pg)->max_iter == 0;
+  using LaneT = Lane<Eqp, KIN, (RACE > 1) || TWIN>;
+  if constexpr (STR) {
+    // Strided layout: the group sums run on the matrix pipe, and an MFMA reads its operands from ALL 64 lanes
+    // whatever EXEC says - the all-ones A operand included, which the compiler materialises under the current
+    // EXEC.  So nothing here may run under a partial EXEC: every lane carries a robot (groups beyond the fill
+    // shadow robot 0) through a wave-uniform loop, and only the lanes of running robots commit what a
+    // recalculation produced.
+    // RACE > 1: the wave holds 16 / RACE robots; group grp solves robot grp % ROB with strategy sid
+    constexpr int ROB = 16 / RACE;
+    const int slot = grp & (ROB - 1);
+    const int sid = (grp / ROB) * (4 / RACE);  // 4 strategies: 0 .. 3; 2: {0, 2}
+    if constexpr (RACE > 1) {
+      busy = slot < stock_n;
+      // (clamp steps, drop rule) = (1, most negative) (1, all) (2, all) (3, most negative): over eight 4 096-robot
+      // batches the slowest robot takes 13.25 recalculations on average against 16.9 with the first strategy alone
+      // (13.9 for the pair {0, 2} a 2-way race runs); oracle/prototypes/proto_race_strategies.py
+      L.nclamp = sid == 3 ? 3 : (sid == 2 ? 2 : 1);
+      L.drop_all = sid == 1 || sid == 2;
+    }
+    double tol0;  // (RESIDENT: from the register copy - another scalar load here is a memory round trip a lone wave waits out)
+    if constexpr (RESIDENT) tol0 = uc.tol_start;
+    else tol0 = QC_PARAMS_HERE(Pg)->tol_start;
+    L.template load_from_stock<SP>(sin, busy ? slot : 0, member, tol0);
+    eqp.setup(*QC_PARAMS_HERE(Pg), L.Wr, L.foot0);
+    busy = busy && !probe;
+    unsigned solved_mask = 0;  // RACE: strategies of this lane's robot that have reached the KKT point
+    // the robot is finished as soon as one strategy has solved it; the others stop with it
+    auto after = [&](bool done) {
       if constexpr (RACE > 1) {
-        busy = slot < stock_n;
-        // (clamp steps, drop rule) = (1, most negative) (1, all) (2, all) (3, most negative): over eight 4 096-robot
-        // batches the slowest robot takes 13.25 recalculations on average against 16.9 with the first strategy alone
-        // (13.9 for the pair {0, 2} a 2-way race runs); oracle/prototypes/proto_race_strategies.py
-        L.nclamp = sid == 3 ? 3 : (sid == 2 ? 2 : 1);
-        L.drop_all = sid == 1 || sid == 2;
-      }
-      double tol0;  // (RESIDENT: from the register copy - another scalar load here is a memory round trip a lone wave waits out)
-      if constexpr (RESIDENT) tol0 = uc.tol_start;
-      else tol0 = QC_PARAMS_HERE(Pg)->tol_start;
-      L.template load_from_stock<SP>(sin, busy ? slot : 0, member, tol0);
-      eqp.setup(*QC_PARAMS_HERE(Pg), L.Wr, L.foot0);
-      busy = busy && !probe;
-      unsigned solved_mask = 0;  // RACE: strategies of this lane's robot that have reached the KKT point
-      // the robot is finished as soon as one strategy has solved it; the others stop with it
-      auto after = [&](bool done) {
-        if constexpr (RACE > 1) {
-          const int mine = (busy & done & (L.status == QC_SOLVED)) ? (1 << sid) : 0;
-          int m = mine | __builtin_amdgcn_update_dpp(0, mine, 0x120 + ROB, 0xF, 0xF, true);  // row_ror by ROB lanes: the partner groups
-          if constexpr (RACE == 4) {
-            m |= __builtin_amdgcn_update_dpp(0, mine, 0x120 + 2 * ROB, 0xF, 0xF, true);
-            m |= __builtin_amdgcn_update_dpp(0, mine, 0x120 + 3 * ROB, 0xF, 0xF, true);
-          }
-          solved_mask |= (unsigned)m;
-          busy = busy & !done & (solved_mask == 0);
-        } else {
-          busy = busy & !done;
+        const int mine = (busy & done & (L.status == QC_SOLVED)) ? (1 << sid) : 0;
+        int m = mine | __builtin_amdgcn_update_dpp(0, mine, 0x120 + ROB, 0xF, 0xF, true);  // row_ror by ROB lanes: the partner groups
+        if constexpr (RACE == 4) {
+          m |= __builtin_amdgcn_update_dpp(0, mine, 0x120 + 2 * ROB, 0xF, 0xF, true);
+          m |= __builtin_amdgcn_update_dpp(0, mine, 0x120 + 3 * ROB, 0xF, 0xF, true);
         }
-      };
-      QC_CLK(0, 2);
-      // clamp steps: one for the racing lanes (their strategies take more in the MIXED recalculations below)
-      const int first_steps = RACE > 1 ? 1 : clamp_steps_for<G>(*QC_PARAMS_HERE(Pg), warm);
+        solved_mask |= (unsigned)m;
+        busy = busy & !done & (solved_mask == 0);
+      } else {
+        busy = busy & !done;
+      }
+    };
+    QC_CLK(0, 2);
+    // clamp steps: one for the racing lanes (their strategies take more in the MIXED recalculations below)
+    const int first_steps = RACE > 1 ? 1 : clamp_steps_for<G>(*QC_PARAMS_HERE(Pg), warm);
 #pragma unroll 1
-      for (int k = 0; k < first_steps && (k == 0 || __builtin_amdgcn_ballot_w64(busy) != 0); k++) {
-        if (k) QC_CLK(7, 2);
-        bool done;
-        if constexpr (RESIDENT) {
-          pin_uconst(uc);
-          done = L.template iterate<LaneT::FIRST>(uc, eqp, busy, k == 0 && warm == nullptr);
-        } else {
-          done = L.template iterate<LaneT::FIRST>(*QC_PARAMS_HERE(Pg), eqp, busy, k == 0 && warm == nullptr);
-        }
-        after(done);
+    for (int k = 0; k < first_steps && (k == 0 || __builtin_amdgcn_ballot_w64(busy) != 0); k++) {
+      if (k) QC_CLK(7, 2);
+      bool done;
+      if constexpr (RESIDENT) {
+        pin_uconst(uc);
+        done = L.template iterate<LaneT::FIRST>(uc, eqp, busy, k == 0 && warm == nullptr);
+      } else {
+        done = L.template iterate<LaneT::FIRST>(*QC_PARAMS_HERE(Pg), eqp, busy, k == 0 && warm == nullptr);
       }
-      if constexpr (RACE > 1) {  // recalculations 2 and 3: clamp steps for the strategies that take them, ordinary steps for the others
+      after(done);
+    }
+    if constexpr (RACE > 1) {  // recalculations 2 and 3: clamp steps for the strategies that take them, ordinary steps for the others
 #pragma unroll 1
-        for (int it = 2; it <= 3 && __builtin_amdgcn_ballot_w64(busy) != 0; it++) {
-          QC_CLK(7, 2);
-          bool done;
-          if constexpr (RESIDENT) {
-            pin_uconst(uc);
-            done = L.template iterate<LaneT::MIXED>(uc, eqp, busy);
-          } else {
-            done = L.template iterate<LaneT::MIXED>(*QC_PARAMS_HERE(Pg), eqp, busy);
-          }
-          after(done);
-        }
-      }
-      while (__builtin_amdgcn_ballot_w64(busy) != 0) {
+      for (int it = 2; it <= 3 && __builtin_amdgcn_ballot_w64(busy) != 0; it++) {
         QC_CLK(7, 2);
         bool done;
         if constexpr (RESIDENT) {
           pin_uconst(uc);
-          done = L.template iterate<LaneT::STEADY>(uc, eqp, busy);
+          done = L.template iterate<LaneT::MIXED>(uc, eqp, busy);
         } else {
-          done = L.template iterate<LaneT::STEADY>(*QC_PARAMS_HERE(Pg), eqp, busy);
+          done = L.template iterate<LaneT::MIXED>(*QC_PARAMS_HERE(Pg), eqp, busy);
         }
         after(done);
       }
-      if constexpr (RACE > 1) {
-        // the winner - the lowest-numbered strategy among those that solved the robot in the deciding
-        // recalculation, or strategy 0 with whatever status it has if none did - parks the result
-        const int win = solved_mask ? __builtin_ctz(solved_mask) : 0;
-        QC_CLK(7, 8);
-        if (slot < stock_n && sid == win) L.template push_result<SP>(sout, slot);
-        __syncthreads();
-        flush_out<Eqp::G, KIN, STR, SP>(Pg, IN(), OUT(), sout, stock_n, lane);
-        QC_CLK_END(8);
-        return;
+    }
+    while (__builtin_amdgcn_ballot_w64(busy) != 0) {
+      QC_CLK(7, 2);
+      bool done;
+      if constexpr (RESIDENT) {
+        pin_uconst(uc);
+        done = L.template iterate<LaneT::STEADY>(uc, eqp, busy);
+      } else {
+        done = L.template iterate<LaneT::STEADY>(*QC_PARAMS_HERE(Pg), eqp, busy);
       }
+      after(done);
+    }
+    if constexpr (RACE > 1) {
+      // the winner - the lowest-numbered strategy among those that solved the robot in the deciding
+      // recalculation, or strategy 0 with whatever status it has if none did - parks the result
+      const int win = solved_mask ? __builtin_ctz(solved_mask) : 0;
       QC_CLK(7, 8);
-      if (grp < stock_n) L.template push_result<SP>(sout, grp);
+      if (slot < stock_n && sid == win) L.template push_result<SP>(sout, slot);
       __syncthreads();
       flush_out<Eqp::G, KIN, STR, SP>(Pg, IN(), OUT(), sout, stock_n, lane);
       QC_CLK_END(8);
       return;
     }
-    if (busy || TWIN) {  // (TWIN: the shadow lanes of a ragged fill get their Hessian column too)
-      if constexpr (!DIRECT) L.template load_from_stock<SP>(sin, grp, member, QC_PARAMS_HERE(Pg)->tol_start);
-      eqp.setup(*QC_PARAMS_HERE(Pg), L.Wr, L.foot0);
-    }
-    const bool mine = busy;
-    busy = busy && !probe;
-    QC_CLK(0, 2);
-    const int first_steps = clamp_steps_for<G>(*QC_PARAMS_HERE(Pg), warm);
-#pragma unroll 1
-    for (int k = 0; k < first_steps; k++) {
-      if (k) QC_CLK(7, 2);
-      if (busy) {  // every robot of a one-fill wave is fresh exactly once: the clamp steps are peeled
-        if constexpr (RESIDENT) {
-          pin_uconst(uc);
-          busy = !L.template iterate<LaneT::FIRST>(uc, eqp, true, k == 0 && warm == nullptr);
-        } else {
-          busy = !L.template iterate<LaneT::FIRST>(*QC_PARAMS_HERE(Pg), eqp, true, k == 0 && warm == nullptr);
-        }
-      }
-    }
-    if constexpr (Eqp::kRepackTail) {
-      unsigned long long bm = __builtin_amdgcn_ballot_w64(busy);
-      while (__builtin_popcountll(bm) > 16 * G) {  // more than 16 robots still running
-        QC_CLK(7, 2);
-        if (busy) busy = !L.template iterate<LaneT::STEADY>(*QC_PARAMS_HERE(Pg), eqp);
-        bm = __builtin_amdgcn_ballot_w64(busy);
-      }
-      if constexpr (QPARK) {
-        // the re-pack records live under the output stock: the tail parks its results after its last record read, and the robots that
-        // finished on the one-lane body after the tail (their results wait in this lane's registers)
-        finish_on_four_lanes<KIN, Eqp::kUniform, SP, true>(Pg, L, busy, bm, grp, member, lane, sout, sout, warm == nullptr);
-        if (!busy && mine) L.template push_result<SP>(sout, grp);
-      } else {
-        if (!busy && mine) L.template push_result<SP>(sout, grp);  // finished in the one- / two-lane layout
-        finish_on_four_lanes<KIN, Eqp::kUniform, SP>(Pg, L, busy, bm, grp, member, lane, sin + R_PLANES * SP, sout, warm == nullptr);
-      }
-    } else if constexpr (TWIN) {
-      // The one-lane dense form has no 4-lane tail (the exchange tile of the 4-lane dense body does not fit next to the Hessian
-      // planes), so a wave walks its one-lane body until its slowest robot is done - at half the lanes or fewer busy for most of
-      // that walk.  Those idle lanes race: once at most 32 robots still run, every running robot is copied into an idle lane
-      // (working set, point, c; the 78 Hessian entries are READ from the owner's LDS column by both - nobody writes them after
-      // setup) which continues with the OTHER drop rule - all negative multipliers at once instead of the most negative one -
-      // and whoever reaches the KKT point first ends both (the tail race of the 6x6 forms, profiles/r02_tail_race_scan.log, with
-      // lanes instead of lane groups).  Cold batches only: a warm-started robot that is not done after its first recalculation
-      // is a face or two away.
-      unsigned long long bm = __builtin_amdgcn_ballot_w64(busy);
-      const bool fork_ok = warm == nullptr && QC_PARAMS_HERE(Pg)->tail_race != 0;
-      // (both loops are wave-uniform and run every lane with `live` = busy - see Lane::iterate on why a finished or empty lane may
-      // keep computing: a per-lane branch around the 2 600-instruction body costs exec-mask saves in SGPR pairs, which spill here)
-      while (__builtin_popcountll(bm) > (fork_ok ? 32 : 0)) {
-        const bool done = L.template iterate<LaneT::STEADY>(*QC_PARAMS_HERE(Pg), eqp, busy);
-        busy = busy & !done;
-        bm = __builtin_amdgcn_ballot_w64(busy);
-      }
-      int partner = lane;   // the lane racing on the same robot (itself: no race)
-      // per-lane flags of the race, packed into one VGPR (as separate bools they live in SGPR pairs across the 2 600-instruction
-      // body, and SGPR pairs that spill leave frame slots): bit 0 this lane still holds a result (its own robot's) that has to
-      // reach the output, bit 1 it is a twin, bit 2 it brought its robot to the KKT point
-      int role = mine ? 1 : 0;
-      if (bm != 0) {
-        // lanes whose own robot is finished store it straight from their registers (the output stock aliases Hessian planes that
-        // are still being read; Rwb comes from memory) - their registers are about to carry somebody else's robot
-        if (mine && !busy) {
-          CParams& P = *QC_PARAMS_HERE(Pg);
-          store_result<KIN, 4, false>(P, IN(), OUT(), L.idx, L.stance, L.status, L.iters, L.word_bits() | 0x80000000u, L.f, 0);
-          role = 0;
-        }
-        const int nb = __builtin_popcountll(bm);
-        const unsigned long long idle = ~bm;
-        const int my_rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)((busy ? bm : idle) >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)(busy ? bm : idle), 0));
-        // lane id of the rank-th set bit of m (ranks from 0; m has more than `rank` bits set): binary search on popcounts
-        auto nth = [](unsigned long long m, int rank) {
-          int pos = 0;
-#pragma unroll
-          for (int w = 32; w >= 1; w >>= 1) {
-            const int c = __builtin_popcountll(m & ((1ull << w) - 1ull));
-            const bool up = rank >= c;
-            m = up ? (m >> w) : m;
-            rank -= up ? c : 0;
-            pos += up ? w : 0;
-          }
-          return pos;
-        };
-        const bool twin = !busy && my_rank < nb;  // the my_rank-th idle lane takes the my_rank-th running robot
-        if (busy) partner = nth(idle, my_rank);
-        if (twin) partner = nth(bm, my_rank);
-        // the owner's state, read by its twin (every lane executes the shuffles; only twins keep what they read)
-        const int src = twin ? partner : lane;
-        auto take_i = [&](int v) { return __builtin_amdgcn_ds_bpermute(src << 2, v); };
-        auto take_d = [&](double v) {
-          const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-          const unsigned lo = (unsigned)take_i((int)(unsigned)u), hi = (unsigned)take_i((int)(unsigned)(u >> 32));
-          return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-        };
-        const uint32_t wbits = (uint32_t)take_i((int)L.word_bits());
-        const uint32_t stance_o = (uint32_t)take_i((int)L.stance);
-        const int iters_o = take_i(L.iters);
-        const double tol_o = take_d(L.tol_s);
-        const int idx_lo = take_i((int)(unsigned)(unsigned long long)L.idx), idx_hi = take_i((int)(unsigned)((unsigned long long)L.idx >> 32));
-        // (one value at a time, selected in place: two dozen temporaries next to the 78-entry factor's registers would spill)
-#pragma unroll
-        for (int k = 0; k < 12; k++) {
-          const double tf = take_d(L.f[k]);
-          L.f[k] = twin ? tf : L.f[k];
-          const double tc = take_d(eqp.c[k]);
-          eqp.c[k] = twin ? tc : eqp.c[k];
-        }
-        if (twin) {
-          L.stance = stance_o;
-          L.iters = iters_o;
-          L.idx = (long)(((unsigned long long)(unsigned)idx_hi << 32) | (unsigned)idx_lo);
-          L.status = QC_MAX_ITER;
-          L.tol_s = tol_o;
-          L.have_f = true;
-          L.drop_all = true;
-          L.foot0 = 0;
-#pragma unroll
-          for (int i = 0; i < 4; i++) {
-            const uint32_t fb = wbits >> (6 * i);
-            L.C.sx[i] = dec2(fb); L.C.sy[i] = dec2(fb >> 2); L.C.sz[i] = dec2(fb >> 4);
-          }
-          // the robot's Hessian: the twin reads the owner's LDS column (read-only after setup; same address in both lanes = a broadcast)
-          eqp.Qs = eqp.Qs - lane + partner;
-          role = 2;
-          busy = true;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      }
-      asm volatile("" : "+v"(role), "+v"(partner));
-      while (__builtin_amdgcn_ballot_w64(busy) != 0) {
-        const bool done = L.template iterate<LaneT::STEADY>(*QC_PARAMS_HERE(Pg), eqp, busy);
-        asm volatile("" : "+v"(role), "+v"(partner));
-        const int solved = (busy && done && L.status == QC_SOLVED) ? 1 : 0;
-        const int fin = (busy && done) ? 1 : 0;
-        const int theirs = __builtin_amdgcn_ds_bpermute(partner << 2, solved);
-        // a tie goes to the owner (the classic rule); a twin stops as soon as its owner is finished in any way
-        const int owner_done = __builtin_amdgcn_ds_bpermute(partner << 2, fin);
-        const bool is_twin = (role & 2) != 0;
-        role |= (solved && !(is_twin && theirs)) ? 4 : 0;
-        busy = busy && !done && !(partner != lane && theirs) && !(is_twin && owner_done);
-      }
-      // who stores: the owner, unless its twin got to the KKT point first (then the twin)
-      const int twin_won = __builtin_amdgcn_ds_bpermute(partner << 2, ((role & 6) == 6) ? 1 : 0);
-      const bool store_own = (role & 1) && !(partner != lane && twin_won);
-      if (store_own || (role & 6) == 6) {  // straight from the registers, like the lanes that finished before the fork: no output stock on this path
-        CParams& P = *QC_PARAMS_HERE(Pg);
-        store_result<KIN, 4, false>(P, IN(), OUT(), L.idx, L.stance, L.status, L.iters, L.word_bits() | 0x80000000u, L.f, 0);
-      }
-      QC_CLK_END(8);
-      return;
-    } else {
-      while (busy) {
-        if constexpr (RESIDENT) {
-          pin_uconst(uc);
-          busy = !L.template iterate<LaneT::STEADY>(uc, eqp);
-        } else {
-          busy = !L.template iterate<LaneT::STEADY>(*QC_PARAMS_HERE(Pg), eqp);
-        }
-      }
-      if constexpr (HESS_ONLY) __syncthreads();  // (the dense joint_q kernel) every lane is past its last read of the Hessian planes the output stock aliases
-      if (mine) L.template push_result<SP>(sout, grp);
-    }
     QC_CLK(7, 8);
+    if (grp < stock_n) L.template push_result<SP>(sout, grp);
     __syncthreads();
-    flush_out<Eqp::G, KIN, STR, SP, RPARK>(Pg, IN(), OUT(), sout, stock_n, lane, RPARK ? sin : nullptr, QPARK ? sin + QPARK_Q * SP : nullptr);
+    flush_out<Eqp::G, KIN, STR, SP>(Pg, IN(), OUT(), sout, stock_n, lane);
     QC_CLK_END(8);
     return;
   }
-  // The first restock runs before any solver state is live, so (unlike its copy
-  // inside the loop) it needs no spills: batches that fit one fill per wave
-  // never execute the in-loop copy.
-  if (cursor < end) {
-    stock_n = restock<G, KIN, false, SP>(Pg, IN(), warm, cursor, end, lane, member, sin);
-    cursor += stock_n;
+  if (busy || TWIN) {  // (TWIN: the shadow lanes of a ragged fill get their Hessian column too)
+    if constexpr (!DIRECT) L.template load_from_stock<SP>(sin, grp, member, QC_PARAMS_HERE(Pg)->tol_start);
+    eqp.setup(*QC_PARAMS_HERE(Pg), L.Wr, L.foot0);
   }
-  QC_CLK(0, 1);
-  for (;;) {
-    const unsigned long long busy_mask = __builtin_amdgcn_ballot_w64(busy);
-    const int n_free = (64 - __builtin_popcountll(busy_mask)) / G;  // free groups
-    const long avail = (end - cursor) + (long)(stock_n - stock_next);
-    if (avail > 0 && (n_free >= refill_t || busy_mask == 0)) {
-      if (stock_next == stock_n) {
-        stock_n = restock<G, KIN, false, SP>(Pg, IN(), warm, cursor, end, lane, member, sin);
-        stock_next = 0;
-        cursor += stock_n;
+  const bool mine = busy;
+  busy = busy && !probe;
+  QC_CLK(0, 2);
+  const int first_steps = clamp_steps_for<G>(*QC_PARAMS_HERE(Pg), warm);
+#pragma unroll 1
+  for (int k = 0; k < first_steps; k++) {
+    if (k) QC_CLK(7, 2);
+    if (busy) {  // every robot of a one-fill wave is fresh exactly once: the clamp steps are peeled
+      if constexpr (RESIDENT) {
+        pin_uconst(uc);
+        busy = !L.template iterate<LaneT::FIRST>(uc, eqp, true, k == 0 && warm == nullptr);
+      } else {
+        busy = !L.template iterate<LaneT::FIRST>(*QC_PARAMS_HERE(Pg), eqp, true, k == 0 && warm == nullptr);
       }
-      const int have = stock_n - stock_next;
-      const int take = n_free < have ? n_free : have;
-      const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(~busy_mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)~busy_mask, 0)) / G;
-      if (!busy && rank < take) {
-        L.template load_from_stock<SP>(sin, stock_next + rank, member, QC_PARAMS_HERE(Pg)->tol_start);
+    }
+  }
+  if constexpr (Eqp::kRepackTail) {
+    unsigned long long bm = __builtin_amdgcn_ballot_w64(busy);
+    while (__builtin_popcountll(bm) > 16 * G) {  // more than 16 robots still running
+      QC_CLK(7, 2);
+      if (busy) busy = !L.template iterate<LaneT::STEADY>(*QC_PARAMS_HERE(Pg), eqp);
+      bm = __builtin_amdgcn_ballot_w64(busy);
+    }
+    if constexpr (QPARK) {
+      // the re-pack records live under the output stock: the tail parks its results after its last record read, and the robots that
+      // finished on the one-lane body after the tail (their results wait in this lane's registers)
+      finish_on_four_lanes<KIN, Eqp::kUniform, SP, true>(Pg, L, busy, bm, grp, member, lane, sout, sout, warm == nullptr);
+      if (!busy && mine) L.template push_result<SP>(sout, grp);
+    } else {
+      if (!busy && mine) L.template push_result<SP>(sout, grp);  // finished in the one- / two-lane layout
+      finish_on_four_lanes<KIN, Eqp::kUniform, SP>(Pg, L, busy, bm, grp, member, lane, sin + R_PLANES * SP, sout, warm == nullptr);
+    }
+  } else if constexpr (TWIN) {
+    // The one-lane dense form has no 4-lane tail (the exchange tile of the 4-lane dense body does not fit next to the Hessian
+    // planes), so a wave walks its one-lane body until its slowest robot is done - at half the lanes or fewer busy for most of
+    // that walk.  Those idle lanes race: once at most 32 robots still run, every running robot is copied into an idle lane
+    // (working set, point, c; the 78 Hessian entries are READ from the owner's LDS column by both - nobody writes them after
+    // setup) which continues with the OTHER drop rule - all negative multipliers at once instead of the most negative one -
+    // and whoever reaches the KKT point first ends both (the tail race of the 6x6 forms, profiles/r02_tail_race_scan.log, with
+    // lanes instead of lane groups).  Cold batches only: a warm-started robot that is not done after its first recalculation
+    // is a face or two away.
+    unsigned long long bm = __builtin_amdgcn_ballot_w64(busy);
+    const bool fork_ok = warm == nullptr && QC_PARAMS_HERE(Pg)->tail_race != 0;
+    // (both loops are wave-uniform and run every lane with `live` = busy - see Lane::iterate on why a finished or empty lane may
+    // keep computing: a per-lane branch around the 2 600-instruction body costs exec-mask saves in SGPR pairs, which spill here)
+    while (__builtin_popcountll(bm) > (fork_ok ? 32 : 0)) {
+      const bool done = L.template iterate<LaneT::STEADY>(*QC_PARAMS_HERE(Pg), eqp, busy);
+      busy = busy & !done;
+      bm = __builtin_amdgcn_ballot_w64(busy);
+    }
+    int partner = lane;   // the lane racing on the same robot (itself: no race)
+    // per-lane flags of the race, packed into one VGPR (as separate bools they live in SGPR pairs across the 2 600-instruction
+    // body, and SGPR pairs that spill leave frame slots): bit 0 this lane still holds a result (its own robot's) that has to
+    // reach the output, bit 1 it is a twin, bit 2 it brought its robot to the KKT point
+    int role = mine ? 1 : 0;
+    if (bm != 0) {
+      // lanes whose own robot is finished store it straight from their registers (the output stock aliases Hessian planes that
+      // are still being read; Rwb comes from memory) - their registers are about to carry somebody else's robot
+      if (mine && !busy) {
         CParams& P = *QC_PARAMS_HERE(Pg);
-        eqp.setup(P, L.Wr, L.foot0);
+        store_result<KIN, 4, false>(P, IN(), OUT(), L.idx, L.stance, L.status, L.iters, L.word_bits() | 0x80000000u, L.f, 0);
+        role = 0;
+      }
+      const int nb = __builtin_popcountll(bm);
+      const unsigned long long idle = ~bm;
+      const int my_rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)((busy ? bm : idle) >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)(busy ? bm : idle), 0));
+      // lane id of the rank-th set bit of m (ranks from 0; m has more than `rank` bits set): binary search on popcounts
+      auto nth = [](unsigned long long m, int rank) {
+        int pos = 0;
+#pragma unroll
+        for (int w = 32; w >= 1; w >>= 1) {
+          const int c = __builtin_popcountll(m & ((1ull << w) - 1ull));
+          const bool up = rank >= c;
+          m = up ? (m >> w) : m;
+          rank -= up ? c : 0;
+          pos += up ? w : 0;
+        }
+        return pos;
+      };
+      const bool twin = !busy && my_rank < nb;  // the my_rank-th idle lane takes the my_rank-th running robot
+      if (busy) partner = nth(idle, my_rank);
+      if (twin) partner = nth(bm, my_rank);
+      // the owner's state, read by its twin (every lane executes the shuffles; only twins keep what they read)
+      const int src = twin ? partner : lane;
+      auto take_i = [&](int v) { return __builtin_amdgcn_ds_bpermute(src << 2, v); };
+      auto take_d = [&](double v) {
+        const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+        const unsigned lo = (unsigned)take_i((int)(unsigned)u), hi = (unsigned)take_i((int)(unsigned)(u >> 32));
+        return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+      };
+      const uint32_t wbits = (uint32_t)take_i((int)L.word_bits());
+      const uint32_t stance_o = (uint32_t)take_i((int)L.stance);
+      const int iters_o = take_i(L.iters);
+      const double tol_o = take_d(L.tol_s);
+      const int idx_lo = take_i((int)(unsigned)(unsigned long long)L.idx), idx_hi = take_i((int)(unsigned)((unsigned long long)L.idx >> 32));
+      // (one value at a time, selected in place: two dozen temporaries next to the 78-entry factor's registers would spill)
+#pragma unroll
+      for (int k = 0; k < 12; k++) {
+        const double tf = take_d(L.f[k]);
+        L.f[k] = twin ? tf : L.f[k];
+        const double tc = take_d(eqp.c[k]);
+        eqp.c[k] = twin ? tc : eqp.c[k];
+      }
+      if (twin) {
+        L.stance = stance_o;
+        L.iters = iters_o;
+        L.idx = (long)(((unsigned long long)(unsigned)idx_hi << 32) | (unsigned)idx_lo);
+        L.status = QC_MAX_ITER;
+        L.tol_s = tol_o;
+        L.have_f = true;
+        L.drop_all = true;
+        L.foot0 = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const uint32_t fb = wbits >> (6 * i);
+          L.C.sx[i] = dec2(fb); L.C.sy[i] = dec2(fb >> 2); L.C.sz[i] = dec2(fb >> 4);
+        }
+        // the robot's Hessian: the twin reads the owner's LDS column (read-only after setup; same address in both lanes = a broadcast)
+        eqp.Qs = eqp.Qs - lane + partner;
+        role = 2;
         busy = true;
       }
-      stock_next += take;
-      continue;
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
-    if (busy_mask == 0) break;
-    bool fin = false;
-    if (busy) {
-      asm volatile("; QC_ITER_BEGIN");
-      QC_CLK(1, 2);
+    asm volatile("" : "+v"(role), "+v"(partner));
+    while (__builtin_amdgcn_ballot_w64(busy) != 0) {
+      const bool done = L.template iterate<LaneT::STEADY>(*QC_PARAMS_HERE(Pg), eqp, busy);
+      asm volatile("" : "+v"(role), "+v"(partner));
+      const int solved = (busy && done && L.status == QC_SOLVED) ? 1 : 0;
+      const int fin = (busy && done) ? 1 : 0;
+      const int theirs = __builtin_amdgcn_ds_bpermute(partner << 2, solved);
+      // a tie goes to the owner (the classic rule); a twin stops as soon as its owner is finished in any way
+      const int owner_done = __builtin_amdgcn_ds_bpermute(partner << 2, fin);
+      const bool is_twin = (role & 2) != 0;
+      role |= (solved && !(is_twin && theirs)) ? 4 : 0;
+      busy = busy && !done && !(partner != lane && theirs) && !(is_twin && owner_done);
+    }
+    // who stores: the owner, unless its twin got to the KKT point first (then the twin)
+    const int twin_won = __builtin_amdgcn_ds_bpermute(partner << 2, ((role & 6) == 6) ? 1 : 0);
+    const bool store_own = (role & 1) && !(partner != lane && twin_won);
+    if (store_own || (role & 6) == 6) {  // straight from the registers, like the lanes that finished before the fork: no output stock on this path
       CParams& P = *QC_PARAMS_HERE(Pg);
-      if (P.max_iter == 0) fin = true;  // measurement probe: load -> assemble -> store only (wave-uniform branch)
-      else fin = L.iterate(P, eqp);
-      QC_CLK(7, 1);
-      asm volatile("; QC_ITER_END");
+      store_result<KIN, 4, false>(P, IN(), OUT(), L.idx, L.stance, L.status, L.iters, L.word_bits() | 0x80000000u, L.f, 0);
     }
-    const unsigned long long fin_mask = __builtin_amdgcn_ballot_w64(fin);
-    if (fin_mask != 0) {
-      const int n_fin = __builtin_popcountll(fin_mask) / G;
-      if (out_n + n_fin > 64) {  // dense flush of the output stock, one robot per lane
-        __syncthreads();
-        flush_out<Eqp::G, KIN, false, SP>(Pg, IN(), OUT(), sout, out_n, lane);
-        __syncthreads();
-        out_n = 0;
+    QC_CLK_END(8);
+    return;
+  } else {
+    while (busy) {
+      if constexpr (RESIDENT) {
+        pin_uconst(uc);
+        busy = !L.template iterate<LaneT::STEADY>(uc, eqp);
+      } else {
+        busy = !L.template iterate<LaneT::STEADY>(*QC_PARAMS_HERE(Pg), eqp);
       }
-      if (fin) {
-        const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(fin_mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)fin_mask, 0)) / G;
-        L.template push_result<SP>(sout, out_n + rank);
-        busy = false;
-      }
-      out_n += n_fin;
     }
+    if constexpr (HESS_ONLY) __syncthreads();  // (the dense joint_q kernel) every lane is past its last read of the Hessian planes the output stock aliases
+    if (mine) L.template push_result<SP>(sout, grp);
   }
+  QC_CLK(7, 8);
   __syncthreads();
-  QC_CLK(1, 8);
-  flush_out<Eqp::G, KIN, false, SP>(Pg, IN(), OUT(), sout, out_n, lane);
+  flush_out<Eqp::G, KIN, STR, SP, RPARK>(Pg, IN(), OUT(), sout, stock_n, lane, RPARK ? sin : nullptr, QPARK ? sin + QPARK_Q * SP : nullptr);
   QC_CLK_END(8);
 }
 
@@ -1686,7 +1611,7 @@ __global__ __launch_bounds__(128, 2) void balance_pair_kernel(const DevParams* _
   static_assert(8 * REPACK_RS <= PAIR_CAP * PAIR_REC, "the race stage re-packs into the drained list (a solo wave's half of it)");
   constexpr bool UNIFORM = Eqp::kUniform;
   using Lane1 = Lane<Eqp, KIN>;
-  using Eqp4 = EqpDiagW<UNIFORM, 4, true>;
+  using Eqp4 = EqpDiagW<UNIFORM, 4>;
   using Lane4 = Lane<Eqp4, KIN>;
   using LaneR = Lane<Eqp4, KIN, true>;  // with a per-lane drop rule
   __shared__ PairLds lds;
@@ -1906,7 +1831,7 @@ __global__ __launch_bounds__(128, 2) void balance_pair_kernel(const DevParams* _
 }  // namespace qc
 
 // =============================================================== host / C ABI
-typedef void (*qc_kernel_fn)(const qc::DevParams*, long, qc::BatchIn, const uint32_t*, qc::BatchOut, long, int);
+typedef void (*qc_kernel_fn)(const qc::DevParams*, long, qc::BatchIn, const uint32_t*, qc::BatchOut, long);
 
 // qc::BalanceKernelArgs is a hand-written mirror of balance_kernel's parameter list (the kernarg segment lays every argument at the
 // next multiple of its alignment); every instantiation is stored as a qc_kernel_fn, so that type IS the list.  Growing BatchIn or
@@ -1930,11 +1855,10 @@ struct KernargOf<void (*)(A...)> {
   static constexpr size_t at(int i) { return kernarg_offset<A...>(i); }
 };
 using KernelArgList = KernargOf<qc_kernel_fn>;
-static_assert(KernelArgList::count == 7, "balance_kernel's parameter list changed: update qc::BalanceKernelArgs");
+static_assert(KernelArgList::count == 6, "balance_kernel's parameter list changed: update qc::BalanceKernelArgs");
 static_assert(offsetof(qc::BalanceKernelArgs, Pg) == KernelArgList::at(0) && offsetof(qc::BalanceKernelArgs, n) == KernelArgList::at(1) &&
                   offsetof(qc::BalanceKernelArgs, in) == KernelArgList::at(2) && offsetof(qc::BalanceKernelArgs, warm) == KernelArgList::at(3) &&
-                  offsetof(qc::BalanceKernelArgs, out) == KernelArgList::at(4) && offsetof(qc::BalanceKernelArgs, chunk) == KernelArgList::at(5) &&
-                  offsetof(qc::BalanceKernelArgs, refill_t) == KernelArgList::at(6),
+                  offsetof(qc::BalanceKernelArgs, out) == KernelArgList::at(4) && offsetof(qc::BalanceKernelArgs, chunk) == KernelArgList::at(5),
               "qc::BalanceKernelArgs no longer mirrors balance_kernel's kernarg layout");
 static_assert(sizeof(qc::CmdState) == sizeof(qc_commander_state) && offsetof(qc::CmdState, Vb) == offsetof(qc_commander_state, Vb) &&
                   offsetof(qc::CmdState, Rwb_d) == offsetof(qc_commander_state, Rwb_d) && offsetof(qc::CmdState, w_d) == offsetof(qc_commander_state, w_d),
@@ -1954,15 +1878,10 @@ struct qc_handle {
   int cfg_max_iter;
   bool force_general, force_dense, probing;
   // launch heuristics (defaults from measurements; qc_set_tuning overrides them)
-  int refill_t;            // parked lanes that trigger a refill (persistent waves)
-  double rounds_cold;      // cold batches up to rounds x (robots resident as one-fill workgroups) run one-fill
-  double rounds_warm;      // the same for warm-started batches
-  long chunk_override;     // > 0: robots per wave
+  long chunk_override;     // > 0: robots per wave (at most one fill, 64 / G)
   int group_override;      // 1, 2, 4: lanes per robot
-  int one_fill_override;   // 0: never (persistent waves), 1: always, -1: heuristic
   int wave_slots_override; // > 0: resident workgroups assumed for every kernel instead of the occupancy query
   int race_override;       // -1 heuristic; 0 / 1: no racing strategies; 2, 4: at most that many per robot
-  int min_waves;           // development builds (QC_EXPERIMENTAL_OCC): register cap of the one-fill kernels, waves per SIMD
   // resident workgroups per kernel instantiation (hipOccupancyMaxActiveBlocksPerMultiprocessor x CUs), filled lazily
   struct { const void* fn; size_t lds; long resident; } occ[40];
   int n_occ;
@@ -1996,7 +1915,6 @@ static void resolve_form(qc_handle* h) {
   h->uniform = h->cfg_uniform && !h->force_general;
 }
 
-#define QC_COMMA(...) __VA_ARGS__
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) {
   g_err = msg;
@@ -2081,70 +1999,38 @@ static int upload_params(qc_handle* h) {
 // the planner takes the widest group with which the batch still fits ONE wave per SIMD - such a batch cannot fill
 // the chip anyway and the slowest robot's serial chain is what is timed - i.e. G = 4 up to CUs x 4 x 16 robots
 // (16 384), G = 2 up to twice that, and one lane per robot above (tools/size_scan.py: the cross-overs sit exactly
-// there, cold and warm).  Every width finishes its last <= 16 running robots on the 4-lane body.  Batches up to
-// `rounds` times the resident one-fill workgroups run as one-fill workgroups - the hardware scheduler does the
-// refill; with the one-lane kernel that wins at every size measured (2 M robots cold: 633 us against 676 us as
-// persistent waves), so `rounds` is unbounded and the persistent kernels (waves walking contiguous chunks with lane
-// refill) serve qc_set_tuning("one_fill", 0) in development builds only.
+// there, cold and warm).  Every width finishes its last <= 16 running robots on the 4-lane body.  Every launch gives
+// each wave one fill (mode 1 / 2) - the hardware scheduler refills the chip with the next workgroup - or, for the
+// one-lane 6x6 kernels of large batches, a workgroup of two waves (mode 3, balance_pair_kernel); a chunk beyond one fill
+// is an error at launch.
 enum { QC_FORM_UNIFORM = 0, QC_FORM_GENERAL = 1, QC_FORM_DENSE = 2 };
-// The persistent-wave (MODE 0) kernels - round 1's large-batch kernels, which the planner has not picked for any batch of a
-// 6x6 form since the one-lane one-fill kernel exists (round 2) nor for the one-lane dense form since its LDS diet (round 5:
-// one-fill workgroups resident once per SIMD win at every size) - are compiled only into development builds
-// (-DQC_PERSISTENT_6X6=1: the A/B scans, QC_TEST_PERSISTENT_6X6=1 in tests/test_gpu_matrix.py): fourteen instantiations with
-// up to 672 B of scratch per lane that a default handle can never launch.  Without them every form runs as one-fill
-// workgroups and qc_set_tuning("one_fill", 0) / a chunk beyond one fill is an error at launch.
-#ifndef QC_PERSISTENT_6X6
-#define QC_PERSISTENT_6X6 0
-#endif
-#ifndef QC_ROUNDS_COLD
-#define QC_ROUNDS_COLD 1.0e9
-#endif
-#ifndef QC_ROUNDS_WARM
-#define QC_ROUNDS_WARM 1.0e9
-#endif
 
 template <class EQP, int MINW, int MODE, int RACE = 1>
 static qc_kernel_fn kernel_of(bool kin) {
   return kin ? (qc_kernel_fn)qc::balance_kernel<EQP, true, MINW, MODE, RACE> : (qc_kernel_fn)qc::balance_kernel<EQP, false, MINW, MODE, RACE>;
 }
-// the kernel instantiation for (form, lanes per robot, mode); mode 2 exists for the uniform G = 4 form only
-static qc_kernel_fn kernel_for(int form, int G, int mode, bool kin, int minw = 2, int race = 1) {
+// the kernel instantiation for (form, lanes per robot, mode, racing strategies); mode 2 exists for the uniform G = 4 form only,
+// racing strategies for the 4-lane kernels
+static qc_kernel_fn kernel_for(int form, int G, int mode, bool kin, int race = 1) {
   using namespace qc;
-  constexpr bool STR = !QC_NO_STRIDED;
-#ifdef QC_EXPERIMENTAL_OCC  // development builds: register-capped one-fill instantiations of the uniform form (tools/occ_scan.py)
-  if (form == QC_FORM_UNIFORM && mode == 1 && minw > 2) {
-    if (G == 4) return minw >= 4 ? kernel_of<EqpDiagW<true, 4, STR>, 4, 1>(kin) : kernel_of<EqpDiagW<true, 4, STR>, 3, 1>(kin);
-    if (G == 2) return minw >= 4 ? kernel_of<EqpDiagW<true, 2>, 4, 1>(kin) : kernel_of<EqpDiagW<true, 2>, 3, 1>(kin);
-  }
-#endif
-  (void)minw;
 #ifdef QC_DEV_ONLY_DENSE1  // development: compile the one-lane dense kernels alone (seconds instead of a minute; tools/kernel_resources.py)
-  (void)form; (void)G; (void)race;
+  (void)form; (void)G; (void)mode; (void)race;
   return kernel_of<EqpDense, 1, 1>(kin);
 #else
-#if QC_PERSISTENT_6X6
-#define QC_MODE0(EQP) kernel_of<EQP, 2, 0>(kin)
-#define QC_MODE0_DENSE kernel_of<EqpDense, 1, 0>(kin)
-#else
-#define QC_MODE0(EQP) nullptr /* the planner never asks: plan_launch keeps every form on one-fill workgroups */
-#define QC_MODE0_DENSE nullptr
-#endif
   if (form == QC_FORM_DENSE && G == 4) return race == 4 ? kernel_of<EqpDense4, 1, 1, 4>(kin) : (race == 2 ? kernel_of<EqpDense4, 1, 1, 2>(kin) : kernel_of<EqpDense4, 1, 1>(kin));
-  if (form == QC_FORM_DENSE) return mode ? kernel_of<EqpDense, 1, 1>(kin) : QC_MODE0_DENSE;
+  if (form == QC_FORM_DENSE) return kernel_of<EqpDense, 1, 1>(kin);
   if (form == QC_FORM_GENERAL) {
-    if (G == 4 && mode && STR && race == 4) return kernel_of<EqpDiagW<false, 4, STR>, 2, 1, (STR ? 4 : 1)>(kin);
-    if (G == 4 && mode && STR && race == 2) return kernel_of<EqpDiagW<false, 4, STR>, 2, 1, (STR ? 2 : 1)>(kin);
-    if (G == 4) return mode ? kernel_of<EqpDiagW<false, 4, STR>, 2, 1>(kin) : QC_MODE0(QC_COMMA(EqpDiagW<false, 4>));
-    if (G == 2) return mode ? kernel_of<EqpDiagW<false, 2>, 2, 1>(kin) : QC_MODE0(QC_COMMA(EqpDiagW<false, 2>));
-    return mode ? kernel_of<EqpDiagW<false, 1>, 2, 1>(kin) : QC_MODE0(QC_COMMA(EqpDiagW<false, 1>));
+    if (G == 4 && race == 4) return kernel_of<EqpDiagW<false, 4>, 2, 1, 4>(kin);
+    if (G == 4 && race == 2) return kernel_of<EqpDiagW<false, 4>, 2, 1, 2>(kin);
+    if (G == 4) return kernel_of<EqpDiagW<false, 4>, 2, 1>(kin);
+    if (G == 2) return kernel_of<EqpDiagW<false, 2>, 2, 1>(kin);
+    return kernel_of<EqpDiagW<false, 1>, 2, 1>(kin);
   }
-  if (G == 4 && mode == 2 && STR && race == 4) return kernel_of<EqpDiagW<true, 4, STR>, 2, 2, (STR ? 4 : 1)>(kin);
-  if (G == 4 && mode == 2 && STR && race == 2) return kernel_of<EqpDiagW<true, 4, STR>, 2, 2, (STR ? 2 : 1)>(kin);
-  if (G == 4) return mode == 2 ? kernel_of<EqpDiagW<true, 4, STR>, 2, 2>(kin) : (mode ? kernel_of<EqpDiagW<true, 4, STR>, 2, 1>(kin) : QC_MODE0(QC_COMMA(EqpDiagW<true, 4>)));
-  if (G == 2) return mode ? kernel_of<EqpDiagW<true, 2>, 2, 1>(kin) : QC_MODE0(QC_COMMA(EqpDiagW<true, 2>));
-  return mode ? kernel_of<EqpDiagW<true, 1>, 2, 1>(kin) : QC_MODE0(QC_COMMA(EqpDiagW<true, 1>));
-#undef QC_MODE0
-#undef QC_MODE0_DENSE
+  if (G == 4 && mode == 2 && race == 4) return kernel_of<EqpDiagW<true, 4>, 2, 2, 4>(kin);
+  if (G == 4 && mode == 2 && race == 2) return kernel_of<EqpDiagW<true, 4>, 2, 2, 2>(kin);
+  if (G == 4) return mode == 2 ? kernel_of<EqpDiagW<true, 4>, 2, 2>(kin) : kernel_of<EqpDiagW<true, 4>, 2, 1>(kin);
+  if (G == 2) return kernel_of<EqpDiagW<true, 2>, 2, 1>(kin);
+  return kernel_of<EqpDiagW<true, 1>, 2, 1>(kin);
 #endif  // QC_DEV_ONLY_DENSE1
 }
 typedef void (*qc_pair_kernel_fn)(const qc::DevParams*, long, qc::BatchIn, const uint32_t*, qc::BatchOut, int, int, int, unsigned);
@@ -2160,10 +2046,9 @@ static qc_pair_kernel_fn pair_kernel_for(int form) {
 static size_t lds_for(int form, int G, int mode, bool kin = false) {
   if (mode == 3) return 0;  // (static LDS: Rwb rows, record list, two counters)
   if (kin && G == 1 && mode == 1 && form != QC_FORM_DENSE) return (size_t)qc::qpark_doubles() * sizeof(double);  // (balance_kernel: QPARK)
-
-  const size_t stock = (size_t)qc::stock_doubles(qc::stock_slots(G, mode)) * sizeof(double);
-  if (form == QC_FORM_DENSE && G != 4 && mode != 0) return (size_t)78 * 64 * sizeof(double);  // the Hessian planes alone (balance_kernel: HESS_ONLY)
-  if (form == QC_FORM_DENSE) return stock + (G == 4 ? (size_t)qc::EqpDense4::X_DOUBLES : (size_t)78 * 64) * sizeof(double);
+  if (form == QC_FORM_DENSE && G != 4) return (size_t)78 * 64 * sizeof(double);  // the Hessian planes alone (balance_kernel: HESS_ONLY)
+  const size_t stock = (size_t)qc::stock_doubles(qc::stock_slots(G)) * sizeof(double);
+  if (form == QC_FORM_DENSE) return stock + (size_t)qc::EqpDense4::X_DOUBLES * sizeof(double);
   return stock;
 }
 // workgroups of this kernel the device holds at once (registers, LDS and the 32-waves-per-CU cap, as the runtime sees them)
@@ -2188,7 +2073,7 @@ struct qc_launch_plan {
   size_t lds;
   unsigned blocks;
   long chunk;
-  int refill_t, G, mode, race;
+  int G, mode, race;
   long resident;
 };
 
@@ -2196,33 +2081,30 @@ static int plan_launch(qc_handle* h, long n, bool kin, bool warm, qc_launch_plan
   const int form = !h->diag_w ? QC_FORM_DENSE : (h->uniform ? QC_FORM_UNIFORM : QC_FORM_GENERAL);
   int G = 1;
   const long simds = (long)h->cus * 4;
-  const long cap4 = resident_workgroups(h, (const void*)kernel_for(form, 4, 1, kin, h->min_waves), lds_for(form, 4, 1, kin)) * 16;
+  const long cap4 = resident_workgroups(h, (const void*)kernel_for(form, 4, 1, kin), lds_for(form, 4, 1, kin)) * 16;
   if (form != QC_FORM_DENSE) {
     G = n <= 16 * simds ? 4 : (n <= 32 * simds ? 2 : 1);
     if (h->group_override) G = h->group_override;
   } else {
-    // dense form: four lanes per robot (one-fill workgroups only) while the batch fits the resident waves - the
-    // latency regime; one lane per robot with the LDS-staged Hessian above that
+    // dense form: four lanes per robot while the batch fits the resident waves - the latency regime; one lane per robot
+    // with the LDS-staged Hessian above that
     G = n <= cap4 ? 4 : 1;
     if (h->group_override) G = h->group_override == 4 ? 4 : 1;
-    if (QC_PERSISTENT_6X6 && G == 4 && (h->one_fill_override == 0 || h->chunk_override > 16)) G = 1;
     // a chunk of 17 ... 64 robots is more than a four-lane wave holds and exactly what a one-lane one-fill wave does (ADVICE r5:
     // rounds 2-4 served such a request on the one-lane kernel; it must not become an error because the four-lane one would have been picked)
     if (!h->group_override && G == 4 && h->chunk_override > 16 && h->chunk_override <= 64) G = 1;
   }
   lp->pfn = nullptr;
   lp->p_th = lp->p_refill = 0;
-  // A request this build cannot honour is an error, not a silent fall-back to one-fill workgroups: the persistent (mode 0)
-  // kernels - of the 6x6 forms and, since round 5, of the one-lane dense form too - exist only in -DQC_PERSISTENT_6X6=1 builds.
-  if (!QC_PERSISTENT_6X6 && (h->one_fill_override == 0 || h->chunk_override > 64 / G))
-    return fail(QC_ERR_INVALID, "qc_set_tuning: one_fill = 0 / a chunk beyond one fill asks for a persistent-wave kernel, which this "
-                                "build does not contain (compile with -DQC_PERSISTENT_6X6=1)");
+  // A request the kernels cannot honour is an error, not a silent change of the launch: a wave holds one fill.
+  if (h->chunk_override > 64 / G)
+    return fail(QC_ERR_INVALID, "qc_set_tuning: a chunk beyond one fill (64 / lanes per robot) asks for more robots than a wave holds");
   // MODE 3 (paired waves): 6x6 forms, one lane per robot, batches of at least four rounds of one-fill workgroups (524 288
   // robots): measured -5 % there and nothing below (profiles/r03_paired_waves.log) - with few rounds the consumer of two
   // waves' stragglers is mostly a longer chain at the end of the launch.  (Not the joint_q variants: they always run as
   // one-fill workgroups.)
-  if (form != QC_FORM_DENSE && G == 1 && !kin && h->chunk_override <= 0 && h->one_fill_override != 0) {
-    const long res1 = resident_workgroups(h, (const void*)kernel_for(form, 1, 1, kin, h->min_waves), lds_for(form, 1, 1, kin));
+  if (form != QC_FORM_DENSE && G == 1 && !kin && h->chunk_override <= 0) {
+    const long res1 = resident_workgroups(h, (const void*)kernel_for(form, 1, 1, kin), lds_for(form, 1, 1, kin));
     bool use_pair = n >= 4 * res1 * 64;
     if (h->pair_override >= 0) use_pair = h->pair_override != 0;
     if (use_pair) {
@@ -2231,7 +2113,6 @@ static int plan_launch(qc_handle* h, long n, bool kin, bool warm, qc_launch_plan
       lp->lds = 0;
       lp->blocks = (unsigned)((n + 127) / 128);
       lp->chunk = 128;
-      lp->refill_t = 0;
       lp->G = 1;
       lp->mode = 3;
       lp->race = 1;
@@ -2244,54 +2125,28 @@ static int plan_launch(qc_handle* h, long n, bool kin, bool warm, qc_launch_plan
     }
   }
   const long rpw = 64 / G;  // robots per wave fill
-  const bool can_one_fill = true;
-  bool one_fill = false;
-  long resident = 0;
-  if (can_one_fill) {
-    resident = resident_workgroups(h, (const void*)kernel_for(form, G, 1, kin, h->min_waves), lds_for(form, G, 1, kin));
-    // (round 5: the one-lane dense kernel too - with the Hessian planes as its only LDS it is resident once per SIMD and, as
-    // one-fill workgroups, beats its persistent form at every size: 65 536 robots 138 vs 172 us, 262 144 317 vs 415,
-    // profiles/r05_dense_sizes.log)
-    const double rounds = warm ? h->rounds_warm : h->rounds_cold;
-    one_fill = (double)n <= rounds * (double)(resident * rpw);
-    // The joint_q / joint_tau variants carry the kinematics through the persistent loop and spill 400-700 B per
-    // lane there; as one-fill workgroups they stay at <= 68 B and win at every size.
-    if (kin) one_fill = true;
-    if (h->one_fill_override >= 0) one_fill = h->one_fill_override != 0;
-    if (h->chunk_override > 0) one_fill = h->chunk_override <= rpw;
-    if (form == QC_FORM_DENSE && G == 4) one_fill = true;
-    if (!QC_PERSISTENT_6X6) one_fill = true;  // (the persistent kernels are not in this build)
+  const long resident = resident_workgroups(h, (const void*)kernel_for(form, G, 1, kin), lds_for(form, G, 1, kin));
+  long chunk = h->chunk_override > 0 ? h->chunk_override : rpw;
+  const long blocks = (n + chunk - 1) / chunk;
+  // one wave per SIMD is enough: the recalculation's constants stay resident in VGPRs (uniform G = 4 form)
+  const int mode = (form == QC_FORM_UNIFORM && G == 4 && blocks <= (long)h->cus * 4) ? 2 : 1;
+  // ... and when even that leaves SIMDs idle the 4-lane kernels (all three forms) race pivoting strategies on the
+  // same robot (Lane: RACE): four per robot up to CUs x 4 x 4 robots (4 096)
+  int race = 1;
+  if (G == 4 && h->chunk_override <= 0 && (mode == 2 || form != QC_FORM_UNIFORM)) {
+    // (a 2-way race up to 8 192 robots is built and selectable - qc_set_tuning("race", 2) - but measured neutral on
+    // average: its two fewer recalculations pay for the heavier body, tools/race_scan.py)
+    // (cold batches: a warm-started one has little chain to shorten - 10-17 us either way, 0.2-0.6 us dearer with the race,
+    // tools/warm_race_scan.py)
+    race = (!warm && n <= 4 * simds) ? 4 : 1;
+    if (h->race_override >= 0) race = (h->race_override == 4 && n <= 4 * simds) ? 4 : ((h->race_override >= 2 && n <= 8 * simds) ? 2 : 1);
+    chunk = 16 / race;
   }
-  int mode = 0, race = 1;
-  long chunk;
-  if (one_fill) {
-    chunk = (h->chunk_override > 0 && h->chunk_override <= rpw) ? h->chunk_override : rpw;
-    const long blocks = (n + chunk - 1) / chunk;
-    // one wave per SIMD is enough: the recalculation's constants stay resident in VGPRs (uniform G = 4 form)
-    mode = (form == QC_FORM_UNIFORM && G == 4 && blocks <= (long)h->cus * 4) ? 2 : 1;
-    // ... and when even that leaves SIMDs idle the 4-lane kernels (all three forms) race pivoting strategies on the
-    // same robot (Lane: RACE): four per robot up to CUs x 4 x 4 robots (4 096)
-    if (G == 4 && !QC_NO_STRIDED && h->chunk_override <= 0 && (mode == 2 || form != QC_FORM_UNIFORM)) {
-      // (a 2-way race up to 8 192 robots is built and selectable - qc_set_tuning("race", 2) - but measured neutral on
-      // average: its two fewer recalculations pay for the heavier body, tools/race_scan.py)
-      // (cold batches: a warm-started one has little chain to shorten - 10-17 us either way, 0.2-0.6 us dearer with the race,
-      // tools/warm_race_scan.py)
-      race = (!warm && n <= 4 * simds) ? 4 : 1;
-      if (h->race_override >= 0) race = (h->race_override == 4 && n <= 4 * simds) ? 4 : ((h->race_override >= 2 && n <= 8 * simds) ? 2 : 1);
-      chunk = 16 / race;
-    }
-  } else {
-    resident = resident_workgroups(h, (const void*)kernel_for(form, G, 0, kin), lds_for(form, G, 0));
-    chunk = rpw;
-    if (n > rpw * resident) chunk = ((n + resident - 1) / resident + 15) / 16 * 16;
-    if (h->chunk_override > 0) chunk = h->chunk_override;
-  }
-  lp->fn = kernel_for(form, G, mode, kin, h->min_waves, race);
+  lp->fn = kernel_for(form, G, mode, kin, race);
   lp->race = race;
   lp->lds = lds_for(form, G, mode, kin);
   lp->blocks = (unsigned)((n + chunk - 1) / chunk);
   lp->chunk = chunk;
-  lp->refill_t = h->refill_t > 0 ? (h->refill_t + G - 1) / G : 1;
   lp->G = G;
   lp->mode = mode;
   lp->resident = resident;
@@ -2514,14 +2369,9 @@ int qc_create_abi(const qc_params* p, int device, qc_handle** out, int abi_versi
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) != hipSuccess) { delete h; return fail(QC_ERR_HIP, "qc_create: hipGetDeviceProperties failed"); }
   h->cus = prop.multiProcessorCount;
-  h->refill_t = 16;
-  h->rounds_cold = QC_ROUNDS_COLD;
-  h->rounds_warm = QC_ROUNDS_WARM;
   h->chunk_override = 0;
   h->group_override = 0;
-  h->one_fill_override = -1;
   h->wave_slots_override = 0;
-  h->min_waves = 2;
   h->race_override = -1;
   h->pair_override = -1;
   h->pair_th = 0;
@@ -2545,7 +2395,9 @@ int qc_set_tuning(qc_handle* h, const char* key, double value) {
     const int g = (int)value;
     if (g != 0 && g != 1 && g != 2 && g != 4) return fail(QC_ERR_INVALID, "qc_set_tuning: group is 0 (heuristic), 1, 2 or 4");
     h->group_override = g;
-  } else if (k == "one_fill") h->one_fill_override = value < 0 ? -1 : (value != 0 ? 1 : 0);
+  } else if (k == "one_fill") {  // (-1 heuristic / 1 always: every launch is one fill per wave, the key stays for existing callers)
+    if (value == 0) return fail(QC_ERR_INVALID, "qc_set_tuning: one_fill = 0 asked for the persistent-wave kernels, which were removed");
+  }
   else if (k == "chunk") h->chunk_override = value > 0 ? (long)value : 0;
   else if (k == "wave_slots") h->wave_slots_override = value > 0 ? (int)value : 0;
   else if (k == "race") {  // (0 / 1 also switch the race in the 4-lane tail of the wider kernels off)
@@ -2557,10 +2409,6 @@ int qc_set_tuning(qc_handle* h, const char* key, double value) {
   else if (k == "pair_th") h->pair_th = value > 0 ? (int)value : 0;
   else if (k == "pair_refill") h->pair_refill = value > 0 ? (int)value : 0;
   else if (k == "pair_solo") h->pair_solo = value != 0 ? 1 : 0;
-  else if (k == "min_waves") h->min_waves = value > 2 ? (int)value : 2;
-  else if (k == "refill_t") h->refill_t = value > 0 ? (int)value : 16;
-  else if (k == "rounds_cold") h->rounds_cold = value;
-  else if (k == "rounds_warm") h->rounds_warm = value;
   else if (k == "force_general" || k == "force_dense") {
     // general 6x6 form on uniform weights / dense 12x12 form on a diagonal W (same minimiser).  The form follows from what
     // qc_create was given and the two flags, in one place, whatever the order of the calls.
@@ -2653,7 +2501,7 @@ static int launch_batch(qc_handle* h, size_t n, bool kin, const qc::BatchIn& bi,
     QC_HIP(hipGetLastError());
     return QC_OK;
   }
-  lp.fn<<<dim3(lp.blocks), dim3(64), lp.lds, (hipStream_t)stream>>>(h->d_params, (long)n, bi, warm, bo, lp.chunk, lp.refill_t);
+  lp.fn<<<dim3(lp.blocks), dim3(64), lp.lds, (hipStream_t)stream>>>(h->d_params, (long)n, bi, warm, bo, lp.chunk);
   QC_HIP(hipGetLastError());
   return QC_OK;
 }

@@ -38,10 +38,6 @@
 #define QC_CLK_ABS(from, to)  // harness: a phase boundary between two absolute clock slots (the torque pass: 13 lists, 14 swing, 15 stance)
 #endif
 
-#ifndef QC_NO_STRIDED
-#define QC_NO_STRIDED 0  // development: 1 keeps the adjacent-lane (DPP) layout in the 4-lanes-per-robot kernels
-#endif
-
 namespace qc {
 
 // Uniform (per-handle) constants, uploaded once by qc_create.
@@ -81,7 +77,7 @@ struct DevParams {
 // Device code reads the constants through the CONSTANT address space (scalar
 // loads).  The kernel re-derives the pointer behind an opaque asm before each
 // phase (QC_PARAMS_HERE) so the constants are fetched where they are used
-// instead of being hoisted out of the persistent loop, which would overflow the
+// instead of being hoisted out of the recalculation loops, which would overflow the
 // 102-SGPR file and spill to VGPR lanes.
 typedef const __attribute__((address_space(4))) DevParams CParams;
 #define QC_PARAMS_HERE(ptr)                 \
@@ -164,17 +160,11 @@ struct BatchOut {
 };
 
 // ------------------------------------------------------------ lane groups
-// DPP quad permutes: data of lane^1 / lane^2 inside each aligned quad.
+// DPP quad permute: data of lane^1 inside each aligned quad.
 QC_DEV int dpp_xor1_i(int v) { return __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true); }  // quad_perm [1,0,3,2]
-QC_DEV int dpp_xor2_i(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true); }  // quad_perm [2,3,0,1]
 QC_DEV double dpp_xor1(double v) {
   const long long b = __double_as_longlong(v);
   const unsigned lo = (unsigned)dpp_xor1_i((int)(unsigned)b), hi = (unsigned)dpp_xor1_i((int)(unsigned)(b >> 32));
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-QC_DEV double dpp_xor2(double v) {
-  const long long b = __double_as_longlong(v);
-  const unsigned lo = (unsigned)dpp_xor2_i((int)(unsigned)b), hi = (unsigned)dpp_xor2_i((int)(unsigned)(b >> 32));
   return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 // min/max of values known to be non-NaN (tagged candidates, magnitudes): the bare instruction.  fmin()/fmax()
@@ -198,8 +188,8 @@ QC_DEV double max_abs_nn(double a, double b) {  // max(|a|, |b|)
 // All-reduce over the G lanes of a group.  x op y is commutative, so every
 // lane of the group ends up with the bit-identical result: decisions taken
 // from reduced values are uniform inside the group.
-// Two lane layouts: adjacent lanes (member = lane & (G-1), DPP quad permutes), and - S = true, G = 4 only - the
-// four lanes {i, i+16, i+32, i+48} (member = lane >> 4, group = lane & 15).  In the strided layout the matrix pipe
+// Two lane layouts: adjacent lanes (member = lane & (G-1), a DPP quad permute; G = 1 or 2 only), and - S = true, G = 4
+// only - the four lanes {i, i+16, i+32, i+48} (member = lane >> 4, group = lane & 15).  In the strided layout the matrix pipe
 // does the sums: v_mfma_f64_4x4x4f64 with A = 1 computes, for every lane, the sum of B over the lanes that share
 // its (lane & 15) - one instruction per reduced double instead of four DPP moves and two adds (27 doubles per
 // recalculation: 412 vs 904 cycles, tools/ubench_mfma_reduce.hip), all four lanes getting the bit-identical dot
@@ -235,67 +225,50 @@ QC_DEV double swap32_op_max(double v) {
 }
 template <int G, bool S = false>
 QC_DEV double group_sum(double v) {
-  static_assert(!S || G == 4, "the strided layout is a 4-lane layout");
+  static_assert(S ? G == 4 : G <= 2, "the strided layout is a 4-lane layout, the adjacent one a 1- or 2-lane layout");
   if constexpr (S) {
-#ifdef QC_SUM_BY_SWAPS
-    {
-      const long long b = __double_as_longlong(v);
-      const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)b, (unsigned)b, false, false);
-      const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)(b >> 32), (unsigned)(b >> 32), false, false);
-      v = __longlong_as_double((long long)(((unsigned long long)hi[0] << 32) | lo[0])) + __longlong_as_double((long long)(((unsigned long long)hi[1] << 32) | lo[1]));
-      const long long c = __double_as_longlong(v);
-      const auto lo2 = __builtin_amdgcn_permlane32_swap((unsigned)c, (unsigned)c, false, false);
-      const auto hi2 = __builtin_amdgcn_permlane32_swap((unsigned)(c >> 32), (unsigned)(c >> 32), false, false);
-      return __longlong_as_double((long long)(((unsigned long long)hi2[0] << 32) | lo2[0])) + __longlong_as_double((long long)(((unsigned long long)hi2[1] << 32) | lo2[1]));
-    }
-#endif
     return __builtin_amdgcn_mfma_f64_4x4x4f64(1.0, v, 0.0, 0, 0, 0);
   } else {
-    if (G >= 2) v += dpp_xor1(v);
-    if (G >= 4) v += dpp_xor2(v);
+    if (G == 2) v += dpp_xor1(v);
     return v;
   }
 }
 // group sum plus a group-uniform addend: in the strided layout the addend is the MFMA's C operand
 template <int G, bool S = false>
 QC_DEV double group_sum_add(double v, double addend) {
-  if constexpr (S) {
-#ifndef QC_SUM_BY_SWAPS
-    return __builtin_amdgcn_mfma_f64_4x4x4f64(1.0, v, addend, 0, 0, 0);
-#endif
-  }
-  return group_sum<G, S>(v) + addend;
+  if constexpr (S) return __builtin_amdgcn_mfma_f64_4x4x4f64(1.0, v, addend, 0, 0, 0);
+  else return group_sum<G, S>(v) + addend;
 }
 template <int G, bool S = false>
 QC_DEV double group_min(double v) {
+  static_assert(S ? G == 4 : G <= 2, "the strided layout is a 4-lane layout, the adjacent one a 1- or 2-lane layout");
   if constexpr (S) {
     return swap32_op_min(swap16_op_min(v));
   } else {
-    if (G >= 2) v = min_nn(v, dpp_xor1(v));
-    if (G >= 4) v = min_nn(v, dpp_xor2(v));
+    if (G == 2) v = min_nn(v, dpp_xor1(v));
     return v;
   }
 }
 template <int G, bool S = false>
 QC_DEV double group_max(double v) {
+  static_assert(S ? G == 4 : G <= 2, "the strided layout is a 4-lane layout, the adjacent one a 1- or 2-lane layout");
   if constexpr (S) {
     return swap32_op_max(swap16_op_max(v));
   } else {
-    if (G >= 2) v = max_nn(v, dpp_xor1(v));
-    if (G >= 4) v = max_nn(v, dpp_xor2(v));
+    if (G == 2) v = max_nn(v, dpp_xor1(v));
     return v;
   }
 }
 template <int G, bool S = false>
 QC_DEV int group_or(int v) {
+  static_assert(S ? G == 4 : G <= 2, "the strided layout is a 4-lane layout, the adjacent one a 1- or 2-lane layout");
   if constexpr (S) {
     const auto a = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
     const unsigned w = a[0] | a[1];
     const auto c = __builtin_amdgcn_permlane32_swap(w, w, false, false);
     return (int)(c[0] | c[1]);
   } else {
-    if (G >= 2) v |= dpp_xor1_i(v);
-    if (G >= 4) v |= dpp_xor2_i(v);
+    if (G == 2) v |= dpp_xor1_i(v);
     return v;
   }
 }
@@ -1227,11 +1200,11 @@ QC_DEV bool eqp_diagw(const PT& P, const FootW (&lane_w)[4 / G], const Wrench<4 
   return ok;
 }
 
-template <bool UNIFORM, int GROUP, bool STRIDED = false>
+template <bool UNIFORM, int GROUP>
 struct EqpDiagW {
   static constexpr int G = GROUP;
   static constexpr bool kHessianInLds = false;
-  static constexpr bool kStrided = STRIDED;  // lane layout of the group, see group_sum
+  static constexpr bool kStrided = GROUP == 4;  // lane layout of the group, see group_sum
   static constexpr bool kUniform = UNIFORM;
   static constexpr bool kRepackTail = GROUP <= 2;  // one-fill waves finish their stragglers 4 lanes per robot
   static constexpr bool kNegB = true;  // the lane keeps -b (what the right-hand side adds), not b: no negation per recalculation
@@ -1250,7 +1223,7 @@ struct EqpDiagW {
   template <class PT>
   QC_DEV bool solve(const PT& P, const Wrench<4 / GROUP>& Wr, const Cube<4 / GROUP>& C, uint32_t stance, int foot0, double (&f)[12 / GROUP],
                     double (&g)[12 / GROUP]) {
-    return eqp_diagw<UNIFORM, GROUP, STRIDED>(P, lane_w, Wr, C, stance, foot0, f, g, gscale);
+    return eqp_diagw<UNIFORM, GROUP, kStrided>(P, lane_w, Wr, C, stance, foot0, f, g, gscale);
   }
 };
 

@@ -11,7 +11,7 @@ import torch
 LIB_PATH = os.environ.get("QC_DEVICE_PROBE_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "hip", "libqc_device_probe.so")  # (the env: development builds)
 LAUNCHERS = ("qcp_set_params", "qcp_sincos", "qcp_rsqrt_rcp", "qcp_angle_axis", "qcp_wraps", "qcp_leg", "qcp_pinv3", "qcp_swing_torque",
              "qcp_swing_pd", "qcp_track_swing", "qcp_ldlt6", "qcp_ldlt12", "qcp_tag", "qcp_group")
-GROUP_VARIANTS = {(2, False): 0, (4, False): 1, (4, True): 2}
+GROUP_VARIANTS = {(2, False): 0, (4, True): 2}
 
 _lib = None
 

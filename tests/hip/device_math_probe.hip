@@ -204,12 +204,11 @@ hipError_t qcp_tag(const double* v, const int* code, const int* free_face, const
                    double* cand, int n, hipStream_t st) {
   return launch(k_tag, n, st, v, code, free_face, slack, nd, tagged, code_back, cand);
 }
-// variant 0: (G, S) = (2, false), 1: (4, false), 2: (4, true)
+// variant 0: (G, S) = (2, false), 2: (4, true): the two lane layouts of the kernels
 hipError_t qcp_group(int variant, const double* v, const double* addend, const int* bits, double* out, int n, hipStream_t st) {
   if (n % kBlock != 0) return hipErrorInvalidValue;
   switch (variant) {
     case 0: return launch(k_group<2, false>, n, st, v, addend, bits, out);
-    case 1: return launch(k_group<4, false>, n, st, v, addend, bits, out);
     case 2: return launch(k_group<4, true>, n, st, v, addend, bits, out);
     default: return hipErrorInvalidValue;
   }

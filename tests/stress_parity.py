@@ -1,5 +1,6 @@
-"""One-off stress check: all kernel forms agree with each other on N robots (default 1,048,576: persistent waves;
-16,384 / 65,536 exercise the one-fill kernel modes) and with the C oracle on a subset of up to 65,536.
+"""One-off stress check: all kernel forms agree with each other on N robots (default 1,048,576: many rounds of workgroups,
+paired waves on the 6x6 forms; 16,384 / 65,536 exercise the narrower one-fill layouts) and with the C oracle on a subset of
+up to 65,536.
 usage: python tests/stress_parity.py [N]"""
 import os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))

@@ -1,7 +1,7 @@
 """-m gpu: oracle parity over EVERY kernel instantiation the launch planner can pick.
 
 The planner (plan_launch, qc_balance.hip) chooses by formulation (uniform 6x6 / general 6x6 / dense 12x12),
-lanes per robot (1 / 2 / 4) and kernel mode (0 persistent waves with lane refill, 1 one fill per wave, 2 one fill
+lanes per robot (1 / 2 / 4) and kernel mode (1 one fill per wave, 2 one fill
 with register-resident constants, 3 paired waves: two one-lane waves per workgroup, the last to arrive finishes both
 waves' stragglers from a list in LDS).  Each test forces one branch with qc_set_tuning, checks through qc_query_launch
 that this branch is the one that runs, and compares with the C oracle on config-3 inputs (mixed 2/3/4-foot contact
@@ -18,22 +18,12 @@ RTOL = 1e-6  # of max|GRF| per robot; north_star's bar is 1e-4
 FORMS = {"uniform": {}, "general": {"force_general": 1}, "dense": {"force_dense": 1}}
 FORM_ID = {"uniform": 0, "general": 1, "dense": 2}
 # (form, lanes per robot, mode) -> (tuning, robots): every branch of kernel_for()
-import os
-
-# The persistent-wave (mode 0) kernels exist in development builds only (-DQC_PERSISTENT_6X6=1; no default handle can launch
-# one - 6x6 forms since round 2, the one-lane dense form since round 5): QC_TEST_PERSISTENT_6X6=1 adds their rows when such a
-# build is under test.
-PERSISTENT_6X6 = os.environ.get("QC_TEST_PERSISTENT_6X6") == "1"
 CASES = []
 for form in ("uniform", "general"):
     CASES += [(form, 1, 1, dict(group=1, one_fill=1), 8200),  # ragged: the last wave holds 8 robots
               (form, 2, 1, dict(group=2, one_fill=1), 8200),  # ragged: the last wave holds 8 robots
               (form, 4, 1, dict(group=4, one_fill=1, race=0), 20480 if form == "uniform" else 8192)]
     CASES += [(form, 1, 3, dict(group=1, pair=1), 8200 + 64 + 13)]  # paired waves: 65 workgroups, the last one with a ragged second wave
-    if PERSISTENT_6X6:
-        CASES += [(form, 1, 0, dict(group=1, chunk=256), 8192), (form, 2, 0, dict(group=2, chunk=256), 8192), (form, 4, 0, dict(group=4, chunk=128), 8192)]
-if PERSISTENT_6X6:
-    CASES += [("dense", 1, 0, dict(group=1, chunk=256), 8192)]
 CASES += [("uniform", 4, 2, dict(group=4, one_fill=1, race=0), 8192),
           ("dense", 1, 1, dict(group=1, one_fill=1), 8200),  # ragged; the Hessian planes are the workgroup's only LDS (output stock aliased)
           ("dense", 4, 1, dict(group=4, race=0), 8192)]
@@ -94,8 +84,6 @@ def test_kernel_instantiation_vs_oracle(q, form, G, mode, tune, n, start):
     ctl = _controller(q, P, form, tune)
     info = ctl.query_launch(n, warm=(start == "warm"))
     assert (info["form"], info["lanes_per_robot"], info["mode"]) == (FORM_ID[form], G, mode), info
-    if mode == 0:
-        assert info["chunk"] > 64 // G  # persistent waves really refill
     d = q.to_device(b)
     warm = None
     if start == "warm":
@@ -126,9 +114,8 @@ def test_kernel_instantiation_vs_oracle(q, form, G, mode, tune, n, start):
         assert _relerr(again["grf_body"].cpu().numpy(), ref) < RTOL
 
 
-# every one-fill branch, every G > 1 branch, both dense widths (the one-lane persistent 6x6 kernels with joint_q spill
-# 532 B per lane and are never planned: kin batches always run as one-fill workgroups)
-KIN_CASES = [c for c in CASES if not (c[0] != "dense" and c[1] == 1 and c[2] == 0) and c[2] != 3]  # (mode 3 has no joint_q variant)
+# every one-fill branch, both dense widths
+KIN_CASES = [c for c in CASES if c[2] != 3]  # (mode 3 has no joint_q variant)
 
 
 @pytest.mark.parametrize("form,G,mode,tune,n", KIN_CASES, ids=[f"kin-{f}-G{g}-mode{m}" for f, g, m, _, _ in KIN_CASES])
@@ -140,7 +127,7 @@ def test_kin_instantiation_vs_oracle(q, form, G, mode, tune, n):
     n = min(n, 8192) if not (form == "uniform" and G == 4 and mode == 1) else n
     P = q.cheetah_params(0.6)
     b = W.with_joint_angles(W.config3(n, seed=0x5EED00A4))
-    ctl = _controller(q, P, form, dict(tune, one_fill=0) if mode == 0 else tune)
+    ctl = _controller(q, P, form, tune)
     info = ctl.query_launch(n, kin=True)
     assert (info["form"], info["lanes_per_robot"], info["mode"]) == (FORM_ID[form], G, mode), info
     o = ctl.control_batch_host(b, want_torques=True)

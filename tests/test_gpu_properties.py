@@ -548,7 +548,7 @@ def test_nearly_straight_knee_inverts_like_the_reference(q):
             assert np.abs(rt[sw & (theta < 1e-6)]).max() > 1e6 and np.abs(tau[sw & (theta < 1e-6)]).max() > 1e6  # the inverse, not a rank-2 pseudo-inverse
 
 
-@pytest.mark.parametrize("n", [600, 36000, 140000])  # G = 4; G = 2 single fill; G = 2 persistent waves (dense restock)
+@pytest.mark.parametrize("n", [600, 36000, 140000])  # G = 4; wider layouts, one round of one-fill workgroups and several
 def test_on_device_swing_planning_multi_tick(q, n):
     """SURVEY 8f rank 4, stateful half: foothold planner + sextic swing trajectories kept in a
     per-robot state buffer across ticks; torques and the carried state track the oracle tick by tick."""
@@ -1025,6 +1025,14 @@ def test_tuning_overrides_restore_what_the_handle_was_created_with(q):
     assert ctl.query_launch(4096)["form"] == 2
     ctl.set_tuning(force_dense=0)
     assert ctl.query_launch(4096)["form"] == 0
+    # the persistent-wave kernels are gone: one_fill = 0 and their keys are refused, one_fill = 1 (every launch) changes nothing
+    with pytest.raises(ValueError, match="one_fill"):
+        ctl.set_tuning(one_fill=0)
+    with pytest.raises(ValueError, match="unknown key"):
+        ctl.set_tuning(refill_t=16)
+    for n in (4096, 40000, 600000):
+        before = ctl.query_launch(n)
+        assert ctl.set_tuning(one_fill=1).query_launch(n) == before
 
 
 def test_paired_waves_kernel_full_size(q):

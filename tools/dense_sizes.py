@@ -1,4 +1,4 @@
-"""Round 5: the one-lane dense 12x12 kernel (general SPD W, `force_dense`) as one-fill workgroups vs persistent waves over batch sizes,
+"""Round 5: the one-lane dense 12x12 kernel (general SPD W, `force_dense`) as one-fill workgroups over batch sizes,
 with the resident workgroups the occupancy query reports (the LDS diet: 58 KB -> 39 KB per workgroup = 2 -> 4 per CU).
 usage: python tools/dense_sizes.py [sizes...]"""
 import os, sys
@@ -22,7 +22,7 @@ sizes = [int(a) for a in sys.argv[1:]] or [4096, 16384, 32768, 65536, 131072, 26
 for n in sizes:
     b = WD.config3(n, start=0, seed=W.SEEDS[3], device=0)
     ref = None
-    for tune in (dict(), dict(force_dense=1), dict(force_dense=1, group=1, one_fill=1), dict(force_dense=1, group=1, one_fill=0), dict(force_dense=1, group=4)):
+    for tune in (dict(), dict(force_dense=1), dict(force_dense=1, group=1, one_fill=1), dict(force_dense=1, group=4)):
         ctl = q.BalanceController.from_params(P).set_tuning(**tune)
         try:
             info = ctl.query_launch(n)

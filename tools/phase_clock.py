@@ -1,5 +1,5 @@
 """Development tool: where the cycles of one wave go (needs tools/_build/libqc_balance_clk.so, see phase_clock.hip).
-usage: python tools/phase_clock.py [n=4096] [config=2] [lanes per robot=4] [persistent=0] [key=value ...]"""
+usage: python tools/phase_clock.py [n=4096] [config=2] [lanes per robot=4] [key=value ...]"""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 import numpy as np, torch
@@ -10,12 +10,10 @@ from quadruped_control_amd import workloads as W
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 cfg = int(sys.argv[2]) if len(sys.argv) > 2 else 2
-# markers bracket the recalculation in the persistent loop (mode 0) and in the strided one-fill loops (G = 4, modes 1 / 2);
-# argv[3] = lanes per robot, argv[4] = 1 forces the persistent kernel
+# markers bracket the recalculation in the one-fill loops (strided at G = 4, modes 1 / 2) and in the 4-lane tail;
+# argv[3] = lanes per robot
 tune = dict(group=int(sys.argv[3]) if len(sys.argv) > 3 else 4)
-if len(sys.argv) > 4 and sys.argv[4] == "1":
-    tune["one_fill"] = 0  # (6x6 forms: needs a -DQC_PERSISTENT_6X6=1 build of the clock library, otherwise the launch is refused)
-for kv in sys.argv[5:]:  # further tuning keys, e.g. race=0
+for kv in sys.argv[4:]:  # further tuning keys, e.g. race=0
     k, v = kv.split("=")
     tune[k] = float(v)
 ctl = q.BalanceController.from_params(q.cheetah_params(0.6)).set_tuning(**tune)

@@ -19,13 +19,8 @@ def timeit(ctl, b, warm, reps=20):
     for _ in range(reps): launch()
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / reps * 1e3
-for name, tune in (("mode1 G1", dict(group=1, one_fill=1)), ("mode1 G2", dict(group=2, one_fill=1)), ("mode0 G2", dict(group=2, one_fill=0)), ("mode1 G4", dict(group=4, one_fill=1)), ("mode0 G1", dict(group=1, one_fill=0))):
+for name, tune in (("mode1 G1", dict(group=1, one_fill=1)), ("mode1 G2", dict(group=2, one_fill=1)), ("mode1 G4", dict(group=4, one_fill=1))):
     row = []
-    try:  # persistent (mode 0) kernels of the 6x6 forms exist only in -DQC_PERSISTENT_6X6=1 builds: asking for one is an error since round 4
-        q.BalanceController.from_params(P).set_tuning(**tune).query_launch(n, warm=True)
-    except RuntimeError as e:
-        print("%-9s n/a in this build (%s)" % (name, str(e).split(":")[-1].strip()[:80]), flush=True)
-        continue
     for cap in (0, 1, 2, 200):
         ctl = q.BalanceController.from_params(P).set_tuning(**tune)
         if cap == 0: ctl.set_tuning(probe_batch_load=1)

@@ -17,8 +17,7 @@ def timeit(ctl, b, warm, reps):
     e1.record(); torch.cuda.synchronize()
     assert int((out["status"] != 0).sum()) == 0
     return e0.elapsed_time(e1) / reps * 1e3
-VAR = [("auto", dict()), ("G4 1fill", dict(group=4, one_fill=1)), ("G2 1fill", dict(group=2, one_fill=1)), ("G1 1fill", dict(group=1, one_fill=1)),
-       ("G2 pers", dict(group=2, one_fill=0)), ("G1 pers", dict(group=1, one_fill=0))]
+VAR = [("auto", dict()), ("G4 1fill", dict(group=4, one_fill=1)), ("G2 1fill", dict(group=2, one_fill=1)), ("G1 1fill", dict(group=1, one_fill=1))]
 print("%9s " % "n" + " ".join("%9s" % v[0] for v in VAR))
 for n in (4096, 8192, 16384, 24576, 32768, 49152, 65536, 98304, 131072, 196608, 262144, 524288, 1048576, 2097152):
     if warm_mode:
@@ -30,9 +29,6 @@ for n in (4096, 8192, 16384, 24576, 32768, 49152, 65536, 98304, 131072, 196608, 
     row = []
     for name, tune in VAR:
         if name == "G4 1fill" and n > 262144: row.append(float("nan")); continue
-        try:
-            row.append(timeit(q.BalanceController.from_params(P).set_tuning(**tune), b, w, 20 if n <= 262144 else 6))
-        except RuntimeError:  # "pers" columns need a -DQC_PERSISTENT_6X6=1 build (an error, not a silent one-fill run, since round 4)
-            row.append(float("nan"))
+        row.append(timeit(q.BalanceController.from_params(P).set_tuning(**tune), b, w, 20 if n <= 262144 else 6))
     best = int(np.nanargmin(row[1:])) + 1
     print("%9d " % n + " ".join("%9.1f" % v for v in row) + "   best: " + VAR[best][0], flush=True)
