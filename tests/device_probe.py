@@ -10,7 +10,7 @@ import torch
 
 LIB_PATH = os.environ.get("QC_DEVICE_PROBE_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "hip", "libqc_device_probe.so")  # (the env: development builds)
 LAUNCHERS = ("qcp_set_params", "qcp_sincos", "qcp_rsqrt_rcp", "qcp_angle_axis", "qcp_wraps", "qcp_leg", "qcp_pinv3", "qcp_swing_torque",
-             "qcp_swing_pd", "qcp_track_swing", "qcp_ldlt6", "qcp_ldlt12", "qcp_tag", "qcp_group")
+             "qcp_swing_pd", "qcp_track_swing", "qcp_wrench", "qcp_foothold", "qcp_ldlt6", "qcp_ldlt12", "qcp_tag", "qcp_group")
 GROUP_VARIANTS = {(2, False): 0, (4, True): 2}
 
 _lib = None
@@ -48,12 +48,18 @@ def _host(t):
     return t.cpu().numpy()
 
 
-def set_params(hip, links, jc_kff, jc_kp, jc_kd, traj_basis, t_swing, t_stance, swing_height):
-    arrs = [np.ascontiguousarray(a, np.float64) for a in (hip, links, jc_kff, jc_kp, jc_kd, traj_basis)]
-    for a, n in zip(arrs, (12, 12, 3, 3, 3, 21)):
+def set_params(hip, links, jc_kff, jc_kp, jc_kd, traj_basis, t_swing, t_stance, swing_height, wrench=None):
+    """`wrench`: dict(kp_p, kd_p, kp_w, kd_w [3], kff [6], mass, Ib [3, 3], planner_hip [12], planner_k) - what wrench_from_state
+    and plan_foothold read; zeros when not given."""
+    w = wrench or {}
+    gains = np.concatenate([np.asarray(w.get(k, np.zeros(3)), np.float64).reshape(3) for k in ("kp_p", "kd_p", "kp_w", "kd_w")])
+    extra = (gains, w.get("kff", np.zeros(6)), w.get("Ib", np.zeros(9)), w.get("planner_hip", np.zeros(12)))
+    arrs = [np.ascontiguousarray(a, np.float64).reshape(-1) for a in (hip, links, jc_kff, jc_kp, jc_kd, traj_basis) + extra]
+    for a, n in zip(arrs, (12, 12, 3, 3, 3, 21, 12, 6, 9, 12)):
         assert a.size == n, (a.size, n)
-    ptrs = [a.ctypes.data_as(C.c_void_p) for a in arrs]
-    _call("qcp_set_params", *ptrs, C.c_double(t_swing), C.c_double(t_stance), C.c_double(swing_height))
+    p = [a.ctypes.data_as(C.c_void_p) for a in arrs]
+    _call("qcp_set_params", *p[:6], C.c_double(t_swing), C.c_double(t_stance), C.c_double(swing_height), p[6], p[7],
+          C.c_double(float(w.get("mass", 0.0))), p[8], p[9], C.c_double(float(w.get("planner_k", 0.0))))
 
 
 def sincos(x):
@@ -119,6 +125,29 @@ def track_swing(phase, p0, pf):
     pos, vel = _empty((n, 3)), _empty((n, 3))
     _call("qcp_track_swing", phase, p0, pf, pos, vel, C.c_int(n))
     return _host(pos), _host(vel)
+
+
+STATE_ORDER = ("Rwb", "Rwb_d", "x", "x_d", "xdot", "xdot_d", "w", "w_d")
+
+
+def wrench(state, feet_or_q, kin):
+    """wrench_from_state<4, kin> -> b [n, 6], r [n, 4, 3], the finiteness value [n]; state: dict of [n, ...] arrays"""
+    n = np.asarray(state["x"]).reshape(-1, 3).shape[0]
+    st = np.concatenate([np.asarray(state[k], np.float64).reshape(n, -1) for k in STATE_ORDER], 1)
+    assert st.shape == (n, 36)
+    st = _dev(st, np.float64); fp = _dev(np.reshape(feet_or_q, (n, 12)), np.float64); out = _empty((n, 19))
+    _call("qcp_wrench", C.c_int(1 if kin else 0), st, fp, out, C.c_int(n))
+    o = _host(out)
+    return o[:, :6], o[:, 6:18].reshape(n, 4, 3), o[:, 18]
+
+
+def foothold(legs, Rwb, x, xdot, w, xdot_d, pc):
+    legs = _dev(legs, np.int32); n = legs.numel()
+    a = np.concatenate([np.asarray(v, np.float64).reshape(n, -1) for v in (Rwb, x, xdot, w, xdot_d, pc)], 1)
+    assert a.shape == (n, 24)
+    a = _dev(a, np.float64); fh = _empty((n, 3))
+    _call("qcp_foothold", legs, a, fh, C.c_int(n))
+    return _host(fh)
 
 
 def ldlt(Mpacked, b):

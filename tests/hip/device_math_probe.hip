@@ -109,6 +109,41 @@ __global__ void k_track_swing(const double* phase, const double* p0, const doubl
   track_swing(params(), phase[i], a, b, ps, vl);
   for (int k = 0; k < 3; k++) { pos[3 * i + k] = ps[k]; vel[3 * i + k] = vl[k]; }
 }
+// wrench_from_state<4, KIN> of one robot per thread: st[36 i ..] = Rwb[9] Rwb_d[9] x x_d xdot xdot_d w w_d, fp[12 i ..] = body-frame feet
+// (KIN = false) or joint angles (KIN = true).  out[19 i ..]: b[6], r[4][3], the returned finiteness value.
+template <bool KIN>
+__global__ void k_wrench(const double* st, const double* fp, double* out, int n) {
+  const int i = tid();
+  if (i >= n) return;
+  const double* s = st + 36 * (long)i;
+  RawState S;
+  for (int k = 0; k < 9; k++) { S.R[k] = s[k]; S.Rd[k] = s[9 + k]; }
+  for (int k = 0; k < 3; k++) {
+    S.x[k] = s[18 + k]; S.xd[k] = s[21 + k]; S.xdot[k] = s[24 + k]; S.xdotd[k] = s[27 + k]; S.w[k] = s[30 + k]; S.wd[k] = s[33 + k];
+  }
+  double f[12];
+  for (int k = 0; k < 12; k++) f[k] = fp[12 * (long)i + k];
+  Wrench<4> W;
+  const double fin = wrench_from_state<4, KIN>(params(), S, f, 0, W);
+  double* o = out + 19 * (long)i;
+  for (int k = 0; k < 6; k++) o[k] = W.b[k];
+  for (int j = 0; j < 4; j++)
+    for (int k = 0; k < 3; k++) o[6 + 3 * j + k] = W.r[j][k];
+  o[18] = fin;
+}
+// plan_foothold of one leg per thread: in[24 i ..] = Rwb[9] x xdot w xdot_d pc (pc = Rwb foot_body, the lever arm)
+__global__ void k_foothold(const int* leg, const double* in, double* fh, int n) {
+  const int i = tid();
+  if (i >= n) return;
+  const int l = leg[i];
+  if (l < 0 || l > 3) return;
+  const double* s = in + 24 * (long)i;
+  double R[9], x[3], xdot[3], w[3], xdd[3], pc[3], o[3];
+  for (int k = 0; k < 9; k++) R[k] = s[k];
+  for (int k = 0; k < 3; k++) { x[k] = s[9 + k]; xdot[k] = s[12 + k]; w[k] = s[15 + k]; xdd[k] = s[18 + k]; pc[k] = s[21 + k]; }
+  plan_foothold(params(), l, R, x, xdot, w, xdd, pc, o);
+  for (int k = 0; k < 3; k++) fh[3 * (long)i + k] = o[k];
+}
 // M: packed lower triangles (index r (r + 1) / 2 + c), x: right-hand sides in, solutions out
 template <int N>
 __global__ void k_ldlt(const double* M, double* x, int* ok, int n) {
@@ -161,9 +196,11 @@ hipError_t launch(K kernel, int n, hipStream_t st, A... args) {
 
 extern "C" {
 
-// The constants of the kinematic primitives, from flat arrays; every other field of DevParams stays zero.
+// The constants of the kinematic primitives and of the wrench assembly / foothold planner, from flat arrays (gains[12] = kp_p kd_p
+// kp_w kd_w); every other field of DevParams stays zero.
 hipError_t qcp_set_params(const double* hip, const double* links, const double* jc_kff, const double* jc_kp, const double* jc_kd,
-                          const double* traj_basis, double t_swing, double t_stance, double swing_height, hipStream_t st) {
+                          const double* traj_basis, double t_swing, double t_stance, double swing_height, const double* gains,
+                          const double* kff, double mass, const double* Ib, const double* planner_hip, double planner_k, hipStream_t st) {
   DevParams p;
   std::memset(&p, 0, sizeof(p));
   std::memcpy(p.hip, hip, sizeof(p.hip));
@@ -175,6 +212,15 @@ hipError_t qcp_set_params(const double* hip, const double* links, const double* 
   p.t_swing = t_swing;
   p.t_stance = t_stance;
   p.swing_height = swing_height;
+  std::memcpy(p.kp_p, gains, sizeof(p.kp_p));
+  std::memcpy(p.kd_p, gains + 3, sizeof(p.kd_p));
+  std::memcpy(p.kp_w, gains + 6, sizeof(p.kp_w));
+  std::memcpy(p.kd_w, gains + 9, sizeof(p.kd_w));
+  std::memcpy(p.kff, kff, sizeof(p.kff));
+  p.mass = mass;
+  std::memcpy(p.Ib, Ib, sizeof(p.Ib));
+  std::memcpy(p.planner_hip, planner_hip, sizeof(p.planner_hip));
+  p.planner_k = planner_k;
   hipLaunchKernelGGL(k_set_params, dim3(1), dim3(kBlock), 0, st, p);
   return hipGetLastError();
 }
@@ -198,6 +244,11 @@ hipError_t qcp_swing_pd(const int* leg, const double* qr, const double* q, doubl
 hipError_t qcp_track_swing(const double* phase, const double* p0, const double* pf, double* pos, double* vel, int n, hipStream_t st) {
   return launch(k_track_swing, n, st, phase, p0, pf, pos, vel);
 }
+// kin = 0: wrench_from_state<4, false> (fp = body-frame feet), 1: <4, true> (fp = joint angles)
+hipError_t qcp_wrench(int kin, const double* st, const double* fp, double* out, int n, hipStream_t s) {
+  return kin ? launch(k_wrench<true>, n, s, st, fp, out) : launch(k_wrench<false>, n, s, st, fp, out);
+}
+hipError_t qcp_foothold(const int* leg, const double* in, double* fh, int n, hipStream_t st) { return launch(k_foothold, n, st, leg, in, fh); }
 hipError_t qcp_ldlt6(const double* M, double* x, int* ok, int n, hipStream_t st) { return launch(k_ldlt<6>, n, st, M, x, ok); }
 hipError_t qcp_ldlt12(const double* M, double* x, int* ok, int n, hipStream_t st) { return launch(k_ldlt<12>, n, st, M, x, ok); }
 hipError_t qcp_tag(const double* v, const int* code, const int* free_face, const double* slack, const double* nd, double* tagged, int* code_back,

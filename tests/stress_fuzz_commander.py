@@ -1,0 +1,150 @@
+"""Fuzz campaign: commander mode (qc_tick_batch) over random batch sizes around the lane layouts' boundaries, random
+(stand_height, stand_tol, cmd_dt), height profiles that cross the stand band, sit on its edge or never reach it, `fresh` rates from 0
+to 1, twists from 1e-14 rad to 50 rad of increment and up to 10 m/s, |x| up to 1e4 m, and a small share of non-finite twists and
+heights.  Tick by tick: flags, Vb, gait phases and planner state BIT-EQUAL to tests/commander_restatement.py + the C oracle, the
+desired state within count * EPS * condition sum of the long-double reference (tests/device_math_reference.commander_apply_ld, the
+bars of tests/test_gpu_commander_edges.py) on the ticks a command is applied and untouched otherwise, forces / torques within the
+parity bars of tests/test_gpu_commander.py on robots whose inputs are finite, and no status or NaN on one side only.
+run_campaign() is what tests/test_gpu_fuzz.py calls with a time budget; as a script it runs the long version.
+usage: python tests/stress_fuzz_commander.py [runs=40] [ticks=30]"""
+import os, sys, time
+sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
+import numpy as np
+import quadruped_control_amd as q
+from oracle import c_oracle as O
+from tests import commander_restatement as CR
+from tests import device_math_reference as R
+
+SIZES = (1, 3, 63, 64, 65, 600, 1023, 1025, 4097, 8191, 16385, 20000, 32769)
+FIELDS = ("Rwb_d", "x_d", "xdot_d", "w_d")
+MEAS = ("Rwb", "x", "xdot", "w", "joint_q", "joint_qdot")
+
+
+def _twists(rng, n, cmd_dt):
+    ang = np.exp(rng.uniform(np.log(1e-14), np.log(50.0), n))
+    ang[rng.uniform(size=n) < 0.1] = 0.0
+    ax = rng.normal(size=(n, 3))
+    ax /= np.linalg.norm(ax, axis=1, keepdims=True)
+    v = rng.normal(size=(n, 3)) * rng.uniform(0, 10.0 / np.sqrt(3.0), (n, 1))
+    return np.concatenate([v, ax * (ang / abs(cmd_dt))[:, None]], 1)
+
+
+def run_campaign(runs=40, ticks=30, budget_s=None, min_runs=1):
+    import torch
+    from tests.test_oracle_cpu import _planned_batch
+    from tests.test_gpu_commander import _reference_tick
+
+    rng = np.random.default_rng(int(os.environ.get("QC_FUZZ_SEED", 515151)))
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    C = dict(robot_ticks=0, stand_ups=0, gait_starts=0, applied=0, small_angle=0, gimbal_lock=0, non_finite=0, mismatches=0, runs=0)
+    worst = dict(desired=0.0, grf=0.0, tau=0.0)
+    t0 = time.time()
+    P = q.cheetah_params(0.6)
+    for run in range(runs):
+        if budget_s is not None and run >= min_runs and time.time() - t0 > budget_s: break
+        n = int(SIZES[run % len(SIZES)]) if run < 2 * len(SIZES) else int(rng.integers(1, 40000))
+        h, tol = float(rng.uniform(0.2, 0.35)), float(rng.choice([0.005, 0.0, 0.02, 1e-4]))
+        cmd_dt = float(rng.choice([1e-3, 0.5, -0.25, 0.0, 1.0 / 128]))
+        fresh_rate = float(rng.choice([0.0, 0.05, 0.3, 1.0])) if run % 4 else 0.5
+        ctl = q.BalanceController.from_params(P)
+        base = {k: np.ascontiguousarray(v) for k, v in _planned_batch(n, 0).items()}
+        meas = {k: base[k].copy() for k in MEAS}
+        meas["x"][:, :2] *= np.exp(rng.uniform(0, np.log(1e4), (n, 1)))
+        lock = rng.uniform(size=n) < 0.02  # pitch = +-pi/2 exactly: no yaw to extract
+        meas["Rwb"][lock] = np.array([0.0, 0.0, 1.0, 0.0, 1.0, 0.0, -1.0, 0.0, 0.0])
+        # height profiles: reach the band at tick T (0: from the start), sit on its edge (+-tol exactly, +-1 ulp), or stay 2 tol + 1 cm out
+        T = rng.integers(0, max(2, ticks // 2), n)
+        kind = rng.integers(0, 10, n)
+        goal = h + np.where(kind < 6, rng.uniform(-1, 1, n) * tol * 0.9, np.where(kind == 6, tol, np.where(kind == 7, -tol, np.where(kind == 8, np.nextafter(h + tol, 0) - h, 2 * tol + 0.01))))
+        cmd = CR.Commander(n, x_stand=(0.0, 0.0, h), stand_tol=tol, cmd_dt=cmd_dt)
+        ref_phase, ref_swing = base["gait_phase"].copy(), O.new_swing_states(n)
+        d_state = dev(q.new_commander_states(n, x_stand=(0.0, 0.0, h)).view(np.uint8))
+        d_phase, d_swing = dev(base["gait_phase"]), dev(q.new_swing_states(n).view(np.uint8))
+        dt = rng.uniform(0.002, 0.005, n)
+        d_dt = dev(dt)
+        d_meas = {k: dev(v) for k, v in meas.items() if k != "x"}
+        for tick in range(ticks):
+            if budget_s is not None and run >= min_runs and time.time() - t0 > budget_s: break
+            x = meas["x"].copy()
+            frac = np.where(T == 0, 1.0, np.minimum(1.0, tick / np.maximum(T, 1)))
+            x[:, 2] = goal + (base["x"][:, 2] - goal) * (1.0 - frac)
+            twist = _twists(rng, n, cmd_dt if cmd_dt != 0.0 else 1e-3)
+            fresh = (rng.uniform(size=n) < fresh_rate).astype(np.uint8) * rng.choice([1, 2, 255], n).astype(np.uint8)
+            bad = rng.uniform(size=n) < 0.003
+            twist[bad, rng.integers(0, 6)] = rng.choice([np.nan, np.inf, -np.inf])
+            badh = rng.uniform(size=n) < 0.002
+            x[badh, 2] = rng.choice([np.nan, np.inf])
+            C["non_finite"] += int((bad & (fresh != 0)).sum() + badh.sum())
+            before = cmd.flags().copy()
+            prev = d_state.cpu().numpy().view(q.COMMANDER_STATE_DTYPE).copy()
+            out = ctl.tick_batch(dict(d_meas, x=dev(x), gait_phase=d_phase, gait_dt=d_dt, swing_state=d_swing),
+                                 dict(state=d_state, twist=dev(twist), fresh=dev(fresh), stand_height=h, stand_tol=tol, cmd_dt=cmd_dt))
+            torch.cuda.synchronize()
+            m = dict(meas, x=x)
+            with np.errstate(all="ignore"):
+                run_, applied, r = _reference_tick(O, P, m, cmd, ref_phase, ref_swing, dt, twist, fresh)
+            s = d_state.cpu().numpy().view(q.COMMANDER_STATE_DTYPE)
+            o = {k: v.cpu().numpy() for k, v in out.items()}
+            ph, sw = d_phase.cpu().numpy(), d_swing.cpu().numpy().view(q.SWING_STATE_DTYPE)
+            failed = []
+
+            def chk(name, ok_rows):
+                """ok_rows: bool per robot (or one bool); a failing check is reported with its name, count and first robot"""
+                ok_rows = np.atleast_1d(np.asarray(ok_rows, bool))
+                if not ok_rows.all():
+                    w = np.nonzero(~ok_rows)[0]
+                    failed.append("%s (%d robots, first %d)" % (name, w.size, w[0]))
+
+            chk("flags", (np.stack([s["standing"], s["gait_running"], s["cmd_pending"]], 1) == cmd.flags()).all(1))
+            chk("Vb", (s["Vb"].view(np.uint64) == cmd.Vb.view(np.uint64)).all(1))
+            chk("phase", ((ph == ref_phase) | (np.isnan(ph) & np.isnan(ref_phase))).all(1))
+            chk("planner state", (sw["leg_state"] == ref_swing["leg_state"]).all(1) & (sw["has_traj"] == ref_swing["has_traj"]).all(1))
+            chk("status", o["status"] == r["status"])
+            chk("one-sided NaN torque", (np.isnan(o["joint_tau"]) == np.isnan(r["joint_tau"])).all(1))
+            chk("one-sided NaN force", (np.isnan(o["grf_body"]) == np.isnan(r["grf_body"])).all(1))
+            # desired state: untouched where nothing was applied, within the bars where a finite command was
+            for k in FIELDS:  # (against the device's own record of the tick before: the restatement's is a float64 result, ulps away)
+                chk("untouched " + k, (s[k].view(np.uint64) == prev[k].view(np.uint64)).all(1) | applied)
+            ai = np.nonzero(applied)[0]
+            if ai.size:
+                with np.errstate(all="ignore"):
+                    ref = R.commander_apply_ld(meas["Rwb"][ai], x[ai], cmd.Vb[ai], cmd_dt, h)
+                C["small_angle"] += int(ref["small"].sum())
+                C["gimbal_lock"] += int((~ref["yaw_ok"]).sum())
+                fin = np.isfinite(cmd.Vb[ai]).all(1) & np.isfinite(x[ai]).all(1)
+                for k in FIELDS:
+                    val, cond, cnt = ref[k]
+                    got = s[k][ai]
+                    bar = cnt[fin] * R.EPS * cond[fin]
+                    err = np.abs(got[fin].astype(np.longdouble) - val[fin])
+                    chk("exact entries of " + k, ((got[fin] == np.asarray(val[fin], np.float64)) | (bar != 0)).all(1))
+                    worst["desired"] = max(worst["desired"], float(np.max(np.where(bar == 0, 0.0, err / np.where(bar == 0, 1.0, bar)), initial=0.0)))
+                if (~fin).any():
+                    # a non-finite command: the record is non-finite on both sides (WHICH entries may differ: the device skips the
+                    # structural zeros of Rz, 0 * inf is NaN in a full matrix product - INTEGRATION.md) and the tick says so
+                    j = ai[~fin]
+                    chk("non-finite command leaves a non-finite record", (~np.isfinite(np.concatenate([s[k][j] for k in FIELDS], 1))).any(1))
+                    chk("non-finite command reports QC_NOT_PD", o["status"][j] == 3)
+                # the checked records become the restatement's desired state: the oracle's next ticks see what the device holds
+                cmd.Rwb_d[ai], cmd.x_d[ai], cmd.xdot_d[ai], cmd.w_d[ai] = s["Rwb_d"][ai], s["x_d"][ai], s["xdot_d"][ai], s["w_d"][ai]
+            good = (o["status"] == 0) & (r["status"] == 0)
+            if good.any():
+                scale = np.maximum(1.0, np.abs(r["grf_body"][good]).max(axis=1, keepdims=True))
+                worst["grf"] = max(worst["grf"], float(np.nanmax(np.abs(o["grf_body"][good] - r["grf_body"][good]) / scale)))
+                worst["tau"] = max(worst["tau"], float(np.nanmax(np.abs(o["joint_tau"][good] - r["joint_tau"][good]))))
+            if failed:
+                C["mismatches"] += 1
+                print("run %d (n %d, h %.4f tol %g cmd_dt %g fresh rate %g) tick %d: %s" % (run, n, h, tol, cmd_dt, fresh_rate, tick, "; ".join(failed)))
+            after = cmd.flags()
+            C["robot_ticks"] += n
+            C["stand_ups"] += int(((before[:, 0] == 0) & (after[:, 0] == 1)).sum())
+            C["gait_starts"] += int(((before[:, 1] == 0) & (after[:, 1] == 1)).sum())
+            C["applied"] += int(applied.sum())
+        C["runs"] = run + 1
+    print("commander campaign, %.0f s: %s; worst desired-state error / bar %.3f, worst force error %.2e of max|GRF|, worst torque error %.2e N m" %
+          (time.time() - t0, C, worst["desired"], worst["grf"], worst["tau"]))
+    return C, worst
+
+
+if __name__ == "__main__":
+    run_campaign(int(sys.argv[1]) if len(sys.argv) > 1 else 40, int(sys.argv[2]) if len(sys.argv) > 2 else 30)

@@ -203,3 +203,88 @@ def test_initial_state_and_default_command(built):
     assert c.struct_size == ctypes.sizeof(_lib.QcCommandIn)
     assert (c.stand_height, c.stand_tol, c.cmd_dt) == (CR.X_STAND[2], CR.STAND_TOL, CR.CMD_DT)
     assert not c.twist and not c.fresh and not c.state
+
+
+# ---------------------------------------------------------------- the high-precision commander reference
+def _commander_sweep(rng, n, wide):
+    """`wide`: the GPU sweep's ranges (|w| dt log-uniform over [1e-14, 50], |x| up to 1e6, roll / pitch up to 1.5 rad); else the
+    closed-loop tests' domain (small twists at cmd_dt = 1e-3)."""
+    from scipy.spatial.transform import Rotation
+
+    if wide:
+        dt = 0.5
+        ang = np.exp(rng.uniform(np.log(1e-14), np.log(50.0), n))
+        ax = rng.normal(size=(n, 3))
+        w = ax / np.linalg.norm(ax, axis=1, keepdims=True) * (ang / dt)[:, None]
+        v = rng.normal(size=(n, 3)) * rng.uniform(0, 10.0 / np.sqrt(3), (n, 1))
+        x = rng.normal(size=(n, 3)) * np.exp(rng.uniform(np.log(1e-3), np.log(1e6), (n, 1)))
+        eul = np.stack([rng.uniform(-np.pi, np.pi, n), rng.uniform(-1.5, 1.5, n), rng.uniform(-1.5, 1.5, n)], 1)
+    else:
+        dt = 1e-3
+        w = rng.uniform(-0.05, 0.05, (n, 3))
+        v = rng.uniform(-0.2, 0.2, (n, 3))
+        x = rng.normal(size=(n, 3))
+        eul = np.stack([rng.uniform(-np.pi, np.pi, n), rng.uniform(-0.3, 0.3, n), rng.uniform(-0.3, 0.3, n)], 1)
+    Rw = Rotation.from_euler("ZYX", eul).as_matrix().reshape(n, 9)
+    return Rw, x, np.concatenate([v, w], 1), dt
+
+
+def _restated(Rw, x, Vb, dt, h):
+    Rd, xd = CR.integrate_twist_yaw(Rw, x, Vb, dt)
+    xd[:, 2] = h
+    v, w = CR.adjoint_twist(Rw, x, Vb)
+    return dict(Rwb_d=Rd.reshape(-1, 9), x_d=xd, xdot_d=v, w_d=w)
+
+
+def test_commander_reference_against_the_restatement():
+    """commander_apply_mp / _ld (tests/device_math_reference.py, written from trajectory.cpp and rigid3d.cpp) against the float64
+    restatement, which shares no code with them: to 1e-13 on the restatement's own domain; and over the GPU sweep's ranges the
+    restatement - a plain double evaluation of the same formulas - sits inside count * EPS * condition sum entry by entry, which
+    is what the GPU test asks of the device (a bar a correct double evaluation could miss would be a wrong bar)."""
+    from tests import device_math_reference as R
+
+    rng = np.random.default_rng(21)
+    for wide, n in ((False, 4000), (True, 20000)):
+        Rw, x, Vb, dt = _commander_sweep(rng, n, wide)
+        ref = R.commander_apply_ld(Rw, x, Vb, dt, 0.26)
+        got = _restated(Rw, x, Vb, dt, 0.26)
+        assert ref["small"].sum() > (100 if wide else -1) and (~ref["small"]).sum() > 100
+        for k, (val, cond, cnt) in ((k, ref[k]) for k in got):
+            err = np.abs(got[k] - np.asarray(val, np.float64))
+            if not wide:
+                assert err.max() <= 1e-13, (k, err.max())
+            assert np.all(err <= cnt * R.EPS * cond + 5e-324), (k, wide, float(np.max(err / np.maximum(cnt * R.EPS * cond, 5e-324))))
+            bound = np.where(ref["small"][:, None], R.COMMANDER_COUNTS_SMALL[k], R.COMMANDER_COUNTS[k])
+            assert (cnt <= bound).all() and cnt.max() == R.COMMANDER_COUNTS[k], (k, cnt.max())
+        for i in range(0, n, n // 40):
+            m = R.commander_apply_mp(Rw[i], x[i], Vb[i], dt, 0.26)
+            assert m["small"] == ref["small"][i] and m["yaw_ok"]
+            for k in got:
+                val, cond, cnt = ref[k]
+                assert np.all(np.abs(m[k][0] - np.asarray(val[i], np.float64)) <= 2.0 ** -60 * cnt[i] * cond[i] + 2.0 ** -1074 + R.EPS * np.abs(m[k][0]))
+                assert np.array_equal(m[k][2], cnt[i])
+
+
+def test_commander_reference_branches():
+    """The two double decisions: the angle threshold is |angle| < 1e-12 strictly, on the double norm; a pose without a yaw
+    (R00 = R10 = 0, |R00|, |R10| < 1.5e-162 whose squares underflow to 0, a non-finite entry) takes yaw 0 as INTEGRATION.md says."""
+    from tests import device_math_reference as R
+
+    x, v = np.array([0.0, 0.0, 0.3]), np.array([0.25, -0.5, 0.125])
+    for ang, small in ((0.0, True), (-0.0, True), (9.9e-13, True), (np.nextafter(1e-12, 0), True), (1e-12, False), (np.nextafter(1e-12, 1), False), (1e-9, False)):
+        m = R.commander_apply_mp(np.eye(3), x, np.concatenate([v, [0.0, 0.0, ang * 1024.0]]), 2.0 ** -10, 0.26)
+        assert m["small"] == small, ang
+        if small:
+            assert np.array_equal(m["Rwb_d"][0], np.eye(3).reshape(9)) and np.array_equal(m["x_d"][0], [v[0] / 1024, v[1] / 1024, 0.26])
+        else:
+            assert m["Rwb_d"][0][3] == np.sin(ang) and m["x_d"][0][1] != v[1] / 1024
+    for r00, r10 in ((0.0, 0.0), (1e-163, -1e-163), (np.nan, 0.5), (np.inf, 0.0), (0.3, -np.inf)):
+        Rw = _ry(np.pi / 2)
+        Rw[0, 0], Rw[1, 0] = r00, r10
+        m = R.commander_apply_mp(Rw, x, np.concatenate([v, [0.0, 0.0, 0.0]]), 1e-3, 0.26)
+        assert not m["yaw_ok"] and np.array_equal(m["Rwb_d"][0], np.eye(3).reshape(9))
+    # quadrants with exact zeros: yaw = pi/2 -> Rz = [[0, -1], [1, 0]] exactly, pi -> diag(-1, -1)
+    m = R.commander_apply_mp(np.array([[0.0, -1, 0], [1, 0, 0], [0, 0, 1.0]]), x, np.zeros(6), 1e-3, 0.26)
+    assert np.array_equal(m["Rwb_d"][0], [0, -1, 0, 1, 0, 0, 0, 0, 1])
+    m = R.commander_apply_mp(np.diag([-1.0, -1.0, 1.0]), x, np.zeros(6), 1e-3, 0.26)
+    assert np.array_equal(m["Rwb_d"][0], [-1, 0, 0, 0, -1, 0, 0, 0, 1])

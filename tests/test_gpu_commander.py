@@ -21,6 +21,18 @@ CASES = {
     "dense-forced": (700, {"force_dense": 1}, 4, None, 30),
     "dense-W": (40000, "dense_w", 1, None, 16),
 }
+# Batch sizes that do NOT fill their waves: a lone robot, a partial lane-group set, one robot beyond a whole number of waves
+# (4 096 = 256 racing waves of 16, 16 384 = 512 two-lane waves, 32 768 = 512 one-lane waves) and one just above a multiple
+# of 64 on the one-lane one-fill kernel.  Idle lane groups shadow the last robot there; the step must still run once per robot.
+RAGGED = {
+    "ragged-1": (1, {}, 4, None, 0),
+    "ragged-3": (3, {}, 4, None, 0),
+    "ragged-4097": (4097, {}, 4, None, 0),
+    "ragged-16385": (16385, {}, 2, None, 0),
+    "ragged-32769": (32769, {}, 1, 1, 0),
+    "ragged-1-lane": (140033, {}, 1, 1, 0),
+}
+ALL_CASES = dict(CASES, **RAGGED)
 
 
 @pytest.fixture(scope="module")
@@ -181,13 +193,13 @@ def _standing_states(q, base, n):
     return s
 
 
-@pytest.mark.parametrize("case", list(CASES))
+@pytest.mark.parametrize("case", list(ALL_CASES))
 def test_commander_step_changes_nothing_else(q, case):
     """A running robot with no pending command: qc_tick_batch must give what qc_control_batch gives when fed the state's desired
     values - bit for bit, over two ticks (the planner state carried) - and leave the commander state untouched."""
     import torch
 
-    n, tune, lanes, mode, _ = CASES[case]
+    n, tune, lanes, mode, _ = ALL_CASES[case]
     _, ctl = _controller(q, tune)
     _check_instantiation(ctl, n, lanes, mode, case)
     base = _base(n)
@@ -212,10 +224,11 @@ def test_commander_step_changes_nothing_else(q, case):
         assert _state_host(q, d_state).tobytes() == st0.tobytes(), (case, tick)
 
 
-@pytest.mark.parametrize("n,lanes,mode", [(600, 4, None), (20000, 2, None), (140000, 1, 1)])
+@pytest.mark.parametrize("n,lanes,mode", [(600, 4, None), (20000, 2, None), (140000, 1, 1)] + [(c[0], c[2], c[3]) for c in RAGGED.values()])
 def test_commander_step_runs_exactly_once(q, n, lanes, mode):
     """Cold-started config-3 robots leave stragglers that the lane-group tails (re-packed records) finish: after
-    ONE launch every robot's commander, clock and planner have advanced exactly one step."""
+    ONE launch every robot's commander, clock and planner have advanced exactly one step.  (The RAGGED sizes leave partial waves and
+    idle lane groups; below 600 robots there are too few for a straggler statistic.)"""
     import torch
 
     from oracle import c_oracle as O
@@ -245,10 +258,13 @@ def test_commander_step_runs_exactly_once(q, n, lanes, mode):
                          dict(state=d_state), want_iterations=True)
     torch.cuda.synchronize()
     it = out["iterations"].cpu().numpy()
-    assert it.max() > np.median(it) + 3  # stragglers: the hand-over paths ran
+    if n >= 600:
+        assert it.max() > np.median(it) + 3  # stragglers: the hand-over paths ran
     ref_phase, ref_swing = base["gait_phase"].copy(), O.new_swing_states(n)
     run, applied, r = _reference_tick(O, P, meas, cmd, ref_phase, ref_swing, dt, None, None)
-    assert run.sum() == applied.sum() * 2 and (run == (kind >= 2)).all()
+    assert (run == (kind >= 2)).all() and (applied == (kind == 3)).all()
+    if n % 4 == 0:
+        assert run.sum() == applied.sum() * 2
     dev = dict(out={k: v.cpu().numpy() for k, v in out.items()}, state=_state_host(q, d_state), phase=d_phase.cpu().numpy(),
                swing=d_swing.cpu().numpy().view(q.SWING_STATE_DTYPE))
     _compare_tick(q, O, P, ctl, 0, n, dev, dict(cmd=cmd, out=r, phase=ref_phase, swing=ref_swing), f"once-{n}")

@@ -528,3 +528,165 @@ def test_leg_swing_torque(P):
         err = float(np.abs(tau[i] - ref).max())
         assert err <= bar, f"leg {legs[i]} target {pb[i]!r}: err {err:.3e} > {bar:.3e} (cond {cond:.3e})"
     assert saw["pinv"] >= 12 and saw["folded"] == 4, saw
+
+
+# ---------------------------------------------------------------- wrench_from_state, plan_foothold
+def _wrench_setup(P, seed):
+    """The probe's constants with every quirk of the wrench law visible (tests/test_device_math_cpu._wrench_params: kff[3..5] all
+    different and non-zero, a full non-diagonal Ib, non-uniform gains) and a planner; returns (params dict, restore())."""
+    from tests.test_device_math_cpu import _wrench_params
+
+    rng = np.random.default_rng(seed)
+    W = _wrench_params(rng)
+    W["planner_hip"] = (R.HIP + rng.uniform(-0.01, 0.01, (4, 3))).reshape(12)
+    W["planner_k"] = 0.07
+    _, basis = R.sextic_basis_mp()
+    P.set_params(R.HIP, R.LINKS, R.JC_KFF, R.JC_KP, R.JC_KD, basis, 0.18, 0.31, 0.08, wrench=W)
+    return W, lambda: P.set_params(R.HIP, R.LINKS, R.JC_KFF, R.JC_KP, R.JC_KD, basis, 0.18, 0.8, 0.08)
+
+
+def _check_wrench(P, W, b, fp, kin, sample, tag):
+    """b and r of the probe against wrench_ld on every state and wrench_mp on `sample`; returns the worst error / bar"""
+    bd, rd, fin = P.wrench(b, fp, kin)
+    assert np.array_equal(fin, np.zeros_like(fin)), (tag, fin[fin != 0][:4])
+    ref = R.wrench_ld(W, b, fp, kin=(R.HIP, R.LINKS) if kin else None)
+    worst = 0.0
+    for got, (val, cond, cnt) in ((bd, ref["b"]), (rd, ref["r"])):
+        ratio = np.abs(got.astype(np.longdouble) - val) / (cnt * EPS * cond)
+        worst = max(worst, float(ratio.max()))
+        assert ratio.max() <= 1.0, (tag, kin, float(ratio.max()), np.unravel_index(int(np.argmax(ratio)), ratio.shape))
+    for i in sample:
+        m = R.wrench_mp(W, {k: v[i] for k, v in b.items()}, fp[i], kin=(R.HIP, R.LINKS) if kin else None)
+        for got, (val, cond, cnt) in ((bd[i], m["b"]), (rd[i], m["r"])):
+            ratio = np.abs(got - val) / (cnt * EPS * cond)
+            worst = max(worst, float(ratio.max()))
+            assert ratio.max() <= 1.0, (tag, kin, int(i), float(ratio.max()))
+    return worst
+
+
+def test_wrench_from_state(P):
+    """b [6] and r [4][3] of wrench_from_state<4, false> and <4, true> against BC.cpp:126-139, 244-269 at 50 digits (edge set and a
+    2 000-state sample) and in long double (100 000 random states), entry by entry within count * EPS * condition sum
+    (device_math_reference.Tr: the count is the number of roundings on the entry's longest chain - 5 or 6 for the linear part, 3 for
+    r, 22 for the angular part, where the rotation log enters with its own pinned 8 EPS max(1, angle) plus the sensitivity of the log
+    map to the <= 3 roundings of each entry of Re = Rwb_d Rwb^T, measured by perturbing Re in the reference's precision).  The
+    parameters make the `sic` index (kff5 w_d2 on row 1), a transposed Iw and swapped gains visible (test_device_math_cpu shows each
+    of them far outside these bars).  Rotation errors stay below pi - 1e-3; beyond it test_angle_axis_total's domain applies."""
+    from tests.test_device_math_cpu import _wrench_states
+
+    W, restore = _wrench_setup(P, 31)
+    try:
+        rng = np.random.default_rng(32)
+        n = 100_000
+        b = _wrench_states(rng, n, max_angle=np.pi - 1e-3)
+        feet = b.pop("feet")
+        qj = np.stack([rng.uniform(-0.6, 0.6, (n, 4)), rng.uniform(-0.2, 1.4, (n, 4)), rng.uniform(-2.4, -0.3, (n, 4))], 2).reshape(n, 12)
+        sample = rng.choice(n, 2000, replace=False)
+        w0 = _check_wrench(P, W, b, feet, False, sample, "random")
+        w1 = _check_wrench(P, W, b, qj, True, sample, "random")
+        # edge set: rotation errors 0, 1e-9, pi/2, pi - 1e-3 about coordinate and general axes; x_d - x = 1e-12 next to |x| = 1e3
+        from scipy.spatial.transform import Rotation
+
+        rows = []
+        for ang in (0.0, 1e-9, np.pi / 2, 3.0, np.pi - 1e-3):
+            for ax in (np.eye(3)[0], np.eye(3)[1], np.eye(3)[2], np.array([1.0, 2.0, 3.0]) / np.sqrt(14.0), np.array([-0.3, 0.8, 0.1])):
+                for base in (np.eye(3), Rotation.from_euler("ZYX", [0.7, -0.4, 1.1]).as_matrix()):
+                    rows.append((base, R.rotation_mp(ax, ang) @ base if ang else base.copy()))
+        m = len(rows)
+        e = {k: v[:m].copy() for k, v in b.items()}
+        e["Rwb"] = np.array([r[0].reshape(9) for r in rows])
+        e["Rwb_d"] = np.array([r[1].reshape(9) for r in rows])
+        e["x"][: m // 2] = np.array([1e3, -1e3, 1e3]) * rng.uniform(0.5, 1.0, (m // 2, 3))
+        e["x_d"][: m // 2] = e["x"][: m // 2] + 1e-12
+        w2 = _check_wrench(P, W, e, feet[:m], False, range(m), "edge")
+        w3 = _check_wrench(P, W, e, qj[:m], True, range(m), "edge")
+        # a zero rotation error (Rwb_d == Rwb == I: Re = I exactly): e = 0 exactly, so b[3:] must not move when kp_w does
+        same = [i for i in range(m) if np.array_equal(e["Rwb"][i], np.eye(3).reshape(9)) and np.array_equal(e["Rwb_d"][i], np.eye(3).reshape(9))]
+        assert len(same) == 5
+        bd, _, _ = P.wrench(e, feet[:m], False)
+        W2 = dict(W, kp_w=np.zeros(3))
+        _, basis = R.sextic_basis_mp()
+        P.set_params(R.HIP, R.LINKS, R.JC_KFF, R.JC_KP, R.JC_KD, basis, 0.18, 0.31, 0.08, wrench=W2)
+        bd0, _, _ = P.wrench(e, feet[:m], False)
+        assert np.array_equal(bd[same], bd0[same]) and not np.array_equal(bd[:, 3:], bd0[:, 3:])
+        print(f"wrench_from_state: worst error / bar: random {w0:.3f} (feet) {w1:.3f} (joint angles), edge set {w2:.3f} {w3:.3f}")
+    finally:
+        restore()
+
+
+def test_wrench_finiteness_value(P):
+    """The value wrench_from_state returns is exactly 0.0 for finite inputs - up to 1e150 in every input at once - and non-zero (or
+    NaN) as soon as ONE entry of an input that reaches b, r or R is NaN or Inf: each of Rwb, Rwb_d, x, x_d, xdot, xdot_d, w, w_d and the
+    feet / joint angles in turn, both variants."""
+    from tests.test_device_math_cpu import _wrench_states
+
+    W, restore = _wrench_setup(P, 33)
+    try:
+        rng = np.random.default_rng(34)
+        names = ("Rwb", "Rwb_d", "x", "x_d", "xdot", "xdot_d", "w", "w_d", "fp")
+        rows = [(name, k, bad) for name in names for k in ((0, 4, 8) if name.startswith("Rwb") else (0, 2, 7, 11) if name == "fp" else (0, 1, 2)) for bad in (np.nan, np.inf, -np.inf)]
+        m = len(rows)
+        b = _wrench_states(rng, m, max_angle=2.0)
+        feet = b.pop("feet")
+        qj = np.stack([rng.uniform(-0.6, 0.6, (m, 4)), rng.uniform(-0.2, 1.4, (m, 4)), rng.uniform(-2.4, -0.3, (m, 4))], 2).reshape(m, 12)
+        for kin, fp in ((False, feet), (True, qj)):
+            _, _, fin = P.wrench(b, fp, kin)
+            assert np.array_equal(fin, np.zeros(m)) and not np.signbit(fin).any()
+            bb = {k: v.copy() for k, v in b.items()}
+            ff = fp.copy()
+            for i, (name, k, bad) in enumerate(rows):
+                (ff if name == "fp" else bb[name])[i, k] = bad
+            _, _, fin = P.wrench(bb, ff, kin)
+            assert (fin != 0.0).all(), [rows[i] for i in np.nonzero(fin == 0.0)[0]]
+        big = {k: (v if k.startswith("Rwb") else np.sign(v) * 1e150) for k, v in b.items()}
+        bd, rd, fin = P.wrench(big, np.sign(feet) * 1e150, False)
+        assert np.array_equal(fin, np.zeros(m)) and np.isfinite(bd).all() and np.isfinite(rd).all()
+        for name in names[2:-1]:
+            one = dict(b, **{name: big[name]})
+            for kin, fp in ((False, feet), (True, qj)):
+                assert np.array_equal(P.wrench(one, fp, kin)[2], np.zeros(m)), (name, kin)
+    finally:
+        restore()
+
+
+def test_plan_foothold(P):
+    """plan_foothold against foot_planner.cpp:76-104 at 50 digits (a 1 000-case sample) and in long double (100 000 cases): x and y
+    within count * EPS * sum |terms| (count 7 as Tr counts it: the thigh position 4, then the three sums of the four-term sum), z == 0 exactly.
+    A height of 0 or -0 drops the pendulum term and nothing else; a negative height is NaN in x and y like the reference's
+    std::sqrt, z still 0."""
+    from scipy.spatial.transform import Rotation
+
+    W, restore = _wrench_setup(P, 35)
+    try:
+        rng = np.random.default_rng(36)
+        n = 100_000
+        legs = rng.integers(0, 4, n)
+        Rw = Rotation.random(n, random_state=5).as_matrix().reshape(n, 9)
+        x = np.stack([rng.normal(size=n) * 10, rng.normal(size=n) * 10, rng.uniform(0.02, 0.8, n)], 1)
+        xdot, w, xdd, pc = rng.normal(size=(n, 3)) * 2, rng.normal(size=(n, 3)) * 3, rng.normal(size=(n, 3)) * 2, rng.uniform(-0.5, 0.5, (n, 3))
+        fh = P.foothold(legs, Rw, x, xdot, w, xdd, pc)
+        hips = W["planner_hip"].reshape(4, 3)[legs]
+        val, cond, cnt = R.foothold_ld(hips, W["planner_k"], 0.31, Rw, x, xdot, w, xdd, pc, foot_is_lever=True)
+        assert (fh[:, 2] == 0.0).all() and not np.signbit(fh[:, 2]).any()
+        ratio = np.abs(fh[:, :2].astype(np.longdouble) - val[:, :2]) / (cnt[:, :2] * EPS * cond[:, :2])
+        assert cnt[:, :2].max() == 7 and ratio.max() <= 1.0, (float(ratio.max()), int(cnt.max()))
+        worst = float(ratio.max())
+        for i in rng.choice(n, 1000, replace=False):
+            v, c, k = R.foothold_mp(hips[i], W["planner_k"], 0.31, Rw[i], x[i], xdot[i], w[i], xdd[i], pc[i], foot_is_lever=True)
+            r = np.abs(fh[i, :2] - v[:2]) / (k[:2] * EPS * c[:2])
+            worst = max(worst, float(r.max()))
+            assert r.max() <= 1.0, (int(i), float(r.max()))
+        print(f"plan_foothold: worst error / bar {worst:.3f}")
+        # heights 0, -0, negative
+        m = 12
+        xe = x[:m].copy()
+        xe[:4, 2], xe[4:8, 2], xe[8:, 2] = 0.0, -0.0, -rng.uniform(0.01, 1.0, 4)
+        fe = P.foothold(legs[:m], Rw[:m], xe, xdot[:m], w[:m], xdd[:m], pc[:m])
+        assert (fe[:, 2] == 0.0).all() and np.isnan(fe[8:, :2]).all() and np.isfinite(fe[:8, :2]).all()
+        for i in range(8):  # sqrt(+-0 / g) = +-0: the pendulum term is +-0 xdot
+            xi = xe[i].copy()
+            xi[2] = 1e-300  # (the reference takes a positive height: 0.5 sqrt(1e-300 / g) |xdot| = 1e-150, far below the bar)
+            v, c, k = R.foothold_mp(hips[i], W["planner_k"], 0.31, Rw[i], xi, xdot[i], w[i], xdd[i], pc[i], foot_is_lever=True)
+            assert np.all(np.abs(fe[i, :2] - v[:2]) <= k[:2] * EPS * c[:2])
+    finally:
+        restore()

@@ -131,3 +131,17 @@ def test_cross_form_parity_600k(built):
     idx = np.random.default_rng(0).choice(n, 65536, replace=False)
     ref, st, _ = O.control_batch(P, {k: np.ascontiguousarray(v[idx]) for k, v in b.items()}, threads=16)
     assert (st == 0).all() and np.max(np.abs(base[idx] - ref) / scale[idx]) < 1e-6
+
+
+def test_commander_fuzz_20s(built):
+    """Commander mode over random batch sizes around the lane layouts' boundaries, random (stand_height, stand_tol, cmd_dt), height
+    profiles that cross the stand band, sit on its edge or never reach it, fresh rates 0 ... 1, twists over the whole range of the step
+    and a small share of non-finite inputs (tests/stress_fuzz_commander.py): flags, Vb, phases and planner state bit-equal to the
+    restatement + oracle, the desired state within the derived bars of tests/test_gpu_commander_edges.py, forces and torques within
+    the parity bars of tests/test_gpu_commander.py.  Every branch the campaign is about must have been reached."""
+    from tests import stress_fuzz_commander
+
+    C, worst = stress_fuzz_commander.run_campaign(runs=400, ticks=30, budget_s=20.0)
+    assert C["mismatches"] == 0 and worst["desired"] <= 1.0 and worst["grf"] < 1e-6 and worst["tau"] < 2e-5, (C, worst)
+    for k in ("robot_ticks", "stand_ups", "gait_starts", "applied", "small_angle", "gimbal_lock", "non_finite", "runs"):
+        assert C[k] > 0, (k, C)
