@@ -382,6 +382,38 @@ struct Lane {
   }
 };
 
+// One working-set recalculation with the constants where the loop keeps them.  RESIDENT: a register copy (UConst), loaded
+// once here and pinned before every recalculation - no scalar load + wait per recalculation; otherwise the constant buffer,
+// re-derived at every recalculation (QC_PARAMS_HERE).
+template <bool RESIDENT>
+struct Recalc {
+  const DevParams* Pg;
+  UConst uc;
+  QC_DEV explicit Recalc(const DevParams* pg) : Pg(pg) {
+    if constexpr (RESIDENT) uc = load_uconst(*QC_PARAMS_HERE(Pg));
+  }
+  template <int PHASE, class LaneX, class EqpX>
+  QC_DEV bool step(LaneX& lane, EqpX& eqp, const bool live, const bool empty_set = false) {
+    if constexpr (RESIDENT) {
+      pin_uconst(uc);
+      return lane.template iterate<PHASE>(uc, eqp, live, empty_set);
+    } else {
+      return lane.template iterate<PHASE>(*QC_PARAMS_HERE(Pg), eqp, live, empty_set);
+    }
+  }
+};
+
+// The votes of the lane groups racing on one robot, ORed together: N groups, ROT lanes apart within their row of 16.
+template <int ROT, int N>
+QC_DEV int race_or(const int mine) {
+  int m = mine | __builtin_amdgcn_update_dpp(0, mine, 0x120 + ROT, 0xF, 0xF, true);  // row_ror by ROT lanes: the partner groups
+  if constexpr (N == 4) {
+    m |= __builtin_amdgcn_update_dpp(0, mine, 0x120 + 2 * ROT, 0xF, 0xF, true);
+    m |= __builtin_amdgcn_update_dpp(0, mine, 0x120 + 3 * ROT, 0xF, 0xF, true);
+  }
+  return m;
+}
+
 // Dense phases around the divergent solve.  Robots need 1 ... ~20
 // recalculations, so the solver lanes are refilled a few at a time; running the
 // expensive per-robot assembly (rotation log with atan2/sqrt, Newton-Euler
@@ -1059,21 +1091,12 @@ QC_DEV void finish_on_four_lanes(const DevParams* __restrict__ Pg, const LaneG& 
     // groups beyond the running robots shadow record 0: the strided layout keeps every lane in the loop (MFMA)
     const int slot4 = repack_read(Pg, L4, eqp4, sin + (busy4 ? g4 : 0) * RS, j4);
     const int stop = race ? 8 : 0;
-    if constexpr (UNIFORM) {
-      // the tail has the registers to keep the recalculation's constants resident, as the mode-2 kernel does
-      UConst uc = load_uconst(*QC_PARAMS_HERE(Pg));
-      while (__builtin_popcountll(__builtin_amdgcn_ballot_w64(busy4) & 0xFFFFull) > stop) {
-        QC_CLK(7, 2);
-        pin_uconst(uc);
-        const bool done = L4.template iterate<Lane4::STEADY>(uc, eqp4, busy4);
-        busy4 = busy4 & !done;
-      }
-    } else {
-      while (__builtin_popcountll(__builtin_amdgcn_ballot_w64(busy4) & 0xFFFFull) > stop) {
-        QC_CLK(7, 2);
-        const bool done = L4.template iterate<Lane4::STEADY>(*QC_PARAMS_HERE(Pg), eqp4, busy4);
-        busy4 = busy4 & !done;
-      }
+    // the tail has the registers to keep the recalculation's constants resident, as the mode-2 kernel does
+    Recalc<UNIFORM> rc(Pg);
+    while (__builtin_popcountll(__builtin_amdgcn_ballot_w64(busy4) & 0xFFFFull) > stop) {
+      QC_CLK(7, 2);
+      const bool done = rc.template step<Lane4::STEADY>(L4, eqp4, busy4);
+      busy4 = busy4 & !done;
     }
     if constexpr (HOLD) {
       held = g4 < nb && !busy4;
@@ -1106,22 +1129,14 @@ QC_DEV void finish_on_four_lanes(const DevParams* __restrict__ Pg, const LaneG& 
   unsigned solved_mask = 0;  // strategies of this lane's robot that have reached the KKT point
   auto after = [&](bool done) {
     const int mine = (busyR & done & (LR.status == QC_SOLVED)) ? (1 << sid) : 0;
-    const int m = mine | __builtin_amdgcn_update_dpp(0, mine, 0x120 + 8, 0xF, 0xF, true);  // row_ror 8: the partner group
+    const int m = race_or<8, 2>(mine);
     solved_mask |= (unsigned)m;
     busyR = busyR & !done & (solved_mask == 0);
   };
-  if constexpr (UNIFORM) {
-    UConst uc = load_uconst(*QC_PARAMS_HERE(Pg));
-    while (__builtin_amdgcn_ballot_w64(busyR) != 0) {
-      QC_CLK(7, 2);
-      pin_uconst(uc);
-      after(LR.template iterate<LaneR::STEADY>(uc, eqpR, busyR));
-    }
-  } else {
-    while (__builtin_amdgcn_ballot_w64(busyR) != 0) {
-      QC_CLK(7, 2);
-      after(LR.template iterate<LaneR::STEADY>(*QC_PARAMS_HERE(Pg), eqpR, busyR));
-    }
+  Recalc<UNIFORM> rcR(Pg);
+  while (__builtin_amdgcn_ballot_w64(busyR) != 0) {
+    QC_CLK(7, 2);
+    after(rcR.template step<LaneR::STEADY>(LR, eqpR, busyR));
   }
   QC_CLK_TAIL_END();
   // the winner - the lower-numbered strategy if both got there in the same recalculation, strategy 0 with whatever
@@ -1149,6 +1164,36 @@ QC_DEV int clamp_steps_for(CParams& P, const uint32_t* warm) {
 // MODE 1: the launch gives every wave one fill (chunk <= 64 / G).  MODE 2: one fill and the SIMD to itself,
 // recalculation constants resident in VGPRs.
 // RACE (strided 4-lane one-fill kernels): strategies racing per robot, 1, 2 or 4; a wave then holds 16 / RACE robots (see Lane).
+
+// The dynamic LDS of one balance_kernel instantiation: what the kernel addresses and what the launch asks for (offsets in doubles
+// from the start of the workgroup's LDS).
+template <class Eqp, bool KIN, int MODE>
+struct LdsLayout {
+  static constexpr int G = Eqp::G;
+  static constexpr int SP = stock_slots(G) + 1;  // plane stride of the stock
+  // One-lane dense form as one-fill workgroups (round 5): the 78 Hessian planes (39 936 B) ARE the workgroup's LDS - four
+  // workgroups per CU, one per SIMD.  With the stock in front of them (58.3 KB) a CU held two, i.e. every other SIMD idled
+  // behind the 512-register kernel.  The input stock is not used on this path (one lane assembles and solves its robot),
+  // Rwb is read again for the output transform instead of parked, and the output stock aliases the first Hessian planes
+  // once every robot of the wave is finished.
+  static constexpr bool HESS_ONLY = Eqp::kHessianInLds;
+  static_assert(!HESS_ONLY || (OUT_PLANES * SP + TASK_DOUBLES <= Eqp::kLdsDoubles), "the output stock fits the Hessian planes it aliases");
+  // (see QPARK_* above: Rwb and the joint angles parked, the re-pack records under the output stock)
+  static constexpr bool QPARK = KIN && G == 1 && MODE == 1 && !HESS_ONLY;
+  static_assert(!QPARK || SP == 65, "the QPARK layout is laid out for 64 slots");
+  // One lane per robot: Rwb is parked in the first nine planes of the (otherwise idle) input-stock area for the output transform;
+  // the planes behind them serve as the re-pack area of the tail.
+  static constexpr bool RPARK = G == 1 && !HESS_ONLY;
+  static constexpr int R_PLANES = RPARK ? 9 : 0;
+  static constexpr int IN = 0;                                                            // input stock (one lane per robot: Rwb planes)
+  static constexpr int OUT = HESS_ONLY ? 0 : (QPARK ? QPARK_OUT : IN_PLANES) * SP;        // output stock
+  static constexpr int REPACK = QPARK ? OUT : R_PLANES * SP;                              // re-pack records of the 4-lane tail
+  static_assert(G != 1 || QPARK || (R_PLANES * SP + 16 * REPACK_RS <= IN_PLANES * SP), "Rwb planes + re-pack records fit the input-stock area");
+  static constexpr int EQP = HESS_ONLY ? 0 : stock_doubles(stock_slots(G));               // the form's own planes (Eqp::kLdsDoubles of them)
+  static constexpr size_t BYTES = sizeof(double) * (HESS_ONLY ? (size_t)Eqp::kLdsDoubles
+                                                    : QPARK   ? (size_t)qpark_doubles()
+                                                              : (size_t)(EQP + Eqp::kLdsDoubles));
+};
 
 // The kernel's argument block as the launch lays it out (kernarg segment), for re-deriving BatchIn / BatchOut AT THEIR USE in the
 // joint_q kernels: 23 array pointers held in SGPRs from the kernel's entry to its flush - across a solve that needs none of
@@ -1190,19 +1235,11 @@ __global__ __launch_bounds__(64, MIN_WAVES_PER_SIMD) void balance_kernel(const D
     else return out_k;
   };
   extern __shared__ __attribute__((aligned(16))) double qc_lds[];  // [stock planes][64] (+ the dense form's 78 Hessian planes)
-  constexpr int SP = stock_slots(G) + 1;  // plane stride of the stock
-  // One-lane dense form as one-fill workgroups (round 5): the 78 Hessian planes (39 936 B) ARE the workgroup's LDS - four
-  // workgroups per CU, one per SIMD.  With the stock in front of them (58.3 KB) a CU held two, i.e. every other SIMD idled
-  // behind the 512-register kernel.  The input stock is not used on this path (one lane assembles and solves its robot),
-  // Rwb is read again for the output transform instead of parked, and the output stock aliases the first Hessian planes
-  // once every robot of the wave is finished.
-  constexpr bool HESS_ONLY = Eqp::kHessianInLds;
-  static_assert(!HESS_ONLY || (OUT_PLANES * SP + TASK_DOUBLES <= 78 * 64), "the output stock fits the Hessian planes it aliases");
-  // (see QPARK_* above: Rwb and the joint angles parked, the re-pack records under the output stock)
-  constexpr bool QPARK = KIN && G == 1 && MODE == 1 && !Eqp::kHessianInLds;
-  static_assert(!QPARK || SP == 65, "the QPARK layout is laid out for 64 slots");
-  double* const sin = qc_lds;
-  double* const sout = HESS_ONLY ? qc_lds : qc_lds + (QPARK ? QPARK_OUT : IN_PLANES) * SP;
+  using Lay = LdsLayout<Eqp, KIN, MODE>;
+  constexpr int SP = Lay::SP;
+  constexpr bool HESS_ONLY = Lay::HESS_ONLY, QPARK = Lay::QPARK;
+  double* const sin = qc_lds + Lay::IN;
+  double* const sout = qc_lds + Lay::OUT;
   // XCD-aware workgroup -> chunk map.  The dispatcher places workgroup b on XCD b % 8 (observed, MI355X_MICROARCH.md "Workgroup
   // dispatch"; a speed assumption only - any placement computes the same robots), each XCD with an L2 of its own.  A racing wave holds
   // 4 (or 8) robots: 288 contiguous bytes per 72-byte-row array, so neighbouring waves share the 128-byte lines their rows straddle,
@@ -1235,7 +1272,7 @@ __global__ __launch_bounds__(64, MIN_WAVES_PER_SIMD) void balance_kernel(const D
   Lane<Eqp, KIN, (RACE > 1) || TWIN> L;
   L.idx = -1;
   L.foot0 = member * (4 / G);
-  Eqp eqp(qc_lds + (HESS_ONLY ? 0 : stock_doubles(stock_slots(G))) + lane);
+  Eqp eqp(qc_lds + Lay::EQP + lane);
   bool busy = false;  // group holds an unfinished robot
   QC_CLK_BEGIN();
   // One fill per wave, a divergent solve loop, one push, one flush: nothing but recalculations on the serial chain that
@@ -1245,12 +1282,10 @@ __global__ __launch_bounds__(64, MIN_WAVES_PER_SIMD) void balance_kernel(const D
   UConst uc;  // RESIDENT: the recalculation's constants live in VGPRs (no scalar load + wait per recalculation)
   if constexpr (RESIDENT) uc = load_uconst(*QC_PARAMS_HERE(Pg));
   // One lane per robot: the lane that assembles a robot is the lane that solves it, so the robot goes straight from the
-  // assembly into the solver's registers - no input stock, no barrier - and its Rwb is parked in the first nine planes of
-  // the (otherwise idle) input-stock area for the output transform; the planes behind them serve as the re-pack area of the tail.
+  // assembly into the solver's registers - no input stock, no barrier - and its Rwb is parked in LDS for the output transform
+  // (LdsLayout::RPARK).
   constexpr bool DIRECT = G == 1;
-  constexpr bool RPARK = DIRECT && !HESS_ONLY;  // Rwb parked in LDS for the output transform
-  constexpr int R_PLANES = RPARK ? 9 : 0;
-  static_assert(!DIRECT || QPARK || (R_PLANES * SP + 16 * REPACK_RS <= IN_PLANES * SP), "Rwb planes + re-pack records fit the input-stock area");
+  constexpr bool RPARK = Lay::RPARK;
   if constexpr (DIRECT) {
     const long left = end - cursor;
     stock_n = left < 64 ? (int)left : 64;
@@ -1331,11 +1366,7 @@ __global__ __launch_bounds__(64, MIN_WAVES_PER_SIMD) void balance_kernel(const D
     auto after = [&](bool done) {
       if constexpr (RACE > 1) {
         const int mine = (busy & done & (L.status == QC_SOLVED)) ? (1 << sid) : 0;
-        int m = mine | __builtin_amdgcn_update_dpp(0, mine, 0x120 + ROB, 0xF, 0xF, true);  // row_ror by ROB lanes: the partner groups
-        if constexpr (RACE == 4) {
-          m |= __builtin_amdgcn_update_dpp(0, mine, 0x120 + 2 * ROB, 0xF, 0xF, true);
-          m |= __builtin_amdgcn_update_dpp(0, mine, 0x120 + 3 * ROB, 0xF, 0xF, true);
-        }
+        const int m = race_or<ROB, RACE>(mine);
         solved_mask |= (unsigned)m;
         busy = busy & !done & (solved_mask == 0);
       } else {
@@ -1382,19 +1413,11 @@ __global__ __launch_bounds__(64, MIN_WAVES_PER_SIMD) void balance_kernel(const D
       }
       after(done);
     }
-    if constexpr (RACE > 1) {
-      // the winner - the lowest-numbered strategy among those that solved the robot in the deciding
-      // recalculation, or strategy 0 with whatever status it has if none did - parks the result
-      const int win = solved_mask ? __builtin_ctz(solved_mask) : 0;
-      QC_CLK(7, 8);
-      if (slot < stock_n && sid == win) L.template push_result<SP>(sout, slot);
-      __syncthreads();
-      flush_out<Eqp::G, KIN, STR, SP>(Pg, IN(), OUT(), sout, stock_n, lane);
-      QC_CLK_END(8);
-      return;
-    }
+    // RACE: the winner - the lowest-numbered strategy among those that solved the robot in the deciding
+    // recalculation, or strategy 0 with whatever status it has if none did - parks the result (no race: slot = grp)
+    const int win = (RACE > 1 && solved_mask) ? __builtin_ctz(solved_mask) : 0;
     QC_CLK(7, 8);
-    if (grp < stock_n) L.template push_result<SP>(sout, grp);
+    if (slot < stock_n && (RACE == 1 || sid == win)) L.template push_result<SP>(sout, slot);
     __syncthreads();
     flush_out<Eqp::G, KIN, STR, SP>(Pg, IN(), OUT(), sout, stock_n, lane);
     QC_CLK_END(8);
@@ -1430,11 +1453,11 @@ __global__ __launch_bounds__(64, MIN_WAVES_PER_SIMD) void balance_kernel(const D
     if constexpr (QPARK) {
       // the re-pack records live under the output stock: the tail parks its results after its last record read, and the robots that
       // finished on the one-lane body after the tail (their results wait in this lane's registers)
-      finish_on_four_lanes<KIN, Eqp::kUniform, SP, true>(Pg, L, busy, bm, grp, member, lane, sout, sout, warm == nullptr);
+      finish_on_four_lanes<KIN, Eqp::kUniform, SP, true>(Pg, L, busy, bm, grp, member, lane, qc_lds + Lay::REPACK, sout, warm == nullptr);
       if (!busy && mine) L.template push_result<SP>(sout, grp);
     } else {
       if (!busy && mine) L.template push_result<SP>(sout, grp);  // finished in the one- / two-lane layout
-      finish_on_four_lanes<KIN, Eqp::kUniform, SP>(Pg, L, busy, bm, grp, member, lane, sin + R_PLANES * SP, sout, warm == nullptr);
+      finish_on_four_lanes<KIN, Eqp::kUniform, SP>(Pg, L, busy, bm, grp, member, lane, qc_lds + Lay::REPACK, sout, warm == nullptr);
     }
   } else if constexpr (TWIN) {
     // The one-lane dense form has no 4-lane tail (the exchange tile of the 4-lane dense body does not fit next to the Hessian
@@ -1806,7 +1829,7 @@ __global__ __launch_bounds__(128, 2) void balance_pair_kernel(const DevParams* _
     unsigned solved_mask = 0;
     auto after = [&](bool fin) {
       const int me = (busyR & fin & (LR.status == QC_SOLVED)) ? (1 << sid) : 0;
-      const int m = me | __builtin_amdgcn_update_dpp(0, me, 0x120 + 8, 0xF, 0xF, true);  // row_ror 8: the partner group
+      const int m = race_or<8, 2>(me);
       solved_mask |= (unsigned)m;
       busyR = busyR & !fin & (solved_mask == 0);
     };
@@ -1993,6 +2016,20 @@ static int upload_params(qc_handle* h) {
   return QC_OK;
 }
 
+// the kinematic model and the swing planner's constants of a qc_kinematics, into the device constants
+static void copy_kinematics(qc::DevParams& d, const qc_kinematics& k) {
+  std::memcpy(d.hip, k.hip, sizeof(k.hip));
+  std::memcpy(d.links, k.links, sizeof(k.links));
+  d.tau_min = k.tau_min;
+  d.tau_max = k.tau_max;
+  std::memcpy(d.jc_kff, k.jc_kff, sizeof(k.jc_kff));
+  std::memcpy(d.jc_kp, k.jc_kp, sizeof(k.jc_kp));
+  std::memcpy(d.jc_kd, k.jc_kd, sizeof(k.jc_kd));
+  std::memcpy(d.planner_hip, k.planner_hip, sizeof(k.planner_hip));
+  d.planner_k = k.planner_k;
+  d.swing_height = k.swing_height;
+}
+
 // ---------------------------------------------------------------- launch planning
 // One wave per 64-thread block; a group of G lanes per robot.  The group width trades latency for throughput
 // (instructions per steady recalculation: 487 per 16 robots at G = 4, 730 per 32 at G = 2, ~1170 per 64 at G = 1):
@@ -2005,51 +2042,51 @@ static int upload_params(qc_handle* h) {
 // is an error at launch.
 enum { QC_FORM_UNIFORM = 0, QC_FORM_GENERAL = 1, QC_FORM_DENSE = 2 };
 
-template <class EQP, int MINW, int MODE, int RACE = 1>
-static qc_kernel_fn kernel_of(bool kin) {
-  return kin ? (qc_kernel_fn)qc::balance_kernel<EQP, true, MINW, MODE, RACE> : (qc_kernel_fn)qc::balance_kernel<EQP, false, MINW, MODE, RACE>;
-}
-// the kernel instantiation for (form, lanes per robot, mode, racing strategies); mode 2 exists for the uniform G = 4 form only,
-// racing strategies for the 4-lane kernels
-static qc_kernel_fn kernel_for(int form, int G, int mode, bool kin, int race = 1) {
-  using namespace qc;
-#ifdef QC_DEV_ONLY_DENSE1  // development: compile the one-lane dense kernels alone (seconds instead of a minute; tools/kernel_resources.py)
-  (void)form; (void)G; (void)mode; (void)race;
-  return kernel_of<EqpDense, 1, 1>(kin);
-#else
-  if (form == QC_FORM_DENSE && G == 4) return race == 4 ? kernel_of<EqpDense4, 1, 1, 4>(kin) : (race == 2 ? kernel_of<EqpDense4, 1, 1, 2>(kin) : kernel_of<EqpDense4, 1, 1>(kin));
-  if (form == QC_FORM_DENSE) return kernel_of<EqpDense, 1, 1>(kin);
-  if (form == QC_FORM_GENERAL) {
-    if (G == 4 && race == 4) return kernel_of<EqpDiagW<false, 4>, 2, 1, 4>(kin);
-    if (G == 4 && race == 2) return kernel_of<EqpDiagW<false, 4>, 2, 1, 2>(kin);
-    if (G == 4) return kernel_of<EqpDiagW<false, 4>, 2, 1>(kin);
-    if (G == 2) return kernel_of<EqpDiagW<false, 2>, 2, 1>(kin);
-    return kernel_of<EqpDiagW<false, 1>, 2, 1>(kin);
-  }
-  if (G == 4 && mode == 2 && race == 4) return kernel_of<EqpDiagW<true, 4>, 2, 2, 4>(kin);
-  if (G == 4 && mode == 2 && race == 2) return kernel_of<EqpDiagW<true, 4>, 2, 2, 2>(kin);
-  if (G == 4) return mode == 2 ? kernel_of<EqpDiagW<true, 4>, 2, 2>(kin) : kernel_of<EqpDiagW<true, 4>, 2, 1>(kin);
-  if (G == 2) return kernel_of<EqpDiagW<true, 2>, 2, 1>(kin);
-  return kernel_of<EqpDiagW<true, 1>, 2, 1>(kin);
-#endif  // QC_DEV_ONLY_DENSE1
-}
 typedef void (*qc_pair_kernel_fn)(const qc::DevParams*, long, qc::BatchIn, const uint32_t*, qc::BatchOut, int, int, int, unsigned);
-static qc_pair_kernel_fn pair_kernel_for(int form) {
-  using namespace qc;
-#ifdef QC_DEV_ONLY_DENSE1
-  (void)form;
-  return nullptr;
-#else
-  return form == QC_FORM_UNIFORM ? (qc_pair_kernel_fn)balance_pair_kernel<EqpDiagW<true, 1>, false> : (qc_pair_kernel_fn)balance_pair_kernel<EqpDiagW<false, 1>, false>;
-#endif
+template <class EQP>
+struct FormOf { static constexpr int value = QC_FORM_DENSE; };
+template <bool UNIFORM, int G>
+struct FormOf<qc::EqpDiagW<UNIFORM, G>> { static constexpr int value = UNIFORM ? QC_FORM_UNIFORM : QC_FORM_GENERAL; };
+
+// One row per kernel instantiation, built from the instantiation itself: what it serves (form, lanes per robot, mode, racing
+// strategies), its entry points without and with joint_q, and the dynamic LDS each of them is launched with (qc::LdsLayout, which
+// the kernel addresses by).  Mode 2 exists for the uniform G = 4 form only, racing strategies for the 4-lane kernels.
+struct qc_kernel_row {
+  int form, G, mode, race;
+  qc_kernel_fn fn[2];  // [joint_q]
+  size_t lds[2];
+  qc_pair_kernel_fn pfn;  // mode 3
+};
+template <class EQP, int MINW, int MODE, int RACE = 1>
+static qc_kernel_row kernel_row() {
+  qc_kernel_row r{FormOf<EQP>::value, EQP::G, MODE, RACE, {nullptr, nullptr}, {qc::LdsLayout<EQP, false, MODE>::BYTES, qc::LdsLayout<EQP, true, MODE>::BYTES}, nullptr};
+  r.fn[1] = (qc_kernel_fn)qc::balance_kernel<EQP, true, MINW, MODE, RACE>;
+  r.fn[0] = (qc_kernel_fn)qc::balance_kernel<EQP, false, MINW, MODE, RACE>;
+  return r;
 }
-static size_t lds_for(int form, int G, int mode, bool kin = false) {
-  if (mode == 3) return 0;  // (static LDS: Rwb rows, record list, two counters)
-  if (kin && G == 1 && mode == 1 && form != QC_FORM_DENSE) return (size_t)qc::qpark_doubles() * sizeof(double);  // (balance_kernel: QPARK)
-  if (form == QC_FORM_DENSE && G != 4) return (size_t)78 * 64 * sizeof(double);  // the Hessian planes alone (balance_kernel: HESS_ONLY)
-  const size_t stock = (size_t)qc::stock_doubles(qc::stock_slots(G)) * sizeof(double);
-  if (form == QC_FORM_DENSE) return stock + (size_t)qc::EqpDense4::X_DOUBLES * sizeof(double);
-  return stock;
+template <class EQP>
+static qc_kernel_row pair_kernel_row() {  // (static LDS: Rwb rows, record list, two counters; QP only)
+  return qc_kernel_row{FormOf<EQP>::value, 1, 3, 1, {nullptr, nullptr}, {0, 0}, (qc_pair_kernel_fn)qc::balance_pair_kernel<EQP, false>};
+}
+static const qc_kernel_row* kernel_row_for(int form, int G, int mode, int race = 1) {
+  using namespace qc;
+  static const qc_kernel_row rows[] = {
+#ifdef QC_DEV_ONLY_DENSE1  // development: compile the one-lane dense kernels alone (seconds instead of a minute; tools/kernel_resources.py).
+      // Such a library is for reading the compiler's figures: it plans no launch (the planner needs the 4-lane row of the form).
+      kernel_row<EqpDense, 1, 1>(),
+#else
+      kernel_row<EqpDense4, 1, 1, 4>(),         kernel_row<EqpDense4, 1, 1, 2>(),         kernel_row<EqpDense4, 1, 1>(),
+      kernel_row<EqpDense, 1, 1>(),
+      kernel_row<EqpDiagW<false, 4>, 2, 1, 4>(), kernel_row<EqpDiagW<false, 4>, 2, 1, 2>(), kernel_row<EqpDiagW<false, 4>, 2, 1>(),
+      kernel_row<EqpDiagW<false, 2>, 2, 1>(),    kernel_row<EqpDiagW<false, 1>, 2, 1>(),
+      kernel_row<EqpDiagW<true, 4>, 2, 2, 4>(),  kernel_row<EqpDiagW<true, 4>, 2, 2, 2>(),  kernel_row<EqpDiagW<true, 4>, 2, 2>(),
+      kernel_row<EqpDiagW<true, 4>, 2, 1>(),     kernel_row<EqpDiagW<true, 2>, 2, 1>(),     kernel_row<EqpDiagW<true, 1>, 2, 1>(),
+      pair_kernel_row<EqpDiagW<true, 1>>(),      pair_kernel_row<EqpDiagW<false, 1>>(),
+#endif
+  };
+  for (const qc_kernel_row& r : rows)
+    if (r.form == form && r.G == G && r.mode == mode && r.race == race) return &r;
+  return nullptr;
 }
 // workgroups of this kernel the device holds at once (registers, LDS and the 32-waves-per-CU cap, as the runtime sees them)
 static long resident_workgroups(qc_handle* h, const void* fn, size_t lds, int threads = 64) {
@@ -2077,11 +2114,19 @@ struct qc_launch_plan {
   long resident;
 };
 
+// the formulation a handle runs (resolve_form)
+static int form_of(const qc_handle* h) { return !h->diag_w ? QC_FORM_DENSE : (h->uniform ? QC_FORM_UNIFORM : QC_FORM_GENERAL); }
+
 static int plan_launch(qc_handle* h, long n, bool kin, bool warm, qc_launch_plan* lp) {
-  const int form = !h->diag_w ? QC_FORM_DENSE : (h->uniform ? QC_FORM_UNIFORM : QC_FORM_GENERAL);
+  const int form = form_of(h);
+  // (a kernel that is not instantiated is an error, never another kernel in its place)
+  auto row = [&](int G, int mode, int race = 1) { return kernel_row_for(form, G, mode, race); };
+  const auto no_kernel = [] { return fail(QC_ERR_INVALID, "plan_launch: no kernel instantiation serves this form, group width, mode and race"); };
   int G = 1;
   const long simds = (long)h->cus * 4;
-  const long cap4 = resident_workgroups(h, (const void*)kernel_for(form, 4, 1, kin), lds_for(form, 4, 1, kin)) * 16;
+  const qc_kernel_row* const r4 = row(4, 1);
+  if (!r4) return no_kernel();
+  const long cap4 = resident_workgroups(h, (const void*)r4->fn[kin], r4->lds[kin]) * 16;
   if (form != QC_FORM_DENSE) {
     G = n <= 16 * simds ? 4 : (n <= 32 * simds ? 2 : 1);
     if (h->group_override) G = h->group_override;
@@ -2104,11 +2149,14 @@ static int plan_launch(qc_handle* h, long n, bool kin, bool warm, qc_launch_plan
   // waves' stragglers is mostly a longer chain at the end of the launch.  (Not the joint_q variants: they always run as
   // one-fill workgroups.)
   if (form != QC_FORM_DENSE && G == 1 && !kin && h->chunk_override <= 0) {
-    const long res1 = resident_workgroups(h, (const void*)kernel_for(form, 1, 1, kin), lds_for(form, 1, 1, kin));
+    const qc_kernel_row* const r1 = row(1, 1);
+    const qc_kernel_row* const rp = row(1, 3);
+    if (!r1 || !rp) return no_kernel();
+    const long res1 = resident_workgroups(h, (const void*)r1->fn[kin], r1->lds[kin]);
     bool use_pair = n >= 4 * res1 * 64;
     if (h->pair_override >= 0) use_pair = h->pair_override != 0;
     if (use_pair) {
-      lp->pfn = pair_kernel_for(form);
+      lp->pfn = rp->pfn;
       lp->fn = nullptr;
       lp->lds = 0;
       lp->blocks = (unsigned)((n + 127) / 128);
@@ -2125,7 +2173,9 @@ static int plan_launch(qc_handle* h, long n, bool kin, bool warm, qc_launch_plan
     }
   }
   const long rpw = 64 / G;  // robots per wave fill
-  const long resident = resident_workgroups(h, (const void*)kernel_for(form, G, 1, kin), lds_for(form, G, 1, kin));
+  const qc_kernel_row* const rg = row(G, 1);
+  if (!rg) return no_kernel();
+  const long resident = resident_workgroups(h, (const void*)rg->fn[kin], rg->lds[kin]);
   long chunk = h->chunk_override > 0 ? h->chunk_override : rpw;
   const long blocks = (n + chunk - 1) / chunk;
   // one wave per SIMD is enough: the recalculation's constants stay resident in VGPRs (uniform G = 4 form)
@@ -2142,9 +2192,11 @@ static int plan_launch(qc_handle* h, long n, bool kin, bool warm, qc_launch_plan
     if (h->race_override >= 0) race = (h->race_override == 4 && n <= 4 * simds) ? 4 : ((h->race_override >= 2 && n <= 8 * simds) ? 2 : 1);
     chunk = 16 / race;
   }
-  lp->fn = kernel_for(form, G, mode, kin, race);
+  const qc_kernel_row* const rk = row(G, mode, race);
+  if (!rk) return no_kernel();
+  lp->fn = rk->fn[kin];
   lp->race = race;
-  lp->lds = lds_for(form, G, mode, kin);
+  lp->lds = rk->lds[kin];
   lp->blocks = (unsigned)((n + chunk - 1) / chunk);
   lp->chunk = chunk;
   lp->G = G;
@@ -2172,7 +2224,8 @@ int qc_check_abi(int abi_version, size_t sizeof_params, size_t sizeof_batch_in, 
 }
 const char* qc_kernel_name(const qc_handle* h) {
   if (!h) return "";
-  return h->diag_w ? (h->uniform ? "diagW-6x6-uniform" : "diagW-6x6") : "dense-12x12";
+  static const char* const names[] = {"diagW-6x6-uniform", "diagW-6x6", "dense-12x12"};  // QC_FORM_*
+  return names[form_of(h)];
 }
 
 void qc_default_kinematics(qc_kinematics* k) {
@@ -2227,16 +2280,7 @@ int qc_set_kinematics(qc_handle* h, const qc_kinematics* kin) {
   qc_kinematics k;
   if (kin) k = *kin; else qc_default_kinematics(&k);
   if (!(k.tau_min <= k.tau_max)) return fail(QC_ERR_INVALID, "qc_set_kinematics: need tau_min <= tau_max");
-  std::memcpy(h->dp.hip, k.hip, sizeof(k.hip));
-  std::memcpy(h->dp.links, k.links, sizeof(k.links));
-  h->dp.tau_min = k.tau_min;
-  h->dp.tau_max = k.tau_max;
-  std::memcpy(h->dp.jc_kff, k.jc_kff, sizeof(k.jc_kff));
-  std::memcpy(h->dp.jc_kp, k.jc_kp, sizeof(k.jc_kp));
-  std::memcpy(h->dp.jc_kd, k.jc_kd, sizeof(k.jc_kd));
-  std::memcpy(h->dp.planner_hip, k.planner_hip, sizeof(k.planner_hip));
-  h->dp.planner_k = k.planner_k;
-  h->dp.swing_height = k.swing_height;
+  copy_kinematics(h->dp, k);
   return upload_params(h);
 }
 
@@ -2339,16 +2383,7 @@ int qc_create_abi(const qc_params* p, int device, qc_handle** out, int abi_versi
   {
     qc_kinematics k;
     qc_default_kinematics(&k);
-    std::memcpy(d.hip, k.hip, sizeof(k.hip));
-    std::memcpy(d.links, k.links, sizeof(k.links));
-    d.tau_min = k.tau_min;
-    d.tau_max = k.tau_max;
-    std::memcpy(d.jc_kff, k.jc_kff, sizeof(k.jc_kff));
-    std::memcpy(d.jc_kp, k.jc_kp, sizeof(k.jc_kp));
-    std::memcpy(d.jc_kd, k.jc_kd, sizeof(k.jc_kd));
-    std::memcpy(d.planner_hip, k.planner_hip, sizeof(k.planner_hip));
-    d.planner_k = k.planner_k;
-    d.swing_height = k.swing_height;
+    copy_kinematics(d, k);
     d.t_swing = 0.18;  // mit_cheetah_config.yaml:17-18
     d.t_stance = 0.8;
     sextic_basis(d.traj_basis);
@@ -2445,7 +2480,7 @@ int qc_query_launch(qc_handle* h, size_t n, int kin, int warm, qc_launch_info* o
   if (rc != QC_OK) return rc;
   out->lanes_per_robot = lp.G;
   out->mode = lp.mode;
-  out->form = !h->diag_w ? QC_FORM_DENSE : (h->uniform ? QC_FORM_UNIFORM : QC_FORM_GENERAL);
+  out->form = form_of(h);
   out->strategies = lp.race;
   out->chunk = lp.chunk;
   out->blocks = lp.blocks;
@@ -2466,13 +2501,23 @@ void qc_destroy(qc_handle* h) {
 
 static int launch_batch(qc_handle* h, size_t n, bool kin, const qc::BatchIn& bi, const uint32_t* warm, const qc::BatchOut& bo, void* stream);
 
-int qc_control_batch(qc_handle* h, size_t n, const qc_batch_in* in, const uint32_t* warm, const qc_batch_out* out, void* stream) {
-  if (!h || !in || !out) return fail(QC_ERR_INVALID, "qc_control_batch: null argument");
+// The argument check the batch entry points share (`who`: the entry point, for the message; built only on failure).  The two
+// have always tested the required outputs and "joint_tau needs joint_q" in opposite orders; `outputs_first` keeps each its own.
+static int check_batch_args(const char* who, const qc_handle* h, size_t n, const qc_batch_in* in, const qc_batch_out* out, bool outputs_first) {
+  const auto bad = [who](const char* what) { return fail(QC_ERR_INVALID, std::string(who) + what); };
+  if (!h || !in || !out) return bad(": null argument");
   if (n == 0) return QC_OK;
   if (!in->Rwb || !in->Rwb_d || !in->x || !in->xdot || !in->w || !in->x_d || !in->xdot_d || !in->w_d || (!in->feet && !in->joint_q))
-    return fail(QC_ERR_INVALID, "qc_control_batch: null input array");
-  if (!out->grf_body || !out->status) return fail(QC_ERR_INVALID, "qc_control_batch: grf_body and status are required");
-  if (out->joint_tau && !in->joint_q) return fail(QC_ERR_INVALID, "qc_control_batch: joint_tau needs joint_q");
+    return bad(": null input array");
+  const bool no_outputs = !out->grf_body || !out->status, tau_alone = out->joint_tau && !in->joint_q;
+  if (outputs_first && no_outputs) return bad(": grf_body and status are required");
+  if (tau_alone) return bad(": joint_tau needs joint_q");
+  if (no_outputs) return bad(": grf_body and status are required");
+  return QC_OK;
+}
+
+int qc_control_batch(qc_handle* h, size_t n, const qc_batch_in* in, const uint32_t* warm, const qc_batch_out* out, void* stream) {
+  if (const int rc = check_batch_args("qc_control_batch", h, n, in, out, true); rc != QC_OK || n == 0) return rc;
   QC_HIP(hipSetDevice(h->device));
   const bool kin = in->joint_q != nullptr;
   const int n_sw = (in->swing_pos ? 1 : 0) + (in->swing_vel ? 1 : 0) + (in->joint_qdot ? 1 : 0);
@@ -2543,12 +2588,7 @@ int qc_tick_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_comman
 // stream synchronise instead of a dozen staged copies.
 static constexpr size_t kPinnedMaxN = 8192;  // measured crossover with the staged copies: ~16 384 robots (config 2 records)
 int qc_control_batch_host(qc_handle* h, size_t n, const qc_batch_in* in, const uint32_t* warm, const qc_batch_out* out) {
-  if (!h || !in || !out) return fail(QC_ERR_INVALID, "qc_control_batch_host: null argument");
-  if (n == 0) return QC_OK;
-  if (!in->Rwb || !in->Rwb_d || !in->x || !in->xdot || !in->w || !in->x_d || !in->xdot_d || !in->w_d || (!in->feet && !in->joint_q))
-    return fail(QC_ERR_INVALID, "qc_control_batch_host: null input array");
-  if (out->joint_tau && !in->joint_q) return fail(QC_ERR_INVALID, "qc_control_batch_host: joint_tau needs joint_q");
-  if (!out->grf_body || !out->status) return fail(QC_ERR_INVALID, "qc_control_batch_host: grf_body and status are required");
+  if (const int rc = check_batch_args("qc_control_batch_host", h, n, in, out, false); rc != QC_OK || n == 0) return rc;
   QC_HIP(hipSetDevice(h->device));
   if (!h->stream) QC_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   const bool pinned = n <= kPinnedMaxN;

@@ -1204,6 +1204,7 @@ template <bool UNIFORM, int GROUP>
 struct EqpDiagW {
   static constexpr int G = GROUP;
   static constexpr bool kHessianInLds = false;
+  static constexpr int kLdsDoubles = 0;  // dynamic LDS of its own, next to the stock
   static constexpr bool kStrided = GROUP == 4;  // lane layout of the group, see group_sum
   static constexpr bool kUniform = UNIFORM;
   static constexpr bool kRepackTail = GROUP <= 2;  // one-fill waves finish their stragglers 4 lanes per robot
@@ -1243,6 +1244,7 @@ struct EqpDiagW {
 struct EqpDense {
   static constexpr int G = 1;
   static constexpr bool kHessianInLds = true;  // 78 planes x 64 lanes behind (one-fill workgroups: instead of) the stock
+  static constexpr int kLdsDoubles = 78 * 64;
   static constexpr bool kStrided = false;
   static constexpr bool kRepackTail = false;
   static constexpr bool kNegB = false;
@@ -1441,6 +1443,7 @@ struct EqpDense4 {
   double gscale;  // (unused)
   static constexpr int XS = 17;           // tile stride in doubles (16 robots + 1)
   static constexpr int X_DOUBLES = 156 * XS;
+  static constexpr int kLdsDoubles = X_DOUBLES;
   double* X;        // this robot's column of the wave's exchange tile
   double Qr[3][12]; // rows 3 me .. 3 me + 2 of Q = 2 (A^T S A + W), BC.cpp:152
   double c[3];      // entries of c = -2 A^T S b, BC.cpp:153

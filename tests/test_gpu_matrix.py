@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 RTOL = 1e-6  # of max|GRF| per robot; north_star's bar is 1e-4
 FORMS = {"uniform": {}, "general": {"force_general": 1}, "dense": {"force_dense": 1}}
 FORM_ID = {"uniform": 0, "general": 1, "dense": 2}
-# (form, lanes per robot, mode) -> (tuning, robots): every branch of kernel_for()
+# (form, lanes per robot, mode) -> (tuning, robots): every row of kernel_row_for()
 CASES = []
 for form in ("uniform", "general"):
     CASES += [(form, 1, 1, dict(group=1, one_fill=1), 8200),  # ragged: the last wave holds 8 robots
