@@ -6,10 +6,8 @@
 // for n independent robots per launch.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstddef>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <string>
@@ -17,6 +15,7 @@
 
 #include "../../include/qc_balance.h"
 #include "qc_device.hpp"
+#include "qc_host.hpp"
 
 namespace qc {
 
@@ -1619,7 +1618,7 @@ __global__ __launch_bounds__(64, MIN_WAVES_PER_SIMD) void balance_kernel(const D
 // two-wave workgroup - which is where the planner draws the line.
 constexpr int PAIR_REC = 33;    // doubles per record (odd: the records of the 16 lane groups fall into different banks):
                                 // 0-5 -b, 6 {slot | stance << 8 | face codes << 24 | iters << 48}, 7-18 r, 19-30 f
-constexpr int PAIR_CAP = 32;    // records a wave may leave (hand-over threshold <= PAIR_CAP)
+                                // (PAIR_CAP, the records a wave may leave: qc_device.hpp, the planner clamps the threshold to it)
 struct PairLds {
   double Rrows[128 * 9];                 // Rwb of the workgroup's robots, for the output transform
   double rec[2 * PAIR_CAP * PAIR_REC];   // the record list; once it is drained, the race stage's re-pack area
@@ -1888,123 +1887,28 @@ static_assert(sizeof(qc::CmdState) == sizeof(qc_commander_state) && offsetof(qc:
               "qc::CmdState mirrors qc_commander_state");
 
 struct qc_handle {
-  int device;
-  int cus;                  // compute units of the device
+  int device = 0;
+  int cus = 0;  // compute units of the device
   qc::DevParams dp;
-  qc::DevParams* d_params;  // device copy of dp (rewritten only by the qc_set_* calls, after a device synchronise)
-  bool diag_w;   // W diagonal -> 6x6 formulation
-  bool uniform;  // additionally S diagonal and W = w*I -> scalar-constant specialisation
-  // what qc_create was given: the tuning overrides (force_general / force_dense / max_iter / probe_batch_load) restore from these
-  bool cfg_diag_w, cfg_uniform;
-  bool small_w;     // qc_create's rule: max diag(S) / min diag(W) above QC_DENSE_RATIO - the 6x6 dual forms lose digits that matter there
-  bool auto_dense;  // ... and such a handle runs the dense 12x12 form (qc_set_tuning "auto_dense", default on)
-  int cfg_max_iter;
-  bool force_general, force_dense, probing;
-  // launch heuristics (defaults from measurements; qc_set_tuning overrides them)
-  long chunk_override;     // > 0: robots per wave (at most one fill, 64 / G)
-  int group_override;      // 1, 2, 4: lanes per robot
-  int wave_slots_override; // > 0: resident workgroups assumed for every kernel instead of the occupancy query
-  int race_override;       // -1 heuristic; 0 / 1: no racing strategies; 2, 4: at most that many per robot
-  // resident workgroups per kernel instantiation (hipOccupancyMaxActiveBlocksPerMultiprocessor x CUs), filled lazily
-  struct { const void* fn; size_t lds; long resident; } occ[40];
-  int n_occ;
+  qc::DevParams* d_params = nullptr;  // device copy of dp (rewritten only by the qc_set_* calls, after a device synchronise)
+  qc::Tuning tune;
+  long resident[qc::N_KERNELS][2] = {};  // resident_workgroups' answers per kernel and joint_q variant, 0 = not asked yet
   // staging buffers for the host-pointer entry points
-  void* stage;
-  size_t stage_bytes;
-  void* pin;  // pinned host buffer the kernel reads/writes in place for small batches
-  size_t pin_bytes;
-  uint32_t last_word;  // qc_control(): working set of the previous call (hot start)
-  bool has_last;
-  hipStream_t stream;
-  int pair_override;  // MODE 3 (paired waves): -1 heuristic, 0 never, 1 whenever the form allows it
-  int pair_th;        // hand-over threshold (0: heuristic)
-  int pair_refill;    // free lane groups that trigger a refill (0: heuristic)
-  int pair_solo;      // 1: the last round of workgroups keeps each wave's stragglers in the wave (default), 0: pairs everywhere
+  void* stage = nullptr;
+  size_t stage_bytes = 0;
+  void* pin = nullptr;  // pinned host buffer the kernel reads/writes in place for small batches
+  size_t pin_bytes = 0;
+  uint32_t last_word = 0;  // qc_control(): working set of the previous call (hot start)
+  bool has_last = false;
+  hipStream_t stream = nullptr;
 };
 
-// The 6x6 forms solve the DUAL system M = S^-1 + A~ B^-1 A~^T, whose B^-1 = O(1/w) part has rank = the number of free force
-// coordinates: with fewer than six of them free, M is a rank-k term of size 1/w on top of an S^-1 of order one and the forces
-// (1/w) A~^T v come out with an absolute error of eps (S/w) |b| - 1e-5 N at S/w = 1e9 (the parameter campaigns' 1.4e-5 ... 2.4e-5
-// at w ~ 1e-7, S ~ 100: profiles/r06_fuzz_campaigns.log), 1e-8 N at the reference's S/w = 1e6 (commander_node.cpp:305-307).  The
-// dense 12x12 form factorises the PRIMAL reduced Hessian, which is well-conditioned exactly there (tests/test_gpu_parity.py::
-// test_small_w_golden: < 5e-6 where the dual forms are at 2.4e-5), at three to five times the time.  Above this ratio a handle
-// therefore runs the dense form: accuracy before speed for regularisation weights this far below the reference's.
-#ifndef QC_DENSE_RATIO
-#define QC_DENSE_RATIO 3.0e8
-#endif
-// the formulation a handle runs, from what qc_create was given and the tuning flags - in one place, whatever the order of the calls
-static void resolve_form(qc_handle* h) {
-  h->diag_w = h->cfg_diag_w && !h->force_dense && !(h->small_w && h->auto_dense);
-  h->uniform = h->cfg_uniform && !h->force_general;
-}
-
-static thread_local std::string g_err;
-static int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
+using qc::fail;
 #define QC_HIP(expr)                                                                      \
   do {                                                                                    \
     hipError_t e_ = (expr);                                                               \
     if (e_ != hipSuccess) return fail(QC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
   } while (0)
-
-// Cholesky-based inverse of a small SPD matrix (host, once per handle)
-static bool spd_inverse(const double* A, int n, double* inv) {
-  double L[36];
-  for (int i = 0; i < n; i++)
-    for (int j = 0; j <= i; j++) {
-      double s = A[i * n + j];
-      for (int k = 0; k < j; k++) s -= L[i * n + k] * L[j * n + k];
-      if (i == j) {
-        if (!(s > 0.0)) return false;
-        L[i * n + i] = std::sqrt(s);
-      } else {
-        L[i * n + j] = s / L[j * n + j];
-      }
-    }
-  for (int c = 0; c < n; c++) {
-    double y[6], x[6];
-    for (int i = 0; i < n; i++) {
-      double s = (i == c) ? 1.0 : 0.0;
-      for (int k = 0; k < i; k++) s -= L[i * n + k] * y[k];
-      y[i] = s / L[i * n + i];
-    }
-    for (int i = n - 1; i >= 0; i--) {
-      double s = y[i];
-      for (int k = i + 1; k < n; k++) s -= L[k * n + i] * x[k];
-      x[i] = s / L[i * n + i];
-    }
-    for (int i = 0; i < n; i++) inv[i * n + c] = x[i];
-  }
-  return true;
-}
-
-// Columns 0..2 of the inverse of FootTrajectory::initSystem()'s 7x7 matrix (trajectory.cpp:256-277):
-// the responses of the sextic coefficients to p_start, p_final and p_centre.  basis[3*j + k].
-static void sextic_basis(double* basis) {
-  double A[7][7] = {{1, 0, 0, 0, 0, 0, 0}, {1, 1, 1, 1, 1, 1, 1}, {1, 0.5, 0.25, 0.125, 0.0625, 0.03125, 0.015625},
-                    {0, 1, 0, 0, 0, 0, 0}, {0, 1, 2, 3, 4, 5, 6}, {0, 0, 2, 0, 0, 0, 0}, {0, 0, 2, 6, 12, 20, 30}};
-  double M[7][10];
-  for (int i = 0; i < 7; i++) {
-    for (int j = 0; j < 7; j++) M[i][j] = A[i][j];
-    for (int k = 0; k < 3; k++) M[i][7 + k] = (i == k) ? 1.0 : 0.0;
-  }
-  for (int c = 0; c < 7; c++) {
-    int p = c;
-    for (int r = c + 1; r < 7; r++) if (std::fabs(M[r][c]) > std::fabs(M[p][c])) p = r;
-    for (int j = 0; j < 10; j++) std::swap(M[c][j], M[p][j]);
-    const double piv = M[c][c];
-    for (int j = 0; j < 10; j++) M[c][j] /= piv;
-    for (int r = 0; r < 7; r++) {
-      if (r == c) continue;
-      const double m = M[r][c];
-      for (int j = 0; j < 10; j++) M[r][j] -= m * M[c][j];
-    }
-  }
-  for (int j = 0; j < 7; j++)
-    for (int k = 0; k < 3; k++) basis[3 * j + k] = M[j][7 + k];
-}
 
 // Rewrites the device copy of the constants.  Launches in flight - on any stream, non-blocking ones included -
 // may still be reading the old copy through scalar loads, so the device is drained first; the copy itself is
@@ -2016,198 +1920,68 @@ static int upload_params(qc_handle* h) {
   return QC_OK;
 }
 
-// the kinematic model and the swing planner's constants of a qc_kinematics, into the device constants
-static void copy_kinematics(qc::DevParams& d, const qc_kinematics& k) {
-  std::memcpy(d.hip, k.hip, sizeof(k.hip));
-  std::memcpy(d.links, k.links, sizeof(k.links));
-  d.tau_min = k.tau_min;
-  d.tau_max = k.tau_max;
-  std::memcpy(d.jc_kff, k.jc_kff, sizeof(k.jc_kff));
-  std::memcpy(d.jc_kp, k.jc_kp, sizeof(k.jc_kp));
-  std::memcpy(d.jc_kd, k.jc_kd, sizeof(k.jc_kd));
-  std::memcpy(d.planner_hip, k.planner_hip, sizeof(k.planner_hip));
-  d.planner_k = k.planner_k;
-  d.swing_height = k.swing_height;
-}
-
-// ---------------------------------------------------------------- launch planning
-// One wave per 64-thread block; a group of G lanes per robot.  The group width trades latency for throughput
-// (instructions per steady recalculation: 487 per 16 robots at G = 4, 730 per 32 at G = 2, ~1170 per 64 at G = 1):
-// the planner takes the widest group with which the batch still fits ONE wave per SIMD - such a batch cannot fill
-// the chip anyway and the slowest robot's serial chain is what is timed - i.e. G = 4 up to CUs x 4 x 16 robots
-// (16 384), G = 2 up to twice that, and one lane per robot above (tools/size_scan.py: the cross-overs sit exactly
-// there, cold and warm).  Every width finishes its last <= 16 running robots on the 4-lane body.  Every launch gives
-// each wave one fill (mode 1 / 2) - the hardware scheduler refills the chip with the next workgroup - or, for the
-// one-lane 6x6 kernels of large batches, a workgroup of two waves (mode 3, balance_pair_kernel); a chunk beyond one fill
-// is an error at launch.
-enum { QC_FORM_UNIFORM = 0, QC_FORM_GENERAL = 1, QC_FORM_DENSE = 2 };
-
+// ---------------------------------------------------------------- the kernel table
 typedef void (*qc_pair_kernel_fn)(const qc::DevParams*, long, qc::BatchIn, const uint32_t*, qc::BatchOut, int, int, int, unsigned);
-template <class EQP>
-struct FormOf { static constexpr int value = QC_FORM_DENSE; };
-template <bool UNIFORM, int G>
-struct FormOf<qc::EqpDiagW<UNIFORM, G>> { static constexpr int value = UNIFORM ? QC_FORM_UNIFORM : QC_FORM_GENERAL; };
+// the EQP struct that solves a form on G lanes per robot
+template <int FORM, int G>
+struct EqpOf { using type = qc::EqpDiagW<FORM == qc::QC_FORM_UNIFORM, G>; };
+template <>
+struct EqpOf<qc::QC_FORM_DENSE, 4> { using type = qc::EqpDense4; };
+template <>
+struct EqpOf<qc::QC_FORM_DENSE, 1> { using type = qc::EqpDense; };
 
-// One row per kernel instantiation, built from the instantiation itself: what it serves (form, lanes per robot, mode, racing
-// strategies), its entry points without and with joint_q, and the dynamic LDS each of them is launched with (qc::LdsLayout, which
-// the kernel addresses by).  Mode 2 exists for the uniform G = 4 form only, racing strategies for the 4-lane kernels.
+// One row per key of qc::KERNEL_KEYS (same index): the instantiation's entry points without and with joint_q and the dynamic LDS each
+// is launched with (qc::LdsLayout, which the kernel addresses by), or the paired-waves one (mode 3; static LDS, QP only).
 struct qc_kernel_row {
-  int form, G, mode, race;
   qc_kernel_fn fn[2];  // [joint_q]
   size_t lds[2];
   qc_pair_kernel_fn pfn;  // mode 3
 };
-template <class EQP, int MINW, int MODE, int RACE = 1>
+template <int I>
 static qc_kernel_row kernel_row() {
-  qc_kernel_row r{FormOf<EQP>::value, EQP::G, MODE, RACE, {nullptr, nullptr}, {qc::LdsLayout<EQP, false, MODE>::BYTES, qc::LdsLayout<EQP, true, MODE>::BYTES}, nullptr};
-  r.fn[1] = (qc_kernel_fn)qc::balance_kernel<EQP, true, MINW, MODE, RACE>;
-  r.fn[0] = (qc_kernel_fn)qc::balance_kernel<EQP, false, MINW, MODE, RACE>;
-  return r;
-}
-template <class EQP>
-static qc_kernel_row pair_kernel_row() {  // (static LDS: Rwb rows, record list, two counters; QP only)
-  return qc_kernel_row{FormOf<EQP>::value, 1, 3, 1, {nullptr, nullptr}, {0, 0}, (qc_pair_kernel_fn)qc::balance_pair_kernel<EQP, false>};
-}
-static const qc_kernel_row* kernel_row_for(int form, int G, int mode, int race = 1) {
-  using namespace qc;
-  static const qc_kernel_row rows[] = {
-#ifdef QC_DEV_ONLY_DENSE1  // development: compile the one-lane dense kernels alone (seconds instead of a minute; tools/kernel_resources.py).
-      // Such a library is for reading the compiler's figures: it plans no launch (the planner needs the 4-lane row of the form).
-      kernel_row<EqpDense, 1, 1>(),
-#else
-      kernel_row<EqpDense4, 1, 1, 4>(),         kernel_row<EqpDense4, 1, 1, 2>(),         kernel_row<EqpDense4, 1, 1>(),
-      kernel_row<EqpDense, 1, 1>(),
-      kernel_row<EqpDiagW<false, 4>, 2, 1, 4>(), kernel_row<EqpDiagW<false, 4>, 2, 1, 2>(), kernel_row<EqpDiagW<false, 4>, 2, 1>(),
-      kernel_row<EqpDiagW<false, 2>, 2, 1>(),    kernel_row<EqpDiagW<false, 1>, 2, 1>(),
-      kernel_row<EqpDiagW<true, 4>, 2, 2, 4>(),  kernel_row<EqpDiagW<true, 4>, 2, 2, 2>(),  kernel_row<EqpDiagW<true, 4>, 2, 2>(),
-      kernel_row<EqpDiagW<true, 4>, 2, 1>(),     kernel_row<EqpDiagW<true, 2>, 2, 1>(),     kernel_row<EqpDiagW<true, 1>, 2, 1>(),
-      pair_kernel_row<EqpDiagW<true, 1>>(),      pair_kernel_row<EqpDiagW<false, 1>>(),
-#endif
-  };
-  for (const qc_kernel_row& r : rows)
-    if (r.form == form && r.G == G && r.mode == mode && r.race == race) return &r;
-  return nullptr;
-}
-// workgroups of this kernel the device holds at once (registers, LDS and the 32-waves-per-CU cap, as the runtime sees them)
-static long resident_workgroups(qc_handle* h, const void* fn, size_t lds, int threads = 64) {
-  if (h->wave_slots_override > 0) return h->wave_slots_override;
-  for (int i = 0; i < h->n_occ; i++)
-    if (h->occ[i].fn == fn && h->occ[i].lds == lds) return h->occ[i].resident;
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, lds) != hipSuccess || per_cu <= 0) per_cu = 4;
-  const long r = (long)per_cu * h->cus;
-  if (h->n_occ < (int)(sizeof(h->occ) / sizeof(h->occ[0]))) {
-    h->occ[h->n_occ].fn = fn; h->occ[h->n_occ].lds = lds; h->occ[h->n_occ].resident = r;
-    h->n_occ++;
-  }
-  return r;
-}
-
-struct qc_launch_plan {
-  qc_pair_kernel_fn pfn;  // mode 3
-  int p_th, p_refill;
-  qc_kernel_fn fn;
-  size_t lds;
-  unsigned blocks;
-  long chunk;
-  int G, mode, race;
-  long resident;
-};
-
-// the formulation a handle runs (resolve_form)
-static int form_of(const qc_handle* h) { return !h->diag_w ? QC_FORM_DENSE : (h->uniform ? QC_FORM_UNIFORM : QC_FORM_GENERAL); }
-
-static int plan_launch(qc_handle* h, long n, bool kin, bool warm, qc_launch_plan* lp) {
-  const int form = form_of(h);
-  // (a kernel that is not instantiated is an error, never another kernel in its place)
-  auto row = [&](int G, int mode, int race = 1) { return kernel_row_for(form, G, mode, race); };
-  const auto no_kernel = [] { return fail(QC_ERR_INVALID, "plan_launch: no kernel instantiation serves this form, group width, mode and race"); };
-  int G = 1;
-  const long simds = (long)h->cus * 4;
-  const qc_kernel_row* const r4 = row(4, 1);
-  if (!r4) return no_kernel();
-  const long cap4 = resident_workgroups(h, (const void*)r4->fn[kin], r4->lds[kin]) * 16;
-  if (form != QC_FORM_DENSE) {
-    G = n <= 16 * simds ? 4 : (n <= 32 * simds ? 2 : 1);
-    if (h->group_override) G = h->group_override;
+  constexpr qc::KernelKey k = qc::KERNEL_KEYS[I];
+  using EQP = typename EqpOf<k.form, k.G>::type;
+  constexpr int MINW = k.form == qc::QC_FORM_DENSE ? 1 : 2;
+  if constexpr (k.mode == 3) {
+    return qc_kernel_row{{nullptr, nullptr}, {0, 0}, (qc_pair_kernel_fn)qc::balance_pair_kernel<EQP, false>};
   } else {
-    // dense form: four lanes per robot while the batch fits the resident waves - the latency regime; one lane per robot
-    // with the LDS-staged Hessian above that
-    G = n <= cap4 ? 4 : 1;
-    if (h->group_override) G = h->group_override == 4 ? 4 : 1;
-    // a chunk of 17 ... 64 robots is more than a four-lane wave holds and exactly what a one-lane one-fill wave does (ADVICE r5:
-    // rounds 2-4 served such a request on the one-lane kernel; it must not become an error because the four-lane one would have been picked)
-    if (!h->group_override && G == 4 && h->chunk_override > 16 && h->chunk_override <= 64) G = 1;
+    qc_kernel_row r{{nullptr, nullptr}, {qc::LdsLayout<EQP, false, k.mode>::BYTES, qc::LdsLayout<EQP, true, k.mode>::BYTES}, nullptr};
+    r.fn[1] = (qc_kernel_fn)qc::balance_kernel<EQP, true, MINW, k.mode, k.race>;
+    r.fn[0] = (qc_kernel_fn)qc::balance_kernel<EQP, false, MINW, k.mode, k.race>;
+    return r;
   }
-  lp->pfn = nullptr;
-  lp->p_th = lp->p_refill = 0;
-  // A request the kernels cannot honour is an error, not a silent change of the launch: a wave holds one fill.
-  if (h->chunk_override > 64 / G)
-    return fail(QC_ERR_INVALID, "qc_set_tuning: a chunk beyond one fill (64 / lanes per robot) asks for more robots than a wave holds");
-  // MODE 3 (paired waves): 6x6 forms, one lane per robot, batches of at least four rounds of one-fill workgroups (524 288
-  // robots): measured -5 % there and nothing below (profiles/r03_paired_waves.log) - with few rounds the consumer of two
-  // waves' stragglers is mostly a longer chain at the end of the launch.  (Not the joint_q variants: they always run as
-  // one-fill workgroups.)
-  if (form != QC_FORM_DENSE && G == 1 && !kin && h->chunk_override <= 0) {
-    const qc_kernel_row* const r1 = row(1, 1);
-    const qc_kernel_row* const rp = row(1, 3);
-    if (!r1 || !rp) return no_kernel();
-    const long res1 = resident_workgroups(h, (const void*)r1->fn[kin], r1->lds[kin]);
-    bool use_pair = n >= 4 * res1 * 64;
-    if (h->pair_override >= 0) use_pair = h->pair_override != 0;
-    if (use_pair) {
-      lp->pfn = rp->pfn;
-      lp->fn = nullptr;
-      lp->lds = 0;
-      lp->blocks = (unsigned)((n + 127) / 128);
-      lp->chunk = 128;
-      lp->G = 1;
-      lp->mode = 3;
-      lp->race = 1;
-      // two-wave workgroups of the pair kernel itself (its own registers and 26 KB of static LDS), not half of the one-fill figure
-      lp->resident = resident_workgroups(h, (const void*)lp->pfn, 0, 128);
-      lp->p_th = h->pair_th > 0 ? (h->pair_th < qc::PAIR_CAP ? h->pair_th : qc::PAIR_CAP) : 24;
-      // (1 ... 16 free lane groups: beyond 16 the refill test of the consumer could never fire and it would spin on a full list)
-      lp->p_refill = h->pair_refill > 0 ? (h->pair_refill < 16 ? h->pair_refill : 16) : 4;
-      return QC_OK;
-    }
+}
+template <int... I>
+static const qc_kernel_row& kernel_row_at(int kernel, std::integer_sequence<int, I...>) {
+  static const qc_kernel_row rows[] = {kernel_row<I>()...};
+  return rows[kernel];
+}
+static const qc_kernel_row& kernel_row_at(int kernel) { return kernel_row_at(kernel, std::make_integer_sequence<int, qc::N_KERNELS>()); }
+
+// workgroups of a kernel (its joint_q variant with `kin`) the device holds at once: registers, LDS and the 32-waves-per-CU cap, as
+// the runtime sees them
+static long resident_workgroups(qc_handle* h, int kernel, bool kin) {
+  if (h->tune.wave_slots_override > 0) return h->tune.wave_slots_override;
+  long& r = h->resident[kernel][kin];
+  if (r == 0) {
+    const qc_kernel_row& k = kernel_row_at(kernel);
+    int per_cu = 0;
+    const hipError_t e = k.pfn ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k.pfn, 128, 0)
+                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k.fn[kin], 64, k.lds[kin]);
+    if (e != hipSuccess || per_cu <= 0) per_cu = 4;
+    r = (long)per_cu * h->cus;
   }
-  const long rpw = 64 / G;  // robots per wave fill
-  const qc_kernel_row* const rg = row(G, 1);
-  if (!rg) return no_kernel();
-  const long resident = resident_workgroups(h, (const void*)rg->fn[kin], rg->lds[kin]);
-  long chunk = h->chunk_override > 0 ? h->chunk_override : rpw;
-  const long blocks = (n + chunk - 1) / chunk;
-  // one wave per SIMD is enough: the recalculation's constants stay resident in VGPRs (uniform G = 4 form)
-  const int mode = (form == QC_FORM_UNIFORM && G == 4 && blocks <= (long)h->cus * 4) ? 2 : 1;
-  // ... and when even that leaves SIMDs idle the 4-lane kernels (all three forms) race pivoting strategies on the
-  // same robot (Lane: RACE): four per robot up to CUs x 4 x 4 robots (4 096)
-  int race = 1;
-  if (G == 4 && h->chunk_override <= 0 && (mode == 2 || form != QC_FORM_UNIFORM)) {
-    // (a 2-way race up to 8 192 robots is built and selectable - qc_set_tuning("race", 2) - but measured neutral on
-    // average: its two fewer recalculations pay for the heavier body, tools/race_scan.py)
-    // (cold batches: a warm-started one has little chain to shorten - 10-17 us either way, 0.2-0.6 us dearer with the race,
-    // tools/warm_race_scan.py)
-    race = (!warm && n <= 4 * simds) ? 4 : 1;
-    if (h->race_override >= 0) race = (h->race_override == 4 && n <= 4 * simds) ? 4 : ((h->race_override >= 2 && n <= 8 * simds) ? 2 : 1);
-    chunk = 16 / race;
-  }
-  const qc_kernel_row* const rk = row(G, mode, race);
-  if (!rk) return no_kernel();
-  lp->fn = rk->fn[kin];
-  lp->race = race;
-  lp->lds = rk->lds[kin];
-  lp->blocks = (unsigned)((n + chunk - 1) / chunk);
-  lp->chunk = chunk;
-  lp->G = G;
-  lp->mode = mode;
-  lp->resident = resident;
-  return QC_OK;
+  return r;
+}
+
+// the planner (qc_host.hpp) on a handle's form, tuning and device
+static int plan_launch(qc_handle* h, long n, bool kin, bool warm, qc::LaunchPlan* lp) {
+  return qc::plan_launch(qc::form_of(h->tune), n, kin, warm, h->tune, h->cus, [h](int kernel, bool k) { return resident_workgroups(h, kernel, k); }, lp);
 }
 
 extern "C" {
 
-const char* qc_last_error(void) { return g_err.c_str(); }
+const char* qc_last_error(void) { return qc::g_err.c_str(); }
 int qc_abi_version(void) { return QC_ABI_VERSION; }
 int qc_check_abi(int abi_version, size_t sizeof_params, size_t sizeof_batch_in, size_t sizeof_batch_out) {
   // A caller compiled against another revision of include/qc_balance.h would hand over structs of another size
@@ -2225,29 +1999,10 @@ int qc_check_abi(int abi_version, size_t sizeof_params, size_t sizeof_batch_in, 
 const char* qc_kernel_name(const qc_handle* h) {
   if (!h) return "";
   static const char* const names[] = {"diagW-6x6-uniform", "diagW-6x6", "dense-12x12"};  // QC_FORM_*
-  return names[form_of(h)];
+  return names[qc::form_of(h->tune)];
 }
 
-void qc_default_kinematics(qc_kinematics* k) {
-  if (!k) return;
-  // QuadrupedKinematics::QuadrupedKinematics(), kinematics.cpp:20-47
-  const double xbh = 0.196, ybh = 0.050, zbh = 0.0, l1 = 0.077, l2 = 0.211, l3 = 0.230;
-  const double hip[12] = {-xbh, ybh, zbh, xbh, ybh, zbh, -xbh, -ybh, zbh, xbh, -ybh, zbh};  // RL FL RR FR
-  const double links[12] = {l1, -l2, -l3, l1, -l2, -l3, -l1, -l2, -l3, -l1, -l2, -l3};    // left, left, right, right
-  std::memcpy(k->hip, hip, sizeof(hip));
-  std::memcpy(k->links, links, sizeof(links));
-  k->tau_min = -20.0;  // commander_node.cpp:324-325
-  k->tau_max = 20.0;
-  const double kff[3] = {0.0, 0.0, 0.0}, kp[3] = {40.0, 40.0, 50.0}, kd[3] = {1.0, 1.0, 1.0};  // mit_cheetah_config.yaml:50-53
-  std::memcpy(k->jc_kff, kff, sizeof(kff));
-  std::memcpy(k->jc_kp, kp, sizeof(kp));
-  std::memcpy(k->jc_kd, kd, sizeof(kd));
-  const double xbt = 0.196, ybt = 0.127, zbt = 0.0;  // foot_planner.cpp:27-42
-  const double phip[12] = {-xbt, ybt, zbt, xbt, ybt, zbt, -xbt, -ybt, zbt, xbt, -ybt, zbt};
-  std::memcpy(k->planner_hip, phip, sizeof(phip));
-  k->planner_k = 0.01;     // foot_planner.cpp:25
-  k->swing_height = 0.08;  // gait/height, commander_node.cpp:247
-}
+void qc_default_kinematics(qc_kinematics* k) { qc::default_kinematics(k); }
 
 void qc_swing_state_init(qc_swing_state* s, size_t n) {
   if (!s) return;
@@ -2278,9 +2033,9 @@ void qc_commander_state_init(qc_commander_state* s, size_t n, const double x_sta
 int qc_set_kinematics(qc_handle* h, const qc_kinematics* kin) {
   if (!h) return fail(QC_ERR_INVALID, "qc_set_kinematics: null handle");
   qc_kinematics k;
-  if (kin) k = *kin; else qc_default_kinematics(&k);
+  if (kin) k = *kin; else qc::default_kinematics(&k);
   if (!(k.tau_min <= k.tau_max)) return fail(QC_ERR_INVALID, "qc_set_kinematics: need tau_min <= tau_max");
-  copy_kinematics(h->dp, k);
+  qc::copy_kinematics(h->dp, k);
   return upload_params(h);
 }
 
@@ -2303,116 +2058,14 @@ int qc_create_abi(const qc_params* p, int device, qc_handle** out, int abi_versi
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return fail(QC_ERR_NO_DEVICE, "qc_create: no HIP device visible (this library has no CPU path)");
   if (device < 0 || device >= ndev) return fail(QC_ERR_INVALID, "qc_create: device ordinal out of range");
-  if (!(p->mu > 0.0) || !(p->mass > 0.0)) return fail(QC_ERR_INVALID, "qc_create: mu and mass must be > 0");
-  if (!(p->fzmin >= 0.0) || !(p->fzmax >= p->fzmin)) return fail(QC_ERR_INVALID, "qc_create: need 0 <= fzmin <= fzmax");
-  // The cone rows of the reference are two-sided with +-1e6 on the far side (BC.cpp:296-301: -1e6 <= fx - mu fz <= 0, ...).
-  // Inside the cone |fx -+ mu fz| <= 2 mu fz <= 2 mu fzmax, so those sides cannot bind - and this solver does not carry
-  // them - as long as 2 mu fzmax < 1e6.  Parameters beyond that would make the reference's QP a different one: refused.
-  // (the hand-over records of the re-packed tails carry the recalculation count in 16 bits)
-  if (p->max_iter > QC_MAX_ITER_LIMIT) return fail(QC_ERR_INVALID, "qc_create: max_iter must be <= 65535");
-  if (!(2.0 * p->mu * p->fzmax < 1.0e6))
-    return fail(QC_ERR_INVALID, "qc_create: need 2 * mu * fzmax < 1e6 (the +-1e6 sides of the reference's cone rows, balance_controller.cpp:296-301, are not carried)");
-  for (int i = 0; i < 6; i++)
-    for (int j = 0; j < i; j++)
-      if (std::fabs(p->S[6 * i + j] - p->S[6 * j + i]) > 1e-12 * (std::fabs(p->S[6 * i + i]) + std::fabs(p->S[6 * j + j])))
-        return fail(QC_ERR_INVALID, "qc_create: S must be symmetric");
-  bool diag = true;
-  for (int i = 0; i < 12; i++) {
-    if (!(p->W[12 * i + i] > 0.0)) return fail(QC_ERR_INVALID, "qc_create: W must be positive definite");
-    for (int j = 0; j < 12; j++)
-      if (i != j && p->W[12 * i + j] != 0.0) diag = false;
-  }
-  for (int i = 0; i < 12; i++)
-    for (int j = 0; j < i; j++)
-      if (std::fabs(p->W[12 * i + j] - p->W[12 * j + i]) > 1e-12 * (p->W[12 * i + i] + p->W[12 * j + j]))
-        return fail(QC_ERR_INVALID, "qc_create: W must be symmetric");
-
+  if (const int rc = qc::check_params(p); rc != QC_OK) return rc;
   qc_handle* h = new (std::nothrow) qc_handle();
   if (!h) return fail(QC_ERR_INVALID, "qc_create: out of memory");
   h->device = device;
-  h->diag_w = diag;
-  h->stage = nullptr;
-  h->stage_bytes = 0;
-  h->pin = nullptr;
-  h->pin_bytes = 0;
-  h->last_word = 0;
-  h->has_last = false;
-  h->stream = nullptr;
-  h->d_params = nullptr;
-  qc::DevParams& d = h->dp;
-  std::memset(&d, 0, sizeof(d));
-  d.mu = p->mu; d.mass = p->mass; d.fzmin = p->fzmin; d.fzmax = p->fzmax;
-  std::memcpy(d.Ib, p->Ib, sizeof(d.Ib));
-  std::memcpy(d.S, p->S, sizeof(d.S));
-  if (!spd_inverse(p->S, 6, d.V)) { delete h; return fail(QC_ERR_INVALID, "qc_create: S must be positive definite"); }
-  for (int i = 0; i < 12; i++) d.w[i] = p->W[12 * i + i];
-  std::memcpy(d.W, p->W, sizeof(d.W));
-  for (int i = 0; i < 4; i++) {
-    d.inv_wx[i] = 1.0 / d.w[3 * i];
-    d.inv_wy[i] = 1.0 / d.w[3 * i + 1];
-    for (int a = 0; a < 2; a++)
-      for (int b = 0; b < 2; b++)
-        d.inv_bz[4 * i + 2 * a + b] = 1.0 / (d.w[3 * i + 2] + p->mu * p->mu * (a * d.w[3 * i] + b * d.w[3 * i + 1]));
-  }
-  bool uni = diag;
-  for (int i = 0; i < 6; i++)
-    for (int j = 0; j < 6; j++)
-      if (i != j && p->S[6 * i + j] != 0.0) uni = false;
-  for (int i = 1; i < 12; i++)
-    if (p->W[12 * i + i] != p->W[0]) uni = false;
-  h->cfg_diag_w = diag;
-  h->cfg_uniform = uni;
-  h->force_general = h->force_dense = h->probing = false;
-  {
-    double smax = 0.0, wmin = p->W[0];
-    for (int i = 0; i < 6; i++) smax = std::fmax(smax, p->S[6 * i + i]);
-    for (int i = 1; i < 12; i++) wmin = std::fmin(wmin, p->W[12 * i + i]);
-    h->small_w = diag && smax > QC_DENSE_RATIO * wmin;
-    h->auto_dense = true;
-  }
-  resolve_form(h);
-  for (int i = 0; i < 6; i++) d.Vd[i] = d.V[6 * i + i];
-  d.w_u = p->W[0];
-  d.inv_w_u = 1.0 / p->W[0];
-  for (int k = 0; k < 3; k++) d.inv_bz_u[k] = 1.0 / (p->W[0] * (1.0 + p->mu * p->mu * k));
-  std::memcpy(d.kff, p->kff, sizeof(d.kff));
-  std::memcpy(d.kp_p, p->kp_p, sizeof(d.kp_p));
-  std::memcpy(d.kd_p, p->kd_p, sizeof(d.kd_p));
-  std::memcpy(d.kp_w, p->kp_w, sizeof(d.kp_w));
-  std::memcpy(d.kd_w, p->kd_w, sizeof(d.kd_w));
-  {
-    qc_kinematics k;
-    qc_default_kinematics(&k);
-    copy_kinematics(d, k);
-    d.t_swing = 0.18;  // mit_cheetah_config.yaml:17-18
-    d.t_stance = 0.8;
-    sextic_basis(d.traj_basis);
-  }
-  d.stance_phase = 0.8 / (0.18 + 0.8);  // mit_cheetah_config.yaml:17-18
-  // Multiplier tolerance, relative to max(1, |grad|_inf).  It has to sit just above the rounding noise of the
-  // multipliers, not at a "reasonable" 1e-9: along a weakly active face the objective curves only with 2w, so a
-  // multiplier accepted at -tol*|g| leaves the force tol*|g|/(2w) away from the minimiser (w = 2.8e-7, |g| ~ 1e6:
-  // 1e-12 gave 0.2 N = 2e-3 relative in the parameter fuzz; 1e-13 ... 1e-15 all agree with the NNLS restatement
-  // and change neither the recalculation counts of 1 M robots nor anything else measurable).
-  d.tol_d = 1e-14;
-  d.tol_start = d.tol_d;  // (polish on)
-  d.max_iter = p->max_iter > 0 ? p->max_iter : 200;
-  h->cfg_max_iter = d.max_iter;
-  d.clamp_steps = 0;  // 0: per kernel (clamp_steps_for)
-  d.tail_race = 1;
-  d.polish = 1;  // the polish at acceptance (Lane::iterate)
+  if (const int rc = qc::derive_params(p, h->dp, h->tune); rc != QC_OK) { delete h; return rc; }
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) != hipSuccess) { delete h; return fail(QC_ERR_HIP, "qc_create: hipGetDeviceProperties failed"); }
   h->cus = prop.multiProcessorCount;
-  h->chunk_override = 0;
-  h->group_override = 0;
-  h->wave_slots_override = 0;
-  h->race_override = -1;
-  h->pair_override = -1;
-  h->pair_th = 0;
-  h->pair_refill = 0;
-  h->pair_solo = 1;
-  h->n_occ = 0;
   if (hipSetDevice(device) != hipSuccess || hipMalloc((void**)&h->d_params, sizeof(qc::DevParams)) != hipSuccess ||
       hipMemcpy(h->d_params, &h->dp, sizeof(qc::DevParams), hipMemcpyHostToDevice) != hipSuccess) {
     delete h;
@@ -2424,68 +2077,26 @@ int qc_create_abi(const qc_params* p, int device, qc_handle** out, int abi_versi
 
 int qc_set_tuning(qc_handle* h, const char* key, double value) {
   if (!h || !key) return fail(QC_ERR_INVALID, "qc_set_tuning: null argument");
-  const std::string k(key);
-  bool params = false;
-  if (k == "group") {
-    const int g = (int)value;
-    if (g != 0 && g != 1 && g != 2 && g != 4) return fail(QC_ERR_INVALID, "qc_set_tuning: group is 0 (heuristic), 1, 2 or 4");
-    h->group_override = g;
-  } else if (k == "one_fill") {  // (-1 heuristic / 1 always: every launch is one fill per wave, the key stays for existing callers)
-    if (value == 0) return fail(QC_ERR_INVALID, "qc_set_tuning: one_fill = 0 asked for the persistent-wave kernels, which were removed");
-  }
-  else if (k == "chunk") h->chunk_override = value > 0 ? (long)value : 0;
-  else if (k == "wave_slots") h->wave_slots_override = value > 0 ? (int)value : 0;
-  else if (k == "race") {  // (0 / 1 also switch the race in the 4-lane tail of the wider kernels off)
-    h->race_override = value < 0 ? -1 : (int)value;
-    h->dp.tail_race = (value < 0 || value >= 2) ? 1 : 0;
-    params = true;
-  }
-  else if (k == "pair") h->pair_override = value < 0 ? -1 : (value != 0 ? 1 : 0);
-  else if (k == "pair_th") h->pair_th = value > 0 ? (int)value : 0;
-  else if (k == "pair_refill") h->pair_refill = value > 0 ? (int)value : 0;
-  else if (k == "pair_solo") h->pair_solo = value != 0 ? 1 : 0;
-  else if (k == "force_general" || k == "force_dense") {
-    // general 6x6 form on uniform weights / dense 12x12 form on a diagonal W (same minimiser).  The form follows from what
-    // qc_create was given and the two flags, in one place, whatever the order of the calls.
-    (k == "force_general" ? h->force_general : h->force_dense) = value != 0;
-    resolve_form(h);
-  } else if (k == "auto_dense") {  // 0: a diagonal W keeps its 6x6 form however small it is (QC_DENSE_RATIO above)
-    h->auto_dense = value != 0;
-    resolve_form(h);
-  } else if (k == "tol_d") { h->dp.tol_d = value; h->dp.tol_start = h->dp.polish ? value : -value; params = true; }
-  else if (k == "max_iter") {  // <= 0: back to the handle's own cap (qc_params.max_iter)
-    if (value > (double)QC_MAX_ITER_LIMIT) return fail(QC_ERR_INVALID, "qc_set_tuning: max_iter must be <= 65535");
-    h->probing = false;
-    h->dp.max_iter = value > 0 ? (int)value : h->cfg_max_iter; params = true;
-  }
-  else if (k == "clamp_steps") { h->dp.clamp_steps = value >= 1 ? (int)value : 0; params = true; }
-  else if (k == "polish") {  // 0: round 5's acceptance rule
-    h->dp.polish = value != 0 ? 1 : 0;
-    h->dp.tol_start = h->dp.polish ? h->dp.tol_d : -h->dp.tol_d;
-    params = true;
-  }
-  else if (k == "probe_batch_load") {
-    // measurement probe: load -> assemble -> store only (every robot reports QC_MAX_ITER); 0 restores the handle's own cap
-    h->probing = value != 0;
-    h->dp.max_iter = h->probing ? 0 : h->cfg_max_iter; params = true;
-  } else return fail(QC_ERR_INVALID, "qc_set_tuning: unknown key '" + k + "'");
-  return params ? upload_params(h) : QC_OK;
+  bool upload = false;
+  if (const int rc = qc::set_tuning(h->tune, h->dp, key, value, &upload); rc != QC_OK) return rc;
+  return upload ? upload_params(h) : QC_OK;
 }
 
 int qc_query_launch(qc_handle* h, size_t n, int kin, int warm, qc_launch_info* out) {
   if (!h || !out) return fail(QC_ERR_INVALID, "qc_query_launch: null argument");
   QC_HIP(hipSetDevice(h->device));
-  qc_launch_plan lp;
+  qc::LaunchPlan lp;
   const int rc = plan_launch(h, (long)(n ? n : 1), kin != 0, warm != 0, &lp);
   if (rc != QC_OK) return rc;
-  out->lanes_per_robot = lp.G;
-  out->mode = lp.mode;
-  out->form = form_of(h);
-  out->strategies = lp.race;
+  const qc::KernelKey& k = qc::KERNEL_KEYS[lp.kernel];
+  out->lanes_per_robot = k.G;
+  out->mode = k.mode;
+  out->form = k.form;
+  out->strategies = k.race;
   out->chunk = lp.chunk;
   out->blocks = lp.blocks;
-  out->resident_workgroups = lp.mode == 3 ? lp.resident : resident_workgroups(h, (const void*)lp.fn, lp.lds);
-  out->lds_bytes = (int64_t)lp.lds;
+  out->resident_workgroups = resident_workgroups(h, lp.kernel, kin != 0);
+  out->lds_bytes = (int64_t)kernel_row_at(lp.kernel).lds[kin != 0];
   return QC_OK;
 }
 
@@ -2499,33 +2110,30 @@ void qc_destroy(qc_handle* h) {
   delete h;
 }
 
-static int launch_batch(qc_handle* h, size_t n, bool kin, const qc::BatchIn& bi, const uint32_t* warm, const qc::BatchOut& bo, void* stream);
-
-// The argument check the batch entry points share (`who`: the entry point, for the message; built only on failure).  The two
-// have always tested the required outputs and "joint_tau needs joint_q" in opposite orders; `outputs_first` keeps each its own.
-static int check_batch_args(const char* who, const qc_handle* h, size_t n, const qc_batch_in* in, const qc_batch_out* out, bool outputs_first) {
-  const auto bad = [who](const char* what) { return fail(QC_ERR_INVALID, std::string(who) + what); };
-  if (!h || !in || !out) return bad(": null argument");
-  if (n == 0) return QC_OK;
-  if (!in->Rwb || !in->Rwb_d || !in->x || !in->xdot || !in->w || !in->x_d || !in->xdot_d || !in->w_d || (!in->feet && !in->joint_q))
-    return bad(": null input array");
-  const bool no_outputs = !out->grf_body || !out->status, tau_alone = out->joint_tau && !in->joint_q;
-  if (outputs_first && no_outputs) return bad(": grf_body and status are required");
-  if (tau_alone) return bad(": joint_tau needs joint_q");
-  if (no_outputs) return bad(": grf_body and status are required");
+// the one launch behind qc_control_batch and qc_tick_batch (arguments validated)
+static int launch_batch(qc_handle* h, size_t n, bool kin, const qc::BatchIn& bi, const uint32_t* warm, const qc::BatchOut& bo, void* stream) {
+  qc::LaunchPlan lp;
+  const int rc = plan_launch(h, (long)n, kin, warm != nullptr, &lp);
+  if (rc != QC_OK) return rc;
+  const qc_kernel_row& r = kernel_row_at(lp.kernel);
+  if (r.pfn) {  // mode 3
+    // the last round of workgroups (those behind which nothing waits for a slot) runs solo
+    const long solo_from = h->tune.pair_solo == 0 ? (long)lp.blocks : ((long)lp.blocks > lp.resident ? (long)lp.blocks - lp.resident : 0);
+    r.pfn<<<dim3(lp.blocks), dim3(128), 0, (hipStream_t)stream>>>(h->d_params, (long)n, bi, warm, bo, lp.p_th, lp.p_refill,
+                                                                  h->dp.tail_race && warm == nullptr ? 1 : 0, (unsigned)solo_from);
+    QC_HIP(hipGetLastError());
+    return QC_OK;
+  }
+  r.fn[kin]<<<dim3(lp.blocks), dim3(64), r.lds[kin], (hipStream_t)stream>>>(h->d_params, (long)n, bi, warm, bo, lp.chunk);
+  QC_HIP(hipGetLastError());
   return QC_OK;
 }
 
 int qc_control_batch(qc_handle* h, size_t n, const qc_batch_in* in, const uint32_t* warm, const qc_batch_out* out, void* stream) {
-  if (const int rc = check_batch_args("qc_control_batch", h, n, in, out, true); rc != QC_OK || n == 0) return rc;
+  if (const int rc = qc::check_batch_args("qc_control_batch", h, n, in, out, true); rc != QC_OK || n == 0) return rc;
   QC_HIP(hipSetDevice(h->device));
   const bool kin = in->joint_q != nullptr;
-  const int n_sw = (in->swing_pos ? 1 : 0) + (in->swing_vel ? 1 : 0) + (in->joint_qdot ? 1 : 0);
-  if (!in->swing_state && n_sw != 0 && (n_sw != 3 || !in->joint_q || !out->joint_tau))
-    return fail(QC_ERR_INVALID, "qc_control_batch: swing_pos, swing_vel and joint_qdot go together and need joint_q and joint_tau");
-  if (in->gait_dt && (!in->gait_phase || in->stance)) return fail(QC_ERR_INVALID, "qc_control_batch: gait_dt advances gait_phase (needed, and stance must be NULL)");
-  if (in->swing_state && (!in->joint_q || !in->joint_qdot || !in->gait_phase || !out->joint_tau || in->swing_pos || in->swing_vel))
-    return fail(QC_ERR_INVALID, "qc_control_batch: swing_state needs joint_q, joint_qdot, gait_phase and joint_tau, and excludes swing_pos/swing_vel");
+  if (const int rc = qc::check_swing_gait_args(in, out); rc != QC_OK) return rc;
   qc::BatchIn bi{in->Rwb, in->Rwb_d, in->x, in->xdot, in->w, in->x_d, in->xdot_d, in->w_d, in->feet, in->stance, in->joint_q,
                  in->gait_phase, in->gait_duty, in->swing_pos, in->swing_vel, in->joint_qdot,
                  reinterpret_cast<qc::SwingState*>(in->swing_state), in->gait_dt};
@@ -2533,44 +2141,9 @@ int qc_control_batch(qc_handle* h, size_t n, const qc_batch_in* in, const uint32
   return launch_batch(h, n, kin, bi, warm, bo, stream);
 }
 
-// the one launch behind qc_control_batch and qc_tick_batch (arguments validated)
-static int launch_batch(qc_handle* h, size_t n, bool kin, const qc::BatchIn& bi, const uint32_t* warm, const qc::BatchOut& bo, void* stream) {
-  qc_launch_plan lp;
-  const int rc = plan_launch(h, (long)n, kin, warm != nullptr, &lp);
-  if (rc != QC_OK) return rc;
-  if (lp.mode == 3) {
-    // the last round of workgroups (those behind which nothing waits for a slot) runs solo
-    const long solo_from = h->pair_solo == 0 ? (long)lp.blocks : ((long)lp.blocks > lp.resident ? (long)lp.blocks - lp.resident : 0);
-    lp.pfn<<<dim3(lp.blocks), dim3(128), 0, (hipStream_t)stream>>>(h->d_params, (long)n, bi, warm, bo, lp.p_th, lp.p_refill,
-                                                                  h->dp.tail_race && warm == nullptr ? 1 : 0, (unsigned)solo_from);
-    QC_HIP(hipGetLastError());
-    return QC_OK;
-  }
-  lp.fn<<<dim3(lp.blocks), dim3(64), lp.lds, (hipStream_t)stream>>>(h->d_params, (long)n, bi, warm, bo, lp.chunk);
-  QC_HIP(hipGetLastError());
-  return QC_OK;
-}
-
 int qc_tick_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_command_in* cmd, const uint32_t* warm, const qc_batch_out* out,
                   void* stream) {
-  if (!h || !in || !cmd || !out) return fail(QC_ERR_INVALID, "qc_tick_batch: null argument");
-  if (cmd->struct_size != sizeof(qc_command_in)) {
-    char msg[160];
-    std::snprintf(msg, sizeof(msg), "qc_tick_batch: qc_command_in.struct_size is %zu, this library's qc_command_in has %zu B (qc_default_command sets it)",
-                  cmd->struct_size, sizeof(qc_command_in));
-    return fail(QC_ERR_INVALID, msg);
-  }
-  if (!in->Rwb || !in->x || !in->xdot || !in->w || !in->joint_q || !in->joint_qdot || !in->gait_phase || !in->gait_dt || !in->swing_state)
-    return fail(QC_ERR_INVALID, "qc_tick_batch: the complete tick needs Rwb, x, xdot, w, joint_q, joint_qdot, gait_phase, gait_dt and swing_state");
-  if (in->Rwb_d || in->x_d || in->xdot_d || in->w_d)
-    return fail(QC_ERR_INVALID, "qc_tick_batch: Rwb_d, x_d, xdot_d and w_d must be NULL (the desired state lives in qc_command_in.state)");
-  if (in->stance || in->swing_pos || in->swing_vel)
-    return fail(QC_ERR_INVALID, "qc_tick_batch: stance, swing_pos and swing_vel must be NULL (the gait clock and the planner make them)");
-  if (!out->grf_body || !out->status || !out->joint_tau) return fail(QC_ERR_INVALID, "qc_tick_batch: grf_body, status and joint_tau are required");
-  if (!cmd->state) return fail(QC_ERR_INVALID, "qc_tick_batch: qc_command_in.state is required");
-  if (cmd->fresh && !cmd->twist) return fail(QC_ERR_INVALID, "qc_tick_batch: qc_command_in.fresh needs twist");
-  if (!std::isfinite(cmd->stand_height) || !(cmd->stand_tol >= 0.0) || !std::isfinite(cmd->stand_tol) || !std::isfinite(cmd->cmd_dt))
-    return fail(QC_ERR_INVALID, "qc_tick_batch: stand_height, stand_tol (>= 0) and cmd_dt must be finite");
+  if (const int rc = qc::check_tick_args(h, in, cmd, out); rc != QC_OK) return rc;
   if (n == 0) return QC_OK;
   QC_HIP(hipSetDevice(h->device));
   qc::BatchIn bi{in->Rwb, nullptr, in->x, in->xdot, in->w, nullptr, nullptr, nullptr, in->feet, nullptr, in->joint_q,
@@ -2588,7 +2161,7 @@ int qc_tick_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_comman
 // stream synchronise instead of a dozen staged copies.
 static constexpr size_t kPinnedMaxN = 8192;  // measured crossover with the staged copies: ~16 384 robots (config 2 records)
 int qc_control_batch_host(qc_handle* h, size_t n, const qc_batch_in* in, const uint32_t* warm, const qc_batch_out* out) {
-  if (const int rc = check_batch_args("qc_control_batch_host", h, n, in, out, false); rc != QC_OK || n == 0) return rc;
+  if (const int rc = qc::check_batch_args("qc_control_batch_host", h, n, in, out, false); rc != QC_OK || n == 0) return rc;
   QC_HIP(hipSetDevice(h->device));
   if (!h->stream) QC_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   const bool pinned = n <= kPinnedMaxN;

@@ -20,24 +20,9 @@
 // quadruped_controller/src/quadruped_controller/balance_controller.cpp:98-330
 // (cited below as BC.cpp).
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define QC_DEV __device__ __forceinline__
-// Phase-clock hooks: empty in the product; tools/phase_clock.hip defines them to attribute cycles to phases.
-#ifndef QC_CLK
-#define QC_CLK(from, to)
-#define QC_CLK_BEGIN()
-#define QC_CLK_END(last)
-#define QC_CLK_TAIL_BEGIN()  // harness: the 4-lane tail of a one / two lanes-per-robot wave is clocked into its own slots
-#define QC_CLK_TAIL_LOOP()
-#define QC_CLK_TAIL_END()
-#define QC_CLK_PIN(arr)  // harness: pins the values of `arr` at this point so the scheduler cannot move a phase across its marker
-#endif
-#ifndef QC_CLK_ABS
-#define QC_CLK_ABS(from, to)  // harness: a phase boundary between two absolute clock slots (the torque pass: 13 lists, 14 swing, 15 stance)
-#endif
-
+// First the plain structs and the list of kernel instantiations, which the host logic (qc_host.hpp) and its CPU test read without HIP.
 namespace qc {
 
 // Uniform (per-handle) constants, uploaded once by qc_create.
@@ -73,6 +58,91 @@ struct DevParams {
   int tail_race;       // the 4-lane tail races two drop rules on its last <= 8 robots
   int polish;          // 1: a robot whose smallest multiplier is inside the noise band at its first acceptance releases that face once
 };
+
+// mirrors qc_swing_state (include/qc_balance.h)
+struct SwingState {
+  int32_t leg_state[4];
+  int32_t has_traj[4];
+  double p_start[12];
+  double p_final[12];
+};
+
+// mirrors qc_commander_state (include/qc_balance.h)
+struct CmdState {
+  int32_t standing, gait_running, cmd_pending, reserved;
+  double Vb[6], Rwb_d[9], x_d[3], xdot_d[3], w_d[3];
+};
+
+struct BatchIn {
+  const double *Rwb, *Rwb_d, *x, *xdot, *w, *x_d, *xdot_d, *w_d, *feet;
+  const uint8_t* stance;
+  const double* joint_q;
+  double* gait_phase;  // written when gait_dt is given
+  const double* gait_duty;
+  const double* swing_pos;
+  const double* swing_vel;
+  const double* joint_qdot;
+  struct SwingState* swing_state;
+  const double* gait_dt;
+  // commander mode (qc_tick_batch; cmd_state == NULL everywhere else): the desired state comes from cmd_state, not from
+  // Rwb_d / x_d / xdot_d / w_d (NULL then), and the robot's commander step gates the gait clock and the planner
+  struct CmdState* cmd_state;
+  const double* cmd_twist;
+  const uint8_t* cmd_fresh;
+  double stand_height, stand_tol, cmd_dt;
+};
+struct BatchOut {
+  double* grf_body;
+  int32_t* status;
+  uint32_t* active_set;
+  int32_t* iterations;
+  double* joint_tau;
+};
+
+constexpr int PAIR_CAP = 32;  // records a wave of the paired kernel (mode 3) may leave (hand-over threshold <= PAIR_CAP)
+
+// The formulations and the kernel instantiations, stated once: qc_balance.hip builds its table of entry points from this array and the
+// planner (qc_host.hpp) looks its choice up in it.  Mode 2 exists for the uniform G = 4 form only, racing strategies for the 4-lane
+// kernels, mode 3 (paired waves) for the one-lane 6x6 forms.
+enum { QC_FORM_UNIFORM = 0, QC_FORM_GENERAL = 1, QC_FORM_DENSE = 2 };
+struct KernelKey {
+  int form, G, mode, race;
+};
+constexpr KernelKey KERNEL_KEYS[] = {
+#ifdef QC_DEV_ONLY_DENSE1  // development: compile the one-lane dense kernels alone (seconds instead of a minute; tools/kernel_resources.py).
+    // Such a library is for reading the compiler's figures: it plans no launch (the planner needs the 4-lane row of the form).
+    {QC_FORM_DENSE, 1, 1, 1},
+#else
+    {QC_FORM_DENSE, 4, 1, 4},   {QC_FORM_DENSE, 4, 1, 2},   {QC_FORM_DENSE, 4, 1, 1},   {QC_FORM_DENSE, 1, 1, 1},
+    {QC_FORM_GENERAL, 4, 1, 4}, {QC_FORM_GENERAL, 4, 1, 2}, {QC_FORM_GENERAL, 4, 1, 1}, {QC_FORM_GENERAL, 2, 1, 1}, {QC_FORM_GENERAL, 1, 1, 1},
+    {QC_FORM_UNIFORM, 4, 2, 4}, {QC_FORM_UNIFORM, 4, 2, 2}, {QC_FORM_UNIFORM, 4, 2, 1},
+    {QC_FORM_UNIFORM, 4, 1, 1}, {QC_FORM_UNIFORM, 2, 1, 1}, {QC_FORM_UNIFORM, 1, 1, 1},
+    {QC_FORM_UNIFORM, 1, 3, 1}, {QC_FORM_GENERAL, 1, 3, 1},
+#endif
+};
+constexpr int N_KERNELS = (int)(sizeof(KERNEL_KEYS) / sizeof(KERNEL_KEYS[0]));
+
+}  // namespace qc
+
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+
+#define QC_DEV __device__ __forceinline__
+// Phase-clock hooks: empty in the product; tools/phase_clock.hip defines them to attribute cycles to phases.
+#ifndef QC_CLK
+#define QC_CLK(from, to)
+#define QC_CLK_BEGIN()
+#define QC_CLK_END(last)
+#define QC_CLK_TAIL_BEGIN()  // harness: the 4-lane tail of a one / two lanes-per-robot wave is clocked into its own slots
+#define QC_CLK_TAIL_LOOP()
+#define QC_CLK_TAIL_END()
+#define QC_CLK_PIN(arr)  // harness: pins the values of `arr` at this point so the scheduler cannot move a phase across its marker
+#endif
+#ifndef QC_CLK_ABS
+#define QC_CLK_ABS(from, to)  // harness: a phase boundary between two absolute clock slots (the torque pass: 13 lists, 14 swing, 15 stance)
+#endif
+
+namespace qc {
 
 // Device code reads the constants through the CONSTANT address space (scalar
 // loads).  The kernel re-derives the pointer behind an opaque asm before each
@@ -118,46 +188,6 @@ QC_DEV void pin_uconst(UConst& u) {
   asm volatile("" : "+v"(u.inv_bz_u[0]), "+v"(u.inv_bz_u[1]), "+v"(u.inv_bz_u[2]));
   asm volatile("" : "+v"(u.Vd[0]), "+v"(u.Vd[1]), "+v"(u.Vd[2]), "+v"(u.Vd[3]), "+v"(u.Vd[4]), "+v"(u.Vd[5]), "+v"(u.max_iter));
 }
-
-// mirrors qc_swing_state (include/qc_balance.h)
-struct SwingState {
-  int32_t leg_state[4];
-  int32_t has_traj[4];
-  double p_start[12];
-  double p_final[12];
-};
-
-// mirrors qc_commander_state (include/qc_balance.h)
-struct CmdState {
-  int32_t standing, gait_running, cmd_pending, reserved;
-  double Vb[6], Rwb_d[9], x_d[3], xdot_d[3], w_d[3];
-};
-
-struct BatchIn {
-  const double *Rwb, *Rwb_d, *x, *xdot, *w, *x_d, *xdot_d, *w_d, *feet;
-  const uint8_t* stance;
-  const double* joint_q;
-  double* gait_phase;  // written when gait_dt is given
-  const double* gait_duty;
-  const double* swing_pos;
-  const double* swing_vel;
-  const double* joint_qdot;
-  struct SwingState* swing_state;
-  const double* gait_dt;
-  // commander mode (qc_tick_batch; cmd_state == NULL everywhere else): the desired state comes from cmd_state, not from
-  // Rwb_d / x_d / xdot_d / w_d (NULL then), and the robot's commander step gates the gait clock and the planner
-  struct CmdState* cmd_state;
-  const double* cmd_twist;
-  const uint8_t* cmd_fresh;
-  double stand_height, stand_tol, cmd_dt;
-};
-struct BatchOut {
-  double* grf_body;
-  int32_t* status;
-  uint32_t* active_set;
-  int32_t* iterations;
-  double* joint_tau;
-};
 
 // ------------------------------------------------------------ lane groups
 // DPP quad permute: data of lane^1 inside each aligned quad.
@@ -1594,3 +1624,4 @@ struct EqpDense4 {
 };
 
 }  // namespace qc
+#endif  // __HIPCC__

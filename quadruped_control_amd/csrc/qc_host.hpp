@@ -1,0 +1,445 @@
+// qc_host.hpp - the host logic behind the C ABI that needs no device (C++17, no HIP): qc_balance.hip includes it for the
+// library, tests/cpp/host_logic_test.cpp compiles it with the host compiler alone.
+#pragma once
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <utility>
+
+#include "../../include/qc_balance.h"
+#include "qc_device.hpp"
+
+namespace qc {
+
+// The 6x6 forms solve the DUAL system M = S^-1 + A~ B^-1 A~^T, whose B^-1 = O(1/w) part has rank = the number of free force
+// coordinates: with fewer than six of them free, M is a rank-k term of size 1/w on top of an S^-1 of order one and the forces
+// (1/w) A~^T v come out with an absolute error of eps (S/w) |b| - 1e-5 N at S/w = 1e9 (the parameter campaigns' 1.4e-5 ... 2.4e-5
+// at w ~ 1e-7, S ~ 100: profiles/r06_fuzz_campaigns.log), 1e-8 N at the reference's S/w = 1e6 (commander_node.cpp:305-307).  The
+// dense 12x12 form factorises the PRIMAL reduced Hessian, which is well-conditioned exactly there (tests/test_gpu_parity.py::
+// test_small_w_golden: < 5e-6 where the dual forms are at 2.4e-5), at three to five times the time.  Above this ratio a handle
+// therefore runs the dense form: accuracy before speed for regularisation weights this far below the reference's.
+#ifndef QC_DENSE_RATIO
+#define QC_DENSE_RATIO 3.0e8
+#endif
+
+inline thread_local std::string g_err;
+inline int fail(int code, const std::string& msg) {
+  g_err = msg;
+  return code;
+}
+
+// What qc_create derived from its parameters about the formulation, and the overrides of qc_set_tuning.
+struct Tuning {
+  bool diag_w = false;   // W diagonal -> 6x6 formulation
+  bool uniform = false;  // additionally S diagonal and W = w*I -> scalar-constant specialisation
+  // what qc_create was given: the tuning overrides (force_general / force_dense / max_iter / probe_batch_load) restore from these
+  bool cfg_diag_w = false, cfg_uniform = false;
+  bool small_w = false;    // qc_create's rule: max diag(S) / min diag(W) above QC_DENSE_RATIO - the 6x6 dual forms lose digits that matter there
+  bool auto_dense = true;  // ... and such a handle runs the dense 12x12 form (qc_set_tuning "auto_dense", default on)
+  int cfg_max_iter = 0;
+  bool force_general = false, force_dense = false, probing = false;
+  // launch heuristics (defaults from measurements; qc_set_tuning overrides them)
+  long chunk_override = 0;      // > 0: robots per wave (at most one fill, 64 / G)
+  int group_override = 0;       // 1, 2, 4: lanes per robot
+  int wave_slots_override = 0;  // > 0: resident workgroups assumed for every kernel instead of the occupancy query
+  int race_override = -1;       // -1 heuristic; 0 / 1: no racing strategies; 2, 4: at most that many per robot
+  int pair_override = -1;       // MODE 3 (paired waves): -1 heuristic, 0 never, 1 whenever the form allows it
+  int pair_th = 0;              // hand-over threshold (0: heuristic)
+  int pair_refill = 0;          // free lane groups that trigger a refill (0: heuristic)
+  int pair_solo = 1;            // 1: the last round of workgroups keeps each wave's stragglers in the wave (default), 0: pairs everywhere
+};
+
+// the formulation a handle runs, from what qc_create was given and the tuning flags - in one place, whatever the order of the calls
+inline void resolve_form(Tuning& t) {
+  t.diag_w = t.cfg_diag_w && !t.force_dense && !(t.small_w && t.auto_dense);
+  t.uniform = t.cfg_uniform && !t.force_general;
+}
+// the formulation a handle runs (resolve_form)
+inline int form_of(const Tuning& t) { return !t.diag_w ? QC_FORM_DENSE : (t.uniform ? QC_FORM_UNIFORM : QC_FORM_GENERAL); }
+
+// Cholesky-based inverse of a small SPD matrix (host, once per handle)
+inline bool spd_inverse(const double* A, int n, double* inv) {
+  double L[36];
+  for (int i = 0; i < n; i++)
+    for (int j = 0; j <= i; j++) {
+      double s = A[i * n + j];
+      for (int k = 0; k < j; k++) s -= L[i * n + k] * L[j * n + k];
+      if (i == j) {
+        if (!(s > 0.0)) return false;
+        L[i * n + i] = std::sqrt(s);
+      } else {
+        L[i * n + j] = s / L[j * n + j];
+      }
+    }
+  for (int c = 0; c < n; c++) {
+    double y[6], x[6];
+    for (int i = 0; i < n; i++) {
+      double s = (i == c) ? 1.0 : 0.0;
+      for (int k = 0; k < i; k++) s -= L[i * n + k] * y[k];
+      y[i] = s / L[i * n + i];
+    }
+    for (int i = n - 1; i >= 0; i--) {
+      double s = y[i];
+      for (int k = i + 1; k < n; k++) s -= L[k * n + i] * x[k];
+      x[i] = s / L[i * n + i];
+    }
+    for (int i = 0; i < n; i++) inv[i * n + c] = x[i];
+  }
+  return true;
+}
+
+// Columns 0..2 of the inverse of FootTrajectory::initSystem()'s 7x7 matrix (trajectory.cpp:256-277):
+// the responses of the sextic coefficients to p_start, p_final and p_centre.  basis[3*j + k].
+inline void sextic_basis(double* basis) {
+  double A[7][7] = {{1, 0, 0, 0, 0, 0, 0}, {1, 1, 1, 1, 1, 1, 1}, {1, 0.5, 0.25, 0.125, 0.0625, 0.03125, 0.015625},
+                    {0, 1, 0, 0, 0, 0, 0}, {0, 1, 2, 3, 4, 5, 6}, {0, 0, 2, 0, 0, 0, 0}, {0, 0, 2, 6, 12, 20, 30}};
+  double M[7][10];
+  for (int i = 0; i < 7; i++) {
+    for (int j = 0; j < 7; j++) M[i][j] = A[i][j];
+    for (int k = 0; k < 3; k++) M[i][7 + k] = (i == k) ? 1.0 : 0.0;
+  }
+  for (int c = 0; c < 7; c++) {
+    int p = c;
+    for (int r = c + 1; r < 7; r++) if (std::fabs(M[r][c]) > std::fabs(M[p][c])) p = r;
+    for (int j = 0; j < 10; j++) std::swap(M[c][j], M[p][j]);
+    const double piv = M[c][c];
+    for (int j = 0; j < 10; j++) M[c][j] /= piv;
+    for (int r = 0; r < 7; r++) {
+      if (r == c) continue;
+      const double m = M[r][c];
+      for (int j = 0; j < 10; j++) M[r][j] -= m * M[c][j];
+    }
+  }
+  for (int j = 0; j < 7; j++)
+    for (int k = 0; k < 3; k++) basis[3 * j + k] = M[j][7 + k];
+}
+
+inline void default_kinematics(qc_kinematics* k) {  // qc_default_kinematics
+  if (!k) return;
+  // QuadrupedKinematics::QuadrupedKinematics(), kinematics.cpp:20-47
+  const double xbh = 0.196, ybh = 0.050, zbh = 0.0, l1 = 0.077, l2 = 0.211, l3 = 0.230;
+  const double hip[12] = {-xbh, ybh, zbh, xbh, ybh, zbh, -xbh, -ybh, zbh, xbh, -ybh, zbh};  // RL FL RR FR
+  const double links[12] = {l1, -l2, -l3, l1, -l2, -l3, -l1, -l2, -l3, -l1, -l2, -l3};    // left, left, right, right
+  std::memcpy(k->hip, hip, sizeof(hip));
+  std::memcpy(k->links, links, sizeof(links));
+  k->tau_min = -20.0;  // commander_node.cpp:324-325
+  k->tau_max = 20.0;
+  const double kff[3] = {0.0, 0.0, 0.0}, kp[3] = {40.0, 40.0, 50.0}, kd[3] = {1.0, 1.0, 1.0};  // mit_cheetah_config.yaml:50-53
+  std::memcpy(k->jc_kff, kff, sizeof(kff));
+  std::memcpy(k->jc_kp, kp, sizeof(kp));
+  std::memcpy(k->jc_kd, kd, sizeof(kd));
+  const double xbt = 0.196, ybt = 0.127, zbt = 0.0;  // foot_planner.cpp:27-42
+  const double phip[12] = {-xbt, ybt, zbt, xbt, ybt, zbt, -xbt, -ybt, zbt, xbt, -ybt, zbt};
+  std::memcpy(k->planner_hip, phip, sizeof(phip));
+  k->planner_k = 0.01;     // foot_planner.cpp:25
+  k->swing_height = 0.08;  // gait/height, commander_node.cpp:247
+}
+
+// the kinematic model and the swing planner's constants of a qc_kinematics, into the device constants
+inline void copy_kinematics(DevParams& d, const qc_kinematics& k) {
+  std::memcpy(d.hip, k.hip, sizeof(k.hip));
+  std::memcpy(d.links, k.links, sizeof(k.links));
+  d.tau_min = k.tau_min;
+  d.tau_max = k.tau_max;
+  std::memcpy(d.jc_kff, k.jc_kff, sizeof(k.jc_kff));
+  std::memcpy(d.jc_kp, k.jc_kp, sizeof(k.jc_kp));
+  std::memcpy(d.jc_kd, k.jc_kd, sizeof(k.jc_kd));
+  std::memcpy(d.planner_hip, k.planner_hip, sizeof(k.planner_hip));
+  d.planner_k = k.planner_k;
+  d.swing_height = k.swing_height;
+}
+
+// ---------------------------------------------------------------- qc_create: validation and derived constants
+// what qc_create refuses about its parameters without looking at a device
+inline int check_params(const qc_params* p) {
+  if (!(p->mu > 0.0) || !(p->mass > 0.0)) return fail(QC_ERR_INVALID, "qc_create: mu and mass must be > 0");
+  if (!(p->fzmin >= 0.0) || !(p->fzmax >= p->fzmin)) return fail(QC_ERR_INVALID, "qc_create: need 0 <= fzmin <= fzmax");
+  // The cone rows of the reference are two-sided with +-1e6 on the far side (BC.cpp:296-301: -1e6 <= fx - mu fz <= 0, ...).
+  // Inside the cone |fx -+ mu fz| <= 2 mu fz <= 2 mu fzmax, so those sides cannot bind - and this solver does not carry
+  // them - as long as 2 mu fzmax < 1e6.  Parameters beyond that would make the reference's QP a different one: refused.
+  // (the hand-over records of the re-packed tails carry the recalculation count in 16 bits)
+  if (p->max_iter > QC_MAX_ITER_LIMIT) return fail(QC_ERR_INVALID, "qc_create: max_iter must be <= 65535");
+  if (!(2.0 * p->mu * p->fzmax < 1.0e6))
+    return fail(QC_ERR_INVALID, "qc_create: need 2 * mu * fzmax < 1e6 (the +-1e6 sides of the reference's cone rows, balance_controller.cpp:296-301, are not carried)");
+  for (int i = 0; i < 6; i++)
+    for (int j = 0; j < i; j++)
+      if (std::fabs(p->S[6 * i + j] - p->S[6 * j + i]) > 1e-12 * (std::fabs(p->S[6 * i + i]) + std::fabs(p->S[6 * j + j])))
+        return fail(QC_ERR_INVALID, "qc_create: S must be symmetric");
+  for (int i = 0; i < 12; i++)
+    if (!(p->W[12 * i + i] > 0.0)) return fail(QC_ERR_INVALID, "qc_create: W must be positive definite");
+  for (int i = 0; i < 12; i++)
+    for (int j = 0; j < i; j++)
+      if (std::fabs(p->W[12 * i + j] - p->W[12 * j + i]) > 1e-12 * (p->W[12 * i + i] + p->W[12 * j + j]))
+        return fail(QC_ERR_INVALID, "qc_create: W must be symmetric");
+  return QC_OK;
+}
+
+// the device constants and the formulation flags of validated parameters (fails on an S that is not positive definite)
+inline int derive_params(const qc_params* p, DevParams& d, Tuning& t) {
+  bool diag = true;
+  for (int i = 0; i < 12; i++)
+    for (int j = 0; j < 12; j++)
+      if (i != j && p->W[12 * i + j] != 0.0) diag = false;
+  std::memset(&d, 0, sizeof(d));
+  d.mu = p->mu; d.mass = p->mass; d.fzmin = p->fzmin; d.fzmax = p->fzmax;
+  std::memcpy(d.Ib, p->Ib, sizeof(d.Ib));
+  std::memcpy(d.S, p->S, sizeof(d.S));
+  if (!spd_inverse(p->S, 6, d.V)) return fail(QC_ERR_INVALID, "qc_create: S must be positive definite");
+  for (int i = 0; i < 12; i++) d.w[i] = p->W[12 * i + i];
+  std::memcpy(d.W, p->W, sizeof(d.W));
+  for (int i = 0; i < 4; i++) {
+    d.inv_wx[i] = 1.0 / d.w[3 * i];
+    d.inv_wy[i] = 1.0 / d.w[3 * i + 1];
+    for (int a = 0; a < 2; a++)
+      for (int b = 0; b < 2; b++)
+        d.inv_bz[4 * i + 2 * a + b] = 1.0 / (d.w[3 * i + 2] + p->mu * p->mu * (a * d.w[3 * i] + b * d.w[3 * i + 1]));
+  }
+  bool uni = diag;
+  for (int i = 0; i < 6; i++)
+    for (int j = 0; j < 6; j++)
+      if (i != j && p->S[6 * i + j] != 0.0) uni = false;
+  for (int i = 1; i < 12; i++)
+    if (p->W[12 * i + i] != p->W[0]) uni = false;
+  t.cfg_diag_w = diag;
+  t.cfg_uniform = uni;
+  {
+    double smax = 0.0, wmin = p->W[0];
+    for (int i = 0; i < 6; i++) smax = std::fmax(smax, p->S[6 * i + i]);
+    for (int i = 1; i < 12; i++) wmin = std::fmin(wmin, p->W[12 * i + i]);
+    t.small_w = diag && smax > QC_DENSE_RATIO * wmin;
+  }
+  resolve_form(t);
+  for (int i = 0; i < 6; i++) d.Vd[i] = d.V[6 * i + i];
+  d.w_u = p->W[0];
+  d.inv_w_u = 1.0 / p->W[0];
+  for (int k = 0; k < 3; k++) d.inv_bz_u[k] = 1.0 / (p->W[0] * (1.0 + p->mu * p->mu * k));
+  std::memcpy(d.kff, p->kff, sizeof(d.kff));
+  std::memcpy(d.kp_p, p->kp_p, sizeof(d.kp_p));
+  std::memcpy(d.kd_p, p->kd_p, sizeof(d.kd_p));
+  std::memcpy(d.kp_w, p->kp_w, sizeof(d.kp_w));
+  std::memcpy(d.kd_w, p->kd_w, sizeof(d.kd_w));
+  {
+    qc_kinematics k;
+    default_kinematics(&k);
+    copy_kinematics(d, k);
+    d.t_swing = 0.18;  // mit_cheetah_config.yaml:17-18
+    d.t_stance = 0.8;
+    sextic_basis(d.traj_basis);
+  }
+  d.stance_phase = 0.8 / (0.18 + 0.8);  // mit_cheetah_config.yaml:17-18
+  // Multiplier tolerance, relative to max(1, |grad|_inf).  It has to sit just above the rounding noise of the
+  // multipliers, not at a "reasonable" 1e-9: along a weakly active face the objective curves only with 2w, so a
+  // multiplier accepted at -tol*|g| leaves the force tol*|g|/(2w) away from the minimiser (w = 2.8e-7, |g| ~ 1e6:
+  // 1e-12 gave 0.2 N = 2e-3 relative in the parameter fuzz; 1e-13 ... 1e-15 all agree with the NNLS restatement
+  // and change neither the recalculation counts of 1 M robots nor anything else measurable).
+  d.tol_d = 1e-14;
+  d.tol_start = d.tol_d;  // (polish on)
+  d.max_iter = p->max_iter > 0 ? p->max_iter : 200;
+  t.cfg_max_iter = d.max_iter;
+  d.clamp_steps = 0;  // 0: per kernel (clamp_steps_for)
+  d.tail_race = 1;
+  d.polish = 1;  // the polish at acceptance (Lane::iterate)
+  return QC_OK;
+}
+
+// ---------------------------------------------------------------- qc_set_tuning
+// `upload`: the key changed a device constant, the caller rewrites the device copy
+inline int set_tuning(Tuning& t, DevParams& dp, const char* key, double value, bool* upload) {
+  const std::string k(key);
+  bool params = false;
+  if (k == "group") {
+    const int g = (int)value;
+    if (g != 0 && g != 1 && g != 2 && g != 4) return fail(QC_ERR_INVALID, "qc_set_tuning: group is 0 (heuristic), 1, 2 or 4");
+    t.group_override = g;
+  } else if (k == "one_fill") {  // (-1 heuristic / 1 always: every launch is one fill per wave, the key stays for existing callers)
+    if (value == 0) return fail(QC_ERR_INVALID, "qc_set_tuning: one_fill = 0 asked for the persistent-wave kernels, which were removed");
+  }
+  else if (k == "chunk") t.chunk_override = value > 0 ? (long)value : 0;
+  else if (k == "wave_slots") t.wave_slots_override = value > 0 ? (int)value : 0;
+  else if (k == "race") {  // (0 / 1 also switch the race in the 4-lane tail of the wider kernels off)
+    t.race_override = value < 0 ? -1 : (int)value;
+    dp.tail_race = (value < 0 || value >= 2) ? 1 : 0;
+    params = true;
+  }
+  else if (k == "pair") t.pair_override = value < 0 ? -1 : (value != 0 ? 1 : 0);
+  else if (k == "pair_th") t.pair_th = value > 0 ? (int)value : 0;
+  else if (k == "pair_refill") t.pair_refill = value > 0 ? (int)value : 0;
+  else if (k == "pair_solo") t.pair_solo = value != 0 ? 1 : 0;
+  else if (k == "force_general" || k == "force_dense") {
+    // general 6x6 form on uniform weights / dense 12x12 form on a diagonal W (same minimiser).  The form follows from what
+    // qc_create was given and the two flags, in one place, whatever the order of the calls.
+    (k == "force_general" ? t.force_general : t.force_dense) = value != 0;
+    resolve_form(t);
+  } else if (k == "auto_dense") {  // 0: a diagonal W keeps its 6x6 form however small it is (QC_DENSE_RATIO above)
+    t.auto_dense = value != 0;
+    resolve_form(t);
+  } else if (k == "tol_d") { dp.tol_d = value; dp.tol_start = dp.polish ? value : -value; params = true; }
+  else if (k == "max_iter") {  // <= 0: back to the handle's own cap (qc_params.max_iter)
+    if (value > (double)QC_MAX_ITER_LIMIT) return fail(QC_ERR_INVALID, "qc_set_tuning: max_iter must be <= 65535");
+    t.probing = false;
+    dp.max_iter = value > 0 ? (int)value : t.cfg_max_iter; params = true;
+  }
+  else if (k == "clamp_steps") { dp.clamp_steps = value >= 1 ? (int)value : 0; params = true; }
+  else if (k == "polish") {  // 0: round 5's acceptance rule
+    dp.polish = value != 0 ? 1 : 0;
+    dp.tol_start = dp.polish ? dp.tol_d : -dp.tol_d;
+    params = true;
+  }
+  else if (k == "probe_batch_load") {
+    // measurement probe: load -> assemble -> store only (every robot reports QC_MAX_ITER); 0 restores the handle's own cap
+    t.probing = value != 0;
+    dp.max_iter = t.probing ? 0 : t.cfg_max_iter; params = true;
+  } else return fail(QC_ERR_INVALID, "qc_set_tuning: unknown key '" + k + "'");
+  *upload = params;
+  return QC_OK;
+}
+
+// ---------------------------------------------------------------- launch planning
+// One wave per 64-thread block; a group of G lanes per robot.  The group width trades latency for throughput
+// (instructions per steady recalculation: 487 per 16 robots at G = 4, 730 per 32 at G = 2, ~1170 per 64 at G = 1):
+// the planner takes the widest group with which the batch still fits ONE wave per SIMD - such a batch cannot fill
+// the chip anyway and the slowest robot's serial chain is what is timed - i.e. G = 4 up to CUs x 4 x 16 robots
+// (16 384), G = 2 up to twice that, and one lane per robot above (tools/size_scan.py: the cross-overs sit exactly
+// there, cold and warm).  Every width finishes its last <= 16 running robots on the 4-lane body.  Every launch gives
+// each wave one fill (mode 1 / 2) - the hardware scheduler refills the chip with the next workgroup - or, for the
+// one-lane 6x6 kernels of large batches, a workgroup of two waves (mode 3, balance_pair_kernel); a chunk beyond one fill
+// is an error at launch.
+struct LaunchPlan {
+  int kernel;  // index into KERNEL_KEYS (form, G, mode, race) and into the library's table of entry points
+  unsigned blocks;
+  long chunk;
+  int p_th, p_refill;  // mode 3
+  long resident;
+};
+
+// the instantiation that serves (form, G, mode, race): its index in KERNEL_KEYS, or -1
+inline int find_kernel(int form, int G, int mode, int race = 1) {
+  for (int i = 0; i < N_KERNELS; i++) {
+    const KernelKey& k = KERNEL_KEYS[i];
+    if (k.form == form && k.G == G && k.mode == mode && k.race == race) return i;
+  }
+  return -1;
+}
+
+// `resident(kernel, kin)`: workgroups of KERNEL_KEYS[kernel] (its joint_q variant with `kin`) the device holds at once
+template <class Resident>
+int plan_launch(int form, long n, bool kin, bool warm, const Tuning& t, int cus, Resident&& resident, LaunchPlan* lp) {
+  // (a kernel that is not instantiated is an error, never another kernel in its place)
+  const auto no_kernel = [] { return fail(QC_ERR_INVALID, "plan_launch: no kernel instantiation serves this form, group width, mode and race"); };
+  int G = 1;
+  const long simds = (long)cus * 4;
+  const int r4 = find_kernel(form, 4, 1);
+  if (r4 < 0) return no_kernel();
+  const long cap4 = resident(r4, kin) * 16;
+  if (form != QC_FORM_DENSE) {
+    G = n <= 16 * simds ? 4 : (n <= 32 * simds ? 2 : 1);
+    if (t.group_override) G = t.group_override;
+  } else {
+    // dense form: four lanes per robot while the batch fits the resident waves - the latency regime; one lane per robot
+    // with the LDS-staged Hessian above that
+    G = n <= cap4 ? 4 : 1;
+    if (t.group_override) G = t.group_override == 4 ? 4 : 1;
+    // a chunk of 17 ... 64 robots is more than a four-lane wave holds and exactly what a one-lane one-fill wave does (ADVICE r5:
+    // rounds 2-4 served such a request on the one-lane kernel; it must not become an error because the four-lane one would have been picked)
+    if (!t.group_override && G == 4 && t.chunk_override > 16 && t.chunk_override <= 64) G = 1;
+  }
+  // A request the kernels cannot honour is an error, not a silent change of the launch: a wave holds one fill.
+  if (t.chunk_override > 64 / G)
+    return fail(QC_ERR_INVALID, "qc_set_tuning: a chunk beyond one fill (64 / lanes per robot) asks for more robots than a wave holds");
+  // MODE 3 (paired waves): 6x6 forms, one lane per robot, batches of at least four rounds of one-fill workgroups (524 288
+  // robots): measured -5 % there and nothing below (profiles/r03_paired_waves.log) - with few rounds the consumer of two
+  // waves' stragglers is mostly a longer chain at the end of the launch.  (Not the joint_q variants: they always run as
+  // one-fill workgroups.)
+  if (form != QC_FORM_DENSE && G == 1 && !kin && t.chunk_override <= 0) {
+    const int r1 = find_kernel(form, 1, 1), rp = find_kernel(form, 1, 3);
+    if (r1 < 0 || rp < 0) return no_kernel();
+    const long res1 = resident(r1, kin);
+    bool use_pair = n >= 4 * res1 * 64;
+    if (t.pair_override >= 0) use_pair = t.pair_override != 0;
+    if (use_pair) {
+      const int p_th = t.pair_th > 0 ? (t.pair_th < PAIR_CAP ? t.pair_th : PAIR_CAP) : 24;
+      // (1 ... 16 free lane groups: beyond 16 the refill test of the consumer could never fire and it would spin on a full list)
+      const int p_refill = t.pair_refill > 0 ? (t.pair_refill < 16 ? t.pair_refill : 16) : 4;
+      // (resident: two-wave workgroups of the pair kernel itself - its own registers and 26 KB of static LDS -, not half of the one-fill figure)
+      *lp = LaunchPlan{rp, (unsigned)((n + 127) / 128), 128, p_th, p_refill, resident(rp, false)};
+      return QC_OK;
+    }
+  }
+  const long rpw = 64 / G;  // robots per wave fill
+  const int rg = find_kernel(form, G, 1);
+  if (rg < 0) return no_kernel();
+  const long res = resident(rg, kin);
+  long chunk = t.chunk_override > 0 ? t.chunk_override : rpw;
+  const long blocks = (n + chunk - 1) / chunk;
+  // one wave per SIMD is enough: the recalculation's constants stay resident in VGPRs (uniform G = 4 form)
+  const int mode = (form == QC_FORM_UNIFORM && G == 4 && blocks <= (long)cus * 4) ? 2 : 1;
+  // ... and when even that leaves SIMDs idle the 4-lane kernels (all three forms) race pivoting strategies on the
+  // same robot (Lane: RACE): four per robot up to CUs x 4 x 4 robots (4 096)
+  int race = 1;
+  if (G == 4 && t.chunk_override <= 0 && (mode == 2 || form != QC_FORM_UNIFORM)) {
+    // (a 2-way race up to 8 192 robots is built and selectable - qc_set_tuning("race", 2) - but measured neutral on
+    // average: its two fewer recalculations pay for the heavier body, tools/race_scan.py)
+    // (cold batches: a warm-started one has little chain to shorten - 10-17 us either way, 0.2-0.6 us dearer with the race,
+    // tools/warm_race_scan.py)
+    race = (!warm && n <= 4 * simds) ? 4 : 1;
+    if (t.race_override >= 0) race = (t.race_override == 4 && n <= 4 * simds) ? 4 : ((t.race_override >= 2 && n <= 8 * simds) ? 2 : 1);
+    chunk = 16 / race;
+  }
+  const int rk = find_kernel(form, G, mode, race);
+  if (rk < 0) return no_kernel();
+  *lp = LaunchPlan{rk, (unsigned)((n + chunk - 1) / chunk), chunk, 0, 0, res};
+  return QC_OK;
+}
+
+// ---------------------------------------------------------------- argument checks of the batch entry points
+// The argument check the batch entry points share (`who`: the entry point, for the message; built only on failure).  The two
+// have always tested the required outputs and "joint_tau needs joint_q" in opposite orders; `outputs_first` keeps each its own.
+inline int check_batch_args(const char* who, const qc_handle* h, size_t n, const qc_batch_in* in, const qc_batch_out* out, bool outputs_first) {
+  const auto bad = [who](const char* what) { return fail(QC_ERR_INVALID, std::string(who) + what); };
+  if (!h || !in || !out) return bad(": null argument");
+  if (n == 0) return QC_OK;
+  if (!in->Rwb || !in->Rwb_d || !in->x || !in->xdot || !in->w || !in->x_d || !in->xdot_d || !in->w_d || (!in->feet && !in->joint_q))
+    return bad(": null input array");
+  const bool no_outputs = !out->grf_body || !out->status, tau_alone = out->joint_tau && !in->joint_q;
+  if (outputs_first && no_outputs) return bad(": grf_body and status are required");
+  if (tau_alone) return bad(": joint_tau needs joint_q");
+  if (no_outputs) return bad(": grf_body and status are required");
+  return QC_OK;
+}
+
+// qc_control_batch: which of the optional swing and gait arrays go together (after check_batch_args)
+inline int check_swing_gait_args(const qc_batch_in* in, const qc_batch_out* out) {
+  const int n_sw = (in->swing_pos ? 1 : 0) + (in->swing_vel ? 1 : 0) + (in->joint_qdot ? 1 : 0);
+  if (!in->swing_state && n_sw != 0 && (n_sw != 3 || !in->joint_q || !out->joint_tau))
+    return fail(QC_ERR_INVALID, "qc_control_batch: swing_pos, swing_vel and joint_qdot go together and need joint_q and joint_tau");
+  if (in->gait_dt && (!in->gait_phase || in->stance)) return fail(QC_ERR_INVALID, "qc_control_batch: gait_dt advances gait_phase (needed, and stance must be NULL)");
+  if (in->swing_state && (!in->joint_q || !in->joint_qdot || !in->gait_phase || !out->joint_tau || in->swing_pos || in->swing_vel))
+    return fail(QC_ERR_INVALID, "qc_control_batch: swing_state needs joint_q, joint_qdot, gait_phase and joint_tau, and excludes swing_pos/swing_vel");
+  return QC_OK;
+}
+
+// qc_tick_batch
+inline int check_tick_args(const qc_handle* h, const qc_batch_in* in, const qc_command_in* cmd, const qc_batch_out* out) {
+  if (!h || !in || !cmd || !out) return fail(QC_ERR_INVALID, "qc_tick_batch: null argument");
+  if (cmd->struct_size != sizeof(qc_command_in)) {
+    char msg[160];
+    std::snprintf(msg, sizeof(msg), "qc_tick_batch: qc_command_in.struct_size is %zu, this library's qc_command_in has %zu B (qc_default_command sets it)",
+                  cmd->struct_size, sizeof(qc_command_in));
+    return fail(QC_ERR_INVALID, msg);
+  }
+  if (!in->Rwb || !in->x || !in->xdot || !in->w || !in->joint_q || !in->joint_qdot || !in->gait_phase || !in->gait_dt || !in->swing_state)
+    return fail(QC_ERR_INVALID, "qc_tick_batch: the complete tick needs Rwb, x, xdot, w, joint_q, joint_qdot, gait_phase, gait_dt and swing_state");
+  if (in->Rwb_d || in->x_d || in->xdot_d || in->w_d)
+    return fail(QC_ERR_INVALID, "qc_tick_batch: Rwb_d, x_d, xdot_d and w_d must be NULL (the desired state lives in qc_command_in.state)");
+  if (in->stance || in->swing_pos || in->swing_vel)
+    return fail(QC_ERR_INVALID, "qc_tick_batch: stance, swing_pos and swing_vel must be NULL (the gait clock and the planner make them)");
+  if (!out->grf_body || !out->status || !out->joint_tau) return fail(QC_ERR_INVALID, "qc_tick_batch: grf_body, status and joint_tau are required");
+  if (!cmd->state) return fail(QC_ERR_INVALID, "qc_tick_batch: qc_command_in.state is required");
+  if (cmd->fresh && !cmd->twist) return fail(QC_ERR_INVALID, "qc_tick_batch: qc_command_in.fresh needs twist");
+  if (!std::isfinite(cmd->stand_height) || !(cmd->stand_tol >= 0.0) || !std::isfinite(cmd->stand_tol) || !std::isfinite(cmd->cmd_dt))
+    return fail(QC_ERR_INVALID, "qc_tick_batch: stand_height, stand_tol (>= 0) and cmd_dt must be finite");
+  return QC_OK;
+}
+
+}  // namespace qc

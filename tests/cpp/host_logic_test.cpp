@@ -1,0 +1,480 @@
+// The library's host logic without a device (quadruped_control_amd/csrc/qc_host.hpp): the launch planner against the library's own
+// list of kernel instantiations, the constants qc_create derives, the tuning setter and the argument checks of the batch entry
+// points.  Host compiler only - links neither HIP nor the library; built with the address and undefined-behaviour sanitizers
+// (__graft_entry__.build_host_logic_test) and run by tests/test_host_cpu.py.  Prints the failing case and exits 1 on the first
+// violated check.
+#include <algorithm>
+#include <cfloat>
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+
+#include "../../quadruped_control_amd/csrc/qc_host.hpp"
+
+using namespace qc;
+
+static long g_checked = 0;
+#define CHECK(cond, ...)                                              \
+  do {                                                                \
+    g_checked++;                                                      \
+    if (!(cond)) {                                                    \
+      std::printf("FAILED %s:%d: %s\n  case: ", __FILE__, __LINE__, #cond); \
+      std::printf(__VA_ARGS__);                                       \
+      std::printf("\n  last error: %s\n", g_err.c_str());             \
+      std::exit(1);                                                   \
+    }                                                                 \
+  } while (0)
+// a call that must fail with this code and exactly this text
+#define CHECK_FAILS(rc, code, text, ...) CHECK((rc) == (code) && g_err == (text), __VA_ARGS__)
+
+// ------------------------------------------------------------------------------------------------ (a) planner sweep
+static const char* const CHUNK_MSG = "qc_set_tuning: a chunk beyond one fill (64 / lanes per robot) asks for more robots than a wave holds";
+
+static void planner_sweep() {
+  const int cus = 256;
+  const long simds = 4L * cus;
+  for (const int per_cu : {4, 2}) {
+    const long res = (long)per_cu * cus;
+    const auto resident = [res](int, bool) { return res; };
+    const long sizes[] = {1, 16, 17, 64, 65, 4096, 4097, 8192, 8193, 16384, 16385, 32768, 32769, 65536, 4 * res * 64 - 1, 4 * res * 64, 2097152};
+    for (const int form : {QC_FORM_UNIFORM, QC_FORM_GENERAL, QC_FORM_DENSE})
+    for (const int kin : {0, 1})
+    for (const int warm : {0, 1})
+    for (const long n : sizes)
+    for (const int group : {0, 1, 2, 4})
+    for (const int race : {-1, 0, 2, 4})
+    for (const int pair : {-1, 0, 1})
+    for (const long chunk : {0L, 4L, 16L, 17L, 64L, 65L})
+    for (const int pair_th : {0, 1, 40})
+    for (const int pair_refill : {0, 1, 20}) {
+      Tuning t;
+      t.group_override = group; t.race_override = race; t.pair_override = pair; t.chunk_override = chunk;
+      t.pair_th = pair_th; t.pair_refill = pair_refill;
+#define CASE "res/CU %d form %d kin %d warm %d n %ld group %d race %d pair %d chunk %ld pair_th %d pair_refill %d", \
+             per_cu, form, kin, warm, n, group, race, pair, chunk, pair_th, pair_refill
+      // lanes per robot, as the planner's rules state them
+      int G;
+      if (form != QC_FORM_DENSE) {
+        G = group ? group : (n <= 16 * simds ? 4 : (n <= 32 * simds ? 2 : 1));
+      } else {
+        G = group ? (group == 4 ? 4 : 1) : (n <= 16 * res ? 4 : 1);
+        if (!group && G == 4 && chunk > 16 && chunk <= 64) G = 1;  // a chunk only a one-lane wave holds
+      }
+      LaunchPlan lp;
+      const int rc = plan_launch(form, n, kin != 0, warm != 0, t, cus, resident, &lp);
+      // outcome: the chunk error exactly when the chunk is beyond one fill, otherwise a kernel of the list
+      if (chunk > 64 / G) {
+        CHECK_FAILS(rc, QC_ERR_INVALID, CHUNK_MSG, CASE);
+        continue;
+      }
+      CHECK(rc == QC_OK, CASE);
+      CHECK(lp.kernel >= 0 && lp.kernel < N_KERNELS, CASE);
+      const KernelKey& k = KERNEL_KEYS[lp.kernel];
+      CHECK(k.form == form && k.G == G, CASE);
+      // bounds on the plan
+      CHECK(lp.chunk >= 1 && (long)lp.blocks * lp.chunk >= n && n > ((long)lp.blocks - 1) * lp.chunk, CASE);
+      CHECK(lp.chunk <= (k.mode == 3 ? 128 : 64 / G), CASE);
+      CHECK(lp.resident == res, CASE);
+      if (k.mode == 3) CHECK(lp.p_th >= 1 && lp.p_th <= PAIR_CAP && lp.p_refill >= 1 && lp.p_refill <= 16, CASE);
+      // the defaults
+      if (group == 0 && race == -1 && pair == -1 && chunk == 0) {
+        // (mode 2 counts the workgroups of one fill per wave, 16 robots each, before a race shortens the chunk)
+        const bool mode2 = form == QC_FORM_UNIFORM && G == 4 && (n + 15) / 16 <= 4L * cus;
+        const bool mode3 = form != QC_FORM_DENSE && G == 1 && !kin && n >= 4 * res * 64;
+        CHECK(k.mode == (mode3 ? 3 : (mode2 ? 2 : 1)), CASE);
+        const bool racing_exists = form != QC_FORM_UNIFORM || k.mode == 2;
+        CHECK(k.race == ((!warm && G == 4 && n <= 16L * cus && racing_exists) ? 4 : 1), CASE);
+      }
+#undef CASE
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ (b) derived constants
+// the reference's controller parameters (commander_node.cpp:289-338, mit_cheetah_config.yaml:66-99)
+static qc_params cheetah_params() {
+  qc_params p{};
+  p.mu = 0.8; p.mass = 11.0; p.fzmin = 10.0; p.fzmax = 120.0;
+  p.Ib[0] = 0.011253; p.Ib[4] = 0.036203; p.Ib[8] = 0.042673;
+  const double s[6] = {1.0, 1.0, 1.0, 10.0, 10.0, 5.0};
+  for (int i = 0; i < 6; i++) p.S[6 * i + i] = s[i];
+  for (int i = 0; i < 12; i++) p.W[12 * i + i] = 1e-5;
+  p.kff[2] = 0.15;
+  for (int i = 0; i < 3; i++) { p.kp_p[i] = 100.0; p.kd_p[i] = 50.0; p.kp_w[i] = 5000.0; p.kd_w[i] = 500.0; }
+  return p;
+}
+// ... with symmetric off-diagonal entries of 1 % of the smaller of the two diagonal entries they sit between, in S and W
+static qc_params general_params() {
+  qc_params p = cheetah_params();
+  for (int i = 0; i < 6; i++)
+    for (int j = 0; j < 6; j++)
+      if (i != j) p.S[6 * i + j] = 0.01 * std::min(p.S[6 * i + i], p.S[6 * j + j]);
+  for (int i = 0; i < 12; i++)
+    for (int j = 0; j < 12; j++)
+      if (i != j) p.W[12 * i + j] = 0.01 * std::min(p.W[12 * i + i], p.W[12 * j + j]);
+  return p;
+}
+
+// kappa_1(S) = |S|_1 |S^-1|_1 of a 6x6 matrix, the inverse by Gauss-Jordan with partial pivoting in long double
+static long double kappa1(const double* S) {
+  long double M[6][12];
+  for (int i = 0; i < 6; i++)
+    for (int j = 0; j < 6; j++) { M[i][j] = S[6 * i + j]; M[i][6 + j] = i == j ? 1.0L : 0.0L; }
+  for (int c = 0; c < 6; c++) {
+    int p = c;
+    for (int r = c + 1; r < 6; r++) if (std::fabs(M[r][c]) > std::fabs(M[p][c])) p = r;
+    for (int j = 0; j < 12; j++) std::swap(M[c][j], M[p][j]);
+    const long double piv = M[c][c];
+    for (int j = 0; j < 12; j++) M[c][j] /= piv;
+    for (int r = 0; r < 6; r++) {
+      if (r == c) continue;
+      const long double m = M[r][c];
+      for (int j = 0; j < 12; j++) M[r][j] -= m * M[c][j];
+    }
+  }
+  long double n1 = 0, n1i = 0;
+  for (int j = 0; j < 6; j++) {
+    long double a = 0, b = 0;
+    for (int i = 0; i < 6; i++) { a += std::fabs((long double)S[6 * i + j]); b += std::fabs(M[i][6 + j]); }
+    n1 = std::max(n1, a); n1i = std::max(n1i, b);
+  }
+  return n1 * n1i;
+}
+
+static const long double EPS = DBL_EPSILON / 2;  // unit roundoff of the library's doubles
+
+static void derived_constants() {
+  const qc_params sets[] = {cheetah_params(), general_params()};
+  for (int s = 0; s < 2; s++) {
+    qc_params p = sets[s];
+    p.max_iter = s == 0 ? 0 : 77;
+    DevParams d;
+    Tuning t;
+    CHECK(check_params(&p) == QC_OK && derive_params(&p, d, t) == QC_OK, "parameter set %d", s);
+    CHECK(form_of(t) == (s == 0 ? QC_FORM_UNIFORM : QC_FORM_DENSE) && t.cfg_diag_w == (s == 0) && t.cfg_uniform == (s == 0) && !t.small_w, "parameter set %d", s);
+    // V = S^-1: the Cholesky inverse's backward-error form c n eps kappa, n = 6, c n rounded up to 64
+    long double worst = 0;
+    for (int i = 0; i < 6; i++)
+      for (int j = 0; j < 6; j++) {
+        long double a = i == j ? -1.0L : 0.0L;
+        for (int k = 0; k < 6; k++) a += (long double)d.V[6 * i + k] * (long double)p.S[6 * k + j];
+        worst = std::max(worst, std::fabs(a));
+      }
+    const long double barV = 64 * EPS * kappa1(p.S);
+    std::printf("set %d: max|V S - I| = %.3Le, bar %.3Le\n", s, worst, barV);
+    CHECK(worst <= barV, "parameter set %d: max|V S - I| = %Le", s, worst);
+    // the sextic basis: A basis = [e0 e1 e2], A = FootTrajectory::initSystem()'s matrix (trajectory.cpp:256-277)
+    const double A[7][7] = {{1, 0, 0, 0, 0, 0, 0}, {1, 1, 1, 1, 1, 1, 1}, {1, 0.5, 0.25, 0.125, 0.0625, 0.03125, 0.015625},
+                            {0, 1, 0, 0, 0, 0, 0}, {0, 1, 2, 3, 4, 5, 6}, {0, 0, 2, 0, 0, 0, 0}, {0, 0, 2, 6, 12, 20, 30}};
+    long double normA = 0, normB = 0, resid = 0;
+    for (int i = 0; i < 7; i++) {
+      long double a = 0, b = 0;
+      for (int j = 0; j < 7; j++) a += std::fabs((long double)A[i][j]);
+      for (int k = 0; k < 3; k++) b += std::fabs((long double)d.traj_basis[3 * i + k]);
+      normA = std::max(normA, a); normB = std::max(normB, b);
+      for (int k = 0; k < 3; k++) {
+        long double r = i == k ? -1.0L : 0.0L;
+        for (int j = 0; j < 7; j++) r += (long double)A[i][j] * (long double)d.traj_basis[3 * j + k];
+        resid = std::max(resid, std::fabs(r));
+      }
+    }
+    const long double barB = 7 * EPS * normA * normB;
+    std::printf("set %d: max|A basis - E| = %.3Le, bar %.3Le\n", s, resid, barB);
+    CHECK(resid <= barB, "parameter set %d: sextic residual %Le", s, resid);
+    // the expressions, exactly
+    const double mu = p.mu;
+    for (int i = 0; i < 4; i++) {
+      CHECK(d.inv_wx[i] == 1.0 / p.W[13 * (3 * i)] && d.inv_wy[i] == 1.0 / p.W[13 * (3 * i + 1)], "parameter set %d foot %d", s, i);
+      for (int a = 0; a < 2; a++)
+        for (int b = 0; b < 2; b++)
+          CHECK(d.inv_bz[4 * i + 2 * a + b] == 1.0 / (p.W[13 * (3 * i + 2)] + mu * mu * (a * p.W[13 * (3 * i)] + b * p.W[13 * (3 * i + 1)])),
+                "parameter set %d foot %d a %d b %d", s, i, a, b);
+    }
+    for (int k = 0; k < 3; k++) CHECK(d.inv_bz_u[k] == 1.0 / (p.W[0] * (1.0 + mu * mu * k)), "parameter set %d k %d", s, k);
+    for (int i = 0; i < 6; i++) CHECK(d.Vd[i] == d.V[7 * i], "parameter set %d i %d", s, i);
+    CHECK(d.w_u == p.W[0] && d.inv_w_u == 1.0 / p.W[0], "parameter set %d", s);
+    CHECK(d.stance_phase == 0.8 / (0.18 + 0.8) && d.tol_d == 1e-14 && d.tol_start == d.tol_d, "parameter set %d", s);
+    CHECK(d.max_iter == (s == 0 ? 200 : 77) && t.cfg_max_iter == d.max_iter, "parameter set %d", s);
+  }
+  // a small W on a diagonal pair runs the dense form until auto_dense is switched off
+  {
+    qc_params p = cheetah_params();
+    for (int i = 0; i < 12; i++) p.W[13 * i] = 10.0 / QC_DENSE_RATIO / 1.01;
+    DevParams d;
+    Tuning t;
+    CHECK(check_params(&p) == QC_OK && derive_params(&p, d, t) == QC_OK && t.small_w && form_of(t) == QC_FORM_DENSE, "small W");
+  }
+  // The rejections, in the order qc_create makes them: parameters that violate every rule, mended one rule at a time.
+  qc_params p = general_params();
+  DevParams d;
+  Tuning t;
+  p.mass = 0.0; p.fzmin = 130.0; p.max_iter = QC_MAX_ITER_LIMIT + 1; p.mu = 5000.0; p.S[1] += 1e-3; p.W[13 * 4] = 0.0; p.W[12] *= 2;
+  p.S[6 * 4 + 5] = p.S[6 * 5 + 4] = 20.0;  // symmetric and indefinite
+  const qc_params ok = general_params();
+  CHECK_FAILS(check_params(&p), QC_ERR_INVALID, "qc_create: mu and mass must be > 0", "mass = 0");
+  p.mass = ok.mass; p.mu = -1.0;
+  CHECK_FAILS(check_params(&p), QC_ERR_INVALID, "qc_create: mu and mass must be > 0", "mu < 0");
+  p.mu = 5000.0;
+  CHECK_FAILS(check_params(&p), QC_ERR_INVALID, "qc_create: need 0 <= fzmin <= fzmax", "fzmin > fzmax");
+  p.fzmin = -1.0;
+  CHECK_FAILS(check_params(&p), QC_ERR_INVALID, "qc_create: need 0 <= fzmin <= fzmax", "fzmin < 0");
+  p.fzmin = ok.fzmin;
+  CHECK_FAILS(check_params(&p), QC_ERR_INVALID, "qc_create: max_iter must be <= 65535", "max_iter 65536");
+  p.max_iter = QC_MAX_ITER_LIMIT;
+  CHECK_FAILS(check_params(&p), QC_ERR_INVALID,
+              "qc_create: need 2 * mu * fzmax < 1e6 (the +-1e6 sides of the reference's cone rows, balance_controller.cpp:296-301, are not carried)", "2 mu fzmax = 1.2e6");
+  p.mu = ok.mu;
+  CHECK_FAILS(check_params(&p), QC_ERR_INVALID, "qc_create: S must be symmetric", "S[0][1] != S[1][0]");
+  p.S[1] = ok.S[1];
+  CHECK_FAILS(check_params(&p), QC_ERR_INVALID, "qc_create: W must be positive definite", "W[4][4] = 0");
+  p.W[13 * 4] = ok.W[13 * 4];
+  CHECK_FAILS(check_params(&p), QC_ERR_INVALID, "qc_create: W must be symmetric", "W[1][0] != W[0][1]");
+  p.W[12] = ok.W[12];
+  CHECK(check_params(&p) == QC_OK, "an indefinite symmetric S passes the device-free checks");
+  CHECK_FAILS(derive_params(&p, d, t), QC_ERR_INVALID, "qc_create: S must be positive definite", "indefinite S");
+  p.S[6 * 4 + 5] = p.S[6 * 5 + 4] = ok.S[6 * 4 + 5];
+  CHECK(check_params(&p) == QC_OK && derive_params(&p, d, t) == QC_OK && d.max_iter == QC_MAX_ITER_LIMIT, "mended parameters");
+}
+
+// ------------------------------------------------------------------------------------------------ (c) tuning
+static void tuning() {
+  // four handles: uniform, general 6x6 (per-axis W), dense (full W), and uniform with a W small enough for the dense rule
+  qc_params sets[4] = {cheetah_params(), cheetah_params(), general_params(), cheetah_params()};
+  sets[1].W[13 * 2] = 2e-5;
+  for (int i = 0; i < 12; i++) sets[3].W[13 * i] = 1e-9;
+  for (int s = 0; s < 4; s++) {
+    DevParams d;
+    Tuning t0;
+    CHECK(derive_params(&sets[s], d, t0) == QC_OK, "parameter set %d", s);
+    const int want0[4] = {QC_FORM_UNIFORM, QC_FORM_GENERAL, QC_FORM_DENSE, QC_FORM_DENSE};
+    CHECK(form_of(t0) == want0[s], "parameter set %d", s);
+    // every order of setting and clearing the three flags: the form is that of the flags as they stand
+    struct Op { const char* key; double value; };
+    const Op ops[6] = {{"force_general", 1}, {"force_general", 0}, {"force_dense", 1}, {"force_dense", 0}, {"auto_dense", 0}, {"auto_dense", 1}};
+    int order[6] = {0, 1, 2, 3, 4, 5};
+    do {
+      Tuning t = t0;
+      for (const int o : order) {
+        bool upload = true;
+        CHECK(set_tuning(t, d, ops[o].key, ops[o].value, &upload) == QC_OK && !upload, "parameter set %d key %s", s, ops[o].key);
+        Tuning fresh = t;
+        resolve_form(fresh);
+        const bool six = t.cfg_diag_w && !t.force_dense && !(t.small_w && t.auto_dense);
+        const int want = !six ? QC_FORM_DENSE : (t.cfg_uniform && !t.force_general ? QC_FORM_UNIFORM : QC_FORM_GENERAL);
+        CHECK(form_of(t) == form_of(fresh) && form_of(t) == want, "parameter set %d order %d%d%d%d%d%d at %s = %g", s, order[0], order[1], order[2],
+              order[3], order[4], order[5], ops[o].key, ops[o].value);
+      }
+    } while (std::next_permutation(order, order + 6));
+  }
+  qc_params p = cheetah_params();
+  p.max_iter = 150;
+  DevParams d;
+  Tuning t;
+  bool upload = false;
+  CHECK(derive_params(&p, d, t) == QC_OK, "cheetah");
+  CHECK_FAILS(set_tuning(t, d, "bogus", 1, &upload), QC_ERR_INVALID, "qc_set_tuning: unknown key 'bogus'", "unknown key");
+  CHECK_FAILS(set_tuning(t, d, "one_fill", 0, &upload), QC_ERR_INVALID, "qc_set_tuning: one_fill = 0 asked for the persistent-wave kernels, which were removed", "one_fill 0");
+  CHECK_FAILS(set_tuning(t, d, "max_iter", QC_MAX_ITER_LIMIT + 1, &upload), QC_ERR_INVALID, "qc_set_tuning: max_iter must be <= 65535", "max_iter 65536");
+  CHECK_FAILS(set_tuning(t, d, "group", 3, &upload), QC_ERR_INVALID, "qc_set_tuning: group is 0 (heuristic), 1, 2 or 4", "group 3");
+  CHECK(d.max_iter == 150 && t.group_override == 0, "a refused call changes nothing");
+  // the probe and the cap restore what qc_create was given
+  CHECK(set_tuning(t, d, "probe_batch_load", 1, &upload) == QC_OK && upload && d.max_iter == 0 && t.probing, "probe on");
+  CHECK(set_tuning(t, d, "probe_batch_load", 0, &upload) == QC_OK && upload && d.max_iter == 150 && !t.probing, "probe off");
+  CHECK(set_tuning(t, d, "max_iter", 7, &upload) == QC_OK && d.max_iter == 7, "max_iter 7");
+  CHECK(set_tuning(t, d, "max_iter", 0, &upload) == QC_OK && d.max_iter == 150, "max_iter 0");
+  // polish and tol_d keep tol_start = +-tol_d
+  CHECK(set_tuning(t, d, "polish", 0, &upload) == QC_OK && d.polish == 0 && d.tol_start == -d.tol_d && d.tol_d == 1e-14, "polish 0");
+  CHECK(set_tuning(t, d, "tol_d", 1e-12, &upload) == QC_OK && d.tol_d == 1e-12 && d.tol_start == -1e-12, "tol_d with polish 0");
+  CHECK(set_tuning(t, d, "polish", 1, &upload) == QC_OK && d.polish == 1 && d.tol_start == 1e-12, "polish 1");
+  CHECK(set_tuning(t, d, "tol_d", 1e-13, &upload) == QC_OK && d.tol_d == 1e-13 && d.tol_start == 1e-13, "tol_d with polish 1");
+  CHECK(set_tuning(t, d, "race", 0, &upload) == QC_OK && t.race_override == 0 && d.tail_race == 0, "race 0");
+  CHECK(set_tuning(t, d, "race", -1, &upload) == QC_OK && t.race_override == -1 && d.tail_race == 1, "race -1");
+  // exactly the keys that change a device constant ask for the upload
+  struct Key { const char* key; double value; bool uploads; };
+  const Key keys[] = {{"group", 2, false}, {"one_fill", 1, false}, {"chunk", 8, false}, {"wave_slots", 512, false}, {"race", 2, true}, {"pair", 1, false},
+                      {"pair_th", 8, false}, {"pair_refill", 2, false}, {"pair_solo", 0, false}, {"force_general", 1, false}, {"force_dense", 1, false},
+                      {"auto_dense", 0, false}, {"tol_d", 1e-13, true}, {"max_iter", 50, true}, {"clamp_steps", 3, true}, {"polish", 0, true},
+                      {"probe_batch_load", 1, true}};
+  for (const Key& k : keys) {
+    upload = !k.uploads;
+    CHECK(set_tuning(t, d, k.key, k.value, &upload) == QC_OK && upload == k.uploads, "key %s", k.key);
+  }
+  CHECK(t.group_override == 2 && t.chunk_override == 8 && t.wave_slots_override == 512 && t.race_override == 2 && t.pair_override == 1 && t.pair_th == 8 &&
+            t.pair_refill == 2 && t.pair_solo == 0 && d.clamp_steps == 3, "the overrides land in their fields");
+}
+
+// ------------------------------------------------------------------------------------------------ (d) argument checks
+static double g_buf[1];
+static void argument_checks() {
+  double* const a = g_buf;  // stands for an array: the checks look at pointers, never through them
+  const qc_handle* const h = reinterpret_cast<const qc_handle*>(g_buf);
+  const qc_batch_in in_ok{a, a, a, a, a, a, a, a, a, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  const qc_batch_out out_ok{a, reinterpret_cast<int32_t*>(a), nullptr, nullptr, nullptr};
+  for (const bool first : {true, false}) {
+    const char* who = first ? "qc_control_batch" : "qc_control_batch_host";
+    const auto msg = [who](const char* what) { return std::string(who) + what; };
+    CHECK(check_batch_args(who, h, 5, &in_ok, &out_ok, first) == QC_OK, "%s: the smallest valid call", who);
+    CHECK_FAILS(check_batch_args(who, nullptr, 5, &in_ok, &out_ok, first), QC_ERR_INVALID, msg(": null argument"), "%s: no handle", who);
+    CHECK_FAILS(check_batch_args(who, h, 5, nullptr, &out_ok, first), QC_ERR_INVALID, msg(": null argument"), "%s: no in", who);
+    CHECK_FAILS(check_batch_args(who, h, 5, &in_ok, nullptr, first), QC_ERR_INVALID, msg(": null argument"), "%s: no out", who);
+    const qc_batch_in none{};
+    const qc_batch_out nothing{};
+    CHECK(check_batch_args(who, h, 0, &none, &nothing, first) == QC_OK, "%s: an empty batch needs no arrays", who);
+    const double* qc_batch_in::*const required[] = {&qc_batch_in::Rwb, &qc_batch_in::Rwb_d, &qc_batch_in::x, &qc_batch_in::xdot, &qc_batch_in::w,
+                                                    &qc_batch_in::x_d, &qc_batch_in::xdot_d, &qc_batch_in::w_d, &qc_batch_in::feet};
+    for (int i = 0; i < 9; i++) {
+      qc_batch_in in = in_ok;
+      in.*required[i] = nullptr;
+      CHECK_FAILS(check_batch_args(who, h, 5, &in, &out_ok, first), QC_ERR_INVALID, msg(": null input array"), "%s: required array %d missing", who, i);
+      if (i == 8) {  // joint_q stands in for feet
+        in.joint_q = a;
+        CHECK(check_batch_args(who, h, 5, &in, &out_ok, first) == QC_OK, "%s: joint_q instead of feet", who);
+      }
+    }
+    qc_batch_out out = out_ok;
+    out.grf_body = nullptr;
+    CHECK_FAILS(check_batch_args(who, h, 5, &in_ok, &out, first), QC_ERR_INVALID, msg(": grf_body and status are required"), "%s: no grf_body", who);
+    out = out_ok;
+    out.status = nullptr;
+    CHECK_FAILS(check_batch_args(who, h, 5, &in_ok, &out, first), QC_ERR_INVALID, msg(": grf_body and status are required"), "%s: no status", who);
+    out = out_ok;
+    out.joint_tau = a;
+    CHECK_FAILS(check_batch_args(who, h, 5, &in_ok, &out, first), QC_ERR_INVALID, msg(": joint_tau needs joint_q"), "%s: joint_tau alone", who);
+    // both at once: each entry point keeps its own order
+    out.status = nullptr;
+    CHECK_FAILS(check_batch_args(who, h, 5, &in_ok, &out, first), QC_ERR_INVALID, msg(first ? ": grf_body and status are required" : ": joint_tau needs joint_q"),
+                "%s: joint_tau alone and no status", who);
+  }
+  // qc_control_batch: the swing and gait arrays that go together
+  {
+    const char* const together = "qc_control_batch: swing_pos, swing_vel and joint_qdot go together and need joint_q and joint_tau";
+    const char* const clock = "qc_control_batch: gait_dt advances gait_phase (needed, and stance must be NULL)";
+    const char* const stateful = "qc_control_batch: swing_state needs joint_q, joint_qdot, gait_phase and joint_tau, and excludes swing_pos/swing_vel";
+    qc_swing_state* const ss = reinterpret_cast<qc_swing_state*>(g_buf);
+    qc_batch_out out = out_ok;
+    out.joint_tau = a;
+    qc_batch_in in = in_ok;
+    in.joint_q = in.swing_pos = in.swing_vel = in.joint_qdot = a;
+    CHECK(check_swing_gait_args(&in_ok, &out_ok) == QC_OK && check_swing_gait_args(&in, &out) == QC_OK, "no swing arrays, and all three");
+    const double* qc_batch_in::*const three[] = {&qc_batch_in::swing_pos, &qc_batch_in::swing_vel, &qc_batch_in::joint_qdot};
+    for (int i = 0; i < 3; i++) {
+      qc_batch_in one = in_ok, two = in;
+      one.*three[i] = a;
+      two.*three[i] = nullptr;
+      CHECK_FAILS(check_swing_gait_args(&one, &out_ok), QC_ERR_INVALID, together, "swing array %d alone", i);
+      CHECK_FAILS(check_swing_gait_args(&two, &out), QC_ERR_INVALID, together, "swing array %d missing", i);
+    }
+    qc_batch_in bad = in;
+    bad.joint_q = nullptr;
+    CHECK_FAILS(check_swing_gait_args(&bad, &out), QC_ERR_INVALID, together, "swing arrays without joint_q");
+    CHECK_FAILS(check_swing_gait_args(&in, &out_ok), QC_ERR_INVALID, together, "swing arrays without joint_tau");
+    bad = in_ok;
+    bad.gait_dt = a;
+    CHECK_FAILS(check_swing_gait_args(&bad, &out_ok), QC_ERR_INVALID, clock, "gait_dt without gait_phase");
+    bad.gait_phase = a;
+    CHECK(check_swing_gait_args(&bad, &out_ok) == QC_OK, "gait_dt with gait_phase");
+    bad.stance = reinterpret_cast<const uint8_t*>(a);
+    CHECK_FAILS(check_swing_gait_args(&bad, &out_ok), QC_ERR_INVALID, clock, "gait_dt with stance");
+    qc_batch_in st = in_ok;
+    st.swing_state = ss; st.joint_q = st.joint_qdot = st.gait_phase = a;
+    CHECK(check_swing_gait_args(&st, &out) == QC_OK, "the smallest stateful tick");
+    CHECK_FAILS(check_swing_gait_args(&st, &out_ok), QC_ERR_INVALID, stateful, "swing_state without joint_tau");
+    const double* qc_batch_in::*const needs[] = {&qc_batch_in::joint_q, &qc_batch_in::joint_qdot};
+    for (int i = 0; i < 2; i++) {
+      bad = st;
+      bad.*needs[i] = nullptr;
+      CHECK_FAILS(check_swing_gait_args(&bad, &out), QC_ERR_INVALID, stateful, "swing_state without array %d", i);
+    }
+    bad = st;
+    bad.gait_phase = nullptr;
+    CHECK_FAILS(check_swing_gait_args(&bad, &out), QC_ERR_INVALID, stateful, "swing_state without gait_phase");
+    bad = st;
+    bad.swing_pos = a;
+    CHECK_FAILS(check_swing_gait_args(&bad, &out), QC_ERR_INVALID, stateful, "swing_state with swing_pos");
+    bad = st;
+    bad.swing_vel = a;
+    CHECK_FAILS(check_swing_gait_args(&bad, &out), QC_ERR_INVALID, stateful, "swing_state with swing_vel");
+  }
+  // qc_tick_batch
+  {
+    qc_batch_in in{};
+    in.Rwb = in.x = in.xdot = in.w = in.joint_q = in.joint_qdot = in.gait_dt = a;
+    in.gait_phase = a;
+    in.swing_state = reinterpret_cast<qc_swing_state*>(g_buf);
+    qc_batch_out out = out_ok;
+    out.joint_tau = a;
+    qc_command_in cmd{};
+    cmd.struct_size = sizeof(qc_command_in);
+    cmd.state = reinterpret_cast<qc_commander_state*>(g_buf);
+    cmd.stand_height = 0.26; cmd.stand_tol = 0.005; cmd.cmd_dt = 0.001;
+    CHECK(check_tick_args(h, &in, &cmd, &out) == QC_OK, "the smallest valid tick");
+    const char* const null_arg = "qc_tick_batch: null argument";
+    CHECK_FAILS(check_tick_args(nullptr, &in, &cmd, &out), QC_ERR_INVALID, null_arg, "no handle");
+    CHECK_FAILS(check_tick_args(h, nullptr, &cmd, &out), QC_ERR_INVALID, null_arg, "no in");
+    CHECK_FAILS(check_tick_args(h, &in, nullptr, &out), QC_ERR_INVALID, null_arg, "no cmd");
+    CHECK_FAILS(check_tick_args(h, &in, &cmd, nullptr), QC_ERR_INVALID, null_arg, "no out");
+    qc_command_in c = cmd;
+    c.struct_size = sizeof(qc_command_in) - 8;
+    char text[160];
+    std::snprintf(text, sizeof(text), "qc_tick_batch: qc_command_in.struct_size is %zu, this library's qc_command_in has %zu B (qc_default_command sets it)",
+                  sizeof(qc_command_in) - 8, sizeof(qc_command_in));
+    CHECK_FAILS(check_tick_args(h, &in, &c, &out), QC_ERR_INVALID, text, "struct_size of another revision");
+    const char* const needs = "qc_tick_batch: the complete tick needs Rwb, x, xdot, w, joint_q, joint_qdot, gait_phase, gait_dt and swing_state";
+    const double* qc_batch_in::*const required[] = {&qc_batch_in::Rwb, &qc_batch_in::x, &qc_batch_in::xdot, &qc_batch_in::w,
+                                                    &qc_batch_in::joint_q, &qc_batch_in::joint_qdot, &qc_batch_in::gait_dt};
+    qc_batch_in bad;
+    for (int i = 0; i < 7; i++) {
+      bad = in;
+      bad.*required[i] = nullptr;
+      CHECK_FAILS(check_tick_args(h, &bad, &cmd, &out), QC_ERR_INVALID, needs, "required array %d missing", i);
+    }
+    bad = in; bad.gait_phase = nullptr;
+    CHECK_FAILS(check_tick_args(h, &bad, &cmd, &out), QC_ERR_INVALID, needs, "no gait_phase");
+    bad = in; bad.swing_state = nullptr;
+    CHECK_FAILS(check_tick_args(h, &bad, &cmd, &out), QC_ERR_INVALID, needs, "no swing_state");
+    const char* const desired = "qc_tick_batch: Rwb_d, x_d, xdot_d and w_d must be NULL (the desired state lives in qc_command_in.state)";
+    const double* qc_batch_in::*const des[] = {&qc_batch_in::Rwb_d, &qc_batch_in::x_d, &qc_batch_in::xdot_d, &qc_batch_in::w_d};
+    for (int i = 0; i < 4; i++) {
+      bad = in;
+      bad.*des[i] = a;
+      CHECK_FAILS(check_tick_args(h, &bad, &cmd, &out), QC_ERR_INVALID, desired, "desired-state array %d given", i);
+    }
+    const char* const made = "qc_tick_batch: stance, swing_pos and swing_vel must be NULL (the gait clock and the planner make them)";
+    bad = in; bad.stance = reinterpret_cast<const uint8_t*>(a);
+    CHECK_FAILS(check_tick_args(h, &bad, &cmd, &out), QC_ERR_INVALID, made, "stance given");
+    bad = in; bad.swing_pos = a;
+    CHECK_FAILS(check_tick_args(h, &bad, &cmd, &out), QC_ERR_INVALID, made, "swing_pos given");
+    bad = in; bad.swing_vel = a;
+    CHECK_FAILS(check_tick_args(h, &bad, &cmd, &out), QC_ERR_INVALID, made, "swing_vel given");
+    const char* const outputs = "qc_tick_batch: grf_body, status and joint_tau are required";
+    qc_batch_out o = out; o.grf_body = nullptr;
+    CHECK_FAILS(check_tick_args(h, &in, &cmd, &o), QC_ERR_INVALID, outputs, "no grf_body");
+    o = out; o.status = nullptr;
+    CHECK_FAILS(check_tick_args(h, &in, &cmd, &o), QC_ERR_INVALID, outputs, "no status");
+    CHECK_FAILS(check_tick_args(h, &in, &cmd, &out_ok), QC_ERR_INVALID, outputs, "no joint_tau");
+    c = cmd; c.state = nullptr;
+    CHECK_FAILS(check_tick_args(h, &in, &c, &out), QC_ERR_INVALID, "qc_tick_batch: qc_command_in.state is required", "no state");
+    c = cmd; c.fresh = reinterpret_cast<const uint8_t*>(a);
+    CHECK_FAILS(check_tick_args(h, &in, &c, &out), QC_ERR_INVALID, "qc_tick_batch: qc_command_in.fresh needs twist", "fresh without twist");
+    c.twist = a;
+    CHECK(check_tick_args(h, &in, &c, &out) == QC_OK, "fresh with twist");
+    const char* const finite = "qc_tick_batch: stand_height, stand_tol (>= 0) and cmd_dt must be finite";
+    c = cmd; c.stand_height = INFINITY;
+    CHECK_FAILS(check_tick_args(h, &in, &c, &out), QC_ERR_INVALID, finite, "stand_height inf");
+    c = cmd; c.stand_tol = -1e-9;
+    CHECK_FAILS(check_tick_args(h, &in, &c, &out), QC_ERR_INVALID, finite, "stand_tol < 0");
+    c = cmd; c.stand_tol = INFINITY;
+    CHECK_FAILS(check_tick_args(h, &in, &c, &out), QC_ERR_INVALID, finite, "stand_tol inf");
+    c = cmd; c.cmd_dt = NAN;
+    CHECK_FAILS(check_tick_args(h, &in, &c, &out), QC_ERR_INVALID, finite, "cmd_dt nan");
+  }
+}
+
+int main() {
+  planner_sweep();
+  derived_constants();
+  tuning();
+  argument_checks();
+  std::printf("host logic ok: %ld checks, %d kernel instantiations\n", g_checked, N_KERNELS);
+  return 0;
+}

@@ -1,6 +1,6 @@
 """-m gpu: oracle parity over EVERY kernel instantiation the launch planner can pick.
 
-The planner (plan_launch, qc_balance.hip) chooses by formulation (uniform 6x6 / general 6x6 / dense 12x12),
+The planner (plan_launch, qc_host.hpp) chooses by formulation (uniform 6x6 / general 6x6 / dense 12x12),
 lanes per robot (1 / 2 / 4) and kernel mode (1 one fill per wave, 2 one fill
 with register-resident constants, 3 paired waves: two one-lane waves per workgroup, the last to arrive finishes both
 waves' stragglers from a list in LDS).  Each test forces one branch with qc_set_tuning, checks through qc_query_launch

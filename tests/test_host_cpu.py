@@ -82,8 +82,28 @@ def test_param_struct_layout_matches_c():
 
 def test_library_reads_no_environment():
     """Stray QC_* variables must not alter the controller: every override goes through qc_set_tuning."""
-    src = open(os.path.join(ROOT, "quadruped_control_amd", "csrc", "qc_balance.hip")).read()
-    assert "getenv" not in src
+    csrc = os.path.join(ROOT, "quadruped_control_amd", "csrc")
+    files = sorted(os.listdir(csrc))
+    assert {"qc_balance.hip", "qc_device.hpp", "qc_host.hpp"} <= set(files)
+    for f in files:
+        assert "getenv" not in open(os.path.join(csrc, f)).read(), f
+
+
+def test_host_logic_without_a_device():
+    """The planner against the library's own list of kernel instantiations, the constants qc_create derives, the tuning setter and
+    the argument checks of the batch entry points (csrc/qc_host.hpp), in a stand-alone program built with the address and
+    undefined-behaviour sanitizers (tests/cpp/host_logic_test.cpp): it prints the failing case and exits non-zero on the first
+    violated check or sanitizer report."""
+    import subprocess
+
+    import __graft_entry__ as g
+
+    exe = g.build_host_logic_test()
+    assert exe is not None and os.path.exists(exe)
+    libs = subprocess.run(["ldd", exe], stdout=subprocess.PIPE, text=True, check=True).stdout
+    assert "amdhip64" not in libs and "qc_balance" not in libs, libs
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
+    assert r.returncode == 0 and "host logic ok" in r.stdout, r.stdout[-3000:]
 
 
 def test_no_gpu_fails_loudly(built):
