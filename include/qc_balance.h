@@ -315,6 +315,33 @@ void qc_commander_state_init(qc_commander_state* states, size_t n, const double 
 int qc_tick_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_command_in* cmd, const uint32_t* warm,
                   const qc_batch_out* out, void* stream);
 
+/* Closing the loop: one step of the plant the controller itself assumes, BalanceController::dynamics()
+ * (balance_controller.cpp:237-272) - ONE rigid body with world-frame forces at the feet - so that a batch advances on the
+ * device between two qc_control_batch launches.  Per robot (mass and Ib from the handle, g = 9.81):
+ *   f_i = -Rwb grf_body_i,  r_i = foot_world_i - x,  a = (sum f_i) / m - (0, 0, g),
+ *   wdot = Iw^-1 (sum r_i x f_i - w x (Iw w)),  Iw = Rwb Ib Rwb^T,
+ *   xdot' = xdot + dt a,  x' = x + dt xdot',  w' = w + dt wdot,  Rwb' = Exp(dt w') Rwb   (semi-implicit Euler, Rodrigues).
+ * `w` is the angular velocity in the WORLD frame, as control() takes it.  `grf_body` is what qc_control_batch wrote (negated,
+ * body frame; 0 for swing legs and failed robots - a failed QP is free fall for that step).  There is NO contact model: the
+ * forces are applied as given and a stance foot is where foot_world says it is; the body has no legs, so joints and the
+ * leg-level tick (joint_q, qc_tick_batch) are outside this model.  Each robot's inputs are all read before any of its outputs
+ * is written: the state is updated in place, and `feet` - Rwb'^T (foot_world_i - x'), the array the next qc_control_batch
+ * reads - may be any array of that layout, foot_world included.  All pointers are DEVICE pointers. */
+typedef struct qc_plant_io {
+  size_t struct_size;        /* = sizeof(qc_plant_io); checked, like qc_command_in                         */
+  double *Rwb, *x, *xdot, *w; /* [n][9], [n][3], [n][3], [n][3] IN/OUT                                       */
+  const double* grf_body;    /* [n][4][3] qc_batch_out.grf_body                                            */
+  const double* foot_world;  /* [n][4][3] world positions of the four feet                                 */
+  double* feet;              /* [n][4][3] OUT, optional (NULL): body-frame feet of the new state           */
+  double dt;                 /* seconds, finite, > 0                                                       */
+} qc_plant_io;
+/* struct_size set, pointers NULL, dt = 1/300 (mit_cheetah_config.yaml:3). */
+void qc_default_plant(qc_plant_io* io);
+/* Asynchronous on `stream`, no host synchronisation; n == 0 launches nothing.  QC_ERR_INVALID (message starting with
+ * "qc_plant_step_batch:", nothing launched) for a null required pointer, a wrong struct_size, a dt that is not finite and
+ * > 0, or a handle whose Ib is not finite, symmetric and positive definite (qc_create itself does not ask that of Ib). */
+int qc_plant_step_batch(qc_handle* h, size_t n, const qc_plant_io* io, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,11 @@ class QcCommandIn(C.Structure):
                 ("stand_height", C.c_double), ("stand_tol", C.c_double), ("cmd_dt", C.c_double)]
 
 
+class QcPlantIo(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("Rwb", C.c_void_p), ("x", C.c_void_p), ("xdot", C.c_void_p), ("w", C.c_void_p),
+                ("grf_body", C.c_void_p), ("foot_world", C.c_void_p), ("feet", C.c_void_p), ("dt", C.c_double)]
+
+
 class QcLaunchInfo(C.Structure):
     _fields_ = [("lanes_per_robot", C.c_int32), ("mode", C.c_int32), ("form", C.c_int32), ("strategies", C.c_int32),
                 ("chunk", C.c_int64), ("blocks", C.c_int64), ("resident_workgroups", C.c_int64), ("lds_bytes", C.c_int64)]
@@ -63,7 +68,8 @@ class QcLaunchInfo(C.Structure):
 
 EXPORTS = ("qc_create_abi", "qc_destroy", "qc_control_batch", "qc_control_batch_host", "qc_control",
            "qc_last_error", "qc_kernel_name", "qc_abi_version", "qc_default_kinematics", "qc_set_kinematics", "qc_set_gait", "qc_swing_state_init",
-           "qc_set_tuning", "qc_query_launch", "qc_check_abi", "qc_default_command", "qc_commander_state_init", "qc_tick_batch")
+           "qc_set_tuning", "qc_query_launch", "qc_check_abi", "qc_default_command", "qc_commander_state_init", "qc_tick_batch",
+           "qc_default_plant", "qc_plant_step_batch")
 
 _lib = None
 
@@ -130,6 +136,10 @@ def load():
     lib.qc_tick_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcBatchIn), C.POINTER(QcCommandIn), C.c_void_p,
                                   C.POINTER(QcBatchOut), C.c_void_p]
     lib.qc_tick_batch.restype = C.c_int
+    lib.qc_default_plant.argtypes = [C.POINTER(QcPlantIo)]
+    lib.qc_default_plant.restype = None
+    lib.qc_plant_step_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcPlantIo), C.c_void_p]
+    lib.qc_plant_step_batch.restype = C.c_int
     # the structures above are hand-written mirrors of the header: a library built from another revision is refused here,
     # before any of them crosses the boundary
     rc = lib.qc_check_abi(ABI_VERSION, C.sizeof(QcParams), C.sizeof(QcBatchIn), C.sizeof(QcBatchOut))

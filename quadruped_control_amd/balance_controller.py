@@ -348,6 +348,94 @@ class BalanceController:
         launch()
         return out
 
+    # ------------------------------------------------------- closing the loop
+    def _marshal_plant(self, state, grf_body, foot_world, dt, feet):
+        """Validate the arguments of plant_step() and build its C struct.  Launches nothing."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        n = state["x"].shape[0]
+        io = _lib.QcPlantIo()
+        self._lib.qc_default_plant(C.byref(io))
+        arrays = [(k, state.get(k), m) for k, m in (("Rwb", 9), ("x", 3), ("xdot", 3), ("w", 3))]
+        arrays += [("grf_body", grf_body, 12), ("foot_world", foot_world, 12)] + ([("feet", feet, 12)] if feet is not None else [])
+        for name, t, k in arrays:
+            if t is None or t.dtype != torch.float64 or not t.is_contiguous() or t.device != dev or t.numel() != n * k:
+                raise ValueError(f"{name}: need contiguous float64 [{n},{k}] on {dev}")
+            setattr(io, name, t.data_ptr() if n else None)
+        io.dt = float(dt)
+        return n, io
+
+    def plan_plant(self, state, grf_body, foot_world, dt, feet=None, stream=None):
+        """plant_step() marshalled once: returns `launch`, one qc_plant_step_batch call on tensors that are updated in place."""
+        import torch
+
+        n, io = self._marshal_plant(state, grf_body, foot_world, dt, feet)
+        s = stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.device))
+        fn, h, sp, io_ref = self._lib.qc_plant_step_batch, self._h, C.c_void_p(s.cuda_stream), C.byref(io)
+        keep = (state, grf_body, foot_world, feet, io)
+
+        def launch(_keep=keep):
+            rc = fn(h, n, io_ref, sp)
+            if rc != _lib.QC_OK:
+                raise RuntimeError(f"qc_plant_step_batch failed ({rc}): {_lib.last_error()}")
+
+        return launch
+
+    def plant_step(self, state, grf_body, foot_world, dt, feet=None, stream=None):
+        """One step of the plant the controller itself assumes (qc_plant_step_batch, include/qc_balance.h): a single rigid body
+        with world-frame forces at the feet, semi-implicit Euler.  `state`: dict of device tensors Rwb [n,9], x, xdot, w [n,3]
+        (w in the world frame), updated IN PLACE; `grf_body` [n,12] as control_batch() wrote it; `foot_world` [n,12] world
+        positions of the feet; `feet` [n,12] optional output, the body-frame feet of the new state (the `feet` the next
+        control_batch() reads).  No contact model: forces are applied as given, a failed QP (zero forces) is free fall.
+        Asynchronous on `stream` (default: torch's current stream).  Returns `state`."""
+        self.plan_plant(state, grf_body, foot_world, dt, feet, stream)()
+        return state
+
+    def rollout(self, batch, foot_world, steps, dt, warm=True, record_every=None, stream=None):
+        """Closed loop on the device: `steps` times control_batch() then plant_step(), on one stream and without a host round
+        trip.  `batch`: device tensors as for control_batch() with `feet` (not joint_q); its Rwb, x, xdot, w and feet are
+        advanced IN PLACE, the desired state and `stance` are held.  `foot_world` [n,12]: world positions of the feet, held.
+        warm=True feeds each solve's active_set back as the next solve's warm start (the first solve is cold).  Everything is
+        marshalled once (plan_batch); the loop itself is two C calls per step.  Returns (state, out): the final state (the
+        tensors of `batch`) and the outputs of the LAST solve, i.e. the forces that produced the last step.  No history is
+        kept unless record_every=k: then `out["history"]` is a list of (step, {Rwb, x, xdot, w, feet} clones) of the state BEFORE
+        steps 0, k, 2k, ... - device tensors, no synchronisation."""
+        import torch
+
+        if batch.get("joint_q") is not None or batch.get("feet") is None:
+            raise ValueError("rollout: the plant is a single rigid body - the batch carries `feet`, not joint_q")
+        steps = int(steps)
+        if steps < 0:
+            raise ValueError("rollout: steps must be >= 0")
+        n = batch["x"].shape[0]
+        dev = torch.device("cuda", self.device)
+        state = {k: batch[k] for k in ("Rwb", "x", "xdot", "w")}
+        out = {"grf_body": torch.zeros((n, 12), dtype=torch.float64, device=dev),
+               "status": torch.full((n,), -1, dtype=torch.int32, device=dev)}
+        # the working sets ping-pong between two arrays: a solve never reads the array it writes
+        sets = [torch.zeros((n,), dtype=torch.int32, device=dev) for _ in range(2)] if warm else []
+        solves = []
+        if warm:
+            cold, _ = self.plan_batch(batch, None, dict(out, active_set=sets[0]), want_active_set=True, stream=stream)
+            a, _ = self.plan_batch(batch, sets[0], dict(out, active_set=sets[1]), want_active_set=True, stream=stream)
+            b, _ = self.plan_batch(batch, sets[1], dict(out, active_set=sets[0]), want_active_set=True, stream=stream)
+            solves = [cold, a, b]
+        else:
+            solves = [self.plan_batch(batch, None, out, stream=stream)[0]]
+        step = self.plan_plant(state, out["grf_body"], foot_world, dt, batch["feet"], stream)
+        history = [] if record_every else None
+        for k in range(steps):
+            if history is not None and k % int(record_every) == 0:
+                history.append((k, {name: batch[name].clone() for name in ("Rwb", "x", "xdot", "w", "feet")}))
+            solves[0 if (k == 0 or not warm) else 1 + (k - 1) % 2]()
+            step()
+        if warm and steps > 0:
+            out["active_set"] = sets[steps % 2 == 0]  # step 0 wrote sets[0], step 1 sets[1], step 2 sets[0], ...
+        if history is not None:
+            out["history"] = history
+        return state, out
+
     def control_batch_host(self, batch, warm=None, want_active_set=False, want_iterations=False, want_torques=False):
         """n robots, numpy (host) arrays in and out; PCIe-inclusive convenience path."""
         n = batch["x"].shape[0]

@@ -16,6 +16,7 @@
 #include "../../include/qc_balance.h"
 #include "qc_device.hpp"
 #include "qc_host.hpp"
+#include "qc_plant.hpp"
 
 namespace qc {
 
@@ -2153,6 +2154,26 @@ int qc_tick_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_comman
                  cmd->stand_height, cmd->stand_tol, cmd->cmd_dt};
   qc::BatchOut bo{out->grf_body, out->status, out->active_set, out->iterations, out->joint_tau};
   return launch_batch(h, n, true, bi, warm, bo, stream);
+}
+
+void qc_default_plant(qc_plant_io* io) {
+  if (!io) return;
+  std::memset(io, 0, sizeof(*io));
+  io->struct_size = sizeof(qc_plant_io);
+  io->dt = 1.0 / 300.0;  // mit_cheetah_config.yaml:3
+}
+
+int qc_plant_step_batch(qc_handle* h, size_t n, const qc_plant_io* io, void* stream) {
+  if (const int rc = qc::check_plant_args(h, n, io); rc != QC_OK || n == 0) return rc;
+  qc::PlantArgs a;
+  if (const int rc = qc::plant_constants(h->dp.mass, h->dp.Ib, io->dt, a); rc != QC_OK) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  a.Rwb = io->Rwb; a.x = io->x; a.xdot = io->xdot; a.w = io->w;
+  a.grf_body = io->grf_body; a.foot_world = io->foot_world; a.feet = io->feet;
+  const unsigned blocks = (unsigned)((n + qc::PLANT_BLOCK - 1) / qc::PLANT_BLOCK);
+  qc::plant_step_kernel<<<dim3(blocks), dim3(qc::PLANT_BLOCK), 0, (hipStream_t)stream>>>((long)n, a);
+  QC_HIP(hipGetLastError());
+  return QC_OK;
 }
 
 // host-pointer variant.  Large batches: one device staging allocation, H2D copies, kernel, D2H copies, sync.

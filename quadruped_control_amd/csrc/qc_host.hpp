@@ -9,6 +9,7 @@
 
 #include "../../include/qc_balance.h"
 #include "qc_device.hpp"
+#include "qc_plant.hpp"
 
 namespace qc {
 
@@ -439,6 +440,50 @@ inline int check_tick_args(const qc_handle* h, const qc_batch_in* in, const qc_c
   if (cmd->fresh && !cmd->twist) return fail(QC_ERR_INVALID, "qc_tick_batch: qc_command_in.fresh needs twist");
   if (!std::isfinite(cmd->stand_height) || !(cmd->stand_tol >= 0.0) || !std::isfinite(cmd->stand_tol) || !std::isfinite(cmd->cmd_dt))
     return fail(QC_ERR_INVALID, "qc_tick_batch: stand_height, stand_tol (>= 0) and cmd_dt must be finite");
+  return QC_OK;
+}
+
+// ---------------------------------------------------------------- qc_plant_step_batch
+// Ib^-1 for the plant step.  qc_create reads Ib only through the wrench law, which needs nothing of it, and keeps accepting what it
+// always has; a rigid body that is to be integrated needs a finite, symmetric positive definite inertia, so the plant refuses the rest.
+inline int plant_inertia_inverse(const double* Ib, double* Ib_inv) {
+  for (int i = 0; i < 9; i++)
+    if (!std::isfinite(Ib[i])) return fail(QC_ERR_INVALID, "qc_plant_step_batch: the handle's Ib is not finite");
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < i; j++)
+      if (std::fabs(Ib[3 * i + j] - Ib[3 * j + i]) > 1e-12 * (std::fabs(Ib[3 * i + i]) + std::fabs(Ib[3 * j + j])))
+        return fail(QC_ERR_INVALID, "qc_plant_step_batch: the handle's Ib is not symmetric");
+  if (!spd_inverse(Ib, 3, Ib_inv)) return fail(QC_ERR_INVALID, "qc_plant_step_batch: the handle's Ib is not positive definite");
+  for (int i = 0; i < 9; i++)  // (an Ib whose entries are finite but whose inverse overflows)
+    if (!std::isfinite(Ib_inv[i])) return fail(QC_ERR_INVALID, "qc_plant_step_batch: the handle's Ib is not positive definite");
+  return QC_OK;
+}
+
+// the kernel's constants from the handle's mass and Ib and the call's dt
+inline int plant_constants(double mass, const double* Ib, double dt, PlantArgs& a) {
+  if (!std::isfinite(mass) || !(mass > 0.0)) return fail(QC_ERR_INVALID, "qc_plant_step_batch: the handle's mass is not finite and > 0");
+  if (const int rc = plant_inertia_inverse(Ib, a.Ib_inv); rc != QC_OK) return rc;
+  a.mass = mass;
+  std::memcpy(a.Ib, Ib, sizeof(a.Ib));
+  a.g = PLANT_G;
+  a.dt = dt;
+  return QC_OK;
+}
+
+inline int check_plant_args(const qc_handle* h, size_t n, const qc_plant_io* io) {
+  if (!h || !io) return fail(QC_ERR_INVALID, "qc_plant_step_batch: null argument");
+  if (io->struct_size != sizeof(qc_plant_io)) {
+    char msg[160];
+    std::snprintf(msg, sizeof(msg), "qc_plant_step_batch: qc_plant_io.struct_size is %zu, this library's qc_plant_io has %zu B (qc_default_plant sets it)",
+                  io->struct_size, sizeof(qc_plant_io));
+    return fail(QC_ERR_INVALID, msg);
+  }
+  if (!std::isfinite(io->dt) || !(io->dt > 0.0)) return fail(QC_ERR_INVALID, "qc_plant_step_batch: dt must be finite and > 0");
+  if (n == 0) return QC_OK;
+  if (!io->Rwb || !io->x || !io->xdot || !io->w) return fail(QC_ERR_INVALID, "qc_plant_step_batch: the state arrays Rwb, x, xdot and w are required");
+  if (!io->grf_body || !io->foot_world) return fail(QC_ERR_INVALID, "qc_plant_step_batch: grf_body and foot_world are required");
+  // one lane per robot in blocks of PLANT_BLOCK: a launch holds fewer than 2^32 threads
+  if (n > (size_t)0xFFFFFF * PLANT_BLOCK) return fail(QC_ERR_INVALID, "qc_plant_step_batch: n is beyond one launch");
   return QC_OK;
 }
 

@@ -1,0 +1,168 @@
+// The device-free host logic of the plant step (quadruped_control_amd/csrc/qc_host.hpp): the Ib^-1 computation with what it
+// refuses, the kernel's constants, and the argument check of qc_plant_step_batch.  Host compiler only - links neither HIP nor the
+// library; built with the address and undefined-behaviour sanitizers (__graft_entry__.build_plant_host_test) and run by
+// tests/test_plant_cpu.py.  Prints the failing case and exits 1 on the first violated check.
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <limits>
+#include <string>
+
+#include "../../quadruped_control_amd/csrc/qc_host.hpp"
+
+using namespace qc;
+
+static long g_checked = 0;
+#define CHECK(cond, ...)                                              \
+  do {                                                                \
+    g_checked++;                                                      \
+    if (!(cond)) {                                                    \
+      std::printf("FAILED %s:%d: %s\n  case: ", __FILE__, __LINE__, #cond); \
+      std::printf(__VA_ARGS__);                                       \
+      std::printf("\n  last error: %s\n", g_err.c_str());             \
+      std::exit(1);                                                   \
+    }                                                                 \
+  } while (0)
+// a call that must fail with QC_ERR_INVALID and a message of qc_plant_step_batch's own
+#define CHECK_REFUSED(rc, ...) CHECK((rc) == QC_ERR_INVALID && g_err.rfind("qc_plant_step_batch:", 0) == 0, __VA_ARGS__)
+#define CHECK_FAILS(rc, text, ...) CHECK((rc) == QC_ERR_INVALID && g_err == (text), __VA_ARGS__)
+
+static const double kInf = std::numeric_limits<double>::infinity();
+static const double kNan = std::numeric_limits<double>::quiet_NaN();
+
+// ------------------------------------------------------------------------------------------------ (a) Ib^-1
+static void inertia_inverse() {
+  // the reference's trunk inertia (mit_cheetah_config.yaml) and a full symmetric positive definite one
+  const double diag[9] = {0.011253, 0, 0, 0, 0.036203, 0, 0, 0, 0.042673};
+  const double full[9] = {0.05, 0.01, -0.004, 0.01, 0.08, 0.006, -0.004, 0.006, 0.11};
+  for (const double* Ib : {diag, full}) {
+    double inv[9];
+    CHECK(plant_inertia_inverse(Ib, inv) == QC_OK, "a valid inertia");
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) {
+        double s = 0.0;
+        for (int k = 0; k < 3; k++) s += Ib[3 * i + k] * inv[3 * k + j];
+        // a 3x3 product of entries |Ib| |Ib^-1| <= cond(Ib) ~ 4: three roundings of the inverse and three of the sum
+        CHECK(std::fabs(s - (i == j ? 1.0 : 0.0)) < 64 * 2.220446049250313e-16, "Ib Ib^-1 = I at (%d, %d): %.17g", i, j, s);
+        CHECK(inv[3 * i + j] == inv[3 * j + i] || std::fabs(inv[3 * i + j] - inv[3 * j + i]) < 1e-12 * std::fabs(inv[3 * i + i]), "Ib^-1 symmetric");
+      }
+  }
+  {
+    double inv[9];
+    CHECK(plant_inertia_inverse(diag, inv) == QC_OK && inv[1] == 0.0 && inv[2] == 0.0 && inv[5] == 0.0, "a diagonal inertia has a diagonal inverse");
+    // (1 / sqrt(d)) / sqrt(d): a square root and two divisions
+    for (int k = 0; k < 3; k++) CHECK(std::fabs(inv[4 * k] * diag[4 * k] - 1.0) < 8 * 2.220446049250313e-16, "principal moment %d: %.17g", k, inv[4 * k]);
+  }
+  double inv[9];
+  {
+    double b[9] = {1, 0, 0, 0, 1, 0.25, 0, 0, 1};
+    CHECK_FAILS(plant_inertia_inverse(b, inv), "qc_plant_step_batch: the handle's Ib is not symmetric", "asymmetric");
+  }
+  {
+    double b[9] = {1, 2, 0, 2, 1, 0, 0, 0, 1};
+    CHECK_FAILS(plant_inertia_inverse(b, inv), "qc_plant_step_batch: the handle's Ib is not positive definite", "indefinite");
+  }
+  {
+    double b[9] = {1, 0, 0, 0, 0, 0, 0, 0, 1};
+    CHECK_FAILS(plant_inertia_inverse(b, inv), "qc_plant_step_batch: the handle's Ib is not positive definite", "singular");
+  }
+  {
+    double b[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    CHECK_FAILS(plant_inertia_inverse(b, inv), "qc_plant_step_batch: the handle's Ib is not positive definite", "zero (a zeroed qc_params)");
+  }
+  {
+    double b[9] = {-1, 0, 0, 0, -1, 0, 0, 0, -1};
+    CHECK_FAILS(plant_inertia_inverse(b, inv), "qc_plant_step_batch: the handle's Ib is not positive definite", "negative definite");
+  }
+  for (const double bad : {kNan, kInf, -kInf})
+    for (int k = 0; k < 9; k++) {
+      double b[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+      b[k] = bad;
+      CHECK_FAILS(plant_inertia_inverse(b, inv), "qc_plant_step_batch: the handle's Ib is not finite", "entry %d = %g", k, bad);
+    }
+  {
+    double b[9] = {1e-320, 0, 0, 0, 1, 0, 0, 0, 1};  // finite and positive definite, but its inverse is not representable
+    CHECK_REFUSED(plant_inertia_inverse(b, inv), "a subnormal principal moment");
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ (b) the kernel's constants
+static void constants() {
+  const double Ib[9] = {0.011253, 0, 0, 0, 0.036203, 0, 0, 0, 0.042673};
+  PlantArgs a{};
+  CHECK(plant_constants(9.0, Ib, 1.0 / 300.0, a) == QC_OK, "the reference's robot");
+  CHECK(a.mass == 9.0 && a.g == 9.81 && a.dt == 1.0 / 300.0, "mass, g, dt travel as given");
+  for (int k = 0; k < 9; k++) CHECK(a.Ib[k] == Ib[k], "Ib[%d]", k);
+  CHECK(std::fabs(a.Ib_inv[4] * Ib[4] - 1.0) < 8 * 2.220446049250313e-16 && a.Ib_inv[1] == 0.0, "Ib^-1");
+  for (const double m : {0.0, -1.0, kInf, kNan})
+    CHECK_FAILS(plant_constants(m, Ib, 0.01, a), "qc_plant_step_batch: the handle's mass is not finite and > 0", "mass %g", m);
+  const double zero[9] = {};
+  CHECK_REFUSED(plant_constants(9.0, zero, 0.01, a), "zero inertia");
+}
+
+// ------------------------------------------------------------------------------------------------ (c) check_plant_args
+static void arguments() {
+  static double buf[4];
+  const qc_handle* const h = reinterpret_cast<const qc_handle*>(buf);  // only compared with null
+  qc_plant_io io{};
+  io.struct_size = sizeof(qc_plant_io);
+  io.Rwb = io.x = io.xdot = io.w = buf;
+  io.grf_body = io.foot_world = buf;
+  io.dt = 1.0 / 300.0;
+  CHECK(check_plant_args(h, 1, &io) == QC_OK, "the smallest valid call (feet NULL)");
+  {
+    qc_plant_io c = io;
+    c.feet = buf;
+    CHECK(check_plant_args(h, 4097, &c) == QC_OK, "with feet");
+  }
+  CHECK_FAILS(check_plant_args(nullptr, 1, &io), "qc_plant_step_batch: null argument", "no handle");
+  CHECK_FAILS(check_plant_args(h, 1, nullptr), "qc_plant_step_batch: null argument", "no io");
+  for (const size_t sz : {(size_t)0, sizeof(qc_plant_io) - 8, sizeof(qc_plant_io) + 8}) {
+    qc_plant_io c = io;
+    c.struct_size = sz;
+    char text[160];
+    std::snprintf(text, sizeof(text), "qc_plant_step_batch: qc_plant_io.struct_size is %zu, this library's qc_plant_io has %zu B (qc_default_plant sets it)",
+                  sz, sizeof(qc_plant_io));
+    CHECK_FAILS(check_plant_args(h, 1, &c), text, "struct_size %zu", sz);
+    CHECK_FAILS(check_plant_args(h, 0, &c), text, "struct_size %zu, n = 0", sz);
+  }
+  const char* const state = "qc_plant_step_batch: the state arrays Rwb, x, xdot and w are required";
+  const char* const inputs = "qc_plant_step_batch: grf_body and foot_world are required";
+  {
+    double* qc_plant_io::*const st[] = {&qc_plant_io::Rwb, &qc_plant_io::x, &qc_plant_io::xdot, &qc_plant_io::w};
+    for (int i = 0; i < 4; i++) {
+      qc_plant_io c = io;
+      c.*st[i] = nullptr;
+      CHECK_FAILS(check_plant_args(h, 1, &c), state, "state array %d missing", i);
+      CHECK(check_plant_args(h, 0, &c) == QC_OK, "n = 0 reads no array (state array %d missing)", i);
+    }
+    const double* qc_plant_io::*const in[] = {&qc_plant_io::grf_body, &qc_plant_io::foot_world};
+    for (int i = 0; i < 2; i++) {
+      qc_plant_io c = io;
+      c.*in[i] = nullptr;
+      CHECK_FAILS(check_plant_args(h, 1, &c), inputs, "input array %d missing", i);
+    }
+  }
+  for (const double dt : {0.0, -0.0, -1.0 / 300.0, kInf, -kInf, kNan}) {
+    qc_plant_io c = io;
+    c.dt = dt;
+    CHECK_FAILS(check_plant_args(h, 1, &c), "qc_plant_step_batch: dt must be finite and > 0", "dt %g", dt);
+    CHECK_FAILS(check_plant_args(h, 0, &c), "qc_plant_step_batch: dt must be finite and > 0", "dt %g, n = 0", dt);
+  }
+  {
+    qc_plant_io c = io;
+    c.dt = 4.9e-324;
+    CHECK(check_plant_args(h, 1, &c) == QC_OK, "the smallest positive dt");
+  }
+  CHECK(check_plant_args(h, (size_t)0xFFFFFF * PLANT_BLOCK, &io) == QC_OK, "the largest launch");
+  CHECK_FAILS(check_plant_args(h, (size_t)0xFFFFFF * PLANT_BLOCK + 1, &io), "qc_plant_step_batch: n is beyond one launch", "one robot more");
+  CHECK(sizeof(qc_plant_io) == 9 * 8, "qc_plant_io is one size field, seven pointers and dt");
+}
+
+int main() {
+  inertia_inverse();
+  constants();
+  arguments();
+  std::printf("plant host logic ok: %ld checks\n", g_checked);
+  return 0;
+}
