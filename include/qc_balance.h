@@ -342,6 +342,48 @@ void qc_default_plant(qc_plant_io* io);
  * > 0, or a handle whose Ib is not finite, symmetric and positive definite (qc_create itself does not ask that of Ib). */
 int qc_plant_step_batch(qc_handle* h, size_t n, const qc_plant_io* io, void* stream);
 
+/* Closing the loop around the complete tick: one step of a LEGGED plant under the joint torques qc_control_batch (with joint_q /
+ * joint_tau) or qc_tick_batch wrote - a single rigid body on massless legs.  Per robot (mass, Ib and the kinematic constants
+ * from the handle, g = 9.81):
+ *   contact mask: `stance` bytes if given; else the phase rule of qc_batch_in.gait_phase (1e-12 slack, `gait_duty` or the
+ *     handle's value) on the phases AS THE TICK LEFT THEM (the plant never advances the clock); else all stance.  `cmd_state`,
+ *     if given, overrides all of it for a robot whose gait_running is 0: all stance.
+ *   stance leg i: p_i = FK(q_i), J_i = legJacobian(q_i); the force the torque encodes, g_i = J_i^-T tau_i (closed form while
+ *     max(eps, 64 eps (sum |l|)^3) <= |det J_i| <= 2^52, the pseudo-inverse of J_i^T and bit i of `flags` otherwise), is in
+ *     grf_body's convention, so f_i = -Rwb g_i acts on the body at r_i = Rwb p_i, and the foot is pinned at c_i = x + r_i.
+ *   swing leg: no force on the body; its joints are three double integrators with the reflected inertia leg_inertia:
+ *     qdot' = qdot + dt tau / I,  q' = q + dt qdot'.
+ *   body: exactly qc_plant_step_batch's step from sum f_i and sum r_i x f_i.
+ *   stance leg afterwards: p_i' = Rwb'^T (c_i - x'), q_i' = legInverseKinematics(p_i') (kinematics.cpp:117-160 with its d > 1
+ *     clamp), qdot_i' = wrapPI(q_i' - q_i) / dt; a clamped leg (foot out of reach) or a NaN leg (d < -1) sets bit 4 + i of
+ *     `flags`, and the NaN propagates as in the reference.
+ * There is no ground (a leg entering stance is pinned wherever its foot is), no leg mass, no gravity on the joints; the
+ * torque clamp of the tick is the plant's actuator limit.  INTEGRATION.md, "Closing the loop around the tick", has the limits.
+ * Every input of a robot is read before any output of that robot is written: Rwb, x, xdot, w, joint_q and joint_qdot are
+ * updated in place.  All pointers are DEVICE pointers. */
+typedef struct qc_leg_plant_io {
+  size_t struct_size;           /* = sizeof(qc_leg_plant_io); checked                                              */
+  double *Rwb, *x, *xdot, *w;   /* [n][9], [n][3], [n][3], [n][3] IN/OUT                                           */
+  double *joint_q, *joint_qdot; /* [n][4][3] IN/OUT                                                                */
+  const double* joint_tau;      /* [n][4][3] qc_batch_out.joint_tau                                                */
+  const uint8_t* stance;        /* [n][4] optional                                                                 */
+  const double* gait_phase;     /* [n][4] optional, as the tick left it                                            */
+  const double* gait_duty;      /* [n] optional (NULL: the handle's stance_phase)                                  */
+  const qc_commander_state* cmd_state; /* [n] optional: gait_running == 0 -> all stance                            */
+  double* foot_world;           /* [n][4][3] OUT, optional: x + Rwb FK(q) of the state the step read - the pinned
+                                   contact point c_i of a stance leg                                               */
+  int32_t* flags;               /* [n] OUT, optional: bit l singular Jacobian, bit 4 + l out of reach (stance leg l) */
+  double leg_inertia[3];        /* kg m^2 (hip, thigh, calf), finite and > 0: the reference has no number for it   */
+  double dt;                    /* seconds, finite, > 0                                                            */
+} qc_leg_plant_io;
+/* struct_size set, pointers NULL, dt = 1/300, leg_inertia = 0 (the caller must give one). */
+void qc_default_leg_plant(qc_leg_plant_io* io);
+/* Asynchronous on `stream`, no host synchronisation (graph-capturable); n == 0 launches nothing and returns QC_OK.
+ * QC_ERR_INVALID (message starting with "qc_leg_plant_step_batch:", nothing launched) for a null required pointer (the
+ * handle, io, Rwb, x, xdot, w, joint_q, joint_qdot, joint_tau), a wrong struct_size, a dt or a leg_inertia entry that is not
+ * finite and > 0, or a handle whose mass or Ib qc_plant_step_batch refuses. */
+int qc_leg_plant_step_batch(qc_handle* h, size_t n, const qc_leg_plant_io* io, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -436,6 +436,139 @@ class BalanceController:
             out["history"] = history
         return state, out
 
+    # ------------------------------------------- closing the loop around the tick
+    def _marshal_leg_plant(self, state, joint_tau, dt, leg_inertia, stance, gait_phase, gait_duty, cmd_state, foot_world, flags):
+        """Validate the arguments of leg_plant_step() and build its C struct.  Launches nothing."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        n = state["x"].shape[0]
+        io = _lib.QcLegPlantIo()
+        self._lib.qc_default_leg_plant(C.byref(io))
+        arrays = [(k, state.get(k), m, torch.float64, True) for k, m in (("Rwb", 9), ("x", 3), ("xdot", 3), ("w", 3), ("joint_q", 12), ("joint_qdot", 12))]
+        arrays += [("joint_tau", joint_tau, 12, torch.float64, True), ("stance", stance, 4, torch.uint8, False),
+                   ("gait_phase", gait_phase, 4, torch.float64, False), ("gait_duty", gait_duty, 1, torch.float64, False),
+                   ("cmd_state", cmd_state, COMMANDER_STATE_DTYPE.itemsize, torch.uint8, False),
+                   ("foot_world", foot_world, 12, torch.float64, False), ("flags", flags, 1, torch.int32, False)]
+        for name, t, k, dtype, required in arrays:
+            if t is None and not required:
+                continue
+            if t is None or t.dtype != dtype or not t.is_contiguous() or t.device != dev or t.numel() != n * k:
+                raise ValueError(f"{name}: need contiguous {dtype} [{n},{k}] on {dev}")
+            setattr(io, name, t.data_ptr() if n else None)
+        _fill(io.leg_inertia, np.broadcast_to(np.asarray(leg_inertia, dtype=np.float64), (3,)), 3, "leg_inertia")
+        io.dt = float(dt)
+        return n, io
+
+    def plan_leg_plant(self, state, joint_tau, dt, leg_inertia, stance=None, gait_phase=None, gait_duty=None, cmd_state=None,
+                       foot_world=None, flags=None, stream=None):
+        """leg_plant_step() marshalled once: returns `launch`, one qc_leg_plant_step_batch call on tensors that are updated in place."""
+        import torch
+
+        n, io = self._marshal_leg_plant(state, joint_tau, dt, leg_inertia, stance, gait_phase, gait_duty, cmd_state, foot_world, flags)
+        s = stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.device))
+        fn, h, sp, io_ref = self._lib.qc_leg_plant_step_batch, self._h, C.c_void_p(s.cuda_stream), C.byref(io)
+        keep = (state, joint_tau, stance, gait_phase, gait_duty, cmd_state, foot_world, flags, io)
+
+        def launch(_keep=keep):
+            rc = fn(h, n, io_ref, sp)
+            if rc != _lib.QC_OK:
+                raise RuntimeError(f"qc_leg_plant_step_batch failed ({rc}): {_lib.last_error()}")
+
+        return launch
+
+    def leg_plant_step(self, state, joint_tau, dt, leg_inertia, stance=None, gait_phase=None, gait_duty=None, cmd_state=None,
+                       foot_world=None, flags=None, stream=None):
+        """One step of the legged plant (qc_leg_plant_step_batch, include/qc_balance.h): a single rigid body on massless legs
+        under the tick's joint torques.  `state`: dict of device tensors Rwb [n,9], x, xdot, w [n,3], joint_q, joint_qdot [n,12],
+        updated IN PLACE; `joint_tau` [n,12] as control_batch(want_torques=True) / tick_batch() wrote it; `leg_inertia`: the
+        reflected joint inertia of a swing leg, kg m^2, a scalar or (hip, thigh, calf).  The contact mask comes from `stance`
+        (uint8 [n,4]), else from `gait_phase` [n,4] (as the tick left it; `gait_duty` [n] or the handle's value), else all
+        stance; `cmd_state` (the tick's commander records) makes a robot whose gait does not run yet all stance.  Optional
+        outputs: `foot_world` [n,12] (x + Rwb FK(q) of the state the step read: the pinned point of a stance leg) and `flags`
+        int32 [n] (bit l: singular Jacobian, bit 4 + l: foot out of reach).  Stance legs come out on the reference IK's knee
+        branch (q3 <= 0).  Asynchronous on `stream`.  Returns `state`."""
+        self.plan_leg_plant(state, joint_tau, dt, leg_inertia, stance, gait_phase, gait_duty, cmd_state, foot_world, flags, stream)()
+        return state
+
+    def rollout_tick(self, batch, command, steps, dt, leg_inertia, warm=True, record_every=None, stream=None):
+        """Closed loop around the complete tick, on the device: `steps` times the tick, then leg_plant_step() under its joint_tau, on
+        one stream and without a host round trip.  command = dict as for tick_batch(): commander mode (qc_tick_batch), `batch` as
+        tick_batch() takes it; command = None: control_batch() with a host-held desired state, `batch` as control_batch() takes it
+        with joint_q and joint_qdot.  A batch["gait_dt"] tensor is filled with `dt`; commander mode without one gets one of its own (the
+        caller's dict is not changed).  Rwb, x, xdot, w, joint_q and joint_qdot of `batch` are advanced IN PLACE; the plant reads the same `stance`
+        / gait_phase / gait_duty / commander state as the tick.  command["fresh"] is applied on step 0 only.  warm=True feeds each
+        solve's active_set back (ping-pong between two arrays, the first solve is cold), as rollout() does.
+        The plant reads gait_running AFTER the tick: on the one tick where the commander starts the gait, the tick used all stance
+        and the plant uses the unmoved phases - the two agree when the initial phases lie in stance (the reference's offsets
+        [0, .5, .5, 0] at duty 0.8 / 0.98 do).  Returns (state, out): the final state and the outputs of the LAST tick, plus
+        out["foot_world"] and out["flags"] of the last step; record_every=k adds out["history"] = [(step, rec)] for steps 0, k,
+        2k, ...: rec holds clones of the state BEFORE the step, rec["tick"] what the step's tick left (grf_body, status, joint_tau,
+        gait_phase, swing_state, cmd_state) and rec["step"] the plant's foot_world and flags - device tensors, no synchronisation."""
+        import torch
+
+        if batch.get("joint_q") is None or batch.get("joint_qdot") is None:
+            raise ValueError("rollout_tick: the batch carries joint_q and joint_qdot (rollout() steps the bare rigid body)")
+        steps = int(steps)
+        if steps < 0:
+            raise ValueError("rollout_tick: steps must be >= 0")
+        n = batch["x"].shape[0]
+        dev = torch.device("cuda", self.device)
+        names = ("Rwb", "x", "xdot", "w", "joint_q", "joint_qdot")
+        state = {k: batch[k] for k in names}
+        batch = dict(batch)  # (the caller's dict is left as it is: a gait_dt made here lives in this copy)
+        if command is not None or batch.get("gait_dt") is not None:
+            if batch.get("gait_dt") is None:
+                batch["gait_dt"] = torch.empty((n,), dtype=torch.float64, device=dev)
+            batch["gait_dt"].fill_(float(dt))
+        out = {"grf_body": torch.zeros((n, 12), dtype=torch.float64, device=dev),
+               "status": torch.full((n,), -1, dtype=torch.int32, device=dev),
+               "joint_tau": torch.zeros((n, 12), dtype=torch.float64, device=dev)}
+        sets = [torch.zeros((n,), dtype=torch.int32, device=dev) for _ in range(2)] if warm else []
+
+        # control_batch() takes joint_qdot only together with swing references (swing_state, or swing_pos and swing_vel): a
+        # batch without them - all stance - keeps its joint_qdot for the plant alone
+        swings = batch.get("swing_state") is not None or batch.get("swing_pos") is not None
+        tick_in = batch if (command is not None or swings) else {k: v for k, v in batch.items() if k != "joint_qdot"}
+
+        def plan(cmd, w, o):
+            if cmd is None:
+                return self.plan_batch(tick_in, w, o, want_active_set=warm, want_torques=True, stream=stream)[0]
+            return self.plan_tick(batch, cmd, w, o, want_active_set=warm, stream=stream)[0]
+
+        later = None if command is None else {k: v for k, v in command.items() if k != "fresh"}  # `fresh` holds on step 0 only
+        if warm:
+            ticks = [plan(command, None, dict(out, active_set=sets[0])), plan(later, sets[0], dict(out, active_set=sets[1])),
+                     plan(later, sets[1], dict(out, active_set=sets[0]))]
+        else:
+            ticks = [plan(command, None, out), plan(later, None, out)]
+        foot_world = torch.zeros((n, 12), dtype=torch.float64, device=dev)
+        flags = torch.zeros((n,), dtype=torch.int32, device=dev)
+        step = self.plan_leg_plant(state, out["joint_tau"], dt, leg_inertia, stance=batch.get("stance"), gait_phase=batch.get("gait_phase"),
+                                   gait_duty=batch.get("gait_duty"), cmd_state=None if command is None else command["state"],
+                                   foot_world=foot_world, flags=flags, stream=stream)
+        history = [] if record_every else None
+        for k in range(steps):
+            rec = None
+            if history is not None and k % int(record_every) == 0:
+                rec = {name: batch[name].clone() for name in names}
+                history.append((k, rec))
+            ticks[0 if k == 0 else ((1 + (k - 1) % 2) if warm else 1)]()
+            if rec is not None:  # what the tick of this step left behind: its outputs and the state it advances
+                rec["tick"] = {name: out[name].clone() for name in ("grf_body", "status", "joint_tau")}
+                rec["tick"].update({name: batch[name].clone() for name in ("gait_phase", "swing_state") if batch.get(name) is not None})
+                if command is not None:
+                    rec["tick"]["cmd_state"] = command["state"].clone()
+            step()
+            if rec is not None:
+                rec["step"] = {"foot_world": foot_world.clone(), "flags": flags.clone()}
+        if warm and steps > 0:
+            out["active_set"] = sets[steps % 2 == 0]
+        out["foot_world"], out["flags"] = foot_world, flags
+        if history is not None:
+            out["history"] = history
+        return state, out
+
     def control_batch_host(self, batch, warm=None, want_active_set=False, want_iterations=False, want_torques=False):
         """n robots, numpy (host) arrays in and out; PCIe-inclusive convenience path."""
         n = batch["x"].shape[0]

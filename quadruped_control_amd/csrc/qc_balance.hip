@@ -2176,6 +2176,29 @@ int qc_plant_step_batch(qc_handle* h, size_t n, const qc_plant_io* io, void* str
   return QC_OK;
 }
 
+void qc_default_leg_plant(qc_leg_plant_io* io) {
+  if (!io) return;
+  std::memset(io, 0, sizeof(*io));  // (leg_inertia 0: the reference has no number for it, the caller gives one)
+  io->struct_size = sizeof(qc_leg_plant_io);
+  io->dt = 1.0 / 300.0;  // mit_cheetah_config.yaml:3
+}
+
+int qc_leg_plant_step_batch(qc_handle* h, size_t n, const qc_leg_plant_io* io, void* stream) {
+  if (const int rc = qc::check_leg_plant_args(h, n, io); rc != QC_OK || n == 0) return rc;
+  qc::LegPlantArgs a;
+  if (const int rc = qc::leg_plant_constants(h->dp.mass, h->dp.Ib, io, a); rc != QC_OK) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  a.Rwb = io->Rwb; a.x = io->x; a.xdot = io->xdot; a.w = io->w;
+  a.joint_q = io->joint_q; a.joint_qdot = io->joint_qdot; a.joint_tau = io->joint_tau;
+  a.stance = io->stance; a.gait_phase = io->gait_phase; a.gait_duty = io->gait_duty;
+  a.cmd_state = reinterpret_cast<const qc::CmdState*>(io->cmd_state);
+  a.foot_world = io->foot_world; a.flags = io->flags;
+  const unsigned blocks = (unsigned)((n + qc::LEG_PLANT_BLOCK - 1) / qc::LEG_PLANT_BLOCK);
+  qc::leg_plant_step_kernel<<<dim3(blocks), dim3(qc::LEG_PLANT_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, a);
+  QC_HIP(hipGetLastError());
+  return QC_OK;
+}
+
 // host-pointer variant.  Large batches: one device staging allocation, H2D copies, kernel, D2H copies, sync.
 // Small batches (n <= kPinnedMaxN; the reference's own use is one robot per controller tick): the records are packed
 // into a pinned, device-visible host buffer that the kernel reads and writes in place over PCIe - one launch and one

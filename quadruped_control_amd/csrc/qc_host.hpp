@@ -10,6 +10,7 @@
 #include "../../include/qc_balance.h"
 #include "qc_device.hpp"
 #include "qc_plant.hpp"
+#include "qc_leg_plant.hpp"
 
 namespace qc {
 
@@ -484,6 +485,43 @@ inline int check_plant_args(const qc_handle* h, size_t n, const qc_plant_io* io)
   if (!io->grf_body || !io->foot_world) return fail(QC_ERR_INVALID, "qc_plant_step_batch: grf_body and foot_world are required");
   // one lane per robot in blocks of PLANT_BLOCK: a launch holds fewer than 2^32 threads
   if (n > (size_t)0xFFFFFF * PLANT_BLOCK) return fail(QC_ERR_INVALID, "qc_plant_step_batch: n is beyond one launch");
+  return QC_OK;
+}
+
+// ---------------------------------------------------------------- qc_leg_plant_step_batch
+// The argument check of the legged plant step: what is wrong with the call itself.  (The handle's mass and Ib are judged by
+// leg_plant_constants, through the plant's own checks, when the constants are derived.)
+inline int check_leg_plant_args(const qc_handle* h, size_t n, const qc_leg_plant_io* io) {
+  if (!h || !io) return fail(QC_ERR_INVALID, "qc_leg_plant_step_batch: null argument");
+  if (io->struct_size != sizeof(qc_leg_plant_io)) {
+    char msg[192];
+    std::snprintf(msg, sizeof(msg), "qc_leg_plant_step_batch: qc_leg_plant_io.struct_size is %zu, this library's qc_leg_plant_io has %zu B (qc_default_leg_plant sets it)",
+                  io->struct_size, sizeof(qc_leg_plant_io));
+    return fail(QC_ERR_INVALID, msg);
+  }
+  if (!std::isfinite(io->dt) || !(io->dt > 0.0)) return fail(QC_ERR_INVALID, "qc_leg_plant_step_batch: dt must be finite and > 0");
+  for (int k = 0; k < 3; k++)
+    if (!std::isfinite(io->leg_inertia[k]) || !(io->leg_inertia[k] > 0.0))
+      return fail(QC_ERR_INVALID, "qc_leg_plant_step_batch: leg_inertia (hip, thigh, calf) must be finite and > 0; qc_default_leg_plant leaves it at 0, the caller gives it");
+  if (n == 0) return QC_OK;
+  if (!io->Rwb || !io->x || !io->xdot || !io->w) return fail(QC_ERR_INVALID, "qc_leg_plant_step_batch: the state arrays Rwb, x, xdot and w are required");
+  if (!io->joint_q || !io->joint_qdot || !io->joint_tau) return fail(QC_ERR_INVALID, "qc_leg_plant_step_batch: joint_q, joint_qdot and joint_tau are required");
+  // one lane per robot in blocks of LEG_PLANT_BLOCK: a launch holds fewer than 2^32 threads
+  if (n > (size_t)0xFFFFFF * LEG_PLANT_BLOCK) return fail(QC_ERR_INVALID, "qc_leg_plant_step_batch: n is beyond one launch");
+  return QC_OK;
+}
+
+// the kernel's constants: the body's as plant_constants derives (and refuses) them, under this entry point's name
+inline int leg_plant_constants(double mass, const double* Ib, const qc_leg_plant_io* io, LegPlantArgs& a) {
+  PlantArgs b;
+  if (const int rc = plant_constants(mass, Ib, io->dt, b); rc != QC_OK) {
+    const std::string::size_type colon = g_err.find(':');  // "qc_plant_step_batch: the handle's ..."
+    return fail(rc, "qc_leg_plant_step_batch" + (colon == std::string::npos ? ": " + g_err : g_err.substr(colon)));
+  }
+  a.mass = b.mass; a.g = b.g; a.dt = b.dt;
+  std::memcpy(a.Ib, b.Ib, sizeof(a.Ib));
+  std::memcpy(a.Ib_inv, b.Ib_inv, sizeof(a.Ib_inv));
+  for (int k = 0; k < 3; k++) a.leg_inertia[k] = io->leg_inertia[k];
   return QC_OK;
 }
 

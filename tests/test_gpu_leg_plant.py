@@ -1,0 +1,589 @@
+"""GPU: qc_leg_plant_step_batch and BalanceController.rollout_tick against the CPU restatements (tests/leg_plant_restatement.py).
+
+Batch sizes 1, 63, 64, 65, 257 and 4097: below, at and above a wave, above a block (256) and a tail behind 16 full blocks.  Every
+reference is computed once per module on a pool of POOL robots that the batches tile.  Bars: leg_plant_restatement's module
+docstring - derived along the operation chain for Rwb, x, xdot, w, foot_world and the swing joints; for the stance legs' joint_q /
+joint_qdot the CPU numpy-vs-50-digit deviation over the pool times IK_BAR_MARGIN = 8.  Nothing here is set from a device output."""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+
+from tests import leg_plant_restatement as LR
+from tests import plant_restatement as PR
+
+pytestmark = pytest.mark.gpu
+EPS = LR.EPS
+SIZES = (1, 63, 64, 65, 257, 4097)
+STATE = LR.STATE
+POOL = 48
+SENTINEL = -7777.25
+DT = 1.0 / 300.0
+INERTIA = (0.02, 0.015, 0.01)
+MODES = ("stance", "phase", "duty", "cmd")
+
+
+@pytest.fixture(scope="module")
+def q(built):
+    import quadruped_control_amd as q
+
+    return q
+
+
+@pytest.fixture(scope="module")
+def P(q):
+    return q.cheetah_params()
+
+
+@pytest.fixture(scope="module")
+def ctl(q, P):
+    c = q.BalanceController.from_params(P, device=0)
+    yield c
+    c.close()
+
+
+@functools.lru_cache(maxsize=None)
+def _pool():
+    """LR.make_pool plus the contact inputs of the four modes: stance bytes (robot i carries mask i % 16: every mask from 0 to 15,
+    any non-zero byte counting as stance), per-robot duties in [0.3, 0.9], and commander records with gait_running = i % 2."""
+    from quadruped_control_amd import balance_controller as bc
+
+    s = LR.make_pool(POOL, 0x1E6)
+    rng = np.random.default_rng(8)
+    bits = (np.arange(POOL)[:, None] >> np.arange(4)[None, :]) & 1
+    s["stance"] = np.ascontiguousarray((bits * rng.integers(1, 256, (POOL, 4))).astype(np.uint8))
+    s["gait_duty"] = np.ascontiguousarray(rng.uniform(0.3, 0.9, POOL))
+    # the ends of the stance interval with the 1e-12 slack of the device's rule, on both sides of it: robots 0 - 2 carry the handle's
+    # duty as their own, so the same phases are edges in the "phase" and in the "duty" mode
+    duty = 0.8 / (0.18 + 0.8)
+    s["gait_duty"][:3] = duty
+    s["gait_phase"][0] = (0.0, -1e-13, -0.9e-12, -1.1e-12)
+    s["gait_phase"][1] = (duty, duty + 0.9e-12, duty + 1.1e-12, duty - 1.1e-12)
+    s["gait_phase"][2] = (-0.0, 1e-13, duty - 0.9e-12, duty + 2e-12)
+    cs = bc.new_commander_states(POOL)
+    cs["gait_running"] = np.arange(POOL) % 2
+    cs["standing"] = 1
+    s["cmd_state"] = np.ascontiguousarray(cs.view(np.uint8).reshape(POOL, -1))
+    return s
+
+
+def _mode_inputs(mode):
+    """(kwargs of leg_plant_step naming pool arrays, the mask [POOL, 4] the restatement's rule gives)"""
+    s = _pool()
+    if mode == "stance":
+        return ("stance",), LR.contact_mask(POOL, stance=s["stance"])
+    if mode == "phase":
+        return ("gait_phase",), LR.contact_mask(POOL, gait_phase=s["gait_phase"])
+    if mode == "duty":
+        return ("gait_phase", "gait_duty"), LR.contact_mask(POOL, gait_phase=s["gait_phase"], gait_duty=s["gait_duty"])
+    if mode == "cmd":
+        return ("gait_phase", "cmd_state"), LR.contact_mask(POOL, gait_phase=s["gait_phase"], gait_running=np.arange(POOL) % 2)
+    if mode == "all":
+        return (), np.ones((POOL, 4), bool)
+    raise ValueError(mode)
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(mode):
+    """{name: (values [POOL, k], bars [POOL, k])} plus "flags"; the stance legs' joint_q / joint_qdot bars are the measured ones"""
+    import quadruped_control_amd as q
+
+    P, s = q.cheetah_params(), _pool()
+    _, mask = _mode_inputs(mode)
+    refs = [LR.leg_plant_step_mp(P["mass"], P["Ib"], *(s[k][i] for k in STATE), s["joint_tau"][i], mask[i], INERTIA, DT) for i in range(POOL)]
+    out = {k: [np.stack([r[k][0] for r in refs]), np.stack([r[k][1] for r in refs])] for k in STATE + ("foot_world",)}
+    host = LR.leg_plant_step_np(P["mass"], P["Ib"], *(s[k] for k in STATE), s["joint_tau"], mask, INERTIA, DT)
+    assert (host["flags"] == 0).all()
+    if mask.any():
+        bars = LR.stance_ik_bars(host, {k: out[k][0] for k in ("joint_q", "joint_qdot")}, mask)
+        for k, b in bars.items():
+            out[k][1] = np.where(np.isnan(out[k][1]), b, out[k][1])
+    assert not any(np.isnan(v[1]).any() for v in out.values())
+    # the pool's margins, after the step as well (before: tests/test_leg_plant_cpu.py::test_pool_margins on the same generator)
+    knee = np.array([r["knee"] for r in refs])
+    assert np.nanmax(np.abs(knee), initial=0.0) <= 0.9
+    return out
+
+
+def _tile(a, n):
+    return np.ascontiguousarray(np.concatenate([a] * -(-n // a.shape[0]), 0)[:n])
+
+
+def _device_arrays(host, n, pad=2):
+    """{name: (whole tensor [n + pad, k], view of its first n rows)}: the rows behind row n - 1 hold a sentinel"""
+    import torch
+
+    out = {}
+    for k, a in host.items():
+        a2 = a.reshape(a.shape[0], -1)
+        sent = SENTINEL if a2.dtype == np.float64 else (0x5A if a2.dtype == np.uint8 else -77)
+        full = np.full((n + pad, a2.shape[1]), sent, dtype=a2.dtype)
+        full[:n] = _tile(a2, n)
+        t = torch.from_numpy(full).cuda()
+        out[k] = (t, t[:n] if a.ndim > 1 else t[:n].reshape(n))
+    return out
+
+
+def _step(ctl, host, n, names, outputs=True):
+    """One step over n robots (the pool tiled).  Returns {name: host array [n + 2, k]} of every array after the step."""
+    import torch
+
+    d = _device_arrays({k: host[k] for k in STATE + ("joint_tau",) + tuple(names)}, n)
+    if outputs:
+        d.update(_device_arrays(dict(foot_world=np.full((1, 12), SENTINEL), flags=np.full((1, 1), -77, np.int32)), n))
+    state = {k: d[k][1] for k in STATE}
+    kw = {k: d[k][1] for k in names}
+    if "gait_duty" in kw:
+        kw["gait_duty"] = kw["gait_duty"].reshape(n)
+    if outputs:
+        kw.update(foot_world=d["foot_world"][1], flags=d["flags"][1].reshape(n))
+    ctl.leg_plant_step(state, d["joint_tau"][1], DT, INERTIA, **kw)
+    torch.cuda.synchronize()
+    return {k: v[0].cpu().numpy() for k, v in d.items()}
+
+
+def _check(got, ref, n, what):
+    worst = {}
+    for k in STATE + ("foot_world",):
+        val, bar = _tile(ref[k][0], n), _tile(ref[k][1], n)
+        err = np.abs(got[k][:n] - val)
+        exact = bar == 0
+        assert np.array_equal(got[k][:n][exact], val[exact]), (what, k)
+        worst[k] = float(np.where(exact, 0.0, err / np.where(exact, 1.0, bar)).max())
+    print(f"{what}: worst error / bar {worst}")
+    assert max(worst.values()) <= 1.0, (what, worst)
+    assert (got["flags"][:n] == 0).all(), what
+    for k, a in got.items():
+        sent = SENTINEL if a.dtype == np.float64 else (0x5A if a.dtype == np.uint8 else -77)
+        assert (a[n:] == sent).all(), (what, k)
+
+
+# ------------------------------------------------------------------ 1. one step against the 50-digit restatement
+@pytest.mark.parametrize("mode", MODES + ("all",))
+def test_one_step_against_50_digits(ctl, mode):
+    """Every output within its bar of the 50-digit step at every batch size, for each way of giving the contact state: stance
+    bytes (every mask 0 ... 15 occurs), phases with the handle's duty, phases with per-robot duties, phases under commander
+    records with gait_running 0 and 1, and nothing (all stance).  No flag is set; the rows behind row n - 1 keep their sentinels."""
+    names, mask = _mode_inputs(mode)
+    if mode == "stance":
+        assert {int(v) for v in (mask * (1 << np.arange(4))).sum(1)} == set(range(16))
+    elif mode != "all":
+        assert mask.any() and not mask.all()
+    if mode in ("phase", "duty"):  # the edge phases of robots 0 - 2 fall on both sides of the slack
+        assert mask[:3].tolist() == [[True, True, True, False], [True, True, False, True], [True, True, True, False]]
+    ref = _reference(mode)
+    for n in SIZES:
+        _check(_step(ctl, _pool(), n, names), ref, n, f"{mode} n {n}")
+
+
+# ------------------------------------------------------------------ 2. optional outputs, inputs untouched
+@pytest.mark.parametrize("n", SIZES)
+def test_optional_outputs_and_inputs_untouched(ctl, n):
+    """foot_world and flags are optional: the state comes out bit for bit the same without them.  joint_tau and the contact inputs
+    are not written."""
+    s = _pool()
+    names = ("gait_phase", "gait_duty")
+    a, b = _step(ctl, s, n, names, True), _step(ctl, s, n, names, False)
+    for k in STATE:
+        assert np.array_equal(a[k], b[k]), k
+    for k in ("joint_tau",) + names:
+        assert np.array_equal(a[k][:n], _tile(s[k].reshape(POOL, -1), n)), k
+    assert (a["foot_world"][:n] != SENTINEL).all() and (a["joint_q"][:n] != _tile(s["joint_q"], n)).any()
+
+
+# ------------------------------------------------------------------ 3. tie to the existing kernels
+def test_agrees_with_the_rigid_body_plant_behind_control_batch(q, ctl, P):
+    """control_batch with joint_q / joint_tau on an all-stance pool whose torques stay inside +-20 N m; then the leg plant from
+    joint_tau and the old plant_step from grf_body with foot_world = the leg plant's c_i.  The body states agree within the bar of
+    the J^-T J^T round trip: each of the two 3x3 products loses at most cond(J) ulps of |g| (cond <= 40 on this pool, asserted),
+    dg = 16 cond EPS max |g| with the factor for the sums' own roundings (tests/test_leg_plant_cpu.py derives and meets the same),
+    propagated as tests/test_gpu_plant.py propagates a force difference: xdot: dt 4 dg / m, x: dt times that,
+    w: dt / min(Ib) 4 r_max sqrt(3) dg, Rwb: dt sqrt(3) dw - plus 64 EPS for the two kernels' own roundings of O(1) sums."""
+    import torch
+
+    n = 257
+    rng = np.random.default_rng(21)
+    from scipy.spatial.transform import Rotation
+
+    sc = 0.3  # (pose and velocity errors at which the wrench law's torques peak at 11 N m - the CPU tick says - well inside the clamp)
+    R = Rotation.from_rotvec(sc * rng.uniform(-0.05, 0.05, (n, 3))).as_matrix()
+    jq = np.tile(LR.STAND_Q, (n, 4)) + rng.uniform(-0.1, 0.1, (n, 12))
+    b = dict(Rwb=R.reshape(n, 9), Rwb_d=np.tile(np.eye(3).reshape(9), (n, 1)), x=np.array([0.0, 0.0, 0.30]) + sc * rng.uniform(-0.02, 0.02, (n, 3)),
+             xdot=sc * rng.uniform(-0.1, 0.1, (n, 3)), w=sc * rng.uniform(-0.2, 0.2, (n, 3)), x_d=np.tile([0.0, 0.0, 0.30], (n, 1)), xdot_d=np.zeros((n, 3)),
+             w_d=np.zeros((n, 3)), joint_q=jq)
+    b = {k: np.ascontiguousarray(v) for k, v in b.items()}
+    dev = q.to_device(b)
+    out = ctl.control_batch(dev, want_torques=True)
+    torch.cuda.synchronize()
+    tau, grf = out["joint_tau"].cpu().numpy(), out["grf_body"].cpu().numpy()
+    assert (out["status"].cpu().numpy() == 0).all() and np.abs(tau).max() < 20.0 and np.abs(grf).max() > 5.0
+    cond = max(np.linalg.cond(LR.jacobian(l, jq[i, 3 * l:3 * l + 3])) for i in range(n) for l in range(4))
+    assert cond <= 40.0
+    legs = {k: dev[k].clone() for k in ("Rwb", "x", "xdot", "w", "joint_q")}
+    legs["joint_qdot"] = torch.zeros((n, 12), dtype=torch.float64, device="cuda")
+    pw = torch.zeros((n, 12), dtype=torch.float64, device="cuda")
+    flags = torch.full((n,), -1, dtype=torch.int32, device="cuda")
+    ctl.leg_plant_step(legs, out["joint_tau"], DT, INERTIA, foot_world=pw, flags=flags)
+    body = {k: dev[k].clone() for k in ("Rwb", "x", "xdot", "w")}
+    ctl.plant_step(body, out["grf_body"], pw, DT)
+    torch.cuda.synchronize()
+    assert (flags.cpu().numpy() == 0).all()
+    dg = 16 * cond * EPS * np.abs(grf).max()
+    r_max = 0.5
+    d_v = DT * 4 * dg / P["mass"]
+    d_w = DT / np.min(np.diagonal(np.asarray(P["Ib"]).reshape(3, 3))) * 4 * r_max * np.sqrt(3.0) * dg
+    bars = dict(xdot=d_v + 64 * EPS, x=DT * d_v + 64 * EPS, w=d_w + 64 * EPS, Rwb=DT * np.sqrt(3.0) * d_w + 64 * EPS)
+    diff = {k: float((legs[k] - body[k]).abs().max()) for k in bars}
+    print(f"leg plant - rigid-body plant {diff}; bars {bars}")
+    for k in bars:
+        assert diff[k] <= bars[k], (k, diff[k], bars[k])
+
+
+# ------------------------------------------------------------------ 4. flags
+def test_flags_of_a_stretched_and_a_singular_leg(ctl, P):
+    """Robot 5: leg 1 almost straight (q3 = -0.01) under a body rising at 3 m/s - after the step the pinned foot is 1 cm out of
+    reach, the restatement's d > 1: bit 4 + 1 and no other.  Robot 9: leg 2 with q3 = 0 exactly - det J is rounding noise below
+    the band - under a body sinking at 1 m/s, so the foot stays in reach: bit 2 and no other.  Every other robot of the launch is
+    bit-identical to the launch without those two."""
+    s = {k: v.copy() for k, v in _pool().items()}
+    plain = _step(ctl, s, POOL, ())
+    Rid = np.eye(3).reshape(9)
+    for i, leg, q3, vz in ((5, 1, -0.01, 3.0), (9, 2, 0.0, -1.0)):
+        s["Rwb"][i], s["w"][i], s["xdot"][i] = Rid, 0.0, (0.0, 0.0, vz)
+        s["joint_q"][i, 3 * leg:3 * leg + 3] = (0.0, -q3 / 2, q3)
+        s["joint_tau"][i] = 0.0
+    mask = np.ones((POOL, 4), bool)
+    host = LR.leg_plant_step_np(P["mass"], P["Ib"], *(s[k] for k in STATE), s["joint_tau"], mask, INERTIA, DT)
+    assert host["flags"][5] == 16 << 1 and host["flags"][9] == 1 << 2 and (np.delete(host["flags"], [5, 9]) == 0).all()
+    assert LR.knee_cosine(1, host["Rwb"][5].reshape(3, 3).T @ (host["foot_world"][5, 3:6] - host["x"][5])) > 1.0 + 1e-6
+    assert abs(LR.det3(LR.jacobian(2, s["joint_q"][9, 6:9]))) < LR.DET_LO / 10
+    got = _step(ctl, s, POOL, ())
+    assert got["flags"][5, 0] == 16 << 1 and got["flags"][9, 0] == 1 << 2, (got["flags"][5], got["flags"][9])
+    others = np.setdiff1d(np.arange(POOL), [5, 9])
+    for k in STATE + ("foot_world", "flags"):
+        assert np.array_equal(got[k][others], plain[k][others]), k
+    # the stretched leg comes back clamped (q3 = -0 or 0), finite
+    assert np.isfinite(got["joint_q"][5]).all() and abs(got["joint_q"][5, 5]) == 0.0
+
+
+# ------------------------------------------------------------------ 5. argument errors
+def test_argument_errors_launch_nothing(q, ctl):
+    """Each rejected call returns QC_ERR_INVALID with a message of qc_leg_plant_step_batch's own and writes nothing."""
+    import torch
+
+    from quadruped_control_amd import _lib
+
+    lib, n = _lib.load(), 65
+    s = _pool()
+    d = _device_arrays({k: s[k] for k in STATE + ("joint_tau",)}, n)
+    d.update(_device_arrays(dict(foot_world=np.full((1, 12), SENTINEL), flags=np.full((1, 1), -77, np.int32)), n))
+    before = {k: v[0].clone() for k, v in d.items()}
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def io(**kw):
+        t = _lib.QcLegPlantIo()
+        lib.qc_default_leg_plant(ctypes.byref(t))
+        assert t.struct_size == ctypes.sizeof(_lib.QcLegPlantIo) and t.dt == 1.0 / 300.0 and list(t.leg_inertia) == [0.0] * 3 and not t.Rwb
+        for k in STATE + ("joint_tau", "foot_world", "flags"):
+            setattr(t, k, d[k][1].data_ptr())
+        t.leg_inertia[:] = INERTIA
+        for k, v in kw.items():
+            setattr(t, k, v)
+        return t
+
+    def refused(handle, t, what):
+        rc = lib.qc_leg_plant_step_batch(handle, n, ctypes.byref(t) if t is not None else None, stream)
+        assert rc == -1 and _lib.last_error().startswith("qc_leg_plant_step_batch:"), (what, rc, _lib.last_error())
+        torch.cuda.synchronize()
+        for k, v in d.items():
+            assert torch.equal(v[0], before[k]), (what, k)
+
+    for k in STATE + ("joint_tau",):
+        refused(ctl._h, io(**{k: None}), f"{k} = NULL")
+    refused(ctl._h, io(struct_size=72), "qc_plant_io's struct_size")
+    refused(ctl._h, io(struct_size=0), "struct_size not set")
+    for dt in (0.0, -1.0 / 300.0, float("nan"), float("inf")):
+        refused(ctl._h, io(dt=dt), f"dt = {dt}")
+    for k in range(3):
+        for v in (0.0, -0.02, float("nan"), float("inf")):
+            t = io()
+            t.leg_inertia[k] = v
+            refused(ctl._h, t, f"leg_inertia[{k}] = {v}")
+    refused(None, io(), "no handle")
+    refused(ctl._h, None, "no io")
+    P = dict(q.cheetah_params())
+    P["Ib"] = np.diag([0.011253, -0.036203, 0.042673])
+    odd = q.BalanceController.from_params(P, device=0)
+    refused(odd._h, io(), "Ib not positive definite")
+    assert "positive definite" in _lib.last_error()
+    odd.close()
+    assert lib.qc_leg_plant_step_batch(ctl._h, 0, ctypes.byref(io()), stream) == 0
+    with pytest.raises(ValueError, match="joint_tau"):
+        ctl.leg_plant_step({k: d[k][1] for k in STATE}, d["joint_tau"][1][:, :6].contiguous(), DT, INERTIA)
+    with pytest.raises(RuntimeError, match="qc_leg_plant_step_batch: leg_inertia"):
+        ctl.leg_plant_step({k: d[k][1] for k in STATE}, d["joint_tau"][1], DT, 0.0)
+    torch.cuda.synchronize()
+    for k, v in d.items():
+        assert torch.equal(v[0], before[k]), k
+    assert lib.qc_leg_plant_step_batch(ctl._h, n, ctypes.byref(io()), stream) == 0
+    torch.cuda.synchronize()
+    assert not torch.equal(d["x"][0][:n], before["x"][:n]) and (d["flags"][0][:n] == 0).all() and (d["x"][0][n:] == SENTINEL).all()
+
+
+# ------------------------------------------------------------------ 6. closed loop: standing
+STAND_INERTIA = 0.02
+
+
+def _stand_start(n):
+    rng = np.random.default_rng(0x57A9D)
+    from scipy.spatial.transform import Rotation
+
+    home = LR.fk(0, LR.STAND_Q)
+    R = Rotation.from_rotvec(rng.uniform(-0.05, 0.05, (n, 3))).as_matrix()  # a few degrees
+    x = np.array([0.0, 0.0, -home[2]]) + rng.uniform(-0.03, 0.03, (n, 3))  # a few cm
+    # the feet stand where the home pose puts them: joint angles by IK of the world points seen from the perturbed body
+    jq = np.zeros((n, 12))
+    for i in range(n):
+        for l in range(4):
+            foot = LR.fk(l, LR.STAND_Q) + np.array([0.0, 0.0, -home[2]])
+            jq[i, 3 * l:3 * l + 3], out = LR.ik(l, R[i].T @ (foot - x[i]))
+            assert not out
+    c = np.ascontiguousarray
+    return dict(Rwb=c(R.reshape(n, 9)), Rwb_d=c(np.tile(np.eye(3).reshape(9), (n, 1))), x=c(x), xdot=np.zeros((n, 3)), w=np.zeros((n, 3)),
+                x_d=c(np.tile([0.0, 0.0, -home[2]], (n, 1))), xdot_d=np.zeros((n, 3)), w_d=np.zeros((n, 3)), joint_q=c(jq), joint_qdot=np.zeros((n, 12)),
+                stance=np.ones((n, 4), np.uint8))
+
+
+def _cpu_stand_loop(P, b, steps, rows=None, ulp=False, seed=1):
+    """oracle/tick_restatement.py's tick (all stance: phases 0, the clock not advanced) then the numpy plant, `steps` times.
+    ulp: the inputs of EVERY iteration - the state the tick and the plant read - move by 1 ulp, each entry up or down, the
+    directions drawn afresh at every step (as plant_restatement.cpu_rollout perturbs its forces)."""
+    from oracle import tick_restatement as TR
+
+    rows = range(b["x"].shape[0]) if rows is None else rows
+    s = {k: np.array(b[k][list(rows)], np.float64) for k in STATE}
+    rng = np.random.default_rng(seed)
+    n = len(rows)
+    cmds = [TR.Commander(P, [0.0] * 4) for _ in range(n)]
+    status = np.zeros((steps, n), int)
+    flags = np.zeros(n, int)
+    mask = np.ones((n, 4), bool)
+    for t in range(steps):
+        if ulp:
+            s = {k: np.nextafter(v, np.where(rng.random(v.shape) < 0.5, -np.inf, np.inf)) for k, v in s.items()}
+        tau = np.zeros((n, 12))
+        for j, i in enumerate(rows):
+            tau[j], _, status[t, j], _ = cmds[j].tick(s["Rwb"][j], b["Rwb_d"][i], s["x"][j], s["xdot"][j], s["w"][j], b["x_d"][i], b["xdot_d"][i], b["w_d"][i],
+                                                     s["joint_q"][j], s["joint_qdot"][j])
+        o = LR.leg_plant_step_np(P["mass"], P["Ib"], *(s[k] for k in STATE), tau, mask, STAND_INERTIA, DT)
+        flags |= o["flags"]
+        s = {k: o[k] for k in STATE}
+    return s, status, flags
+
+
+def _pose_error(s, b, rows=None):
+    rows = slice(None) if rows is None else list(rows)
+    from scipy.spatial.transform import Rotation
+
+    ang = np.linalg.norm(Rotation.from_matrix(s["Rwb"].reshape(-1, 3, 3)).as_rotvec(), axis=1)
+    return np.linalg.norm((s["x"] - b["x_d"][rows])[:, :2], axis=1), ang  # (horizontal: see test_closed_loop_standing on the height)
+
+
+def test_closed_loop_standing(q, P):
+    """n = 65, 300 steps of the complete tick (control_batch with joint_q / joint_tau, all-stance stance bytes, a host-held
+    desired pose) and the leg plant, from poses perturbed by a few cm and a few degrees, against the same loop on the CPU
+    (oracle/tick_restatement.py's tick + the numpy plant), which is the reference.  Every status of every tick is QC_SOLVED, no
+    flag is set at any step, the pose error (largest and mean horizontal distance to the desired position, largest and mean angle to the
+    desired attitude) shrank as on the CPU - the HEIGHT does not: the wrench law's PD term carries the weight through a position
+    error, so every robot settles about 3 cm under the desired height, on the CPU as on the device, and the height is held to the
+    CPU loop by the final-state bar instead -, and the final state agrees with the CPU loop within 10 x the CPU loop's own
+    sensitivity to a 1-ulp move of its inputs.  leg_inertia = 0.02 kg m^2; the CPU loop settles with it (asserted).
+
+    The sensitivity run: the CPU loop again with the inputs of EVERY iteration - the state that the tick and the plant read -
+    moved by 1 ulp, each entry up or down, directions drawn afresh at every step (the way plant_restatement.cpu_rollout perturbs
+    its forces); on every fifth robot, the maximum over them serving all 65 (fewer robots can only make the bar smaller).  A loop's
+    inputs are read at every iteration, and another double evaluation rounds differently at every iteration, so that is where the
+    ulp enters; a move of the start alone dies out in this loop, which is a contraction, and leaves 1 ulp of x after 300 steps.
+    Measured on the CPU (max over robots and entries): Rwb 4.7e-15, x 1.1e-15, xdot 2.2e-15, w 7.3e-15, joint_q 2.0e-12,
+    joint_qdot 2.4e-12; the test uses what it measures."""
+    import torch
+
+    n, steps = 65, 300
+    b = _stand_start(n)
+    cpu, status, flags = _cpu_stand_loop(P, b, steps)
+    assert (status == 0).all() and (flags == 0).all()
+    e0 = _pose_error({k: b[k] for k in STATE}, b)
+    e1 = _pose_error(cpu, b)
+    shrank = lambda a, z: all(z[k].max() < a[k].max() and z[k].mean() < a[k].mean() for k in (0, 1))  # noqa: E731 (position, angle)
+    assert shrank(e0, e1), "the CPU loop itself does not settle"
+    rows = range(0, n, 5)
+    cpu_p, st_p, _ = _cpu_stand_loop(P, b, steps, rows, ulp=True)
+    assert (st_p == 0).all()
+    spread = {k: float(np.abs(cpu_p[k] - cpu[k][list(rows)]).max()) for k in STATE}
+    c = q.BalanceController.from_params(P, device=0)
+    dev = q.to_device(b)
+    state, out = c.rollout_tick(dev, None, steps, DT, STAND_INERTIA, record_every=1)
+    torch.cuda.synchronize()
+    assert len(out["history"]) == steps and "gait_dt" not in dev
+    assert all((rec["tick"]["status"] == 0).all().item() and (rec["step"]["flags"] == 0).all().item() for _, rec in out["history"])
+    got = {k: dev[k].cpu().numpy() for k in STATE}
+    diff = {k: float(np.abs(got[k] - cpu[k]).max()) for k in STATE}
+    print(f"CPU loop's spread under 1-ulp moves of every iteration's inputs {spread}\ndevice - CPU loop {diff}")
+    assert (out["status"].cpu().numpy() == 0).all() and (out["flags"].cpu().numpy() == 0).all() and state["x"] is dev["x"]
+    g1 = _pose_error(got, b)
+    assert shrank(e0, g1)
+    for k in diff:
+        assert diff[k] <= 10 * spread[k], (k, diff[k], spread[k])
+    c.close()
+
+
+def test_rollout_tick_without_warm_start_and_with_sparse_records(q, P):
+    """warm=False (every solve cold, one output set) walks to the same minimisers: 20 standing steps end within the project's
+    force parity bar propagated through the loop - 1e-6 max(1, |GRF|) ~ 1e-4 N per component, dt / m of it per step on xdot, 20
+    steps: 2e-7 - of the warm-started run, taken here as 1e-6 on every state entry.  record_every=5 records steps 0, 5, 10, 15,
+    the first record being the start; the caller's batch dict gains no key."""
+    import torch
+
+    n, steps = 65, 20
+    b = _stand_start(n)
+    c = q.BalanceController.from_params(P, device=0)
+    warm, cold = q.to_device(b), q.to_device(b)
+    keys = set(cold)
+    c.rollout_tick(warm, None, steps, DT, STAND_INERTIA)
+    _, out = c.rollout_tick(cold, None, steps, DT, STAND_INERTIA, warm=False, record_every=5)
+    torch.cuda.synchronize()
+    assert set(cold) == keys and "active_set" not in out and (out["status"] == 0).all().item()
+    assert [k for k, _ in out["history"]] == [0, 5, 10, 15]
+    for k in STATE:
+        assert np.array_equal(out["history"][0][1][k].cpu().numpy(), b[k]), k
+        assert float((warm[k] - cold[k]).abs().max()) <= 1e-6, k
+        assert not torch.equal(cold[k], out["history"][3][1][k]), k
+    c.close()
+
+
+# ------------------------------------------------------------------ 7. closed loop: commander mode
+def _commander_start(n):
+    """At the stand height (0.26 +- 2 mm: inside the commander's 5 mm band), level within 0.01 rad, within 1 mm of the origin, at
+    rest; the feet under the hips where the home pose puts them; the reference's phase offsets [0, .5, .5, 0] (all four in stance
+    at duty 0.8 / 0.98: the condition under which plant and tick agree on the tick that starts the gait)."""
+    from scipy.spatial.transform import Rotation
+
+    rng = np.random.default_rng(0xC0FFEE)
+    R = Rotation.from_rotvec(rng.uniform(-0.01, 0.01, (n, 3))).as_matrix()
+    x = np.array([0.0, 0.0, 0.26]) + rng.uniform(-1, 1, (n, 3)) * np.array([1e-3, 1e-3, 2e-3])
+    jq = np.zeros((n, 12))
+    for i in range(n):
+        for l in range(4):
+            foot = LR.fk(l, LR.STAND_Q)
+            foot[2] = 0.0
+            jq[i, 3 * l:3 * l + 3], out = LR.ik(l, R[i].T @ (foot - x[i]))
+            assert not out
+    c = np.ascontiguousarray
+    return dict(Rwb=c(R.reshape(n, 9)), x=c(x), xdot=np.zeros((n, 3)), w=np.zeros((n, 3)), joint_q=c(jq), joint_qdot=np.zeros((n, 12)),
+                gait_phase=c(np.tile([0.0, 0.5, 0.5, 0.0], (n, 1))))
+
+
+def _commander_rollout(q, ctl, n, steps, vx):
+    import torch
+
+    from quadruped_control_amd import balance_controller as bc
+
+    b = _commander_start(n)
+    dev = q.to_device(b)
+    dev["swing_state"] = torch.from_numpy(q.new_swing_states(n).view(np.uint8).copy()).cuda()
+    twist = np.zeros((n, 6))
+    twist[:, 0] = vx
+    command = dict(state=torch.from_numpy(bc.new_commander_states(n).view(np.uint8).copy()).cuda(), twist=torch.from_numpy(twist).cuda(),
+                   fresh=torch.ones((n,), dtype=torch.uint8, device="cuda"))
+    keys = set(dev)
+    state, out = ctl.rollout_tick(dev, command, steps, DT, STAND_INERTIA, record_every=1)
+    torch.cuda.synchronize()
+    assert set(dev) == keys  # (gait_dt was made inside)
+    hist = []
+    for _, rec in out["history"]:
+        h = {k: v.cpu().numpy() for k, v in rec.items() if k not in ("tick", "step")}
+        h["tick"] = {k: v.cpu().numpy() for k, v in rec["tick"].items()}
+        h["step"] = {k: v.cpu().numpy() for k, v in rec["step"].items()}
+        hist.append(h)
+    final = {k: dev[k].cpu().numpy() for k in STATE}
+    return b, twist, hist, final
+
+
+def _report(tag, b, hist, final):
+    flagged = sum(int((h["step"]["flags"] != 0).sum()) for h in hist)
+    solved = float(np.mean([(h["tick"]["status"] == 0).mean() for h in hist]))
+    ok = np.isfinite(final["x"]).all(axis=1)
+    drift = np.linalg.norm((final["x"] - b["x"])[ok, :2], axis=1)
+    z = final["x"][ok, 2]
+    print(f"REPORT {tag}: {int(ok.sum())} of {ok.size} robots finite; of those: final height {z.min(initial=np.inf):.4f} ... {z.max(initial=-np.inf):.4f} m, "
+          f"horizontal drift {drift.min(initial=np.inf):.4f} ... {drift.max(initial=-np.inf):.4f} m; flagged robot-steps {flagged}, solved fraction {solved:.4f}")
+
+
+def test_closed_loop_commander_mode(q):
+    """rollout_tick in commander mode, zero twist (a fresh zero command on step 0), from the stand height with the reference's
+    phase offsets, 300 steps on the device without a host in the loop, 5 robots (the smallest batch that still differs robot by
+    robot; the batch sizes are test 1's business, and every robot-step here gets a 50-digit plant step).  Afterwards every step
+    is re-synchronised from the recorded device state BEFORE it:
+      * the tick: tests/test_gpu_commander.py's reference tick (commander restatement + C oracle) on that state, compared by that
+        file's _compare_tick - flags and phases exactly, desired state 1e-12, swing plans 1e-9, forces 1e-6 relative, torques 2e-5;
+      * the plant: the 50-digit step on that state under the DEVICE's joint_tau and the restatement's contact mask, against the
+        recorded next state within the one-step bars of leg_plant_restatement (the stance-IK bars measured over this run's own
+        robot-steps on the CPU, numpy against 50 digits, times IK_BAR_MARGIN); foot_world too, and the flags are those of the numpy
+        step (none as long as the legs stay in reach, asserted);
+      * `standing` latches on tick 1, which also sets `gait_running` (qc_balance.h: "standing but not yet running: gait_running
+        is set and nothing else happens this tick"), and the gait runs - clock, phase rule, planner - from tick 2 on, for every
+        robot.  Tick 1 is therefore the tick of the documented limit: it used all stance, the plant reads the flag it left and
+        applies the phase rule to the unmoved phases;
+      * the contact mask the tick used (all stance until the gait runs, then the LegState words it left in the swing state) equals
+        the plant's (the rule on the phases and the gait_running flag the tick left) on every tick.
+    Reported only, no threshold (profiles/leg_plant_step.md holds the figures): final height and drift of this run and of a run
+    with a fresh 0.2 m/s forward command."""
+    from oracle import c_oracle as O
+    from tests import commander_restatement as CR
+    from tests import test_gpu_commander as TC
+
+    n, steps = 5, 300
+    P = q.cheetah_params()
+    ctl = q.BalanceController.from_params(P, device=0)
+    b, twist, hist, final = _commander_rollout(q, ctl, n, steps, 0.0)
+    _report("zero twist", b, hist, final)
+    cmd = CR.Commander(n)
+    ref_phase, ref_swing = b["gait_phase"].copy(), O.new_swing_states(n)
+    dt = np.full(n, DT)
+    checks = []
+    for k, h in enumerate(hist):
+        meas = {name: h[name] for name in STATE}
+        fresh = np.full(n, 1 if k == 0 else 0, np.uint8)
+        run, _, r = TC._reference_tick(O, P, meas, cmd, ref_phase, ref_swing, dt, twist, fresh)
+        state = h["tick"]["cmd_state"].view(q.COMMANDER_STATE_DTYPE).reshape(n)
+        swing = h["tick"]["swing_state"].view(q.SWING_STATE_DTYPE).reshape(n)
+        TC._compare_tick(q, O, P, ctl, k, n, dict(out=h["tick"], state=state, phase=h["tick"]["gait_phase"], swing=swing),
+                         dict(cmd=cmd, out=r, phase=ref_phase, swing=ref_swing), "rollout_tick")
+        assert (state["standing"] == 1).all() and (state["gait_running"] == 1).all() and (run == (k > 0)).all(), k
+        tick_mask = np.where(run[:, None], swing["leg_state"] == 1, True)
+        mask = LR.contact_mask(n, gait_phase=h["tick"]["gait_phase"], gait_running=state["gait_running"])
+        assert np.array_equal(tick_mask, mask), k
+        after = hist[k + 1] if k + 1 < steps else final
+        host = LR.leg_plant_step_np(P["mass"], P["Ib"], *(meas[name] for name in STATE), h["tick"]["joint_tau"], mask, STAND_INERTIA, DT)
+        refs = [LR.leg_plant_step_mp(P["mass"], P["Ib"], *(meas[name][i] for name in STATE), h["tick"]["joint_tau"][i], mask[i], STAND_INERTIA, DT)
+                for i in range(n)]
+        assert np.array_equal(h["step"]["flags"], host["flags"]) and (host["flags"] == 0).all(), k
+        checks.append((k, mask, host, refs, dict(after, foot_world=h["step"]["foot_world"])))
+    assert any((~m).any() for _, m, _, _, _ in checks), "no leg ever swung"
+    ik_bar = {name: 0.0 for name in ("joint_q", "joint_qdot")}
+    for _, mask, host, refs, _ in checks:
+        for name, v in LR.stance_ik_bars(host, {name: np.stack([r[name][0] for r in refs]) for name in ik_bar}, mask).items():
+            ik_bar[name] = max(ik_bar[name], v)
+    worst = {}
+    for k, mask, host, refs, got in checks:
+        for name in STATE + ("foot_world",):
+            val, bar = np.stack([r[name][0] for r in refs]), np.stack([r[name][1] for r in refs])
+            if name in ik_bar:
+                bar = np.where(np.isnan(bar), ik_bar[name], bar)
+            worst[name] = max(worst.get(name, 0.0), PR.worst_over_bar(got[name], (val, bar)))
+    print(f"plant step / one-step bar over {steps} re-synchronised steps: {worst}; stance-IK bars {ik_bar}")
+    assert max(worst.values()) <= 1.0, worst
+    b2, _, hist2, final2 = _commander_rollout(q, ctl, n, steps, 0.2)
+    _report("0.2 m/s forward", b2, hist2, final2)
+    ctl.close()
