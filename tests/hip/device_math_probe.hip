@@ -1,12 +1,16 @@
 // Device-math probe (test infrastructure, not the product): one primitive of quadruped_control_amd/csrc/qc_device.hpp per
 // thread over arrays, so tests/test_gpu_device_math.py can hold each hand-written primitive against a high-precision
-// reference.  The wrappers call the header's functions as they are; nothing here restates them.
+// reference.  The wrappers call the header's functions as they are; nothing here restates them.  The working-set recalculations
+// (EqpDiagW, EqpDense, EqpDense4: one robot per lane group, whole waves) and clamp_foot / the foot code are probed the same way for
+// tests/test_gpu_eqp.py.
 //
 // Every launcher takes device pointers (torch tensors), n and a stream and returns the hipError_t of its launch.  No
 // allocation and no copies: the constants the kinematic primitives read live in a __device__ DevParams that
-// qcp_set_params fills by a one-block kernel, and the kernels read it through QC_PARAMS_HERE as the product does.
+// qcp_set_params fills by a one-block kernel (qcp_set_qp_params: from the product's own derive_params), and the kernels read it
+// through QC_PARAMS_HERE as the product does.
 // Built by __graft_entry__.build_device_probe() with the product's own HIP_FLAGS (contraction and inlining as in the library).
 #include "../../quadruped_control_amd/csrc/qc_device.hpp"
+#include "../../quadruped_control_amd/csrc/qc_host.hpp"  // derive_params: the product's own derivation of the QP constants
 
 #include <cstring>
 
@@ -184,6 +188,118 @@ __global__ void k_group(const double* v, const double* addend, const int* bits, 
   }
 }
 
+// ---------------------------------------------------------------- working-set recalculations (EQPs)
+// One robot per lane group, whole waves with every lane active (the group reductions and the LDS exchange read their neighbours):
+// the launchers refuse an n that does not fill its blocks.  Inputs per robot: b[6], r[4][3], a 4-bit stance mask and the cube
+// (sx, sy, sz) of each foot.  A lane's robot and member come from lane_group / lane_member, foot0 = member (4 / G), as in the kernels.
+template <int FPL>
+__device__ __forceinline__ void load_robot(const double* b, const double* r, const int* cube, long robot, int foot0, double sign_b, Wrench<FPL>& Wr,
+                                           Cube<FPL>& C) {
+#pragma unroll
+  for (int k = 0; k < 6; k++) Wr.b[k] = sign_b * b[6 * robot + k];
+#pragma unroll
+  for (int i = 0; i < FPL; i++) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) Wr.r[i][k] = r[12 * robot + 3 * (foot0 + i) + k];
+    C.sx[i] = cube[12 * robot + 3 * (foot0 + i)];
+    C.sy[i] = cube[12 * robot + 3 * (foot0 + i) + 1];
+    C.sz[i] = cube[12 * robot + 3 * (foot0 + i) + 2];
+  }
+}
+// EqpDiagW<UNIFORM, G>: setup, then solve.  UC: the constants travel as a UConst (load_uconst + pin_uconst, mode 2's carrier).
+// Out: every member writes the f and g of its own feet into row `robot` and its gscale and ok into [robot][member].
+template <bool UNIFORM, int G, bool UC>
+__global__ void k_eqp_diagw(const double* b, const double* r, const int* stance, const int* cube, double* f, double* g, double* gscale, int* ok, int n) {
+  using Eqp = EqpDiagW<UNIFORM, G>;
+  constexpr bool S = Eqp::kStrided;
+  constexpr int FPL = 4 / G;
+  const int lane = (int)threadIdx.x;
+  const int member = lane_member<G, S>(lane);
+  const long robot = (long)blockIdx.x * (kBlock / G) + lane_group<G, S>(lane);  // < n: the launcher takes whole blocks only
+  const int foot0 = member * FPL;
+  Wrench<FPL> Wr;
+  Cube<FPL> C;
+  load_robot<FPL>(b, r, cube, robot, foot0, -1.0, Wr, C);  // -b: the 6x6 forms keep the NEGATED wrench target in Wr.b (Eqp::kNegB)
+  static_assert(Eqp::kNegB, "the 6x6 forms take -b");
+  const uint32_t st = (uint32_t)stance[robot] & 15u;
+  Eqp eqp(nullptr);
+  eqp.setup(params(), Wr, foot0);
+  double fo[3 * FPL], go[3 * FPL];
+  bool pd;
+  if constexpr (UC) {
+    UConst uc = load_uconst(params());
+    pin_uconst(uc);
+    pd = eqp.solve(uc, Wr, C, st, foot0, fo, go);
+  } else {
+    pd = eqp.solve(params(), Wr, C, st, foot0, fo, go);
+  }
+#pragma unroll
+  for (int k = 0; k < 3 * FPL; k++) { f[12 * robot + 3 * foot0 + k] = fo[k]; g[12 * robot + 3 * foot0 + k] = go[k]; }
+  gscale[4 * robot + member] = eqp.gscale;
+  ok[4 * robot + member] = pd ? 1 : 0;
+  (void)n;
+}
+// EqpDense: one robot per lane, its own 78 x 64 doubles of dynamic LDS per block
+__global__ void k_eqp_dense(const double* b, const double* r, const int* stance, const int* cube, double* f, double* g, int* ok, int n) {
+  extern __shared__ __attribute__((aligned(16))) double probe_lds[];
+  const int lane = (int)threadIdx.x;
+  const long robot = (long)blockIdx.x * kBlock + lane;
+  Wrench<4> Wr;
+  Cube<4> C;
+  load_robot<4>(b, r, cube, robot, 0, 1.0, Wr, C);
+  static_assert(!EqpDense::kNegB, "the dense forms take b");
+  const uint32_t st = (uint32_t)stance[robot] & 15u;
+  EqpDense eqp(probe_lds + lane);
+  eqp.setup(params(), Wr, 0);
+  double fo[12], go[12];
+  const bool pd = eqp.solve(params(), Wr, C, st, 0, fo, go);
+#pragma unroll
+  for (int k = 0; k < 12; k++) { f[12 * robot + k] = fo[k]; g[12 * robot + k] = go[k]; }
+  ok[robot] = pd ? 1 : 0;
+  (void)n;
+}
+// EqpDense4: X_DOUBLES of dynamic LDS per wave; setup once, then solve on cube and on cube2 for the same robot (the second
+// recalculation reads the tile the first one left).  f, g: [2][n][12], ok: [2][n][4].
+__global__ void k_eqp_dense4(const double* b, const double* r, const int* stance, const int* cube, const int* cube2, double* f, double* g, int* ok, int n) {
+  extern __shared__ __attribute__((aligned(16))) double probe_lds[];
+  const int lane = (int)threadIdx.x;
+  const int member = lane_member<4, true>(lane);
+  const long robot = (long)blockIdx.x * 16 + lane_group<4, true>(lane);
+  Wrench<1> Wr;
+  Cube<1> C, C2;
+  load_robot<1>(b, r, cube, robot, member, 1.0, Wr, C);
+  load_robot<1>(b, r, cube2, robot, member, 1.0, Wr, C2);
+  static_assert(!EqpDense4::kNegB, "the dense forms take b");
+  const uint32_t st = (uint32_t)stance[robot] & 15u;
+  EqpDense4 eqp(probe_lds + lane);
+  eqp.setup(params(), Wr, member);
+  double fo[3], go[3];
+  bool pd = eqp.solve(params(), Wr, C, st, member, fo, go);
+#pragma unroll
+  for (int k = 0; k < 3; k++) { f[12 * robot + 3 * member + k] = fo[k]; g[12 * robot + 3 * member + k] = go[k]; }
+  ok[4 * robot + member] = pd ? 1 : 0;
+  pd = eqp.solve(params(), Wr, C2, st, member, fo, go);
+  const long o = 12 * (long)n;
+#pragma unroll
+  for (int k = 0; k < 3; k++) { f[o + 12 * robot + 3 * member + k] = fo[k]; g[o + 12 * robot + 3 * member + k] = go[k]; }
+  ok[4 * (long)n + 4 * robot + member] = pd ? 1 : 0;
+}
+// clamp_foot and the foot code.  in[6 i ..] = mu lo hi fx fy fz, w[3 i ..] = the kept state (wx, wy, wz).
+// out[3 i ..] = the clamped point, state[7 i ..] = sx sy sz, moved, then dec2 of the three fields of encode_foot(sx, sy, sz).
+__global__ void k_clamp_foot(const double* in, const int* w, double* out, int* state, int n) {
+  const int i = tid();
+  if (i >= n) return;
+  const double* a = in + 6 * (long)i;
+  double fx = a[3], fy = a[4], fz = a[5];
+  int sx, sy, sz;
+  const bool moved = clamp_foot(a[0], a[1], a[2], w[3 * i], w[3 * i + 1], w[3 * i + 2], fx, fy, fz, sx, sy, sz);
+  out[3 * (long)i] = fx; out[3 * (long)i + 1] = fy; out[3 * (long)i + 2] = fz;
+  const uint32_t code = encode_foot(sx, sy, sz);
+  int* s = state + 7 * (long)i;
+  s[0] = sx; s[1] = sy; s[2] = sz; s[3] = moved ? 1 : 0;
+  s[4] = dec2(code); s[5] = dec2(code >> 2); s[6] = dec2(code >> 4);
+}
+
 template <class K, class... A>
 hipError_t launch(K kernel, int n, hipStream_t st, A... args) {
   if (n < 0) return hipErrorInvalidValue;
@@ -264,5 +380,53 @@ hipError_t qcp_group(int variant, const double* v, const double* addend, const i
     default: return hipErrorInvalidValue;
   }
 }
+
+// The QP's constants (mu, fzmin, fzmax, S, V, w, W, inv_wx, inv_wy, inv_bz, Vd, w_u, inv_w_u, inv_bz_u - and everything else
+// qc_create derives) by the product's own derive_params (qc_host.hpp), into the probe's constants.  Also reports what the host
+// rule makes of the parameters: flags[0] = W diagonal, [1] = uniform, [2] = small_w (the 6x6 forms are routed to the dense form),
+// [3] = the form the handle would run (QC_FORM_*).  A parameter set derive_params refuses returns hipErrorInvalidValue.
+hipError_t qcp_set_qp_params(const qc_params* p, int* flags, hipStream_t st) {
+  DevParams d;
+  Tuning t;
+  if (derive_params(p, d, t) != QC_OK) return hipErrorInvalidValue;
+  if (flags) { flags[0] = t.cfg_diag_w; flags[1] = t.cfg_uniform; flags[2] = t.small_w; flags[3] = form_of(t); }
+  hipLaunchKernelGGL(k_set_params, dim3(1), dim3(kBlock), 0, st, d);
+  return hipGetLastError();
+}
+// the host rule's threshold on max diag(S) / min diag(W) (qc_host.hpp)
+double qcp_dense_ratio(void) { return QC_DENSE_RATIO; }
+
+// variant: 0-2 uniform G = 1, 2, 4; 3-5 general G = 1, 2, 4; 6 uniform G = 4 with the constants in a UConst (mode 2).  n robots, a
+// multiple of the robots of a block (64 / G).
+hipError_t qcp_eqp_diagw(int variant, const double* b, const double* r, const int* stance, const int* cube, double* f, double* g, double* gscale,
+                         int* ok, int n, hipStream_t st) {
+  const int G = variant == 6 ? 4 : 1 << (variant % 3);
+  if (variant < 0 || variant > 6 || n <= 0 || n % (kBlock / G) != 0) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)(n / (kBlock / G)));
+#define QCP_DIAGW(U, GG, UC) hipLaunchKernelGGL((k_eqp_diagw<U, GG, UC>), grid, dim3(kBlock), 0, st, b, r, stance, cube, f, g, gscale, ok, n)
+  switch (variant) {
+    case 0: QCP_DIAGW(true, 1, false); break;
+    case 1: QCP_DIAGW(true, 2, false); break;
+    case 2: QCP_DIAGW(true, 4, false); break;
+    case 3: QCP_DIAGW(false, 1, false); break;
+    case 4: QCP_DIAGW(false, 2, false); break;
+    case 5: QCP_DIAGW(false, 4, false); break;
+    default: QCP_DIAGW(true, 4, true); break;
+  }
+#undef QCP_DIAGW
+  return hipGetLastError();
+}
+hipError_t qcp_eqp_dense(const double* b, const double* r, const int* stance, const int* cube, double* f, double* g, int* ok, int n, hipStream_t st) {
+  if (n <= 0 || n % kBlock != 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_eqp_dense, dim3((unsigned)(n / kBlock)), dim3(kBlock), sizeof(double) * EqpDense::kLdsDoubles, st, b, r, stance, cube, f, g, ok, n);
+  return hipGetLastError();
+}
+hipError_t qcp_eqp_dense4(const double* b, const double* r, const int* stance, const int* cube, const int* cube2, double* f, double* g, int* ok, int n,
+                          hipStream_t st) {
+  if (n <= 0 || n % 16 != 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_eqp_dense4, dim3((unsigned)(n / 16)), dim3(kBlock), sizeof(double) * EqpDense4::X_DOUBLES, st, b, r, stance, cube, cube2, f, g, ok, n);
+  return hipGetLastError();
+}
+hipError_t qcp_clamp_foot(const double* in, const int* w, double* out, int* state, int n, hipStream_t st) { return launch(k_clamp_foot, n, st, in, w, out, state); }
 
 }  // extern "C"
