@@ -384,6 +384,65 @@ void qc_default_leg_plant(qc_leg_plant_io* io);
  * finite and > 0, or a handle whose mass or Ib qc_plant_step_batch refuses. */
 int qc_leg_plant_step_batch(qc_handle* h, size_t n, const qc_leg_plant_io* io, void* stream);
 
+/* Certifying a batch: the solver-independent KKT certificate of the forces qc_control_batch returned, and their Lagrange
+ * multipliers, on the device.  Per robot, from the SAME qc_batch_in the solve read (r_i = Rwb p_i with p_i from `feet`, or from
+ * joint_q by the forward kinematics; b from the PD law) and the handle's mu, fzmin, fzmax and FULL S (6x6) and W (12x12),
+ * whatever formulation the solver ran:
+ *   f_i = -Rwb grf_body_i,   grad = 2 (A^T S (A f - b) + W f)                               (world frame)
+ *   contact mask: `stance` bytes if given; else the phase rule on gait_phase AS IT IS NOW (gait_duty or the handle's value);
+ *     else all stance.  gait_dt, swing_pos, swing_vel, joint_qdot and swing_state are ignored: the certificate never advances
+ *     a clock and never writes to `in`.
+ *   primal [N]: the largest of |fx| - mu fz, |fy| - mu fz, fzmin - fz, fz - fzmax over the stance feet (a swing foot counts 0).
+ *   active rows per stance foot and axis, a code 0 none, 1 lower row, 2 upper row, 3 both: x lower is fx = -mu fz, x upper
+ *     fx = +mu fz, a row being active when its slack is <= act_tol (1 + mu |fz|); y alike; z lower is fz = fzmin (slack <=
+ *     act_tol (1 + fzmin)), z upper fz = fzmax (slack <= act_tol (1 + fzmax)).
+ *   multipliers with one row active (s = -1 lower, +1 upper): lam_x = -s_x g_x, lam_y = -s_y g_y,
+ *     lam_z = s_z (mu (lam_x + lam_y) - g_z); an axis without a row has lam = 0 and contributes |g| to the residual
+ *     (z: |mu (lam_x + lam_y) - g_z|), an axis with one row max(0, -lam).
+ *   BOTH rows of an axis active (the apex of the pyramid at fz = 0 = fzmin, or fzmin = fzmax): x, y: lam = |g|, carried by the
+ *     row on the side -sign(g) - the pair of least sum, the choice that can satisfy the z row - and the axis contributes 0;
+ *     z: the equality leaves lam_z free, the axis contributes 0 and lam_z reports the net value mu (lam_x + lam_y) - g_z
+ *     (upper minus lower).
+ *   stationarity: the largest contribution over the stance feet / (1 + |grad|_2).
+ * Non-finite inputs propagate as NaN; nothing is clamped.  Commander mode (qc_tick_batch) is out of scope: its desired state
+ * lives in qc_commander_state, not in qc_batch_in. */
+typedef struct qc_certify_summary {
+  int64_t n_fail;            /* robots with !(primal <= primal_tol) || !(stationarity <= stat_tol) or the swing flag (a NaN fails) */
+  int64_t n_nonfinite;       /* robots whose primal or stationarity residual is not finite                                     */
+  int64_t n_swing_nonzero;   /* robots with a non-zero force on a swing foot                                                   */
+  double worst_primal;       /* the largest FINITE primal residual (NaN if none is finite)                                     */
+  double worst_stationarity; /* the largest FINITE stationarity residual (NaN if none is finite)                               */
+  int64_t arg_primal;        /* its robot, the lowest index on a tie; -1 if none is finite                                     */
+  int64_t arg_stationarity;
+} qc_certify_summary;
+
+/* Per-call arguments of qc_certify_batch (DEVICE pointers).  Every output is optional; at least one must be given. */
+typedef struct qc_certify_io {
+  size_t struct_size;        /* = sizeof(qc_certify_io); checked                                                     */
+  const double* grf_body;    /* [n][4][3] qc_batch_out.grf_body                                                      */
+  double act_tol;            /* active-row tolerance, finite and >= 0                                                */
+  double primal_tol;         /* bars of qc_certify_summary.n_fail, finite and >= 0                                   */
+  double stat_tol;
+  double* primal;            /* [n]                                                                                  */
+  double* stationarity;      /* [n]                                                                                  */
+  double* lambda;            /* [n][4][3] (x, y, z) multipliers as defined above: raw values, negative where the point
+                                is not optimal; 0 on an axis without an active row and for swing feet               */
+  double* grad;              /* [n][12] world frame                                                                  */
+  uint8_t* active;           /* [n][4]: x code | y code << 2 | z code << 4; 0x80 for a swing foot                    */
+  int32_t* flags;            /* [n]: bit 0 a swing foot carries force, bit 1 a residual is not finite                */
+  qc_certify_summary* summary; /* one struct, written by a second, one-workgroup kernel                              */
+} qc_certify_io;
+/* struct_size set, pointers NULL, act_tol = 1e-7, primal_tol = 1e-7, stat_tol = 1e-8. */
+void qc_default_certify(qc_certify_io* io);
+/* Asynchronous on `stream`, no host synchronisation (graph-capturable); n == 0 launches nothing and returns QC_OK.  The
+ * summary goes through a partial buffer the handle owns, reduced without atomics: it is deterministic and bit-equal to
+ * reducing the per-robot arrays, works with all of them NULL, and two calls with a summary on one handle must be ordered on
+ * the device (one stream, or an event between them).  QC_ERR_INVALID (message starting with "qc_certify_batch:", nothing
+ * launched) for a null handle, `in` or `io`, a wrong struct_size, a tolerance that is not finite and >= 0, no output
+ * requested at all, a missing grf_body, a missing state array (Rwb, Rwb_d, x, xdot, w, x_d, xdot_d, w_d), neither feet nor
+ * joint_q, or n beyond one launch. */
+int qc_certify_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_certify_io* io, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,17 @@ class QcLegPlantIo(C.Structure):
                  "foot_world", "flags")] + [("leg_inertia", C.c_double * 3), ("dt", C.c_double)]
 
 
+class QcCertifySummary(C.Structure):
+    _fields_ = [("n_fail", C.c_int64), ("n_nonfinite", C.c_int64), ("n_swing_nonzero", C.c_int64), ("worst_primal", C.c_double),
+                ("worst_stationarity", C.c_double), ("arg_primal", C.c_int64), ("arg_stationarity", C.c_int64)]
+
+
+class QcCertifyIo(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("grf_body", C.c_void_p), ("act_tol", C.c_double), ("primal_tol", C.c_double),
+                ("stat_tol", C.c_double)] + [(k, C.c_void_p) for k in
+                ("primal", "stationarity", "lambda", "grad", "active", "flags", "summary")]
+
+
 class QcLaunchInfo(C.Structure):
     _fields_ = [("lanes_per_robot", C.c_int32), ("mode", C.c_int32), ("form", C.c_int32), ("strategies", C.c_int32),
                 ("chunk", C.c_int64), ("blocks", C.c_int64), ("resident_workgroups", C.c_int64), ("lds_bytes", C.c_int64)]
@@ -75,7 +86,8 @@ class QcLaunchInfo(C.Structure):
 EXPORTS = ("qc_create_abi", "qc_destroy", "qc_control_batch", "qc_control_batch_host", "qc_control",
            "qc_last_error", "qc_kernel_name", "qc_abi_version", "qc_default_kinematics", "qc_set_kinematics", "qc_set_gait", "qc_swing_state_init",
            "qc_set_tuning", "qc_query_launch", "qc_check_abi", "qc_default_command", "qc_commander_state_init", "qc_tick_batch",
-           "qc_default_plant", "qc_plant_step_batch", "qc_default_leg_plant", "qc_leg_plant_step_batch")
+           "qc_default_plant", "qc_plant_step_batch", "qc_default_leg_plant", "qc_leg_plant_step_batch",
+           "qc_default_certify", "qc_certify_batch")
 
 _lib = None
 
@@ -150,6 +162,10 @@ def load():
     lib.qc_default_leg_plant.restype = None
     lib.qc_leg_plant_step_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcLegPlantIo), C.c_void_p]
     lib.qc_leg_plant_step_batch.restype = C.c_int
+    lib.qc_default_certify.argtypes = [C.POINTER(QcCertifyIo)]
+    lib.qc_default_certify.restype = None
+    lib.qc_certify_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcBatchIn), C.POINTER(QcCertifyIo), C.c_void_p]
+    lib.qc_certify_batch.restype = C.c_int
     # the structures above are hand-written mirrors of the header: a library built from another revision is refused here,
     # before any of them crosses the boundary
     rc = lib.qc_check_abi(ABI_VERSION, C.sizeof(QcParams), C.sizeof(QcBatchIn), C.sizeof(QcBatchOut))

@@ -392,7 +392,7 @@ class BalanceController:
         self.plan_plant(state, grf_body, foot_world, dt, feet, stream)()
         return state
 
-    def rollout(self, batch, foot_world, steps, dt, warm=True, record_every=None, stream=None):
+    def rollout(self, batch, foot_world, steps, dt, warm=True, record_every=None, stream=None, certify_every=None):
         """Closed loop on the device: `steps` times control_batch() then plant_step(), on one stream and without a host round
         trip.  `batch`: device tensors as for control_batch() with `feet` (not joint_q); its Rwb, x, xdot, w and feet are
         advanced IN PLACE, the desired state and `stance` are held.  `foot_world` [n,12]: world positions of the feet, held.
@@ -400,7 +400,9 @@ class BalanceController:
         marshalled once (plan_batch); the loop itself is two C calls per step.  Returns (state, out): the final state (the
         tensors of `batch`) and the outputs of the LAST solve, i.e. the forces that produced the last step.  No history is
         kept unless record_every=k: then `out["history"]` is a list of (step, {Rwb, x, xdot, w, feet} clones) of the state BEFORE
-        steps 0, k, 2k, ... - device tensors, no synchronisation."""
+        steps 0, k, 2k, ... - device tensors, no synchronisation.  certify_every=k launches the KKT certificate (certify_batch's
+        summary, default tolerances) after the solve of steps 0, k, 2k, ... and returns `out["certificates"]`, a list of (step,
+        summary clone); None (the default) launches exactly what it always did."""
         import torch
 
         if batch.get("joint_q") is not None or batch.get("feet") is None:
@@ -425,16 +427,31 @@ class BalanceController:
             solves = [self.plan_batch(batch, None, out, stream=stream)[0]]
         step = self.plan_plant(state, out["grf_body"], foot_world, dt, batch["feet"], stream)
         history = [] if record_every else None
+        certify, cert, certificates = self._plan_rollout_certify("rollout", batch, out["grf_body"], certify_every, stream)
         for k in range(steps):
             if history is not None and k % int(record_every) == 0:
                 history.append((k, {name: batch[name].clone() for name in ("Rwb", "x", "xdot", "w", "feet")}))
             solves[0 if (k == 0 or not warm) else 1 + (k - 1) % 2]()
+            if certify is not None and k % int(certify_every) == 0:
+                certify()
+                certificates.append((k, cert["summary"].clone()))
             step()
         if warm and steps > 0:
             out["active_set"] = sets[steps % 2 == 0]  # step 0 wrote sets[0], step 1 sets[1], step 2 sets[0], ...
         if history is not None:
             out["history"] = history
+        if certificates is not None:
+            out["certificates"] = certificates
         return state, out
+
+    def _plan_rollout_certify(self, who, batch, grf_body, certify_every, stream):
+        """(launch, outputs, list) of the certificate a rollout launches every `certify_every` steps, or (None, None, None)."""
+        if certify_every is None:
+            return None, None, None
+        if int(certify_every) < 1:
+            raise ValueError(f"{who}: certify_every must be >= 1")
+        launch, cert = self.plan_certify(batch, grf_body, want=(), summary=True, stream=stream)
+        return launch, cert, []
 
     # ------------------------------------------- closing the loop around the tick
     def _marshal_leg_plant(self, state, joint_tau, dt, leg_inertia, stance, gait_phase, gait_duty, cmd_state, foot_world, flags):
@@ -491,7 +508,7 @@ class BalanceController:
         self.plan_leg_plant(state, joint_tau, dt, leg_inertia, stance, gait_phase, gait_duty, cmd_state, foot_world, flags, stream)()
         return state
 
-    def rollout_tick(self, batch, command, steps, dt, leg_inertia, warm=True, record_every=None, stream=None):
+    def rollout_tick(self, batch, command, steps, dt, leg_inertia, warm=True, record_every=None, stream=None, certify_every=None):
         """Closed loop around the complete tick, on the device: `steps` times the tick, then leg_plant_step() under its joint_tau, on
         one stream and without a host round trip.  command = dict as for tick_batch(): commander mode (qc_tick_batch), `batch` as
         tick_batch() takes it; command = None: control_batch() with a host-held desired state, `batch` as control_batch() takes it
@@ -504,11 +521,17 @@ class BalanceController:
         [0, .5, .5, 0] at duty 0.8 / 0.98 do).  Returns (state, out): the final state and the outputs of the LAST tick, plus
         out["foot_world"] and out["flags"] of the last step; record_every=k adds out["history"] = [(step, rec)] for steps 0, k,
         2k, ...: rec holds clones of the state BEFORE the step, rec["tick"] what the step's tick left (grf_body, status, joint_tau,
-        gait_phase, swing_state, cmd_state) and rec["step"] the plant's foot_world and flags - device tensors, no synchronisation."""
+        gait_phase, swing_state, cmd_state) and rec["step"] the plant's foot_world and flags - device tensors, no synchronisation.
+        certify_every=k (command = None only: the certificate reads the desired state from the batch, commander mode keeps it in the
+        commander state) launches the KKT certificate after the tick of steps 0, k, 2k, ..., on the state and the phases as the tick
+        left them, and returns out["certificates"] = [(step, summary clone)]; None (the default) launches exactly what it always did."""
         import torch
 
         if batch.get("joint_q") is None or batch.get("joint_qdot") is None:
             raise ValueError("rollout_tick: the batch carries joint_q and joint_qdot (rollout() steps the bare rigid body)")
+        if certify_every is not None and command is not None:
+            raise ValueError("rollout_tick: certify_every needs command=None - the certificate is out of scope in commander mode "
+                             "(its desired state lives in the commander state, not in the batch)")
         steps = int(steps)
         if steps < 0:
             raise ValueError("rollout_tick: steps must be >= 0")
@@ -548,6 +571,7 @@ class BalanceController:
                                    gait_duty=batch.get("gait_duty"), cmd_state=None if command is None else command["state"],
                                    foot_world=foot_world, flags=flags, stream=stream)
         history = [] if record_every else None
+        certify, cert, certificates = self._plan_rollout_certify("rollout_tick", batch, out["grf_body"], certify_every, stream)
         for k in range(steps):
             rec = None
             if history is not None and k % int(record_every) == 0:
@@ -559,6 +583,9 @@ class BalanceController:
                 rec["tick"].update({name: batch[name].clone() for name in ("gait_phase", "swing_state") if batch.get(name) is not None})
                 if command is not None:
                     rec["tick"]["cmd_state"] = command["state"].clone()
+            if certify is not None and k % int(certify_every) == 0:
+                certify()
+                certificates.append((k, cert["summary"].clone()))
             step()
             if rec is not None:
                 rec["step"] = {"foot_world": foot_world.clone(), "flags": flags.clone()}
@@ -567,7 +594,78 @@ class BalanceController:
         out["foot_world"], out["flags"] = foot_world, flags
         if history is not None:
             out["history"] = history
+        if certificates is not None:
+            out["certificates"] = certificates
         return state, out
+
+    # ------------------------------------------------------ certifying a batch
+    def plan_certify(self, batch, grf_body, act_tol=1e-7, primal_tol=1e-7, stat_tol=1e-8, want=("primal", "stationarity"), summary=True,
+                     out=None, stream=None):
+        """certify_batch() marshalled once: returns (launch, out), `launch()` being one qc_certify_batch call (graph-capturable) on
+        tensors that are read in place.  Planning launches nothing.  `out`: a dict of tensors to write into instead of new ones
+        (every name in `want`, and "summary" if summary=True)."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        sized = [t for t in [batch.get(k) for k, _ in _IN_FIELDS] + [grf_body] if t is not None]
+        if not sized:
+            raise ValueError("certify: the batch holds no state array")
+        n = sized[0].shape[0]  # (a missing array is the library's refusal, not a KeyError here)
+        bi = _lib.QcBatchIn()
+        for name, k, dtype in [(f, m, torch.float64) for f, m in _IN_FIELDS] + [("joint_q", 12, torch.float64), ("stance", 4, torch.uint8),
+                                                                               ("gait_phase", 4, torch.float64), ("gait_duty", 1, torch.float64)]:
+            t = batch.get(name)
+            if t is None:
+                continue  # (what is required is the library's decision: qc_certify_batch names what is missing)
+            if t.dtype != dtype or not t.is_contiguous() or t.device != dev or t.numel() != n * k:
+                raise ValueError(f"{name}: need contiguous {dtype} [{n},{k}] on {dev}")
+            setattr(bi, name, t.data_ptr())
+        io = _lib.QcCertifyIo()
+        self._lib.qc_default_certify(C.byref(io))
+        if grf_body is not None:
+            if grf_body.dtype != torch.float64 or not grf_body.is_contiguous() or grf_body.device != dev or grf_body.numel() != n * 12:
+                raise ValueError(f"grf_body: need contiguous float64 [{n},12] on {dev}")
+            io.grf_body = grf_body.data_ptr()
+        io.act_tol, io.primal_tol, io.stat_tol = float(act_tol), float(primal_tol), float(stat_tol)
+        unknown = [w for w in want if w not in _CERTIFY_OUTPUTS]
+        if unknown:
+            raise ValueError(f"certify: unknown output(s) {unknown}; want is a subset of {tuple(_CERTIFY_OUTPUTS)}")
+        names = list(want) + (["summary"] if summary else [])
+        res = {}
+        for name in names:
+            shape, dtype = (None, torch.uint8) if name == "summary" else (_CERTIFY_OUTPUTS[name][0], getattr(torch, _CERTIFY_OUTPUTS[name][1]))
+            size = (CERTIFY_SUMMARY_DTYPE.itemsize,) if name == "summary" else (n,) + shape
+            t = None if out is None else out.get(name)
+            if t is None:
+                if out is not None:
+                    raise ValueError(f"out: '{name}' was asked for but the supplied `out` has no such tensor")
+                t = torch.zeros(size, dtype=dtype, device=dev)
+            elif t.dtype != dtype or not t.is_contiguous() or t.device != dev or t.numel() != int(np.prod(size)):
+                raise ValueError(f"out['{name}']: need contiguous {dtype} with {int(np.prod(size))} elements on {dev}")
+            res[name] = t
+            setattr(io, name, t.data_ptr())
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        fn, h, sp, bi_ref, io_ref = self._lib.qc_certify_batch, self._h, C.c_void_p(s.cuda_stream), C.byref(bi), C.byref(io)
+        keep = (batch, grf_body, res, bi, io)
+
+        def launch(_keep=keep):
+            rc = fn(h, n, bi_ref, io_ref, sp)
+            if rc != _lib.QC_OK:
+                raise RuntimeError(f"qc_certify_batch failed ({rc}): {_lib.last_error()}")
+
+        return launch, res
+
+    def certify_batch(self, batch, grf_body, act_tol=1e-7, primal_tol=1e-7, stat_tol=1e-8, want=("primal", "stationarity"), summary=True,
+                      out=None, stream=None):
+        """The solver-independent KKT certificate of `grf_body` [n,12] (as control_batch() wrote it) for the batch the solve read,
+        on the device (qc_certify_batch, include/qc_balance.h; INTEGRATION.md "Certifying a batch").  `want`: any of "primal" [n],
+        "stationarity" [n], "lambda" [n,4,3], "grad" [n,12], "active" uint8 [n,4], "flags" int32 [n]; summary=True adds "summary",
+        a uint8 tensor holding one qc_certify_summary record (certify_summary() reads it on the host).  The contact mask is
+        batch["stance"], else the phase rule on batch["gait_phase"] as it is now, else all stance; gait_dt and the swing arrays are
+        ignored, nothing of `batch` is written.  Asynchronous on `stream`, no synchronisation.  Returns the dict of device tensors."""
+        launch, res = self.plan_certify(batch, grf_body, act_tol, primal_tol, stat_tol, want, summary, out, stream)
+        launch()
+        return res
 
     def control_batch_host(self, batch, warm=None, want_active_set=False, want_iterations=False, want_torques=False):
         """n robots, numpy (host) arrays in and out; PCIe-inclusive convenience path."""
@@ -647,6 +745,21 @@ def new_commander_states(n, x_stand=(0.0, 0.0, 0.26)):
     xs = np.ascontiguousarray(np.asarray(x_stand, dtype=np.float64).reshape(3))
     _lib.load().qc_commander_state_init(s.ctypes.data_as(C.c_void_p), n, xs.ctypes.data_as(C.c_void_p))
     return s
+
+
+CERTIFY_SUMMARY_DTYPE = np.dtype([("n_fail", np.int64), ("n_nonfinite", np.int64), ("n_swing_nonzero", np.int64), ("worst_primal", np.float64),
+                                  ("worst_stationarity", np.float64), ("arg_primal", np.int64), ("arg_stationarity", np.int64)])  # == qc_certify_summary
+
+
+# the per-robot outputs of the certificate: name -> (trailing shape, torch dtype name)
+_CERTIFY_OUTPUTS = {"primal": ((), "float64"), "stationarity": ((), "float64"), "lambda": ((4, 3), "float64"), "grad": ((12,), "float64"),
+                    "active": ((4,), "uint8"), "flags": ((), "int32")}
+
+
+def certify_summary(t):
+    """The qc_certify_summary record of certify_batch()["summary"] as a dict of Python numbers (copies to the host: synchronises)."""
+    rec = t.cpu().numpy().view(CERTIFY_SUMMARY_DTYPE)[0]
+    return {k: rec[k].item() for k in CERTIFY_SUMMARY_DTYPE.names}
 
 
 def to_device(batch, device=0):

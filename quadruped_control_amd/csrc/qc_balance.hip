@@ -1883,6 +1883,9 @@ static_assert(offsetof(qc::BalanceKernelArgs, Pg) == KernelArgList::at(0) && off
                   offsetof(qc::BalanceKernelArgs, in) == KernelArgList::at(2) && offsetof(qc::BalanceKernelArgs, warm) == KernelArgList::at(3) &&
                   offsetof(qc::BalanceKernelArgs, out) == KernelArgList::at(4) && offsetof(qc::BalanceKernelArgs, chunk) == KernelArgList::at(5),
               "qc::BalanceKernelArgs no longer mirrors balance_kernel's kernarg layout");
+static_assert(sizeof(qc::CertifySummary) == sizeof(qc_certify_summary) && offsetof(qc::CertifySummary, worst_primal) == offsetof(qc_certify_summary, worst_primal) &&
+                  offsetof(qc::CertifySummary, arg_stationarity) == offsetof(qc_certify_summary, arg_stationarity),
+              "qc::CertifySummary mirrors qc_certify_summary");
 static_assert(sizeof(qc::CmdState) == sizeof(qc_commander_state) && offsetof(qc::CmdState, Vb) == offsetof(qc_commander_state, Vb) &&
                   offsetof(qc::CmdState, Rwb_d) == offsetof(qc_commander_state, Rwb_d) && offsetof(qc::CmdState, w_d) == offsetof(qc_commander_state, w_d),
               "qc::CmdState mirrors qc_commander_state");
@@ -1902,6 +1905,7 @@ struct qc_handle {
   uint32_t last_word = 0;  // qc_control(): working set of the previous call (hot start)
   bool has_last = false;
   hipStream_t stream = nullptr;
+  qc::CertifySummary* certify_parts = nullptr;  // qc_certify_batch: one partial per workgroup of certify_kernel (CERTIFY_MAX_PARTIALS)
 };
 
 using qc::fail;
@@ -2069,8 +2073,15 @@ int qc_create_abi(const qc_params* p, int device, qc_handle** out, int abi_versi
   h->cus = prop.multiProcessorCount;
   if (hipSetDevice(device) != hipSuccess || hipMalloc((void**)&h->d_params, sizeof(qc::DevParams)) != hipSuccess ||
       hipMemcpy(h->d_params, &h->dp, sizeof(qc::DevParams), hipMemcpyHostToDevice) != hipSuccess) {
+    if (h->d_params) (void)hipFree(h->d_params);
     delete h;
     return fail(QC_ERR_HIP, "qc_create: could not upload the controller constants");
+  }
+  // qc_certify_batch's partial buffer (224 KB), allocated here and not at the first certificate: that call may be inside a graph capture
+  if (hipMalloc((void**)&h->certify_parts, sizeof(qc::CertifySummary) * qc::CERTIFY_MAX_PARTIALS) != hipSuccess) {
+    (void)hipFree(h->d_params);
+    delete h;
+    return fail(QC_ERR_HIP, "qc_create: could not allocate the certificate's partial buffer");
   }
   *out = h;
   return QC_OK;
@@ -2105,6 +2116,7 @@ void qc_destroy(qc_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->d_params) (void)hipFree(h->d_params);
+  if (h->certify_parts) (void)hipFree(h->certify_parts);
   if (h->stage) (void)hipFree(h->stage);
   if (h->pin) (void)hipHostFree(h->pin);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -2196,6 +2208,35 @@ int qc_leg_plant_step_batch(qc_handle* h, size_t n, const qc_leg_plant_io* io, v
   const unsigned blocks = (unsigned)((n + qc::LEG_PLANT_BLOCK - 1) / qc::LEG_PLANT_BLOCK);
   qc::leg_plant_step_kernel<<<dim3(blocks), dim3(qc::LEG_PLANT_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, a);
   QC_HIP(hipGetLastError());
+  return QC_OK;
+}
+
+void qc_default_certify(qc_certify_io* io) {
+  if (!io) return;
+  std::memset(io, 0, sizeof(*io));
+  io->struct_size = sizeof(qc_certify_io);
+  io->act_tol = 1e-7;  // the defaults of tests/kkt_batch.py: kkt_batch's act_tol, assert_kkt's bars
+  io->primal_tol = 1e-7;
+  io->stat_tol = 1e-8;
+}
+
+int qc_certify_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_certify_io* io, void* stream) {
+  if (const int rc = qc::check_certify_args(h, n, in, io); rc != QC_OK || n == 0) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  // what the solve reads of `in`, minus everything that advances or plans (gait_dt, swing_*): nothing of `in` is written
+  qc::BatchIn bi{in->Rwb, in->Rwb_d, in->x, in->xdot, in->w, in->x_d, in->xdot_d, in->w_d, in->feet, in->stance, in->joint_q,
+                 in->gait_phase, in->gait_duty, nullptr, nullptr, nullptr, nullptr, nullptr};
+  qc::CertifyArgs a{io->grf_body, io->act_tol, io->primal_tol, io->stat_tol, io->primal, io->stationarity, io->lambda, io->grad,
+                    io->active, io->flags, io->summary ? h->certify_parts : nullptr};
+  const unsigned blocks = qc::certify_blocks(n);
+  if (in->joint_q) qc::certify_kernel<true><<<dim3(blocks), dim3(qc::CERTIFY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, bi, a);
+  else qc::certify_kernel<false><<<dim3(blocks), dim3(qc::CERTIFY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, bi, a);
+  QC_HIP(hipGetLastError());
+  if (io->summary) {
+    qc::certify_summary_kernel<<<dim3(1), dim3(qc::CERTIFY_SUMMARY_BLOCK), 0, (hipStream_t)stream>>>(h->certify_parts, (int)blocks,
+                                                                                                    reinterpret_cast<qc::CertifySummary*>(io->summary));
+    QC_HIP(hipGetLastError());
+  }
   return QC_OK;
 }
 

@@ -11,6 +11,7 @@
 #include "qc_device.hpp"
 #include "qc_plant.hpp"
 #include "qc_leg_plant.hpp"
+#include "qc_certify.hpp"
 
 namespace qc {
 
@@ -523,6 +524,37 @@ inline int leg_plant_constants(double mass, const double* Ib, const qc_leg_plant
   std::memcpy(a.Ib_inv, b.Ib_inv, sizeof(a.Ib_inv));
   for (int k = 0; k < 3; k++) a.leg_inertia[k] = io->leg_inertia[k];
   return QC_OK;
+}
+
+// ---------------------------------------------------------------- qc_certify_batch
+// The argument check of the certificate: what is wrong with the call itself (message prefix "qc_certify_batch:").
+inline int check_certify_args(const qc_handle* h, size_t n, const qc_batch_in* in, const qc_certify_io* io) {
+  if (!h || !in || !io) return fail(QC_ERR_INVALID, "qc_certify_batch: null argument");
+  if (io->struct_size != sizeof(qc_certify_io)) {
+    char msg[192];
+    std::snprintf(msg, sizeof(msg), "qc_certify_batch: qc_certify_io.struct_size is %zu, this library's qc_certify_io has %zu B (qc_default_certify sets it)",
+                  io->struct_size, sizeof(qc_certify_io));
+    return fail(QC_ERR_INVALID, msg);
+  }
+  const double tols[3] = {io->act_tol, io->primal_tol, io->stat_tol};
+  for (int k = 0; k < 3; k++)
+    if (!std::isfinite(tols[k]) || !(tols[k] >= 0.0)) return fail(QC_ERR_INVALID, "qc_certify_batch: act_tol, primal_tol and stat_tol must be finite and >= 0");
+  if (!io->primal && !io->stationarity && !io->lambda && !io->grad && !io->active && !io->flags && !io->summary)
+    return fail(QC_ERR_INVALID, "qc_certify_batch: no output requested (primal, stationarity, lambda, grad, active, flags, summary are all NULL)");
+  if (n == 0) return QC_OK;
+  if (!io->grf_body) return fail(QC_ERR_INVALID, "qc_certify_batch: grf_body is required");
+  if (!in->Rwb || !in->Rwb_d || !in->x || !in->xdot || !in->w || !in->x_d || !in->xdot_d || !in->w_d)
+    return fail(QC_ERR_INVALID, "qc_certify_batch: the state arrays Rwb, Rwb_d, x, xdot, w, x_d, xdot_d and w_d are required (commander mode is out of scope)");
+  if (!in->feet && !in->joint_q) return fail(QC_ERR_INVALID, "qc_certify_batch: feet or joint_q is required");
+  // (robot indices times 12 stay far inside 64 bits; the bound is the plant steps': fewer than 2^32 lanes of CERTIFY_BLOCK-wide groups)
+  if (n > (size_t)0xFFFFFF * CERTIFY_BLOCK) return fail(QC_ERR_INVALID, "qc_certify_batch: n is beyond one launch");
+  return QC_OK;
+}
+
+// workgroups of certify_kernel for n robots: one wave each, capped at the handle's partial buffer (the waves stride beyond it)
+inline unsigned certify_blocks(size_t n) {
+  const size_t b = (n + CERTIFY_BLOCK - 1) / CERTIFY_BLOCK;
+  return (unsigned)(b < (size_t)CERTIFY_MAX_PARTIALS ? b : (size_t)CERTIFY_MAX_PARTIALS);
 }
 
 }  // namespace qc

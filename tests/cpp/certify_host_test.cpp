@@ -1,0 +1,146 @@
+// The device-free host logic of the KKT certificate (quadruped_control_amd/csrc/qc_host.hpp): check_certify_args through every
+// refusal of qc_certify_batch, and the grid the entry point launches.  Host compiler only - links neither HIP nor the library;
+// built with the address and undefined-behaviour sanitizers (__graft_entry__.build_certify_host_test) and run by
+// tests/test_kkt_certificate_cpu.py.  Prints the failing case and exits 1 on the first violated check.
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <limits>
+#include <string>
+
+#include "../../quadruped_control_amd/csrc/qc_host.hpp"
+
+using namespace qc;
+
+static long g_checked = 0;
+#define CHECK(cond, ...)                                              \
+  do {                                                                \
+    g_checked++;                                                      \
+    if (!(cond)) {                                                    \
+      std::printf("FAILED %s:%d: %s\n  case: ", __FILE__, __LINE__, #cond); \
+      std::printf(__VA_ARGS__);                                       \
+      std::printf("\n  last error: %s\n", g_err.c_str());             \
+      std::exit(1);                                                   \
+    }                                                                 \
+  } while (0)
+#define CHECK_FAILS(rc, text, ...) CHECK((rc) == QC_ERR_INVALID && g_err == (text), __VA_ARGS__)
+
+static const double kInf = std::numeric_limits<double>::infinity();
+static const double kNan = std::numeric_limits<double>::quiet_NaN();
+
+static double buf[4];
+static uint8_t bytes[4];
+static int32_t word;
+static qc_certify_summary summary;
+
+static qc_batch_in valid_in() {
+  qc_batch_in in{};
+  in.Rwb = in.Rwb_d = in.x = in.xdot = in.w = in.x_d = in.xdot_d = in.w_d = in.feet = buf;
+  return in;
+}
+static qc_certify_io valid_io() {
+  qc_certify_io io{};
+  io.struct_size = sizeof(qc_certify_io);
+  io.grf_body = buf;
+  io.act_tol = 1e-7; io.primal_tol = 1e-7; io.stat_tol = 1e-8;
+  io.primal = buf;
+  return io;
+}
+
+static void arguments() {
+  const qc_handle* const h = reinterpret_cast<const qc_handle*>(buf);  // only compared with null
+  const qc_batch_in in = valid_in();
+  const qc_certify_io io = valid_io();
+  CHECK(check_certify_args(h, 1, &in, &io) == QC_OK, "the smallest valid call (one output)");
+  {
+    qc_batch_in b = in;
+    b.feet = nullptr; b.joint_q = buf; b.stance = bytes; b.gait_phase = buf; b.gait_duty = buf;
+    b.gait_dt = buf; b.swing_pos = b.swing_vel = b.joint_qdot = buf;  // ignored, not refused
+    qc_certify_io c = io;
+    c.stationarity = c.lambda = c.grad = buf; c.active = bytes; c.flags = &word; c.summary = &summary;
+    CHECK(check_certify_args(h, 4097, &b, &c) == QC_OK, "joint_q, every optional input and every output");
+  }
+  const char* const null_arg = "qc_certify_batch: null argument";
+  CHECK_FAILS(check_certify_args(nullptr, 1, &in, &io), null_arg, "no handle");
+  CHECK_FAILS(check_certify_args(h, 1, nullptr, &io), null_arg, "no in");
+  CHECK_FAILS(check_certify_args(h, 1, &in, nullptr), null_arg, "no io");
+  CHECK_FAILS(check_certify_args(nullptr, 0, &in, &io), null_arg, "no handle, n = 0");
+  for (const size_t sz : {(size_t)0, sizeof(qc_certify_io) - 8, sizeof(qc_certify_io) + 8, sizeof(qc_plant_io)}) {
+    qc_certify_io c = io;
+    c.struct_size = sz;
+    char text[192];
+    std::snprintf(text, sizeof(text), "qc_certify_batch: qc_certify_io.struct_size is %zu, this library's qc_certify_io has %zu B (qc_default_certify sets it)", sz,
+                  sizeof(qc_certify_io));
+    CHECK_FAILS(check_certify_args(h, 1, &in, &c), text, "struct_size %zu", sz);
+    CHECK_FAILS(check_certify_args(h, 0, &in, &c), text, "struct_size %zu, n = 0", sz);
+  }
+  const char* const tol = "qc_certify_batch: act_tol, primal_tol and stat_tol must be finite and >= 0";
+  for (const double bad : {-1e-300, -1.0, kInf, -kInf, kNan}) {
+    for (int which = 0; which < 3; which++) {
+      qc_certify_io c = io;
+      (which == 0 ? c.act_tol : which == 1 ? c.primal_tol : c.stat_tol) = bad;
+      CHECK_FAILS(check_certify_args(h, 1, &in, &c), tol, "tolerance %d = %g", which, bad);
+      CHECK_FAILS(check_certify_args(h, 0, &in, &c), tol, "tolerance %d = %g, n = 0", which, bad);
+    }
+  }
+  {
+    qc_certify_io c = io;
+    c.act_tol = c.primal_tol = c.stat_tol = 0.0;
+    CHECK(check_certify_args(h, 1, &in, &c) == QC_OK, "zero tolerances are allowed");
+  }
+  {
+    qc_certify_io c = io;
+    c.primal = nullptr;
+    const char* const none = "qc_certify_batch: no output requested (primal, stationarity, lambda, grad, active, flags, summary are all NULL)";
+    CHECK_FAILS(check_certify_args(h, 1, &in, &c), none, "no output");
+    CHECK_FAILS(check_certify_args(h, 0, &in, &c), none, "no output, n = 0");
+    // each output alone is enough
+    c = io; c.primal = nullptr; c.stationarity = buf; CHECK(check_certify_args(h, 1, &in, &c) == QC_OK, "stationarity alone");
+    c = io; c.primal = nullptr; c.lambda = buf;       CHECK(check_certify_args(h, 1, &in, &c) == QC_OK, "lambda alone");
+    c = io; c.primal = nullptr; c.grad = buf;         CHECK(check_certify_args(h, 1, &in, &c) == QC_OK, "grad alone");
+    c = io; c.primal = nullptr; c.active = bytes;     CHECK(check_certify_args(h, 1, &in, &c) == QC_OK, "active alone");
+    c = io; c.primal = nullptr; c.flags = &word;      CHECK(check_certify_args(h, 1, &in, &c) == QC_OK, "flags alone");
+    c = io; c.primal = nullptr; c.summary = &summary; CHECK(check_certify_args(h, 1, &in, &c) == QC_OK, "the summary alone");
+  }
+  {
+    qc_certify_io c = io;
+    c.grf_body = nullptr;
+    CHECK_FAILS(check_certify_args(h, 1, &in, &c), "qc_certify_batch: grf_body is required", "no grf_body");
+    CHECK(check_certify_args(h, 0, &in, &c) == QC_OK, "n = 0 asks for no array");
+  }
+  const char* const state = "qc_certify_batch: the state arrays Rwb, Rwb_d, x, xdot, w, x_d, xdot_d and w_d are required (commander mode is out of scope)";
+  const double* qc_batch_in::* const members[] = {&qc_batch_in::Rwb, &qc_batch_in::Rwb_d, &qc_batch_in::x, &qc_batch_in::xdot,
+                                                  &qc_batch_in::w, &qc_batch_in::x_d, &qc_batch_in::xdot_d, &qc_batch_in::w_d};
+  for (size_t m = 0; m < sizeof(members) / sizeof(members[0]); m++) {
+    qc_batch_in b = in;
+    b.*members[m] = nullptr;
+    CHECK_FAILS(check_certify_args(h, 1, &b, &io), state, "state array %zu missing", m);
+    CHECK(check_certify_args(h, 0, &b, &io) == QC_OK, "state array %zu missing, n = 0", m);
+  }
+  {
+    qc_batch_in b = in;
+    b.feet = nullptr;
+    CHECK_FAILS(check_certify_args(h, 1, &b, &io), "qc_certify_batch: feet or joint_q is required", "neither feet nor joint_q");
+    b.joint_q = buf;
+    CHECK(check_certify_args(h, 1, &b, &io) == QC_OK, "joint_q in place of feet");
+  }
+  const size_t most = (size_t)0xFFFFFF * CERTIFY_BLOCK;
+  CHECK(check_certify_args(h, most, &in, &io) == QC_OK, "the largest batch of one launch");
+  CHECK_FAILS(check_certify_args(h, most + 1, &in, &io), "qc_certify_batch: n is beyond one launch", "one robot more");
+}
+
+static void grid() {
+  CHECK(certify_blocks(1) == 1 && certify_blocks(64) == 1 && certify_blocks(65) == 2 && certify_blocks(1000) == 16, "one wave per 64 robots");
+  const size_t cap = (size_t)CERTIFY_MAX_PARTIALS * CERTIFY_BLOCK;
+  CHECK(certify_blocks(cap) == (unsigned)CERTIFY_MAX_PARTIALS && certify_blocks(cap + 1) == (unsigned)CERTIFY_MAX_PARTIALS &&
+            certify_blocks((size_t)0xFFFFFF * CERTIFY_BLOCK) == (unsigned)CERTIFY_MAX_PARTIALS,
+        "never more workgroups than the handle's partial buffer holds");
+  CHECK(sizeof(CertifySummary) == sizeof(qc_certify_summary) && sizeof(qc_certify_summary) == 56, "the summary record");
+}
+
+int main() {
+  arguments();
+  grid();
+  std::printf("certify host logic ok (%ld checks)\n", g_checked);
+  return 0;
+}

@@ -1,0 +1,441 @@
+"""GPU: qc_certify_batch (csrc/qc_certify.hpp) and certify_every of the rollouts against the numpy restatement
+(tests/kkt_certificate_restatement.py) and, on a fixed subset, against the same formulas at 50 digits.
+
+Batch sizes 1, 63, 64, 65, 257 and 1000: tail lanes, one wave +- 1 (a workgroup is one wave), several workgroups + a tail for
+the summary.  Robot i of every batch has contact pattern i % 16.  All references are computed once per module.
+
+Bars.  `active`, `flags` and the summary's counts and indices are compared exactly.  The test forces make that meaningful: every
+component is exactly on a face (fx ASSIGNED as mu * fz, fz as fzmin / fzmax) or at least 0.1 mu fz / 1 N inside, and the on-face
+components sit on robots with Rwb = I, where f_w = -grf_body exactly - the device evaluates the row tests without contraction,
+so such a slack is exactly 0 on both sides and the worst primal residual (0.0, many ties, lowest index) is the same robot.
+Floating-point outputs: in the 50-digit test the device may be 8 x as far from the 50-digit value as the numpy restatement is
+(FMA contraction, another summation order), with a floor of 16 * 2^-53 times the sum of |terms| of the expression
+(device_math_reference.Tr's condition sums; stationarity: on the scale 1 + |grad|).  The sweeps over sizes and handles use
+_sweep_bars: both evaluations round sums of ~30 terms, so they differ by at most 2 * 32 * 2^-53 times the sum of |terms|
+T = 2 (|A|^T |S| (|A| |f| + |b| + 1e3) + |W| |f|) - 1e3 N / N m bounding the terms of b itself for these parameters
+(m kp |dx| ~ 11 * 100 * 1, |Iw| kp_w pi ~ 0.043 * 5000 * 3.2) - taken x 4 for the chain through f_w, r and b."""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+
+from tests import device_math_reference as DMR
+from tests import kkt_certificate_restatement as KR
+from tests.kkt_batch import wrench_data
+
+pytestmark = pytest.mark.gpu
+SIZES = (1, 63, 64, 65, 257, 1000)
+U = 2.0 ** -53
+SENTINEL = -7777.25
+STATE_KEYS = ("Rwb", "Rwb_d", "x", "xdot", "w", "x_d", "xdot_d", "w_d")
+WANT_ALL = ("primal", "stationarity", "lambda", "grad", "active", "flags")
+
+
+@pytest.fixture(scope="module")
+def q(built):
+    import quadruped_control_amd as q
+
+    return q
+
+
+def _params(q, kind):
+    P = q.cheetah_params(mu=0.6)
+    if kind == "uniform":
+        return P
+    rng = np.random.default_rng(5)
+    if kind == "per-axis":
+        return dict(P, W=np.diag(1e-5 * rng.uniform(0.5, 2.0, 12)))
+    M = rng.normal(size=(12, 12))
+    N = rng.normal(size=(6, 6))
+    return dict(P, W=1e-5 * (np.eye(12) + 0.05 * (M @ M.T) / 12.0), S=np.asarray(P["S"]) + 0.2 * (N @ N.T) / 6.0)  # dense S and W
+
+
+@pytest.fixture(scope="module")
+def ctls(q):
+    out = {k: q.BalanceController.from_params(_params(q, k), device=0) for k in ("uniform", "per-axis", "dense")}
+    assert [c.kernel_name for c in out.values()] == ["diagW-6x6-uniform", "diagW-6x6", "dense-12x12"]
+    yield out
+    for c in out.values():
+        c.close()
+
+
+@functools.lru_cache(maxsize=None)
+def _inputs(n, source):
+    """(batch, world forces): contact pattern i % 16; even robots level (Rwb = I).  source: 'feet' with stance bytes, 'joint_q' with
+    gait_phase (0.3 stance / 0.9 swing against the handle's duty 0.816), 'duty' = joint_q, gait_phase 0.3 / 0.7 and gait_duty 0.5."""
+    import quadruped_control_amd as q
+    from quadruped_control_amd import workloads
+
+    P = q.cheetah_params(mu=0.6)
+    b = dict(workloads.config3(n=n))
+    b["Rwb"] = b["Rwb"].copy()
+    b["Rwb"][0::2] = np.eye(3).reshape(9)
+    st = ((np.arange(n)[:, None] >> np.arange(4)[None, :]) & 1).astype(np.uint8)
+    if source == "feet":
+        b["stance"] = st
+    else:
+        b = workloads.with_joint_angles(b)
+        b.pop("feet", None)
+        b.pop("stance", None)
+        b["gait_phase"] = np.where(st != 0, 0.3, 0.9 if source == "joint_q" else 0.7)
+        if source == "duty":
+            b["gait_duty"] = np.full(n, 0.5)
+    rng = np.random.default_rng(1000 + n)
+    mu, fzmin, fzmax = P["mu"], P["fzmin"], P["fzmax"]
+    level = (np.arange(n) % 2 == 0)[:, None]
+    pick = rng.integers(0, 3, (n, 4))
+    fz = np.where(level & (pick == 0), fzmin, np.where(level & (pick == 1), fzmax, rng.uniform(fzmin + 1.0, fzmax - 1.0, (n, 4))))
+    fw = np.zeros((n, 4, 3))
+    fw[..., 2] = fz
+    for k in range(2):
+        side = rng.integers(-1, 2, (n, 4))
+        inside = rng.uniform(-0.9, 0.9, (n, 4)) * (mu * fz)
+        fw[..., k] = np.where(level & (side == 1), mu * fz, np.where(level & (side == -1), -(mu * fz), inside))
+    fw[st == 0] = 0.0
+    R = b["Rwb"].reshape(n, 3, 3)
+    grf = -np.einsum("nji,nkj->nki", R, fw).reshape(n, 12)  # grf_body = -Rwb^T f_w
+    grf[0::2] = -fw[0::2].reshape(-1, 12)  # exactly, where Rwb = I
+    grf += 0.0  # (no -0.0)
+    return {k: np.ascontiguousarray(v) for k, v in b.items()}, np.ascontiguousarray(grf)
+
+
+def _certify(q, ctl, b, grf, want=WANT_ALL, summary=True, **kw):
+    import torch
+
+    dev = q.to_device(b)
+    g = torch.from_numpy(grf).cuda()
+    out = ctl.certify_batch(dev, g, want=want, summary=summary, **kw)
+    torch.cuda.synchronize()
+    res = {k: v.cpu().numpy() for k, v in out.items() if k != "summary"}
+    if summary:
+        from quadruped_control_amd.balance_controller import certify_summary
+
+        res["summary"] = certify_summary(out["summary"])
+    return res
+
+
+def _sweep_bars(P, b, grf):
+    """(grad [n,12], lam [n,4,3], primal [n], stationarity [n]) bars of the module docstring"""
+    bb = KR.with_feet(b)
+    n = grf.shape[0]
+    A, bv = wrench_data(P, bb)
+    f = np.abs(np.einsum("nij,nkj->nki", bb["Rwb"].reshape(n, 3, 3), grf.reshape(n, 4, 3))).reshape(n, 12)
+    S, W = np.abs(np.asarray(P["S"], float).reshape(6, 6)), np.abs(np.asarray(P["W"], float).reshape(12, 12))
+    T = 2.0 * (np.einsum("nji,nj->ni", np.abs(A), (np.einsum("nij,nj->ni", np.abs(A), f) + np.abs(bv) + 1e3) @ S.T) + f @ W.T)
+    grad = 4 * 64 * U * T
+    t = grad.reshape(n, 4, 3)
+    lam = np.stack([t[..., 0], t[..., 1], P["mu"] * (t[..., 0] + t[..., 1]) + t[..., 2]], axis=-1)
+    primal = 16 * 2 * U * (f.reshape(n, 4, 3).sum(axis=2).max(axis=1) * (1.0 + P["mu"]) + P["fzmax"])
+    return grad, lam, primal, lam[..., 2].max(axis=1)
+
+
+def _check_against_restatement(P, b, grf, got, ref):
+    n = grf.shape[0]
+    assert np.array_equal(got["active"], ref["active"])
+    assert np.array_equal(got["flags"], ref["flags"])
+    bg, bl, bp, bs = _sweep_bars(P, b, grf)
+    assert np.all(np.abs(got["grad"] - ref["grad"]) <= bg)
+    assert np.all(np.abs(got["lambda"].reshape(n, 4, 3) - ref["lam"]) <= bl)
+    assert np.all(np.abs(got["primal"] - ref["primal"]) <= bp)
+    gn = 1.0 + np.linalg.norm(ref["grad"], axis=1)
+    assert np.all(np.abs(got["stationarity"] - ref["stationarity"]) <= bs / gn + 4 * U * ref["stationarity"])
+    s, r = got["summary"], ref["summary"]
+    for k in ("n_fail", "n_nonfinite", "n_swing_nonzero", "arg_primal", "arg_stationarity"):
+        assert s[k] == r[k], (k, s, r)
+
+
+# ------------------------------------------------------------------ tails and block edges
+@pytest.mark.parametrize("n", SIZES)
+@pytest.mark.parametrize("source", ["feet", "joint_q", "duty"])
+def test_sizes_contact_patterns_and_inputs(q, ctls, n, source):
+    """Every size, every contact pattern, feet + stance bytes and joint_q + gait_phase (with the handle's duty and a given one):
+    all outputs against the restatement, nothing written past the end (each array is allocated with a sentinel row behind it)."""
+    import torch
+
+    P = _params(q, "uniform")
+    b, grf = _inputs(n, source)
+    ref = KR.certificate(P, b, grf, default_duty=KR.DEFAULT_DUTY)
+    dev = q.to_device(b)
+    shapes = {"primal": ((n + 1,), torch.float64), "stationarity": ((n + 1,), torch.float64), "lambda": ((n + 1, 4, 3), torch.float64),
+              "grad": ((n + 1, 12), torch.float64), "active": ((n + 1, 4), torch.uint8), "flags": ((n + 1,), torch.int32)}
+    big = {k: torch.full(s, 77 if dt != torch.float64 else SENTINEL, dtype=dt, device="cuda") for k, (s, dt) in shapes.items()}
+    out = {k: v[:n] for k, v in big.items()}
+    out["summary"] = torch.zeros(56, dtype=torch.uint8, device="cuda")
+    res = ctls["uniform"].certify_batch(dev, torch.from_numpy(grf).cuda(), want=WANT_ALL, out=out)
+    torch.cuda.synchronize()
+    from quadruped_control_amd.balance_controller import certify_summary
+
+    got = {k: v.cpu().numpy() for k, v in res.items() if k != "summary"}
+    got["summary"] = certify_summary(res["summary"])
+    _check_against_restatement(P, b, grf, got, ref)
+    for k, v in big.items():
+        tail = v[n].cpu().numpy()
+        assert np.all(tail == (SENTINEL if v.dtype == torch.float64 else 77)), k
+
+
+@pytest.mark.parametrize("form", ["uniform", "per-axis", "dense"])
+def test_every_formulation_uses_the_full_weights(q, ctls, form):
+    """The certificate reads the handle's full S and W whatever form the solver runs: uniform W, per-axis W, dense S and W."""
+    P = _params(q, form)
+    b, grf = _inputs(257, "feet")
+    got = _certify(q, ctls[form], b, grf)
+    _check_against_restatement(P, b, grf, got, KR.certificate(P, b, grf))
+
+
+# ------------------------------------------------------------------ non-optimal points against 50 digits
+@pytest.mark.parametrize("source", ["feet", "joint_q"])
+def test_non_optimal_points_against_50_digits(q, ctls, source):
+    """Feasible but wrong forces (module docstring): the integer outputs equal the restatement's exactly on all 257 robots, and on
+    the first 32 the device is at most 8 x as far from the 50-digit value as the numpy restatement is (floor 16 * 2^-53 * sum of
+    |terms|).  Measured worst ratios device distance / bar: profiles/kkt_certificate.md."""
+    P = _params(q, "dense")
+    n = 257
+    b, grf = _inputs(n, source)
+    ref = KR.certificate(P, b, grf)
+    got = _certify(q, ctls["dense"], b, grf)
+    assert ref["summary"]["n_fail"] >= 200 and ref["summary"]["n_nonfinite"] == 0  # (the robots without a stance foot carry no force: they pass)
+    assert np.array_equal(got["active"], ref["active"]) and np.array_equal(got["flags"], ref["flags"])
+    for k in ("n_fail", "n_nonfinite", "n_swing_nonzero", "arg_primal", "arg_stationarity"):
+        assert got["summary"][k] == ref["summary"][k], (k, got["summary"], ref["summary"])
+    codes = ref["active"]
+    assert set(np.unique(codes & 3)) == {0, 1, 2} and set(np.unique((codes >> 4) & 3)) == {0, 1, 2}  # every single-row case occurs
+    kin = None if source == "feet" else (DMR.HIP.reshape(-1), DMR.LINKS.reshape(-1))
+    worst = {}
+    for i in range(32):
+        mpv = KR.certificate_mp(P, b, grf, i, ref["active"][i], kin=kin)
+        for name, dev_v, np_v in (("grad", got["grad"][i], ref["grad"][i]), ("lam", got["lambda"][i], ref["lam"][i]),
+                                  ("primal", got["primal"][i], ref["primal"][i]), ("stationarity", got["stationarity"][i], ref["stationarity"][i])):
+            vals, scale = mpv[name]
+            d_dev, d_np = KR.distance(dev_v, vals), KR.distance(np_v, vals)
+            bar = np.maximum(8.0 * d_np, 16 * U * scale)
+            ok = d_dev <= bar
+            ratio = float(np.max(d_dev / np.where(bar > 0, bar, 1.0)))
+            worst[name] = max(worst.get(name, 0.0), ratio)
+            assert np.all(ok), (i, name, d_dev, d_np, scale)
+    print(f"kkt certificate, {source}: worst device distance / bar over 32 robots: " + ", ".join(f"{k} {v:.3f}" for k, v in worst.items()))
+
+
+# ------------------------------------------------------------------ solved points, perturbation
+@functools.lru_cache(maxsize=None)
+def _solved(n):
+    import torch
+
+    import quadruped_control_amd as q
+    from quadruped_control_amd import workloads
+
+    P = q.cheetah_params(mu=0.6)
+    b = {k: np.ascontiguousarray(v) for k, v in workloads.config3(n=n).items()}
+    ctl = q.BalanceController.from_params(P, device=0)
+    out = ctl.control_batch(q.to_device(b))
+    torch.cuda.synchronize()
+    res = out["grf_body"].cpu().numpy(), out["status"].cpu().numpy()
+    ctl.close()
+    return b, res[0], res[1]
+
+
+def test_solved_points_pass_the_projects_bars(q, ctls):
+    """After control_batch every robot with status 0 passes assert_kkt's defaults on the device: primal < 1e-7, stationarity < 1e-8."""
+    b, grf, status = _solved(1000)
+    got = _certify(q, ctls["uniform"], b, grf)
+    ok = status == 0
+    assert ok.sum() >= 990
+    assert np.all(got["primal"][ok] < 1e-7) and np.all(got["stationarity"][ok] < 1e-8) and np.all(got["flags"][ok] == 0)
+    ref = KR.certificate(_params(q, "uniform"), b, grf)
+    assert got["summary"]["n_fail"] == ref["summary"]["n_fail"] == int((~ok & ((ref["primal"] > 1e-7) | (ref["stationarity"] > 1e-8))).sum())
+
+
+def test_failed_robots_are_counted_where_zero_forces_violate(q):
+    """A handle capped at two recalculations leaves most robots unsolved, with zero forces: n_fail is the number of robots with
+    status != 0 whose zero forces really violate the bounds (fzmin = 10 N: every one with a stance foot), as the restatement counts."""
+    import torch
+    from quadruped_control_amd import workloads
+
+    P = q.cheetah_params(mu=0.6)
+    b = {k: np.ascontiguousarray(v) for k, v in workloads.config3(n=257).items()}
+    ctl = q.BalanceController.from_params(P, device=0, max_iter=2)
+    dev = q.to_device(b)
+    out = ctl.control_batch(dev)
+    cert = ctl.certify_batch(dev, out["grf_body"])
+    torch.cuda.synchronize()
+    from quadruped_control_amd.balance_controller import certify_summary
+
+    status, grf = out["status"].cpu().numpy(), out["grf_body"].cpu().numpy()
+    s = certify_summary(cert["summary"])
+    ctl.close()
+    ref = KR.certificate(P, b, grf)
+    failed = status != 0
+    assert failed.sum() >= 50 and not grf[failed].any()
+    bad = ~(ref["primal"] <= 1e-7) | ~(ref["stationarity"] <= 1e-8) | ref["swing_nonzero"]
+    assert not bad[~failed].any()
+    assert s["n_fail"] == int((failed & bad).sum()) == ref["summary"]["n_fail"]
+    assert np.all(cert["primal"].cpu().numpy()[failed & bad] == 10.0)  # fzmin - 0
+
+
+def test_perturbing_one_force_fails_exactly_that_robot(q, ctls):
+    """+1e-3 N on one component of one solved robot: its residual rises above the bars, it becomes the summary's worst robot, n_fail
+    grows by exactly one, and every other robot's outputs are bit-identical."""
+    b, grf, status = _solved(257)
+    assert (status == 0).all()
+    base = _certify(q, ctls["uniform"], b, grf)
+    assert base["summary"]["n_fail"] == 0
+    victim = 133
+    foot = int(np.flatnonzero(b["stance"][victim])[0])
+    g2 = grf.copy()
+    g2[victim, 3 * foot + 2] += 1e-3
+    got = _certify(q, ctls["uniform"], b, g2)
+    assert got["stationarity"][victim] > 1e-8 or got["primal"][victim] > 1e-7
+    assert got["summary"]["n_fail"] == 1
+    assert victim in (got["summary"]["arg_stationarity"], got["summary"]["arg_primal"])
+    others = np.arange(257) != victim
+    for k in WANT_ALL:
+        assert np.array_equal(got[k][others], base[k][others]), k
+
+
+# ------------------------------------------------------------------ the summary
+def test_summary_is_the_reduction_of_the_per_robot_arrays(q, ctls):
+    """Bit-equal to reducing the device's own per-robot arrays on the host; identical with every per-robot pointer NULL; one NaN
+    state sets n_nonfinite = 1 and leaves worst_* finite.  n = 1000: sixteen workgroups, the last one with a tail."""
+    b, grf = _inputs(1000, "feet")
+    got = _certify(q, ctls["uniform"], b, grf)
+    host = KR.summarize(got["primal"], got["stationarity"], (got["flags"] & 1) != 0)
+    assert got["summary"] == host
+    alone = _certify(q, ctls["uniform"], b, grf, want=())
+    assert alone == {"summary": got["summary"]}
+    bn = dict(b, x=b["x"].copy())
+    bn["x"][517, 1] = np.nan
+    nan = _certify(q, ctls["uniform"], bn, grf)
+    s = nan["summary"]
+    assert s["n_nonfinite"] == 1 and nan["flags"][517] & 2 and np.isnan(nan["stationarity"][517])
+    assert np.isfinite(s["worst_primal"]) and np.isfinite(s["worst_stationarity"]) and s["arg_stationarity"] != 517
+    assert s == KR.summarize(nan["primal"], nan["stationarity"], (nan["flags"] & 1) != 0)
+    assert not (nan["stationarity"][517] <= 1e-8) and s["n_fail"] >= got["summary"]["n_fail"]  # a NaN fails
+
+
+def test_inputs_are_left_alone_and_the_result_repeats(q, ctls):
+    """Every tensor of the batch and grf_body is bit-identical after the call - gait_phase too, although gait_dt is given: the
+    certificate advances no clock - and two calls give identical outputs."""
+    import torch
+
+    b, grf = _inputs(257, "joint_q")
+    b = dict(b, gait_dt=np.full(257, 1.0 / 300.0), joint_qdot=np.zeros((257, 12)))
+    dev = q.to_device(b)
+    g = torch.from_numpy(grf).cuda()
+    before = {k: v.clone() for k, v in dev.items()}
+    g0 = g.clone()
+    one = {k: v.clone() for k, v in ctls["uniform"].certify_batch(dev, g, want=WANT_ALL).items()}
+    two = ctls["uniform"].certify_batch(dev, g, want=WANT_ALL)
+    torch.cuda.synchronize()
+    for k, v in dev.items():
+        assert torch.equal(v.view(torch.uint8), before[k].view(torch.uint8)), k
+    assert torch.equal(g.view(torch.uint8), g0.view(torch.uint8))
+    for k in one:
+        assert torch.equal(one[k].view(torch.uint8), two[k].view(torch.uint8)), k
+    ref = KR.certificate(_params(q, "uniform"), {k: v for k, v in b.items() if k not in ("gait_dt", "joint_qdot")}, grf)
+    assert np.array_equal(two["active"].cpu().numpy(), ref["active"])
+
+
+# ------------------------------------------------------------------ closed loop
+def test_rollout_certifies_every_second_step(q):
+    """rollout(steps=6, certify_every=2) on an all-solved batch of 64: three summaries with n_fail == 0, and a final state bit-equal
+    to the same rollout without certificates."""
+    import torch
+    from quadruped_control_amd import workloads
+    from quadruped_control_amd.balance_controller import certify_summary
+
+    P = q.cheetah_params()
+    b = workloads.config2(n=64)
+    R = b["Rwb"].reshape(64, 3, 3)
+    pw = np.ascontiguousarray((b["x"][:, None, :] + np.einsum("nij,nlj->nli", R, b["feet"].reshape(64, 4, 3))).reshape(64, 12))
+    ctl = q.BalanceController.from_params(P, device=0)
+    ends = []
+    for every in (None, 2):
+        dev = q.to_device(b)
+        state, out = ctl.rollout(dev, torch.from_numpy(pw).cuda(), steps=6, dt=1.0 / 300.0, certify_every=every)
+        torch.cuda.synchronize()
+        ends.append(({k: v.clone() for k, v in state.items()}, out))
+    ctl.close()
+    assert "certificates" not in ends[0][1]
+    certs = ends[1][1]["certificates"]
+    assert [k for k, _ in certs] == [0, 2, 4]
+    assert (ends[1][1]["status"] == 0).all()
+    for _, t in certs:
+        s = certify_summary(t)
+        assert s["n_fail"] == 0 and s["n_nonfinite"] == 0 and s["worst_stationarity"] < 1e-8, s
+    for k in ends[0][0]:
+        assert torch.equal(ends[0][0][k].view(torch.uint8), ends[1][0][k].view(torch.uint8)), k
+    assert torch.equal(ends[0][1]["grf_body"], ends[1][1]["grf_body"])
+
+
+def test_rollout_tick_certifies_and_refuses_commander_mode(q):
+    """rollout_tick(command=None, certify_every=2): the certificate reads joint_q and the contact rule of the tick; in commander
+    mode certify_every raises ValueError before anything is launched."""
+    import torch
+    from quadruped_control_amd import workloads
+    from quadruped_control_amd.balance_controller import certify_summary
+
+    P = q.cheetah_params()
+    b = workloads.with_joint_angles(workloads.config2(n=64))
+    b.pop("feet", None)
+    b["joint_qdot"] = np.zeros((64, 12))
+    ctl = q.BalanceController.from_params(P, device=0)
+    dev = q.to_device({k: np.ascontiguousarray(v) for k, v in b.items()})
+    with pytest.raises(ValueError, match="certify_every"):
+        ctl.rollout_tick(dev, {"state": None}, steps=2, dt=1.0 / 300.0, leg_inertia=0.02, certify_every=1)
+    state, out = ctl.rollout_tick(dev, None, steps=4, dt=1.0 / 300.0, leg_inertia=0.02, certify_every=2)
+    torch.cuda.synchronize()
+    ctl.close()
+    assert [k for k, _ in out["certificates"]] == [0, 2]
+    sums = [certify_summary(t) for _, t in out["certificates"]]
+    assert sums[0]["n_fail"] == 0, sums[0]  # (the first tick solves config 2's states; later ones are whatever the plant made of them)
+    for s in sums:
+        assert s["n_nonfinite"] == 0 and s["n_swing_nonzero"] == 0 and s["arg_stationarity"] >= 0, s
+
+
+# ------------------------------------------------------------------ refusals
+def test_refusals_raise_and_launch_nothing(q, ctls):
+    """Each refusal of qc_certify_batch raises from Python with the entry point's prefix and launches nothing: the output tensors
+    keep their sentinel."""
+    import torch
+    from quadruped_control_amd import _lib
+
+    ctl = ctls["uniform"]
+    n = 65
+    b, grf = _inputs(n, "feet")
+    dev = q.to_device(b)
+    g = torch.from_numpy(grf).cuda()
+    out = {"primal": torch.full((n,), SENTINEL, dtype=torch.float64, device="cuda"), "summary": torch.full((56,), 77, dtype=torch.uint8, device="cuda")}
+
+    def refused(batch, grf_body, **kw):
+        with pytest.raises(RuntimeError, match=r"qc_certify_batch failed \(-1\): qc_certify_batch:"):
+            ctl.certify_batch(batch, grf_body, want=kw.pop("want", ("primal",)), out=kw.pop("out", out), **kw)
+
+    refused(dev, None)
+    for k in STATE_KEYS:
+        refused({a: v for a, v in dev.items() if a != k}, g)
+    refused({a: v for a, v in dev.items() if a != "feet"}, g)
+    for name in ("act_tol", "primal_tol", "stat_tol"):
+        for bad in (-1e-9, float("nan"), float("inf")):
+            refused(dev, g, **{name: bad})
+    refused(dev, g, want=(), summary=False, out=None)
+    # the struct itself, the handle, `in`, `io` and n: straight on the C ABI
+    lib = _lib.load()
+    io = _lib.QcCertifyIo()
+    lib.qc_default_certify(ctypes.byref(io))
+    io.grf_body, io.primal, io.summary = g.data_ptr(), out["primal"].data_ptr(), out["summary"].data_ptr()
+    bi = _lib.QcBatchIn()
+    for k in STATE_KEYS + ("feet", "stance"):
+        setattr(bi, k, dev[k].data_ptr())
+    calls = [(None, n, ctypes.byref(bi), ctypes.byref(io)), (ctl._h, n, None, ctypes.byref(io)), (ctl._h, n, ctypes.byref(bi), None),
+             (ctl._h, 0xFFFFFF * 64 + 1, ctypes.byref(bi), ctypes.byref(io))]
+    for h, m, pin, pio in calls:
+        assert lib.qc_certify_batch(h, m, pin, pio, None) == -1 and _lib.last_error().startswith("qc_certify_batch:")
+    io.struct_size = 88
+    assert lib.qc_certify_batch(ctl._h, n, ctypes.byref(bi), ctypes.byref(io), None) == -1 and _lib.last_error().startswith("qc_certify_batch: qc_certify_io.struct_size")
+    io.struct_size = 96
+    assert lib.qc_certify_batch(ctl._h, 0, ctypes.byref(bi), ctypes.byref(io), None) == 0  # n == 0: QC_OK, nothing launched
+    torch.cuda.synchronize()
+    assert bool((out["primal"] == SENTINEL).all()) and bool((out["summary"] == 77).all())
+    assert lib.qc_certify_batch(ctl._h, n, ctypes.byref(bi), ctypes.byref(io), None) == 0  # and the same structs, valid, do launch
+    torch.cuda.synchronize()
+    assert bool((out["primal"] != SENTINEL).all()) and not bool((out["summary"] == 77).all())
