@@ -35,6 +35,63 @@ def _fill(carr, values, n, name):
     carr[:] = a.tolist()
 
 
+def _check_tensor(name, t, n, k, dtype, dev, required, label=None):
+    """`t` is a contiguous `dtype` tensor of n * k elements on `dev` (k None: [n]) - or, unless required, None.  Returns whether
+    there is a tensor.  `label`: the dtype as the message words it, where that is not str(dtype)."""
+    if t is None and not required:
+        return False
+    if t is None or t.dtype != dtype or not t.is_contiguous() or t.device != dev or t.numel() != n * (k or 1):
+        raise ValueError(f"{name}: need contiguous {label or dtype} [{n}{'' if k is None else f',{k}'}] on {dev}")
+    return True
+
+
+class _RolloutPlans:
+    """What rollout() and rollout_tick() share: the output tensors, the two working-set arrays a warm rollout ping-pongs between (a
+    solve never reads the array it writes), the solves marshalled once - `plan(first, warm, out)` returns the launch of step 0
+    (first) or of a later step -, the certificate of every `certify_every`-th step, and the returned dict's tail."""
+
+    def __init__(self, ctl, who, batch, n, warm, plan, certify_every, stream, torques=False):
+        import torch
+
+        dev = torch.device("cuda", ctl.device)
+        self.out = out = {"grf_body": torch.zeros((n, 12), dtype=torch.float64, device=dev),
+                          "status": torch.full((n,), -1, dtype=torch.int32, device=dev)}
+        if torques:
+            out["joint_tau"] = torch.zeros((n, 12), dtype=torch.float64, device=dev)
+        self.warm = warm
+        self.sets = sets = [torch.zeros((n,), dtype=torch.int32, device=dev) for _ in range(2)] if warm else []
+        if warm:
+            self.solves = [plan(True, None, dict(out, active_set=sets[0])), plan(False, sets[0], dict(out, active_set=sets[1])),
+                           plan(False, sets[1], dict(out, active_set=sets[0]))]
+        else:
+            self.solves = [plan(True, None, out), plan(False, None, out)]
+        self.certify_every, self.certificates = certify_every, None
+        if certify_every is not None:
+            if int(certify_every) < 1:
+                raise ValueError(f"{who}: certify_every must be >= 1")
+            self._certify, self._cert = ctl.plan_certify(batch, out["grf_body"], want=(), summary=True, stream=stream)
+            self.certificates = []
+
+    def solve(self, k):
+        self.solves[0 if k == 0 else (1 + (k - 1) % 2 if self.warm else 1)]()
+
+    def certify(self, k):
+        if self.certificates is not None and k % int(self.certify_every) == 0:
+            self._certify()
+            self.certificates.append((k, self._cert["summary"].clone()))
+
+    def finish(self, steps, history, **last):
+        out = self.out
+        if self.warm and steps > 0:
+            out["active_set"] = self.sets[steps % 2 == 0]  # step 0 wrote sets[0], step 1 sets[1], step 2 sets[0], ...
+        out.update(last)
+        if history is not None:
+            out["history"] = history
+        if self.certificates is not None:
+            out["certificates"] = self.certificates
+        return out
+
+
 class BalanceController:
     """Reactive optimal force-balance controller (drop-in for the reference class)."""
 
@@ -188,8 +245,7 @@ class BalanceController:
             t = batch.get(name)
             if t is None and name == "feet" and batch.get("joint_q") is not None:
                 continue  # feet come from forward kinematics on the device
-            if t is None or t.dtype != torch.float64 or not t.is_contiguous() or t.device != dev or t.numel() != n * k:
-                raise ValueError(f"{name}: need contiguous float64 [{n},{k}] on {dev}")
+            _check_tensor(name, t, n, k, torch.float64, dev, True, "float64")
             setattr(bi, name, t.data_ptr())
         st = batch.get("stance")
         if st is not None:
@@ -200,9 +256,7 @@ class BalanceController:
                         ("gait_dt", 1),  # on-device gait clock (gait.cpp:113-123): gait_phase is advanced in place
                         ("swing_pos", 12), ("swing_vel", 12), ("joint_qdot", 12)):  # swing-leg torques
             t = batch.get(name)
-            if t is not None:
-                if t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != n * k or t.device != dev:
-                    raise ValueError(f"{name}: need contiguous float64 [{n},{k}] on {dev}")
+            if _check_tensor(name, t, n, k, torch.float64, dev, False, "float64"):
                 setattr(bi, name, t.data_ptr())
         ss = batch.get("swing_state")
         if ss is not None:  # torch.uint8 tensor of n * sizeof(qc_swing_state) bytes, updated in place
@@ -246,6 +300,25 @@ class BalanceController:
             warm_ptr = warm.data_ptr()
         return n, bi, bo, warm_ptr, out
 
+    def _stream_ptr(self, stream):
+        """The stream a call runs on, for the C ABI: `stream`, or torch's current stream of this controller's device."""
+        import torch
+
+        s = stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.device))
+        return C.c_void_p(s.cuda_stream)
+
+    def _launcher(self, name, args, keep):
+        """`launch()`: exactly one call of the library's `name`(handle, *args), nothing marshalled per call.  `keep` holds what the
+        pointers in `args` point into for as long as the closure lives."""
+        fn, h = getattr(self._lib, name), self._h
+
+        def launch(_keep=keep):
+            rc = fn(h, *args)
+            if rc != _lib.QC_OK:
+                raise RuntimeError(f"{name} failed ({rc}): {_lib.last_error()}")
+
+        return launch
+
     def control_batch(self, batch, warm=None, out=None, want_active_set=False, want_iterations=False, stream=None,
                       want_torques=False):
         """n robots, device-resident.  `batch`: dict of CUDA/HIP torch tensors
@@ -255,11 +328,8 @@ class BalanceController:
         With batch['joint_q'] [n,12] the foot positions come from the reference's
         forward kinematics (kinematics.cpp:81-103) and want_torques=True adds
         joint_tau [n,12] = clamp(J^T f_body) for stance legs (kinematics.cpp:219-231)."""
-        import torch
-
         n, bi, bo, warm_ptr, out = self._marshal(batch, warm, out, want_active_set, want_iterations, want_torques)
-        s = stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.device))
-        rc = self._lib.qc_control_batch(self._h, n, C.byref(bi), warm_ptr, C.byref(bo), C.c_void_p(s.cuda_stream))
+        rc = self._lib.qc_control_batch(self._h, n, C.byref(bi), warm_ptr, C.byref(bo), self._stream_ptr(stream))
         if rc != _lib.QC_OK:
             raise RuntimeError(f"qc_control_batch failed ({rc}): {_lib.last_error()}")
         return out
@@ -272,21 +342,10 @@ class BalanceController:
         benchmark loop where the tensors are updated in place.  Planning launches
         NOTHING: the first launch() is the first tick (the gait clock and the swing
         planner of a stateful batch are not advanced by plan_batch itself)."""
-        import torch
-
         n, bi, bo, warm_ptr, out = self._marshal(batch, warm, out, want_active_set, want_iterations, want_torques)
         self.query_launch(n, kin=batch.get("joint_q") is not None, warm=warm is not None)  # occupancy query done now, not inside a graph capture
-        s = stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.device))
-        fn, h, sp = self._lib.qc_control_batch, self._h, C.c_void_p(s.cuda_stream)
-        bi_ref, bo_ref = C.byref(bi), C.byref(bo)
-        keep = (batch, warm, out, bi, bo)
-
-        def launch(_keep=keep):
-            rc = fn(h, n, bi_ref, warm_ptr, bo_ref, sp)
-            if rc != _lib.QC_OK:
-                raise RuntimeError(f"qc_control_batch failed ({rc}): {_lib.last_error()}")
-
-        return launch, out
+        args = (n, C.byref(bi), warm_ptr, C.byref(bo), self._stream_ptr(stream))
+        return self._launcher("qc_control_batch", args, (batch, warm, out, bi, bo)), out
 
     # --------------------------------------------------------- commander mode
     def _marshal_command(self, n, command):
@@ -301,15 +360,11 @@ class BalanceController:
                              "(new_commander_states)")
         c.state = st.data_ptr()
         fresh, twist = command.get("fresh"), command.get("twist")
-        if fresh is not None:
-            if fresh.dtype != torch.uint8 or not fresh.is_contiguous() or fresh.numel() != n or fresh.device != dev:
-                raise ValueError(f"command['fresh']: need contiguous uint8 [{n}] on {dev}")
+        if _check_tensor("command['fresh']", fresh, n, None, torch.uint8, dev, False, "uint8"):
             if twist is None:
                 raise ValueError("command['fresh'] needs command['twist']")
             c.fresh = fresh.data_ptr()
-        if twist is not None:
-            if twist.dtype != torch.float64 or not twist.is_contiguous() or twist.numel() != n * 6 or twist.device != dev:
-                raise ValueError(f"command['twist']: need contiguous float64 [{n},6] on {dev}")
+        if _check_tensor("command['twist']", twist, n, 6, torch.float64, dev, False, "float64"):
             c.twist = twist.data_ptr()
         for name in ("stand_height", "stand_tol", "cmd_dt"):
             if command.get(name) is not None:
@@ -319,22 +374,11 @@ class BalanceController:
     def plan_tick(self, batch, command, warm=None, out=None, want_active_set=False, want_iterations=False, stream=None):
         """tick_batch() marshalled once: returns (launch, out), `launch()` being one qc_tick_batch call (graph-capturable).
         Like plan_batch, planning launches nothing."""
-        import torch
-
         n, bi, bo, warm_ptr, out = self._marshal(batch, warm, out, want_active_set, want_iterations, True, commander=True)
         c = self._marshal_command(n, command)
         self.query_launch(n, kin=True, warm=warm is not None)  # occupancy query done now, not inside a graph capture
-        s = stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.device))
-        fn, h, sp = self._lib.qc_tick_batch, self._h, C.c_void_p(s.cuda_stream)
-        bi_ref, c_ref, bo_ref = C.byref(bi), C.byref(c), C.byref(bo)
-        keep = (batch, command, warm, out, bi, c, bo)
-
-        def launch(_keep=keep):
-            rc = fn(h, n, bi_ref, c_ref, warm_ptr, bo_ref, sp)
-            if rc != _lib.QC_OK:
-                raise RuntimeError(f"qc_tick_batch failed ({rc}): {_lib.last_error()}")
-
-        return launch, out
+        args = (n, C.byref(bi), C.byref(c), warm_ptr, C.byref(bo), self._stream_ptr(stream))
+        return self._launcher("qc_tick_batch", args, (batch, command, warm, out, bi, c, bo)), out
 
     def tick_batch(self, batch, command, warm=None, out=None, want_active_set=False, want_iterations=False, stream=None):
         """The complete tick in commander mode (qc_tick_batch, include/qc_balance.h): the desired COM state is not an input but
@@ -360,27 +404,15 @@ class BalanceController:
         arrays = [(k, state.get(k), m) for k, m in (("Rwb", 9), ("x", 3), ("xdot", 3), ("w", 3))]
         arrays += [("grf_body", grf_body, 12), ("foot_world", foot_world, 12)] + ([("feet", feet, 12)] if feet is not None else [])
         for name, t, k in arrays:
-            if t is None or t.dtype != torch.float64 or not t.is_contiguous() or t.device != dev or t.numel() != n * k:
-                raise ValueError(f"{name}: need contiguous float64 [{n},{k}] on {dev}")
+            _check_tensor(name, t, n, k, torch.float64, dev, True, "float64")
             setattr(io, name, t.data_ptr() if n else None)
         io.dt = float(dt)
         return n, io
 
     def plan_plant(self, state, grf_body, foot_world, dt, feet=None, stream=None):
         """plant_step() marshalled once: returns `launch`, one qc_plant_step_batch call on tensors that are updated in place."""
-        import torch
-
         n, io = self._marshal_plant(state, grf_body, foot_world, dt, feet)
-        s = stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.device))
-        fn, h, sp, io_ref = self._lib.qc_plant_step_batch, self._h, C.c_void_p(s.cuda_stream), C.byref(io)
-        keep = (state, grf_body, foot_world, feet, io)
-
-        def launch(_keep=keep):
-            rc = fn(h, n, io_ref, sp)
-            if rc != _lib.QC_OK:
-                raise RuntimeError(f"qc_plant_step_batch failed ({rc}): {_lib.last_error()}")
-
-        return launch
+        return self._launcher("qc_plant_step_batch", (n, C.byref(io), self._stream_ptr(stream)), (state, grf_body, foot_world, feet, io))
 
     def plant_step(self, state, grf_body, foot_world, dt, feet=None, stream=None):
         """One step of the plant the controller itself assumes (qc_plant_step_batch, include/qc_balance.h): a single rigid body
@@ -403,55 +435,24 @@ class BalanceController:
         steps 0, k, 2k, ... - device tensors, no synchronisation.  certify_every=k launches the KKT certificate (certify_batch's
         summary, default tolerances) after the solve of steps 0, k, 2k, ... and returns `out["certificates"]`, a list of (step,
         summary clone); None (the default) launches exactly what it always did."""
-        import torch
-
         if batch.get("joint_q") is not None or batch.get("feet") is None:
             raise ValueError("rollout: the plant is a single rigid body - the batch carries `feet`, not joint_q")
         steps = int(steps)
         if steps < 0:
             raise ValueError("rollout: steps must be >= 0")
         n = batch["x"].shape[0]
-        dev = torch.device("cuda", self.device)
         state = {k: batch[k] for k in ("Rwb", "x", "xdot", "w")}
-        out = {"grf_body": torch.zeros((n, 12), dtype=torch.float64, device=dev),
-               "status": torch.full((n,), -1, dtype=torch.int32, device=dev)}
-        # the working sets ping-pong between two arrays: a solve never reads the array it writes
-        sets = [torch.zeros((n,), dtype=torch.int32, device=dev) for _ in range(2)] if warm else []
-        solves = []
-        if warm:
-            cold, _ = self.plan_batch(batch, None, dict(out, active_set=sets[0]), want_active_set=True, stream=stream)
-            a, _ = self.plan_batch(batch, sets[0], dict(out, active_set=sets[1]), want_active_set=True, stream=stream)
-            b, _ = self.plan_batch(batch, sets[1], dict(out, active_set=sets[0]), want_active_set=True, stream=stream)
-            solves = [cold, a, b]
-        else:
-            solves = [self.plan_batch(batch, None, out, stream=stream)[0]]
-        step = self.plan_plant(state, out["grf_body"], foot_world, dt, batch["feet"], stream)
+        r = _RolloutPlans(self, "rollout", batch, n, warm, lambda first, w, o: self.plan_batch(batch, w, o, want_active_set=warm, stream=stream)[0],
+                          certify_every, stream)
+        step = self.plan_plant(state, r.out["grf_body"], foot_world, dt, batch["feet"], stream)
         history = [] if record_every else None
-        certify, cert, certificates = self._plan_rollout_certify("rollout", batch, out["grf_body"], certify_every, stream)
         for k in range(steps):
             if history is not None and k % int(record_every) == 0:
                 history.append((k, {name: batch[name].clone() for name in ("Rwb", "x", "xdot", "w", "feet")}))
-            solves[0 if (k == 0 or not warm) else 1 + (k - 1) % 2]()
-            if certify is not None and k % int(certify_every) == 0:
-                certify()
-                certificates.append((k, cert["summary"].clone()))
+            r.solve(k)
+            r.certify(k)
             step()
-        if warm and steps > 0:
-            out["active_set"] = sets[steps % 2 == 0]  # step 0 wrote sets[0], step 1 sets[1], step 2 sets[0], ...
-        if history is not None:
-            out["history"] = history
-        if certificates is not None:
-            out["certificates"] = certificates
-        return state, out
-
-    def _plan_rollout_certify(self, who, batch, grf_body, certify_every, stream):
-        """(launch, outputs, list) of the certificate a rollout launches every `certify_every` steps, or (None, None, None)."""
-        if certify_every is None:
-            return None, None, None
-        if int(certify_every) < 1:
-            raise ValueError(f"{who}: certify_every must be >= 1")
-        launch, cert = self.plan_certify(batch, grf_body, want=(), summary=True, stream=stream)
-        return launch, cert, []
+        return state, r.finish(steps, history)
 
     # ------------------------------------------- closing the loop around the tick
     def _marshal_leg_plant(self, state, joint_tau, dt, leg_inertia, stance, gait_phase, gait_duty, cmd_state, foot_world, flags):
@@ -468,11 +469,8 @@ class BalanceController:
                    ("cmd_state", cmd_state, COMMANDER_STATE_DTYPE.itemsize, torch.uint8, False),
                    ("foot_world", foot_world, 12, torch.float64, False), ("flags", flags, 1, torch.int32, False)]
         for name, t, k, dtype, required in arrays:
-            if t is None and not required:
-                continue
-            if t is None or t.dtype != dtype or not t.is_contiguous() or t.device != dev or t.numel() != n * k:
-                raise ValueError(f"{name}: need contiguous {dtype} [{n},{k}] on {dev}")
-            setattr(io, name, t.data_ptr() if n else None)
+            if _check_tensor(name, t, n, k, dtype, dev, required):
+                setattr(io, name, t.data_ptr() if n else None)
         _fill(io.leg_inertia, np.broadcast_to(np.asarray(leg_inertia, dtype=np.float64), (3,)), 3, "leg_inertia")
         io.dt = float(dt)
         return n, io
@@ -480,19 +478,9 @@ class BalanceController:
     def plan_leg_plant(self, state, joint_tau, dt, leg_inertia, stance=None, gait_phase=None, gait_duty=None, cmd_state=None,
                        foot_world=None, flags=None, stream=None):
         """leg_plant_step() marshalled once: returns `launch`, one qc_leg_plant_step_batch call on tensors that are updated in place."""
-        import torch
-
         n, io = self._marshal_leg_plant(state, joint_tau, dt, leg_inertia, stance, gait_phase, gait_duty, cmd_state, foot_world, flags)
-        s = stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.device))
-        fn, h, sp, io_ref = self._lib.qc_leg_plant_step_batch, self._h, C.c_void_p(s.cuda_stream), C.byref(io)
         keep = (state, joint_tau, stance, gait_phase, gait_duty, cmd_state, foot_world, flags, io)
-
-        def launch(_keep=keep):
-            rc = fn(h, n, io_ref, sp)
-            if rc != _lib.QC_OK:
-                raise RuntimeError(f"qc_leg_plant_step_batch failed ({rc}): {_lib.last_error()}")
-
-        return launch
+        return self._launcher("qc_leg_plant_step_batch", (n, C.byref(io), self._stream_ptr(stream)), keep)
 
     def leg_plant_step(self, state, joint_tau, dt, leg_inertia, stance=None, gait_phase=None, gait_duty=None, cmd_state=None,
                        foot_world=None, flags=None, stream=None):
@@ -544,59 +532,42 @@ class BalanceController:
             if batch.get("gait_dt") is None:
                 batch["gait_dt"] = torch.empty((n,), dtype=torch.float64, device=dev)
             batch["gait_dt"].fill_(float(dt))
-        out = {"grf_body": torch.zeros((n, 12), dtype=torch.float64, device=dev),
-               "status": torch.full((n,), -1, dtype=torch.int32, device=dev),
-               "joint_tau": torch.zeros((n, 12), dtype=torch.float64, device=dev)}
-        sets = [torch.zeros((n,), dtype=torch.int32, device=dev) for _ in range(2)] if warm else []
-
         # control_batch() takes joint_qdot only together with swing references (swing_state, or swing_pos and swing_vel): a
         # batch without them - all stance - keeps its joint_qdot for the plant alone
         swings = batch.get("swing_state") is not None or batch.get("swing_pos") is not None
         tick_in = batch if (command is not None or swings) else {k: v for k, v in batch.items() if k != "joint_qdot"}
 
-        def plan(cmd, w, o):
-            if cmd is None:
-                return self.plan_batch(tick_in, w, o, want_active_set=warm, want_torques=True, stream=stream)[0]
-            return self.plan_tick(batch, cmd, w, o, want_active_set=warm, stream=stream)[0]
-
         later = None if command is None else {k: v for k, v in command.items() if k != "fresh"}  # `fresh` holds on step 0 only
-        if warm:
-            ticks = [plan(command, None, dict(out, active_set=sets[0])), plan(later, sets[0], dict(out, active_set=sets[1])),
-                     plan(later, sets[1], dict(out, active_set=sets[0]))]
-        else:
-            ticks = [plan(command, None, out), plan(later, None, out)]
+
+        def plan(first, w, o):
+            if command is None:
+                return self.plan_batch(tick_in, w, o, want_active_set=warm, want_torques=True, stream=stream)[0]
+            return self.plan_tick(batch, command if first else later, w, o, want_active_set=warm, stream=stream)[0]
+
+        r = _RolloutPlans(self, "rollout_tick", batch, n, warm, plan, certify_every, stream, torques=True)
+        out = r.out
         foot_world = torch.zeros((n, 12), dtype=torch.float64, device=dev)
         flags = torch.zeros((n,), dtype=torch.int32, device=dev)
         step = self.plan_leg_plant(state, out["joint_tau"], dt, leg_inertia, stance=batch.get("stance"), gait_phase=batch.get("gait_phase"),
                                    gait_duty=batch.get("gait_duty"), cmd_state=None if command is None else command["state"],
                                    foot_world=foot_world, flags=flags, stream=stream)
         history = [] if record_every else None
-        certify, cert, certificates = self._plan_rollout_certify("rollout_tick", batch, out["grf_body"], certify_every, stream)
         for k in range(steps):
             rec = None
             if history is not None and k % int(record_every) == 0:
                 rec = {name: batch[name].clone() for name in names}
                 history.append((k, rec))
-            ticks[0 if k == 0 else ((1 + (k - 1) % 2) if warm else 1)]()
+            r.solve(k)
             if rec is not None:  # what the tick of this step left behind: its outputs and the state it advances
                 rec["tick"] = {name: out[name].clone() for name in ("grf_body", "status", "joint_tau")}
                 rec["tick"].update({name: batch[name].clone() for name in ("gait_phase", "swing_state") if batch.get(name) is not None})
                 if command is not None:
                     rec["tick"]["cmd_state"] = command["state"].clone()
-            if certify is not None and k % int(certify_every) == 0:
-                certify()
-                certificates.append((k, cert["summary"].clone()))
+            r.certify(k)
             step()
             if rec is not None:
                 rec["step"] = {"foot_world": foot_world.clone(), "flags": flags.clone()}
-        if warm and steps > 0:
-            out["active_set"] = sets[steps % 2 == 0]
-        out["foot_world"], out["flags"] = foot_world, flags
-        if history is not None:
-            out["history"] = history
-        if certificates is not None:
-            out["certificates"] = certificates
-        return state, out
+        return state, r.finish(steps, history, foot_world=foot_world, flags=flags)
 
     # ------------------------------------------------------ certifying a batch
     def plan_certify(self, batch, grf_body, act_tol=1e-7, primal_tol=1e-7, stat_tol=1e-8, want=("primal", "stationarity"), summary=True,
@@ -615,16 +586,11 @@ class BalanceController:
         for name, k, dtype in [(f, m, torch.float64) for f, m in _IN_FIELDS] + [("joint_q", 12, torch.float64), ("stance", 4, torch.uint8),
                                                                                ("gait_phase", 4, torch.float64), ("gait_duty", 1, torch.float64)]:
             t = batch.get(name)
-            if t is None:
-                continue  # (what is required is the library's decision: qc_certify_batch names what is missing)
-            if t.dtype != dtype or not t.is_contiguous() or t.device != dev or t.numel() != n * k:
-                raise ValueError(f"{name}: need contiguous {dtype} [{n},{k}] on {dev}")
-            setattr(bi, name, t.data_ptr())
+            if _check_tensor(name, t, n, k, dtype, dev, False):  # (what is required is the library's decision: qc_certify_batch names what is missing)
+                setattr(bi, name, t.data_ptr())
         io = _lib.QcCertifyIo()
         self._lib.qc_default_certify(C.byref(io))
-        if grf_body is not None:
-            if grf_body.dtype != torch.float64 or not grf_body.is_contiguous() or grf_body.device != dev or grf_body.numel() != n * 12:
-                raise ValueError(f"grf_body: need contiguous float64 [{n},12] on {dev}")
+        if _check_tensor("grf_body", grf_body, n, 12, torch.float64, dev, False, "float64"):
             io.grf_body = grf_body.data_ptr()
         io.act_tol, io.primal_tol, io.stat_tol = float(act_tol), float(primal_tol), float(stat_tol)
         unknown = [w for w in want if w not in _CERTIFY_OUTPUTS]
@@ -644,16 +610,8 @@ class BalanceController:
                 raise ValueError(f"out['{name}']: need contiguous {dtype} with {int(np.prod(size))} elements on {dev}")
             res[name] = t
             setattr(io, name, t.data_ptr())
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
-        fn, h, sp, bi_ref, io_ref = self._lib.qc_certify_batch, self._h, C.c_void_p(s.cuda_stream), C.byref(bi), C.byref(io)
-        keep = (batch, grf_body, res, bi, io)
-
-        def launch(_keep=keep):
-            rc = fn(h, n, bi_ref, io_ref, sp)
-            if rc != _lib.QC_OK:
-                raise RuntimeError(f"qc_certify_batch failed ({rc}): {_lib.last_error()}")
-
-        return launch, res
+        args = (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
+        return self._launcher("qc_certify_batch", args, (batch, grf_body, res, bi, io)), res
 
     def certify_batch(self, batch, grf_body, act_tol=1e-7, primal_tol=1e-7, stat_tol=1e-8, want=("primal", "stationarity"), summary=True,
                       out=None, stream=None):

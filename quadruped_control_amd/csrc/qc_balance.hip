@@ -582,7 +582,7 @@ QC_DEV uint32_t assemble_from_state(CParams& P, const BatchIn& in, long robot, i
   if (in.stance) {
     stance = ((sw & 0xFFu) ? 1u : 0u) | ((sw & 0xFF00u) ? 2u : 0u) | ((sw & 0xFF0000u) ? 4u : 0u) | ((sw & 0xFF000000u) ? 8u : 0u);
   } else if (in.gait_phase && run) {
-    // GaitScheduler::phase(), gait.cpp:125-134 (almost_equal = |a-b| < 1e-12, math/numerics.cpp:18-21)
+    // GaitScheduler::phase(): phase_in_stance (qc_device.hpp)
     const double duty = in.gait_duty ? X.duty : P.stance_phase;
     stance = 0;
     double phs[4];
@@ -603,12 +603,7 @@ QC_DEV uint32_t assemble_from_state(CParams& P, const BatchIn& in, long robot, i
       }
     }
 #pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const double ph = phs[i];
-      const bool ge0 = (ph > 0.0) || (fabs(ph) < 1.0e-12);
-      const bool le = (ph < duty) || (fabs(ph - duty) < 1.0e-12);
-      stance |= (ge0 && le) ? (1u << i) : 0u;
-    }
+    for (int i = 0; i < 4; i++) stance |= phase_in_stance(phs[i], duty) ? (1u << i) : 0u;
   }
   if (KIN && in.swing_state && run)  // (bits 12-15: has_traj per leg, for the torque pass; only member 0's word reaches the stock: the group's bits are or-ed)
     stance |= (uint32_t)group_or<GG, STR>((int)swing_plan<FPL, STR>(P, in, robot, foot0, stance, S, W, X)) << 12;

@@ -6,7 +6,7 @@
 // Per robot, from the SAME qc_batch_in the solve read (conventions of qc_plant.hpp):
 //   r_i, b         wrench_from_state on fetch_state's loads: r_i = Rwb p_i (p_i from `feet`, or from joint_q by leg_fk), b from the PD
 //                  law, angle_axis_total and Iw - the solver's own functions, nothing restated
-//   contact mask   plant_contact_mask: `stance` bytes, else the phase rule on gait_phase AS IT IS NOW (gait_duty or the handle's
+//   contact mask   load_contact_mask: `stance` bytes, else the phase rule on gait_phase AS IT IS NOW (gait_duty or the handle's
 //                  value), else all stance.  gait_dt, swing_* and swing_state are ignored: no clock is advanced, `in` is never written.
 //   f_i            = -Rwb grf_body_i (world frame, all four feet: a non-zero swing force enters A f and W f, as in kkt_batch.py)
 //   grad           = 2 (A^T S (A f - b) + W f) with the handle's full 6x6 S and full 12x12 W whatever form the solver ran:
@@ -32,7 +32,7 @@
 // ordinary vector stores - no atomics; certify_summary_kernel, one workgroup, finishes them.  Maxima, minima and integer sums are
 // exact, so the summary is deterministic and bit-equal to reducing the per-robot arrays.
 #pragma once
-#include "qc_leg_plant.hpp"
+#include "qc_device.hpp"
 
 namespace qc {
 
@@ -116,14 +116,7 @@ __global__ __launch_bounds__(CERTIFY_BLOCK) void certify_kernel(const DevParams*
     fetch_state<4, KIN>(in, i, 0, S, fp);
 #pragma unroll
     for (int l = 0; l < 4; l++) load3(a.grf_body, 4 * i + l, gb[l]);
-    double ph[4] = {0.0, 0.0, 0.0, 0.0};
-    if (in.gait_phase && !in.stance) {
-#pragma unroll
-      for (int l = 0; l < 4; l++) ph[l] = in.gait_phase[4 * i + l];
-    }
-    const uint32_t sw = in.stance ? *reinterpret_cast<const uint32_t*>(in.stance + 4 * i) : 0u;
-    const double duty = in.gait_duty ? in.gait_duty[i] : P.stance_phase;
-    const uint32_t mask = plant_contact_mask(in.stance != nullptr, sw, in.gait_phase != nullptr, ph, duty, true);
+    const uint32_t mask = load_contact_mask(&P, in.stance, in.gait_phase, in.gait_duty, i, true);
     Wrench<4> W;
     (void)wrench_from_state<4, KIN>(P, S, fp, 0, W);
 

@@ -382,6 +382,56 @@ QC_DEV void load9(const double* __restrict__ p, long idx, double (&v)[9]) {
 #pragma unroll
   for (int k = 0; k < 9; k++) v[k] = q[k];
 }
+QC_DEV void store3(double* p, long idx, const double (&v)[3]) {
+  double* q = p + 3 * idx;
+  q[0] = v[0]; q[1] = v[1]; q[2] = v[2];
+}
+QC_DEV void mat_vec(const double (&m)[9], const double (&v)[3], double (&o)[3]) {  // o = m v
+#pragma unroll
+  for (int r = 0; r < 3; r++) o[r] = m[3 * r] * v[0] + m[3 * r + 1] * v[1] + m[3 * r + 2] * v[2];
+}
+QC_DEV void mat_t_vec(const double (&m)[9], const double (&v)[3], double (&o)[3]) {  // o = m^T v
+#pragma unroll
+  for (int c = 0; c < 3; c++) o[c] = m[c] * v[0] + m[3 + c] * v[1] + m[6 + c] * v[2];
+}
+QC_DEV void cross3(const double (&a)[3], const double (&b)[3], double (&o)[3]) {
+  o[0] = a[1] * b[2] - a[2] * b[1];
+  o[1] = a[2] * b[0] - a[0] * b[2];
+  o[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// The contact rule, in one place.  phase_in_stance: GaitScheduler::phase(), gait.cpp:125-134, on one leg's phase - 0 <= ph <= duty
+// with the 1e-12 slack of almost_equal (math/numerics.cpp:18-21) on both ends.
+QC_DEV bool phase_in_stance(double ph, double duty) {
+  const bool ge0 = (ph > 0.0) || (fabs(ph) < 1.0e-12);
+  const bool le = (ph < duty) || (fabs(ph - duty) < 1.0e-12);
+  return ge0 && le;
+}
+// The contact mask (bits 0-3), resolved as qc_control_batch resolves it: `sw` = the robot's four LegState bytes if has_stance; else
+// phase_in_stance on the four phases if has_phase; else make_stance_gait().  `running` false (a commander state whose gait_running
+// is 0) is all stance whatever the rest.
+QC_DEV uint32_t contact_mask(bool has_stance, uint32_t sw, bool has_phase, const double (&ph)[4], double duty, bool running) {
+  if (!running) return 0xFu;
+  if (has_stance) return ((sw & 0xFFu) ? 1u : 0u) | ((sw & 0xFF00u) ? 2u : 0u) | ((sw & 0xFF0000u) ? 4u : 0u) | ((sw & 0xFF000000u) ? 8u : 0u);
+  if (!has_phase) return 0xFu;
+  uint32_t m = 0;
+#pragma unroll
+  for (int i = 0; i < 4; i++) m |= phase_in_stance(ph[i], duty) ? (1u << i) : 0u;
+  return m;
+}
+// ... and its inputs, gathered for robot i from the optional arrays of a call (the phases as they are now: no clock is advanced;
+// the default duty is the handle's).  P is a pointer, not a reference: a reference argument is known to be dereferenceable, and
+// the compiler then hoists the load of stance_phase out of its branch - other code than the kernels had with the rule spelled out.
+QC_DEV uint32_t load_contact_mask(CParams* P, const uint8_t* stance, const double* gait_phase, const double* gait_duty, long i, bool running) {
+  double ph[4] = {0.0, 0.0, 0.0, 0.0};
+  if (gait_phase && !stance) {
+#pragma unroll
+    for (int l = 0; l < 4; l++) ph[l] = gait_phase[4 * i + l];
+  }
+  const uint32_t sw = stance ? *reinterpret_cast<const uint32_t*>(stance + 4 * i) : 0u;
+  const double duty = gait_duty ? gait_duty[i] : P->stance_phase;
+  return contact_mask(stance != nullptr, sw, gait_phase != nullptr, ph, duty, running);
+}
 
 // Leg kinematics of the reference (kinematics.cpp), one leg: sines/cosines of
 // (t1, t2, t2+t3) from three sincos calls and the angle-addition formulas.

@@ -32,6 +32,20 @@ inline int fail(int code, const std::string& msg) {
   return code;
 }
 
+// Two refusals every versioned entry point shares (`who`: the entry point, for the message).  A struct of another revision of the
+// header: `got` is its struct_size field, `want` this library's sizeof, `default_fn_name` the function that sets the field.
+inline int check_struct_size(const char* who, const char* struct_name, const char* default_fn_name, size_t got, size_t want) {
+  if (got == want) return QC_OK;
+  char msg[192];
+  std::snprintf(msg, sizeof(msg), "%s: %s.struct_size is %zu, this library's %s has %zu B (%s sets it)", who, struct_name, got, struct_name, want, default_fn_name);
+  return fail(QC_ERR_INVALID, msg);
+}
+// One lane per robot in blocks of `block`: a launch holds fewer than 2^32 threads.
+inline int check_one_launch(const char* who, size_t n, int block) {
+  if (n > (size_t)0xFFFFFF * (size_t)block) return fail(QC_ERR_INVALID, std::string(who) + ": n is beyond one launch");
+  return QC_OK;
+}
+
 // What qc_create derived from its parameters about the formulation, and the overrides of qc_set_tuning.
 struct Tuning {
   bool diag_w = false;   // W diagonal -> 6x6 formulation
@@ -425,12 +439,7 @@ inline int check_swing_gait_args(const qc_batch_in* in, const qc_batch_out* out)
 // qc_tick_batch
 inline int check_tick_args(const qc_handle* h, const qc_batch_in* in, const qc_command_in* cmd, const qc_batch_out* out) {
   if (!h || !in || !cmd || !out) return fail(QC_ERR_INVALID, "qc_tick_batch: null argument");
-  if (cmd->struct_size != sizeof(qc_command_in)) {
-    char msg[160];
-    std::snprintf(msg, sizeof(msg), "qc_tick_batch: qc_command_in.struct_size is %zu, this library's qc_command_in has %zu B (qc_default_command sets it)",
-                  cmd->struct_size, sizeof(qc_command_in));
-    return fail(QC_ERR_INVALID, msg);
-  }
+  if (const int rc = check_struct_size("qc_tick_batch", "qc_command_in", "qc_default_command", cmd->struct_size, sizeof(qc_command_in)); rc != QC_OK) return rc;
   if (!in->Rwb || !in->x || !in->xdot || !in->w || !in->joint_q || !in->joint_qdot || !in->gait_phase || !in->gait_dt || !in->swing_state)
     return fail(QC_ERR_INVALID, "qc_tick_batch: the complete tick needs Rwb, x, xdot, w, joint_q, joint_qdot, gait_phase, gait_dt and swing_state");
   if (in->Rwb_d || in->x_d || in->xdot_d || in->w_d)
@@ -448,45 +457,39 @@ inline int check_tick_args(const qc_handle* h, const qc_batch_in* in, const qc_c
 // ---------------------------------------------------------------- qc_plant_step_batch
 // Ib^-1 for the plant step.  qc_create reads Ib only through the wrench law, which needs nothing of it, and keeps accepting what it
 // always has; a rigid body that is to be integrated needs a finite, symmetric positive definite inertia, so the plant refuses the rest.
-inline int plant_inertia_inverse(const double* Ib, double* Ib_inv) {
+inline int plant_inertia_inverse(const double* Ib, double* Ib_inv, const char* who = "qc_plant_step_batch") {
+  const auto bad = [who](const char* what) { return fail(QC_ERR_INVALID, std::string(who) + what); };
   for (int i = 0; i < 9; i++)
-    if (!std::isfinite(Ib[i])) return fail(QC_ERR_INVALID, "qc_plant_step_batch: the handle's Ib is not finite");
+    if (!std::isfinite(Ib[i])) return bad(": the handle's Ib is not finite");
   for (int i = 0; i < 3; i++)
     for (int j = 0; j < i; j++)
-      if (std::fabs(Ib[3 * i + j] - Ib[3 * j + i]) > 1e-12 * (std::fabs(Ib[3 * i + i]) + std::fabs(Ib[3 * j + j])))
-        return fail(QC_ERR_INVALID, "qc_plant_step_batch: the handle's Ib is not symmetric");
-  if (!spd_inverse(Ib, 3, Ib_inv)) return fail(QC_ERR_INVALID, "qc_plant_step_batch: the handle's Ib is not positive definite");
+      if (std::fabs(Ib[3 * i + j] - Ib[3 * j + i]) > 1e-12 * (std::fabs(Ib[3 * i + i]) + std::fabs(Ib[3 * j + j]))) return bad(": the handle's Ib is not symmetric");
+  if (!spd_inverse(Ib, 3, Ib_inv)) return bad(": the handle's Ib is not positive definite");
   for (int i = 0; i < 9; i++)  // (an Ib whose entries are finite but whose inverse overflows)
-    if (!std::isfinite(Ib_inv[i])) return fail(QC_ERR_INVALID, "qc_plant_step_batch: the handle's Ib is not positive definite");
+    if (!std::isfinite(Ib_inv[i])) return bad(": the handle's Ib is not positive definite");
   return QC_OK;
 }
 
-// the kernel's constants from the handle's mass and Ib and the call's dt
-inline int plant_constants(double mass, const double* Ib, double dt, PlantArgs& a) {
-  if (!std::isfinite(mass) || !(mass > 0.0)) return fail(QC_ERR_INVALID, "qc_plant_step_batch: the handle's mass is not finite and > 0");
-  if (const int rc = plant_inertia_inverse(Ib, a.Ib_inv); rc != QC_OK) return rc;
-  a.mass = mass;
-  std::memcpy(a.Ib, Ib, sizeof(a.Ib));
-  a.g = PLANT_G;
-  a.dt = dt;
+// the body's constants of both plant kernels from the handle's mass and Ib and the call's dt, refused under the entry point's name
+inline int body_constants(const char* who, double mass, const double* Ib, double dt, BodyConst& b) {
+  if (!std::isfinite(mass) || !(mass > 0.0)) return fail(QC_ERR_INVALID, std::string(who) + ": the handle's mass is not finite and > 0");
+  if (const int rc = plant_inertia_inverse(Ib, b.Ib_inv, who); rc != QC_OK) return rc;
+  b.mass = mass;
+  std::memcpy(b.Ib, Ib, sizeof(b.Ib));
+  b.g = PLANT_G;
+  b.dt = dt;
   return QC_OK;
 }
+inline int plant_constants(double mass, const double* Ib, double dt, PlantArgs& a) { return body_constants("qc_plant_step_batch", mass, Ib, dt, a); }
 
 inline int check_plant_args(const qc_handle* h, size_t n, const qc_plant_io* io) {
   if (!h || !io) return fail(QC_ERR_INVALID, "qc_plant_step_batch: null argument");
-  if (io->struct_size != sizeof(qc_plant_io)) {
-    char msg[160];
-    std::snprintf(msg, sizeof(msg), "qc_plant_step_batch: qc_plant_io.struct_size is %zu, this library's qc_plant_io has %zu B (qc_default_plant sets it)",
-                  io->struct_size, sizeof(qc_plant_io));
-    return fail(QC_ERR_INVALID, msg);
-  }
+  if (const int rc = check_struct_size("qc_plant_step_batch", "qc_plant_io", "qc_default_plant", io->struct_size, sizeof(qc_plant_io)); rc != QC_OK) return rc;
   if (!std::isfinite(io->dt) || !(io->dt > 0.0)) return fail(QC_ERR_INVALID, "qc_plant_step_batch: dt must be finite and > 0");
   if (n == 0) return QC_OK;
   if (!io->Rwb || !io->x || !io->xdot || !io->w) return fail(QC_ERR_INVALID, "qc_plant_step_batch: the state arrays Rwb, x, xdot and w are required");
   if (!io->grf_body || !io->foot_world) return fail(QC_ERR_INVALID, "qc_plant_step_batch: grf_body and foot_world are required");
-  // one lane per robot in blocks of PLANT_BLOCK: a launch holds fewer than 2^32 threads
-  if (n > (size_t)0xFFFFFF * PLANT_BLOCK) return fail(QC_ERR_INVALID, "qc_plant_step_batch: n is beyond one launch");
-  return QC_OK;
+  return check_one_launch("qc_plant_step_batch", n, PLANT_BLOCK);
 }
 
 // ---------------------------------------------------------------- qc_leg_plant_step_batch
@@ -494,12 +497,8 @@ inline int check_plant_args(const qc_handle* h, size_t n, const qc_plant_io* io)
 // leg_plant_constants, through the plant's own checks, when the constants are derived.)
 inline int check_leg_plant_args(const qc_handle* h, size_t n, const qc_leg_plant_io* io) {
   if (!h || !io) return fail(QC_ERR_INVALID, "qc_leg_plant_step_batch: null argument");
-  if (io->struct_size != sizeof(qc_leg_plant_io)) {
-    char msg[192];
-    std::snprintf(msg, sizeof(msg), "qc_leg_plant_step_batch: qc_leg_plant_io.struct_size is %zu, this library's qc_leg_plant_io has %zu B (qc_default_leg_plant sets it)",
-                  io->struct_size, sizeof(qc_leg_plant_io));
-    return fail(QC_ERR_INVALID, msg);
-  }
+  if (const int rc = check_struct_size("qc_leg_plant_step_batch", "qc_leg_plant_io", "qc_default_leg_plant", io->struct_size, sizeof(qc_leg_plant_io)); rc != QC_OK)
+    return rc;
   if (!std::isfinite(io->dt) || !(io->dt > 0.0)) return fail(QC_ERR_INVALID, "qc_leg_plant_step_batch: dt must be finite and > 0");
   for (int k = 0; k < 3; k++)
     if (!std::isfinite(io->leg_inertia[k]) || !(io->leg_inertia[k] > 0.0))
@@ -507,21 +506,12 @@ inline int check_leg_plant_args(const qc_handle* h, size_t n, const qc_leg_plant
   if (n == 0) return QC_OK;
   if (!io->Rwb || !io->x || !io->xdot || !io->w) return fail(QC_ERR_INVALID, "qc_leg_plant_step_batch: the state arrays Rwb, x, xdot and w are required");
   if (!io->joint_q || !io->joint_qdot || !io->joint_tau) return fail(QC_ERR_INVALID, "qc_leg_plant_step_batch: joint_q, joint_qdot and joint_tau are required");
-  // one lane per robot in blocks of LEG_PLANT_BLOCK: a launch holds fewer than 2^32 threads
-  if (n > (size_t)0xFFFFFF * LEG_PLANT_BLOCK) return fail(QC_ERR_INVALID, "qc_leg_plant_step_batch: n is beyond one launch");
-  return QC_OK;
+  return check_one_launch("qc_leg_plant_step_batch", n, LEG_PLANT_BLOCK);
 }
 
-// the kernel's constants: the body's as plant_constants derives (and refuses) them, under this entry point's name
+// the kernel's constants: the body's (body_constants, under this entry point's name) and the call's leg inertia
 inline int leg_plant_constants(double mass, const double* Ib, const qc_leg_plant_io* io, LegPlantArgs& a) {
-  PlantArgs b;
-  if (const int rc = plant_constants(mass, Ib, io->dt, b); rc != QC_OK) {
-    const std::string::size_type colon = g_err.find(':');  // "qc_plant_step_batch: the handle's ..."
-    return fail(rc, "qc_leg_plant_step_batch" + (colon == std::string::npos ? ": " + g_err : g_err.substr(colon)));
-  }
-  a.mass = b.mass; a.g = b.g; a.dt = b.dt;
-  std::memcpy(a.Ib, b.Ib, sizeof(a.Ib));
-  std::memcpy(a.Ib_inv, b.Ib_inv, sizeof(a.Ib_inv));
+  if (const int rc = body_constants("qc_leg_plant_step_batch", mass, Ib, io->dt, a); rc != QC_OK) return rc;
   for (int k = 0; k < 3; k++) a.leg_inertia[k] = io->leg_inertia[k];
   return QC_OK;
 }
@@ -530,12 +520,7 @@ inline int leg_plant_constants(double mass, const double* Ib, const qc_leg_plant
 // The argument check of the certificate: what is wrong with the call itself (message prefix "qc_certify_batch:").
 inline int check_certify_args(const qc_handle* h, size_t n, const qc_batch_in* in, const qc_certify_io* io) {
   if (!h || !in || !io) return fail(QC_ERR_INVALID, "qc_certify_batch: null argument");
-  if (io->struct_size != sizeof(qc_certify_io)) {
-    char msg[192];
-    std::snprintf(msg, sizeof(msg), "qc_certify_batch: qc_certify_io.struct_size is %zu, this library's qc_certify_io has %zu B (qc_default_certify sets it)",
-                  io->struct_size, sizeof(qc_certify_io));
-    return fail(QC_ERR_INVALID, msg);
-  }
+  if (const int rc = check_struct_size("qc_certify_batch", "qc_certify_io", "qc_default_certify", io->struct_size, sizeof(qc_certify_io)); rc != QC_OK) return rc;
   const double tols[3] = {io->act_tol, io->primal_tol, io->stat_tol};
   for (int k = 0; k < 3; k++)
     if (!std::isfinite(tols[k]) || !(tols[k] >= 0.0)) return fail(QC_ERR_INVALID, "qc_certify_batch: act_tol, primal_tol and stat_tol must be finite and >= 0");
@@ -547,8 +532,7 @@ inline int check_certify_args(const qc_handle* h, size_t n, const qc_batch_in* i
     return fail(QC_ERR_INVALID, "qc_certify_batch: the state arrays Rwb, Rwb_d, x, xdot, w, x_d, xdot_d and w_d are required (commander mode is out of scope)");
   if (!in->feet && !in->joint_q) return fail(QC_ERR_INVALID, "qc_certify_batch: feet or joint_q is required");
   // (robot indices times 12 stay far inside 64 bits; the bound is the plant steps': fewer than 2^32 lanes of CERTIFY_BLOCK-wide groups)
-  if (n > (size_t)0xFFFFFF * CERTIFY_BLOCK) return fail(QC_ERR_INVALID, "qc_certify_batch: n is beyond one launch");
-  return QC_OK;
+  return check_one_launch("qc_certify_batch", n, CERTIFY_BLOCK);
 }
 
 // workgroups of certify_kernel for n robots: one wave each, capped at the handle's partial buffer (the waves stride beyond it)

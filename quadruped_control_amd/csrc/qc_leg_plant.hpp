@@ -3,13 +3,13 @@
 // (include/qc_balance.h) alternates with the tick on one stream, so stand, gait start and twist tracking run without a host in the loop.
 //
 // Per robot (conventions of qc_plant.hpp; leg kinematics of qc_device.hpp):
-//   contact mask   plant_contact_mask below: the rule of qc_control_batch on the phases as the tick left them
+//   contact mask   contact_mask (qc_device.hpp): the rule of qc_control_batch on the phases as the tick left them
 //   stance leg i   t = leg_trig(q_i), p_i = leg_fk, J_i (the nine entries of swing_pd);  g_i = J_i^-T tau_i is the force the torque
 //                  encodes (the tick wrote tau = J^T grf_body, clamped: the clamp is the plant's actuator limit), by the cofactors
 //                  inside swing_pd's band lo <= |det| <= 2^52 and by pinv3_apply on J^T outside it (flags bit i);
 //                  f_i = -Rwb g_i acts at r_i = Rwb p_i, and the foot is pinned at c_i = x + r_i
 //   swing leg      no force on the body; three decoupled double integrators: qdot' = qdot + dt (tau / I), q' = q + dt qdot'
-//   body           leg_plant_body_step: exactly plant_step_kernel's arithmetic from fs, tau on (a copy, see there)
+//   body           rigid_body_step (qc_plant.hpp): plant_step_kernel's own step from fs, tau on
 //   stance leg, after the body has moved:  p_i' = Rwb'^T (c_i - x'),  q_i' = leg_ik(p_i'),  qdot_i' = wrap_PI(q_i' - q_i) / dt;
 //                  a clamped (d > 1) or NaN (d < -1) leg sets flags bit 4 + i
 // There is no ground, no leg mass, no gravity on the joints ("Closing the loop around the tick").
@@ -26,9 +26,8 @@
 
 namespace qc {
 
-// The kernel's argument struct (by value in the kernarg segment).  mass ... dt: as PlantArgs.
-struct LegPlantArgs {
-  double mass, Ib[9], Ib_inv[9], g, dt;
+// The kernel's argument struct (by value in the kernarg segment).
+struct LegPlantArgs : BodyConst {
   double leg_inertia[3];
   double *Rwb, *x, *xdot, *w;     // IN/OUT
   double *joint_q, *joint_qdot;   // [n][4][3] IN/OUT
@@ -47,23 +46,6 @@ constexpr int LEG_PLANT_BLOCK = 256;
 
 #ifdef __HIPCC__
 namespace qc {
-
-// The contact mask of the step (bits 0-3), resolved as qc_control_batch resolves it: `sw` = the robot's four LegState bytes if
-// has_stance; else GaitScheduler::phase() (gait.cpp:125-134) on the four phases with the 1e-12 slack of almost_equal if
-// has_phase; else make_stance_gait().  `running` false (a commander state whose gait_running is 0) is all stance whatever the rest.
-QC_DEV uint32_t plant_contact_mask(bool has_stance, uint32_t sw, bool has_phase, const double (&ph)[4], double duty, bool running) {
-  if (!running) return 0xFu;
-  if (has_stance) return ((sw & 0xFFu) ? 1u : 0u) | ((sw & 0xFF00u) ? 2u : 0u) | ((sw & 0xFF0000u) ? 4u : 0u) | ((sw & 0xFF000000u) ? 8u : 0u);
-  if (!has_phase) return 0xFu;
-  uint32_t m = 0;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const bool ge0 = (ph[i] > 0.0) || (fabs(ph[i]) < 1.0e-12);
-    const bool le = (ph[i] < duty) || (fabs(ph[i] - duty) < 1.0e-12);
-    m |= (ge0 && le) ? (1u << i) : 0u;
-  }
-  return m;
-}
 
 // legInverseKinematics (kinematics.cpp:117-160), stand-alone and reference-shaped (the evaluation leg_swing_torque keeps as its
 // fallback): unsigned link lengths, d > 1 clamped to 1, d < -1 not clamped (sqrt of a negative number: q2 and q3 NaN, as in the
@@ -109,50 +91,6 @@ QC_DEV bool leg_force_from_torque(const LegGeom& lg, const LegTrig& t, const dou
   return true;
 }
 
-// The body's step from the net force fs and the net moment tau about the centre of mass (world frame): plant_step_kernel's
-// arithmetic from there on, line for line - gyroscopic term, Ib^-1, semi-implicit Euler, Rodrigues without 1 - cos.  A COPY, not a
-// shared function: with the tail factored out of plant_step_kernel its gfx950 assembly no longer matched the parent's (the same
-// instructions with commuted operands in eleven v_mul_f64 / v_add_f64), so that kernel is left as it is.  x, v, w are updated,
-// tau is consumed, Rn = Rwb'.
-QC_DEV void leg_plant_body_step(const LegPlantArgs& a, const double (&R)[9], double (&x)[3], double (&v)[3], double (&w)[3], const double (&fs)[3],
-                                double (&tau)[3], double (&Rn)[9]) {
-  // wdot = R Ib^-1 R^T (tau - w x (R Ib R^T w))
-  double wb[3], Iwb[3], Iw_w[3], gyro[3], nb[3], Inb[3], wdot[3];
-  mat_t_vec(R, w, wb);
-  mat_vec(a.Ib, wb, Iwb);
-  mat_vec(R, Iwb, Iw_w);
-  cross3(w, Iw_w, gyro);
-#pragma unroll
-  for (int k = 0; k < 3; k++) tau[k] -= gyro[k];
-  mat_t_vec(R, tau, nb);
-  mat_vec(a.Ib_inv, nb, Inb);
-  mat_vec(R, Inb, wdot);
-  // semi-implicit Euler
-  double phi[3];
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    const double acc = fs[k] / a.mass - (k == 2 ? a.g : 0.0);
-    v[k] += a.dt * acc;
-    x[k] += a.dt * v[k];
-    w[k] += a.dt * wdot[k];
-    phi[k] = a.dt * w[k];
-  }
-  // Rwb' = Exp(phi) Rwb
-  const double xx = phi[0] * phi[0], yy = phi[1] * phi[1], zz = phi[2] * phi[2];
-  const double h = 0.5 * sqrt(xx + yy + zz);
-  double sh, ch;
-  sincos_joint(h, &sh, &ch);
-  const double sc = h > 0.0 ? sh / h : 1.0;  // sin(h) / h, 1 at h = 0 (NaN stays NaN through ch)
-  const double A = sc * ch, B = 0.5 * (sc * sc);
-  const double E[9] = {1.0 - B * (yy + zz),                 B * (phi[0] * phi[1]) - A * phi[2], B * (phi[0] * phi[2]) + A * phi[1],
-                       B * (phi[0] * phi[1]) + A * phi[2], 1.0 - B * (xx + zz),                 B * (phi[1] * phi[2]) - A * phi[0],
-                       B * (phi[0] * phi[2]) - A * phi[1], B * (phi[1] * phi[2]) + A * phi[0], 1.0 - B * (xx + yy)};
-#pragma unroll
-  for (int r = 0; r < 3; r++)
-#pragma unroll
-    for (int c = 0; c < 3; c++) Rn[3 * r + c] = E[3 * r] * R[c] + E[3 * r + 1] * R[3 + c] + E[3 * r + 2] * R[6 + c];
-}
-
 __global__ __launch_bounds__(LEG_PLANT_BLOCK) void leg_plant_step_kernel(const DevParams* __restrict__ Pg, const long n, const LegPlantArgs a) {
   const long i = (long)blockIdx.x * LEG_PLANT_BLOCK + threadIdx.x;
   if (i >= n) return;  // tail lanes
@@ -168,6 +106,8 @@ __global__ __launch_bounds__(LEG_PLANT_BLOCK) void leg_plant_step_kernel(const D
     load3(a.joint_qdot, 4 * i + l, qd[l]);
     load3(a.joint_tau, 4 * i + l, tq[l]);
   }
+  // (the gather of load_contact_mask, spelled out: through the function this kernel's scalar code came out differently - its pointers
+  // are fetched from the kernarg segment up front - and 0.1 to 0.3 us slower at 65 536 and 262 144 robots; this text compiles to the parent's)
   double ph[4] = {0.0, 0.0, 0.0, 0.0};
   if (a.gait_phase && !a.stance) {
 #pragma unroll
@@ -176,7 +116,7 @@ __global__ __launch_bounds__(LEG_PLANT_BLOCK) void leg_plant_step_kernel(const D
   const uint32_t sw = a.stance ? *reinterpret_cast<const uint32_t*>(a.stance + 4 * i) : 0u;
   const double duty = a.gait_duty ? a.gait_duty[i] : P.stance_phase;
   const bool running = a.cmd_state ? a.cmd_state[i].gait_running != 0 : true;
-  const uint32_t mask = plant_contact_mask(a.stance != nullptr, sw, a.gait_phase != nullptr, ph, duty, running);
+  const uint32_t mask = contact_mask(a.stance != nullptr, sw, a.gait_phase != nullptr, ph, duty, running);
 
   // force pass: net force and moment about the centre of mass (world frame); swing joints integrate
   double fs[3] = {0.0, 0.0, 0.0}, tau[3] = {0.0, 0.0, 0.0};
@@ -212,7 +152,7 @@ __global__ __launch_bounds__(LEG_PLANT_BLOCK) void leg_plant_step_kernel(const D
     }
   }
   double Rn[9];
-  leg_plant_body_step(a, R, x, v, w, fs, tau, Rn);
+  rigid_body_step(a, R, x, v, w, fs, tau, Rn);
   // IK pass: the stance feet stay where they were
 #pragma unroll
   for (int l = 0; l < 4; l++) {

@@ -24,14 +24,24 @@
 // only its own rows, so the state arrays are updated in place and an output may be the same array as an input of the same
 // layout.  Like the solver kernels it reads the per-argument arrays directly (load3 / load9): a wave's loads of one array cover
 // one contiguous span (64 x 24, 72 or 96 B) and consume every fetched line; 336 B in and 240 B out per robot.
+//
+// The body's step from the net force and moment on is ONE function, rigid_body_step, which this kernel and leg_plant_step_kernel
+// (qc_leg_plant.hpp) both call.  The rule for touching it: a change must leave both kernels' RESULTS (bit for bit, against the parent
+// build, on the tests' pools) and RESOURCES (registers, scratch, occupancy, instruction counts: profiles/*_kernel_resources.txt) as
+// they are - not their assembly text.  Register numbers, instruction order and the operand order of a commutative IEEE multiply or
+// add may move: commuting the operands changes no finite result, no infinity and no NaN-ness.
 #pragma once
 #include "qc_device.hpp"
 
 namespace qc {
 
-// The kernel's argument struct (by value in the kernarg segment; not part of DevParams).
-struct PlantArgs {
+// The constants of the body: the base of both plant kernels' argument structs (by value in the kernarg segment; not part of
+// DevParams), so they lead both layouts and read a.mass ... a.dt in either.
+struct BodyConst {
   double mass, Ib[9], Ib_inv[9], g, dt;
+};
+
+struct PlantArgs : BodyConst {
   double *Rwb, *x, *xdot, *w;  // [n][9], [n][3] x 3, IN/OUT
   const double *grf_body, *foot_world;  // [n][4][3]
   double* feet;  // [n][4][3] OUT or nullptr
@@ -45,22 +55,45 @@ constexpr int PLANT_BLOCK = 256;
 #ifdef __HIPCC__
 namespace qc {
 
-QC_DEV void store3(double* p, long idx, const double (&v)[3]) {
-  double* q = p + 3 * idx;
-  q[0] = v[0]; q[1] = v[1]; q[2] = v[2];
-}
-QC_DEV void mat_vec(const double (&m)[9], const double (&v)[3], double (&o)[3]) {  // o = m v
+// The body's step from the net force fs and the net moment tau about the centre of mass (world frame): gyroscopic term, Ib^-1,
+// semi-implicit Euler, Rodrigues without 1 - cos.  x, v, w are updated, tau is consumed, Rn = Rwb'.
+QC_DEV void rigid_body_step(const BodyConst& b, const double (&R)[9], double (&x)[3], double (&v)[3], double (&w)[3], const double (&fs)[3],
+                            double (&tau)[3], double (&Rn)[9]) {
+  // wdot = R Ib^-1 R^T (tau - w x (R Ib R^T w))
+  double wb[3], Iwb[3], Iw_w[3], gyro[3], nb[3], Inb[3], wdot[3];
+  mat_t_vec(R, w, wb);
+  mat_vec(b.Ib, wb, Iwb);
+  mat_vec(R, Iwb, Iw_w);
+  cross3(w, Iw_w, gyro);
 #pragma unroll
-  for (int r = 0; r < 3; r++) o[r] = m[3 * r] * v[0] + m[3 * r + 1] * v[1] + m[3 * r + 2] * v[2];
-}
-QC_DEV void mat_t_vec(const double (&m)[9], const double (&v)[3], double (&o)[3]) {  // o = m^T v
+  for (int k = 0; k < 3; k++) tau[k] -= gyro[k];
+  mat_t_vec(R, tau, nb);
+  mat_vec(b.Ib_inv, nb, Inb);
+  mat_vec(R, Inb, wdot);
+  // semi-implicit Euler
+  double phi[3];
 #pragma unroll
-  for (int c = 0; c < 3; c++) o[c] = m[c] * v[0] + m[3 + c] * v[1] + m[6 + c] * v[2];
-}
-QC_DEV void cross3(const double (&a)[3], const double (&b)[3], double (&o)[3]) {
-  o[0] = a[1] * b[2] - a[2] * b[1];
-  o[1] = a[2] * b[0] - a[0] * b[2];
-  o[2] = a[0] * b[1] - a[1] * b[0];
+  for (int k = 0; k < 3; k++) {
+    const double acc = fs[k] / b.mass - (k == 2 ? b.g : 0.0);
+    v[k] += b.dt * acc;
+    x[k] += b.dt * v[k];
+    w[k] += b.dt * wdot[k];
+    phi[k] = b.dt * w[k];
+  }
+  // Rwb' = Exp(phi) Rwb
+  const double xx = phi[0] * phi[0], yy = phi[1] * phi[1], zz = phi[2] * phi[2];
+  const double h = 0.5 * sqrt(xx + yy + zz);
+  double sh, ch;
+  sincos_joint(h, &sh, &ch);
+  const double sc = h > 0.0 ? sh / h : 1.0;  // sin(h) / h, 1 at h = 0 (NaN stays NaN through ch)
+  const double A = sc * ch, B = 0.5 * (sc * sc);
+  const double E[9] = {1.0 - B * (yy + zz),                 B * (phi[0] * phi[1]) - A * phi[2], B * (phi[0] * phi[2]) + A * phi[1],
+                       B * (phi[0] * phi[1]) + A * phi[2], 1.0 - B * (xx + zz),                 B * (phi[1] * phi[2]) - A * phi[0],
+                       B * (phi[0] * phi[2]) - A * phi[1], B * (phi[1] * phi[2]) + A * phi[0], 1.0 - B * (xx + yy)};
+#pragma unroll
+  for (int r = 0; r < 3; r++)
+#pragma unroll
+    for (int c = 0; c < 3; c++) Rn[3 * r + c] = E[3 * r] * R[c] + E[3 * r + 1] * R[3 + c] + E[3 * r + 2] * R[6 + c];
 }
 
 __global__ __launch_bounds__(PLANT_BLOCK) void plant_step_kernel(const long n, const PlantArgs a) {
@@ -94,42 +127,8 @@ __global__ __launch_bounds__(PLANT_BLOCK) void plant_step_kernel(const long n, c
       tau[k] += m[k];
     }
   }
-  // wdot = R Ib^-1 R^T (tau - w x (R Ib R^T w))
-  double wb[3], Iwb[3], Iw_w[3], gyro[3], nb[3], Inb[3], wdot[3];
-  mat_t_vec(R, w, wb);
-  mat_vec(a.Ib, wb, Iwb);
-  mat_vec(R, Iwb, Iw_w);
-  cross3(w, Iw_w, gyro);
-#pragma unroll
-  for (int k = 0; k < 3; k++) tau[k] -= gyro[k];
-  mat_t_vec(R, tau, nb);
-  mat_vec(a.Ib_inv, nb, Inb);
-  mat_vec(R, Inb, wdot);
-  // semi-implicit Euler
-  double phi[3];
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    const double acc = fs[k] / a.mass - (k == 2 ? a.g : 0.0);
-    v[k] += a.dt * acc;
-    x[k] += a.dt * v[k];
-    w[k] += a.dt * wdot[k];
-    phi[k] = a.dt * w[k];
-  }
-  // Rwb' = Exp(phi) Rwb
-  const double xx = phi[0] * phi[0], yy = phi[1] * phi[1], zz = phi[2] * phi[2];
-  const double h = 0.5 * sqrt(xx + yy + zz);
-  double sh, ch;
-  sincos_joint(h, &sh, &ch);
-  const double sc = h > 0.0 ? sh / h : 1.0;  // sin(h) / h, 1 at h = 0 (NaN stays NaN through ch)
-  const double A = sc * ch, B = 0.5 * (sc * sc);
-  const double E[9] = {1.0 - B * (yy + zz),                 B * (phi[0] * phi[1]) - A * phi[2], B * (phi[0] * phi[2]) + A * phi[1],
-                       B * (phi[0] * phi[1]) + A * phi[2], 1.0 - B * (xx + zz),                 B * (phi[1] * phi[2]) - A * phi[0],
-                       B * (phi[0] * phi[2]) - A * phi[1], B * (phi[1] * phi[2]) + A * phi[0], 1.0 - B * (xx + yy)};
   double Rn[9];
-#pragma unroll
-  for (int r = 0; r < 3; r++)
-#pragma unroll
-    for (int c = 0; c < 3; c++) Rn[3 * r + c] = E[3 * r] * R[c] + E[3 * r + 1] * R[3 + c] + E[3 * r + 2] * R[6 + c];
+  rigid_body_step(a, R, x, v, w, fs, tau, Rn);
   // every input of this robot has been read: the outputs may overwrite them
   {
     double* q = a.Rwb + 9 * i;

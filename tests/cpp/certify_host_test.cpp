@@ -8,22 +8,10 @@
 #include <limits>
 #include <string>
 
-#include "../../quadruped_control_amd/csrc/qc_host.hpp"
+#include "host_check.hpp"
 
 using namespace qc;
 
-static long g_checked = 0;
-#define CHECK(cond, ...)                                              \
-  do {                                                                \
-    g_checked++;                                                      \
-    if (!(cond)) {                                                    \
-      std::printf("FAILED %s:%d: %s\n  case: ", __FILE__, __LINE__, #cond); \
-      std::printf(__VA_ARGS__);                                       \
-      std::printf("\n  last error: %s\n", g_err.c_str());             \
-      std::exit(1);                                                   \
-    }                                                                 \
-  } while (0)
-#define CHECK_FAILS(rc, text, ...) CHECK((rc) == QC_ERR_INVALID && g_err == (text), __VA_ARGS__)
 
 static const double kInf = std::numeric_limits<double>::infinity();
 static const double kNan = std::numeric_limits<double>::quiet_NaN();

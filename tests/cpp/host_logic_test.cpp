@@ -9,23 +9,9 @@
 #include <cstdlib>
 #include <string>
 
-#include "../../quadruped_control_amd/csrc/qc_host.hpp"
+#include "host_check.hpp"
 
 using namespace qc;
-
-static long g_checked = 0;
-#define CHECK(cond, ...)                                              \
-  do {                                                                \
-    g_checked++;                                                      \
-    if (!(cond)) {                                                    \
-      std::printf("FAILED %s:%d: %s\n  case: ", __FILE__, __LINE__, #cond); \
-      std::printf(__VA_ARGS__);                                       \
-      std::printf("\n  last error: %s\n", g_err.c_str());             \
-      std::exit(1);                                                   \
-    }                                                                 \
-  } while (0)
-// a call that must fail with this code and exactly this text
-#define CHECK_FAILS(rc, code, text, ...) CHECK((rc) == (code) && g_err == (text), __VA_ARGS__)
 
 // ------------------------------------------------------------------------------------------------ (a) planner sweep
 static const char* const CHUNK_MSG = "qc_set_tuning: a chunk beyond one fill (64 / lanes per robot) asks for more robots than a wave holds";
@@ -64,7 +50,7 @@ static void planner_sweep() {
       const int rc = plan_launch(form, n, kin != 0, warm != 0, t, cus, resident, &lp);
       // outcome: the chunk error exactly when the chunk is beyond one fill, otherwise a kernel of the list
       if (chunk > 64 / G) {
-        CHECK_FAILS(rc, QC_ERR_INVALID, CHUNK_MSG, CASE);
+        CHECK_FAILS(rc, CHUNK_MSG, CASE);
         continue;
       }
       CHECK(rc == QC_OK, CASE);
@@ -211,27 +197,26 @@ static void derived_constants() {
   p.mass = 0.0; p.fzmin = 130.0; p.max_iter = QC_MAX_ITER_LIMIT + 1; p.mu = 5000.0; p.S[1] += 1e-3; p.W[13 * 4] = 0.0; p.W[12] *= 2;
   p.S[6 * 4 + 5] = p.S[6 * 5 + 4] = 20.0;  // symmetric and indefinite
   const qc_params ok = general_params();
-  CHECK_FAILS(check_params(&p), QC_ERR_INVALID, "qc_create: mu and mass must be > 0", "mass = 0");
+  CHECK_FAILS(check_params(&p), "qc_create: mu and mass must be > 0", "mass = 0");
   p.mass = ok.mass; p.mu = -1.0;
-  CHECK_FAILS(check_params(&p), QC_ERR_INVALID, "qc_create: mu and mass must be > 0", "mu < 0");
+  CHECK_FAILS(check_params(&p), "qc_create: mu and mass must be > 0", "mu < 0");
   p.mu = 5000.0;
-  CHECK_FAILS(check_params(&p), QC_ERR_INVALID, "qc_create: need 0 <= fzmin <= fzmax", "fzmin > fzmax");
+  CHECK_FAILS(check_params(&p), "qc_create: need 0 <= fzmin <= fzmax", "fzmin > fzmax");
   p.fzmin = -1.0;
-  CHECK_FAILS(check_params(&p), QC_ERR_INVALID, "qc_create: need 0 <= fzmin <= fzmax", "fzmin < 0");
+  CHECK_FAILS(check_params(&p), "qc_create: need 0 <= fzmin <= fzmax", "fzmin < 0");
   p.fzmin = ok.fzmin;
-  CHECK_FAILS(check_params(&p), QC_ERR_INVALID, "qc_create: max_iter must be <= 65535", "max_iter 65536");
+  CHECK_FAILS(check_params(&p), "qc_create: max_iter must be <= 65535", "max_iter 65536");
   p.max_iter = QC_MAX_ITER_LIMIT;
-  CHECK_FAILS(check_params(&p), QC_ERR_INVALID,
-              "qc_create: need 2 * mu * fzmax < 1e6 (the +-1e6 sides of the reference's cone rows, balance_controller.cpp:296-301, are not carried)", "2 mu fzmax = 1.2e6");
+  CHECK_FAILS(check_params(&p), "qc_create: need 2 * mu * fzmax < 1e6 (the +-1e6 sides of the reference's cone rows, balance_controller.cpp:296-301, are not carried)", "2 mu fzmax = 1.2e6");
   p.mu = ok.mu;
-  CHECK_FAILS(check_params(&p), QC_ERR_INVALID, "qc_create: S must be symmetric", "S[0][1] != S[1][0]");
+  CHECK_FAILS(check_params(&p), "qc_create: S must be symmetric", "S[0][1] != S[1][0]");
   p.S[1] = ok.S[1];
-  CHECK_FAILS(check_params(&p), QC_ERR_INVALID, "qc_create: W must be positive definite", "W[4][4] = 0");
+  CHECK_FAILS(check_params(&p), "qc_create: W must be positive definite", "W[4][4] = 0");
   p.W[13 * 4] = ok.W[13 * 4];
-  CHECK_FAILS(check_params(&p), QC_ERR_INVALID, "qc_create: W must be symmetric", "W[1][0] != W[0][1]");
+  CHECK_FAILS(check_params(&p), "qc_create: W must be symmetric", "W[1][0] != W[0][1]");
   p.W[12] = ok.W[12];
   CHECK(check_params(&p) == QC_OK, "an indefinite symmetric S passes the device-free checks");
-  CHECK_FAILS(derive_params(&p, d, t), QC_ERR_INVALID, "qc_create: S must be positive definite", "indefinite S");
+  CHECK_FAILS(derive_params(&p, d, t), "qc_create: S must be positive definite", "indefinite S");
   p.S[6 * 4 + 5] = p.S[6 * 5 + 4] = ok.S[6 * 4 + 5];
   CHECK(check_params(&p) == QC_OK && derive_params(&p, d, t) == QC_OK && d.max_iter == QC_MAX_ITER_LIMIT, "mended parameters");
 }
@@ -272,10 +257,10 @@ static void tuning() {
   Tuning t;
   bool upload = false;
   CHECK(derive_params(&p, d, t) == QC_OK, "cheetah");
-  CHECK_FAILS(set_tuning(t, d, "bogus", 1, &upload), QC_ERR_INVALID, "qc_set_tuning: unknown key 'bogus'", "unknown key");
-  CHECK_FAILS(set_tuning(t, d, "one_fill", 0, &upload), QC_ERR_INVALID, "qc_set_tuning: one_fill = 0 asked for the persistent-wave kernels, which were removed", "one_fill 0");
-  CHECK_FAILS(set_tuning(t, d, "max_iter", QC_MAX_ITER_LIMIT + 1, &upload), QC_ERR_INVALID, "qc_set_tuning: max_iter must be <= 65535", "max_iter 65536");
-  CHECK_FAILS(set_tuning(t, d, "group", 3, &upload), QC_ERR_INVALID, "qc_set_tuning: group is 0 (heuristic), 1, 2 or 4", "group 3");
+  CHECK_FAILS(set_tuning(t, d, "bogus", 1, &upload), "qc_set_tuning: unknown key 'bogus'", "unknown key");
+  CHECK_FAILS(set_tuning(t, d, "one_fill", 0, &upload), "qc_set_tuning: one_fill = 0 asked for the persistent-wave kernels, which were removed", "one_fill 0");
+  CHECK_FAILS(set_tuning(t, d, "max_iter", QC_MAX_ITER_LIMIT + 1, &upload), "qc_set_tuning: max_iter must be <= 65535", "max_iter 65536");
+  CHECK_FAILS(set_tuning(t, d, "group", 3, &upload), "qc_set_tuning: group is 0 (heuristic), 1, 2 or 4", "group 3");
   CHECK(d.max_iter == 150 && t.group_override == 0, "a refused call changes nothing");
   // the probe and the cap restore what qc_create was given
   CHECK(set_tuning(t, d, "probe_batch_load", 1, &upload) == QC_OK && upload && d.max_iter == 0 && t.probing, "probe on");
@@ -314,9 +299,9 @@ static void argument_checks() {
     const char* who = first ? "qc_control_batch" : "qc_control_batch_host";
     const auto msg = [who](const char* what) { return std::string(who) + what; };
     CHECK(check_batch_args(who, h, 5, &in_ok, &out_ok, first) == QC_OK, "%s: the smallest valid call", who);
-    CHECK_FAILS(check_batch_args(who, nullptr, 5, &in_ok, &out_ok, first), QC_ERR_INVALID, msg(": null argument"), "%s: no handle", who);
-    CHECK_FAILS(check_batch_args(who, h, 5, nullptr, &out_ok, first), QC_ERR_INVALID, msg(": null argument"), "%s: no in", who);
-    CHECK_FAILS(check_batch_args(who, h, 5, &in_ok, nullptr, first), QC_ERR_INVALID, msg(": null argument"), "%s: no out", who);
+    CHECK_FAILS(check_batch_args(who, nullptr, 5, &in_ok, &out_ok, first), msg(": null argument"), "%s: no handle", who);
+    CHECK_FAILS(check_batch_args(who, h, 5, nullptr, &out_ok, first), msg(": null argument"), "%s: no in", who);
+    CHECK_FAILS(check_batch_args(who, h, 5, &in_ok, nullptr, first), msg(": null argument"), "%s: no out", who);
     const qc_batch_in none{};
     const qc_batch_out nothing{};
     CHECK(check_batch_args(who, h, 0, &none, &nothing, first) == QC_OK, "%s: an empty batch needs no arrays", who);
@@ -325,7 +310,7 @@ static void argument_checks() {
     for (int i = 0; i < 9; i++) {
       qc_batch_in in = in_ok;
       in.*required[i] = nullptr;
-      CHECK_FAILS(check_batch_args(who, h, 5, &in, &out_ok, first), QC_ERR_INVALID, msg(": null input array"), "%s: required array %d missing", who, i);
+      CHECK_FAILS(check_batch_args(who, h, 5, &in, &out_ok, first), msg(": null input array"), "%s: required array %d missing", who, i);
       if (i == 8) {  // joint_q stands in for feet
         in.joint_q = a;
         CHECK(check_batch_args(who, h, 5, &in, &out_ok, first) == QC_OK, "%s: joint_q instead of feet", who);
@@ -333,16 +318,16 @@ static void argument_checks() {
     }
     qc_batch_out out = out_ok;
     out.grf_body = nullptr;
-    CHECK_FAILS(check_batch_args(who, h, 5, &in_ok, &out, first), QC_ERR_INVALID, msg(": grf_body and status are required"), "%s: no grf_body", who);
+    CHECK_FAILS(check_batch_args(who, h, 5, &in_ok, &out, first), msg(": grf_body and status are required"), "%s: no grf_body", who);
     out = out_ok;
     out.status = nullptr;
-    CHECK_FAILS(check_batch_args(who, h, 5, &in_ok, &out, first), QC_ERR_INVALID, msg(": grf_body and status are required"), "%s: no status", who);
+    CHECK_FAILS(check_batch_args(who, h, 5, &in_ok, &out, first), msg(": grf_body and status are required"), "%s: no status", who);
     out = out_ok;
     out.joint_tau = a;
-    CHECK_FAILS(check_batch_args(who, h, 5, &in_ok, &out, first), QC_ERR_INVALID, msg(": joint_tau needs joint_q"), "%s: joint_tau alone", who);
+    CHECK_FAILS(check_batch_args(who, h, 5, &in_ok, &out, first), msg(": joint_tau needs joint_q"), "%s: joint_tau alone", who);
     // both at once: each entry point keeps its own order
     out.status = nullptr;
-    CHECK_FAILS(check_batch_args(who, h, 5, &in_ok, &out, first), QC_ERR_INVALID, msg(first ? ": grf_body and status are required" : ": joint_tau needs joint_q"),
+    CHECK_FAILS(check_batch_args(who, h, 5, &in_ok, &out, first), msg(first ? ": grf_body and status are required" : ": joint_tau needs joint_q"),
                 "%s: joint_tau alone and no status", who);
   }
   // qc_control_batch: the swing and gait arrays that go together
@@ -361,39 +346,39 @@ static void argument_checks() {
       qc_batch_in one = in_ok, two = in;
       one.*three[i] = a;
       two.*three[i] = nullptr;
-      CHECK_FAILS(check_swing_gait_args(&one, &out_ok), QC_ERR_INVALID, together, "swing array %d alone", i);
-      CHECK_FAILS(check_swing_gait_args(&two, &out), QC_ERR_INVALID, together, "swing array %d missing", i);
+      CHECK_FAILS(check_swing_gait_args(&one, &out_ok), together, "swing array %d alone", i);
+      CHECK_FAILS(check_swing_gait_args(&two, &out), together, "swing array %d missing", i);
     }
     qc_batch_in bad = in;
     bad.joint_q = nullptr;
-    CHECK_FAILS(check_swing_gait_args(&bad, &out), QC_ERR_INVALID, together, "swing arrays without joint_q");
-    CHECK_FAILS(check_swing_gait_args(&in, &out_ok), QC_ERR_INVALID, together, "swing arrays without joint_tau");
+    CHECK_FAILS(check_swing_gait_args(&bad, &out), together, "swing arrays without joint_q");
+    CHECK_FAILS(check_swing_gait_args(&in, &out_ok), together, "swing arrays without joint_tau");
     bad = in_ok;
     bad.gait_dt = a;
-    CHECK_FAILS(check_swing_gait_args(&bad, &out_ok), QC_ERR_INVALID, clock, "gait_dt without gait_phase");
+    CHECK_FAILS(check_swing_gait_args(&bad, &out_ok), clock, "gait_dt without gait_phase");
     bad.gait_phase = a;
     CHECK(check_swing_gait_args(&bad, &out_ok) == QC_OK, "gait_dt with gait_phase");
     bad.stance = reinterpret_cast<const uint8_t*>(a);
-    CHECK_FAILS(check_swing_gait_args(&bad, &out_ok), QC_ERR_INVALID, clock, "gait_dt with stance");
+    CHECK_FAILS(check_swing_gait_args(&bad, &out_ok), clock, "gait_dt with stance");
     qc_batch_in st = in_ok;
     st.swing_state = ss; st.joint_q = st.joint_qdot = st.gait_phase = a;
     CHECK(check_swing_gait_args(&st, &out) == QC_OK, "the smallest stateful tick");
-    CHECK_FAILS(check_swing_gait_args(&st, &out_ok), QC_ERR_INVALID, stateful, "swing_state without joint_tau");
+    CHECK_FAILS(check_swing_gait_args(&st, &out_ok), stateful, "swing_state without joint_tau");
     const double* qc_batch_in::*const needs[] = {&qc_batch_in::joint_q, &qc_batch_in::joint_qdot};
     for (int i = 0; i < 2; i++) {
       bad = st;
       bad.*needs[i] = nullptr;
-      CHECK_FAILS(check_swing_gait_args(&bad, &out), QC_ERR_INVALID, stateful, "swing_state without array %d", i);
+      CHECK_FAILS(check_swing_gait_args(&bad, &out), stateful, "swing_state without array %d", i);
     }
     bad = st;
     bad.gait_phase = nullptr;
-    CHECK_FAILS(check_swing_gait_args(&bad, &out), QC_ERR_INVALID, stateful, "swing_state without gait_phase");
+    CHECK_FAILS(check_swing_gait_args(&bad, &out), stateful, "swing_state without gait_phase");
     bad = st;
     bad.swing_pos = a;
-    CHECK_FAILS(check_swing_gait_args(&bad, &out), QC_ERR_INVALID, stateful, "swing_state with swing_pos");
+    CHECK_FAILS(check_swing_gait_args(&bad, &out), stateful, "swing_state with swing_pos");
     bad = st;
     bad.swing_vel = a;
-    CHECK_FAILS(check_swing_gait_args(&bad, &out), QC_ERR_INVALID, stateful, "swing_state with swing_vel");
+    CHECK_FAILS(check_swing_gait_args(&bad, &out), stateful, "swing_state with swing_vel");
   }
   // qc_tick_batch
   {
@@ -409,16 +394,16 @@ static void argument_checks() {
     cmd.stand_height = 0.26; cmd.stand_tol = 0.005; cmd.cmd_dt = 0.001;
     CHECK(check_tick_args(h, &in, &cmd, &out) == QC_OK, "the smallest valid tick");
     const char* const null_arg = "qc_tick_batch: null argument";
-    CHECK_FAILS(check_tick_args(nullptr, &in, &cmd, &out), QC_ERR_INVALID, null_arg, "no handle");
-    CHECK_FAILS(check_tick_args(h, nullptr, &cmd, &out), QC_ERR_INVALID, null_arg, "no in");
-    CHECK_FAILS(check_tick_args(h, &in, nullptr, &out), QC_ERR_INVALID, null_arg, "no cmd");
-    CHECK_FAILS(check_tick_args(h, &in, &cmd, nullptr), QC_ERR_INVALID, null_arg, "no out");
+    CHECK_FAILS(check_tick_args(nullptr, &in, &cmd, &out), null_arg, "no handle");
+    CHECK_FAILS(check_tick_args(h, nullptr, &cmd, &out), null_arg, "no in");
+    CHECK_FAILS(check_tick_args(h, &in, nullptr, &out), null_arg, "no cmd");
+    CHECK_FAILS(check_tick_args(h, &in, &cmd, nullptr), null_arg, "no out");
     qc_command_in c = cmd;
     c.struct_size = sizeof(qc_command_in) - 8;
     char text[160];
     std::snprintf(text, sizeof(text), "qc_tick_batch: qc_command_in.struct_size is %zu, this library's qc_command_in has %zu B (qc_default_command sets it)",
                   sizeof(qc_command_in) - 8, sizeof(qc_command_in));
-    CHECK_FAILS(check_tick_args(h, &in, &c, &out), QC_ERR_INVALID, text, "struct_size of another revision");
+    CHECK_FAILS(check_tick_args(h, &in, &c, &out), text, "struct_size of another revision");
     const char* const needs = "qc_tick_batch: the complete tick needs Rwb, x, xdot, w, joint_q, joint_qdot, gait_phase, gait_dt and swing_state";
     const double* qc_batch_in::*const required[] = {&qc_batch_in::Rwb, &qc_batch_in::x, &qc_batch_in::xdot, &qc_batch_in::w,
                                                     &qc_batch_in::joint_q, &qc_batch_in::joint_qdot, &qc_batch_in::gait_dt};
@@ -426,47 +411,69 @@ static void argument_checks() {
     for (int i = 0; i < 7; i++) {
       bad = in;
       bad.*required[i] = nullptr;
-      CHECK_FAILS(check_tick_args(h, &bad, &cmd, &out), QC_ERR_INVALID, needs, "required array %d missing", i);
+      CHECK_FAILS(check_tick_args(h, &bad, &cmd, &out), needs, "required array %d missing", i);
     }
     bad = in; bad.gait_phase = nullptr;
-    CHECK_FAILS(check_tick_args(h, &bad, &cmd, &out), QC_ERR_INVALID, needs, "no gait_phase");
+    CHECK_FAILS(check_tick_args(h, &bad, &cmd, &out), needs, "no gait_phase");
     bad = in; bad.swing_state = nullptr;
-    CHECK_FAILS(check_tick_args(h, &bad, &cmd, &out), QC_ERR_INVALID, needs, "no swing_state");
+    CHECK_FAILS(check_tick_args(h, &bad, &cmd, &out), needs, "no swing_state");
     const char* const desired = "qc_tick_batch: Rwb_d, x_d, xdot_d and w_d must be NULL (the desired state lives in qc_command_in.state)";
     const double* qc_batch_in::*const des[] = {&qc_batch_in::Rwb_d, &qc_batch_in::x_d, &qc_batch_in::xdot_d, &qc_batch_in::w_d};
     for (int i = 0; i < 4; i++) {
       bad = in;
       bad.*des[i] = a;
-      CHECK_FAILS(check_tick_args(h, &bad, &cmd, &out), QC_ERR_INVALID, desired, "desired-state array %d given", i);
+      CHECK_FAILS(check_tick_args(h, &bad, &cmd, &out), desired, "desired-state array %d given", i);
     }
     const char* const made = "qc_tick_batch: stance, swing_pos and swing_vel must be NULL (the gait clock and the planner make them)";
     bad = in; bad.stance = reinterpret_cast<const uint8_t*>(a);
-    CHECK_FAILS(check_tick_args(h, &bad, &cmd, &out), QC_ERR_INVALID, made, "stance given");
+    CHECK_FAILS(check_tick_args(h, &bad, &cmd, &out), made, "stance given");
     bad = in; bad.swing_pos = a;
-    CHECK_FAILS(check_tick_args(h, &bad, &cmd, &out), QC_ERR_INVALID, made, "swing_pos given");
+    CHECK_FAILS(check_tick_args(h, &bad, &cmd, &out), made, "swing_pos given");
     bad = in; bad.swing_vel = a;
-    CHECK_FAILS(check_tick_args(h, &bad, &cmd, &out), QC_ERR_INVALID, made, "swing_vel given");
+    CHECK_FAILS(check_tick_args(h, &bad, &cmd, &out), made, "swing_vel given");
     const char* const outputs = "qc_tick_batch: grf_body, status and joint_tau are required";
     qc_batch_out o = out; o.grf_body = nullptr;
-    CHECK_FAILS(check_tick_args(h, &in, &cmd, &o), QC_ERR_INVALID, outputs, "no grf_body");
+    CHECK_FAILS(check_tick_args(h, &in, &cmd, &o), outputs, "no grf_body");
     o = out; o.status = nullptr;
-    CHECK_FAILS(check_tick_args(h, &in, &cmd, &o), QC_ERR_INVALID, outputs, "no status");
-    CHECK_FAILS(check_tick_args(h, &in, &cmd, &out_ok), QC_ERR_INVALID, outputs, "no joint_tau");
+    CHECK_FAILS(check_tick_args(h, &in, &cmd, &o), outputs, "no status");
+    CHECK_FAILS(check_tick_args(h, &in, &cmd, &out_ok), outputs, "no joint_tau");
     c = cmd; c.state = nullptr;
-    CHECK_FAILS(check_tick_args(h, &in, &c, &out), QC_ERR_INVALID, "qc_tick_batch: qc_command_in.state is required", "no state");
+    CHECK_FAILS(check_tick_args(h, &in, &c, &out), "qc_tick_batch: qc_command_in.state is required", "no state");
     c = cmd; c.fresh = reinterpret_cast<const uint8_t*>(a);
-    CHECK_FAILS(check_tick_args(h, &in, &c, &out), QC_ERR_INVALID, "qc_tick_batch: qc_command_in.fresh needs twist", "fresh without twist");
+    CHECK_FAILS(check_tick_args(h, &in, &c, &out), "qc_tick_batch: qc_command_in.fresh needs twist", "fresh without twist");
     c.twist = a;
     CHECK(check_tick_args(h, &in, &c, &out) == QC_OK, "fresh with twist");
     const char* const finite = "qc_tick_batch: stand_height, stand_tol (>= 0) and cmd_dt must be finite";
     c = cmd; c.stand_height = INFINITY;
-    CHECK_FAILS(check_tick_args(h, &in, &c, &out), QC_ERR_INVALID, finite, "stand_height inf");
+    CHECK_FAILS(check_tick_args(h, &in, &c, &out), finite, "stand_height inf");
     c = cmd; c.stand_tol = -1e-9;
-    CHECK_FAILS(check_tick_args(h, &in, &c, &out), QC_ERR_INVALID, finite, "stand_tol < 0");
+    CHECK_FAILS(check_tick_args(h, &in, &c, &out), finite, "stand_tol < 0");
     c = cmd; c.stand_tol = INFINITY;
-    CHECK_FAILS(check_tick_args(h, &in, &c, &out), QC_ERR_INVALID, finite, "stand_tol inf");
+    CHECK_FAILS(check_tick_args(h, &in, &c, &out), finite, "stand_tol inf");
     c = cmd; c.cmd_dt = NAN;
-    CHECK_FAILS(check_tick_args(h, &in, &c, &out), QC_ERR_INVALID, finite, "cmd_dt nan");
+    CHECK_FAILS(check_tick_args(h, &in, &c, &out), finite, "cmd_dt nan");
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ (e) the refusals every entry point shares
+static void shared_refusals() {
+  CHECK(check_struct_size("qc_some_batch", "qc_some_io", "qc_default_some", 72, 72) == QC_OK, "the library's own size");
+  for (const size_t got : {(size_t)0, (size_t)64, (size_t)80})
+    for (const char* who : {"qc_some_batch", "qc_certify_batch"}) {
+      char text[192];
+      std::snprintf(text, sizeof(text), "%s: qc_some_io.struct_size is %zu, this library's qc_some_io has 72 B (qc_default_some sets it)", who, got);
+      CHECK_FAILS(check_struct_size(who, "qc_some_io", "qc_default_some", got, 72), text, "%s: struct_size %zu of 72", who, got);
+    }
+  {  // the longest names of the ABI fit the message buffer
+    const char* const text = "qc_leg_plant_step_batch: qc_leg_plant_io.struct_size is 18446744073709551615, this library's qc_leg_plant_io has 144 B (qc_default_leg_plant sets it)";
+    CHECK_FAILS(check_struct_size("qc_leg_plant_step_batch", "qc_leg_plant_io", "qc_default_leg_plant", ~(size_t)0, 144), text, "the largest size_t");
+  }
+  for (const int block : {64, 256}) {
+    const size_t most = (size_t)0xFFFFFF * (size_t)block;
+    CHECK(check_one_launch("qc_some_batch", 0, block) == QC_OK && check_one_launch("qc_some_batch", 1, block) == QC_OK, "small batches, block %d", block);
+    CHECK(check_one_launch("qc_some_batch", most, block) == QC_OK, "the largest launch of block %d", block);
+    CHECK_FAILS(check_one_launch("qc_some_batch", most + 1, block), "qc_some_batch: n is beyond one launch", "one robot more, block %d", block);
+    CHECK_FAILS(check_one_launch("qc_some_batch", ~(size_t)0, block), "qc_some_batch: n is beyond one launch", "the largest size_t, block %d", block);
   }
 }
 
@@ -475,6 +482,7 @@ int main() {
   derived_constants();
   tuning();
   argument_checks();
+  shared_refusals();
   std::printf("host logic ok: %ld checks, %d kernel instantiations\n", g_checked, N_KERNELS);
   return 0;
 }

@@ -8,24 +8,12 @@
 #include <limits>
 #include <string>
 
-#include "../../quadruped_control_amd/csrc/qc_host.hpp"
+#include "host_check.hpp"
 
 using namespace qc;
 
-static long g_checked = 0;
-#define CHECK(cond, ...)                                              \
-  do {                                                                \
-    g_checked++;                                                      \
-    if (!(cond)) {                                                    \
-      std::printf("FAILED %s:%d: %s\n  case: ", __FILE__, __LINE__, #cond); \
-      std::printf(__VA_ARGS__);                                       \
-      std::printf("\n  last error: %s\n", g_err.c_str());             \
-      std::exit(1);                                                   \
-    }                                                                 \
-  } while (0)
 // a call that must fail with QC_ERR_INVALID and a message of qc_plant_step_batch's own
 #define CHECK_REFUSED(rc, ...) CHECK((rc) == QC_ERR_INVALID && g_err.rfind("qc_plant_step_batch:", 0) == 0, __VA_ARGS__)
-#define CHECK_FAILS(rc, text, ...) CHECK((rc) == QC_ERR_INVALID && g_err == (text), __VA_ARGS__)
 
 static const double kInf = std::numeric_limits<double>::infinity();
 static const double kNan = std::numeric_limits<double>::quiet_NaN();
@@ -98,6 +86,26 @@ static void constants() {
     CHECK_FAILS(plant_constants(m, Ib, 0.01, a), "qc_plant_step_batch: the handle's mass is not finite and > 0", "mass %g", m);
   const double zero[9] = {};
   CHECK_REFUSED(plant_constants(9.0, zero, 0.01, a), "zero inertia");
+  // the filler both plant steps share, under whatever name it is given
+  BodyConst b{};
+  CHECK(body_constants("qc_other_batch", 9.0, Ib, 0.002, b) == QC_OK, "the filler itself");
+  CHECK(b.mass == 9.0 && b.g == PLANT_G && b.dt == 0.002, "mass, g, dt");
+  for (int k = 0; k < 9; k++) CHECK(b.Ib[k] == Ib[k] && b.Ib_inv[k] == a.Ib_inv[k], "Ib and Ib^-1, entry %d", k);
+  CHECK_FAILS(body_constants("qc_other_batch", 0.0, Ib, 0.002, b), "qc_other_batch: the handle's mass is not finite and > 0", "mass 0 under another name");
+  CHECK_FAILS(body_constants("qc_other_batch", 9.0, zero, 0.002, b), "qc_other_batch: the handle's Ib is not positive definite", "zero inertia under another name");
+  {
+    const double asym[9] = {1, 0, 0, 0, 1, 0.25, 0, 0, 1}, nan[9] = {1, 0, 0, 0, kNan, 0, 0, 0, 1};
+    CHECK_FAILS(body_constants("qc_other_batch", 9.0, asym, 0.002, b), "qc_other_batch: the handle's Ib is not symmetric", "asymmetric under another name");
+    CHECK_FAILS(body_constants("qc_other_batch", 9.0, nan, 0.002, b), "qc_other_batch: the handle's Ib is not finite", "NaN under another name");
+  }
+  {
+    LegPlantArgs l{};
+    const char *pa = reinterpret_cast<const char*>(&a), *pl = reinterpret_cast<const char*>(&l);
+    CHECK(sizeof(BodyConst) == 21 * 8 && reinterpret_cast<const char*>(static_cast<const BodyConst*>(&a)) == pa &&
+              reinterpret_cast<const char*>(static_cast<const BodyConst*>(&l)) == pl && reinterpret_cast<const char*>(&a.Rwb) - pa == 21 * 8 &&
+              reinterpret_cast<const char*>(&l.leg_inertia) - pl == 21 * 8 && sizeof(PlantArgs) == 28 * 8 && sizeof(LegPlantArgs) == 37 * 8,
+          "the body's constants lead both argument structs, 21 doubles, and the kernarg layouts are the flat ones");
+  }
 }
 
 // ------------------------------------------------------------------------------------------------ (c) check_plant_args

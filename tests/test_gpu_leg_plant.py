@@ -12,13 +12,13 @@ import pytest
 
 from tests import leg_plant_restatement as LR
 from tests import plant_restatement as PR
+from tests.gpu_arrays import SENTINEL, _device_arrays, _sentinel, _tile, _worst_over_bar
 
 pytestmark = pytest.mark.gpu
 EPS = LR.EPS
 SIZES = (1, 63, 64, 65, 257, 4097)
 STATE = LR.STATE
 POOL = 48
-SENTINEL = -7777.25
 DT = 1.0 / 300.0
 INERTIA = (0.02, 0.015, 0.01)
 MODES = ("stance", "phase", "duty", "cmd")
@@ -106,25 +106,6 @@ def _reference(mode):
     return out
 
 
-def _tile(a, n):
-    return np.ascontiguousarray(np.concatenate([a] * -(-n // a.shape[0]), 0)[:n])
-
-
-def _device_arrays(host, n, pad=2):
-    """{name: (whole tensor [n + pad, k], view of its first n rows)}: the rows behind row n - 1 hold a sentinel"""
-    import torch
-
-    out = {}
-    for k, a in host.items():
-        a2 = a.reshape(a.shape[0], -1)
-        sent = SENTINEL if a2.dtype == np.float64 else (0x5A if a2.dtype == np.uint8 else -77)
-        full = np.full((n + pad, a2.shape[1]), sent, dtype=a2.dtype)
-        full[:n] = _tile(a2, n)
-        t = torch.from_numpy(full).cuda()
-        out[k] = (t, t[:n] if a.ndim > 1 else t[:n].reshape(n))
-    return out
-
-
 def _step(ctl, host, n, names, outputs=True):
     """One step over n robots (the pool tiled).  Returns {name: host array [n + 2, k]} of every array after the step."""
     import torch
@@ -144,19 +125,12 @@ def _step(ctl, host, n, names, outputs=True):
 
 
 def _check(got, ref, n, what):
-    worst = {}
-    for k in STATE + ("foot_world",):
-        val, bar = _tile(ref[k][0], n), _tile(ref[k][1], n)
-        err = np.abs(got[k][:n] - val)
-        exact = bar == 0
-        assert np.array_equal(got[k][:n][exact], val[exact]), (what, k)
-        worst[k] = float(np.where(exact, 0.0, err / np.where(exact, 1.0, bar)).max())
+    worst = _worst_over_bar(got, ref, STATE + ("foot_world",), n, what)
     print(f"{what}: worst error / bar {worst}")
     assert max(worst.values()) <= 1.0, (what, worst)
     assert (got["flags"][:n] == 0).all(), what
     for k, a in got.items():
-        sent = SENTINEL if a.dtype == np.float64 else (0x5A if a.dtype == np.uint8 else -77)
-        assert (a[n:] == sent).all(), (what, k)
+        assert (a[n:] == _sentinel(a.dtype)).all(), (what, k)
 
 
 # ------------------------------------------------------------------ 1. one step against the 50-digit restatement
@@ -587,3 +561,54 @@ def test_closed_loop_commander_mode(q):
     b2, _, hist2, final2 = _commander_rollout(q, ctl, n, steps, 0.2)
     _report("0.2 m/s forward", b2, hist2, final2)
     ctl.close()
+
+
+# ------------------------------------------------------------------ 8. one contact rule in three kernels
+def _fma(a, b, c):
+    """round(a b + c), one rounding: what -ffp-contract=on makes of `c + a * b` on the device (float(Fraction) rounds correctly)"""
+    from fractions import Fraction
+
+    return np.array([float(Fraction(x) * Fraction(y) + Fraction(z)) for x, y, z in zip(np.broadcast_to(a, c.shape).ravel(), b.ravel(), c.ravel())]).reshape(c.shape)
+
+
+@pytest.mark.parametrize("own_duty", [False, True])
+def test_one_contact_rule_in_three_kernels(q, ctl, own_duty):
+    """The solve, the leg plant and the certificate resolve the same phases to the same legs.  Robots 0 - 2 of the pool (the edge
+    phases on both sides of the 1e-12 slack; each has one leg in swing, and the C oracle solves all three on the CPU with these
+    three stance legs), tiled to 65, once with the handle's duty and once with gait_duty: control_batch on joint_q and gait_phase
+    (no clock, no swing references) leaves grf_body exactly 0 on precisely the legs the restatement's rule puts in swing and
+    solves every robot; certify_batch marks precisely those legs 0x80; leg_plant_step integrates precisely those legs' joints as
+    double integrators, qdot' = qdot + dt (tau / I), q' = q + dt qdot', to the bit."""
+    import torch
+
+    n, s = 65, _pool()
+    duty = s["gait_duty"][:3] if own_duty else None
+    swing = _tile(~LR.contact_mask(3, gait_phase=s["gait_phase"][:3], gait_duty=duty), n)
+    assert swing[:3].tolist() == [[False, False, False, True], [False, False, True, False], [False, False, False, True]]
+    host = {k: _tile(s[k][:3], n) for k in STATE + ("gait_phase",)}
+    host.update(Rwb_d=host["Rwb"], x_d=host["x"], xdot_d=np.zeros((n, 3)), w_d=np.zeros((n, 3)))
+    if own_duty:
+        host["gait_duty"] = _tile(duty, n)
+    dev = q.to_device(host)
+    batch = {k: v for k, v in dev.items() if k != "joint_qdot"}
+    out = ctl.control_batch(batch, want_torques=True)
+    cert = ctl.certify_batch(batch, out["grf_body"], want=("active",), summary=False)
+    state = {k: dev[k].clone() for k in STATE}
+    foot_world = torch.zeros((n, 12), dtype=torch.float64, device="cuda")
+    flags = torch.full((n,), -1, dtype=torch.int32, device="cuda")
+    ctl.leg_plant_step(state, out["joint_tau"], DT, INERTIA, gait_phase=dev["gait_phase"], gait_duty=dev.get("gait_duty"), foot_world=foot_world, flags=flags)
+    torch.cuda.synchronize()
+    assert np.array_equal(dev["gait_phase"].cpu().numpy(), host["gait_phase"])  # (no clock ran: all three read the same phases)
+    grf = out["grf_body"].cpu().numpy().reshape(n, 4, 3)
+    active = cert["active"].cpu().numpy().reshape(n, 4)
+    tau = out["joint_tau"].cpu().numpy().reshape(n, 4, 3)
+    q0, qd0 = host["joint_q"].reshape(n, 4, 3), host["joint_qdot"].reshape(n, 4, 3)
+    q1 = state["joint_q"].cpu().numpy().reshape(n, 4, 3)
+    qd1 = _fma(DT, tau / np.asarray(INERTIA), qd0)
+    integrated = np.all(q1 == _fma(DT, qd1, q0), axis=2)
+    print(f"own_duty {own_duty}: status {np.unique(out['status'].cpu().numpy())}, zero-force legs {(grf == 0.0).all(axis=2)[:3].tolist()}, "
+          f"0x80 legs {((active & 0x80) != 0)[:3].tolist()}, integrated legs {integrated[:3].tolist()}, flags {np.unique(flags.cpu().numpy())}")
+    assert np.array_equal((grf == 0.0).all(axis=2), swing)
+    assert np.array_equal((active & 0x80) != 0, swing)
+    assert np.array_equal(integrated, swing)
+    assert (out["status"].cpu().numpy() == 0).all()  # QC_SOLVED

@@ -16,13 +16,13 @@ import numpy as np
 import pytest
 
 from tests import plant_restatement as PR
+from tests.gpu_arrays import SENTINEL, _device_arrays, _tile, _worst_over_bar
 
 pytestmark = pytest.mark.gpu
 EPS = PR.EPS
 SIZES = (1, 63, 64, 65, 257, 4097)
 STATE = ("Rwb", "x", "xdot", "w")
 POOL = 257
-SENTINEL = -7777.25
 FEET_XY = np.array([[-0.196, 0.127], [0.196, 0.127], [-0.196, -0.127], [0.196, -0.127]])
 
 
@@ -84,23 +84,6 @@ def _pool_reference(dt):
     return {k: (np.stack([r[k][0] for r in refs]), np.stack([r[k][1] for r in refs])) for k in STATE + ("feet",)}
 
 
-def _tile(a, n):
-    return np.ascontiguousarray(np.concatenate([a] * -(-n // a.shape[0]), 0)[:n])
-
-
-def _device_arrays(host, n, pad=2):
-    """{name: (whole tensor [n + pad, k], view of its first n rows)}: the rows behind row n - 1 hold SENTINEL"""
-    import torch
-
-    out = {}
-    for k, a in host.items():
-        full = np.full((n + pad, a.shape[1]), SENTINEL)
-        full[:n] = _tile(a, n)
-        t = torch.from_numpy(full).cuda()
-        out[k] = (t, t[:n])
-    return out
-
-
 def _step(ctl, host, n, dt, feet="own"):
     """One plant step over n robots (the pool tiled).  feet: "own" (an array of its own), "alias" (written over foot_world) or
     None.  Returns {name: host array [n + 2, k]} of every array after the step, the sentinel rows included."""
@@ -128,14 +111,7 @@ def test_one_step_against_50_digits(ctl, dt):
     assert still.sum() >= 8 and tiny.sum() >= 8 and (~still & ~tiny).sum() >= 100, (still.sum(), tiny.sum())
     for n in SIZES:
         got = _step(ctl, s, n, dt)
-        worst = {}
-        for k in STATE + ("feet",):
-            val, bar = _tile(ref[k][0], n), _tile(ref[k][1], n)
-            err = np.abs(got[k][:n] - val)
-            exact = bar == 0
-            assert np.array_equal(got[k][:n][exact], val[exact]), (n, k)
-            ratio = np.where(exact, 0.0, err / np.where(exact, 1.0, bar))
-            worst[k] = float(ratio.max())
+        worst = _worst_over_bar(got, ref, STATE + ("feet",), n, n)
         print(f"dt {dt} n {n}: worst error / bar {worst}")
         assert max(worst.values()) <= 1.0, (n, worst)
         assert np.array_equal(got["Rwb"][:n][_tile(still, n)], _tile(s["Rwb"], n)[_tile(still, n)])
