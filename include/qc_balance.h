@@ -443,6 +443,47 @@ void qc_default_certify(qc_certify_io* io);
  * joint_q, or n beyond one launch. */
 int qc_certify_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_certify_io* io, void* stream);
 
+/* Sensitivity of a solved batch: the adjoint of the balance QP on the active face of the forces qc_control_batch returned.  Per
+ * robot the solve minimises (A f - b)^T S (A f - b) + f^T W f over the world-frame forces f (12 values) under the pyramid rows
+ * described at qc_certify_batch; A = [I I I I; [r_1]x ... [r_4]x], r_i = Rwb p_i (p_i from `feet`, or from joint_q by the forward
+ * kinematics), b from the PD law, the handle's FULL S (6x6) and W (12x12) whatever formulation the solver ran; H = 2 (A^T S A + W).
+ * Inputs are the SAME qc_batch_in the solve read (contact mask resolved as qc_certify_batch resolves it; gait_dt and the swing
+ * arrays are ignored, `in` is never written), the forces and a cotangent grf_bar on them.
+ *   The face: each stance foot's axes get qc_certify_batch's codes at act_tol (0 none, 1 lower, 2 upper, 3 both), and f = Z y + f0:
+ *     z code != 0: fz is pinned; z code 0: fz is free.  x (or y) code 0: free; code 1 or 2: fx = -mu fz or +mu fz - tied to fz if fz
+ *     is free, pinned otherwise.  A code 3 on any axis of a foot pins the whole foot and sets bit 0 of `flags`: the derivative is
+ *     one-sided there.  Swing feet are pinned.  A failed robot has all-zero forces, so every stance foot of it is pinned and
+ *     flagged and its adjoint is 0.
+ *   f_bar = -Rwb grf_bar (Rwb held fixed);  adjoint z = Z (Z^T H Z)^-1 Z^T f_bar (world frame, 0 in pinned coordinates);
+ *   b_bar = 2 S A z;  r_bar_i = -2 (z_i x v_ang + f_i x q_ang) with v = S (A f - b), q = S A z;  feet_bar_i = Rwb^T r_bar_i, the
+ *   cotangent of the body-frame foot position whether it came from `feet` or from the kinematics of joint_q;
+ *   x_bar, xdot_bar, w_bar, x_d_bar, xdot_d_bar, w_d_bar: b_bar pulled back through the PD law at fixed Rwb and Rwb_d, exactly
+ *   as the library evaluates that law (the kff terms on xdot_d[0], xdot_d[1] and w_d included).
+ * NOT produced: the cotangents of Rwb and Rwb_d - a caller chains them from b_bar, r_bar_i = Rwb feet_bar_i and z (INTEGRATION.md,
+ * "Sensitivity of a solved batch"); the cotangents of mu, fzmin, fzmax and the weights; weak activity - a row whose multiplier is
+ * about 0 counts as active like any other (qc_certify_batch's lambda shows such rows).  Commander mode is out of scope.
+ * The reduced system is solved as a fixed 12x12 LDL^T; a pivot that is not positive and finite sets bit 1 of `flags` and makes
+ * every output of that robot NaN.  Non-finite inputs propagate as NaN; nothing is clamped. */
+typedef struct qc_sensitivity_io {
+  size_t struct_size;        /* = sizeof(qc_sensitivity_io); checked                                                 */
+  const double* grf_body;    /* [n][4][3] qc_batch_out.grf_body                                                      */
+  const double* grf_bar;     /* [n][4][3] cotangent on grf_body                                                      */
+  double act_tol;            /* active-row tolerance, finite and >= 0                                                */
+  double* adjoint;           /* [n][12] z, world frame                                                               */
+  double* b_bar;             /* [n][6]                                                                               */
+  double* feet_bar;          /* [n][4][3] body frame                                                                 */
+  double *x_bar, *xdot_bar, *w_bar, *x_d_bar, *xdot_d_bar, *w_d_bar; /* [n][3] each                                   */
+  int32_t* flags;            /* [n]: bit 0 a foot sits on both rows of an axis (one-sided), bit 1 a bad pivot        */
+} qc_sensitivity_io;
+/* struct_size set, pointers NULL, act_tol = 1e-7. */
+void qc_default_sensitivity(qc_sensitivity_io* io);
+/* Asynchronous on `stream`, no host synchronisation (graph-capturable); n == 0 launches nothing and returns QC_OK.  Every output
+ * is optional; at least one must be given.  QC_ERR_INVALID (message starting with "qc_sensitivity_batch:", nothing launched) for a
+ * null handle, `in` or `io`, a wrong struct_size, an act_tol that is not finite and >= 0, a missing grf_body or grf_bar, no output
+ * requested at all, a missing state array (Rwb, Rwb_d, x, xdot, w, x_d, xdot_d, w_d), neither feet nor joint_q, or n beyond one
+ * launch. */
+int qc_sensitivity_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_io* io, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("QC_LIB_PATH") or os.path.join(_HERE, "libqc_balance.so")  # QC_LIB_PATH: development builds (tools/)
 
 QC_OK = 0
+QC_ERR_INVALID = -1
 QC_ERR_ABI = -4
 ABI_VERSION = 6  # the revision of include/qc_balance.h these ctypes structures were written against
 STATUS_NAMES = {0: "solved", 1: "max_iter", 2: "infeasible", 3: "not_pd"}
@@ -78,6 +79,11 @@ class QcCertifyIo(C.Structure):
                 ("primal", "stationarity", "lambda", "grad", "active", "flags", "summary")]
 
 
+class QcSensitivityIo(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("grf_body", C.c_void_p), ("grf_bar", C.c_void_p), ("act_tol", C.c_double)] + [(k, C.c_void_p) for k in
+                ("adjoint", "b_bar", "feet_bar", "x_bar", "xdot_bar", "w_bar", "x_d_bar", "xdot_d_bar", "w_d_bar", "flags")]
+
+
 class QcLaunchInfo(C.Structure):
     _fields_ = [("lanes_per_robot", C.c_int32), ("mode", C.c_int32), ("form", C.c_int32), ("strategies", C.c_int32),
                 ("chunk", C.c_int64), ("blocks", C.c_int64), ("resident_workgroups", C.c_int64), ("lds_bytes", C.c_int64)]
@@ -87,7 +93,7 @@ EXPORTS = ("qc_create_abi", "qc_destroy", "qc_control_batch", "qc_control_batch_
            "qc_last_error", "qc_kernel_name", "qc_abi_version", "qc_default_kinematics", "qc_set_kinematics", "qc_set_gait", "qc_swing_state_init",
            "qc_set_tuning", "qc_query_launch", "qc_check_abi", "qc_default_command", "qc_commander_state_init", "qc_tick_batch",
            "qc_default_plant", "qc_plant_step_batch", "qc_default_leg_plant", "qc_leg_plant_step_batch",
-           "qc_default_certify", "qc_certify_batch")
+           "qc_default_certify", "qc_certify_batch", "qc_default_sensitivity", "qc_sensitivity_batch")
 
 _lib = None
 
@@ -166,6 +172,10 @@ def load():
     lib.qc_default_certify.restype = None
     lib.qc_certify_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcBatchIn), C.POINTER(QcCertifyIo), C.c_void_p]
     lib.qc_certify_batch.restype = C.c_int
+    lib.qc_default_sensitivity.argtypes = [C.POINTER(QcSensitivityIo)]
+    lib.qc_default_sensitivity.restype = None
+    lib.qc_sensitivity_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcBatchIn), C.POINTER(QcSensitivityIo), C.c_void_p]
+    lib.qc_sensitivity_batch.restype = C.c_int
     # the structures above are hand-written mirrors of the header: a library built from another revision is refused here,
     # before any of them crosses the boundary
     rc = lib.qc_check_abi(ABI_VERSION, C.sizeof(QcParams), C.sizeof(QcBatchIn), C.sizeof(QcBatchOut))

@@ -625,6 +625,69 @@ class BalanceController:
         launch()
         return res
 
+    # ------------------------------------------------------ sensitivity of a solved batch
+    def plan_sensitivity(self, batch, grf_body, grf_bar, want=("adjoint", "b_bar"), act_tol=1e-7, out=None, stream=None):
+        """sensitivity_batch() marshalled once: returns (launch, out), `launch()` being one qc_sensitivity_batch call
+        (graph-capturable) on tensors that are read in place.  Planning launches nothing.  `out`: a dict of tensors to write into
+        instead of new ones (every name in `want`).  A call the library refuses raises ValueError with its message, from launch()."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        sized = [t for t in [batch.get(k) for k, _ in _IN_FIELDS] + [grf_body, grf_bar] if t is not None]
+        if not sized:
+            raise ValueError("sensitivity: the batch holds no state array")
+        n = sized[0].shape[0]  # (a missing array is the library's refusal, not a KeyError here)
+        bi = _lib.QcBatchIn()
+        for name, k, dtype in [(f, m, torch.float64) for f, m in _IN_FIELDS] + [("joint_q", 12, torch.float64), ("stance", 4, torch.uint8),
+                                                                               ("gait_phase", 4, torch.float64), ("gait_duty", 1, torch.float64)]:
+            t = batch.get(name)
+            if _check_tensor(name, t, n, k, dtype, dev, False):
+                setattr(bi, name, t.data_ptr())
+        io = _lib.QcSensitivityIo()
+        self._lib.qc_default_sensitivity(C.byref(io))
+        for name, t in (("grf_body", grf_body), ("grf_bar", grf_bar)):
+            if _check_tensor(name, t, n, 12, torch.float64, dev, False, "float64"):
+                setattr(io, name, t.data_ptr())
+        io.act_tol = float(act_tol)
+        unknown = [w for w in want if w not in _SENSITIVITY_OUTPUTS]
+        if unknown:
+            raise ValueError(f"sensitivity: unknown output(s) {unknown}; want is a subset of {tuple(_SENSITIVITY_OUTPUTS)}")
+        res = {}
+        for name in want:
+            shape, dtype = _SENSITIVITY_OUTPUTS[name][0], getattr(torch, _SENSITIVITY_OUTPUTS[name][1])
+            size = (n,) + shape
+            t = None if out is None else out.get(name)
+            if t is None:
+                if out is not None:
+                    raise ValueError(f"out: '{name}' was asked for but the supplied `out` has no such tensor")
+                t = torch.zeros(size, dtype=dtype, device=dev)
+            elif t.dtype != dtype or not t.is_contiguous() or t.device != dev or t.numel() != int(np.prod(size)):
+                raise ValueError(f"out['{name}']: need contiguous {dtype} with {int(np.prod(size))} elements on {dev}")
+            res[name] = t
+            setattr(io, name, t.data_ptr())
+        fn, h, args = self._lib.qc_sensitivity_batch, self._h, (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
+
+        def launch(_keep=(batch, grf_body, grf_bar, res, bi, io)):
+            rc = fn(h, *args)
+            if rc == _lib.QC_ERR_INVALID:
+                raise ValueError(_lib.last_error())
+            if rc != _lib.QC_OK:
+                raise RuntimeError(f"qc_sensitivity_batch failed ({rc}): {_lib.last_error()}")
+
+        return launch, res
+
+    def sensitivity_batch(self, batch, grf_body, grf_bar, want=("adjoint", "b_bar"), act_tol=1e-7, out=None, stream=None):
+        """The adjoint of the balance QP on the active face of `grf_body` [n,12] (as control_batch() wrote it) for the batch the
+        solve read, given the cotangent `grf_bar` [n,12] on those forces (qc_sensitivity_batch, include/qc_balance.h;
+        INTEGRATION.md "Sensitivity of a solved batch").  `want`: any of "adjoint" [n,12] (world frame), "b_bar" [n,6], "feet_bar"
+        [n,4,3], "x_bar", "xdot_bar", "w_bar", "x_d_bar", "xdot_d_bar", "w_d_bar" [n,3], "flags" int32 [n] (bit 0: a foot on both rows
+        of an axis, the derivative is one-sided; bit 1: a bad pivot, the robot's outputs are NaN).  Rwb and Rwb_d are held fixed; no
+        cotangent of them, of mu, fzmin, fzmax or the weights is produced.  Nothing of `batch` is written.  Asynchronous on `stream`,
+        no synchronisation.  Returns the dict of device tensors; ValueError with the library's message for a call it refuses."""
+        launch, res = self.plan_sensitivity(batch, grf_body, grf_bar, want, act_tol, out, stream)
+        launch()
+        return res
+
     def control_batch_host(self, batch, warm=None, want_active_set=False, want_iterations=False, want_torques=False):
         """n robots, numpy (host) arrays in and out; PCIe-inclusive convenience path."""
         n = batch["x"].shape[0]
@@ -712,6 +775,8 @@ CERTIFY_SUMMARY_DTYPE = np.dtype([("n_fail", np.int64), ("n_nonfinite", np.int64
 # the per-robot outputs of the certificate: name -> (trailing shape, torch dtype name)
 _CERTIFY_OUTPUTS = {"primal": ((), "float64"), "stationarity": ((), "float64"), "lambda": ((4, 3), "float64"), "grad": ((12,), "float64"),
                     "active": ((4,), "uint8"), "flags": ((), "int32")}
+_SENSITIVITY_OUTPUTS = {"adjoint": ((12,), "float64"), "b_bar": ((6,), "float64"), "feet_bar": ((4, 3), "float64"),
+                        **{k: ((3,), "float64") for k in ("x_bar", "xdot_bar", "w_bar", "x_d_bar", "xdot_d_bar", "w_d_bar")}, "flags": ((), "int32")}
 
 
 def certify_summary(t):

@@ -103,6 +103,20 @@ QC_DEV void certify_xy(int code, double g, double& lam, double& res) {
   res = code == 0 ? fabs(g) : (code == 3 ? 0.0 : max_nan(0.0, -one));
 }
 
+// One stance foot's rows at the world-frame force (fx, fy, fz): the primal residual and the active codes of the three axes (0 none,
+// 1 lower, 2 upper, 3 both) - shared with the sensitivity kernel (qc_sensitivity.hpp), whose face these codes define.
+// No contraction here: the residual and the row tests are the expressions of tests/kkt_batch.py to the bit, so a force that sits
+// exactly on a face (fx = mu fz as assigned) has slack exactly 0 and is classified the same everywhere.
+QC_DEV void classify_foot(double mu, double fzmin, double fzmax, double act_tol, double fx, double fy, double fz, double& viol, int& cx,
+                          int& cy, int& cz) {
+#pragma clang fp contract(off)
+  viol = max_nan(max_nan(fabs(fx) - mu * fz, fabs(fy) - mu * fz), max_nan(fzmin - fz, fz - fzmax));
+  const double tol = act_tol * (1.0 + fabs(fz) * mu);
+  cx = (mu * fz + fx <= tol ? 1 : 0) | (mu * fz - fx <= tol ? 2 : 0);
+  cy = (mu * fz + fy <= tol ? 1 : 0) | (mu * fz - fy <= tol ? 2 : 0);
+  cz = (fz - fzmin <= act_tol * (1.0 + fzmin) ? 1 : 0) | (fzmax - fz <= act_tol * (1.0 + fzmax) ? 2 : 0);
+}
+
 template <bool KIN>
 __global__ __launch_bounds__(CERTIFY_BLOCK) void certify_kernel(const DevParams* __restrict__ Pg, const long n, const BatchIn in, const CertifyArgs a) {
   CertifySummary acc = summary_empty();
@@ -181,14 +195,11 @@ __global__ __launch_bounds__(CERTIFY_BLOCK) void certify_kernel(const DevParams*
     for (int l = 0; l < 4; l++) {
       const double fx = f[l][0], fy = f[l][1], fz = f[l][2];
       if (mask & (1u << l)) {
-        // No contraction here: the residual and the row tests are the expressions of tests/kkt_batch.py to the bit, so a force
-        // that sits exactly on a face (fx = mu fz as assigned) has slack exactly 0 and is classified the same everywhere.
+        // (no contraction in the multipliers either: they were written under classify_foot's rule and stay as they were)
 #pragma clang fp contract(off)
-        const double viol = max_nan(max_nan(fabs(fx) - mu * fz, fabs(fy) - mu * fz), max_nan(fzmin - fz, fz - fzmax));
-        const double tol = a.act_tol * (1.0 + fabs(fz) * mu);
-        const int cx = (mu * fz + fx <= tol ? 1 : 0) | (mu * fz - fx <= tol ? 2 : 0);
-        const int cy = (mu * fz + fy <= tol ? 1 : 0) | (mu * fz - fy <= tol ? 2 : 0);
-        const int cz = (fz - fzmin <= a.act_tol * (1.0 + fzmin) ? 1 : 0) | (fzmax - fz <= a.act_tol * (1.0 + fzmax) ? 2 : 0);
+        double viol;
+        int cx, cy, cz;
+        classify_foot(mu, fzmin, fzmax, a.act_tol, fx, fy, fz, viol, cx, cy, cz);
         double rx, ry;
         certify_xy(cx, g[l][0], lam[l][0], rx);
         certify_xy(cy, g[l][1], lam[l][1], ry);

@@ -12,6 +12,7 @@
 #include "qc_plant.hpp"
 #include "qc_leg_plant.hpp"
 #include "qc_certify.hpp"
+#include "qc_sensitivity.hpp"
 
 namespace qc {
 
@@ -539,6 +540,29 @@ inline int check_certify_args(const qc_handle* h, size_t n, const qc_batch_in* i
 inline unsigned certify_blocks(size_t n) {
   const size_t b = (n + CERTIFY_BLOCK - 1) / CERTIFY_BLOCK;
   return (unsigned)(b < (size_t)CERTIFY_MAX_PARTIALS ? b : (size_t)CERTIFY_MAX_PARTIALS);
+}
+
+// ---------------------------------------------------------------- qc_sensitivity_batch
+// The argument check of the adjoint: what is wrong with the call itself (message prefix "qc_sensitivity_batch:").
+inline int check_sensitivity_args(const qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_io* io) {
+  if (!h || !in || !io) return fail(QC_ERR_INVALID, "qc_sensitivity_batch: null argument");
+  if (const int rc = check_struct_size("qc_sensitivity_batch", "qc_sensitivity_io", "qc_default_sensitivity", io->struct_size, sizeof(qc_sensitivity_io)); rc != QC_OK)
+    return rc;
+  if (!std::isfinite(io->act_tol) || !(io->act_tol >= 0.0)) return fail(QC_ERR_INVALID, "qc_sensitivity_batch: act_tol must be finite and >= 0");
+  if (!io->adjoint && !io->b_bar && !io->feet_bar && !io->x_bar && !io->xdot_bar && !io->w_bar && !io->x_d_bar && !io->xdot_d_bar && !io->w_d_bar && !io->flags)
+    return fail(QC_ERR_INVALID, "qc_sensitivity_batch: no output requested (adjoint, b_bar, feet_bar, x_bar, xdot_bar, w_bar, x_d_bar, xdot_d_bar, w_d_bar, flags are all NULL)");
+  if (n == 0) return QC_OK;
+  if (!io->grf_body || !io->grf_bar) return fail(QC_ERR_INVALID, "qc_sensitivity_batch: grf_body and grf_bar are required");
+  if (!in->Rwb || !in->Rwb_d || !in->x || !in->xdot || !in->w || !in->x_d || !in->xdot_d || !in->w_d)
+    return fail(QC_ERR_INVALID, "qc_sensitivity_batch: the state arrays Rwb, Rwb_d, x, xdot, w, x_d, xdot_d and w_d are required (commander mode is out of scope)");
+  if (!in->feet && !in->joint_q) return fail(QC_ERR_INVALID, "qc_sensitivity_batch: feet or joint_q is required");
+  return check_one_launch("qc_sensitivity_batch", n, SENSITIVITY_BLOCK);
+}
+
+// workgroups of sensitivity_kernel for n robots: one wave each, capped (the waves stride beyond the cap)
+inline unsigned sensitivity_blocks(size_t n) {
+  const size_t b = (n + SENSITIVITY_BLOCK - 1) / SENSITIVITY_BLOCK;
+  return (unsigned)(b < (size_t)SENSITIVITY_MAX_BLOCKS ? b : (size_t)SENSITIVITY_MAX_BLOCKS);
 }
 
 }  // namespace qc
