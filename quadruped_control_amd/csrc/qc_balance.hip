@@ -78,6 +78,10 @@ struct Lane {
   static constexpr int G = Eqp::G;
   static constexpr int FPL = 4 / G;  // feet per lane
   static constexpr bool S = Eqp::kStrided;
+  // the state update of a recalculation on the packed working-set word (iterate): the strided 4-lane kernels, whose lone
+  // wave pays every instruction of the recalculation on its serial chain
+  static constexpr bool kPacked = S;
+  static_assert(!kPacked || FPL == 1, "the packed update takes negbits in the working-set word's layout, which multipliers_ok builds only below FPL == 4");
   Wrench<FPL> Wr;
   Cube<FPL> C;
   double f[3 * FPL];
@@ -87,6 +91,10 @@ struct Lane {
   int status, iters;
   double tol_s;  // relative multiplier tolerance of this robot (tol_d x Eqp::kTolScale), signed: + while it still has its polish release, - after
   bool have_f;  // (read only by a MIXED recalculation without RACE, which no kernel runs; yet dropping its stores reshuffles the registers of most kernels)
+  // the last recalculation was this robot's KKT point and the robot was live: what a racing group votes with.  It stands for
+  // `busy & done & status == QC_SOLVED` only where the caller passes its `busy` as `live` and votes right after iterate() - all
+  // three after() lambdas do (a live robot's status turns QC_SOLVED in exactly that recalculation); nothing else reads it
+  bool kkt = false;
   int nclamp = 1;        // RACE: recalculations that clamp instead of stepping
   bool drop_all = false;  // RACE: drop every negative multiplier after a full step
 
@@ -131,6 +139,11 @@ struct Lane {
           // kernel whose pointers already fill half of the SGPR file - they spill, and SGPR pairs that spill leave frame slots.
           // The same twelve answers as bits of one VGPR (negbits); the bool array is dead on this path.
           negbits |= (neg[3 * i + 0] ? 1u : 0u) << (3 * i) | (neg[3 * i + 1] ? 2u : 0u) << (3 * i) | (neg[3 * i + 2] ? 4u : 0u) << (3 * i);
+          neg[3 * i + 0] = neg[3 * i + 1] = neg[3 * i + 2] = false;
+        } else if constexpr (kPacked) {
+          // packed state update (iterate): the answers as the release mask itself, both bits of every negative axis, at the
+          // axis' place in the working-set word
+          negbits |= ((neg[3 * i + 0] ? 3u : 0u) | (neg[3 * i + 1] ? 12u : 0u) | (neg[3 * i + 2] ? 48u : 0u)) << (6 * (foot0 + i));
           neg[3 * i + 0] = neg[3 * i + 1] = neg[3 * i + 2] = false;
         }
       } else {
@@ -199,6 +212,7 @@ struct Lane {
     // (b) otherwise: ratio test over the faces outside the working set (tree min, face code in the low bits)
     bool blocked = false;
     int bcode = -1;
+    uint32_t alo = 0u;  // (kPacked: the low word of the smallest ratio - its face code)
     if constexpr (PHASE != FIRST) {
       double cand[6 * FPL];
 #pragma unroll
@@ -222,6 +236,7 @@ struct Lane {
       const double amin = group_min<G, S>(cand[0]);
       blocked = !fresh & (amin < 1.0e299);
       bcode = blocked ? tag_code(amin) : -1;
+      alo = (uint32_t)__double_as_longlong(amin);
       // f <- f^ + (1 - alpha)(f - f^): exactly f^ for a full step.  No face blocks: amin = +BIG, clamped to alpha = 1
       // (branch-free; a blocking ratio that the approximate reciprocal rounds up to 1 is clamped too)
       const double beta = 1.0 - min_nn(max_nn(amin, 0.0), 1.0);
@@ -262,6 +277,41 @@ struct Lane {
     }
     const bool dall = RACE & drop_all & at_fh;  // this lane's strategy drops every multiplier below the bar at once
     const bool take_clamp = fresh & changed;
+    if constexpr (kPacked) {
+      // The same update on the working-set word: two bits per axis (encode_foot: 0 free, 1 upper face, 3 = -1 lower face), six
+      // per foot, foot k at bit 6 k - the layout of the warm-start word, in which a release code c = 3 foot + axis names the field
+      // at bit 2 c and a blocking code c = 6 foot + 2 axis + (upper) the field at bit c & ~1.  A lane holds the fields of its own
+      // feet and reads only those back, so masks that name another lane's field pass through unnoticed.  What the select chains
+      // per axis decided is decided here by the same conditions: release (one field, or the strategy's negbits), then the
+      // blocking face over it, then the clamp's set, then `live`.  Per recalculation that is a dozen integer instructions behind
+      // the two reduced doubles instead of about fifty compares and selects.
+      const uint32_t sh0 = 6u * (uint32_t)foot0;
+      uint32_t w = 0u, wc = 0u;
+#pragma unroll
+      for (int i = 0; i < FPL; i++) {
+        w |= encode_foot(C.sx[i], C.sy[i], C.sz[i]) << (6 * i);
+        if constexpr (PHASE != STEADY) wc |= encode_foot(Cc.sx[i], Cc.sy[i], Cc.sz[i]) << (6 * i);
+      }
+      w <<= sh0;
+      const uint32_t wlo = (uint32_t)__double_as_longlong(worst);
+      const uint32_t rel1 = (at_fh & !opt) ? 3u << (((wlo & 31u) << 1) & 31u) : 0u;
+      const uint32_t rel = RACE ? (dall ? negbits : rel1) : rel1;
+      uint32_t nw = w & ~rel;
+      if constexpr (PHASE != FIRST) {
+        const uint32_t field = 3u << (alo & 30u);
+        const uint32_t val = field ^ ((alo & 1u) << (alo & 31u));  // upper face (odd code): 1, lower: 3
+        const uint32_t bm = blocked ? field : 0u;
+        nw = (nw & ~bm) | (val & bm);
+      }
+      if constexpr (PHASE != STEADY) nw = take_clamp ? wc << sh0 : nw;
+      nw = live ? nw : w;
+#pragma unroll
+      for (int i = 0; i < FPL; i++) {
+        C.sx[i] = __builtin_amdgcn_sbfe((int)nw, sh0 + 6 * i, 2);
+        C.sy[i] = __builtin_amdgcn_sbfe((int)nw, sh0 + 6 * i + 2, 2);
+        C.sz[i] = __builtin_amdgcn_sbfe((int)nw, sh0 + 6 * i + 4, 2);
+      }
+    } else {
 #pragma unroll
     for (int i = 0; i < FPL; i++) {
       int sx = C.sx[i], sy = C.sy[i], sz = C.sz[i];
@@ -279,8 +329,10 @@ struct Lane {
       C.sy[i] = live ? (take_clamp ? Cc.sy[i] : sy) : C.sy[i];
       C.sz[i] = live ? (take_clamp ? Cc.sz[i] : sz) : C.sz[i];
     }
+    }
     // (bitwise on purpose: short-circuit forms become exec-mask branches on the serial chain)
     const bool solved = pd & at_fh & opt;
+    kkt = live & solved;  // (a live robot's status is QC_SOLVED exactly when it has just been solved: the vote needs no look at `status`)
     status = live ? (!pd ? (int)QC_NOT_PD : (solved ? (int)QC_SOLVED : status)) : status;  // otherwise it stays QC_MAX_ITER
     return (!pd) | solved | (iters >= P.max_iter);
   }
@@ -1123,7 +1175,7 @@ QC_DEV void finish_on_four_lanes(const DevParams* __restrict__ Pg, const LaneG& 
   LR.drop_all = sid == 1;
   unsigned solved_mask = 0;  // strategies of this lane's robot that have reached the KKT point
   auto after = [&](bool done) {
-    const int mine = (busyR & done & (LR.status == QC_SOLVED)) ? (1 << sid) : 0;
+    const int mine = (busyR & LR.kkt) ? (1 << sid) : 0;
     const int m = race_or<8, 2>(mine);
     solved_mask |= (unsigned)m;
     busyR = busyR & !done & (solved_mask == 0);
@@ -1360,7 +1412,7 @@ __global__ __launch_bounds__(64, MIN_WAVES_PER_SIMD) void balance_kernel(const D
     // the robot is finished as soon as one strategy has solved it; the others stop with it
     auto after = [&](bool done) {
       if constexpr (RACE > 1) {
-        const int mine = (busy & done & (L.status == QC_SOLVED)) ? (1 << sid) : 0;
+        const int mine = (busy & L.kkt) ? (1 << sid) : 0;
         const int m = race_or<ROB, RACE>(mine);
         solved_mask |= (unsigned)m;
         busy = busy & !done & (solved_mask == 0);
@@ -1823,7 +1875,7 @@ __global__ __launch_bounds__(128, 2) void balance_pair_kernel(const DevParams* _
     LR.drop_all = sid == 1;
     unsigned solved_mask = 0;
     auto after = [&](bool fin) {
-      const int me = (busyR & fin & (LR.status == QC_SOLVED)) ? (1 << sid) : 0;
+      const int me = (busyR & LR.kkt) ? (1 << sid) : 0;
       const int m = race_or<8, 2>(me);
       solved_mask |= (unsigned)m;
       busyR = busyR & !fin & (solved_mask == 0);

@@ -1,0 +1,449 @@
+"""-m gpu: the decision block that ends a working-set recalculation (Lane::iterate after the solve: ratio test, multiplier
+test, state update, the race's vote) at the shapes where IT can go wrong, not the workload's.
+
+The strided 4-lane kernels update the working set on the packed word (two bits per axis); the one- and two-lane kernels keep
+the per-axis select chains.  Both must take the same decisions, so every batch is solved at the group widths 1, 2 and 4 with
+one strategy (status, iteration count, active-set word and forces must agree, the bar of
+test_gpu_matrix.py::test_iteration_cap_and_bad_inputs_agree_across_widths) and through the racing body (race = 4 and 2) and
+with race = 1, all against the C oracle at the suite's 1e-6.
+
+Shapes: n = 1, 3, 4, 5 and 17 robots (a racing wave holds 4 robots: a ragged wave, a full one, one over, and groups that
+shadow robot 0), the 15 non-empty contact patterns rotating through every batch, cold and warm-started.
+
+Branches of the block reached on purpose, each input chosen and its branch proven on the CPU by a traced walk of the
+strategy model (oracle/prototypes: QP.eqp of prototype_as, the clamp of proto_race_strategies_lib; `_walk` below):
+solved in recalculation 1 with no blocking face, a zero-length step where the face just released blocks again at once, a
+drop-all release of two or more faces at once by the strategy that then wins the race, the iteration-cap exit and the
+QC_NOT_PD exit.  Only robots whose every decision has a margin (no near-tie in the ratio test, no multiplier near the bar)
+are chosen, so the device must take the model's walk: its recalculation count and working-set word are asserted EQUAL
+to the model's, classic and racing - a wrong release mask in a racing strategy shows as a count above the model's.
+The polish release (|worst| <= tol |g|) is pinned with the tolerance raised through qc_set_tuning (tol_d = POLISH_TOL): at
+the default 1e-14 the band is the solve's own rounding noise, at 2e-2 a multiplier is decidably inside or outside it (a
+factor 2 clear of either edge of the band tol max(1, 4 |v|_inf)).  The model then releases
+below +tol |g| until the first release of a multiplier inside the band and below -tol |g| afterwards; chosen robots
+include walks with that release and walks that, after the flip, accept a second weak multiplier without releasing it.
+"""
+import numpy as np
+import pytest
+
+gpu = pytest.mark.gpu  # (the CPU-side proof of the pinned branches runs without one)
+
+RTOL = 1e-6   # of max(1, max|GRF|) per robot, against the oracle (the suite's bar)
+XTOL = 1e-8   # across widths / strategies (the existing cross-width bar)
+SIZES = (1, 3, 4, 5, 17)
+PATTERNS = tuple(range(1, 16))
+
+
+@pytest.fixture(scope="module")
+def q(built):
+    import quadruped_control_amd as q
+
+    return q
+
+
+_cache = {}
+
+
+def _batch(q, n, first):
+    """n config-3 robots whose contact patterns rotate through the 15 non-empty ones starting at `first`, their oracle
+    solution, and the 'previous tick' (slightly different commands) that a warm start comes from.  Computed once."""
+    key = (n, first)
+    if key not in _cache:
+        from oracle import c_oracle as O
+        from quadruped_control_amd import workloads as W
+
+        P = q.cheetah_params(0.6)
+        b = W.config3(n, seed=0x5EED0D00 + 16 * n + first)
+        pat = (first - 1 + np.arange(n)) % 15 + 1
+        b["stance"] = np.ascontiguousarray(((pat[:, None] >> np.arange(4)[None, :]) & 1).astype(np.uint8))
+        prev = dict(b)
+        prev["xdot_d"] = b["xdot_d"] * 0.9
+        prev["x"] = b["x"] + 1e-3
+        ref, st, it = O.control_batch(P, b, threads=4)
+        _cache[key] = (P, b, prev, ref, st)
+    return _cache[key]
+
+
+def _ctl(q, P, max_iter=None, **tune):
+    kw = {} if max_iter is None else {"max_iter": max_iter}
+    return q.BalanceController.from_params(P, **kw).set_tuning(one_fill=1, **tune)
+
+
+def _relerr(a, ref):
+    scale = np.maximum(1.0, np.abs(ref).max(axis=1, keepdims=True))
+    return float(np.max(np.abs(a - ref) / scale)) if a.size else 0.0
+
+
+def _solve(ctl, b, warm):
+    return ctl.control_batch_host(b, warm=warm, want_iterations=True, want_active_set=True)
+
+
+@gpu
+@pytest.mark.parametrize("start", ["cold", "warm"])
+@pytest.mark.parametrize("n", SIZES)
+def test_widths_and_strategies_agree(q, n, start):
+    for first in PATTERNS:
+        P, b, prev, ref, ref_st = _batch(q, n, first)
+        warm = None
+        if start == "warm":
+            warm = _solve(_ctl(q, P, group=4, race=0, clamp_steps=1), prev, None)["active_set"]
+        outs = {}
+        for g in (4, 2, 1):
+            ctl = _ctl(q, P, group=g, race=0, clamp_steps=1)  # one strategy, one start: the widths walk the same path
+            assert ctl.query_launch(n, warm=warm is not None)["lanes_per_robot"] == g
+            outs[g] = _solve(ctl, b, warm)
+        o4 = outs[4]
+        assert np.array_equal(o4["status"], ref_st), (n, first, o4["status"], ref_st)
+        ok = o4["status"] == 0
+        assert _relerr(o4["grf_body"][ok], ref[ok]) < RTOL, (n, first)
+        assert np.all(o4["grf_body"][np.repeat(b["stance"] == 0, 3, axis=1)] == 0.0)
+        for g in (2, 1):
+            o = outs[g]
+            assert np.array_equal(o["status"], o4["status"]), (n, first, g)
+            assert np.array_equal(o["iterations"], o4["iterations"]), (n, first, g, o["iterations"], o4["iterations"])
+            assert np.array_equal(o["active_set"], o4["active_set"]), (n, first, g)
+            assert _relerr(o["grf_body"][ok], o4["grf_body"][ok]) < XTOL, (n, first, g)
+            assert np.all(o["grf_body"][~ok] == 0.0)
+        # the racing body (4 and 2 strategies per robot) and the same kernel family with race = 1
+        for r in (4, 2, 1):
+            ctl = _ctl(q, P, group=4, race=r)
+            info = ctl.query_launch(n, warm=warm is not None)
+            assert info["lanes_per_robot"] == 4 and info["strategies"] == r, info
+            o = _solve(ctl, b, warm)
+            assert np.array_equal(o["status"], ref_st), (n, first, r)
+            assert _relerr(o["grf_body"][ok], ref[ok]) < RTOL, (n, first, r)
+            assert _relerr(o["grf_body"][ok], o4["grf_body"][ok]) < XTOL, (n, first, r)
+            assert (o["iterations"][ok] >= 1).all() and (o["iterations"][ok] <= o4["iterations"][ok]).all(), (n, first, r)
+            if r == 1:  # equal strategies: the same walk
+                assert np.array_equal(o["iterations"], o4["iterations"]), (n, first)
+                assert np.array_equal(o["active_set"], o4["active_set"]), (n, first)
+            # the winner's working set is the KKT point's: the classic strategy restarts from it in one recalculation
+            again = _solve(_ctl(q, P, group=4, race=0, clamp_steps=1), b, o["active_set"])
+            assert (again["iterations"][ok] == 1).all(), (n, first, r, again["iterations"])
+            assert _relerr(again["grf_body"][ok], ref[ok]) < RTOL
+
+
+@gpu
+@pytest.mark.parametrize("n", SIZES)
+def test_solved_in_first_recalculation_without_blocking_face(q, n):
+    """A robot started on its solved working set: recalculation 1 finds no blocking face and no multiplier below the bar, at
+    every width and in the racing body, and hands the same word back."""
+    P, b, prev, ref, ref_st = _batch(q, n, 15)  # robot 0: all four feet in stance
+    base = _solve(_ctl(q, P, group=4, race=0, clamp_steps=1), b, None)
+    ok = base["status"] == 0
+    assert ok.any()
+    for tune in (dict(group=4, race=0), dict(group=2, race=0), dict(group=1, race=0), dict(group=4, race=4), dict(group=4, race=2)):
+        o = _solve(_ctl(q, P, **tune), b, base["active_set"])
+        assert np.array_equal(o["status"], base["status"]), tune
+        assert (o["iterations"][ok] == 1).all(), (tune, o["iterations"])
+        assert np.array_equal(o["active_set"][ok], base["active_set"][ok]), tune
+        assert _relerr(o["grf_body"][ok], ref[ok]) < RTOL, tune
+
+
+@gpu
+@pytest.mark.parametrize("cap", [1, 2, 4])
+@pytest.mark.parametrize("n", SIZES)
+def test_iteration_cap_exit(q, n, cap):
+    """Robots that run out of recalculations leave with status 1, `cap` recalculations and zero forces at every width, in the
+    racing body too; robots the classic strategy solves within the cap are solved."""
+    P, b, prev, ref, ref_st = _batch(q, n, 15)
+    full = _solve(_ctl(q, P, group=4, race=0, clamp_steps=1), b, None)
+    outs = {g: _solve(_ctl(q, P, max_iter=cap, group=g, race=0, clamp_steps=1), b, None) for g in (4, 2, 1)}
+    o4 = outs[4]
+    want_capped = (full["status"] == 0) & (full["iterations"] > cap)
+    assert np.array_equal(o4["status"] == 1, want_capped | (full["status"] == 1)), (o4["status"], full["iterations"])
+    capped = o4["status"] == 1
+    assert (o4["iterations"][capped] == cap).all() and np.all(o4["grf_body"][capped] == 0.0)
+    ok = o4["status"] == 0
+    assert _relerr(o4["grf_body"][ok], ref[ok]) < RTOL
+    for g in (2, 1):
+        o = outs[g]
+        assert np.array_equal(o["status"], o4["status"]) and np.array_equal(o["iterations"], o4["iterations"]), g
+        assert np.array_equal(o["active_set"][ok], o4["active_set"][ok]), g
+        assert _relerr(o["grf_body"][ok], o4["grf_body"][ok]) < XTOL and np.all(o["grf_body"][~ok] == 0.0), g
+    for r in (4, 2):
+        o = _solve(_ctl(q, P, max_iter=cap, group=4, race=r), b, None)
+        assert (o["status"][ok] == 0).all() and (o["iterations"] <= cap).all(), r
+        assert set(np.unique(o["status"])) <= {0, 1}, r
+        assert np.all(o["grf_body"][o["status"] != 0] == 0.0), r
+        assert _relerr(o["grf_body"][ok], ref[ok]) < RTOL, r
+
+
+@gpu
+@pytest.mark.parametrize("n", SIZES)
+def test_not_pd_exit(q, n):
+    """Non-finite inputs end the robot with QC_NOT_PD (3) and zero forces in recalculation 1, whichever width or strategy
+    count, and leave its neighbours in the wave untouched."""
+    P, b0, prev, ref, ref_st = _batch(q, n, 15)
+    b = {k: np.array(v, copy=True) for k, v in b0.items()}
+    bad = np.arange(0, n, 3)
+    b["x"][bad[::2], 1] = np.nan
+    b["Rwb"][bad[1::2], 4] = np.inf
+    good = np.setdiff1d(np.arange(n), bad)
+    outs = {}
+    for name, tune in (("g4", dict(group=4, race=0, clamp_steps=1)), ("g2", dict(group=2, race=0, clamp_steps=1)),
+                       ("g1", dict(group=1, race=0, clamp_steps=1)), ("r4", dict(group=4, race=4)), ("r2", dict(group=4, race=2)),
+                       ("r1", dict(group=4, race=1))):
+        o = outs[name] = _solve(_ctl(q, P, **tune), b, None)
+        assert (o["status"][bad] == 3).all(), (name, o["status"])
+        assert np.all(o["grf_body"][bad] == 0.0), name
+        assert np.array_equal(o["status"][good], ref_st[good]), name
+        ok = good[ref_st[good] == 0]
+        assert _relerr(o["grf_body"][ok], ref[ok]) < RTOL, name
+    for name in ("g2", "g1"):
+        assert np.array_equal(outs[name]["iterations"], outs["g4"]["iterations"]), name
+        assert np.array_equal(outs[name]["active_set"][good], outs["g4"]["active_set"][good]), name
+
+
+# ---------------------------------------------------------------- pinned branches, proven on the CPU by the strategy model
+STRATEGIES = ((1, "most"), (1, "all"), (2, "all"), (3, "most"))  # sid 0 .. 3 of the racing kernel; a 2-way race runs sid 0 and 2
+MARGIN = 1e-6  # smallest relative margin of any decision on a chosen robot's walks (v_rcp_f64 ranks ratios to 2^-23)
+
+
+def _walk(qp, nclamp, drop, cap=200, tol=0.0):
+    """Primal active-set walk of one strategy (proto_race_strategies_lib.solve) with a trace: returns (recalculations, S,
+    events, margin).  events: 'clamp', 'block', 'zero' (zero-length step on the face released one recalculation before),
+    'drop1', 'dropN' (N >= 2 faces at once), 'solved'.  margin: the smallest relative distance of any decision from a tie.
+    tol > 0: the device's acceptance rule with that tolerance (Lane::iterate, POLISH) - the bar is +tol |g| until the first
+    release of a multiplier inside the band ('polish'), -tol |g| afterwards ('weak_kept': solved with a multiplier inside the
+    band left in the set); tol = 0: the bar is 0 and every multiplier must be clear of it."""
+    from oracle.prototypes.proto_race_strategies_lib import clamp_keep
+
+    S = [np.zeros(4, int), np.zeros(4, int), np.zeros(4, int)]
+    f, ev, margin, released, polish_on = None, [], np.inf, set(), True
+    for it in range(cap):
+        if margin <= MARGIN:  # a decision too close to call: the robot is not chosen, no need to walk on
+            return it, S, ev + ["rejected"], 0.0
+        fh, lx, ly, lz = qp.eqp(S)
+        scale = max(1.0, float(np.max(np.abs(fh))))
+        if it < nclamp:
+            # (margin of the clamp: no coordinate of f^ within MARGIN of a bound it is compared with)
+            for i in range(4):
+                if qp.st[i]:
+                    fz = fh[3 * i + 2]
+                    margin = min(margin, abs(fz - qp.hi) / scale, abs(fz - qp.lo) / scale)
+                    m = qp.mu * min(max(fz, qp.lo), qp.hi)
+                    for a in (0, 1):
+                        if S[a][i] == 0:
+                            margin = min(margin, abs(fh[3 * i + a] - m) / scale, abs(fh[3 * i + a] + m) / scale)
+            f, Sn, moved = clamp_keep(qp, fh, S)
+            S = Sn
+            if moved:
+                ev.append("clamp"); released = set(); continue
+        else:
+            d = fh - f
+            cands = []
+            for i in range(4):
+                if not qp.st[i]:
+                    continue
+                fx, fy, fz = f[3 * i:3 * i + 3]; dx, dy, dz = d[3 * i:3 * i + 3]
+                if S[2][i] == 0:
+                    cands += [(2, i, 1, dz, qp.hi - fz), (2, i, -1, -dz, fz - qp.lo)]
+                for a, (v, dv) in enumerate(((fx, dx), (fy, dy))):
+                    if S[a][i] == 0:
+                        cands += [(a, i, 1, dv - qp.mu * dz, qp.mu * fz - v), (a, i, -1, -dv - qp.mu * dz, qp.mu * fz + v)]
+            al = sorted((max(sl, 0.0) / nd, a, i, sg) for a, i, sg, nd, sl in cands if nd > 1e-9 * scale)
+            # (a direction component too small to rank is a tie with "cannot block")
+            margin = min([margin] + [1.0 if nd > 1e-9 * scale or nd < -1e-9 * scale else 0.0 for a, i, sg, nd, sl in cands])
+            al = [t for t in al if t[0] < 1.0 + MARGIN]
+            if al:
+                margin = min(margin, abs(1.0 - al[0][0]))
+                if len(al) > 1:
+                    margin = min(margin, al[1][0] - al[0][0])
+            if al and al[0][0] < 1.0:
+                a0, (_, a, i, sg) = al[0][0], al[0]
+                zero = (a, i) in released and a0 * np.max(np.abs(d)) <= 1e-9 * scale
+                if a0 * np.max(np.abs(d)) <= 1e-9 * scale and not zero:
+                    margin = 0.0  # a zero-length step on another face: degenerate, not chosen
+                f = f + a0 * d; S[a][i] = sg
+                ev.append("zero" if zero else "block"); released = set(); continue
+            f = fh
+        lam = np.stack([np.where(S[0] != 0, lx, np.inf), np.where(S[1] != 0, ly, np.inf), np.where(S[2] != 0, lz, np.inf)])
+        gs = max(1.0, float(np.max(np.abs(qp.Q @ fh + qp.c))), float(np.max(np.abs(qp.c))))
+        fin = lam[np.isfinite(lam)]
+        inband = np.zeros(lam.shape, bool)
+        if tol > 0.0:
+            # the device's scale is max(1, 4 |v|_inf), v = S (A f^ - b) (eqp_diagw; lever arms in the world frame, as here)
+            gs = max(1.0, 4.0 * float(np.max(np.abs(qp.Sm @ (qp.A @ fh - qp.b)))))
+            inband = np.abs(lam) < 0.5 * tol * gs
+            clear = np.isfinite(lam) & (np.abs(lam) > 2.0 * tol * gs)
+            if (np.isfinite(lam) & ~inband & ~clear).any():
+                margin = 0.0  # a multiplier near an edge of the band: not chosen
+            neg = (clear & (lam < 0.0)) | (inband & polish_on)
+        else:
+            if fin.size:
+                margin = min(margin, float(np.min(np.abs(fin))) / gs)
+            neg = lam < 0.0
+        if not neg.any():
+            if inband.any():
+                ev.append("weak_kept")
+            ev.append("solved")
+            return it + 1, S, ev, margin
+        k = np.unravel_index(np.argmin(lam), lam.shape)  # the worst multiplier: below the bar, since something is
+        if drop == "all":
+            released = {(a, i) for a in range(3) for i in range(4) if neg[a][i]}
+            for a in range(3):
+                S[a][neg[a]] = 0
+            ev.append("dropN" if len(released) >= 2 else "drop1")
+        else:
+            srt = np.sort(fin)
+            if srt.size > 1:
+                margin = min(margin, float(srt[1] - srt[0]) / gs)
+            S[k[0]][k[1]] = 0
+            released = {(int(k[0]), int(k[1]))}
+            ev.append("drop1")
+        if inband[k]:  # the release was not of a clearly negative multiplier: the tolerance flips for good
+            polish_on = False
+            ev.append("polish")
+    return cap, S, ev + ["cap"], margin
+
+
+def _word(S):
+    w = 0
+    for i in range(4):
+        w |= ((int(S[0][i]) & 3) | (int(S[1][i]) & 3) << 2 | (int(S[2][i]) & 3) << 4) << (6 * i)
+    return w | 0x80000000
+
+
+POLISH_TOL = 2e-2
+_pinned = {}
+
+
+def _model_batch():
+    from oracle import numpy_restatement as R
+    from oracle.prototypes.prototype_as import QP
+    from quadruped_control_amd import workloads as W
+
+    P = R.cheetah_params(mu=0.6)
+    B = W.config2(2048, seed=0x5EED0DB1)
+    qps = []
+    for i in range(B["x"].shape[0]):
+        d = R.assemble(P, B["Rwb"][i].reshape(3, 3), B["Rwb_d"][i].reshape(3, 3), B["x"][i], B["xdot"][i], B["w"][i], B["x_d"][i],
+                       B["xdot_d"][i], B["w_d"][i], B["feet"][i], B["stance"][i])
+        qp = QP(d["H"], d["g"], B["stance"][i], P["mu"], P["fzmin"], P["fzmax"])
+        qp.A, qp.b, qp.Sm = d["A"], d["b"], np.asarray(P["S"], float).reshape(6, 6)
+        qps.append(qp)
+    return B, qps
+
+
+def _pinned_robots():
+    """Robots of a 2 048-robot config-2 batch (long walks) with a margin on every decision of all four strategies'
+    walks, grouped by the branch their walks take; the branch is what the traced model proves.  Once with the default
+    tolerance (modelled as a bar at 0 with every multiplier clear of it) and once with
+    tol_d = POLISH_TOL.  Computed once, on the CPU."""
+    if not _pinned:
+        B, qps = _model_batch()
+        for key, tol, count in (("plain", 0.0, len(qps)), ("polish", POLISH_TOL, len(qps))):
+            rows, walks = [], []
+            for i in range(count):
+                w = [_walk(qps[i], *s, tol=tol) for s in STRATEGIES]
+                # (with the raised tolerance a margin on the classic walk is enough for the widths; the races take the robots
+                # with a margin on all four)
+                if min(x[3] for x in w) > MARGIN or (tol > 0.0 and w[0][3] > MARGIN):
+                    rows.append(i); walks.append(w)
+            pick = {"zero": [], "dropN_wins": [], "polish": [], "weak_kept": []}
+            for k, w in enumerate(walks):
+                n = [x[0] for x in w]
+                if min(x[3] for x in w) <= MARGIN:  # classic walk only
+                    for name in ("zero", "polish", "weak_kept"):
+                        if name in w[0][2]:
+                            pick[name].append(k)
+                    continue
+                first = [j for j in range(4) if j == 0 or n[j] == min(n)]  # the classic walk, and the strategies first (alone or tied) to the KKT point
+                for name in ("zero", "polish", "weak_kept"):
+                    if any(name in w[j][2] for j in first):
+                        pick[name].append(k)
+                # a drop-all strategy that released several faces at once and then reached the KKT point strictly first
+                if min(n[1], n[2]) < min(n[0], n[3]) and any("dropN" in w[j][2] for j in (1, 2) if n[j] == min(n)):
+                    pick["dropN_wins"].append(k)
+            idx = np.array(rows)
+            _pinned[key] = dict(b={k: np.ascontiguousarray(v[idx]) for k, v in B.items()}, walks=walks, pick=pick)
+    return _pinned
+
+
+def _assert_device_walks_the_model(q, b, walks, **extra):
+    """Classic strategy at widths 4, 2, 1 and with race = 1: count and word equal the model's.  race = 4 / 2: the count is the
+    model's minimum over the strategies run, the word the winning (lowest-numbered first) strategy's."""
+    P = q.cheetah_params(0.6)
+    nrob = len(walks)
+    n_model = np.array([[x[0] for x in w] for w in walks])
+    words = np.array([[_word(x[1]) for x in w] for w in walks], dtype=np.uint32)
+    for tune in (dict(group=4, race=0, clamp_steps=1), dict(group=2, race=0, clamp_steps=1), dict(group=1, race=0, clamp_steps=1),
+                 dict(group=4, race=1, clamp_steps=1)):
+        o = _solve(_ctl(q, P, **tune, **extra), b, None)
+        assert (o["status"] == 0).all(), tune
+        assert np.array_equal(o["iterations"], n_model[:, 0]), (tune, np.flatnonzero(o["iterations"] != n_model[:, 0])[:8])
+        assert np.array_equal(o["active_set"], words[:, 0]), (tune, np.flatnonzero(o["active_set"] != words[:, 0])[:8])
+    full = np.array([min(x[3] for x in w) > MARGIN for w in walks])  # robots with a margin on all four strategies' walks
+    b = {k: np.ascontiguousarray(v[full]) for k, v in b.items()}
+    n_all, n_model, words, nrob = n_model, n_model[full], words[full], int(full.sum())
+    for r, sids in ((4, (0, 1, 2, 3)), (2, (0, 2))):
+        o = _solve(_ctl(q, P, group=4, race=r, **extra), b, None)
+        assert (o["status"] == 0).all(), r
+        best = n_model[:, sids].min(axis=1)
+        assert np.array_equal(o["iterations"], best), (r, np.flatnonzero(o["iterations"] != best)[:8], o["iterations"][:16], best[:16])
+        win = np.array([sids[int(np.argmax(n_model[k, sids] == best[k]))] for k in range(nrob)])  # lowest strategy number among the first
+        assert np.array_equal(o["active_set"], words[np.arange(nrob), win]), (r, np.flatnonzero(o["active_set"] != words[np.arange(nrob), win])[:8])
+    return n_all
+
+
+@gpu
+def test_pinned_walks_match_the_strategy_model(q):
+    """Every chosen robot: the device walks the model's walk at every width and in the racing kernels.  The chosen set holds
+    the pinned branches: zero-length re-blocks of the face just released, and drop-all releases of two or more faces at once
+    by the strategy that wins."""
+    pin = _pinned_robots()["plain"]
+    b, walks, pick = pin["b"], pin["walks"], pin["pick"]
+    print("pinned robots:", len(walks), {k: len(v) for k, v in pick.items()})
+    assert len(walks) >= 32 and len(pick["zero"]) >= 1 and len(pick["dropN_wins"]) >= 1, {k: len(v) for k, v in pick.items()}
+    n_model = _assert_device_walks_the_model(q, b, walks)
+    # the drop-all winners really are decided by strategy 1 or 2 (their count is below both most-negative strategies')
+    k = np.array(pick["dropN_wins"])
+    o = _solve(_ctl(q, q.cheetah_params(0.6), group=4, race=4), b, None)
+    assert (o["iterations"][k] < n_model[k][:, [0, 3]].min(axis=1)).all()
+
+
+@gpu
+def test_polish_release_and_flip_match_the_strategy_model(q):
+    """tol_d = POLISH_TOL: robots whose walk releases a multiplier inside the band (the polish release, which flips the
+    tolerance) and robots that afterwards accept a weak multiplier without releasing it, at every width and in the racing
+    kernels; and the release really is the polish's - with polish = 0 the classic count of those robots differs."""
+    pin = _pinned_robots()["polish"]
+    b, walks, pick = pin["b"], pin["walks"], pin["pick"]
+    print("polish robots:", len(walks), {k: len(v) for k, v in pick.items()})
+    assert len(walks) >= 32 and len(pick["polish"]) >= 1 and len(pick["weak_kept"]) >= 1, {k: len(v) for k, v in pick.items()}
+    n_model = _assert_device_walks_the_model(q, b, walks, tol_d=POLISH_TOL)
+    k = np.array([j for j in pick["polish"] if "polish" in walks[j][0][2]])  # in the classic walk
+    if k.size:
+        off = _solve(_ctl(q, q.cheetah_params(0.6), group=4, race=0, clamp_steps=1, tol_d=POLISH_TOL, polish=0), b, None)
+        assert (off["iterations"][k] < n_model[k, 0]).all(), (off["iterations"][k], n_model[k, 0])
+
+
+def test_cpu_model_proves_the_pinned_branches():
+    """The CPU side alone (no GPU): the model's walks of the chosen robots contain the branches by name."""
+    pins = _pinned_robots()
+    for key in ("plain", "polish"):
+        walks, pick = pins[key]["walks"], pins[key]["pick"]
+        for k in pick["zero"]:
+            n = [x[0] for x in walks[k]]
+            evs = [walks[k][j][2] for j in range(4) if (j == 0 or n[j] == min(n)) and "zero" in walks[k][j][2] and walks[k][j][3] > MARGIN]
+            assert evs
+            for ev in evs:
+                j = ev.index("zero")
+                assert j >= 1 and ev[j - 1] in ("drop1", "dropN", "polish"), ev  # released, then blocked again at a zero-length step
+        for k in pick["dropN_wins"]:
+            assert min(x[3] for x in walks[k]) > MARGIN
+            n = [x[0] for x in walks[k]]
+            assert any("dropN" in walks[k][j][2] and n[j] == min(n) for j in (1, 2)) and min(n[1], n[2]) < min(n[0], n[3])
+        for w in walks[:32]:
+            assert w[0][2][-1] == "solved" and w[0][2].count("solved") == 1
+    walks, pick = pins["polish"]["walks"], pins["polish"]["pick"]
+    assert pick["polish"] and pick["weak_kept"]
+    for k in pick["polish"]:
+        for x in walks[k]:
+            assert x[2].count("polish") <= 1  # the tolerance flips once
+            if "polish" in x[2] and x[3] > MARGIN:
+                j = x[2].index("polish")
+                assert x[2][j - 1] in ("drop1", "dropN")
+    for k in pick["weak_kept"]:
+        assert any(x[2][-2:] == ["weak_kept", "solved"] and "polish" in x[2] for x in walks[k] if x[3] > MARGIN)  # kept only after the flip
