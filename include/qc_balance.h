@@ -459,8 +459,7 @@ int qc_certify_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_cer
  *   cotangent of the body-frame foot position whether it came from `feet` or from the kinematics of joint_q;
  *   x_bar, xdot_bar, w_bar, x_d_bar, xdot_d_bar, w_d_bar: b_bar pulled back through the PD law at fixed Rwb and Rwb_d, exactly
  *   as the library evaluates that law (the kff terms on xdot_d[0], xdot_d[1] and w_d included).
- * NOT produced: the cotangents of Rwb and Rwb_d - a caller chains them from b_bar, r_bar_i = Rwb feet_bar_i and z (INTEGRATION.md,
- * "Sensitivity of a solved batch"); the cotangents of mu, fzmin, fzmax and the weights; weak activity - a row whose multiplier is
+ * NOT produced: the cotangents of Rwb and Rwb_d - qc_sensitivity_rot_batch below makes them from b_bar and feet_bar; the cotangents of mu, fzmin, fzmax and the weights; weak activity - a row whose multiplier is
  * about 0 counts as active like any other (qc_certify_batch's lambda shows such rows).  Commander mode is out of scope.
  * The reduced system is solved as a fixed 12x12 LDL^T; a pivot that is not positive and finite sets bit 1 of `flags` and makes
  * every output of that robot NaN.  Non-finite inputs propagate as NaN; nothing is clamped. */
@@ -483,6 +482,45 @@ void qc_default_sensitivity(qc_sensitivity_io* io);
  * requested at all, a missing state array (Rwb, Rwb_d, x, xdot, w, x_d, xdot_d, w_d), neither feet nor joint_q, or n beyond one
  * launch. */
 int qc_sensitivity_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_io* io, void* stream);
+
+/* The rotation cotangents of a solved batch: what qc_sensitivity_batch leaves out.  Given the SAME qc_batch_in, the forces, the
+ * cotangent grf_bar on them and the b_bar and feet_bar qc_sensitivity_batch wrote for that grf_bar (the adjoint itself is not needed;
+ * no solve is repeated), with R = Rwb, Rd = Rwb_d, f_i = -R grf_body_i, ba = b_bar[3:6], p_i the body-frame foot (`feet`, or joint_q
+ * through the forward kinematics), the ENTRYWISE cotangents (row-major, dL / dR_ab of the expressions exactly as the library
+ * evaluates them, the nine entries taken as independent) are the sum of
+ *   the output transform grf_body_i = -R^T f_i at fixed f:   R_bar += -sum_i f_i grf_bar_i^T
+ *   the lever arms r_i = R p_i:                              R_bar += sum_i (R feet_bar_i) p_i^T
+ *   Iw = R Ib R^T in b_ang = Iw al + w_d x (Iw w_d):         Iw_bar = ba al^T + (ba x w_d) w_d^T,  R_bar += Iw_bar R Ib^T + Iw_bar^T R Ib
+ *   the rotation error e = log(Rd R^T) in al = kp_w e + ...: e_bar = kp_w o (Iw^T ba), Re_bar its pull-back through the library's
+ *     Eigen-convention log on the branch it took,            R_bar += Re_bar^T Rd,   Rd_bar = Re_bar R.
+ * Rwb_rot_bar and Rwb_d_rot_bar are the world-frame left-tangent projections: for R <- exp([delta]x) R the cotangent of delta is
+ * axial(R_bar R^T), axial(M) = (M32 - M23, M13 - M31, M21 - M12); the same form for Rd.  These are what a caller that keeps its
+ * rotations on the manifold wants; the entrywise ones are what an autodiff that holds nine numbers wants.
+ * Where the error is exactly the identity the log's smooth limit is differentiated, not the select that returns 0 there.  At an
+ * error angle of exactly pi the log is discontinuous for any implementation: the derivative is that of the branch evaluated.
+ * As every output of qc_sensitivity_batch this is the gradient ON THE ACTIVE FACE: valid while the working set holds, one-sided for
+ * robots with bit 0 of its flags, NaN for robots with bit 1 (their b_bar and feet_bar are NaN and every output here with them).
+ * Non-finite inputs propagate as NaN; nothing is clamped.  Commander mode is out of scope: Rwb_d must be in `in`. */
+typedef struct qc_sensitivity_rot_io {
+  size_t struct_size;        /* = sizeof(qc_sensitivity_rot_io); checked                                             */
+  const double* grf_body;    /* [n][4][3] qc_batch_out.grf_body                                                      */
+  const double* grf_bar;     /* [n][4][3] cotangent on grf_body                                                      */
+  const double* b_bar;       /* [n][6]    qc_sensitivity_io.b_bar for that grf_bar                                   */
+  const double* feet_bar;    /* [n][4][3] qc_sensitivity_io.feet_bar for that grf_bar                                */
+  double* Rwb_bar;           /* [n][9] entrywise, row-major                                                          */
+  double* Rwb_d_bar;         /* [n][9]                                                                               */
+  double* Rwb_rot_bar;       /* [n][3] world-frame left tangent                                                      */
+  double* Rwb_d_rot_bar;     /* [n][3]                                                                               */
+} qc_sensitivity_rot_io;
+/* struct_size set, pointers NULL. */
+void qc_default_sensitivity_rot(qc_sensitivity_rot_io* io);
+/* Asynchronous on `stream`, no host synchronisation (graph-capturable; ordered behind qc_sensitivity_batch on the same stream it
+ * needs no event); n == 0 launches nothing and returns QC_OK.  Every output is optional; at least one must be given.
+ * QC_ERR_INVALID (message starting with "qc_sensitivity_rot_batch:", nothing launched) for a null handle, `in` or `io`, a wrong
+ * struct_size, no output requested at all, a missing grf_body, grf_bar, b_bar or feet_bar, a missing state array (Rwb, Rwb_d, x,
+ * xdot, w, x_d, xdot_d, w_d - commander mode keeps the desired ones in its own record and is refused by this), neither feet nor
+ * joint_q, or n beyond one launch. */
+int qc_sensitivity_rot_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_rot_io* io, void* stream);
 
 #ifdef __cplusplus
 }

@@ -84,6 +84,11 @@ class QcSensitivityIo(C.Structure):
                 ("adjoint", "b_bar", "feet_bar", "x_bar", "xdot_bar", "w_bar", "x_d_bar", "xdot_d_bar", "w_d_bar", "flags")]
 
 
+class QcSensitivityRotIo(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t)] + [(k, C.c_void_p) for k in
+                ("grf_body", "grf_bar", "b_bar", "feet_bar", "Rwb_bar", "Rwb_d_bar", "Rwb_rot_bar", "Rwb_d_rot_bar")]
+
+
 class QcLaunchInfo(C.Structure):
     _fields_ = [("lanes_per_robot", C.c_int32), ("mode", C.c_int32), ("form", C.c_int32), ("strategies", C.c_int32),
                 ("chunk", C.c_int64), ("blocks", C.c_int64), ("resident_workgroups", C.c_int64), ("lds_bytes", C.c_int64)]
@@ -93,7 +98,8 @@ EXPORTS = ("qc_create_abi", "qc_destroy", "qc_control_batch", "qc_control_batch_
            "qc_last_error", "qc_kernel_name", "qc_abi_version", "qc_default_kinematics", "qc_set_kinematics", "qc_set_gait", "qc_swing_state_init",
            "qc_set_tuning", "qc_query_launch", "qc_check_abi", "qc_default_command", "qc_commander_state_init", "qc_tick_batch",
            "qc_default_plant", "qc_plant_step_batch", "qc_default_leg_plant", "qc_leg_plant_step_batch",
-           "qc_default_certify", "qc_certify_batch", "qc_default_sensitivity", "qc_sensitivity_batch")
+           "qc_default_certify", "qc_certify_batch", "qc_default_sensitivity", "qc_sensitivity_batch",
+           "qc_default_sensitivity_rot", "qc_sensitivity_rot_batch")
 
 _lib = None
 
@@ -176,6 +182,10 @@ def load():
     lib.qc_default_sensitivity.restype = None
     lib.qc_sensitivity_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcBatchIn), C.POINTER(QcSensitivityIo), C.c_void_p]
     lib.qc_sensitivity_batch.restype = C.c_int
+    lib.qc_default_sensitivity_rot.argtypes = [C.POINTER(QcSensitivityRotIo)]
+    lib.qc_default_sensitivity_rot.restype = None
+    lib.qc_sensitivity_rot_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcBatchIn), C.POINTER(QcSensitivityRotIo), C.c_void_p]
+    lib.qc_sensitivity_rot_batch.restype = C.c_int
     # the structures above are hand-written mirrors of the header: a library built from another revision is refused here,
     # before any of them crosses the boundary
     rc = lib.qc_check_abi(ABI_VERSION, C.sizeof(QcParams), C.sizeof(QcBatchIn), C.sizeof(QcBatchOut))

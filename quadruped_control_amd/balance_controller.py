@@ -681,12 +681,89 @@ class BalanceController:
         solve read, given the cotangent `grf_bar` [n,12] on those forces (qc_sensitivity_batch, include/qc_balance.h;
         INTEGRATION.md "Sensitivity of a solved batch").  `want`: any of "adjoint" [n,12] (world frame), "b_bar" [n,6], "feet_bar"
         [n,4,3], "x_bar", "xdot_bar", "w_bar", "x_d_bar", "xdot_d_bar", "w_d_bar" [n,3], "flags" int32 [n] (bit 0: a foot on both rows
-        of an axis, the derivative is one-sided; bit 1: a bad pivot, the robot's outputs are NaN).  Rwb and Rwb_d are held fixed; no
-        cotangent of them, of mu, fzmin, fzmax or the weights is produced.  Nothing of `batch` is written.  Asynchronous on `stream`,
+        of an axis, the derivative is one-sided; bit 1: a bad pivot, the robot's outputs are NaN).  Rwb and Rwb_d are held fixed here:
+        their cotangents come from sensitivity_rotation_batch(), given this call's b_bar and feet_bar; no cotangent of mu, fzmin,
+        fzmax or the weights is produced.  Nothing of `batch` is written.  Asynchronous on `stream`,
         no synchronisation.  Returns the dict of device tensors; ValueError with the library's message for a call it refuses."""
         launch, res = self.plan_sensitivity(batch, grf_body, grf_bar, want, act_tol, out, stream)
         launch()
         return res
+
+    def plan_sensitivity_rotation(self, batch, grf_body, grf_bar, b_bar, feet_bar, want=("Rwb_bar", "Rwb_d_bar"), out=None, stream=None):
+        """sensitivity_rotation_batch() marshalled once: returns (launch, out), `launch()` being one qc_sensitivity_rot_batch call
+        (graph-capturable) on tensors that are read in place.  Planning launches nothing.  `out`: a dict of tensors to write into
+        instead of new ones (every name in `want`).  A call the library refuses raises ValueError with its message, from launch()."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        sized = [t for t in [batch.get(k) for k, _ in _IN_FIELDS] + [grf_body, grf_bar, b_bar, feet_bar] if t is not None]
+        if not sized:
+            raise ValueError("sensitivity_rotation: the batch holds no state array")
+        n = sized[0].shape[0]  # (a missing array is the library's refusal, not a KeyError here)
+        bi = _lib.QcBatchIn()
+        for name, k in _IN_FIELDS + (("joint_q", 12),):
+            t = batch.get(name)
+            if _check_tensor(name, t, n, k, torch.float64, dev, False):
+                setattr(bi, name, t.data_ptr())
+        io = _lib.QcSensitivityRotIo()
+        self._lib.qc_default_sensitivity_rot(C.byref(io))
+        for name, t, k in (("grf_body", grf_body, 12), ("grf_bar", grf_bar, 12), ("b_bar", b_bar, 6), ("feet_bar", feet_bar, 12)):
+            if _check_tensor(name, t, n, k, torch.float64, dev, False, "float64"):
+                setattr(io, name, t.data_ptr())
+        unknown = [w for w in want if w not in _SENSITIVITY_ROT_OUTPUTS]
+        if unknown:
+            raise ValueError(f"sensitivity_rotation: unknown output(s) {unknown}; want is a subset of {tuple(_SENSITIVITY_ROT_OUTPUTS)}")
+        res = {}
+        for name in want:
+            size = (n, _SENSITIVITY_ROT_OUTPUTS[name])
+            t = None if out is None else out.get(name)
+            if t is None:
+                if out is not None:
+                    raise ValueError(f"out: '{name}' was asked for but the supplied `out` has no such tensor")
+                t = torch.zeros(size, dtype=torch.float64, device=dev)
+            elif t.dtype != torch.float64 or not t.is_contiguous() or t.device != dev or t.numel() != size[0] * size[1]:
+                raise ValueError(f"out['{name}']: need contiguous {torch.float64} with {size[0] * size[1]} elements on {dev}")
+            res[name] = t
+            setattr(io, name, t.data_ptr())
+        fn, h, args = self._lib.qc_sensitivity_rot_batch, self._h, (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
+
+        def launch(_keep=(batch, grf_body, grf_bar, b_bar, feet_bar, res, bi, io)):
+            rc = fn(h, *args)
+            if rc == _lib.QC_ERR_INVALID:
+                raise ValueError(_lib.last_error())
+            if rc != _lib.QC_OK:
+                raise RuntimeError(f"qc_sensitivity_rot_batch failed ({rc}): {_lib.last_error()}")
+
+        return launch, res
+
+    def sensitivity_rotation_batch(self, batch, grf_body, grf_bar, b_bar, feet_bar, want=("Rwb_bar", "Rwb_d_bar"), out=None, stream=None):
+        """The cotangents of Rwb and Rwb_d that sensitivity_batch() leaves out (qc_sensitivity_rot_batch, include/qc_balance.h;
+        INTEGRATION.md "Sensitivity of a solved batch"), from the batch the solve read, its forces `grf_body` [n,12], the cotangent
+        `grf_bar` [n,12] and the `b_bar` [n,6] and `feet_bar` [n,4,3] sensitivity_batch() returned for that grf_bar, on the same
+        stream behind it.  `want`: any of "Rwb_bar", "Rwb_d_bar" [n,9] (entrywise, row-major: dL / dR_ab of the expressions as the
+        library evaluates them) and "Rwb_rot_bar", "Rwb_d_rot_bar" [n,3] (world-frame left tangent: the cotangent of delta in
+        R <- exp([delta]x) R).  The gradient is the one on the active face, as sensitivity_batch()'s: valid while the working set
+        holds, one-sided for robots with bit 0 of its flags, NaN for robots with bit 1.  Nothing of `batch` is written.
+        Asynchronous on `stream`, no synchronisation.  Returns the dict of device tensors; ValueError with the library's message for
+        a call it refuses."""
+        launch, res = self.plan_sensitivity_rotation(batch, grf_body, grf_bar, b_bar, feet_bar, want, out, stream)
+        launch()
+        return res
+
+    def control_batch_autograd(self, batch, act_tol=1e-7, flags=None, **control_kwargs):
+        """control_batch() with a gradient: returns (grf_body, status), grf_body carrying a grad_fn whenever any of Rwb, Rwb_d, x,
+        xdot, w, x_d, xdot_d, w_d, feet in `batch` requires grad (quadruped_control_amd/autograd.py).  Forward is exactly
+        control_batch(batch, **control_kwargs); backward is sensitivity_batch() and, if a rotation requires grad,
+        sensitivity_rotation_batch() on the current stream, without host synchronisation, asking only for the cotangents needed;
+        inputs that do not require grad get None.  The rotations' gradients are entrywise ([n,9] as the inputs are).  There is no
+        double backward.  `flags`: an int32 [n] tensor that receives sensitivity_batch()'s flags at backward time.
+        The gradient is the one ON THE ACTIVE FACE at `act_tol`: valid while the working set holds - a loss that moves a robot
+        across a face change sees a kink there -, one-sided for robots whose flags have bit 0 (a foot on both rows of an axis;
+        failed robots among them, with gradient 0), NaN for robots with bit 1 (a bad pivot).  batch["joint_q"].requires_grad raises
+        ValueError: chain the leg Jacobian from feet_bar yourself."""
+        from .autograd import control_batch_autograd
+
+        return control_batch_autograd(self, batch, act_tol, flags, **control_kwargs)
 
     def control_batch_host(self, batch, warm=None, want_active_set=False, want_iterations=False, want_torques=False):
         """n robots, numpy (host) arrays in and out; PCIe-inclusive convenience path."""
@@ -777,6 +854,7 @@ _CERTIFY_OUTPUTS = {"primal": ((), "float64"), "stationarity": ((), "float64"), 
                     "active": ((4,), "uint8"), "flags": ((), "int32")}
 _SENSITIVITY_OUTPUTS = {"adjoint": ((12,), "float64"), "b_bar": ((6,), "float64"), "feet_bar": ((4, 3), "float64"),
                         **{k: ((3,), "float64") for k in ("x_bar", "xdot_bar", "w_bar", "x_d_bar", "xdot_d_bar", "w_d_bar")}, "flags": ((), "int32")}
+_SENSITIVITY_ROT_OUTPUTS = {"Rwb_bar": 9, "Rwb_d_bar": 9, "Rwb_rot_bar": 3, "Rwb_d_rot_bar": 3}  # name -> trailing size (float64)
 
 
 def certify_summary(t):

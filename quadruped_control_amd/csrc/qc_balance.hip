@@ -2309,6 +2309,26 @@ int qc_sensitivity_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc
   return QC_OK;
 }
 
+void qc_default_sensitivity_rot(qc_sensitivity_rot_io* io) {
+  if (!io) return;
+  std::memset(io, 0, sizeof(*io));
+  io->struct_size = sizeof(qc_sensitivity_rot_io);
+}
+
+int qc_sensitivity_rot_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_rot_io* io, void* stream) {
+  if (const int rc = qc::check_sensitivity_rot_args(h, n, in, io); rc != QC_OK || n == 0) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  // the state and the feet, nothing else of `in` (no contact mask: swing feet carry zeros); nothing of it is written
+  qc::BatchIn bi{in->Rwb, in->Rwb_d, in->x, in->xdot, in->w, in->x_d, in->xdot_d, in->w_d, in->feet, nullptr, in->joint_q,
+                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  qc::SensitivityRotArgs a{io->grf_body, io->grf_bar, io->b_bar, io->feet_bar, io->Rwb_bar, io->Rwb_d_bar, io->Rwb_rot_bar, io->Rwb_d_rot_bar};
+  const unsigned blocks = qc::sensitivity_blocks(n);
+  if (in->joint_q) qc::sensitivity_rot_kernel<true><<<dim3(blocks), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, bi, a);
+  else qc::sensitivity_rot_kernel<false><<<dim3(blocks), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, bi, a);
+  QC_HIP(hipGetLastError());
+  return QC_OK;
+}
+
 // host-pointer variant.  Large batches: one device staging allocation, H2D copies, kernel, D2H copies, sync.
 // Small batches (n <= kPinnedMaxN; the reference's own use is one robot per controller tick): the records are packed
 // into a pinned, device-visible host buffer that the kernel reads and writes in place over PCIe - one launch and one

@@ -364,6 +364,67 @@ QC_DEV void angle_axis_total(const double (&m)[9], double (&out)[3]) {
   out[2] = qz * s;
 }
 
+// The reverse pass of angle_axis_total: mb[3 i + j] = sum_k ob[k] d out[k] / d m[3 i + j], entry by entry, of the expressions above
+// as they are evaluated on the branch they take - the same b0 / b1 / b2 selects and the same sign of qw; m need not be a rotation
+// (the nine entries are independent variables; |q| is not taken for 1).  One root for d as in the forward pass, one for n2, one
+// reciprocal for |q|^2 = n2 + qw^2, which is where the derivative of atan2 lives:
+//   out = q_v s,  s = sgn(qw) angle / n,  angle = 2 atan2(n, |qw|):   d angle = 2 (|qw| dn - n d|qw|) / |q|^2,  so with
+//   sb = <q_v, ob>:   qw_bar = -2 sb / |q|^2,   q_v_bar = s ob + sb (2 qw / |q|^2 - s) / n2  q_v     (dn = <q_v, dq_v> / n)
+//   (2 qw / |q|^2 - s is O(n2) for a small angle and cancels to eps there; with sb q_v = O(n2) the term keeps an absolute error of
+//   eps |ob|, next to s ob = 2 ob).
+//   big = sqrt(d) / 2, h = 1 / (2 sqrt(d)):   d_bar = (big_bar - h_bar / d) / (4 sqrt(d)),  and d = 1 +- m00 +- m11 +- m22.
+// n2 == 0 (the error is exactly the identity): the forward pass SELECTS s = 0 there, but the function is smooth - out = q_v s
+// with s -> 2 / qw as n -> 0 - so the reverse pass uses that limit, q_v_bar = (2 / qw) ob, and nothing flows through s (sb = 0).
+// The select's literal zero derivative would be wrong by the whole gradient at the one point every hovering robot sits on.
+// At an error angle of exactly pi (qw = 0 up to the last bit of m) the log is discontinuous for any implementation; the
+// derivative returned is that of the branch evaluated, i.e. of whichever sign qw rounded to.
+QC_DEV void angle_axis_total_bwd(const double (&m)[9], const double (&ob)[3], double (&mb)[9]) {
+  const double tr = m[0] + m[4] + m[8];
+  const bool b0 = tr > 0.0;
+  const bool b1 = !b0 && (m[0] >= m[4]) && (m[0] >= m[8]);
+  const bool b2 = !b0 && !b1 && (m[4] >= m[8]);
+  const bool b3 = !b0 && !b1 && !b2;
+  const double d = 1.0 + (b0 ? tr : (b1 ? (m[0] - m[4] - m[8]) : (b2 ? (m[4] - m[8] - m[0]) : (m[8] - m[0] - m[4]))));
+  const double r = rsqrt_nr(d);
+  const double big = 0.5 * (d * r);
+  const double h = 0.5 * r;
+  const double da = m[7] - m[5], db = m[2] - m[6], dc = m[3] - m[1];
+  const double pxy = m[3] + m[1], pxz = m[6] + m[2], pyz = m[7] + m[5];
+  const double a = da * h, b = db * h, c = dc * h;
+  const double sxy = pxy * h, sxz = pxz * h, syz = pyz * h;
+  const double qw = b0 ? big : (b1 ? a : (b2 ? b : c));
+  const double qx = b0 ? a : (b1 ? big : (b2 ? sxy : sxz));
+  const double qy = b0 ? b : (b1 ? sxy : (b2 ? big : syz));
+  const double qz = b0 ? c : (b1 ? sxz : (b2 ? syz : big));
+  const double n2 = qx * qx + qy * qy + qz * qz;
+  const double rn = rsqrt_nr(n2);
+  const double angle = 2.0 * atan2(n2 * rn, fabs(qw));
+  const bool some = n2 != 0.0;
+  const double iw = rcp_nr(n2 + qw * qw);  // 1 / |q|^2
+  const double lim = 2.0 * (qw * iw);      // 2 qw / |q|^2: s at n2 = 0
+  const double s = some ? (qw < 0.0 ? -angle : angle) * rn : lim;
+  // quaternion -> angle-axis, reversed
+  const double sb = qx * ob[0] + qy * ob[1] + qz * ob[2];
+  const double kq = some ? (sb * (rn * rn)) * (lim - s) : 0.0;
+  const double qwb = some ? -2.0 * (sb * iw) : 0.0;
+  const double qxb = s * ob[0] + kq * qx, qyb = s * ob[1] + kq * qy, qzb = s * ob[2] + kq * qz;
+  // the selects, reversed: each of the seven products lands in at most one quaternion entry per branch
+  const double bigb = b0 ? qwb : (b1 ? qxb : (b2 ? qyb : qzb));
+  const double ab = b0 ? qxb : (b1 ? qwb : 0.0), bb = b0 ? qyb : (b2 ? qwb : 0.0), cb = b0 ? qzb : (b3 ? qwb : 0.0);
+  const double sxyb = b1 ? qyb : (b2 ? qxb : 0.0), sxzb = b1 ? qzb : (b3 ? qxb : 0.0), syzb = b2 ? qzb : (b3 ? qyb : 0.0);
+  const double hb = (da * ab + db * bb + dc * cb) + (pxy * sxyb + pxz * sxzb + pyz * syzb);
+  const double dbar = (0.25 * r) * (bigb - hb * (r * r));
+  mb[0] = (b0 || b1) ? dbar : -dbar;
+  mb[4] = (b0 || b2) ? dbar : -dbar;
+  mb[8] = (b0 || b3) ? dbar : -dbar;
+  mb[7] = (syzb + ab) * h;
+  mb[5] = (syzb - ab) * h;
+  mb[2] = (sxzb + bb) * h;
+  mb[6] = (sxzb - bb) * h;
+  mb[3] = (sxyb + cb) * h;
+  mb[1] = (sxyb - cb) * h;
+}
+
 // Per-robot quantities every formulation needs: r_i = Rwb p_i (BC.cpp:244-248)
 // for the FPL feet this lane owns, and the wrench target b (BC.cpp:126-139,
 // 264-269; replicated in every lane of the group).

@@ -13,6 +13,7 @@
 #include "qc_leg_plant.hpp"
 #include "qc_certify.hpp"
 #include "qc_sensitivity.hpp"
+#include "qc_sensitivity_rot.hpp"
 
 namespace qc {
 
@@ -563,6 +564,26 @@ inline int check_sensitivity_args(const qc_handle* h, size_t n, const qc_batch_i
 inline unsigned sensitivity_blocks(size_t n) {
   const size_t b = (n + SENSITIVITY_BLOCK - 1) / SENSITIVITY_BLOCK;
   return (unsigned)(b < (size_t)SENSITIVITY_MAX_BLOCKS ? b : (size_t)SENSITIVITY_MAX_BLOCKS);
+}
+
+
+// ---------------------------------------------------------------- qc_sensitivity_rot_batch
+// The argument check of the rotation cotangents: what is wrong with the call itself (message prefix "qc_sensitivity_rot_batch:").
+// The grid is the adjoint kernel's (sensitivity_blocks).
+inline int check_sensitivity_rot_args(const qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_rot_io* io) {
+  if (!h || !in || !io) return fail(QC_ERR_INVALID, "qc_sensitivity_rot_batch: null argument");
+  if (const int rc = check_struct_size("qc_sensitivity_rot_batch", "qc_sensitivity_rot_io", "qc_default_sensitivity_rot", io->struct_size, sizeof(qc_sensitivity_rot_io));
+      rc != QC_OK)
+    return rc;
+  if (!io->Rwb_bar && !io->Rwb_d_bar && !io->Rwb_rot_bar && !io->Rwb_d_rot_bar)
+    return fail(QC_ERR_INVALID, "qc_sensitivity_rot_batch: no output requested (Rwb_bar, Rwb_d_bar, Rwb_rot_bar, Rwb_d_rot_bar are all NULL)");
+  if (n == 0) return QC_OK;
+  if (!io->grf_body || !io->grf_bar || !io->b_bar || !io->feet_bar)
+    return fail(QC_ERR_INVALID, "qc_sensitivity_rot_batch: grf_body, grf_bar, b_bar and feet_bar are required");
+  if (!in->Rwb || !in->Rwb_d || !in->x || !in->xdot || !in->w || !in->x_d || !in->xdot_d || !in->w_d)
+    return fail(QC_ERR_INVALID, "qc_sensitivity_rot_batch: the state arrays Rwb, Rwb_d, x, xdot, w, x_d, xdot_d and w_d are required (commander mode is out of scope)");
+  if (!in->feet && !in->joint_q) return fail(QC_ERR_INVALID, "qc_sensitivity_rot_batch: feet or joint_q is required");
+  return check_one_launch("qc_sensitivity_rot_batch", n, SENSITIVITY_BLOCK);
 }
 
 }  // namespace qc

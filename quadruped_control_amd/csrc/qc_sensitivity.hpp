@@ -31,7 +31,7 @@
 //                                             with al_bar = Iw^T b_bar_ang,  w_bar = -kd_w al_bar,  w_d_bar = kd_w al_bar +
 //                                             (kff[3] al_bar[0], kff[4] al_bar[1], kff[5] al_bar[1]) + (Iw w_d) x b_bar_ang +
 //                                             Iw^T (b_bar_ang x w_d)
-// NOT produced: the cotangents of Rwb and Rwb_d (a caller chains them from b_bar, r_bar = Rwb feet_bar and z: INTEGRATION.md); the
+// NOT produced: the cotangents of Rwb and Rwb_d (qc_sensitivity_rot.hpp makes them from b_bar and feet_bar, in a kernel of its own); the
 // cotangents of mu, fzmin, fzmax and the weights; weak activity - a row whose multiplier is about 0 is on the face like any other
 // active row (the caller has the certificate's lambda for that).  Commander mode is out of scope, as for the certificate.
 //

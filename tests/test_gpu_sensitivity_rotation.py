@@ -1,0 +1,388 @@
+"""GPU: qc_sensitivity_rot_batch (csrc/qc_sensitivity_rot.hpp) against the numpy restatement (tests/sensitivity_rotation_restatement.py),
+against the same definitions at 50 digits on the branch sweep, against central differences of control_batch itself, and the
+torch.autograd wrapper (quadruped_control_amd/autograd.py) against the direct calls.
+
+Batch sizes 1, 63, 64, 65 and 130: tail lanes, one wave +- 1 (a workgroup is one wave), more than one workgroup.  The placed forces
+and the handles are test_gpu_kkt_certificate's.  To isolate the kernel from the 12x12 solve both sides are fed the SAME b_bar and
+feet_bar: the device's own, from sensitivity_batch.
+
+The bar against the restatement, per output entry: C eps `terms`, `terms` being the restatement's sum of the magnitudes of the four
+contributions, each evaluated with the absolute values of all its factors - not the result, whose contributions cancel.  C from the
+longest rounded chain, the rotation-error contribution: e_bar = kp_w o (R (Ib^T (R^T ba))) is 3 x 5 + 1 = 16 rounded operations;
+Re = Rwb_d Rwb^T 3; the reverse pass of the log ~45 (d 3, two rsqrt and a reciprocal at 2 each, the seven products 2 each, n2 5,
+atan2 and s 4, sb 5, the q_v_bar 4, h_bar 11, d_bar 4, the entries 2); Re_bar^T Rwb_d 5 and the sum of the four contributions 4;
+the log's own sensitivity to the 3 roundings of Re is of the size of its first derivative for the error angles of these batches
+(<= 0.2 rad, asserted: qw > 0.99), 8 more: 16 + 3 + 45 + 9 + 8 = 81 per evaluation, and the two evaluations may be twice that
+apart: C = 160.  With joint_q the foot positions come from two forward kinematics (three trigonometric factors at 2 eps each and a
+sum of three terms: 8 per evaluation): C = 176.  On the branch sweep the angles go to pi - 1e-7, where the second derivative of the
+log grows as 1 / qw^2 against a first derivative of 1 / |qw|: the bar there is (C + 32 / |qw|) eps terms, twice the CPU test's
+16 / |qw| for one evaluation.  In the 50-digit test the device may be 8 x as far from the 50-digit value as the numpy restatement
+is at its worst, with a floor of 64 eps of the output's scale (test_gpu_sensitivity's rule); both are printed and recorded in
+profiles/sensitivity_rotation.md."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from tests import sensitivity_rotation_restatement as RR
+from tests.test_gpu_kkt_certificate import _inputs, _params
+from tests.test_sensitivity_cpu import fd_batch
+from tests.test_sensitivity_rotation_cpu import FD_H, fd_directions
+
+pytestmark = pytest.mark.gpu
+SIZES = (1, 63, 64, 65, 130)
+EPS = 2.0 ** -52
+SENTINEL = -7777.25
+STATE_KEYS = ("Rwb", "Rwb_d", "x", "xdot", "w", "x_d", "xdot_d", "w_d")
+DIFFERENTIABLE = STATE_KEYS + ("feet",)
+WANT_ALL = RR.OUTPUTS
+
+
+@pytest.fixture(scope="module")
+def q(built):
+    import quadruped_control_amd as q
+
+    return q
+
+
+@pytest.fixture(scope="module")
+def ctl(q):
+    c = q.BalanceController.from_params(_params(q, "uniform"), device=0)
+    yield c
+    c.close()
+
+
+def _gbar(n, seed=0):
+    return np.random.default_rng(5000 + n + seed).normal(0.0, 1.0, (n, 12))
+
+
+def _both(q, ctl, b, grf, gbar, want=WANT_ALL):
+    """sensitivity_batch then sensitivity_rotation_batch on the device; returns (rotation outputs, b_bar, feet_bar, flags) as numpy"""
+    import torch
+
+    dev = q.to_device(b)
+    g, gb = torch.from_numpy(grf).cuda(), torch.from_numpy(gbar).cuda()
+    s = ctl.sensitivity_batch(dev, g, gb, want=("b_bar", "feet_bar", "flags"))
+    r = ctl.sensitivity_rotation_batch(dev, g, gb, s["b_bar"], s["feet_bar"], want=want)
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy() for k, v in r.items()}, s["b_bar"].cpu().numpy(), s["feet_bar"].cpu().numpy(), s["flags"].cpu().numpy()
+
+
+def _assert_close(got, ref, c, what, qw_term=False):
+    c_row = np.full(ref["qw"].shape[0], c) + (32.0 / np.abs(ref["qw"]) if qw_term else 0.0)
+    for k in RR.OUTPUTS:
+        bar = c_row[:, None] * EPS * ref["terms"][k]
+        err = np.abs(got[k] - ref[k])
+        worst = float((err / np.maximum(bar, 1e-300)).max())
+        print(what, k, "worst error / bar", worst)
+        assert np.all(err <= bar), (what, k, worst)
+
+
+@pytest.mark.parametrize("n", SIZES)
+@pytest.mark.parametrize("source", ["feet", "joint_q", "duty"])
+def test_every_output_against_the_restatement(q, ctl, n, source):
+    """Placed forces; `feet` with stance bytes, joint_q with the phase rule (the handle's duty, and gait_duty); all 16 contact masks
+    once n >= 16; the all-swing mask gives exact zeros; even robots have Rwb = Rwb_d = I, the n2 = 0 limit of the log."""
+    P = _params(q, "uniform")
+    b, grf = _inputs(n, source)
+    gbar = _gbar(n)
+    got, b_bar, feet_bar, flags = _both(q, ctl, b, grf, gbar)
+    ref = RR.rotation_cotangents(P, b, grf, gbar, b_bar, feet_bar)
+    assert (ref["qw"] > 0.99).all() and (ref["case"] == -1).all()
+    assert (ref["qw"][0::2] == 1.0).all()  # the limit is in the batch
+    _assert_close(got, ref, 160.0 if source == "feet" else 176.0, (n, source))
+    for i in range(0, n, 16):  # contact pattern 0: every foot swings
+        assert all(not got[k][i].any() for k in RR.OUTPUTS)
+    if n >= 16:
+        assert all(np.abs(got[k]).max() > 0 for k in RR.OUTPUTS) and (flags == 0).all()
+        assert np.abs(got["Rwb_d_bar"][2::16]).max() > 0  # ... and it is not the select's zero derivative
+
+
+@pytest.fixture(scope="module")
+def sweep(q):
+    import torch
+
+    P = dict(q.cheetah_params(mu=0.6), kp_w=np.full(3, 20.0))
+    b, grf, gbar, b_bar, feet_bar, expect = RR.branch_sweep()
+    c = q.BalanceController.from_params(P, device=0)
+    try:
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+        r = c.sensitivity_rotation_batch(q.to_device(b), t(grf), t(gbar), t(b_bar), t(feet_bar), want=WANT_ALL)
+        torch.cuda.synchronize()
+        got = {k: v.cpu().numpy() for k, v in r.items()}
+    finally:
+        c.close()
+    ref = RR.rotation_cotangents(P, b, grf, gbar, b_bar, feet_bar)
+    assert np.array_equal(ref["case"], expect)
+    return dict(P=P, b=b, grf=grf, gbar=gbar, b_bar=b_bar, feet_bar=feet_bar, got=got, ref=ref)
+
+
+def test_branch_sweep_against_the_restatement(sweep):
+    """Every case of RR.branch_sweep (nine axes x angles 0 ... pi - 1e-7 x both signs, and Rwb = Rwb_d = I) on the device against
+    the numpy restatement, which tests/test_sensitivity_rotation_cpu.py holds to 50 digits on the same cases.  The forces and
+    cotangents are arbitrary finite numbers (nothing is solved: the kernel is downstream of the solve)."""
+    _assert_close(sweep["got"], sweep["ref"], 160.0, "sweep", qw_term=True)
+    assert np.isfinite(np.concatenate([sweep["got"][k].reshape(-1) for k in RR.OUTPUTS])).all()
+
+
+def test_branch_sweep_against_50_digits(sweep):
+    """Every case of the sweep, the identity robot included, at 50 digits: the device's and the numpy restatement's distance relative
+    to the output's largest entry, worst over the robots.  The device may be 8 x as far as numpy, floor 64 eps."""
+    c = sweep
+    pick = range(c["ref"]["case"].shape[0])
+    assert set(c["ref"]["case"].tolist()) == {-1, 0, 1, 2} and (c["ref"]["qw"] < 0).any()
+    worst = {k: [0.0, 0.0] for k in RR.OUTPUTS}
+    for i in pick:
+        ref = RR.rotation_cotangents_mp(c["P"], c["b"], c["grf"], c["gbar"], c["b_bar"], c["feet_bar"], i)
+        for k in RR.OUTPUTS:
+            mag = max(RR.magnitude(ref[k]), 1e-300)
+            worst[k][0] = max(worst[k][0], float(RR.distance(c["got"][k][i], ref[k]).max()) / mag)
+            worst[k][1] = max(worst[k][1], float(RR.distance(c["ref"][k][i], ref[k]).max()) / mag)
+    for k, (dev, host) in worst.items():
+        print(f"50-digit {k}: device {dev:.3e} numpy {host:.3e}")
+    for k, (dev, host) in worst.items():
+        assert dev <= 8 * max(host, 8 * EPS), (k, dev, host)
+
+
+def test_finite_differences_of_control_batch(q, ctl):
+    """<Rwb_bar, D> + <Rwb_d_bar, Dd> against control_batch itself at Rwb + k h D, Rwb_d + k h Dd, k = 0, +-1, +-2: ENTRYWISE
+    directions (the matrices leave the manifold; the library evaluates its expressions on the nine numbers as they are), the
+    committed directions and h = 1e-4 of tests/test_sensitivity_rotation_cpu.py on the first 128 robots of its batch, race = 0.  Kept:
+    solved and the same want_active_set word at all five points, flags 0; at least 0.75.  Truncation per robot from the solver alone,
+    t = |FD(h) - FD(2h)|.  Bar: t + 1e-5 |theta_bar| |d| - test_gpu_sensitivity's feet test's rounding term, for the same reason: the
+    forces' absolute error of ~1e-8 N (csrc/qc_host.hpp) over h."""
+    import torch
+
+    ctl.set_tuning(race=0)
+    n, h = 128, FD_H
+    b = fd_batch(n)
+    _, _, D, Dd = (d[:n] for d in fd_directions())
+    gbar = _gbar(n, 6)
+
+    def solve(k):
+        bb = dict(b, Rwb=np.ascontiguousarray(b["Rwb"] + k * h * D), Rwb_d=np.ascontiguousarray(b["Rwb_d"] + k * h * Dd))
+        dev = q.to_device(bb)
+        o = ctl.control_batch(dev, want_active_set=True)
+        torch.cuda.synchronize()
+        return dev, o
+
+    dev0, o0 = solve(0)
+    pts = {k: solve(k)[1] for k in (-2, -1, 1, 2)}
+    gb = torch.from_numpy(gbar).cuda()
+    s = ctl.sensitivity_batch(dev0, o0["grf_body"], gb, want=("b_bar", "feet_bar", "flags"))
+    r = ctl.sensitivity_rotation_batch(dev0, o0["grf_body"], gb, s["b_bar"], s["feet_bar"], want=("Rwb_bar", "Rwb_d_bar"))
+    torch.cuda.synchronize()
+    Rb, Rdb, flags = r["Rwb_bar"].cpu().numpy(), r["Rwb_d_bar"].cpu().numpy(), s["flags"].cpu().numpy()
+    w0 = o0["active_set"].cpu().numpy()
+    keep = (o0["status"].cpu().numpy() == 0) & (flags == 0)
+    for o in pts.values():
+        keep &= (o["status"].cpu().numpy() == 0) & (o["active_set"].cpu().numpy() == w0)
+    F = {k: o["grf_body"].cpu().numpy() for k, o in pts.items()}
+    fd1 = (gbar * (F[1] - F[-1])).sum(axis=1) / (2 * h)
+    fd2 = (gbar * (F[2] - F[-2])).sum(axis=1) / (4 * h)
+    an = (Rb * D).sum(axis=1) + (Rdb * Dd).sum(axis=1)
+    scale = np.sqrt((Rb ** 2).sum(axis=1) + (Rdb ** 2).sum(axis=1)) * np.sqrt((D ** 2).sum(axis=1) + (Dd ** 2).sum(axis=1))
+    err, t = np.abs(fd1 - an), np.abs(fd1 - fd2)
+    rel = lambda v: float((v[keep] / np.maximum(scale[keep], 1e-300)).max())
+    print("kept", keep.mean(), "worst relative error", rel(err), "worst t", rel(t), "worst error beyond t", rel(np.maximum(err - t, 0.0)))
+    assert keep.mean() >= 0.75, keep.mean()
+    assert (scale[keep] > 0).mean() > 0.9
+    assert np.median(t[keep] / np.maximum(scale[keep], 1e-300)) < 1e-6  # (the estimate itself is small: the bar is tight)
+    assert np.all(err[keep] <= t[keep] + 1e-5 * scale[keep])
+
+
+@pytest.mark.parametrize("source", ["feet", "joint_q"])
+def test_poisoned_robot_is_nan_and_its_neighbours_are_untouched(q, ctl, source):
+    """A NaN foot position (or joint angle) of a stance foot under placed forces: qc_sensitivity_batch poisons the robot (bit 1, NaN
+    b_bar and feet_bar), and every rotation output of it is NaN; the robots next to it compare as ever."""
+    P = _params(q, "uniform")
+    n = 65
+    b, grf = _inputs(n, source)
+    b = {k: v.copy() for k, v in b.items()}
+    bad = [15, 47]  # contact pattern 15: four stance feet
+    for i in bad:
+        b["feet" if source == "feet" else "joint_q"][i, 4] = np.nan
+    gbar = _gbar(n, 7)
+    got, b_bar, feet_bar, flags = _both(q, ctl, b, grf, gbar)
+    assert [int(flags[i]) for i in bad] == [2, 2] and np.isnan(b_bar[bad]).all() and np.isnan(feet_bar[bad]).all()
+    for k in RR.OUTPUTS:
+        assert np.isnan(got[k][bad]).all(), k
+    good = np.setdiff1d(np.arange(n), bad)
+    clean = {k: v[good] for k, v in b.items()}
+    ref = RR.rotation_cotangents(P, clean, grf[good], gbar[good], b_bar[good], feet_bar[good])
+    _assert_close({k: v[good] for k, v in got.items()}, ref, 160.0 if source == "feet" else 176.0, ("poison", source))
+
+
+def test_inputs_untouched_repeatable_and_capturable_as_a_pair(q, ctl):
+    """The inputs are left bit-identical, a second call repeats the first bit for bit, and sensitivity -> sensitivity_rotation
+    captured into one graph on one stream (no parallel branches) and replayed gives the same bits."""
+    import torch
+
+    n = 130
+    b, grf = _inputs(n, "feet")
+    dev = q.to_device(b)
+    before = {k: v.clone() for k, v in dev.items()}
+    g, gb = torch.from_numpy(grf).cuda(), torch.from_numpy(_gbar(n, 5)).cuda()
+    s = ctl.sensitivity_batch(dev, g, gb, want=("b_bar", "feet_bar"))
+    kept = [t.clone() for t in (g, gb, s["b_bar"], s["feet_bar"])]
+    first = ctl.sensitivity_rotation_batch(dev, g, gb, s["b_bar"], s["feet_bar"], want=WANT_ALL)
+    second = ctl.sensitivity_rotation_batch(dev, g, gb, s["b_bar"], s["feet_bar"], want=WANT_ALL)
+    torch.cuda.synchronize()
+    assert all(torch.equal(dev[k], before[k]) for k in before)
+    assert all(torch.equal(a, c) for a, c in zip((g, gb, s["b_bar"], s["feet_bar"]), kept))
+    for k in WANT_ALL:
+        assert torch.equal(first[k], second[k]), k
+    graph = torch.cuda.CUDAGraph()
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):
+        l1, s2 = ctl.plan_sensitivity(dev, g, gb, want=("b_bar", "feet_bar"), stream=stream)
+        l2, out = ctl.plan_sensitivity_rotation(dev, g, gb, s2["b_bar"], s2["feet_bar"], want=WANT_ALL, stream=stream)
+        torch.cuda.synchronize()
+        with torch.cuda.graph(graph, stream=stream):
+            l1()
+            l2()
+    for v in list(out.values()) + list(s2.values()):
+        v.zero_()
+    graph.replay()
+    torch.cuda.synchronize()
+    for k in WANT_ALL:
+        assert torch.equal(out[k], first[k]), k
+
+
+def test_refusals_raise_and_launch_nothing(q, ctl):
+    """Each refusal of qc_sensitivity_rot_batch raises ValueError with the library's message and launches nothing: the output tensor
+    keeps its sentinel."""
+    import torch
+    from quadruped_control_amd import _lib
+
+    n = 65
+    b, grf = _inputs(n, "feet")
+    dev = q.to_device(b)
+    g, gb = torch.from_numpy(grf).cuda(), torch.from_numpy(_gbar(n)).cuda()
+    bb, fb = torch.zeros((n, 6), dtype=torch.float64, device="cuda"), torch.zeros((n, 4, 3), dtype=torch.float64, device="cuda")
+    out = {"Rwb_bar": torch.full((n, 9), SENTINEL, dtype=torch.float64, device="cuda")}
+
+    def refused(batch, *inputs, **kw):
+        with pytest.raises(ValueError, match=r"^qc_sensitivity_rot_batch:"):
+            ctl.sensitivity_rotation_batch(batch, *inputs, want=kw.pop("want", ("Rwb_bar",)), out=kw.pop("out", out), **kw)
+
+    for m in range(4):
+        refused(dev, *[None if k == m else t for k, t in enumerate((g, gb, bb, fb))])
+    for k in STATE_KEYS:
+        refused({a: v for a, v in dev.items() if a != k}, g, gb, bb, fb)
+    refused({a: v for a, v in dev.items() if a not in ("Rwb_d", "x_d", "xdot_d", "w_d")}, g, gb, bb, fb)  # a commander-mode batch
+    refused({a: v for a, v in dev.items() if a != "feet"}, g, gb, bb, fb)
+    refused(dev, g, gb, bb, fb, want=(), out=None)
+    lib = _lib.load()
+    io = _lib.QcSensitivityRotIo()
+    lib.qc_default_sensitivity_rot(ctypes.byref(io))
+    io.grf_body, io.grf_bar, io.b_bar, io.feet_bar, io.Rwb_bar = g.data_ptr(), gb.data_ptr(), bb.data_ptr(), fb.data_ptr(), out["Rwb_bar"].data_ptr()
+    bi = _lib.QcBatchIn()
+    for k in STATE_KEYS + ("feet",):
+        setattr(bi, k, dev[k].data_ptr())
+    calls = [(None, n, ctypes.byref(bi), ctypes.byref(io)), (ctl._h, n, None, ctypes.byref(io)), (ctl._h, n, ctypes.byref(bi), None),
+             (ctl._h, 0xFFFFFF * 64 + 1, ctypes.byref(bi), ctypes.byref(io))]
+    for h, m, pin, pio in calls:
+        assert lib.qc_sensitivity_rot_batch(h, m, pin, pio, None) == -1 and _lib.last_error().startswith("qc_sensitivity_rot_batch:")
+    io.struct_size = 64
+    assert lib.qc_sensitivity_rot_batch(ctl._h, n, ctypes.byref(bi), ctypes.byref(io), None) == -1
+    assert _lib.last_error().startswith("qc_sensitivity_rot_batch: qc_sensitivity_rot_io.struct_size")
+    io.struct_size = 72
+    assert lib.qc_sensitivity_rot_batch(ctl._h, 0, ctypes.byref(bi), ctypes.byref(io), None) == 0  # n == 0: QC_OK, nothing launched
+    torch.cuda.synchronize()
+    assert bool((out["Rwb_bar"] == SENTINEL).all())
+    assert lib.qc_sensitivity_rot_batch(ctl._h, n, ctypes.byref(bi), ctypes.byref(io), None) == 0  # and the same structs, valid, do launch
+    torch.cuda.synchronize()
+    assert not bool((out["Rwb_bar"] == SENTINEL).any())
+
+
+# ------------------------------------------------------------------ the autograd wrapper
+@pytest.fixture(scope="module")
+def solved_autograd(q, ctl):
+    """130 robots solved by control_batch, and the direct sensitivity + sensitivity_rotation outputs for one cotangent"""
+    import torch
+
+    ctl.set_tuning(race=0)
+    n = 130
+    b = fd_batch(n)
+    dev = q.to_device(b)
+    o = ctl.control_batch(dev)
+    gb = torch.from_numpy(_gbar(n, 9)).cuda()
+    s = ctl.sensitivity_batch(dev, o["grf_body"], gb, want=tuple(k + "_bar" for k in DIFFERENTIABLE[2:]) + ("b_bar", "flags"))
+    s.update(ctl.sensitivity_rotation_batch(dev, o["grf_body"], gb, s["b_bar"], s["feet_bar"], want=("Rwb_bar", "Rwb_d_bar")))
+    torch.cuda.synchronize()
+    return dict(b=b, out=o, gbar=gb, direct=s)
+
+
+def _leaves(q, b, requires):
+    dev = q.to_device(b)
+    for k in requires:
+        dev[k].requires_grad_(True)
+    return dev
+
+
+def test_autograd_equals_the_direct_calls_bit_for_bit(q, ctl, solved_autograd):
+    import torch
+
+    c = solved_autograd
+    dev = _leaves(q, c["b"], DIFFERENTIABLE)
+    flags = torch.full((130,), -1, dtype=torch.int32, device="cuda")
+    grf, status = ctl.control_batch_autograd(dev, flags=flags)
+    assert grf.grad_fn is not None and not status.requires_grad
+    assert torch.equal(grf.detach(), c["out"]["grf_body"]) and torch.equal(status, c["out"]["status"])  # forward is control_batch
+    grads = torch.autograd.grad(grf, [dev[k] for k in DIFFERENTIABLE], c["gbar"])
+    torch.cuda.synchronize()
+    for k, g in zip(DIFFERENTIABLE, grads):
+        assert g.shape == dev[k].shape and torch.equal(g.reshape(-1), c["direct"][k + "_bar"].reshape(-1)), k
+    assert torch.equal(flags, c["direct"]["flags"])
+    assert float(grads[0].abs().max()) > 0 and float(grads[1].abs().max()) > 0
+
+
+def test_autograd_asks_only_for_what_is_needed(q, ctl, solved_autograd, monkeypatch):
+    """Inputs that do not require grad give None; with only x requiring grad the rotation kernel is not launched (backward has no
+    output of its own for it to leave a sentinel in: the call behind it is watched and never made); with only Rwb_d the rotation
+    kernel is asked for Rwb_d_bar alone."""
+    import torch
+
+    c = solved_autograd
+    calls = []
+    real = ctl.sensitivity_rotation_batch
+
+    def spy(*a, **kw):
+        calls.append(kw.get("want"))
+        return real(*a, **kw)
+
+    monkeypatch.setattr(ctl, "sensitivity_rotation_batch", spy)
+    dev = _leaves(q, c["b"], ("x",))
+    grf, _ = ctl.control_batch_autograd(dev)
+    grf.backward(c["gbar"])
+    torch.cuda.synchronize()
+    assert calls == []
+    assert torch.equal(dev["x"].grad, c["direct"]["x_bar"])
+    assert all(dev[k].grad is None for k in DIFFERENTIABLE if k != "x")
+    dev = _leaves(q, c["b"], ("Rwb_d",))
+    grf, _ = ctl.control_batch_autograd(dev)
+    got = torch.autograd.grad(grf, [dev["Rwb_d"]], c["gbar"])[0]
+    torch.cuda.synchronize()
+    assert calls == [("Rwb_d_bar",)] and torch.equal(got, c["direct"]["Rwb_d_bar"])
+    dev = _leaves(q, c["b"], ())
+    grf, status = ctl.control_batch_autograd(dev)
+    assert grf.grad_fn is None and not grf.requires_grad  # nothing requires grad: plain control_batch
+
+
+def test_autograd_refuses_joint_q_and_a_second_backward(q, ctl, solved_autograd):
+    import torch
+    from quadruped_control_amd import workloads
+
+    c = solved_autograd
+    bj = workloads.with_joint_angles(c["b"])
+    dev = _leaves(q, bj, ("joint_q",))
+    with pytest.raises(ValueError, match="joint_q"):
+        ctl.control_batch_autograd(dev)
+    dev = _leaves(q, c["b"], ("Rwb", "w"))
+    grf, _ = ctl.control_batch_autograd(dev)
+    grf.backward(c["gbar"])
+    with pytest.raises(RuntimeError, match="backward through the graph a second time"):
+        grf.backward(c["gbar"])
+    torch.cuda.synchronize()
+    assert torch.equal(dev["Rwb"].grad, c["direct"]["Rwb_bar"]) and torch.equal(dev["w"].grad, c["direct"]["w_bar"])

@@ -1,0 +1,248 @@
+"""CPU: the rotation cotangents' numpy restatement (tests/sensitivity_rotation_restatement.py) against central differences of the C
+oracle and against its own 50-digit variant, and the C ABI of qc_sensitivity_rot_batch as far as it goes without a device."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+from scipy.spatial.transform import Rotation
+
+import quadruped_control_amd as q
+from tests import sensitivity_restatement as SR
+from tests import sensitivity_rotation_restatement as RR
+from tests.test_sensitivity_cpu import N_FD, _check_kept, _kept, fd_batch
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+EPS = 2.0 ** -52
+FD_H = 1e-4  # the step the sweep below settled on; tests/test_gpu_sensitivity_rotation.py uses it too
+
+
+def fd_directions(n=N_FD):
+    """the committed directions: (delta, delta_d) [n, 3] tangent directions and (D, Dd) [n, 9] entrywise ones"""
+    rng = np.random.default_rng(8)
+    return rng.normal(0.0, 1.0, (n, 3)), rng.normal(0.0, 1.0, (n, 3)), rng.normal(0.0, 1.0, (n, 9)), rng.normal(0.0, 1.0, (n, 9))
+
+
+def rotate(b, delta, delta_d, h):
+    """the batch at exp(h [delta]x) Rwb, exp(h [delta_d]x) Rwb_d"""
+    n = b["x"].shape[0]
+    turn = lambda d, R: np.ascontiguousarray((Rotation.from_rotvec(h * d).as_matrix() @ R.reshape(n, 3, 3)).reshape(n, 9))
+    return dict(b, Rwb=turn(delta, b["Rwb"]), Rwb_d=turn(delta_d, b["Rwb_d"]))
+
+
+@pytest.fixture(scope="module")
+def solved(built):
+    from oracle import c_oracle
+
+    P = q.cheetah_params(mu=0.6)
+    b = fd_batch()
+    gbar = np.random.default_rng(5).normal(0.0, 1.0, (N_FD, 12))
+    F0, st0, _ = c_oracle.control_batch(P, b)
+    s = SR.sensitivity(P, b, F0, gbar)
+    r = RR.rotation_cotangents(P, b, F0, gbar, s["b_bar"], s["feet_bar"])
+    return dict(P=P, b=b, gbar=gbar, F0=F0, st0=st0, s=s, r=r)
+
+
+def test_rotation_cotangents_against_oracle_differences(solved):
+    """<Rwb_rot_bar, delta> + <Rwb_d_rot_bar, delta_d> against central differences of the C oracle's forces along the paths
+    exp(h [delta]x) Rwb, exp(h [delta_d]x) Rwb_d: test_feet_cotangent_against_oracle_differences' setup - the 480-robot fd_batch,
+    solves at 0, +-h, +-2h, truncation estimated per robot from the oracle alone, t = |FD(h) - FD(2h)|, bar t + 1e-7 |theta_bar| |d|
+    (1e-7: that test's rounding term, oracle force error / h), its _kept rule, >= 0.75 kept with all 15 patterns among them.
+
+    ON-MANIFOLD paths and the two tangent outputs, not entrywise directions: neither the oracle nor the library refuses a matrix
+    that is not a rotation, but the keep rule does - it classifies the world-frame forces -Rwb grf_body, and grf_body = -Rwb^T f
+    comes back as Rwb Rwb^T f, off by h |f| ~ 1e-2 N for an entrywise step: every pinned row reads as inactive at act_tol and 2 %
+    of the robots are kept (on those 2 % the entrywise outputs agree with the entrywise quotient to 1.8e-8 at h = 1e-4).  The
+    entrywise outputs are tied to the tangent ones by test_tangent_outputs_are_the_projection_of_the_entrywise_ones, checked
+    against the 50-digit variant below and against entrywise differences of control_batch itself on the GPU, where kept is judged
+    by the solver's working-set word.
+
+    The sweep on the oracle (committed seed; worst over the kept robots, relative to |theta_bar| |d|):
+      h      kept   worst error  worst t    median error
+      1e-3   0.860  3.8e-05      1.1e-04    4.1e-07
+      1e-4   0.960  3.8e-07      1.1e-06    4.4e-09
+      1e-5   0.983  6.3e-06      1.9e-05    5.0e-11
+      1e-6   0.998  1.5e-06      9.6e-07    8.9e-12      (one robot beyond the bar: rounding)
+      1e-7   1.000  1.1e-05      1.5e-05    8.2e-11      (beyond the bar)
+    The worst robot's error falls as h^2 from 1e-3 to 1e-4 and is rounding (oracle force error / h on the robots whose reduced
+    Hessian is carried by W alone) from 1e-5 down: h = 1e-4, as for the feet.  Kept share of the committed seed at h = 1e-4: 0.96,
+    all 15 patterns among the kept."""
+    c = solved
+    P, b, n, h = c["P"], c["b"], N_FD, FD_H
+    delta, delta_d, _, _ = fd_directions()
+
+    def at(k):
+        from oracle import c_oracle
+        from tests import kkt_certificate_restatement as KR
+
+        bb = rotate(b, delta, delta_d, k * h)
+        F, st, _ = c_oracle.control_batch(P, bb)
+        return F, st, KR.certificate(P, bb, F)["active"]
+
+    pts = {k: at(k) for k in (-2, -1, 1, 2)}
+    keep = _kept(c, pts.values())
+    print("kept", keep.mean())
+    _check_kept(c, keep)
+    fd1 = (c["gbar"] * (pts[1][0] - pts[-1][0])).sum(axis=1) / (2 * h)
+    fd2 = (c["gbar"] * (pts[2][0] - pts[-2][0])).sum(axis=1) / (4 * h)
+    r = c["r"]
+    an = (r["Rwb_rot_bar"] * delta).sum(axis=1) + (r["Rwb_d_rot_bar"] * delta_d).sum(axis=1)
+    scale = np.sqrt((r["Rwb_rot_bar"] ** 2).sum(axis=1) + (r["Rwb_d_rot_bar"] ** 2).sum(axis=1)) * np.sqrt((delta ** 2).sum(axis=1) + (delta_d ** 2).sum(axis=1))
+    err, t = np.abs(fd1 - an), np.abs(fd1 - fd2)
+    rel = lambda v: float((v[keep] / np.maximum(scale[keep], 1e-300)).max())
+    print("worst relative error", rel(err), "worst t", rel(t))
+    assert (scale[keep] > 0).mean() > 0.9
+    assert np.median(t[keep] / np.maximum(scale[keep], 1e-300)) < 1e-6  # (the bar is tight: the estimate itself is small)
+    assert np.all(err[keep] <= t[keep] + 1e-7 * scale[keep])
+
+
+def test_each_contribution_is_needed(solved):
+    """Not a bar but a guard on the test above: leaving any one of the four contributions out of Rwb_rot_bar moves the analytic value
+    by far more than that test's bar on most kept robots, so that test does see each of them."""
+    c = solved
+    b, r = c["b"], c["r"]
+    delta = fd_directions()[0]
+    R = b["Rwb"].reshape(N_FD, 3, 3)
+    solvedm = (c["st0"] == 0) & (c["s"]["flags"] == 0)
+    full = np.sqrt((r["Rwb_rot_bar"] ** 2).sum(axis=1) + (r["Rwb_d_rot_bar"] ** 2).sum(axis=1)) * np.linalg.norm(delta, axis=1)
+    for k in range(4):
+        part = np.array([RR.axial(r["contributions"][i, k].reshape(3, 3) @ R[i].T) @ delta[i] for i in range(N_FD)])
+        assert np.mean(np.abs(part[solvedm]) > 1e-4 * full[solvedm]) > 0.5, k
+
+
+@pytest.fixture(scope="module")
+def sweep():
+    P = dict(q.cheetah_params(mu=0.6), kp_w=np.full(3, 20.0))
+    b, grf, gbar, b_bar, feet_bar, expect = RR.branch_sweep()
+    return dict(P=P, b=b, grf=grf, gbar=gbar, b_bar=b_bar, feet_bar=feet_bar, expect=expect, r=RR.rotation_cotangents(P, b, grf, gbar, b_bar, feet_bar))
+
+
+def test_restatement_against_50_digits_on_every_branch(sweep):
+    """The float64 restatement against rotation_cotangents_mp on the branch sweep (RR.branch_sweep: nine axes, angles 0 ... pi - 1e-7,
+    both signs, and Rwb = Rwb_d = I exactly): the branch each case takes is asserted - all four of Eigen's are hit, and the
+    negative-qw side of each pivot branch - and the 50-digit variant takes the same one.
+    Bar per robot and output: the restatement's Jacobian of the log is exact on the double Re it is handed, but Re = Rwb_d Rwb^T is
+    itself rounded (3 eps on |Rwb_d| |Rwb|^T <= 3 eps sqrt(3)), which the 50-digit variant is not; the log's second derivative grows
+    as 1 / qw^2 towards pi against a first derivative of 1 / |qw|, so the relative error of J is up to ~6 eps / |qw| there
+    (|qw| >= 5e-8 at pi - 1e-7: 3e-8).  Everything else is chains of < 40 rounded operations on the magnitude sums `terms`.  The bar
+    is (64 + 16 / |qw|) eps terms."""
+    c = sweep
+    r, n = c["r"], c["expect"].shape[0]
+    assert np.array_equal(r["case"], c["expect"]), np.flatnonzero(r["case"] != c["expect"])
+    assert set(r["case"].tolist()) == {-1, 0, 1, 2}
+    assert all(((r["case"] == k) & (r["qw"] < 0)).any() and ((r["case"] == k) & (r["qw"] > 0)).any() for k in (0, 1, 2))
+    eye = np.eye(3).reshape(9)
+    assert r["qw"][-1] == 1.0 and np.array_equal(c["b"]["Rwb"][-1], eye) and np.array_equal(c["b"]["Rwb_d"][-1], eye)  # the n2 = 0 robot
+    worst = {k: 0.0 for k in RR.OUTPUTS}
+    for i in range(n):
+        ref = RR.rotation_cotangents_mp(c["P"], c["b"], c["grf"], c["gbar"], c["b_bar"], c["feet_bar"], i)
+        assert ref["case"] == r["case"][i]
+        for k in RR.OUTPUTS:
+            dist = RR.distance(r[k][i], ref[k])
+            bar = (64 + 16 / abs(r["qw"][i])) * EPS * r["terms"][k][i]
+            worst[k] = max(worst[k], float((dist / np.maximum(bar, 1e-300)).max()))
+            assert np.all(dist <= bar), (i, k, float(dist.max()), bar)
+    print("worst error / bar", worst)
+
+
+def test_identity_error_uses_the_smooth_limit(sweep):
+    """Rwb = Rwb_d = I: the forward log selects 0 at n2 = 0; its derivative there is the limit - J = the axial map (de = axial(dRe) / 1,
+    s = 2 / qw = 2, h = 1 / 4 ... ) - not 0: Rwb_d_bar of that robot is not zero, and the 50-digit central difference, which
+    straddles the point, agrees (test_restatement_against_50_digits_on_every_branch includes the robot)."""
+    e, J, case, qw = RR.log_jacobian(np.eye(3))
+    assert case == -1 and qw == 1.0 and not e.any()
+    expect = np.zeros((3, 9))
+    expect[0, 7], expect[0, 5], expect[1, 2], expect[1, 6], expect[2, 3], expect[2, 1] = 0.5, -0.5, 0.5, -0.5, 0.5, -0.5
+    assert np.array_equal(J, expect)
+    assert np.abs(sweep["r"]["Rwb_d_bar"][-1]).max() > 0
+
+
+def test_tangent_outputs_are_the_projection_of_the_entrywise_ones(sweep, solved):
+    """Rwb_rot_bar = axial(Rwb_bar Rwb^T) and the same for Rwb_d, on the sweep and on the solved batch: the two are computed from the
+    same matrix, so the bar is the projection's own rounding, 8 eps of its magnitude sum."""
+    for c in (sweep, solved):
+        r, b = c["r"], c["b"]
+        for name, key in (("Rwb", "Rwb"), ("Rwb_d", "Rwb_d")):
+            X = b[key].reshape(-1, 3, 3)
+            for i in range(X.shape[0]):
+                t = RR.axial(r[name + "_bar"][i].reshape(3, 3) @ X[i].T)
+                assert np.all(np.abs(t - r[name + "_rot_bar"][i]) <= 8 * EPS * r["terms"][name + "_rot_bar"][i]), (name, i)
+
+
+def test_swing_only_and_poisoned_robots(solved):
+    """All-zero forces and cotangents (contact pattern 0 as qc_sensitivity_batch leaves it): every output exactly 0.  NaN b_bar and
+    feet_bar (a robot it poisoned): every output NaN."""
+    P, b = solved["P"], {k: v[:2] for k, v in solved["b"].items()}
+    z = np.zeros((2, 12))
+    r = RR.rotation_cotangents(P, b, z, np.ones((2, 12)), np.zeros((2, 6)), np.zeros((2, 4, 3)))
+    assert all(not r[k].any() for k in RR.OUTPUTS)
+    r = RR.rotation_cotangents(P, b, z + 1.0, np.ones((2, 12)), np.full((2, 6), np.nan), np.full((2, 4, 3), np.nan))
+    assert all(np.isnan(r[k]).all() for k in RR.OUTPUTS)
+
+
+# ------------------------------------------------------------------ the C ABI without a device
+IO_POINTERS = ("grf_body", "grf_bar", "b_bar", "feet_bar", "Rwb_bar", "Rwb_d_bar", "Rwb_rot_bar", "Rwb_d_rot_bar")
+
+
+def test_symbols_are_exported_and_the_abi_stays(built):
+    from quadruped_control_amd import _lib
+
+    lib = ctypes.CDLL(os.path.join(ROOT, "quadruped_control_amd", "libqc_balance.so"))
+    for name in ("qc_default_sensitivity_rot", "qc_sensitivity_rot_batch"):
+        assert hasattr(lib, name) and name in _lib.EXPORTS, name
+    assert _lib.load().qc_abi_version() == 6 and _lib.ABI_VERSION == 6  # new entry points, no change to what existed
+    assert ctypes.sizeof(_lib.QcSensitivityIo) == 112
+
+
+def test_mirror_matches_the_header(built, tmp_path):
+    """sizeof and the member offsets of qc_sensitivity_rot_io as the C compiler lays the header's struct out, against the ctypes
+    mirror; qc_default_sensitivity_rot fills the io as documented and needs no device."""
+    from quadruped_control_amd import _lib
+
+    fields = [f for f, _ in _lib.QcSensitivityRotIo._fields_]
+    assert fields == ["struct_size"] + list(IO_POINTERS)
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "qc_balance.h"\nint main(void) {\n  printf("%zu", sizeof(qc_sensitivity_rot_io));\n'
+                   + "".join(f'  printf(" %zu", offsetof(qc_sensitivity_rot_io, {f}));\n' for f in fields) + '  return 0;\n}\n')
+    exe = tmp_path / "layout"
+    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = [int(v) for v in subprocess.run([str(exe)], stdout=subprocess.PIPE, text=True, check=True).stdout.split()]
+    assert got[0] == ctypes.sizeof(_lib.QcSensitivityRotIo) == 72
+    assert got[1:] == [getattr(_lib.QcSensitivityRotIo, f).offset for f in fields]
+    io = _lib.QcSensitivityRotIo()
+    io.grf_body, io.Rwb_bar, io.struct_size = 123, 456, 7
+    _lib.load().qc_default_sensitivity_rot(ctypes.byref(io))
+    assert io.struct_size == 72
+    assert all(getattr(io, f) is None for f in IO_POINTERS)
+
+
+def test_argument_check_needs_no_device(built):
+    """qc_sensitivity_rot_batch refuses a bad call before it touches the device - the handle is null, so every call below ends in the
+    argument check - and each message is its own."""
+    from quadruped_control_amd import _lib
+
+    lib = _lib.load()
+    io = _lib.QcSensitivityRotIo()
+    lib.qc_default_sensitivity_rot(ctypes.byref(io))
+    bi = _lib.QcBatchIn()
+    assert lib.qc_sensitivity_rot_batch(None, 1, ctypes.byref(bi), ctypes.byref(io), None) == -1
+    assert _lib.last_error() == "qc_sensitivity_rot_batch: null argument"
+    assert lib.qc_sensitivity_rot_batch(None, 0, ctypes.byref(bi), None, None) == -1 and _lib.last_error() == "qc_sensitivity_rot_batch: null argument"
+    assert lib.qc_sensitivity_rot_batch(None, 1, None, ctypes.byref(io), None) == -1 and _lib.last_error() == "qc_sensitivity_rot_batch: null argument"
+
+
+def test_host_logic_without_a_device():
+    """check_sensitivity_rot_args through every refusal - a null handle, `in` or `io`, a wrong struct_size, each missing input, no
+    output, each missing state array, a commander-mode batch, neither feet nor joint_q, n beyond one launch - with its message
+    (csrc/qc_host.hpp), in a stand-alone program built with the address and undefined-behaviour sanitizers
+    (tests/cpp/sensitivity_rot_host_test.cpp)."""
+    import __graft_entry__ as g
+
+    assert "sensitivity_rot_host_test" in g.HOST_TESTS
+    exe = g.build_host_test("sensitivity_rot_host_test")
+    assert exe is not None and os.path.exists(exe)
+    libs = subprocess.run(["ldd", exe], stdout=subprocess.PIPE, text=True, check=True).stdout
+    assert "amdhip64" not in libs and "qc_balance" not in libs, libs
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
+    assert r.returncode == 0 and "sensitivity rotation host logic ok" in r.stdout, r.stdout[-3000:]
