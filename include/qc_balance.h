@@ -522,6 +522,52 @@ void qc_default_sensitivity_rot(qc_sensitivity_rot_io* io);
  * joint_q, or n beyond one launch. */
 int qc_sensitivity_rot_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_rot_io* io, void* stream);
 
+/* Differentiating a rollout: the reverse pass of qc_plant_step_batch.  Given the state BEFORE a step (Rwb, x, xdot, w), the grf_body
+ * and foot_world that step read, its dt, and cotangents on what it wrote (Rwb', x', xdot', w' and the optional feet'), this writes
+ * the cotangents of Rwb, x, xdot, w, grf_body and foot_world: the transpose-Jacobian of the step exactly as the library evaluates it.
+ * Nothing is saved by the forward call; the step is recomputed.  Matrix cotangents are ENTRYWISE and row-major (dL / dR_ab, the nine
+ * entries of Rwb taken as independent - qc_sensitivity_rot_io.Rwb_bar's convention, so the two add up); no left-tangent form is made.
+ * With Rn = Rwb' = E Rwb, E = Exp(phi) = I + A K + B K^2, K = hat(phi), phi = dt w', the reverse pass is
+ *   feet'_l = Rn^T d_l, d_l = foot_world_l - x':  Rn_bar += d_l feet_bar_l^T,  d_bar_l = Rn feet_bar_l,  foot_world_bar_l += d_bar_l,
+ *                                                 x'_bar -= d_bar_l
+ *   Rn = E Rwb:                                   E_bar = Rn_bar Rwb^T,  Rwb_bar += E^T Rn_bar
+ *   E = Exp(phi):                                 phi_bar = vee(K_bar - K_bar^T) + (A_bar A1 + B_bar B1) phi,
+ *                                                 K_bar = A E_bar + B (E_bar K^T + K^T E_bar),  A_bar = <E_bar, K>,  B_bar = <E_bar, K^2>,
+ *                                                 A1 = (cos theta - A) / theta^2,  B1 = (A - 2 B) / theta^2 - evaluated as series in
+ *                                                 theta^2 below theta = 1 (limits -1/3 and -1/12: at theta = 0 exactly the smooth limit
+ *                                                 is differentiated, not the step's select) and as the quotients above it
+ *   the semi-implicit Euler step, wdot = Rwb Ib^-1 Rwb^T (tau - w x (Rwb Ib Rwb^T w)) into Rwb_bar, w_bar and tau_bar, and
+ *   tau = sum r_l x f_l, r_l = foot_world_l - x, f_l = -Rwb grf_body_l:  f_bar_l = fs_bar + tau_bar x r_l,  r_bar_l = f_l x tau_bar,
+ *                                                 grf_bar_l = -Rwb^T f_bar_l,  Rwb_bar += -f_bar_l grf_body_l^T.
+ * NOT produced: the cotangents of mass, Ib and dt.  Outputs are written, not accumulated.  Non-finite inputs propagate as NaN;
+ * nothing is clamped.  Each robot's inputs are all read before any of its outputs is written, and a robot touches its own rows
+ * only: an output may be the SAME array as an input cotangent of the same layout (x_bar over x_next_bar, Rwb_bar over
+ * Rwb_next_bar, foot_world_bar or grf_bar over feet_next_bar, ...), so backpropagation through time runs in place.  The six state
+ * and force inputs are never written.  All pointers are DEVICE pointers. */
+typedef struct qc_plant_adjoint_io {
+  size_t struct_size;            /* = sizeof(qc_plant_adjoint_io); checked                                              */
+  const double *Rwb, *x, *xdot, *w; /* [n][9], [n][3], [n][3], [n][3]: the state BEFORE the step                        */
+  const double* grf_body;        /* [n][4][3] the forces the step read                                                  */
+  const double* foot_world;      /* [n][4][3] the feet the step read                                                    */
+  const double* Rwb_next_bar;    /* [n][9]    cotangents on the step's outputs: each optional (NULL = zero),            */
+  const double* x_next_bar;      /* [n][3]    at least one given                                                        */
+  const double* xdot_next_bar;   /* [n][3]                                                                              */
+  const double* w_next_bar;      /* [n][3]                                                                              */
+  const double* feet_next_bar;   /* [n][4][3] on qc_plant_io.feet                                                       */
+  double* Rwb_bar;               /* [n][9]    outputs: each optional, at least one given                                */
+  double *x_bar, *xdot_bar, *w_bar; /* [n][3] each                                                                      */
+  double* grf_bar;               /* [n][4][3] on grf_body: the grf_bar qc_sensitivity_batch takes                       */
+  double* foot_world_bar;        /* [n][4][3]                                                                           */
+  double dt;                     /* seconds, finite, > 0: the step's                                                    */
+} qc_plant_adjoint_io;
+/* struct_size set, pointers NULL, dt = 1/300. */
+void qc_default_plant_adjoint(qc_plant_adjoint_io* io);
+/* Asynchronous on `stream`, no host synchronisation (graph-capturable); n == 0 launches nothing and returns QC_OK.
+ * QC_ERR_INVALID (message starting with "qc_plant_step_adjoint_batch:", nothing launched) for a null handle or `io`, a wrong
+ * struct_size, a dt that is not finite and > 0, no input cotangent at all, no output at all, a missing Rwb, x, xdot, w, grf_body or
+ * foot_world, n beyond one launch, or a handle whose mass or Ib qc_plant_step_batch refuses. */
+int qc_plant_step_adjoint_batch(qc_handle* h, size_t n, const qc_plant_adjoint_io* io, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

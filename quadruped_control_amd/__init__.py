@@ -26,4 +26,8 @@ def __getattr__(name):
         from . import balance_controller as _bc
 
         return getattr(_bc, name)
+    if name in ("control_batch_autograd", "plant_step_autograd", "rollout_autograd"):
+        from . import autograd as _ag
+
+        return getattr(_ag, name)
     raise AttributeError(name)

@@ -62,6 +62,12 @@ class QcPlantIo(C.Structure):
                 ("grf_body", C.c_void_p), ("foot_world", C.c_void_p), ("feet", C.c_void_p), ("dt", C.c_double)]
 
 
+class QcPlantAdjointIo(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t)] + [(k, C.c_void_p) for k in
+                ("Rwb", "x", "xdot", "w", "grf_body", "foot_world", "Rwb_next_bar", "x_next_bar", "xdot_next_bar", "w_next_bar", "feet_next_bar",
+                 "Rwb_bar", "x_bar", "xdot_bar", "w_bar", "grf_bar", "foot_world_bar")] + [("dt", C.c_double)]
+
+
 class QcLegPlantIo(C.Structure):
     _fields_ = [("struct_size", C.c_size_t)] + [(k, C.c_void_p) for k in
                 ("Rwb", "x", "xdot", "w", "joint_q", "joint_qdot", "joint_tau", "stance", "gait_phase", "gait_duty", "cmd_state",
@@ -99,7 +105,7 @@ EXPORTS = ("qc_create_abi", "qc_destroy", "qc_control_batch", "qc_control_batch_
            "qc_set_tuning", "qc_query_launch", "qc_check_abi", "qc_default_command", "qc_commander_state_init", "qc_tick_batch",
            "qc_default_plant", "qc_plant_step_batch", "qc_default_leg_plant", "qc_leg_plant_step_batch",
            "qc_default_certify", "qc_certify_batch", "qc_default_sensitivity", "qc_sensitivity_batch",
-           "qc_default_sensitivity_rot", "qc_sensitivity_rot_batch")
+           "qc_default_sensitivity_rot", "qc_sensitivity_rot_batch", "qc_default_plant_adjoint", "qc_plant_step_adjoint_batch")
 
 _lib = None
 
@@ -186,6 +192,10 @@ def load():
     lib.qc_default_sensitivity_rot.restype = None
     lib.qc_sensitivity_rot_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcBatchIn), C.POINTER(QcSensitivityRotIo), C.c_void_p]
     lib.qc_sensitivity_rot_batch.restype = C.c_int
+    lib.qc_default_plant_adjoint.argtypes = [C.POINTER(QcPlantAdjointIo)]
+    lib.qc_default_plant_adjoint.restype = None
+    lib.qc_plant_step_adjoint_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcPlantAdjointIo), C.c_void_p]
+    lib.qc_plant_step_adjoint_batch.restype = C.c_int
     # the structures above are hand-written mirrors of the header: a library built from another revision is refused here,
     # before any of them crosses the boundary
     rc = lib.qc_check_abi(ABI_VERSION, C.sizeof(QcParams), C.sizeof(QcBatchIn), C.sizeof(QcBatchOut))

@@ -1,9 +1,13 @@
-"""torch.autograd for control_batch(): BalanceController.control_batch_autograd().
+"""torch.autograd for control_batch(), plant_step() and the closed loop of the two: BalanceController.control_batch_autograd(),
+plant_step_autograd() and rollout_autograd().
 
 Forward is control_batch() itself; backward is the adjoint of the balance QP on the active face of the forces it returned
 (qc_sensitivity_batch) and, where a rotation requires grad, the rotation cotangents behind it (qc_sensitivity_rot_batch), both
 on the current stream, without host synchronisation.  The gradient is the one on the active face: valid while the working set
-holds; robots with bit 0 of the sensitivity flags have a one-sided derivative, robots with bit 1 NaN gradients."""
+holds; robots with bit 0 of the sensitivity flags have a one-sided derivative, robots with bit 1 NaN gradients.
+
+plant_step_autograd() is OUT OF PLACE - plant_step() on clones of the state - and its backward is one qc_plant_step_adjoint_batch call
+on the saved pre-step tensors; rollout_autograd() alternates the two and threads new tensors through."""
 from __future__ import annotations
 
 import torch
@@ -65,3 +69,69 @@ def control_batch_autograd(ctl, batch, act_tol=1e-7, flags=None, **control_kwarg
     tensors = [batch.get(k) for k in DIFFERENTIABLE]
     detached = {k: (v.detach() if isinstance(v, torch.Tensor) else v) for k, v in batch.items()}
     return _ControlBatch.apply(ctl, detached, float(act_tol), flags, control_kwargs, *tensors)
+
+
+# the inputs of a plant step a gradient is produced for, in the order backward returns them; the step's outputs, in the order forward returns them
+PLANT_DIFFERENTIABLE = ("Rwb", "x", "xdot", "w", "grf_body", "foot_world")
+PLANT_OUTPUTS = ("Rwb", "x", "xdot", "w", "feet")
+_PLANT_BAR = {"Rwb": "Rwb_bar", "x": "x_bar", "xdot": "xdot_bar", "w": "w_bar", "grf_body": "grf_bar", "foot_world": "foot_world_bar"}
+
+
+class _PlantStep(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ctl, dt, Rwb, x, xdot, w, grf_body, foot_world):
+        new = {"Rwb": Rwb.clone(), "x": x.clone(), "xdot": xdot.clone(), "w": w.clone()}
+        feet = torch.empty_like(foot_world)
+        ctl.plant_step(new, grf_body, foot_world, dt, feet=feet)
+        ctx.ctl, ctx.dt = ctl, dt
+        ctx.set_materialize_grads(False)  # an output the loss never reached arrives as None: a NULL cotangent, not an array of zeros
+        ctx.save_for_backward(Rwb, x, xdot, w, grf_body, foot_world)
+        return new["Rwb"], new["x"], new["xdot"], new["w"], feet
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *bars):
+        Rwb, x, xdot, w, grf_body, foot_world = ctx.saved_tensors
+        need = dict(zip(PLANT_DIFFERENTIABLE, ctx.needs_input_grad[2:]))
+        want = tuple(_PLANT_BAR[k] for k in PLANT_DIFFERENTIABLE if need[k])
+        cot = {k: b.contiguous() for k, b in zip(PLANT_OUTPUTS, bars) if b is not None}
+        if not cot:  # no output reached the loss: every gradient is zero
+            grads = [torch.zeros_like(t) if need[k] else None for k, t in zip(PLANT_DIFFERENTIABLE, ctx.saved_tensors)]
+            return (None, None, *grads)
+        s = ctx.ctl.plant_step_adjoint({"Rwb": Rwb, "x": x, "xdot": xdot, "w": w}, grf_body, foot_world, ctx.dt, cot, want=want)
+        grads = [s[_PLANT_BAR[k]].view_as(t) if need[k] else None for k, t in zip(PLANT_DIFFERENTIABLE, ctx.saved_tensors)]
+        return (None, None, *grads)
+
+
+def plant_step_autograd(ctl, state, grf_body, foot_world, dt):
+    """BalanceController.plant_step_autograd (see there): (Rwb', x', xdot', w', feet') of one plant step as NEW tensors, `state` left as
+    it is, with a grad_fn whenever one of PLANT_DIFFERENTIABLE requires grad."""
+    tensors = [state[k] for k in ("Rwb", "x", "xdot", "w")] + [grf_body, foot_world]
+    return _PlantStep.apply(ctl, float(dt), *tensors)
+
+
+def rollout_autograd(ctl, batch, foot_world, steps, dt, act_tol=1e-7, warm=True):
+    """BalanceController.rollout_autograd (see there): `steps` times control_batch_autograd() then plant_step_autograd(), out of place.
+    The gradient is the one on the active face of every solve along the way; memory grows with `steps`."""
+    if batch.get("joint_q") is not None or batch.get("feet") is None:
+        raise ValueError("rollout: the plant is a single rigid body - the batch carries `feet`, not joint_q")
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError("rollout: steps must be >= 0")
+    cur = dict(batch)
+    out, active = {}, None
+    for _ in range(steps):
+        kwargs = {}
+        if warm:  # the solve writes its working-set word into a tensor of this step's own; the next solve starts from it (detached: an int32)
+            n, dev = cur["x"].shape[0], cur["x"].device
+            res = {"grf_body": torch.zeros((n, 12), dtype=torch.float64, device=dev), "status": torch.full((n,), -1, dtype=torch.int32, device=dev),
+                   "active_set": torch.zeros((n,), dtype=torch.int32, device=dev)}
+            kwargs = dict(warm=active, out=res, want_active_set=True)
+            active = res["active_set"]
+        grf, status = control_batch_autograd(ctl, cur, act_tol, **kwargs)
+        Rwb, x, xdot, w, feet = plant_step_autograd(ctl, cur, grf, foot_world, dt)
+        cur = dict(cur, Rwb=Rwb, x=x, xdot=xdot, w=w, feet=feet)
+        out = {"grf_body": grf, "status": status}
+    if warm and active is not None:
+        out["active_set"] = active
+    return {k: cur[k] for k in ("Rwb", "x", "xdot", "w", "feet")}, out

@@ -454,6 +454,94 @@ class BalanceController:
             step()
         return state, r.finish(steps, history)
 
+    # ------------------------------------------------------- differentiating a rollout
+    def plan_plant_adjoint(self, state, grf_body, foot_world, dt, cotangents, want=("Rwb_bar", "x_bar", "xdot_bar", "w_bar", "grf_bar", "foot_world_bar"),
+                           out=None, stream=None):
+        """plant_step_adjoint() marshalled once: returns (launch, out), `launch()` being one qc_plant_step_adjoint_batch call
+        (graph-capturable) on tensors that are read in place.  Planning launches nothing.  `out`: a dict of tensors to write into
+        instead of new ones (every name in `want`); a tensor of `out` may be a tensor of `cotangents` of the same layout (the
+        aliasing contract of include/qc_balance.h).  A call the library refuses raises ValueError with its message, from launch()."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        n = state["x"].shape[0]
+        io = _lib.QcPlantAdjointIo()
+        self._lib.qc_default_plant_adjoint(C.byref(io))
+        for name, t, k in [(k, state.get(k), m) for k, m in (("Rwb", 9), ("x", 3), ("xdot", 3), ("w", 3))] + [("grf_body", grf_body, 12), ("foot_world", foot_world, 12)]:
+            _check_tensor(name, t, n, k, torch.float64, dev, True, "float64")
+            setattr(io, name, t.data_ptr() if n else None)
+        unknown = [k for k in cotangents if k not in _PLANT_COTANGENTS]
+        if unknown:
+            raise ValueError(f"plant_step_adjoint: unknown cotangent(s) {unknown}; the step's outputs are {tuple(_PLANT_COTANGENTS)}")
+        for name, t in cotangents.items():
+            if _check_tensor(f"cotangents['{name}']", t, n, _PLANT_COTANGENTS[name], torch.float64, dev, False, "float64"):
+                setattr(io, name + "_next_bar", t.data_ptr())
+        unknown = [w for w in want if w not in _PLANT_ADJOINT_OUTPUTS]
+        if unknown:
+            raise ValueError(f"plant_step_adjoint: unknown output(s) {unknown}; want is a subset of {tuple(_PLANT_ADJOINT_OUTPUTS)}")
+        res = {}
+        for name in want:
+            size = (n, _PLANT_ADJOINT_OUTPUTS[name])
+            t = None if out is None else out.get(name)
+            if t is None:
+                if out is not None:
+                    raise ValueError(f"out: '{name}' was asked for but the supplied `out` has no such tensor")
+                t = torch.zeros(size, dtype=torch.float64, device=dev)
+            elif t.dtype != torch.float64 or not t.is_contiguous() or t.device != dev or t.numel() != size[0] * size[1]:
+                raise ValueError(f"out['{name}']: need contiguous {torch.float64} with {size[0] * size[1]} elements on {dev}")
+            res[name] = t
+            setattr(io, name, t.data_ptr())
+        io.dt = float(dt)
+        fn, h, args = self._lib.qc_plant_step_adjoint_batch, self._h, (n, C.byref(io), self._stream_ptr(stream))
+
+        def launch(_keep=(state, grf_body, foot_world, cotangents, res, io)):
+            rc = fn(h, *args)
+            if rc == _lib.QC_ERR_INVALID:
+                raise ValueError(_lib.last_error())
+            if rc != _lib.QC_OK:
+                raise RuntimeError(f"qc_plant_step_adjoint_batch failed ({rc}): {_lib.last_error()}")
+
+        return launch, res
+
+    def plant_step_adjoint(self, state, grf_body, foot_world, dt, cotangents, want=("Rwb_bar", "x_bar", "xdot_bar", "w_bar", "grf_bar", "foot_world_bar"),
+                           out=None, stream=None):
+        """The reverse pass of plant_step() (qc_plant_step_adjoint_batch, include/qc_balance.h; INTEGRATION.md "Differentiating a
+        rollout").  `state`: the tensors Rwb [n,9], x, xdot, w [n,3] as they were BEFORE the step; `grf_body`, `foot_world` [n,12] and
+        `dt` as the step read them; `cotangents`: a dict with any of "Rwb" [n,9] (entrywise, row-major), "x", "xdot", "w" [n,3] and
+        "feet" [n,12] - cotangents on the step's outputs, a missing one (or None) being zero, at least one given.  `want`: any of
+        "Rwb_bar" [n,9] (entrywise), "x_bar", "xdot_bar", "w_bar" [n,3], "grf_bar" and "foot_world_bar" [n,12]; they are written, not
+        accumulated.  The step is recomputed from `state`; nothing of it is written.  No cotangent of mass, Ib or dt is produced.
+        Asynchronous on `stream`, no synchronisation.  Returns the dict of device tensors; ValueError with the library's message for
+        a call it refuses."""
+        launch, res = self.plan_plant_adjoint(state, grf_body, foot_world, dt, cotangents, want, out, stream)
+        launch()
+        return res
+
+    def plant_step_autograd(self, state, grf_body, foot_world, dt):
+        """plant_step() with a gradient, OUT OF PLACE: returns (Rwb', x', xdot', w', feet') as new tensors and leaves `state` as it
+        is; the outputs carry a grad_fn whenever one of Rwb, x, xdot, w, grf_body, foot_world requires grad
+        (quadruped_control_amd/autograd.py).  Backward is one plant_step_adjoint() call on the saved pre-step tensors, on the
+        current stream, without host synchronisation, asking only for the cotangents needed; inputs that do not require grad get
+        None.  Rwb's gradient is entrywise.  There is no double backward and no gradient with respect to dt."""
+        from .autograd import plant_step_autograd
+
+        return plant_step_autograd(self, state, grf_body, foot_world, dt)
+
+    def rollout_autograd(self, batch, foot_world, steps, dt, act_tol=1e-7, warm=True):
+        """The functional twin of rollout(): `steps` times control_batch_autograd() then plant_step_autograd(), new tensors threaded
+        through instead of `batch` being updated - `batch` is not modified.  The desired state, `stance` and `foot_world` are held;
+        they, and the start state Rwb, x, xdot, w, feet, are differentiable where they require grad.  warm=True feeds each solve's
+        (detached) active_set to the next solve as its warm start, as rollout() does.  Returns (state, out): `state` a dict of the
+        final Rwb, x, xdot, w and feet, `out` the grf_body, status (and active_set) of the LAST solve; for steps = 0 the state is
+        the batch's own tensors and `out` is empty.
+        The gradient is control_batch_autograd()'s: the one ON THE ACTIVE FACE of every solve at `act_tol` - valid while every
+        working set along the rollout holds, one-sided where a foot sits on both rows of an axis, NaN behind a bad pivot - so a loss
+        that moves a robot across a face change at ANY step sees a kink there.  Memory grows with `steps`: every step keeps its
+        pre-step state, forces and feet (about 0.6 kB per robot and step) until backward has run."""
+        from .autograd import rollout_autograd
+
+        return rollout_autograd(self, batch, foot_world, steps, dt, act_tol, warm)
+
     # ------------------------------------------- closing the loop around the tick
     def _marshal_leg_plant(self, state, joint_tau, dt, leg_inertia, stance, gait_phase, gait_duty, cmd_state, foot_world, flags):
         """Validate the arguments of leg_plant_step() and build its C struct.  Launches nothing."""
@@ -854,6 +942,8 @@ _CERTIFY_OUTPUTS = {"primal": ((), "float64"), "stationarity": ((), "float64"), 
                     "active": ((4,), "uint8"), "flags": ((), "int32")}
 _SENSITIVITY_OUTPUTS = {"adjoint": ((12,), "float64"), "b_bar": ((6,), "float64"), "feet_bar": ((4, 3), "float64"),
                         **{k: ((3,), "float64") for k in ("x_bar", "xdot_bar", "w_bar", "x_d_bar", "xdot_d_bar", "w_d_bar")}, "flags": ((), "int32")}
+_PLANT_COTANGENTS = {"Rwb": 9, "x": 3, "xdot": 3, "w": 3, "feet": 12}  # the step's outputs a cotangent may be given on -> trailing size
+_PLANT_ADJOINT_OUTPUTS = {"Rwb_bar": 9, "x_bar": 3, "xdot_bar": 3, "w_bar": 3, "grf_bar": 12, "foot_world_bar": 12}  # name -> trailing size (float64)
 _SENSITIVITY_ROT_OUTPUTS = {"Rwb_bar": 9, "Rwb_d_bar": 9, "Rwb_rot_bar": 3, "Rwb_d_rot_bar": 3}  # name -> trailing size (float64)
 
 

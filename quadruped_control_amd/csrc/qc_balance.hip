@@ -2235,6 +2235,24 @@ int qc_plant_step_batch(qc_handle* h, size_t n, const qc_plant_io* io, void* str
   return QC_OK;
 }
 
+void qc_default_plant_adjoint(qc_plant_adjoint_io* io) {
+  if (!io) return;
+  std::memset(io, 0, sizeof(*io));
+  io->struct_size = sizeof(qc_plant_adjoint_io);
+  io->dt = 1.0 / 300.0;  // qc_default_plant's
+}
+
+int qc_plant_step_adjoint_batch(qc_handle* h, size_t n, const qc_plant_adjoint_io* io, void* stream) {
+  if (const int rc = qc::check_plant_adjoint_args(h, n, io); rc != QC_OK || n == 0) return rc;
+  qc::PlantAdjointArgs a;
+  if (const int rc = qc::plant_adjoint_constants(h->dp.mass, h->dp.Ib, io, a); rc != QC_OK) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  const unsigned blocks = (unsigned)((n + qc::PLANT_BLOCK - 1) / qc::PLANT_BLOCK);
+  qc::plant_step_adjoint_kernel<<<dim3(blocks), dim3(qc::PLANT_BLOCK), 0, (hipStream_t)stream>>>((long)n, a);
+  QC_HIP(hipGetLastError());
+  return QC_OK;
+}
+
 void qc_default_leg_plant(qc_leg_plant_io* io) {
   if (!io) return;
   std::memset(io, 0, sizeof(*io));  // (leg_inertia 0: the reference has no number for it, the caller gives one)

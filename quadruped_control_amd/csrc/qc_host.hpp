@@ -10,6 +10,7 @@
 #include "../../include/qc_balance.h"
 #include "qc_device.hpp"
 #include "qc_plant.hpp"
+#include "qc_plant_adjoint.hpp"
 #include "qc_leg_plant.hpp"
 #include "qc_certify.hpp"
 #include "qc_sensitivity.hpp"
@@ -492,6 +493,37 @@ inline int check_plant_args(const qc_handle* h, size_t n, const qc_plant_io* io)
   if (!io->Rwb || !io->x || !io->xdot || !io->w) return fail(QC_ERR_INVALID, "qc_plant_step_batch: the state arrays Rwb, x, xdot and w are required");
   if (!io->grf_body || !io->foot_world) return fail(QC_ERR_INVALID, "qc_plant_step_batch: grf_body and foot_world are required");
   return check_one_launch("qc_plant_step_batch", n, PLANT_BLOCK);
+}
+
+// ---------------------------------------------------------------- qc_plant_step_adjoint_batch
+// The argument check of the plant step's reverse pass: what is wrong with the call itself (message prefix
+// "qc_plant_step_adjoint_batch:").  The handle's mass and Ib are judged by plant_adjoint_constants, through the plant's own checks.
+inline int check_plant_adjoint_args(const qc_handle* h, size_t n, const qc_plant_adjoint_io* io) {
+  if (!h || !io) return fail(QC_ERR_INVALID, "qc_plant_step_adjoint_batch: null argument");
+  if (const int rc = check_struct_size("qc_plant_step_adjoint_batch", "qc_plant_adjoint_io", "qc_default_plant_adjoint", io->struct_size, sizeof(qc_plant_adjoint_io));
+      rc != QC_OK)
+    return rc;
+  if (!std::isfinite(io->dt) || !(io->dt > 0.0)) return fail(QC_ERR_INVALID, "qc_plant_step_adjoint_batch: dt must be finite and > 0");
+  if (!io->Rwb_next_bar && !io->x_next_bar && !io->xdot_next_bar && !io->w_next_bar && !io->feet_next_bar)
+    return fail(QC_ERR_INVALID, "qc_plant_step_adjoint_batch: no input cotangent given (Rwb_next_bar, x_next_bar, xdot_next_bar, w_next_bar, feet_next_bar are all NULL)");
+  if (!io->Rwb_bar && !io->x_bar && !io->xdot_bar && !io->w_bar && !io->grf_bar && !io->foot_world_bar)
+    return fail(QC_ERR_INVALID, "qc_plant_step_adjoint_batch: no output requested (Rwb_bar, x_bar, xdot_bar, w_bar, grf_bar, foot_world_bar are all NULL)");
+  if (n == 0) return QC_OK;
+  if (!io->Rwb || !io->x || !io->xdot || !io->w) return fail(QC_ERR_INVALID, "qc_plant_step_adjoint_batch: the state arrays Rwb, x, xdot and w are required");
+  if (!io->grf_body || !io->foot_world) return fail(QC_ERR_INVALID, "qc_plant_step_adjoint_batch: grf_body and foot_world are required");
+  return check_one_launch("qc_plant_step_adjoint_batch", n, PLANT_BLOCK);
+}
+
+// the kernel's arguments: the body's constants (body_constants, under this entry point's name) and the call's arrays
+inline int plant_adjoint_constants(double mass, const double* Ib, const qc_plant_adjoint_io* io, PlantAdjointArgs& a) {
+  if (const int rc = body_constants("qc_plant_step_adjoint_batch", mass, Ib, io->dt, a); rc != QC_OK) return rc;
+  a.Rwb = io->Rwb; a.x = io->x; a.xdot = io->xdot; a.w = io->w;
+  a.grf_body = io->grf_body; a.foot_world = io->foot_world;
+  a.Rwb_next_bar = io->Rwb_next_bar; a.x_next_bar = io->x_next_bar; a.xdot_next_bar = io->xdot_next_bar;
+  a.w_next_bar = io->w_next_bar; a.feet_next_bar = io->feet_next_bar;
+  a.Rwb_bar = io->Rwb_bar; a.x_bar = io->x_bar; a.xdot_bar = io->xdot_bar; a.w_bar = io->w_bar;
+  a.grf_bar = io->grf_bar; a.foot_world_bar = io->foot_world_bar;
+  return QC_OK;
 }
 
 // ---------------------------------------------------------------- qc_leg_plant_step_batch
