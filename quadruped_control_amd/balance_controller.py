@@ -35,14 +35,39 @@ def _fill(carr, values, n, name):
     carr[:] = a.tolist()
 
 
-def _check_tensor(name, t, n, k, dtype, dev, required, label=None):
+def _check_tensor(name, t, n, k, dtype, dev, required, label=None, msg=None):
     """`t` is a contiguous `dtype` tensor of n * k elements on `dev` (k None: [n]) - or, unless required, None.  Returns whether
-    there is a tensor.  `label`: the dtype as the message words it, where that is not str(dtype)."""
+    there is a tensor.  `label`: the dtype as the message words it, where that is not str(dtype); `msg`: the whole message, for
+    the arguments whose refusal has words of its own."""
     if t is None and not required:
         return False
     if t is None or t.dtype != dtype or not t.is_contiguous() or t.device != dev or t.numel() != n * (k or 1):
-        raise ValueError(f"{name}: need contiguous {label or dtype} [{n}{'' if k is None else f',{k}'}] on {dev}")
+        raise ValueError(msg or f"{name}: need contiguous {label or dtype} [{n}{'' if k is None else f',{k}'}] on {dev}")
     return True
+
+
+def _outputs(who, table, want, out, n, dev, io, extra=()):
+    """The outputs of a call: every name in `want` - a subset of `table`, name -> (trailing shape, torch dtype name) - and every
+    (name, shape, dtype name) of `extra`, the entries whose shape does not depend on n.  Each is the tensor of that name in `out`,
+    validated, or new zeros where `out` is None; its pointer becomes the field of that name in `io`.  Returns the dict."""
+    import torch
+
+    unknown = [w for w in want if w not in table]
+    if unknown:
+        raise ValueError(f"{who}: unknown output(s) {unknown}; want is a subset of {tuple(table)}")
+    res = {}
+    for name, shape, dtype in [(w, (n,) + table[w][0], table[w][1]) for w in want] + list(extra):
+        dtype, count = getattr(torch, dtype), int(np.prod(shape))
+        t = None if out is None else out.get(name)
+        if t is None:
+            if out is not None:
+                raise ValueError(f"out: '{name}' was asked for but the supplied `out` has no such tensor")
+            t = torch.zeros(shape, dtype=dtype, device=dev)
+        else:
+            _check_tensor(name, t, count, None, dtype, dev, True, msg=f"out['{name}']: need contiguous {dtype} with {count} elements on {dev}")
+        res[name] = t
+        setattr(io, name, t.data_ptr())
+    return res
 
 
 class _RolloutPlans:
@@ -248,9 +273,7 @@ class BalanceController:
             _check_tensor(name, t, n, k, torch.float64, dev, True, "float64")
             setattr(bi, name, t.data_ptr())
         st = batch.get("stance")
-        if st is not None:
-            if st.dtype != torch.uint8 or not st.is_contiguous() or st.numel() != n * 4 or st.device != dev:
-                raise ValueError("stance: need contiguous uint8 [n,4]")
+        if _check_tensor("stance", st, n, 4, torch.uint8, dev, False, msg="stance: need contiguous uint8 [n,4]"):
             bi.stance = st.data_ptr()
         for name, k in (("gait_phase", 4), ("gait_duty", 1),  # on-device contact rule (gait.cpp:125-134)
                         ("gait_dt", 1),  # on-device gait clock (gait.cpp:113-123): gait_phase is advanced in place
@@ -259,9 +282,9 @@ class BalanceController:
             if _check_tensor(name, t, n, k, torch.float64, dev, False, "float64"):
                 setattr(bi, name, t.data_ptr())
         ss = batch.get("swing_state")
-        if ss is not None:  # torch.uint8 tensor of n * sizeof(qc_swing_state) bytes, updated in place
-            if ss.dtype != torch.uint8 or not ss.is_contiguous() or ss.numel() != n * SWING_STATE_DTYPE.itemsize or ss.device != dev:
-                raise ValueError("swing_state: need a contiguous uint8 tensor of n * 224 bytes on the device")
+        # torch.uint8 tensor of n * sizeof(qc_swing_state) bytes, updated in place
+        if _check_tensor("swing_state", ss, n, SWING_STATE_DTYPE.itemsize, torch.uint8, dev, False,
+                         msg="swing_state: need a contiguous uint8 tensor of n * 224 bytes on the device"):
             bi.swing_state = ss.data_ptr()
         if out is None:
             # Allocated here: defined contents until the first launch has run (plan_batch launches nothing) - zero forces and
@@ -280,13 +303,9 @@ class BalanceController:
                     raise ValueError(f"out: '{name}' was asked for (want_{'torques' if name == 'joint_tau' else name}=True) but the supplied `out` has no such tensor")
             for name, shape, dt in (("grf_body", n * 12, torch.float64), ("status", n, torch.int32), ("active_set", n, torch.int32),
                                     ("iterations", n, torch.int32), ("joint_tau", n * 12, torch.float64)):
-                t = out.get(name)
-                if t is None:
-                    if name in ("grf_body", "status"):
-                        raise ValueError(f"out: '{name}' is required")
-                    continue
-                if t.dtype != dt or not t.is_contiguous() or t.numel() != shape or t.device != dev:
-                    raise ValueError(f"out['{name}']: need contiguous {dt} with {shape} elements on {dev}")
+                if out.get(name) is None and name in ("grf_body", "status"):
+                    raise ValueError(f"out: '{name}' is required")
+                _check_tensor(name, out.get(name), shape, None, dt, dev, False, msg=f"out['{name}']: need contiguous {dt} with {shape} elements on {dev}")
         bo = _lib.QcBatchOut()
         bo.grf_body = out["grf_body"].data_ptr()
         bo.status = out["status"].data_ptr()
@@ -294,9 +313,7 @@ class BalanceController:
         bo.iterations = out["iterations"].data_ptr() if "iterations" in out else None
         bo.joint_tau = out["joint_tau"].data_ptr() if "joint_tau" in out else None
         warm_ptr = None
-        if warm is not None:
-            if warm.dtype != torch.int32 or warm.numel() != n or not warm.is_contiguous() or warm.device != dev:
-                raise ValueError("warm: need contiguous int32 [n] (an active_set output) on the controller's device")
+        if _check_tensor("warm", warm, n, None, torch.int32, dev, False, msg="warm: need contiguous int32 [n] (an active_set output) on the controller's device"):
             warm_ptr = warm.data_ptr()
         return n, bi, bo, warm_ptr, out
 
@@ -307,13 +324,16 @@ class BalanceController:
         s = stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.device))
         return C.c_void_p(s.cuda_stream)
 
-    def _launcher(self, name, args, keep):
+    def _launcher(self, name, args, keep, invalid=RuntimeError):
         """`launch()`: exactly one call of the library's `name`(handle, *args), nothing marshalled per call.  `keep` holds what the
-        pointers in `args` point into for as long as the closure lives."""
+        pointers in `args` point into for as long as the closure lives.  `invalid`: what a call the library refuses (QC_ERR_INVALID)
+        raises - ValueError carries the library's bare message, RuntimeError the words of every other failure."""
         fn, h = getattr(self._lib, name), self._h
 
         def launch(_keep=keep):
             rc = fn(h, *args)
+            if rc == _lib.QC_ERR_INVALID and invalid is not RuntimeError:
+                raise invalid(_lib.last_error())
             if rc != _lib.QC_OK:
                 raise RuntimeError(f"{name} failed ({rc}): {_lib.last_error()}")
 
@@ -393,19 +413,25 @@ class BalanceController:
         return out
 
     # ------------------------------------------------------- closing the loop
-    def _marshal_plant(self, state, grf_body, foot_world, dt, feet):
-        """Validate the arguments of plant_step() and build its C struct.  Launches nothing."""
+    def _plant_arrays(self, io, state, grf_body, foot_world, feet=None):
+        """What plant_step() and its adjoint read alike: Rwb, x, xdot, w of `state`, grf_body, foot_world (and the plant's `feet`),
+        validated and set in `io`.  Returns (n, dev)."""
         import torch
 
         dev = torch.device("cuda", self.device)
         n = state["x"].shape[0]
-        io = _lib.QcPlantIo()
-        self._lib.qc_default_plant(C.byref(io))
         arrays = [(k, state.get(k), m) for k, m in (("Rwb", 9), ("x", 3), ("xdot", 3), ("w", 3))]
         arrays += [("grf_body", grf_body, 12), ("foot_world", foot_world, 12)] + ([("feet", feet, 12)] if feet is not None else [])
         for name, t, k in arrays:
             _check_tensor(name, t, n, k, torch.float64, dev, True, "float64")
             setattr(io, name, t.data_ptr() if n else None)
+        return n, dev
+
+    def _marshal_plant(self, state, grf_body, foot_world, dt, feet):
+        """Validate the arguments of plant_step() and build its C struct.  Launches nothing."""
+        io = _lib.QcPlantIo()
+        self._lib.qc_default_plant(C.byref(io))
+        n, _ = self._plant_arrays(io, state, grf_body, foot_world, feet)
         io.dt = float(dt)
         return n, io
 
@@ -463,45 +489,19 @@ class BalanceController:
         aliasing contract of include/qc_balance.h).  A call the library refuses raises ValueError with its message, from launch()."""
         import torch
 
-        dev = torch.device("cuda", self.device)
-        n = state["x"].shape[0]
         io = _lib.QcPlantAdjointIo()
         self._lib.qc_default_plant_adjoint(C.byref(io))
-        for name, t, k in [(k, state.get(k), m) for k, m in (("Rwb", 9), ("x", 3), ("xdot", 3), ("w", 3))] + [("grf_body", grf_body, 12), ("foot_world", foot_world, 12)]:
-            _check_tensor(name, t, n, k, torch.float64, dev, True, "float64")
-            setattr(io, name, t.data_ptr() if n else None)
+        n, dev = self._plant_arrays(io, state, grf_body, foot_world)
         unknown = [k for k in cotangents if k not in _PLANT_COTANGENTS]
         if unknown:
             raise ValueError(f"plant_step_adjoint: unknown cotangent(s) {unknown}; the step's outputs are {tuple(_PLANT_COTANGENTS)}")
         for name, t in cotangents.items():
-            if _check_tensor(f"cotangents['{name}']", t, n, _PLANT_COTANGENTS[name], torch.float64, dev, False, "float64"):
+            if _check_tensor(f"cotangents['{name}']", t, n, int(np.prod(_PLANT_COTANGENTS[name][0])), torch.float64, dev, False, "float64"):
                 setattr(io, name + "_next_bar", t.data_ptr())
-        unknown = [w for w in want if w not in _PLANT_ADJOINT_OUTPUTS]
-        if unknown:
-            raise ValueError(f"plant_step_adjoint: unknown output(s) {unknown}; want is a subset of {tuple(_PLANT_ADJOINT_OUTPUTS)}")
-        res = {}
-        for name in want:
-            size = (n, _PLANT_ADJOINT_OUTPUTS[name])
-            t = None if out is None else out.get(name)
-            if t is None:
-                if out is not None:
-                    raise ValueError(f"out: '{name}' was asked for but the supplied `out` has no such tensor")
-                t = torch.zeros(size, dtype=torch.float64, device=dev)
-            elif t.dtype != torch.float64 or not t.is_contiguous() or t.device != dev or t.numel() != size[0] * size[1]:
-                raise ValueError(f"out['{name}']: need contiguous {torch.float64} with {size[0] * size[1]} elements on {dev}")
-            res[name] = t
-            setattr(io, name, t.data_ptr())
+        res = _outputs("plant_step_adjoint", _PLANT_ADJOINT_OUTPUTS, want, out, n, dev, io)
         io.dt = float(dt)
-        fn, h, args = self._lib.qc_plant_step_adjoint_batch, self._h, (n, C.byref(io), self._stream_ptr(stream))
-
-        def launch(_keep=(state, grf_body, foot_world, cotangents, res, io)):
-            rc = fn(h, *args)
-            if rc == _lib.QC_ERR_INVALID:
-                raise ValueError(_lib.last_error())
-            if rc != _lib.QC_OK:
-                raise RuntimeError(f"qc_plant_step_adjoint_batch failed ({rc}): {_lib.last_error()}")
-
-        return launch, res
+        args = (n, C.byref(io), self._stream_ptr(stream))
+        return self._launcher("qc_plant_step_adjoint_batch", args, (state, grf_body, foot_world, cotangents, res, io), ValueError), res
 
     def plant_step_adjoint(self, state, grf_body, foot_world, dt, cotangents, want=("Rwb_bar", "x_bar", "xdot_bar", "w_bar", "grf_bar", "foot_world_bar"),
                            out=None, stream=None):
@@ -658,46 +658,39 @@ class BalanceController:
         return state, r.finish(steps, history, foot_world=foot_world, flags=flags)
 
     # ------------------------------------------------------ certifying a batch
+    def _readonly_batch(self, who, batch, fields, io, own):
+        """The batch of a call that only reads it, and the call's own input arrays: n from the first array that is there among
+        _IN_FIELDS and `own` ((name, tensor, k) entries, float64), a QcBatchIn filled from whatever `fields` ((name, k, torch dtype
+        name) entries) the batch holds, the arrays of `own` set in `io`.  What is required is the library's decision: it names what is
+        missing, from launch().  Returns (n, dev, bi)."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        sized = [t for t in [batch.get(k) for k, _ in _IN_FIELDS] + [t for _, t, _ in own] if t is not None]
+        if not sized:
+            raise ValueError(f"{who}: the batch holds no state array")
+        n = sized[0].shape[0]  # (a missing array is the library's refusal, not a KeyError here)
+        bi = _lib.QcBatchIn()
+        for name, k, dtype in fields:
+            t = batch.get(name)
+            if _check_tensor(name, t, n, k, getattr(torch, dtype), dev, False):
+                setattr(bi, name, t.data_ptr())
+        for name, t, k in own:
+            if _check_tensor(name, t, n, k, torch.float64, dev, False, "float64"):
+                setattr(io, name, t.data_ptr())
+        return n, dev, bi
+
     def plan_certify(self, batch, grf_body, act_tol=1e-7, primal_tol=1e-7, stat_tol=1e-8, want=("primal", "stationarity"), summary=True,
                      out=None, stream=None):
         """certify_batch() marshalled once: returns (launch, out), `launch()` being one qc_certify_batch call (graph-capturable) on
         tensors that are read in place.  Planning launches nothing.  `out`: a dict of tensors to write into instead of new ones
         (every name in `want`, and "summary" if summary=True)."""
-        import torch
-
-        dev = torch.device("cuda", self.device)
-        sized = [t for t in [batch.get(k) for k, _ in _IN_FIELDS] + [grf_body] if t is not None]
-        if not sized:
-            raise ValueError("certify: the batch holds no state array")
-        n = sized[0].shape[0]  # (a missing array is the library's refusal, not a KeyError here)
-        bi = _lib.QcBatchIn()
-        for name, k, dtype in [(f, m, torch.float64) for f, m in _IN_FIELDS] + [("joint_q", 12, torch.float64), ("stance", 4, torch.uint8),
-                                                                               ("gait_phase", 4, torch.float64), ("gait_duty", 1, torch.float64)]:
-            t = batch.get(name)
-            if _check_tensor(name, t, n, k, dtype, dev, False):  # (what is required is the library's decision: qc_certify_batch names what is missing)
-                setattr(bi, name, t.data_ptr())
         io = _lib.QcCertifyIo()
         self._lib.qc_default_certify(C.byref(io))
-        if _check_tensor("grf_body", grf_body, n, 12, torch.float64, dev, False, "float64"):
-            io.grf_body = grf_body.data_ptr()
+        n, dev, bi = self._readonly_batch("certify", batch, _READONLY_FIELDS, io, [("grf_body", grf_body, 12)])
         io.act_tol, io.primal_tol, io.stat_tol = float(act_tol), float(primal_tol), float(stat_tol)
-        unknown = [w for w in want if w not in _CERTIFY_OUTPUTS]
-        if unknown:
-            raise ValueError(f"certify: unknown output(s) {unknown}; want is a subset of {tuple(_CERTIFY_OUTPUTS)}")
-        names = list(want) + (["summary"] if summary else [])
-        res = {}
-        for name in names:
-            shape, dtype = (None, torch.uint8) if name == "summary" else (_CERTIFY_OUTPUTS[name][0], getattr(torch, _CERTIFY_OUTPUTS[name][1]))
-            size = (CERTIFY_SUMMARY_DTYPE.itemsize,) if name == "summary" else (n,) + shape
-            t = None if out is None else out.get(name)
-            if t is None:
-                if out is not None:
-                    raise ValueError(f"out: '{name}' was asked for but the supplied `out` has no such tensor")
-                t = torch.zeros(size, dtype=dtype, device=dev)
-            elif t.dtype != dtype or not t.is_contiguous() or t.device != dev or t.numel() != int(np.prod(size)):
-                raise ValueError(f"out['{name}']: need contiguous {dtype} with {int(np.prod(size))} elements on {dev}")
-            res[name] = t
-            setattr(io, name, t.data_ptr())
+        extra = [("summary", (CERTIFY_SUMMARY_DTYPE.itemsize,), "uint8")] if summary else []
+        res = _outputs("certify", _CERTIFY_OUTPUTS, want, out, n, dev, io, extra)
         args = (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
         return self._launcher("qc_certify_batch", args, (batch, grf_body, res, bi, io)), res
 
@@ -718,51 +711,13 @@ class BalanceController:
         """sensitivity_batch() marshalled once: returns (launch, out), `launch()` being one qc_sensitivity_batch call
         (graph-capturable) on tensors that are read in place.  Planning launches nothing.  `out`: a dict of tensors to write into
         instead of new ones (every name in `want`).  A call the library refuses raises ValueError with its message, from launch()."""
-        import torch
-
-        dev = torch.device("cuda", self.device)
-        sized = [t for t in [batch.get(k) for k, _ in _IN_FIELDS] + [grf_body, grf_bar] if t is not None]
-        if not sized:
-            raise ValueError("sensitivity: the batch holds no state array")
-        n = sized[0].shape[0]  # (a missing array is the library's refusal, not a KeyError here)
-        bi = _lib.QcBatchIn()
-        for name, k, dtype in [(f, m, torch.float64) for f, m in _IN_FIELDS] + [("joint_q", 12, torch.float64), ("stance", 4, torch.uint8),
-                                                                               ("gait_phase", 4, torch.float64), ("gait_duty", 1, torch.float64)]:
-            t = batch.get(name)
-            if _check_tensor(name, t, n, k, dtype, dev, False):
-                setattr(bi, name, t.data_ptr())
         io = _lib.QcSensitivityIo()
         self._lib.qc_default_sensitivity(C.byref(io))
-        for name, t in (("grf_body", grf_body), ("grf_bar", grf_bar)):
-            if _check_tensor(name, t, n, 12, torch.float64, dev, False, "float64"):
-                setattr(io, name, t.data_ptr())
+        n, dev, bi = self._readonly_batch("sensitivity", batch, _READONLY_FIELDS, io, [("grf_body", grf_body, 12), ("grf_bar", grf_bar, 12)])
         io.act_tol = float(act_tol)
-        unknown = [w for w in want if w not in _SENSITIVITY_OUTPUTS]
-        if unknown:
-            raise ValueError(f"sensitivity: unknown output(s) {unknown}; want is a subset of {tuple(_SENSITIVITY_OUTPUTS)}")
-        res = {}
-        for name in want:
-            shape, dtype = _SENSITIVITY_OUTPUTS[name][0], getattr(torch, _SENSITIVITY_OUTPUTS[name][1])
-            size = (n,) + shape
-            t = None if out is None else out.get(name)
-            if t is None:
-                if out is not None:
-                    raise ValueError(f"out: '{name}' was asked for but the supplied `out` has no such tensor")
-                t = torch.zeros(size, dtype=dtype, device=dev)
-            elif t.dtype != dtype or not t.is_contiguous() or t.device != dev or t.numel() != int(np.prod(size)):
-                raise ValueError(f"out['{name}']: need contiguous {dtype} with {int(np.prod(size))} elements on {dev}")
-            res[name] = t
-            setattr(io, name, t.data_ptr())
-        fn, h, args = self._lib.qc_sensitivity_batch, self._h, (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
-
-        def launch(_keep=(batch, grf_body, grf_bar, res, bi, io)):
-            rc = fn(h, *args)
-            if rc == _lib.QC_ERR_INVALID:
-                raise ValueError(_lib.last_error())
-            if rc != _lib.QC_OK:
-                raise RuntimeError(f"qc_sensitivity_batch failed ({rc}): {_lib.last_error()}")
-
-        return launch, res
+        res = _outputs("sensitivity", _SENSITIVITY_OUTPUTS, want, out, n, dev, io)
+        args = (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
+        return self._launcher("qc_sensitivity_batch", args, (batch, grf_body, grf_bar, res, bi, io), ValueError), res
 
     def sensitivity_batch(self, batch, grf_body, grf_bar, want=("adjoint", "b_bar"), act_tol=1e-7, out=None, stream=None):
         """The adjoint of the balance QP on the active face of `grf_body` [n,12] (as control_batch() wrote it) for the batch the
@@ -781,48 +736,13 @@ class BalanceController:
         """sensitivity_rotation_batch() marshalled once: returns (launch, out), `launch()` being one qc_sensitivity_rot_batch call
         (graph-capturable) on tensors that are read in place.  Planning launches nothing.  `out`: a dict of tensors to write into
         instead of new ones (every name in `want`).  A call the library refuses raises ValueError with its message, from launch()."""
-        import torch
-
-        dev = torch.device("cuda", self.device)
-        sized = [t for t in [batch.get(k) for k, _ in _IN_FIELDS] + [grf_body, grf_bar, b_bar, feet_bar] if t is not None]
-        if not sized:
-            raise ValueError("sensitivity_rotation: the batch holds no state array")
-        n = sized[0].shape[0]  # (a missing array is the library's refusal, not a KeyError here)
-        bi = _lib.QcBatchIn()
-        for name, k in _IN_FIELDS + (("joint_q", 12),):
-            t = batch.get(name)
-            if _check_tensor(name, t, n, k, torch.float64, dev, False):
-                setattr(bi, name, t.data_ptr())
         io = _lib.QcSensitivityRotIo()
         self._lib.qc_default_sensitivity_rot(C.byref(io))
-        for name, t, k in (("grf_body", grf_body, 12), ("grf_bar", grf_bar, 12), ("b_bar", b_bar, 6), ("feet_bar", feet_bar, 12)):
-            if _check_tensor(name, t, n, k, torch.float64, dev, False, "float64"):
-                setattr(io, name, t.data_ptr())
-        unknown = [w for w in want if w not in _SENSITIVITY_ROT_OUTPUTS]
-        if unknown:
-            raise ValueError(f"sensitivity_rotation: unknown output(s) {unknown}; want is a subset of {tuple(_SENSITIVITY_ROT_OUTPUTS)}")
-        res = {}
-        for name in want:
-            size = (n, _SENSITIVITY_ROT_OUTPUTS[name])
-            t = None if out is None else out.get(name)
-            if t is None:
-                if out is not None:
-                    raise ValueError(f"out: '{name}' was asked for but the supplied `out` has no such tensor")
-                t = torch.zeros(size, dtype=torch.float64, device=dev)
-            elif t.dtype != torch.float64 or not t.is_contiguous() or t.device != dev or t.numel() != size[0] * size[1]:
-                raise ValueError(f"out['{name}']: need contiguous {torch.float64} with {size[0] * size[1]} elements on {dev}")
-            res[name] = t
-            setattr(io, name, t.data_ptr())
-        fn, h, args = self._lib.qc_sensitivity_rot_batch, self._h, (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
-
-        def launch(_keep=(batch, grf_body, grf_bar, b_bar, feet_bar, res, bi, io)):
-            rc = fn(h, *args)
-            if rc == _lib.QC_ERR_INVALID:
-                raise ValueError(_lib.last_error())
-            if rc != _lib.QC_OK:
-                raise RuntimeError(f"qc_sensitivity_rot_batch failed ({rc}): {_lib.last_error()}")
-
-        return launch, res
+        own = [("grf_body", grf_body, 12), ("grf_bar", grf_bar, 12), ("b_bar", b_bar, 6), ("feet_bar", feet_bar, 12)]
+        n, dev, bi = self._readonly_batch("sensitivity_rotation", batch, _STATE_FIELDS, io, own)  # (no contact mask: swing feet carry zeros)
+        res = _outputs("sensitivity_rotation", _SENSITIVITY_ROT_OUTPUTS, want, out, n, dev, io)
+        args = (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
+        return self._launcher("qc_sensitivity_rot_batch", args, (batch, grf_body, grf_bar, b_bar, feet_bar, res, bi, io), ValueError), res
 
     def sensitivity_rotation_batch(self, batch, grf_body, grf_bar, b_bar, feet_bar, want=("Rwb_bar", "Rwb_d_bar"), out=None, stream=None):
         """The cotangents of Rwb and Rwb_d that sensitivity_batch() leaves out (qc_sensitivity_rot_batch, include/qc_balance.h;
@@ -937,14 +857,17 @@ CERTIFY_SUMMARY_DTYPE = np.dtype([("n_fail", np.int64), ("n_nonfinite", np.int64
                                   ("worst_stationarity", np.float64), ("arg_primal", np.int64), ("arg_stationarity", np.int64)])  # == qc_certify_summary
 
 
-# the per-robot outputs of the certificate: name -> (trailing shape, torch dtype name)
+# the per-robot outputs of the certificate, the adjoint, the rotation cotangents and the plant's adjoint: name -> (trailing shape, torch dtype name)
 _CERTIFY_OUTPUTS = {"primal": ((), "float64"), "stationarity": ((), "float64"), "lambda": ((4, 3), "float64"), "grad": ((12,), "float64"),
                     "active": ((4,), "uint8"), "flags": ((), "int32")}
 _SENSITIVITY_OUTPUTS = {"adjoint": ((12,), "float64"), "b_bar": ((6,), "float64"), "feet_bar": ((4, 3), "float64"),
                         **{k: ((3,), "float64") for k in ("x_bar", "xdot_bar", "w_bar", "x_d_bar", "xdot_d_bar", "w_d_bar")}, "flags": ((), "int32")}
-_PLANT_COTANGENTS = {"Rwb": 9, "x": 3, "xdot": 3, "w": 3, "feet": 12}  # the step's outputs a cotangent may be given on -> trailing size
-_PLANT_ADJOINT_OUTPUTS = {"Rwb_bar": 9, "x_bar": 3, "xdot_bar": 3, "w_bar": 3, "grf_bar": 12, "foot_world_bar": 12}  # name -> trailing size (float64)
-_SENSITIVITY_ROT_OUTPUTS = {"Rwb_bar": 9, "Rwb_d_bar": 9, "Rwb_rot_bar": 3, "Rwb_d_rot_bar": 3}  # name -> trailing size (float64)
+_SENSITIVITY_ROT_OUTPUTS = {k: ((m,), "float64") for k, m in (("Rwb_bar", 9), ("Rwb_d_bar", 9), ("Rwb_rot_bar", 3), ("Rwb_d_rot_bar", 3))}
+_PLANT_ADJOINT_OUTPUTS = {k: ((m,), "float64") for k, m in (("Rwb_bar", 9), ("x_bar", 3), ("xdot_bar", 3), ("w_bar", 3), ("grf_bar", 12), ("foot_world_bar", 12))}
+_PLANT_COTANGENTS = {k: ((m,), "float64") for k, m in (("Rwb", 9), ("x", 3), ("xdot", 3), ("w", 3), ("feet", 12))}  # the step's outputs a cotangent may be given on
+# the batch a read-only call marshals (_readonly_batch): (name, trailing size, torch dtype name) - the state and the feet, and with the contact mask
+_STATE_FIELDS = tuple((k, m, "float64") for k, m in _IN_FIELDS + (("joint_q", 12),))
+_READONLY_FIELDS = _STATE_FIELDS + (("stance", 4, "uint8"), ("gait_phase", 4, "float64"), ("gait_duty", 1, "float64"))
 
 
 def certify_summary(t):

@@ -2031,6 +2031,31 @@ static int plan_launch(qc_handle* h, long n, bool kin, bool warm, qc::LaunchPlan
   return qc::plan_launch(qc::form_of(h->tune), n, kin, warm, h->tune, h->cus, [h](int kernel, bool k) { return resident_workgroups(h, kernel, k); }, lp);
 }
 
+// how every qc_default_* opens: the record zeroed and its struct_size set; false for a null record
+template <class Io>
+static bool zeroed(Io* io) {
+  if (!io) return false;
+  std::memset(io, 0, sizeof(Io));
+  io->struct_size = sizeof(Io);
+  return true;
+}
+
+// What the certificate and the adjoint kernels read of a qc_batch_in: what the solve reads minus everything that advances or plans
+// (gait_dt, swing_*) - nothing of `in` is written.  mask = false drops the contact-mask arrays too (stance, gait_phase, gait_duty).
+static qc::BatchIn readonly_view(const qc_batch_in* in, bool mask) {
+  return qc::BatchIn{in->Rwb, in->Rwb_d, in->x, in->xdot, in->w, in->x_d, in->xdot_d, in->w_d, in->feet, mask ? in->stance : nullptr, in->joint_q,
+                     mask ? in->gait_phase : nullptr, mask ? in->gait_duty : nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+}
+
+// one launch of a `template <bool KIN>` per-robot kernel - `kin` where `bi` carries joint_q, `feet` where it does not -, checked
+template <class Args>
+static int launch_per_robot(void (*kin)(const qc::DevParams*, long, qc::BatchIn, Args), void (*feet)(const qc::DevParams*, long, qc::BatchIn, Args),
+                            unsigned blocks, int block, const qc_handle* h, size_t n, const qc::BatchIn& bi, const Args& a, void* stream) {
+  (bi.joint_q ? kin : feet)<<<dim3(blocks), dim3(block), 0, (hipStream_t)stream>>>(h->d_params, (long)n, bi, a);
+  QC_HIP(hipGetLastError());
+  return QC_OK;
+}
+
 extern "C" {
 
 const char* qc_last_error(void) { return qc::g_err.c_str(); }
@@ -2064,9 +2089,7 @@ void qc_swing_state_init(qc_swing_state* s, size_t n) {
 }
 
 void qc_default_command(qc_command_in* c) {
-  if (!c) return;
-  std::memset(c, 0, sizeof(*c));
-  c->struct_size = sizeof(qc_command_in);
+  if (!zeroed(c)) return;
   c->stand_height = 0.26;  // x_stand(2), commander_node.cpp:355
   c->stand_tol = 0.005;    // commander_node.cpp:387
   c->cmd_dt = 0.001;       // "User cmd integration step", commander_node.cpp:344
@@ -2216,19 +2239,15 @@ int qc_tick_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_comman
 }
 
 void qc_default_plant(qc_plant_io* io) {
-  if (!io) return;
-  std::memset(io, 0, sizeof(*io));
-  io->struct_size = sizeof(qc_plant_io);
+  if (!zeroed(io)) return;
   io->dt = 1.0 / 300.0;  // mit_cheetah_config.yaml:3
 }
 
 int qc_plant_step_batch(qc_handle* h, size_t n, const qc_plant_io* io, void* stream) {
   if (const int rc = qc::check_plant_args(h, n, io); rc != QC_OK || n == 0) return rc;
   qc::PlantArgs a;
-  if (const int rc = qc::plant_constants(h->dp.mass, h->dp.Ib, io->dt, a); rc != QC_OK) return rc;
+  if (const int rc = qc::plant_constants(h->dp.mass, h->dp.Ib, io, a); rc != QC_OK) return rc;
   QC_HIP(hipSetDevice(h->device));
-  a.Rwb = io->Rwb; a.x = io->x; a.xdot = io->xdot; a.w = io->w;
-  a.grf_body = io->grf_body; a.foot_world = io->foot_world; a.feet = io->feet;
   const unsigned blocks = (unsigned)((n + qc::PLANT_BLOCK - 1) / qc::PLANT_BLOCK);
   qc::plant_step_kernel<<<dim3(blocks), dim3(qc::PLANT_BLOCK), 0, (hipStream_t)stream>>>((long)n, a);
   QC_HIP(hipGetLastError());
@@ -2236,9 +2255,7 @@ int qc_plant_step_batch(qc_handle* h, size_t n, const qc_plant_io* io, void* str
 }
 
 void qc_default_plant_adjoint(qc_plant_adjoint_io* io) {
-  if (!io) return;
-  std::memset(io, 0, sizeof(*io));
-  io->struct_size = sizeof(qc_plant_adjoint_io);
+  if (!zeroed(io)) return;
   io->dt = 1.0 / 300.0;  // qc_default_plant's
 }
 
@@ -2254,9 +2271,7 @@ int qc_plant_step_adjoint_batch(qc_handle* h, size_t n, const qc_plant_adjoint_i
 }
 
 void qc_default_leg_plant(qc_leg_plant_io* io) {
-  if (!io) return;
-  std::memset(io, 0, sizeof(*io));  // (leg_inertia 0: the reference has no number for it, the caller gives one)
-  io->struct_size = sizeof(qc_leg_plant_io);
+  if (!zeroed(io)) return;  // (leg_inertia 0: the reference has no number for it, the caller gives one)
   io->dt = 1.0 / 300.0;  // mit_cheetah_config.yaml:3
 }
 
@@ -2265,11 +2280,6 @@ int qc_leg_plant_step_batch(qc_handle* h, size_t n, const qc_leg_plant_io* io, v
   qc::LegPlantArgs a;
   if (const int rc = qc::leg_plant_constants(h->dp.mass, h->dp.Ib, io, a); rc != QC_OK) return rc;
   QC_HIP(hipSetDevice(h->device));
-  a.Rwb = io->Rwb; a.x = io->x; a.xdot = io->xdot; a.w = io->w;
-  a.joint_q = io->joint_q; a.joint_qdot = io->joint_qdot; a.joint_tau = io->joint_tau;
-  a.stance = io->stance; a.gait_phase = io->gait_phase; a.gait_duty = io->gait_duty;
-  a.cmd_state = reinterpret_cast<const qc::CmdState*>(io->cmd_state);
-  a.foot_world = io->foot_world; a.flags = io->flags;
   const unsigned blocks = (unsigned)((n + qc::LEG_PLANT_BLOCK - 1) / qc::LEG_PLANT_BLOCK);
   qc::leg_plant_step_kernel<<<dim3(blocks), dim3(qc::LEG_PLANT_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, a);
   QC_HIP(hipGetLastError());
@@ -2277,9 +2287,7 @@ int qc_leg_plant_step_batch(qc_handle* h, size_t n, const qc_leg_plant_io* io, v
 }
 
 void qc_default_certify(qc_certify_io* io) {
-  if (!io) return;
-  std::memset(io, 0, sizeof(*io));
-  io->struct_size = sizeof(qc_certify_io);
+  if (!zeroed(io)) return;
   io->act_tol = 1e-7;  // the defaults of tests/kkt_batch.py: kkt_batch's act_tol, assert_kkt's bars
   io->primal_tol = 1e-7;
   io->stat_tol = 1e-8;
@@ -2288,15 +2296,10 @@ void qc_default_certify(qc_certify_io* io) {
 int qc_certify_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_certify_io* io, void* stream) {
   if (const int rc = qc::check_certify_args(h, n, in, io); rc != QC_OK || n == 0) return rc;
   QC_HIP(hipSetDevice(h->device));
-  // what the solve reads of `in`, minus everything that advances or plans (gait_dt, swing_*): nothing of `in` is written
-  qc::BatchIn bi{in->Rwb, in->Rwb_d, in->x, in->xdot, in->w, in->x_d, in->xdot_d, in->w_d, in->feet, in->stance, in->joint_q,
-                 in->gait_phase, in->gait_duty, nullptr, nullptr, nullptr, nullptr, nullptr};
   qc::CertifyArgs a{io->grf_body, io->act_tol, io->primal_tol, io->stat_tol, io->primal, io->stationarity, io->lambda, io->grad,
                     io->active, io->flags, io->summary ? h->certify_parts : nullptr};
   const unsigned blocks = qc::certify_blocks(n);
-  if (in->joint_q) qc::certify_kernel<true><<<dim3(blocks), dim3(qc::CERTIFY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, bi, a);
-  else qc::certify_kernel<false><<<dim3(blocks), dim3(qc::CERTIFY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, bi, a);
-  QC_HIP(hipGetLastError());
+  if (const int rc = launch_per_robot(qc::certify_kernel<true>, qc::certify_kernel<false>, blocks, qc::CERTIFY_BLOCK, h, n, readonly_view(in, true), a, stream); rc != QC_OK) return rc;
   if (io->summary) {
     qc::certify_summary_kernel<<<dim3(1), dim3(qc::CERTIFY_SUMMARY_BLOCK), 0, (hipStream_t)stream>>>(h->certify_parts, (int)blocks,
                                                                                                     reinterpret_cast<qc::CertifySummary*>(io->summary));
@@ -2306,45 +2309,26 @@ int qc_certify_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_cer
 }
 
 void qc_default_sensitivity(qc_sensitivity_io* io) {
-  if (!io) return;
-  std::memset(io, 0, sizeof(*io));
-  io->struct_size = sizeof(qc_sensitivity_io);
+  if (!zeroed(io)) return;
   io->act_tol = 1e-7;  // qc_default_certify's
 }
 
 int qc_sensitivity_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_io* io, void* stream) {
   if (const int rc = qc::check_sensitivity_args(h, n, in, io); rc != QC_OK || n == 0) return rc;
   QC_HIP(hipSetDevice(h->device));
-  // what the certificate reads of `in`: nothing of it is written
-  qc::BatchIn bi{in->Rwb, in->Rwb_d, in->x, in->xdot, in->w, in->x_d, in->xdot_d, in->w_d, in->feet, in->stance, in->joint_q,
-                 in->gait_phase, in->gait_duty, nullptr, nullptr, nullptr, nullptr, nullptr};
   qc::SensitivityArgs a{io->grf_body, io->grf_bar, io->act_tol, io->adjoint, io->b_bar, io->feet_bar, io->x_bar, io->xdot_bar, io->w_bar,
                         io->x_d_bar, io->xdot_d_bar, io->w_d_bar, io->flags};
-  const unsigned blocks = qc::sensitivity_blocks(n);
-  if (in->joint_q) qc::sensitivity_kernel<true><<<dim3(blocks), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, bi, a);
-  else qc::sensitivity_kernel<false><<<dim3(blocks), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, bi, a);
-  QC_HIP(hipGetLastError());
-  return QC_OK;
+  return launch_per_robot(qc::sensitivity_kernel<true>, qc::sensitivity_kernel<false>, qc::sensitivity_blocks(n), qc::SENSITIVITY_BLOCK, h, n, readonly_view(in, true), a, stream);
 }
 
-void qc_default_sensitivity_rot(qc_sensitivity_rot_io* io) {
-  if (!io) return;
-  std::memset(io, 0, sizeof(*io));
-  io->struct_size = sizeof(qc_sensitivity_rot_io);
-}
+void qc_default_sensitivity_rot(qc_sensitivity_rot_io* io) { (void)zeroed(io); }
 
 int qc_sensitivity_rot_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_rot_io* io, void* stream) {
   if (const int rc = qc::check_sensitivity_rot_args(h, n, in, io); rc != QC_OK || n == 0) return rc;
   QC_HIP(hipSetDevice(h->device));
-  // the state and the feet, nothing else of `in` (no contact mask: swing feet carry zeros); nothing of it is written
-  qc::BatchIn bi{in->Rwb, in->Rwb_d, in->x, in->xdot, in->w, in->x_d, in->xdot_d, in->w_d, in->feet, nullptr, in->joint_q,
-                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   qc::SensitivityRotArgs a{io->grf_body, io->grf_bar, io->b_bar, io->feet_bar, io->Rwb_bar, io->Rwb_d_bar, io->Rwb_rot_bar, io->Rwb_d_rot_bar};
-  const unsigned blocks = qc::sensitivity_blocks(n);
-  if (in->joint_q) qc::sensitivity_rot_kernel<true><<<dim3(blocks), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, bi, a);
-  else qc::sensitivity_rot_kernel<false><<<dim3(blocks), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, bi, a);
-  QC_HIP(hipGetLastError());
-  return QC_OK;
+  // (no contact mask: swing feet carry zeros)
+  return launch_per_robot(qc::sensitivity_rot_kernel<true>, qc::sensitivity_rot_kernel<false>, qc::sensitivity_blocks(n), qc::SENSITIVITY_BLOCK, h, n, readonly_view(in, false), a, stream);
 }
 
 // host-pointer variant.  Large batches: one device staging allocation, H2D copies, kernel, D2H copies, sync.

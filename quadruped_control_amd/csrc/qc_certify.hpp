@@ -117,6 +117,28 @@ QC_DEV void classify_foot(double mu, double fzmin, double fzmax, double act_tol,
   cz = (fz - fzmin <= act_tol * (1.0 + fzmin) ? 1 : 0) | (fzmax - fz <= act_tol * (1.0 + fzmax) ? 2 : 0);
 }
 
+// The world-frame forces and the wrench residual of a robot: f_l = -Rwb grf_body_l, u = A f - b = (sum f_l, sum r_l x f_l) - b -
+// shared with the sensitivity kernel.
+QC_DEV void forces_and_residual(const double (&R)[9], const double (&gb)[4][3], const Wrench<4>& W, double (&f)[4][3], double (&u)[6]) {
+#pragma unroll
+  for (int k = 0; k < 6; k++) u[k] = 0.0;
+#pragma unroll
+  for (int l = 0; l < 4; l++) {
+    double rg[3], m[3];
+    mat_vec(R, gb[l], rg);
+#pragma unroll
+    for (int k = 0; k < 3; k++) f[l][k] = -rg[k];
+    cross3(W.r[l], f[l], m);
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      u[k] += f[l][k];
+      u[3 + k] += m[k];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 6; k++) u[k] -= W.b[k];
+}
+
 template <bool KIN>
 __global__ __launch_bounds__(CERTIFY_BLOCK) void certify_kernel(const DevParams* __restrict__ Pg, const long n, const BatchIn in, const CertifyArgs a) {
   CertifySummary acc = summary_empty();
@@ -136,23 +158,7 @@ __global__ __launch_bounds__(CERTIFY_BLOCK) void certify_kernel(const DevParams*
 
     // f_w,i = -Rwb grf_body_i;  u = A f - b
     double f[4][3], u[6];
-#pragma unroll
-    for (int k = 0; k < 6; k++) u[k] = 0.0;
-#pragma unroll
-    for (int l = 0; l < 4; l++) {
-      double rg[3], m[3];
-      mat_vec(S.R, gb[l], rg);
-#pragma unroll
-      for (int k = 0; k < 3; k++) f[l][k] = -rg[k];
-      cross3(W.r[l], f[l], m);
-#pragma unroll
-      for (int k = 0; k < 3; k++) {
-        u[k] += f[l][k];
-        u[3 + k] += m[k];
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 6; k++) u[k] -= W.b[k];
+    forces_and_residual(S.R, gb, W, f, u);
     // v = S u, grad = 2 (A^T v + W f)
     double v[6];
     {

@@ -447,11 +447,14 @@ QC_DEV void store3(double* p, long idx, const double (&v)[3]) {
   double* q = p + 3 * idx;
   q[0] = v[0]; q[1] = v[1]; q[2] = v[2];
 }
-QC_DEV void mat_vec(const double (&m)[9], const double (&v)[3], double (&o)[3]) {  // o = m v
+// (T: double, or the constant address space's double of a matrix that lives in CParams)
+template <class T>
+QC_DEV void mat_vec(const T (&m)[9], const double (&v)[3], double (&o)[3]) {  // o = m v
 #pragma unroll
   for (int r = 0; r < 3; r++) o[r] = m[3 * r] * v[0] + m[3 * r + 1] * v[1] + m[3 * r + 2] * v[2];
 }
-QC_DEV void mat_t_vec(const double (&m)[9], const double (&v)[3], double (&o)[3]) {  // o = m^T v
+template <class T>
+QC_DEV void mat_t_vec(const T (&m)[9], const double (&v)[3], double (&o)[3]) {  // o = m^T v
 #pragma unroll
   for (int c = 0; c < 3; c++) o[c] = m[c] * v[0] + m[3 + c] * v[1] + m[6 + c] * v[2];
 }

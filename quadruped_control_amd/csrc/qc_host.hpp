@@ -48,6 +48,17 @@ inline int check_one_launch(const char* who, size_t n, int block) {
   if (n > (size_t)0xFFFFFF * (size_t)block) return fail(QC_ERR_INVALID, std::string(who) + ": n is beyond one launch");
   return QC_OK;
 }
+// How an entry point with an io record opens: the handle and the batch (`others`) and the record are there, in this library's revision.
+template <class Io>
+int check_io(const char* who, bool others, const Io* io, const char* struct_name, const char* default_fn_name) {
+  if (!others || !io) return fail(QC_ERR_INVALID, std::string(who) + ": null argument");
+  return check_struct_size(who, struct_name, default_fn_name, io->struct_size, sizeof(Io));
+}
+// workgroups of a per-robot kernel for n robots: `block` robots each, capped at `cap` (the waves stride beyond it)
+inline unsigned capped_blocks(size_t n, int block, int cap) {
+  const size_t b = (n + (size_t)block - 1) / (size_t)block;
+  return (unsigned)(b < (size_t)cap ? b : (size_t)cap);
+}
 
 // What qc_create derived from its parameters about the formulation, and the overrides of qc_set_tuning.
 struct Tuning {
@@ -441,8 +452,7 @@ inline int check_swing_gait_args(const qc_batch_in* in, const qc_batch_out* out)
 
 // qc_tick_batch
 inline int check_tick_args(const qc_handle* h, const qc_batch_in* in, const qc_command_in* cmd, const qc_batch_out* out) {
-  if (!h || !in || !cmd || !out) return fail(QC_ERR_INVALID, "qc_tick_batch: null argument");
-  if (const int rc = check_struct_size("qc_tick_batch", "qc_command_in", "qc_default_command", cmd->struct_size, sizeof(qc_command_in)); rc != QC_OK) return rc;
+  if (const int rc = check_io("qc_tick_batch", h && in && out, cmd, "qc_command_in", "qc_default_command"); rc != QC_OK) return rc;
   if (!in->Rwb || !in->x || !in->xdot || !in->w || !in->joint_q || !in->joint_qdot || !in->gait_phase || !in->gait_dt || !in->swing_state)
     return fail(QC_ERR_INVALID, "qc_tick_batch: the complete tick needs Rwb, x, xdot, w, joint_q, joint_qdot, gait_phase, gait_dt and swing_state");
   if (in->Rwb_d || in->x_d || in->xdot_d || in->w_d)
@@ -484,138 +494,127 @@ inline int body_constants(const char* who, double mass, const double* Ib, double
   return QC_OK;
 }
 inline int plant_constants(double mass, const double* Ib, double dt, PlantArgs& a) { return body_constants("qc_plant_step_batch", mass, Ib, dt, a); }
+// the kernel's arguments: the body's constants and the call's arrays
+inline int plant_constants(double mass, const double* Ib, const qc_plant_io* io, PlantArgs& a) {
+  if (const int rc = plant_constants(mass, Ib, io->dt, a); rc != QC_OK) return rc;
+  a.Rwb = io->Rwb; a.x = io->x; a.xdot = io->xdot; a.w = io->w; a.grf_body = io->grf_body; a.foot_world = io->foot_world; a.feet = io->feet;
+  return QC_OK;
+}
+
+// What the three plant-type calls refuse after check_io, in this order: dt; `own`, the call's first refusal about its other scalars
+// and optional arrays (nullptr: none); for n > 0 the state arrays, the call's other required arrays (`others`) and the launch bound.
+template <class Io>
+int check_plant_io(const char* who, size_t n, const Io* io, const char* own, bool others, const char* others_msg, int block) {
+  const auto bad = [who](const char* what) { return fail(QC_ERR_INVALID, std::string(who) + what); };
+  if (!std::isfinite(io->dt) || !(io->dt > 0.0)) return bad(": dt must be finite and > 0");
+  if (own) return bad(own);
+  if (n == 0) return QC_OK;
+  if (!io->Rwb || !io->x || !io->xdot || !io->w) return bad(": the state arrays Rwb, x, xdot and w are required");
+  if (!others) return bad(others_msg);
+  return check_one_launch(who, n, block);
+}
 
 inline int check_plant_args(const qc_handle* h, size_t n, const qc_plant_io* io) {
-  if (!h || !io) return fail(QC_ERR_INVALID, "qc_plant_step_batch: null argument");
-  if (const int rc = check_struct_size("qc_plant_step_batch", "qc_plant_io", "qc_default_plant", io->struct_size, sizeof(qc_plant_io)); rc != QC_OK) return rc;
-  if (!std::isfinite(io->dt) || !(io->dt > 0.0)) return fail(QC_ERR_INVALID, "qc_plant_step_batch: dt must be finite and > 0");
-  if (n == 0) return QC_OK;
-  if (!io->Rwb || !io->x || !io->xdot || !io->w) return fail(QC_ERR_INVALID, "qc_plant_step_batch: the state arrays Rwb, x, xdot and w are required");
-  if (!io->grf_body || !io->foot_world) return fail(QC_ERR_INVALID, "qc_plant_step_batch: grf_body and foot_world are required");
-  return check_one_launch("qc_plant_step_batch", n, PLANT_BLOCK);
+  const char* who = "qc_plant_step_batch";
+  if (const int rc = check_io(who, h != nullptr, io, "qc_plant_io", "qc_default_plant"); rc != QC_OK) return rc;
+  return check_plant_io(who, n, io, nullptr, io->grf_body && io->foot_world, ": grf_body and foot_world are required", PLANT_BLOCK);
 }
 
 // ---------------------------------------------------------------- qc_plant_step_adjoint_batch
-// The argument check of the plant step's reverse pass: what is wrong with the call itself (message prefix
-// "qc_plant_step_adjoint_batch:").  The handle's mass and Ib are judged by plant_adjoint_constants, through the plant's own checks.
+// What is wrong with the call itself; the handle's mass and Ib are judged by plant_adjoint_constants, through the plant's own checks.
 inline int check_plant_adjoint_args(const qc_handle* h, size_t n, const qc_plant_adjoint_io* io) {
-  if (!h || !io) return fail(QC_ERR_INVALID, "qc_plant_step_adjoint_batch: null argument");
-  if (const int rc = check_struct_size("qc_plant_step_adjoint_batch", "qc_plant_adjoint_io", "qc_default_plant_adjoint", io->struct_size, sizeof(qc_plant_adjoint_io));
-      rc != QC_OK)
-    return rc;
-  if (!std::isfinite(io->dt) || !(io->dt > 0.0)) return fail(QC_ERR_INVALID, "qc_plant_step_adjoint_batch: dt must be finite and > 0");
+  const char* who = "qc_plant_step_adjoint_batch";
+  if (const int rc = check_io(who, h != nullptr, io, "qc_plant_adjoint_io", "qc_default_plant_adjoint"); rc != QC_OK) return rc;
+  const char* own = nullptr;
   if (!io->Rwb_next_bar && !io->x_next_bar && !io->xdot_next_bar && !io->w_next_bar && !io->feet_next_bar)
-    return fail(QC_ERR_INVALID, "qc_plant_step_adjoint_batch: no input cotangent given (Rwb_next_bar, x_next_bar, xdot_next_bar, w_next_bar, feet_next_bar are all NULL)");
-  if (!io->Rwb_bar && !io->x_bar && !io->xdot_bar && !io->w_bar && !io->grf_bar && !io->foot_world_bar)
-    return fail(QC_ERR_INVALID, "qc_plant_step_adjoint_batch: no output requested (Rwb_bar, x_bar, xdot_bar, w_bar, grf_bar, foot_world_bar are all NULL)");
-  if (n == 0) return QC_OK;
-  if (!io->Rwb || !io->x || !io->xdot || !io->w) return fail(QC_ERR_INVALID, "qc_plant_step_adjoint_batch: the state arrays Rwb, x, xdot and w are required");
-  if (!io->grf_body || !io->foot_world) return fail(QC_ERR_INVALID, "qc_plant_step_adjoint_batch: grf_body and foot_world are required");
-  return check_one_launch("qc_plant_step_adjoint_batch", n, PLANT_BLOCK);
+    own = ": no input cotangent given (Rwb_next_bar, x_next_bar, xdot_next_bar, w_next_bar, feet_next_bar are all NULL)";
+  else if (!io->Rwb_bar && !io->x_bar && !io->xdot_bar && !io->w_bar && !io->grf_bar && !io->foot_world_bar)
+    own = ": no output requested (Rwb_bar, x_bar, xdot_bar, w_bar, grf_bar, foot_world_bar are all NULL)";
+  return check_plant_io(who, n, io, own, io->grf_body && io->foot_world, ": grf_body and foot_world are required", PLANT_BLOCK);
 }
 
 // the kernel's arguments: the body's constants (body_constants, under this entry point's name) and the call's arrays
 inline int plant_adjoint_constants(double mass, const double* Ib, const qc_plant_adjoint_io* io, PlantAdjointArgs& a) {
   if (const int rc = body_constants("qc_plant_step_adjoint_batch", mass, Ib, io->dt, a); rc != QC_OK) return rc;
-  a.Rwb = io->Rwb; a.x = io->x; a.xdot = io->xdot; a.w = io->w;
-  a.grf_body = io->grf_body; a.foot_world = io->foot_world;
-  a.Rwb_next_bar = io->Rwb_next_bar; a.x_next_bar = io->x_next_bar; a.xdot_next_bar = io->xdot_next_bar;
-  a.w_next_bar = io->w_next_bar; a.feet_next_bar = io->feet_next_bar;
-  a.Rwb_bar = io->Rwb_bar; a.x_bar = io->x_bar; a.xdot_bar = io->xdot_bar; a.w_bar = io->w_bar;
-  a.grf_bar = io->grf_bar; a.foot_world_bar = io->foot_world_bar;
+  a.Rwb = io->Rwb; a.x = io->x; a.xdot = io->xdot; a.w = io->w; a.grf_body = io->grf_body; a.foot_world = io->foot_world;
+  a.Rwb_next_bar = io->Rwb_next_bar; a.x_next_bar = io->x_next_bar; a.xdot_next_bar = io->xdot_next_bar; a.w_next_bar = io->w_next_bar;
+  a.feet_next_bar = io->feet_next_bar;
+  a.Rwb_bar = io->Rwb_bar; a.x_bar = io->x_bar; a.xdot_bar = io->xdot_bar; a.w_bar = io->w_bar; a.grf_bar = io->grf_bar; a.foot_world_bar = io->foot_world_bar;
   return QC_OK;
 }
 
 // ---------------------------------------------------------------- qc_leg_plant_step_batch
-// The argument check of the legged plant step: what is wrong with the call itself.  (The handle's mass and Ib are judged by
-// leg_plant_constants, through the plant's own checks, when the constants are derived.)
+// What is wrong with the call itself; the handle's mass and Ib are judged by leg_plant_constants, through the plant's own checks.
 inline int check_leg_plant_args(const qc_handle* h, size_t n, const qc_leg_plant_io* io) {
-  if (!h || !io) return fail(QC_ERR_INVALID, "qc_leg_plant_step_batch: null argument");
-  if (const int rc = check_struct_size("qc_leg_plant_step_batch", "qc_leg_plant_io", "qc_default_leg_plant", io->struct_size, sizeof(qc_leg_plant_io)); rc != QC_OK)
-    return rc;
-  if (!std::isfinite(io->dt) || !(io->dt > 0.0)) return fail(QC_ERR_INVALID, "qc_leg_plant_step_batch: dt must be finite and > 0");
+  const char* who = "qc_leg_plant_step_batch";
+  if (const int rc = check_io(who, h != nullptr, io, "qc_leg_plant_io", "qc_default_leg_plant"); rc != QC_OK) return rc;
+  const char* own = nullptr;
   for (int k = 0; k < 3; k++)
     if (!std::isfinite(io->leg_inertia[k]) || !(io->leg_inertia[k] > 0.0))
-      return fail(QC_ERR_INVALID, "qc_leg_plant_step_batch: leg_inertia (hip, thigh, calf) must be finite and > 0; qc_default_leg_plant leaves it at 0, the caller gives it");
-  if (n == 0) return QC_OK;
-  if (!io->Rwb || !io->x || !io->xdot || !io->w) return fail(QC_ERR_INVALID, "qc_leg_plant_step_batch: the state arrays Rwb, x, xdot and w are required");
-  if (!io->joint_q || !io->joint_qdot || !io->joint_tau) return fail(QC_ERR_INVALID, "qc_leg_plant_step_batch: joint_q, joint_qdot and joint_tau are required");
-  return check_one_launch("qc_leg_plant_step_batch", n, LEG_PLANT_BLOCK);
+      own = ": leg_inertia (hip, thigh, calf) must be finite and > 0; qc_default_leg_plant leaves it at 0, the caller gives it";
+  return check_plant_io(who, n, io, own, io->joint_q && io->joint_qdot && io->joint_tau, ": joint_q, joint_qdot and joint_tau are required", LEG_PLANT_BLOCK);
 }
 
-// the kernel's constants: the body's (body_constants, under this entry point's name) and the call's leg inertia
+// the kernel's arguments: the body's constants (body_constants, under this entry point's name), the call's leg inertia and its arrays
 inline int leg_plant_constants(double mass, const double* Ib, const qc_leg_plant_io* io, LegPlantArgs& a) {
   if (const int rc = body_constants("qc_leg_plant_step_batch", mass, Ib, io->dt, a); rc != QC_OK) return rc;
   for (int k = 0; k < 3; k++) a.leg_inertia[k] = io->leg_inertia[k];
+  a.Rwb = io->Rwb; a.x = io->x; a.xdot = io->xdot; a.w = io->w; a.joint_q = io->joint_q; a.joint_qdot = io->joint_qdot; a.joint_tau = io->joint_tau;
+  a.stance = io->stance; a.gait_phase = io->gait_phase; a.gait_duty = io->gait_duty; a.cmd_state = reinterpret_cast<const CmdState*>(io->cmd_state);
+  a.foot_world = io->foot_world; a.flags = io->flags;
   return QC_OK;
 }
 
-// ---------------------------------------------------------------- qc_certify_batch
+// ---------------------------------------------------------------- qc_certify_batch, qc_sensitivity_batch, qc_sensitivity_rot_batch
+// What the three calls that only read a solved batch refuse after check_io, in this order: `own`, the call's first refusal about its
+// scalars and outputs (nullptr: none); for n > 0 the call's input arrays (`inputs`), the state, feet or joint_q and the launch bound.
+inline int check_readonly_batch(const char* who, size_t n, const qc_batch_in* in, const char* own, bool inputs, const char* inputs_msg, int block) {
+  const auto bad = [who](const char* what) { return fail(QC_ERR_INVALID, std::string(who) + what); };
+  if (own) return bad(own);
+  if (n == 0) return QC_OK;
+  if (!inputs) return bad(inputs_msg);
+  if (!in->Rwb || !in->Rwb_d || !in->x || !in->xdot || !in->w || !in->x_d || !in->xdot_d || !in->w_d)
+    return bad(": the state arrays Rwb, Rwb_d, x, xdot, w, x_d, xdot_d and w_d are required (commander mode is out of scope)");
+  if (!in->feet && !in->joint_q) return bad(": feet or joint_q is required");
+  return check_one_launch(who, n, block);
+}
+
 // The argument check of the certificate: what is wrong with the call itself (message prefix "qc_certify_batch:").
 inline int check_certify_args(const qc_handle* h, size_t n, const qc_batch_in* in, const qc_certify_io* io) {
-  if (!h || !in || !io) return fail(QC_ERR_INVALID, "qc_certify_batch: null argument");
-  if (const int rc = check_struct_size("qc_certify_batch", "qc_certify_io", "qc_default_certify", io->struct_size, sizeof(qc_certify_io)); rc != QC_OK) return rc;
-  const double tols[3] = {io->act_tol, io->primal_tol, io->stat_tol};
-  for (int k = 0; k < 3; k++)
-    if (!std::isfinite(tols[k]) || !(tols[k] >= 0.0)) return fail(QC_ERR_INVALID, "qc_certify_batch: act_tol, primal_tol and stat_tol must be finite and >= 0");
-  if (!io->primal && !io->stationarity && !io->lambda && !io->grad && !io->active && !io->flags && !io->summary)
-    return fail(QC_ERR_INVALID, "qc_certify_batch: no output requested (primal, stationarity, lambda, grad, active, flags, summary are all NULL)");
-  if (n == 0) return QC_OK;
-  if (!io->grf_body) return fail(QC_ERR_INVALID, "qc_certify_batch: grf_body is required");
-  if (!in->Rwb || !in->Rwb_d || !in->x || !in->xdot || !in->w || !in->x_d || !in->xdot_d || !in->w_d)
-    return fail(QC_ERR_INVALID, "qc_certify_batch: the state arrays Rwb, Rwb_d, x, xdot, w, x_d, xdot_d and w_d are required (commander mode is out of scope)");
-  if (!in->feet && !in->joint_q) return fail(QC_ERR_INVALID, "qc_certify_batch: feet or joint_q is required");
-  // (robot indices times 12 stay far inside 64 bits; the bound is the plant steps': fewer than 2^32 lanes of CERTIFY_BLOCK-wide groups)
-  return check_one_launch("qc_certify_batch", n, CERTIFY_BLOCK);
+  const char* who = "qc_certify_batch";
+  if (const int rc = check_io(who, h && in, io, "qc_certify_io", "qc_default_certify"); rc != QC_OK) return rc;
+  const auto tol_ok = [](double t) { return std::isfinite(t) && t >= 0.0; };
+  const char* own = nullptr;
+  if (!tol_ok(io->act_tol) || !tol_ok(io->primal_tol) || !tol_ok(io->stat_tol)) own = ": act_tol, primal_tol and stat_tol must be finite and >= 0";
+  else if (!io->primal && !io->stationarity && !io->lambda && !io->grad && !io->active && !io->flags && !io->summary)
+    own = ": no output requested (primal, stationarity, lambda, grad, active, flags, summary are all NULL)";
+  return check_readonly_batch(who, n, in, own, io->grf_body != nullptr, ": grf_body is required", CERTIFY_BLOCK);
 }
 
-// workgroups of certify_kernel for n robots: one wave each, capped at the handle's partial buffer (the waves stride beyond it)
-inline unsigned certify_blocks(size_t n) {
-  const size_t b = (n + CERTIFY_BLOCK - 1) / CERTIFY_BLOCK;
-  return (unsigned)(b < (size_t)CERTIFY_MAX_PARTIALS ? b : (size_t)CERTIFY_MAX_PARTIALS);
-}
+// workgroups of certify_kernel for n robots: one wave each, capped at the handle's partial buffer
+inline unsigned certify_blocks(size_t n) { return capped_blocks(n, CERTIFY_BLOCK, CERTIFY_MAX_PARTIALS); }
 
-// ---------------------------------------------------------------- qc_sensitivity_batch
 // The argument check of the adjoint: what is wrong with the call itself (message prefix "qc_sensitivity_batch:").
 inline int check_sensitivity_args(const qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_io* io) {
-  if (!h || !in || !io) return fail(QC_ERR_INVALID, "qc_sensitivity_batch: null argument");
-  if (const int rc = check_struct_size("qc_sensitivity_batch", "qc_sensitivity_io", "qc_default_sensitivity", io->struct_size, sizeof(qc_sensitivity_io)); rc != QC_OK)
-    return rc;
-  if (!std::isfinite(io->act_tol) || !(io->act_tol >= 0.0)) return fail(QC_ERR_INVALID, "qc_sensitivity_batch: act_tol must be finite and >= 0");
-  if (!io->adjoint && !io->b_bar && !io->feet_bar && !io->x_bar && !io->xdot_bar && !io->w_bar && !io->x_d_bar && !io->xdot_d_bar && !io->w_d_bar && !io->flags)
-    return fail(QC_ERR_INVALID, "qc_sensitivity_batch: no output requested (adjoint, b_bar, feet_bar, x_bar, xdot_bar, w_bar, x_d_bar, xdot_d_bar, w_d_bar, flags are all NULL)");
-  if (n == 0) return QC_OK;
-  if (!io->grf_body || !io->grf_bar) return fail(QC_ERR_INVALID, "qc_sensitivity_batch: grf_body and grf_bar are required");
-  if (!in->Rwb || !in->Rwb_d || !in->x || !in->xdot || !in->w || !in->x_d || !in->xdot_d || !in->w_d)
-    return fail(QC_ERR_INVALID, "qc_sensitivity_batch: the state arrays Rwb, Rwb_d, x, xdot, w, x_d, xdot_d and w_d are required (commander mode is out of scope)");
-  if (!in->feet && !in->joint_q) return fail(QC_ERR_INVALID, "qc_sensitivity_batch: feet or joint_q is required");
-  return check_one_launch("qc_sensitivity_batch", n, SENSITIVITY_BLOCK);
+  const char* who = "qc_sensitivity_batch";
+  if (const int rc = check_io(who, h && in, io, "qc_sensitivity_io", "qc_default_sensitivity"); rc != QC_OK) return rc;
+  const char* own = nullptr;
+  if (!std::isfinite(io->act_tol) || !(io->act_tol >= 0.0)) own = ": act_tol must be finite and >= 0";
+  else if (!io->adjoint && !io->b_bar && !io->feet_bar && !io->x_bar && !io->xdot_bar && !io->w_bar && !io->x_d_bar && !io->xdot_d_bar && !io->w_d_bar && !io->flags)
+    own = ": no output requested (adjoint, b_bar, feet_bar, x_bar, xdot_bar, w_bar, x_d_bar, xdot_d_bar, w_d_bar, flags are all NULL)";
+  return check_readonly_batch(who, n, in, own, io->grf_body && io->grf_bar, ": grf_body and grf_bar are required", SENSITIVITY_BLOCK);
 }
 
-// workgroups of sensitivity_kernel for n robots: one wave each, capped (the waves stride beyond the cap)
-inline unsigned sensitivity_blocks(size_t n) {
-  const size_t b = (n + SENSITIVITY_BLOCK - 1) / SENSITIVITY_BLOCK;
-  return (unsigned)(b < (size_t)SENSITIVITY_MAX_BLOCKS ? b : (size_t)SENSITIVITY_MAX_BLOCKS);
-}
+// workgroups of sensitivity_kernel and sensitivity_rot_kernel for n robots: one wave each, capped
+inline unsigned sensitivity_blocks(size_t n) { return capped_blocks(n, SENSITIVITY_BLOCK, SENSITIVITY_MAX_BLOCKS); }
 
-
-// ---------------------------------------------------------------- qc_sensitivity_rot_batch
 // The argument check of the rotation cotangents: what is wrong with the call itself (message prefix "qc_sensitivity_rot_batch:").
-// The grid is the adjoint kernel's (sensitivity_blocks).
 inline int check_sensitivity_rot_args(const qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_rot_io* io) {
-  if (!h || !in || !io) return fail(QC_ERR_INVALID, "qc_sensitivity_rot_batch: null argument");
-  if (const int rc = check_struct_size("qc_sensitivity_rot_batch", "qc_sensitivity_rot_io", "qc_default_sensitivity_rot", io->struct_size, sizeof(qc_sensitivity_rot_io));
-      rc != QC_OK)
-    return rc;
-  if (!io->Rwb_bar && !io->Rwb_d_bar && !io->Rwb_rot_bar && !io->Rwb_d_rot_bar)
-    return fail(QC_ERR_INVALID, "qc_sensitivity_rot_batch: no output requested (Rwb_bar, Rwb_d_bar, Rwb_rot_bar, Rwb_d_rot_bar are all NULL)");
-  if (n == 0) return QC_OK;
-  if (!io->grf_body || !io->grf_bar || !io->b_bar || !io->feet_bar)
-    return fail(QC_ERR_INVALID, "qc_sensitivity_rot_batch: grf_body, grf_bar, b_bar and feet_bar are required");
-  if (!in->Rwb || !in->Rwb_d || !in->x || !in->xdot || !in->w || !in->x_d || !in->xdot_d || !in->w_d)
-    return fail(QC_ERR_INVALID, "qc_sensitivity_rot_batch: the state arrays Rwb, Rwb_d, x, xdot, w, x_d, xdot_d and w_d are required (commander mode is out of scope)");
-  if (!in->feet && !in->joint_q) return fail(QC_ERR_INVALID, "qc_sensitivity_rot_batch: feet or joint_q is required");
-  return check_one_launch("qc_sensitivity_rot_batch", n, SENSITIVITY_BLOCK);
+  const char* who = "qc_sensitivity_rot_batch";
+  if (const int rc = check_io(who, h && in, io, "qc_sensitivity_rot_io", "qc_default_sensitivity_rot"); rc != QC_OK) return rc;
+  const bool no_out = !io->Rwb_bar && !io->Rwb_d_bar && !io->Rwb_rot_bar && !io->Rwb_d_rot_bar;
+  const char* own = no_out ? ": no output requested (Rwb_bar, Rwb_d_bar, Rwb_rot_bar, Rwb_d_rot_bar are all NULL)" : nullptr;
+  return check_readonly_batch(who, n, in, own, io->grf_body && io->grf_bar && io->b_bar && io->feet_bar, ": grf_body, grf_bar, b_bar and feet_bar are required", SENSITIVITY_BLOCK);
 }
 
 }  // namespace qc

@@ -87,27 +87,14 @@ __global__ __launch_bounds__(SENSITIVITY_BLOCK) void sensitivity_kernel(const De
 
     // f_i = -Rwb grf_body_i, f_bar_i = -Rwb grf_bar_i;  v = S (A f - b)
     double f[4][3], fbar[4][3], u[6];
-#pragma unroll
-    for (int k = 0; k < 6; k++) u[k] = 0.0;
+    forces_and_residual(S.R, gb, W, f, u);
 #pragma unroll
     for (int l = 0; l < 4; l++) {
-      double rg[3], rb[3], m[3];
-      mat_vec(S.R, gb[l], rg);
+      double rb[3];
       mat_vec(S.R, gbar[l], rb);
 #pragma unroll
-      for (int k = 0; k < 3; k++) {
-        f[l][k] = -rg[k];
-        fbar[l][k] = -rb[k];
-      }
-      cross3(W.r[l], f[l], m);
-#pragma unroll
-      for (int k = 0; k < 3; k++) {
-        u[k] += f[l][k];
-        u[3 + k] += m[k];
-      }
+      for (int k = 0; k < 3; k++) fbar[l][k] = -rb[k];
     }
-#pragma unroll
-    for (int k = 0; k < 6; k++) u[k] -= W.b[k];
     double v[6];
     {
       CParams& Ps = *QC_PARAMS_HERE(Pg);
@@ -275,12 +262,9 @@ __global__ __launch_bounds__(SENSITIVITY_BLOCK) void sensitivity_kernel(const De
         mat_t_vec(S.R, ba, t1);
         mat_t_vec(S.R, bxw, t2);
         mat_t_vec(S.R, S.wd, t3);
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-          u1[k] = Pb.Ib[k] * t1[0] + Pb.Ib[3 + k] * t1[1] + Pb.Ib[6 + k] * t1[2];  // Ib^T
-          u2[k] = Pb.Ib[k] * t2[0] + Pb.Ib[3 + k] * t2[1] + Pb.Ib[6 + k] * t2[2];
-          u3[k] = Pb.Ib[3 * k] * t3[0] + Pb.Ib[3 * k + 1] * t3[1] + Pb.Ib[3 * k + 2] * t3[2];  // Ib
-        }
+        mat_t_vec(Pb.Ib, t1, u1);
+        mat_t_vec(Pb.Ib, t2, u2);
+        mat_vec(Pb.Ib, t3, u3);
         mat_vec(S.R, u1, alb);
         mat_vec(S.R, u2, itb);
         mat_vec(S.R, u3, iw);

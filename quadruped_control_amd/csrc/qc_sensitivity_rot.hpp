@@ -114,13 +114,10 @@ __global__ __launch_bounds__(SENSITIVITY_BLOCK) void sensitivity_rot_kernel(cons
     mat_t_vec(R, wd, t2);
     mat_t_vec(R, ba, t3);
     mat_t_vec(R, bxw, t4);
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      u1[k] = Pb.Ib[3 * k] * t1[0] + Pb.Ib[3 * k + 1] * t1[1] + Pb.Ib[3 * k + 2] * t1[2];  // Ib
-      u2[k] = Pb.Ib[3 * k] * t2[0] + Pb.Ib[3 * k + 1] * t2[1] + Pb.Ib[3 * k + 2] * t2[2];
-      v1[k] = Pb.Ib[k] * t3[0] + Pb.Ib[3 + k] * t3[1] + Pb.Ib[6 + k] * t3[2];  // Ib^T
-      v2[k] = Pb.Ib[k] * t4[0] + Pb.Ib[3 + k] * t4[1] + Pb.Ib[6 + k] * t4[2];
-    }
+    mat_vec(Pb.Ib, t1, u1);
+    mat_vec(Pb.Ib, t2, u2);
+    mat_t_vec(Pb.Ib, t3, v1);
+    mat_t_vec(Pb.Ib, t4, v2);
 #pragma unroll
     for (int r = 0; r < 3; r++)
 #pragma unroll

@@ -475,6 +475,24 @@ static void shared_refusals() {
     CHECK_FAILS(check_one_launch("qc_some_batch", most + 1, block), "qc_some_batch: n is beyond one launch", "one robot more, block %d", block);
     CHECK_FAILS(check_one_launch("qc_some_batch", ~(size_t)0, block), "qc_some_batch: n is beyond one launch", "the largest size_t, block %d", block);
   }
+  // the capped grid of the per-robot kernels: one workgroup per `block` robots up to `cap` workgroups, `cap` beyond
+  CHECK(capped_blocks(1, 64, 4096) == 1 && capped_blocks(64, 64, 4096) == 1 && capped_blocks(65, 64, 4096) == 2, "one workgroup per 64 robots");
+  CHECK(capped_blocks(1, 256, 8) == 1 && capped_blocks(256, 256, 8) == 1 && capped_blocks(257, 256, 8) == 2 && capped_blocks(2048, 256, 8) == 8 &&
+            capped_blocks(2049, 256, 8) == 8 && capped_blocks(~(size_t)0 - 256, 256, 8) == 8,
+        "another block and cap");
+  const struct { const char* who; int block, cap; unsigned (*blocks)(size_t); } grids[] = {
+      {"certify", CERTIFY_BLOCK, CERTIFY_MAX_PARTIALS, certify_blocks}, {"sensitivity", SENSITIVITY_BLOCK, SENSITIVITY_MAX_BLOCKS, sensitivity_blocks}};
+  for (const auto& g : grids) {
+    const size_t full = (size_t)g.cap * (size_t)g.block;
+    CHECK(capped_blocks(full, g.block, g.cap) == (unsigned)g.cap && capped_blocks(full + 1, g.block, g.cap) == (unsigned)g.cap &&
+              capped_blocks(full - g.block, g.block, g.cap) == (unsigned)g.cap - 1 && capped_blocks(full - g.block + 1, g.block, g.cap) == (unsigned)g.cap,
+          "%s: the cap is reached at cap * block robots and held one robot later", g.who);
+    // what certify_blocks and sensitivity_blocks returned before they were built on capped_blocks: ceil(n / 64), at most 4096
+    const size_t ns[] = {1, 64, 65, full, full + 1};
+    const unsigned before[] = {1, 1, 2, 4096, 4096};
+    for (int k = 0; k < 5; k++)
+      CHECK(g.blocks(ns[k]) == before[k] && g.blocks(ns[k]) == capped_blocks(ns[k], g.block, g.cap), "%s_blocks(%zu)", g.who, ns[k]);
+  }
 }
 
 int main() {

@@ -98,7 +98,7 @@ def test_host_logic_without_a_device():
 
     import __graft_entry__ as g
 
-    exe = g.build_host_logic_test()
+    exe = g.build_host_test("host_logic_test")
     assert exe is not None and os.path.exists(exe)
     libs = subprocess.run(["ldd", exe], stdout=subprocess.PIPE, text=True, check=True).stdout
     assert "amdhip64" not in libs and "qc_balance" not in libs, libs

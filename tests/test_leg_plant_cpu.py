@@ -30,7 +30,7 @@ def test_host_program_passes():
     """check_leg_plant_args and leg_plant_constants with every message, under the address and undefined-behaviour sanitizers"""
     import __graft_entry__ as g
 
-    exe = g.build_leg_plant_host_test()
+    exe = g.build_host_test("leg_plant_host_test")
     assert exe is not None
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr

@@ -201,7 +201,7 @@ def test_plant_host_logic_without_a_device():
     stand-alone program built with the address and undefined-behaviour sanitizers (tests/cpp/plant_host_test.cpp)."""
     import __graft_entry__ as g
 
-    exe = g.build_plant_host_test()
+    exe = g.build_host_test("plant_host_test")
     assert exe is not None and os.path.exists(exe)
     libs = subprocess.run(["ldd", exe], stdout=subprocess.PIPE, text=True, check=True).stdout
     assert "amdhip64" not in libs and "qc_balance" not in libs, libs

@@ -241,7 +241,7 @@ def test_sensitivity_host_logic_without_a_device():
     import __graft_entry__ as g
 
     assert "sensitivity_host_test" in g.HOST_TESTS
-    exe = g.build_sensitivity_host_test()
+    exe = g.build_host_test("sensitivity_host_test")
     assert exe is not None and os.path.exists(exe)
     libs = subprocess.run(["ldd", exe], stdout=subprocess.PIPE, text=True, check=True).stdout
     assert "amdhip64" not in libs and "qc_balance" not in libs, libs
