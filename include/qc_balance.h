@@ -24,6 +24,7 @@ extern "C" {
 #endif
 
 #define QC_ABI_VERSION 6
+#define QC_PARAM_COUNT 211 /* the doubles of qc_params, in its order: the layout of a parameter cotangent (qc_sensitivity_param_batch) */
 
 /* Replaces the constructor arguments of BalanceController
  * (balance_controller.hpp:85-88; defaults in commander_node.cpp:289-334 and
@@ -459,8 +460,10 @@ int qc_certify_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_cer
  *   cotangent of the body-frame foot position whether it came from `feet` or from the kinematics of joint_q;
  *   x_bar, xdot_bar, w_bar, x_d_bar, xdot_d_bar, w_d_bar: b_bar pulled back through the PD law at fixed Rwb and Rwb_d, exactly
  *   as the library evaluates that law (the kff terms on xdot_d[0], xdot_d[1] and w_d included).
- * NOT produced: the cotangents of Rwb and Rwb_d - qc_sensitivity_rot_batch below makes them from b_bar and feet_bar; the cotangents of mu, fzmin, fzmax and the weights; weak activity - a row whose multiplier is
- * about 0 counts as active like any other (qc_certify_batch's lambda shows such rows).  Commander mode is out of scope.
+ * NOT produced: the cotangents of Rwb and Rwb_d - qc_sensitivity_rot_batch below makes them from b_bar and feet_bar; weak activity -
+ * a row whose multiplier is about 0 counts as active like any other (qc_certify_batch's lambda shows such rows).  The cotangents of the
+ * handle's own parameters - mu, fzmin, fzmax, the weights, the gains, mass and Ib - come from qc_sensitivity_param_batch below, given
+ * this call's adjoint.  Commander mode is out of scope.
  * The reduced system is solved as a fixed 12x12 LDL^T; a pivot that is not positive and finite sets bit 1 of `flags` and makes
  * every output of that robot NaN.  Non-finite inputs propagate as NaN; nothing is clamped. */
 typedef struct qc_sensitivity_io {
@@ -521,6 +524,48 @@ void qc_default_sensitivity_rot(qc_sensitivity_rot_io* io);
  * xdot, w, x_d, xdot_d, w_d - commander mode keeps the desired ones in its own record and is refused by this), neither feet nor
  * joint_q, or n beyond one launch. */
 int qc_sensitivity_rot_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_rot_io* io, void* stream);
+
+/* The parameter cotangents of a solved batch: the gradient of <grf_bar, grf_body> in the handle's own qc_params - the gains kp_p, kd_p,
+ * kp_w, kd_w and kff, the weights S and W, mu, fzmin, fzmax and the controller's mass and Ib.  Given the SAME qc_batch_in, the forces,
+ * the cotangent grf_bar on them and the `adjoint` z qc_sensitivity_batch wrote for that grf_bar (no solve is repeated).
+ * A parameter cotangent is QC_PARAM_COUNT = 211 doubles in the order of the double members of qc_params: mu, mass, fzmin, fzmax, Ib[9],
+ * S[36], W[144], kff[6], kp_p[3], kd_p[3], kp_w[3], kd_w[3].  Matrices are ENTRYWISE and row-major, the entries taken as independent
+ * (Rwb_bar's convention).  S_bar and W_bar are therefore the UNSYMMETRISED forms below: qc_create accepts symmetric S and W only, so
+ * only <S_bar, dS> with a symmetric dS (and W alike) is a derivative of anything; symmetrise them if a single entry is to be read.
+ * On the active face at fixed codes, with f the world forces, f_bar = -Rwb grf_bar, u = A f - b, v = S u, g = 2 (A^T v + W f),
+ * b_bar = 2 S A z, rho = f_bar - 2 (A^T S A z + W z):
+ *   S_bar = -2 (A z) u^T,   W_bar = -2 z f^T;
+ *   mass, kff, kp_p, kd_p, kp_w, kd_w: b_bar pulled back through the PD law line by line, exactly as the library evaluates it (mass
+ *     enters three times - m a, kff[2] m 9.81 inside a[2], and -9.81 m -, kff[5] acts on the SECOND angular component);
+ *   Ib_bar = Rwb^T (ba al^T + (ba x w_d) w_d^T) Rwb with ba = b_bar[3:6] (qc_sensitivity_rot_batch's Iw_bar);
+ *   mu_bar: over the stance feet, with sx, sy in {-1, 0, +1} from the x / y codes 1 / 2 / 0,
+ *     <rho_l, (sx f_lz, sy f_lz, 0)> - [fz free] z_lz (sx g_lx + sy g_ly);
+ *   fzmin_bar: over the feet with z code 1, <rho_l, (sx mu, sy mu, 1)>;  fzmax_bar: the same over the feet with z code 2.
+ * mass_bar and Ib_bar are the gradient of the CONTROLLER's use of mass and Ib (the wrench target); what a plant makes of the same two
+ * numbers is another function (qc_plant_step_adjoint_batch produces no such cotangent).  A foot with a code 3 on any axis adds nothing
+ * to mu_bar, fzmin_bar and fzmax_bar (bit 0 of qc_sensitivity_batch's flags marks that robot: one-sided).  A failed robot (all forces
+ * zero) gives a zero row, a NaN adjoint (flags bit 1) a NaN row - and a NaN sum.  Non-finite inputs propagate; nothing is clamped.
+ * Commander mode is out of scope. */
+typedef struct qc_sensitivity_param_io {
+  size_t struct_size;        /* = sizeof(qc_sensitivity_param_io); checked                                           */
+  const double* grf_body;    /* [n][4][3] qc_batch_out.grf_body                                                      */
+  const double* grf_bar;     /* [n][4][3] cotangent on grf_body                                                      */
+  const double* adjoint;     /* [n][12]   qc_sensitivity_io.adjoint for that grf_bar, at the same act_tol            */
+  double act_tol;            /* active-row tolerance, finite and >= 0: the one qc_sensitivity_batch was given        */
+  double* param_bar_rows;    /* [n][QC_PARAM_COUNT] per robot                                                        */
+  double* param_bar;         /* [QC_PARAM_COUNT] the sum over the batch, written by a second, one-workgroup kernel   */
+} qc_sensitivity_param_io;
+/* struct_size set, pointers NULL, act_tol = 1e-7. */
+void qc_default_sensitivity_param(qc_sensitivity_param_io* io);
+/* Asynchronous on `stream`, no host synchronisation (graph-capturable; ordered behind qc_sensitivity_batch on the same stream it
+ * needs no event); n == 0 launches nothing and returns QC_OK (param_bar is then left as it is).  Both outputs are optional; at least
+ * one must be given.  The sum goes through a partial buffer the handle owns, reduced without atomics in an order that depends on n
+ * alone: it is bit-reproducible, the same with and without param_bar_rows, and independent of what an earlier call left in the
+ * buffer; two calls with a param_bar on one handle must be ordered on the device (one stream, or an event between them).
+ * QC_ERR_INVALID (message starting with "qc_sensitivity_param_batch:", nothing launched) for a null handle, `in` or `io`, a wrong
+ * struct_size, an act_tol that is not finite and >= 0, no output requested at all, a missing grf_body, grf_bar or adjoint, a missing
+ * state array (Rwb, Rwb_d, x, xdot, w, x_d, xdot_d, w_d), neither feet nor joint_q, or n beyond one launch. */
+int qc_sensitivity_param_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_param_io* io, void* stream);
 
 /* Differentiating a rollout: the reverse pass of qc_plant_step_batch.  Given the state BEFORE a step (Rwb, x, xdot, w), the grf_body
  * and foot_world that step read, its dt, and cotangents on what it wrote (Rwb', x', xdot', w' and the optional feet'), this writes

@@ -22,7 +22,8 @@ def cheetah_params(mu=0.8):
 
 
 def __getattr__(name):
-    if name in ("BalanceController", "to_device", "new_swing_states", "SWING_STATE_DTYPE", "new_commander_states", "COMMANDER_STATE_DTYPE"):
+    if name in ("BalanceController", "to_device", "new_swing_states", "SWING_STATE_DTYPE", "new_commander_states", "COMMANDER_STATE_DTYPE",
+                "PARAM_LAYOUT", "unpack_param_bar"):
         from . import balance_controller as _bc
 
         return getattr(_bc, name)

@@ -95,6 +95,14 @@ class QcSensitivityRotIo(C.Structure):
                 ("grf_body", "grf_bar", "b_bar", "feet_bar", "Rwb_bar", "Rwb_d_bar", "Rwb_rot_bar", "Rwb_d_rot_bar")]
 
 
+class QcSensitivityParamIo(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("grf_body", C.c_void_p), ("grf_bar", C.c_void_p), ("adjoint", C.c_void_p), ("act_tol", C.c_double),
+                ("param_bar_rows", C.c_void_p), ("param_bar", C.c_void_p)]
+
+
+PARAM_COUNT = 211  # QC_PARAM_COUNT: the doubles of QcParams, in its order
+
+
 class QcLaunchInfo(C.Structure):
     _fields_ = [("lanes_per_robot", C.c_int32), ("mode", C.c_int32), ("form", C.c_int32), ("strategies", C.c_int32),
                 ("chunk", C.c_int64), ("blocks", C.c_int64), ("resident_workgroups", C.c_int64), ("lds_bytes", C.c_int64)]
@@ -105,7 +113,8 @@ EXPORTS = ("qc_create_abi", "qc_destroy", "qc_control_batch", "qc_control_batch_
            "qc_set_tuning", "qc_query_launch", "qc_check_abi", "qc_default_command", "qc_commander_state_init", "qc_tick_batch",
            "qc_default_plant", "qc_plant_step_batch", "qc_default_leg_plant", "qc_leg_plant_step_batch",
            "qc_default_certify", "qc_certify_batch", "qc_default_sensitivity", "qc_sensitivity_batch",
-           "qc_default_sensitivity_rot", "qc_sensitivity_rot_batch", "qc_default_plant_adjoint", "qc_plant_step_adjoint_batch")
+           "qc_default_sensitivity_rot", "qc_sensitivity_rot_batch", "qc_default_plant_adjoint", "qc_plant_step_adjoint_batch",
+           "qc_default_sensitivity_param", "qc_sensitivity_param_batch")
 
 _lib = None
 
@@ -192,6 +201,10 @@ def load():
     lib.qc_default_sensitivity_rot.restype = None
     lib.qc_sensitivity_rot_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcBatchIn), C.POINTER(QcSensitivityRotIo), C.c_void_p]
     lib.qc_sensitivity_rot_batch.restype = C.c_int
+    lib.qc_default_sensitivity_param.argtypes = [C.POINTER(QcSensitivityParamIo)]
+    lib.qc_default_sensitivity_param.restype = None
+    lib.qc_sensitivity_param_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcBatchIn), C.POINTER(QcSensitivityParamIo), C.c_void_p]
+    lib.qc_sensitivity_param_batch.restype = C.c_int
     lib.qc_default_plant_adjoint.argtypes = [C.POINTER(QcPlantAdjointIo)]
     lib.qc_default_plant_adjoint.restype = None
     lib.qc_plant_step_adjoint_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcPlantAdjointIo), C.c_void_p]

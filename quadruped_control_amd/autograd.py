@@ -2,7 +2,8 @@
 plant_step_autograd() and rollout_autograd().
 
 Forward is control_batch() itself; backward is the adjoint of the balance QP on the active face of the forces it returned
-(qc_sensitivity_batch) and, where a rotation requires grad, the rotation cotangents behind it (qc_sensitivity_rot_batch), both
+(qc_sensitivity_batch) and, where a rotation requires grad, the rotation cotangents behind it (qc_sensitivity_rot_batch), and where
+the `params` leaf requires grad the parameter cotangents summed over the batch (qc_sensitivity_param_batch), all
 on the current stream, without host synchronisation.  The gradient is the one on the active face: valid while the working set
 holds; robots with bit 0 of the sensitivity flags have a one-sided derivative, robots with bit 1 NaN gradients.
 
@@ -12,6 +13,7 @@ from __future__ import annotations
 
 import torch
 
+from ._lib import PARAM_COUNT
 from .balance_controller import _SENSITIVITY_OUTPUTS
 
 # the inputs a gradient is produced for, in the order backward returns them, and the sensitivity output behind each
@@ -22,6 +24,7 @@ _ROTATIONS = ("Rwb", "Rwb_d")
 class _ControlBatch(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ctl, batch, act_tol, flags, control_kwargs, *tensors):
+        *tensors, params = tensors  # (params is never read: the solve uses the handle's own parameters)
         out = ctl.control_batch(batch, **control_kwargs)
         grf_body, status = out["grf_body"], out["status"]
         ctx.ctl, ctx.act_tol, ctx.flags = ctl, act_tol, flags
@@ -39,10 +42,13 @@ class _ControlBatch(torch.autograd.Function):
         inputs = {k: (next(given) if there else None) for k, there in zip(DIFFERENTIABLE, ctx.present)}
         batch = dict(ctx.rest, **{k: v for k, v in inputs.items() if v is not None})
         need = dict(zip(DIFFERENTIABLE, ctx.needs_input_grad[5:]))
+        need_params = ctx.needs_input_grad[5 + len(DIFFERENTIABLE)]
         rot = [k for k in _ROTATIONS if need[k]]
         want = [k + "_bar" for k in DIFFERENTIABLE[2:] if need[k]]
         if rot:
             want += [k for k in ("b_bar", "feet_bar") if k not in want]
+        if need_params:
+            want.append("adjoint")
         out = None
         if ctx.flags is not None:  # the caller's tensor receives the flags; the other outputs are allocated as sensitivity_batch would
             shape = lambda k: (grf_body.shape[0],) + _SENSITIVITY_OUTPUTS[k][0]
@@ -54,12 +60,19 @@ class _ControlBatch(torch.autograd.Function):
         if rot:
             s.update(ctx.ctl.sensitivity_rotation_batch(batch, grf_body, grf_bar, s["b_bar"], s["feet_bar"], want=tuple(k + "_bar" for k in rot)))
         grads = [s[k + "_bar"].view_as(inputs[k]) if need[k] else None for k in DIFFERENTIABLE]
-        return (None, None, None, None, None, *grads)
+        param_bar = None
+        if need_params:  # sum-only: no [n,211] rows are written
+            param_bar = ctx.ctl.sensitivity_params_batch(batch, grf_body, grf_bar, s["adjoint"], want=("param_bar",), act_tol=ctx.act_tol)["param_bar"]
+        return (None, None, None, None, None, *grads, param_bar)
 
 
-def control_batch_autograd(ctl, batch, act_tol=1e-7, flags=None, **control_kwargs):
+def control_batch_autograd(ctl, batch, act_tol=1e-7, flags=None, params=None, **control_kwargs):
     """BalanceController.control_batch_autograd (see there): (grf_body, status) of control_batch(batch, **control_kwargs), with a
-    grad_fn on grf_body whenever one of DIFFERENTIABLE in `batch` requires grad."""
+    grad_fn on grf_body whenever one of DIFFERENTIABLE in `batch`, or `params`, requires grad.  `params` ([211], PARAM_LAYOUT's order,
+    ctl.parameter_tensor() makes it) is never read by forward - the handle's own parameters are used -; its gradient is
+    sensitivity_params_batch()'s sum over the batch."""
+    if params is not None and (params.dtype != torch.float64 or params.numel() != PARAM_COUNT or params.dim() != 1):
+        raise ValueError(f"params: need a float64 [{PARAM_COUNT}] tensor (BalanceController.parameter_tensor() makes one)")
     jq = batch.get("joint_q")
     if jq is not None and jq.requires_grad:
         raise ValueError("control_batch_autograd: joint_q.requires_grad is not supported - differentiate with respect to `feet`, or chain the "
@@ -68,7 +81,7 @@ def control_batch_autograd(ctl, batch, act_tol=1e-7, flags=None, **control_kwarg
         raise ValueError("flags: need a contiguous int32 [n] tensor")
     tensors = [batch.get(k) for k in DIFFERENTIABLE]
     detached = {k: (v.detach() if isinstance(v, torch.Tensor) else v) for k, v in batch.items()}
-    return _ControlBatch.apply(ctl, detached, float(act_tol), flags, control_kwargs, *tensors)
+    return _ControlBatch.apply(ctl, detached, float(act_tol), flags, control_kwargs, *tensors, params)
 
 
 # the inputs of a plant step a gradient is produced for, in the order backward returns them; the step's outputs, in the order forward returns them
@@ -110,9 +123,10 @@ def plant_step_autograd(ctl, state, grf_body, foot_world, dt):
     return _PlantStep.apply(ctl, float(dt), *tensors)
 
 
-def rollout_autograd(ctl, batch, foot_world, steps, dt, act_tol=1e-7, warm=True):
+def rollout_autograd(ctl, batch, foot_world, steps, dt, act_tol=1e-7, warm=True, params=None):
     """BalanceController.rollout_autograd (see there): `steps` times control_batch_autograd() then plant_step_autograd(), out of place.
-    The gradient is the one on the active face of every solve along the way; memory grows with `steps`."""
+    The gradient is the one on the active face of every solve along the way; memory grows with `steps`.  `params` goes to every
+    solve: its gradient is that of the controller's use of the parameters, the plant's use of mass and Ib held fixed."""
     if batch.get("joint_q") is not None or batch.get("feet") is None:
         raise ValueError("rollout: the plant is a single rigid body - the batch carries `feet`, not joint_q")
     steps = int(steps)
@@ -128,7 +142,7 @@ def rollout_autograd(ctl, batch, foot_world, steps, dt, act_tol=1e-7, warm=True)
                    "active_set": torch.zeros((n,), dtype=torch.int32, device=dev)}
             kwargs = dict(warm=active, out=res, want_active_set=True)
             active = res["active_set"]
-        grf, status = control_batch_autograd(ctl, cur, act_tol, **kwargs)
+        grf, status = control_batch_autograd(ctl, cur, act_tol, params=params, **kwargs)
         Rwb, x, xdot, w, feet = plant_step_autograd(ctl, cur, grf, foot_world, dt)
         cur = dict(cur, Rwb=Rwb, x=x, xdot=xdot, w=w, feet=feet)
         out = {"grf_body": grf, "status": status}

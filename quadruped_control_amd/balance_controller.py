@@ -129,6 +129,8 @@ class BalanceController:
         _fill(p.kff, kff, 6, "kff"); _fill(p.kp_p, kp_p, 3, "kp_p"); _fill(p.kd_p, kd_p, 3, "kd_p")
         _fill(p.kp_w, kp_w, 3, "kp_w"); _fill(p.kd_w, kd_w, 3, "kd_w")
         p.max_iter = int(max_iter)
+        # the 211 doubles of qc_params, in its order (PARAM_LAYOUT): what parameter_tensor() hands out
+        self._param_values = np.ctypeslib.as_array((C.c_double * _lib.PARAM_COUNT).from_buffer_copy(p)).copy()
         self.leg_names = tuple(leg_names)
         if len(self.leg_names) != 4:
             raise ValueError("leg_names must hold 4 names (order RL, FL, RR, FR in the reference)")
@@ -527,7 +529,7 @@ class BalanceController:
 
         return plant_step_autograd(self, state, grf_body, foot_world, dt)
 
-    def rollout_autograd(self, batch, foot_world, steps, dt, act_tol=1e-7, warm=True):
+    def rollout_autograd(self, batch, foot_world, steps, dt, act_tol=1e-7, warm=True, params=None):
         """The functional twin of rollout(): `steps` times control_batch_autograd() then plant_step_autograd(), new tensors threaded
         through instead of `batch` being updated - `batch` is not modified.  The desired state, `stance` and `foot_world` are held;
         they, and the start state Rwb, x, xdot, w, feet, are differentiable where they require grad.  warm=True feeds each solve's
@@ -537,10 +539,13 @@ class BalanceController:
         The gradient is control_batch_autograd()'s: the one ON THE ACTIVE FACE of every solve at `act_tol` - valid while every
         working set along the rollout holds, one-sided where a foot sits on both rows of an axis, NaN behind a bad pivot - so a loss
         that moves a robot across a face change at ANY step sees a kink there.  Memory grows with `steps`: every step keeps its
-        pre-step state, forces and feet (about 0.6 kB per robot and step) until backward has run."""
+        pre-step state, forces and feet (about 0.6 kB per robot and step) until backward has run.
+        `params`: as control_batch_autograd()'s, handed to every solve of the rollout; params.grad receives the sum over the steps
+        and the robots.  It is the gradient of the CONTROLLER's use of the parameters: the plant integrates the handle's mass and Ib
+        too, and that use is held fixed (plant_step_adjoint() produces no cotangent of them)."""
         from .autograd import rollout_autograd
 
-        return rollout_autograd(self, batch, foot_world, steps, dt, act_tol, warm)
+        return rollout_autograd(self, batch, foot_world, steps, dt, act_tol, warm, params)
 
     # ------------------------------------------- closing the loop around the tick
     def _marshal_leg_plant(self, state, joint_tau, dt, leg_inertia, stance, gait_phase, gait_duty, cmd_state, foot_world, flags):
@@ -725,8 +730,8 @@ class BalanceController:
         INTEGRATION.md "Sensitivity of a solved batch").  `want`: any of "adjoint" [n,12] (world frame), "b_bar" [n,6], "feet_bar"
         [n,4,3], "x_bar", "xdot_bar", "w_bar", "x_d_bar", "xdot_d_bar", "w_d_bar" [n,3], "flags" int32 [n] (bit 0: a foot on both rows
         of an axis, the derivative is one-sided; bit 1: a bad pivot, the robot's outputs are NaN).  Rwb and Rwb_d are held fixed here:
-        their cotangents come from sensitivity_rotation_batch(), given this call's b_bar and feet_bar; no cotangent of mu, fzmin,
-        fzmax or the weights is produced.  Nothing of `batch` is written.  Asynchronous on `stream`,
+        their cotangents come from sensitivity_rotation_batch(), given this call's b_bar and feet_bar; the cotangents of the
+        handle's parameters come from sensitivity_params_batch(), given this call's adjoint.  Nothing of `batch` is written.  Asynchronous on `stream`,
         no synchronisation.  Returns the dict of device tensors; ValueError with the library's message for a call it refuses."""
         launch, res = self.plan_sensitivity(batch, grf_body, grf_bar, want, act_tol, out, stream)
         launch()
@@ -758,7 +763,52 @@ class BalanceController:
         launch()
         return res
 
-    def control_batch_autograd(self, batch, act_tol=1e-7, flags=None, **control_kwargs):
+    def parameter_tensor(self):
+        """The handle's own parameters as a new float64 [211] tensor on its device, in PARAM_LAYOUT's order (the doubles of
+        qc_params: mu, mass, fzmin, fzmax, Ib, S, W, kff, kp_p, kd_p, kp_w, kd_w): the leaf to hand to control_batch_autograd() or
+        rollout_autograd() as `params`, after requires_grad_(), so that the values a gradient step starts from are the ones the
+        handle solves with.  Changing the tensor does not change the handle: build a new controller from unpack_param_bar() of it."""
+        import torch
+
+        return torch.from_numpy(self._param_values.copy()).to(torch.device("cuda", self.device))
+
+    def plan_sensitivity_params(self, batch, grf_body, grf_bar, adjoint, want=("param_bar",), act_tol=1e-7, out=None, stream=None):
+        """sensitivity_params_batch() marshalled once: returns (launch, out), `launch()` being one qc_sensitivity_param_batch call
+        (graph-capturable) on tensors that are read in place.  Planning launches nothing.  `out`: a dict of tensors to write into
+        instead of new ones (every name in `want`).  A call the library refuses raises ValueError with its message, from launch()."""
+        io = _lib.QcSensitivityParamIo()
+        self._lib.qc_default_sensitivity_param(C.byref(io))
+        own = [("grf_body", grf_body, 12), ("grf_bar", grf_bar, 12), ("adjoint", adjoint, 12)]
+        n, dev, bi = self._readonly_batch("sensitivity_params", batch, _READONLY_FIELDS, io, own)
+        io.act_tol = float(act_tol)
+        unknown = [w for w in want if w not in ("param_bar", "param_bar_rows")]
+        if unknown:
+            raise ValueError(f"sensitivity_params: unknown output(s) {unknown}; want is a subset of ('param_bar', 'param_bar_rows')")
+        rows = tuple(w for w in want if w == "param_bar_rows")
+        extra = [("param_bar", (_lib.PARAM_COUNT,), "float64")] if "param_bar" in want else []
+        res = _outputs("sensitivity_params", _SENSITIVITY_PARAM_OUTPUTS, rows, out, n, dev, io, extra)
+        args = (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
+        return self._launcher("qc_sensitivity_param_batch", args, (batch, grf_body, grf_bar, adjoint, res, bi, io), ValueError), res
+
+    def sensitivity_params_batch(self, batch, grf_body, grf_bar, adjoint, want=("param_bar",), act_tol=1e-7, out=None, stream=None):
+        """The cotangents of the handle's own parameters (qc_sensitivity_param_batch, include/qc_balance.h; INTEGRATION.md
+        "Sensitivity of a solved batch"): from the batch the solve read, its forces `grf_body` [n,12], the cotangent `grf_bar`
+        [n,12] and the `adjoint` [n,12] sensitivity_batch() returned for that grf_bar at the same act_tol, on the same stream
+        behind it.  `want`: "param_bar" [211], the cotangent SUMMED over the batch (the handle holds one parameter set), and / or
+        "param_bar_rows" [n,211], one row per robot; both in PARAM_LAYOUT's order (unpack_param_bar() names the pieces).  S_bar and
+        W_bar are entrywise and unsymmetrised: pair them with symmetric directions.  mass_bar and Ib_bar are the gradient of the
+        controller's use of mass and Ib, not of a plant's.  The sum is reduced without atomics in an order that depends on n alone:
+        bit-reproducible, and the same with and without the rows; two calls with "param_bar" on one controller must be ordered on
+        the device (one stream, or an event between them).  The gradient is the one on the active face, as sensitivity_batch()'s:
+        valid while the working set holds, one-sided for robots with bit 0 of its flags, NaN for robots with bit 1 - and then the sum
+        is NaN.  Nothing of `batch` is written.  Asynchronous on `stream`, no synchronisation.  For n = 0 nothing is launched and the
+        outputs stay as they were (new ones: zeros).  Returns the dict of device tensors; ValueError with the library's message for
+        a call it refuses."""
+        launch, res = self.plan_sensitivity_params(batch, grf_body, grf_bar, adjoint, want, act_tol, out, stream)
+        launch()
+        return res
+
+    def control_batch_autograd(self, batch, act_tol=1e-7, flags=None, params=None, **control_kwargs):
         """control_batch() with a gradient: returns (grf_body, status), grf_body carrying a grad_fn whenever any of Rwb, Rwb_d, x,
         xdot, w, x_d, xdot_d, w_d, feet in `batch` requires grad (quadruped_control_amd/autograd.py).  Forward is exactly
         control_batch(batch, **control_kwargs); backward is sensitivity_batch() and, if a rotation requires grad,
@@ -768,10 +818,14 @@ class BalanceController:
         The gradient is the one ON THE ACTIVE FACE at `act_tol`: valid while the working set holds - a loss that moves a robot
         across a face change sees a kink there -, one-sided for robots whose flags have bit 0 (a foot on both rows of an axis;
         failed robots among them, with gradient 0), NaN for robots with bit 1 (a bad pivot).  batch["joint_q"].requires_grad raises
-        ValueError: chain the leg Jacobian from feet_bar yourself."""
+        ValueError: chain the leg Jacobian from feet_bar yourself.
+        `params`: a float64 [211] tensor in PARAM_LAYOUT's order - parameter_tensor() makes the matching leaf.  Forward NEVER reads
+        its values: the solve uses the handle's own parameters.  When it requires grad, grf_body carries a grad_fn and backward adds
+        "adjoint" to what it asks of sensitivity_batch() and launches sensitivity_params_batch() in sum-only mode behind it;
+        params.grad receives the cotangent summed over the batch.  With params=None nothing changes."""
         from .autograd import control_batch_autograd
 
-        return control_batch_autograd(self, batch, act_tol, flags, **control_kwargs)
+        return control_batch_autograd(self, batch, act_tol, flags, params=params, **control_kwargs)
 
     def control_batch_host(self, batch, warm=None, want_active_set=False, want_iterations=False, want_torques=False):
         """n robots, numpy (host) arrays in and out; PCIe-inclusive convenience path."""
@@ -863,11 +917,35 @@ _CERTIFY_OUTPUTS = {"primal": ((), "float64"), "stationarity": ((), "float64"), 
 _SENSITIVITY_OUTPUTS = {"adjoint": ((12,), "float64"), "b_bar": ((6,), "float64"), "feet_bar": ((4, 3), "float64"),
                         **{k: ((3,), "float64") for k in ("x_bar", "xdot_bar", "w_bar", "x_d_bar", "xdot_d_bar", "w_d_bar")}, "flags": ((), "int32")}
 _SENSITIVITY_ROT_OUTPUTS = {k: ((m,), "float64") for k, m in (("Rwb_bar", 9), ("Rwb_d_bar", 9), ("Rwb_rot_bar", 3), ("Rwb_d_rot_bar", 3))}
+_SENSITIVITY_PARAM_OUTPUTS = {"param_bar_rows": ((_lib.PARAM_COUNT,), "float64")}
 _PLANT_ADJOINT_OUTPUTS = {k: ((m,), "float64") for k, m in (("Rwb_bar", 9), ("x_bar", 3), ("xdot_bar", 3), ("w_bar", 3), ("grf_bar", 12), ("foot_world_bar", 12))}
 _PLANT_COTANGENTS = {k: ((m,), "float64") for k, m in (("Rwb", 9), ("x", 3), ("xdot", 3), ("w", 3), ("feet", 12))}  # the step's outputs a cotangent may be given on
 # the batch a read-only call marshals (_readonly_batch): (name, trailing size, torch dtype name) - the state and the feet, and with the contact mask
 _STATE_FIELDS = tuple((k, m, "float64") for k, m in _IN_FIELDS + (("joint_q", 12),))
 _READONLY_FIELDS = _STATE_FIELDS + (("stance", 4, "uint8"), ("gait_phase", 4, "float64"), ("gait_duty", 1, "float64"))
+
+
+# a parameter cotangent: name -> (slice of the 211 values, shape), in the order of the double members of qc_params
+PARAM_LAYOUT = {}
+for _name, _shape in (("mu", ()), ("mass", ()), ("fzmin", ()), ("fzmax", ()), ("Ib", (3, 3)), ("S", (6, 6)), ("W", (12, 12)), ("kff", (6,)),
+                      ("kp_p", (3,)), ("kd_p", (3,)), ("kp_w", (3,)), ("kd_w", (3,))):
+    _at = PARAM_LAYOUT[next(reversed(PARAM_LAYOUT))][0].stop if PARAM_LAYOUT else 0
+    PARAM_LAYOUT[_name] = (slice(_at, _at + int(np.prod(_shape, dtype=int))), _shape)
+assert PARAM_LAYOUT["kd_w"][0].stop == _lib.PARAM_COUNT
+
+
+def unpack_param_bar(t):
+    """A parameter cotangent (or parameter_tensor()) [211] - a tensor (copied to the host: synchronises) or an array - as a dict of
+    named float64 arrays in the shapes of cheetah_params(): scalars as Python floats, Ib [3,3], S [6,6], W [12,12], kff [6], the
+    gains [3].  A [n,211] array of rows gives arrays with a leading n."""
+    a = np.asarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t, np.float64)
+    if a.shape[-1] != _lib.PARAM_COUNT:
+        raise ValueError(f"unpack_param_bar: the last axis must hold {_lib.PARAM_COUNT} values")
+    out = {}
+    for name, (sl, shape) in PARAM_LAYOUT.items():
+        v = a[..., sl].reshape(a.shape[:-1] + shape)
+        out[name] = float(v) if v.shape == () else v
+    return out
 
 
 def certify_summary(t):

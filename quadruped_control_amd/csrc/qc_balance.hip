@@ -1933,6 +1933,8 @@ static_assert(offsetof(qc::BalanceKernelArgs, Pg) == KernelArgList::at(0) && off
 static_assert(sizeof(qc::CertifySummary) == sizeof(qc_certify_summary) && offsetof(qc::CertifySummary, worst_primal) == offsetof(qc_certify_summary, worst_primal) &&
                   offsetof(qc::CertifySummary, arg_stationarity) == offsetof(qc_certify_summary, arg_stationarity),
               "qc::CertifySummary mirrors qc_certify_summary");
+static_assert(qc::PARAM_COUNT == QC_PARAM_COUNT && offsetof(qc_params, max_iter) == sizeof(double) * QC_PARAM_COUNT,
+              "QC_PARAM_COUNT is the number of doubles of qc_params, in its order");
 static_assert(sizeof(qc::CmdState) == sizeof(qc_commander_state) && offsetof(qc::CmdState, Vb) == offsetof(qc_commander_state, Vb) &&
                   offsetof(qc::CmdState, Rwb_d) == offsetof(qc_commander_state, Rwb_d) && offsetof(qc::CmdState, w_d) == offsetof(qc_commander_state, w_d),
               "qc::CmdState mirrors qc_commander_state");
@@ -1953,6 +1955,7 @@ struct qc_handle {
   bool has_last = false;
   hipStream_t stream = nullptr;
   qc::CertifySummary* certify_parts = nullptr;  // qc_certify_batch: one partial per workgroup of certify_kernel (CERTIFY_MAX_PARTIALS)
+  double* param_parts = nullptr;  // qc_sensitivity_param_batch: one partial of PARAM_COUNT doubles per workgroup (SENSITIVITY_PARAM_MAX_BLOCKS)
 };
 
 using qc::fail;
@@ -2153,6 +2156,13 @@ int qc_create_abi(const qc_params* p, int device, qc_handle** out, int abi_versi
     delete h;
     return fail(QC_ERR_HIP, "qc_create: could not allocate the certificate's partial buffer");
   }
+  // ... and qc_sensitivity_param_batch's (1.7 MB), for the same reason
+  if (hipMalloc((void**)&h->param_parts, sizeof(double) * qc::PARAM_COUNT * qc::SENSITIVITY_PARAM_MAX_BLOCKS) != hipSuccess) {
+    (void)hipFree(h->certify_parts);
+    (void)hipFree(h->d_params);
+    delete h;
+    return fail(QC_ERR_HIP, "qc_create: could not allocate the parameter cotangents' partial buffer");
+  }
   *out = h;
   return QC_OK;
 }
@@ -2187,6 +2197,7 @@ void qc_destroy(qc_handle* h) {
   (void)hipSetDevice(h->device);
   if (h->d_params) (void)hipFree(h->d_params);
   if (h->certify_parts) (void)hipFree(h->certify_parts);
+  if (h->param_parts) (void)hipFree(h->param_parts);
   if (h->stage) (void)hipFree(h->stage);
   if (h->pin) (void)hipHostFree(h->pin);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -2329,6 +2340,24 @@ int qc_sensitivity_rot_batch(qc_handle* h, size_t n, const qc_batch_in* in, cons
   qc::SensitivityRotArgs a{io->grf_body, io->grf_bar, io->b_bar, io->feet_bar, io->Rwb_bar, io->Rwb_d_bar, io->Rwb_rot_bar, io->Rwb_d_rot_bar};
   // (no contact mask: swing feet carry zeros)
   return launch_per_robot(qc::sensitivity_rot_kernel<true>, qc::sensitivity_rot_kernel<false>, qc::sensitivity_blocks(n), qc::SENSITIVITY_BLOCK, h, n, readonly_view(in, false), a, stream);
+}
+
+void qc_default_sensitivity_param(qc_sensitivity_param_io* io) {
+  if (!zeroed(io)) return;
+  io->act_tol = 1e-7;  // qc_default_sensitivity's
+}
+
+int qc_sensitivity_param_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_param_io* io, void* stream) {
+  if (const int rc = qc::check_sensitivity_param_args(h, n, in, io); rc != QC_OK || n == 0) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  qc::SensitivityParamArgs a{io->grf_body, io->grf_bar, io->adjoint, io->act_tol, io->param_bar_rows, io->param_bar ? h->param_parts : nullptr};
+  const unsigned blocks = qc::sensitivity_param_blocks(n);
+  if (const int rc = launch_per_robot(qc::sensitivity_param_kernel<true>, qc::sensitivity_param_kernel<false>, blocks, qc::SENSITIVITY_PARAM_BLOCK, h, n, readonly_view(in, true), a, stream); rc != QC_OK) return rc;
+  if (io->param_bar) {
+    qc::sensitivity_param_sum_kernel<<<dim3(1), dim3(qc::SENSITIVITY_PARAM_SUM_BLOCK), 0, (hipStream_t)stream>>>(h->param_parts, (int)blocks, io->param_bar);
+    QC_HIP(hipGetLastError());
+  }
+  return QC_OK;
 }
 
 // host-pointer variant.  Large batches: one device staging allocation, H2D copies, kernel, D2H copies, sync.

@@ -15,6 +15,7 @@
 #include "qc_certify.hpp"
 #include "qc_sensitivity.hpp"
 #include "qc_sensitivity_rot.hpp"
+#include "qc_sensitivity_params.hpp"
 
 namespace qc {
 
@@ -565,8 +566,8 @@ inline int leg_plant_constants(double mass, const double* Ib, const qc_leg_plant
   return QC_OK;
 }
 
-// ---------------------------------------------------------------- qc_certify_batch, qc_sensitivity_batch, qc_sensitivity_rot_batch
-// What the three calls that only read a solved batch refuse after check_io, in this order: `own`, the call's first refusal about its
+// ---------------------------------------------------------------- qc_certify_batch, qc_sensitivity_batch, qc_sensitivity_rot_batch, qc_sensitivity_param_batch
+// What the four calls that only read a solved batch refuse after check_io, in this order: `own`, the call's first refusal about its
 // scalars and outputs (nullptr: none); for n > 0 the call's input arrays (`inputs`), the state, feet or joint_q and the launch bound.
 inline int check_readonly_batch(const char* who, size_t n, const qc_batch_in* in, const char* own, bool inputs, const char* inputs_msg, int block) {
   const auto bad = [who](const char* what) { return fail(QC_ERR_INVALID, std::string(who) + what); };
@@ -616,5 +617,18 @@ inline int check_sensitivity_rot_args(const qc_handle* h, size_t n, const qc_bat
   const char* own = no_out ? ": no output requested (Rwb_bar, Rwb_d_bar, Rwb_rot_bar, Rwb_d_rot_bar are all NULL)" : nullptr;
   return check_readonly_batch(who, n, in, own, io->grf_body && io->grf_bar && io->b_bar && io->feet_bar, ": grf_body, grf_bar, b_bar and feet_bar are required", SENSITIVITY_BLOCK);
 }
+
+// The argument check of the parameter cotangents: what is wrong with the call itself (message prefix "qc_sensitivity_param_batch:").
+inline int check_sensitivity_param_args(const qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_param_io* io) {
+  const char* who = "qc_sensitivity_param_batch";
+  if (const int rc = check_io(who, h && in, io, "qc_sensitivity_param_io", "qc_default_sensitivity_param"); rc != QC_OK) return rc;
+  const char* own = nullptr;
+  if (!std::isfinite(io->act_tol) || !(io->act_tol >= 0.0)) own = ": act_tol must be finite and >= 0";
+  else if (!io->param_bar_rows && !io->param_bar) own = ": no output requested (param_bar_rows and param_bar are both NULL)";
+  return check_readonly_batch(who, n, in, own, io->grf_body && io->grf_bar && io->adjoint, ": grf_body, grf_bar and adjoint are required", SENSITIVITY_PARAM_BLOCK);
+}
+
+// workgroups of sensitivity_param_kernel for n robots: one wave each, capped at the handle's partial buffer
+inline unsigned sensitivity_param_blocks(size_t n) { return capped_blocks(n, SENSITIVITY_PARAM_BLOCK, SENSITIVITY_PARAM_MAX_BLOCKS); }
 
 }  // namespace qc

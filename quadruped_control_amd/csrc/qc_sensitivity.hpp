@@ -32,8 +32,9 @@
 //                                             (kff[3] al_bar[0], kff[4] al_bar[1], kff[5] al_bar[1]) + (Iw w_d) x b_bar_ang +
 //                                             Iw^T (b_bar_ang x w_d)
 // NOT produced: the cotangents of Rwb and Rwb_d (qc_sensitivity_rot.hpp makes them from b_bar and feet_bar, in a kernel of its own); the
-// cotangents of mu, fzmin, fzmax and the weights; weak activity - a row whose multiplier is about 0 is on the face like any other
-// active row (the caller has the certificate's lambda for that).  Commander mode is out of scope, as for the certificate.
+// weak activity - a row whose multiplier is about 0 is on the face like any other active row (the caller has the certificate's lambda
+// for that).  The cotangents of the handle's parameters (mu, fzmin, fzmax, the weights, the gains, mass, Ib) come from
+// qc_sensitivity_params.hpp, from the adjoint written here, in a kernel of its own.  Commander mode is out of scope, as for the certificate.
 //
 // The reduced solve is branch-free: with e_j = 1 for a coordinate of y and 0 for a pinned or tied one, the fixed 12x12 system
 // M = Z^T H Z (rows and columns with e = 1) + diag(1 - e), rhs e o Z^T f_bar - the pinned coordinates are identity rows selected
