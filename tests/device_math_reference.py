@@ -668,6 +668,33 @@ def wrench_ld(P, state, feet_or_q, kin=None, sic=True):
         return dict(b=_unpack(b, (6,)), r=_unpack(r, (4, 3)), angle=np.asarray(angle, np.float64))
 
 
+def _wrench_params(rng):
+    """Test parameters for wrench_mp / wrench_ld with every quirk visible: kff[3..5] all different and non-zero, a full symmetric
+    positive definite Ib, non-uniform gains"""
+    import quadruped_control_amd as q
+
+    P = q.cheetah_params(0.6)
+    A = rng.normal(size=(3, 3))
+    P["Ib"] = np.diag([0.011253, 0.036203, 0.042673]) + 0.004 * (A @ A.T) + 0.001 * (A + A.T) * np.array([[0, 1, 1], [1, 0, 1], [1, 1, 0]])
+    P["kff"] = np.array([0.3, -0.2, 0.15, 0.7, -1.1, 1.9])
+    P["kp_p"], P["kd_p"] = np.array([100.0, 80.0, 130.0]), np.array([50.0, 35.0, 61.0])
+    P["kp_w"], P["kd_w"] = np.array([5000.0, 4200.0, 3100.0]), np.array([500.0, 410.0, 290.0])
+    return P
+
+
+def _wrench_states(rng, n, max_angle=2.5):
+    """n random test states for them: any Rwb, Rwb_d up to max_angle away from it"""
+    from scipy.spatial.transform import Rotation
+
+    Rw = Rotation.random(n, random_state=int(rng.integers(1 << 30)))
+    ax = rng.normal(size=(n, 3))
+    ax /= np.linalg.norm(ax, axis=1, keepdims=True)
+    Rd = Rotation.from_rotvec(ax * rng.uniform(0, max_angle, (n, 1))) * Rw
+    v = lambda s: rng.normal(size=(n, 3)) * s
+    return dict(Rwb=Rw.as_matrix().reshape(n, 9), Rwb_d=Rd.as_matrix().reshape(n, 9), x=v(1.0), x_d=v(1.0), xdot=v(1.0), xdot_d=v(1.0), w=v(2.0),
+                w_d=v(2.0), feet=rng.uniform(-0.4, 0.4, (n, 12)))
+
+
 def _foothold_core(hipv, k_, t_stance, R, x, xdot, w, xdot_d, foot, half, g, foot_is_lever=False):
     """foot_planner.cpp:76-104: p_thigh = Rwb hip + x; tang = w x (Rwb foot); foothold = p_thigh + (t_stance / 2) xdot +
     k (xdot - xdot_d) + (t_stance / 2) tang + 0.5 sqrt(x(2) / g) xdot, g = 9.81; foothold(2) = 0.

@@ -1,8 +1,30 @@
-"""What the GPU tests of the plant steps share (a plain module, no fixtures): pools tiled to a batch size, device copies with
-sentinel rows behind the batch, and the comparison of an output against (value, bar) references."""
+"""What the GPU tests share (a plain module; test modules import its fixtures by name, `from tests.gpu_arrays import q  # noqa: F401`):
+the package fixture `q`, the plant steps' default-parameter handle, pools tiled to a batch size, device copies with sentinel rows
+behind the batch, and the comparison of an output against (value, bar) references."""
 import numpy as np
+import pytest
 
 SENTINEL = -7777.25
+
+
+@pytest.fixture(scope="module")
+def q(built):
+    import quadruped_control_amd as q
+
+    return q
+
+
+@pytest.fixture(scope="module")
+def P(q):
+    return q.cheetah_params()
+
+
+@pytest.fixture(scope="module")
+def ctl(q, P):
+    """one handle at cheetah_params(): the plant family's (the solved-batch tests build theirs at mu = 0.6)"""
+    c = q.BalanceController.from_params(P, device=0)
+    yield c
+    c.close()
 
 
 def _sentinel(dtype):

@@ -196,3 +196,9 @@ def distance(values, mp_values):
     """|double - 50-digit value| per entry, as floats"""
     with mp.workdps(DMR.DPS):
         return np.array([float(abs(DMR.mpf(float(a)) - m)) for a, m in zip(np.asarray(values, np.float64).reshape(-1), mp_values)])
+
+
+def magnitude(mp_values):
+    """the largest |entry| of a 50-digit result, as a float"""
+    with mp.workdps(DMR.DPS):
+        return max(float(abs(m)) for m in mp_values)

@@ -24,6 +24,7 @@ import numpy as np
 
 from tests import device_math_reference as DMR
 from tests import kkt_certificate_restatement as KR
+from tests.kkt_certificate_restatement import distance  # noqa: F401 - the one definition, under this module's name too
 from tests import sensitivity_rotation_restatement as RR
 
 COUNT = 211
@@ -197,8 +198,3 @@ def param_cotangents_mp(P, b, grf_body, grf_bar, adjoint, i, active, kin=None):
         e = np.array(RR.log_jacobian_mp(Re)[0], dtype=object)
         row = _row(_params(P, conv=lift), st, p, arr(grf_body[i], (4, 3)), arr(grf_bar[i], (4, 3)), arr(adjoint[i], (12,)), active, e)
         return list(row)
-
-
-def distance(values, mp_values):
-    """|double - 50-digit value| per entry, as floats"""
-    return KR.distance(values, mp_values)

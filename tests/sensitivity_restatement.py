@@ -24,6 +24,7 @@ import numpy as np
 
 from tests import device_math_reference as DMR
 from tests import kkt_certificate_restatement as KR
+from tests.kkt_certificate_restatement import distance, magnitude  # noqa: F401 - the one definition of each, under this module's name too
 from tests.kkt_batch import wrench_data
 
 OUTPUTS = ("adjoint", "b_bar", "feet_bar", "x_bar", "xdot_bar", "w_bar", "x_d_bar", "xdot_d_bar", "w_d_bar")
@@ -184,14 +185,3 @@ def sensitivity_mp(P, b, grf_body, grf_bar, i, active, kin=None):
         out = dict(adjoint=zl, b_bar=tl(bb), feet_bar=fbar_body, r_bar=rbar)
         out.update({k: list(val) for k, val in pb.items()})
         return out
-
-
-def distance(values, mp_values):
-    """|double - 50-digit value| per entry, as floats"""
-    return KR.distance(values, mp_values)
-
-
-def magnitude(mp_values):
-    """the largest |entry| of a 50-digit result, as a float"""
-    with mp.workdps(DMR.DPS):
-        return max(float(abs(m)) for m in mp_values)

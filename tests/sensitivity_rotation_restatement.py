@@ -25,6 +25,7 @@ import numpy as np
 
 from tests import device_math_reference as DMR
 from tests import kkt_certificate_restatement as KR
+from tests.kkt_certificate_restatement import distance, magnitude  # noqa: F401 - the one definition of each, under this module's name too
 
 OUTPUTS = ("Rwb_bar", "Rwb_d_bar", "Rwb_rot_bar", "Rwb_d_rot_bar")
 BRANCH_NAMES = {-1: "trace", 0: "pivot 0", 1: "pivot 1", 2: "pivot 2"}
@@ -238,15 +239,6 @@ def rotation_cotangents_mp(P, b, grf_body, grf_bar, b_bar, feet_bar, i, kin=None
         flat = lambda M: [M[r, c] for r in range(M.rows) for c in range(M.cols)]
         ax = lambda M: [M[2, 1] - M[1, 2], M[0, 2] - M[2, 0], M[1, 0] - M[0, 1]]
         return dict(Rwb_bar=flat(Rb), Rwb_d_bar=flat(Rdb), Rwb_rot_bar=ax(Rb * R.T), Rwb_d_rot_bar=ax(Rdb * Rd.T), case=case)
-
-
-def distance(values, mp_values):
-    return KR.distance(values, mp_values)
-
-
-def magnitude(mp_values):
-    with mp.workdps(DMR.DPS):
-        return max(float(abs(m)) for m in mp_values)
 
 
 # ------------------------------------------------------------------ the branch sweep

@@ -31,8 +31,7 @@ def _twists(rng, n, cmd_dt):
 
 def run_campaign(runs=40, ticks=30, budget_s=None, min_runs=1):
     import torch
-    from tests.test_oracle_cpu import _planned_batch
-    from tests.test_gpu_commander import _reference_tick
+    from tests.commander_support import _planned_batch, _reference_tick
 
     rng = np.random.default_rng(int(os.environ.get("QC_FUZZ_SEED", 515151)))
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()

@@ -17,26 +17,20 @@ test_commander_cpu pins them and shows that a plain double evaluation of the sam
   2 EPS absolute plus the angle's own 4 roundings through |d sin| <= |d angle| - condition 1 + angle, count 4; 1 - cos 5;
   (1 - cos) a_i a_j 19; Rbb' 20; cy = R00 / h 3 (h^2 2, h 2, the division 1); Rwb_d rows 0 and 1: 25, row 2: 20;
   tbb' = (Rbb' v) dt 24; x_d = x + (cy t0 - sy t1): 30; almost-zero angle: Rwb_d 5, x_d 7; xdot_d = R^T (v - x x w): 6; w_d: 3.
-Every lane layout of test_gpu_commander.CASES runs the same robots and must leave the same bits."""
+Every lane layout of commander_support.CASES runs the same robots and must leave the same bits."""
 import functools
 
 import numpy as np
 import pytest
 
 from tests import device_math_reference as R
-from tests.test_gpu_commander import CASES, DESIRED, MEAS, _base, _check_instantiation, _controller, _state_host, _to_dev
+from tests.commander_support import CASES, DESIRED, MEAS, _base, _check_instantiation, _controller, _state_host, _to_dev
+from tests.gpu_arrays import q  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 EPS = R.EPS
 FIELDS = ("Rwb_d", "x_d", "xdot_d", "w_d")
 QC_SOLVED, QC_NOT_PD = 0, 3
-
-
-@pytest.fixture(scope="module")
-def q(built):
-    import quadruped_control_amd as q
-
-    return q
 
 
 @functools.lru_cache(maxsize=None)

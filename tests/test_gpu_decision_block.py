@@ -26,19 +26,14 @@ include walks with that release and walks that, after the flip, accept a second 
 import numpy as np
 import pytest
 
+from tests.gpu_arrays import q  # noqa: F401
+
 gpu = pytest.mark.gpu  # (the CPU-side proof of the pinned branches runs without one)
 
 RTOL = 1e-6   # of max(1, max|GRF|) per robot, against the oracle (the suite's bar)
 XTOL = 1e-8   # across widths / strategies (the existing cross-width bar)
 SIZES = (1, 3, 4, 5, 17)
 PATTERNS = tuple(range(1, 16))
-
-
-@pytest.fixture(scope="module")
-def q(built):
-    import quadruped_control_amd as q
-
-    return q
 
 
 _cache = {}

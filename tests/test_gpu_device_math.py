@@ -532,12 +532,11 @@ def test_leg_swing_torque(P):
 
 # ---------------------------------------------------------------- wrench_from_state, plan_foothold
 def _wrench_setup(P, seed):
-    """The probe's constants with every quirk of the wrench law visible (tests/test_device_math_cpu._wrench_params: kff[3..5] all
+    """The probe's constants with every quirk of the wrench law visible (device_math_reference._wrench_params: kff[3..5] all
     different and non-zero, a full non-diagonal Ib, non-uniform gains) and a planner; returns (params dict, restore())."""
-    from tests.test_device_math_cpu import _wrench_params
 
     rng = np.random.default_rng(seed)
-    W = _wrench_params(rng)
+    W = R._wrench_params(rng)
     W["planner_hip"] = (R.HIP + rng.uniform(-0.01, 0.01, (4, 3))).reshape(12)
     W["planner_k"] = 0.07
     _, basis = R.sextic_basis_mp()
@@ -572,13 +571,12 @@ def test_wrench_from_state(P):
     map to the <= 3 roundings of each entry of Re = Rwb_d Rwb^T, measured by perturbing Re in the reference's precision).  The
     parameters make the `sic` index (kff5 w_d2 on row 1), a transposed Iw and swapped gains visible (test_device_math_cpu shows each
     of them far outside these bars).  Rotation errors stay below pi - 1e-3; beyond it test_angle_axis_total's domain applies."""
-    from tests.test_device_math_cpu import _wrench_states
 
     W, restore = _wrench_setup(P, 31)
     try:
         rng = np.random.default_rng(32)
         n = 100_000
-        b = _wrench_states(rng, n, max_angle=np.pi - 1e-3)
+        b = R._wrench_states(rng, n, max_angle=np.pi - 1e-3)
         feet = b.pop("feet")
         qj = np.stack([rng.uniform(-0.6, 0.6, (n, 4)), rng.uniform(-0.2, 1.4, (n, 4)), rng.uniform(-2.4, -0.3, (n, 4))], 2).reshape(n, 12)
         sample = rng.choice(n, 2000, replace=False)
@@ -618,7 +616,6 @@ def test_wrench_finiteness_value(P):
     """The value wrench_from_state returns is exactly 0.0 for finite inputs - up to 1e150 in every input at once - and non-zero (or
     NaN) as soon as ONE entry of an input that reaches b, r or R is NaN or Inf: each of Rwb, Rwb_d, x, x_d, xdot, xdot_d, w, w_d and the
     feet / joint angles in turn, both variants."""
-    from tests.test_device_math_cpu import _wrench_states
 
     W, restore = _wrench_setup(P, 33)
     try:
@@ -626,7 +623,7 @@ def test_wrench_finiteness_value(P):
         names = ("Rwb", "Rwb_d", "x", "x_d", "xdot", "xdot_d", "w", "w_d", "fp")
         rows = [(name, k, bad) for name in names for k in ((0, 4, 8) if name.startswith("Rwb") else (0, 2, 7, 11) if name == "fp" else (0, 1, 2)) for bad in (np.nan, np.inf, -np.inf)]
         m = len(rows)
-        b = _wrench_states(rng, m, max_angle=2.0)
+        b = R._wrench_states(rng, m, max_angle=2.0)
         feet = b.pop("feet")
         qj = np.stack([rng.uniform(-0.6, 0.6, (m, 4)), rng.uniform(-0.2, 1.4, (m, 4)), rng.uniform(-2.4, -0.3, (m, 4))], 2).reshape(m, 12)
         for kin, fp in ((False, feet), (True, qj)):

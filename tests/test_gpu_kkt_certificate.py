@@ -23,91 +23,17 @@ import pytest
 from tests import device_math_reference as DMR
 from tests import kkt_certificate_restatement as KR
 from tests.kkt_batch import wrench_data
+from tests.solved_batch_support import SENTINEL, STATE_KEYS, assert_raw_refusals, batch_in, ctls, inputs, params, q, run  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 SIZES = (1, 63, 64, 65, 257, 1000)
 U = 2.0 ** -53
-SENTINEL = -7777.25
-STATE_KEYS = ("Rwb", "Rwb_d", "x", "xdot", "w", "x_d", "xdot_d", "w_d")
 WANT_ALL = ("primal", "stationarity", "lambda", "grad", "active", "flags")
 
 
-@pytest.fixture(scope="module")
-def q(built):
-    import quadruped_control_amd as q
-
-    return q
-
-
-def _params(q, kind):
-    P = q.cheetah_params(mu=0.6)
-    if kind == "uniform":
-        return P
-    rng = np.random.default_rng(5)
-    if kind == "per-axis":
-        return dict(P, W=np.diag(1e-5 * rng.uniform(0.5, 2.0, 12)))
-    M = rng.normal(size=(12, 12))
-    N = rng.normal(size=(6, 6))
-    return dict(P, W=1e-5 * (np.eye(12) + 0.05 * (M @ M.T) / 12.0), S=np.asarray(P["S"]) + 0.2 * (N @ N.T) / 6.0)  # dense S and W
-
-
-@pytest.fixture(scope="module")
-def ctls(q):
-    out = {k: q.BalanceController.from_params(_params(q, k), device=0) for k in ("uniform", "per-axis", "dense")}
-    assert [c.kernel_name for c in out.values()] == ["diagW-6x6-uniform", "diagW-6x6", "dense-12x12"]
-    yield out
-    for c in out.values():
-        c.close()
-
-
-@functools.lru_cache(maxsize=None)
-def _inputs(n, source):
-    """(batch, world forces): contact pattern i % 16; even robots level (Rwb = I).  source: 'feet' with stance bytes, 'joint_q' with
-    gait_phase (0.3 stance / 0.9 swing against the handle's duty 0.816), 'duty' = joint_q, gait_phase 0.3 / 0.7 and gait_duty 0.5."""
-    import quadruped_control_amd as q
-    from quadruped_control_amd import workloads
-
-    P = q.cheetah_params(mu=0.6)
-    b = dict(workloads.config3(n=n))
-    b["Rwb"] = b["Rwb"].copy()
-    b["Rwb"][0::2] = np.eye(3).reshape(9)
-    st = ((np.arange(n)[:, None] >> np.arange(4)[None, :]) & 1).astype(np.uint8)
-    if source == "feet":
-        b["stance"] = st
-    else:
-        b = workloads.with_joint_angles(b)
-        b.pop("feet", None)
-        b.pop("stance", None)
-        b["gait_phase"] = np.where(st != 0, 0.3, 0.9 if source == "joint_q" else 0.7)
-        if source == "duty":
-            b["gait_duty"] = np.full(n, 0.5)
-    rng = np.random.default_rng(1000 + n)
-    mu, fzmin, fzmax = P["mu"], P["fzmin"], P["fzmax"]
-    level = (np.arange(n) % 2 == 0)[:, None]
-    pick = rng.integers(0, 3, (n, 4))
-    fz = np.where(level & (pick == 0), fzmin, np.where(level & (pick == 1), fzmax, rng.uniform(fzmin + 1.0, fzmax - 1.0, (n, 4))))
-    fw = np.zeros((n, 4, 3))
-    fw[..., 2] = fz
-    for k in range(2):
-        side = rng.integers(-1, 2, (n, 4))
-        inside = rng.uniform(-0.9, 0.9, (n, 4)) * (mu * fz)
-        fw[..., k] = np.where(level & (side == 1), mu * fz, np.where(level & (side == -1), -(mu * fz), inside))
-    fw[st == 0] = 0.0
-    R = b["Rwb"].reshape(n, 3, 3)
-    grf = -np.einsum("nji,nkj->nki", R, fw).reshape(n, 12)  # grf_body = -Rwb^T f_w
-    grf[0::2] = -fw[0::2].reshape(-1, 12)  # exactly, where Rwb = I
-    grf += 0.0  # (no -0.0)
-    return {k: np.ascontiguousarray(v) for k, v in b.items()}, np.ascontiguousarray(grf)
-
-
 def _certify(q, ctl, b, grf, want=WANT_ALL, summary=True, **kw):
-    import torch
-
-    dev = q.to_device(b)
-    g = torch.from_numpy(grf).cuda()
-    out = ctl.certify_batch(dev, g, want=want, summary=summary, **kw)
-    torch.cuda.synchronize()
-    res = {k: v.cpu().numpy() for k, v in out.items() if k != "summary"}
+    res, out = run(q, ctl.certify_batch, b, grf, want=want, summary=summary, **kw)
+    res.pop("summary", None)
     if summary:
         from quadruped_control_amd.balance_controller import certify_summary
 
@@ -153,8 +79,8 @@ def test_sizes_contact_patterns_and_inputs(q, ctls, n, source):
     all outputs against the restatement, nothing written past the end (each array is allocated with a sentinel row behind it)."""
     import torch
 
-    P = _params(q, "uniform")
-    b, grf = _inputs(n, source)
+    P = params(q, "uniform")
+    b, grf = inputs(n, source)
     ref = KR.certificate(P, b, grf, default_duty=KR.DEFAULT_DUTY)
     dev = q.to_device(b)
     shapes = {"primal": ((n + 1,), torch.float64), "stationarity": ((n + 1,), torch.float64), "lambda": ((n + 1, 4, 3), torch.float64),
@@ -177,8 +103,8 @@ def test_sizes_contact_patterns_and_inputs(q, ctls, n, source):
 @pytest.mark.parametrize("form", ["uniform", "per-axis", "dense"])
 def test_every_formulation_uses_the_full_weights(q, ctls, form):
     """The certificate reads the handle's full S and W whatever form the solver runs: uniform W, per-axis W, dense S and W."""
-    P = _params(q, form)
-    b, grf = _inputs(257, "feet")
+    P = params(q, form)
+    b, grf = inputs(257, "feet")
     got = _certify(q, ctls[form], b, grf)
     _check_against_restatement(P, b, grf, got, KR.certificate(P, b, grf))
 
@@ -189,9 +115,9 @@ def test_non_optimal_points_against_50_digits(q, ctls, source):
     """Feasible but wrong forces (module docstring): the integer outputs equal the restatement's exactly on all 257 robots, and on
     the first 32 the device is at most 8 x as far from the 50-digit value as the numpy restatement is (floor 16 * 2^-53 * sum of
     |terms|).  Measured worst ratios device distance / bar: profiles/kkt_certificate.md."""
-    P = _params(q, "dense")
+    P = params(q, "dense")
     n = 257
-    b, grf = _inputs(n, source)
+    b, grf = inputs(n, source)
     ref = KR.certificate(P, b, grf)
     got = _certify(q, ctls["dense"], b, grf)
     assert ref["summary"]["n_fail"] >= 200 and ref["summary"]["n_nonfinite"] == 0  # (the robots without a stance foot carry no force: they pass)
@@ -241,7 +167,7 @@ def test_solved_points_pass_the_projects_bars(q, ctls):
     ok = status == 0
     assert ok.sum() >= 990
     assert np.all(got["primal"][ok] < 1e-7) and np.all(got["stationarity"][ok] < 1e-8) and np.all(got["flags"][ok] == 0)
-    ref = KR.certificate(_params(q, "uniform"), b, grf)
+    ref = KR.certificate(params(q, "uniform"), b, grf)
     assert got["summary"]["n_fail"] == ref["summary"]["n_fail"] == int((~ok & ((ref["primal"] > 1e-7) | (ref["stationarity"] > 1e-8))).sum())
 
 
@@ -296,7 +222,7 @@ def test_perturbing_one_force_fails_exactly_that_robot(q, ctls):
 def test_summary_is_the_reduction_of_the_per_robot_arrays(q, ctls):
     """Bit-equal to reducing the device's own per-robot arrays on the host; identical with every per-robot pointer NULL; one NaN
     state sets n_nonfinite = 1 and leaves worst_* finite.  n = 1000: sixteen workgroups, the last one with a tail."""
-    b, grf = _inputs(1000, "feet")
+    b, grf = inputs(1000, "feet")
     got = _certify(q, ctls["uniform"], b, grf)
     host = KR.summarize(got["primal"], got["stationarity"], (got["flags"] & 1) != 0)
     assert got["summary"] == host
@@ -317,7 +243,7 @@ def test_inputs_are_left_alone_and_the_result_repeats(q, ctls):
     certificate advances no clock - and two calls give identical outputs."""
     import torch
 
-    b, grf = _inputs(257, "joint_q")
+    b, grf = inputs(257, "joint_q")
     b = dict(b, gait_dt=np.full(257, 1.0 / 300.0), joint_qdot=np.zeros((257, 12)))
     dev = q.to_device(b)
     g = torch.from_numpy(grf).cuda()
@@ -331,7 +257,7 @@ def test_inputs_are_left_alone_and_the_result_repeats(q, ctls):
     assert torch.equal(g.view(torch.uint8), g0.view(torch.uint8))
     for k in one:
         assert torch.equal(one[k].view(torch.uint8), two[k].view(torch.uint8)), k
-    ref = KR.certificate(_params(q, "uniform"), {k: v for k, v in b.items() if k not in ("gait_dt", "joint_qdot")}, grf)
+    ref = KR.certificate(params(q, "uniform"), {k: v for k, v in b.items() if k not in ("gait_dt", "joint_qdot")}, grf)
     assert np.array_equal(two["active"].cpu().numpy(), ref["active"])
 
 
@@ -401,7 +327,7 @@ def test_refusals_raise_and_launch_nothing(q, ctls):
 
     ctl = ctls["uniform"]
     n = 65
-    b, grf = _inputs(n, "feet")
+    b, grf = inputs(n, "feet")
     dev = q.to_device(b)
     g = torch.from_numpy(grf).cuda()
     out = {"primal": torch.full((n,), SENTINEL, dtype=torch.float64, device="cuda"), "summary": torch.full((56,), 77, dtype=torch.uint8, device="cuda")}
@@ -423,19 +349,6 @@ def test_refusals_raise_and_launch_nothing(q, ctls):
     io = _lib.QcCertifyIo()
     lib.qc_default_certify(ctypes.byref(io))
     io.grf_body, io.primal, io.summary = g.data_ptr(), out["primal"].data_ptr(), out["summary"].data_ptr()
-    bi = _lib.QcBatchIn()
-    for k in STATE_KEYS + ("feet", "stance"):
-        setattr(bi, k, dev[k].data_ptr())
-    calls = [(None, n, ctypes.byref(bi), ctypes.byref(io)), (ctl._h, n, None, ctypes.byref(io)), (ctl._h, n, ctypes.byref(bi), None),
-             (ctl._h, 0xFFFFFF * 64 + 1, ctypes.byref(bi), ctypes.byref(io))]
-    for h, m, pin, pio in calls:
-        assert lib.qc_certify_batch(h, m, pin, pio, None) == -1 and _lib.last_error().startswith("qc_certify_batch:")
-    io.struct_size = 88
-    assert lib.qc_certify_batch(ctl._h, n, ctypes.byref(bi), ctypes.byref(io), None) == -1 and _lib.last_error().startswith("qc_certify_batch: qc_certify_io.struct_size")
-    io.struct_size = 96
-    assert lib.qc_certify_batch(ctl._h, 0, ctypes.byref(bi), ctypes.byref(io), None) == 0  # n == 0: QC_OK, nothing launched
-    torch.cuda.synchronize()
-    assert bool((out["primal"] == SENTINEL).all()) and bool((out["summary"] == 77).all())
-    assert lib.qc_certify_batch(ctl._h, n, ctypes.byref(bi), ctypes.byref(io), None) == 0  # and the same structs, valid, do launch
-    torch.cuda.synchronize()
-    assert bool((out["primal"] != SENTINEL).all()) and not bool((out["summary"] == 77).all())
+    bi = batch_in(dev, STATE_KEYS + ("feet", "stance"))
+    assert_raw_refusals(lib.qc_certify_batch, lambda: (ctl._h, n, bi, io), "qc_certify_io", 96, 88,
+                        [(out["primal"], SENTINEL, True), (out["summary"], 77, False)])

@@ -12,7 +12,8 @@ import pytest
 
 from tests import leg_plant_restatement as LR
 from tests import plant_restatement as PR
-from tests.gpu_arrays import SENTINEL, _device_arrays, _sentinel, _tile, _worst_over_bar
+from tests.gpu_arrays import SENTINEL, P, _device_arrays, _sentinel, _tile, _worst_over_bar, ctl, q  # noqa: F401
+from tests.solved_batch_support import assert_raw_refusals
 
 pytestmark = pytest.mark.gpu
 EPS = LR.EPS
@@ -22,25 +23,6 @@ POOL = 48
 DT = 1.0 / 300.0
 INERTIA = (0.02, 0.015, 0.01)
 MODES = ("stance", "phase", "duty", "cmd")
-
-
-@pytest.fixture(scope="module")
-def q(built):
-    import quadruped_control_amd as q
-
-    return q
-
-
-@pytest.fixture(scope="module")
-def P(q):
-    return q.cheetah_params()
-
-
-@pytest.fixture(scope="module")
-def ctl(q, P):
-    c = q.BalanceController.from_params(P, device=0)
-    yield c
-    c.close()
 
 
 @functools.lru_cache(maxsize=None)
@@ -266,16 +248,18 @@ def test_argument_errors_launch_nothing(q, ctl):
             setattr(t, k, v)
         return t
 
-    def refused(handle, t, what):
-        rc = lib.qc_leg_plant_step_batch(handle, n, ctypes.byref(t) if t is not None else None, stream)
-        assert rc == -1 and _lib.last_error().startswith("qc_leg_plant_step_batch:"), (what, rc, _lib.last_error())
-        torch.cuda.synchronize()
+    def untouched(what):
         for k, v in d.items():
             assert torch.equal(v[0], before[k]), (what, k)
 
+    def refused(handle, t, what):
+        rc = lib.qc_leg_plant_step_batch(handle, n, ctypes.byref(t), stream)
+        assert rc == -1 and _lib.last_error().startswith("qc_leg_plant_step_batch:"), (what, rc, _lib.last_error())
+        torch.cuda.synchronize()
+        untouched(what)
+
     for k in STATE + ("joint_tau",):
         refused(ctl._h, io(**{k: None}), f"{k} = NULL")
-    refused(ctl._h, io(struct_size=72), "qc_plant_io's struct_size")
     refused(ctl._h, io(struct_size=0), "struct_size not set")
     for dt in (0.0, -1.0 / 300.0, float("nan"), float("inf")):
         refused(ctl._h, io(dt=dt), f"dt = {dt}")
@@ -284,25 +268,24 @@ def test_argument_errors_launch_nothing(q, ctl):
             t = io()
             t.leg_inertia[k] = v
             refused(ctl._h, t, f"leg_inertia[{k}] = {v}")
-    refused(None, io(), "no handle")
-    refused(ctl._h, None, "no io")
     P = dict(q.cheetah_params())
     P["Ib"] = np.diag([0.011253, -0.036203, 0.042673])
     odd = q.BalanceController.from_params(P, device=0)
     refused(odd._h, io(), "Ib not positive definite")
     assert "positive definite" in _lib.last_error()
     odd.close()
-    assert lib.qc_leg_plant_step_batch(ctl._h, 0, ctypes.byref(io()), stream) == 0
     with pytest.raises(ValueError, match="joint_tau"):
         ctl.leg_plant_step({k: d[k][1] for k in STATE}, d["joint_tau"][1][:, :6].contiguous(), DT, INERTIA)
     with pytest.raises(RuntimeError, match="qc_leg_plant_step_batch: leg_inertia"):
         ctl.leg_plant_step({k: d[k][1] for k in STATE}, d["joint_tau"][1], DT, 0.0)
-    torch.cuda.synchronize()
-    for k, v in d.items():
-        assert torch.equal(v[0], before[k]), k
-    assert lib.qc_leg_plant_step_batch(ctl._h, n, ctypes.byref(io()), stream) == 0
-    torch.cuda.synchronize()
-    assert not torch.equal(d["x"][0][:n], before["x"][:n]) and (d["flags"][0][:n] == 0).all() and (d["x"][0][n:] == SENTINEL).all()
+
+    def stepped():
+        assert not torch.equal(d["x"][0][:n], before["x"][:n]) and (d["flags"][0][:n] == 0).all() and (d["x"][0][n:] == SENTINEL).all(), "after the valid call"
+
+    # no handle, no io, n beyond one launch, qc_plant_io's struct_size; n = 0 launches nothing; the same call, valid, does step
+    assert_raw_refusals(lib.qc_leg_plant_step_batch, lambda: (ctl._h, n, None, io()), "qc_leg_plant_io", ctypes.sizeof(_lib.QcLegPlantIo), 72,
+                        [(d["foot_world"][1], SENTINEL, True), (d["flags"][1], -77, True)], beyond=0xFFFFFF * 256 + 1, stream=stream,
+                        untouched=untouched, launched=stepped)
 
 
 # ------------------------------------------------------------------ 6. closed loop: standing
@@ -499,7 +482,7 @@ def test_closed_loop_commander_mode(q):
     phase offsets, 300 steps on the device without a host in the loop, 5 robots (the smallest batch that still differs robot by
     robot; the batch sizes are test 1's business, and every robot-step here gets a 50-digit plant step).  Afterwards every step
     is re-synchronised from the recorded device state BEFORE it:
-      * the tick: tests/test_gpu_commander.py's reference tick (commander restatement + C oracle) on that state, compared by that
+      * the tick: tests/commander_support.py's reference tick (commander restatement + C oracle) on that state, compared by that
         file's _compare_tick - flags and phases exactly, desired state 1e-12, swing plans 1e-9, forces 1e-6 relative, torques 2e-5;
       * the plant: the 50-digit step on that state under the DEVICE's joint_tau and the restatement's contact mask, against the
         recorded next state within the one-step bars of leg_plant_restatement (the stance-IK bars measured over this run's own
@@ -515,7 +498,7 @@ def test_closed_loop_commander_mode(q):
     with a fresh 0.2 m/s forward command."""
     from oracle import c_oracle as O
     from tests import commander_restatement as CR
-    from tests import test_gpu_commander as TC
+    from tests import commander_support as TC
 
     n, steps = 5, 300
     P = q.cheetah_params()

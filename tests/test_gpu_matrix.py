@@ -12,6 +12,8 @@ Reference semantics held: balance_controller.cpp:152-153 (QP data), 274-330 (con
 import numpy as np
 import pytest
 
+from tests.gpu_arrays import q  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-6  # of max|GRF| per robot; north_star's bar is 1e-4
@@ -28,13 +30,6 @@ CASES += [("uniform", 4, 2, dict(group=4, one_fill=1, race=0), 8192),
           ("dense", 1, 1, dict(group=1, one_fill=1), 8200),  # ragged; the Hessian planes are the workgroup's only LDS (output stock aliased)
           ("dense", 4, 1, dict(group=4, race=0), 8192)]
 IDS = [f"{f}-G{g}-mode{m}" for f, g, m, _, _ in CASES]
-
-
-@pytest.fixture(scope="module")
-def q(built):
-    import quadruped_control_amd as q
-
-    return q
 
 
 _cache = {}

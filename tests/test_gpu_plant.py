@@ -16,7 +16,8 @@ import numpy as np
 import pytest
 
 from tests import plant_restatement as PR
-from tests.gpu_arrays import SENTINEL, _device_arrays, _tile, _worst_over_bar
+from tests.gpu_arrays import SENTINEL, P, _device_arrays, _tile, _worst_over_bar, ctl, q  # noqa: F401
+from tests.solved_batch_support import assert_raw_refusals
 
 pytestmark = pytest.mark.gpu
 EPS = PR.EPS
@@ -24,25 +25,6 @@ SIZES = (1, 63, 64, 65, 257, 4097)
 STATE = ("Rwb", "x", "xdot", "w")
 POOL = 257
 FEET_XY = np.array([[-0.196, 0.127], [0.196, 0.127], [-0.196, -0.127], [0.196, -0.127]])
-
-
-@pytest.fixture(scope="module")
-def q(built):
-    import quadruped_control_amd as q
-
-    return q
-
-
-@pytest.fixture(scope="module")
-def P(q):
-    return q.cheetah_params()
-
-
-@pytest.fixture(scope="module")
-def ctl(q, P):
-    c = q.BalanceController.from_params(P, device=0)
-    yield c
-    c.close()
 
 
 @functools.lru_cache(maxsize=None)
@@ -283,22 +265,22 @@ def test_argument_errors_launch_nothing(q, ctl):
             setattr(s, k, v)
         return s
 
-    def refused(handle, s, what):
-        rc = lib.qc_plant_step_batch(handle, n, ctypes.byref(s) if s is not None else None, stream)
-        assert rc == -1 and _lib.last_error().startswith("qc_plant_step_batch:"), (what, rc, _lib.last_error())
-        torch.cuda.synchronize()
+    def untouched(what):
         for k, v in d.items():
             assert torch.equal(v[0], before[k]), (what, k)
+
+    def refused(handle, s, what):
+        rc = lib.qc_plant_step_batch(handle, n, ctypes.byref(s), stream)
+        assert rc == -1 and _lib.last_error().startswith("qc_plant_step_batch:"), (what, rc, _lib.last_error())
+        torch.cuda.synchronize()
+        untouched(what)
         assert (feet == SENTINEL).all(), what
 
     for k in STATE + ("grf_body", "foot_world"):
         refused(ctl._h, io(**{k: None}), f"{k} = NULL")
-    refused(ctl._h, io(struct_size=64), "struct_size of another revision")
     refused(ctl._h, io(struct_size=0), "struct_size not set")
     for dt in (0.0, -1.0 / 300.0, float("nan"), float("inf")):
         refused(ctl._h, io(dt=dt), f"dt = {dt}")
-    refused(None, io(), "no handle")
-    refused(ctl._h, None, "no io")
     # a handle whose inertia no rigid body has: qc_create takes it (the wrench law reads nothing of it), the plant does not
     P = dict(q.cheetah_params())
     P["Ib"] = np.diag([0.011253, -0.036203, 0.042673])
@@ -308,14 +290,14 @@ def test_argument_errors_launch_nothing(q, ctl):
     with pytest.raises(RuntimeError, match="qc_plant_step_batch:"):
         odd.plant_step({k: d[k][1] for k in STATE}, d["grf_body"][1], d["foot_world"][1], 1.0 / 300.0)
     odd.close()
-    # n = 0 is no error and launches nothing; the Python wrapper checks shapes before it calls
-    assert lib.qc_plant_step_batch(ctl._h, 0, ctypes.byref(io()), stream) == 0
+    # the Python wrapper checks shapes before it calls
     with pytest.raises(ValueError, match="grf_body"):
         ctl.plant_step({k: d[k][1] for k in STATE}, d["grf_body"][1][:, :6].contiguous(), d["foot_world"][1], 1.0 / 300.0)
-    torch.cuda.synchronize()
-    for k, v in d.items():
-        assert torch.equal(v[0], before[k]), k
-    # ... and the same call with everything in order does step
-    assert lib.qc_plant_step_batch(ctl._h, n, ctypes.byref(io()), stream) == 0
-    torch.cuda.synchronize()
-    assert not torch.equal(d["x"][0][:n], before["x"][:n]) and (feet != SENTINEL).all() and (d["x"][0][n:] == SENTINEL).all()
+
+    def stepped():
+        assert not torch.equal(d["x"][0][:n], before["x"][:n]) and (d["x"][0][n:] == SENTINEL).all(), "x after the valid call"
+
+    # no handle, no io, n beyond one launch, a struct_size of another revision; n = 0 is no error and launches nothing; the same
+    # call with everything in order does step
+    assert_raw_refusals(lib.qc_plant_step_batch, lambda: (ctl._h, n, None, io()), "qc_plant_io", ctypes.sizeof(_lib.QcPlantIo), 64,
+                        [(feet, SENTINEL, True)], beyond=0xFFFFFF * 256 + 1, stream=stream, untouched=untouched, launched=stepped)

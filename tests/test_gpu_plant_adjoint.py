@@ -18,35 +18,17 @@ import pytest
 
 from tests import plant_adjoint_restatement as AR
 from tests import plant_restatement as PR
-from tests.gpu_arrays import SENTINEL, _device_arrays, _tile
+from tests.fd_support import BAR_OF, fd_bar
+from tests.gpu_arrays import SENTINEL, P, _device_arrays, _tile, ctl, q  # noqa: F401
+from tests.solved_batch_support import assert_raw_refusals
 
 pytestmark = pytest.mark.gpu
 EPS = AR.EPS
 SIZES = (1, 63, 64, 65, 257, 4097)
 STATE = ("Rwb", "x", "xdot", "w")
 K = {k: 4.0 * v for k, v in AR.C_NP.items()}  # c_np is measured on the CPU, never taken from the device
-BAR_OF = {"Rwb": "Rwb_bar", "x": "x_bar", "xdot": "xdot_bar", "w": "w_bar", "grf_body": "grf_bar", "foot_world": "foot_world_bar"}
 # an output and the input cotangent of its layout it may be written over
 ALIASES = (("Rwb_bar", "Rwb"), ("x_bar", "x"), ("xdot_bar", "xdot"), ("w_bar", "w"), ("foot_world_bar", "feet"), ("grf_bar", "feet"), ("x_bar", "w"))
-
-
-@pytest.fixture(scope="module")
-def q(built):
-    import quadruped_control_amd as q
-
-    return q
-
-
-@pytest.fixture(scope="module")
-def P(q):
-    return q.cheetah_params()
-
-
-@pytest.fixture(scope="module")
-def ctl(q, P):
-    c = q.BalanceController.from_params(P, device=0)
-    yield c
-    c.close()
 
 
 def _adjoint(ctl, s, bars, n, dt, want=AR.OUTPUTS, given=None, alias=None, zeros=False):
@@ -148,8 +130,6 @@ def test_consistent_with_differences_of_plant_step(ctl, P):
     quotient's rounding from the forward kernel's derived one-step bars (tests/test_gpu_plant.py holds the kernel to them) plus
     the analytic side's 4 EPS sum condsum |v|."""
     import torch
-
-    from tests.test_plant_adjoint_cpu import fd_bar
 
     dt, h, n = 1.0 / 300.0, AR.FD_H, AR.FD_N
     s, bars = ({k: a[:n] for k, a in d.items()} for d in AR.pool(dt))
@@ -323,17 +303,17 @@ def test_argument_errors_launch_nothing(q, ctl):
             setattr(a, k, val)
         return a
 
-    def refused(handle, a, what, m=n):
-        rc = lib.qc_plant_step_adjoint_batch(handle, m, ctypes.byref(a) if a is not None else None, stream)
-        assert rc == -1 and _lib.last_error().startswith("qc_plant_step_adjoint_batch:"), (what, rc, _lib.last_error())
-        torch.cuda.synchronize()
-        assert all(bool((t == SENTINEL).all()) for t in outs.values()), what
+    def untouched(what="the valid call"):
         for k, t in list(d.items()) + [("bar_" + k, t) for k, t in bd.items()]:
             assert torch.equal(t[0], before[k]), (what, k)
 
-    refused(None, io(), "no handle")
-    refused(ctl._h, None, "no io")
-    refused(ctl._h, io(struct_size=72), "struct_size of another struct")
+    def refused(handle, a, what):
+        rc = lib.qc_plant_step_adjoint_batch(handle, n, ctypes.byref(a), stream)
+        assert rc == -1 and _lib.last_error().startswith("qc_plant_step_adjoint_batch:"), (what, rc, _lib.last_error())
+        torch.cuda.synchronize()
+        assert all(bool((t == SENTINEL).all()) for t in outs.values()), what
+        untouched(what)
+
     refused(ctl._h, io(struct_size=0), "struct_size not set")
     for k in AR.INPUTS:
         refused(ctl._h, io(**{k: None}), f"{k} = NULL")
@@ -341,7 +321,6 @@ def test_argument_errors_launch_nothing(q, ctl):
     refused(ctl._h, io(**{k: None for k in outs}), "no output")
     for bad in (0.0, -1.0 / 300.0, float("nan"), float("inf")):
         refused(ctl._h, io(dt=bad), f"dt = {bad}")
-    refused(ctl._h, io(), "n beyond one launch", m=0xFFFFFF * 256 + 1)
     Podd = dict(q.cheetah_params())
     Podd["Ib"] = np.diag([0.011253, -0.036203, 0.042673])
     odd = q.BalanceController.from_params(Podd, device=0)
@@ -362,11 +341,6 @@ def test_argument_errors_launch_nothing(q, ctl):
         ctl.plant_step_adjoint(state, d["grf_body"][1], d["foot_world"][1], dt, {"x": bd["x"][1]}, want=("feet_bar",))
     with pytest.raises(ValueError, match="^qc_plant_step_adjoint_batch: no input cotangent"):
         ctl.plant_step_adjoint(state, d["grf_body"][1], d["foot_world"][1], dt, {}, want=("x_bar",), out={"x_bar": outs["x_bar"]})
-    assert lib.qc_plant_step_adjoint_batch(ctl._h, 0, ctypes.byref(io()), stream) == 0  # n == 0: QC_OK, nothing launched
-    torch.cuda.synchronize()
-    assert all(bool((t == SENTINEL).all()) for t in outs.values())
-    assert lib.qc_plant_step_adjoint_batch(ctl._h, n, ctypes.byref(io()), stream) == 0  # and the same structs, valid, do launch
-    torch.cuda.synchronize()
-    assert all(not bool((t == SENTINEL).any()) for t in outs.values())
-    for k, t in list(d.items()) + [("bar_" + k, t) for k, t in bd.items()]:
-        assert torch.equal(t[0], before[k]), k
+    # no handle, no io, n beyond one launch, the struct_size of another struct; n == 0 launches nothing; the same structs, valid, do
+    assert_raw_refusals(lib.qc_plant_step_adjoint_batch, lambda: (ctl._h, n, None, io()), "qc_plant_adjoint_io", ctypes.sizeof(_lib.QcPlantAdjointIo), 72,
+                        [(t, SENTINEL, True) for t in outs.values()], beyond=0xFFFFFF * 256 + 1, stream=stream, untouched=untouched, launched=untouched)

@@ -3,16 +3,11 @@ batch sizes (the oracle only sees bounded samples there)."""
 import numpy as np
 import pytest
 
+from tests.gpu_arrays import q  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 FIELDS = ("Rwb", "Rwb_d", "x", "xdot", "w", "x_d", "xdot_d", "w_d", "feet")
-
-
-@pytest.fixture(scope="module")
-def q(built):
-    import quadruped_control_amd as q
-
-    return q
 
 
 def _world_forces(batch, grf):
@@ -553,7 +548,7 @@ def test_on_device_swing_planning_multi_tick(q, n):
     """SURVEY 8f rank 4, stateful half: foothold planner + sextic swing trajectories kept in a
     per-robot state buffer across ticks; torques and the carried state track the oracle tick by tick."""
     from oracle import c_oracle as O
-    from tests.test_oracle_cpu import _planned_batch
+    from tests.commander_support import _planned_batch
 
     P = q.cheetah_params(0.6)
     ctl = q.BalanceController.from_params(P)
@@ -598,7 +593,7 @@ def test_stateful_tick_on_general_and_dense_forms(q, form, n):
     diagonal (balance_controller.hpp:76-77: W is the caller's) - tracks the oracle tick by tick like the uniform form does
     (test_on_device_swing_planning_multi_tick).  700 robots: four lanes per robot; 40 000: one lane per robot, Hessian planes in LDS."""
     from oracle import c_oracle as O
-    from tests.test_oracle_cpu import _planned_batch
+    from tests.commander_support import _planned_batch
 
     P = q.cheetah_params(0.6)
     tune = {}
@@ -674,7 +669,7 @@ def test_small_batch_in_place_host_path_matches_staged(q):
     """qc_control_batch_host serves n <= 8192 from a pinned buffer the kernel reads/writes in place and larger
     batches through staged copies: the same robots must come back bit-identical either way, for the plain
     call and for the complete tick (swing state updated in place on the host)."""
-    from tests.test_oracle_cpu import _planned_batch
+    from tests.commander_support import _planned_batch
     from quadruped_control_amd import workloads as W
 
     P = q.cheetah_params(0.6)
@@ -855,7 +850,7 @@ def test_non_finite_states_in_the_stateful_tick(q):
     the statuses and the NaN pattern of the torques follow the oracle (std::clamp of the trajectory time,
     trajectory.cpp:369, keeps a NaN phase NaN)."""
     from oracle import c_oracle as O
-    from tests.test_oracle_cpu import _planned_batch
+    from tests.commander_support import _planned_batch
 
     P = q.cheetah_params(0.6)
     ctl = q.BalanceController.from_params(P)

@@ -2,7 +2,7 @@
 same definitions at 50 digits on a fixed subset, and against central differences of control_batch itself.
 
 Batch sizes 1, 63, 64, 65 and 130: tail lanes, one wave +- 1 (a workgroup is one wave), more than one workgroup.  Robot i of
-every batch has contact pattern i % 16.  The placed forces and the three handles are test_gpu_kkt_certificate's: every component
+every batch has contact pattern i % 16.  The placed forces and the three handles are solved_batch_support's: every component
 exactly on a face or well inside, so the device and numpy classify alike.
 
 Bars.  `flags` is compared exactly.  Floating-point outputs of a robot: the device solves the padded 12 x 12 system by LDL^T, the
@@ -17,49 +17,25 @@ the last.  In the 50-digit test the device may be 8 x as far from the 50-digit v
 contraction, another elimination order), with a floor of 64 eps max|output|; both measured values are printed and recorded in
 profiles/sensitivity.md."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
 
 from tests import sensitivity_restatement as SR
-from tests.test_gpu_kkt_certificate import _inputs, _params
+from tests import solved_batch_support as SB
+from tests.solved_batch_support import EPS, FORMS, SENTINEL, STATE_KEYS, assert_raw_refusals, batch_in, ctls, inputs, params, q, run  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 SIZES = (1, 63, 64, 65, 130)
-EPS = 2.0 ** -52
-SENTINEL = -7777.25
-STATE_KEYS = ("Rwb", "Rwb_d", "x", "xdot", "w", "x_d", "xdot_d", "w_d")
 WANT_ALL = SR.OUTPUTS + ("flags",)
-FORMS = {"uniform": "diagW-6x6-uniform", "per-axis": "diagW-6x6", "dense": "dense-12x12"}
 
 
-@pytest.fixture(scope="module")
-def q(built):
-    import quadruped_control_amd as q
-
-    return q
-
-
-@pytest.fixture(scope="module")
-def ctls(q):
-    out = {k: q.BalanceController.from_params(_params(q, k), device=0) for k in FORMS}
-    assert [c.kernel_name for c in out.values()] == list(FORMS.values())
-    yield out
-    for c in out.values():
-        c.close()
-
-
-def _gbar(n, seed=0):
-    return np.random.default_rng(4000 + n + seed).normal(0.0, 1.0, (n, 12))
+_gbar = functools.partial(SB.gbar, 4000)
 
 
 def _run(q, ctl, b, grf, gbar, want=WANT_ALL, **kw):
-    import torch
-
-    dev = q.to_device(b)
-    out = ctl.sensitivity_batch(dev, torch.from_numpy(grf).cuda(), torch.from_numpy(gbar).cuda(), want=want, **kw)
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in out.items()}
+    return run(q, ctl.sensitivity_batch, b, grf, gbar, want=want, **kw)[0]
 
 
 def _assert_close(P, b, got, ref, what):
@@ -78,8 +54,8 @@ def _assert_close(P, b, got, ref, what):
 def test_every_output_against_the_restatement(q, ctls, n, source):
     """Placed forces; `feet` with stance bytes, joint_q with the phase rule (the handle's duty, and gait_duty); all 16 contact
     masks once n >= 16; the all-swing mask gives all zeros."""
-    P = _params(q, "uniform")
-    b, grf = _inputs(n, source)
+    P = params(q, "uniform")
+    b, grf = inputs(n, source)
     gbar = _gbar(n)
     got = _run(q, ctls["uniform"], b, grf, gbar)
     ref = SR.sensitivity(P, b, grf, gbar)
@@ -91,8 +67,8 @@ def test_every_output_against_the_restatement(q, ctls, n, source):
 
 
 def test_all_stance_without_stance_or_phase(q, ctls):
-    P = _params(q, "uniform")
-    b = {k: v for k, v in _inputs(64, "feet")[0].items() if k != "stance"}
+    P = params(q, "uniform")
+    b = {k: v for k, v in inputs(64, "feet")[0].items() if k != "stance"}
     fw = np.tile([[2.0, -1.0, 30.0], [0.6 * 40.0, 3.0, 40.0], [-4.0, 5.0, 120.0], [1.0, 1.0, 10.0]], (64, 1, 1))  # interior, tied, fzmax, fzmin
     grf = -np.einsum("nji,nkj->nki", b["Rwb"].reshape(64, 3, 3), fw).reshape(64, 12)
     gbar = _gbar(64, 1)
@@ -123,7 +99,7 @@ def solved(q, ctls):
         grf = o["grf_body"].cpu().numpy()
         s = ctl.sensitivity_batch(dev, o["grf_body"], torch.from_numpy(gbar).cuda(), want=WANT_ALL)
         torch.cuda.synchronize()
-        P = _params(q, kind)
+        P = params(q, kind)
         out[kind] = dict(P=P, b=b, grf=grf, gbar=gbar, got={k: v.cpu().numpy() for k, v in s.items()}, ref=SR.sensitivity(P, b, grf, gbar))
     return out
 
@@ -251,9 +227,9 @@ def test_bad_pivot_sets_bit_1_and_poisons_the_robot(q, ctls, source):
     """A non-finite foot position (or joint angle) of a stance foot under given, finite forces: the face is read from the forces and
     has free coordinates, the reduced matrix is not finite, so the pivot check sets bit 1 and every output of that robot is NaN - on
     the device as in the restatement - and the robots next to it are untouched."""
-    P = _params(q, "uniform")
+    P = params(q, "uniform")
     n = 65
-    b, grf = _inputs(n, source)
+    b, grf = inputs(n, source)
     b = {k: v.copy() for k, v in b.items()}
     bad = [15, 47]  # contact pattern 15: four stance feet
     for i in bad:
@@ -305,7 +281,7 @@ def test_inputs_untouched_repeatable_and_capturable(q, ctls):
     import torch
 
     n = 130
-    b, grf = _inputs(n, "feet")
+    b, grf = inputs(n, "feet")
     dev = q.to_device(b)
     before = {k: v.clone() for k, v in dev.items()}
     g, gb = torch.from_numpy(grf).cuda(), torch.from_numpy(_gbar(n, 5)).cuda()
@@ -340,7 +316,7 @@ def test_refusals_raise_and_launch_nothing(q, ctls):
 
     ctl = ctls["uniform"]
     n = 65
-    b, grf = _inputs(n, "feet")
+    b, grf = inputs(n, "feet")
     dev = q.to_device(b)
     g, gb = torch.from_numpy(grf).cuda(), torch.from_numpy(_gbar(n)).cuda()
     out = {"adjoint": torch.full((n, 12), SENTINEL, dtype=torch.float64, device="cuda")}
@@ -361,20 +337,5 @@ def test_refusals_raise_and_launch_nothing(q, ctls):
     io = _lib.QcSensitivityIo()
     lib.qc_default_sensitivity(ctypes.byref(io))
     io.grf_body, io.grf_bar, io.adjoint = g.data_ptr(), gb.data_ptr(), out["adjoint"].data_ptr()
-    bi = _lib.QcBatchIn()
-    for k in STATE_KEYS + ("feet", "stance"):
-        setattr(bi, k, dev[k].data_ptr())
-    calls = [(None, n, ctypes.byref(bi), ctypes.byref(io)), (ctl._h, n, None, ctypes.byref(io)), (ctl._h, n, ctypes.byref(bi), None),
-             (ctl._h, 0xFFFFFF * 64 + 1, ctypes.byref(bi), ctypes.byref(io))]
-    for h, m, pin, pio in calls:
-        assert lib.qc_sensitivity_batch(h, m, pin, pio, None) == -1 and _lib.last_error().startswith("qc_sensitivity_batch:")
-    io.struct_size = 104
-    assert lib.qc_sensitivity_batch(ctl._h, n, ctypes.byref(bi), ctypes.byref(io), None) == -1
-    assert _lib.last_error().startswith("qc_sensitivity_batch: qc_sensitivity_io.struct_size")
-    io.struct_size = 112
-    assert lib.qc_sensitivity_batch(ctl._h, 0, ctypes.byref(bi), ctypes.byref(io), None) == 0  # n == 0: QC_OK, nothing launched
-    torch.cuda.synchronize()
-    assert bool((out["adjoint"] == SENTINEL).all())
-    assert lib.qc_sensitivity_batch(ctl._h, n, ctypes.byref(bi), ctypes.byref(io), None) == 0  # and the same structs, valid, do launch
-    torch.cuda.synchronize()
-    assert not bool((out["adjoint"] == SENTINEL).any())
+    bi = batch_in(dev, STATE_KEYS + ("feet", "stance"))
+    assert_raw_refusals(lib.qc_sensitivity_batch, lambda: (ctl._h, n, bi, io), "qc_sensitivity_io", 112, 104, [(out["adjoint"], SENTINEL, True)])

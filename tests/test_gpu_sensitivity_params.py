@@ -3,7 +3,7 @@
 at perturbed parameter sets, and the `params` leaf of the torch.autograd wrappers.
 
 Rows: batch sizes 1, 63, 64, 65 and 130 (tail lanes, one wave +- 1, more than one workgroup); the placed forces and the handles are
-test_gpu_kkt_certificate's.  Both sides are fed the SAME adjoint: the device's own, from sensitivity_batch.  The bar per entry is
+solved_batch_support's.  Both sides are fed the SAME adjoint: the device's own, from sensitivity_batch.  The bar per entry is
 C eps `terms`, `terms` being the restatement's sum of the magnitudes of the entry's contributions (every factor absolute).  C from
 the longest rounded chain, mu_bar's: the lever arms r = R p 5; A z (a cross product 3, four feet and the sum 5) 8; q = S A z 11;
 H z's row (cross product and sum 5, the 12-term row of W 23, the sum and the factor 2) 30; f_bar 5 and rho 1; the tie 3, its product
@@ -16,39 +16,22 @@ ceil(ceil(n / 64) / 1024) * 64 additions), the finisher's 16 waves each add ever
 threads, and the grid is capped at its thread count (1024), so "one partial more than the finisher's stride" is 17 partials (n = 1025)
 and "one workgroup more than the cap" is n = 65537, where workgroup 0 walks a second round of the grid stride; both are in SUM_SIZES."""
 import ctypes
+import functools
 import math
 
 import numpy as np
 import pytest
 
 from tests import sensitivity_params_restatement as PR
-from tests.test_gpu_kkt_certificate import _inputs, _params
-from tests.test_sensitivity_cpu import fd_batch
-from tests.test_sensitivity_params_cpu import GROUPS
+from tests import solved_batch_support as SB
+from tests.fd_support import GROUPS, fd_batch
+from tests.solved_batch_support import EPS, FORMS, SENTINEL, STATE_KEYS, assert_raw_refusals, batch_in, ctls, inputs, params, q  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 SIZES = (1, 63, 64, 65, 130)
 SUM_SIZES = (130, 1000, 1025, 65537)
-EPS = 2.0 ** -52
-SENTINEL = -7777.25
-STATE_KEYS = ("Rwb", "Rwb_d", "x", "xdot", "w", "x_d", "xdot_d", "w_d")
-HANDLES = ("uniform", "per-axis", "dense")
+HANDLES = tuple(FORMS)
 FD_N = 480
-
-
-@pytest.fixture(scope="module")
-def q(built):
-    import quadruped_control_amd as q
-
-    return q
-
-
-@pytest.fixture(scope="module")
-def ctls(q):
-    out = {k: q.BalanceController.from_params(_params(q, k), device=0) for k in HANDLES}
-    yield out
-    for c in out.values():
-        c.close()
 
 
 @pytest.fixture(scope="module")
@@ -56,8 +39,7 @@ def ctl(ctls):
     return ctls["uniform"]
 
 
-def _gbar(n, seed=0):
-    return np.random.default_rng(7000 + n + seed).normal(0.0, 1.0, (n, 12))
+_gbar = functools.partial(SB.gbar, 7000)
 
 
 def _guarded(n, rows=True, total=True):
@@ -98,8 +80,8 @@ def test_rows_against_the_restatement(q, ctls, n, source, handle):
     once n >= 16; the all-swing mask gives exact zero rows.  A sentinel row sits behind the rows and behind the sum."""
     import torch
 
-    P, c = _params(q, handle), ctls[handle]
-    b, grf = _inputs(n, source)
+    P, c = params(q, handle), ctls[handle]
+    b, grf = inputs(n, source)
     gbar = _gbar(n)
     dev = q.to_device(b)
     g, gb = torch.from_numpy(grf).cuda(), torch.from_numpy(gbar).cuda()
@@ -129,8 +111,8 @@ def test_sum_is_reproducible_and_is_the_sum_of_the_rows(q, ctl, n):
     rows are asked for or not; against a float64 sum of the device's own rows the error is at most depth(n) eps sum_i |row_i|."""
     import torch
 
-    b, grf = _inputs(n, "feet")
-    other_b, other_grf = _inputs(130 if n != 130 else 65, "feet")
+    b, grf = inputs(n, "feet")
+    other_b, other_grf = inputs(130 if n != 130 else 65, "feet")
     dev, other = q.to_device(b), q.to_device(other_b)
     g, gb = torch.from_numpy(grf).cuda(), torch.from_numpy(_gbar(n, 1)).cuda()
     og, ogb = torch.from_numpy(other_grf).cuda(), torch.from_numpy(_gbar(other_grf.shape[0], 2)).cuda()
@@ -218,7 +200,7 @@ def test_nan_adjoint_gives_a_nan_row_and_a_nan_sum(q, ctl):
     import torch
 
     n = 65
-    b, grf = _inputs(n, "feet")
+    b, grf = inputs(n, "feet")
     dev = q.to_device(b)
     g, gb = torch.from_numpy(grf).cuda(), torch.from_numpy(_gbar(n, 4)).cuda()
     z = _adjoint(ctl, dev, g, gb)["adjoint"]
@@ -239,7 +221,7 @@ def test_inputs_untouched_and_capturable_behind_the_adjoint(q, ctl):
     import torch
 
     n = 130
-    b, grf = _inputs(n, "feet")
+    b, grf = inputs(n, "feet")
     dev = q.to_device(b)
     before = {k: v.clone() for k, v in dev.items()}
     g, gb = torch.from_numpy(grf).cuda(), torch.from_numpy(_gbar(n, 5)).cuda()
@@ -273,7 +255,7 @@ def test_refusals_raise_and_launch_nothing(q, ctl):
     from quadruped_control_amd import _lib
 
     n = 65
-    b, grf = _inputs(n, "feet")
+    b, grf = inputs(n, "feet")
     dev = q.to_device(b)
     g, gb = torch.from_numpy(grf).cuda(), torch.from_numpy(_gbar(n)).cuda()
     z = torch.zeros((n, 12), dtype=torch.float64, device="cuda")
@@ -299,32 +281,22 @@ def test_refusals_raise_and_launch_nothing(q, ctl):
     lib.qc_default_sensitivity_param(ctypes.byref(io))
     io.grf_body, io.grf_bar, io.adjoint = g.data_ptr(), gb.data_ptr(), z.data_ptr()
     io.param_bar_rows, io.param_bar = out["param_bar_rows"].data_ptr(), out["param_bar"].data_ptr()
-    bi = _lib.QcBatchIn()
-    for k in STATE_KEYS + ("feet",):
-        setattr(bi, k, dev[k].data_ptr())
-    calls = [(None, n, ctypes.byref(bi), ctypes.byref(io)), (ctl._h, n, None, ctypes.byref(io)), (ctl._h, n, ctypes.byref(bi), None),
-             (ctl._h, 0xFFFFFF * 64 + 1, ctypes.byref(bi), ctypes.byref(io))]
-    for h, m, pin, pio in calls:
-        assert lib.qc_sensitivity_param_batch(h, m, pin, pio, None) == -1 and _lib.last_error().startswith("qc_sensitivity_param_batch:")
-    io.struct_size = 48
-    assert lib.qc_sensitivity_param_batch(ctl._h, n, ctypes.byref(bi), ctypes.byref(io), None) == -1
-    assert _lib.last_error().startswith("qc_sensitivity_param_batch: qc_sensitivity_param_io.struct_size")
-    io.struct_size = 56
-    assert lib.qc_sensitivity_param_batch(ctl._h, 0, ctypes.byref(bi), ctypes.byref(io), None) == 0  # n == 0: QC_OK, nothing launched
-    torch.cuda.synchronize()
-    assert all(bool((t == SENTINEL).all()) for t in full.values())
-    assert lib.qc_sensitivity_param_batch(ctl._h, n, ctypes.byref(bi), ctypes.byref(io), None) == 0  # and the same structs, valid, do launch
-    torch.cuda.synchronize()
-    assert not bool((out["param_bar_rows"] == SENTINEL).any()) and not bool((out["param_bar"] == SENTINEL).any()) and _sentinels_intact(full)
+    bi = batch_in(dev, STATE_KEYS + ("feet",))
+
+    def rows_behind(what="the valid call"):
+        assert _sentinels_intact(full), what
+
+    assert_raw_refusals(lib.qc_sensitivity_param_batch, lambda: (ctl._h, n, bi, io), "qc_sensitivity_param_io", 56, 48,
+                        [(out["param_bar_rows"], SENTINEL, True), (out["param_bar"], SENTINEL, True)], untouched=rows_behind, launched=rows_behind)
 
 
 # ------------------------------------------------------------------ the autograd wrappers
 def test_parameter_tensor_is_the_handles_own(q, ctl):
     theta = ctl.parameter_tensor()
     assert theta.shape == (211,) and theta.is_cuda and str(theta.dtype) == "torch.float64"
-    assert np.array_equal(theta.cpu().numpy(), PR.pack(_params(q, "uniform")))
+    assert np.array_equal(theta.cpu().numpy(), PR.pack(params(q, "uniform")))
     P = q.unpack_param_bar(theta)
-    assert P["mu"] == 0.6 and np.array_equal(P["S"], np.asarray(_params(q, "uniform")["S"], float)) and list(q.PARAM_LAYOUT) == list(PR.LAYOUT)
+    assert P["mu"] == 0.6 and np.array_equal(P["S"], np.asarray(params(q, "uniform")["S"], float)) and list(q.PARAM_LAYOUT) == list(PR.LAYOUT)
 
 
 def test_autograd_params_grad_equals_the_direct_sum_bit_for_bit(q, ctl):

@@ -3,7 +3,7 @@ against the same definitions at 50 digits on the branch sweep, against central d
 torch.autograd wrapper (quadruped_control_amd/autograd.py) against the direct calls.
 
 Batch sizes 1, 63, 64, 65 and 130: tail lanes, one wave +- 1 (a workgroup is one wave), more than one workgroup.  The placed forces
-and the handles are test_gpu_kkt_certificate's.  To isolate the kernel from the 12x12 solve both sides are fed the SAME b_bar and
+and the handles are solved_batch_support's.  To isolate the kernel from the 12x12 solve both sides are fed the SAME b_bar and
 feet_bar: the device's own, from sensitivity_batch.
 
 The bar against the restatement, per output entry: C eps `terms`, `terms` being the restatement's sum of the magnitudes of the four
@@ -20,40 +20,30 @@ log grows as 1 / qw^2 against a first derivative of 1 / |qw|: the bar there is (
 is at its worst, with a floor of 64 eps of the output's scale (test_gpu_sensitivity's rule); both are printed and recorded in
 profiles/sensitivity_rotation.md."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
 
 from tests import sensitivity_rotation_restatement as RR
-from tests.test_gpu_kkt_certificate import _inputs, _params
-from tests.test_sensitivity_cpu import fd_batch
-from tests.test_sensitivity_rotation_cpu import FD_H, fd_directions
+from tests import solved_batch_support as SB
+from tests.fd_support import FD_H, fd_batch, fd_directions
+from tests.solved_batch_support import EPS, SENTINEL, STATE_KEYS, assert_raw_refusals, batch_in, inputs, params, q  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 SIZES = (1, 63, 64, 65, 130)
-EPS = 2.0 ** -52
-SENTINEL = -7777.25
-STATE_KEYS = ("Rwb", "Rwb_d", "x", "xdot", "w", "x_d", "xdot_d", "w_d")
 DIFFERENTIABLE = STATE_KEYS + ("feet",)
 WANT_ALL = RR.OUTPUTS
 
 
 @pytest.fixture(scope="module")
-def q(built):
-    import quadruped_control_amd as q
-
-    return q
-
-
-@pytest.fixture(scope="module")
 def ctl(q):
-    c = q.BalanceController.from_params(_params(q, "uniform"), device=0)
+    c = q.BalanceController.from_params(params(q, "uniform"), device=0)
     yield c
     c.close()
 
 
-def _gbar(n, seed=0):
-    return np.random.default_rng(5000 + n + seed).normal(0.0, 1.0, (n, 12))
+_gbar = functools.partial(SB.gbar, 5000)
 
 
 def _both(q, ctl, b, grf, gbar, want=WANT_ALL):
@@ -83,8 +73,8 @@ def _assert_close(got, ref, c, what, qw_term=False):
 def test_every_output_against_the_restatement(q, ctl, n, source):
     """Placed forces; `feet` with stance bytes, joint_q with the phase rule (the handle's duty, and gait_duty); all 16 contact masks
     once n >= 16; the all-swing mask gives exact zeros; even robots have Rwb = Rwb_d = I, the n2 = 0 limit of the log."""
-    P = _params(q, "uniform")
-    b, grf = _inputs(n, source)
+    P = params(q, "uniform")
+    b, grf = inputs(n, source)
     gbar = _gbar(n)
     got, b_bar, feet_bar, flags = _both(q, ctl, b, grf, gbar)
     ref = RR.rotation_cotangents(P, b, grf, gbar, b_bar, feet_bar)
@@ -147,7 +137,7 @@ def test_branch_sweep_against_50_digits(sweep):
 def test_finite_differences_of_control_batch(q, ctl):
     """<Rwb_bar, D> + <Rwb_d_bar, Dd> against control_batch itself at Rwb + k h D, Rwb_d + k h Dd, k = 0, +-1, +-2: ENTRYWISE
     directions (the matrices leave the manifold; the library evaluates its expressions on the nine numbers as they are), the
-    committed directions and h = 1e-4 of tests/test_sensitivity_rotation_cpu.py on the first 128 robots of its batch, race = 0.  Kept:
+    committed directions and h = 1e-4 of tests/fd_support.py on the first 128 robots of its batch, race = 0.  Kept:
     solved and the same want_active_set word at all five points, flags 0; at least 0.75.  Truncation per robot from the solver alone,
     t = |FD(h) - FD(2h)|.  Bar: t + 1e-5 |theta_bar| |d| - test_gpu_sensitivity's feet test's rounding term, for the same reason: the
     forces' absolute error of ~1e-8 N (csrc/qc_host.hpp) over h."""
@@ -195,9 +185,9 @@ def test_finite_differences_of_control_batch(q, ctl):
 def test_poisoned_robot_is_nan_and_its_neighbours_are_untouched(q, ctl, source):
     """A NaN foot position (or joint angle) of a stance foot under placed forces: qc_sensitivity_batch poisons the robot (bit 1, NaN
     b_bar and feet_bar), and every rotation output of it is NaN; the robots next to it compare as ever."""
-    P = _params(q, "uniform")
+    P = params(q, "uniform")
     n = 65
-    b, grf = _inputs(n, source)
+    b, grf = inputs(n, source)
     b = {k: v.copy() for k, v in b.items()}
     bad = [15, 47]  # contact pattern 15: four stance feet
     for i in bad:
@@ -219,7 +209,7 @@ def test_inputs_untouched_repeatable_and_capturable_as_a_pair(q, ctl):
     import torch
 
     n = 130
-    b, grf = _inputs(n, "feet")
+    b, grf = inputs(n, "feet")
     dev = q.to_device(b)
     before = {k: v.clone() for k, v in dev.items()}
     g, gb = torch.from_numpy(grf).cuda(), torch.from_numpy(_gbar(n, 5)).cuda()
@@ -256,7 +246,7 @@ def test_refusals_raise_and_launch_nothing(q, ctl):
     from quadruped_control_amd import _lib
 
     n = 65
-    b, grf = _inputs(n, "feet")
+    b, grf = inputs(n, "feet")
     dev = q.to_device(b)
     g, gb = torch.from_numpy(grf).cuda(), torch.from_numpy(_gbar(n)).cuda()
     bb, fb = torch.zeros((n, 6), dtype=torch.float64, device="cuda"), torch.zeros((n, 4, 3), dtype=torch.float64, device="cuda")
@@ -277,23 +267,8 @@ def test_refusals_raise_and_launch_nothing(q, ctl):
     io = _lib.QcSensitivityRotIo()
     lib.qc_default_sensitivity_rot(ctypes.byref(io))
     io.grf_body, io.grf_bar, io.b_bar, io.feet_bar, io.Rwb_bar = g.data_ptr(), gb.data_ptr(), bb.data_ptr(), fb.data_ptr(), out["Rwb_bar"].data_ptr()
-    bi = _lib.QcBatchIn()
-    for k in STATE_KEYS + ("feet",):
-        setattr(bi, k, dev[k].data_ptr())
-    calls = [(None, n, ctypes.byref(bi), ctypes.byref(io)), (ctl._h, n, None, ctypes.byref(io)), (ctl._h, n, ctypes.byref(bi), None),
-             (ctl._h, 0xFFFFFF * 64 + 1, ctypes.byref(bi), ctypes.byref(io))]
-    for h, m, pin, pio in calls:
-        assert lib.qc_sensitivity_rot_batch(h, m, pin, pio, None) == -1 and _lib.last_error().startswith("qc_sensitivity_rot_batch:")
-    io.struct_size = 64
-    assert lib.qc_sensitivity_rot_batch(ctl._h, n, ctypes.byref(bi), ctypes.byref(io), None) == -1
-    assert _lib.last_error().startswith("qc_sensitivity_rot_batch: qc_sensitivity_rot_io.struct_size")
-    io.struct_size = 72
-    assert lib.qc_sensitivity_rot_batch(ctl._h, 0, ctypes.byref(bi), ctypes.byref(io), None) == 0  # n == 0: QC_OK, nothing launched
-    torch.cuda.synchronize()
-    assert bool((out["Rwb_bar"] == SENTINEL).all())
-    assert lib.qc_sensitivity_rot_batch(ctl._h, n, ctypes.byref(bi), ctypes.byref(io), None) == 0  # and the same structs, valid, do launch
-    torch.cuda.synchronize()
-    assert not bool((out["Rwb_bar"] == SENTINEL).any())
+    bi = batch_in(dev, STATE_KEYS + ("feet",))
+    assert_raw_refusals(lib.qc_sensitivity_rot_batch, lambda: (ctl._h, n, bi, io), "qc_sensitivity_rot_io", 72, 64, [(out["Rwb_bar"], SENTINEL, True)])
 
 
 # ------------------------------------------------------------------ the autograd wrapper

@@ -18,27 +18,12 @@ import pytest
 import quadruped_control_amd as q
 from tests import plant_adjoint_restatement as AR
 from tests import plant_restatement as PR
+from tests.fd_support import BAR_OF, fd_bar
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 EPS = AR.EPS
 C_NP = AR.C_NP
-BAR_OF = {"Rwb": "Rwb_bar", "x": "x_bar", "xdot": "xdot_bar", "w": "w_bar", "grf_body": "grf_bar", "foot_world": "foot_world_bar"}
 FD_DT = 1.0 / 300.0
-
-
-def fd_bar(P, s, bars, v, cond, fd1, fd2, h, dt):
-    """The bar of <x_bar, v> against FD(h), per robot: the truncation estimated from the differences alone, |FD(h) - FD(2h)| (three
-    times the h^2 term of FD(h)), plus the rounding of the quotient - each of its two losses is <c, y> with every entry of y within
-    plant_restatement.plant_step_mp's derived bar of the exact step (for a plain double evaluation: tests/test_plant_cpu.py; for the
-    device: tests/test_gpu_plant.py), so the quotient is off by at most sum |c_j| bar_j / h - plus the analytic side's own rounding,
-    4 EPS sum condsum_i |v_i| (four times what c_np leaves it, see the module docstring)."""
-    n = fd1.shape[0]
-    rounding = np.zeros(n)
-    for i in range(n):
-        ref = PR.plant_step_mp(P["mass"], P["Ib"], *(s[k][i] for k in AR.INPUTS), dt)
-        rounding[i] = sum((np.abs(bars[k][i]) * ref[k][1]).sum() for k in bars)
-    analytic = 4 * EPS * sum((cond[BAR_OF[k]] * np.abs(v[k])).sum(axis=1) for k in AR.INPUTS)
-    return np.abs(fd1 - fd2) + rounding / h + analytic
 
 
 @pytest.fixture(scope="module")

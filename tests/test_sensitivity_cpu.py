@@ -12,19 +12,11 @@ from quadruped_control_amd import workloads
 from tests import device_math_reference as DMR
 from tests import kkt_certificate_restatement as KR
 from tests import sensitivity_restatement as SR
+from tests.fd_support import N_FD, _check_kept, _kept, fd_batch, pinned_cases
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 EPS = 2.0 ** -52
-N_FD = 480
 B_KEYS = ("x", "xdot", "w", "x_d", "xdot_d", "w_d")
-
-
-def fd_batch(n=N_FD):
-    """config3's states with the 15 non-empty contact patterns in turn"""
-    b = workloads.config3(n=n)
-    pats = np.array([[(p >> l) & 1 for l in range(4)] for p in range(1, 16)], np.uint8)
-    b["stance"] = np.ascontiguousarray(pats[np.arange(n) % 15])
-    return b
 
 
 @pytest.fixture(scope="module")
@@ -48,20 +40,6 @@ def _oracle_at(P, b, d, h):
         bb[k] = b[k] + h * v
     F, st, _ = c_oracle.control_batch(P, bb)
     return F, st, KR.certificate(P, bb, F)["active"]
-
-
-def _kept(c, points):
-    """the keep rule: solved, no code 3 (flags 0), and the certificate's working set of the oracle's forces unchanged at every point"""
-    keep = (c["st0"] == 0) & (c["s"]["flags"] == 0)
-    for F, st, a in points:
-        keep &= (st == 0) & (a == c["s"]["active"]).all(axis=1)
-    return keep
-
-
-def _check_kept(c, keep):
-    assert keep.mean() >= 0.75, keep.mean()
-    pats = set((c["b"]["stance"][keep].astype(int) * [1, 2, 4, 8]).sum(axis=1).tolist())
-    assert pats == set(range(1, 16)), sorted(pats)
 
 
 def test_b_type_cotangents_against_oracle_differences(solved):
@@ -120,30 +98,6 @@ def test_feet_cotangent_against_oracle_differences(solved):
 
 
 # ------------------------------------------------------------------ 50 digits
-def pinned_cases():
-    """Hand-picked robots with forces placed exactly on faces: (name, P, batch of one, grf_body, expected codes of the four feet).
-    Foot 0 tied (fx = +mu fz, fz free), foot 1 pinned at fz = fzmax with fy = -mu fz, foot 2 interior, foot 3 swing or fz = fzmin."""
-    base = q.cheetah_params(mu=0.6)
-    rng = np.random.default_rng(17)
-    G = rng.normal(0.0, 1.0, (6, 6))
-    S_gen = np.asarray(base["S"], float).reshape(6, 6) + 0.2 * (G @ G.T)
-    G = rng.normal(0.0, 1.0, (12, 12))
-    W_dense = np.asarray(base["W"], float).reshape(12, 12) + 2e-6 * (G @ G.T)
-    cases = []
-    for name, P, swing in (("uniform", base, True), ("general-S-dense-W", dict(base, S=S_gen, W=W_dense), True),
-                           ("general-S-dense-W-all-stance", dict(base, S=S_gen, W=W_dense), False)):
-        mu, fzmin, fzmax = P["mu"], P["fzmin"], P["fzmax"]
-        b = workloads.slice_batch(workloads.config3(n=8), 5, 6)
-        b["stance"] = np.array([[1, 1, 1, 0 if swing else 1]], np.uint8)
-        fw = np.array([[mu * 40.0, 3.0, 40.0], [5.0, -mu * fzmax, fzmax], [2.0, -1.0, 30.0], [0.0, 0.0, 0.0] if swing else [1.0, 2.0, fzmin]])
-        R = b["Rwb"][0].reshape(3, 3)
-        grf = -(fw @ R).reshape(1, 12)  # grf_body = -R^T f (the round trip through R is not exact: the codes are asserted)
-        codes = [2, (1 << 2) | (2 << 4), 0, KR.SWING if swing else (1 << 4)]
-        cases.append((name, P, b, grf, codes))
-    name, P, b, grf, codes = cases[1]
-    b = workloads.with_joint_angles(b)
-    cases.append((name + "-joint_q", P, b, grf, codes))
-    return cases
 
 
 def test_restatement_against_50_digits():

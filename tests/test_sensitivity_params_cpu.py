@@ -13,13 +13,13 @@ from tests import device_math_reference as DMR
 from tests import kkt_certificate_restatement as KR
 from tests import sensitivity_params_restatement as PR
 from tests import sensitivity_restatement as SR
-from tests.test_sensitivity_cpu import N_FD, _check_kept, _kept, fd_batch, pinned_cases
+from tests.fd_support import GROUPS, N_FD, _check_kept, _kept, fd_batch, pinned_cases
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 EPS = 2.0 ** -52
 
-# per group: (the parameter set's changes, the relative step h, the least share of kept robots with a non-zero contribution or None).
-# h from a sweep on the oracle alone, h = 1e-2 ... 1e-7 of the parameters' own size (direction() scales d by them), the worst
+# fd_support.GROUPS, per group: (the parameter set's changes, the relative step h, the least share of kept robots with a non-zero
+# contribution or None).  h from a sweep on the oracle alone, h = 1e-2 ... 1e-7 of the parameters' own size (direction() scales d by them), the worst
 # |FD(h) - FD(2h)| / (|row| |d|) over the kept robots:
 #   gains   8e-12, 2e-11, 5e-10, 3e-9, 5e-8, 3e-7     linear in b: rounding only, growing as 1 / h           -> 1e-3 (kept 0.97)
 #   mass    9e-10, 5e-9, 1e-7, 2e-6, 8e-6, 9e-5       linear                                                 -> 1e-2 (kept 0.85)
@@ -31,8 +31,6 @@ EPS = 2.0 ** -52
 #   fzmin   5e-12, 2e-11, 7e-10, 9e-9, 4e-8, 1e-7     f0 is linear in the limit: rounding only               -> 1e-3
 #   fzmax   3e-11, 3e-10, 2e-9, 8e-9, 4e-7, 2e-7                                                             -> 1e-3
 # fzmin is raised to 25 N and fzmax lowered to 60 N for their own groups, so that feet actually sit on them.
-GROUPS = {"gains": ({}, 1e-3, None), "mass": ({}, 1e-2, None), "Ib": ({}, 1e-2, None), "S": ({}, 1e-3, None), "W_diag": ({}, 1e-3, None),
-          "W": ({}, 1e-3, None), "mu": ({}, 1e-4, 0.9), "fzmin": ({"fzmin": 25.0}, 1e-3, 0.4), "fzmax": ({"fzmax": 60.0}, 1e-3, 0.5)}
 
 
 def solve_fd_case(changes):
@@ -101,7 +99,7 @@ def quotient_check(c, d, h, F_at, rows, share):
 def test_parameter_cotangents_against_oracle_differences(fd_case, group):
     """<param_bar_row, d> against <grf_bar, (F(theta + h d) - F(theta - h d)) / 2h> of the C oracle run with the perturbed parameter
     sets, for one random direction d inside each parameter group (direction(): symmetric for Ib, S and W, a diagonal and a dense one
-    for W), 480 robots, every non-empty contact pattern 32 times, the keep rule of test_sensitivity_cpu (the working set the same at
+    for W), 480 robots, every non-empty contact pattern 32 times, the keep rule of fd_support (the working set the same at
     0, +-h, +-2h; share >= 0.75, all 15 patterns).  h per group: GROUPS above, from the sweep recorded there.  The bar is
     quotient_check's, made of the oracle's quotients alone.  Gains, mass, Ib and the limits are linear on the face (no truncation);
     S, W and mu have O(h^2).  Measured worst error / (|row| |d|) on the committed seeds: profiles/sensitivity_params.md."""
@@ -113,7 +111,7 @@ def test_parameter_cotangents_against_oracle_differences(fd_case, group):
 
 
 def test_restatement_against_50_digits():
-    """The float64 rows against param_cotangents_mp on pinned_cases() of test_sensitivity_cpu - a tied axis, a foot pinned at fzmax
+    """The float64 rows against param_cotangents_mp on pinned_cases() of fd_support - a tied axis, a foot pinned at fzmax
     with a tied y, a foot at fzmin, an interior foot, a swing foot; uniform weights and a general S with a dense W; feet from joint_q -
     both fed the float64 adjoint.  Bar per entry: 64 eps terms - the longest chain is about 60 roundings (the 12-term row of W z
     behind the 6-term row of S behind the 8 additions of A z behind the lever arms, then rho, mu's sum over four feet), each at most

@@ -11,17 +11,10 @@ from scipy.spatial.transform import Rotation
 import quadruped_control_amd as q
 from tests import sensitivity_restatement as SR
 from tests import sensitivity_rotation_restatement as RR
-from tests.test_sensitivity_cpu import N_FD, _check_kept, _kept, fd_batch
+from tests.fd_support import FD_H, N_FD, _check_kept, _kept, fd_batch, fd_directions
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 EPS = 2.0 ** -52
-FD_H = 1e-4  # the step the sweep below settled on; tests/test_gpu_sensitivity_rotation.py uses it too
-
-
-def fd_directions(n=N_FD):
-    """the committed directions: (delta, delta_d) [n, 3] tangent directions and (D, Dd) [n, 9] entrywise ones"""
-    rng = np.random.default_rng(8)
-    return rng.normal(0.0, 1.0, (n, 3)), rng.normal(0.0, 1.0, (n, 3)), rng.normal(0.0, 1.0, (n, 9)), rng.normal(0.0, 1.0, (n, 9))
 
 
 def rotate(b, delta, delta_d, h):
