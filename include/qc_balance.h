@@ -567,6 +567,45 @@ void qc_default_sensitivity_param(qc_sensitivity_param_io* io);
  * state array (Rwb, Rwb_d, x, xdot, w, x_d, xdot_d, w_d), neither feet nor joint_q, or n beyond one launch. */
 int qc_sensitivity_param_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_param_io* io, void* stream);
 
+/* The joint-angle cotangents of a fused tick (joint_q -> forward kinematics -> QP -> clamped J^T -> joint_tau): the two ends
+ * qc_sensitivity_batch leaves open, in one kernel.  Per robot and leg l, with q = joint_q_l, p the forward kinematics of q,
+ * J[r][c] = d p_r / d q_c its exact Jacobian (the matrix of the torque map), H_r = d^2 p_r / d q^2 and g = grf_body_l: the tick's
+ * torque is tau_raw = J^T g clamped by two compares to [tau_min, tau_max] of qc_set_kinematics, emitted for a stance leg of a robot
+ * with status 0 and 0 otherwise.  Given the optional cotangents joint_tau_bar, feet_bar, grf_bar_in and joint_q_bar_in (a missing
+ * one counts as zero):
+ *   the mask    m_c = 1 where !(tau_raw_c < tau_min) && !(tau_raw_c > tau_max) - equality passes, a NaN passes and propagates -,
+ *               m = 0 for a swing leg and for a robot with status != 0;  s = m o joint_tau_bar_l
+ *   grf_bar_l     = grf_bar_in_l + J s                       body frame: the cotangent on grf_body that qc_sensitivity_batch takes
+ *   joint_q_bar_l = joint_q_bar_in_l + (sum_r g_r H_r) s + J^T feet_bar_l
+ * The term J^T feet_bar_l is UNMASKED: a swing leg's feet_bar from qc_sensitivity_batch is zero already, and a caller's own loss on a
+ * foot position must pass.  The two typical calls: the torque half alone in front of qc_sensitivity_batch (joint_tau_bar, and the
+ * loss's direct cotangent on grf_body as grf_bar_in: grf_bar is the total that call takes), then the kinematics half behind it
+ * (its feet_bar, and the first call's joint_q_bar as joint_q_bar_in, in place).
+ * Of `in` the call reads joint_q and the contact mask, resolved as qc_certify_batch resolves it (`stance` bytes, else the phase rule
+ * on gait_phase as it is now, else all stance); none of the state arrays is read or required, `in` is never written.
+ * OUT OF SCOPE: the swing legs' PD torques - with swing references the joint_tau_bar of a swing leg is ignored -, commander mode, and
+ * the cotangents of the kinematic constants and of tau_min / tau_max.  Non-finite inputs propagate; nothing is clamped.
+ * Each output may be the SAME array as its `_in`: every input of a leg is read before any output of it is written, and a leg touches
+ * its own rows only.  All pointers are DEVICE pointers. */
+typedef struct qc_sensitivity_kin_io {
+  size_t struct_size;           /* = sizeof(qc_sensitivity_kin_io); checked                                          */
+  const double* grf_body;       /* [n][4][3] qc_batch_out.grf_body; required with joint_tau_bar                      */
+  const int32_t* status;        /* [n]       qc_batch_out.status;   required with joint_tau_bar                      */
+  const double* joint_tau_bar;  /* [n][4][3] cotangent on qc_batch_out.joint_tau; optional                           */
+  const double* feet_bar;       /* [n][4][3] cotangent on the body-frame feet (qc_sensitivity_io.feet_bar); optional */
+  const double* grf_bar_in;     /* [n][4][3] added to grf_bar; optional                                              */
+  const double* joint_q_bar_in; /* [n][4][3] added to joint_q_bar; optional                                          */
+  double* grf_bar;              /* [n][4][3] OUT, optional; needs joint_tau_bar                                      */
+  double* joint_q_bar;          /* [n][4][3] OUT, optional                                                           */
+} qc_sensitivity_kin_io;
+/* struct_size set, pointers NULL. */
+void qc_default_sensitivity_kin(qc_sensitivity_kin_io* io);
+/* Asynchronous on `stream`, no host synchronisation (graph-capturable); n == 0 launches nothing and returns QC_OK.  No buffer is
+ * kept on the handle.  QC_ERR_INVALID (message starting with "qc_sensitivity_kin_batch:", nothing launched) for a null handle, `in`
+ * or `io`, a wrong struct_size, no output requested, none of joint_tau_bar, feet_bar and joint_q_bar_in given, joint_tau_bar
+ * without grf_body or without status, grf_bar requested without joint_tau_bar, a missing joint_q, or n beyond one launch. */
+int qc_sensitivity_kin_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_kin_io* io, void* stream);
+
 /* Differentiating a rollout: the reverse pass of qc_plant_step_batch.  Given the state BEFORE a step (Rwb, x, xdot, w), the grf_body
  * and foot_world that step read, its dt, and cotangents on what it wrote (Rwb', x', xdot', w' and the optional feet'), this writes
  * the cotangents of Rwb, x, xdot, w, grf_body and foot_world: the transpose-Jacobian of the step exactly as the library evaluates it.

@@ -100,6 +100,11 @@ class QcSensitivityParamIo(C.Structure):
                 ("param_bar_rows", C.c_void_p), ("param_bar", C.c_void_p)]
 
 
+class QcSensitivityKinIo(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t)] + [(k, C.c_void_p) for k in
+                ("grf_body", "status", "joint_tau_bar", "feet_bar", "grf_bar_in", "joint_q_bar_in", "grf_bar", "joint_q_bar")]
+
+
 PARAM_COUNT = 211  # QC_PARAM_COUNT: the doubles of QcParams, in its order
 
 
@@ -114,7 +119,7 @@ EXPORTS = ("qc_create_abi", "qc_destroy", "qc_control_batch", "qc_control_batch_
            "qc_default_plant", "qc_plant_step_batch", "qc_default_leg_plant", "qc_leg_plant_step_batch",
            "qc_default_certify", "qc_certify_batch", "qc_default_sensitivity", "qc_sensitivity_batch",
            "qc_default_sensitivity_rot", "qc_sensitivity_rot_batch", "qc_default_plant_adjoint", "qc_plant_step_adjoint_batch",
-           "qc_default_sensitivity_param", "qc_sensitivity_param_batch")
+           "qc_default_sensitivity_param", "qc_sensitivity_param_batch", "qc_default_sensitivity_kin", "qc_sensitivity_kin_batch")
 
 _lib = None
 
@@ -205,6 +210,10 @@ def load():
     lib.qc_default_sensitivity_param.restype = None
     lib.qc_sensitivity_param_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcBatchIn), C.POINTER(QcSensitivityParamIo), C.c_void_p]
     lib.qc_sensitivity_param_batch.restype = C.c_int
+    lib.qc_default_sensitivity_kin.argtypes = [C.POINTER(QcSensitivityKinIo)]
+    lib.qc_default_sensitivity_kin.restype = None
+    lib.qc_sensitivity_kin_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcBatchIn), C.POINTER(QcSensitivityKinIo), C.c_void_p]
+    lib.qc_sensitivity_kin_batch.restype = C.c_int
     lib.qc_default_plant_adjoint.argtypes = [C.POINTER(QcPlantAdjointIo)]
     lib.qc_default_plant_adjoint.restype = None
     lib.qc_plant_step_adjoint_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcPlantAdjointIo), C.c_void_p]

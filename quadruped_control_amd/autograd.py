@@ -1,11 +1,14 @@
-"""torch.autograd for control_batch(), plant_step() and the closed loop of the two: BalanceController.control_batch_autograd(),
-plant_step_autograd() and rollout_autograd().
+"""torch.autograd for control_batch(), the fused stance tick, plant_step() and the closed loop of control_batch() and plant_step():
+BalanceController.control_batch_autograd(), fused_tick_autograd(), plant_step_autograd() and rollout_autograd().
 
 Forward is control_batch() itself; backward is the adjoint of the balance QP on the active face of the forces it returned
 (qc_sensitivity_batch) and, where a rotation requires grad, the rotation cotangents behind it (qc_sensitivity_rot_batch), and where
 the `params` leaf requires grad the parameter cotangents summed over the batch (qc_sensitivity_param_batch), all
 on the current stream, without host synchronisation.  The gradient is the one on the active face: valid while the working set
 holds; robots with bit 0 of the sensitivity flags have a one-sided derivative, robots with bit 1 NaN gradients.
+
+fused_tick_autograd() is control_batch(want_torques=True) on joint_q: its backward puts the reverse pass of the clamped J^T torque map
+in front of the same calls and that of the forward kinematics behind them (qc_sensitivity_kin_batch, twice).
 
 plant_step_autograd() is OUT OF PLACE - plant_step() on clones of the state - and its backward is one qc_plant_step_adjoint_batch call
 on the saved pre-step tensors; rollout_autograd() alternates the two and threads new tensors through."""
@@ -43,27 +46,37 @@ class _ControlBatch(torch.autograd.Function):
         batch = dict(ctx.rest, **{k: v for k, v in inputs.items() if v is not None})
         need = dict(zip(DIFFERENTIABLE, ctx.needs_input_grad[5:]))
         need_params = ctx.needs_input_grad[5 + len(DIFFERENTIABLE)]
-        rot = [k for k in _ROTATIONS if need[k]]
-        want = [k + "_bar" for k in DIFFERENTIABLE[2:] if need[k]]
-        if rot:
-            want += [k for k in ("b_bar", "feet_bar") if k not in want]
-        if need_params:
-            want.append("adjoint")
-        out = None
-        if ctx.flags is not None:  # the caller's tensor receives the flags; the other outputs are allocated as sensitivity_batch would
-            shape = lambda k: (grf_body.shape[0],) + _SENSITIVITY_OUTPUTS[k][0]
-            out = {k: torch.zeros(shape(k), dtype=torch.float64, device=grf_body.device) for k in want}
-            out["flags"] = ctx.flags
-            want.append("flags")
-        grf_bar = grf_bar.contiguous()
-        s = ctx.ctl.sensitivity_batch(batch, grf_body, grf_bar, want=tuple(want), act_tol=ctx.act_tol, out=out)
-        if rot:
-            s.update(ctx.ctl.sensitivity_rotation_batch(batch, grf_body, grf_bar, s["b_bar"], s["feet_bar"], want=tuple(k + "_bar" for k in rot)))
+        s, param_bar = _qp_backward(ctx.ctl, batch, grf_body, grf_bar.contiguous(), ctx.act_tol, ctx.flags, need, need_params)
         grads = [s[k + "_bar"].view_as(inputs[k]) if need[k] else None for k in DIFFERENTIABLE]
-        param_bar = None
-        if need_params:  # sum-only: no [n,211] rows are written
-            param_bar = ctx.ctl.sensitivity_params_batch(batch, grf_body, grf_bar, s["adjoint"], want=("param_bar",), act_tol=ctx.act_tol)["param_bar"]
         return (None, None, None, None, None, *grads, param_bar)
+
+
+def _qp_backward(ctl, batch, grf_body, grf_bar, act_tol, flags, need, need_params, feet_bar=False):
+    """The reverse pass of the solve that control_batch_autograd() and fused_tick_autograd() share: sensitivity_batch() asked for the
+    cotangents `need` (name -> bool over DIFFERENTIABLE) names - and feet_bar if `feet_bar` -, sensitivity_rotation_batch() behind it
+    where a rotation is among them, sensitivity_params_batch() in sum-only mode if need_params.  Returns (the dict of cotangents,
+    param_bar or None)."""
+    rot = [k for k in _ROTATIONS if need.get(k)]
+    want = [k + "_bar" for k in DIFFERENTIABLE[2:] if need.get(k)]
+    if feet_bar and "feet_bar" not in want:
+        want.append("feet_bar")
+    if rot:
+        want += [k for k in ("b_bar", "feet_bar") if k not in want]
+    if need_params:
+        want.append("adjoint")
+    out = None
+    if flags is not None:  # the caller's tensor receives the flags; the other outputs are allocated as sensitivity_batch would
+        shape = lambda k: (grf_body.shape[0],) + _SENSITIVITY_OUTPUTS[k][0]
+        out = {k: torch.zeros(shape(k), dtype=torch.float64, device=grf_body.device) for k in want}
+        out["flags"] = flags
+        want.append("flags")
+    s = ctl.sensitivity_batch(batch, grf_body, grf_bar, want=tuple(want), act_tol=act_tol, out=out)
+    if rot:
+        s.update(ctl.sensitivity_rotation_batch(batch, grf_body, grf_bar, s["b_bar"], s["feet_bar"], want=tuple(k + "_bar" for k in rot)))
+    param_bar = None
+    if need_params:  # sum-only: no [n,211] rows are written
+        param_bar = ctl.sensitivity_params_batch(batch, grf_body, grf_bar, s["adjoint"], want=("param_bar",), act_tol=act_tol)["param_bar"]
+    return s, param_bar
 
 
 def control_batch_autograd(ctl, batch, act_tol=1e-7, flags=None, params=None, **control_kwargs):
@@ -82,6 +95,70 @@ def control_batch_autograd(ctl, batch, act_tol=1e-7, flags=None, params=None, **
     tensors = [batch.get(k) for k in DIFFERENTIABLE]
     detached = {k: (v.detach() if isinstance(v, torch.Tensor) else v) for k, v in batch.items()}
     return _ControlBatch.apply(ctl, detached, float(act_tol), flags, control_kwargs, *tensors, params)
+
+
+# ------------------------------------------------------------------ the fused stance tick: joint_q -> FK -> QP -> clamped J^T -> joint_tau
+TICK_DIFFERENTIABLE = DIFFERENTIABLE[:-1] + ("joint_q",)
+_TICK_REFUSED = {"feet": "a batch with `feet` is control_batch_autograd()'s", "swing_pos": "the swing legs' PD torques are out of scope",
+                 "swing_state": "the swing legs' PD torques are out of scope", "gait_dt": "the gait clock writes gait_phase in place"}
+
+
+class _FusedTick(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ctl, batch, act_tol, flags, control_kwargs, *tensors):
+        *tensors, params = tensors  # (params is never read: the solve uses the handle's own parameters)
+        out = ctl.control_batch(batch, want_torques=True, **control_kwargs)
+        joint_tau, grf_body, status = out["joint_tau"], out["grf_body"], out["status"]
+        ctx.ctl, ctx.act_tol, ctx.flags = ctl, act_tol, flags
+        ctx.rest = {k: v for k, v in batch.items() if k not in TICK_DIFFERENTIABLE}
+        ctx.set_materialize_grads(False)  # an output the loss never reached arrives as None: a NULL cotangent, not an array of zeros
+        ctx.save_for_backward(grf_body, status, *tensors)
+        ctx.mark_non_differentiable(status)
+        return joint_tau, grf_body, status
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, tau_bar, grf_bar, _status_bar):
+        grf_body, status, *given = ctx.saved_tensors
+        inputs = dict(zip(TICK_DIFFERENTIABLE, given))
+        batch = dict(ctx.rest, **inputs)
+        need = dict(zip(TICK_DIFFERENTIABLE, ctx.needs_input_grad[5:]))
+        need_params = ctx.needs_input_grad[5 + len(TICK_DIFFERENTIABLE)]
+        if tau_bar is None and grf_bar is None:  # no output reached the loss: every gradient is zero
+            grads = [torch.zeros_like(inputs[k]) if need[k] else None for k in TICK_DIFFERENTIABLE]
+            return (None, None, None, None, None, *grads, torch.zeros(PARAM_COUNT, dtype=torch.float64, device=grf_body.device) if need_params else None)
+        ctl = ctx.ctl
+        grf_bar = None if grf_bar is None else grf_bar.contiguous()
+        q_bar = None
+        if tau_bar is not None:  # the torque half: the total cotangent on grf_body, and joint_q's through the torque map
+            k = ctl.sensitivity_kinematics_batch(batch, grf_body, status, joint_tau_bar=tau_bar.contiguous(), grf_bar_in=grf_bar,
+                                                 want=("grf_bar", "joint_q_bar") if need["joint_q"] else ("grf_bar",))
+            grf_bar, q_bar = k["grf_bar"].view_as(grf_body), k.get("joint_q_bar")
+        s, param_bar = _qp_backward(ctl, batch, grf_body, grf_bar, ctx.act_tol, ctx.flags, need, need_params, feet_bar=need["joint_q"])
+        if need["joint_q"]:  # the kinematics half, added in place
+            out = None if q_bar is None else {"joint_q_bar": q_bar}
+            s["joint_q_bar"] = ctl.sensitivity_kinematics_batch(batch, feet_bar=s["feet_bar"], joint_q_bar_in=q_bar, want=("joint_q_bar",), out=out)["joint_q_bar"]
+        grads = [s[k + "_bar"].view_as(inputs[k]) if need[k] else None for k in TICK_DIFFERENTIABLE]
+        return (None, None, None, None, None, *grads, param_bar)
+
+
+def fused_tick_autograd(ctl, batch, act_tol=1e-7, flags=None, params=None, **control_kwargs):
+    """BalanceController.fused_tick_autograd (see there): (joint_tau, grf_body, status) of control_batch(batch, want_torques=True,
+    **control_kwargs) for a batch with joint_q and no feet, differentiable in TICK_DIFFERENTIABLE and `params` through joint_tau,
+    grf_body or both."""
+    if params is not None and (params.dtype != torch.float64 or params.numel() != PARAM_COUNT or params.dim() != 1):
+        raise ValueError(f"params: need a float64 [{PARAM_COUNT}] tensor (BalanceController.parameter_tensor() makes one)")
+    for k, why in _TICK_REFUSED.items():
+        if batch.get(k) is not None:
+            raise ValueError(f"fused_tick_autograd: the batch carries {k} - {why}")
+    missing = [k for k in TICK_DIFFERENTIABLE if batch.get(k) is None]
+    if missing:
+        raise ValueError(f"fused_tick_autograd: the batch lacks {missing} (the fused stance tick reads joint_q and the eight state arrays)")
+    if flags is not None and (flags.dtype != torch.int32 or not flags.is_contiguous() or flags.numel() != batch["x"].shape[0]):
+        raise ValueError("flags: need a contiguous int32 [n] tensor")
+    tensors = [batch[k] for k in TICK_DIFFERENTIABLE]
+    detached = {k: (v.detach() if isinstance(v, torch.Tensor) else v) for k, v in batch.items()}
+    return _FusedTick.apply(ctl, detached, float(act_tol), flags, control_kwargs, *tensors, params)
 
 
 # the inputs of a plant step a gradient is produced for, in the order backward returns them; the step's outputs, in the order forward returns them

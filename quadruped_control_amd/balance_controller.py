@@ -808,6 +808,60 @@ class BalanceController:
         launch()
         return res
 
+    def plan_sensitivity_kinematics(self, batch, grf_body=None, status=None, joint_tau_bar=None, feet_bar=None, grf_bar_in=None,
+                                    joint_q_bar_in=None, want=("joint_q_bar",), out=None, stream=None):
+        """sensitivity_kinematics_batch() marshalled once: returns (launch, out), `launch()` being one qc_sensitivity_kin_batch call
+        (graph-capturable) on tensors that are read in place.  Planning launches nothing.  `out`: a dict of tensors to write into
+        instead of new ones (every name in `want`) - out["grf_bar"] may be grf_bar_in and out["joint_q_bar"] joint_q_bar_in.  A call
+        the library refuses raises ValueError with its message, from launch()."""
+        import torch
+
+        io = _lib.QcSensitivityKinIo()
+        self._lib.qc_default_sensitivity_kin(C.byref(io))
+        own = [("grf_body", grf_body, 12), ("joint_tau_bar", joint_tau_bar, 12), ("feet_bar", feet_bar, 12), ("grf_bar_in", grf_bar_in, 12),
+               ("joint_q_bar_in", joint_q_bar_in, 12)]
+        n, dev, bi = self._readonly_batch("sensitivity_kinematics", batch, _KINEMATICS_FIELDS, io, own)  # (no state array is read)
+        if _check_tensor("status", status, n, None, torch.int32, dev, False):
+            io.status = status.data_ptr()
+        res = _outputs("sensitivity_kinematics", _SENSITIVITY_KIN_OUTPUTS, want, out, n, dev, io)
+        args = (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
+        keep = (batch, grf_body, status, joint_tau_bar, feet_bar, grf_bar_in, joint_q_bar_in, res, bi, io)
+        return self._launcher("qc_sensitivity_kin_batch", args, keep, ValueError), res
+
+    def sensitivity_kinematics_batch(self, batch, grf_body=None, status=None, joint_tau_bar=None, feet_bar=None, grf_bar_in=None,
+                                     joint_q_bar_in=None, want=("joint_q_bar",), out=None, stream=None):
+        """The two ends of the fused tick's reverse pass (qc_sensitivity_kin_batch, include/qc_balance.h; INTEGRATION.md "Sensitivity
+        of a solved batch"): the cotangent of joint_q through the forward kinematics and the reverse pass of the clamped J^T torque
+        map, per leg.  `batch`: the one control_batch(want_torques=True) read - joint_q and the contact mask (stance, else the phase
+        rule on gait_phase as it is now, else all stance) are all that is read of it.  Inputs, each [n,12] or [n,4,3] and each
+        optional: `joint_tau_bar`, the cotangent on joint_tau (then `grf_body` and `status` int32 [n] as the solve wrote them are
+        needed too); `feet_bar`, the cotangent on the body-frame feet (sensitivity_batch()'s, or a loss's own); `grf_bar_in` and
+        `joint_q_bar_in`, added to the outputs.  `want`: "grf_bar" [n,4,3] = grf_bar_in + J (m o joint_tau_bar), the cotangent on
+        grf_body to hand to sensitivity_batch() (needs joint_tau_bar), and / or "joint_q_bar" [n,4,3].  m is 1 where the forward
+        torque passed through the clamp, 0 where it was clamped, for swing legs and for robots with status != 0; the feet_bar term
+        is unmasked.  Out of scope: the swing legs' PD torques (their joint_tau_bar is ignored), commander mode, the cotangents of
+        the kinematic constants and the torque limits.  Nothing of `batch` is written.  Asynchronous on `stream`, no synchronisation.
+        Returns the dict of device tensors; ValueError with the library's message for a call it refuses."""
+        launch, res = self.plan_sensitivity_kinematics(batch, grf_body, status, joint_tau_bar, feet_bar, grf_bar_in, joint_q_bar_in, want, out, stream)
+        launch()
+        return res
+
+    def fused_tick_autograd(self, batch, act_tol=1e-7, flags=None, params=None, **control_kwargs):
+        """The fused stance tick with a gradient: returns (joint_tau, grf_body, status) of control_batch(batch, want_torques=True,
+        **control_kwargs) for a batch that carries joint_q and no `feet`, joint_tau and grf_body carrying a grad_fn whenever joint_q,
+        one of Rwb, Rwb_d, x, xdot, w, x_d, xdot_d, w_d, or `params` requires grad (quadruped_control_amd/autograd.py).  A loss may
+        reach joint_tau, grf_body or both; an output it never reached costs nothing (a missing cotangent, not an array of zeros).
+        Backward, on the current stream without host synchronisation: sensitivity_kinematics_batch() on joint_tau's cotangent (the
+        torque half: the total cotangent on grf_body and the first part of joint_q's), sensitivity_batch() on that total, the
+        rotation and parameter calls exactly as control_batch_autograd() makes them, and sensitivity_kinematics_batch() again on
+        feet_bar (the kinematics half, added in place).  `act_tol`, `flags`, `params` and the validity of the gradient are
+        control_batch_autograd()'s: the active face of the QP - and here also the clamp mask of the torques as the forward pass took
+        it.  ValueError for a batch that carries `feet` (not this path: control_batch_autograd()), swing_pos or swing_state (the
+        swing legs' PD torques are out of scope) or gait_dt (the clock writes gait_phase in place).  There is no double backward."""
+        from .autograd import fused_tick_autograd
+
+        return fused_tick_autograd(self, batch, act_tol, flags, params=params, **control_kwargs)
+
     def control_batch_autograd(self, batch, act_tol=1e-7, flags=None, params=None, **control_kwargs):
         """control_batch() with a gradient: returns (grf_body, status), grf_body carrying a grad_fn whenever any of Rwb, Rwb_d, x,
         xdot, w, x_d, xdot_d, w_d, feet in `batch` requires grad (quadruped_control_amd/autograd.py).  Forward is exactly
@@ -918,11 +972,13 @@ _SENSITIVITY_OUTPUTS = {"adjoint": ((12,), "float64"), "b_bar": ((6,), "float64"
                         **{k: ((3,), "float64") for k in ("x_bar", "xdot_bar", "w_bar", "x_d_bar", "xdot_d_bar", "w_d_bar")}, "flags": ((), "int32")}
 _SENSITIVITY_ROT_OUTPUTS = {k: ((m,), "float64") for k, m in (("Rwb_bar", 9), ("Rwb_d_bar", 9), ("Rwb_rot_bar", 3), ("Rwb_d_rot_bar", 3))}
 _SENSITIVITY_PARAM_OUTPUTS = {"param_bar_rows": ((_lib.PARAM_COUNT,), "float64")}
+_SENSITIVITY_KIN_OUTPUTS = {"grf_bar": ((4, 3), "float64"), "joint_q_bar": ((4, 3), "float64")}
 _PLANT_ADJOINT_OUTPUTS = {k: ((m,), "float64") for k, m in (("Rwb_bar", 9), ("x_bar", 3), ("xdot_bar", 3), ("w_bar", 3), ("grf_bar", 12), ("foot_world_bar", 12))}
 _PLANT_COTANGENTS = {k: ((m,), "float64") for k, m in (("Rwb", 9), ("x", 3), ("xdot", 3), ("w", 3), ("feet", 12))}  # the step's outputs a cotangent may be given on
 # the batch a read-only call marshals (_readonly_batch): (name, trailing size, torch dtype name) - the state and the feet, and with the contact mask
 _STATE_FIELDS = tuple((k, m, "float64") for k, m in _IN_FIELDS + (("joint_q", 12),))
 _READONLY_FIELDS = _STATE_FIELDS + (("stance", 4, "uint8"), ("gait_phase", 4, "float64"), ("gait_duty", 1, "float64"))
+_KINEMATICS_FIELDS = (("joint_q", 12, "float64"),) + _READONLY_FIELDS[len(_STATE_FIELDS):]  # sensitivity_kinematics: joint_q and the contact mask
 
 
 # a parameter cotangent: name -> (slice of the 211 values, shape), in the order of the double members of qc_params

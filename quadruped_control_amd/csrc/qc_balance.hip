@@ -2360,6 +2360,23 @@ int qc_sensitivity_param_batch(qc_handle* h, size_t n, const qc_batch_in* in, co
   return QC_OK;
 }
 
+void qc_default_sensitivity_kin(qc_sensitivity_kin_io* io) { (void)zeroed(io); }
+
+int qc_sensitivity_kin_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_kin_io* io, void* stream) {
+  if (const int rc = qc::check_sensitivity_kin_args(h, n, in, io); rc != QC_OK || n == 0) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  // (of `in`: joint_q and the contact mask as it is now - no state array, nothing that advances or plans)
+  const qc::SensitivityKinArgs a{in->joint_q, in->stance, in->gait_phase, in->gait_duty, io->grf_body, io->status, io->joint_tau_bar, io->feet_bar,
+                                 io->grf_bar_in, io->joint_q_bar_in, io->grf_bar, io->joint_q_bar};
+  const bool tau = io->joint_tau_bar != nullptr, fk = io->feet_bar != nullptr;
+  void (*const fn)(const qc::DevParams*, long, qc::SensitivityKinArgs) =
+      tau ? (fk ? qc::sensitivity_kin_kernel<true, true> : qc::sensitivity_kin_kernel<true, false>)
+          : (fk ? qc::sensitivity_kin_kernel<false, true> : qc::sensitivity_kin_kernel<false, false>);
+  fn<<<dim3(qc::sensitivity_kin_blocks(n)), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)(4 * n), a);
+  QC_HIP(hipGetLastError());
+  return QC_OK;
+}
+
 // host-pointer variant.  Large batches: one device staging allocation, H2D copies, kernel, D2H copies, sync.
 // Small batches (n <= kPinnedMaxN; the reference's own use is one robot per controller tick): the records are packed
 // into a pinned, device-visible host buffer that the kernel reads and writes in place over PCIe - one launch and one

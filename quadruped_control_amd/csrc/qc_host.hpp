@@ -16,6 +16,7 @@
 #include "qc_sensitivity.hpp"
 #include "qc_sensitivity_rot.hpp"
 #include "qc_sensitivity_params.hpp"
+#include "qc_sensitivity_kin.hpp"
 
 namespace qc {
 
@@ -630,5 +631,24 @@ inline int check_sensitivity_param_args(const qc_handle* h, size_t n, const qc_b
 
 // workgroups of sensitivity_param_kernel for n robots: one wave each, capped at the handle's partial buffer
 inline unsigned sensitivity_param_blocks(size_t n) { return capped_blocks(n, SENSITIVITY_PARAM_BLOCK, SENSITIVITY_PARAM_MAX_BLOCKS); }
+
+// ---------------------------------------------------------------- qc_sensitivity_kin_batch
+// The argument check of the joint-angle cotangents: what is wrong with the call itself (message prefix "qc_sensitivity_kin_batch:").
+// The kernel reads joint_q and the contact mask of `in` and none of the state arrays: they are not asked for.
+inline int check_sensitivity_kin_args(const qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_kin_io* io) {
+  const char* who = "qc_sensitivity_kin_batch";
+  if (const int rc = check_io(who, h && in, io, "qc_sensitivity_kin_io", "qc_default_sensitivity_kin"); rc != QC_OK) return rc;
+  const auto bad = [who](const char* what) { return fail(QC_ERR_INVALID, std::string(who) + what); };
+  if (!io->grf_bar && !io->joint_q_bar) return bad(": no output requested (grf_bar and joint_q_bar are both NULL)");
+  if (!io->joint_tau_bar && !io->feet_bar && !io->joint_q_bar_in) return bad(": no cotangent given (joint_tau_bar, feet_bar and joint_q_bar_in are all NULL)");
+  if (io->joint_tau_bar && (!io->grf_body || !io->status)) return bad(": joint_tau_bar needs grf_body and status");
+  if (io->grf_bar && !io->joint_tau_bar) return bad(": grf_bar needs joint_tau_bar");
+  if (n == 0) return QC_OK;
+  if (!in->joint_q) return bad(": joint_q is required");
+  return check_one_launch(who, n, SENSITIVITY_BLOCK);
+}
+
+// workgroups of sensitivity_kin_kernel for n robots: one wave of 16 robots' legs each, capped
+inline unsigned sensitivity_kin_blocks(size_t n) { return capped_blocks(4 * n, SENSITIVITY_BLOCK, SENSITIVITY_MAX_BLOCKS); }
 
 }  // namespace qc

@@ -1,0 +1,211 @@
+"""TEST INFRASTRUCTURE - numpy restatement of the joint-angle cotangents (csrc/qc_sensitivity_kin.hpp, qc_sensitivity_kin_batch),
+and the same definitions for single legs at 50 digits.
+
+Per robot and leg l, with q = joint_q_l, p = FK(q), J[r][c] = d p_r / d q_c, H[r][c][k] = d^2 p_r / d q_c d q_k, g = grf_body_l:
+  tau_raw = J^T g;  m_c = stance and status == 0 and not (tau_raw_c < tau_min) and not (tau_raw_c > tau_max);  s = m o joint_tau_bar_l
+  grf_bar_l        = grf_bar_in_l + J s
+  joint_q_bar_l[c] = joint_q_bar_in_l[c] + sum_r g_r sum_k H[r][c][k] s_k + sum_r J[r][c] feet_bar_l[r]        (the last term unmasked)
+
+Written independently of the device code: the forward kinematics (kinematics.cpp:81-103) is stated ONCE, as a sum of monomials
+  sign * link * f0(q0) * f1(q1) * f23(q1 + q2),   f in {1, sin, cos},
+and J and H are made from it by differentiating the monomials (sin -> cos, cos -> -sin, the chain rule on q1 + q2) - no entry of
+either is typed in.  The same monomials evaluate on numpy arrays and on mpmath numbers, with the sines and cosines of q1 + q2 taken
+of the sum itself (the device uses the angle-addition formulas).  Every value comes with its MAGNITUDE, the sum of the absolute
+values of its monomials: kin_cotangents() returns, per output entry, `terms` - the sum of the magnitudes of its contributions, each
+evaluated with the absolute values of all its factors -, the scale rounding errors are measured against."""
+from __future__ import annotations
+
+import mpmath as mp
+import numpy as np
+
+from tests import device_math_reference as DMR
+from tests.kkt_certificate_restatement import DEFAULT_DUTY, distance, magnitude  # noqa: F401 - the one definition of each
+from tests.leg_plant_restatement import contact_mask
+
+EPS = 2.0 ** -52
+OUTPUTS = ("grf_bar", "joint_q_bar")
+ONE, SIN, COS = 0, 1, 2
+# the forward kinematics: p_r - hip_r as monomials (sign, link index, (f0, f1, f23))
+FK = (((+1, 1, (ONE, SIN, ONE)), (+1, 2, (ONE, ONE, SIN))),
+      ((+1, 0, (COS, ONE, ONE)), (-1, 1, (SIN, COS, ONE)), (-1, 2, (SIN, ONE, COS))),
+      ((+1, 0, (SIN, ONE, ONE)), (+1, 1, (COS, COS, ONE)), (+1, 2, (COS, ONE, COS))))
+SLOTS_OF = ((0,), (1, 2), (2,))  # q_c enters the angle of these factors (q1 through q1 and through q1 + q2)
+
+
+def differentiate(monomials, c):
+    """d / d q_c of a sum of monomials, as monomials"""
+    out = []
+    for sign, link, f in monomials:
+        for slot in SLOTS_OF[c]:
+            if f[slot] == ONE:
+                continue
+            g = list(f)
+            g[slot] = COS if f[slot] == SIN else SIN
+            out.append((sign if f[slot] == SIN else -sign, link, tuple(g)))
+    return out
+
+
+JAC = tuple(tuple(differentiate(FK[r], c) for c in range(3)) for r in range(3))
+HESS = tuple(tuple(tuple(differentiate(JAC[r][c], k) for k in range(3)) for c in range(3)) for r in range(3))
+
+
+def evaluate(monomials, links, trig):
+    """(value, magnitude) of a sum of monomials: links[k] and trig[slot] = (1, sin, cos) are numbers or arrays of one shape"""
+    value, mag = 0 * trig[0][SIN], 0 * abs(trig[0][SIN])
+    for sign, link, f in monomials:
+        term = links[link] * trig[0][f[0]] * trig[1][f[1]] * trig[2][f[2]]
+        value = value + sign * term
+        mag = mag + abs(term)
+    return value, mag
+
+
+def _trig_np(q):
+    one = np.ones_like(q[..., 0])
+    return [(one, np.sin(a), np.cos(a)) for a in (q[..., 0], q[..., 1], q[..., 1] + q[..., 2])]
+
+
+def geometry(joint_q, hip=DMR.HIP, links=DMR.LINKS):
+    """dict(p [n,4,3], J [n,4,3,3], H [n,4,3,3,3], aJ, aH: the magnitudes) of the four legs of n robots, float64"""
+    q = np.asarray(joint_q, np.float64).reshape(-1, 4, 3)
+    n = q.shape[0]
+    trig = _trig_np(q)
+    L = [np.broadcast_to(np.asarray(links, np.float64).reshape(4, 3)[:, k], (n, 4)) for k in range(3)]
+    p, J, H = np.zeros((n, 4, 3)), np.zeros((n, 4, 3, 3)), np.zeros((n, 4, 3, 3, 3))
+    aJ, aH = np.zeros_like(J), np.zeros_like(H)
+    for r in range(3):
+        p[..., r] = evaluate(FK[r], L, trig)[0] + np.asarray(hip, np.float64).reshape(4, 3)[None, :, r]
+        for c in range(3):
+            J[..., r, c], aJ[..., r, c] = evaluate(JAC[r][c], L, trig)
+            for k in range(3):
+                H[..., r, c, k], aH[..., r, c, k] = evaluate(HESS[r][c][k], L, trig)
+    return dict(p=p, J=J, H=H, aJ=aJ, aH=aH)
+
+
+def _opt(a, n):
+    return np.zeros((n, 4, 3)) if a is None else np.asarray(a, np.float64).reshape(n, 4, 3)
+
+
+def kin_cotangents(b, grf_body, status, tau_min, tau_max, joint_tau_bar=None, feet_bar=None, grf_bar_in=None, joint_q_bar_in=None,
+                   default_duty=DEFAULT_DUTY):
+    """dict: grf_bar, joint_q_bar [n,4,3]; tau_raw [n,4,3]; emit [n,4] (stance and status 0); mask [n,4,3]; torque_part [n,4,3] of
+    joint_q_bar; terms (dict output -> [n,4,3] magnitude sums)."""
+    with np.errstate(invalid="ignore"):
+        geo = geometry(b["joint_q"])
+        n = geo["p"].shape[0]
+        J, H, aJ, aH = geo["J"], geo["H"], geo["aJ"], geo["aH"]
+        g = _opt(grf_body, n)
+        tb, fb, gin, qin = _opt(joint_tau_bar, n), _opt(feet_bar, n), _opt(grf_bar_in, n), _opt(joint_q_bar_in, n)
+        st = np.zeros(n, np.int32) if status is None else np.asarray(status).reshape(n)
+        tau_raw = np.einsum("nlrc,nlr->nlc", J, g)
+        emit = contact_mask(n, b.get("stance"), b.get("gait_phase"), b.get("gait_duty"), default_duty) & (st == 0)[:, None]
+        mask = emit[..., None] & ~(tau_raw < tau_min) & ~(tau_raw > tau_max)
+        s = np.where(mask, tb, 0.0)
+        Js = np.einsum("nlrc,nlc->nlr", J, s)
+        torque = np.einsum("nlr,nlrck,nlk->nlc", g, H, s)
+        JTf = np.einsum("nlrc,nlr->nlc", J, fb)
+        a = np.abs
+        terms = dict(grf_bar=a(gin) + np.einsum("nlrc,nlc->nlr", aJ, a(s)),
+                     joint_q_bar=a(qin) + np.einsum("nlr,nlrck,nlk->nlc", a(g), aH, a(s)) + np.einsum("nlrc,nlr->nlc", aJ, a(fb)))
+        return dict(grf_bar=gin + Js, joint_q_bar=qin + torque + JTf, tau_raw=tau_raw, emit=emit, mask=mask, torque_part=torque, terms=terms)
+
+
+# ------------------------------------------------------------------ the inputs the CPU and the GPU test share
+# Torque limits for the tests, picked on the raw stance torques J^T g of case() (quartiles about -2.3 and 9 N m, extremes -32 and
+# 38 N m at these sizes): about half of the stance components are clamped, a quarter at each end.
+TAU_MIN, TAU_MAX = -2.5, 9.0
+FAILED_EVERY = 7  # robots 5, 12, 19, ... of case() carry status 2
+
+
+def case(n, source):
+    """(batch with joint_q, grf_body [n,12], status int32 [n], cotangents dict) - solved_batch_support.inputs' placed forces and
+    contact pattern i % 16 over workloads.with_joint_angles; source "stance": the stance bytes, "phase": the phase rule.  Robots
+    5, 12, 19, ... are failed through the status array alone.  The cotangents are committed normal draws."""
+    from quadruped_control_amd import workloads
+    from tests import solved_batch_support as SB
+
+    if source == "stance":
+        b, grf = SB.inputs(n, "feet")
+        b = workloads.with_joint_angles(b)
+    else:
+        b, grf = SB.inputs(n, "joint_q")
+    assert "feet" not in b and ("stance" in b) == (source == "stance") and ("gait_phase" in b) == (source == "phase")
+    status = np.zeros(n, np.int32)
+    status[5::FAILED_EVERY] = 2
+    rng = np.random.default_rng(9000 + n)
+    cot = {k: np.ascontiguousarray(rng.normal(0.0, s, (n, 12))) for k, s in
+           (("joint_tau_bar", 1.0), ("feet_bar", 30.0), ("grf_bar_in", 1.0), ("joint_q_bar_in", 5.0))}
+    return {k: np.ascontiguousarray(v) for k, v in b.items()}, grf, status, cot
+
+
+FD_TAU_MIN, FD_TAU_MAX = -4.0, 12.0  # the limits of the end-to-end finite-difference tests: both ends clamp some of fd_case's torques
+
+
+def fd_case(n=480):
+    """(batch with joint_q, directions): fd_support.fd_batch's states and contact patterns with joint angles in place of the feet;
+    committed directions dq [n,12] on joint_q and dx [n,3] on x, and the loss's coefficients c_tau, c_g [n,12]."""
+    from quadruped_control_amd import workloads
+    from tests.fd_support import fd_batch
+
+    b = workloads.with_joint_angles(fd_batch(n))
+    rng = np.random.default_rng(12)
+    return b, dict(dq=rng.normal(0.0, 1.0, (n, 12)), dx=rng.normal(0.0, 1.0, (n, 3)), c_tau=rng.normal(0.0, 1.0, (n, 12)), c_g=rng.normal(0.0, 1.0, (n, 12)))
+
+
+# ------------------------------------------------------------------ 50 digits, one leg
+def lift(v):
+    return DMR.mpf(float(v))
+
+
+def geometry_mp(leg, q, hip=DMR.HIP, links=DMR.LINKS):
+    """(p [3], J [3][3], H [3][3][3]) of one leg at 50 digits; q: three mpmath numbers (call inside mp.workdps(DMR.DPS))"""
+    L = [lift(v) for v in np.asarray(links, np.float64).reshape(4, 3)[leg]]
+    trig = [(mp.mpf(1), mp.sin(a), mp.cos(a)) for a in (q[0], q[1], q[1] + q[2])]
+    p = [evaluate(FK[r], L, trig)[0] + lift(np.asarray(hip, np.float64).reshape(4, 3)[leg, r]) for r in range(3)]
+    J = [[evaluate(JAC[r][c], L, trig)[0] for c in range(3)] for r in range(3)]
+    H = [[[evaluate(HESS[r][c][k], L, trig)[0] for k in range(3)] for c in range(3)] for r in range(3)]
+    return p, J, H
+
+
+def clamp_mp(t, lo, hi):
+    """the forward pass's two compares"""
+    return lo if t < lo else (hi if t > hi else t)
+
+
+def loss_mp(leg, q, g, emit, tau_min, tau_max, tau_bar, feet_bar, grf_bar_in, joint_q_bar_in):
+    """<tau_bar, tau> + <feet_bar, p> + <grf_bar_in, g> + <joint_q_bar_in, q> of one leg at 50 digits: the function whose gradient
+    in (q, g) the outputs are; tau = clamp(J(q)^T g) for an emitting leg, 0 otherwise.  Returns (loss, the pass-through mask)."""
+    p, J, _ = geometry_mp(leg, q)
+    raw = [sum(J[r][c] * g[r] for r in range(3)) for c in range(3)]
+    tau = [clamp_mp(raw[c], tau_min, tau_max) if emit else mp.mpf(0) for c in range(3)]
+    mask = [bool(emit) and not raw[c] < tau_min and not raw[c] > tau_max for c in range(3)]
+    total = sum(tau_bar[c] * tau[c] + feet_bar[c] * p[c] + grf_bar_in[c] * g[c] + joint_q_bar_in[c] * q[c] for c in range(3))
+    return total, mask
+
+
+def kin_cotangents_mp(leg, q, g, mask, tau_bar, feet_bar, grf_bar_in, joint_q_bar_in):
+    """(grf_bar [3], joint_q_bar [3]) of one leg at 50 digits on the exact doubles, for the pass-through mask given"""
+    with mp.workdps(DMR.DPS):
+        q, g, tb, fb, gin, qin = ([lift(v) for v in a] for a in (q, g, tau_bar, feet_bar, grf_bar_in, joint_q_bar_in))
+        _, J, H = geometry_mp(leg, q)
+        s = [tb[c] if mask[c] else mp.mpf(0) for c in range(3)]
+        grf_bar = [gin[r] + sum(J[r][c] * s[c] for c in range(3)) for r in range(3)]
+        q_bar = [qin[c] + sum(g[r] * sum(H[r][c][k] * s[k] for k in range(3)) for r in range(3)) + sum(J[r][c] * fb[r] for r in range(3))
+                 for c in range(3)]
+        return grf_bar, q_bar
+
+
+def worst_against_50_digits(b, grf_body, ref, values, joint_tau_bar, feet_bar, grf_bar_in, joint_q_bar_in, rows=None):
+    """Over the legs `rows` ((robot, leg) pairs; None: all): the worst |values - 50-digit value| of each output, relative to EPS terms
+    (`per_terms`) and relative to the leg's largest 50-digit entry (`per_magnitude`); `values`: dict output -> [n,4,3] (the
+    restatement's own, or the device's), `ref`: kin_cotangents() of the same inputs (its mask and terms are used)."""
+    n = ref["grf_bar"].shape[0]
+    q, g = np.asarray(b["joint_q"], np.float64).reshape(n, 4, 3), _opt(grf_body, n)
+    tb, fb, gin, qin = _opt(joint_tau_bar, n), _opt(feet_bar, n), _opt(grf_bar_in, n), _opt(joint_q_bar_in, n)
+    per_terms, per_mag = {k: 0.0 for k in OUTPUTS}, {k: 0.0 for k in OUTPUTS}
+    for i, l in (rows if rows is not None else [(i, l) for i in range(n) for l in range(4)]):
+        exact = dict(zip(OUTPUTS, kin_cotangents_mp(l, q[i, l], g[i, l], ref["mask"][i, l], tb[i, l], fb[i, l], gin[i, l], qin[i, l])))
+        for k in OUTPUTS:
+            d = distance(values[k].reshape(n, 4, 3)[i, l], exact[k])
+            per_terms[k] = max(per_terms[k], float((d / np.maximum(EPS * ref["terms"][k][i, l], 1e-300)).max()))
+            per_mag[k] = max(per_mag[k], float(d.max()) / max(magnitude(exact[k]), 1e-300))
+    return per_terms, per_mag
