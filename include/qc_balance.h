@@ -652,6 +652,59 @@ void qc_default_plant_adjoint(qc_plant_adjoint_io* io);
  * foot_world, n beyond one launch, or a handle whose mass or Ib qc_plant_step_batch refuses. */
 int qc_plant_step_adjoint_batch(qc_handle* h, size_t n, const qc_plant_adjoint_io* io, void* stream);
 
+/* Differentiating the closed loop around the tick: the reverse pass of qc_leg_plant_step_batch.  Given the state BEFORE a step (Rwb,
+ * x, xdot, w, joint_q, joint_qdot), the joint_tau and the contact inputs (stance / gait_phase / gait_duty / cmd_state, resolved as
+ * that call resolves them) the step read, its dt and leg_inertia, and cotangents on what it wrote, this writes the cotangents of Rwb,
+ * x, xdot, w, joint_q, joint_qdot and joint_tau: the transpose-Jacobian of the step exactly as the library evaluates it.  Nothing is
+ * saved by the forward call; the step is recomputed.  Rwb's cotangents are ENTRYWISE (qc_plant_adjoint_io's convention).  Per leg,
+ * with q', qd' the step's joint outputs and qn = q' of a stance leg:
+ *   stance leg:  qn_bar = q'_bar + qd'_bar / dt,  q_bar = -qd'_bar / dt  (wrapPI has slope 1);  the inverse kinematics inverts the
+ *                forward kinematics inside reach, so p'_bar = J(qn)^-T qn_bar;  p' = Rn^T (c - x'):  Rn_bar += (c - x') p'_bar^T,
+ *                c_bar = Rn p'_bar,  x'_bar -= c_bar;  then qc_plant_step_adjoint_batch's body block to Rwb_bar, x_bar, xdot_bar,
+ *                w_bar and the cotangents fs_bar, tau_bar of the net force and moment;  f = -Rwb g at r = Rwb FK(q), c = x + r:
+ *                f_bar = fs_bar + tau_bar x r,  r_bar = f x tau_bar + c_bar,  x_bar += c_bar,  g_bar = -Rwb^T f_bar,
+ *                Rwb_bar += r_bar FK(q)^T - f_bar g^T,  q_bar += J(q)^T Rwb^T r_bar;  g = J^-T tau:  joint_tau_bar = J^-1 g_bar,
+ *                q_bar -= (sum_r g_r d^2 FK_r / dq^2) joint_tau_bar;  joint_qdot_bar = 0 (the step does not read it)
+ *   swing leg:   s = qd'_bar + dt q'_bar;  q_bar = q'_bar,  joint_qdot_bar = s,  joint_tau_bar = dt s / leg_inertia.
+ * UNDEFINED GRADIENTS: `flags` bit l - J(q_l) of stance leg l is outside the closed-form band (the step took the pseudo-inverse);
+ * bit 4 + l - the step's inverse kinematics reported leg l out of reach, or J(qn_l) is outside the band.  A robot with any bit set
+ * gets NaN in every output row.  Other non-finite inputs propagate; nothing is clamped.
+ * NOT produced: a cotangent through the optional foot_world output, the cotangents of mass, Ib, leg_inertia, dt and the kinematic
+ * constants; the contact mask is held (no gradient in the phases).  Outputs are written, not accumulated.  Each robot's inputs are
+ * all read before any of its outputs is written, and a robot touches its own rows only: an output may be the SAME array as an input
+ * cotangent of the same layout (joint_q_bar over joint_q_next_bar, x_bar over x_next_bar, ...).  The inputs are never written.
+ * All pointers are DEVICE pointers. */
+typedef struct qc_leg_plant_adjoint_io {
+  size_t struct_size;               /* = sizeof(qc_leg_plant_adjoint_io); checked                                        */
+  const double *Rwb, *x, *xdot, *w; /* [n][9], [n][3], [n][3], [n][3]: the state BEFORE the step                         */
+  const double *joint_q, *joint_qdot; /* [n][4][3] before the step (joint_qdot's values are not read: the step is linear
+                                       in a swing leg's and ignores a stance leg's)                                      */
+  const double* joint_tau;          /* [n][4][3] the torques the step read                                               */
+  const uint8_t* stance;            /* [n][4] optional: the contact inputs of the forward call                           */
+  const double* gait_phase;         /* [n][4] optional                                                                   */
+  const double* gait_duty;          /* [n] optional                                                                      */
+  const qc_commander_state* cmd_state; /* [n] optional                                                                   */
+  const double* Rwb_next_bar;       /* [n][9]    cotangents on the step's outputs: each optional (NULL = zero),          */
+  const double* x_next_bar;         /* [n][3]    at least one given                                                      */
+  const double* xdot_next_bar;      /* [n][3]                                                                            */
+  const double* w_next_bar;         /* [n][3]                                                                            */
+  const double* joint_q_next_bar;   /* [n][4][3]                                                                         */
+  const double* joint_qdot_next_bar; /* [n][4][3]                                                                        */
+  double* Rwb_bar;                  /* [n][9]    outputs: each optional, at least one given (flags counts)               */
+  double *x_bar, *xdot_bar, *w_bar; /* [n][3] each                                                                       */
+  double *joint_q_bar, *joint_qdot_bar, *joint_tau_bar; /* [n][4][3] each                                                */
+  int32_t* flags;                   /* [n]: bit l singular J(q_l), bit 4 + l out of reach or singular J(qn_l)            */
+  double leg_inertia[3];            /* kg m^2 (hip, thigh, calf), finite and > 0: the step's                             */
+  double dt;                        /* seconds, finite, > 0: the step's                                                  */
+} qc_leg_plant_adjoint_io;
+/* struct_size set, pointers NULL, dt = 1/300, leg_inertia = 0 (the caller must give the step's). */
+void qc_default_leg_plant_adjoint(qc_leg_plant_adjoint_io* io);
+/* Asynchronous on `stream`, no host synchronisation (graph-capturable); n == 0 launches nothing and returns QC_OK.
+ * QC_ERR_INVALID (message starting with "qc_leg_plant_step_adjoint_batch:", nothing launched) for a null handle or `io`, a wrong
+ * struct_size, a dt or a leg_inertia entry that is not finite and > 0, no input cotangent at all, no output at all, a missing Rwb,
+ * x, xdot, w, joint_q, joint_qdot or joint_tau, n beyond one launch, or a handle whose mass or Ib qc_plant_step_batch refuses. */
+int qc_leg_plant_step_adjoint_batch(qc_handle* h, size_t n, const qc_leg_plant_adjoint_io* io, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -74,6 +74,14 @@ class QcLegPlantIo(C.Structure):
                  "foot_world", "flags")] + [("leg_inertia", C.c_double * 3), ("dt", C.c_double)]
 
 
+class QcLegPlantAdjointIo(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t)] + [(k, C.c_void_p) for k in
+                ("Rwb", "x", "xdot", "w", "joint_q", "joint_qdot", "joint_tau", "stance", "gait_phase", "gait_duty", "cmd_state",
+                 "Rwb_next_bar", "x_next_bar", "xdot_next_bar", "w_next_bar", "joint_q_next_bar", "joint_qdot_next_bar",
+                 "Rwb_bar", "x_bar", "xdot_bar", "w_bar", "joint_q_bar", "joint_qdot_bar", "joint_tau_bar", "flags")] + [
+                ("leg_inertia", C.c_double * 3), ("dt", C.c_double)]
+
+
 class QcCertifySummary(C.Structure):
     _fields_ = [("n_fail", C.c_int64), ("n_nonfinite", C.c_int64), ("n_swing_nonzero", C.c_int64), ("worst_primal", C.c_double),
                 ("worst_stationarity", C.c_double), ("arg_primal", C.c_int64), ("arg_stationarity", C.c_int64)]
@@ -119,7 +127,8 @@ EXPORTS = ("qc_create_abi", "qc_destroy", "qc_control_batch", "qc_control_batch_
            "qc_default_plant", "qc_plant_step_batch", "qc_default_leg_plant", "qc_leg_plant_step_batch",
            "qc_default_certify", "qc_certify_batch", "qc_default_sensitivity", "qc_sensitivity_batch",
            "qc_default_sensitivity_rot", "qc_sensitivity_rot_batch", "qc_default_plant_adjoint", "qc_plant_step_adjoint_batch",
-           "qc_default_sensitivity_param", "qc_sensitivity_param_batch", "qc_default_sensitivity_kin", "qc_sensitivity_kin_batch")
+           "qc_default_sensitivity_param", "qc_sensitivity_param_batch", "qc_default_sensitivity_kin", "qc_sensitivity_kin_batch",
+           "qc_default_leg_plant_adjoint", "qc_leg_plant_step_adjoint_batch")
 
 _lib = None
 
@@ -218,6 +227,10 @@ def load():
     lib.qc_default_plant_adjoint.restype = None
     lib.qc_plant_step_adjoint_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcPlantAdjointIo), C.c_void_p]
     lib.qc_plant_step_adjoint_batch.restype = C.c_int
+    lib.qc_default_leg_plant_adjoint.argtypes = [C.POINTER(QcLegPlantAdjointIo)]
+    lib.qc_default_leg_plant_adjoint.restype = None
+    lib.qc_leg_plant_step_adjoint_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcLegPlantAdjointIo), C.c_void_p]
+    lib.qc_leg_plant_step_adjoint_batch.restype = C.c_int
     # the structures above are hand-written mirrors of the header: a library built from another revision is refused here,
     # before any of them crosses the boundary
     rc = lib.qc_check_abi(ABI_VERSION, C.sizeof(QcParams), C.sizeof(QcBatchIn), C.sizeof(QcBatchOut))

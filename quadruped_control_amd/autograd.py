@@ -1,5 +1,6 @@
-"""torch.autograd for control_batch(), the fused stance tick, plant_step() and the closed loop of control_batch() and plant_step():
-BalanceController.control_batch_autograd(), fused_tick_autograd(), plant_step_autograd() and rollout_autograd().
+"""torch.autograd for control_batch(), the fused stance tick, plant_step(), leg_plant_step() and the two closed loops:
+BalanceController.control_batch_autograd(), fused_tick_autograd(), plant_step_autograd(), rollout_autograd(), leg_plant_step_autograd()
+and rollout_tick_autograd().
 
 Forward is control_batch() itself; backward is the adjoint of the balance QP on the active face of the forces it returned
 (qc_sensitivity_batch) and, where a rotation requires grad, the rotation cotangents behind it (qc_sensitivity_rot_batch), and where
@@ -11,7 +12,9 @@ fused_tick_autograd() is control_batch(want_torques=True) on joint_q: its backwa
 in front of the same calls and that of the forward kinematics behind them (qc_sensitivity_kin_batch, twice).
 
 plant_step_autograd() is OUT OF PLACE - plant_step() on clones of the state - and its backward is one qc_plant_step_adjoint_batch call
-on the saved pre-step tensors; rollout_autograd() alternates the two and threads new tensors through."""
+on the saved pre-step tensors; rollout_autograd() alternates the two and threads new tensors through.  leg_plant_step_autograd() and
+rollout_tick_autograd() are the same pair around the tick: leg_plant_step() on clones, one qc_leg_plant_step_adjoint_batch call
+backward, alternated with fused_tick_autograd()."""
 from __future__ import annotations
 
 import torch
@@ -226,3 +229,83 @@ def rollout_autograd(ctl, batch, foot_world, steps, dt, act_tol=1e-7, warm=True,
     if warm and active is not None:
         out["active_set"] = active
     return {k: cur[k] for k in ("Rwb", "x", "xdot", "w", "feet")}, out
+
+
+# ------------------------------------------------------------------ the legged plant and the closed loop around the tick
+LEG_PLANT_DIFFERENTIABLE = ("Rwb", "x", "xdot", "w", "joint_q", "joint_qdot", "joint_tau")  # also the step's outputs, less joint_tau
+
+
+class _LegPlantStep(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ctl, dt, leg_inertia, contact, flags, *tensors):
+        *state, joint_tau = tensors
+        new = {k: t.clone() for k, t in zip(LEG_PLANT_DIFFERENTIABLE, state)}
+        ctl.leg_plant_step(new, joint_tau, dt, leg_inertia, flags=flags, **contact)
+        ctx.ctl, ctx.dt, ctx.leg_inertia, ctx.contact = ctl, dt, leg_inertia, contact
+        ctx.set_materialize_grads(False)  # an output the loss never reached arrives as None: a NULL cotangent, not an array of zeros
+        ctx.save_for_backward(*tensors)
+        return tuple(new[k] for k in LEG_PLANT_DIFFERENTIABLE[:-1])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *bars):
+        *state, joint_tau = ctx.saved_tensors
+        need = dict(zip(LEG_PLANT_DIFFERENTIABLE, ctx.needs_input_grad[5:]))
+        cot = {k: b.contiguous() for k, b in zip(LEG_PLANT_DIFFERENTIABLE, bars) if b is not None}
+        if not cot:  # no output reached the loss: every gradient is zero
+            grads = [torch.zeros_like(t) if need[k] else None for k, t in zip(LEG_PLANT_DIFFERENTIABLE, ctx.saved_tensors)]
+            return (None, None, None, None, None, *grads)
+        want = tuple(k + "_bar" for k in LEG_PLANT_DIFFERENTIABLE if need[k])
+        s = ctx.ctl.leg_plant_step_adjoint(dict(zip(LEG_PLANT_DIFFERENTIABLE, state)), joint_tau, ctx.dt, ctx.leg_inertia, cot, want=want, **ctx.contact)
+        grads = [s[k + "_bar"].view_as(t) if need[k] else None for k, t in zip(LEG_PLANT_DIFFERENTIABLE, ctx.saved_tensors)]
+        return (None, None, None, None, None, *grads)
+
+
+def leg_plant_step_autograd(ctl, state, joint_tau, dt, leg_inertia, stance=None, gait_phase=None, gait_duty=None, flags=None):
+    """BalanceController.leg_plant_step_autograd (see there): (Rwb', x', xdot', w', joint_q', joint_qdot') of one legged plant step as
+    NEW tensors, `state` left as it is, with a grad_fn whenever one of LEG_PLANT_DIFFERENTIABLE requires grad."""
+    contact = {k: (v.detach() if v is not None else None) for k, v in (("stance", stance), ("gait_phase", gait_phase), ("gait_duty", gait_duty))}
+    tensors = [state[k] for k in LEG_PLANT_DIFFERENTIABLE[:-1]] + [joint_tau]
+    return _LegPlantStep.apply(ctl, float(dt), leg_inertia, contact, flags, *tensors)
+
+
+_ROLLOUT_TICK_REFUSED = {"gait_dt": "the gait clock writes gait_phase in place; the contact mask is held over the rollout",
+                         "swing_pos": "the swing legs' PD torques are out of scope", "swing_state": "the swing legs' PD torques are out of scope",
+                         "feet": "the tick reads joint_q (rollout_autograd() steps the bare rigid body on `feet`)"}
+
+
+def rollout_tick_autograd(ctl, batch, steps, dt, leg_inertia, act_tol=1e-7, warm=True, params=None):
+    """BalanceController.rollout_tick_autograd (see there): `steps` times fused_tick_autograd() then leg_plant_step_autograd(), out of
+    place.  The gradient is the one on the active face of every solve, at every tick's clamp mask and off the plant's flagged legs;
+    memory grows with `steps`."""
+    for k, why in _ROLLOUT_TICK_REFUSED.items():
+        if batch.get(k) is not None:
+            raise ValueError(f"rollout_tick_autograd: the batch carries {k} - {why}")
+    if batch.get("joint_q") is None or batch.get("joint_qdot") is None:
+        raise ValueError("rollout_tick_autograd: the batch carries joint_q and joint_qdot (rollout_autograd() steps the bare rigid body)")
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError("rollout_tick_autograd: steps must be >= 0")
+    names = LEG_PLANT_DIFFERENTIABLE[:-1]
+    cur = dict(batch)
+    contact = {k: batch.get(k) for k in ("stance", "gait_phase", "gait_duty")}
+    out, active = {}, None
+    n, dev = batch["x"].shape[0], batch["x"].device
+    flags = torch.zeros((n,), dtype=torch.int32, device=dev) if steps else None
+    for _ in range(steps):
+        # the tick, as rollout_tick(batch, None, ...) plans it: an all-stance control_batch() takes no joint_qdot
+        res = {"grf_body": torch.zeros((n, 12), dtype=torch.float64, device=dev), "status": torch.full((n,), -1, dtype=torch.int32, device=dev),
+               "joint_tau": torch.zeros((n, 12), dtype=torch.float64, device=dev)}
+        kwargs = dict(out=res)
+        if warm:  # this step's own working-set word; the next solve starts from it (detached: an int32)
+            res["active_set"] = torch.zeros((n,), dtype=torch.int32, device=dev)
+            kwargs.update(warm=active, want_active_set=True)
+            active = res["active_set"]
+        tick_in = {k: v for k, v in cur.items() if k != "joint_qdot"}
+        tau, grf, status = fused_tick_autograd(ctl, tick_in, act_tol, params=params, **kwargs)
+        new = leg_plant_step_autograd(ctl, cur, tau, dt, leg_inertia, flags=flags, **contact)
+        cur = dict(cur, **dict(zip(names, new)))
+        out = {"joint_tau": tau, "grf_body": grf, "status": status, "flags": flags}
+    if warm and active is not None:
+        out["active_set"] = active
+    return {k: cur[k] for k in names}, out

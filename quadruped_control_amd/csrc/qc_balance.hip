@@ -2297,6 +2297,22 @@ int qc_leg_plant_step_batch(qc_handle* h, size_t n, const qc_leg_plant_io* io, v
   return QC_OK;
 }
 
+void qc_default_leg_plant_adjoint(qc_leg_plant_adjoint_io* io) {
+  if (!zeroed(io)) return;  // (leg_inertia 0, as qc_default_leg_plant leaves it)
+  io->dt = 1.0 / 300.0;  // qc_default_leg_plant's
+}
+
+int qc_leg_plant_step_adjoint_batch(qc_handle* h, size_t n, const qc_leg_plant_adjoint_io* io, void* stream) {
+  if (const int rc = qc::check_leg_plant_adjoint_args(h, n, io); rc != QC_OK || n == 0) return rc;
+  qc::LegPlantAdjointArgs a;
+  if (const int rc = qc::leg_plant_adjoint_constants(h->dp.mass, h->dp.Ib, io, a); rc != QC_OK) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  const unsigned blocks = (unsigned)((n + qc::LEG_PLANT_BLOCK - 1) / qc::LEG_PLANT_BLOCK);
+  qc::leg_plant_step_adjoint_kernel<<<dim3(blocks), dim3(qc::LEG_PLANT_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, a);
+  QC_HIP(hipGetLastError());
+  return QC_OK;
+}
+
 void qc_default_certify(qc_certify_io* io) {
   if (!zeroed(io)) return;
   io->act_tol = 1e-7;  // the defaults of tests/kkt_batch.py: kkt_batch's act_tol, assert_kkt's bars

@@ -12,6 +12,7 @@
 #include "qc_plant.hpp"
 #include "qc_plant_adjoint.hpp"
 #include "qc_leg_plant.hpp"
+#include "qc_leg_plant_adjoint.hpp"
 #include "qc_certify.hpp"
 #include "qc_sensitivity.hpp"
 #include "qc_sensitivity_rot.hpp"
@@ -564,6 +565,35 @@ inline int leg_plant_constants(double mass, const double* Ib, const qc_leg_plant
   a.Rwb = io->Rwb; a.x = io->x; a.xdot = io->xdot; a.w = io->w; a.joint_q = io->joint_q; a.joint_qdot = io->joint_qdot; a.joint_tau = io->joint_tau;
   a.stance = io->stance; a.gait_phase = io->gait_phase; a.gait_duty = io->gait_duty; a.cmd_state = reinterpret_cast<const CmdState*>(io->cmd_state);
   a.foot_world = io->foot_world; a.flags = io->flags;
+  return QC_OK;
+}
+
+// ---------------------------------------------------------------- qc_leg_plant_step_adjoint_batch
+// What is wrong with the call itself; the handle's mass and Ib are judged by leg_plant_adjoint_constants, through the plant's own checks.
+inline int check_leg_plant_adjoint_args(const qc_handle* h, size_t n, const qc_leg_plant_adjoint_io* io) {
+  const char* who = "qc_leg_plant_step_adjoint_batch";
+  if (const int rc = check_io(who, h != nullptr, io, "qc_leg_plant_adjoint_io", "qc_default_leg_plant_adjoint"); rc != QC_OK) return rc;
+  const char* own = nullptr;
+  if (!io->Rwb_next_bar && !io->x_next_bar && !io->xdot_next_bar && !io->w_next_bar && !io->joint_q_next_bar && !io->joint_qdot_next_bar)
+    own = ": no input cotangent given (Rwb_next_bar, x_next_bar, xdot_next_bar, w_next_bar, joint_q_next_bar, joint_qdot_next_bar are all NULL)";
+  else if (!io->Rwb_bar && !io->x_bar && !io->xdot_bar && !io->w_bar && !io->joint_q_bar && !io->joint_qdot_bar && !io->joint_tau_bar && !io->flags)
+    own = ": no output requested (Rwb_bar, x_bar, xdot_bar, w_bar, joint_q_bar, joint_qdot_bar, joint_tau_bar, flags are all NULL)";
+  for (int k = 0; k < 3; k++)
+    if (!std::isfinite(io->leg_inertia[k]) || !(io->leg_inertia[k] > 0.0))
+      own = ": leg_inertia (hip, thigh, calf) must be finite and > 0; qc_default_leg_plant_adjoint leaves it at 0, the caller gives the step's";
+  return check_plant_io(who, n, io, own, io->joint_q && io->joint_qdot && io->joint_tau, ": joint_q, joint_qdot and joint_tau are required", LEG_PLANT_BLOCK);
+}
+
+// the kernel's arguments: the body's constants (body_constants, under this entry point's name), the call's leg inertia and its arrays
+inline int leg_plant_adjoint_constants(double mass, const double* Ib, const qc_leg_plant_adjoint_io* io, LegPlantAdjointArgs& a) {
+  if (const int rc = body_constants("qc_leg_plant_step_adjoint_batch", mass, Ib, io->dt, a); rc != QC_OK) return rc;
+  for (int k = 0; k < 3; k++) a.leg_inertia[k] = io->leg_inertia[k];
+  a.Rwb = io->Rwb; a.x = io->x; a.xdot = io->xdot; a.w = io->w; a.joint_q = io->joint_q; a.joint_qdot = io->joint_qdot; a.joint_tau = io->joint_tau;
+  a.stance = io->stance; a.gait_phase = io->gait_phase; a.gait_duty = io->gait_duty; a.cmd_state = reinterpret_cast<const CmdState*>(io->cmd_state);
+  a.Rwb_next_bar = io->Rwb_next_bar; a.x_next_bar = io->x_next_bar; a.xdot_next_bar = io->xdot_next_bar; a.w_next_bar = io->w_next_bar;
+  a.joint_q_next_bar = io->joint_q_next_bar; a.joint_qdot_next_bar = io->joint_qdot_next_bar;
+  a.Rwb_bar = io->Rwb_bar; a.x_bar = io->x_bar; a.xdot_bar = io->xdot_bar; a.w_bar = io->w_bar;
+  a.joint_q_bar = io->joint_q_bar; a.joint_qdot_bar = io->joint_qdot_bar; a.joint_tau_bar = io->joint_tau_bar; a.flags = io->flags;
   return QC_OK;
 }
 
