@@ -705,6 +705,57 @@ void qc_default_leg_plant_adjoint(qc_leg_plant_adjoint_io* io);
  * x, xdot, w, joint_q, joint_qdot or joint_tau, n beyond one launch, or a handle whose mass or Ib qc_plant_step_batch refuses. */
 int qc_leg_plant_step_adjoint_batch(qc_handle* h, size_t n, const qc_leg_plant_adjoint_io* io, void* stream);
 
+/* Differentiating the tick through a gait: the reverse pass of the SWING legs' PD torques, which qc_sensitivity_kin_batch leaves out.
+ * With swing references (swing_pos, swing_vel) the tick commands, for every swing leg l and whatever the QP's status,
+ *   p_b = Rwb^T pos_l - x (sic),  v_b = Rwb^T vel_l,  q_ref = IK(p_b),  qd = J(q_ref)^-1 v_b,
+ *   tau_raw = kp o e + kd o (qd - joint_qdot_l) + kff,  e = wrapPI(wrap2PI(q_ref) - wrap2PI(joint_q_l)),
+ * clamped by two compares to [tau_min, tau_max] (qc_set_kinematics holds the gains and the limits).  Given joint_tau_bar, the
+ * cotangent on qc_batch_out.joint_tau, this writes per swing leg - tau_raw evaluated by the tick's own device function, so the
+ * clamp mask is the forward pass's bit for bit -
+ *   m_c = 1 where !(tau_raw_c < tau_min) && !(tau_raw_c > tau_max),  s = m o joint_tau_bar_l
+ *   joint_q_bar_l = joint_q_bar_in_l - kp o s,  joint_qdot_bar_l = -kd o s          (the wrapped error has slope +1 in q_ref, -1 in q)
+ *   gain_bar_l = (s o e, s o (qd - joint_qdot_l), s)                                nine numbers: kp, kd, kff
+ *   g = J(q_ref)^-T (kd o s),  q_ref_bar = kp o s - (sum_r g_r d^2 FK_r / dq^2 (q_ref)) qd,  p_b_bar = J(q_ref)^-T q_ref_bar
+ *                                                                                   (inside reach the IK inverts the FK)
+ *   swing_pos_bar_l = Rwb p_b_bar,  swing_vel_bar_l = Rwb g
+ * and per robot, summed over its swing legs in a fixed order,
+ *   Rwb_bar[r][i] = Rwb_bar_in[r][i] + sum_l (pos_l,r p_b_bar_i + vel_l,r g_i)      ENTRYWISE, row-major: qc_sensitivity_rot_io's
+ *   x_bar = x_bar_in - sum_l p_b_bar                                                (the body-frame subtraction as written)
+ * A STANCE leg contributes nothing: its rows of the per-leg outputs are zero (joint_q_bar: joint_q_bar_in).  A missing `_in` counts
+ * as zero.  Of `in` the call reads Rwb, x, joint_q, joint_qdot, swing_pos, swing_vel and the contact mask, resolved as
+ * qc_sensitivity_kin_batch resolves it (`stance` bytes, else the phase rule on gait_phase as it is now, else all stance); `in` is
+ * never written.
+ * UNDEFINED GRADIENTS: `flags` bit l - swing leg l's reference is outside the smooth domain of the chain: the knee cosine d >= 1
+ * (clamped) or d < -1, y^2 + z^2 - l1^2 < 0 (clamped), a target that is not finite, or det J(q_ref) outside the closed-form band
+ * (the tick took the pseudo-inverse).  A flagged leg has NaN in its rows of the per-leg outputs and in the robot's Rwb_bar and
+ * x_bar, whatever the mask.  Other non-finite inputs propagate.
+ * NOT produced: the cotangents of the kinematic constants and of tau_min / tau_max; anything through swing_state's planner or the
+ * gait clock (both refused); commander mode.
+ * Each output may be the SAME array as its `_in`: every input of a robot is read before any of its outputs is written.  All
+ * pointers are DEVICE pointers. */
+typedef struct qc_sensitivity_swing_io {
+  size_t struct_size;            /* = sizeof(qc_sensitivity_swing_io); checked                        */
+  const double* joint_tau_bar;   /* [n][4][3] cotangent on qc_batch_out.joint_tau; required           */
+  const double* joint_q_bar_in;  /* [n][4][3] added to joint_q_bar; optional                          */
+  const double* Rwb_bar_in;      /* [n][9]    added to Rwb_bar; optional                              */
+  const double* x_bar_in;        /* [n][3]    added to x_bar; optional                                */
+  double* swing_pos_bar;         /* [n][4][3] OUT: each optional, at least one given (flags counts)   */
+  double* swing_vel_bar;         /* [n][4][3]                                                         */
+  double* joint_q_bar;           /* [n][4][3]                                                         */
+  double* joint_qdot_bar;        /* [n][4][3]                                                         */
+  double* gain_bar;              /* [n][4][9] kp, kd, kff of every leg                                */
+  double* Rwb_bar;               /* [n][9]    entrywise, row-major                                    */
+  double* x_bar;                 /* [n][3]                                                            */
+  int32_t* flags;                /* [n]: bit l - swing leg l has no gradient                          */
+} qc_sensitivity_swing_io;
+/* struct_size set, pointers NULL. */
+void qc_default_sensitivity_swing(qc_sensitivity_swing_io* io);
+/* Asynchronous on `stream`, no host synchronisation (graph-capturable); n == 0 launches nothing and returns QC_OK.  No buffer is
+ * kept on the handle.  QC_ERR_INVALID (message starting with "qc_sensitivity_swing_batch:", nothing launched) for a null handle,
+ * `in` or `io`, a wrong struct_size, a swing_state or a gait_dt in `in`, no output requested, a missing joint_tau_bar, a missing
+ * Rwb, x, joint_q, joint_qdot, swing_pos or swing_vel, or n beyond one launch. */
+int qc_sensitivity_swing_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_swing_io* io, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

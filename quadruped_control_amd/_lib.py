@@ -113,6 +113,12 @@ class QcSensitivityKinIo(C.Structure):
                 ("grf_body", "status", "joint_tau_bar", "feet_bar", "grf_bar_in", "joint_q_bar_in", "grf_bar", "joint_q_bar")]
 
 
+class QcSensitivitySwingIo(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t)] + [(k, C.c_void_p) for k in
+                ("joint_tau_bar", "joint_q_bar_in", "Rwb_bar_in", "x_bar_in", "swing_pos_bar", "swing_vel_bar", "joint_q_bar", "joint_qdot_bar",
+                 "gain_bar", "Rwb_bar", "x_bar", "flags")]
+
+
 PARAM_COUNT = 211  # QC_PARAM_COUNT: the doubles of QcParams, in its order
 
 
@@ -128,7 +134,7 @@ EXPORTS = ("qc_create_abi", "qc_destroy", "qc_control_batch", "qc_control_batch_
            "qc_default_certify", "qc_certify_batch", "qc_default_sensitivity", "qc_sensitivity_batch",
            "qc_default_sensitivity_rot", "qc_sensitivity_rot_batch", "qc_default_plant_adjoint", "qc_plant_step_adjoint_batch",
            "qc_default_sensitivity_param", "qc_sensitivity_param_batch", "qc_default_sensitivity_kin", "qc_sensitivity_kin_batch",
-           "qc_default_leg_plant_adjoint", "qc_leg_plant_step_adjoint_batch")
+           "qc_default_leg_plant_adjoint", "qc_leg_plant_step_adjoint_batch", "qc_default_sensitivity_swing", "qc_sensitivity_swing_batch")
 
 _lib = None
 
@@ -231,6 +237,10 @@ def load():
     lib.qc_default_leg_plant_adjoint.restype = None
     lib.qc_leg_plant_step_adjoint_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcLegPlantAdjointIo), C.c_void_p]
     lib.qc_leg_plant_step_adjoint_batch.restype = C.c_int
+    lib.qc_default_sensitivity_swing.argtypes = [C.POINTER(QcSensitivitySwingIo)]
+    lib.qc_default_sensitivity_swing.restype = None
+    lib.qc_sensitivity_swing_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcBatchIn), C.POINTER(QcSensitivitySwingIo), C.c_void_p]
+    lib.qc_sensitivity_swing_batch.restype = C.c_int
     # the structures above are hand-written mirrors of the header: a library built from another revision is refused here,
     # before any of them crosses the boundary
     rc = lib.qc_check_abi(ABI_VERSION, C.sizeof(QcParams), C.sizeof(QcBatchIn), C.sizeof(QcBatchOut))

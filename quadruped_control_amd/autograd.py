@@ -14,7 +14,11 @@ in front of the same calls and that of the forward kinematics behind them (qc_se
 plant_step_autograd() is OUT OF PLACE - plant_step() on clones of the state - and its backward is one qc_plant_step_adjoint_batch call
 on the saved pre-step tensors; rollout_autograd() alternates the two and threads new tensors through.  leg_plant_step_autograd() and
 rollout_tick_autograd() are the same pair around the tick: leg_plant_step() on clones, one qc_leg_plant_step_adjoint_batch call
-backward, alternated with fused_tick_autograd()."""
+backward, alternated with fused_tick_autograd().
+
+tick_autograd() is control_batch(want_torques=True) with swing references (swing_pos, swing_vel): its backward is the fused stance
+tick's, then the reverse pass of the swing legs' PD torques (qc_sensitivity_swing_batch) added in place; rollout_tick_autograd() uses
+it for a batch that carries the references."""
 from __future__ import annotations
 
 import torch
@@ -106,6 +110,23 @@ _TICK_REFUSED = {"feet": "a batch with `feet` is control_batch_autograd()'s", "s
                  "swing_state": "the swing legs' PD torques are out of scope", "gait_dt": "the gait clock writes gait_phase in place"}
 
 
+def _stance_backward(ctl, batch, grf_body, status, tau_bar, grf_bar, act_tol, flags, need, need_params):
+    """The reverse pass of the stance legs that fused_tick_autograd() and tick_autograd() share, for cotangents tau_bar and grf_bar of
+    which at least one is there: the torque half of sensitivity_kinematics_batch(), _qp_backward(), the kinematics half.  Returns (the
+    dict of cotangents, param_bar or None)."""
+    grf_bar = None if grf_bar is None else grf_bar.contiguous()
+    q_bar = None
+    if tau_bar is not None:  # the torque half: the total cotangent on grf_body, and joint_q's through the torque map
+        k = ctl.sensitivity_kinematics_batch(batch, grf_body, status, joint_tau_bar=tau_bar.contiguous(), grf_bar_in=grf_bar,
+                                             want=("grf_bar", "joint_q_bar") if need["joint_q"] else ("grf_bar",))
+        grf_bar, q_bar = k["grf_bar"].view_as(grf_body), k.get("joint_q_bar")
+    s, param_bar = _qp_backward(ctl, batch, grf_body, grf_bar, act_tol, flags, need, need_params, feet_bar=need["joint_q"])
+    if need["joint_q"]:  # the kinematics half, added in place
+        out = None if q_bar is None else {"joint_q_bar": q_bar}
+        s["joint_q_bar"] = ctl.sensitivity_kinematics_batch(batch, feet_bar=s["feet_bar"], joint_q_bar_in=q_bar, want=("joint_q_bar",), out=out)["joint_q_bar"]
+    return s, param_bar
+
+
 class _FusedTick(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ctl, batch, act_tol, flags, control_kwargs, *tensors):
@@ -130,17 +151,7 @@ class _FusedTick(torch.autograd.Function):
         if tau_bar is None and grf_bar is None:  # no output reached the loss: every gradient is zero
             grads = [torch.zeros_like(inputs[k]) if need[k] else None for k in TICK_DIFFERENTIABLE]
             return (None, None, None, None, None, *grads, torch.zeros(PARAM_COUNT, dtype=torch.float64, device=grf_body.device) if need_params else None)
-        ctl = ctx.ctl
-        grf_bar = None if grf_bar is None else grf_bar.contiguous()
-        q_bar = None
-        if tau_bar is not None:  # the torque half: the total cotangent on grf_body, and joint_q's through the torque map
-            k = ctl.sensitivity_kinematics_batch(batch, grf_body, status, joint_tau_bar=tau_bar.contiguous(), grf_bar_in=grf_bar,
-                                                 want=("grf_bar", "joint_q_bar") if need["joint_q"] else ("grf_bar",))
-            grf_bar, q_bar = k["grf_bar"].view_as(grf_body), k.get("joint_q_bar")
-        s, param_bar = _qp_backward(ctl, batch, grf_body, grf_bar, ctx.act_tol, ctx.flags, need, need_params, feet_bar=need["joint_q"])
-        if need["joint_q"]:  # the kinematics half, added in place
-            out = None if q_bar is None else {"joint_q_bar": q_bar}
-            s["joint_q_bar"] = ctl.sensitivity_kinematics_batch(batch, feet_bar=s["feet_bar"], joint_q_bar_in=q_bar, want=("joint_q_bar",), out=out)["joint_q_bar"]
+        s, param_bar = _stance_backward(ctx.ctl, batch, grf_body, status, tau_bar, grf_bar, ctx.act_tol, ctx.flags, need, need_params)
         grads = [s[k + "_bar"].view_as(inputs[k]) if need[k] else None for k in TICK_DIFFERENTIABLE]
         return (None, None, None, None, None, *grads, param_bar)
 
@@ -162,6 +173,79 @@ def fused_tick_autograd(ctl, batch, act_tol=1e-7, flags=None, params=None, **con
     tensors = [batch[k] for k in TICK_DIFFERENTIABLE]
     detached = {k: (v.detach() if isinstance(v, torch.Tensor) else v) for k, v in batch.items()}
     return _FusedTick.apply(ctl, detached, float(act_tol), flags, control_kwargs, *tensors, params)
+
+
+# ------------------------------------------------------------------ the tick through a gait: the fused stance tick and the swing legs' PD torques
+TICK_SWING_DIFFERENTIABLE = TICK_DIFFERENTIABLE + ("joint_qdot", "swing_pos", "swing_vel")
+_TICK_SWING_REFUSED = {"feet": "a batch with `feet` is control_batch_autograd()'s", "swing_state": "the planner's references are out of scope",
+                       "gait_dt": "the gait clock writes gait_phase in place"}
+_SWING_IN_PLACE = ("joint_q", "Rwb", "x")  # the cotangents the swing kernel adds to in place, through its `_in` arrays
+JOINT_GAIN_COUNT = 9  # kp, kd, kff of the joint controller
+
+
+class _Tick(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ctl, batch, act_tol, flags, control_kwargs, *tensors):
+        *tensors, params, joint_gains = tensors  # (neither is ever read: the tick uses the handle's own parameters and gains)
+        out = ctl.control_batch(batch, want_torques=True, **control_kwargs)
+        joint_tau, grf_body, status = out["joint_tau"], out["grf_body"], out["status"]
+        ctx.ctl, ctx.act_tol, ctx.flags = ctl, act_tol, flags
+        ctx.rest = {k: v for k, v in batch.items() if k not in TICK_SWING_DIFFERENTIABLE}
+        ctx.set_materialize_grads(False)  # an output the loss never reached arrives as None: a NULL cotangent, not an array of zeros
+        ctx.save_for_backward(grf_body, status, *tensors)
+        ctx.mark_non_differentiable(status)
+        return joint_tau, grf_body, status
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, tau_bar, grf_bar, _status_bar):
+        grf_body, status, *given = ctx.saved_tensors
+        names = TICK_SWING_DIFFERENTIABLE
+        inputs = dict(zip(names, given))
+        batch = dict(ctx.rest, **inputs)
+        need = dict(zip(names, ctx.needs_input_grad[5:]))
+        need_params, need_gains = ctx.needs_input_grad[5 + len(names):]
+        dev = grf_body.device
+        zeros = lambda m: torch.zeros(m, dtype=torch.float64, device=dev)
+        if tau_bar is None and grf_bar is None:  # no output reached the loss: every gradient is zero
+            grads = [torch.zeros_like(inputs[k]) if need[k] else None for k in names]
+            return (None, None, None, None, None, *grads, zeros(PARAM_COUNT) if need_params else None, zeros(JOINT_GAIN_COUNT) if need_gains else None)
+        ctl = ctx.ctl
+        s, param_bar = _stance_backward(ctl, batch, grf_body, status, tau_bar, grf_bar, ctx.act_tol, ctx.flags, need, need_params)
+        n = grf_body.shape[0]
+        want = [k + "_bar" for k in ("swing_pos", "swing_vel", "joint_q", "joint_qdot", "Rwb", "x") if need[k]] + (["gain_bar"] if need_gains else [])
+        if tau_bar is None:  # a loss on grf_body alone never reaches a swing leg's torque
+            s.update({k: zeros((n, 4, 9) if k == "gain_bar" else (n, 12)) for k in want if k not in s})
+        elif want:  # the swing legs last, added in place to what the stance chain left
+            in_place = {k + "_bar": s[k + "_bar"] for k in _SWING_IN_PLACE if need[k]}
+            out = dict(in_place, **{k: zeros((n, 4, 9) if k == "gain_bar" else (n, 4, 3)) for k in want if k not in in_place})
+            s.update(ctl.sensitivity_swing_batch(batch, tau_bar.contiguous(), want=tuple(want), out=out,
+                                                 **{k + "_in": t for k, t in in_place.items()}))
+        grads = [s[k + "_bar"].view_as(inputs[k]) if need[k] else None for k in names]
+        return (None, None, None, None, None, *grads, param_bar, s["gain_bar"].sum(dim=(0, 1)) if need_gains else None)
+
+
+def tick_autograd(ctl, batch, act_tol=1e-7, flags=None, params=None, joint_gains=None, **control_kwargs):
+    """BalanceController.tick_autograd (see there): (joint_tau, grf_body, status) of control_batch(batch, want_torques=True,
+    **control_kwargs) for a batch with joint_q, joint_qdot, swing_pos, swing_vel and a contact mask, differentiable in
+    TICK_SWING_DIFFERENTIABLE, `params` and `joint_gains`.  `joint_gains` ([9]: kp, kd, kff) is never read by forward - the handle's
+    own gains are used -; its gradient is sensitivity_swing_batch()'s gain_bar summed over robots and legs."""
+    if params is not None and (params.dtype != torch.float64 or params.numel() != PARAM_COUNT or params.dim() != 1):
+        raise ValueError(f"params: need a float64 [{PARAM_COUNT}] tensor (BalanceController.parameter_tensor() makes one)")
+    if joint_gains is not None and (joint_gains.dtype != torch.float64 or joint_gains.numel() != JOINT_GAIN_COUNT or joint_gains.dim() != 1):
+        raise ValueError(f"joint_gains: need a float64 [{JOINT_GAIN_COUNT}] tensor (kp, kd, kff of the joint controller)")
+    for k, why in _TICK_SWING_REFUSED.items():
+        if batch.get(k) is not None:
+            raise ValueError(f"tick_autograd: the batch carries {k} - {why}")
+    missing = [k for k in TICK_SWING_DIFFERENTIABLE if batch.get(k) is None]
+    if missing:
+        raise ValueError(f"tick_autograd: the batch lacks {missing} (the tick with swing references reads joint_q, joint_qdot, swing_pos, "
+                         "swing_vel and the eight state arrays)")
+    if flags is not None and (flags.dtype != torch.int32 or not flags.is_contiguous() or flags.numel() != batch["x"].shape[0]):
+        raise ValueError("flags: need a contiguous int32 [n] tensor")
+    tensors = [batch[k] for k in TICK_SWING_DIFFERENTIABLE]
+    detached = {k: (v.detach() if isinstance(v, torch.Tensor) else v) for k, v in batch.items()}
+    return _Tick.apply(ctl, detached, float(act_tol), flags, control_kwargs, *tensors, params, joint_gains)
 
 
 # the inputs of a plant step a gradient is produced for, in the order backward returns them; the step's outputs, in the order forward returns them
@@ -270,19 +354,22 @@ def leg_plant_step_autograd(ctl, state, joint_tau, dt, leg_inertia, stance=None,
 
 
 _ROLLOUT_TICK_REFUSED = {"gait_dt": "the gait clock writes gait_phase in place; the contact mask is held over the rollout",
-                         "swing_pos": "the swing legs' PD torques are out of scope", "swing_state": "the swing legs' PD torques are out of scope",
+                         "swing_state": "the planner's references are out of scope (swing_pos and swing_vel are held over the rollout)",
                          "feet": "the tick reads joint_q (rollout_autograd() steps the bare rigid body on `feet`)"}
 
 
 def rollout_tick_autograd(ctl, batch, steps, dt, leg_inertia, act_tol=1e-7, warm=True, params=None):
-    """BalanceController.rollout_tick_autograd (see there): `steps` times fused_tick_autograd() then leg_plant_step_autograd(), out of
-    place.  The gradient is the one on the active face of every solve, at every tick's clamp mask and off the plant's flagged legs;
+    """BalanceController.rollout_tick_autograd (see there): `steps` times fused_tick_autograd() - tick_autograd() for a batch with
+    swing_pos and swing_vel, both held over the rollout - then leg_plant_step_autograd(), out of place.  The gradient is the one on the active face of every solve, at every tick's clamp mask and off the plant's flagged legs;
     memory grows with `steps`."""
     for k, why in _ROLLOUT_TICK_REFUSED.items():
         if batch.get(k) is not None:
             raise ValueError(f"rollout_tick_autograd: the batch carries {k} - {why}")
     if batch.get("joint_q") is None or batch.get("joint_qdot") is None:
         raise ValueError("rollout_tick_autograd: the batch carries joint_q and joint_qdot (rollout_autograd() steps the bare rigid body)")
+    swings = batch.get("swing_pos") is not None
+    if swings != (batch.get("swing_vel") is not None):
+        raise ValueError("rollout_tick_autograd: swing_pos and swing_vel go together")
     steps = int(steps)
     if steps < 0:
         raise ValueError("rollout_tick_autograd: steps must be >= 0")
@@ -293,7 +380,7 @@ def rollout_tick_autograd(ctl, batch, steps, dt, leg_inertia, act_tol=1e-7, warm
     n, dev = batch["x"].shape[0], batch["x"].device
     flags = torch.zeros((n,), dtype=torch.int32, device=dev) if steps else None
     for _ in range(steps):
-        # the tick, as rollout_tick(batch, None, ...) plans it: an all-stance control_batch() takes no joint_qdot
+        # the tick, as rollout_tick(batch, None, ...) plans it: a control_batch() without swing references takes no joint_qdot
         res = {"grf_body": torch.zeros((n, 12), dtype=torch.float64, device=dev), "status": torch.full((n,), -1, dtype=torch.int32, device=dev),
                "joint_tau": torch.zeros((n, 12), dtype=torch.float64, device=dev)}
         kwargs = dict(out=res)
@@ -301,8 +388,11 @@ def rollout_tick_autograd(ctl, batch, steps, dt, leg_inertia, act_tol=1e-7, warm
             res["active_set"] = torch.zeros((n,), dtype=torch.int32, device=dev)
             kwargs.update(warm=active, want_active_set=True)
             active = res["active_set"]
-        tick_in = {k: v for k, v in cur.items() if k != "joint_qdot"}
-        tau, grf, status = fused_tick_autograd(ctl, tick_in, act_tol, params=params, **kwargs)
+        if swings:  # the swing legs' PD torques read joint_qdot and the held references
+            tau, grf, status = tick_autograd(ctl, cur, act_tol, params=params, **kwargs)
+        else:
+            tick_in = {k: v for k, v in cur.items() if k != "joint_qdot"}
+            tau, grf, status = fused_tick_autograd(ctl, tick_in, act_tol, params=params, **kwargs)
         new = leg_plant_step_autograd(ctl, cur, tau, dt, leg_inertia, flags=flags, **contact)
         cur = dict(cur, **dict(zip(names, new)))
         out = {"joint_tau": tau, "grf_body": grf, "status": status, "flags": flags}

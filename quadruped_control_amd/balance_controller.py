@@ -28,6 +28,7 @@ _IN_FIELDS = (("Rwb", 9), ("Rwb_d", 9), ("x", 3), ("xdot", 3), ("w", 3), ("x_d",
               ("w_d", 3), ("feet", 12))
 
 
+_SENSITIVITY_SWING_WANT = ("swing_pos_bar", "swing_vel_bar", "joint_q_bar", "joint_qdot_bar", "Rwb_bar", "x_bar")  # sensitivity_swing_batch's default
 _LEG_PLANT_ADJOINT_WANT = ("Rwb_bar", "x_bar", "xdot_bar", "w_bar", "joint_q_bar", "joint_qdot_bar", "joint_tau_bar")  # leg_plant_step_adjoint's default
 
 
@@ -737,8 +738,10 @@ class BalanceController:
         contact mask is the batch's `stance` / `gait_phase` / `gait_duty`, HELD over the rollout.  The start state Rwb, x, xdot, w,
         joint_q, joint_qdot and the desired state are differentiable where they require grad; `params` as fused_tick_autograd()'s,
         handed to every tick.  warm=True feeds each solve's (detached) active_set to the next solve, as rollout_tick() does.
-        ValueError for a batch with gait_dt (the clock writes gait_phase in place), swing_pos or swing_state (the swing legs' PD
-        torques are out of scope), `feet`, or without joint_q / joint_qdot.  Returns (state, out): `state` a dict of the final Rwb,
+        A batch with swing_pos AND swing_vel holds both over the rollout, as it holds the contact mask, runs tick_autograd() in
+        place of fused_tick_autograd() and gives both a gradient; a batch without them takes the stance path unchanged.
+        ValueError for a batch with gait_dt (the clock writes gait_phase in place), swing_state (the planner is out of scope), only
+        one of swing_pos / swing_vel, `feet`, or without joint_q / joint_qdot.  Returns (state, out): `state` a dict of the final Rwb,
         x, xdot, w, joint_q and joint_qdot, `out` the joint_tau, grf_body, status (and active_set) of the LAST tick and "flags", the
         last step's plant flags; for steps = 0 the state is the batch's own tensors and `out` is empty.  The forward values are
         rollout_tick(batch, None, ...)'s bit for bit.
@@ -933,6 +936,60 @@ class BalanceController:
         launch()
         return res
 
+    def plan_sensitivity_swing(self, batch, joint_tau_bar, want=_SENSITIVITY_SWING_WANT, out=None, joint_q_bar_in=None, Rwb_bar_in=None,
+                               x_bar_in=None, stream=None):
+        """sensitivity_swing_batch() marshalled once: returns (launch, out), `launch()` being one qc_sensitivity_swing_batch call
+        (graph-capturable) on tensors that are read in place.  Planning launches nothing.  `out`: a dict of tensors to write into
+        instead of new ones (every name in `want`) - out["joint_q_bar"] may be joint_q_bar_in, out["Rwb_bar"] Rwb_bar_in and
+        out["x_bar"] x_bar_in.  A call the library refuses raises ValueError with its message, from launch()."""
+        import torch
+
+        io = _lib.QcSensitivitySwingIo()
+        self._lib.qc_default_sensitivity_swing(C.byref(io))
+        own = [("joint_tau_bar", joint_tau_bar, 12), ("joint_q_bar_in", joint_q_bar_in, 12), ("Rwb_bar_in", Rwb_bar_in, 9), ("x_bar_in", x_bar_in, 3)]
+        n, dev, bi = self._readonly_batch("sensitivity_swing", batch, _SWING_FIELDS, io, own)
+        ss = batch.get("swing_state")  # (handed over so that the library names its refusal)
+        if _check_tensor("swing_state", ss, n, SWING_STATE_DTYPE.itemsize, torch.uint8, dev, False,
+                         msg="swing_state: need a contiguous uint8 tensor of n * 224 bytes on the device"):
+            bi.swing_state = ss.data_ptr()
+        res = _outputs("sensitivity_swing", _SENSITIVITY_SWING_OUTPUTS, want, out, n, dev, io)
+        args = (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
+        keep = (batch, joint_tau_bar, joint_q_bar_in, Rwb_bar_in, x_bar_in, res, bi, io)
+        return self._launcher("qc_sensitivity_swing_batch", args, keep, ValueError), res
+
+    def sensitivity_swing_batch(self, batch, joint_tau_bar, want=_SENSITIVITY_SWING_WANT, out=None, joint_q_bar_in=None, Rwb_bar_in=None,
+                                x_bar_in=None, stream=None):
+        """The reverse pass of the swing legs' PD torques (qc_sensitivity_swing_batch, include/qc_balance.h; INTEGRATION.md
+        "Differentiating a rollout").  `batch`: the one control_batch(want_torques=True) read, with swing_pos and swing_vel - Rwb, x,
+        joint_q, joint_qdot, the two references and the contact mask (stance, else the phase rule on gait_phase as it is now, else
+        all stance) are all that is read of it; a batch with swing_state or gait_dt is refused.  `joint_tau_bar` [n,12] or [n,4,3]:
+        the cotangent on joint_tau.  `want`: any of "swing_pos_bar", "swing_vel_bar", "joint_q_bar", "joint_qdot_bar" [n,4,3],
+        "gain_bar" [n,4,9] (kp, kd, kff of the joint controller, per leg), "Rwb_bar" [n,9] (entrywise, row-major), "x_bar" [n,3] and
+        "flags" int32 [n].  `joint_q_bar_in`, `Rwb_bar_in`, `x_bar_in`: added to the outputs of those names; each may be the output's
+        own tensor.  A stance leg's rows are zero (joint_q_bar: joint_q_bar_in); a swing leg's torque passes where the forward pass
+        did not clamp it, whatever the QP's status.  flags bit l: swing leg l's reference is out of reach, inside the inner limit, not
+        finite, or at a singular J(q_ref) - NaN in its rows and in the robot's Rwb_bar and x_bar.  Nothing of `batch` is written.
+        Asynchronous on `stream`, no synchronisation.  Returns the dict of device tensors; ValueError with the library's message for
+        a call it refuses."""
+        launch, res = self.plan_sensitivity_swing(batch, joint_tau_bar, want, out, joint_q_bar_in, Rwb_bar_in, x_bar_in, stream)
+        launch()
+        return res
+
+    def tick_autograd(self, batch, act_tol=1e-7, flags=None, params=None, joint_gains=None, **control_kwargs):
+        """The tick with swing references, with a gradient: returns (joint_tau, grf_body, status) of control_batch(batch,
+        want_torques=True, **control_kwargs) for a batch that carries joint_q, joint_qdot, swing_pos, swing_vel and a contact mask
+        (any mix of stance and swing legs), joint_tau and grf_body carrying a grad_fn whenever one of fused_tick_autograd()'s
+        inputs, joint_qdot, swing_pos, swing_vel, `params` or `joint_gains` requires grad (quadruped_control_amd/autograd.py).
+        `joint_gains`: a float64 [9] tensor - kp, kd, kff of the joint controller; forward NEVER reads it (the handle's own gains
+        are used), its gradient is sensitivity_swing_batch()'s gain_bar summed over robots and legs.  Backward, on the current stream
+        without host synchronisation: the stance chain exactly as fused_tick_autograd() runs it, then sensitivity_swing_batch() last,
+        adding in place to joint_q's, Rwb's and x's cotangents.  `act_tol`, `flags`, `params` and the validity of the gradient are
+        fused_tick_autograd()'s; a swing leg whose reference the swing kernel flags gives NaN.  ValueError for a batch with `feet`,
+        swing_state or gait_dt, or without one of the arrays above.  There is no double backward."""
+        from .autograd import tick_autograd
+
+        return tick_autograd(self, batch, act_tol, flags, params=params, joint_gains=joint_gains, **control_kwargs)
+
     def fused_tick_autograd(self, batch, act_tol=1e-7, flags=None, params=None, **control_kwargs):
         """The fused stance tick with a gradient: returns (joint_tau, grf_body, status) of control_batch(batch, want_torques=True,
         **control_kwargs) for a batch that carries joint_q and no `feet`, joint_tau and grf_body carrying a grad_fn whenever joint_q,
@@ -1060,6 +1117,8 @@ _SENSITIVITY_OUTPUTS = {"adjoint": ((12,), "float64"), "b_bar": ((6,), "float64"
 _SENSITIVITY_ROT_OUTPUTS = {k: ((m,), "float64") for k, m in (("Rwb_bar", 9), ("Rwb_d_bar", 9), ("Rwb_rot_bar", 3), ("Rwb_d_rot_bar", 3))}
 _SENSITIVITY_PARAM_OUTPUTS = {"param_bar_rows": ((_lib.PARAM_COUNT,), "float64")}
 _SENSITIVITY_KIN_OUTPUTS = {"grf_bar": ((4, 3), "float64"), "joint_q_bar": ((4, 3), "float64")}
+_SENSITIVITY_SWING_OUTPUTS = {**{k: ((4, 3), "float64") for k in ("swing_pos_bar", "swing_vel_bar", "joint_q_bar", "joint_qdot_bar")},
+                              "gain_bar": ((4, 9), "float64"), "Rwb_bar": ((9,), "float64"), "x_bar": ((3,), "float64"), "flags": ((), "int32")}
 _PLANT_ADJOINT_OUTPUTS = {k: ((m,), "float64") for k, m in (("Rwb_bar", 9), ("x_bar", 3), ("xdot_bar", 3), ("w_bar", 3), ("grf_bar", 12), ("foot_world_bar", 12))}
 _PLANT_COTANGENTS = {k: ((m,), "float64") for k, m in (("Rwb", 9), ("x", 3), ("xdot", 3), ("w", 3), ("feet", 12))}  # the step's outputs a cotangent may be given on
 _LEG_PLANT_ADJOINT_OUTPUTS = {k: ((m,), "float64") for k, m in (("Rwb_bar", 9), ("x_bar", 3), ("xdot_bar", 3), ("w_bar", 3), ("joint_q_bar", 12),
@@ -1069,6 +1128,9 @@ _LEG_PLANT_COTANGENTS = {k: ((m,), "float64") for k, m in (("Rwb", 9), ("x", 3),
 _STATE_FIELDS = tuple((k, m, "float64") for k, m in _IN_FIELDS + (("joint_q", 12),))
 _READONLY_FIELDS = _STATE_FIELDS + (("stance", 4, "uint8"), ("gait_phase", 4, "float64"), ("gait_duty", 1, "float64"))
 _KINEMATICS_FIELDS = (("joint_q", 12, "float64"),) + _READONLY_FIELDS[len(_STATE_FIELDS):]  # sensitivity_kinematics: joint_q and the contact mask
+# sensitivity_swing: the six arrays of the swing chain, the contact mask, and gait_dt so that the library names its refusal
+_SWING_FIELDS = (("Rwb", 9, "float64"), ("x", 3, "float64")) + tuple((k, 12, "float64") for k in ("joint_q", "joint_qdot", "swing_pos", "swing_vel")) + \
+    _READONLY_FIELDS[len(_STATE_FIELDS):] + (("gait_dt", 1, "float64"),)
 
 
 # a parameter cotangent: name -> (slice of the 211 values, shape), in the order of the double members of qc_params

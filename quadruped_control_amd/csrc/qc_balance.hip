@@ -2393,6 +2393,24 @@ int qc_sensitivity_kin_batch(qc_handle* h, size_t n, const qc_batch_in* in, cons
   return QC_OK;
 }
 
+void qc_default_sensitivity_swing(qc_sensitivity_swing_io* io) { (void)zeroed(io); }
+
+int qc_sensitivity_swing_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_swing_io* io, void* stream) {
+  if (const int rc = qc::check_sensitivity_swing_args(h, n, in, io); rc != QC_OK || n == 0) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  // (of `in`: the six arrays of the swing chain and the contact mask as it is now - nothing that advances or plans)
+  const qc::SensitivitySwingArgs a{in->Rwb, in->x, in->joint_q, in->joint_qdot, in->swing_pos, in->swing_vel, in->stance, in->gait_phase, in->gait_duty,
+                                   io->joint_tau_bar, io->joint_q_bar_in, io->Rwb_bar_in, io->x_bar_in, io->swing_pos_bar, io->swing_vel_bar,
+                                   io->joint_q_bar, io->joint_qdot_bar, io->gain_bar, io->Rwb_bar, io->x_bar, io->flags};
+  const bool leg = io->swing_pos_bar || io->swing_vel_bar || io->joint_q_bar || io->joint_qdot_bar || io->gain_bar, body = io->Rwb_bar || io->x_bar;
+  void (*const fn)(const qc::DevParams*, long, qc::SensitivitySwingArgs) =
+      leg ? (body ? qc::sensitivity_swing_kernel<true, true> : qc::sensitivity_swing_kernel<true, false>)
+          : (body ? qc::sensitivity_swing_kernel<false, true> : qc::sensitivity_swing_kernel<false, false>);
+  fn<<<dim3(qc::sensitivity_swing_blocks(n)), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)(4 * n), a);
+  QC_HIP(hipGetLastError());
+  return QC_OK;
+}
+
 // host-pointer variant.  Large batches: one device staging allocation, H2D copies, kernel, D2H copies, sync.
 // Small batches (n <= kPinnedMaxN; the reference's own use is one robot per controller tick): the records are packed
 // into a pinned, device-visible host buffer that the kernel reads and writes in place over PCIe - one launch and one

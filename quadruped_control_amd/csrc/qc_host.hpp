@@ -18,6 +18,7 @@
 #include "qc_sensitivity_rot.hpp"
 #include "qc_sensitivity_params.hpp"
 #include "qc_sensitivity_kin.hpp"
+#include "qc_sensitivity_swing.hpp"
 
 namespace qc {
 
@@ -680,5 +681,26 @@ inline int check_sensitivity_kin_args(const qc_handle* h, size_t n, const qc_bat
 
 // workgroups of sensitivity_kin_kernel for n robots: one wave of 16 robots' legs each, capped
 inline unsigned sensitivity_kin_blocks(size_t n) { return capped_blocks(4 * n, SENSITIVITY_BLOCK, SENSITIVITY_MAX_BLOCKS); }
+
+// ---------------------------------------------------------------- qc_sensitivity_swing_batch
+// The argument check of the swing-leg torque adjoint: what is wrong with the call itself (message prefix "qc_sensitivity_swing_batch:").
+// The kernel reads six arrays of `in` and the contact mask as it is now; what would plan or advance (swing_state, gait_dt) is refused.
+inline int check_sensitivity_swing_args(const qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_swing_io* io) {
+  const char* who = "qc_sensitivity_swing_batch";
+  if (const int rc = check_io(who, h && in, io, "qc_sensitivity_swing_io", "qc_default_sensitivity_swing"); rc != QC_OK) return rc;
+  const auto bad = [who](const char* what) { return fail(QC_ERR_INVALID, std::string(who) + what); };
+  if (in->swing_state) return bad(": swing_state must be NULL (the planner's references are out of scope: give swing_pos and swing_vel)");
+  if (in->gait_dt) return bad(": gait_dt must be NULL (the gait clock is out of scope: the contact mask is read as it is now)");
+  if (!io->swing_pos_bar && !io->swing_vel_bar && !io->joint_q_bar && !io->joint_qdot_bar && !io->gain_bar && !io->Rwb_bar && !io->x_bar && !io->flags)
+    return bad(": no output requested (swing_pos_bar, swing_vel_bar, joint_q_bar, joint_qdot_bar, gain_bar, Rwb_bar, x_bar, flags are all NULL)");
+  if (n == 0) return QC_OK;
+  if (!io->joint_tau_bar) return bad(": joint_tau_bar is required");
+  if (!in->Rwb || !in->x || !in->joint_q || !in->joint_qdot || !in->swing_pos || !in->swing_vel)
+    return bad(": Rwb, x, joint_q, joint_qdot, swing_pos and swing_vel are required");
+  return check_one_launch(who, n, SENSITIVITY_BLOCK);
+}
+
+// workgroups of sensitivity_swing_kernel for n robots: one wave of 16 robots' legs each, capped
+inline unsigned sensitivity_swing_blocks(size_t n) { return capped_blocks(4 * n, SENSITIVITY_BLOCK, SENSITIVITY_MAX_BLOCKS); }
 
 }  // namespace qc
