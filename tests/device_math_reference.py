@@ -21,6 +21,45 @@ LEG_NAMES = ("RL", "FL", "RR", "FR")
 JC_KFF, JC_KP, JC_KD = (0.0, 0.0, 0.0), (40.0, 40.0, 50.0), (1.0, 1.0, 1.0)  # mit_cheetah_config.yaml:50-53
 
 
+class Kin:
+    """One kinematic model as the restatements take it (their optional `kin` argument): hip, links [4, 3], the joint controller's
+    gains, the torque limits and the leg inertia the plant tests use with it.  No module keeps a "current" model."""
+
+    def __init__(self, name, hip, links, jc_kp, jc_kd, jc_kff, tau_min, tau_max, leg_inertia):
+        self.name = name
+        self.hip, self.links = np.array(hip, np.float64).reshape(4, 3), np.array(links, np.float64).reshape(4, 3)
+        self.jc_kp, self.jc_kd, self.jc_kff = tuple(map(float, jc_kp)), tuple(map(float, jc_kd)), tuple(map(float, jc_kff))
+        self.tau_min, self.tau_max = float(tau_min), float(tau_max)
+        self.leg_inertia = tuple(map(float, leg_inertia))
+        self.hip.setflags(write=False)
+        self.links.setflags(write=False)
+
+    def det_lo(self, leg):
+        """the lower end of the closed-form band of det J for this leg, from the leg's own links (swing_pd's `lo`)"""
+        return max(EPS, 64.0 * EPS * float(np.abs(self.links[leg]).sum()) ** 3)
+
+    def handle_arguments(self):
+        """the keywords of BalanceController.set_kinematics for this model"""
+        return dict(hip=self.hip.reshape(12), links=self.links.reshape(12), tau_min=self.tau_min, tau_max=self.tau_max, jc_kp=self.jc_kp,
+                    jc_kd=self.jc_kd, jc_kff=self.jc_kff)
+
+
+# the library's default model (qc_default_kinematics).  It is a degenerate point of the model space: hip z = 0, kff = 0, kd = 1, the
+# same |links| on all four legs, hips that differ in sign only, tau_min = -tau_max - a kernel that reads the wrong leg's or the wrong
+# joint's constant is bit-identical there.
+DEFAULT_KIN = Kin("default", HIP, LINKS, JC_KP, JC_KD, JC_KFF, -20.0, 20.0, (0.02, 0.03, 0.025))
+# ODD_KIN: the second model of the tests, committed as literal numbers.  Links: the defaults times the twelve factors 0.85 1.10 0.95 /
+# 1.20 0.90 1.05 / 0.97 1.18 0.82 / 1.08 0.83 1.22 (signs kept; no two legs share a length, |l2| != |l3| on every leg).  Hip x, y: the
+# defaults times 0.90 1.20 / 1.15 0.88 / 1.05 1.10 / 0.84 0.93; hip z non-zero, of both signs, |z| <= 0.04.  Nine distinct gains, no kd
+# equal to 1, kff non-zero with mixed signs and small against the limits; asymmetric limits; an anisotropic leg inertia.
+ODD_KIN = Kin("odd",
+              hip=[[-0.1764, 0.060, 0.031], [0.2254, 0.044, -0.017], [-0.2058, -0.055, -0.038], [0.16464, -0.0465, 0.012]],
+              links=[[0.06545, -0.2321, -0.2185], [0.0924, -0.1899, -0.2415], [-0.07469, -0.24898, -0.1886], [-0.08316, -0.17513, -0.2806]],
+              jc_kp=(33.0, 47.0, 58.0), jc_kd=(0.7, 1.3, 1.9), jc_kff=(0.4, -0.25, 0.15), tau_min=-13.0, tau_max=17.0,
+              leg_inertia=(0.018, 0.031, 0.024))
+KINS = {"default": DEFAULT_KIN, "odd": ODD_KIN}
+
+
 def mpf(x):
     return mp.mpf(float(x))
 
@@ -127,19 +166,19 @@ def normalize_angle_PI_unfused(rad):
 
 
 # ------------------------------------------------------------------ leg kinematics
-def leg_fk_ld(leg, q):
+def leg_fk_ld(leg, q, kin=DEFAULT_KIN):
     """forwardKinematics (kinematics.cpp:81-103) in long double; q [n, 3]"""
-    l1, l2, l3 = (np.longdouble(v) for v in LINKS[leg])
+    l1, l2, l3 = (np.longdouble(v) for v in kin.links[leg])
     q = np.asarray(q, np.longdouble)
     t1, t2, t3 = q[:, 0], q[:, 1], q[:, 2]
-    h = HIP[leg].astype(np.longdouble)
+    h = kin.hip[leg].astype(np.longdouble)
     s1, c1, s2, c2, s23, c23 = np.sin(t1), np.cos(t1), np.sin(t2), np.cos(t2), np.sin(t2 + t3), np.cos(t2 + t3)
     return np.stack([l2 * s2 + l3 * s23 + h[0], l1 * c1 - l2 * s1 * c2 - l3 * s1 * c23 + h[1], l1 * s1 + l2 * c1 * c2 + l3 * c1 * c23 + h[2]], 1)
 
 
-def leg_jacobian_ld(leg, q):
+def leg_jacobian_ld(leg, q, kin=DEFAULT_KIN):
     """legJacobian (kinematics.cpp:162-188) in long double; q [n, 3] -> [n, 3, 3]"""
-    l1, l2, l3 = (np.longdouble(v) for v in LINKS[leg])
+    l1, l2, l3 = (np.longdouble(v) for v in kin.links[leg])
     q = np.asarray(q, np.longdouble)
     t1, t2, t3 = q[:, 0], q[:, 1], q[:, 2]
     s1, c1, s2, c2, s23, c23 = np.sin(t1), np.cos(t1), np.sin(t2), np.cos(t2), np.sin(t2 + t3), np.cos(t2 + t3)
@@ -149,8 +188,8 @@ def leg_jacobian_ld(leg, q):
                      np.stack([l1 * c1 - l2 * s1 * c2 - l3 * s1 * c23, -(l2 * s2 + l3 * s23) * c1, -l3 * s23 * c1], 1)], 1)
 
 
-def _jacobian_mp(leg, q):
-    l1, l2, l3 = (mpf(v) for v in LINKS[leg])
+def _jacobian_mp(leg, q, kin=DEFAULT_KIN):
+    l1, l2, l3 = (mpf(v) for v in kin.links[leg])
     t1, t2, t3 = q
     s1, c1, s2, c2, s23, c23 = mp.sin(t1), mp.cos(t1), mp.sin(t2), mp.cos(t2), mp.sin(t2 + t3), mp.cos(t2 + t3)
     return mp.matrix([[0, l2 * c2 + l3 * c23, l3 * c23],
@@ -158,19 +197,19 @@ def _jacobian_mp(leg, q):
                       [l1 * c1 - l2 * s1 * c2 - l3 * s1 * c23, -(l2 * s2 + l3 * s23) * c1, -l3 * s23 * c1]])
 
 
-def knee_cosine_double(leg, p):
+def knee_cosine_double(leg, p, kin=DEFAULT_KIN):
     """d of legInverseKinematics as the reference's build computes it: float64, every operation rounded on its own"""
-    l1, l2, l3 = (abs(float(v)) for v in LINKS[leg])
-    x, y, z = (float(p[k]) - float(HIP[leg][k]) for k in range(3))
+    l1, l2, l3 = (abs(float(v)) for v in kin.links[leg])
+    x, y, z = (float(p[k]) - float(kin.hip[leg][k]) for k in range(3))
     num = x * x + y * y + z * z - l1 * l1 - l2 * l2 - l3 * l3
     return num / (2.0 * l2 * l3)
 
 
-def leg_inverse_kinematics_mp(leg, p, d=None):
+def leg_inverse_kinematics_mp(leg, p, d=None, kin=DEFAULT_KIN):
     """legInverseKinematics (kinematics.cpp:117-160) at 50 digits on the exact double target p (body frame); returns mp values.
     `d`: the knee cosine to use instead of the exact one (near full stretch every ulp of d is a different knee angle)."""
-    l1, l2, l3 = (abs(mpf(v)) for v in LINKS[leg])
-    x, y, z = (mpf(p[k]) - mpf(HIP[leg][k]) for k in range(3))
+    l1, l2, l3 = (abs(mpf(v)) for v in kin.links[leg])
+    x, y, z = (mpf(p[k]) - mpf(kin.hip[leg][k]) for k in range(3))
     if d is None:
         d = (x * x + y * y + z * z - l1 * l1 - l2 * l2 - l3 * l3) / (2 * l2 * l3)
     else:
@@ -195,16 +234,17 @@ def _wrap_PI_mp(v):
     return r
 
 
-def swing_torque_mp(leg, pb, vb, q, qdot, kff=JC_KFF, kp=JC_KP, kd=JC_KD, d=None):
+def swing_torque_mp(leg, pb, vb, q, qdot, kff=None, kp=None, kd=None, d=None, kin=DEFAULT_KIN):
     """The swing-leg torque: legInverseKinematics -> legJacobianInverse -> JointController::control (joint_controller.cpp:21-39:
     kff + kp wrap(q_ref - q) + kd (J^-1 v - qdot)).  The inverse is the exact one where J is regular; where IK makes J singular
     (the knee stretched, d clamped to 1, or folded, d = -1: sin q3 = 0 exactly) it is the pseudo-inverse of rank 2, the rank
     the device's elimination keeps there.  The error is wrapped into [-pi, pi) exactly as
     normalize_angle_PI(normalize_angle_2PI(a) - normalize_angle_2PI(b)) is mathematically.
     Returns (tau as floats, cond = sigma_1 / sigma_rank, the knee cosine d, max |J^+ vb|)."""
+    kff, kp, kd = (kin.jc_kff if kff is None else kff), (kin.jc_kp if kp is None else kp), (kin.jc_kd if kd is None else kd)
     with mp.workdps(DPS):
-        qr, d = leg_inverse_kinematics_mp(leg, pb, d)
-        J = _jacobian_mp(leg, qr)
+        qr, d = leg_inverse_kinematics_mp(leg, pb, d, kin)
+        J = _jacobian_mp(leg, qr, kin)
         U, S, V = mp.svd_r(J)
         order = sorted(range(3), key=lambda k: -S[k])
         rank = 3 if S[order[2]] > mp.mpf(10) ** -30 * S[order[0]] else 2

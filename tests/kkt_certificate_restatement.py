@@ -28,12 +28,13 @@ DEFAULT_DUTY = 0.8 / (0.18 + 0.8)  # the handle's stance_phase (qc_host.hpp deri
 SWING = 0x80
 
 
-def with_feet(b):
-    """the batch with `feet` made from joint_q by the reference's forward kinematics, if it has none"""
+def with_feet(b, kin=None):
+    """the batch with `feet` made from joint_q by the reference's forward kinematics, if it has none.  kin: the kinematic model
+    (device_math_reference.Kin; default the library's) - a test at another model hands the restatements with_feet(b, kin)"""
     if b.get("feet") is not None or b.get("joint_q") is None:
         return b
     q = np.asarray(b["joint_q"], np.float64).reshape(-1, 4, 3)
-    feet = np.array([[fk(l, q[i, l]) for l in range(4)] for i in range(q.shape[0])]).reshape(-1, 12)
+    feet = np.array([[fk(l, q[i, l], *(() if kin is None else (kin,))) for l in range(4)] for i in range(q.shape[0])]).reshape(-1, 12)
     return dict(b, feet=feet)
 
 

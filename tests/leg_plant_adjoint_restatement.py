@@ -28,7 +28,7 @@ import mpmath as mp
 import numpy as np
 
 from tests import leg_plant_restatement as LR
-from tests.device_math_reference import DPS, EPS, HIP, LINKS, mpf
+from tests.device_math_reference import DEFAULT_KIN, DPS, EPS, mpf
 from tests.plant_adjoint_restatement import exp_slopes_mp, exp_slopes_np
 from tests.plant_restatement import G
 
@@ -40,6 +40,11 @@ BAR_OF = {k: k + "_bar" for k in INPUTS}
 # tests/test_leg_plant_adjoint_cpu.py measures it (6.46, 0.11, 7.88, 0.93, 0.86, 0.65, 1.28), rounded up to one decimal with a little
 # headroom; that test asserts the measurement stays below, tests/test_gpu_leg_plant_adjoint.py derives the device's bar (4 c_np) from it
 C_NP = {"Rwb_bar": 6.6, "x_bar": 0.2, "xdot_bar": 8.0, "w_bar": 1.0, "joint_q_bar": 0.9, "joint_qdot_bar": 0.7, "joint_tau_bar": 1.3}
+# C_NP_ODD: the same measurement at device_math_reference.ODD_KIN over pool(ODD_KIN), all 257 robots (4.40, 0.087, 5.60, 1.05, 0.58, 0.65,
+# 1.27: tests/test_leg_plant_adjoint_cpu.py::test_restatement_against_50_digits_on_the_pool_at_the_odd_model prints and asserts them).  Never measured
+# on the device.
+C_NP_ODD = {"Rwb_bar": 4.5, "x_bar": 0.1, "xdot_bar": 5.7, "w_bar": 1.1, "joint_q_bar": 0.6, "joint_qdot_bar": 0.7, "joint_tau_bar": 1.3}
+C_NP_OF = {"default": C_NP, "odd": C_NP_ODD}
 DT = 1.0 / 300.0
 INERTIA = (0.02, 0.03, 0.025)
 
@@ -151,19 +156,20 @@ def _sub(P, Q):
     return [p - q for p, q in zip(P, Q)]
 
 
-def _in_band(det):
-    return LR.DET_LO <= abs(det) <= LR.DET_HI  # (False for NaN)
+def _in_band(det, lo=LR.DET_LO):
+    return lo <= abs(det) <= LR.DET_HI  # (False for NaN); lo: the leg's own lower end at a model other than the default (Kin.det_lo)
 
 
 class _Leg:
     """One leg at joint angles q in arithmetic A: FK, the Jacobian J = dFK / dq (flat, row-major), its cofactors and determinant"""
 
-    def __init__(self, A, leg, q):
-        l1, l2, l3 = (A.const(v) for v in LINKS[leg])
+    def __init__(self, A, leg, q, kin=DEFAULT_KIN):
+        l1, l2, l3 = (A.const(v) for v in kin.links[leg])
         s1, c1, s2, c2 = A.sin(q[0]), A.cos(q[0]), A.sin(q[1]), A.cos(q[1])
         q23 = q[1] + q[2]
         s23, c23 = A.sin(q23), A.cos(q23)
-        hip = [A.const(v) for v in HIP[leg]]
+        hip = [A.const(v) for v in kin.hip[leg]]
+        self.det_lo = kin.det_lo(leg)
         self.p = [l2 * s2 + l3 * s23 + hip[0], l1 * c1 - l2 * s1 * c2 - l3 * s1 * c23 + hip[1], l1 * s1 + l2 * c1 * c2 + l3 * c1 * c23 + hip[2]]
         a, b, d, e = l2 * c2 + l3 * c23, l2 * s2 + l3 * s23, l3 * c23, l3 * s23
         zero = A.const(0.0)
@@ -190,10 +196,10 @@ class _Leg:
         return [G00 * y[0] + G01 * y[1] + G02 * y[2], G01 * y[0] + G11 * y[1] + G12 * y[2], G02 * y[0] + G12 * y[1] + G12 * y[2]]
 
 
-def _ik(A, leg, pb):
+def _ik(A, leg, pb, kin=DEFAULT_KIN):
     """legInverseKinematics (kinematics.cpp:117-160) in arithmetic A for a foot in reach: (q, knee cosine d as a float, tape)"""
-    l1, l2, l3 = (A.const(abs(v)) for v in LINKS[leg])
-    x, y, z = (pb[k] - A.const(HIP[leg][k]) for k in range(3))
+    l1, l2, l3 = (A.const(abs(v)) for v in kin.links[leg])
+    x, y, z = (pb[k] - A.const(kin.hip[leg][k]) for k in range(3))
     two = A.const(2.0)
     d = (x * x + y * y + z * z - l1 * l1 - l2 * l2 - l3 * l3) / (two * l2 * l3)
     dv = A.val(d)
@@ -201,7 +207,7 @@ def _ik(A, leg, pb):
         return None, dv, None
     sc = y * y + z * z - l1 * l1
     rt = A.sqrt(sc) if A.val(sc) > 0.0 else A.const(0.0)
-    right = LINKS[leg][0] < 0.0
+    right = kin.links[leg][0] < 0.0
     ya = y if right else -y
     q1 = A.atan2(z, ya) + A.atan2(rt, -l1)
     if not right:
@@ -245,7 +251,7 @@ def _ik_reverse(A, tape, qb):
     return [xb + two * x * nb, yb + two * y * nb, zb + two * z * nb]
 
 
-def _adjoint_one(A, mass, Ib, state, mask, leg_inertia, dt, bars, ik, g=G):
+def _adjoint_one(A, mass, Ib, state, mask, leg_inertia, dt, bars, ik, g=G, kin=DEFAULT_KIN):
     """One robot in arithmetic A.  state: the seven INPUTS as flat float arrays; bars: {output name: flat float array or None}.
     Returns ({name: list of A-values} or None if flagged, flags)."""
     vec = lambda a, k: [A.const(v) for v in np.asarray(a, float).reshape(k)]
@@ -272,8 +278,8 @@ def _adjoint_one(A, mass, Ib, state, mask, leg_inertia, dt, bars, ik, g=G):
     for l in range(4):
         if not mask[l]:
             continue
-        L = legs[l] = _Leg(A, l, leg3(Q, l))
-        if not _in_band(A.val(L.det)):
+        L = legs[l] = _Leg(A, l, leg3(Q, l), kin)
+        if not _in_band(A.val(L.det), L.det_lo):
             flags |= 1 << l
             continue
         gl[l] = L.solve_t(leg3(TQ, l))
@@ -307,12 +313,12 @@ def _adjoint_one(A, mass, Ib, state, mask, leg_inertia, dt, bars, ik, g=G):
             qb[l], qdb[l], tqb[l] = leg3(qnb, l), s, [dtm * s[k] / iner[k] for k in range(3)]
             continue
         dl = _sub(C[l], X1)
-        qn, d, tape = _ik(A, l, _mtv(Rn, dl))
+        qn, d, tape = _ik(A, l, _mtv(Rn, dl), kin)
         if qn is None:
             flags |= 16 << l
             continue
-        Ln = _Leg(A, l, qn)
-        if not _in_band(A.val(Ln.det)):
+        Ln = _Leg(A, l, qn, kin)
+        if not _in_band(A.val(Ln.det), Ln.det_lo):
             flags |= 16 << l
             continue
         s = [leg3(qdnb, l)[k] / dtm for k in range(3)]
@@ -371,7 +377,7 @@ def _adjoint_one(A, mass, Ib, state, mask, leg_inertia, dt, bars, ik, g=G):
 _SIZES = {"Rwb_bar": 9, "x_bar": 3, "xdot_bar": 3, "w_bar": 3, "joint_q_bar": 12, "joint_qdot_bar": 12, "joint_tau_bar": 12}
 
 
-def leg_plant_adjoint_np(mass, Ib, Rwb, x, xdot, w, joint_q, joint_qdot, joint_tau, mask, leg_inertia, dt, bars, ik="jacobian"):
+def leg_plant_adjoint_np(mass, Ib, Rwb, x, xdot, w, joint_q, joint_qdot, joint_tau, mask, leg_inertia, dt, bars, ik="jacobian", kin=DEFAULT_KIN):
     """The transpose-Jacobian of leg_plant_step_np for n robots, float64.  mask [n, 4] bool; `bars`: {name of a step output: cotangent
     array} (COTANGENTS; a missing one is zero).  Returns {name: array} for OUTPUTS (NaN rows where flagged) and "flags" [n] int32."""
     n = x.shape[0]
@@ -380,14 +386,14 @@ def leg_plant_adjoint_np(mass, Ib, Rwb, x, xdot, w, joint_q, joint_qdot, joint_t
     arrays = dict(Rwb=Rwb, x=x, xdot=xdot, w=w, joint_q=joint_q, joint_qdot=joint_qdot, joint_tau=joint_tau)
     for i in range(n):
         res, out["flags"][i] = _adjoint_one(_Float, mass, Ib, {k: np.asarray(v)[i] for k, v in arrays.items()}, mask[i], leg_inertia, dt,
-                                            {k: (None if v is None else np.asarray(v)[i]) for k, v in bars.items()}, ik)
+                                            {k: (None if v is None else np.asarray(v)[i]) for k, v in bars.items()}, ik, kin=kin)
         if res is not None:
             for k in OUTPUTS:
                 out[k][i] = res[k]
     return out
 
 
-def leg_plant_adjoint_mp(mass, Ib, Rwb, x, xdot, w, joint_q, joint_qdot, joint_tau, mask, leg_inertia, dt, bars, ik="chain"):
+def leg_plant_adjoint_mp(mass, Ib, Rwb, x, xdot, w, joint_q, joint_qdot, joint_tau, mask, leg_inertia, dt, bars, ik="chain", kin=DEFAULT_KIN):
     """One robot at 50 digits.  Returns ({name: (value, condition sum)} for OUTPUTS, flat float arrays - NaN where flagged -, flags).
     The VALUES are those of the pass with the IK end `ik` ("chain": as written).  The CONDITION SUMS are always those of the
     "jacobian" pass, the expression a double evaluation actually computes (the kernel, leg_plant_adjoint_np): the reversed chain
@@ -395,10 +401,10 @@ def leg_plant_adjoint_mp(mass, Ib, Rwb, x, xdot, w, joint_q, joint_qdot, joint_t
     condition sum comes out 1e7 times that of the same derivative through J(qn)^-T, a scale that would let any error pass."""
     state = dict(Rwb=Rwb, x=x, xdot=xdot, w=w, joint_q=joint_q, joint_qdot=joint_qdot, joint_tau=joint_tau)
     with mp.workdps(DPS):
-        res, flags = _adjoint_one(_Mp, mass, Ib, state, mask, leg_inertia, dt, bars, ik)
+        res, flags = _adjoint_one(_Mp, mass, Ib, state, mask, leg_inertia, dt, bars, ik, kin=kin)
         if res is None:
             return {k: (np.full(m, np.nan), np.full(m, np.nan)) for k, m in _SIZES.items()}, flags
-        scale = res if ik == "jacobian" else _adjoint_one(_Mp, mass, Ib, state, mask, leg_inertia, dt, bars, "jacobian")[0]
+        scale = res if ik == "jacobian" else _adjoint_one(_Mp, mass, Ib, state, mask, leg_inertia, dt, bars, "jacobian", kin=kin)[0]
         return {k: (np.array([float(t.v) for t in res[k]]), np.array([t.c for t in scale[k]])) for k in OUTPUTS}, flags
 
 
@@ -408,9 +414,12 @@ FLAGGED = {"stretched": 16 << 0, "folded": 16 << 1, "singular": 1 << 2}  # the s
 TWO_PI = 2.0 * math.pi
 
 
-def tau_limits():
-    """(tau_min, tau_max) of the library's default kinematics: the tick's torque clamp"""
+def tau_limits(kin=DEFAULT_KIN):
+    """(tau_min, tau_max) of the model: the tick's torque clamp - the library's own record for its default kinematics"""
     import ctypes
+
+    if kin is not DEFAULT_KIN:
+        return kin.tau_min, kin.tau_max
 
     from quadruped_control_amd import _lib
 
@@ -420,8 +429,8 @@ def tau_limits():
 
 
 @functools.lru_cache(maxsize=None)
-def pool():
-    """POOL unflagged robots: leg_plant_restatement.make_pool (bent stance legs, torques of ground-reaction-sized forces, every fourth
+def pool(kin=DEFAULT_KIN):
+    """POOL unflagged robots (rebuilt under `kin`: the torques through the model's Jacobians, the clamp values the model's): leg_plant_restatement.make_pool (bent stance legs, torques of ground-reaction-sized forces, every fourth
     w = 0) with the contact mask 15 - i mod 16 - all 16 masks, row 0 all stance -, and
       row 0   the identity rotation          row 1   a rotation by nearly pi
       row 2   joint_q of stance leg 0 offset by 2 pi from what the IK returns: wrapPI acts on q' - q
@@ -430,13 +439,13 @@ def pool():
     Cotangents on all six outputs: normal(0, 1), committed seed.  Returns (inputs, mask [POOL, 4] bool, cotangents)."""
     from scipy.spatial.transform import Rotation
 
-    s = {k: np.array(v) for k, v in LR.make_pool(POOL, 0x1E6AD1).items()}
+    s = {k: np.array(v) for k, v in LR.make_pool(POOL, 0x1E6AD1, kin).items()}
     mask = np.array([[((15 - i) % 16 >> l) & 1 for l in range(4)] for i in range(POOL)], bool)
     R = s["Rwb"].reshape(POOL, 3, 3)
     R[0] = np.eye(3)
     R[1] = Rotation.from_rotvec(np.array([1.0, 2.0, -2.0]) / 3.0 * (math.pi - 1e-9)).as_matrix()
     s["joint_q"].reshape(POOL, 4, 3)[2, 0] += TWO_PI
-    lo, hi = tau_limits()
+    lo, hi = tau_limits(kin)
     s["joint_tau"].reshape(POOL, 4, 3)[3, 2:] = [[hi, lo, hi], [lo, hi, lo]]
     s["w"][15] = 0.0
     s.pop("gait_phase")
@@ -448,7 +457,7 @@ def pool():
 
 
 @functools.lru_cache(maxsize=None)
-def flagged_pool():
+def flagged_pool(kin=DEFAULT_KIN):
     """Three all-stance robots at rest, Rwb = I, zero torques, one leg each put where the gradient is undefined (FLAGGED's order):
       stretched  leg 0 nearly straight (q3 = -0.05) and the body rising at 2 m/s: the pinned foot is out of reach after the step (d > 1)
       folded     leg 1 nearly folded (q3 = -(pi - 0.02)) and the hip moving at 2 m/s towards the foot in the leg's plane: d < -1, the NaN leg
@@ -461,9 +470,9 @@ def flagged_pool():
     q[0, 0] = [0.0, 0.4, -0.05]
     xdot[0] = [0.0, 0.0, 2.0]
     q[1, 1] = [0.0, 1.2, -(math.pi - 0.02)]
-    p = LR.fk(1, q[1, 1]) - HIP[1]
+    p = LR.fk(1, q[1, 1], kin) - kin.hip[1]
     xdot[1] = 2.0 * np.array([p[0], 0.0, p[2]]) / math.hypot(p[0], p[2])
-    l2, l3 = LINKS[2][1], LINKS[2][2]
+    l2, l3 = kin.links[2][1], kin.links[2][2]
     q[2, 2] = [0.0, math.atan2(l2 + l3 * math.cos(-1.6), l3 * math.sin(-1.6)), -1.6]
     xdot[2] = [0.0, 0.0, 0.5]
     s = dict(Rwb=np.tile(np.eye(3).reshape(9), (n, 1)), x=np.tile([0.0, 0.0, 0.3], (n, 1)), xdot=xdot, w=np.zeros((n, 3)),
@@ -501,13 +510,15 @@ def contact_inputs(mask, way):
 
 
 @functools.lru_cache(maxsize=None)
-def pool_reference():
-    """{name: (values [POOL, k], condition sums [POOL, k])} of leg_plant_adjoint_mp on pool(), computed once per process, and the flags"""
+def pool_reference(kin=DEFAULT_KIN):
+    """{name: (values [POOL, k], condition sums [POOL, k])} of leg_plant_adjoint_mp on pool(kin), computed once per process and model,
+    and the flags.  The leg inertia is INERTIA at either model (anisotropic)."""
     import quadruped_control_amd as q
 
     P = q.cheetah_params()
-    s, mask, bars = pool()
-    refs = [leg_plant_adjoint_mp(P["mass"], P["Ib"], *(s[k][i] for k in INPUTS), mask[i], INERTIA, DT, {k: v[i] for k, v in bars.items()}) for i in range(POOL)]
+    s, mask, bars = pool(kin)
+    refs = [leg_plant_adjoint_mp(P["mass"], P["Ib"], *(s[k][i] for k in INPUTS), mask[i], INERTIA, DT, {k: v[i] for k, v in bars.items()}, kin=kin)
+            for i in range(POOL)]
     return {k: (np.stack([r[0][k][0] for r in refs]), np.stack([r[0][k][1] for r in refs])) for k in OUTPUTS}, np.array([r[1] for r in refs], np.int32)
 
 

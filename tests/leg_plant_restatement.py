@@ -31,14 +31,15 @@ import mpmath as mp
 import numpy as np
 
 from tests import plant_restatement as PR
-from tests.device_math_reference import DPS, EPS, HIP, LINKS, _cross, mpf
+from tests.device_math_reference import DEFAULT_KIN, DPS, EPS, LINKS, _cross, mpf
 from tests.plant_restatement import Er, er_sinc_cos, er_sqrt
 
 G = PR.G
 PI = math.pi
 IK_BAR_MARGIN = 8.0
 SINCOS_EPS = 2.0  # sincos_joint's pinned absolute bar, in EPS
-DET_LO = max(EPS, 64.0 * EPS * float(np.abs(LINKS[0]).sum()) ** 3)  # the lower end of the closed-form band (swing_pd's `lo`)
+DET_LO = max(EPS, 64.0 * EPS * float(np.abs(LINKS[0]).sum()) ** 3)  # the lower end of the closed-form band (swing_pd's `lo`) at the default model:
+# all four legs share it there; at another model it is per leg, from that leg's own links (Kin.det_lo)
 DET_HI = 2.0 ** 52
 STATE = ("Rwb", "x", "xdot", "w", "joint_q", "joint_qdot")
 
@@ -62,15 +63,15 @@ def contact_mask(n, stance=None, gait_phase=None, gait_duty=None, default_duty=0
 
 
 # ------------------------------------------------------------------ leg kinematics, double
-def fk(leg, q):
-    l1, l2, l3 = LINKS[leg]
+def fk(leg, q, kin=DEFAULT_KIN):
+    l1, l2, l3 = kin.links[leg]
     t1, t2, t3 = q
     return np.array([l2 * math.sin(t2) + l3 * math.sin(t2 + t3), l1 * math.cos(t1) - l2 * math.sin(t1) * math.cos(t2) - l3 * math.sin(t1) * math.cos(t2 + t3),
-                     l1 * math.sin(t1) + l2 * math.cos(t1) * math.cos(t2) + l3 * math.cos(t1) * math.cos(t2 + t3)]) + HIP[leg]
+                     l1 * math.sin(t1) + l2 * math.cos(t1) * math.cos(t2) + l3 * math.cos(t1) * math.cos(t2 + t3)]) + kin.hip[leg]
 
 
-def jacobian(leg, q):
-    l1, l2, l3 = LINKS[leg]
+def jacobian(leg, q, kin=DEFAULT_KIN):
+    l1, l2, l3 = kin.links[leg]
     t1, t2, t3 = q
     s1, c1, s2, c2, s23, c23 = math.sin(t1), math.cos(t1), math.sin(t2), math.cos(t2), math.sin(t2 + t3), math.cos(t2 + t3)
     a, b = l2 * c2 + l3 * c23, l2 * s2 + l3 * s23
@@ -98,13 +99,13 @@ def _rank(A):
     return rank
 
 
-def force_from_torque(leg, q, tau):
-    """(g, singular): g = J^-T tau inside the band, pinv(J^T) tau with the device's rank rule outside"""
-    J = jacobian(leg, q)
+def force_from_torque(leg, q, tau, kin=DEFAULT_KIN):
+    """(g, singular): g = J^-T tau inside the band (the leg's own: Kin.det_lo), pinv(J^T) tau with the device's rank rule outside"""
+    J = jacobian(leg, q, kin)
     d = det3(J)
     if math.isnan(d):
         return np.full(3, np.nan), False
-    if DET_LO <= abs(d) <= DET_HI:
+    if kin.det_lo(leg) <= abs(d) <= DET_HI:
         return np.linalg.solve(J.T, np.asarray(tau, float)), False
     rank = _rank(J.T)
     U, s, Vt = np.linalg.svd(J.T)
@@ -114,10 +115,10 @@ def force_from_torque(leg, q, tau):
     return g, True
 
 
-def knee_cosine(leg, p):
+def knee_cosine(leg, p, kin=DEFAULT_KIN):
     """d of legInverseKinematics, rounded term by term as the reference's build does"""
-    x, y, z = (float(v) for v in np.asarray(p, float) - HIP[leg])
-    l1, l2, l3 = (abs(float(v)) for v in LINKS[leg])
+    x, y, z = (float(v) for v in np.asarray(p, float) - kin.hip[leg])
+    l1, l2, l3 = (abs(float(v)) for v in kin.links[leg])
     return (x * x + y * y + z * z - l1 * l1 - l2 * l2 - l3 * l3) / (2.0 * l2 * l3)
 
 
@@ -125,17 +126,17 @@ def _sqrt(v):
     return math.sqrt(v) if v >= 0.0 else float("nan")
 
 
-def ik(leg, p):
+def ik(leg, p, kin=DEFAULT_KIN):
     """(q, out_of_reach): kinematics.cpp:117-160"""
-    x, y, z = (float(v) for v in np.asarray(p, float) - HIP[leg])
-    l1, l2, l3 = (abs(float(v)) for v in LINKS[leg])
-    d = knee_cosine(leg, p)
+    x, y, z = (float(v) for v in np.asarray(p, float) - kin.hip[leg])
+    l1, l2, l3 = (abs(float(v)) for v in kin.links[leg])
+    d = knee_cosine(leg, p, kin)
     out = not (-1.0 <= d <= 1.0)
     if d > 1.0:
         d = 1.0
     rt = _sqrt(max(y * y + z * z - l1 * l1, 0.0))
     q = np.zeros(3)
-    if LINKS[leg][0] < 0.0:
+    if kin.links[leg][0] < 0.0:
         q[0] = math.atan2(z, y) + math.atan2(rt, -l1)
     else:
         q[0] = -(math.atan2(z, -y) + math.atan2(rt, -l1))
@@ -158,7 +159,7 @@ def wrap_pi(r):
 
 
 # ------------------------------------------------------------------ the step, numpy
-def leg_plant_step_np(mass, Ib, Rwb, x, xdot, w, joint_q, joint_qdot, joint_tau, mask, leg_inertia, dt):
+def leg_plant_step_np(mass, Ib, Rwb, x, xdot, w, joint_q, joint_qdot, joint_tau, mask, leg_inertia, dt, kin=DEFAULT_KIN):
     """One step for n robots; mask [n, 4] bool (contact_mask).  Returns a dict of NEW arrays Rwb, x, xdot, w, joint_q,
     joint_qdot, foot_world [n, 12], flags [n] int32 and the recovered forces g [n, 12] (0 for swing legs)."""
     n = x.shape[0]
@@ -171,9 +172,9 @@ def leg_plant_step_np(mass, Ib, Rwb, x, xdot, w, joint_q, joint_qdot, joint_tau,
     qn, qdn = q.copy(), qd.copy()
     for i in range(n):
         for l in range(4):
-            c[i, l] = x[i] + R[i] @ fk(l, q[i, l])
+            c[i, l] = x[i] + R[i] @ fk(l, q[i, l], kin)
             if mask[i, l]:
-                g[i, l], singular = force_from_torque(l, q[i, l], tq[i, l])
+                g[i, l], singular = force_from_torque(l, q[i, l], tq[i, l], kin)
                 flags[i] |= int(singular) << l
             else:
                 qdn[i, l] = qd[i, l] + dt * (tq[i, l] / inertia)
@@ -183,7 +184,7 @@ def leg_plant_step_np(mass, Ib, Rwb, x, xdot, w, joint_q, joint_qdot, joint_tau,
     for i in range(n):
         for l in range(4):
             if mask[i, l]:
-                qn[i, l], out = ik(l, R1[i].T @ (c[i, l] - body["x"][i]))
+                qn[i, l], out = ik(l, R1[i].T @ (c[i, l] - body["x"][i]), kin)
                 flags[i] |= int(out) << (4 + l)
                 qdn[i, l] = [wrap_pi(qn[i, l, k] - q[i, l, k]) / dt for k in range(3)]
     cc = np.ascontiguousarray
@@ -192,16 +193,16 @@ def leg_plant_step_np(mass, Ib, Rwb, x, xdot, w, joint_q, joint_qdot, joint_tau,
 
 
 # ------------------------------------------------------------------ the step, 50 digits with bars
-def _ik_mp(leg, p):
+def _ik_mp(leg, p, kin=DEFAULT_KIN):
     """legInverseKinematics on 50-digit inputs, d taken as is (the pool keeps |d| <= 0.9: no clamp, no NaN)"""
-    hx, hy, hz = (mpf(v) for v in HIP[leg])
-    l1, l2, l3 = (abs(mpf(v)) for v in LINKS[leg])
+    hx, hy, hz = (mpf(v) for v in kin.hip[leg])
+    l1, l2, l3 = (abs(mpf(v)) for v in kin.links[leg])
     x, y, z = p[0] - hx, p[1] - hy, p[2] - hz
     d = (x * x + y * y + z * z - l1 * l1 - l2 * l2 - l3 * l3) / (2 * l2 * l3)
     assert -1 < d < 1, "the 50-digit IK is written for a bent leg in reach"
     sc = y * y + z * z - l1 * l1
     rt = mp.sqrt(sc) if sc > 0 else mp.mpf(0)
-    if LINKS[leg][0] < 0.0:
+    if kin.links[leg][0] < 0.0:
         q1 = mp.atan2(z, y) + mp.atan2(rt, -l1)
     else:
         q1 = -(mp.atan2(z, -y) + mp.atan2(rt, -l1))
@@ -215,7 +216,7 @@ def _wrap_pi_mp(r):
     return r - mp.floor((r + mp.pi) / two_pi) * two_pi
 
 
-def leg_plant_step_mp(mass, Ib, Rwb, x, xdot, w, joint_q, joint_qdot, joint_tau, mask, leg_inertia, dt, g=G):
+def leg_plant_step_mp(mass, Ib, Rwb, x, xdot, w, joint_q, joint_qdot, joint_tau, mask, leg_inertia, dt, g=G, kin=DEFAULT_KIN):
     """One robot at 50 digits.  Returns {name: (value, bar)} for Rwb [9], x, xdot, w [3], foot_world, joint_q, joint_qdot [12].
     The bar of a stance leg's joint_q / joint_qdot entries is NaN here: stance_ik_bars measures it over the pool.  Also
     "knee" [4]: the 50-digit knee cosine d of the stance legs' IK (NaN for swing legs) and "det" [4]: det J of the stance legs."""
@@ -243,8 +244,8 @@ def leg_plant_step_mp(mass, Ib, Rwb, x, xdot, w, joint_q, joint_qdot, joint_tau,
             cs = [Er(mp.cos(a.v), 1.0, SINCOS_EPS) for a in q]
             s1, c1, s2, c2 = sn[0], cs[0], sn[1], cs[1]
             s23, c23 = s2 * cs[2] + c2 * sn[2], c2 * cs[2] - s2 * sn[2]
-            l1, l2, l3 = (T(v) for v in LINKS[leg])
-            hip = [T(v) for v in HIP[leg]]
+            l1, l2, l3 = (T(v) for v in kin.links[leg])
+            hip = [T(v) for v in kin.hip[leg]]
             p = [l2 * s2 + l3 * s23 + hip[0], l1 * c1 - l2 * s1 * c2 - l3 * s1 * c23 + hip[1], l1 * s1 + l2 * c1 * c2 + l3 * c1 * c23 + hip[2]]
             r = PR._mat_vec(R, p)
             C += [X[k] + r[k] for k in range(3)]
@@ -257,7 +258,7 @@ def leg_plant_step_mp(mass, Ib, Rwb, x, xdot, w, joint_q, joint_qdot, joint_tau,
                        J[1] * J[5] - J[2] * J[4], J[2] * J[3] - J[0] * J[5], J[0] * J[4] - J[1] * J[3]]
                 dj = J[1] * cof[1] + J[2] * cof[2]  # (J[0] = 0 exactly)
                 det[leg] = float(dj.v)
-                assert DET_LO <= abs(det[leg]) <= DET_HI, "the 50-digit step is written for the closed-form band"
+                assert kin.det_lo(leg) <= abs(det[leg]) <= DET_HI, "the 50-digit step is written for the closed-form band"
                 t = TQ[3 * leg:3 * leg + 3]
                 gl = [(cof[3 * r_] * t[0] + cof[3 * r_ + 1] * t[1] + cof[3 * r_ + 2] * t[2]) / dj for r_ in range(3)]
                 f = [-v for v in PR._mat_vec(R, gl)]
@@ -295,7 +296,7 @@ def leg_plant_step_mp(mass, Ib, Rwb, x, xdot, w, joint_q, joint_qdot, joint_tau,
         for leg in range(4):
             if mask[leg]:
                 pb = PR._mat_t_vec(R1, [C[3 * leg + k] - X1[k] for k in range(3)])
-                qn, d = _ik_mp(leg, [v.v for v in pb])
+                qn, d = _ik_mp(leg, [v.v for v in pb], kin)
                 knee[leg] = float(d)
                 for k in range(3):
                     QN[3 * leg + k] = Er(qn[k])
@@ -332,19 +333,19 @@ def bent_legs(rng, n):
     return q.reshape(n, 12)
 
 
-def pool_margins(q, mask):
-    """(max |d|, min |det J| / DET_LO) over the stance legs of joint angles q [n, 12]: the two margins of the pools"""
+def pool_margins(q, mask, kin=DEFAULT_KIN):
+    """(max |d|, min |det J| / the leg's DET_LO) over the stance legs of joint angles q [n, 12]: the two margins of the pools"""
     q = np.asarray(q).reshape(-1, 4, 3)
     dmax, detmin = 0.0, np.inf
     for i in range(q.shape[0]):
         for l in range(4):
             if mask[i, l]:
-                dmax = max(dmax, abs(knee_cosine(l, fk(l, q[i, l]))))
-                detmin = min(detmin, abs(det3(jacobian(l, q[i, l]))) / DET_LO)
+                dmax = max(dmax, abs(knee_cosine(l, fk(l, q[i, l], kin), kin)))
+                detmin = min(detmin, abs(det3(jacobian(l, q[i, l], kin))) / kin.det_lo(l))
     return dmax, detmin
 
 
-def make_pool(n, seed):
+def make_pool(n, seed, kin=DEFAULT_KIN):
     """n robots for the one-step tests: tilted up to 0.4 rad about a random axis on top of any yaw, near the stand height, moving
     and turning at a few dm/s and rad/s (every fourth one with w = 0 exactly); bent legs (bent_legs) with joint velocities up to
     2 rad/s; torques tau = J^T g of ground-reaction-sized forces g (|tau| < 20: inside the tick's clamp); uniformly random gait
@@ -357,8 +358,8 @@ def make_pool(n, seed):
     R = (Rotation.from_rotvec(tilt) * Rotation.from_euler("z", rng.uniform(-PI, PI, n))).as_matrix()
     q = bent_legs(rng, n)
     g = rng.uniform(-1, 1, (n, 4, 3)) * np.array([10.0, 10.0, 25.0]) - np.array([0.0, 0.0, 25.0])
-    tau = np.array([[jacobian(l, q.reshape(n, 4, 3)[i, l]).T @ g[i, l] for l in range(4)] for i in range(n)])
-    assert np.abs(tau).max() < 20.0
+    tau = np.array([[jacobian(l, q.reshape(n, 4, 3)[i, l], kin).T @ g[i, l] for l in range(4)] for i in range(n)])
+    assert kin.tau_min < tau.min() and tau.max() < kin.tau_max  # (the default model's: |tau| < 20)
     w = rng.uniform(-2, 2, (n, 3))
     w[0::4] = 0.0
     c = np.ascontiguousarray

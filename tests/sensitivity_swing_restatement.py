@@ -28,7 +28,7 @@ import numpy as np
 
 from oracle import tick_restatement as TR
 from tests import leg_plant_adjoint_restatement as LA
-from tests.device_math_reference import DPS, EPS, HIP, LINKS, mpf
+from tests.device_math_reference import DEFAULT_KIN, DPS, EPS, mpf
 from tests.leg_plant_adjoint_restatement import Cs, _Float, _ik, _ik_reverse, _in_band, _Leg, _Mp, _mtv, _mv
 
 PER_LEG = ("swing_pos_bar", "swing_vel_bar", "joint_q_bar", "joint_qdot_bar", "gain_bar")
@@ -45,6 +45,12 @@ TAU_MIN, TAU_MAX = -20.0, 20.0
 # Measured over the first 65 robots of the pool: 0.0032, 0.712, 0.978, 0 (kd = 1: exact), 1.081, 0.0011, 0.0006 - the outputs behind
 # J^-T carry condition sums that compound through the cofactors, so their figures are small.
 C_SWING = {"swing_pos_bar": 0.1, "swing_vel_bar": 0.8, "joint_q_bar": 1.0, "joint_qdot_bar": 0.1, "gain_bar": 1.2, "Rwb_bar": 0.1, "x_bar": 0.1}
+# C_SWING_ODD: the same measurement at device_math_reference.ODD_KIN over the first 65 robots of model_pool(ODD_KIN) - clamped on both sides in
+# every joint, torques within |kff| of a limit among them: 0.0021, 1.555, 0.985, 0 (one product, rounded once in either arithmetic),
+# 1.163, 0.0005, 0.0003 (tests/test_sensitivity_swing_cpu.py::test_float64_against_50_digits_at_the_odd_model prints and asserts them).  Never
+# measured on the device.
+C_SWING_ODD = {"swing_pos_bar": 0.1, "swing_vel_bar": 1.7, "joint_q_bar": 1.0, "joint_qdot_bar": 0.1, "gain_bar": 1.2, "Rwb_bar": 0.1, "x_bar": 0.1}
+C_SWING_OF = {"default": C_SWING, "odd": C_SWING_ODD}
 TWO_PI = 2.0 * math.pi
 
 
@@ -58,23 +64,25 @@ def _two_pi(A, k):
     return Cs(2 * mp.pi * k) if A is _Mp else TWO_PI * k
 
 
-def _swing_leg(A, leg, R, x, pos, vel, q, qdot, tb, ik, kp=KP, kd=KD, kff=KFF, tau_min=TAU_MIN, tau_max=TAU_MAX):
-    """One swing leg in arithmetic A on flat float inputs.  Returns (dict name -> list of A-values or None if flagged, flagged, tau_raw
-    as floats or None)."""
+def _swing_leg(A, leg, R, x, pos, vel, q, qdot, tb, ik, kp=None, kd=None, kff=None, tau_min=None, tau_max=None, kin=DEFAULT_KIN):
+    """One swing leg in arithmetic A on flat float inputs.  Gains and limits left out are the model's (at the default model: KP, KD,
+    KFF, TAU_MIN, TAU_MAX).  Returns (dict name -> list of A-values or None if flagged, flagged, tau_raw as floats or None)."""
+    kp, kd, kff = (kin.jc_kp if kp is None else kp), (kin.jc_kd if kd is None else kd), (kin.jc_kff if kff is None else kff)
+    tau_min, tau_max = (kin.tau_min if tau_min is None else tau_min), (kin.tau_max if tau_max is None else tau_max)
     if not all(math.isfinite(v) for v in list(R) + list(x) + list(pos) + list(vel)):
         return None, True, None
     c = A.const
     Rm, posA, velA = [c(v) for v in R], [c(v) for v in pos], [c(v) for v in vel]
     rp, vb = _mtv(Rm, posA), _mtv(Rm, velA)
     pb = [rp[k] - c(x[k]) for k in range(3)]
-    qr, dv, tape = _ik(A, leg, pb)
+    qr, dv, tape = _ik(A, leg, pb, kin)
     if qr is None or not dv < 1.0:  # d >= 1: clamped, no slope; d < -1: NaN
         return None, True, None
     y, z, l1 = tape[1], tape[2], tape[6]
     if A.val(y * y + z * z - l1 * l1) < 0.0:
         return None, True, None
-    L = _Leg(A, leg, qr)
-    if not _in_band(A.val(L.det)):
+    L = _Leg(A, leg, qr, kin)
+    if not _in_band(A.val(L.det), L.det_lo):
         return None, True, None
     qd = L.solve(vb)
     kpA, kdA, kffA = [c(v) for v in kp], [c(v) for v in kd], [c(v) for v in kff]
@@ -94,7 +102,7 @@ def _swing_leg(A, leg, R, x, pos, vel, q, qdot, tb, ik, kp=KP, kd=KD, kff=KFF, t
     return out, False, raw
 
 
-def _swing_adjoint(A, b, swing, tau_bar, ins, ik):
+def _swing_adjoint(A, b, swing, tau_bar, ins, ik, kin=DEFAULT_KIN):
     """The batch in arithmetic A.  b: dict of float arrays (Rwb [n,9], x [n,3], joint_q, joint_qdot, swing_pos, swing_vel [n,12]); swing:
     [n,4] bool; tau_bar [n,12]; ins: dict of the optional `_in` arrays.  Returns (values, condition sums or None, flags, tau_raw)."""
     n = b["x"].shape[0]
@@ -121,7 +129,7 @@ def _swing_adjoint(A, b, swing, tau_bar, ins, ik):
         for leg in range(4):
             rows = {k: start(k, (i, leg)) for k in PER_LEG}
             if swing[i, leg]:
-                out, bad, tr = _swing_leg(A, leg, R[i], x[i], pos[i, leg], vel[i, leg], q[i, leg], qdot[i, leg], tb[i, leg], ik)
+                out, bad, tr = _swing_leg(A, leg, R[i], x[i], pos[i, leg], vel[i, leg], q[i, leg], qdot[i, leg], tb[i, leg], ik, kin=kin)
                 if bad:
                     flags[i] |= 1 << leg
                     flagged = True
@@ -141,16 +149,16 @@ def _swing_adjoint(A, b, swing, tau_bar, ins, ik):
     return val, cond, flags, raw
 
 
-def swing_adjoint_np(b, swing, tau_bar, ik="jacobian", **ins):
+def swing_adjoint_np(b, swing, tau_bar, ik="jacobian", kin=DEFAULT_KIN, **ins):
     """float64: (dict of outputs, flags [n] int32, tau_raw [n,4,3] - NaN for stance and flagged legs)"""
-    val, _, flags, raw = _swing_adjoint(_Float, b, np.asarray(swing, bool), tau_bar, ins, ik)
+    val, _, flags, raw = _swing_adjoint(_Float, b, np.asarray(swing, bool), tau_bar, ins, ik, kin)
     return val, flags, raw
 
 
-def swing_adjoint_mp(b, swing, tau_bar, ik="chain", **ins):
+def swing_adjoint_mp(b, swing, tau_bar, ik="chain", kin=DEFAULT_KIN, **ins):
     """50 digits: (dict of outputs rounded to double, dict of condition sums, flags, tau_raw)"""
     with mp.workdps(DPS):
-        return _swing_adjoint(_Mp, b, np.asarray(swing, bool), tau_bar, ins, ik)
+        return _swing_adjoint(_Mp, b, np.asarray(swing, bool), tau_bar, ins, ik, kin)
 
 
 # ------------------------------------------------------------------ the forward pass, from the oracle's own functions
@@ -188,11 +196,16 @@ def masks(n, seed=5):
     return m
 
 
-def pool(n=POOL, seed=11, saturate=False):
+def pool(n=POOL, seed=11, saturate=False, kin=DEFAULT_KIN, near_limit=False):
     """n robots whose four swing references are all inside reach: q_ref = HOME + U(-0.3, 0.3)^3, the target FK(q_ref) moved to the
     world frame the way the tick reads it back (pos = Rwb (p_b + x)), |q_ref - q| < 0.15 rad, |qdot| < 0.5 rad/s, |vel| < 0.1 m/s:
     kp |e| < 7.5 and kd |qd - qdot| stays below ~3, so every torque is strictly inside +-20 and no wrap is crossed.  saturate=True
-    moves q of every third leg by +-0.8 rad in one joint: that torque is clamped (kp 0.65 - 3 > 20)."""
+    moves q of every third leg by +-0.8 rad in one joint: that torque is clamped (kp 0.65 - 3 > 20).  The targets are FK(q_ref) of
+    `kin`, so the pool is rebuilt in reach under any model (the figures above are the default model's).  saturate="every joint"
+    does the same with the joint moved taken in turn, so that every joint is clamped on both sides.  near_limit=True then moves one
+    joint of every leg of every robot i = 5 mod 8 so that its raw torque (the float64 restatement's, the model's gains) lands half a
+    |kff_c| beyond a limit: clamped with kff, passing without it - and, on alternate legs, inside it by as much.  A model with kff =
+    0 has no such point (refused)."""
     rng = np.random.default_rng(seed)
     b = {"Rwb": np.zeros((n, 9)), "x": rng.uniform(-0.2, 0.2, (n, 3)), "joint_q": np.zeros((n, 12)), "joint_qdot": rng.uniform(-0.5, 0.5, (n, 12)),
          "swing_pos": np.zeros((n, 12)), "swing_vel": rng.uniform(-0.1, 0.1, (n, 12))}
@@ -201,13 +214,31 @@ def pool(n=POOL, seed=11, saturate=False):
         b["Rwb"][i] = R.reshape(9)
         for leg in range(4):
             q_ref = np.asarray(HOME) + rng.uniform(-0.3, 0.3, 3)
-            p_b = LA.LR.fk(leg, q_ref)
+            p_b = LA.LR.fk(leg, q_ref, kin)
             b["swing_pos"][i, 3 * leg:3 * leg + 3] = R @ (p_b + b["x"][i])
             qq = q_ref + rng.uniform(-0.15, 0.15, 3)
             if saturate and (4 * i + leg) % 3 == 0:
-                qq[(i + leg) % 3] += 0.8 if i % 2 else -0.8
+                # ((4 i + leg) % 3 == 0 makes (i + leg) % 3 == 0: saturate=True always moves joint 0; "every joint" takes them in turn)
+                qq[(i + 2 * leg) % 3 if saturate == "every joint" else (i + leg) % 3] += 0.8 if i % 2 else -0.8
             b["joint_q"][i, 3 * leg:3 * leg + 3] = qq
+    if near_limit:
+        assert all(v != 0.0 for v in kin.jc_kff)
+        for i, leg in ((i, leg) for i in range(5, n, 8) for leg in range(4)):
+            c, sl = (i // 8 + leg) % 3, slice(3 * leg, 3 * leg + 3)
+            _, bad, raw = _swing_leg(_Float, leg, b["Rwb"][i], b["x"][i], b["swing_pos"][i, sl], b["swing_vel"][i, sl], b["joint_q"][i, sl],
+                                     b["joint_qdot"][i, sl], (1.0, 1.0, 1.0), "jacobian", kin=kin)
+            assert not bad
+            kff = kin.jc_kff[c]
+            lim = kin.tau_max if kff > 0.0 else kin.tau_min  # the limit kff pushes towards
+            target = lim + 0.5 * kff if leg % 2 == 0 else lim - 0.5 * kff  # beyond it by |kff| / 2, or inside it by as much
+            b["joint_q"][i, 3 * leg + c] += (raw[c] - target) / kin.jc_kp[c]  # tau_raw_c falls by kp_c per radian of q_c
     return b
+
+
+def model_pool(kin, n=POOL):
+    """The pool of the 50-digit comparisons under `kin`: the default model's is pool() as it always was (unclamped); any other model's
+    is clamped on both sides in every joint and has torques within |kff| of a limit."""
+    return pool(n) if kin.name == "default" else pool(n, kin=kin, saturate="every joint", near_limit=True)
 
 
 def cotangent(n, seed=23):
@@ -222,17 +253,17 @@ def accumulators(n, seed=29):
 FLAGGED = ("stretched", "inside", "nonfinite", "folded")
 
 
-def flagged_pool():
+def flagged_pool(kin=DEFAULT_KIN):
     """Four robots, all legs swinging, leg k of robot k constructed outside the smooth domain: stretched (a target 1 m below the hip: d
     > 1, clamped), inside the hip roll's cylinder (the target on the hip axis: y^2 + z^2 < l1^2), a non-finite target, and inside the
     inner reach limit (the target 1 cm from the hip-roll offset point: d < -1).  Returns (b, expected flags)."""
-    b = pool(4, seed=31)
+    b = pool(4, seed=31, kin=kin)
     R = b["Rwb"].reshape(4, 3, 3)
     place = lambda i, leg, p_b: b["swing_pos"][i].__setitem__(slice(3 * leg, 3 * leg + 3), R[i] @ (np.asarray(p_b) + b["x"][i]))
-    place(0, 0, HIP[0] + np.array([0.0, 0.0, -1.0]))
-    place(1, 1, HIP[1] + np.array([0.1, 0.0, -0.01]))
+    place(0, 0, kin.hip[0] + np.array([0.0, 0.0, -1.0]))
+    place(1, 1, kin.hip[1] + np.array([0.1, 0.0, -0.01]))
     b["swing_pos"][2, 6] = np.inf
-    place(3, 3, HIP[3] + np.array([0.0, float(LINKS[3][0]), -0.01]))
+    place(3, 3, kin.hip[3] + np.array([0.0, float(kin.links[3][0]), -0.01]))
     return b, np.array([1, 2, 4, 8], np.int32)
 
 
@@ -243,7 +274,7 @@ STATE = LA.INPUTS[:-1]
 LIFT = 0.02
 
 
-def trot_start(n=ROLLOUT_N):
+def trot_start(n=ROLLOUT_N, kin=DEFAULT_KIN):
     """leg_plant_adjoint_restatement.stand_start's generic standing placement on a trot mask - the two diagonals in turn -, the swing
     references HELD: every foot's world position at the start raised by LIFT, at rest.  The swing legs' errors stay below 0.2 rad, so
     their torques stay inside the limits."""
@@ -254,7 +285,7 @@ def trot_start(n=ROLLOUT_N):
     # (the tick reads the reference back as Rwb^T pos - x, sic: the held point is placed so that THAT lands LIFT above the foot)
     for i in range(n):
         for leg in range(4):
-            p_b = LA.LR.fk(leg, b["joint_q"][i, 3 * leg:3 * leg + 3]) + R[i].T @ np.array([0.0, 0.0, LIFT])
+            p_b = LA.LR.fk(leg, b["joint_q"][i, 3 * leg:3 * leg + 3], kin) + R[i].T @ np.array([0.0, 0.0, LIFT])
             pos[i, 3 * leg:3 * leg + 3] = R[i] @ (p_b + b["x"][i])
     b["swing_pos"], b["swing_vel"] = np.ascontiguousarray(pos), np.zeros((n, 12))
     return b

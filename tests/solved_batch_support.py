@@ -39,6 +39,27 @@ def ctls(q):
         c.close()
 
 
+def odd_handle(q, kind="uniform"):
+    """a NEW handle at params(q, kind) with ODD_KIN's hip and links (the caller's fixture owns and closes it; never set_kinematics on
+    a shared one)"""
+    from tests.device_math_reference import ODD_KIN
+
+    c = q.BalanceController.from_params(params(q, kind), device=0)
+    c.set_kinematics(hip=ODD_KIN.hip.reshape(12), links=ODD_KIN.links.reshape(12))
+    return c
+
+
+def odd_inputs(n):
+    """inputs(n, "joint_q") for a handle at ODD_KIN: (the batch the device reads - joint_q and gait_phase, no feet -, the same batch
+    with `feet` = ODD_KIN's forward kinematics of joint_q for the numpy restatements, the forces, kin = (hip [12], links [12]) for the
+    50-digit passes)"""
+    from tests import kkt_certificate_restatement as KR
+    from tests.device_math_reference import ODD_KIN
+
+    b, grf = inputs(n, "joint_q")
+    return b, KR.with_feet(b, ODD_KIN), grf, (ODD_KIN.hip.reshape(-1), ODD_KIN.links.reshape(-1))
+
+
 @functools.lru_cache(maxsize=None)
 def inputs(n, source):
     """(batch, world forces): contact pattern i % 16; even robots level (Rwb = I).  source: 'feet' with stance bytes, 'joint_q' with

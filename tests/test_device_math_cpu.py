@@ -189,3 +189,28 @@ def test_probe_wraps_the_wrench_and_the_foothold():
     assert "wrench_from_state<4, KIN>(params(), S, f, 0, W)" in src and "plan_foothold(params(), l, R, x, xdot, w, xdd, pc, o)" in src
     for word in ("angle_axis_total(Re", "9.81", "kff[", "sqrt("):
         assert word not in src.split("extern \"C\"")[0], word
+
+
+def test_odd_kin_is_off_every_symmetry_of_the_default_model():
+    """ODD_KIN against the default model: every link and hip x, y is the default times a factor in [0.8, 1.25], all twelve factors of
+    each distinct; the links keep their signs, no two legs share a length and |l2| != |l3| on every leg; hip z is non-zero, of both
+    signs, within 0.04; nine distinct gains, no kd equal to 1, kff non-zero with mixed signs and at most 0.5; asymmetric limits; an
+    anisotropic leg inertia.  The default model's per-leg band end is the one constant the restatements always used."""
+    from tests import leg_plant_restatement as LR
+
+    k, d = R.ODD_KIN, R.DEFAULT_KIN
+    f = k.links / d.links
+    assert (f >= 0.8).all() and (f <= 1.25).all() and len(set(np.round(f.reshape(-1), 9))) == 12
+    assert (np.sign(k.links) == np.sign(d.links)).all()
+    for c in range(3):
+        assert len(set(np.abs(k.links[:, c]))) == 4
+    assert (np.abs(k.links[:, 1]) != np.abs(k.links[:, 2])).all()
+    h = k.hip[:, :2] / d.hip[:, :2]
+    assert (h >= 0.8).all() and (h <= 1.25).all() and len(set(np.round(h.reshape(-1), 9))) == 8 and len(set(k.hip.reshape(-1))) == 12
+    z = k.hip[:, 2]
+    assert (z != 0).all() and (z > 0).any() and (z < 0).any() and (np.abs(z) <= 0.04).all()
+    gains = k.jc_kp + k.jc_kd + k.jc_kff
+    assert len(set(gains)) == 9 and 1.0 not in k.jc_kd and all(v != 0 for v in k.jc_kff) and min(k.jc_kff) < 0 < max(k.jc_kff)
+    assert max(abs(v) for v in k.jc_kff) <= 0.5 and k.tau_min != -k.tau_max and k.tau_min < 0 < k.tau_max
+    assert len(set(k.leg_inertia)) == 3
+    assert all(d.det_lo(leg) == LR.DET_LO for leg in range(4)) and len({k.det_lo(leg) for leg in range(4)}) == 4

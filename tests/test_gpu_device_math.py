@@ -28,6 +28,13 @@ def P():
     return D
 
 
+def _set_model(D, kin, t_stance=0.8, gains=None, wrench=None):
+    """the probe's constants at the model `kin` (gains: (kff, kp, kd) instead of the model's)"""
+    _, basis = R.sextic_basis_mp()
+    kff, kp, kd = gains or (kin.jc_kff, kin.jc_kp, kin.jc_kd)
+    D.set_params(kin.hip, kin.links, kff, kp, kd, basis, 0.18, t_stance, 0.08, wrench=wrench)
+
+
 def _ulp_walk(x, k):
     """x and its +-1 ... k ulp neighbours"""
     out = [x]
@@ -214,12 +221,22 @@ def test_wraps(P):
 
 
 def test_swing_pd_error_fast_vs_reference(P):
+    """_swing_pd_error_fast_vs_reference at the default model"""
+    _swing_pd_error_fast_vs_reference(P, "default")
+
+
+def test_swing_pd_error_fast_vs_reference_at_the_odd_model(P):
+    """_swing_pd_error_fast_vs_reference with ODD_KIN's hip and links"""
+    _swing_pd_error_fast_vs_reference(P, "odd")
+
+
+def _swing_pd_error_fast_vs_reference(P, model):
     """The PD error e of swing_pd<FAST> (multiplication-form wraps, Newton reciprocal) and swing_pd<false> (numerics.cpp's
     wraps, a division) agree to 2 ulp(2 pi), or both lie within 1e-14 of +-pi (a +pi / -pi flip is a torque jump of 2 pi kp:
-    only allowed where the inputs sit on the branch).  kp = 1, kd = kff = 0 in the constants so the torque is e itself."""
+    only allowed where the inputs sit on the branch).  kp = 1, kd = kff = 0 in the constants so the torque is e itself; hip and
+    links are the model's."""
     D = P
-    _, basis = R.sextic_basis_mp()
-    D.set_params(R.HIP, R.LINKS, (0, 0, 0), (1, 1, 1), (0, 0, 0), basis, 0.18, 0.8, 0.08)
+    _set_model(D, R.KINS[model], gains=((0, 0, 0), (1, 1, 1), (0, 0, 0)))
     try:
         rng = np.random.default_rng(6)
         n = 60_000
@@ -236,13 +253,33 @@ def test_swing_pd_error_fast_vs_reference(P):
         branch = (np.abs(np.abs(tf) - np.pi) <= 1e-14) & (np.abs(np.abs(tr) - np.pi) <= 1e-14)
         assert (close | branch).all(), f"{(~(close | branch)).sum()} PD errors differ: {tf[~(close | branch)][:4]} vs {tr[~(close | branch)][:4]}"
     finally:
-        D.set_params(R.HIP, R.LINKS, R.JC_KFF, R.JC_KP, R.JC_KD, basis, 0.18, 0.8, 0.08)
+        _set_model(D, R.DEFAULT_KIN)
 
 
 # ---------------------------------------------------------------- leg kinematics
 def test_leg_fk_and_jt_force(P):
+    """_leg_fk_and_jt_force_at at the default model"""
+    _leg_fk_and_jt_force_at(P, "default")
+
+
+def test_leg_fk_and_jt_force_at_the_odd_model(P):
+    """_leg_fk_and_jt_force_at at ODD_KIN"""
+    _leg_fk_and_jt_force_at(P, "odd")
+
+
+def _leg_fk_and_jt_force_at(P, model):
     """leg_trig + leg_fk <= 8 EPS sum|l|; leg_jt_force (both overloads) <= 16 EPS sum|l| |f| against long double, random q in
-    [-pi, pi]^3 and +-50 rad, all four legs; J^T f of the two overloads bit-identical."""
+    [-pi, pi]^3 and +-50 rad, all four legs; J^T f of the two overloads bit-identical.  At ODD_KIN every leg has its own links and
+    a hip with z != 0; the bars are the same expressions of the model's links."""
+    kin = R.KINS[model]
+    _set_model(P, kin)
+    try:
+        _leg_fk_and_jt_force(P, kin)
+    finally:
+        _set_model(P, R.DEFAULT_KIN)
+
+
+def _leg_fk_and_jt_force(P, kin):
     rng = np.random.default_rng(8)
     n = 200_000
     q = np.concatenate([rng.uniform(-np.pi, np.pi, (n // 2, 3)), rng.uniform(-50, 50, (n // 2, 3))])
@@ -250,13 +287,13 @@ def test_leg_fk_and_jt_force(P):
     legs = rng.integers(0, 4, n)
     _, p, tc, tg = P.leg(legs, q, f)
     np.testing.assert_array_equal(tc, tg)
-    lsum = np.abs(R.LINKS).sum(1)
+    lsum = np.abs(kin.links).sum(1)
     for leg in range(4):
         sel = legs == leg
-        pr = R.leg_fk_ld(leg, q[sel])
+        pr = R.leg_fk_ld(leg, q[sel], kin)
         err = float(np.abs(p[sel] - pr).max())
         assert err <= 8 * EPS * lsum[leg], f"FK leg {leg}: {err:.3e}"
-        J = R.leg_jacobian_ld(leg, q[sel])
+        J = R.leg_jacobian_ld(leg, q[sel], kin)
         tr = np.einsum("nij,ni->nj", J, f[sel].astype(np.longdouble))
         terr = np.abs(tc[sel] - tr).max(1) / np.abs(f[sel]).sum(1)
         assert terr.max() <= 16 * EPS * lsum[leg], f"J^T f leg {leg}: {float(terr.max()):.3e} per |f|"
@@ -461,47 +498,57 @@ def test_pinv3_apply(P):
 
 
 # ---------------------------------------------------------------- leg_swing_torque
-def _swing_cases(rng):
+def _swing_cases(rng, kin=R.DEFAULT_KIN):
     legs, pb = [], []
     for _ in range(300):  # inside the workspace: FK of a knee-bent posture
         leg = int(rng.integers(0, 4))
         q = np.array([[rng.uniform(-0.6, 0.6), rng.uniform(-0.2, 1.4), rng.uniform(-2.4, -0.3)]])
-        legs.append(leg); pb.append(np.asarray(R.leg_fk_ld(leg, q)[0], np.float64))
+        legs.append(leg); pb.append(np.asarray(R.leg_fk_ld(leg, q, kin)[0], np.float64))
     for leg in range(4):  # near full stretch: the knee cosine d = 1 - k 2^-53 (to the rounding of the target), k <= 8
         for k in range(1, 9):
             q3 = -math.sqrt(2.0 * k * 2.0 ** -53)
             q = np.array([[rng.uniform(-0.3, 0.3), rng.uniform(0.0, 0.8), q3]])
-            legs.append(leg); pb.append(np.asarray(R.leg_fk_ld(leg, q)[0], np.float64))
+            legs.append(leg); pb.append(np.asarray(R.leg_fk_ld(leg, q, kin)[0], np.float64))
     for leg in range(4):  # the foot near the hip's x axis (rho^2 -> 0, rt -> 0 after the lateral clamp)
         for r in (1e-3, 1e-6):
-            hip = R.HIP[leg]
+            hip = kin.hip[leg]
             legs.append(leg); pb.append(hip + np.array([0.2, r, -r]))
     for _ in range(12):  # out of reach: d clamped to 1, q3 = 0, J of rank 2 (the pseudo-inverse inside swing_pd)
         leg = int(rng.integers(0, 4))
         u = rng.normal(size=3); u /= np.linalg.norm(u)
-        legs.append(leg); pb.append(R.HIP[leg] + u * rng.uniform(0.6, 2.0))
+        legs.append(leg); pb.append(kin.hip[leg] + u * rng.uniform(0.6, 2.0))
     for leg in range(4):  # fully folded: d = -1 exactly (u = 0, q3 = pi), again the pseudo-inverse
-        p = _folded_target(leg, rng)
+        p = _folded_target(leg, rng, kin)
         legs.append(leg); pb.append(p)
     return np.array(legs), np.array(pb)
 
 
-def _folded_target(leg, rng):
+def _folded_target(leg, rng, kin=R.DEFAULT_KIN):
     """A target whose float64 knee cosine is exactly -1: |p - hip|^2 = l1^2 + (l2 - l3)^2, walked by ulps until it rounds there"""
-    l1, l2, l3 = np.abs(R.LINKS[leg])
+    l1, l2, l3 = np.abs(kin.links[leg])
     rad = math.sqrt(l1 * l1 + (l2 - l3) ** 2)
     phi = rng.uniform(-2.5, -0.6)  # x = 0 relative to the hip, (y, z) on a circle outside the lateral offset l1
-    p = R.HIP[leg] + rad * np.array([0.0, math.cos(phi), math.sin(phi)])
+    p = kin.hip[leg] + rad * np.array([0.0, math.cos(phi), math.sin(phi)])
     for _ in range(4000):
-        d = R.knee_cosine_double(leg, p)
+        d = R.knee_cosine_double(leg, p, kin)
         if d == -1.0:
             return p
-        outward = np.sign(p[2] - R.HIP[leg][2])  # |z - hip_z| grows with z moved this way
+        outward = np.sign(p[2] - kin.hip[leg][2])  # |z - hip_z| grows with z moved this way
         p = p.copy(); p[2] = np.nextafter(p[2], outward * np.inf if d < -1.0 else -outward * np.inf)
     raise AssertionError("no target with d = -1 found")
 
 
 def test_leg_swing_torque(P):
+    """_leg_swing_torque_at at the default model"""
+    _leg_swing_torque_at(P, "default")
+
+
+def test_leg_swing_torque_at_the_odd_model(P):
+    """_leg_swing_torque_at at ODD_KIN"""
+    _leg_swing_torque_at(P, "odd")
+
+
+def _leg_swing_torque_at(P, model):
     """The trig-free swing-leg torque against a 50-digit legInverseKinematics -> legJacobian^-1 -> joint PD.  Bar:
     c EPS cond(J) (|kp| pi + |kd| (|J^-1 vb| + |qdot|)) with c = 64: the IK angles carry a few ulps of the target (~8 roundings
     of lengths of order sum|l|), the inverse amplifies them by cond(J), and the rest is a dozen rounded products; 64 leaves ~4x
@@ -510,9 +557,20 @@ def test_leg_swing_torque(P):
     The knee cosine d is the one input whose conditioning cond(J) does not cover: near full stretch q3 ~ -sqrt(2 (1 - d)), so one
     ulp of d moves q3, and J^-1 vb with it, by a fraction 1 / k of itself at d = 1 - k 2^-53.  The reference rounds d in float64,
     every operation on its own, and the device computes it the same way (ik_knee_num, a true division), so the reference is
-    evaluated at that double d and the device must agree with it there, with no allowance for another d."""
+    evaluated at that double d and the device must agree with it there, with no allowance for another d.
+    At ODD_KIN the cases - the knee-cosine boundary ones among them - are rebuilt from the model's hip and links, and the gains
+    in the bar are the model's (kff adds one exact term)."""
+    kin = R.KINS[model]
+    _set_model(P, kin)
+    try:
+        _leg_swing_torque(P, kin)
+    finally:
+        _set_model(P, R.DEFAULT_KIN)
+
+
+def _leg_swing_torque(P, kin):
     rng = np.random.default_rng(15)
-    legs, pb = _swing_cases(rng)
+    legs, pb = _swing_cases(rng, kin)
     n = len(legs)
     vb = rng.normal(size=(n, 3)) * 0.5
     q = rng.uniform(-np.pi, np.pi, (n, 3))
@@ -520,18 +578,18 @@ def test_leg_swing_torque(P):
     tau = P.swing_torque(legs, pb, vb, q, qdot)
     saw = dict(pinv=0, folded=0)
     for i in range(n):
-        d0 = min(R.knee_cosine_double(int(legs[i]), pb[i]), 1.0)
-        ref, cond, _, qdn = R.swing_torque_mp(int(legs[i]), pb[i], vb[i], q[i], qdot[i], d=d0)
+        d0 = min(R.knee_cosine_double(int(legs[i]), pb[i], kin), 1.0)
+        ref, cond, _, qdn = R.swing_torque_mp(int(legs[i]), pb[i], vb[i], q[i], qdot[i], d=d0, kin=kin)
         saw["pinv"] += d0 == 1.0
         saw["folded"] += d0 == -1.0
-        bar = 64 * EPS * cond * (max(R.JC_KP) * np.pi + max(R.JC_KD) * (qdn + np.abs(qdot[i]).max()))
+        bar = 64 * EPS * cond * (max(kin.jc_kp) * np.pi + max(kin.jc_kd) * (qdn + np.abs(qdot[i]).max()))
         err = float(np.abs(tau[i] - ref).max())
         assert err <= bar, f"leg {legs[i]} target {pb[i]!r}: err {err:.3e} > {bar:.3e} (cond {cond:.3e})"
     assert saw["pinv"] >= 12 and saw["folded"] == 4, saw
 
 
 # ---------------------------------------------------------------- wrench_from_state, plan_foothold
-def _wrench_setup(P, seed):
+def _wrench_setup(P, seed, kin=R.DEFAULT_KIN):
     """The probe's constants with every quirk of the wrench law visible (device_math_reference._wrench_params: kff[3..5] all
     different and non-zero, a full non-diagonal Ib, non-uniform gains) and a planner; returns (params dict, restore())."""
 
@@ -540,22 +598,22 @@ def _wrench_setup(P, seed):
     W["planner_hip"] = (R.HIP + rng.uniform(-0.01, 0.01, (4, 3))).reshape(12)
     W["planner_k"] = 0.07
     _, basis = R.sextic_basis_mp()
-    P.set_params(R.HIP, R.LINKS, R.JC_KFF, R.JC_KP, R.JC_KD, basis, 0.18, 0.31, 0.08, wrench=W)
+    P.set_params(kin.hip, kin.links, kin.jc_kff, kin.jc_kp, kin.jc_kd, basis, 0.18, 0.31, 0.08, wrench=W)
     return W, lambda: P.set_params(R.HIP, R.LINKS, R.JC_KFF, R.JC_KP, R.JC_KD, basis, 0.18, 0.8, 0.08)
 
 
-def _check_wrench(P, W, b, fp, kin, sample, tag):
+def _check_wrench(P, W, b, fp, kin, sample, tag, model=R.DEFAULT_KIN):
     """b and r of the probe against wrench_ld on every state and wrench_mp on `sample`; returns the worst error / bar"""
     bd, rd, fin = P.wrench(b, fp, kin)
     assert np.array_equal(fin, np.zeros_like(fin)), (tag, fin[fin != 0][:4])
-    ref = R.wrench_ld(W, b, fp, kin=(R.HIP, R.LINKS) if kin else None)
+    ref = R.wrench_ld(W, b, fp, kin=(model.hip, model.links) if kin else None)
     worst = 0.0
     for got, (val, cond, cnt) in ((bd, ref["b"]), (rd, ref["r"])):
         ratio = np.abs(got.astype(np.longdouble) - val) / (cnt * EPS * cond)
         worst = max(worst, float(ratio.max()))
         assert ratio.max() <= 1.0, (tag, kin, float(ratio.max()), np.unravel_index(int(np.argmax(ratio)), ratio.shape))
     for i in sample:
-        m = R.wrench_mp(W, {k: v[i] for k, v in b.items()}, fp[i], kin=(R.HIP, R.LINKS) if kin else None)
+        m = R.wrench_mp(W, {k: v[i] for k, v in b.items()}, fp[i], kin=(model.hip, model.links) if kin else None)
         for got, (val, cond, cnt) in ((bd[i], m["b"]), (rd[i], m["r"])):
             ratio = np.abs(got - val) / (cnt * EPS * cond)
             worst = max(worst, float(ratio.max()))
@@ -608,6 +666,35 @@ def test_wrench_from_state(P):
         bd0, _, _ = P.wrench(e, feet[:m], False)
         assert np.array_equal(bd[same], bd0[same]) and not np.array_equal(bd[:, 3:], bd0[:, 3:])
         print(f"wrench_from_state: worst error / bar: random {w0:.3f} (feet) {w1:.3f} (joint angles), edge set {w2:.3f} {w3:.3f}")
+    finally:
+        restore()
+
+
+def test_wrench_from_state_with_joint_angles_at_the_odd_model(P):
+    """The KIN = true wrench (the feet through forwardKinematics) with ODD_KIN's hip and links in the probe's constants: 20 000 random
+    states in long double, 200 of them and the rotation edge set at 50 digits, the same count * EPS * condition-sum bars; the
+    defaults are restored afterwards."""
+    kin = R.ODD_KIN
+    W, restore = _wrench_setup(P, 31, kin)
+    try:
+        rng = np.random.default_rng(33)
+        n = 20_000
+        b = R._wrench_states(rng, n, max_angle=np.pi - 1e-3)
+        b.pop("feet")
+        qj = np.stack([rng.uniform(-0.6, 0.6, (n, 4)), rng.uniform(-0.2, 1.4, (n, 4)), rng.uniform(-2.4, -0.3, (n, 4))], 2).reshape(n, 12)
+        w1 = _check_wrench(P, W, b, qj, True, rng.choice(n, 200, replace=False), "random, odd model", kin)
+        from scipy.spatial.transform import Rotation
+
+        rows = [(base, R.rotation_mp(ax, ang) @ base if ang else base.copy()) for ang in (0.0, 1e-9, np.pi / 2, np.pi - 1e-3)
+                for ax in (np.eye(3)[2], np.array([1.0, 2.0, 3.0]) / np.sqrt(14.0)) for base in (np.eye(3), Rotation.from_euler("ZYX", [0.7, -0.4, 1.1]).as_matrix())]
+        m = len(rows)
+        e = {k: v[:m].copy() for k, v in b.items()}
+        e["Rwb"], e["Rwb_d"] = np.array([r[0].reshape(9) for r in rows]), np.array([r[1].reshape(9) for r in rows])
+        w3 = _check_wrench(P, W, e, qj[:m], True, range(m), "edge, odd model", kin)
+        # the model matters: the default geometry's lever arms on the same angles are centimetres away
+        _, rd, _ = P.wrench(b, qj, True)
+        assert np.abs(rd.reshape(n, -1) - np.asarray(R.wrench_ld(W, b, qj, kin=(R.HIP, R.LINKS))["r"][0], np.float64).reshape(n, -1)).max() > 0.01
+        print(f"wrench_from_state at the odd model: worst error / bar: random {w1:.3f}, edge set {w3:.3f}")
     finally:
         restore()
 

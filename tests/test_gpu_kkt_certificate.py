@@ -56,6 +56,17 @@ def _sweep_bars(P, b, grf):
     return grad, lam, primal, lam[..., 2].max(axis=1)
 
 
+@pytest.fixture(scope="module")
+def odd_ctls(q):
+    """this module's own handles at ODD_KIN's hip and links"""
+    from tests.solved_batch_support import odd_handle
+
+    out = {k: odd_handle(q, k) for k in ("uniform", "dense")}
+    yield out
+    for c in out.values():
+        c.close()
+
+
 def _check_against_restatement(P, b, grf, got, ref):
     n = grf.shape[0]
     assert np.array_equal(got["active"], ref["active"])
@@ -100,6 +111,28 @@ def test_sizes_contact_patterns_and_inputs(q, ctls, n, source):
         assert np.all(tail == (SENTINEL if v.dtype == torch.float64 else 77)), k
 
 
+def test_joint_q_source_at_the_odd_model(q, odd_ctls):
+    """The joint_q source on a handle at ODD_KIN (n = 65): every output against the restatement, which gets the feet of ODD_KIN's
+    forward kinematics; the same bars.  The default model's feet on the same angles are centimetres away (asserted)."""
+    from tests.solved_batch_support import odd_inputs
+
+    P = params(q, "uniform")
+    b, b_ref, grf, _ = odd_inputs(65)
+    assert np.abs(b_ref["feet"] - KR.with_feet(b)["feet"]).max() > 0.01
+    ref = KR.certificate(P, b_ref, grf, default_duty=KR.DEFAULT_DUTY)
+    got = _certify(q, odd_ctls["uniform"], b, grf)
+    _check_against_restatement(P, b_ref, grf, got, ref)
+
+
+def test_non_optimal_points_against_50_digits_at_the_odd_model(q, odd_ctls):
+    """test_non_optimal_points_against_50_digits' joint_q case on a handle at ODD_KIN, n = 65: the same body, the 50-digit pass
+    through ODD_KIN's forward kinematics."""
+    from tests.solved_batch_support import odd_inputs
+
+    b, b_ref, grf, kin = odd_inputs(65)
+    _non_optimal_points(q, odd_ctls["dense"], b, b_ref, grf, kin, 40)
+
+
 @pytest.mark.parametrize("form", ["uniform", "per-axis", "dense"])
 def test_every_formulation_uses_the_full_weights(q, ctls, form):
     """The certificate reads the handle's full S and W whatever form the solver runs: uniform W, per-axis W, dense S and W."""
@@ -115,18 +148,23 @@ def test_non_optimal_points_against_50_digits(q, ctls, source):
     """Feasible but wrong forces (module docstring): the integer outputs equal the restatement's exactly on all 257 robots, and on
     the first 32 the device is at most 8 x as far from the 50-digit value as the numpy restatement is (floor 16 * 2^-53 * sum of
     |terms|).  Measured worst ratios device distance / bar: profiles/kkt_certificate.md."""
+    b, grf = inputs(257, source)
+    _non_optimal_points(q, ctls["dense"], b, b, grf, None if source == "feet" else (DMR.HIP.reshape(-1), DMR.LINKS.reshape(-1)), 200)
+
+
+def _non_optimal_points(q, ctl, b, b_ref, grf, kin, least_failed):
+    """b: what the device reads; b_ref: what the restatements read (b itself, or b with the model's feet)"""
     P = params(q, "dense")
-    n = 257
-    b, grf = inputs(n, source)
-    ref = KR.certificate(P, b, grf)
-    got = _certify(q, ctls["dense"], b, grf)
-    assert ref["summary"]["n_fail"] >= 200 and ref["summary"]["n_nonfinite"] == 0  # (the robots without a stance foot carry no force: they pass)
+    ref = KR.certificate(P, b_ref, grf)
+    got = _certify(q, ctl, b, grf)
+    source = "feet" if kin is None else "joint_q"
+    b = b_ref
+    assert ref["summary"]["n_fail"] >= least_failed and ref["summary"]["n_nonfinite"] == 0  # (the robots without a stance foot carry no force: they pass)
     assert np.array_equal(got["active"], ref["active"]) and np.array_equal(got["flags"], ref["flags"])
     for k in ("n_fail", "n_nonfinite", "n_swing_nonzero", "arg_primal", "arg_stationarity"):
         assert got["summary"][k] == ref["summary"][k], (k, got["summary"], ref["summary"])
     codes = ref["active"]
     assert set(np.unique(codes & 3)) == {0, 1, 2} and set(np.unique((codes >> 4) & 3)) == {0, 1, 2}  # every single-row case occurs
-    kin = None if source == "feet" else (DMR.HIP.reshape(-1), DMR.LINKS.reshape(-1))
     worst = {}
     for i in range(32):
         mpv = KR.certificate_mp(P, b, grf, i, ref["active"][i], kin=kin)
@@ -236,6 +274,84 @@ def test_summary_is_the_reduction_of_the_per_robot_arrays(q, ctls):
     assert np.isfinite(s["worst_primal"]) and np.isfinite(s["worst_stationarity"]) and s["arg_stationarity"] != 517
     assert s == KR.summarize(nan["primal"], nan["stationarity"], (nan["flags"] & 1) != 0)
     assert not (nan["stationarity"][517] <= 1e-8) and s["n_fail"] >= got["summary"]["n_fail"]  # a NaN fails
+
+
+@pytest.mark.parametrize("source", ["feet", "joint_q"])
+def test_second_round_of_the_grid_stride(q, ctls, source):
+    """n = 4096 x 64 + 65 = 262 209 robots: the grid is capped at 4096 one-wave workgroups, so workgroup 0 walks a full second round,
+    carrying its summary accumulator across, and workgroup 1 has one live lane (robot n - 1) and 63 tail lanes in its second.  The
+    batch is inputs(130) - placed forces, all 16 contact masks - with robot 15 poisoned by a NaN position (bit 1), robot 21 with a
+    force on a swing foot (bit 0) and robot 31 failed (all-zero forces under four stance feet), tiled on the device (index =
+    arange(n) % 130).  Robot i of the large launch equals robot i % 130 of the n = 130 launch of the same kernel - the launch
+    test_sizes_contact_patterns_and_inputs holds to the restatement - in every per-robot output, bit for bit, NaN positions
+    included.  The summary of the large launch equals the host reduction of its own per-robot arrays (KR.summarize), and its counts
+    are the tiled counts.  Then two forces are moved: a normal force of robot n - 1 far above fzmax, the unique worst primal
+    residual, and robot 262 144 + 5 becomes the period's worst stationarity robot with one more push, the unique worst stationarity
+    residual (both settled on the restatement, asserted there first): arg_primal and arg_stationarity name them - indices beyond
+    2^18, found in a second round."""
+    import torch
+    from quadruped_control_amd.balance_controller import certify_summary
+
+    n, p = 4096 * 64 + 65, 130
+    a, c = n - 1, 262144 + 5
+    ctl, P = ctls["uniform"], params(q, "uniform")
+    b, grf = inputs(p, source)
+    b, grf = {k: v.copy() for k, v in b.items()}, grf.copy()
+    for k in b:  # (robot n - 1 is period robot 128, contact pattern 0: it gets robot 127's four stance feet)
+        b[k][a % p] = b[k][127]
+    grf[a % p] = grf[127]
+    grf[31] = 0.0                  # fails: fzmin - 0 under four stance feet
+    grf[21, 3:6] = (1.0, 0.0, 0.0)  # a force on a swing foot (contact pattern 5): flags bit 0
+    ref = KR.certificate(P, b, grf, default_duty=KR.DEFAULT_DUTY)  # (before the poison: the restatement's worst robots are finite ones)
+    b["x"][15, 1] = np.nan         # poisoned: flags bit 1
+    # the two moved forces, settled on the restatement alone: the period's worst stationarity robot w with one more push, as robot c
+    w = int(np.argmax(ref["stationarity"]))
+    comp, push = {"feet": (1, -5.0), "joint_q": (0, -5.0)}[source]
+    foot_w = [l for l in range(4) if (w >> l) & 1][0]
+    moved = grf.copy()
+    moved[w, 3 * foot_w + comp] += push
+    moved[a % p, 2] -= 1.0e3       # grf_body = -Rwb^T f: the world normal force of foot 0 rises by ~1e3 N, far above fzmax
+    ref2 = KR.certificate(P, {k: np.where(np.isnan(v), 0.0, v) if k == "x" else v for k, v in b.items()}, moved, default_duty=KR.DEFAULT_DUTY)
+    rest = np.delete(ref["stationarity"], 15)
+    assert ref2["stationarity"][w] > rest.max() + 1e-3 > ref2["stationarity"][a % p] + 1e-3, (ref2["stationarity"][w], rest.max(), ref2["stationarity"][a % p])
+    assert ref2["primal"][a % p] > 100.0 > 2 * max(np.delete(ref["primal"], 15).max(), ref2["primal"][w])
+    dev, g = q.to_device(b), torch.from_numpy(grf).cuda()
+    small = ctl.certify_batch(dev, g, want=WANT_ALL, summary=True)
+    torch.cuda.synchronize()
+    host = {k: small[k].cpu().numpy() for k in ("primal", "stationarity", "flags")}
+    s_small = certify_summary(small["summary"])
+    assert host["flags"][15] & 2 and host["flags"][21] & 1 and not host["primal"][31] <= 1e-7, (host["flags"][15], host["flags"][21], host["primal"][31])
+    assert s_small["n_nonfinite"] == 1 and s_small["n_swing_nonzero"] == 1 and s_small["n_fail"] >= 3
+    index = torch.arange(n, device="cuda") % p
+    tile = lambda v: v.index_select(0, index).contiguous()
+    tiled, gt = {k: tile(v) for k, v in dev.items()}, tile(g)
+    big = ctl.certify_batch(tiled, gt, want=WANT_ALL, summary=True)
+    torch.cuda.synchronize()
+    for k in WANT_ALL:
+        bits = lambda t: t.contiguous().view(torch.int64) if t.dtype == torch.float64 else t.contiguous()
+        want, got = tile(bits(small[k])), bits(big[k])
+        assert got.shape == want.shape and torch.equal(got, want), (k, int((got != want).reshape(n, -1).any(dim=1).nonzero()[0]))
+    s_big = certify_summary(big["summary"])
+    assert s_big == KR.summarize(big["primal"].cpu().numpy(), big["stationarity"].cpu().numpy(), (big["flags"].cpu().numpy() & 1) != 0)
+    tiled_sum = lambda per_robot: int(np.asarray(per_robot)[np.arange(n) % p].sum())
+    fail = ~(host["primal"] <= 1e-7) | ~(host["stationarity"] <= 1e-8) | ((host["flags"] & 1) != 0)
+    assert s_big["n_fail"] == tiled_sum(fail) and s_big["n_nonfinite"] == tiled_sum((host["flags"] & 2) != 0) == 2017
+    assert s_big["n_swing_nonzero"] == tiled_sum((host["flags"] & 1) != 0) == 2017
+    # robot c becomes the pushed copy of the period's worst robot, robot n - 1 gets its normal force
+    for k, v in tiled.items():
+        v[c] = dev[k][w]
+    gt[c] = torch.from_numpy(moved[w]).cuda()
+    gt[a] = torch.from_numpy(moved[a % p]).cuda()
+    got = ctl.certify_batch(tiled, gt, want=("primal", "stationarity", "flags"), summary=True)
+    torch.cuda.synchronize()
+    s = certify_summary(got["summary"])
+    pr, stn = got["primal"].cpu().numpy(), got["stationarity"].cpu().numpy()
+    assert s == KR.summarize(pr, stn, (got["flags"].cpu().numpy() & 1) != 0)
+    fin = lambda v: np.where(np.isfinite(v), v, -np.inf)
+    assert (fin(pr)[a] > np.delete(fin(pr), a)).all() and (fin(stn)[c] > np.delete(fin(stn), c)).all()  # unique worsts
+    assert s["arg_primal"] == a == n - 1 and s["arg_stationarity"] == c == 262144 + 5, s
+    del big, got, tiled, gt, index, small
+    torch.cuda.empty_cache()
 
 
 def test_inputs_are_left_alone_and_the_result_repeats(q, ctls):

@@ -12,6 +12,7 @@ import pytest
 
 from tests import leg_plant_restatement as LR
 from tests import plant_restatement as PR
+from tests.device_math_reference import DEFAULT_KIN, ODD_KIN
 from tests.gpu_arrays import SENTINEL, P, _device_arrays, _sentinel, _tile, _worst_over_bar, ctl, q  # noqa: F401
 from tests.solved_batch_support import assert_raw_refusals
 
@@ -25,13 +26,22 @@ INERTIA = (0.02, 0.015, 0.01)
 MODES = ("stance", "phase", "duty", "cmd")
 
 
+@pytest.fixture(scope="module")
+def odd_ctl(q, P):
+    """a handle of this module's own at ODD_KIN (the shared `ctl` keeps the library's model)"""
+    c = q.BalanceController.from_params(P, device=0)
+    c.set_kinematics(**ODD_KIN.handle_arguments())
+    yield c
+    c.close()
+
+
 @functools.lru_cache(maxsize=None)
-def _pool():
-    """LR.make_pool plus the contact inputs of the four modes: stance bytes (robot i carries mask i % 16: every mask from 0 to 15,
+def _pool(kin=DEFAULT_KIN):
+    """LR.make_pool (under the model `kin`) plus the contact inputs of the four modes: stance bytes (robot i carries mask i % 16: every mask from 0 to 15,
     any non-zero byte counting as stance), per-robot duties in [0.3, 0.9], and commander records with gait_running = i % 2."""
     from quadruped_control_amd import balance_controller as bc
 
-    s = LR.make_pool(POOL, 0x1E6)
+    s = LR.make_pool(POOL, 0x1E6, kin)
     rng = np.random.default_rng(8)
     bits = (np.arange(POOL)[:, None] >> np.arange(4)[None, :]) & 1
     s["stance"] = np.ascontiguousarray((bits * rng.integers(1, 256, (POOL, 4))).astype(np.uint8))
@@ -50,9 +60,9 @@ def _pool():
     return s
 
 
-def _mode_inputs(mode):
+def _mode_inputs(mode, kin=DEFAULT_KIN):
     """(kwargs of leg_plant_step naming pool arrays, the mask [POOL, 4] the restatement's rule gives)"""
-    s = _pool()
+    s = _pool(kin)
     if mode == "stance":
         return ("stance",), LR.contact_mask(POOL, stance=s["stance"])
     if mode == "phase":
@@ -67,15 +77,16 @@ def _mode_inputs(mode):
 
 
 @functools.lru_cache(maxsize=None)
-def _reference(mode):
-    """{name: (values [POOL, k], bars [POOL, k])} plus "flags"; the stance legs' joint_q / joint_qdot bars are the measured ones"""
+def _reference(mode, kin=DEFAULT_KIN, inertia=INERTIA):
+    """{name: (values [POOL, k], bars [POOL, k])} plus "flags"; the stance legs' joint_q / joint_qdot bars are the measured ones
+    (measured on the CPU over the model's own pool)"""
     import quadruped_control_amd as q
 
-    P, s = q.cheetah_params(), _pool()
-    _, mask = _mode_inputs(mode)
-    refs = [LR.leg_plant_step_mp(P["mass"], P["Ib"], *(s[k][i] for k in STATE), s["joint_tau"][i], mask[i], INERTIA, DT) for i in range(POOL)]
+    P, s = q.cheetah_params(), _pool(kin)
+    _, mask = _mode_inputs(mode, kin)
+    refs = [LR.leg_plant_step_mp(P["mass"], P["Ib"], *(s[k][i] for k in STATE), s["joint_tau"][i], mask[i], inertia, DT, kin=kin) for i in range(POOL)]
     out = {k: [np.stack([r[k][0] for r in refs]), np.stack([r[k][1] for r in refs])] for k in STATE + ("foot_world",)}
-    host = LR.leg_plant_step_np(P["mass"], P["Ib"], *(s[k] for k in STATE), s["joint_tau"], mask, INERTIA, DT)
+    host = LR.leg_plant_step_np(P["mass"], P["Ib"], *(s[k] for k in STATE), s["joint_tau"], mask, inertia, DT, kin=kin)
     assert (host["flags"] == 0).all()
     if mask.any():
         bars = LR.stance_ik_bars(host, {k: out[k][0] for k in ("joint_q", "joint_qdot")}, mask)
@@ -88,7 +99,7 @@ def _reference(mode):
     return out
 
 
-def _step(ctl, host, n, names, outputs=True):
+def _step(ctl, host, n, names, outputs=True, inertia=INERTIA):
     """One step over n robots (the pool tiled).  Returns {name: host array [n + 2, k]} of every array after the step."""
     import torch
 
@@ -101,7 +112,7 @@ def _step(ctl, host, n, names, outputs=True):
         kw["gait_duty"] = kw["gait_duty"].reshape(n)
     if outputs:
         kw.update(foot_world=d["foot_world"][1], flags=d["flags"][1].reshape(n))
-    ctl.leg_plant_step(state, d["joint_tau"][1], DT, INERTIA, **kw)
+    ctl.leg_plant_step(state, d["joint_tau"][1], DT, inertia, **kw)
     torch.cuda.synchronize()
     return {k: v[0].cpu().numpy() for k, v in d.items()}
 
@@ -131,6 +142,19 @@ def test_one_step_against_50_digits(ctl, mode):
     ref = _reference(mode)
     for n in SIZES:
         _check(_step(ctl, _pool(), n, names), ref, n, f"{mode} n {n}")
+
+
+@pytest.mark.parametrize("mode", ("stance", "phase", "all"))
+def test_one_step_against_50_digits_at_the_odd_model(odd_ctl, mode):
+    """The same comparison on a handle at ODD_KIN: the pool rebuilt under the model, the reference and the measured stance-IK bars
+    from the model's own pool, ODD_KIN's anisotropic leg inertia; all 16 contact masks (stance bytes), the phase rule and all
+    stance; a tail, one wave + 1 and more than one workgroup.  No flag is set."""
+    names, mask = _mode_inputs(mode, ODD_KIN)
+    if mode == "stance":
+        assert {int(v) for v in (mask * (1 << np.arange(4))).sum(1)} == set(range(16))
+    ref = _reference(mode, ODD_KIN, ODD_KIN.leg_inertia)
+    for n in (1, 65, 257):
+        _check(_step(odd_ctl, _pool(ODD_KIN), n, names, inertia=ODD_KIN.leg_inertia), ref, n, f"odd {mode} n {n}")
 
 
 # ------------------------------------------------------------------ 2. optional outputs, inputs untouched
@@ -197,12 +221,21 @@ def test_agrees_with_the_rigid_body_plant_behind_control_batch(q, ctl, P):
 
 
 # ------------------------------------------------------------------ 4. flags
+def test_flags_of_a_stretched_and_a_singular_leg_at_the_odd_model(odd_ctl, P):
+    """The same two legs at ODD_KIN: expected bits exact, from the restatement under the model (the band's end the leg's own)."""
+    _flags_of_a_stretched_and_a_singular_leg(odd_ctl, P, ODD_KIN)
+
+
 def test_flags_of_a_stretched_and_a_singular_leg(ctl, P):
+    _flags_of_a_stretched_and_a_singular_leg(ctl, P, DEFAULT_KIN)
+
+
+def _flags_of_a_stretched_and_a_singular_leg(ctl, P, kin):
     """Robot 5: leg 1 almost straight (q3 = -0.01) under a body rising at 3 m/s - after the step the pinned foot is 1 cm out of
     reach, the restatement's d > 1: bit 4 + 1 and no other.  Robot 9: leg 2 with q3 = 0 exactly - det J is rounding noise below
     the band - under a body sinking at 1 m/s, so the foot stays in reach: bit 2 and no other.  Every other robot of the launch is
     bit-identical to the launch without those two."""
-    s = {k: v.copy() for k, v in _pool().items()}
+    s = {k: v.copy() for k, v in _pool(kin).items()}
     plain = _step(ctl, s, POOL, ())
     Rid = np.eye(3).reshape(9)
     for i, leg, q3, vz in ((5, 1, -0.01, 3.0), (9, 2, 0.0, -1.0)):
@@ -210,10 +243,10 @@ def test_flags_of_a_stretched_and_a_singular_leg(ctl, P):
         s["joint_q"][i, 3 * leg:3 * leg + 3] = (0.0, -q3 / 2, q3)
         s["joint_tau"][i] = 0.0
     mask = np.ones((POOL, 4), bool)
-    host = LR.leg_plant_step_np(P["mass"], P["Ib"], *(s[k] for k in STATE), s["joint_tau"], mask, INERTIA, DT)
+    host = LR.leg_plant_step_np(P["mass"], P["Ib"], *(s[k] for k in STATE), s["joint_tau"], mask, INERTIA, DT, kin=kin)
     assert host["flags"][5] == 16 << 1 and host["flags"][9] == 1 << 2 and (np.delete(host["flags"], [5, 9]) == 0).all()
-    assert LR.knee_cosine(1, host["Rwb"][5].reshape(3, 3).T @ (host["foot_world"][5, 3:6] - host["x"][5])) > 1.0 + 1e-6
-    assert abs(LR.det3(LR.jacobian(2, s["joint_q"][9, 6:9]))) < LR.DET_LO / 10
+    assert LR.knee_cosine(1, host["Rwb"][5].reshape(3, 3).T @ (host["foot_world"][5, 3:6] - host["x"][5]), kin) > 1.0 + 1e-6
+    assert abs(LR.det3(LR.jacobian(2, s["joint_q"][9, 6:9], kin))) < kin.det_lo(2) / 10
     got = _step(ctl, s, POOL, ())
     assert got["flags"][5, 0] == 16 << 1 and got["flags"][9, 0] == 1 << 2, (got["flags"][5], got["flags"][9])
     others = np.setdiff1d(np.arange(POOL), [5, 9])

@@ -30,6 +30,17 @@ ALIASES = (("Rwb_bar", "Rwb"), ("x_bar", "x"), ("xdot_bar", "xdot"), ("w_bar", "
 DT, INERTIA = LA.DT, LA.INERTIA
 
 
+@pytest.fixture(scope="module")
+def odd_ctl(q, P):
+    """a handle of this module's own at ODD_KIN (the shared `ctl` keeps the library's model)"""
+    from tests.device_math_reference import ODD_KIN
+
+    c = q.BalanceController.from_params(P, device=0)
+    c.set_kinematics(**ODD_KIN.handle_arguments())
+    yield c
+    c.close()
+
+
 def _adjoint(ctl, s, mask, bars, n, want=LA.OUTPUTS, given=None, alias=None, zeros=False, way="stance"):
     """One adjoint call over n robots (the pool tiled), every array with sentinel rows behind row n - 1.  given: the cotangents that
     are handed over (default all; the others are NULL); zeros: arrays of zeros in their place; alias = (output, cotangent): that
@@ -62,9 +73,23 @@ def _adjoint(ctl, s, mask, bars, n, want=LA.OUTPUTS, given=None, alias=None, zer
 def test_every_output_against_50_digits(ctl, way):
     """Every output entry within K EPS condsum (module docstring) of the 50-digit reverse pass on the same doubles, at every batch
     size and with the contact mask given in each of the four ways; no robot of the pool is flagged."""
-    s, mask, bars = LA.pool()
-    ref, _ = LA.pool_reference()
-    for n in SIZES:
+    _every_output_against_50_digits(ctl, way, "default", SIZES)
+
+
+@pytest.mark.parametrize("way", LA.WAYS)
+def test_every_output_against_50_digits_at_the_odd_model(odd_ctl, way):
+    """The same body on a handle at ODD_KIN, the pool rebuilt under the model (all 16 contact masks), K = 4 C_NP_ODD; the sizes with
+    a tail, one full wave and more than one workgroup."""
+    _every_output_against_50_digits(odd_ctl, way, "odd", (1, 65, 257))
+
+
+def _every_output_against_50_digits(ctl, way, model, sizes):
+    from tests.device_math_reference import KINS
+
+    K = {k: 4.0 * v for k, v in LA.C_NP_OF[model].items()}
+    s, mask, bars = LA.pool(KINS[model])
+    ref, _ = LA.pool_reference(KINS[model])
+    for n in sizes:
         got, _ = _adjoint(ctl, s, mask, bars, n, way=way)
         assert not got["flags"][:n].any() and (got["flags"][n:] == -77).all()
         worst = {}
@@ -74,7 +99,7 @@ def test_every_output_against_50_digits(ctl, way):
             assert np.array_equal(got[k][:n][~live], val[~live]), k
             worst[k] = float((np.abs(got[k][:n] - val)[live] / (EPS * cond[live])).max(initial=0.0))
             assert (got[k][n:] == SENTINEL).all(), k
-        print(f"{way} n {n}: worst error / (EPS condsum) {worst}")
+        print(f"{model} {way} n {n}: worst error / (EPS condsum) {worst}")
         for k in LA.OUTPUTS:
             assert worst[k] <= K[k], (n, k, worst[k], K[k])
 
@@ -82,8 +107,19 @@ def test_every_output_against_50_digits(ctl, way):
 def test_flagged_rows_are_nan_with_the_expected_bits(ctl):
     """The stretched leg, the leg with d < -1 and the singular J(q): exactly the expected bits, NaN in every output row - and the
     unflagged robots of the same call keep their values."""
-    s, mask, bars = LA.pool()
-    fs, fmask, fbars, expected = LA.flagged_pool()
+    _flagged_rows(ctl, "default")
+
+
+def test_flagged_rows_are_nan_with_the_expected_bits_at_the_odd_model(odd_ctl):
+    """The same body at ODD_KIN: the stretched, folded and singular legs rebuilt from the model's hip and links."""
+    _flagged_rows(odd_ctl, "odd")
+
+
+def _flagged_rows(ctl, model):
+    from tests.device_math_reference import KINS
+
+    s, mask, bars = LA.pool(KINS[model])
+    fs, fmask, fbars, expected = LA.flagged_pool(KINS[model])
     m = len(expected)
     both = lambda a, b: np.concatenate([a, b[:5]], 0)
     got, _ = _adjoint(ctl, {k: both(fs[k], s[k]) for k in s}, both(fmask, mask), {k: both(fbars[k], bars[k]) for k in bars}, m + 5)

@@ -66,6 +66,29 @@ def test_every_output_against_the_restatement(q, ctls, n, source):
         assert np.abs(got["adjoint"]).max() > 0 and (ref["flags"] == 0).all()
 
 
+@pytest.fixture(scope="module")
+def odd_ctl(q):
+    """this module's own handle at ODD_KIN's hip and links"""
+    c = SB.odd_handle(q)
+    yield c
+    c.close()
+
+
+def test_joint_q_source_at_the_odd_model(q, odd_ctl):
+    """test_every_output_against_the_restatement's joint_q case on a handle at ODD_KIN, n = 65: the restatement gets the feet of
+    ODD_KIN's forward kinematics; the same bar."""
+    P = params(q, "uniform")
+    n = 65
+    b, b_ref, grf, _ = SB.odd_inputs(n)
+    gbar = _gbar(n)
+    got = _run(q, odd_ctl, b, grf, gbar)
+    ref = SR.sensitivity(P, b_ref, grf, gbar)
+    _assert_close(P, b_ref, got, ref, (n, "joint_q at the odd model"))
+    assert np.abs(got["adjoint"]).max() > 0 and (ref["flags"] == 0).all()
+    wrong = SR.sensitivity(P, b, grf, gbar)  # the default model on the same angles: far outside the bar
+    assert np.abs(wrong["feet_bar"] - ref["feet_bar"]).max() > 1e-6 * np.abs(ref["feet_bar"]).max()
+
+
 def test_all_stance_without_stance_or_phase(q, ctls):
     P = params(q, "uniform")
     b = {k: v for k, v in inputs(64, "feet")[0].items() if k != "stance"}
@@ -244,6 +267,41 @@ def test_bad_pivot_sets_bit_1_and_poisons_the_robot(q, ctls, source):
     good = np.setdiff1d(np.arange(n), bad)
     clean = {k: v[good] for k, v in b.items()}
     _assert_close(P, clean, {k: v[good] for k, v in got.items()}, SR.sensitivity(P, clean, grf[good], gbar[good]), ("bad pivot", source))
+
+
+@pytest.mark.parametrize("source", ["feet", "joint_q"])
+def test_second_round_of_the_grid_stride(q, ctls, source):
+    """n = 4096 x 64 + 65 = 262 209 robots: the grid is capped at 4096 one-wave workgroups, so workgroup 0 walks a full second round
+    and workgroup 1 has one live lane and 63 tail lanes in its second.  The batch is inputs(130) - placed forces, all 16 contact
+    masks - with robot 15 poisoned by a NaN foot (bit 1, every output NaN) and robot 31 failed (all-zero forces: bit 0), tiled on the device
+    (index = arange(n) % 130).  Robot i of the large launch equals robot i % 130 of the n = 130 launch of the same kernel - the launch
+    test_every_output_against_the_restatement holds to the restatement - in every output, bit for bit, NaN positions included: a
+    robot's arithmetic reads no other lane.  Both sources of the lever arms (feet; joint_q through the forward kinematics)."""
+    import torch
+
+    n, p = 4096 * 64 + 65, 130
+    b, grf = inputs(p, source)
+    b, grf = {k: v.copy() for k, v in b.items()}, grf.copy()
+    b["feet" if source == "feet" else "joint_q"][15, 4] = np.nan
+    grf[31] = 0.0
+    dev = q.to_device(b)
+    g, gb = SB.to_cuda(grf, _gbar(p))
+    small = ctls["uniform"].sensitivity_batch(dev, g, gb, want=WANT_ALL)
+    torch.cuda.synchronize()
+    flags = small["flags"].cpu().numpy()
+    print("flags of the period:", np.flatnonzero(flags).tolist(), flags[flags != 0].tolist())
+    assert flags[15] == 2 and all(bool(torch.isnan(small[k][15]).all()) for k in SR.OUTPUTS)
+    assert flags[31] & 1 and np.flatnonzero(flags).tolist() == [15, 31]  # the failed robot (all-zero forces under four stance feet): bit 0
+    index = torch.arange(n, device="cuda") % p
+    tile = lambda v: v.index_select(0, index).contiguous()
+    big = ctls["uniform"].sensitivity_batch({k: tile(v) for k, v in dev.items()}, tile(g), tile(gb), want=WANT_ALL)
+    torch.cuda.synchronize()
+    for k in WANT_ALL:
+        bits = lambda t: t.contiguous() if t.dtype != torch.float64 else t.contiguous().view(torch.int64)
+        want, got = tile(bits(small[k])), bits(big[k])
+        assert got.shape == want.shape and torch.equal(got, want), (k, int((got != want).reshape(n, -1).any(dim=1).nonzero()[0]))
+    del big, small, index, dev, g, gb
+    torch.cuda.empty_cache()
 
 
 def test_flagged_robots(q, ctls):

@@ -46,6 +46,15 @@ def ctl(q):
 
 
 @pytest.fixture(scope="module")
+def odd_ctl(q):
+    """a handle of this module's own with ODD_KIN's hip and links and the limits the odd-model tests use (KN.ODD_TAU_MIN, ODD_TAU_MAX)"""
+    c = q.BalanceController.from_params(params(q, "uniform"), device=0)
+    c.set_kinematics(**dict(DMR.ODD_KIN.handle_arguments(), tau_min=KN.ODD_TAU_MIN, tau_max=KN.ODD_TAU_MAX))
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
 def fd_ctl(q):
     c = q.BalanceController.from_params(params(q, "uniform"), device=0)
     c.set_kinematics(tau_min=KN.FD_TAU_MIN, tau_max=KN.FD_TAU_MAX)
@@ -83,13 +92,25 @@ def _run(q, ctl, b, grf, status, cot, want=KN.OUTPUTS, out=None):
 def test_every_output_against_the_restatement(q, ctl, n, source):
     """Both halves in one call with all four cotangents; stance bytes and the phase rule; contact pattern 0 and the failed robots
     give exact zeros in grf_bar - grf_bar_in and in the torque part of joint_q_bar; the rows behind row n keep their sentinel."""
+    _every_output_against_the_restatement(q, ctl, n, source, None, KN.TAU_MIN, KN.TAU_MAX)
+
+
+@pytest.mark.parametrize("n", SIZES)
+@pytest.mark.parametrize("source", ["stance", "phase"])
+def test_every_output_against_the_restatement_at_the_odd_model(q, odd_ctl, n, source):
+    """The same body on a handle at ODD_KIN's hip and links, the restatement evaluated under the model; the bar C EPS terms is the
+    same expression (its assertions on the angles hold: the angles are the same)."""
+    _every_output_against_the_restatement(q, odd_ctl, n, source, DMR.ODD_KIN, KN.ODD_TAU_MIN, KN.ODD_TAU_MAX)
+
+
+def _every_output_against_the_restatement(q, ctl, n, source, kin, lo, hi):
     b, grf, status, cot = KN.case(n, source)
-    ref = KN.kin_cotangents(b, grf, status, KN.TAU_MIN, KN.TAU_MAX, **cot)
+    ref = KN.kin_cotangents(b, grf, status, lo, hi, kin=kin, **cot)
     qq = b["joint_q"].reshape(n, 4, 3)
     a23 = qq[..., 1] + qq[..., 2]
     assert min(np.abs(np.sin(a23)).min(), np.abs(np.cos(a23)).min()) >= 0.26
     assert min(np.abs(np.cos(qq[..., 0])).min(), np.abs(np.sin(qq[..., 1])).min(), np.abs(np.cos(qq[..., 1])).min()) >= 0.49
-    assert np.abs(np.abs(ref["tau_raw"] - KN.TAU_MIN)).min() > 1e-9 and np.abs(ref["tau_raw"] - KN.TAU_MAX).min() > 1e-9  # no torque on a limit
+    assert np.abs(np.abs(ref["tau_raw"] - lo)).min() > 1e-9 and np.abs(ref["tau_raw"] - hi).min() > 1e-9  # no torque on a limit
     if n >= 16:
         share = 1.0 - ref["mask"][ref["emit"]].mean()
         print((n, source), "clamped share of the stance torque components", share)
@@ -125,6 +146,51 @@ def test_against_50_digits(q, ctl):
         print(f"50-digit {k}: device {dev[k]:.3e} numpy {host[k]:.3e} of the largest entry; device {dev_terms[k]:.2f} numpy {host_terms[k]:.2f} EPS terms")
     for k in KN.OUTPUTS:
         assert dev[k] <= 4 * max(host[k], 16 * EPS), (k, dev[k], host[k])
+
+
+def test_against_50_digits_at_the_odd_model(q, odd_ctl):
+    """Every leg of the 40-robot case at 50 digits under ODD_KIN: the device's distance relative to the leg's largest entry within
+    4 x max(C_KIN_ODD, 16) EPS - C_KIN_ODD the float64 restatement's own distance, measured on the CPU
+    (tests/test_sensitivity_kinematics_cpu.py), never on the device; 16 EPS the default test's floor."""
+    n, K = 40, DMR.ODD_KIN
+    b, grf, status, cot = KN.case(n, "stance")
+    ref = KN.kin_cotangents(b, grf, status, KN.ODD_TAU_MIN, KN.ODD_TAU_MAX, kin=K, **cot)
+    got = _run(q, odd_ctl, b, grf, status, cot)
+    dev_terms, dev = KN.worst_against_50_digits(b, grf, ref, got, kin=K, **cot)
+    for k in KN.OUTPUTS:
+        print(f"odd model 50-digit {k}: device {dev[k] / EPS:.2f} EPS of the largest entry (C_KIN_ODD {KN.C_KIN_ODD[k]}); {dev_terms[k]:.2f} EPS terms")
+        assert dev[k] <= 4 * max(KN.C_KIN_ODD[k], 16.0) * EPS, (k, dev[k])
+
+
+def test_second_round_of_the_grid_stride(q, ctl):
+    """n = 65 536 + 17 robots, 262 212 (robot, leg) rows: the grid is capped at 4096 one-wave workgroups of 16 robots, so workgroup 0
+    walks a full second round and workgroup 1 has four live rows in its second.  The batch is case(130) - all 16 contact masks, the
+    failed robots 5, 12, 19, ..., about half of the torques clamped - with one robot's forces and another's joint angles poisoned
+    with NaN, tiled on the device (index = arange(n) % 130).  Robot i of the large launch equals robot i % 130 of the n = 130 launch
+    of the same kernel - the launch the tests above hold to the restatement and to 50 digits - in both outputs, bit for bit, NaN
+    positions included: a row's arithmetic reads no other lane."""
+    import torch
+
+    n, p = 65536 + 17, 130
+    b, grf, status, cot = KN.case(p, "stance")
+    b, grf = {k: v.copy() for k, v in b.items()}, grf.copy()
+    grf[33, 4] = np.nan
+    b["joint_q"][34, 7] = np.nan
+    assert (status != 0).any() and len({tuple(r) for r in b["stance"].tolist()}) == 16
+    dev, t = q.to_device(b), {k: _cuda(v) for k, v in cot.items()}
+    small = ctl.sensitivity_kinematics_batch(dev, _cuda(grf), _cuda(status), **t, want=KN.OUTPUTS)
+    torch.cuda.synchronize()
+    assert all(bool(torch.isnan(small[k][33:35]).any()) and bool(torch.isfinite(small[k][:33]).all()) for k in KN.OUTPUTS)
+    index = torch.arange(n, device="cuda") % p
+    tile = lambda v: v.index_select(0, index).contiguous()
+    big = ctl.sensitivity_kinematics_batch({k: tile(v) for k, v in dev.items()}, tile(_cuda(grf)), tile(_cuda(status)),
+                                           **{k: tile(v) for k, v in t.items()}, want=KN.OUTPUTS)
+    torch.cuda.synchronize()
+    for k in KN.OUTPUTS:
+        want, got = tile(small[k].contiguous().view(torch.int64)), big[k].contiguous().view(torch.int64)
+        assert got.shape == want.shape and torch.equal(got, want), (k, int((got != want).reshape(n, -1).any(dim=1).nonzero()[0]))
+    del big, small, index, dev, t
+    torch.cuda.empty_cache()
 
 
 def test_halves_and_aliasing(q, ctl):

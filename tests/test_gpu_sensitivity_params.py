@@ -105,6 +105,34 @@ def test_rows_against_the_restatement(q, ctls, n, source, handle):
         assert (s["flags"].cpu().numpy() == 0).all()
 
 
+def test_joint_q_source_at_the_odd_model(q):
+    """test_rows_against_the_restatement's joint_q case on a handle of this test's own at ODD_KIN, n = 65: the restatement gets the
+    feet of ODD_KIN's forward kinematics; the same bar (176 EPS terms)."""
+    import torch
+
+    P, n = params(q, "uniform"), 65
+    b, b_ref, grf, _ = SB.odd_inputs(n)
+    gbar = _gbar(n)
+    dev = q.to_device(b)
+    g, gb = torch.from_numpy(grf).cuda(), torch.from_numpy(gbar).cuda()
+    c = SB.odd_handle(q)
+    try:
+        s = _adjoint(c, dev, g, gb)
+        got = c.sensitivity_params_batch(dev, g, gb, s["adjoint"], want=("param_bar_rows",))
+        torch.cuda.synchronize()
+    finally:
+        c.close()
+    rows, z = got["param_bar_rows"].cpu().numpy(), s["adjoint"].cpu().numpy()
+    ref = PR.param_cotangents(P, b_ref, grf, gbar, z)
+    bar = 176.0 * EPS * ref["terms"]
+    err = np.abs(rows - ref["rows"])
+    print("joint_q at the odd model: worst error / bar", float((err / np.maximum(bar, 1e-300)).max()))
+    assert np.all(err <= bar)
+    for k in PR.LAYOUT:
+        assert np.abs(rows[:, PR.LAYOUT[k][0]]).max() > 0, k
+    assert (s["flags"].cpu().numpy() == 0).all()
+
+
 @pytest.mark.parametrize("n", SUM_SIZES)
 def test_sum_is_reproducible_and_is_the_sum_of_the_rows(q, ctl, n):
     """Two calls give bit-equal sums; a call on another batch in between does not change the bits; the sum is the same whether the

@@ -88,6 +88,57 @@ def test_every_output_against_the_restatement(q, ctl, n, source):
         assert np.abs(got["Rwb_d_bar"][2::16]).max() > 0  # ... and it is not the select's zero derivative
 
 
+def test_joint_q_source_at_the_odd_model(q):
+    """test_every_output_against_the_restatement's joint_q case on a handle of this test's own at ODD_KIN, n = 65: the restatement
+    gets the feet of ODD_KIN's forward kinematics; the same bar (176)."""
+    P = params(q, "uniform")
+    n = 65
+    b, b_ref, grf, _ = SB.odd_inputs(n)
+    gbar = _gbar(n)
+    odd = SB.odd_handle(q)
+    try:
+        got, b_bar, feet_bar, flags = _both(q, odd, b, grf, gbar)
+    finally:
+        odd.close()
+    ref = RR.rotation_cotangents(P, b_ref, grf, gbar, b_bar, feet_bar)
+    _assert_close(got, ref, 176.0, (n, "joint_q at the odd model"))
+    assert all(np.abs(got[k]).max() > 0 for k in RR.OUTPUTS) and (flags == 0).all()
+
+
+@pytest.mark.parametrize("source", ["feet", "joint_q"])
+def test_second_round_of_the_grid_stride(q, ctl, source):
+    """n = 4096 x 64 + 65 = 262 209 robots: the grid is capped at 4096 one-wave workgroups, so workgroup 0 walks a full second round
+    and workgroup 1 has one live lane and 63 tail lanes in its second.  The batch is inputs(130) - placed forces, all 16 contact
+    masks - with robot 15 poisoned by a NaN foot (the adjoint's bit 1: b_bar and feet_bar NaN) and robot 31 failed (all-zero
+    forces: bit 0), b_bar and feet_bar from sensitivity_batch on the period, everything tiled on the device (index = arange(n) %
+    130).  Robot i of the large launch equals robot i % 130 of the n = 130 launch of the same kernel - the launch
+    test_every_output_against_the_restatement holds to the restatement - in every output, bit for bit, NaN positions included."""
+    import torch
+
+    n, p = 4096 * 64 + 65, 130
+    b, grf = inputs(p, source)
+    b, grf = {k: v.copy() for k, v in b.items()}, grf.copy()
+    b["feet" if source == "feet" else "joint_q"][15, 4] = np.nan
+    grf[31] = 0.0
+    dev = q.to_device(b)
+    g, gb = torch.from_numpy(grf).cuda(), torch.from_numpy(_gbar(p)).cuda()
+    s = ctl.sensitivity_batch(dev, g, gb, want=("b_bar", "feet_bar", "flags"))
+    small = ctl.sensitivity_rotation_batch(dev, g, gb, s["b_bar"], s["feet_bar"], want=WANT_ALL)
+    torch.cuda.synchronize()
+    flags = s["flags"].cpu().numpy()
+    assert flags[15] == 2 and flags[31] & 1 and np.flatnonzero(flags).tolist() == [15, 31], flags
+    assert all(bool(torch.isnan(small[k][15]).any()) for k in WANT_ALL) and all(bool(torch.isfinite(small[k][:15]).all()) for k in WANT_ALL)
+    index = torch.arange(n, device="cuda") % p
+    tile = lambda v: v.index_select(0, index).contiguous()
+    big = ctl.sensitivity_rotation_batch({k: tile(v) for k, v in dev.items()}, tile(g), tile(gb), tile(s["b_bar"]), tile(s["feet_bar"]), want=WANT_ALL)
+    torch.cuda.synchronize()
+    for k in WANT_ALL:
+        want, got = tile(small[k].contiguous().view(torch.int64)), big[k].contiguous().view(torch.int64)
+        assert got.shape == want.shape and torch.equal(got, want), (k, int((got != want).reshape(n, -1).any(dim=1).nonzero()[0]))
+    del big, small, s, index, dev, g, gb
+    torch.cuda.empty_cache()
+
+
 @pytest.fixture(scope="module")
 def sweep(q):
     import torch

@@ -16,12 +16,15 @@ import pytest
 
 from tests import leg_plant_adjoint_restatement as LA
 from tests import sensitivity_swing_restatement as SW
+from tests.device_math_reference import KINS, ODD_KIN
 from tests.solved_batch_support import EPS, SENTINEL, assert_raw_refusals, batch_in, params, q  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 SIZES = (1, 15, 16, 17, 257, 4097)
 N_REF = 65
 K_BAR = {k: 4.0 * c for k, c in SW.C_SWING.items()}
+K_BAR_OF = {"default": K_BAR, "odd": {k: 4.0 * c for k, c in SW.C_SWING_ODD.items()}}  # (C_SWING_ODD: measured on the CPU at ODD_KIN)
+SECOND_ROUND_N, PERIOD = 65536 + 17, 130  # one full second round of the 4096-workgroup grid (16 robots a wave) and four live rows
 ALL = SW.OUTPUTS + ("flags",)
 SWING_KEYS = ("Rwb", "x", "joint_q", "joint_qdot", "swing_pos", "swing_vel")
 
@@ -35,14 +38,44 @@ def ctl(q):
 
 
 @pytest.fixture(scope="module")
-def reference():
-    """the 50-digit pass on the first N_REF robots of the pool with every accumulator, once"""
-    b = {k: v[:N_REF] for k, v in SW.pool().items()}
+def odd_ctl(q):
+    """a handle of this module's own at ODD_KIN (never set_kinematics on a shared one: the model would leak)"""
+    c = q.BalanceController.from_params(params(q, "uniform"), device=0)
+    c.set_tuning(race=0)
+    c.set_kinematics(**ODD_KIN.handle_arguments())
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def handles(ctl, odd_ctl):
+    return {"default": ctl, "odd": odd_ctl}
+
+
+def _reference(kin):
+    b = {k: v[:N_REF] for k, v in SW.model_pool(kin).items()}
     stance = SW.masks(N_REF)
     tb, ins = SW.cotangent(N_REF), {k: v[:N_REF] for k, v in SW.accumulators(N_REF).items()}
-    ref, cond, flags, raw = SW.swing_adjoint_mp(b, stance == 0, tb, **ins)
+    ref, cond, flags, raw = SW.swing_adjoint_mp(b, stance == 0, tb, kin=kin, **ins)
     assert not flags.any()
-    return dict(b=b, stance=stance, tb=tb, ins=ins, ref=ref, cond=cond)
+    return dict(b=b, stance=stance, tb=tb, ins=ins, ref=ref, cond=cond, raw=raw)
+
+
+@pytest.fixture(scope="module")
+def reference():
+    """the 50-digit pass on the first N_REF robots of the pool with every accumulator, once"""
+    return _reference(KINS["default"])
+
+
+@pytest.fixture(scope="module")
+def references(reference):
+    """the default model's reference and ODD_KIN's (its pool clamped on both sides in every joint), once each"""
+    class Lazy(dict):  # (ODD_KIN's pass is built when an odd-model test first asks for it)
+        def __missing__(self, model):
+            self[model] = _reference(KINS[model])
+            return self[model]
+
+    return Lazy(default=reference)
 
 
 def _cuda(a):
@@ -71,10 +104,24 @@ def _run(q, ctl, b, tb, want=ALL, out=None, **ins):
 
 
 @pytest.mark.parametrize("n", SIZES)
-def test_against_50_digits(q, ctl, reference, n):
+def test_against_50_digits(q, handles, references, n):
+    """_against_50_digits at the default model (this id is the one the test always had)"""
+    _against_50_digits(q, handles, references, n, "default")
+
+
+@pytest.mark.parametrize("n", SIZES)
+def test_against_50_digits_at_the_odd_model(q, handles, references, n):
+    """_against_50_digits at ODD_KIN: the same body, the same assertions"""
+    _against_50_digits(q, handles, references, n, "odd")
+
+
+def _against_50_digits(q, handles, references, n, model):
     """Every output within K EPS x condition sum of the 50-digit pass; rows without a contribution (stance legs) equal it exactly.  The
-    mask comes from stance bytes, for n = 17 from the phases at the handle's duty and for n = 16 from the phases at a per-robot duty."""
-    c = reference
+    mask comes from stance bytes, for n = 17 from the phases at the handle's duty and for n = 16 from the phases at a per-robot duty.
+    At ODD_KIN (a handle of its own, K from C_SWING_ODD) the pool is clamped at tau_min and at tau_max in every joint and holds
+    torques within |kff| of a limit: the device's clamp mask is the 50-digit pass's bit for bit (gain_bar's last three entries are s),
+    and gain_bar's nine entries per leg are held like every other output."""
+    c, ctl, K_BAR = references[model], handles[model], K_BAR_OF[model]
     b = {k: _tile(v, n) for k, v in c["b"].items()}
     st = _tile(c["stance"], n)
     if n == 17:
@@ -90,20 +137,43 @@ def test_against_50_digits(q, ctl, reference, n):
         live = cond > 0
         assert np.array_equal(val[~live], ref[~live]), k
         worst = float(np.max(np.abs(val - ref)[live] / (EPS * cond[live]))) if live.any() else 0.0
-        print(f"n={n} {k}: worst {worst:.4f} EPS x condition sum (bar {K_BAR[k]})")
+        print(f"n={n} {model} {k}: worst {worst:.4f} EPS x condition sum (bar {K_BAR[k]})")
         assert worst <= K_BAR[k], (k, worst)
+    kin = KINS[model]
+    raw, tb = _tile(c["raw"], n), _tile(c["tb"], n).reshape(n, 4, 3)
+    passes = ~(raw < kin.tau_min) & ~(raw > kin.tau_max)  # (raw is NaN for a stance leg: left out below)
+    swing = np.isfinite(raw)
+    s = got["gain_bar"].reshape(n, 4, 3, 3)[:, :, 2]
+    assert np.array_equal(s[swing], np.where(passes, tb, 0.0)[swing])  # the clamp mask, bit for bit
 
 
-def test_mask_and_flags(q, ctl):
+def test_mask_and_flags(q, handles):
+    """_mask_and_flags at the default model"""
+    _mask_and_flags(q, handles, "default")
+
+
+def test_mask_and_flags_at_the_odd_model(q, handles):
+    """_mask_and_flags at ODD_KIN: the same body, the same assertions"""
+    _mask_and_flags(q, handles, "odd")
+
+
+def _mask_and_flags(q, handles, model):
     """Saturated joints give exact zeros in that component; flagged legs NaN with the expected bits; all-stance zeros, or the `_in`
-    arrays, bit for bit."""
-    n = N_REF
-    b = SW.pool(n, saturate=True)
+    arrays, bit for bit.  At ODD_KIN the saturated pool is the one clamped in every joint with torques within |kff| of a limit, and
+    the device's clamp mask equals the restatement's bit for bit (the float64 and the 50-digit masks agree: the CPU test)."""
+    n, kin, ctl = N_REF, KINS[model], handles[model]
+    b = SW.pool(n, saturate=True) if model == "default" else SW.model_pool(kin, n)
     b["stance"] = np.zeros((n, 4), np.uint8)
     tb = SW.cotangent(n)
-    _, flags, raw = SW.swing_adjoint_np(b, np.ones((n, 4), bool), tb)
-    sat = (raw < SW.TAU_MIN - 1.0) | (raw > SW.TAU_MAX + 1.0)
-    assert not flags.any() and sat.sum() > n and (np.abs(raw)[~sat] < 19.0).all()  # no torque near a limit: the masks agree
+    _, flags, raw = SW.swing_adjoint_np(b, np.ones((n, 4), bool), tb, kin=kin)
+    if model == "default":
+        sat = (raw < SW.TAU_MIN - 1.0) | (raw > SW.TAU_MAX + 1.0)
+        assert not flags.any() and sat.sum() > n and (np.abs(raw)[~sat] < 19.0).all()  # no torque near a limit: the masks agree
+    else:
+        sat = (raw < kin.tau_min) | (raw > kin.tau_max)
+        near = np.minimum(np.abs(raw - kin.tau_min), np.abs(raw - kin.tau_max))
+        assert not flags.any() and all((raw[:, :, j] < kin.tau_min).any() and (raw[:, :, j] > kin.tau_max).any() for j in range(3))
+        assert near.min() > 0.05 and all((near[:, :, j] < abs(kin.jc_kff[j])).any() for j in range(3))  # near a limit, 1e13 roundings off it
     got = _run(q, ctl, b, tb)
     assert not got["flags"].any()
     g = got["gain_bar"].reshape(n, 4, 3, 3)
@@ -112,7 +182,7 @@ def test_mask_and_flags(q, ctl):
         assert (val[sat] == 0.0).all() and (val[~sat] != 0.0).all(), name
     assert np.array_equal(g[:, :, 2][~sat], tb.reshape(n, 4, 3)[~sat])  # kff's cotangent is s itself
     # flagged legs
-    fb, expect = SW.flagged_pool()
+    fb, expect = SW.flagged_pool(kin)
     fb["stance"] = np.zeros((4, 4), np.uint8)
     got = _run(q, ctl, fb, SW.cotangent(4), **SW.accumulators(4))
     assert np.array_equal(got["flags"], expect), got["flags"]
@@ -132,6 +202,44 @@ def test_mask_and_flags(q, ctl):
         assert np.array_equal(bits(got[k]), bits(want)), k
     got = _run(q, ctl, b, tb)
     assert all(np.array_equal(bits(got[k]), bits(np.zeros((n,) + SW.SIZES[k]))) for k in SW.OUTPUTS) and not got["flags"].any()
+
+
+def test_second_round_of_the_grid_stride(q, ctl):
+    """n = 65 536 + 17 robots, 262 212 rows: the grid is capped at 4096 one-wave workgroups of 16 robots, so workgroup 0 walks a full
+    second round and workgroup 1 has four live rows in its second.  The batch is a period of PERIOD robots tiled on the device (index
+    = arange(n) % PERIOD): the restatement's pool under its mix of contact masks, four robots with a flagged leg each (flagged_pool)
+    and one robot with a NaN position.  Robot i of the large launch equals robot i % PERIOD of the n = PERIOD launch of the same
+    kernel - the launch the tests above hold to 50 digits - in every output, bit for bit, NaN positions included: a row's arithmetic
+    reads no other lane."""
+    import torch
+
+    n, p = SECOND_ROUND_N, PERIOD
+    b = SW.pool(p)
+    b["stance"] = SW.masks(p)
+    fb, expect = SW.flagged_pool()
+    for k in fb:
+        b[k][40:44] = fb[k]
+    b["stance"][40:44] = 0
+    b["x"][77, 1] = np.nan
+    b["stance"][77] = (1, 0, 0, 1)
+    tb, ins = SW.cotangent(p), SW.accumulators(p)
+    small = ctl.sensitivity_swing_batch(q.to_device(b), _cuda(tb), want=ALL, **{k: _cuda(v) for k, v in ins.items()})
+    torch.cuda.synchronize()
+    flags = small["flags"].cpu().numpy()
+    assert np.array_equal(flags[40:44], expect) and flags[77] == 0b0110 and np.count_nonzero(flags) == 5, flags
+    assert len({tuple(r) for r in b["stance"].tolist()}) > len(SW.PATTERNS)
+    index = torch.arange(n, device="cuda") % p
+    dev = {k: v.index_select(0, index).contiguous() for k, v in q.to_device(b).items()}
+    big = ctl.sensitivity_swing_batch(dev, _cuda(tb).index_select(0, index).contiguous(), want=ALL,
+                                      **{k: _cuda(v).index_select(0, index).contiguous() for k, v in ins.items()})
+    torch.cuda.synchronize()
+    for k in ALL:
+        bits = lambda t: t if t.dtype == torch.int32 else t.contiguous().view(torch.int64)
+        want, got = bits(small[k]).index_select(0, index), bits(big[k])
+        assert got.shape == want.shape and torch.equal(got, want), (k, int((got != want).reshape(n, -1).any(dim=1).nonzero()[0]))
+    assert bool(torch.isnan(big["x_bar"][n - 1 - (n - 1 - 77) % p]).all())  # (a poisoned robot of the second round)
+    del dev, big, small, index
+    torch.cuda.empty_cache()
 
 
 def test_in_place_and_output_groups(q, ctl, reference):
@@ -247,6 +355,54 @@ def test_tick_autograd(q, ctl, reference):
         ctl.tick_autograd(dict(dev, gait_dt=dev["x"]))
     with pytest.raises(ValueError, match="tick_autograd: the batch lacks"):
         ctl.tick_autograd({k: t for k, t in dev.items() if k != "swing_vel"})
+
+
+def test_tick_autograd_at_the_odd_model_against_central_differences(q, odd_ctl):
+    """The composed check at ODD_KIN: tick_autograd on this module's odd handle, a trot mask (the two diagonals in turn, n = 17, the swing
+    references held LIFT above the model's own feet), against central differences of control_batch(want_torques=True) along the
+    rollout test's committed kind of directions (joint_q, x, swing_pos), with its step (SW.ROLLOUT_H), its keep rule - solved, no
+    sensitivity or swing flag, the working set and the clamp mask of the tick unchanged at -2h, -h, h, 2h - and its bar, |FD(h) -
+    FD(2h)| + 1e-5 |gradient| |direction|.  The kept share is at least 0.5."""
+    import torch
+    from quadruped_control_amd.autograd import TICK_SWING_DIFFERENTIABLE
+
+    n, h = 17, SW.ROLLOUT_H
+    b = SW.trot_start(n, ODD_KIN)
+    rng = np.random.default_rng(0x0DD)
+    ct, cg = rng.normal(0.0, 1.0, (n, 12)), rng.normal(0.0, 1.0, (n, 12))
+    v = {k: rng.normal(0.0, 1.0, b[k].shape) for k in SW.ROLLOUT_DIRECTIONS}
+    lo, hi = ODD_KIN.tau_min, ODD_KIN.tau_max
+
+    def tick(k):
+        bb = dict(b, **{name: np.ascontiguousarray(b[name] + k * h * v[name]) for name in v})
+        _, out = odd_ctl.rollout_tick(q.to_device(bb), None, 1, LA.DT, LA.STAND_INERTIA)
+        tau, grf = out["joint_tau"].cpu().numpy(), out["grf_body"].cpu().numpy()
+        return (tau * ct + grf * cg).sum(axis=1), out["active_set"].cpu().numpy(), out["status"].cpu().numpy(), (tau <= lo) | (tau >= hi)
+
+    L0, w0, st0, cl0 = tick(0)
+    dev = _leaves(q, b, TICK_SWING_DIFFERENTIABLE)
+    tau, grf, status = odd_ctl.tick_autograd(dev)
+    plain = odd_ctl.control_batch(q.to_device(b), want_torques=True)
+    assert torch.equal(tau, plain["joint_tau"]) and np.array_equal(((tau.detach().cpu().numpy() * ct) + grf.detach().cpu().numpy() * cg).sum(axis=1), L0)
+    keep = st0 == 0
+    keep &= odd_ctl.sensitivity_batch(q.to_device(b), plain["grf_body"], torch.ones_like(plain["grf_body"]), want=("flags",))["flags"].cpu().numpy() == 0
+    keep &= odd_ctl.sensitivity_swing_batch(q.to_device(b), torch.ones_like(plain["joint_tau"]), want=("flags",))["flags"].cpu().numpy() == 0
+    pts = {k: tick(k) for k in (-2, -1, 1, 2)}
+    for _, wk, stk, clk in pts.values():
+        keep &= (stk == 0) & (wk == w0) & (clk == cl0).all(axis=1)
+    print("kept", keep.mean(), "entries at the clamp at the base point:", int(cl0.sum()))
+    assert keep.mean() >= 0.5, keep.mean()
+    kept = _cuda(keep.astype(np.float64))[:, None]
+    ((tau * _cuda(ct) + grf * _cuda(cg)) * kept).sum().backward()
+    torch.cuda.synchronize()
+    g = {name: dev[name].grad.cpu().numpy() for name in v}
+    fd1, fd2 = (pts[1][0] - pts[-1][0]) / (2 * h), (pts[2][0] - pts[-2][0]) / (4 * h)
+    an = sum((g[name] * v[name]).sum(axis=1) for name in v)
+    scale = np.sqrt(sum((g[name] ** 2).sum(axis=1) for name in v)) * np.sqrt(sum((v[name] ** 2).sum(axis=1) for name in v))
+    err, t = np.abs(fd1 - an), np.abs(fd1 - fd2)
+    print("worst relative error", float((err[keep] / scale[keep]).max()), "worst t", float((t[keep] / scale[keep]).max()))
+    assert (scale[keep] > 0).all() and bool(np.abs(g["swing_pos"][keep]).max() > 0)
+    assert np.all(err[keep] <= t[keep] + 1e-5 * scale[keep])
 
 
 def test_rollout_tick_autograd_through_a_trot(q):

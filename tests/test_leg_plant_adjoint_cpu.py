@@ -26,7 +26,7 @@ def P(built):
     return q.cheetah_params()
 
 
-def _np(P, s, mask, bars, **kw):
+def _np(P, s, mask, bars, **kw):  # (kin=: the model, default the library's)
     return LA.leg_plant_adjoint_np(P["mass"], P["Ib"], *(s[k] for k in LA.INPUTS), mask, LA.INERTIA, LA.DT, bars, **kw)
 
 
@@ -54,18 +54,44 @@ def test_pool_covers_what_it_says(P):
 
 def test_restatement_against_50_digits_on_the_pool(P):
     """The float64 pass against leg_plant_adjoint_mp on the pool, every output entry, in units of EPS x condition sum: c_np"""
-    s, mask, bars = LA.pool()
-    ref, _ = LA.pool_reference()
-    an = _np(P, s, mask, bars)
+    _restatement_against_50_digits(P, "default")
+
+
+def test_restatement_against_50_digits_on_the_pool_at_the_odd_model(P):
+    """The same at ODD_KIN, against C_NP_ODD; and the odd pool's conditions on the reference alone: all 16 masks, no robot flagged by
+    the forward step or by either pass, the pools' margins (|d| <= 0.9, det J far inside the leg's own band) before and after the
+    step, torques inside the model's limits with two legs at the clamp values."""
+    from tests.device_math_reference import ODD_KIN
+
+    s, mask, bars = LA.pool(ODD_KIN)
+    assert set((mask * [1, 2, 4, 8]).sum(axis=1).tolist()) == set(range(16))
+    step = LR.leg_plant_step_np(P["mass"], P["Ib"], *(s[k] for k in LA.INPUTS), mask, LA.INERTIA, LA.DT, kin=ODD_KIN)
+    assert not step["flags"].any()
+    for jq in (s["joint_q"], step["joint_q"]):
+        dmax, detmin = LR.pool_margins(jq, mask, ODD_KIN)
+        assert dmax <= 0.9 and detmin > 1e4
+    lo, hi = LA.tau_limits(ODD_KIN)
+    assert (lo, hi) == (ODD_KIN.tau_min, ODD_KIN.tau_max) and s["joint_tau"].min() == lo and s["joint_tau"].max() == hi
+    _restatement_against_50_digits(P, "odd")
+
+
+def _restatement_against_50_digits(P, model):
+    from tests.device_math_reference import KINS
+
+    kin = KINS[model]
+    s, mask, bars = LA.pool(kin)
+    ref, flags = LA.pool_reference(kin)
+    an = _np(P, s, mask, bars, kin=kin)
+    assert not flags.any() and not an["flags"].any()
     worst = {}
     for k in LA.OUTPUTS:
         val, cond = ref[k]
         live = cond > 0  # (a stance leg's joint_qdot_bar is an exact 0 with condition sum 0)
         assert np.array_equal(an[k][~live], val[~live])
         worst[k] = float((np.abs(an[k] - val)[live] / (EPS * cond[live])).max())
-    print("c_np", worst)
+    print("c_np", model, worst)
     for k in LA.OUTPUTS:
-        assert worst[k] <= LA.C_NP[k], (k, worst[k])
+        assert worst[k] <= LA.C_NP_OF[model][k], (k, worst[k])
 
 
 def test_ik_derivative_is_the_inverse_jacobian_at_50_digits(P):
@@ -113,17 +139,32 @@ def test_ik_derivative_identity_unrounded():
     assert worst < 1e-40
 
 
+def test_flagged_rows_carry_exactly_the_expected_bits_at_the_odd_model(P):
+    """The flagged pool rebuilt from ODD_KIN's hip and links: exactly FLAGGED's bits in the forward step and in both passes."""
+    from tests.device_math_reference import ODD_KIN
+
+    _flagged_bits(P, ODD_KIN)
+
+
+def _flagged_bits(P, kin):
+    s, mask, bars, expected = LA.flagged_pool(kin)
+    step = LR.leg_plant_step_np(P["mass"], P["Ib"], *(s[k] for k in LA.INPUTS), mask, LA.INERTIA, LA.DT, kin=kin)
+    assert np.array_equal(step["flags"], expected)
+    an = _np(P, s, mask, bars, kin=kin)
+    assert np.array_equal(an["flags"], expected) and all(np.isnan(an[k]).all() for k in LA.OUTPUTS)
+    for i in range(len(expected)):
+        ref, flags = LA.leg_plant_adjoint_mp(P["mass"], P["Ib"], *(s[k][i] for k in LA.INPUTS), mask[i], LA.INERTIA, LA.DT,
+                                             {k: v[i] for k, v in bars.items()}, kin=kin)
+        assert flags == expected[i] and all(np.isnan(ref[k][0]).all() for k in LA.OUTPUTS)
+    return s, step
+
+
 def test_flagged_rows_carry_exactly_the_expected_bits(P):
     """The small flagged pool: the stretched leg, the leg with d < -1 and the singular J(q) carry exactly FLAGGED's bits in both
     passes and in the forward step itself, and every output row is NaN."""
-    s, mask, bars, expected = LA.flagged_pool()
-    step = LR.leg_plant_step_np(P["mass"], P["Ib"], *(s[k] for k in LA.INPUTS), mask, LA.INERTIA, LA.DT)
-    assert np.array_equal(step["flags"], expected)
-    an = _np(P, s, mask, bars)
-    assert np.array_equal(an["flags"], expected) and all(np.isnan(an[k]).all() for k in LA.OUTPUTS)
-    for i in range(len(expected)):
-        ref, flags = LA.leg_plant_adjoint_mp(P["mass"], P["Ib"], *(s[k][i] for k in LA.INPUTS), mask[i], LA.INERTIA, LA.DT, {k: v[i] for k, v in bars.items()})
-        assert flags == expected[i] and all(np.isnan(ref[k][0]).all() for k in LA.OUTPUTS)
+    from tests.device_math_reference import DEFAULT_KIN
+
+    s, step = _flagged_bits(P, DEFAULT_KIN)
     # the margins that make the bits unambiguous: the knee cosines after the step, and the determinants before it
     d0 = LR.knee_cosine(0, np.eye(3) @ (LR.fk(0, s["joint_q"].reshape(-1, 4, 3)[0, 0]) + s["x"][0] - step["x"][0]))
     d1 = LR.knee_cosine(1, np.eye(3) @ (LR.fk(1, s["joint_q"].reshape(-1, 4, 3)[1, 1]) + s["x"][1] - step["x"][1]))

@@ -170,3 +170,31 @@ def test_numpy_step_inside_the_50_digit_bars(P):
         assert np.abs(ref["knee"][mask[i]]).max() <= 0.9
     print(f"numpy step / bar: {worst}")
     assert max(worst.values()) <= 1.0, worst
+
+
+def test_numpy_step_inside_the_50_digit_bars_at_the_odd_model(P):
+    """The same comparison at ODD_KIN with its anisotropic leg inertia: the pool rebuilt under the model (torques through the model's
+    Jacobians, inside its limits), no robot flagged by the float64 step, both margins before and after the step against each leg's
+    own band, and the float64 step inside the derived bars of the 50-digit step."""
+    from tests.device_math_reference import ODD_KIN as K
+
+    s = LR.make_pool(24, 3, K)
+    n = s["x"].shape[0]
+    assert K.tau_min < s["joint_tau"].min() and s["joint_tau"].max() < K.tau_max and len(set(K.leg_inertia)) == 3
+    for mask in (np.ones((n, 4), bool), LR.contact_mask(n, gait_phase=s["gait_phase"])):
+        o = LR.leg_plant_step_np(P["mass"], P["Ib"], *(s[k] for k in LR.STATE), s["joint_tau"], mask, K.leg_inertia, DT, kin=K)
+        assert (o["flags"] == 0).all()
+        for jq in (s["joint_q"], o["joint_q"]):
+            dmax, detmin = LR.pool_margins(jq, mask, K)
+            assert dmax <= 0.9 and detmin >= 1e4, (dmax, detmin)
+    assert mask.any() and not mask.all()
+    worst = {}
+    for i in range(n):
+        ref = LR.leg_plant_step_mp(P["mass"], P["Ib"], *(s[k][i] for k in LR.STATE), s["joint_tau"][i], mask[i], K.leg_inertia, DT, kin=K)
+        for k in LR.STATE + ("foot_world",):
+            val, bar = ref[k]
+            has = ~np.isnan(bar)
+            worst[k] = max(worst.get(k, 0.0), PR.worst_over_bar(o[k][i][has], (val[has], bar[has])))
+        assert np.abs(ref["knee"][mask[i]]).max(initial=0.0) <= 0.9
+    print(f"numpy step / bar at the odd model: {worst}")
+    assert max(worst.values()) <= 1.0, worst

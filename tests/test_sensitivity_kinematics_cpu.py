@@ -123,6 +123,38 @@ def test_restatement_against_50_digits(legs):
     assert all(v <= 16.0 for v in worst.values()), worst
 
 
+def test_restatement_against_50_digits_at_the_odd_model():
+    """The same measurement at ODD_KIN (hip, links) with the limits (ODD_TAU_MIN, ODD_TAU_MAX), both mask sources: error / (EPS terms)
+    held to the same 16, and the distance relative to the leg's largest entry recorded as KN.C_KIN_ODD.  The pool's conditions, on the
+    restatement alone: at every size the GPU test uses from 15 on, every joint is clamped at tau_min, clamped at tau_max and passes at
+    least once, no torque lies within 1e-9 of a limit, and the clamped share stays between 10 % and 90 % from n = 16 on."""
+    K = DMR.ODD_KIN
+    lo, hi = KN.ODD_TAU_MIN, KN.ODD_TAU_MAX
+    assert lo != -hi
+    for n in (15, 16, 17, 40):
+        b, grf, status, cot = KN.case(n, "stance")
+        ref = KN.kin_cotangents(b, grf, status, lo, hi, kin=K, **cot)
+        raw, emit = ref["tau_raw"], ref["emit"]
+        for c in range(3):
+            r = raw[..., c][emit]
+            assert (r < lo).any() and (r > hi).any() and ref["mask"][..., c].any(), (n, c)
+        assert np.abs(raw - lo).min() > 1e-9 and np.abs(raw - hi).min() > 1e-9
+        assert n < 16 or 0.1 <= 1.0 - ref["mask"][emit].mean() <= 0.9
+    worst, mag = {k: 0.0 for k in KN.OUTPUTS}, {k: 0.0 for k in KN.OUTPUTS}
+    for source in ("stance", "phase"):
+        b, grf, status, cot = KN.case(40, source)
+        ref = KN.kin_cotangents(b, grf, status, lo, hi, kin=K, **cot)
+        per_terms, per_mag = KN.worst_against_50_digits(b, grf, ref, ref, kin=K, **cot)
+        worst = {k: max(worst[k], per_terms[k]) for k in KN.OUTPUTS}
+        mag = {k: max(mag[k], per_mag[k] / EPS) for k in KN.OUTPUTS}
+    print("odd model, restatement against 50 digits: error / (EPS terms)", worst, "EPS of the largest entry", mag)
+    assert all(v <= 16.0 for v in worst.values()), worst
+    assert all(mag[k] <= KN.C_KIN_ODD[k] for k in KN.OUTPUTS), mag
+    # the model matters: the default geometry on the same inputs is far from the odd one
+    dflt = KN.kin_cotangents(b, grf, status, lo, hi, **cot)
+    assert np.abs(dflt["joint_q_bar"] - ref["joint_q_bar"]).max() > 1e-3
+
+
 def test_masks_and_exact_zeros(legs):
     """Contact pattern 0 and failed robots: grf_bar - grf_bar_in and the torque part of joint_q_bar are exactly 0; the kinematics term
     is unmasked (their joint_q_bar still moves with feet_bar); equality with a limit passes through; a NaN torque passes and

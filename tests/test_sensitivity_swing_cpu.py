@@ -13,19 +13,35 @@ import numpy as np
 import pytest
 
 from tests import sensitivity_swing_restatement as SW
+from tests.device_math_reference import KINS, ODD_KIN
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 EPS = 2.0 ** -52
 N_CPU = 65  # the first robots of the pool: every pattern of SW.masks() thirteen times over
 
 
-@pytest.fixture(scope="module")
-def case():
-    b = {k: v[:N_CPU] for k, v in SW.pool().items()}
+def _case(kin):
+    b = {k: v[:N_CPU] for k, v in SW.model_pool(kin).items()}
     swing = SW.masks(N_CPU) == 0
     tb, ins = SW.cotangent(N_CPU), {k: v[:N_CPU] for k, v in SW.accumulators(N_CPU).items()}
-    ref, cond, flags, raw = SW.swing_adjoint_mp(b, swing, tb, **ins)
-    return dict(b=b, swing=swing, tb=tb, ins=ins, ref=ref, cond=cond, flags=flags, raw=raw)
+    ref, cond, flags, raw = SW.swing_adjoint_mp(b, swing, tb, kin=kin, **ins)
+    return dict(b=b, swing=swing, tb=tb, ins=ins, ref=ref, cond=cond, flags=flags, raw=raw, kin=kin)
+
+
+@pytest.fixture(scope="module")
+def case():
+    return _case(KINS["default"])
+
+
+@pytest.fixture(scope="module")
+def cases(case):
+    """the default model's case (the one every default-only test uses) and ODD_KIN's"""
+    class Lazy(dict):  # (ODD_KIN's pass is built when an odd-model test first asks for it)
+        def __missing__(self, model):
+            self[model] = _case(KINS[model])
+            return self[model]
+
+    return Lazy(default=case)
 
 
 def test_the_pool_is_in_reach_and_unclamped(case):
@@ -46,19 +62,50 @@ def test_the_pool_is_in_reach_and_unclamped(case):
             assert not bad and (np.abs(out["gain_bar"][:3]) < 0.2).all()  # s = 1: gain_bar's first three are e
 
 
-def test_float64_against_50_digits(case):
-    """C_SWING: the float64 restatement (the kernel's identity at the IK end) against the 50-digit pass (the atan2 chain reversed as
-    written), per output in EPS x condition sum - asserted and recorded."""
-    c = case
-    val, flags, raw = SW.swing_adjoint_np(c["b"], c["swing"], c["tb"], **c["ins"])
+def test_the_odd_pool_is_in_reach_and_clamped_on_both_sides(cases):
+    """ODD_KIN's pool, on the 50-digit reference alone: no swing leg is flagged; in every joint at least one torque is clamped at
+    tau_min, one at tau_max and one passes; some torques sit within |kff| of a limit on either side of it (dropping kff flips their
+    mask); every contact pattern is there."""
+    c, kin = cases["odd"], ODD_KIN
+    assert not c["flags"].any()
+    assert kin.tau_min != -kin.tau_max and all(v != 1.0 for v in kin.jc_kd) and all(v != 0.0 for v in kin.jc_kff)
+    for j in range(3):
+        raw = c["raw"][:, :, j][c["swing"]]
+        assert np.isfinite(raw).all()
+        low, high = raw < kin.tau_min, raw > kin.tau_max
+        assert low.any() and high.any() and (~low & ~high).any(), j
+        without = raw - kin.jc_kff[j]
+        flips = ((without < kin.tau_min) != low) | ((without > kin.tau_max) != high)
+        print(f"joint {j}: {int(low.sum())} at tau_min, {int(high.sum())} at tau_max, {int((~low & ~high).sum())} pass, {int(flips.sum())} masks flip without kff")
+        assert flips.any(), j
+    pats = {tuple(r) for r in (~c["swing"]).astype(int).tolist()}
+    assert set(SW.PATTERNS) <= pats and len(pats) > len(SW.PATTERNS)
+
+
+def test_float64_against_50_digits(cases):
+    """_float64_against_50_digits at the default model: C_SWING"""
+    _float64_against_50_digits(cases, "default")
+
+
+def test_float64_against_50_digits_at_the_odd_model(cases):
+    """_float64_against_50_digits at ODD_KIN: C_SWING_ODD"""
+    _float64_against_50_digits(cases, "odd")
+
+
+def _float64_against_50_digits(cases, model):
+    """C_SWING, C_SWING_ODD: the float64 restatement (the kernel's identity at the IK end) against the 50-digit pass (the atan2 chain
+    reversed as written), per output in EPS x condition sum - asserted and recorded - at the default model and at ODD_KIN."""
+    c = cases[model]
+    kin, C = c["kin"], SW.C_SWING_OF[model]
+    val, flags, raw = SW.swing_adjoint_np(c["b"], c["swing"], c["tb"], kin=kin, **c["ins"])
     assert (flags == c["flags"]).all()
-    assert ((raw < SW.TAU_MIN) == (c["raw"] < SW.TAU_MIN)).all() and ((raw > SW.TAU_MAX) == (c["raw"] > SW.TAU_MAX)).all()
+    assert ((raw < kin.tau_min) == (c["raw"] < kin.tau_min)).all() and ((raw > kin.tau_max) == (c["raw"] > kin.tau_max)).all()
     for k in SW.OUTPUTS:
         live = c["cond"][k] > 0
         assert (val[k][~live] == c["ref"][k][~live]).all(), k  # stance rows: zeros, or the accumulator, exactly
         worst = float(np.max(np.abs(val[k] - c["ref"][k])[live] / (EPS * c["cond"][k][live])))
-        print(f"C_SWING {k}: {worst:.3f} (recorded {SW.C_SWING[k]})")
-        assert worst <= SW.C_SWING[k], (k, worst)
+        print(f"C_SWING[{model}] {k}: {worst:.4f} (recorded {C[k]})")
+        assert worst <= C[k], (k, worst)
 
 
 def test_ik_derivative_is_the_inverse_jacobian(case):
@@ -120,12 +167,24 @@ def test_central_differences_of_the_oracle_swing_torque(case):
 
 
 def test_flag_bits_on_constructed_legs():
+    """_flag_bits_on_constructed_legs at the default model"""
+    _flag_bits_on_constructed_legs("default")
+
+
+def test_flag_bits_on_constructed_legs_at_the_odd_model():
+    """_flag_bits_on_constructed_legs at ODD_KIN"""
+    _flag_bits_on_constructed_legs("odd")
+
+
+def _flag_bits_on_constructed_legs(model):
     """Stretched (d > 1), inside the hip roll's cylinder, a non-finite target and inside the inner reach limit (d < -1): the expected bit,
-    NaN in that leg's rows and in the robot's Rwb_bar and x_bar, finite numbers everywhere else - in both arithmetics."""
-    b, expect = SW.flagged_pool()
+    NaN in that leg's rows and in the robot's Rwb_bar and x_bar, finite numbers everywhere else - in both arithmetics, at both models
+    (the targets are placed from the model's own hip and links)."""
+    kin = KINS[model]
+    b, expect = SW.flagged_pool(kin)
     swing = np.ones((4, 4), bool)
     tb = SW.cotangent(4)
-    for val, flags in (SW.swing_adjoint_np(b, swing, tb)[:2], (lambda r: (r[0], r[2]))(SW.swing_adjoint_mp(b, swing, tb))):
+    for val, flags in (SW.swing_adjoint_np(b, swing, tb, kin=kin)[:2], (lambda r: (r[0], r[2]))(SW.swing_adjoint_mp(b, swing, tb, kin=kin))):
         assert (flags == expect).all(), flags
         for i in range(4):
             for k in SW.PER_LEG:
