@@ -756,6 +756,89 @@ void qc_default_sensitivity_swing(qc_sensitivity_swing_io* io);
  * Rwb, x, joint_q, joint_qdot, swing_pos or swing_vel, or n beyond one launch. */
 int qc_sensitivity_swing_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_swing_io* io, void* stream);
 
+/* The swing references as a launch of their own: what the tick does BEFORE the QP when qc_batch_in.swing_state is given, per robot
+ * and in the tick's order, by the tick's own device functions - the values are the tick's bit for bit.
+ *   1. clock  if in->gait_dt is given the four phases advance (phase += dt / (t_swing + t_stance), fmod 1) and are written back to
+ *             in->gait_phase;
+ *   2. mask   in->stance bytes, else the phase rule on the (advanced) phases with in->gait_duty or the handle's value;
+ *   3. plan   leg l gets a new foothold on a stance -> swing edge, or whenever it swings on the first call (leg_state = -1):
+ *             p_start_l = Rwb FK(joint_q_l) + x, p_final_l = the Raibert + LIP foothold (foot_planner.cpp:76-104).  If ANY leg is
+ *             replanned, has_traj of every other leg is cleared (trajectory.cpp:308-344), else it is kept; leg_state = the mask;
+ *   4. track  swing leg with a trajectory: swing_pos_l, swing_vel_l = the sextic through p_start_l, the centre ((p_start_l +
+ *             p_final_l) / 2 in x, y; swing_height in z) and p_final_l at the leg's phase, WORLD frame - the arrays qc_control_batch
+ *             takes as qc_batch_in.swing_pos / swing_vel.  A stance leg and a swing leg without a trajectory get zeros.
+ * So qc_control_batch with swing_state and gait_dt equals this call with the same gait_dt followed by qc_control_batch with the
+ * returned swing_pos / swing_vel and the phases it left (no gait_dt): records, phases, joint_tau, grf_body and status.
+ * Of `in` it reads Rwb, x, xdot, w, xdot_d, joint_q, gait_phase and swing_state (IN/OUT) - all required - and the optional stance,
+ * gait_duty and gait_dt; the other members are ignored, except that `feet` without joint_q and a swing_pos / swing_vel are refused.
+ * Commander mode is out of scope.  All pointers are DEVICE pointers. */
+typedef struct qc_swing_reference_io {
+  size_t struct_size;  /* = sizeof(qc_swing_reference_io); checked                           */
+  double* swing_pos;   /* [n][4][3] OUT: each optional, at least one given                    */
+  double* swing_vel;   /* [n][4][3]                                                           */
+  uint8_t* planned;    /* [n]: bit l - leg l was replanned by this call                       */
+} qc_swing_reference_io;
+/* struct_size set, pointers NULL. */
+void qc_default_swing_reference(qc_swing_reference_io* io);
+/* Asynchronous on `stream`, no host synchronisation (graph-capturable); n == 0 launches nothing and returns QC_OK.  QC_ERR_INVALID
+ * (message starting with "qc_swing_reference_batch:", nothing launched) for a null handle, `in` or `io`, a wrong struct_size, a
+ * swing_pos or swing_vel in `in`, `feet` without joint_q, gait_dt together with stance, no output requested, a missing Rwb, x, xdot, w,
+ * xdot_d, joint_q, gait_phase or swing_state, or n beyond one launch. */
+int qc_swing_reference_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_swing_reference_io* io, void* stream);
+
+/* The reverse pass of qc_swing_reference_batch.  The forward launch saves nothing: pass the same `in` with gait_phase AS THE FORWARD
+ * CALL LEFT IT (gait_dt is refused: no clock is advanced here) and `state_before`, a copy of the qc_swing_state records from BEFORE the
+ * forward call - the plan decision is recomputed from its leg_state / has_traj and the contact mask.  With (h, h') the sextic's basis
+ * functions and their derivatives at leg l's clamped trajectory time (zero if the leg is in stance or has no trajectory after the
+ * call), per leg
+ *   a_r = (h0 + h2 / 2) swing_pos_bar_r + (h0' + h2' / 2) swing_vel_bar_r,  c_r likewise with h1, h1'      r = 0, 1
+ *   a_2 = h0 swing_pos_bar_2 + h0' swing_vel_bar_2,                         c_2 likewise                    (the centre's z is a constant)
+ *   A = a + p_start_next_bar_l,  C = c + p_final_next_bar_l                 the total on the record after the call
+ *   leg NOT replanned:  p_start_bar_l = A,  p_final_bar_l = C               (the record passed through)
+ *   leg replanned:      p_start_bar_l = p_final_bar_l = 0 (overwritten);  C_2 := 0 (the foothold's z is 0);  with p = FK(joint_q_l),
+ *                       r = Rwb p, half = t_stance / 2, k = planner_k, lip = sqrt(x_z / 9.81) / 2, hip = planner_hip[l]:
+ *     x_bar += A + C,  x_bar[2] += 0.25 / (9.81 sqrt(x_z / 9.81)) <C, xdot>,  xdot_bar += (half + k + lip) C,  xdot_d_bar += -k C,
+ *     w_bar += half (r x C),  r_bar = A + half (C x w),  Rwb_bar += r_bar p^T + C hip^T     ENTRYWISE, row-major: qc_sensitivity_rot_io's
+ *     joint_q_bar_l += J(joint_q_l)^T Rwb^T r_bar
+ * summed over the legs in the order 0, 1, 2, 3 on top of the `_in` arrays (a missing one counts as zero, as does a missing cotangent).
+ * Of `in` it reads Rwb, x, xdot, w, joint_q, gait_phase - required - and the optional stance and gait_duty; `in` is never written.
+ * UNDEFINED GRADIENT: `flags` bit l - leg l is replanned and x_z is not finite and > 0: the LIP square root has no derivative there;
+ * every output row of that robot is NaN.  Other non-finite inputs propagate; nothing is clamped.
+ * NOT produced: a cotangent of the phases, of gait_dt, of the gait's periods, of swing_height, planner_k or the kinematic constants -
+ * the clock and the contact mask are held, as in qc_leg_plant_step_adjoint_batch.  Commander mode is out of scope.
+ * Each of Rwb_bar, x_bar, xdot_bar, w_bar and joint_q_bar may be the SAME array as its `_in`, and p_start_bar / p_final_bar the same
+ * arrays as p_start_next_bar / p_final_next_bar: every input of a robot is read before any of its outputs is written.  All pointers
+ * are DEVICE pointers. */
+typedef struct qc_swing_reference_adjoint_io {
+  size_t struct_size;                         /* = sizeof(qc_swing_reference_adjoint_io); checked                    */
+  const struct qc_swing_state* state_before;  /* [n] the records before the forward call; required                   */
+  const double* swing_pos_bar;                /* [n][4][3] cotangents: each optional, at least one given             */
+  const double* swing_vel_bar;                /* [n][4][3]                                                           */
+  const double* p_start_next_bar;             /* [n][12]   on the record after the call                              */
+  const double* p_final_next_bar;             /* [n][12]                                                             */
+  const double* Rwb_bar_in;                   /* [n][9]    added to the output of that name; each optional           */
+  const double* x_bar_in;                     /* [n][3]                                                              */
+  const double* xdot_bar_in;                  /* [n][3]                                                              */
+  const double* w_bar_in;                     /* [n][3]                                                              */
+  const double* joint_q_bar_in;               /* [n][4][3]                                                           */
+  double* Rwb_bar;                            /* [n][9]    OUT: each optional, at least one given (flags counts)     */
+  double* x_bar;                              /* [n][3]                                                              */
+  double* xdot_bar;                           /* [n][3]                                                              */
+  double* w_bar;                              /* [n][3]                                                              */
+  double* xdot_d_bar;                         /* [n][3]                                                              */
+  double* joint_q_bar;                        /* [n][4][3]                                                           */
+  double* p_start_bar;                        /* [n][12]   on the record before the call                             */
+  double* p_final_bar;                        /* [n][12]                                                             */
+  int32_t* flags;                             /* [n]: bit l - replanned leg l has no gradient                        */
+} qc_swing_reference_adjoint_io;
+/* struct_size set, pointers NULL. */
+void qc_default_swing_reference_adjoint(qc_swing_reference_adjoint_io* io);
+/* Asynchronous on `stream`, no host synchronisation (graph-capturable); n == 0 launches nothing and returns QC_OK.  QC_ERR_INVALID
+ * (message starting with "qc_swing_reference_adjoint_batch:", nothing launched) for a null handle, `in` or `io`, a wrong struct_size,
+ * a gait_dt, swing_pos or swing_vel in `in`, `feet` without joint_q, no cotangent given, no output requested, a missing state_before,
+ * a missing Rwb, x, xdot, w, joint_q or gait_phase, or n beyond one launch. */
+int qc_swing_reference_adjoint_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_swing_reference_adjoint_io* io, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -119,6 +119,17 @@ class QcSensitivitySwingIo(C.Structure):
                  "gain_bar", "Rwb_bar", "x_bar", "flags")]
 
 
+class QcSwingReferenceIo(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t)] + [(k, C.c_void_p) for k in ("swing_pos", "swing_vel", "planned")]
+
+
+class QcSwingReferenceAdjointIo(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t)] + [(k, C.c_void_p) for k in
+                ("state_before", "swing_pos_bar", "swing_vel_bar", "p_start_next_bar", "p_final_next_bar", "Rwb_bar_in", "x_bar_in", "xdot_bar_in",
+                 "w_bar_in", "joint_q_bar_in", "Rwb_bar", "x_bar", "xdot_bar", "w_bar", "xdot_d_bar", "joint_q_bar", "p_start_bar", "p_final_bar",
+                 "flags")]
+
+
 PARAM_COUNT = 211  # QC_PARAM_COUNT: the doubles of QcParams, in its order
 
 
@@ -134,7 +145,8 @@ EXPORTS = ("qc_create_abi", "qc_destroy", "qc_control_batch", "qc_control_batch_
            "qc_default_certify", "qc_certify_batch", "qc_default_sensitivity", "qc_sensitivity_batch",
            "qc_default_sensitivity_rot", "qc_sensitivity_rot_batch", "qc_default_plant_adjoint", "qc_plant_step_adjoint_batch",
            "qc_default_sensitivity_param", "qc_sensitivity_param_batch", "qc_default_sensitivity_kin", "qc_sensitivity_kin_batch",
-           "qc_default_leg_plant_adjoint", "qc_leg_plant_step_adjoint_batch", "qc_default_sensitivity_swing", "qc_sensitivity_swing_batch")
+           "qc_default_leg_plant_adjoint", "qc_leg_plant_step_adjoint_batch", "qc_default_sensitivity_swing", "qc_sensitivity_swing_batch",
+           "qc_default_swing_reference", "qc_swing_reference_batch", "qc_default_swing_reference_adjoint", "qc_swing_reference_adjoint_batch")
 
 _lib = None
 
@@ -241,6 +253,14 @@ def load():
     lib.qc_default_sensitivity_swing.restype = None
     lib.qc_sensitivity_swing_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcBatchIn), C.POINTER(QcSensitivitySwingIo), C.c_void_p]
     lib.qc_sensitivity_swing_batch.restype = C.c_int
+    lib.qc_default_swing_reference.argtypes = [C.POINTER(QcSwingReferenceIo)]
+    lib.qc_default_swing_reference.restype = None
+    lib.qc_swing_reference_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcBatchIn), C.POINTER(QcSwingReferenceIo), C.c_void_p]
+    lib.qc_swing_reference_batch.restype = C.c_int
+    lib.qc_default_swing_reference_adjoint.argtypes = [C.POINTER(QcSwingReferenceAdjointIo)]
+    lib.qc_default_swing_reference_adjoint.restype = None
+    lib.qc_swing_reference_adjoint_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcBatchIn), C.POINTER(QcSwingReferenceAdjointIo), C.c_void_p]
+    lib.qc_swing_reference_adjoint_batch.restype = C.c_int
     # the structures above are hand-written mirrors of the header: a library built from another revision is refused here,
     # before any of them crosses the boundary
     rc = lib.qc_check_abi(ABI_VERSION, C.sizeof(QcParams), C.sizeof(QcBatchIn), C.sizeof(QcBatchOut))

@@ -18,7 +18,12 @@ backward, alternated with fused_tick_autograd().
 
 tick_autograd() is control_batch(want_torques=True) with swing references (swing_pos, swing_vel): its backward is the fused stance
 tick's, then the reverse pass of the swing legs' PD torques (qc_sensitivity_swing_batch) added in place; rollout_tick_autograd() uses
-it for a batch that carries the references."""
+it for a batch that carries the references.
+
+swing_reference_autograd() is swing_reference_batch() - the gait clock, the contact mask, the foothold planner and the sextic swing
+trajectory, the front half of the tick - on a copy of the swing record, its backward one qc_swing_reference_adjoint_batch call;
+rollout_gait_autograd() chains it with tick_autograd() and leg_plant_step_autograd() and threads the record through: the twin of
+rollout_tick() on a batch with swing_state and a running clock."""
 from __future__ import annotations
 
 import torch
@@ -351,6 +356,126 @@ def leg_plant_step_autograd(ctl, state, joint_tau, dt, leg_inertia, stance=None,
     contact = {k: (v.detach() if v is not None else None) for k, v in (("stance", stance), ("gait_phase", gait_phase), ("gait_duty", gait_duty))}
     tensors = [state[k] for k in LEG_PLANT_DIFFERENTIABLE[:-1]] + [joint_tau]
     return _LegPlantStep.apply(ctl, float(dt), leg_inertia, contact, flags, *tensors)
+
+
+# ------------------------------------------------------------------ the swing references: clock, contact mask, foothold planner, sextic trajectory
+SWING_REFERENCE_DIFFERENTIABLE = ("Rwb", "x", "xdot", "w", "xdot_d", "joint_q", "p_start", "p_final")
+_SWING_RECORD_DOUBLES = 28  # qc_swing_state as doubles: 4 hold the eight int32 words, then p_start [12] and p_final [12]
+
+
+def _record_points(record):
+    """the p_start / p_final columns of a swing-state tensor, as float64 views [n,12] into it"""
+    d = record.view(torch.float64).view(-1, _SWING_RECORD_DOUBLES)
+    return d[:, 4:16], d[:, 16:28]
+
+
+class _SwingReference(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ctl, batch, swing_state, *tensors):
+        *state, p_start, p_final = tensors
+        before = swing_state.clone()
+        ps, pf = _record_points(before)
+        ps.copy_(p_start.reshape(ps.shape))
+        pf.copy_(p_final.reshape(pf.shape))
+        after = before.clone()
+        res = ctl.swing_reference_batch(dict(batch, swing_state=after), want=("swing_pos", "swing_vel", "planned"))
+        ctx.ctl = ctl
+        ctx.rest = {k: batch[k] for k in ("stance", "gait_duty") if batch.get(k) is not None}
+        ctx.set_materialize_grads(False)  # an output the loss never reached arrives as None: a NULL cotangent, not an array of zeros
+        # (the phases as the call left them: a copy, the caller's tensor advances again on the next tick)
+        ctx.save_for_backward(before, batch["gait_phase"].clone(), *tensors)
+        ps, pf = _record_points(after)
+        ctx.mark_non_differentiable(after, res["planned"])
+        return res["swing_pos"], res["swing_vel"], ps.clone(), pf.clone(), after, res["planned"]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, pos_bar, vel_bar, ps_bar, pf_bar, _state_bar, _planned_bar):
+        before, phase, *given = ctx.saved_tensors
+        names = SWING_REFERENCE_DIFFERENTIABLE
+        inputs = dict(zip(names, given))
+        need = dict(zip(names, ctx.needs_input_grad[3:]))
+        cot = {k: b.contiguous() for k, b in (("swing_pos", pos_bar), ("swing_vel", vel_bar), ("p_start", ps_bar), ("p_final", pf_bar)) if b is not None}
+        want = tuple(k + "_bar" for k in names if need[k])
+        if not cot or not want:  # no output reached the loss: every gradient is zero
+            return (None, None, None, *[torch.zeros_like(inputs[k]) if need[k] else None for k in names])
+        batch = dict(ctx.rest, gait_phase=phase, **{k: inputs[k] for k in names[:-2] if k != "xdot_d"})
+        s = ctx.ctl.swing_reference_adjoint_batch(batch, before, cot, want=want)
+        return (None, None, None, *[s[k + "_bar"].view_as(inputs[k]) if need[k] else None for k in names])
+
+
+def swing_reference_autograd(ctl, batch, swing_state, p_start, p_final):
+    """BalanceController.swing_reference_autograd (see there): (swing_pos, swing_vel, p_start', p_final', swing_state', planned) of
+    swing_reference_batch() on a copy of `swing_state` whose end points are `p_start` / `p_final`, differentiable in
+    SWING_REFERENCE_DIFFERENTIABLE."""
+    for k in ("swing_pos", "swing_vel"):
+        if batch.get(k) is not None:
+            raise ValueError(f"swing_reference_autograd: the batch carries {k} - this call makes the references")
+    missing = [k for k in SWING_REFERENCE_DIFFERENTIABLE[:-2] + ("gait_phase",) if batch.get(k) is None]
+    if missing:
+        raise ValueError(f"swing_reference_autograd: the batch lacks {missing}")
+    n = batch["x"].shape[0]
+    for name, t in (("p_start", p_start), ("p_final", p_final)):
+        if t is None or t.dtype != torch.float64 or t.numel() != 12 * n:
+            raise ValueError(f"swing_reference_autograd: {name} is a float64 [n,12] tensor")
+    tensors = [batch[k] for k in SWING_REFERENCE_DIFFERENTIABLE[:-2]] + [p_start, p_final]
+    detached = {k: (v.detach() if isinstance(v, torch.Tensor) else v) for k, v in batch.items() if k != "swing_state"}
+    return _SwingReference.apply(ctl, detached, swing_state.detach(), *tensors)
+
+
+_ROLLOUT_GAIT_REFUSED = {"stance": "the gait clock makes the contact mask from gait_phase", "swing_pos": "the references are made per step",
+                         "swing_vel": "the references are made per step", "gait_dt": "the clock's step is this call's gait_dt argument",
+                         "feet": "the tick reads joint_q (rollout_autograd() steps the bare rigid body on `feet`)"}
+
+
+def rollout_gait_autograd(ctl, batch, steps, dt, leg_inertia, gait_dt, act_tol=1e-7, warm=True, params=None, joint_gains=None):
+    """BalanceController.rollout_gait_autograd (see there): `steps` times swing_reference_autograd() with the clock advancing,
+    tick_autograd() on its references and phases, leg_plant_step_autograd() with those phases; the swing record threaded through."""
+    for k, why in _ROLLOUT_GAIT_REFUSED.items():
+        if batch.get(k) is not None:
+            raise ValueError(f"rollout_gait_autograd: the batch carries {k} - {why}")
+    missing = [k for k in ("joint_q", "joint_qdot", "gait_phase", "swing_state") if batch.get(k) is None]
+    if missing:
+        raise ValueError(f"rollout_gait_autograd: the batch lacks {missing}")
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError("rollout_gait_autograd: steps must be >= 0")
+    names = LEG_PLANT_DIFFERENTIABLE[:-1]
+    n, dev = batch["x"].shape[0], batch["x"].device
+    if isinstance(gait_dt, torch.Tensor):
+        clock = gait_dt.detach().to(dtype=torch.float64, device=dev).contiguous()
+    else:
+        clock = torch.full((n,), float(gait_dt), dtype=torch.float64, device=dev)
+    cur = {k: v for k, v in batch.items() if k not in ("swing_state", "gait_phase")}
+    duty = batch.get("gait_duty")
+    record, phase = batch["swing_state"].detach(), batch["gait_phase"].detach()
+    p_start, p_final = (t.clone() for t in _record_points(record))
+    out, active, planned = {}, None, None
+    flags = torch.zeros((n,), dtype=torch.int32, device=dev) if steps else None
+    for _ in range(steps):
+        phase = phase.clone()  # this step's own phases: advanced in place by the references' clock, then read by the tick and the plant
+        ref_in = dict({k: cur[k] for k in SWING_REFERENCE_DIFFERENTIABLE[:-2]}, gait_phase=phase, gait_dt=clock)
+        if duty is not None:
+            ref_in["gait_duty"] = duty
+        pos, vel, p_start, p_final, record, planned = swing_reference_autograd(ctl, ref_in, record, p_start, p_final)
+        res = {"grf_body": torch.zeros((n, 12), dtype=torch.float64, device=dev), "status": torch.full((n,), -1, dtype=torch.int32, device=dev),
+               "joint_tau": torch.zeros((n, 12), dtype=torch.float64, device=dev)}
+        kwargs = dict(out=res)
+        if warm:  # this step's own working-set word; the next solve starts from it (detached: an int32)
+            res["active_set"] = torch.zeros((n,), dtype=torch.int32, device=dev)
+            kwargs.update(warm=active, want_active_set=True)
+            active = res["active_set"]
+        tick_in = dict(cur, gait_phase=phase, swing_pos=pos, swing_vel=vel)
+        tau, grf, status = tick_autograd(ctl, tick_in, act_tol, params=params, joint_gains=joint_gains, **kwargs)
+        new = leg_plant_step_autograd(ctl, cur, tau, dt, leg_inertia, gait_phase=phase, gait_duty=duty, flags=flags)
+        cur = dict(cur, **dict(zip(names, new)))
+        out = {"joint_tau": tau, "grf_body": grf, "status": status, "flags": flags}
+    if warm and active is not None:
+        out["active_set"] = active
+    out.update(gait_phase=phase, swing_state=record, p_start=p_start, p_final=p_final)
+    if planned is not None:
+        out["planned"] = planned
+    return {k: cur[k] for k in names}, out
 
 
 _ROLLOUT_TICK_REFUSED = {"gait_dt": "the gait clock writes gait_phase in place; the contact mask is held over the rollout",

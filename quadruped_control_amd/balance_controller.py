@@ -29,6 +29,7 @@ _IN_FIELDS = (("Rwb", 9), ("Rwb_d", 9), ("x", 3), ("xdot", 3), ("w", 3), ("x_d",
 
 
 _SENSITIVITY_SWING_WANT = ("swing_pos_bar", "swing_vel_bar", "joint_q_bar", "joint_qdot_bar", "Rwb_bar", "x_bar")  # sensitivity_swing_batch's default
+_SWING_REFERENCE_ADJOINT_WANT = ("Rwb_bar", "x_bar", "xdot_bar", "w_bar", "xdot_d_bar", "joint_q_bar", "p_start_bar", "p_final_bar")  # swing_reference_adjoint_batch's default
 _LEG_PLANT_ADJOINT_WANT = ("Rwb_bar", "x_bar", "xdot_bar", "w_bar", "joint_q_bar", "joint_qdot_bar", "joint_tau_bar")  # leg_plant_step_adjoint's default
 
 
@@ -975,6 +976,117 @@ class BalanceController:
         launch()
         return res
 
+    # ------------------------------------------- the swing references as a launch of their own, and their reverse pass
+    def _swing_reference_batch(self, who, batch, io, own):
+        """_readonly_batch() for the two swing-reference calls, plus the batch's swing_state record."""
+        import torch
+
+        n, dev, bi = self._readonly_batch(who, batch, _SWING_REFERENCE_FIELDS, io, own)
+        ss = batch.get("swing_state")
+        if _check_tensor("swing_state", ss, n, SWING_STATE_DTYPE.itemsize, torch.uint8, dev, False,
+                         msg="swing_state: need a contiguous uint8 tensor of n * 224 bytes on the device"):
+            bi.swing_state = ss.data_ptr()
+        return n, dev, bi
+
+    def plan_swing_reference(self, batch, want=("swing_pos", "swing_vel"), out=None, stream=None):
+        """swing_reference_batch() marshalled once: returns (launch, out), `launch()` being one qc_swing_reference_batch call
+        (graph-capturable) on tensors that are read and updated in place.  Planning launches nothing.  `out`: a dict of tensors to
+        write into instead of new ones (every name in `want`).  A call the library refuses raises ValueError with its message, from
+        launch()."""
+        io = _lib.QcSwingReferenceIo()
+        self._lib.qc_default_swing_reference(C.byref(io))
+        n, dev, bi = self._swing_reference_batch("swing_reference", batch, io, [])
+        res = _outputs("swing_reference", _SWING_REFERENCE_OUTPUTS, want, out, n, dev, io)
+        args = (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
+        return self._launcher("qc_swing_reference_batch", args, (batch, res, bi, io), ValueError), res
+
+    def swing_reference_batch(self, batch, want=("swing_pos", "swing_vel"), out=None, stream=None):
+        """The front half of the tick as a launch of its own (qc_swing_reference_batch, include/qc_balance.h; INTEGRATION.md
+        "Differentiating a rollout"): what control_batch() does before the QP for a batch with swing_state.  `batch`: Rwb, x, xdot, w,
+        xdot_d, joint_q, gait_phase [n,4] and swing_state (the uint8 record tensor control_batch() takes), optionally stance,
+        gait_duty and gait_dt.  With gait_dt the phases advance IN PLACE; the records are updated IN PLACE (leg_state, has_traj and,
+        for a replanned leg, p_start and p_final).  `want`: any of "swing_pos", "swing_vel" [n,4,3] - the world-frame references
+        control_batch() takes as batch["swing_pos"] / batch["swing_vel"]; zeros for a stance leg and a swing leg without a trajectory -
+        and "planned" uint8 [n] (bit l: leg l was replanned by this call).  control_batch() on the returned references and the phases
+        this call left gives the tick's joint_tau, grf_body and status bit for bit.  Asynchronous on `stream`, no synchronisation.
+        Returns the dict of device tensors; ValueError with the library's message for a call it refuses."""
+        launch, res = self.plan_swing_reference(batch, want, out, stream)
+        launch()
+        return res
+
+    def plan_swing_reference_adjoint(self, batch, state_before, cotangents, want=_SWING_REFERENCE_ADJOINT_WANT, out=None, Rwb_bar_in=None,
+                                     x_bar_in=None, xdot_bar_in=None, w_bar_in=None, joint_q_bar_in=None, stream=None):
+        """swing_reference_adjoint_batch() marshalled once: returns (launch, out), `launch()` being one
+        qc_swing_reference_adjoint_batch call (graph-capturable) on tensors that are read in place.  Planning launches nothing.  `out`:
+        a dict of tensors to write into instead of new ones (every name in `want`) - an output may be its `_in` tensor, and
+        out["p_start_bar"] / out["p_final_bar"] may be cotangents["p_start"] / cotangents["p_final"].  A call the library refuses raises
+        ValueError with its message, from launch()."""
+        import torch
+
+        io = _lib.QcSwingReferenceAdjointIo()
+        self._lib.qc_default_swing_reference_adjoint(C.byref(io))
+        unknown = [k for k in cotangents if k not in _SWING_REFERENCE_COTANGENTS]
+        if unknown:
+            raise ValueError(f"swing_reference_adjoint: unknown cotangent(s) {unknown}; the call's outputs are {tuple(_SWING_REFERENCE_COTANGENTS)}")
+        own = [(_SWING_REFERENCE_COTANGENTS[k], t, 12) for k, t in cotangents.items()]
+        own += [("Rwb_bar_in", Rwb_bar_in, 9), ("x_bar_in", x_bar_in, 3), ("xdot_bar_in", xdot_bar_in, 3), ("w_bar_in", w_bar_in, 3),
+                ("joint_q_bar_in", joint_q_bar_in, 12)]
+        n, dev, bi = self._swing_reference_batch("swing_reference_adjoint", batch, io, own)
+        if _check_tensor("state_before", state_before, n, SWING_STATE_DTYPE.itemsize, torch.uint8, dev, False,
+                         msg="state_before: need a contiguous uint8 tensor of n * 224 bytes on the device"):
+            io.state_before = state_before.data_ptr()
+        res = _outputs("swing_reference_adjoint", _SWING_REFERENCE_ADJOINT_OUTPUTS, want, out, n, dev, io)
+        args = (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
+        keep = (batch, state_before, cotangents, Rwb_bar_in, x_bar_in, xdot_bar_in, w_bar_in, joint_q_bar_in, res, bi, io)
+        return self._launcher("qc_swing_reference_adjoint_batch", args, keep, ValueError), res
+
+    def swing_reference_adjoint_batch(self, batch, state_before, cotangents, want=_SWING_REFERENCE_ADJOINT_WANT, out=None, Rwb_bar_in=None,
+                                      x_bar_in=None, xdot_bar_in=None, w_bar_in=None, joint_q_bar_in=None, stream=None):
+        """The reverse pass of swing_reference_batch() (qc_swing_reference_adjoint_batch, include/qc_balance.h).  `batch`: the one the
+        forward call read, with gait_phase AS THAT CALL LEFT IT and without gait_dt - Rwb, x, xdot, w, joint_q, gait_phase and the
+        optional stance / gait_duty are all that is read of it.  `state_before`: a copy of the swing_state tensor from BEFORE the
+        forward call.  `cotangents`: a dict with any of "swing_pos", "swing_vel" [n,4,3], "p_start", "p_final" [n,12] (on the record
+        after the call); a missing one is zero, at least one given.  `want`: any of "Rwb_bar" [n,9] (entrywise, row-major), "x_bar",
+        "xdot_bar", "w_bar", "xdot_d_bar" [n,3], "joint_q_bar" [n,4,3], "p_start_bar", "p_final_bar" [n,12] (on the record before the
+        call) and "flags" int32 [n].  `Rwb_bar_in`, `x_bar_in`, `xdot_bar_in`, `w_bar_in`, `joint_q_bar_in`: added to the outputs of
+        those names; each may be the output's own tensor.  flags bit l: leg l is replanned at an x_z that is not finite and > 0 - NaN
+        in every row of the robot.  The clock and the contact mask are held: no cotangent of the phases.  Nothing of `batch` is written.
+        Asynchronous on `stream`, no synchronisation.  Returns the dict of device tensors; ValueError with the library's message for a
+        call it refuses."""
+        launch, res = self.plan_swing_reference_adjoint(batch, state_before, cotangents, want, out, Rwb_bar_in, x_bar_in, xdot_bar_in, w_bar_in,
+                                                        joint_q_bar_in, stream)
+        launch()
+        return res
+
+    def swing_reference_autograd(self, batch, swing_state, p_start, p_final):
+        """swing_reference_batch() with a gradient, OUT OF PLACE in the record: returns (swing_pos, swing_vel, p_start', p_final',
+        swing_state', planned) - the references [n,4,3], the trajectory end points [n,12] and the record tensor AFTER the call, and the
+        replan bits -, differentiable in Rwb, x, xdot, w, xdot_d, joint_q of `batch` and in `p_start`, `p_final` [n,12], the end points
+        BEFORE the call (they take the place of the record's own; the integer part of the record, leg_state and has_traj, is carried
+        undifferentiated).  `swing_state` is left as it is; a batch["gait_dt"] advances batch["gait_phase"] IN PLACE, as control_batch()
+        does, and backward reads a copy of the advanced phases.  Backward is one swing_reference_adjoint_batch() call on the current
+        stream, without host synchronisation; an output the loss never reached is a missing cotangent.  The clock and the contact mask
+        are held; a robot replanned at x_z <= 0 gets NaN gradients.  There is no double backward."""
+        from .autograd import swing_reference_autograd
+
+        return swing_reference_autograd(self, batch, swing_state, p_start, p_final)
+
+    def rollout_gait_autograd(self, batch, steps, dt, leg_inertia, gait_dt, act_tol=1e-7, warm=True, params=None, joint_gains=None):
+        """The functional twin of rollout_tick(batch, None, ...) for a batch with swing_state and a running clock: per step
+        swing_reference_autograd() with the clock advancing by `gait_dt` (a number, or a float64 [n] tensor), tick_autograd() on the
+        references it returned and the phases it left, leg_plant_step_autograd() with those same phases; the swing record and its
+        p_start / p_final are threaded from step to step, so footholds replanned on a stance -> swing edge carry a gradient to the state
+        they were planned from and to xdot_d.  `batch` is not modified (its gait_phase and swing_state are copied).  ValueError for a
+        batch with stance (the clock makes the mask), swing_pos / swing_vel, gait_dt (it is this call's argument), `feet`, or without
+        joint_q, joint_qdot, gait_phase or swing_state.  Returns (state, out): `state` the final Rwb, x, xdot, w, joint_q, joint_qdot,
+        `out` the joint_tau, grf_body, status (and active_set) of the LAST tick, "flags" (the last step's plant flags) and the final
+        "gait_phase", "swing_state", "p_start", "p_final" and "planned".  With gait_dt = dt the forward values are rollout_tick(batch,
+        None, ...)'s bit for bit.  The gradient is the one on every solve's active face, at every tick's clamp mask, with the clock, the
+        contact mask and the plan decisions held; `params` and `joint_gains` as tick_autograd()'s.  Memory grows with `steps`."""
+        from .autograd import rollout_gait_autograd
+
+        return rollout_gait_autograd(self, batch, steps, dt, leg_inertia, gait_dt, act_tol, warm, params, joint_gains)
+
     def tick_autograd(self, batch, act_tol=1e-7, flags=None, params=None, joint_gains=None, **control_kwargs):
         """The tick with swing references, with a gradient: returns (joint_tau, grf_body, status) of control_batch(batch,
         want_torques=True, **control_kwargs) for a batch that carries joint_q, joint_qdot, swing_pos, swing_vel and a contact mask
@@ -1131,6 +1243,18 @@ _KINEMATICS_FIELDS = (("joint_q", 12, "float64"),) + _READONLY_FIELDS[len(_STATE
 # sensitivity_swing: the six arrays of the swing chain, the contact mask, and gait_dt so that the library names its refusal
 _SWING_FIELDS = (("Rwb", 9, "float64"), ("x", 3, "float64")) + tuple((k, 12, "float64") for k in ("joint_q", "joint_qdot", "swing_pos", "swing_vel")) + \
     _READONLY_FIELDS[len(_STATE_FIELDS):] + (("gait_dt", 1, "float64"),)
+
+
+# swing_reference / swing_reference_adjoint: what the two calls read of the batch, and - so that the library names its refusal - `feet`,
+# gait_dt, swing_pos and swing_vel
+_SWING_REFERENCE_FIELDS = tuple((k, m, "float64") for k, m in (("Rwb", 9), ("x", 3), ("xdot", 3), ("w", 3), ("xdot_d", 3), ("joint_q", 12), ("feet", 12))) + \
+    _READONLY_FIELDS[len(_STATE_FIELDS):] + (("gait_dt", 1, "float64"), ("swing_pos", 12, "float64"), ("swing_vel", 12, "float64"))
+_SWING_REFERENCE_OUTPUTS = {"swing_pos": ((4, 3), "float64"), "swing_vel": ((4, 3), "float64"), "planned": ((), "uint8")}
+_SWING_REFERENCE_ADJOINT_OUTPUTS = {"Rwb_bar": ((9,), "float64"), **{k: ((3,), "float64") for k in ("x_bar", "xdot_bar", "w_bar", "xdot_d_bar")},
+                                    "joint_q_bar": ((4, 3), "float64"), "p_start_bar": ((12,), "float64"), "p_final_bar": ((12,), "float64"),
+                                    "flags": ((), "int32")}
+# the forward call's outputs a cotangent may be given on -> the io field
+_SWING_REFERENCE_COTANGENTS = {"swing_pos": "swing_pos_bar", "swing_vel": "swing_vel_bar", "p_start": "p_start_next_bar", "p_final": "p_final_next_bar"}
 
 
 # a parameter cotangent: name -> (slice of the 211 values, shape), in the order of the double members of qc_params

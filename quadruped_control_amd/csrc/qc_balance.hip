@@ -641,14 +641,11 @@ QC_DEV uint32_t assemble_from_state(CParams& P, const BatchIn& in, long robot, i
 #pragma unroll
     for (int i = 0; i < 4; i++) phs[i] = X.ph[i];
     if (in.gait_dt) {  // GaitScheduler::update(dt), gait.cpp:113-123: the clock of this robot advances first
-      const double step = 1.0 / (P.t_swing + P.t_stance) * X.dt;
+      const double step = gait_clock_step(P, X.dt);
       double* wp = in.gait_phase + 4 * robot;
 #pragma unroll
       for (int i = 0; i < 4; i++) {
-        // fmod(v, 1.0), bit for bit, without the library's division loop (four of them per robot were ~2 us of a wave's fill): the
-        // integer part of a double subtracts exactly, and fmod's result carries the sign of v (-1.0 -> -0.0; inf -> NaN both ways)
-        const double v = phs[i] + step;
-        phs[i] = __builtin_copysign(v - __builtin_trunc(v), v);
+        phs[i] = advance_phase(phs[i], step);  // (qc_device.hpp: fmod(v, 1.0) bit for bit)
         // every lane of the group computes the same four values; the first one stores them (read again by this wave's
         // store phase for the swing trajectories - workgroup scope, see swing_fetch)
         if (member == 0) __hip_atomic_store(wp + i, phs[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -2407,6 +2404,34 @@ int qc_sensitivity_swing_batch(qc_handle* h, size_t n, const qc_batch_in* in, co
       leg ? (body ? qc::sensitivity_swing_kernel<true, true> : qc::sensitivity_swing_kernel<true, false>)
           : (body ? qc::sensitivity_swing_kernel<false, true> : qc::sensitivity_swing_kernel<false, false>);
   fn<<<dim3(qc::sensitivity_swing_blocks(n)), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)(4 * n), a);
+  QC_HIP(hipGetLastError());
+  return QC_OK;
+}
+
+void qc_default_swing_reference(qc_swing_reference_io* io) { (void)zeroed(io); }
+
+int qc_swing_reference_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_swing_reference_io* io, void* stream) {
+  if (const int rc = qc::check_swing_reference_args(h, n, in, io); rc != QC_OK || n == 0) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  const qc::SwingReferenceArgs a{in->Rwb, in->x, in->xdot, in->w, in->xdot_d, in->joint_q, in->gait_phase, in->stance, in->gait_duty, in->gait_dt,
+                                 reinterpret_cast<qc::SwingState*>(in->swing_state), io->swing_pos, io->swing_vel, io->planned};
+  qc::swing_reference_kernel<<<dim3(qc::swing_reference_blocks(n)), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, a);
+  QC_HIP(hipGetLastError());
+  return QC_OK;
+}
+
+void qc_default_swing_reference_adjoint(qc_swing_reference_adjoint_io* io) { (void)zeroed(io); }
+
+int qc_swing_reference_adjoint_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_swing_reference_adjoint_io* io, void* stream) {
+  if (const int rc = qc::check_swing_reference_adjoint_args(h, n, in, io); rc != QC_OK || n == 0) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  // (of `in`: the state, joint_q and the contact mask as the forward call left it - nothing of it is written)
+  const qc::SwingReferenceAdjointArgs a{in->Rwb, in->x, in->xdot, in->w, in->joint_q, in->gait_phase, in->stance, in->gait_duty,
+                                        reinterpret_cast<const qc::SwingState*>(io->state_before), io->swing_pos_bar, io->swing_vel_bar,
+                                        io->p_start_next_bar, io->p_final_next_bar, io->Rwb_bar_in, io->x_bar_in, io->xdot_bar_in, io->w_bar_in,
+                                        io->joint_q_bar_in, io->Rwb_bar, io->x_bar, io->xdot_bar, io->w_bar, io->xdot_d_bar, io->joint_q_bar,
+                                        io->p_start_bar, io->p_final_bar, io->flags};
+  qc::swing_reference_adjoint_kernel<<<dim3(qc::swing_reference_blocks(n)), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, a);
   QC_HIP(hipGetLastError());
   return QC_OK;
 }

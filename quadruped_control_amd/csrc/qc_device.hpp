@@ -471,6 +471,20 @@ QC_DEV bool phase_in_stance(double ph, double duty) {
   const bool le = (ph < duty) || (fabs(ph - duty) < 1.0e-12);
   return ge0 && le;
 }
+// The gait clock, in one place.  GaitScheduler::update(dt), gait.cpp:113-123: every phase advances by dt / (t_swing + t_stance) and is
+// wrapped by fmod(v, 1.0) - bit for bit, without the library's division loop (four of them per robot were ~2 us of a wave's fill): the
+// integer part of a double subtracts exactly, and fmod's result carries the sign of v (-1.0 -> -0.0; inf -> NaN both ways).
+QC_DEV double gait_clock_step(CParams& P, double dt) { return 1.0 / (P.t_swing + P.t_stance) * dt; }
+QC_DEV double advance_phase(double ph, double step) {
+  const double v = ph + step;
+  return __builtin_copysign(v - __builtin_trunc(v), v);
+}
+// The plan decision of one leg.  FootPlanner::updateStates, foot_planner.cpp:106-157: a leg gets a new foothold on a stance -> swing
+// edge (`prev` = the LegState of the previous tick), or whenever it swings on the very first call (`first`).  DUPLICATED: the tick's
+// swing_plan (qc_balance.hip) keeps the same line written out - called from there, this function reorders the operands of a few
+// scalar and / or instructions of the solve kernels, and their code is to stay byte for byte what it was (profiles/swing_reference.md).
+// The kernels of qc_swing_reference.hpp call it; tests/test_gpu_swing_reference.py holds the two together record by record.
+QC_DEV bool leg_replans(bool swing_now, bool first, int prev) { return swing_now && (first || prev == 1); }
 // The contact mask (bits 0-3), resolved as qc_control_batch resolves it: `sw` = the robot's four LegState bytes if has_stance; else
 // phase_in_stance on the four phases if has_phase; else make_stance_gait().  `running` false (a commander state whose gait_running
 // is 0) is all stance whatever the rest.
@@ -832,12 +846,13 @@ QC_DEV void plan_foothold(CParams& P, int leg, const double (&R)[9], const doubl
 // FootTrajectoryManager::referenceState + FootTrajectory::trackTrajectory, trajectory.cpp:234-254, 360-388.
 // coefficients = A^-1 B with B = [p_start; p_final; p_centre; 0...] (trajectory.cpp:220-225, 279-296), so
 // s(t) = h0(t) p_start + h1(t) p_final + h2(t) p_centre with h_k(t) = sum_j basis[j][k] t^j.
-QC_DEV void track_swing(CParams& P, double phase, const double (&p0)[3], const double (&pf)[3], double (&pos)[3], double (&vel)[3]) {
+// (swing_basis: h_k and h_k' at the clamped t of `phase` - the loop the reverse pass of the references, qc_swing_reference.hpp, shares)
+QC_DEV void swing_basis(CParams& P, double phase, double (&h)[3], double (&dh)[3]) {
   const double duty = P.t_stance / (P.t_swing + P.t_stance);  // stance_phase_, trajectory.cpp:303
   const double slope = 1.0 / (1.0 - duty), yint = 1.0 - slope; // :304-305
   const double u = slope * phase + yint;
   const double t = u < 0.0 ? 0.0 : (1.0 < u ? 1.0 : u);  // std::clamp, :369 (two compares: a NaN phase stays NaN)
-  double h[3] = {0.0, 0.0, 0.0}, dh[3] = {0.0, 0.0, 0.0};
+  h[0] = h[1] = h[2] = dh[0] = dh[1] = dh[2] = 0.0;
   double tp = 1.0, tpm = 0.0;  // t^j and j t^(j-1)
 #pragma unroll
   for (int j = 0; j < 7; j++) {
@@ -849,6 +864,10 @@ QC_DEV void track_swing(CParams& P, double phase, const double (&p0)[3], const d
     tpm = (double)(j + 1) * tp;
     tp *= t;
   }
+}
+QC_DEV void track_swing(CParams& P, double phase, const double (&p0)[3], const double (&pf)[3], double (&pos)[3], double (&vel)[3]) {
+  double h[3], dh[3];
+  swing_basis(P, phase, h, dh);
   const double pc[3] = {0.5 * (p0[0] + pf[0]), 0.5 * (p0[1] + pf[1]), P.swing_height};  // trajectory.cpp:325-326
 #pragma unroll
   for (int r = 0; r < 3; r++) {

@@ -19,6 +19,7 @@
 #include "qc_sensitivity_params.hpp"
 #include "qc_sensitivity_kin.hpp"
 #include "qc_sensitivity_swing.hpp"
+#include "qc_swing_reference.hpp"
 
 namespace qc {
 
@@ -702,5 +703,49 @@ inline int check_sensitivity_swing_args(const qc_handle* h, size_t n, const qc_b
 
 // workgroups of sensitivity_swing_kernel for n robots: one wave of 16 robots' legs each, capped
 inline unsigned sensitivity_swing_blocks(size_t n) { return capped_blocks(4 * n, SENSITIVITY_BLOCK, SENSITIVITY_MAX_BLOCKS); }
+
+// ---------------------------------------------------------------- qc_swing_reference_batch, qc_swing_reference_adjoint_batch
+// What the two calls refuse about `in` before their own arrays, in this order: references that are already there, feet in place of
+// joint_q (as the tick refuses them for a batch with swing_state).
+inline int check_swing_reference_batch(const char* who, const qc_batch_in* in) {
+  const auto bad = [who](const char* what) { return fail(QC_ERR_INVALID, std::string(who) + what); };
+  if (in->swing_pos || in->swing_vel) return bad(": swing_pos and swing_vel must be NULL (this call makes them)");
+  if (in->feet && !in->joint_q) return bad(": feet without joint_q (the planner starts from the forward kinematics of joint_q)");
+  return QC_OK;
+}
+
+// The argument check of the swing references: what is wrong with the call itself (message prefix "qc_swing_reference_batch:").
+inline int check_swing_reference_args(const qc_handle* h, size_t n, const qc_batch_in* in, const qc_swing_reference_io* io) {
+  const char* who = "qc_swing_reference_batch";
+  if (const int rc = check_io(who, h && in, io, "qc_swing_reference_io", "qc_default_swing_reference"); rc != QC_OK) return rc;
+  const auto bad = [who](const char* what) { return fail(QC_ERR_INVALID, std::string(who) + what); };
+  if (const int rc = check_swing_reference_batch(who, in); rc != QC_OK) return rc;
+  if (in->gait_dt && in->stance) return bad(": gait_dt advances gait_phase (stance must be NULL)");
+  if (!io->swing_pos && !io->swing_vel && !io->planned) return bad(": no output requested (swing_pos, swing_vel, planned are all NULL)");
+  if (n == 0) return QC_OK;
+  if (!in->Rwb || !in->x || !in->xdot || !in->w || !in->xdot_d || !in->joint_q || !in->gait_phase || !in->swing_state)
+    return bad(": Rwb, x, xdot, w, xdot_d, joint_q, gait_phase and swing_state are required");
+  return check_one_launch(who, n, SENSITIVITY_BLOCK);
+}
+
+// The argument check of their reverse pass (message prefix "qc_swing_reference_adjoint_batch:").
+inline int check_swing_reference_adjoint_args(const qc_handle* h, size_t n, const qc_batch_in* in, const qc_swing_reference_adjoint_io* io) {
+  const char* who = "qc_swing_reference_adjoint_batch";
+  if (const int rc = check_io(who, h && in, io, "qc_swing_reference_adjoint_io", "qc_default_swing_reference_adjoint"); rc != QC_OK) return rc;
+  const auto bad = [who](const char* what) { return fail(QC_ERR_INVALID, std::string(who) + what); };
+  if (const int rc = check_swing_reference_batch(who, in); rc != QC_OK) return rc;
+  if (in->gait_dt) return bad(": gait_dt must be NULL (the reverse pass advances no clock: gait_phase is read as the forward call left it)");
+  if (!io->swing_pos_bar && !io->swing_vel_bar && !io->p_start_next_bar && !io->p_final_next_bar)
+    return bad(": no cotangent given (swing_pos_bar, swing_vel_bar, p_start_next_bar, p_final_next_bar are all NULL)");
+  if (!io->Rwb_bar && !io->x_bar && !io->xdot_bar && !io->w_bar && !io->xdot_d_bar && !io->joint_q_bar && !io->p_start_bar && !io->p_final_bar && !io->flags)
+    return bad(": no output requested (Rwb_bar, x_bar, xdot_bar, w_bar, xdot_d_bar, joint_q_bar, p_start_bar, p_final_bar, flags are all NULL)");
+  if (n == 0) return QC_OK;
+  if (!io->state_before) return bad(": state_before is required (the swing records from before the forward call)");
+  if (!in->Rwb || !in->x || !in->xdot || !in->w || !in->joint_q || !in->gait_phase) return bad(": Rwb, x, xdot, w, joint_q and gait_phase are required");
+  return check_one_launch(who, n, SENSITIVITY_BLOCK);
+}
+
+// workgroups of the two kernels for n robots: one wave each, capped
+inline unsigned swing_reference_blocks(size_t n) { return capped_blocks(n, SENSITIVITY_BLOCK, SENSITIVITY_MAX_BLOCKS); }
 
 }  // namespace qc

@@ -1,0 +1,372 @@
+"""-m gpu: qc_swing_reference_batch and qc_swing_reference_adjoint_batch on the device - identity with the tick, the reverse pass
+against the 50-digit restatement (tests/swing_reference_restatement.py), aliasing, flagged robots, refusals, and a gait rollout with a
+gradient.  The handle is at a non-default model and gait (SR.ODD_MODEL: set_kinematics, set_gait); the batches hold robots on their
+first call, crossing one and two stance -> swing edges, mid-swing with a carried trajectory, with a trajectory just cleared by another
+leg's replan, and all stance (SR.pool's kinds)."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from tests import leg_plant_adjoint_restatement as LA
+from tests import swing_reference_restatement as SR
+from tests.solved_batch_support import SENTINEL, assert_raw_refusals, batch_in, params, q  # noqa: F401
+
+pytestmark = pytest.mark.gpu
+SIZES = (1, 63, 64, 65, 257)
+M = SR.ODD_MODEL
+K_REF = {k: 4.0 * c for k, c in SR.C_REF.items()}  # the device's bars: 4 x the float64 restatement's own worst ratio (measured on the CPU)
+K_FWD = {k: 4.0 * c for k, c in SR.C_FWD.items()}
+STATE_KEYS = ("Rwb", "x", "xdot", "w", "xdot_d", "joint_q")
+
+
+def _handle(q, model):
+    c = q.BalanceController.from_params(params(q, "uniform"), device=0)
+    c.set_tuning(race=0)  # deterministic: `iterations` cannot differ between the two paths
+    c.set_kinematics(**model.handle_arguments())
+    c.set_gait(model.t_swing, model.t_stance)
+    return c
+
+
+@pytest.fixture(scope="module")
+def ctl(q):
+    c = _handle(q, M)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def reference():
+    """the pool of 257 robots and its 50-digit forward and reverse passes with every accumulator, once; never changed"""
+    n = 257
+    b, state, dt = SR.pool(M, n)
+    fwd, fcond, after, phases, planned = SR.reference_mp(M, b, state, gait_dt=dt)
+    bars, ins = SR.cotangents(n), SR.accumulators(n)
+    rev, rcond, flags = SR.reference_adjoint_mp(M, dict(b, gait_phase=phases), state, bars, **ins)
+    assert not flags.any()
+    kinds = [set(np.flatnonzero(np.arange(n) % 6 == k)) for k in range(6)]
+    assert all(planned[sorted(kinds[k])].all() for k in (0, 1, 2)) and not any(planned[sorted(kinds[k])].any() for k in (3, 4, 5))
+    return dict(b=b, state=state, dt=dt, fwd=fwd, fcond=fcond, after=after, phases=phases, planned=planned, bars=bars, ins=ins, rev=rev, rcond=rcond)
+
+
+def _cuda(a):
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _records(state):
+    return _cuda(state.view(np.uint8).reshape(state.shape[0], -1))
+
+
+def _full(b):
+    """the pool's arrays with the rest of what a tick reads: the desired pose the robot's own, joints at rest"""
+    n = b["x"].shape[0]
+    return dict(b, Rwb_d=b["Rwb"].copy(), x_d=b["x"].copy(), w_d=np.zeros((n, 3)), joint_qdot=np.zeros((n, 12)))
+
+
+def _first(c, n):
+    cut = lambda v: np.ascontiguousarray(v[:n])
+    return {k: cut(v) for k, v in c["b"].items()}, cut(c["state"]), cut(c["dt"])
+
+
+@pytest.mark.parametrize("n", SIZES)
+def test_identity_with_the_tick(q, ctl, reference, n):
+    """Path A: control_batch(want_torques=True) with swing_state and gait_dt.  Path B: swing_reference_batch with the same gait_dt, then
+    control_batch on the returned swing_pos / swing_vel and the phases it left.  The records bytewise, gait_phase, joint_tau, grf_body,
+    status and iterations: bit equality.  planned and the records are the restatement's; the references within 4 C_FWD of 50 digits."""
+    import torch
+
+    b, state, dt = _first(reference, n)
+    full = _full(b)
+    a_in = dict(q.to_device(full), swing_state=_records(state), gait_dt=_cuda(dt))
+    A = ctl.control_batch(a_in, want_torques=True, want_iterations=True)
+    b_in = dict(q.to_device(full), swing_state=_records(state), gait_dt=_cuda(dt))
+    refs = ctl.swing_reference_batch({k: b_in[k] for k in STATE_KEYS + ("gait_phase", "swing_state", "gait_dt")}, want=("swing_pos", "swing_vel", "planned"))
+    tick = {k: v for k, v in b_in.items() if k not in ("swing_state", "gait_dt")}
+    B = ctl.control_batch(dict(tick, swing_pos=refs["swing_pos"], swing_vel=refs["swing_vel"]), want_torques=True, want_iterations=True)
+    torch.cuda.synchronize()
+    assert torch.equal(a_in["swing_state"], b_in["swing_state"]), "the swing records differ"
+    assert torch.equal(a_in["gait_phase"], b_in["gait_phase"]) and not torch.equal(a_in["gait_phase"], _cuda(b["gait_phase"]))
+    for k in ("joint_tau", "grf_body", "status", "iterations"):
+        assert torch.equal(A[k].view(torch.int64) if A[k].dtype == torch.float64 else A[k], B[k].view(torch.int64) if B[k].dtype == torch.float64 else B[k]), k
+    assert bool((A["joint_tau"] != 0).any())
+    # ... and against the restatement
+    rec = b_in["swing_state"].cpu().numpy().reshape(-1).view(SR.STATE_DTYPE)
+    exp = reference["after"][:n]
+    assert np.array_equal(refs["planned"].cpu().numpy(), reference["planned"][:n])
+    assert np.array_equal(rec["leg_state"], exp["leg_state"]) and np.array_equal(rec["has_traj"], exp["has_traj"])
+    assert np.array_equal(b_in["gait_phase"].cpu().numpy(), reference["phases"][:n])
+    got = {"swing_pos": refs["swing_pos"].cpu().numpy().reshape(n, 12), "swing_vel": refs["swing_vel"].cpu().numpy().reshape(n, 12),
+           "p_start": rec["p_start"], "p_final": rec["p_final"]}
+    for k, bar in K_FWD.items():
+        r = SR.worst_ratio(got[k], reference["fwd"][k][:n], reference["fcond"][k][:n])
+        print(f"n={n} forward {k}: {r:.3f} EPS x condition sum (bar {bar})")
+        assert r <= bar, (k, r)
+
+
+def _adjoint(q, ctl, c, n, want=SR.OUTPUTS + ("flags",), out=None, ins=True, bars=None, b=None):
+    import torch
+
+    bb, state, _ = _first(c, n)
+    bb = dict(bb if b is None else b, gait_phase=c["phases"][:n])
+    cot = {k: _cuda(v[:n]) for k, v in (c["bars"] if bars is None else bars).items()}
+    acc = {k: _cuda(v[:n]) for k, v in c["ins"].items()} if ins is True else (ins or {})
+    r = ctl.swing_reference_adjoint_batch(q.to_device({k: bb[k] for k in STATE_KEYS + ("gait_phase",)}), _records(state), cot, want=want, out=out, **acc)
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy().reshape(n, -1) for k, v in r.items()}
+
+
+@pytest.mark.parametrize("n", SIZES)
+def test_reverse_pass_against_50_digits(q, ctl, reference, n):
+    got = _adjoint(q, ctl, reference, n)
+    assert not got["flags"].any()
+    for k, bar in K_REF.items():
+        r = SR.worst_ratio(got[k], reference["rev"][k][:n], reference["rcond"][k][:n])
+        print(f"n={n} reverse {k}: {r:.3f} EPS x condition sum (bar {bar})")
+        assert r <= bar, (k, r)
+    plan = reference["planned"][:n] != 0
+    assert np.array_equal(np.abs(got["xdot_d_bar"]).sum(axis=1) > 0, plan)  # xdot_d enters through the planner alone
+
+
+def test_aliasing_and_output_groups(q, ctl, reference):
+    """Every output over its `_in` / `_next_` array gives the out-of-place bits; every output asked for alone gives its bits of the
+    all-outputs call."""
+    import torch
+
+    n, c = 65, reference
+    base = _adjoint(q, ctl, c, n)
+    bb, state, _ = _first(c, n)
+    dev = q.to_device(dict({k: bb[k] for k in STATE_KEYS}, gait_phase=c["phases"][:n]))
+    cot = {k: _cuda(v[:n]) for k, v in c["bars"].items()}
+    acc = {k: _cuda(v[:n]) for k, v in c["ins"].items()}
+    out = {k[:-3]: t for k, t in acc.items()}
+    out.update(p_start_bar=cot["p_start"], p_final_bar=cot["p_final"], xdot_d_bar=torch.zeros((n, 3), dtype=torch.float64, device="cuda"))
+    r = ctl.swing_reference_adjoint_batch(dev, _records(state), cot, want=SR.OUTPUTS, out=out, **acc)
+    torch.cuda.synchronize()
+    for k in SR.OUTPUTS:
+        assert np.array_equal(r[k].cpu().numpy().reshape(n, -1), base[k]), ("in place", k)
+    for k in SR.OUTPUTS:
+        alone = _adjoint(q, ctl, c, n, want=(k,))
+        assert np.array_equal(alone[k], base[k]), ("alone", k)
+    # a missing accumulator is zero, a missing cotangent is zero
+    none = _adjoint(q, ctl, c, n, ins=None, bars={"swing_pos": c["bars"]["swing_pos"]})
+    ref, _ = SR.reference_adjoint_np(M, dict(bb, gait_phase=c["phases"][:n]), state, {"swing_pos": c["bars"]["swing_pos"][:n]})
+    assert all(np.allclose(none[k], ref[k], rtol=0, atol=1e-12) for k in SR.OUTPUTS)
+
+
+def test_flagged_robots(q, ctl, reference):
+    """x_z = 0, < 0, NaN on a replanned leg: the flag bits of its replanned legs and NaN rows; the same x_z on a robot that replans
+    nothing: no flag, finite rows."""
+    n, c = 24, reference
+    bb, _, _ = _first(c, n)
+    bb = dict(bb, x=bb["x"].copy())
+    bb["x"][:, 2] = np.array([0.0, -0.1, np.nan])[(np.arange(n) // 6) % 3]  # every kind of the pool meets every one of the three
+    got = _adjoint(q, ctl, c, n, b=bb)
+    plan = c["planned"][:n]
+    assert np.array_equal(got["flags"].reshape(-1), plan.astype(np.int32)) and plan.any() and (plan == 0).any()
+    for k in SR.OUTPUTS:
+        assert np.isnan(got[k][plan != 0]).all() and np.isfinite(got[k][plan == 0]).all(), k
+
+
+def test_refusals_launch_nothing(q, ctl, reference):
+    import torch
+    from quadruped_control_amd import _lib
+
+    lib, n, c = _lib.load(), 17, reference
+    bb, state, dt = _first(c, n)
+    dev = q.to_device(dict(_full(bb), gait_dt=dt))
+    records = _records(state)
+    dev["swing_state"] = records
+    before = {k: t.clone() for k, t in dev.items()}
+    fkeys = STATE_KEYS + ("gait_phase", "swing_state", "gait_dt")
+    pos, vel = (torch.full((n, 12), SENTINEL, dtype=torch.float64, device="cuda") for _ in range(2))
+    planned = torch.full((n,), 99, dtype=torch.uint8, device="cuda")
+
+    def fio():
+        s = _lib.QcSwingReferenceIo()
+        lib.qc_default_swing_reference(ctypes.byref(s))
+        s.swing_pos, s.swing_vel, s.planned = pos.data_ptr(), vel.data_ptr(), planned.data_ptr()
+        return s
+
+    def untouched(what):
+        assert all(torch.equal(dev[k], before[k]) for k in dev), ("forward wrote its batch", what)
+
+    def refused(fn, prefix, what, bi, s, check=untouched):
+        rc = fn(ctl._h, n, ctypes.byref(bi), ctypes.byref(s), None)
+        assert rc == -1 and _lib.last_error().startswith(prefix), (what, rc, _lib.last_error())
+        torch.cuda.synchronize()
+        check(what)
+
+    fguards = [(pos, SENTINEL, False), (vel, SENTINEL, False), (planned, 99, False)]
+
+    def fintact(what):
+        untouched(what)
+        assert all(bool((t == s_).all()) for t, s_, _ in fguards), what
+
+    f = lib.qc_swing_reference_batch
+    for missing in STATE_KEYS + ("gait_phase", "swing_state"):
+        refused(f, "qc_swing_reference_batch:", "no " + missing, batch_in(dev, [k for k in fkeys if k != missing]), fio(), fintact)
+    for extra in ("swing_pos", "swing_vel"):
+        bi = batch_in(dev, fkeys)
+        setattr(bi, extra, dev["x"].data_ptr())
+        refused(f, "qc_swing_reference_batch: swing_pos and swing_vel must be NULL", extra, bi, fio(), fintact)
+    bi = batch_in(dev, [k for k in fkeys if k != "joint_q"])
+    bi.feet = dev["joint_q"].data_ptr()
+    refused(f, "qc_swing_reference_batch: feet without joint_q", "feet", bi, fio(), fintact)
+    bi = batch_in(dev, fkeys)
+    bi.stance = dev["x"].data_ptr()
+    refused(f, "qc_swing_reference_batch: gait_dt advances", "gait_dt with stance", bi, fio(), fintact)
+    s = _lib.QcSwingReferenceIo()
+    lib.qc_default_swing_reference(ctypes.byref(s))
+    refused(f, "qc_swing_reference_batch: no output", "no output", batch_in(dev, fkeys), s, fintact)
+    assert_raw_refusals(f, lambda: (ctl._h, n, batch_in(dev, fkeys), fio()), "qc_swing_reference_io", ctypes.sizeof(_lib.QcSwingReferenceIo), 16,
+                        fguards, untouched=untouched, launched=lambda: None)
+    assert not torch.equal(dev["swing_state"], before["swing_state"]) and not torch.equal(dev["gait_phase"], before["gait_phase"])  # the valid call ran
+
+    # ---- the reverse pass
+    akeys = ("Rwb", "x", "xdot", "w", "joint_q", "gait_phase")
+    cot = {k: _cuda(v[:n]) for k, v in c["bars"].items()}
+    outs = {k: torch.full((n, SR.SIZES[k]), SENTINEL, dtype=torch.float64, device="cuda") for k in SR.OUTPUTS}
+    flags = torch.full((n,), 77, dtype=torch.int32, device="cuda")
+    state_before = _records(state)
+
+    def aio():
+        s = _lib.QcSwingReferenceAdjointIo()
+        lib.qc_default_swing_reference_adjoint(ctypes.byref(s))
+        s.state_before = state_before.data_ptr()
+        for k, t in cot.items():
+            setattr(s, {"swing_pos": "swing_pos_bar", "swing_vel": "swing_vel_bar", "p_start": "p_start_next_bar", "p_final": "p_final_next_bar"}[k], t.data_ptr())
+        for k, t in outs.items():
+            setattr(s, k, t.data_ptr())
+        s.flags = flags.data_ptr()
+        return s
+
+    aguards = [(t, SENTINEL, True) for t in outs.values()] + [(flags, 77, True)]
+
+    def aintact(what):
+        assert all(bool((t == s_).all()) for t, s_, _ in aguards), what
+
+    g = lib.qc_swing_reference_adjoint_batch
+    prefix = "qc_swing_reference_adjoint_batch:"
+    for missing in akeys:
+        refused(g, prefix, "no " + missing, batch_in(dev, [k for k in akeys if k != missing]), aio(), aintact)
+    bi = batch_in(dev, akeys)
+    bi.gait_dt = dev["gait_dt"].data_ptr()
+    refused(g, prefix + " gait_dt must be NULL", "gait_dt", bi, aio(), aintact)
+    bi = batch_in(dev, akeys)
+    bi.swing_pos = dev["x"].data_ptr()
+    refused(g, prefix + " swing_pos and swing_vel must be NULL", "swing_pos", bi, aio(), aintact)
+    s = aio()
+    s.state_before = None
+    refused(g, prefix + " state_before is required", "no state_before", batch_in(dev, akeys), s, aintact)
+    s = aio()
+    s.swing_pos_bar = s.swing_vel_bar = s.p_start_next_bar = s.p_final_next_bar = None
+    refused(g, prefix + " no cotangent given", "no cotangent", batch_in(dev, akeys), s, aintact)
+    s = _lib.QcSwingReferenceAdjointIo()
+    lib.qc_default_swing_reference_adjoint(ctypes.byref(s))
+    s.state_before, s.swing_pos_bar = state_before.data_ptr(), cot["swing_pos"].data_ptr()
+    refused(g, prefix + " no output requested", "no output", batch_in(dev, akeys), s, aintact)
+    with pytest.raises(ValueError, match="^qc_swing_reference_adjoint_batch: gait_dt"):
+        ctl.swing_reference_adjoint_batch({k: dev[k] for k in akeys + ("gait_dt",)}, state_before, cot)
+    with pytest.raises(ValueError, match="unknown output"):
+        ctl.swing_reference_adjoint_batch({k: dev[k] for k in akeys}, state_before, cot, want=("grf_bar",))
+    assert_raw_refusals(g, lambda: (ctl._h, n, batch_in(dev, akeys), aio()), "qc_swing_reference_adjoint_io",
+                        ctypes.sizeof(_lib.QcSwingReferenceAdjointIo), 32, aguards)
+
+
+# ------------------------------------------------------------------ a gait rollout has a gradient
+ROLLOUT_N, ROLLOUT_STEPS, ROLLOUT_H = 65, 4, 1e-4
+ROLLOUT_DIRECTIONS = ("x", "xdot", "w", "xdot_d", "joint_q")
+STATE = LA.INPUTS[:-1]
+
+
+def gait_start(model, n=ROLLOUT_N):
+    """LA.stand_start's generic standing placement on a trot whose diagonal 1, 2 crosses its stance -> swing edge at the SECOND tick of a
+    clock stepping LA.DT: all four legs start in stance on the first call (nothing is planned), legs 1 and 2 one and a half clock steps
+    below the duty, legs 0 and 3 deep in stance; ticks 2, 3 and 4 swing the diagonal along the trajectories replanned at tick 2."""
+    b = {k: v for k, v in LA.stand_start(n).items() if k != "stance"}
+    step = LA.DT / (model.t_swing + model.t_stance)
+    b["gait_phase"] = np.ascontiguousarray(np.tile([0.3 * model.duty, model.duty - 1.5 * step, model.duty - 1.5 * step, 0.3 * model.duty], (n, 1)))
+    return b
+
+
+def test_gait_rollout_has_a_gradient(q):
+    """rollout_gait_autograd over H = 4 ticks of a trot with the clock running and the footholds replanned at the second tick: the
+    forward state is rollout_tick's bit for bit; the gradient in x, xdot, w, xdot_d and joint_q against central differences of
+    rollout_tick under the rule of the existing trot test (tests/test_gpu_sensitivity_swing.py): kept = solved, unflagged, the working
+    set, the clamp mask and here also the replan bits of every step unchanged at +-h, +-2h; the bar |FD(h) - FD(2h)| + 1e-5 |gradient|
+    |direction|; the kept share at least 0.5.  The default model and gait (the standing placement is the default model's)."""
+    import torch
+
+    model = SR.DEFAULT_MODEL
+    ctl = _handle(q, model)
+    n, H, h = ROLLOUT_N, ROLLOUT_STEPS, ROLLOUT_H
+    b = gait_start(model)
+    rng = np.random.default_rng(0x6A17)
+    c = {k: rng.normal(0.0, 1.0, b[k].shape) for k in STATE}
+    v = {k: rng.normal(0.0, 1.0, b[k].shape) for k in ROLLOUT_DIRECTIONS}
+    lo, hi = LA.tau_limits()
+    from quadruped_control_amd.balance_controller import new_swing_states
+
+    def fresh(start):
+        dev = q.to_device(start)
+        dev["swing_state"] = _records(new_swing_states(n))
+        return dev
+
+    def rollout(k):
+        start = dict(b, **{name: np.ascontiguousarray(b[name] + k * h * v[name]) for name in v})
+        words, status, clamp, flags, plans = [], [], [], [], []
+        for steps in range(1, H + 1):  # (the last tick of an s-step rollout is step s - 1's)
+            dev = dict(fresh(start), gait_dt=torch.zeros(n, dtype=torch.float64, device="cuda"))
+            state, out = ctl.rollout_tick(dev, None, steps, LA.DT, LA.STAND_INERTIA)
+            words.append(out["active_set"].cpu().numpy())
+            status.append(out["status"].cpu().numpy())
+            tau = out["joint_tau"].cpu().numpy()
+            clamp.append((tau <= lo) | (tau >= hi))
+            flags.append(out["flags"].cpu().numpy())
+            rec = dev["swing_state"].cpu().numpy().reshape(-1).view(SR.STATE_DTYPE)
+            plans.append(np.c_[rec["leg_state"], rec["has_traj"]])
+        final = {name: state[name].cpu().numpy() for name in STATE}
+        final["gait_phase"], final["swing_state"] = dev["gait_phase"].cpu().numpy(), dev["swing_state"].cpu().numpy()
+        return sum((final[name] * c[name]).sum(axis=1) for name in STATE), np.array(words), np.array(status), np.array(clamp), np.array(flags), final, np.array(plans)
+
+    L0, w0, st0, cl0, fl0, final0, pl0 = rollout(0)
+    assert (pl0[0][:, :4] == 1).all() and (pl0[1][:, [1, 2]] == 0).all() and (pl0[1][:, 4:] == [0, 1, 1, 0]).all(), "one edge, at the second tick"
+    keep = (st0 == 0).all(axis=0) & (fl0 == 0).all(axis=0)
+    pts = {k: rollout(k) for k in (-2, -1, 1, 2)}
+    for Lk, wk, stk, clk, flk, _, plk in pts.values():
+        keep &= (stk == 0).all(axis=0) & (wk == w0).all(axis=0) & (clk == cl0).all(axis=(0, 2)) & (flk == 0).all(axis=0) & (plk == pl0).all(axis=(0, 2))
+    print("kept", keep.mean(), "entries at the clamp at the base point:", int(cl0.sum()))
+
+    dev = fresh(b)
+    for name in v:
+        dev[name].requires_grad_(True)
+    before = {name: t.detach().clone() for name, t in dev.items()}
+    state, out = ctl.rollout_gait_autograd(dev, H, LA.DT, LA.STAND_INERTIA, LA.DT)
+    for name in STATE:
+        assert np.array_equal(state[name].detach().cpu().numpy(), final0[name]), name  # forward: ctl.rollout_tick's bits
+    assert np.array_equal(out["gait_phase"].cpu().numpy(), final0["gait_phase"]) and np.array_equal(out["swing_state"].cpu().numpy(), final0["swing_state"])
+    assert torch.equal(out["active_set"], torch.from_numpy(w0[-1]).cuda()) and np.array_equal(out["flags"].cpu().numpy(), fl0[-1])
+    assert all(torch.equal(dev[name].detach(), before[name]) for name in dev)  # `batch` is not modified
+    assert keep.mean() >= 0.5, keep.mean()
+    kept = torch.from_numpy(keep.astype(np.float64)).cuda()[:, None]
+    sum((state[name] * torch.from_numpy(c[name]).cuda() * kept).sum() for name in STATE).backward()
+    torch.cuda.synchronize()
+    g = {name: dev[name].grad.cpu().numpy() for name in v}
+    fd1, fd2 = (pts[1][0] - pts[-1][0]) / (2 * h), (pts[2][0] - pts[-2][0]) / (4 * h)
+    an = sum((g[name] * v[name]).sum(axis=1) for name in v)
+    scale = np.sqrt(sum((g[name] ** 2).sum(axis=1) for name in v)) * np.sqrt(sum((v[name] ** 2).sum(axis=1) for name in v))
+    err, t = np.abs(fd1 - an), np.abs(fd1 - fd2)
+    rel = lambda a: float((a[keep] / scale[keep]).max())
+    print("worst relative error", rel(err), "worst t", rel(t), "worst error beyond t", rel(np.maximum(err - t, 0.0)))
+    assert (scale[keep] > 0).all() and bool((np.abs(g["xdot_d"][keep]).sum(axis=1) > 0).all())
+    assert np.all(err[keep] <= t[keep] + 1e-5 * scale[keep])
+    assert not any(g[name][~keep].any() for name in v)
+    for key in ("stance", "swing_pos", "gait_dt", "feet"):
+        with pytest.raises(ValueError, match=f"rollout_gait_autograd: the batch carries {key}"):
+            ctl.rollout_gait_autograd(dict(dev, **{key: dev["x"]}), H, LA.DT, LA.STAND_INERTIA, LA.DT)
+    for key in ("gait_dt", "swing_state"):  # the existing refusals are untouched
+        with pytest.raises(ValueError, match=f"rollout_tick_autograd: the batch carries {key}"):
+            ctl.rollout_tick_autograd(dict(dev, **{key: dev["x"]}), H, LA.DT, LA.STAND_INERTIA)
+    ctl.close()
