@@ -463,7 +463,8 @@ int qc_certify_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_cer
  * NOT produced: the cotangents of Rwb and Rwb_d - qc_sensitivity_rot_batch below makes them from b_bar and feet_bar; weak activity -
  * a row whose multiplier is about 0 counts as active like any other (qc_certify_batch's lambda shows such rows).  The cotangents of the
  * handle's own parameters - mu, fzmin, fzmax, the weights, the gains, mass and Ib - come from qc_sensitivity_param_batch below, given
- * this call's adjoint.  Commander mode is out of scope.
+ * this call's adjoint.  Commander mode: the desired state is qc_commander_step_batch's, given here as Rwb_d / x_d / xdot_d / w_d; x_d_bar,
+ * xdot_d_bar and w_d_bar go on to qc_commander_step_adjoint_batch.
  * The reduced system is solved as a fixed 12x12 LDL^T; a pivot that is not positive and finite sets bit 1 of `flags` and makes
  * every output of that robot NaN.  Non-finite inputs propagate as NaN; nothing is clamped. */
 typedef struct qc_sensitivity_io {
@@ -503,7 +504,8 @@ int qc_sensitivity_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc
  * error angle of exactly pi the log is discontinuous for any implementation: the derivative is that of the branch evaluated.
  * As every output of qc_sensitivity_batch this is the gradient ON THE ACTIVE FACE: valid while the working set holds, one-sided for
  * robots with bit 0 of its flags, NaN for robots with bit 1 (their b_bar and feet_bar are NaN and every output here with them).
- * Non-finite inputs propagate as NaN; nothing is clamped.  Commander mode is out of scope: Rwb_d must be in `in`. */
+ * Non-finite inputs propagate as NaN; nothing is clamped.  Rwb_d must be in `in`: in commander mode it is
+ * qc_commander_step_batch's, and Rwb_d_bar goes on to qc_commander_step_adjoint_batch. */
 typedef struct qc_sensitivity_rot_io {
   size_t struct_size;        /* = sizeof(qc_sensitivity_rot_io); checked                                             */
   const double* grf_body;    /* [n][4][3] qc_batch_out.grf_body                                                      */
@@ -771,7 +773,7 @@ int qc_sensitivity_swing_batch(qc_handle* h, size_t n, const qc_batch_in* in, co
  * returned swing_pos / swing_vel and the phases it left (no gait_dt): records, phases, joint_tau, grf_body and status.
  * Of `in` it reads Rwb, x, xdot, w, xdot_d, joint_q, gait_phase and swing_state (IN/OUT) - all required - and the optional stance,
  * gait_duty and gait_dt; the other members are ignored, except that `feet` without joint_q and a swing_pos / swing_vel are refused.
- * Commander mode is out of scope.  All pointers are DEVICE pointers. */
+ * In commander mode qc_commander_step_batch comes first: its xdot_d is the one this call takes.  All pointers are DEVICE pointers. */
 typedef struct qc_swing_reference_io {
   size_t struct_size;  /* = sizeof(qc_swing_reference_io); checked                           */
   double* swing_pos;   /* [n][4][3] OUT: each optional, at least one given                    */
@@ -805,7 +807,8 @@ int qc_swing_reference_batch(qc_handle* h, size_t n, const qc_batch_in* in, cons
  * UNDEFINED GRADIENT: `flags` bit l - leg l is replanned and x_z is not finite and > 0: the LIP square root has no derivative there;
  * every output row of that robot is NaN.  Other non-finite inputs propagate; nothing is clamped.
  * NOT produced: a cotangent of the phases, of gait_dt, of the gait's periods, of swing_height, planner_k or the kinematic constants -
- * the clock and the contact mask are held, as in qc_leg_plant_step_adjoint_batch.  Commander mode is out of scope.
+ * the clock and the contact mask are held, as in qc_leg_plant_step_adjoint_batch.  In commander mode xdot_d_bar goes on to
+ * qc_commander_step_adjoint_batch.
  * Each of Rwb_bar, x_bar, xdot_bar, w_bar and joint_q_bar may be the SAME array as its `_in`, and p_start_bar / p_final_bar the same
  * arrays as p_start_next_bar / p_final_next_bar: every input of a robot is read before any of its outputs is written.  All pointers
  * are DEVICE pointers. */
@@ -838,6 +841,92 @@ void qc_default_swing_reference_adjoint(qc_swing_reference_adjoint_io* io);
  * a gait_dt, swing_pos or swing_vel in `in`, `feet` without joint_q, no cotangent given, no output requested, a missing state_before,
  * a missing Rwb, x, xdot, w, joint_q or gait_phase, or n beyond one launch. */
 int qc_swing_reference_adjoint_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_swing_reference_adjoint_io* io, void* stream);
+
+/* The commander step as a launch of its own: what qc_tick_batch does FIRST for every robot (steps 1-3 of "Commander mode" above), by
+ * the tick's own device function - the values are the tick's bit for bit.  `cmd` is qc_tick_batch's: twist, fresh, state (IN/OUT,
+ * updated in place exactly as the tick updates it), stand_height, stand_tol, cmd_dt.  Every state of the record is handled: a fresh
+ * command or none; not standing; standing but not running (gait_running is set, nothing else); running with or without a pending
+ * command.  Optionally written: the desired state the tick would feed the QP THIS tick - the record's own where no command was
+ * applied - `run` (the gait runs this tick: gait_running was set before the call and standing is set after it) and
+ * `applied` (a command was applied by this call).
+ * CONTRACT: for a batch in which every robot has standing and gait_running set, qc_tick_batch equals this call followed by
+ * qc_control_batch on the same `in` with the four returned arrays as Rwb_d / x_d / xdot_d / w_d (swing_state and gait_dt unchanged) in
+ * joint_tau, grf_body, status, phases, swing records and commander records, bit for bit.  For ANY batch the commander records after
+ * this call equal those after qc_tick_batch, bit for bit.
+ * Of `in` it reads Rwb and x only.  All pointers are DEVICE pointers. */
+typedef struct qc_commander_step_io {
+  size_t struct_size; /* = sizeof(qc_commander_step_io); checked                                   */
+  double* Rwb_d;      /* [n][9] OUT, row-major: each optional (the records are always updated)     */
+  double* x_d;        /* [n][3]                                                                    */
+  double* xdot_d;     /* [n][3]                                                                    */
+  double* w_d;        /* [n][3]                                                                    */
+  uint8_t* run;       /* [n]: 1 - the gait runs this tick                                          */
+  uint8_t* applied;   /* [n]: 1 - a command was applied by this call                               */
+} qc_commander_step_io;
+/* struct_size set, pointers NULL. */
+void qc_default_commander_step(qc_commander_step_io* io);
+/* Asynchronous on `stream`, no host synchronisation (graph-capturable); n == 0 launches nothing and returns QC_OK.  QC_ERR_INVALID
+ * (message starting with "qc_commander_step_batch:", nothing launched) for a null handle, `in`, `cmd` or `io`, a wrong struct_size of
+ * either record, a missing cmd->state, Rwb or x, `fresh` without `twist`, a stand_height, stand_tol (>= 0) or cmd_dt that is not
+ * finite, or n beyond one launch. */
+int qc_commander_step_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_command_in* cmd, const qc_commander_step_io* io, void* stream);
+
+/* The reverse pass of qc_commander_step_batch.  The forward launch saves nothing: pass the same Rwb, x (`in`), twist, fresh and the
+ * three scalars (`cmd`; cmd->state is not read) and `state_before`, a copy of the qc_commander_state records from BEFORE the forward
+ * call.  The branch decisions (fresh, standing, running, pending, applied) are recomputed from those and held.
+ * Cotangents in (a missing one counts as zero): G = Rwb_d_bar (ENTRYWISE, row-major: qc_sensitivity_rot_io's layout), a = x_d_bar,
+ * b = xdot_d_bar, c = w_d_bar - on the four arrays the forward call returns - and Vb_next_bar, on the held command AFTER the call.
+ *   command source  vb = fresh ? twist : Vb.  Its total cotangent vb_bar is Vb_next_bar (a fresh twist is stored as Vb, a held one
+ *                   stays) plus the applied terms below.  fresh: twist_bar = vb_bar, Vb_bar = 0.  held: Vb_bar = vb_bar, twist_bar = 0.
+ *   NOT applied     Rwb_d_prev_bar, x_d_prev_bar, xdot_d_prev_bar, w_d_prev_bar = G, a, b, c: the record passed through.  Nothing reaches
+ *                   Rwb_bar, x_bar (they equal their `_in`) or vb.
+ *   applied         the four _prev_bar are zero: the record was overwritten.  The forward function, with v = vb[0:3], om = vb[3:6],
+ *                   d = cmd_dt om, Rb = Exp(d), t = cmd_dt Rb v, Y = Rz(yaw), (cy, sy) = (R00, R10) / h, h = hypot(R00, R10):
+ *                     Rwb_d = Y Rb,  x_d = (x0 + (Y t)0, x1 + (Y t)1, stand_height),  xdot_d = Rwb^T (v - x x om),  w_d = Rwb^T om
+ *                   is reversed exactly: a_2 is dropped (the height is a constant), and with u = v - x x om, ub = Rwb b, tb = Y^T (a_0, a_1, 0),
+ *                   M = Y^T G + cmd_dt tb v^T, wv = axial(M Rb^T), d_bar = Jl(d)^T wv (Jl: the left Jacobian of Exp):
+ *                     v_bar = ub + cmd_dt Rb^T tb,  om_bar = Rwb c + x x ub + cmd_dt d_bar,  x_bar += ub x om + (a_0, a_1, 0),
+ *                     Rwb_bar[i][k] += u_i b_k + om_i c_k (every entry, from the two Rwb^T products), and entries 0 and 3 get the yaw
+ *                     normalisation: with cy_bar, sy_bar the cotangents of (cy, sy) from Y t and Y Rb and q = cy_bar sy - sy_bar cy,
+ *                     Rwb_bar[0] += sy q / h,  Rwb_bar[3] -= cy q / h.
+ *   small angle     |d| < 1e-12, where the forward pass takes Rb = I and t = cmd_dt v: the SMOOTH function is differentiated - Exp and Jl
+ *                   by their own formulas down to d = 0, where delta Rb = [delta d]x, delta t = cmd_dt [delta d]x v (d_bar = wv) - not
+ *                   the branch as written, whose derivative in om is zero: a twist with zero angular rate is where an optimisation
+ *                   starts, and a yaw-rate command must not get a silently zero gradient there (qc_sensitivity_rot_batch's
+ *                   "smooth limit at zero error").
+ * Rwb_bar and x_bar are added on top of Rwb_bar_in / x_bar_in (a missing one counts as zero).
+ * UNDEFINED GRADIENT: `flags` bit 0 - a command is applied at the gimbal-lock branch (h == 0, or h not finite and below 1e300, where
+ * the forward pass takes yaw 0); every output row of that robot is NaN.  Other non-finite inputs propagate; nothing is clamped.
+ * NOT produced: cotangents of stand_height, stand_tol, cmd_dt; the flags and latches are held.
+ * Each of Rwb_bar, x_bar may be the SAME array as its `_in`; Vb_bar the same as Vb_next_bar; the four _prev_bar the same as the four
+ * desired-state cotangents: every input of a robot is read before any of its outputs is written.  All pointers are DEVICE pointers. */
+typedef struct qc_commander_step_adjoint_io {
+  size_t struct_size;                             /* = sizeof(qc_commander_step_adjoint_io); checked                 */
+  const struct qc_commander_state* state_before;  /* [n] the records before the forward call; required               */
+  const double* Rwb_d_bar;                        /* [n][9] cotangents: each optional, at least one given            */
+  const double* x_d_bar;                          /* [n][3]                                                          */
+  const double* xdot_d_bar;                       /* [n][3]                                                          */
+  const double* w_d_bar;                          /* [n][3]                                                          */
+  const double* Vb_next_bar;                      /* [n][6] on the held command after the call                       */
+  const double* Rwb_bar_in;                       /* [n][9] added to the output of that name; each optional          */
+  const double* x_bar_in;                         /* [n][3]                                                          */
+  double* twist_bar;                              /* [n][6] OUT: each optional, at least one given (flags counts)    */
+  double* Vb_bar;                                 /* [n][6] on the held command before the call                      */
+  double* Rwb_bar;                                /* [n][9]                                                          */
+  double* x_bar;                                  /* [n][3]                                                          */
+  double* Rwb_d_prev_bar;                         /* [n][9] on the record's desired state before the call            */
+  double* x_d_prev_bar;                           /* [n][3]                                                          */
+  double* xdot_d_prev_bar;                        /* [n][3]                                                          */
+  double* w_d_prev_bar;                           /* [n][3]                                                          */
+  int32_t* flags;                                 /* [n]: bit 0 - applied at gimbal lock, no gradient                */
+} qc_commander_step_adjoint_io;
+/* struct_size set, pointers NULL. */
+void qc_default_commander_step_adjoint(qc_commander_step_adjoint_io* io);
+/* Asynchronous on `stream`, no host synchronisation (graph-capturable); n == 0 launches nothing and returns QC_OK.  QC_ERR_INVALID
+ * (message starting with "qc_commander_step_adjoint_batch:", nothing launched) for a null handle, `in`, `cmd` or `io`, a wrong
+ * struct_size of either record, no cotangent given, no output requested, a missing state_before, Rwb or x, `fresh` without `twist`,
+ * a stand_height, stand_tol (>= 0) or cmd_dt that is not finite, or n beyond one launch. */
+int qc_commander_step_adjoint_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_command_in* cmd, const qc_commander_step_adjoint_io* io, void* stream);
 
 #ifdef __cplusplus
 }

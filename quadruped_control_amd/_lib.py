@@ -130,6 +130,16 @@ class QcSwingReferenceAdjointIo(C.Structure):
                  "flags")]
 
 
+class QcCommanderStepIo(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t)] + [(k, C.c_void_p) for k in ("Rwb_d", "x_d", "xdot_d", "w_d", "run", "applied")]
+
+
+class QcCommanderStepAdjointIo(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t)] + [(k, C.c_void_p) for k in
+                ("state_before", "Rwb_d_bar", "x_d_bar", "xdot_d_bar", "w_d_bar", "Vb_next_bar", "Rwb_bar_in", "x_bar_in", "twist_bar", "Vb_bar",
+                 "Rwb_bar", "x_bar", "Rwb_d_prev_bar", "x_d_prev_bar", "xdot_d_prev_bar", "w_d_prev_bar", "flags")]
+
+
 PARAM_COUNT = 211  # QC_PARAM_COUNT: the doubles of QcParams, in its order
 
 
@@ -146,7 +156,8 @@ EXPORTS = ("qc_create_abi", "qc_destroy", "qc_control_batch", "qc_control_batch_
            "qc_default_sensitivity_rot", "qc_sensitivity_rot_batch", "qc_default_plant_adjoint", "qc_plant_step_adjoint_batch",
            "qc_default_sensitivity_param", "qc_sensitivity_param_batch", "qc_default_sensitivity_kin", "qc_sensitivity_kin_batch",
            "qc_default_leg_plant_adjoint", "qc_leg_plant_step_adjoint_batch", "qc_default_sensitivity_swing", "qc_sensitivity_swing_batch",
-           "qc_default_swing_reference", "qc_swing_reference_batch", "qc_default_swing_reference_adjoint", "qc_swing_reference_adjoint_batch")
+           "qc_default_swing_reference", "qc_swing_reference_batch", "qc_default_swing_reference_adjoint", "qc_swing_reference_adjoint_batch",
+           "qc_default_commander_step", "qc_commander_step_batch", "qc_default_commander_step_adjoint", "qc_commander_step_adjoint_batch")
 
 _lib = None
 
@@ -261,6 +272,15 @@ def load():
     lib.qc_default_swing_reference_adjoint.restype = None
     lib.qc_swing_reference_adjoint_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcBatchIn), C.POINTER(QcSwingReferenceAdjointIo), C.c_void_p]
     lib.qc_swing_reference_adjoint_batch.restype = C.c_int
+    lib.qc_default_commander_step.argtypes = [C.POINTER(QcCommanderStepIo)]
+    lib.qc_default_commander_step.restype = None
+    lib.qc_commander_step_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcBatchIn), C.POINTER(QcCommandIn), C.POINTER(QcCommanderStepIo), C.c_void_p]
+    lib.qc_commander_step_batch.restype = C.c_int
+    lib.qc_default_commander_step_adjoint.argtypes = [C.POINTER(QcCommanderStepAdjointIo)]
+    lib.qc_default_commander_step_adjoint.restype = None
+    lib.qc_commander_step_adjoint_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcBatchIn), C.POINTER(QcCommandIn), C.POINTER(QcCommanderStepAdjointIo),
+                                                    C.c_void_p]
+    lib.qc_commander_step_adjoint_batch.restype = C.c_int
     # the structures above are hand-written mirrors of the header: a library built from another revision is refused here,
     # before any of them crosses the boundary
     rc = lib.qc_check_abi(ABI_VERSION, C.sizeof(QcParams), C.sizeof(QcBatchIn), C.sizeof(QcBatchOut))

@@ -478,6 +478,155 @@ def rollout_gait_autograd(ctl, batch, steps, dt, leg_inertia, gait_dt, act_tol=1
     return {k: cur[k] for k in names}, out
 
 
+# ------------------------------------------------------------------ commander mode: the commander step and a rollout with a gradient in the command
+COMMANDER_STEP_DIFFERENTIABLE = ("Rwb", "x", "twist", "Vb", "Rwb_d", "x_d", "xdot_d", "w_d")
+# the reverse pass's output for each of them, and the forward call's outputs a cotangent may arrive on
+_COMMANDER_STEP_BARS = ("Rwb_bar", "x_bar", "twist_bar", "Vb_bar", "Rwb_d_prev_bar", "x_d_prev_bar", "xdot_d_prev_bar", "w_d_prev_bar")
+_COMMANDER_RECORD_DOUBLES = 26  # qc_commander_state as doubles: 2 hold the four int32 words, then Vb [6], Rwb_d [9], x_d, xdot_d, w_d [3]
+_COMMANDER_RECORD_COLUMNS = {"Vb": (2, 8), "Rwb_d": (8, 17), "x_d": (17, 20), "xdot_d": (20, 23), "w_d": (23, 26)}
+
+
+def _commander_columns(record):
+    """the Vb / Rwb_d / x_d / xdot_d / w_d columns of a commander-state tensor, as float64 views into it"""
+    d = record.view(torch.float64).view(-1, _COMMANDER_RECORD_DOUBLES)
+    return {k: d[:, a:b] for k, (a, b) in _COMMANDER_RECORD_COLUMNS.items()}
+
+
+class _CommanderStep(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ctl, command, state, *tensors):
+        given = dict(zip(COMMANDER_STEP_DIFFERENTIABLE, tensors))
+        before = state.clone()
+        for k, col in _commander_columns(before).items():
+            col.copy_(given[k].reshape(col.shape))
+        after = before.clone()
+        cmd = dict(command, state=after, twist=given["twist"])
+        res = ctl.commander_step_batch({"Rwb": given["Rwb"], "x": given["x"]}, cmd, want=("Rwb_d", "x_d", "xdot_d", "w_d", "run", "applied"))
+        ctx.ctl, ctx.command = ctl, command
+        ctx.set_materialize_grads(False)  # an output the loss never reached arrives as None: a NULL cotangent, not an array of zeros
+        ctx.save_for_backward(before, *[t for t in tensors if t is not None])
+        ctx.present = [t is not None for t in tensors]
+        ctx.mark_non_differentiable(after, res["run"], res["applied"])
+        return res["Rwb_d"], res["x_d"], res["xdot_d"], res["w_d"], _commander_columns(after)["Vb"].clone(), after, res["run"], res["applied"]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, Rd_bar, xd_bar, xdd_bar, wd_bar, vb_bar, _state_bar, _run_bar, _applied_bar):
+        before, *saved = ctx.saved_tensors
+        names = COMMANDER_STEP_DIFFERENTIABLE
+        saved = iter(saved)
+        inputs = {k: (next(saved) if there else None) for k, there in zip(names, ctx.present)}
+        need = dict(zip(names, ctx.needs_input_grad[3:]))
+        cot = {k: b.contiguous() for k, b in (("Rwb_d", Rd_bar), ("x_d", xd_bar), ("xdot_d", xdd_bar), ("w_d", wd_bar), ("Vb", vb_bar)) if b is not None}
+        want = tuple(bar for k, bar in zip(names, _COMMANDER_STEP_BARS) if need[k])
+        if not cot or not want:  # no output reached the loss: every gradient is zero
+            return (None, None, None, *[torch.zeros_like(inputs[k]) if need[k] else None for k in names])
+        cmd = dict(ctx.command, twist=inputs["twist"])
+        s = ctx.ctl.commander_step_adjoint_batch({"Rwb": inputs["Rwb"], "x": inputs["x"]}, cmd, before, cot, want=want)
+        return (None, None, None, *[s[bar].view_as(inputs[k]) if need[k] else None for k, bar in zip(names, _COMMANDER_STEP_BARS)])
+
+
+def commander_step_autograd(ctl, batch, command, desired, Vb):
+    """BalanceController.commander_step_autograd (see there): (Rwb_d, x_d, xdot_d, w_d, Vb', state', run, applied) of
+    commander_step_batch() on a copy of command["state"] whose held command is `Vb` and whose desired state is `desired`,
+    differentiable in COMMANDER_STEP_DIFFERENTIABLE."""
+    missing = [k for k in ("Rwb", "x") if batch.get(k) is None]
+    if missing:
+        raise ValueError(f"commander_step_autograd: the batch lacks {missing}")
+    if command.get("state") is None:
+        raise ValueError("commander_step_autograd: command['state'] is required (new_commander_states)")
+    n = batch["x"].shape[0]
+    if len(desired) != 4:
+        raise ValueError("commander_step_autograd: desired is the tuple (Rwb_d, x_d, xdot_d, w_d)")
+    for name, t, k in (("Vb", Vb, 6), ("Rwb_d", desired[0], 9), ("x_d", desired[1], 3), ("xdot_d", desired[2], 3), ("w_d", desired[3], 3)):
+        if t is None or t.dtype != torch.float64 or t.numel() != k * n:
+            raise ValueError(f"commander_step_autograd: {name} is a float64 [n,{k}] tensor")
+    twist = command.get("twist")
+    if twist is not None and not twist.is_contiguous():
+        twist = twist.contiguous()
+    rest = {k: (v.detach() if isinstance(v, torch.Tensor) else v) for k, v in command.items() if k not in ("state", "twist")}
+    return _CommanderStep.apply(ctl, rest, command["state"].detach(), batch["Rwb"], batch["x"], twist, Vb, *desired)
+
+
+def rollout_commander_autograd(ctl, batch, command, steps, dt, leg_inertia, gait_dt, act_tol=1e-7, warm=True, params=None, joint_gains=None):
+    """BalanceController.rollout_commander_autograd (see there): `steps` times commander_step_autograd(), swing_reference_autograd()
+    with the commander's xdot_d and the clock advancing, tick_autograd() on the commander's desired state, leg_plant_step_autograd();
+    the held command, the records' desired state and the swing record threaded through."""
+    who = "rollout_commander_autograd"
+    for k, why in _ROLLOUT_GAIT_REFUSED.items():
+        if batch.get(k) is not None:
+            raise ValueError(f"{who}: the batch carries {k} - {why}")
+    for k in ("Rwb_d", "x_d", "xdot_d", "w_d"):
+        if batch.get(k) is not None:
+            raise ValueError(f"{who}: the batch carries {k} - in commander mode the desired state lives in command['state']")
+    missing = [k for k in ("joint_q", "joint_qdot", "gait_phase", "swing_state") if batch.get(k) is None]
+    if missing:
+        raise ValueError(f"{who}: the batch lacks {missing}")
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError(f"{who}: steps must be >= 0")
+    if command.get("state") is None:
+        raise ValueError(f"{who}: command['state'] is required (new_commander_states)")
+    names = LEG_PLANT_DIFFERENTIABLE[:-1]
+    n, dev = batch["x"].shape[0], batch["x"].device
+    cstate = command["state"].detach()
+    # standing and gait_running are latched and never reset: read ONCE, here (the rollout's one host synchronisation)
+    latched = cstate.view(torch.int32).view(n, -1)[:, :2].ne(0).all(dim=0).tolist()
+    if not all(latched):
+        raise ValueError(f"{who}: every robot must have standing and gait_running set (not all have {'standing' if not latched[0] else 'gait_running'}): "
+                         "until then the commander ignores the twist - the gradient is identically zero - and rollout_tick() runs the stand-up")
+    twist, fresh = command.get("twist"), command.get("fresh")
+    sequence = twist is not None and twist.dim() == 3
+    if sequence and (twist.shape[0] != steps or (fresh is not None and (fresh.dim() != 2 or fresh.shape[0] != steps))):
+        raise ValueError(f"{who}: a command sequence is twist [steps,n,6] with an optional fresh [steps,n]")
+    if sequence and fresh is None:
+        fresh = torch.ones((steps, n), dtype=torch.uint8, device=dev)
+    scalars = {k: command[k] for k in ("stand_height", "stand_tol", "cmd_dt") if command.get(k) is not None}
+    if isinstance(gait_dt, torch.Tensor):
+        clock = gait_dt.detach().to(dtype=torch.float64, device=dev).contiguous()
+    else:
+        clock = torch.full((n,), float(gait_dt), dtype=torch.float64, device=dev)
+    cur = {k: v for k, v in batch.items() if k not in ("swing_state", "gait_phase")}
+    duty = batch.get("gait_duty")
+    record, phase = batch["swing_state"].detach(), batch["gait_phase"].detach()
+    p_start, p_final = (t.clone() for t in _record_points(record))
+    held = {k: t.clone() for k, t in _commander_columns(cstate).items()}
+    Vb, desired = held["Vb"], (held["Rwb_d"], held["x_d"], held["xdot_d"], held["w_d"])
+    out, active, planned, applied = {}, None, None, None
+    flags = torch.zeros((n,), dtype=torch.int32, device=dev) if steps else None
+    for k in range(steps):
+        if sequence:
+            cmd = dict(scalars, state=cstate, twist=twist[k], fresh=fresh[k])
+        elif k == 0 and fresh is not None:  # rollout_tick's rule: `fresh` holds on step 0 only
+            cmd = dict(scalars, state=cstate, twist=twist, fresh=fresh)
+        else:
+            cmd = dict(scalars, state=cstate)
+        *desired, Vb, cstate, _run, applied = commander_step_autograd(ctl, cur, cmd, desired, Vb)
+        phase = phase.clone()  # this step's own phases: advanced in place by the references' clock, then read by the tick and the plant
+        ref_in = dict({name: cur[name] for name in SWING_REFERENCE_DIFFERENTIABLE[:-2] if name != "xdot_d"}, xdot_d=desired[2], gait_phase=phase, gait_dt=clock)
+        if duty is not None:
+            ref_in["gait_duty"] = duty
+        pos, vel, p_start, p_final, record, planned = swing_reference_autograd(ctl, ref_in, record, p_start, p_final)
+        res = {"grf_body": torch.zeros((n, 12), dtype=torch.float64, device=dev), "status": torch.full((n,), -1, dtype=torch.int32, device=dev),
+               "joint_tau": torch.zeros((n, 12), dtype=torch.float64, device=dev)}
+        kwargs = dict(out=res)
+        if warm:  # this step's own working-set word; the next solve starts from it (detached: an int32)
+            res["active_set"] = torch.zeros((n,), dtype=torch.int32, device=dev)
+            kwargs.update(warm=active, want_active_set=True)
+            active = res["active_set"]
+        tick_in = dict(cur, gait_phase=phase, swing_pos=pos, swing_vel=vel, Rwb_d=desired[0], x_d=desired[1], xdot_d=desired[2], w_d=desired[3])
+        tau, grf, status = tick_autograd(ctl, tick_in, act_tol, params=params, joint_gains=joint_gains, **kwargs)
+        new = leg_plant_step_autograd(ctl, cur, tau, dt, leg_inertia, gait_phase=phase, gait_duty=duty, flags=flags)
+        cur = dict(cur, **dict(zip(names, new)))
+        out = {"joint_tau": tau, "grf_body": grf, "status": status, "flags": flags}
+    if warm and active is not None:
+        out["active_set"] = active
+    out.update(gait_phase=phase, swing_state=record, p_start=p_start, p_final=p_final, cmd_state=cstate)
+    if planned is not None:
+        out.update(planned=planned, applied=applied)
+    return {k: cur[k] for k in names}, out
+
+
 _ROLLOUT_TICK_REFUSED = {"gait_dt": "the gait clock writes gait_phase in place; the contact mask is held over the rollout",
                          "swing_state": "the planner's references are out of scope (swing_pos and swing_vel are held over the rollout)",
                          "feet": "the tick reads joint_q (rollout_autograd() steps the bare rigid body on `feet`)"}

@@ -30,6 +30,7 @@ _IN_FIELDS = (("Rwb", 9), ("Rwb_d", 9), ("x", 3), ("xdot", 3), ("w", 3), ("x_d",
 
 _SENSITIVITY_SWING_WANT = ("swing_pos_bar", "swing_vel_bar", "joint_q_bar", "joint_qdot_bar", "Rwb_bar", "x_bar")  # sensitivity_swing_batch's default
 _SWING_REFERENCE_ADJOINT_WANT = ("Rwb_bar", "x_bar", "xdot_bar", "w_bar", "xdot_d_bar", "joint_q_bar", "p_start_bar", "p_final_bar")  # swing_reference_adjoint_batch's default
+_COMMANDER_STEP_ADJOINT_WANT = ("twist_bar", "Vb_bar", "Rwb_bar", "x_bar", "Rwb_d_prev_bar", "x_d_prev_bar", "xdot_d_prev_bar", "w_d_prev_bar")  # commander_step_adjoint_batch's default
 _LEG_PLANT_ADJOINT_WANT = ("Rwb_bar", "x_bar", "xdot_bar", "w_bar", "joint_q_bar", "joint_qdot_bar", "joint_tau_bar")  # leg_plant_step_adjoint's default
 
 
@@ -375,17 +376,20 @@ class BalanceController:
         return self._launcher("qc_control_batch", args, (batch, warm, out, bi, bo)), out
 
     # --------------------------------------------------------- commander mode
-    def _marshal_command(self, n, command):
+    def _marshal_command(self, n, command, need_state=True):
         import torch
 
         dev = torch.device("cuda", self.device)
         c = _lib.QcCommandIn()
         self._lib.qc_default_command(C.byref(c))
         st = command.get("state")
-        if st is None or st.dtype != torch.uint8 or not st.is_contiguous() or st.numel() != n * COMMANDER_STATE_DTYPE.itemsize or st.device != dev:
+        if not need_state:  # (commander_step_adjoint: the records it reads are its state_before)
+            pass
+        elif st is None or st.dtype != torch.uint8 or not st.is_contiguous() or st.numel() != n * COMMANDER_STATE_DTYPE.itemsize or st.device != dev:
             raise ValueError(f"command['state']: need a contiguous uint8 tensor of n * {COMMANDER_STATE_DTYPE.itemsize} bytes on {dev} "
                              "(new_commander_states)")
-        c.state = st.data_ptr()
+        else:
+            c.state = st.data_ptr()
         fresh, twist = command.get("fresh"), command.get("twist")
         if _check_tensor("command['fresh']", fresh, n, None, torch.uint8, dev, False, "uint8"):
             if twist is None:
@@ -1087,6 +1091,103 @@ class BalanceController:
 
         return rollout_gait_autograd(self, batch, steps, dt, leg_inertia, gait_dt, act_tol, warm, params, joint_gains)
 
+    # ------------------------------------------- the commander step as a launch of its own, and its reverse pass
+    def plan_commander_step(self, batch, command, want=_DESIRED, out=None, stream=None):
+        """commander_step_batch() marshalled once: returns (launch, out), `launch()` being one qc_commander_step_batch call
+        (graph-capturable) on tensors that are read and updated in place.  Planning launches nothing.  `out`: a dict of tensors to
+        write into instead of new ones (every name in `want`).  A call the library refuses raises ValueError with its message, from
+        launch()."""
+        io = _lib.QcCommanderStepIo()
+        self._lib.qc_default_commander_step(C.byref(io))
+        n, dev, bi = self._readonly_batch("commander_step", batch, _COMMANDER_STEP_FIELDS, io, [])
+        c = self._marshal_command(n, command)
+        res = _outputs("commander_step", _COMMANDER_STEP_OUTPUTS, want, out, n, dev, io)
+        args = (n, C.byref(bi), C.byref(c), C.byref(io), self._stream_ptr(stream))
+        return self._launcher("qc_commander_step_batch", args, (batch, command, res, bi, c, io), ValueError), res
+
+    def commander_step_batch(self, batch, command, want=_DESIRED, out=None, stream=None):
+        """The commander step of the tick as a launch of its own (qc_commander_step_batch, include/qc_balance.h; INTEGRATION.md
+        "Commander mode"): what tick_batch() does first.  `batch`: Rwb and x are all that is read of it.  `command`: tick_batch()'s dict;
+        its records are updated IN PLACE exactly as tick_batch() updates them.  `want`: any of "Rwb_d" [n,9], "x_d", "xdot_d", "w_d"
+        [n,3] - the desired state the tick feeds the QP this tick, the record's own where no command was applied - and "run", "applied"
+        uint8 [n].  For robots that stand and run, control_batch() on those four and the batch's swing_state / gait_dt gives the
+        tick's outputs and records bit for bit.  Asynchronous on `stream`, no synchronisation.  Returns the dict of device tensors;
+        ValueError with the library's message for a call it refuses."""
+        launch, res = self.plan_commander_step(batch, command, want, out, stream)
+        launch()
+        return res
+
+    def plan_commander_step_adjoint(self, batch, command, state_before, cotangents, want=_COMMANDER_STEP_ADJOINT_WANT, out=None, Rwb_bar_in=None,
+                                    x_bar_in=None, stream=None):
+        """commander_step_adjoint_batch() marshalled once: returns (launch, out), `launch()` being one qc_commander_step_adjoint_batch
+        call (graph-capturable) on tensors that are read in place.  Planning launches nothing.  `out`: a dict of tensors to write into
+        instead of new ones (every name in `want`) - an output may be its `_in` tensor, out["Vb_bar"] may be cotangents["Vb"], and the
+        four `_prev_bar` may be the four desired-state cotangents.  A call the library refuses raises ValueError with its message, from
+        launch()."""
+        import torch
+
+        io = _lib.QcCommanderStepAdjointIo()
+        self._lib.qc_default_commander_step_adjoint(C.byref(io))
+        unknown = [k for k in cotangents if k not in _COMMANDER_STEP_COTANGENTS]
+        if unknown:
+            raise ValueError(f"commander_step_adjoint: unknown cotangent(s) {unknown}; the call's outputs are {tuple(_COMMANDER_STEP_COTANGENTS)}")
+        own = [_COMMANDER_STEP_COTANGENTS[k][:1] + (t,) + _COMMANDER_STEP_COTANGENTS[k][1:] for k, t in cotangents.items()]
+        own += [("Rwb_bar_in", Rwb_bar_in, 9), ("x_bar_in", x_bar_in, 3)]
+        n, dev, bi = self._readonly_batch("commander_step_adjoint", batch, _COMMANDER_STEP_FIELDS, io, own)
+        c = self._marshal_command(n, command, need_state=False)
+        if _check_tensor("state_before", state_before, n, COMMANDER_STATE_DTYPE.itemsize, torch.uint8, dev, False,
+                         msg=f"state_before: need a contiguous uint8 tensor of n * {COMMANDER_STATE_DTYPE.itemsize} bytes on the device"):
+            io.state_before = state_before.data_ptr()
+        res = _outputs("commander_step_adjoint", _COMMANDER_STEP_ADJOINT_OUTPUTS, want, out, n, dev, io)
+        args = (n, C.byref(bi), C.byref(c), C.byref(io), self._stream_ptr(stream))
+        keep = (batch, command, state_before, cotangents, Rwb_bar_in, x_bar_in, res, bi, c, io)
+        return self._launcher("qc_commander_step_adjoint_batch", args, keep, ValueError), res
+
+    def commander_step_adjoint_batch(self, batch, command, state_before, cotangents, want=_COMMANDER_STEP_ADJOINT_WANT, out=None, Rwb_bar_in=None,
+                                     x_bar_in=None, stream=None):
+        """The reverse pass of commander_step_batch() (qc_commander_step_adjoint_batch, include/qc_balance.h).  `batch`: Rwb and x as
+        the forward call read them.  `command`: its twist, fresh and scalars (its records are not read).  `state_before`: a copy of the
+        record tensor from BEFORE the forward call.  `cotangents`: a dict with any of "Rwb_d" [n,9] (entrywise, row-major), "x_d",
+        "xdot_d", "w_d" [n,3] and "Vb" [n,6] (on the held command after the call); a missing one is zero, at least one given.  `want`:
+        any of "twist_bar", "Vb_bar" [n,6], "Rwb_bar" [n,9], "x_bar" [n,3], "Rwb_d_prev_bar" [n,9], "x_d_prev_bar", "xdot_d_prev_bar",
+        "w_d_prev_bar" [n,3] (on the record's desired state before the call) and "flags" int32 [n].  `Rwb_bar_in`, `x_bar_in`: added to
+        the outputs of those names.  Where a command was applied with zero angular rate the smooth limit of the rotation's derivative is
+        used, so twist_bar[3:6] is not silently zero there.  flags bit 0: a command applied at gimbal lock (R00 = R10 = 0) - NaN in every
+        row of the robot.  The latches and branch decisions are held.  Asynchronous on `stream`, no synchronisation.  Returns the dict
+        of device tensors; ValueError with the library's message for a call it refuses."""
+        launch, res = self.plan_commander_step_adjoint(batch, command, state_before, cotangents, want, out, Rwb_bar_in, x_bar_in, stream)
+        launch()
+        return res
+
+    def commander_step_autograd(self, batch, command, desired, Vb):
+        """commander_step_batch() with a gradient, OUT OF PLACE in the records: returns (Rwb_d, x_d, xdot_d, w_d, Vb', state', run,
+        applied) - the desired state this tick, the held command [n,6] and the record tensor AFTER the call, and the two flag bytes -,
+        differentiable in Rwb and x of `batch`, in command["twist"], in `Vb` [n,6], the held command BEFORE the call, and in `desired`, the
+        tuple (Rwb_d, x_d, xdot_d, w_d) BEFORE the call (they take the place of the records' own values; the flags of the records are
+        carried undifferentiated).  command["state"] is left as it is.  Backward is one commander_step_adjoint_batch() call on the
+        current stream, without host synchronisation; an output the loss never reached is a missing cotangent.  The latches and branch
+        decisions are held; a robot whose command is applied at gimbal lock gets NaN gradients.  There is no double backward."""
+        from .autograd import commander_step_autograd
+
+        return commander_step_autograd(self, batch, command, desired, Vb)
+
+    def rollout_commander_autograd(self, batch, command, steps, dt, leg_inertia, gait_dt, act_tol=1e-7, warm=True, params=None, joint_gains=None):
+        """The functional twin of rollout_tick(batch, command, ...) - commander mode - for robots that stand and run: per step
+        commander_step_autograd(), swing_reference_autograd() with the commander's xdot_d and the clock advancing by `gait_dt`,
+        tick_autograd() on the commander's desired state, the references and the phases, leg_plant_step_autograd().  The held command,
+        the records' desired state and the swing record are threaded from step to step, so a loss on the rollout has a gradient in
+        command["twist"]: [n,6] with command["fresh"] [n] applied on step 0 only (rollout_tick's rule; with gait_dt = dt the forward
+        values are rollout_tick(batch, command, ...)'s bit for bit), or a command SEQUENCE [steps,n,6] with an optional fresh
+        [steps,n] (default all ones).  `batch` and command["state"] are not modified.  standing and gait_running are latched and never
+        reset, so the two flags are read ONCE at entry - one host synchronisation - and ValueError is raised unless every robot has
+        both set: before that the commander ignores the twist and the gradient is identically zero (the all-stance and held-clock rules
+        of a robot that does not run yet stay with rollout_tick).  ValueError also for what rollout_gait_autograd() refuses and for
+        Rwb_d / x_d / xdot_d / w_d in the batch.  Returns (state, out) as rollout_gait_autograd() does, plus out["cmd_state"], the final
+        records, and out["applied"]."""
+        from .autograd import rollout_commander_autograd
+
+        return rollout_commander_autograd(self, batch, command, steps, dt, leg_inertia, gait_dt, act_tol, warm, params, joint_gains)
+
     def tick_autograd(self, batch, act_tol=1e-7, flags=None, params=None, joint_gains=None, **control_kwargs):
         """The tick with swing references, with a gradient: returns (joint_tau, grf_body, status) of control_batch(batch,
         want_torques=True, **control_kwargs) for a batch that carries joint_q, joint_qdot, swing_pos, swing_vel and a contact mask
@@ -1255,6 +1356,16 @@ _SWING_REFERENCE_ADJOINT_OUTPUTS = {"Rwb_bar": ((9,), "float64"), **{k: ((3,), "
                                     "flags": ((), "int32")}
 # the forward call's outputs a cotangent may be given on -> the io field
 _SWING_REFERENCE_COTANGENTS = {"swing_pos": "swing_pos_bar", "swing_vel": "swing_vel_bar", "p_start": "p_start_next_bar", "p_final": "p_final_next_bar"}
+
+
+# commander_step / commander_step_adjoint: what the two calls read of the batch
+_COMMANDER_STEP_FIELDS = (("Rwb", 9, "float64"), ("x", 3, "float64"))
+_COMMANDER_STEP_OUTPUTS = {"Rwb_d": ((9,), "float64"), **{k: ((3,), "float64") for k in ("x_d", "xdot_d", "w_d")}, "run": ((), "uint8"), "applied": ((), "uint8")}
+_COMMANDER_STEP_ADJOINT_OUTPUTS = {"twist_bar": ((6,), "float64"), "Vb_bar": ((6,), "float64"), "Rwb_bar": ((9,), "float64"), "x_bar": ((3,), "float64"),
+                                   "Rwb_d_prev_bar": ((9,), "float64"), **{k: ((3,), "float64") for k in ("x_d_prev_bar", "xdot_d_prev_bar", "w_d_prev_bar")},
+                                   "flags": ((), "int32")}
+# the forward call's outputs a cotangent may be given on -> (the io field, its trailing size)
+_COMMANDER_STEP_COTANGENTS = {"Rwb_d": ("Rwb_d_bar", 9), "x_d": ("x_d_bar", 3), "xdot_d": ("xdot_d_bar", 3), "w_d": ("w_d_bar", 3), "Vb": ("Vb_next_bar", 6)}
 
 
 # a parameter cotangent: name -> (slice of the 211 values, shape), in the order of the double members of qc_params

@@ -525,99 +525,6 @@ QC_DEV uint32_t swing_plan(CParams& P, const BatchIn& in, long robot, int foot0,
   return has_bits;
 }
 
-// Commander mode (qc_tick_batch): one step of the reference's commander loop (commander_node.cpp:372-478) for this robot, run
-// where the robot is assembled - once per robot per launch (the hand-over paths re-read records, not inputs, and do not come
-// here).  Replaces the desired state in `S` when a held command is applied and returns whether the gait runs this tick (gait
-// clock, contact rule, planner).  Every member of a lane group computes the same values; member 0 stores what changed.
-QC_DEV bool commander_step(const BatchIn& in, long robot, int member, RawState& S, const TickExtra& X) {
-  int standing = X.flags[0], running = X.flags[1], pending = X.flags[2];
-  const bool fresh = X.fresh != 0;
-  double vb[6];
-#pragma unroll
-  for (int k = 0; k < 6; k++) vb[k] = fresh ? X.tw[k] : X.vb[k];  // cmdCallback, :191-202: the latest command wins
-  if (fresh) pending = 1;
-  if (!standing && fabs(S.x[2] - in.stand_height) < in.stand_tol) standing = 1;  // :386-391, almost_equal (strict)
-  bool run = false, applied = false;
-  if (standing) {
-    if (running) {
-      if (pending) {  // :397-428
-        // integrate_twist_yaw (trajectory.cpp:29-69): Rbb' from the angle-axis increment, the translation rotated by it
-        const double dt = in.cmd_dt;
-        const double d[3] = {vb[3] * dt, vb[4] * dt, vb[5] * dt};
-        const double th = __builtin_sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-        double Rb[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
-        double t[3];
-        if (fabs(th) < 1.0e-12) {  // almost_equal(angle, 0.0)
-#pragma unroll
-          for (int k = 0; k < 3; k++) t[k] = vb[k] * dt;
-        } else {
-          const double a[3] = {d[0] / th, d[1] / th, d[2] / th};
-          double s, c;
-          sincos_joint(th, &s, &c);
-          const double oc = 1.0 - c;
-#pragma unroll
-          for (int i = 0; i < 3; i++)
-#pragma unroll
-            for (int j = 0; j < 3; j++) Rb[3 * i + j] = oc * a[i] * a[j] + (i == j ? c : 0.0);
-          Rb[1] -= s * a[2]; Rb[3] += s * a[2];
-          Rb[2] += s * a[1]; Rb[6] -= s * a[1];
-          Rb[5] -= s * a[0]; Rb[7] += s * a[0];
-#pragma unroll
-          for (int i = 0; i < 3; i++) t[i] = (Rb[3 * i] * vb[0] + Rb[3 * i + 1] * vb[1] + Rb[3 * i + 2] * vb[2]) * dt;
-        }
-        // Rz(yaw of Rwb) without atan2 / sincos: yaw = atan2(R10, R00) away from pitch = +-pi/2.  At gimbal lock (h == 0, or a
-        // non-finite h) yaw 0 is taken: Drake's branch there is not pinned.
-        const double h = __builtin_sqrt(S.R[0] * S.R[0] + S.R[3] * S.R[3]);
-        const bool ok = h > 0.0 && h < 1.0e300;
-        const double cy = ok ? S.R[0] / h : 1.0, sy = ok ? S.R[3] / h : 0.0;
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-          S.Rd[j] = cy * Rb[j] - sy * Rb[3 + j];
-          S.Rd[3 + j] = sy * Rb[j] + cy * Rb[3 + j];
-          S.Rd[6 + j] = Rb[6 + j];
-        }
-        S.xd[0] = S.x[0] + (cy * t[0] - sy * t[1]);
-        S.xd[1] = S.x[1] + (sy * t[0] + cy * t[1]);
-        S.xd[2] = in.stand_height;  // "TODO: height drifts", :409
-        // Ad_T of the CURRENT pose (rigid3d.cpp:259-271): [R^T, -R^T [x]x; 0, R^T] Vb
-        const double u[3] = {vb[0] - (S.x[1] * vb[5] - S.x[2] * vb[4]), vb[1] - (S.x[2] * vb[3] - S.x[0] * vb[5]),
-                             vb[2] - (S.x[0] * vb[4] - S.x[1] * vb[3])};
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-          S.xdotd[k] = S.R[k] * u[0] + S.R[3 + k] * u[1] + S.R[6 + k] * u[2];
-          S.wd[k] = S.R[k] * vb[3] + S.R[3 + k] * vb[4] + S.R[6 + k] * vb[5];
-        }
-        pending = 0;
-        applied = true;
-      }
-      run = true;
-    } else {
-      running = 1;  // gait_scheduler.start(), :474-478: the first schedule() is next tick
-    }
-  }
-  if (member == 0) {
-    CmdState* C = in.cmd_state + robot;
-    if (standing != X.flags[0]) C->standing = standing;
-    if (running != X.flags[1]) C->gait_running = running;
-    if (pending != X.flags[2]) C->cmd_pending = pending;
-    if (fresh) {
-#pragma unroll
-      for (int k = 0; k < 6; k++) C->Vb[k] = vb[k];
-    }
-    if (applied) {
-#pragma unroll
-      for (int k = 0; k < 9; k++) C->Rwb_d[k] = S.Rd[k];
-#pragma unroll
-      for (int k = 0; k < 3; k++) {
-        C->x_d[k] = S.xd[k];
-        C->xdot_d[k] = S.xdotd[k];
-        C->w_d[k] = S.wd[k];
-      }
-    }
-  }
-  return run;
-}
-
 // the assembly of one robot (or of this lane's feet of it): wrench target and lever arms, contact state, optional
 // gait clock and swing planning.  Returns the stance word (bits 0-3 LegState, bit 8 = non-finite input).
 // (`S`, `fp`: what fetch_state() read - in commander mode the step may replace its desired state; `sw`: the robot's four
@@ -2432,6 +2339,34 @@ int qc_swing_reference_adjoint_batch(qc_handle* h, size_t n, const qc_batch_in* 
                                         io->joint_q_bar_in, io->Rwb_bar, io->x_bar, io->xdot_bar, io->w_bar, io->xdot_d_bar, io->joint_q_bar,
                                         io->p_start_bar, io->p_final_bar, io->flags};
   qc::swing_reference_adjoint_kernel<<<dim3(qc::swing_reference_blocks(n)), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, a);
+  QC_HIP(hipGetLastError());
+  return QC_OK;
+}
+
+void qc_default_commander_step(qc_commander_step_io* io) { (void)zeroed(io); }
+
+int qc_commander_step_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_command_in* cmd, const qc_commander_step_io* io, void* stream) {
+  if (const int rc = qc::check_commander_step_args(h, n, in, cmd, io); rc != QC_OK || n == 0) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  const qc::CommanderStepArgs a{in->Rwb, in->x, cmd->twist, cmd->fresh, reinterpret_cast<qc::CmdState*>(cmd->state), cmd->stand_height, cmd->stand_tol,
+                                cmd->cmd_dt, io->Rwb_d, io->x_d, io->xdot_d, io->w_d, io->run, io->applied};
+  qc::commander_step_kernel<<<dim3(qc::commander_step_blocks(n)), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>((long)n, a);
+  QC_HIP(hipGetLastError());
+  return QC_OK;
+}
+
+void qc_default_commander_step_adjoint(qc_commander_step_adjoint_io* io) { (void)zeroed(io); }
+
+int qc_commander_step_adjoint_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_command_in* cmd, const qc_commander_step_adjoint_io* io,
+                                    void* stream) {
+  if (const int rc = qc::check_commander_step_adjoint_args(h, n, in, cmd, io); rc != QC_OK || n == 0) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  // (of `cmd`: twist, fresh and the three scalars - its records are not read, the ones from before the forward call are)
+  const qc::CommanderStepAdjointArgs a{in->Rwb, in->x, cmd->twist, cmd->fresh, reinterpret_cast<const qc::CmdState*>(io->state_before), cmd->stand_height,
+                                       cmd->stand_tol, cmd->cmd_dt, io->Rwb_d_bar, io->x_d_bar, io->xdot_d_bar, io->w_d_bar, io->Vb_next_bar,
+                                       io->Rwb_bar_in, io->x_bar_in, io->twist_bar, io->Vb_bar, io->Rwb_bar, io->x_bar, io->Rwb_d_prev_bar,
+                                       io->x_d_prev_bar, io->xdot_d_prev_bar, io->w_d_prev_bar, io->flags};
+  qc::commander_step_adjoint_kernel<<<dim3(qc::commander_step_blocks(n)), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>((long)n, a);
   QC_HIP(hipGetLastError());
   return QC_OK;
 }

@@ -951,6 +951,99 @@ QC_DEV void fetch_extra(const BatchIn& in, long robot, TickExtra& X) {
     }
   }
 }
+// Commander mode (qc_tick_batch): one step of the reference's commander loop (commander_node.cpp:372-478) for this robot, run
+// where the robot is assembled - once per robot per launch (the hand-over paths re-read records, not inputs, and do not come
+// here).  Replaces the desired state in `S` when a held command is applied and returns whether the gait runs this tick (gait
+// clock, contact rule, planner).  Every member of a lane group computes the same values; member 0 stores what changed.
+QC_DEV bool commander_step(const BatchIn& in, long robot, int member, RawState& S, const TickExtra& X) {
+  int standing = X.flags[0], running = X.flags[1], pending = X.flags[2];
+  const bool fresh = X.fresh != 0;
+  double vb[6];
+#pragma unroll
+  for (int k = 0; k < 6; k++) vb[k] = fresh ? X.tw[k] : X.vb[k];  // cmdCallback, :191-202: the latest command wins
+  if (fresh) pending = 1;
+  if (!standing && fabs(S.x[2] - in.stand_height) < in.stand_tol) standing = 1;  // :386-391, almost_equal (strict)
+  bool run = false, applied = false;
+  if (standing) {
+    if (running) {
+      if (pending) {  // :397-428
+        // integrate_twist_yaw (trajectory.cpp:29-69): Rbb' from the angle-axis increment, the translation rotated by it
+        const double dt = in.cmd_dt;
+        const double d[3] = {vb[3] * dt, vb[4] * dt, vb[5] * dt};
+        const double th = __builtin_sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+        double Rb[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+        double t[3];
+        if (fabs(th) < 1.0e-12) {  // almost_equal(angle, 0.0)
+#pragma unroll
+          for (int k = 0; k < 3; k++) t[k] = vb[k] * dt;
+        } else {
+          const double a[3] = {d[0] / th, d[1] / th, d[2] / th};
+          double s, c;
+          sincos_joint(th, &s, &c);
+          const double oc = 1.0 - c;
+#pragma unroll
+          for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) Rb[3 * i + j] = oc * a[i] * a[j] + (i == j ? c : 0.0);
+          Rb[1] -= s * a[2]; Rb[3] += s * a[2];
+          Rb[2] += s * a[1]; Rb[6] -= s * a[1];
+          Rb[5] -= s * a[0]; Rb[7] += s * a[0];
+#pragma unroll
+          for (int i = 0; i < 3; i++) t[i] = (Rb[3 * i] * vb[0] + Rb[3 * i + 1] * vb[1] + Rb[3 * i + 2] * vb[2]) * dt;
+        }
+        // Rz(yaw of Rwb) without atan2 / sincos: yaw = atan2(R10, R00) away from pitch = +-pi/2.  At gimbal lock (h == 0, or a
+        // non-finite h) yaw 0 is taken: Drake's branch there is not pinned.
+        const double h = __builtin_sqrt(S.R[0] * S.R[0] + S.R[3] * S.R[3]);
+        const bool ok = h > 0.0 && h < 1.0e300;
+        const double cy = ok ? S.R[0] / h : 1.0, sy = ok ? S.R[3] / h : 0.0;
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+          S.Rd[j] = cy * Rb[j] - sy * Rb[3 + j];
+          S.Rd[3 + j] = sy * Rb[j] + cy * Rb[3 + j];
+          S.Rd[6 + j] = Rb[6 + j];
+        }
+        S.xd[0] = S.x[0] + (cy * t[0] - sy * t[1]);
+        S.xd[1] = S.x[1] + (sy * t[0] + cy * t[1]);
+        S.xd[2] = in.stand_height;  // "TODO: height drifts", :409
+        // Ad_T of the CURRENT pose (rigid3d.cpp:259-271): [R^T, -R^T [x]x; 0, R^T] Vb
+        const double u[3] = {vb[0] - (S.x[1] * vb[5] - S.x[2] * vb[4]), vb[1] - (S.x[2] * vb[3] - S.x[0] * vb[5]),
+                             vb[2] - (S.x[0] * vb[4] - S.x[1] * vb[3])};
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+          S.xdotd[k] = S.R[k] * u[0] + S.R[3 + k] * u[1] + S.R[6 + k] * u[2];
+          S.wd[k] = S.R[k] * vb[3] + S.R[3 + k] * vb[4] + S.R[6 + k] * vb[5];
+        }
+        pending = 0;
+        applied = true;
+      }
+      run = true;
+    } else {
+      running = 1;  // gait_scheduler.start(), :474-478: the first schedule() is next tick
+    }
+  }
+  if (member == 0) {
+    CmdState* C = in.cmd_state + robot;
+    if (standing != X.flags[0]) C->standing = standing;
+    if (running != X.flags[1]) C->gait_running = running;
+    if (pending != X.flags[2]) C->cmd_pending = pending;
+    if (fresh) {
+#pragma unroll
+      for (int k = 0; k < 6; k++) C->Vb[k] = vb[k];
+    }
+    if (applied) {
+#pragma unroll
+      for (int k = 0; k < 9; k++) C->Rwb_d[k] = S.Rd[k];
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        C->x_d[k] = S.xd[k];
+        C->xdot_d[k] = S.xdotd[k];
+        C->w_d[k] = S.wd[k];
+      }
+    }
+  }
+  return run;
+}
+
 // `foot0` = first foot owned by this lane; KIN: foot positions from joint_q by
 // forward kinematics instead of the `feet` array.  Returns 0.0 iff every input was finite.
 template <int FPL, bool KIN>

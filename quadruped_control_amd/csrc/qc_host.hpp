@@ -20,6 +20,7 @@
 #include "qc_sensitivity_kin.hpp"
 #include "qc_sensitivity_swing.hpp"
 #include "qc_swing_reference.hpp"
+#include "qc_commander.hpp"
 
 namespace qc {
 
@@ -747,5 +748,44 @@ inline int check_swing_reference_adjoint_args(const qc_handle* h, size_t n, cons
 
 // workgroups of the two kernels for n robots: one wave each, capped
 inline unsigned swing_reference_blocks(size_t n) { return capped_blocks(n, SENSITIVITY_BLOCK, SENSITIVITY_MAX_BLOCKS); }
+
+// ---------------------------------------------------------------- qc_commander_step_batch, qc_commander_step_adjoint_batch
+// What the two calls refuse about `cmd` and the scalars after their own outputs (`own`: the call's first refusal about its arrays,
+// nullptr: none; `state`: the records the call reads - cmd->state or io->state_before - and what it calls them), as qc_tick_batch does.
+inline int check_commander_step_batch(const char* who, size_t n, const qc_batch_in* in, const qc_command_in* cmd, const char* own, bool state, const char* state_msg) {
+  const auto bad = [who](const char* what) { return fail(QC_ERR_INVALID, std::string(who) + what); };
+  if (own) return bad(own);
+  if (cmd->fresh && !cmd->twist) return bad(": qc_command_in.fresh needs twist");
+  if (!std::isfinite(cmd->stand_height) || !(cmd->stand_tol >= 0.0) || !std::isfinite(cmd->stand_tol) || !std::isfinite(cmd->cmd_dt))
+    return bad(": stand_height, stand_tol (>= 0) and cmd_dt must be finite");
+  if (n == 0) return QC_OK;
+  if (!state) return bad(state_msg);
+  if (!in->Rwb || !in->x) return bad(": Rwb and x are required");
+  return check_one_launch(who, n, SENSITIVITY_BLOCK);
+}
+
+// The argument check of the commander step: what is wrong with the call itself (message prefix "qc_commander_step_batch:").
+inline int check_commander_step_args(const qc_handle* h, size_t n, const qc_batch_in* in, const qc_command_in* cmd, const qc_commander_step_io* io) {
+  const char* who = "qc_commander_step_batch";
+  if (const int rc = check_io(who, h && in && io, cmd, "qc_command_in", "qc_default_command"); rc != QC_OK) return rc;
+  if (const int rc = check_io(who, true, io, "qc_commander_step_io", "qc_default_commander_step"); rc != QC_OK) return rc;
+  return check_commander_step_batch(who, n, in, cmd, nullptr, cmd->state != nullptr, ": qc_command_in.state is required");
+}
+
+// The argument check of its reverse pass (message prefix "qc_commander_step_adjoint_batch:").
+inline int check_commander_step_adjoint_args(const qc_handle* h, size_t n, const qc_batch_in* in, const qc_command_in* cmd, const qc_commander_step_adjoint_io* io) {
+  const char* who = "qc_commander_step_adjoint_batch";
+  if (const int rc = check_io(who, h && in && io, cmd, "qc_command_in", "qc_default_command"); rc != QC_OK) return rc;
+  if (const int rc = check_io(who, true, io, "qc_commander_step_adjoint_io", "qc_default_commander_step_adjoint"); rc != QC_OK) return rc;
+  const char* own = nullptr;
+  if (!io->Rwb_d_bar && !io->x_d_bar && !io->xdot_d_bar && !io->w_d_bar && !io->Vb_next_bar)
+    own = ": no cotangent given (Rwb_d_bar, x_d_bar, xdot_d_bar, w_d_bar, Vb_next_bar are all NULL)";
+  else if (!io->twist_bar && !io->Vb_bar && !io->Rwb_bar && !io->x_bar && !io->Rwb_d_prev_bar && !io->x_d_prev_bar && !io->xdot_d_prev_bar && !io->w_d_prev_bar && !io->flags)
+    own = ": no output requested (twist_bar, Vb_bar, Rwb_bar, x_bar, Rwb_d_prev_bar, x_d_prev_bar, xdot_d_prev_bar, w_d_prev_bar, flags are all NULL)";
+  return check_commander_step_batch(who, n, in, cmd, own, io->state_before != nullptr, ": state_before is required (the commander records from before the forward call)");
+}
+
+// workgroups of the two kernels for n robots: one wave each, capped
+inline unsigned commander_step_blocks(size_t n) { return capped_blocks(n, SENSITIVITY_BLOCK, SENSITIVITY_MAX_BLOCKS); }
 
 }  // namespace qc
