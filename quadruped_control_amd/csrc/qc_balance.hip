@@ -82,6 +82,13 @@ struct Lane {
   // wave pays every instruction of the recalculation on its serial chain
   static constexpr bool kPacked = S;
   static_assert(!kPacked || FPL == 1, "the packed update takes negbits in the working-set word's layout, which multipliers_ok builds only below FPL == 4");
+  // ... and that word IS the lane's working-set state (the 6x6 forms' packed lanes): `wset` is carried from one recalculation
+  // to the next, iterate() decodes the ints of `C` from it for the solve and writes only the word back, so `C` is scratch
+  // inside iterate() there and everything outside reads and writes the state through set_foot_code() / foot_code()
+  static constexpr bool kWord = kPacked && Eqp::kWordState;
+  static_assert(!kWord || FPL == 1, "foot_code() / set_foot_code() hold the one foot of the lane: `wset` has no second field to keep");
+  // ... whose face coefficients and force bounds come from the lane's FaceConst (uniform form)
+  static constexpr bool kArith = kWord && Eqp::kFaceArith;
   Wrench<FPL> Wr;
   Cube<FPL> C;
   double f[3 * FPL];
@@ -97,11 +104,45 @@ struct Lane {
   bool kkt = false;
   int nclamp = 1;        // RACE: recalculations that clamp instead of stepping
   bool drop_all = false;  // RACE: drop every negative multiplier after a full step
+  // kWord: the working-set word, this lane's foot at ITS place (bits 6 foot0 ... 6 foot0 + 5: the update's masks need no
+  // shift).  Bits outside that field are whatever the group-uniform masks of past updates left there; readers take the field
+  uint32_t wset = 0u;
+  FaceConst fk = {0.0, 0.0, 0.0};  // kArith: set_face_const()
+
+  // the six bits (encode_foot) of foot i of this lane
+  QC_DEV uint32_t foot_code(int i) const {
+    if constexpr (kWord) return (wset >> (6 * foot0)) & 63u;
+    else return encode_foot(C.sx[i], C.sy[i], C.sz[i]);
+  }
+  // ... and their only writer outside iterate(); `code` holds valid fields (0, 1 or 3).  After foot0.
+  QC_DEV void set_foot_code(int i, uint32_t code) {
+    if constexpr (kWord) {
+      wset = (code & 63u) << (6 * foot0);
+    } else {
+      C.sx[i] = dec2(code); C.sy[i] = dec2(code >> 2); C.sz[i] = dec2(code >> 4);
+    }
+  }
+  // kArith: the foot's constants with its contact state folded in.  After stance and foot0, by whoever hands the lane a robot.
+  template <class PT>
+  QC_DEV void set_face_const(const PT& P) {
+    if constexpr (kArith) {
+      const bool st = (stance >> foot0) & 1u;
+      fk.iw = st ? P.inv_w_u : 0.0;
+      fk.lo = st ? P.fzmin : 0.0;
+      fk.hi = st ? P.fzmax : 0.0;
+    }
+  }
 
   template <class PT>
-  QC_DEV double lo(const PT& P, int i) const { return ((stance >> (foot0 + i)) & 1u) ? P.fzmin : 0.0; }
+  QC_DEV double lo(const PT& P, int i) const {
+    if constexpr (kArith) return fk.lo;
+    else return ((stance >> (foot0 + i)) & 1u) ? P.fzmin : 0.0;
+  }
   template <class PT>
-  QC_DEV double hi(const PT& P, int i) const { return ((stance >> (foot0 + i)) & 1u) ? P.fzmax : 0.0; }
+  QC_DEV double hi(const PT& P, int i) const {
+    if constexpr (kArith) return fk.hi;
+    else return ((stance >> (foot0 + i)) & 1u) ? P.fzmax : 0.0;
+  }
 
   // multiplier test on the current face: true if all active faces have
   // lambda >= -tol; otherwise wcode = 3*foot+axis of the most negative one.
@@ -181,13 +222,25 @@ struct Lane {
   // tests/test_gpu_matrix.py::test_iteration_cap_and_bad_inputs_agree_across_widths holds status, iteration count and the
   // (zero) forces of capped / bad robots equal across the lane-group widths.
   enum { MIXED = 0, FIRST = 1, STEADY = 2 };
+  // the equality-constrained solve on the current face (kArith: with the lane's FaceConst)
+  template <class PT>
+  QC_DEV bool solve_face(const PT& P, Eqp& eqp, double (&fh)[3 * FPL], double (&g)[3 * FPL]) {
+    if constexpr (kArith) return eqp.solve_arith(P, Wr, C, stance, foot0, fh, g, fk);
+    else return eqp.solve(P, Wr, C, stance, foot0, fh, g);
+  }
   // `empty_set` (wave-uniform): every robot of the wave still has the EMPTY working set - the first recalculation of a cold
   // fill.  With no active face there is no multiplier to test (every candidate is +BIG), so the test is skipped.
   template <int PHASE, class PT>
   QC_DEV bool iterate(const PT& P, Eqp& eqp, const bool live = true, const bool empty_set = false) {
     double fh[3 * FPL], g[3 * FPL];
     iters += live ? 1 : 0;
-    const bool pd = eqp.solve(P, Wr, C, stance, foot0, fh, g);
+    if constexpr (kWord) {  // the solve's ints from the word's fields
+      const uint32_t sh = 6u * (uint32_t)foot0;
+      C.sx[0] = __builtin_amdgcn_sbfe((int)wset, sh, 2);
+      C.sy[0] = __builtin_amdgcn_sbfe((int)wset, sh + 2, 2);
+      C.sz[0] = __builtin_amdgcn_sbfe((int)wset, sh + 4, 2);
+    }
+    const bool pd = solve_face(P, eqp, fh, g);
     // RACE, MIXED: the lane's strategy decides (its first `nclamp` recalculations are clamp steps)
     const bool fresh = PHASE == FIRST ? true : (PHASE == STEADY ? false : (RACE ? iters <= nclamp : !have_f));
     have_f = true;
@@ -289,10 +342,11 @@ struct Lane {
       uint32_t w = 0u, wc = 0u;
 #pragma unroll
       for (int i = 0; i < FPL; i++) {
-        w |= encode_foot(C.sx[i], C.sy[i], C.sz[i]) << (6 * i);
+        if constexpr (!kWord) w |= encode_foot(C.sx[i], C.sy[i], C.sz[i]) << (6 * i);
         if constexpr (PHASE != STEADY) wc |= encode_foot(Cc.sx[i], Cc.sy[i], Cc.sz[i]) << (6 * i);
       }
       w <<= sh0;
+      if constexpr (kWord) w = wset;  // carried, not re-encoded
       const uint32_t wlo = (uint32_t)__double_as_longlong(worst);
       const uint32_t rel1 = (at_fh & !opt) ? 3u << (((wlo & 31u) << 1) & 31u) : 0u;
       const uint32_t rel = RACE ? (dall ? negbits : rel1) : rel1;
@@ -305,11 +359,15 @@ struct Lane {
       }
       if constexpr (PHASE != STEADY) nw = take_clamp ? wc << sh0 : nw;
       nw = live ? nw : w;
+      if constexpr (kWord) {
+        wset = nw;
+      } else {
 #pragma unroll
-      for (int i = 0; i < FPL; i++) {
-        C.sx[i] = __builtin_amdgcn_sbfe((int)nw, sh0 + 6 * i, 2);
-        C.sy[i] = __builtin_amdgcn_sbfe((int)nw, sh0 + 6 * i + 2, 2);
-        C.sz[i] = __builtin_amdgcn_sbfe((int)nw, sh0 + 6 * i + 4, 2);
+        for (int i = 0; i < FPL; i++) {
+          C.sx[i] = __builtin_amdgcn_sbfe((int)nw, sh0 + 6 * i, 2);
+          C.sy[i] = __builtin_amdgcn_sbfe((int)nw, sh0 + 6 * i + 2, 2);
+          C.sz[i] = __builtin_amdgcn_sbfe((int)nw, sh0 + 6 * i + 4, 2);
+        }
       }
     } else {
 #pragma unroll
@@ -363,9 +421,15 @@ struct Lane {
     for (int i = 0; i < FPL; i++) {
       const uint32_t fb = wv >> (6 * (foot0 + i));
       const bool st = use_warm && ((stance >> (foot0 + i)) & 1u);
-      C.sx[i] = st ? dec2(fb) : 0;
-      C.sy[i] = st ? dec2(fb >> 2) : 0;
-      C.sz[i] = st ? dec2(fb >> 4) : 0;
+      if constexpr (kWord) {
+        // (a caller's word may hold the unused field value 2, which dec2 reads as free: keep a field only if its bit 0 is set)
+        const uint32_t b0 = fb & 0x15u;
+        set_foot_code(i, st ? (fb & (b0 | (b0 << 1))) : 0u);
+      } else {
+        C.sx[i] = st ? dec2(fb) : 0;
+        C.sy[i] = st ? dec2(fb >> 2) : 0;
+        C.sz[i] = st ? dec2(fb >> 4) : 0;
+      }
     }
 #pragma unroll
     for (int k = 0; k < 3 * FPL; k++) f[k] = 0.0;
@@ -411,7 +475,7 @@ struct Lane {
   QC_DEV uint32_t word_bits() const {
     uint32_t word = 0;
 #pragma unroll
-    for (int i = 0; i < FPL; i++) word |= encode_foot(C.sx[i], C.sy[i], C.sz[i]) << (6 * (foot0 + i));
+    for (int i = 0; i < FPL; i++) word |= foot_code(i) << (6 * (foot0 + i));
     return word;
   }
 
@@ -423,7 +487,7 @@ struct Lane {
     for (int i = 0; i < FPL; i++) {
 #pragma unroll
       for (int k = 0; k < 3; k++) sout[(OUT_F + 3 * (foot0 + i) + k) * SP + slot] = f[3 * i + k];
-      word |= encode_foot(C.sx[i], C.sy[i], C.sz[i]) << (6 * (foot0 + i));
+      word |= foot_code(i) << (6 * (foot0 + i));
     }
     word = (uint32_t)group_or<G, S>((int)word) | 0x80000000u;
     if (foot0 == 0) {
@@ -964,7 +1028,7 @@ QC_DEV void repack_write(const LaneX& L, double* __restrict__ rec, int slot, int
       rec[8 + 3 * ft + k] = L.Wr.r[i][k];
       rec[20 + 3 * ft + k] = L.f[3 * i + k];
     }
-    rec[32 + ft] = __longlong_as_double((long long)encode_foot(L.C.sx[i], L.C.sy[i], L.C.sz[i]));
+    rec[32 + ft] = __longlong_as_double((long long)L.foot_code(i));
   }
 }
 // ... and into member j4 of a 4-lane group; returns the robot's slot in the output stock
@@ -981,12 +1045,13 @@ QC_DEV int repack_read(const DevParams* __restrict__ Pg, Lane4X& L4, Eqp4X& eqp4
     L4.f[k] = rec[20 + 3 * j4 + k];
   }
   const uint32_t fw = (uint32_t)__double_as_longlong(rec[32 + j4]);
-  L4.C.sx[0] = dec2(fw); L4.C.sy[0] = dec2(fw >> 2); L4.C.sz[0] = dec2(fw >> 4);
   L4.idx = __double_as_longlong(rec[6]);
   const unsigned long long fl = (unsigned long long)__double_as_longlong(rec[7]);
   L4.stance = (uint32_t)fl & ~QC_POLISH_ONE;
   L4.iters = (int)(fl >> 40);
   L4.foot0 = j4;
+  L4.set_foot_code(0, fw);
+  if constexpr (Lane4X::kArith) L4.set_face_const(*QC_PARAMS_HERE(Pg));
   L4.status = QC_MAX_ITER;
   {
     const double tol = Eqp4X::kTolScale * QC_PARAMS_HERE(Pg)->tol_d;
@@ -1310,6 +1375,10 @@ __global__ __launch_bounds__(64, MIN_WAVES_PER_SIMD) void balance_kernel(const D
     if constexpr (RESIDENT) tol0 = uc.tol_start;
     else tol0 = QC_PARAMS_HERE(Pg)->tol_start;
     L.template load_from_stock<SP>(sin, busy ? slot : 0, member, tol0);
+    if constexpr (LaneT::kArith) {  // (guarded here: deriving the constants' pointer costs the other forms a scalar move)
+      if constexpr (RESIDENT) L.set_face_const(uc);
+      else L.set_face_const(*QC_PARAMS_HERE(Pg));
+    }
     eqp.setup(*QC_PARAMS_HERE(Pg), L.Wr, L.foot0);
     busy = busy && !probe;
     unsigned solved_mask = 0;  // RACE: strategies of this lane's robot that have reached the KKT point
@@ -1701,9 +1770,10 @@ __global__ __launch_bounds__(128, 2) void balance_pair_kernel(const DevParams* _
     L4.idx = base + rslot;
     L4.stance = (uint32_t)((fl >> 8) & 0x1FFu);
     const uint32_t fw = (uint32_t)(fl >> (24 + 6 * j4));
-    L4.C.sx[0] = dec2(fw); L4.C.sy[0] = dec2(fw >> 2); L4.C.sz[0] = dec2(fw >> 4);
     L4.iters = (int)(fl >> 48);
     L4.foot0 = j4;
+    L4.set_foot_code(0, fw);
+    if constexpr (Lane4::kArith) L4.set_face_const(*QC_PARAMS_HERE(Pg));
     L4.status = QC_MAX_ITER;
     {
       const double tol = Eqp4::kTolScale * QC_PARAMS_HERE(Pg)->tol_d;

@@ -1296,13 +1296,51 @@ QC_DEV FootCoef foot_coef(const PT& P, const FootW& fw, int sx, int sy, int sz, 
   }
   return k;
 }
+// The uniform form's constants of one foot with the foot's contact state folded in (0 for a swing foot): loop-invariant
+// per lane, so the strided 4-lane lanes keep them next to the robot (Lane::set_face_const) instead of selecting them
+// from the resident constants in every recalculation.
+struct FaceConst {
+  double iw, lo, hi;  // st ? 1 / w : 0, st ? fzmin : 0, st ? fzmax : 0
+};
+QC_DEV double max0(double a) {  // max(a, 0)
+  double r;
+  asm("v_max_f64 %0, %1, 0" : "=v"(r) : "v"(a));
+  return r;
+}
+QC_DEV double max0_neg(double a) {  // max(-a, 0)
+  double r;
+  asm("v_max_f64 %0, -%1, 0" : "=v"(r) : "v"(a));
+  return r;
+}
+// foot_coef<true> of the strided 4-lane lanes, selects as arithmetic: the states -1 / 0 / +1 as doubles are the
+// coefficients' switches, and every form returns the select's value bit for bit in all 27 states (products by exact 0 and
+// 1; x - x = +0; tests/test_racing_body_cpu.py restates them).  ix, iy: one fma instead of a lane-mask AND and two
+// v_cndmask; fzfix: two max, a product and an fma instead of eight integer / select instructions.  iz stays the select
+// over the three precomputed 1 / (w (1 + mu^2 k)): an exact arithmetic pick of a 64-bit value costs what its two v_cndmask
+// do, and the quadratic through the three values is not exact.
+template <class PT>
+QC_DEV FootCoef foot_coef_arith(const PT& P, const FaceConst& c, int sx, int sy, int sz, bool st) {
+  const double dx = (double)sx, dy = (double)sy, dz = (double)sz;
+  FootCoef k;
+  k.mx = P.mu * dx;
+  k.my = P.mu * dy;
+  k.fzfix = __builtin_fma(max0(dz), c.hi, max0_neg(dz) * c.lo);
+  k.ix = __builtin_fma(-__builtin_fabs(dx), c.iw, c.iw);
+  k.iy = __builtin_fma(-__builtin_fabs(dy), c.iw, c.iw);
+  const double b1 = sy != 0 ? P.inv_bz_u[2] : P.inv_bz_u[1];
+  const double b0 = sy != 0 ? P.inv_bz_u[1] : P.inv_bz_u[0];
+  k.iz = (st && sz == 0) ? (sx != 0 ? b1 : b0) : 0.0;
+  return k;
+}
 
 // `stance` = 4-bit mask of the robot, `foot0` = first foot of this lane.
 // `lane_w`: the lane's foot weights (general form with lane groups; ignored otherwise).
-template <bool UNIFORM, int G, bool S, class PT>
+// ARITH (uniform form, one foot per lane): the face coefficients by arithmetic from the lane's FaceConst `fk`.
+template <bool UNIFORM, int G, bool S, bool ARITH = false, class PT>
 QC_DEV bool eqp_diagw(const PT& P, const FootW (&lane_w)[4 / G], const Wrench<4 / G>& Wr, const Cube<4 / G>& C, uint32_t stance, int foot0,
-                      double (&f)[12 / G], double (&g)[12 / G], double& vmax) {
+                      double (&f)[12 / G], double (&g)[12 / G], double& vmax, const FaceConst* fk = nullptr) {
   constexpr int FPL = 4 / G;
+  static_assert(!ARITH || (UNIFORM && FPL == 1), "the arithmetic coefficients take the lane's one FaceConst");
   // weights of foot i of this lane: compile-time table entries when the lane owns all feet, its registers otherwise
   auto weights = [&](int i) -> FootW {
     if constexpr (UNIFORM) return FootW{};
@@ -1326,7 +1364,9 @@ QC_DEV bool eqp_diagw(const PT& P, const FootW (&lane_w)[4 / G], const Wrench<4 
     const bool first = i == 0;  // compile-time after unrolling
     const bool st = (stance >> (foot0 + i)) & 1u;
     const FootW fwt = weights(i);
-    const FootCoef k = foot_coef<UNIFORM>(P, fwt, C.sx[i], C.sy[i], C.sz[i], st);
+    FootCoef k;
+    if constexpr (ARITH) k = foot_coef_arith(P, *fk, C.sx[i], C.sy[i], C.sz[i], st);
+    else k = foot_coef<UNIFORM>(P, fwt, C.sx[i], C.sy[i], C.sz[i], st);
     if (KEEP) kc[i] = k;
     const double rx = Wr.r[i][0], ry = Wr.r[i][1], rz = Wr.r[i][2];
     double q[6], tq[6];
@@ -1466,6 +1506,11 @@ struct EqpDiagW {
   static constexpr bool kRepackTail = GROUP <= 2;  // one-fill waves finish their stragglers 4 lanes per robot
   static constexpr bool kNegB = true;  // the lane keeps -b (what the right-hand side adds), not b: no negation per recalculation
   static constexpr bool kHasScale = true;  // solve() leaves the group-uniform scale of the multipliers' noise in `gscale`
+  // Lane (uniform form, strided 4-lane lanes): the packed working-set word is the lane's state across recalculations and the face
+  // coefficients come by arithmetic (foot_coef_arith).  The general form keeps the ints and the selects: carrying the word moved two
+  // of its kernels (169 -> 167 registers) across an occupancy boundary
+  static constexpr bool kWordState = UNIFORM && GROUP == 4;
+  static constexpr bool kFaceArith = kWordState;
   static constexpr double kTolScale = 4.0; // ... as max(0.25, |v|_inf): the lane's tolerance carries the 4 (eqp_diagw)
   double gscale;
   FootW lane_w[4 / GROUP];  // general form with lane groups: the weights of this lane's feet (dead otherwise)
@@ -1481,6 +1526,12 @@ struct EqpDiagW {
   QC_DEV bool solve(const PT& P, const Wrench<4 / GROUP>& Wr, const Cube<4 / GROUP>& C, uint32_t stance, int foot0, double (&f)[12 / GROUP],
                     double (&g)[12 / GROUP]) {
     return eqp_diagw<UNIFORM, GROUP, kStrided>(P, lane_w, Wr, C, stance, foot0, f, g, gscale);
+  }
+  // ... with the face coefficients by arithmetic (kFaceArith lanes, which keep the FaceConst of their foot)
+  template <class PT>
+  QC_DEV bool solve_arith(const PT& P, const Wrench<4 / GROUP>& Wr, const Cube<4 / GROUP>& C, uint32_t stance, int foot0, double (&f)[12 / GROUP],
+                          double (&g)[12 / GROUP], const FaceConst& fk) {
+    return eqp_diagw<UNIFORM, GROUP, kStrided, kFaceArith>(P, lane_w, Wr, C, stance, foot0, f, g, gscale, &fk);
   }
 };
 
@@ -1506,6 +1557,7 @@ struct EqpDense {
   static constexpr bool kNegB = false;
   static constexpr bool kHasScale = false;  // the acceptance test scales with max(1, |g|_inf) of the lane group
   static constexpr double kTolScale = 1.0;
+  static constexpr bool kWordState = false, kFaceArith = false;  // (Lane: the ints are the state; coefficients by select)
   double gscale;  // (unused)
   double* Qs;    // LDS base of this lane: element k at Qs[k * 64]
   double c[12];  // c = -2 A^T S b (BC.cpp:153)
@@ -1696,6 +1748,7 @@ struct EqpDense4 {
   static constexpr bool kNegB = false;
   static constexpr bool kHasScale = false;  // the acceptance test scales with max(1, |g|_inf) of the lane group
   static constexpr double kTolScale = 1.0;
+  static constexpr bool kWordState = false, kFaceArith = false;  // (Lane: the ints are the state; coefficients by select)
   double gscale;  // (unused)
   static constexpr int XS = 17;           // tile stride in doubles (16 robots + 1)
   static constexpr int X_DOUBLES = 156 * XS;
