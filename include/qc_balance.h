@@ -928,6 +928,83 @@ void qc_default_commander_step_adjoint(qc_commander_step_adjoint_io* io);
  * a stand_height, stand_tol (>= 0) or cmd_dt that is not finite, or n beyond one launch. */
 int qc_commander_step_adjoint_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_command_in* cmd, const qc_commander_step_adjoint_io* io, void* stream);
 
+/* The virtual support polygon (SupportPolygon::position, trajectory.cpp:73-147): from the scheduled gait, the x, y position at which
+ * the COM should be held.  Per robot, in the reference's evaluation order, with the legs RL, FL, RR, FR = 0, 1, 2, 3 and the
+ * neighbours (minus, plus) of trajectory.cpp:75-78 - RL: (FL, RR), FL: (FR, RL), FR: (RR, FL), RR: (RL, FR):
+ *   1. weight  with phi the leg's RAW gait phase (gait_map.second: not a sub-phase of the stance or of the swing) and
+ *              (c0, cf, s0, sf) = schedule[l] = LegScheduledPhases' (stance_start, stance_end, swing_start, swing_end) - which are
+ *              the WIDTHS (sigma) of the erf ramps, whatever their names say:
+ *                stance leg  w = 0.5 (erf(phi / (c0 sqrt2 + 1e-12)) + erf((1 - phi) / (cf sqrt2 + 1e-12)))
+ *                swing leg   w = 0.5 (2 + erf(-phi / (s0 sqrt2 + 1e-12)) + erf((phi - 1) / (sf sqrt2 + 1e-12)))
+ *   2. points  P = the foot's x, y; zm = P w + P_minus (1 - w), zp = P w + P_plus (1 - w);
+ *              v = (1 / (w + w_minus + w_plus)) (w P + w_minus zm + w_plus zp)
+ *   3. mean    com_xy = (v_FL + v_FR + v_RL + v_RR) / 4, summed in that order (the reference's std::map)
+ * Of `in` it reads the feet - joint_q through the device forward kinematics if given, else `feet` (allowed here without joint_q) -
+ * gait_phase (required, never written) and the contact mask as every entry point resolves it: `stance` bytes, else the phase rule
+ * with gait_duty or the handle's value.  gait_dt, swing_state, swing_pos and swing_vel are refused; the rest is ignored unless
+ * `world` is set: then Rwb and x are required and P is taken of Rwb p + x, so com_xy is a WORLD-frame x, y that can be written
+ * straight into x_d[:, :2].
+ * `flags` bit l: the denominator of leg l's point is zero or not finite - the reference's 0/0.  The arithmetic is reproduced (the
+ * robot's com_xy is NaN); nothing is clamped.  All pointers are DEVICE pointers. */
+typedef struct qc_support_polygon_io {
+  size_t struct_size;      /* = sizeof(qc_support_polygon_io); checked                                          */
+  const double* schedule;  /* [n][4][4] the widths (c0, cf, s0, sf) per leg; required                            */
+  int32_t schedule_shared; /* nonzero: `schedule` is ONE [4][4] block read by every robot                        */
+  int32_t world;           /* nonzero: the polygon of Rwb p + x (in->Rwb and in->x required)                     */
+  double* com_xy;          /* [n][2] OUT: each optional, at least one given                                      */
+  double* weights;         /* [n][4]                                                                             */
+  int32_t* flags;          /* [n]: bit l - leg l's point is 0/0                                                  */
+} qc_support_polygon_io;
+/* struct_size set, the rest zero. */
+void qc_default_support_polygon(qc_support_polygon_io* io);
+/* Asynchronous on `stream`, no host synchronisation (graph-capturable); n == 0 launches nothing and returns QC_OK.  QC_ERR_INVALID
+ * (message starting with "qc_support_polygon_batch:", nothing launched) for a null handle, `in` or `io`, a wrong struct_size, a
+ * gait_dt, swing_state, swing_pos or swing_vel in `in`, no output requested, a missing schedule, gait_phase, feet / joint_q, `world`
+ * without Rwb or x, or n beyond one launch. */
+int qc_support_polygon_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_support_polygon_io* io, void* stream);
+
+/* The reverse pass of qc_support_polygon_batch.  The forward launch saves nothing: pass the same `in`, schedule, schedule_shared and
+ * world.  With g = com_xy_bar, per leg l in the order 0, 1, 2, 3 (m, p its minus and plus neighbours, D_l = w_l + w_m + w_p):
+ *   Nb = (g / 4) / D_l,  Db = -<g / 4, v_l> / D_l
+ *   wb_l += Db + <Nb, P_l> + w_m <Nb, P_l - P_m> + w_p <Nb, P_l - P_p>,  wb_m += Db + <Nb, zm_l>,  wb_p += Db + <Nb, zp_l>
+ *   Pb_l += (w_l + w_l w_m + w_l w_p) Nb,  Pb_m += w_m (1 - w_l) Nb,  Pb_p += w_p (1 - w_l) Nb
+ * then per leg, with a1, a2 the two erf arguments, d1, d2 their denominators, e_i = exp(-a_i^2) / sqrt(pi), sgn = +1 (stance), -1 (swing):
+ *   phase_bar_l = wb_l sgn (e1 / d1 - e2 / d2);  the two widths the leg's branch reads get -wb_l e_i a_i sqrt2 / d_i, the other two 0
+ *   body mode   feet_bar_l = (Pb_l, 0)
+ *   world mode  feet_bar_l = Rwb^T (Pb_l, 0) - BODY frame, what qc_sensitivity_kin_batch carries on to joint_q_bar -
+ *               Rwb_bar += (Pb_l, 0) p_l^T (ENTRYWISE, row-major: qc_sensitivity_rot_io's layout),  x_bar += (Pb_l, 0)  (z = 0)
+ * on top of the `_in` arrays (a missing one counts as zero).  In body mode Rwb_bar and x_bar equal their `_in`.
+ * The contact mask is HELD: a phase exactly on the stance / swing boundary gets the gradient of the branch the forward pass took.
+ * schedule_bar is [n][4][4], one block per robot, with a shared schedule too: it is NOT summed over the batch.
+ * A robot flagged by the forward rule (`flags`, as above) gets NaN in every output row.
+ * Each output may be the SAME array as its `_in`: every input of a robot is read before any of its outputs is written.  All
+ * pointers are DEVICE pointers. */
+typedef struct qc_support_polygon_adjoint_io {
+  size_t struct_size;            /* = sizeof(qc_support_polygon_adjoint_io); checked                             */
+  const double* schedule;        /* as the forward call's                                                        */
+  int32_t schedule_shared;
+  int32_t world;
+  const double* com_xy_bar;      /* [n][2] the cotangent; required                                               */
+  const double* feet_bar_in;     /* [n][4][3] added to the output of that name; each optional                    */
+  const double* Rwb_bar_in;      /* [n][9]                                                                       */
+  const double* x_bar_in;        /* [n][3]                                                                       */
+  const double* phase_bar_in;    /* [n][4]                                                                       */
+  const double* schedule_bar_in; /* [n][4][4]                                                                    */
+  double* feet_bar;              /* [n][4][3] OUT, body frame: each optional, at least one given (flags counts)  */
+  double* Rwb_bar;               /* [n][9]                                                                       */
+  double* x_bar;                 /* [n][3]                                                                       */
+  double* phase_bar;             /* [n][4]                                                                       */
+  double* schedule_bar;          /* [n][4][4]                                                                    */
+  int32_t* flags;                /* [n]: bit l - leg l's point is 0/0, no gradient                               */
+} qc_support_polygon_adjoint_io;
+/* struct_size set, the rest zero. */
+void qc_default_support_polygon_adjoint(qc_support_polygon_adjoint_io* io);
+/* Asynchronous on `stream`, no host synchronisation (graph-capturable); n == 0 launches nothing and returns QC_OK.  QC_ERR_INVALID
+ * (message starting with "qc_support_polygon_adjoint_batch:", nothing launched) for a null handle, `in` or `io`, a wrong
+ * struct_size, a gait_dt, swing_state, swing_pos or swing_vel in `in`, no output requested, a missing com_xy_bar, schedule,
+ * gait_phase, feet / joint_q, `world` without Rwb or x, or n beyond one launch. */
+int qc_support_polygon_adjoint_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_support_polygon_adjoint_io* io, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

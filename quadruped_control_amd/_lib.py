@@ -140,6 +140,17 @@ class QcCommanderStepAdjointIo(C.Structure):
                  "Rwb_bar", "x_bar", "Rwb_d_prev_bar", "x_d_prev_bar", "xdot_d_prev_bar", "w_d_prev_bar", "flags")]
 
 
+class QcSupportPolygonIo(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("schedule", C.c_void_p), ("schedule_shared", C.c_int32), ("world", C.c_int32)] + \
+               [(k, C.c_void_p) for k in ("com_xy", "weights", "flags")]
+
+
+class QcSupportPolygonAdjointIo(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("schedule", C.c_void_p), ("schedule_shared", C.c_int32), ("world", C.c_int32)] + \
+               [(k, C.c_void_p) for k in ("com_xy_bar", "feet_bar_in", "Rwb_bar_in", "x_bar_in", "phase_bar_in", "schedule_bar_in", "feet_bar",
+                                          "Rwb_bar", "x_bar", "phase_bar", "schedule_bar", "flags")]
+
+
 PARAM_COUNT = 211  # QC_PARAM_COUNT: the doubles of QcParams, in its order
 
 
@@ -157,7 +168,8 @@ EXPORTS = ("qc_create_abi", "qc_destroy", "qc_control_batch", "qc_control_batch_
            "qc_default_sensitivity_param", "qc_sensitivity_param_batch", "qc_default_sensitivity_kin", "qc_sensitivity_kin_batch",
            "qc_default_leg_plant_adjoint", "qc_leg_plant_step_adjoint_batch", "qc_default_sensitivity_swing", "qc_sensitivity_swing_batch",
            "qc_default_swing_reference", "qc_swing_reference_batch", "qc_default_swing_reference_adjoint", "qc_swing_reference_adjoint_batch",
-           "qc_default_commander_step", "qc_commander_step_batch", "qc_default_commander_step_adjoint", "qc_commander_step_adjoint_batch")
+           "qc_default_commander_step", "qc_commander_step_batch", "qc_default_commander_step_adjoint", "qc_commander_step_adjoint_batch",
+           "qc_default_support_polygon", "qc_support_polygon_batch", "qc_default_support_polygon_adjoint", "qc_support_polygon_adjoint_batch")
 
 _lib = None
 
@@ -281,6 +293,14 @@ def load():
     lib.qc_commander_step_adjoint_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcBatchIn), C.POINTER(QcCommandIn), C.POINTER(QcCommanderStepAdjointIo),
                                                     C.c_void_p]
     lib.qc_commander_step_adjoint_batch.restype = C.c_int
+    lib.qc_default_support_polygon.argtypes = [C.POINTER(QcSupportPolygonIo)]
+    lib.qc_default_support_polygon.restype = None
+    lib.qc_support_polygon_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcBatchIn), C.POINTER(QcSupportPolygonIo), C.c_void_p]
+    lib.qc_support_polygon_batch.restype = C.c_int
+    lib.qc_default_support_polygon_adjoint.argtypes = [C.POINTER(QcSupportPolygonAdjointIo)]
+    lib.qc_default_support_polygon_adjoint.restype = None
+    lib.qc_support_polygon_adjoint_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcBatchIn), C.POINTER(QcSupportPolygonAdjointIo), C.c_void_p]
+    lib.qc_support_polygon_adjoint_batch.restype = C.c_int
     # the structures above are hand-written mirrors of the header: a library built from another revision is refused here,
     # before any of them crosses the boundary
     rc = lib.qc_check_abi(ABI_VERSION, C.sizeof(QcParams), C.sizeof(QcBatchIn), C.sizeof(QcBatchOut))

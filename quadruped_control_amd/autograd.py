@@ -23,7 +23,10 @@ it for a batch that carries the references.
 swing_reference_autograd() is swing_reference_batch() - the gait clock, the contact mask, the foothold planner and the sextic swing
 trajectory, the front half of the tick - on a copy of the swing record, its backward one qc_swing_reference_adjoint_batch call;
 rollout_gait_autograd() chains it with tick_autograd() and leg_plant_step_autograd() and threads the record through: the twin of
-rollout_tick() on a batch with swing_state and a running clock."""
+rollout_tick() on a batch with swing_state and a running clock.
+
+support_polygon_autograd() is support_polygon_batch() - the desired COM x, y from the feet and the scheduled gait - its backward one
+qc_support_polygon_adjoint_batch call, and for joint_q the kinematics half of qc_sensitivity_kin_batch behind it."""
 from __future__ import annotations
 
 import torch
@@ -673,3 +676,57 @@ def rollout_tick_autograd(ctl, batch, steps, dt, leg_inertia, act_tol=1e-7, warm
     if warm and active is not None:
         out["active_set"] = active
     return {k: cur[k] for k in names}, out
+
+
+# ------------------------------------------------------------------ the virtual support polygon: gait -> desired COM x, y
+# the inputs a gradient is produced for, in the order backward returns them (the feet: `feet`, or joint_q through the kinematics adjoint)
+SUPPORT_POLYGON_DIFFERENTIABLE = ("feet", "joint_q", "Rwb", "x", "gait_phase", "schedule")
+_SUPPORT_POLYGON_BAR = {"feet": "feet_bar", "joint_q": "feet_bar", "Rwb": "Rwb_bar", "x": "x_bar", "gait_phase": "phase_bar", "schedule": "schedule_bar"}
+
+
+class _SupportPolygon(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ctl, batch, world, *tensors):
+        schedule = tensors[-1]
+        res = ctl.support_polygon_batch(batch, schedule, world=world, want=("com_xy",))
+        ctx.ctl, ctx.world = ctl, world
+        ctx.rest = {k: batch[k] for k in ("stance", "gait_duty") if batch.get(k) is not None}
+        ctx.present = tuple(t is not None for t in tensors)
+        ctx.save_for_backward(*[t for t in tensors if t is not None])
+        return res["com_xy"]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, com_bar):
+        names = SUPPORT_POLYGON_DIFFERENTIABLE
+        given = iter(ctx.saved_tensors)
+        inputs = {k: (next(given) if there else None) for k, there in zip(names, ctx.present)}
+        need = dict(zip(names, ctx.needs_input_grad[3:]))
+        want = tuple(dict.fromkeys(_SUPPORT_POLYGON_BAR[k] for k in names if need[k]))
+        if not want:
+            return (None,) * (3 + len(names))
+        batch = dict(ctx.rest, **{k: v for k, v in inputs.items() if v is not None and k != "schedule"})
+        ctl, schedule = ctx.ctl, inputs["schedule"]
+        s = ctl.support_polygon_adjoint_batch(batch, schedule, com_bar.contiguous(), world=ctx.world, want=want)
+        grads = {k: s[_SUPPORT_POLYGON_BAR[k]] for k in names if need[k] and k != "joint_q"}
+        if need["joint_q"]:  # J(q)^T feet_bar, leg by leg: the kinematics half of the fused tick's reverse pass (unmasked: every leg)
+            grads["joint_q"] = ctl.sensitivity_kinematics_batch({"joint_q": inputs["joint_q"]}, feet_bar=s["feet_bar"], want=("joint_q_bar",))["joint_q_bar"]
+        if need["schedule"] and schedule.dim() == 2:  # a shared block: the sum over the robots
+            grads["schedule"] = grads["schedule"].sum(0)
+        return (None, None, None, *[grads[k].view_as(inputs[k]) if need[k] else None for k in names])
+
+
+def support_polygon_autograd(ctl, batch, schedule, world=False):
+    """BalanceController.support_polygon_autograd (see there): com_xy of support_polygon_batch(), differentiable in
+    SUPPORT_POLYGON_DIFFERENTIABLE - `feet` where the batch has no joint_q, which the forward pass would read in its place."""
+    if batch.get("gait_phase") is None or (batch.get("feet") is None and batch.get("joint_q") is None):
+        raise ValueError("support_polygon_autograd: the batch lacks gait_phase, or both feet and joint_q")
+    if world and (batch.get("Rwb") is None or batch.get("x") is None):
+        raise ValueError("support_polygon_autograd: world=True needs Rwb and x")
+    if schedule is None or schedule.dtype != torch.float64:
+        raise ValueError("support_polygon_autograd: schedule is a float64 [n,4,4] or [4,4] tensor")
+    kin = batch.get("joint_q") is not None
+    taken = {"feet": not kin, "joint_q": kin, "Rwb": bool(world), "x": bool(world), "gait_phase": True}
+    tensors = [batch.get(k) if taken[k] else None for k in SUPPORT_POLYGON_DIFFERENTIABLE[:-1]] + [schedule]
+    detached = {k: (v.detach() if isinstance(v, torch.Tensor) else v) for k, v in batch.items() if k != "feet" or not kin}
+    return _SupportPolygon.apply(ctl, detached, bool(world), *tensors)

@@ -31,6 +31,7 @@ _IN_FIELDS = (("Rwb", 9), ("Rwb_d", 9), ("x", 3), ("xdot", 3), ("w", 3), ("x_d",
 _SENSITIVITY_SWING_WANT = ("swing_pos_bar", "swing_vel_bar", "joint_q_bar", "joint_qdot_bar", "Rwb_bar", "x_bar")  # sensitivity_swing_batch's default
 _SWING_REFERENCE_ADJOINT_WANT = ("Rwb_bar", "x_bar", "xdot_bar", "w_bar", "xdot_d_bar", "joint_q_bar", "p_start_bar", "p_final_bar")  # swing_reference_adjoint_batch's default
 _COMMANDER_STEP_ADJOINT_WANT = ("twist_bar", "Vb_bar", "Rwb_bar", "x_bar", "Rwb_d_prev_bar", "x_d_prev_bar", "xdot_d_prev_bar", "w_d_prev_bar")  # commander_step_adjoint_batch's default
+_SUPPORT_POLYGON_ADJOINT_WANT = ("feet_bar", "phase_bar", "schedule_bar")  # support_polygon_adjoint_batch's default
 _LEG_PLANT_ADJOINT_WANT = ("Rwb_bar", "x_bar", "xdot_bar", "w_bar", "joint_q_bar", "joint_qdot_bar", "joint_tau_bar")  # leg_plant_step_adjoint's default
 
 
@@ -1075,6 +1076,104 @@ class BalanceController:
 
         return swing_reference_autograd(self, batch, swing_state, p_start, p_final)
 
+    # ------------------------------------------- the virtual support polygon: the desired COM from the gait, and its reverse pass
+    def _support_polygon_batch(self, who, batch, schedule, world, io, own):
+        """The batch, the schedule and the mode of the two support-polygon calls: n from gait_phase (else feet, else joint_q), a
+        QcBatchIn from whatever of _SUPPORT_POLYGON_FIELDS the batch holds - and its swing_state, so that the library names its
+        refusal -, the float64 arrays of `own` ((name, tensor, k) entries) set in `io`.  Returns (n, dev, bi)."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        sized = [batch.get(k) for k in ("gait_phase", "feet", "joint_q") if batch.get(k) is not None]
+        if not sized:
+            raise ValueError(f"{who}: the batch holds neither gait_phase nor feet nor joint_q")
+        n = sized[0].shape[0]
+        bi = _lib.QcBatchIn()
+        for name, k, dtype in _SUPPORT_POLYGON_FIELDS:
+            t = batch.get(name)
+            if _check_tensor(name, t, n, k, getattr(torch, dtype), dev, False):
+                setattr(bi, name, t.data_ptr())
+        if batch.get("swing_state") is not None:
+            bi.swing_state = batch["swing_state"].data_ptr()
+        for name, t, k in own:
+            if _check_tensor(name, t, n, k, torch.float64, dev, False, "float64"):
+                setattr(io, name, t.data_ptr())
+        if schedule is not None:
+            shared = schedule.dim() == 2
+            if schedule.dtype != torch.float64 or not schedule.is_contiguous() or schedule.device != dev or \
+                    tuple(schedule.shape) != ((4, 4) if shared else (n, 4, 4)):
+                raise ValueError(f"schedule: need contiguous float64 [4,4] (shared) or [{n},4,4] on {dev}")
+            io.schedule, io.schedule_shared = schedule.data_ptr(), int(shared)
+        io.world = int(bool(world))
+        return n, dev, bi
+
+    def plan_support_polygon(self, batch, schedule, world=False, want=("com_xy",), out=None, stream=None):
+        """support_polygon_batch() marshalled once: returns (launch, out), `launch()` being one qc_support_polygon_batch call
+        (graph-capturable) on tensors that are read in place.  Planning launches nothing.  `out`: a dict of tensors to write into
+        instead of new ones (every name in `want`).  A call the library refuses raises ValueError with its message, from launch()."""
+        io = _lib.QcSupportPolygonIo()
+        self._lib.qc_default_support_polygon(C.byref(io))
+        n, dev, bi = self._support_polygon_batch("support_polygon", batch, schedule, world, io, [])
+        res = _outputs("support_polygon", _SUPPORT_POLYGON_OUTPUTS, want, out, n, dev, io)
+        args = (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
+        return self._launcher("qc_support_polygon_batch", args, (batch, schedule, res, bi, io), ValueError), res
+
+    def support_polygon_batch(self, batch, schedule, world=False, want=("com_xy",), out=None, stream=None):
+        """The reference's virtual support polygon (SupportPolygon::position; qc_support_polygon_batch, include/qc_balance.h;
+        INTEGRATION.md "Desired COM from the gait: the virtual support polygon"): the x, y at which the COM should be held, from
+        the feet and the scheduled gait.  `batch`: gait_phase [n,4] (the RAW phases, read only), joint_q (device forward kinematics)
+        or feet [n,4,3], optionally stance / gait_duty (the contact mask as everywhere: stance bytes, else the phase rule); with
+        world=True also Rwb and x, and the polygon is that of Rwb p + x - a world-frame x, y for x_d[:, :2].  A batch with gait_dt,
+        swing_state, swing_pos or swing_vel is refused.  `schedule`: the widths (sigma) of the erf ramps, float64 [n,4,4] - per leg
+        (stance_start, stance_end, swing_start, swing_end) of LegScheduledPhases - or ONE [4,4] block shared by every robot.
+        `want`: any of "com_xy" [n,2], "weights" [n,4], "flags" int32 [n] (bit l: the denominator of leg l's virtual point is zero
+        or not finite - the reference's 0/0, reproduced: com_xy is NaN).  Asynchronous on `stream`, no synchronisation.  Returns the
+        dict of device tensors; ValueError with the library's message for a call it refuses."""
+        launch, res = self.plan_support_polygon(batch, schedule, world, want, out, stream)
+        launch()
+        return res
+
+    def plan_support_polygon_adjoint(self, batch, schedule, com_xy_bar, world=False, want=_SUPPORT_POLYGON_ADJOINT_WANT, out=None,
+                                     feet_bar_in=None, Rwb_bar_in=None, x_bar_in=None, phase_bar_in=None, schedule_bar_in=None, stream=None):
+        """support_polygon_adjoint_batch() marshalled once: returns (launch, out), `launch()` being one
+        qc_support_polygon_adjoint_batch call (graph-capturable) on tensors that are read in place.  Planning launches nothing.
+        `out`: a dict of tensors to write into instead of new ones (every name in `want`) - an output may be its `_in` tensor.  A
+        call the library refuses raises ValueError with its message, from launch()."""
+        io = _lib.QcSupportPolygonAdjointIo()
+        self._lib.qc_default_support_polygon_adjoint(C.byref(io))
+        own = [("com_xy_bar", com_xy_bar, 2), ("feet_bar_in", feet_bar_in, 12), ("Rwb_bar_in", Rwb_bar_in, 9), ("x_bar_in", x_bar_in, 3),
+               ("phase_bar_in", phase_bar_in, 4), ("schedule_bar_in", schedule_bar_in, 16)]
+        n, dev, bi = self._support_polygon_batch("support_polygon_adjoint", batch, schedule, world, io, own)
+        res = _outputs("support_polygon_adjoint", _SUPPORT_POLYGON_ADJOINT_OUTPUTS, want, out, n, dev, io)
+        args = (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
+        keep = (batch, schedule, com_xy_bar, feet_bar_in, Rwb_bar_in, x_bar_in, phase_bar_in, schedule_bar_in, res, bi, io)
+        return self._launcher("qc_support_polygon_adjoint_batch", args, keep, ValueError), res
+
+    def support_polygon_adjoint_batch(self, batch, schedule, com_xy_bar, world=False, want=_SUPPORT_POLYGON_ADJOINT_WANT, out=None,
+                                      feet_bar_in=None, Rwb_bar_in=None, x_bar_in=None, phase_bar_in=None, schedule_bar_in=None, stream=None):
+        """The reverse pass of support_polygon_batch() (qc_support_polygon_adjoint_batch, include/qc_balance.h).  `batch`, `schedule`,
+        `world`: the forward call's - nothing was saved.  `com_xy_bar` [n,2]: the cotangent on com_xy.  `want`: any of "feet_bar"
+        [n,4,3] (BODY frame; in world mode Rwb^T of the world-frame cotangent, what sensitivity_kinematics_batch() carries on to
+        joint_q_bar), "Rwb_bar" [n,9] (entrywise, row-major), "x_bar" [n,3] (z = 0), "phase_bar" [n,4], "schedule_bar" [n,4,4] -
+        per robot with a shared schedule too, never summed over the batch - and "flags" int32 [n].  The five `_in` tensors are
+        added to the outputs of those names; each may be the output's own tensor.  The contact mask is held.  A robot the forward
+        rule flags gets NaN in every row.  Nothing of `batch` is written.  Asynchronous on `stream`, no synchronisation.  Returns the
+        dict of device tensors; ValueError with the library's message for a call it refuses."""
+        launch, res = self.plan_support_polygon_adjoint(batch, schedule, com_xy_bar, world, want, out, feet_bar_in, Rwb_bar_in, x_bar_in,
+                                                        phase_bar_in, schedule_bar_in, stream)
+        launch()
+        return res
+
+    def support_polygon_autograd(self, batch, schedule, world=False):
+        """support_polygon_batch() with a gradient: returns com_xy [n,2], differentiable in batch["feet"] - or batch["joint_q"],
+        through the kinematics adjoint -, batch["gait_phase"], `schedule` ([n,4,4], or [4,4] shared: its gradient is then the sum
+        over the robots, taken by torch) and, with world=True, batch["Rwb"] (entrywise) and batch["x"].  Backward is one
+        support_polygon_adjoint_batch() call - two with joint_q - on the current stream, without host synchronisation.  The contact
+        mask is held; a robot whose polygon is the reference's 0/0 gets NaN gradients.  There is no double backward."""
+        from .autograd import support_polygon_autograd
+
+        return support_polygon_autograd(self, batch, schedule, world)
+
     def rollout_gait_autograd(self, batch, steps, dt, leg_inertia, gait_dt, act_tol=1e-7, warm=True, params=None, joint_gains=None):
         """The functional twin of rollout_tick(batch, None, ...) for a batch with swing_state and a running clock: per step
         swing_reference_autograd() with the clock advancing by `gait_dt` (a number, or a float64 [n] tensor), tick_autograd() on the
@@ -1356,6 +1455,15 @@ _SWING_REFERENCE_ADJOINT_OUTPUTS = {"Rwb_bar": ((9,), "float64"), **{k: ((3,), "
                                     "flags": ((), "int32")}
 # the forward call's outputs a cotangent may be given on -> the io field
 _SWING_REFERENCE_COTANGENTS = {"swing_pos": "swing_pos_bar", "swing_vel": "swing_vel_bar", "p_start": "p_start_next_bar", "p_final": "p_final_next_bar"}
+
+
+# support_polygon / support_polygon_adjoint: what the two calls read of the batch, and - so that the library names its refusal -
+# gait_dt, swing_pos and swing_vel
+_SUPPORT_POLYGON_FIELDS = tuple((k, m, "float64") for k, m in (("Rwb", 9), ("x", 3), ("feet", 12), ("joint_q", 12))) + \
+    _READONLY_FIELDS[len(_STATE_FIELDS):] + (("gait_dt", 1, "float64"), ("swing_pos", 12, "float64"), ("swing_vel", 12, "float64"))
+_SUPPORT_POLYGON_OUTPUTS = {"com_xy": ((2,), "float64"), "weights": ((4,), "float64"), "flags": ((), "int32")}
+_SUPPORT_POLYGON_ADJOINT_OUTPUTS = {"feet_bar": ((4, 3), "float64"), "Rwb_bar": ((9,), "float64"), "x_bar": ((3,), "float64"),
+                                    "phase_bar": ((4,), "float64"), "schedule_bar": ((4, 4), "float64"), "flags": ((), "int32")}
 
 
 # commander_step / commander_step_adjoint: what the two calls read of the batch

@@ -2441,6 +2441,35 @@ int qc_commander_step_adjoint_batch(qc_handle* h, size_t n, const qc_batch_in* i
   return QC_OK;
 }
 
+void qc_default_support_polygon(qc_support_polygon_io* io) { (void)zeroed(io); }
+
+int qc_support_polygon_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_support_polygon_io* io, void* stream) {
+  if (const int rc = qc::check_support_polygon_args(h, n, in, io); rc != QC_OK || n == 0) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  // (of `in`: the feet, the phases and the contact mask as it is now, the pose in world mode - nothing of it is written)
+  const bool world = io->world != 0;
+  const qc::SupportPolygonArgs a{in->feet, in->joint_q, in->gait_phase, in->stance, in->gait_duty, world ? in->Rwb : nullptr, world ? in->x : nullptr,
+                                 io->schedule, io->schedule_shared != 0, io->com_xy, io->weights, io->flags};
+  qc::support_polygon_kernel<<<dim3(qc::support_polygon_blocks(n)), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, a);
+  QC_HIP(hipGetLastError());
+  return QC_OK;
+}
+
+void qc_default_support_polygon_adjoint(qc_support_polygon_adjoint_io* io) { (void)zeroed(io); }
+
+int qc_support_polygon_adjoint_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_support_polygon_adjoint_io* io, void* stream) {
+  if (const int rc = qc::check_support_polygon_adjoint_args(h, n, in, io); rc != QC_OK || n == 0) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  const bool world = io->world != 0;
+  const qc::SupportPolygonAdjointArgs a{in->feet, in->joint_q, in->gait_phase, in->stance, in->gait_duty, world ? in->Rwb : nullptr, world ? in->x : nullptr,
+                                        io->schedule, io->schedule_shared != 0, io->com_xy_bar, io->feet_bar_in, io->Rwb_bar_in, io->x_bar_in,
+                                        io->phase_bar_in, io->schedule_bar_in, io->feet_bar, io->Rwb_bar, io->x_bar, io->phase_bar, io->schedule_bar,
+                                        io->flags};
+  qc::support_polygon_adjoint_kernel<<<dim3(qc::support_polygon_blocks(n)), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, a);
+  QC_HIP(hipGetLastError());
+  return QC_OK;
+}
+
 // host-pointer variant.  Large batches: one device staging allocation, H2D copies, kernel, D2H copies, sync.
 // Small batches (n <= kPinnedMaxN; the reference's own use is one robot per controller tick): the records are packed
 // into a pinned, device-visible host buffer that the kernel reads and writes in place over PCIe - one launch and one

@@ -331,6 +331,84 @@ QC_DEV double rcp_nr(double d) {
   return y;
 }
 
+// exp(hi + lo) for hi + lo in about [-1100, 40], |lo| of order one or less: the sum is reduced by k ln 2 in two fused steps (ln 2 split
+// 32 + 53 bits as in the public-domain fdlibm; k ln2_hi is exact for |k| < 2^21), `lo` joins the remainder after the large part has
+// cancelled, and exp(r) on |r| <= ln 2 / 2 + a little is the Taylor sum to r^13 (next term 4e-18) with the last addition of 1 the only
+// rounding that counts.  No division, no table, no branch; v_ldexp_f64 scales, so a result below the normal range is rounded once more
+// there and underflows to 0.  ~0.7 EPS (2^-52) relative on normal results.  The caller keeps hi + lo inside the range.
+QC_DEV double exp_reduced(double hi, double lo) {
+  const double kf = __builtin_rint((hi + lo) * 1.44269504088896338700e+00);
+  double r = __builtin_fma(-kf, 6.93147180369123816490e-01, hi);
+  r = __builtin_fma(-kf, 1.90821492927058770002e-10, r + lo);
+  double p = 1.0 / 6227020800.0;  // 1 / 13!
+  p = __builtin_fma(p, r, 1.0 / 479001600.0);
+  p = __builtin_fma(p, r, 1.0 / 39916800.0);
+  p = __builtin_fma(p, r, 1.0 / 3628800.0);
+  p = __builtin_fma(p, r, 1.0 / 362880.0);
+  p = __builtin_fma(p, r, 1.0 / 40320.0);
+  p = __builtin_fma(p, r, 1.0 / 5040.0);
+  p = __builtin_fma(p, r, 1.0 / 720.0);
+  p = __builtin_fma(p, r, 1.0 / 120.0);
+  p = __builtin_fma(p, r, 1.0 / 24.0);
+  p = __builtin_fma(p, r, 1.0 / 6.0);
+  p = __builtin_fma(p, r, 0.5);
+  const double y = __builtin_fma(r * r, p, r) + 1.0;
+  return __builtin_ldexp(y, (int)kf);
+}
+
+// exp(-a^2).  a^2 = s + e EXACTLY with s = fl(a a) and e the FMA residual, so the relative error does not grow like a^2 EPS (at
+// a = 26 the rounding of a a alone is 7e-14 of the result): -s is reduced, -e joins the remainder.  EXP_NEG_SQ_ZERO: from s = 750 on
+// the result is 0 (the smallest subnormal is exp(-744.44)); so is that of +-inf and of a finite a whose square overflows.  NaN -> NaN.
+constexpr double EXP_NEG_SQ_ZERO = 750.0;
+QC_DEV double exp_neg_sq(double a) {
+  const double s = a * a;
+  const bool in = s < EXP_NEG_SQ_ZERO;  // (false for NaN)
+  const double sc = in ? s : 0.0, e = in ? __builtin_fma(a, a, -s) : 0.0;
+  const double y = exp_reduced(-sc, -e);
+  return in ? y : (s != s ? s : 0.0);
+}
+
+// erf(x), FP64.  The four rational approximations of the public-domain fdlibm (s_erf.c; its coefficients) on |x| < ERF_B0 = 0.84375
+// (x + x P(x^2)/Q(x^2): a tiny or subnormal x gives x + x 0.12837916709551256, the correctly rounded 2x/sqrt(pi), by one FMA),
+// [ERF_B0, ERF_B1 = 1.25) (erx + P(|x| - 1)/Q(|x| - 1)), [ERF_B1, ERF_B2 = 1/0.35) and [ERF_B2, ERF_ONE = 6) (1 - exp(-x^2 - 0.5625 +
+// R(1/x^2)/S(1/x^2)) / |x|, the exponential by exp_reduced on the exact split of x^2 in place of fdlibm's two exp calls on a truncated
+// x); from ERF_ONE on, and for +-inf, exactly +-1 (erfc(5.93) < 2^-54: the third form already rounds to 1 from there on).  ONE pass for
+// every lane: the interval selects the argument and the coefficients (degree 7 over degree 8, the shorter ones padded with zeros),
+// then one Horner pair, two divisions, one exponential and a select - no branch, no table, no call.  Odd; NaN -> NaN.  Within
+// 0.6 EPS of the 50-digit value on normal results (tests/test_gpu_support_polygon.py).
+constexpr double ERF_B0 = 0.84375, ERF_B1 = 1.25, ERF_B2 = 1.0 / 0.35, ERF_ONE = 6.0;
+QC_DEV double erf_f64(double x) {
+  const double ax = fabs(x);
+  const bool i0 = ax < ERF_B0, i1 = ax < ERF_B1, i2 = ax < ERF_B2, i3 = ax < ERF_ONE;  // (all false for NaN)
+  const double ac = i3 ? ax : ERF_ONE;                                                // what the tail forms see: finite, <= 6
+  const double rx = 1.0 / (i1 ? 1.0 : ac);
+  const double u = i0 ? ac * ac : (i1 ? ac - 1.0 : rx * rx);
+#define QC_ERF_SEL(c0, c1, c2, c3) (i0 ? (c0) : (i1 ? (c1) : (i2 ? (c2) : (c3))))
+  double p = QC_ERF_SEL(0.0, 0.0, -9.81432934416914548592e+00, 0.0);
+  p = __builtin_fma(p, u, QC_ERF_SEL(0.0, -2.16637559486879084300e-03, -8.12874355063065934246e+01, -4.83519191608651397019e+02));
+  p = __builtin_fma(p, u, QC_ERF_SEL(0.0, 3.54783043256182359371e-02, -1.84605092906711035994e+02, -1.02509513161107724954e+03));
+  p = __builtin_fma(p, u, QC_ERF_SEL(-2.37630166566501626084e-05, -1.10894694282396677476e-01, -1.62396669462573470355e+02, -6.37566443368389627722e+02));
+  p = __builtin_fma(p, u, QC_ERF_SEL(-5.77027029648944159157e-03, 3.18346619901161753674e-01, -6.23753324503260060396e+01, -1.60636384855821916062e+02));
+  p = __builtin_fma(p, u, QC_ERF_SEL(-2.84817495755985104766e-02, -3.72207876035701323847e-01, -1.05586262253232909814e+01, -1.77579549177547519889e+01));
+  p = __builtin_fma(p, u, QC_ERF_SEL(-3.25042107247001499370e-01, 4.14856118683748331666e-01, -6.93858572707181764372e-01, -7.99283237680523006574e-01));
+  p = __builtin_fma(p, u, QC_ERF_SEL(1.28379167095512558561e-01, -2.36211856075265944077e-03, -9.86494403484714822705e-03, -9.86494292470009928597e-03));
+  double q = QC_ERF_SEL(0.0, 0.0, -6.04244152148580987438e-02, 0.0);
+  q = __builtin_fma(q, u, QC_ERF_SEL(0.0, 0.0, 6.57024977031928170135e+00, -2.24409524465858183362e+01));
+  q = __builtin_fma(q, u, QC_ERF_SEL(0.0, 1.19844998467991074170e-02, 1.08635005541779435134e+02, 4.74528541206955367215e+02));
+  q = __builtin_fma(q, u, QC_ERF_SEL(-3.96022827877536812320e-06, 1.36370839120290507362e-02, 4.29008140027567833386e+02, 2.55305040643316442583e+03));
+  q = __builtin_fma(q, u, QC_ERF_SEL(1.32494738004321644526e-04, 1.26171219808761642112e-01, 6.45387271733267880336e+02, 3.19985821950859553908e+03));
+  q = __builtin_fma(q, u, QC_ERF_SEL(5.08130628187576562776e-03, 7.18286544141962662868e-02, 4.34565877475229228821e+02, 1.53672958608443695994e+03));
+  q = __builtin_fma(q, u, QC_ERF_SEL(6.50222499887672944485e-02, 5.40397917702171048937e-01, 1.37657754143519042600e+02, 3.25792512996573918826e+02));
+  q = __builtin_fma(q, u, QC_ERF_SEL(3.97917223959155352819e-01, 1.06420880400844228286e-01, 1.96512716674392571292e+01, 3.03380607434824582924e+01));
+  q = __builtin_fma(q, u, 1.0);
+#undef QC_ERF_SEL
+  const double y = p / q;
+  const double s = i1 ? 0.0 : ac * ac, e = i1 ? 0.0 : __builtin_fma(ac, ac, -s);
+  const double tail = __builtin_fma(-exp_reduced(-s, (i1 ? 0.0 : y - 0.5625) - e), rx, 1.0);
+  const double r = i0 ? __builtin_fma(ax, y, ax) : (i1 ? 8.45062911510467529297e-01 + y : (i3 ? tail : 1.0));
+  return x != x ? x : __builtin_copysign(r, x);
+}
+
 // Rotation3d(mat).angleAxisTotal(): math/rigid3d.cpp:177-179,198-203
 // (Drake RotationMatrix::ToAngleAxis -> Eigen matrix->quaternion->angle-axis).
 // Eigen's four cases (trace > 0, else pivot on the largest diagonal entry; ties keep the lower index, as its > tests do)

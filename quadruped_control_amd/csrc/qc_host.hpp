@@ -21,6 +21,7 @@
 #include "qc_sensitivity_swing.hpp"
 #include "qc_swing_reference.hpp"
 #include "qc_commander.hpp"
+#include "qc_support_polygon.hpp"
 
 namespace qc {
 
@@ -787,5 +788,46 @@ inline int check_commander_step_adjoint_args(const qc_handle* h, size_t n, const
 
 // workgroups of the two kernels for n robots: one wave each, capped
 inline unsigned commander_step_blocks(size_t n) { return capped_blocks(n, SENSITIVITY_BLOCK, SENSITIVITY_MAX_BLOCKS); }
+
+// ---------------------------------------------------------------- qc_support_polygon_batch, qc_support_polygon_adjoint_batch
+// What the two calls refuse after check_io, in this order: what would advance, plan or track (`in`); `own`, the call's first refusal
+// about its outputs and cotangent (nullptr: none); for n > 0 the schedule, the phases, the feet, the pose of world mode and the
+// launch bound.
+inline int check_support_polygon_batch(const char* who, size_t n, const qc_batch_in* in, const char* own, const double* schedule, bool world) {
+  const auto bad = [who](const char* what) { return fail(QC_ERR_INVALID, std::string(who) + what); };
+  if (in->gait_dt) return bad(": gait_dt must be NULL (no clock is advanced: gait_phase is read as it is now)");
+  if (in->swing_state) return bad(": swing_state must be NULL (nothing is planned here)");
+  if (in->swing_pos || in->swing_vel) return bad(": swing_pos and swing_vel must be NULL (the polygon reads the feet, not the swing references)");
+  if (own) return bad(own);
+  if (n == 0) return QC_OK;
+  if (!schedule) return bad(": schedule is required (the widths of the ramps, [n][4][4] or one shared [4][4])");
+  if (!in->gait_phase) return bad(": gait_phase is required");
+  if (!in->feet && !in->joint_q) return bad(": feet or joint_q is required");
+  if (world && (!in->Rwb || !in->x)) return bad(": world needs Rwb and x");
+  return check_one_launch(who, n, SENSITIVITY_BLOCK);
+}
+
+// The argument check of the support polygon: what is wrong with the call itself (message prefix "qc_support_polygon_batch:").
+inline int check_support_polygon_args(const qc_handle* h, size_t n, const qc_batch_in* in, const qc_support_polygon_io* io) {
+  const char* who = "qc_support_polygon_batch";
+  if (const int rc = check_io(who, h && in, io, "qc_support_polygon_io", "qc_default_support_polygon"); rc != QC_OK) return rc;
+  const char* own = !io->com_xy && !io->weights && !io->flags ? ": no output requested (com_xy, weights, flags are all NULL)" : nullptr;
+  return check_support_polygon_batch(who, n, in, own, io->schedule, io->world != 0);
+}
+
+// The argument check of its reverse pass (message prefix "qc_support_polygon_adjoint_batch:").
+inline int check_support_polygon_adjoint_args(const qc_handle* h, size_t n, const qc_batch_in* in, const qc_support_polygon_adjoint_io* io) {
+  const char* who = "qc_support_polygon_adjoint_batch";
+  if (const int rc = check_io(who, h && in, io, "qc_support_polygon_adjoint_io", "qc_default_support_polygon_adjoint"); rc != QC_OK) return rc;
+  const char* own = nullptr;
+  if (!io->feet_bar && !io->Rwb_bar && !io->x_bar && !io->phase_bar && !io->schedule_bar && !io->flags)
+    own = ": no output requested (feet_bar, Rwb_bar, x_bar, phase_bar, schedule_bar, flags are all NULL)";
+  else if (n > 0 && !io->com_xy_bar)
+    own = ": com_xy_bar is required";
+  return check_support_polygon_batch(who, n, in, own, io->schedule, io->world != 0);
+}
+
+// workgroups of the two kernels for n robots: one wave each, capped
+inline unsigned support_polygon_blocks(size_t n) { return capped_blocks(n, SENSITIVITY_BLOCK, SENSITIVITY_MAX_BLOCKS); }
 
 }  // namespace qc
