@@ -1005,6 +1005,86 @@ void qc_default_support_polygon_adjoint(qc_support_polygon_adjoint_io* io);
  * gait_phase, feet / joint_q, `world` without Rwb or x, or n beyond one launch. */
 int qc_support_polygon_adjoint_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_support_polygon_adjoint_io* io, void* stream);
 
+/* The desired COM position of a step from the virtual support polygon: one launch in front of the tick makes the x_d it tracks.
+ * Of `in` it reads what qc_support_polygon_batch reads with `world` set - gait_phase, joint_q (device forward kinematics) or feet,
+ * the contact mask (`stance` bytes, else the phase rule), Rwb and x (both required) - and refuses the same batches (gait_dt,
+ * swing_state, swing_pos, swing_vel).  With P_l the x, y of Rwb p_l + x and com_xy the polygon's value, by the polygon's own device
+ * functions (com_xy equals qc_support_polygon_batch's bit for bit):
+ *   QC_COM_REPLACE  x_d_out = (com_xy, x_d_in.z);  gain is ignored
+ *   QC_COM_OFFSET   x_d_out = x_d_in + gain (com_xy - centroid_xy, 0),  centroid_xy = (((P_FL + P_FR) + P_RL) + P_RR) / 4
+ * With all four weights 1, com_xy = centroid_xy in exact arithmetic: the offset is the lean alone, and an x_d that tracks a twist
+ * is not dragged to the feet.  z is copied.  `flags` as the polygon's (bit l: the reference's 0/0 at leg l's point); a flagged
+ * robot gets NaN in x_d_out's x and y, com_xy is what the reference's arithmetic gives.  x_d_out may be the SAME array as x_d_in:
+ * every input of a robot is read before any of its outputs is written.  All pointers are DEVICE pointers. */
+enum { QC_COM_REPLACE = 0, QC_COM_OFFSET = 1 };
+typedef struct qc_com_reference_io {
+  size_t struct_size;      /* = sizeof(qc_com_reference_io); checked                                              */
+  const double* schedule;  /* [n][4][4] the widths (c0, cf, s0, sf) per leg; required                            */
+  int32_t schedule_shared; /* nonzero: `schedule` is ONE [4][4] block read by every robot                        */
+  int32_t mode;            /* QC_COM_REPLACE or QC_COM_OFFSET                                                    */
+  double gain;             /* QC_COM_OFFSET's factor, finite; default 1                                          */
+  const double* x_d_in;    /* [n][3]; required                                                                   */
+  double* x_d_out;         /* [n][3] OUT; required, may be x_d_in                                                */
+  double* com_xy;          /* [n][2] OUT, optional: the polygon's value                                          */
+  int32_t* flags;          /* [n] OUT, optional                                                                  */
+} qc_com_reference_io;
+/* struct_size set, mode = QC_COM_REPLACE, gain = 1, the rest zero. */
+void qc_default_com_reference(qc_com_reference_io* io);
+/* Asynchronous on `stream`, no host synchronisation (graph-capturable); n == 0 launches nothing and returns QC_OK.  QC_ERR_INVALID
+ * (message starting with "qc_com_reference_batch:", nothing launched) for a null handle, `in` or `io`, a wrong struct_size, a
+ * gait_dt, swing_state, swing_pos or swing_vel in `in`, an unknown mode, a gain that is not finite, a missing x_d_out, x_d_in,
+ * schedule, gait_phase, feet / joint_q, Rwb or x, or n beyond one launch. */
+int qc_com_reference_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_com_reference_io* io, void* stream);
+
+/* The reverse pass of qc_com_reference_batch.  The forward launch saves nothing: pass the same `in`, schedule, schedule_shared,
+ * mode and gain.  With o = x_d_out_bar:
+ *   QC_COM_REPLACE  x_d_in_bar = (0, 0, o.z);  the polygon's reverse pass (qc_support_polygon_adjoint_batch, world mode) from
+ *                   com_xy_bar = o.xy
+ *   QC_COM_OFFSET   x_d_in_bar = o;  the polygon's reverse pass from com_xy_bar = gain o.xy, and the centroid adds
+ *                   -gain o.xy / 4 to every Pb_l before the points are carried on to feet_bar, Rwb_bar and x_bar
+ * feet_bar (BODY frame), Rwb_bar (entrywise), x_bar, phase_bar and schedule_bar ([n][4][4], one block per robot) go on top of
+ * their `_in` arrays (a missing one counts as zero), each of which may be its own output, and x_d_in_bar may be x_d_out_bar.
+ * `gain` gets NO cotangent, nor do the contact mask (held) and the mode.  A robot flagged by the forward rule gets NaN in every
+ * output row, x_d_in_bar's included.
+ * schedule_bar_sum [16]: the schedule_bar rows as they are (or would be) stored - the `_in` rows included - summed over the batch
+ * WITHOUT atomics, in an order that depends on n alone: the result is bit-reproducible and the same with and without the rows.  With
+ * B = min(ceil(n / 64), 1024) and every sum starting from 0.0:
+ *   1. partial[b], b < B: for r = 0, 1, ... while (b + r B) 64 < n, for j = 0 .. 63 while i = (b + r B) 64 + j < n: partial[b] += row[i]
+ *   2. group[w], w < 16: for p = w, w + 16, w + 32, ... < B: group[w] += partial[p]
+ *   3. schedule_bar_sum = (..((group[0] + group[1]) + group[2]) .. + group[15])
+ * entry by entry.  A flagged robot makes the sum NaN.  It is allowed with a per-robot schedule too: it is then the sum of the rows,
+ * nothing more.  The partials live in a buffer of the handle: two calls that ask for the sum must not overlap on different streams.
+ * All pointers are DEVICE pointers. */
+typedef struct qc_com_reference_adjoint_io {
+  size_t struct_size;            /* = sizeof(qc_com_reference_adjoint_io); checked                               */
+  const double* schedule;        /* as the forward call's                                                        */
+  int32_t schedule_shared;
+  int32_t mode;
+  double gain;
+  const double* x_d_out_bar;     /* [n][3] the cotangent; required                                               */
+  const double* feet_bar_in;     /* [n][4][3] added to the output of that name; each optional                    */
+  const double* Rwb_bar_in;      /* [n][9]                                                                       */
+  const double* x_bar_in;        /* [n][3]                                                                       */
+  const double* phase_bar_in;    /* [n][4]                                                                       */
+  const double* schedule_bar_in; /* [n][4][4]                                                                    */
+  double* x_d_in_bar;            /* [n][3] OUT: each optional, at least one given (flags counts); may be x_d_out_bar */
+  double* feet_bar;              /* [n][4][3], body frame                                                        */
+  double* Rwb_bar;               /* [n][9]                                                                       */
+  double* x_bar;                 /* [n][3]                                                                       */
+  double* phase_bar;             /* [n][4]                                                                       */
+  double* schedule_bar;          /* [n][4][4]                                                                    */
+  double* schedule_bar_sum;      /* [16]: the rows summed over the batch in the fixed order above                */
+  int32_t* flags;                /* [n]: bit l - leg l's point is 0/0, no gradient                               */
+} qc_com_reference_adjoint_io;
+/* struct_size set, mode = QC_COM_REPLACE, gain = 1, the rest zero. */
+void qc_default_com_reference_adjoint(qc_com_reference_adjoint_io* io);
+/* Asynchronous on `stream`, no host synchronisation (graph-capturable); n == 0 launches nothing, writes nothing (schedule_bar_sum
+ * is left as it is) and returns QC_OK.  QC_ERR_INVALID (message starting with "qc_com_reference_adjoint_batch:", nothing
+ * launched) for a null handle, `in` or `io`, a wrong struct_size, a gait_dt, swing_state, swing_pos or swing_vel in `in`, an
+ * unknown mode, a gain that is not finite, no output requested, a missing x_d_out_bar, schedule, gait_phase, feet / joint_q, Rwb or
+ * x, or n beyond one launch. */
+int qc_com_reference_adjoint_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_com_reference_adjoint_io* io, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -151,6 +151,20 @@ class QcSupportPolygonAdjointIo(C.Structure):
                                           "Rwb_bar", "x_bar", "phase_bar", "schedule_bar", "flags")]
 
 
+COM_MODES = {"replace": 0, "offset": 1}  # QC_COM_REPLACE, QC_COM_OFFSET
+
+
+class QcComReferenceIo(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("schedule", C.c_void_p), ("schedule_shared", C.c_int32), ("mode", C.c_int32), ("gain", C.c_double)] + \
+               [(k, C.c_void_p) for k in ("x_d_in", "x_d_out", "com_xy", "flags")]
+
+
+class QcComReferenceAdjointIo(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("schedule", C.c_void_p), ("schedule_shared", C.c_int32), ("mode", C.c_int32), ("gain", C.c_double)] + \
+               [(k, C.c_void_p) for k in ("x_d_out_bar", "feet_bar_in", "Rwb_bar_in", "x_bar_in", "phase_bar_in", "schedule_bar_in", "x_d_in_bar",
+                                          "feet_bar", "Rwb_bar", "x_bar", "phase_bar", "schedule_bar", "schedule_bar_sum", "flags")]
+
+
 PARAM_COUNT = 211  # QC_PARAM_COUNT: the doubles of QcParams, in its order
 
 
@@ -169,7 +183,8 @@ EXPORTS = ("qc_create_abi", "qc_destroy", "qc_control_batch", "qc_control_batch_
            "qc_default_leg_plant_adjoint", "qc_leg_plant_step_adjoint_batch", "qc_default_sensitivity_swing", "qc_sensitivity_swing_batch",
            "qc_default_swing_reference", "qc_swing_reference_batch", "qc_default_swing_reference_adjoint", "qc_swing_reference_adjoint_batch",
            "qc_default_commander_step", "qc_commander_step_batch", "qc_default_commander_step_adjoint", "qc_commander_step_adjoint_batch",
-           "qc_default_support_polygon", "qc_support_polygon_batch", "qc_default_support_polygon_adjoint", "qc_support_polygon_adjoint_batch")
+           "qc_default_support_polygon", "qc_support_polygon_batch", "qc_default_support_polygon_adjoint", "qc_support_polygon_adjoint_batch",
+           "qc_default_com_reference", "qc_com_reference_batch", "qc_default_com_reference_adjoint", "qc_com_reference_adjoint_batch")
 
 _lib = None
 
@@ -301,6 +316,14 @@ def load():
     lib.qc_default_support_polygon_adjoint.restype = None
     lib.qc_support_polygon_adjoint_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcBatchIn), C.POINTER(QcSupportPolygonAdjointIo), C.c_void_p]
     lib.qc_support_polygon_adjoint_batch.restype = C.c_int
+    lib.qc_default_com_reference.argtypes = [C.POINTER(QcComReferenceIo)]
+    lib.qc_default_com_reference.restype = None
+    lib.qc_com_reference_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcBatchIn), C.POINTER(QcComReferenceIo), C.c_void_p]
+    lib.qc_com_reference_batch.restype = C.c_int
+    lib.qc_default_com_reference_adjoint.argtypes = [C.POINTER(QcComReferenceAdjointIo)]
+    lib.qc_default_com_reference_adjoint.restype = None
+    lib.qc_com_reference_adjoint_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcBatchIn), C.POINTER(QcComReferenceAdjointIo), C.c_void_p]
+    lib.qc_com_reference_adjoint_batch.restype = C.c_int
     # the structures above are hand-written mirrors of the header: a library built from another revision is refused here,
     # before any of them crosses the boundary
     rc = lib.qc_check_abi(ABI_VERSION, C.sizeof(QcParams), C.sizeof(QcBatchIn), C.sizeof(QcBatchOut))

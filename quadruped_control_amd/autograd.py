@@ -26,7 +26,9 @@ rollout_gait_autograd() chains it with tick_autograd() and leg_plant_step_autogr
 rollout_tick() on a batch with swing_state and a running clock.
 
 support_polygon_autograd() is support_polygon_batch() - the desired COM x, y from the feet and the scheduled gait - its backward one
-qc_support_polygon_adjoint_batch call, and for joint_q the kinematics half of qc_sensitivity_kin_batch behind it."""
+qc_support_polygon_adjoint_batch call, and for joint_q the kinematics half of qc_sensitivity_kin_batch behind it.
+com_reference_autograd() is com_reference_batch() - the x_d of a step from that polygon - in the same way; rollout_gait_autograd() and
+rollout_commander_autograd() call it per step when given `lean`, so that a rollout has a gradient in the schedule of the lean."""
 from __future__ import annotations
 
 import torch
@@ -431,9 +433,13 @@ _ROLLOUT_GAIT_REFUSED = {"stance": "the gait clock makes the contact mask from g
                          "feet": "the tick reads joint_q (rollout_autograd() steps the bare rigid body on `feet`)"}
 
 
-def rollout_gait_autograd(ctl, batch, steps, dt, leg_inertia, gait_dt, act_tol=1e-7, warm=True, params=None, joint_gains=None):
+def rollout_gait_autograd(ctl, batch, steps, dt, leg_inertia, gait_dt, act_tol=1e-7, warm=True, params=None, joint_gains=None, lean=None):
     """BalanceController.rollout_gait_autograd (see there): `steps` times swing_reference_autograd() with the clock advancing,
-    tick_autograd() on its references and phases, leg_plant_step_autograd() with those phases; the swing record threaded through."""
+    tick_autograd() on its references and phases, leg_plant_step_autograd() with those phases; the swing record threaded through.
+    With `lean`, com_reference_autograd() in front of each step makes the x_d its tick tracks."""
+    lean = _lean("rollout_gait_autograd", lean, "replace")
+    if lean is not None and batch.get("x_d") is None:
+        raise ValueError("rollout_gait_autograd: lean needs batch['x_d'] (its z in replace mode, the base of the offset)")
     for k, why in _ROLLOUT_GAIT_REFUSED.items():
         if batch.get(k) is not None:
             raise ValueError(f"rollout_gait_autograd: the batch carries {k} - {why}")
@@ -456,6 +462,7 @@ def rollout_gait_autograd(ctl, batch, steps, dt, leg_inertia, gait_dt, act_tol=1
     out, active, planned = {}, None, None
     flags = torch.zeros((n,), dtype=torch.int32, device=dev) if steps else None
     for _ in range(steps):
+        x_d = None if lean is None else _lean_x_d(ctl, lean, cur, phase, duty, batch["x_d"])
         phase = phase.clone()  # this step's own phases: advanced in place by the references' clock, then read by the tick and the plant
         ref_in = dict({k: cur[k] for k in SWING_REFERENCE_DIFFERENTIABLE[:-2]}, gait_phase=phase, gait_dt=clock)
         if duty is not None:
@@ -469,6 +476,8 @@ def rollout_gait_autograd(ctl, batch, steps, dt, leg_inertia, gait_dt, act_tol=1
             kwargs.update(warm=active, want_active_set=True)
             active = res["active_set"]
         tick_in = dict(cur, gait_phase=phase, swing_pos=pos, swing_vel=vel)
+        if x_d is not None:
+            tick_in["x_d"] = x_d
         tau, grf, status = tick_autograd(ctl, tick_in, act_tol, params=params, joint_gains=joint_gains, **kwargs)
         new = leg_plant_step_autograd(ctl, cur, tau, dt, leg_inertia, gait_phase=phase, gait_duty=duty, flags=flags)
         cur = dict(cur, **dict(zip(names, new)))
@@ -551,11 +560,14 @@ def commander_step_autograd(ctl, batch, command, desired, Vb):
     return _CommanderStep.apply(ctl, rest, command["state"].detach(), batch["Rwb"], batch["x"], twist, Vb, *desired)
 
 
-def rollout_commander_autograd(ctl, batch, command, steps, dt, leg_inertia, gait_dt, act_tol=1e-7, warm=True, params=None, joint_gains=None):
+def rollout_commander_autograd(ctl, batch, command, steps, dt, leg_inertia, gait_dt, act_tol=1e-7, warm=True, params=None, joint_gains=None,
+                               lean=None):
     """BalanceController.rollout_commander_autograd (see there): `steps` times commander_step_autograd(), swing_reference_autograd()
     with the commander's xdot_d and the clock advancing, tick_autograd() on the commander's desired state, leg_plant_step_autograd();
-    the held command, the records' desired state and the swing record threaded through."""
+    the held command, the records' desired state and the swing record threaded through.  With `lean`, com_reference_autograd() leans
+    the commander's x_d for the tick alone."""
     who = "rollout_commander_autograd"
+    lean = _lean(who, lean, "offset")
     for k, why in _ROLLOUT_GAIT_REFUSED.items():
         if batch.get(k) is not None:
             raise ValueError(f"{who}: the batch carries {k} - {why}")
@@ -605,6 +617,8 @@ def rollout_commander_autograd(ctl, batch, command, steps, dt, leg_inertia, gait
         else:
             cmd = dict(scalars, state=cstate)
         *desired, Vb, cstate, _run, applied = commander_step_autograd(ctl, cur, cmd, desired, Vb)
+        # (the leaned value goes to the tick only: `desired` keeps the un-leaned integral, the lean never feeds back into twist tracking)
+        x_d = desired[1] if lean is None else _lean_x_d(ctl, lean, cur, phase, duty, desired[1])
         phase = phase.clone()  # this step's own phases: advanced in place by the references' clock, then read by the tick and the plant
         ref_in = dict({name: cur[name] for name in SWING_REFERENCE_DIFFERENTIABLE[:-2] if name != "xdot_d"}, xdot_d=desired[2], gait_phase=phase, gait_dt=clock)
         if duty is not None:
@@ -617,7 +631,7 @@ def rollout_commander_autograd(ctl, batch, command, steps, dt, leg_inertia, gait
             res["active_set"] = torch.zeros((n,), dtype=torch.int32, device=dev)
             kwargs.update(warm=active, want_active_set=True)
             active = res["active_set"]
-        tick_in = dict(cur, gait_phase=phase, swing_pos=pos, swing_vel=vel, Rwb_d=desired[0], x_d=desired[1], xdot_d=desired[2], w_d=desired[3])
+        tick_in = dict(cur, gait_phase=phase, swing_pos=pos, swing_vel=vel, Rwb_d=desired[0], x_d=x_d, xdot_d=desired[2], w_d=desired[3])
         tau, grf, status = tick_autograd(ctl, tick_in, act_tol, params=params, joint_gains=joint_gains, **kwargs)
         new = leg_plant_step_autograd(ctl, cur, tau, dt, leg_inertia, gait_phase=phase, gait_duty=duty, flags=flags)
         cur = dict(cur, **dict(zip(names, new)))
@@ -730,3 +744,76 @@ def support_polygon_autograd(ctl, batch, schedule, world=False):
     tensors = [batch.get(k) if taken[k] else None for k in SUPPORT_POLYGON_DIFFERENTIABLE[:-1]] + [schedule]
     detached = {k: (v.detach() if isinstance(v, torch.Tensor) else v) for k, v in batch.items() if k != "feet" or not kin}
     return _SupportPolygon.apply(ctl, detached, bool(world), *tensors)
+
+
+# ------------------------------------------------------------------ the desired COM of a step from the polygon
+COM_REFERENCE_DIFFERENTIABLE = ("x_d",) + SUPPORT_POLYGON_DIFFERENTIABLE
+_COM_REFERENCE_BAR = dict(_SUPPORT_POLYGON_BAR, x_d="x_d_in_bar")
+
+
+class _ComReference(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ctl, batch, mode, gain, *tensors):
+        x_d, schedule = tensors[0], tensors[-1]
+        res = ctl.com_reference_batch(batch, schedule, x_d.contiguous(), mode, gain)
+        ctx.ctl, ctx.mode, ctx.gain = ctl, mode, gain
+        ctx.rest = {k: batch[k] for k in ("stance", "gait_duty") if batch.get(k) is not None}
+        ctx.present = tuple(t is not None for t in tensors)
+        ctx.save_for_backward(*[t for t in tensors if t is not None])
+        return res["x_d"]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, x_d_bar):
+        names = COM_REFERENCE_DIFFERENTIABLE
+        given = iter(ctx.saved_tensors)
+        inputs = {k: (next(given) if there else None) for k, there in zip(names, ctx.present)}
+        need = dict(zip(names, ctx.needs_input_grad[4:]))
+        schedule = inputs["schedule"]
+        bar = dict(_COM_REFERENCE_BAR, schedule="schedule_bar_sum" if schedule.dim() == 2 else "schedule_bar")  # a shared block: the kernel's sum
+        want = tuple(dict.fromkeys(bar[k] for k in names if need[k]))
+        if not want:
+            return (None,) * (4 + len(names))
+        batch = dict(ctx.rest, **{k: v for k, v in inputs.items() if v is not None and k not in ("schedule", "x_d")})
+        ctl = ctx.ctl
+        s = ctl.com_reference_adjoint_batch(batch, schedule, x_d_bar.contiguous(), ctx.mode, ctx.gain, want=want)
+        grads = {k: s[bar[k]] for k in names if need[k] and k != "joint_q"}
+        if need["joint_q"]:  # J(q)^T feet_bar, leg by leg: the kinematics half of the fused tick's reverse pass (unmasked: every leg)
+            grads["joint_q"] = ctl.sensitivity_kinematics_batch({"joint_q": inputs["joint_q"]}, feet_bar=s["feet_bar"], want=("joint_q_bar",))["joint_q_bar"]
+        return (None, None, None, None, *[grads[k].view_as(inputs[k]) if need[k] else None for k in names])
+
+
+def com_reference_autograd(ctl, batch, schedule, x_d, mode="replace", gain=1.0):
+    """BalanceController.com_reference_autograd (see there): x_d of com_reference_batch(), differentiable in
+    COM_REFERENCE_DIFFERENTIABLE - `feet` where the batch has no joint_q, which the forward pass would read in its place."""
+    missing = [k for k in ("gait_phase", "Rwb", "x") if batch.get(k) is None]
+    if missing or (batch.get("feet") is None and batch.get("joint_q") is None):
+        raise ValueError(f"com_reference_autograd: the batch lacks {missing or 'both feet and joint_q'}")
+    if schedule is None or schedule.dtype != torch.float64:
+        raise ValueError("com_reference_autograd: schedule is a float64 [n,4,4] or [4,4] tensor")
+    if x_d is None or x_d.dtype != torch.float64 or x_d.dim() != 2 or x_d.shape[1] != 3:
+        raise ValueError("com_reference_autograd: x_d is a float64 [n,3] tensor")
+    kin = batch.get("joint_q") is not None
+    taken = {"feet": not kin, "joint_q": kin, "Rwb": True, "x": True, "gait_phase": True}
+    tensors = [x_d] + [batch.get(k) if taken[k] else None for k in SUPPORT_POLYGON_DIFFERENTIABLE[:-1]] + [schedule]
+    detached = {k: (v.detach() if isinstance(v, torch.Tensor) else v) for k, v in batch.items() if k != "feet" or not kin}
+    return _ComReference.apply(ctl, detached, mode, float(gain), *tensors)
+
+
+def _lean(who, lean, default_mode):
+    """the `lean` keyword of the rollouts -> (schedule, mode, gain), or None"""
+    if lean is None:
+        return None
+    unknown = [k for k in lean if k not in ("schedule", "mode", "gain")]
+    if unknown or lean.get("schedule") is None:
+        raise ValueError(f"{who}: lean is dict(schedule=..., mode=..., gain=...) with a schedule{f'; unknown {unknown}' if unknown else ''}")
+    mode, gain = lean.get("mode"), lean.get("gain")
+    return lean["schedule"], default_mode if mode is None else mode, 1.0 if gain is None else float(gain)
+
+
+def _lean_x_d(ctl, lean, cur, phase, duty, x_d):
+    """x_d of this step from the polygon: the state and the phases as the step finds them (before the clock advances), the phases detached"""
+    b = dict({k: cur[k] for k in ("joint_q", "Rwb", "x")}, gait_phase=phase.detach())
+    if duty is not None:
+        b["gait_duty"] = duty
+    return com_reference_autograd(ctl, b, lean[0], x_d, lean[1], lean[2])

@@ -32,6 +32,7 @@ _SENSITIVITY_SWING_WANT = ("swing_pos_bar", "swing_vel_bar", "joint_q_bar", "joi
 _SWING_REFERENCE_ADJOINT_WANT = ("Rwb_bar", "x_bar", "xdot_bar", "w_bar", "xdot_d_bar", "joint_q_bar", "p_start_bar", "p_final_bar")  # swing_reference_adjoint_batch's default
 _COMMANDER_STEP_ADJOINT_WANT = ("twist_bar", "Vb_bar", "Rwb_bar", "x_bar", "Rwb_d_prev_bar", "x_d_prev_bar", "xdot_d_prev_bar", "w_d_prev_bar")  # commander_step_adjoint_batch's default
 _SUPPORT_POLYGON_ADJOINT_WANT = ("feet_bar", "phase_bar", "schedule_bar")  # support_polygon_adjoint_batch's default
+_COM_REFERENCE_ADJOINT_WANT = ("x_d_in_bar", "feet_bar", "phase_bar", "schedule_bar")  # com_reference_adjoint_batch's default
 _LEG_PLANT_ADJOINT_WANT = ("Rwb_bar", "x_bar", "xdot_bar", "w_bar", "joint_q_bar", "joint_qdot_bar", "joint_tau_bar")  # leg_plant_step_adjoint's default
 
 
@@ -599,7 +600,7 @@ class BalanceController:
         self.plan_leg_plant(state, joint_tau, dt, leg_inertia, stance, gait_phase, gait_duty, cmd_state, foot_world, flags, stream)()
         return state
 
-    def rollout_tick(self, batch, command, steps, dt, leg_inertia, warm=True, record_every=None, stream=None, certify_every=None):
+    def rollout_tick(self, batch, command, steps, dt, leg_inertia, warm=True, record_every=None, stream=None, certify_every=None, lean=None):
         """Closed loop around the complete tick, on the device: `steps` times the tick, then leg_plant_step() under its joint_tau, on
         one stream and without a host round trip.  command = dict as for tick_batch(): commander mode (qc_tick_batch), `batch` as
         tick_batch() takes it; command = None: control_batch() with a host-held desired state, `batch` as control_batch() takes it
@@ -615,11 +616,17 @@ class BalanceController:
         gait_phase, swing_state, cmd_state) and rec["step"] the plant's foot_world and flags - device tensors, no synchronisation.
         certify_every=k (command = None only: the certificate reads the desired state from the batch, commander mode keeps it in the
         commander state) launches the KKT certificate after the tick of steps 0, k, 2k, ..., on the state and the phases as the tick
-        left them, and returns out["certificates"] = [(step, summary clone)]; None (the default) launches exactly what it always did."""
+        left them, and returns out["certificates"] = [(step, summary clone)]; None (the default) launches exactly what it always did.
+        lean = dict(schedule=..., mode="replace", gain=1.0) (command = None only): one com_reference_batch() launch per step in
+        front of the tick, planned once, on the state and the phases as the step finds them; it writes batch["x_d"] IN PLACE from a
+        copy taken at entry (the base: offset mode does not accumulate).  None (the default) launches exactly what it always did."""
         import torch
 
         if batch.get("joint_q") is None or batch.get("joint_qdot") is None:
             raise ValueError("rollout_tick: the batch carries joint_q and joint_qdot (rollout() steps the bare rigid body)")
+        if lean is not None and command is not None:
+            raise ValueError("rollout_tick: lean needs command=None - the fused qc_tick_batch keeps x_d inside the launch; "
+                             "rollout_commander_autograd(lean=...) leans a commander-mode rollout")
         if certify_every is not None and command is not None:
             raise ValueError("rollout_tick: certify_every needs command=None - the certificate is out of scope in commander mode "
                              "(its desired state lives in the commander state, not in the batch)")
@@ -655,11 +662,24 @@ class BalanceController:
                                    gait_duty=batch.get("gait_duty"), cmd_state=None if command is None else command["state"],
                                    foot_world=foot_world, flags=flags, stream=stream)
         history = [] if record_every else None
+        lean_x_d = None
+        if lean is not None:
+            from .autograd import _lean
+
+            schedule, mode, gain = _lean("rollout_tick", lean, "replace")
+            missing = [name for name in ("x_d", "gait_phase") if batch.get(name) is None]
+            if missing:
+                raise ValueError(f"rollout_tick: lean needs batch{missing}")
+            # (of the batch: what the polygon reads - the library refuses the clock and the planner's record)
+            reads = {name: batch[name] for name in ("joint_q", "Rwb", "x", "gait_phase", "stance", "gait_duty") if batch.get(name) is not None}
+            lean_x_d = self.plan_com_reference(reads, schedule, batch["x_d"].clone(), mode, gain, out={"x_d": batch["x_d"]}, stream=stream)[0]
         for k in range(steps):
             rec = None
             if history is not None and k % int(record_every) == 0:
                 rec = {name: batch[name].clone() for name in names}
                 history.append((k, rec))
+            if lean_x_d is not None:
+                lean_x_d()
             r.solve(k)
             if rec is not None:  # what the tick of this step left behind: its outputs and the state it advances
                 rec["tick"] = {name: out[name].clone() for name in ("grf_body", "status", "joint_tau")}
@@ -1174,7 +1194,88 @@ class BalanceController:
 
         return support_polygon_autograd(self, batch, schedule, world)
 
-    def rollout_gait_autograd(self, batch, steps, dt, leg_inertia, gait_dt, act_tol=1e-7, warm=True, params=None, joint_gains=None):
+    # ------------------------------------------- the desired COM of a step from the polygon, and its reverse pass
+    def _com_reference_io(self, who, io, batch, schedule, mode, gain, own):
+        """What the two COM-reference calls share on top of _support_polygon_batch (world mode): the mode and the gain."""
+        if mode not in _lib.COM_MODES:
+            raise ValueError(f"{who}: mode is one of {tuple(_lib.COM_MODES)}, not {mode!r}")
+        n, dev, bi = self._support_polygon_batch(who, batch, schedule, True, io, own)
+        io.mode, io.gain = _lib.COM_MODES[mode], float(gain)
+        return n, dev, bi
+
+    def plan_com_reference(self, batch, schedule, x_d, mode="replace", gain=1.0, want=("x_d",), out=None, stream=None):
+        """com_reference_batch() marshalled once: returns (launch, out), `launch()` being one qc_com_reference_batch call
+        (graph-capturable) on tensors that are read in place.  Planning launches nothing.  `out`: a dict of tensors to write into
+        instead of new ones (every name in `want`; "x_d" is always made) - out["x_d"] may be `x_d` itself.  A call the library
+        refuses raises ValueError with its message, from launch()."""
+        io = _lib.QcComReferenceIo()
+        self._lib.qc_default_com_reference(C.byref(io))
+        n, dev, bi = self._com_reference_io("com_reference", io, batch, schedule, mode, gain, [("x_d_in", x_d, 3)])
+        want = tuple(dict.fromkeys(("x_d",) + tuple(want)))
+        res = _outputs("com_reference", _COM_REFERENCE_OUTPUTS, want, out, n, dev, io)
+        io.x_d_out = res["x_d"].data_ptr()
+        args = (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
+        return self._launcher("qc_com_reference_batch", args, (batch, schedule, x_d, res, bi, io), ValueError), res
+
+    def com_reference_batch(self, batch, schedule, x_d, mode="replace", gain=1.0, want=("x_d",), out=None, stream=None):
+        """The desired COM position of a step from the virtual support polygon (qc_com_reference_batch, include/qc_balance.h;
+        INTEGRATION.md "Desired COM from the gait"): one launch in front of the tick.  `batch`, `schedule`: as support_polygon_batch()
+        takes them with world=True - gait_phase, joint_q or feet, Rwb, x, optionally stance / gait_duty; the same batches are refused.
+        `x_d` float64 [n,3].  mode="replace": x_d' = (com_xy, x_d.z), `gain` ignored; mode="offset": x_d' = x_d + gain (com_xy -
+        centroid_xy, 0), the centroid that of the same four world-frame points - all weights 1 leave x_d as it is, so a twist-tracked
+        x_d is leaned, not dragged to the feet.  `want`: "x_d" [n,3] (always), "com_xy" [n,2] (support_polygon_batch's, bit for bit),
+        "flags" int32 [n]; a flagged robot (the reference's 0/0) gets NaN in x and y.  out["x_d"] may be `x_d`.  Asynchronous on
+        `stream`, no synchronisation.  Returns the dict of device tensors; ValueError with the library's message for a call it refuses."""
+        launch, res = self.plan_com_reference(batch, schedule, x_d, mode, gain, want, out, stream)
+        launch()
+        return res
+
+    def plan_com_reference_adjoint(self, batch, schedule, x_d_bar, mode="replace", gain=1.0, want=_COM_REFERENCE_ADJOINT_WANT, out=None,
+                                   feet_bar_in=None, Rwb_bar_in=None, x_bar_in=None, phase_bar_in=None, schedule_bar_in=None, stream=None):
+        """com_reference_adjoint_batch() marshalled once: returns (launch, out), `launch()` being one qc_com_reference_adjoint_batch
+        call (graph-capturable; two kernels when "schedule_bar_sum" is asked for) on tensors that are read in place.  Planning
+        launches nothing.  `out`: a dict of tensors to write into instead of new ones (every name in `want`) - an output may be its
+        `_in` tensor, out["x_d_in_bar"] may be `x_d_bar`.  A call the library refuses raises ValueError with its message, from launch()."""
+        io = _lib.QcComReferenceAdjointIo()
+        self._lib.qc_default_com_reference_adjoint(C.byref(io))
+        own = [("x_d_out_bar", x_d_bar, 3), ("feet_bar_in", feet_bar_in, 12), ("Rwb_bar_in", Rwb_bar_in, 9), ("x_bar_in", x_bar_in, 3),
+               ("phase_bar_in", phase_bar_in, 4), ("schedule_bar_in", schedule_bar_in, 16)]
+        n, dev, bi = self._com_reference_io("com_reference_adjoint", io, batch, schedule, mode, gain, own)
+        rows = tuple(w for w in want if w != "schedule_bar_sum")
+        extra = [("schedule_bar_sum", (4, 4), "float64")] if "schedule_bar_sum" in want else []
+        res = _outputs("com_reference_adjoint", _COM_REFERENCE_ADJOINT_OUTPUTS, rows, out, n, dev, io, extra)
+        args = (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
+        keep = (batch, schedule, x_d_bar, feet_bar_in, Rwb_bar_in, x_bar_in, phase_bar_in, schedule_bar_in, res, bi, io)
+        return self._launcher("qc_com_reference_adjoint_batch", args, keep, ValueError), res
+
+    def com_reference_adjoint_batch(self, batch, schedule, x_d_bar, mode="replace", gain=1.0, want=_COM_REFERENCE_ADJOINT_WANT, out=None,
+                                    feet_bar_in=None, Rwb_bar_in=None, x_bar_in=None, phase_bar_in=None, schedule_bar_in=None, stream=None):
+        """The reverse pass of com_reference_batch() (qc_com_reference_adjoint_batch, include/qc_balance.h).  `batch`, `schedule`,
+        `mode`, `gain`: the forward call's - nothing was saved.  `x_d_bar` [n,3]: the cotangent on the forward call's x_d.  `want`:
+        any of "x_d_in_bar" [n,3] (replace: z only; offset: the cotangent itself), "feet_bar" [n,4,3] (BODY frame, what
+        sensitivity_kinematics_batch() carries on to joint_q_bar), "Rwb_bar" [n,9] (entrywise), "x_bar" [n,3], "phase_bar" [n,4],
+        "schedule_bar" [n,4,4] (per robot), "schedule_bar_sum" [4,4] - those rows summed over the batch by the kernel in a fixed order
+        that depends on n alone: bit-reproducible, the same with and without the rows - and "flags" int32 [n].  The five `_in`
+        tensors are added to the outputs of those names; each may be the output's own tensor.  `gain` gets no cotangent; the contact
+        mask is held.  A robot the forward rule flags gets NaN in every row and makes the sum NaN.  Two calls that ask for the sum
+        share a buffer of the handle: keep them on one stream.  Asynchronous on `stream`, no synchronisation.  Returns the dict of
+        device tensors; ValueError with the library's message for a call it refuses."""
+        launch, res = self.plan_com_reference_adjoint(batch, schedule, x_d_bar, mode, gain, want, out, feet_bar_in, Rwb_bar_in, x_bar_in,
+                                                      phase_bar_in, schedule_bar_in, stream)
+        launch()
+        return res
+
+    def com_reference_autograd(self, batch, schedule, x_d, mode="replace", gain=1.0):
+        """com_reference_batch() with a gradient: returns x_d' [n,3], differentiable in `x_d`, batch["feet"] - or batch["joint_q"],
+        through the kinematics adjoint -, batch["gait_phase"], batch["Rwb"] (entrywise), batch["x"] and `schedule` ([n,4,4], or [4,4]
+        shared: its gradient is then schedule_bar_sum, summed by the kernel in its fixed order, not by torch).  Backward is one
+        com_reference_adjoint_batch() call - two with joint_q - on the current stream, without host synchronisation.  `gain` and
+        `mode` get no gradient; the contact mask is held; a flagged robot gets NaN gradients.  There is no double backward."""
+        from .autograd import com_reference_autograd
+
+        return com_reference_autograd(self, batch, schedule, x_d, mode, gain)
+
+    def rollout_gait_autograd(self, batch, steps, dt, leg_inertia, gait_dt, act_tol=1e-7, warm=True, params=None, joint_gains=None, lean=None):
         """The functional twin of rollout_tick(batch, None, ...) for a batch with swing_state and a running clock: per step
         swing_reference_autograd() with the clock advancing by `gait_dt` (a number, or a float64 [n] tensor), tick_autograd() on the
         references it returned and the phases it left, leg_plant_step_autograd() with those same phases; the swing record and its
@@ -1185,10 +1286,15 @@ class BalanceController:
         `out` the joint_tau, grf_body, status (and active_set) of the LAST tick, "flags" (the last step's plant flags) and the final
         "gait_phase", "swing_state", "p_start", "p_final" and "planned".  With gait_dt = dt the forward values are rollout_tick(batch,
         None, ...)'s bit for bit.  The gradient is the one on every solve's active face, at every tick's clamp mask, with the clock, the
-        contact mask and the plan decisions held; `params` and `joint_gains` as tick_autograd()'s.  Memory grows with `steps`."""
+        contact mask and the plan decisions held; `params` and `joint_gains` as tick_autograd()'s.  Memory grows with `steps`.
+        lean = dict(schedule=..., mode="replace", gain=1.0): in front of each step com_reference_autograd() makes the x_d its tick
+        tracks from the virtual support polygon - the state and the phases as the step finds them, before the clock advances
+        (detached: the clock is held), batch["x_d"] as its x_d - so the rollout has a gradient in the schedule of the lean (a shared
+        [4,4] schedule: summed by the kernel), and the forward pass is rollout_tick(batch, None, ..., lean=lean)'s.  None (the
+        default) launches exactly what it always did."""
         from .autograd import rollout_gait_autograd
 
-        return rollout_gait_autograd(self, batch, steps, dt, leg_inertia, gait_dt, act_tol, warm, params, joint_gains)
+        return rollout_gait_autograd(self, batch, steps, dt, leg_inertia, gait_dt, act_tol, warm, params, joint_gains, lean)
 
     # ------------------------------------------- the commander step as a launch of its own, and its reverse pass
     def plan_commander_step(self, batch, command, want=_DESIRED, out=None, stream=None):
@@ -1270,7 +1376,8 @@ class BalanceController:
 
         return commander_step_autograd(self, batch, command, desired, Vb)
 
-    def rollout_commander_autograd(self, batch, command, steps, dt, leg_inertia, gait_dt, act_tol=1e-7, warm=True, params=None, joint_gains=None):
+    def rollout_commander_autograd(self, batch, command, steps, dt, leg_inertia, gait_dt, act_tol=1e-7, warm=True, params=None, joint_gains=None,
+                                   lean=None):
         """The functional twin of rollout_tick(batch, command, ...) - commander mode - for robots that stand and run: per step
         commander_step_autograd(), swing_reference_autograd() with the commander's xdot_d and the clock advancing by `gait_dt`,
         tick_autograd() on the commander's desired state, the references and the phases, leg_plant_step_autograd().  The held command,
@@ -1282,10 +1389,13 @@ class BalanceController:
         both set: before that the commander ignores the twist and the gradient is identically zero (the all-stance and held-clock rules
         of a robot that does not run yet stay with rollout_tick).  ValueError also for what rollout_gait_autograd() refuses and for
         Rwb_d / x_d / xdot_d / w_d in the batch.  Returns (state, out) as rollout_gait_autograd() does, plus out["cmd_state"], the final
-        records, and out["applied"]."""
+        records, and out["applied"].
+        lean = dict(schedule=..., mode="offset", gain=1.0): per step com_reference_autograd() on the commander step's x_d, the state
+        and the phases as the step finds them; the leaned value goes to the tick ONLY - the commander record keeps the un-leaned
+        integral, so the lean never feeds back into twist tracking.  None (the default) launches exactly what it always did."""
         from .autograd import rollout_commander_autograd
 
-        return rollout_commander_autograd(self, batch, command, steps, dt, leg_inertia, gait_dt, act_tol, warm, params, joint_gains)
+        return rollout_commander_autograd(self, batch, command, steps, dt, leg_inertia, gait_dt, act_tol, warm, params, joint_gains, lean)
 
     def tick_autograd(self, batch, act_tol=1e-7, flags=None, params=None, joint_gains=None, **control_kwargs):
         """The tick with swing references, with a gradient: returns (joint_tau, grf_body, status) of control_batch(batch,
@@ -1465,6 +1575,9 @@ _SUPPORT_POLYGON_OUTPUTS = {"com_xy": ((2,), "float64"), "weights": ((4,), "floa
 _SUPPORT_POLYGON_ADJOINT_OUTPUTS = {"feet_bar": ((4, 3), "float64"), "Rwb_bar": ((9,), "float64"), "x_bar": ((3,), "float64"),
                                     "phase_bar": ((4,), "float64"), "schedule_bar": ((4, 4), "float64"), "flags": ((), "int32")}
 
+
+_COM_REFERENCE_OUTPUTS = {"x_d": ((3,), "float64"), "com_xy": ((2,), "float64"), "flags": ((), "int32")}
+_COM_REFERENCE_ADJOINT_OUTPUTS = {"x_d_in_bar": ((3,), "float64"), **_SUPPORT_POLYGON_ADJOINT_OUTPUTS}
 
 # commander_step / commander_step_adjoint: what the two calls read of the batch
 _COMMANDER_STEP_FIELDS = (("Rwb", 9, "float64"), ("x", 3, "float64"))

@@ -1929,6 +1929,7 @@ struct qc_handle {
   bool has_last = false;
   hipStream_t stream = nullptr;
   qc::CertifySummary* certify_parts = nullptr;  // qc_certify_batch: one partial per workgroup of certify_kernel (CERTIFY_MAX_PARTIALS)
+  double* com_parts = nullptr;    // qc_com_reference_adjoint_batch: one partial of 16 doubles per workgroup (COM_SUM_MAX_BLOCKS)
   double* param_parts = nullptr;  // qc_sensitivity_param_batch: one partial of PARAM_COUNT doubles per workgroup (SENSITIVITY_PARAM_MAX_BLOCKS)
 };
 
@@ -2137,6 +2138,14 @@ int qc_create_abi(const qc_params* p, int device, qc_handle** out, int abi_versi
     delete h;
     return fail(QC_ERR_HIP, "qc_create: could not allocate the parameter cotangents' partial buffer");
   }
+  // ... and qc_com_reference_adjoint_batch's (128 KB)
+  if (hipMalloc((void**)&h->com_parts, sizeof(double) * 16 * qc::COM_SUM_MAX_BLOCKS) != hipSuccess) {
+    (void)hipFree(h->param_parts);
+    (void)hipFree(h->certify_parts);
+    (void)hipFree(h->d_params);
+    delete h;
+    return fail(QC_ERR_HIP, "qc_create: could not allocate the schedule cotangent's partial buffer");
+  }
   *out = h;
   return QC_OK;
 }
@@ -2172,6 +2181,7 @@ void qc_destroy(qc_handle* h) {
   if (h->d_params) (void)hipFree(h->d_params);
   if (h->certify_parts) (void)hipFree(h->certify_parts);
   if (h->param_parts) (void)hipFree(h->param_parts);
+  if (h->com_parts) (void)hipFree(h->com_parts);
   if (h->stage) (void)hipFree(h->stage);
   if (h->pin) (void)hipHostFree(h->pin);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -2466,6 +2476,49 @@ int qc_support_polygon_adjoint_batch(qc_handle* h, size_t n, const qc_batch_in* 
                                         io->phase_bar_in, io->schedule_bar_in, io->feet_bar, io->Rwb_bar, io->x_bar, io->phase_bar, io->schedule_bar,
                                         io->flags};
   qc::support_polygon_adjoint_kernel<<<dim3(qc::support_polygon_blocks(n)), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, a);
+  QC_HIP(hipGetLastError());
+  return QC_OK;
+}
+
+void qc_default_com_reference(qc_com_reference_io* io) {
+  if (!zeroed(io)) return;
+  io->mode = QC_COM_REPLACE;
+  io->gain = 1.0;
+}
+
+int qc_com_reference_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_com_reference_io* io, void* stream) {
+  if (const int rc = qc::check_com_reference_args(h, n, in, io); rc != QC_OK || n == 0) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  // (of `in`: the feet, the phases and the contact mask as it is now, the pose - nothing of it is written)
+  const qc::ComReferenceArgs a{in->feet, in->joint_q, in->gait_phase, in->stance, in->gait_duty, in->Rwb, in->x, io->schedule, io->schedule_shared != 0,
+                               io->x_d_in, io->mode, io->gain, io->x_d_out, io->com_xy, io->flags};
+  qc::com_reference_kernel<<<dim3(qc::com_reference_blocks(n, false)), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, a);
+  QC_HIP(hipGetLastError());
+  return QC_OK;
+}
+
+void qc_default_com_reference_adjoint(qc_com_reference_adjoint_io* io) {
+  if (!zeroed(io)) return;
+  io->mode = QC_COM_REPLACE;
+  io->gain = 1.0;
+}
+
+int qc_com_reference_adjoint_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_com_reference_adjoint_io* io, void* stream) {
+  if (const int rc = qc::check_com_reference_adjoint_args(h, n, in, io); rc != QC_OK || n == 0) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  const bool sum = io->schedule_bar_sum != nullptr;
+  const qc::ComReferenceAdjointArgs a{in->feet, in->joint_q, in->gait_phase, in->stance, in->gait_duty, in->Rwb, in->x, io->schedule,
+                                      io->schedule_shared != 0, io->mode, io->gain, io->x_d_out_bar, io->feet_bar_in, io->Rwb_bar_in, io->x_bar_in,
+                                      io->phase_bar_in, io->schedule_bar_in, io->x_d_in_bar, io->feet_bar, io->Rwb_bar, io->x_bar, io->phase_bar,
+                                      io->schedule_bar, sum ? h->com_parts : nullptr, io->flags};
+  const unsigned blocks = qc::com_reference_blocks(n, sum);
+  if (sum) {
+    qc::com_reference_adjoint_kernel<true><<<dim3(blocks), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, a);
+    QC_HIP(hipGetLastError());
+    qc::com_schedule_sum_kernel<<<dim3(1), dim3(qc::COM_SUM_FINISH_BLOCK), 0, (hipStream_t)stream>>>(h->com_parts, (int)blocks, io->schedule_bar_sum);
+  } else {
+    qc::com_reference_adjoint_kernel<false><<<dim3(blocks), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, a);
+  }
   QC_HIP(hipGetLastError());
   return QC_OK;
 }

@@ -22,6 +22,7 @@
 #include "qc_swing_reference.hpp"
 #include "qc_commander.hpp"
 #include "qc_support_polygon.hpp"
+#include "qc_com_reference.hpp"
 
 namespace qc {
 
@@ -829,5 +830,42 @@ inline int check_support_polygon_adjoint_args(const qc_handle* h, size_t n, cons
 
 // workgroups of the two kernels for n robots: one wave each, capped
 inline unsigned support_polygon_blocks(size_t n) { return capped_blocks(n, SENSITIVITY_BLOCK, SENSITIVITY_MAX_BLOCKS); }
+
+// ---------------------------------------------------------------- qc_com_reference_batch, qc_com_reference_adjoint_batch
+// The polygon's refusals (always world mode: Rwb and x are required), behind the call's own about its mode, gain and arrays.
+inline int check_com_reference_batch(const char* who, size_t n, const qc_batch_in* in, const char* own, const double* schedule) {
+  if (const int rc = check_support_polygon_batch(who, n, in, own, schedule, false); rc != QC_OK || n == 0) return rc;
+  if (!in->Rwb || !in->x) return fail(QC_ERR_INVALID, std::string(who) + ": Rwb and x are required (the polygon is that of Rwb p + x)");
+  return QC_OK;
+}
+inline const char* check_com_mode(int32_t mode, double gain) {
+  if (mode != COM_REPLACE && mode != COM_OFFSET) return ": mode must be QC_COM_REPLACE or QC_COM_OFFSET";
+  if (!std::isfinite(gain)) return ": gain must be finite";
+  return nullptr;
+}
+
+// The argument check of the COM reference: what is wrong with the call itself (message prefix "qc_com_reference_batch:").
+inline int check_com_reference_args(const qc_handle* h, size_t n, const qc_batch_in* in, const qc_com_reference_io* io) {
+  const char* who = "qc_com_reference_batch";
+  if (const int rc = check_io(who, h && in, io, "qc_com_reference_io", "qc_default_com_reference"); rc != QC_OK) return rc;
+  const char* own = check_com_mode(io->mode, io->gain);
+  if (!own && !io->x_d_out) own = ": x_d_out is required";
+  if (!own && n > 0 && !io->x_d_in) own = ": x_d_in is required";
+  return check_com_reference_batch(who, n, in, own, io->schedule);
+}
+
+// The argument check of its reverse pass (message prefix "qc_com_reference_adjoint_batch:").
+inline int check_com_reference_adjoint_args(const qc_handle* h, size_t n, const qc_batch_in* in, const qc_com_reference_adjoint_io* io) {
+  const char* who = "qc_com_reference_adjoint_batch";
+  if (const int rc = check_io(who, h && in, io, "qc_com_reference_adjoint_io", "qc_default_com_reference_adjoint"); rc != QC_OK) return rc;
+  const char* own = check_com_mode(io->mode, io->gain);
+  if (!own && !io->x_d_in_bar && !io->feet_bar && !io->Rwb_bar && !io->x_bar && !io->phase_bar && !io->schedule_bar && !io->schedule_bar_sum && !io->flags)
+    own = ": no output requested (x_d_in_bar, feet_bar, Rwb_bar, x_bar, phase_bar, schedule_bar, schedule_bar_sum, flags are all NULL)";
+  if (!own && n > 0 && !io->x_d_out_bar) own = ": x_d_out_bar is required";
+  return check_com_reference_batch(who, n, in, own, io->schedule);
+}
+
+// workgroups of the kernels for n robots: one wave each, capped - the reverse pass that sums at the partials of the handle's buffer
+inline unsigned com_reference_blocks(size_t n, bool sum) { return capped_blocks(n, SENSITIVITY_BLOCK, sum ? COM_SUM_MAX_BLOCKS : SENSITIVITY_MAX_BLOCKS); }
 
 }  // namespace qc
