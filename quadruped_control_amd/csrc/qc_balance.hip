@@ -89,6 +89,11 @@ struct Lane {
   static_assert(!kWord || FPL == 1, "foot_code() / set_foot_code() hold the one foot of the lane: `wset` has no second field to keep");
   // ... whose face coefficients and force bounds come from the lane's FaceConst (uniform form)
   static constexpr bool kArith = kWord && Eqp::kFaceArith;
+  // what the lane's tolerance carries on top of tol_d: the solve's scale factor, and for the kArith lanes, whose solve hands
+  // over HALF the gradient (eqp_diagw, pass 2), half of that.  Every multiplier test compares a multiple of g with
+  // tol_s x scale, so both sides are the parent's halved exactly and every decision is the same.  Whoever hands a lane a
+  // robot sets tol_s with the RECEIVING lane's kTol.
+  static constexpr double kTol = Eqp::kTolScale * (kArith ? 0.5 : 1.0);
   Wrench<FPL> Wr;
   Cube<FPL> C;
   double f[3 * FPL];
@@ -96,7 +101,7 @@ struct Lane {
   uint32_t stance;  // bits 0-3: LegState per foot, bit 8: non-finite input
   int foot0;        // first foot of this lane
   int status, iters;
-  double tol_s;  // relative multiplier tolerance of this robot (tol_d x Eqp::kTolScale), signed: + while it still has its polish release, - after
+  double tol_s;  // relative multiplier tolerance of this robot (tol_d x kTol), signed: + while it still has its polish release, - after
   bool have_f;  // (read only by a MIXED recalculation without RACE, which no kernel runs; yet dropping its stores reshuffles the registers of most kernels)
   // the last recalculation was this robot's KKT point and the robot was live: what a racing group votes with.  It stands for
   // `busy & done & status == QC_SOLVED` only where the caller passes its `busy` as `live` and votes right after iterate() - all
@@ -413,7 +418,7 @@ struct Lane {
       for (int k = 0; k < 3; k++) Wr.r[i][k] = sin[(IN_R + 3 * (foot0 + i) + k) * SP + slot];
     const unsigned long long fl = (unsigned long long)__double_as_longlong(sin[IN_FLAGS * SP + slot]);
     stance = (uint32_t)fl;
-    tol_s = Eqp::kTolScale * tol;
+    tol_s = kTol * tol;
     const uint32_t wv = (uint32_t)(fl >> 32);
     idx = __double_as_longlong(sin[IN_IDX * SP + slot]);
     const bool use_warm = (wv & 0x80000000u) != 0;
@@ -452,7 +457,7 @@ struct Lane {
 #pragma unroll
       for (int k = 0; k < 3; k++) Wr.r[i][k] = W.r[i][k];
     stance = st;
-    tol_s = Eqp::kTolScale * tol;
+    tol_s = kTol * tol;
     idx = robot;
     const bool use_warm = (wv & 0x80000000u) != 0;
 #pragma unroll
@@ -1054,7 +1059,7 @@ QC_DEV int repack_read(const DevParams* __restrict__ Pg, Lane4X& L4, Eqp4X& eqp4
   if constexpr (Lane4X::kArith) L4.set_face_const(*QC_PARAMS_HERE(Pg));
   L4.status = QC_MAX_ITER;
   {
-    const double tol = Eqp4X::kTolScale * QC_PARAMS_HERE(Pg)->tol_d;
+    const double tol = Lane4X::kTol * QC_PARAMS_HERE(Pg)->tol_d;
     L4.tol_s = ((uint32_t)fl & QC_POLISH_ONE) ? tol : -tol;
   }
   L4.have_f = true;
@@ -1776,7 +1781,7 @@ __global__ __launch_bounds__(128, 2) void balance_pair_kernel(const DevParams* _
     if constexpr (Lane4::kArith) L4.set_face_const(*QC_PARAMS_HERE(Pg));
     L4.status = QC_MAX_ITER;
     {
-      const double tol = Eqp4::kTolScale * QC_PARAMS_HERE(Pg)->tol_d;
+      const double tol = Lane4::kTol * QC_PARAMS_HERE(Pg)->tol_d;
       L4.tol_s = ((fl >> 8) & QC_POLISH_ONE) ? tol : -tol;
     }
     L4.have_f = true;

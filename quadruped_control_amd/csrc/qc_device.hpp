@@ -1413,7 +1413,8 @@ QC_DEV FootCoef foot_coef_arith(const PT& P, const FaceConst& c, int sx, int sy,
 
 // `stance` = 4-bit mask of the robot, `foot0` = first foot of this lane.
 // `lane_w`: the lane's foot weights (general form with lane groups; ignored otherwise).
-// ARITH (uniform form, one foot per lane): the face coefficients by arithmetic from the lane's FaceConst `fk`.
+// ARITH (uniform form, one foot per lane): the face coefficients by arithmetic from the lane's FaceConst `fk`, the SPD flag
+// from the pivots' minimum, and `g` is HALF the gradient (see pass 2).
 template <bool UNIFORM, int G, bool S, bool ARITH = false, class PT>
 QC_DEV bool eqp_diagw(const PT& P, const FootW (&lane_w)[4 / G], const Wrench<4 / G>& Wr, const Cube<4 / G>& C, uint32_t stance, int foot0,
                       double (&f)[12 / G], double (&g)[12 / G], double& vmax, const FaceConst* fk = nullptr) {
@@ -1491,7 +1492,13 @@ QC_DEV bool eqp_diagw(const PT& P, const FootW (&lane_w)[4 / G], const Wrench<4 
   // M = L D L^T (in place: unit lower L below the diagonal, 1/d_k on it).  No square roots: the pivot's
   // reciprocal is v_rcp_f64 + two Newton steps (5 dependent operations instead of the 7 of rsq + Newton), and
   // the triangular solves carry no scaling on their serial chain.
+  // "all six pivots > 0".  ARITH lanes (a lone wave pays the scalar mask arithmetic like any other instruction): the running
+  // minimum of the first five and two compares instead of six compares and five mask ANDs.  v_min_f64 drops a NaN operand, so
+  // the last pivot keeps a compare of its own: a NaN pivot k makes 1 / d_k NaN, L_rk = u_rk / d_k NaN for every row below and
+  // with it every later pivot, the last one included - a NaN anywhere fails `d_5 > 0` as it failed `d_k > 0`
+  // (tests/test_solve_block_cpu.py).
   bool ok = true;
+  double dmin = 0.0;
 #pragma unroll
   for (int k = 0; k < 6; k++) {
     double wk[6];  // w_m = L_km d_m
@@ -1502,7 +1509,13 @@ QC_DEV bool eqp_diagw(const PT& P, const FootW (&lane_w)[4 / G], const Wrench<4 
       M[MI(k, m)] = wk[m] * M[MI(m, m)]; // L_km
       d = __builtin_fma(-M[MI(k, m)], wk[m], d);
     }
-    ok = ok && (d > 0.0);
+    if constexpr (ARITH) {
+      if (k == 0) dmin = d;
+      else if (k < 5) dmin = min_nn(dmin, d);
+      else ok = (dmin > 0.0) & (d > 0.0);
+    } else {
+      ok = ok && (d > 0.0);
+    }
     M[MI(k, k)] = rcp_nr(d);
     // rows below: u_rk = M_rk - sum_m u_rm L_km (kept unscaled until row r becomes the pivot row)
 #pragma unroll
@@ -1563,9 +1576,18 @@ QC_DEV bool eqp_diagw(const PT& P, const FootW (&lane_w)[4 / G], const Wrench<4 
     double wx, wy, wz;
     if constexpr (UNIFORM) wx = wy = wz = P.w_u;
     else { wx = fwt.w[0]; wy = fwt.w[1]; wz = fwt.w[2]; }
-    g[3 * i] = 2.0 * __builtin_fma(wx, fx, ax);
-    g[3 * i + 1] = 2.0 * __builtin_fma(wy, fy, ay);
-    g[3 * i + 2] = 2.0 * __builtin_fma(wz, fz, az);
+    if constexpr (ARITH) {
+      // HALF the gradient: its only readers are the lane's sign and threshold tests, which scale exactly with it (products by
+      // -1 / 0 / +1, sums and one fma, all linear; the face tag sits in mantissa bits a power of two leaves alone), so the
+      // lane halves its tolerance instead (Lane::kTol) and the three doublings leave the chain
+      g[3 * i] = __builtin_fma(wx, fx, ax);
+      g[3 * i + 1] = __builtin_fma(wy, fy, ay);
+      g[3 * i + 2] = __builtin_fma(wz, fz, az);
+    } else {
+      g[3 * i] = 2.0 * __builtin_fma(wx, fx, ax);
+      g[3 * i + 1] = 2.0 * __builtin_fma(wy, fy, ay);
+      g[3 * i + 2] = 2.0 * __builtin_fma(wz, fz, az);
+    }
   }
   QC_CLK_PIN(f); QC_CLK_PIN(g);
   QC_CLK(6, 7);
@@ -1605,7 +1627,8 @@ struct EqpDiagW {
                     double (&g)[12 / GROUP]) {
     return eqp_diagw<UNIFORM, GROUP, kStrided>(P, lane_w, Wr, C, stance, foot0, f, g, gscale);
   }
-  // ... with the face coefficients by arithmetic (kFaceArith lanes, which keep the FaceConst of their foot)
+  // ... with the face coefficients by arithmetic (kFaceArith lanes, which keep the FaceConst of their foot); `g` comes back as
+  // half the gradient, which the lane's halved tolerance (Lane::kTol) answers
   template <class PT>
   QC_DEV bool solve_arith(const PT& P, const Wrench<4 / GROUP>& Wr, const Cube<4 / GROUP>& C, uint32_t stance, int foot0, double (&f)[12 / GROUP],
                           double (&g)[12 / GROUP], const FaceConst& fk) {
