@@ -27,6 +27,10 @@ SIZES = dict(SP.SIZES, x_d_in_bar=3)
 # mode), rounded up with a little headroom; that test asserts the measurement stays below, tests/test_gpu_com_reference.py derives the
 # device's bar (4 x) from it.
 C_FWD, C_REV = 0.4, 0.7
+# C_FWD_ODD / C_REV_ODD: the same measurement on the same draw at device_math_reference.ODD_KIN from joint_q (printed there: forward
+# 0.284 replace, 0.157 offset; reverse 0.567, feet_bar in replace mode) - inside C_FWD and C_REV, so the odd model's bars are the
+# default model's.
+C_FWD_ODD, C_REV_ODD = C_FWD, C_REV
 SUM_BLOCK, SUM_MAX_BLOCKS, SUM_GROUPS = 64, 1024, 16  # the wave, COM_SUM_MAX_BLOCKS and the finisher's groups
 
 

@@ -33,6 +33,9 @@ INS = tuple(k + "_in" for k in OUTPUTS)
 # and 0.640), rounded up with a little headroom; that test asserts the measurement stays below, tests/test_gpu_support_polygon.py
 # derives the device's bar (4 x) from it.
 C_FWD, C_REV = 0.4, 0.8
+# C_FWD_ODD / C_REV_ODD: the same measurement on the same draw at device_math_reference.ODD_KIN from joint_q (printed there: forward
+# 0.150 body, 0.284 world; reverse 0.590, feet_bar) - inside C_FWD and C_REV, so the odd model's bars are the default model's.
+C_FWD_ODD, C_REV_ODD = C_FWD, C_REV
 TROT_OFFSETS, TROT_DUTY = (0.0, 0.5, 0.5, 0.0), 0.5
 # the test_node.cpp:41-57 vector, legs in this module's order
 NODE_SCHEDULE = np.array([[0.0, 0.5, 0.5, 1.0], [0.5, 1.0, 0.0, 0.5], [0.5, 1.0, 0.0, 0.5], [0.0, 0.5, 0.5, 1.0]])

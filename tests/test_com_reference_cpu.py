@@ -13,7 +13,7 @@ import pytest
 
 from tests import com_reference_restatement as CR
 from tests import support_polygon_restatement as SP
-from tests.device_math_reference import EPS
+from tests.device_math_reference import DEFAULT_KIN, EPS, ODD_KIN
 
 N = 24
 GAIN = 0.7
@@ -27,23 +27,41 @@ def drawn():
 
 
 @pytest.mark.parametrize("mode", CR.MODES)
-@pytest.mark.parametrize("kin", [False, True])
-def test_float64_agrees_with_50_digits(drawn, mode, kin):
-    """the measurement behind CR.C_FWD and CR.C_REV"""
+@pytest.mark.parametrize("kin,model", [pytest.param(False, DEFAULT_KIN, id="False"), pytest.param(True, DEFAULT_KIN, id="True"),
+                                       pytest.param(True, ODD_KIN, id="odd")])
+def test_float64_agrees_with_50_digits(drawn, mode, kin, model):
+    """the measurement behind CR.C_FWD and CR.C_REV (the library's model, both input forms) and CR.C_FWD_ODD / C_REV_ODD (ODD_KIN, joint_q)"""
     b, sched, bar, x_d = drawn
     b = {k: v for k, v in b.items() if k != ("feet" if kin else "joint_q")}
-    f = CR.reference_np(b, sched, x_d, mode, GAIN)
-    ref, cond = CR.reference_mp(b, sched, x_d, mode, GAIN)
+    c_fwd, c_rev = (CR.C_FWD_ODD, CR.C_REV_ODD) if model is ODD_KIN else (CR.C_FWD, CR.C_REV)
+    f = CR.reference_np(b, sched, x_d, mode, GAIN, kin=model)
+    ref, cond = CR.reference_mp(b, sched, x_d, mode, GAIN, kin=model)
     assert not f["flags"].any() and not ref["flags"].any()
     r = SP.worst_ratio(f["x_d"], ref["x_d"], cond["x_d"])
-    print(f"forward mode={mode} kin={kin}: {r:.3f} EPS x condition sum")
-    assert r <= CR.C_FWD and np.array_equal(f["x_d"][:, 2], x_d[:, 2])
-    g, _ = CR.reference_adjoint_np(b, sched, bar, mode, GAIN)
-    gref, gcond, _ = CR.reference_adjoint_mp(b, sched, bar, mode, GAIN)
+    print(f"forward mode={mode} kin={kin} model={model.name}: {r:.3f} EPS x condition sum")
+    assert r <= c_fwd and np.array_equal(f["x_d"][:, 2], x_d[:, 2])
+    g, _ = CR.reference_adjoint_np(b, sched, bar, mode, GAIN, kin=model)
+    gref, gcond, _ = CR.reference_adjoint_mp(b, sched, bar, mode, GAIN, kin=model)
     for k in CR.OUTPUTS:
         r = SP.worst_ratio(g[k], gref[k], gcond[k])
-        print(f"reverse {k} mode={mode} kin={kin}: {r:.3f} EPS x condition sum")
-        assert r <= CR.C_REV
+        print(f"reverse {k} mode={mode} kin={kin} model={model.name}: {r:.3f} EPS x condition sum")
+        assert r <= c_rev
+
+
+@pytest.mark.parametrize("mode", CR.MODES)
+def test_the_odd_model_moves_every_robot(mode):
+    """x_d from joint_q at ODD_KIN against x_d at the library's model, over the first 65 robots of the GPU tests' draw: every robot moves
+    by far more than the device's bar (4 C_FWD_ODD EPS x condition sum) - a kernel that ignored the handle's model cannot pass the GPU
+    tests at ODD_KIN.  (In offset mode only gain x (com - centroid) moves, a smaller step than the polygon's own.)"""
+    b, sched = SP.pool(257, seed=61, saturating=16)
+    b, sched = {k: v[:65] for k, v in b.items() if k != "feet"}, sched[:65]
+    x_d = np.random.default_rng(79).uniform(-1.0, 1.0, (65, 3))
+    odd, cond = CR.reference_mp(b, sched, x_d, mode, GAIN, kin=ODD_KIN)
+    plain = CR.reference_np(b, sched, x_d, mode, GAIN)
+    moved = np.abs(odd["x_d"] - plain["x_d"])[:, :2].max(axis=1)
+    bar = 4.0 * CR.C_FWD_ODD * EPS * cond["x_d"][:, :2].max(axis=1)
+    print(f"mode={mode}: x_d moves by {moved.min():.2e} ... {moved.max():.2e} m; the device's bar is at most {bar.max():.2e} m")
+    assert not odd["flags"].any() and (moved > 1e6 * bar).all()
 
 
 def test_replace_is_the_polygon_and_zero_gain_is_the_input(drawn):

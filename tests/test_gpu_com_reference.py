@@ -1,6 +1,8 @@
 """-m gpu: qc_com_reference_batch and qc_com_reference_adjoint_batch on the device - the identities of the two modes with
 qc_support_polygon_batch, both passes against the 50-digit restatement (tests/com_reference_restatement.py), schedule_bar_sum against
-its documented order, aliasing, the 0/0 robot, the refusals, com_reference_autograd, and the `lean` keyword of the three rollouts."""
+its documented order, aliasing, the 0/0 robot, the refusals, com_reference_autograd, and the `lean` keyword of the three rollouts; both
+passes on a handle at ODD_KIN (every combination of input form, schedule sharing and mode once), and the second round of the grid
+stride of the forward kernel in both modes and of the non-summing reverse pass."""
 import numpy as np
 import pytest
 
@@ -8,6 +10,8 @@ from tests import com_reference_restatement as CR
 from tests import leg_plant_adjoint_restatement as LA
 from tests import support_polygon_restatement as SP
 from tests import swing_reference_restatement as SR
+from tests.device_math_reference import ODD_KIN
+from tests.gpu_arrays import PERIOD, SECOND_ROUND_N, UNPLANTED, second_round, sentinel_tensor
 from tests.solved_batch_support import params, q  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -17,6 +21,11 @@ K_FWD, K_REV = 4.0 * CR.C_FWD, 4.0 * CR.C_REV  # the device's bars: 4 x the floa
 GAIN = 0.7
 # (input form, shared schedule, mode) -> the robots the 50-digit passes are made for
 COMBOS = {("feet", False, "replace"): 257, ("joint_q", True, "offset"): 257, ("feet", True, "offset"): 65, ("joint_q", False, "replace"): 65}
+# at ODD_KIN: 4 x the constants measured there (tests/test_com_reference_cpu.py), and every combination once - the two joint_q ones of
+# COMBOS to 257
+K_FWD_ODD, K_REV_ODD = 4.0 * CR.C_FWD_ODD, 4.0 * CR.C_REV_ODD
+ODD_COMBOS = {(form, shared, mode): 257 if (form, shared, mode) in (("joint_q", True, "offset"), ("joint_q", False, "replace")) else 65
+              for form in ("feet", "joint_q") for shared in (False, True) for mode in CR.MODES}
 ROWS = CR.OUTPUTS + ("flags",)
 
 
@@ -24,6 +33,16 @@ ROWS = CR.OUTPUTS + ("flags",)
 def ctl(q):
     c = q.BalanceController.from_params(params(q, "uniform"), device=0)
     c.set_gait(0.3, 0.3)  # duty 0.5 exactly: the draw's trot
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def odd_ctl(q):
+    """a handle of this module's own at ODD_KIN (`ctl` keeps the library's model)"""
+    c = q.BalanceController.from_params(params(q, "uniform"), device=0)
+    c.set_kinematics(**ODD_KIN.handle_arguments())
+    c.set_gait(0.3, 0.3)
     yield c
     c.close()
 
@@ -55,6 +74,21 @@ def reference():
         bb, s = _batch(b, form, n), (out["shared"] if shared else sched[:n])
         fwd, fcond = CR.reference_mp(bb, s, x_d[:n], mode, GAIN)
         rev, rcond, flags = CR.reference_adjoint_mp(bb, s, bar[:n], mode, GAIN, **{k: v[:n] for k, v in ins.items()})
+        assert not flags.any() and not fwd["flags"].any()
+        out[(form, shared, mode)] = dict(fwd=fwd, fcond=fcond, rev=rev, rcond=rcond)
+    return out
+
+
+@pytest.fixture(scope="module")
+def odd_reference(reference):
+    """the same draw, x_d, cotangent and accumulators (the pool's feet are drawn, not derived from its joint angles: nothing to rebuild)
+    and the 50-digit passes at ODD_KIN, once per combination of ODD_COMBOS; never changed"""
+    c = reference
+    out = {k: c[k] for k in ("b", "sched", "bar", "x_d", "ins", "shared")}
+    for (form, shared, mode), n in ODD_COMBOS.items():
+        bb, s = _batch(c["b"], form, n), (c["shared"] if shared else c["sched"][:n])
+        fwd, fcond = CR.reference_mp(bb, s, c["x_d"][:n], mode, GAIN, kin=ODD_KIN)
+        rev, rcond, flags = CR.reference_adjoint_mp(bb, s, c["bar"][:n], mode, GAIN, kin=ODD_KIN, **{k: v[:n] for k, v in c["ins"].items()})
         assert not flags.any() and not fwd["flags"].any()
         out[(form, shared, mode)] = dict(fwd=fwd, fcond=fcond, rev=rev, rcond=rcond)
     return out
@@ -92,16 +126,27 @@ def test_identities_with_the_polygon(ctl, reference, n):
             assert not np.array_equal(lean["x_d"][:, :2], reference["x_d"][:n, :2]) and np.array_equal(lean["x_d"][:, 2], reference["x_d"][:n, 2])
 
 
-@pytest.mark.parametrize("n", SIZES)
-def test_forward_against_50_digits(ctl, reference, n):
-    for combo, most in COMBOS.items():
+def _forward_against_50_digits(ctl, reference, n, combos, bar):
+    for combo, most in combos.items():
         if n > most:
             continue
         got, ref = _forward(ctl, reference, combo, n)[0], reference[combo]
         assert not got["flags"].any()
         r = SP.worst_ratio(got["x_d"], ref["fwd"]["x_d"][:n], ref["fcond"]["x_d"][:n])
-        print(f"n={n} {combo} x_d: {r:.3f} EPS x condition sum (bar {K_FWD})")
-        assert r <= K_FWD, (combo, r)
+        print(f"n={n} {combo} x_d: {r:.3f} EPS x condition sum (bar {bar})")
+        assert r <= bar, (combo, r)
+
+
+@pytest.mark.parametrize("n", SIZES)
+def test_forward_against_50_digits(ctl, reference, n):
+    _forward_against_50_digits(ctl, reference, n, COMBOS, K_FWD)
+
+
+@pytest.mark.parametrize("n", (65, 257))
+def test_forward_at_the_odd_model(odd_ctl, odd_reference, n):
+    """the handle at ODD_KIN against the 50-digit restatement under ODD_KIN: at n = 65 all eight combinations of (input form, schedule
+    sharing, mode), at 257 joint_q in both modes"""
+    _forward_against_50_digits(odd_ctl, odd_reference, n, ODD_COMBOS, K_FWD_ODD)
 
 
 # ------------------------------------------------------------------ reverse
@@ -116,17 +161,28 @@ def _reverse(ctl, c, combo, n, want=ROWS, out=None, ins=True, bar=None):
     return {k: v.cpu().numpy().reshape((n, -1) if k != "schedule_bar_sum" else (16,)) for k, v in r.items()}
 
 
-@pytest.mark.parametrize("n", SIZES)
-def test_reverse_pass_against_50_digits(ctl, reference, n):
-    for combo, most in COMBOS.items():
+def _reverse_pass_against_50_digits(ctl, reference, n, combos, bar):
+    for combo, most in combos.items():
         if n > most:
             continue
         got, ref = _reverse(ctl, reference, combo, n), reference[combo]
         assert not got["flags"].any()
         for k in CR.OUTPUTS:
             r = SP.worst_ratio(got[k], ref["rev"][k][:n], ref["rcond"][k][:n])
-            print(f"n={n} {combo} {k}: {r:.3f} EPS x condition sum (bar {K_REV})")
-            assert r <= K_REV, (combo, k, r)
+            print(f"n={n} {combo} {k}: {r:.3f} EPS x condition sum (bar {bar})")
+            assert r <= bar, (combo, k, r)
+
+
+@pytest.mark.parametrize("n", SIZES)
+def test_reverse_pass_against_50_digits(ctl, reference, n):
+    _reverse_pass_against_50_digits(ctl, reference, n, COMBOS, K_REV)
+
+
+@pytest.mark.parametrize("n", (65, 257))
+def test_reverse_pass_at_the_odd_model(odd_ctl, odd_reference, n):
+    """the reverse pass on the handle at ODD_KIN with every accumulator, as test_forward_at_the_odd_model: Rwb_bar reads the body-frame
+    feet of the model's forward kinematics again"""
+    _reverse_pass_against_50_digits(odd_ctl, odd_reference, n, ODD_COMBOS, K_REV_ODD)
 
 
 def test_outputs_over_their_inputs(ctl, reference):
@@ -146,6 +202,77 @@ def test_outputs_over_their_inputs(ctl, reference):
     x_d = _cuda(reference["x_d"][:n])
     ctl.com_reference_batch(dev, _sched(reference, True, n), x_d, "offset", GAIN, out={"x_d": x_d})
     assert np.array_equal(x_d.cpu().numpy(), fwd["x_d"])
+
+
+# ------------------------------------------------------------------ the second round of the grid stride
+ZERO_AT, OUTSIDE = 77, (200, 201)  # the period's 0/0 robot; the two robots of the draw that are planted after the tiling
+BATCH_KEYS = ("joint_q", "gait_phase", "Rwb", "x")
+
+
+def _second_round_rows(c, names):
+    """(the period, the outside robots) as device rows: the first PERIOD robots of the draw - joint_q, a schedule per robot, x_d, the
+    cotangent and every accumulator - with the 0/0 robot of test_a_flagged_robot at ZERO_AT (the phase rule makes its stance bytes);
+    asserted to hold it, stance and swing legs on every leg, and the saturating family"""
+    rows = dict(_batch(c["b"], "joint_q", 257), schedule=c["sched"], x_d=c["x_d"], x_d_bar=c["bar"], **c["ins"])
+    rows = {k: rows[k].copy() for k in names}
+    rows["gait_phase"][ZERO_AT], rows["schedule"][ZERO_AT] = [0.2, 0.75, 0.75, 0.75], 0.0
+    mask = np.array([[SP.in_stance(float(p), SP.TROT_DUTY) for p in row] for row in rows["gait_phase"][:PERIOD]])
+    assert mask[ZERO_AT].tolist() == [True, False, False, False] and mask.any(axis=0).all() and (~mask).any(axis=0).all()
+    assert all(rows["schedule"][16 * j].max() <= 1e-3 for j in range(9)) and (rows["schedule"][:PERIOD].min(axis=(1, 2)) >= 0.05).sum() > 100
+    assert max(OUTSIDE) < 257 and min(OUTSIDE) >= PERIOD
+    return {k: _cuda(v[:PERIOD]) for k, v in rows.items()}, {k: _cuda(v[list(OUTSIDE)]) for k, v in rows.items()}
+
+
+def _second_round_forward(odd_ctl, reference, mode):
+    """com_reference_kernel at n = 4096 x 64 + 65 = 262 209 robots on the handle at ODD_KIN, replace mode and offset mode at gain 0.7:
+    the grid is capped at 4096 one-wave workgroups, so workgroup 0 walks a full second round and workgroup 1 has one live lane and 63
+    tail lanes in its second.  The batch is the period of _second_round_rows tiled on the device, with robots 262 149 and n - 1
+    replaced by two robots from outside the period.  x_d, com_xy and flags, each starting from its sentinel, equal the n = 130 launch
+    tiled (the two replaced robots: an n = 2 launch of theirs) bit for bit - the 0/0 robot's NaN x, y and bit 3 in every copy."""
+    import torch
+
+    def launch(rows, m, over=False):
+        out = {"x_d": sentinel_tensor((m, 3), torch.float64), "com_xy": sentinel_tensor((m, 2), torch.float64), "flags": sentinel_tensor((m,), torch.int32)}
+        odd_ctl.com_reference_batch({k: rows[k] for k in BATCH_KEYS}, rows["schedule"], rows["x_d"], mode, GAIN, want=tuple(out), out=out)
+        return out
+
+    assert UNPLANTED == (4096 * 64 + 5, SECOND_ROUND_N - 1) and GAIN != 1.0
+    period, outside = _second_round_rows(reference, BATCH_KEYS + ("schedule", "x_d"))
+    small = second_round(launch, period, outside)
+    flags = small["flags"].cpu().numpy()
+    assert flags[ZERO_AT] == 1 << 3 and np.flatnonzero(flags).tolist() == [ZERO_AT]
+    assert bool(torch.isnan(small["x_d"][ZERO_AT, :2]).all()) and bool(small["x_d"][ZERO_AT, 2] == period["x_d"][ZERO_AT, 2])
+    torch.cuda.empty_cache()
+
+
+def _second_round_reverse(odd_ctl, reference, mode):
+    """com_reference_adjoint_kernel (the instantiation that does not sum; test_schedule_bar_sum takes the summing one past its own cap of
+    1024) at the same n on the same tiled period in offset mode, with every `_in` accumulator given (tiled too): every output and the
+    flags against the n = 130 launch tiled, the two replaced robots against their n = 2 launch; then once more at this n with every
+    output written over its `_in` array and x_d_in_bar over the cotangent: the bits of the first run."""
+    import torch
+
+    shape = {"feet_bar": (4, 3), "schedule_bar": (4, 4)}
+
+    def launch(rows, m, over=False):
+        acc = {k: (rows[k].clone() if over else rows[k]) for k in SP.INS}
+        bar = rows["x_d_bar"].clone() if over else rows["x_d_bar"]
+        out = {k: acc[k + "_in"].view((m,) + shape.get(k, (SP.SIZES[k],))) if over else sentinel_tensor((m, SP.SIZES[k]), torch.float64) for k in SP.OUTPUTS}
+        out.update(x_d_in_bar=bar if over else sentinel_tensor((m, 3), torch.float64), flags=sentinel_tensor((m,), torch.int32))
+        odd_ctl.com_reference_adjoint_batch({k: rows[k] for k in BATCH_KEYS}, rows["schedule"], bar, mode, GAIN, want=ROWS, out=out, **acc)
+        return {k: v.reshape(m, -1) if v.dim() > 1 else v for k, v in out.items()}
+
+    small = second_round(launch, *_second_round_rows(reference, BATCH_KEYS + ("schedule", "x_d_bar") + SP.INS), over=True)
+    flags = small["flags"].cpu().numpy()
+    assert flags[ZERO_AT] == 1 << 3 and np.flatnonzero(flags).tolist() == [ZERO_AT]
+    assert all(bool(torch.isnan(small[k][ZERO_AT]).all()) and bool(torch.isfinite(small[k][:ZERO_AT]).all()) for k in CR.OUTPUTS)
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("kernel,mode", [("forward", "replace"), ("forward", "offset"), ("reverse", "offset")])
+def test_second_round_of_the_grid_stride(odd_ctl, reference, kernel, mode):
+    """both kernels past their grid cap (SENSITIVITY_MAX_BLOCKS = 4096 workgroups of 64 robots): _second_round_forward, _second_round_reverse"""
+    {"forward": _second_round_forward, "reverse": _second_round_reverse}[kernel](odd_ctl, reference, mode)
 
 
 # ------------------------------------------------------------------ the sum

@@ -1,6 +1,7 @@
 """GPU tests of the commander step as a launch of its own and its reverse pass (qc_commander_step_batch,
 qc_commander_step_adjoint_batch), and of the commander rollout with a gradient in the command: identity with the tick, the reverse pass
-against 50 digits, aliasing, flags, refusals, rollout_commander_autograd against rollout_tick(batch, command, ...)."""
+against 50 digits, aliasing, flags, the second round of both kernels' grid stride, refusals, rollout_commander_autograd against
+rollout_tick(batch, command, ...)."""
 import ctypes
 
 import numpy as np
@@ -9,6 +10,7 @@ import pytest
 from tests import commander_adjoint_restatement as CA
 from tests import leg_plant_adjoint_restatement as LA
 from tests import swing_reference_restatement as SR
+from tests.gpu_arrays import PERIOD, SECOND_ROUND_N, UNPLANTED, second_round, sentinel_tensor
 from tests.solved_batch_support import SENTINEL, assert_raw_refusals, batch_in, params, q  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -226,6 +228,92 @@ def test_flagged_robots(q, ctl, reference):
     for k in CA.OUTPUTS:
         got, ref = res[k].cpu().numpy().reshape(n, -1), base[k].cpu().numpy().reshape(n, -1)
         assert np.isnan(got[lock[:2]]).all() and np.array_equal(got[others], ref[others]) and np.isfinite(got[lock[2]]).all(), k
+
+
+# ------------------------------------------------------------------ the second round of the grid stride
+OUTSIDE = (200, 201)  # the two robots of the pool that are planted after the tiling
+LOCK = np.array([0.0, 0.0, 1.0, 0.0, 1.0, 0.0, -1.0, 0.0, 0.0])  # test_flagged_robots' pitch = pi / 2
+
+
+def _second_round_rows(c, reverse):
+    """(the period, the outside robots, the gimbal-locked robots) as device rows: the first PERIOD robots of the pool - every kind of
+    CA.KINDS at least 11 times: not standing, latching, starting, a command applied from the twist and from the held one, idle, om = 0
+    exactly and either side of the small-angle branch, yaw at +-pi - with test_flagged_robots' three robots at gimbal lock (two with
+    a command applied, one without).  Forward: Rwb, x, the command and the records; reverse: the cotangents and accumulators too."""
+    applied = c["out"]["applied"][:PERIOD]
+    lock = [int(np.flatnonzero(applied)[1]), int(np.flatnonzero(applied)[7]), int(np.flatnonzero(applied == 0)[0])]
+    Rwb = c["Rwb"].copy()
+    Rwb[lock] = LOCK
+    rows = dict(Rwb=Rwb, x=c["x"], twist=c["twist"], fresh=c["fresh"], state=c["state"].view(np.uint8).reshape(257, -1))
+    if reverse:
+        rows.update(**{"cot_" + k: v for k, v in c["bars"].items()}, **c["ins"])
+    assert set(c["kinds"][:PERIOD]) == set(CA.KINDS) and PERIOD <= min(OUTSIDE) and max(OUTSIDE) < 257
+    assert applied.any() and (applied == 0).any() and c["out"]["run"][:PERIOD].any() and (c["out"]["run"][:PERIOD] == 0).any()
+    assert c["fresh"][:PERIOD].any() and (c["fresh"][:PERIOD] == 0).any() and (np.abs(c["twist"][:PERIOD, 3:6]).max(axis=1) == 0).any()
+    return {k: _cuda(v[:PERIOD]) for k, v in rows.items()}, {k: _cuda(v[list(OUTSIDE)]) for k, v in rows.items()}, lock
+
+
+def _second_round_forward(ctl, c):
+    """commander_step_kernel at n = 4096 x 64 + 65 = 262 209 robots: the grid is capped at 4096 one-wave workgroups, so workgroup 0
+    walks a full second round and workgroup 1 has one live lane and 63 tail lanes in its second.  The batch is the period of
+    _second_round_rows tiled on the device, with robots 262 149 and n - 1 replaced by two robots from outside the period.  The desired
+    state, run and applied, each starting from its sentinel, and the commander records the kernel updates in place - bytewise - equal
+    the n = 130 launch tiled (the two replaced robots: an n = 2 launch of theirs) bit for bit; run, applied and the records' flags of
+    the period are the float64 restatement's."""
+    import torch
+
+    def launch(rows, m, over=False):
+        state = rows["state"].clone()
+        out = {"Rwb_d": sentinel_tensor((m, 9), torch.float64), "x_d": sentinel_tensor((m, 3), torch.float64), "xdot_d": sentinel_tensor((m, 3), torch.float64),
+               "w_d": sentinel_tensor((m, 3), torch.float64), "run": sentinel_tensor((m,), torch.uint8), "applied": sentinel_tensor((m,), torch.uint8)}
+        ctl.commander_step_batch({"Rwb": rows["Rwb"], "x": rows["x"]}, {"twist": rows["twist"], "fresh": rows["fresh"], "state": state}, want=tuple(out), out=out)
+        return dict(out, state=state)
+
+    period, outside, _ = _second_round_rows(c, False)
+    small = second_round(launch, period, outside, in_place=("state",))
+    assert np.array_equal(small["run"].cpu().numpy(), c["out"]["run"][:PERIOD]) and np.array_equal(small["applied"].cpu().numpy(), c["out"]["applied"][:PERIOD])
+    rec, exp = small["state"].cpu().numpy().reshape(-1).view(CA.STATE_DTYPE), c["after"][:PERIOD]
+    assert all(np.array_equal(rec[k], exp[k]) for k in ("standing", "gait_running", "cmd_pending")) and not torch.equal(small["state"], period["state"])
+    torch.cuda.empty_cache()
+
+
+def _second_round_reverse(ctl, c):
+    """commander_step_adjoint_kernel at the same n on the same tiled period, with the five cotangents and both `_in` accumulators given
+    (tiled too): every output and the flags against the n = 130 launch tiled, the two replaced robots against their n = 2 launch; then
+    once more at this n with the outputs over the `_in` arrays and over the incoming cotangents, as test_aliasing_and_output_groups
+    places them: the bits of the first run.  The two robots with a command applied at gimbal lock are flagged (NaN rows), the third
+    and every other robot are not."""
+    import torch
+
+    def launch(rows, m, over=False):
+        take = (lambda t: t.clone()) if over else (lambda t: t)
+        bars = {k: take(rows["cot_" + k]) for k in CA.COTANGENTS}
+        ins = {k: take(rows[k]) for k in CA.INS}
+        if over:
+            out = {"Rwb_bar": ins["Rwb_bar_in"], "x_bar": ins["x_bar_in"], "Vb_bar": bars["Vb"], "Rwb_d_prev_bar": bars["Rwb_d"], "x_d_prev_bar": bars["x_d"],
+                   "xdot_d_prev_bar": bars["xdot_d"], "w_d_prev_bar": bars["w_d"], "twist_bar": sentinel_tensor((m, 6), torch.float64)}
+        else:
+            out = {k: sentinel_tensor((m, CA.SIZES[k]), torch.float64) for k in CA.OUTPUTS}
+        out["flags"] = sentinel_tensor((m,), torch.int32)
+        ctl.commander_step_adjoint_batch({"Rwb": rows["Rwb"], "x": rows["x"]}, {"twist": rows["twist"], "fresh": rows["fresh"]}, rows["state"], bars,
+                                         want=CA.OUTPUTS + ("flags",), out=out, **ins)
+        return out
+
+    period, outside, lock = _second_round_rows(c, True)
+    small = second_round(launch, period, outside, over=True)
+    flags = small["flags"].cpu().numpy()
+    assert flags[lock].tolist() == [1, 1, 0] and flags.sum() == 2
+    for k in CA.OUTPUTS:
+        got = small[k].cpu().numpy()
+        assert np.isnan(got[lock[:2]]).all() and np.isfinite(np.delete(got, lock[:2], axis=0)).all(), k
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("kernel", ["forward", "reverse"])
+def test_second_round_of_the_grid_stride(q, ctl, reference, kernel):
+    """both kernels past their grid cap (SENSITIVITY_MAX_BLOCKS = 4096 workgroups of 64 robots): _second_round_forward, _second_round_reverse"""
+    assert UNPLANTED == (4096 * 64 + 5, SECOND_ROUND_N - 1)
+    {"forward": _second_round_forward, "reverse": _second_round_reverse}[kernel](ctl, reference)
 
 
 def test_refusals_launch_nothing(q, ctl, reference):

@@ -1,7 +1,8 @@
 """-m gpu: erf_f64 and exp_neg_sq against 50-digit mpmath (tests/support_polygon_probe.py), qc_support_polygon_batch and
 qc_support_polygon_adjoint_batch against the 50-digit restatement (tests/support_polygon_restatement.py) - both input forms, body and
 world mode, shared and per-robot schedule, stance bytes and the phase rule -, the reference's own test vector, the 0/0 robot, aliasing,
-the chain into the kinematics adjoint, support_polygon_autograd against central differences, and the refusals."""
+the chain into the kinematics adjoint, support_polygon_autograd against central differences, and the refusals; both passes on a handle
+at ODD_KIN (every combination of input form, frame and schedule sharing once), and the second round of both kernels' grid stride."""
 import math
 
 import mpmath as mp
@@ -9,7 +10,8 @@ import numpy as np
 import pytest
 
 from tests import support_polygon_restatement as SP
-from tests.device_math_reference import DPS, EPS
+from tests.device_math_reference import DPS, EPS, ODD_KIN
+from tests.gpu_arrays import PERIOD, SECOND_ROUND_N, UNPLANTED, second_round, sentinel_tensor
 from tests.solved_batch_support import params, q  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -17,6 +19,11 @@ SIZES = (1, 63, 64, 65, 257)
 K_FWD, K_REV = 4.0 * SP.C_FWD, 4.0 * SP.C_REV  # the device's bars: 4 x the float64 restatement's own worst ratio (measured on the CPU)
 # (input form, world, shared schedule) -> the robots the 50-digit passes are made for: every combination up to the wave boundary, two to 257
 COMBOS = {("feet", False, False): 257, ("joint_q", True, True): 257, ("feet", True, True): 65, ("joint_q", False, False): 65}
+# at ODD_KIN: 4 x the constants measured there (tests/test_support_polygon_cpu.py), and every combination once - the two joint_q ones of
+# COMBOS, body and world frame, to 257
+K_FWD_ODD, K_REV_ODD = 4.0 * SP.C_FWD_ODD, 4.0 * SP.C_REV_ODD
+ODD_COMBOS = {(form, world, shared): 257 if (form, world, shared) in (("joint_q", True, True), ("joint_q", False, False)) else 65
+              for form in ("feet", "joint_q") for world in (False, True) for shared in (False, True)}
 
 
 @pytest.fixture(scope="module")
@@ -25,6 +32,21 @@ def ctl(q):
     c.set_gait(0.3, 0.3)  # duty 0.5 exactly: the draw's trot
     yield c
     c.close()
+
+
+@pytest.fixture(scope="module")
+def odd_ctl(q):
+    """a handle of this module's own at ODD_KIN (`ctl` keeps the library's model)"""
+    c = q.BalanceController.from_params(params(q, "uniform"), device=0)
+    c.set_kinematics(**ODD_KIN.handle_arguments())
+    c.set_gait(0.3, 0.3)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def handles(ctl, odd_ctl):
+    return {"default": ctl, "odd": odd_ctl}
 
 
 def _cuda(a):
@@ -56,6 +78,21 @@ def reference():
         bb, s = _batch(b, form, world, n), (out["shared"] if shared else sched[:n])
         fwd, fcond = SP.reference_mp(bb, s, world)
         rev, rcond, flags = SP.reference_adjoint_mp(bb, s, bar[:n], world, **{k: v[:n] for k, v in ins.items()})
+        assert not flags.any() and not fwd["flags"].any()
+        out[(form, world, shared)] = dict(fwd=fwd, fcond=fcond, rev=rev, rcond=rcond)
+    return out
+
+
+@pytest.fixture(scope="module")
+def odd_reference(reference):
+    """the same draw, cotangent and accumulators (the pool's feet are drawn, not derived from its joint angles: nothing to rebuild) and
+    the 50-digit passes at ODD_KIN, once per combination of ODD_COMBOS; never changed"""
+    c = reference
+    out = {k: c[k] for k in ("b", "sched", "bar", "ins", "shared")}
+    for (form, world, shared), n in ODD_COMBOS.items():
+        bb, s = _batch(c["b"], form, world, n), (c["shared"] if shared else c["sched"][:n])
+        fwd, fcond = SP.reference_mp(bb, s, world, kin=ODD_KIN)
+        rev, rcond, flags = SP.reference_adjoint_mp(bb, s, c["bar"][:n], world, kin=ODD_KIN, **{k: v[:n] for k, v in c["ins"].items()})
         assert not flags.any() and not fwd["flags"].any()
         out[(form, world, shared)] = dict(fwd=fwd, fcond=fcond, rev=rev, rcond=rcond)
     return out
@@ -148,17 +185,28 @@ def _forward(q, ctl, c, combo, n, want=("com_xy", "weights", "flags"), extra=Non
     return {k: v.cpu().numpy() for k, v in r.items()}
 
 
-@pytest.mark.parametrize("n", SIZES)
-def test_forward_against_50_digits(q, ctl, reference, n):
-    for combo, most in COMBOS.items():
+def _forward_against_50_digits(q, ctl, reference, n, combos, bar):
+    for combo, most in combos.items():
         if n > most:
             continue
         got, ref = _forward(q, ctl, reference, combo, n), reference[combo]
         assert not got["flags"].any()
         r = SP.worst_ratio(got["com_xy"], ref["fwd"]["com_xy"][:n], ref["fcond"]["com_xy"][:n])
-        print(f"n={n} {combo} com_xy: {r:.3f} EPS x condition sum (bar {K_FWD})")
-        assert r <= K_FWD, (combo, r)
+        print(f"n={n} {combo} com_xy: {r:.3f} EPS x condition sum (bar {bar})")
+        assert r <= bar, (combo, r)
         assert np.abs(got["weights"] - ref["fwd"]["weights"][:n]).max() <= 4 * EPS  # weights of order one: a few EPS absolute
+
+
+@pytest.mark.parametrize("n", SIZES)
+def test_forward_against_50_digits(q, ctl, reference, n):
+    _forward_against_50_digits(q, ctl, reference, n, COMBOS, K_FWD)
+
+
+@pytest.mark.parametrize("n", (65, 257))
+def test_forward_at_the_odd_model(q, odd_ctl, odd_reference, n):
+    """the handle at ODD_KIN against the 50-digit restatement under ODD_KIN: at n = 65 all eight combinations of (input form, frame,
+    schedule sharing), at 257 joint_q in the body frame and in the world frame"""
+    _forward_against_50_digits(q, odd_ctl, odd_reference, n, ODD_COMBOS, K_FWD_ODD)
 
 
 def test_stance_bytes_and_the_phase_rule(q, ctl, reference):
@@ -227,17 +275,28 @@ def _reverse(q, ctl, c, combo, n, out=None, ins=True):
     return {k: v.cpu().numpy().reshape(n, -1) for k, v in r.items()}
 
 
-@pytest.mark.parametrize("n", SIZES)
-def test_reverse_pass_against_50_digits(q, ctl, reference, n):
-    for combo, most in COMBOS.items():
+def _reverse_pass_against_50_digits(q, ctl, reference, n, combos, bar):
+    for combo, most in combos.items():
         if n > most:
             continue
         got, ref = _reverse(q, ctl, reference, combo, n), reference[combo]
         assert not got["flags"].any()
         for k in SP.OUTPUTS:
             r = SP.worst_ratio(got[k], ref["rev"][k][:n], ref["rcond"][k][:n])
-            print(f"n={n} {combo} {k}: {r:.3f} EPS x condition sum (bar {K_REV})")
-            assert r <= K_REV, (combo, k, r)
+            print(f"n={n} {combo} {k}: {r:.3f} EPS x condition sum (bar {bar})")
+            assert r <= bar, (combo, k, r)
+
+
+@pytest.mark.parametrize("n", SIZES)
+def test_reverse_pass_against_50_digits(q, ctl, reference, n):
+    _reverse_pass_against_50_digits(q, ctl, reference, n, COMBOS, K_REV)
+
+
+@pytest.mark.parametrize("n", (65, 257))
+def test_reverse_pass_at_the_odd_model(q, odd_ctl, odd_reference, n):
+    """the reverse pass on the handle at ODD_KIN with every accumulator, as test_forward_at_the_odd_model: in world mode Rwb_bar reads
+    the body-frame feet of the model's forward kinematics again"""
+    _reverse_pass_against_50_digits(q, odd_ctl, odd_reference, n, ODD_COMBOS, K_REV_ODD)
 
 
 def test_outputs_over_their_accumulators(q, ctl, reference):
@@ -254,11 +313,81 @@ def test_outputs_over_their_accumulators(q, ctl, reference):
     assert all(np.array_equal(apart[k], over[k]) for k in SP.OUTPUTS)
 
 
-def test_feet_bar_chains_into_the_kinematics_adjoint(q, ctl, reference):
-    """world-mode feet_bar handed to sensitivity_kinematics_batch() = the joint_q gradient of support_polygon_autograd()"""
+# ------------------------------------------------------------------ the second round of the grid stride
+ZERO_AT, OUTSIDE = 77, (200, 201)  # the period's 0/0 robot; the two robots of the draw that are planted after the tiling
+
+
+def _second_round_rows(c, names):
+    """(the period, the outside robots) as device rows: the first PERIOD robots of the draw - joint_q, world mode, a schedule per robot,
+    the cotangent and every accumulator - with ZERO_ROBOT at ZERO_AT; asserted to hold a 0/0 robot, stance and swing legs on every leg,
+    and the saturating family"""
+    rows = dict(_batch(c["b"], "joint_q", True, 257), schedule=c["sched"], com_xy_bar=c["bar"], **c["ins"])
+    rows = {k: rows[k].copy() for k in names}
+    rows["gait_phase"][ZERO_AT], rows["schedule"][ZERO_AT] = ZERO_ROBOT["gait_phase"], 0.0  # (the phase rule makes ZERO_ROBOT's stance bytes)
+    mask = np.array([[SP.in_stance(float(p), SP.TROT_DUTY) for p in row] for row in rows["gait_phase"][:PERIOD]])
+    assert mask[ZERO_AT].tolist() == [bool(v) for v in ZERO_ROBOT["stance"]] and mask.any(axis=0).all() and (~mask).any(axis=0).all()
+    assert all(rows["schedule"][16 * j].max() <= 1e-3 for j in range(9)) and (rows["schedule"][:PERIOD].min(axis=(1, 2)) >= 0.05).sum() > 100
+    assert max(OUTSIDE) < 257 and min(OUTSIDE) >= PERIOD
+    return {k: _cuda(v[:PERIOD]) for k, v in rows.items()}, {k: _cuda(v[list(OUTSIDE)]) for k, v in rows.items()}
+
+
+def _second_round_forward(odd_ctl, reference):
+    """support_polygon_kernel at n = 4096 x 64 + 65 = 262 209 robots on the handle at ODD_KIN: the grid is capped at 4096 one-wave
+    workgroups, so workgroup 0 walks a full second round and workgroup 1 has one live lane and 63 tail lanes in its second.  The
+    batch is the period of _second_round_rows tiled on the device, with robots 262 149 and n - 1 replaced by two robots from outside
+    the period.  com_xy, weights and flags, each starting from its sentinel, equal the n = 130 launch tiled (the two replaced robots:
+    an n = 2 launch of theirs) bit for bit - the 0/0 robot's NaN and bit 3 in every copy."""
     import torch
 
-    n = 65
+    def launch(rows, m, over=False):
+        out = {"com_xy": sentinel_tensor((m, 2), torch.float64), "weights": sentinel_tensor((m, 4), torch.float64), "flags": sentinel_tensor((m,), torch.int32)}
+        odd_ctl.support_polygon_batch({k: rows[k] for k in ("joint_q", "gait_phase", "Rwb", "x")}, rows["schedule"], world=True, want=tuple(out), out=out)
+        return out
+
+    assert UNPLANTED == (4096 * 64 + 5, SECOND_ROUND_N - 1)
+    small = second_round(launch, *_second_round_rows(reference, ("joint_q", "gait_phase", "Rwb", "x", "schedule")))
+    flags = small["flags"].cpu().numpy()
+    assert flags[ZERO_AT] == 1 << 3 and np.flatnonzero(flags).tolist() == [ZERO_AT] and bool(torch.isnan(small["com_xy"][ZERO_AT]).all())
+    torch.cuda.empty_cache()
+
+
+def _second_round_reverse(odd_ctl, reference):
+    """support_polygon_adjoint_kernel at the same n on the same tiled period, with every `_in` accumulator given (tiled too): every
+    output and the flags against the n = 130 launch tiled, the two replaced robots against their n = 2 launch; then once more at this
+    n with every output written over its `_in` array: the bits of the first run."""
+    import torch
+
+    shape = {"feet_bar": (4, 3), "schedule_bar": (4, 4)}
+
+    def launch(rows, m, over=False):
+        acc = {k: (rows[k].clone() if over else rows[k]) for k in SP.INS}
+        out = {k: acc[k + "_in"].view((m,) + shape.get(k, (SP.SIZES[k],))) if over else sentinel_tensor((m, SP.SIZES[k]), torch.float64) for k in SP.OUTPUTS}
+        out["flags"] = sentinel_tensor((m,), torch.int32)
+        odd_ctl.support_polygon_adjoint_batch({k: rows[k] for k in ("joint_q", "gait_phase", "Rwb", "x")}, rows["schedule"], rows["com_xy_bar"], world=True,
+                                              want=SP.OUTPUTS + ("flags",), out=out, **acc)
+        return {k: v.reshape(m, -1) if v.dim() > 1 else v for k, v in out.items()}
+
+    names = ("joint_q", "gait_phase", "Rwb", "x", "schedule", "com_xy_bar") + SP.INS
+    small = second_round(launch, *_second_round_rows(reference, names), over=True)
+    flags = small["flags"].cpu().numpy()
+    assert flags[ZERO_AT] == 1 << 3 and np.flatnonzero(flags).tolist() == [ZERO_AT]
+    assert all(bool(torch.isnan(small[k][ZERO_AT]).all()) and bool(torch.isfinite(small[k][:ZERO_AT]).all()) for k in SP.OUTPUTS)
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("kernel", ["forward", "reverse"])
+def test_second_round_of_the_grid_stride(q, odd_ctl, reference, kernel):
+    """both kernels past their grid cap (SENSITIVITY_MAX_BLOCKS = 4096 workgroups of 64 robots): _second_round_forward, _second_round_reverse"""
+    {"forward": _second_round_forward, "reverse": _second_round_reverse}[kernel](odd_ctl, reference)
+
+
+@pytest.mark.parametrize("model", ["default", "odd"])
+def test_feet_bar_chains_into_the_kinematics_adjoint(q, handles, reference, model):
+    """world-mode feet_bar handed to sensitivity_kinematics_batch() = the joint_q gradient of support_polygon_autograd(), on the handle
+    at the library's model and on the one at ODD_KIN"""
+    import torch
+
+    n, ctl = 65, handles[model]
     b = {k: _cuda(v) for k, v in _batch(reference["b"], "joint_q", True, n).items()}
     sched, bar = _cuda(reference["sched"][:n]), _cuda(reference["bar"][:n])
     s = ctl.support_polygon_adjoint_batch(b, sched, bar, world=True, want=("feet_bar",))
@@ -269,13 +398,16 @@ def test_feet_bar_chains_into_the_kinematics_adjoint(q, ctl, reference):
     assert torch.equal(leaf.grad.reshape(n, 12), by_hand.reshape(n, 12)) and bool((leaf.grad != 0).any())
 
 
-def test_autograd_against_central_differences(q, ctl, reference):
+@pytest.mark.parametrize("model", ["default", "odd"])
+def test_autograd_against_central_differences(q, handles, reference, model):
     """support_polygon_autograd at n = 8, world mode on joint_q: every gradient against central differences of the forward launch.
     h = 1e-6: truncation h^2 f''' / 6 ~ 1e-11 at third derivatives of order 50 (the ramps' widths are >= 0.05), rounding
-    EPS |com| / h ~ 1e-10 - the bound 1e-7 max(1, |gradient|) holds both with two digits to spare"""
+    EPS |com| / h ~ 1e-10 - the bound 1e-7 max(1, |gradient|) holds both with two digits to spare.  The same on the handle at ODD_KIN
+    (links and hips within a factor 1.25 of the library's: the same orders of magnitude), where the joint_q gradient of a kernel that
+    took another leg's link is off by that link's share"""
     import torch
 
-    n = 8
+    n, ctl = 8, handles[model]
     b, sched = SP.pool(n, seed=73)
     base = {k: _cuda(v) for k, v in _batch(b, "joint_q", True, n).items()}
     bar = _cuda(np.random.default_rng(74).standard_normal((n, 2)))

@@ -1,8 +1,8 @@
 """-m gpu: qc_swing_reference_batch and qc_swing_reference_adjoint_batch on the device - identity with the tick, the reverse pass
-against the 50-digit restatement (tests/swing_reference_restatement.py), aliasing, flagged robots, refusals, and a gait rollout with a
-gradient.  The handle is at a non-default model and gait (SR.ODD_MODEL: set_kinematics, set_gait); the batches hold robots on their
-first call, crossing one and two stance -> swing edges, mid-swing with a carried trajectory, with a trajectory just cleared by another
-leg's replan, and all stance (SR.pool's kinds)."""
+against the 50-digit restatement (tests/swing_reference_restatement.py), aliasing, flagged robots, the second round of both kernels'
+grid stride, refusals, and a gait rollout with a gradient.  The handle is at a non-default model and gait (SR.ODD_MODEL: set_kinematics,
+set_gait); the batches hold robots on their first call, crossing one and two stance -> swing edges, mid-swing with a carried
+trajectory, with a trajectory just cleared by another leg's replan, and all stance (SR.pool's kinds)."""
 import ctypes
 
 import numpy as np
@@ -10,6 +10,7 @@ import pytest
 
 from tests import leg_plant_adjoint_restatement as LA
 from tests import swing_reference_restatement as SR
+from tests.gpu_arrays import PERIOD, SECOND_ROUND_N, UNPLANTED, second_round, sentinel_tensor
 from tests.solved_batch_support import SENTINEL, assert_raw_refusals, batch_in, params, q  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -167,6 +168,91 @@ def test_flagged_robots(q, ctl, reference):
     assert np.array_equal(got["flags"].reshape(-1), plan.astype(np.int32)) and plan.any() and (plan == 0).any()
     for k in SR.OUTPUTS:
         assert np.isnan(got[k][plan != 0]).all() and np.isfinite(got[k][plan == 0]).all(), k
+
+
+# ------------------------------------------------------------------ the second round of the grid stride
+X_Z_ROBOTS, OUTSIDE = 18, (200, 201)  # the period's robots with test_flagged_robots' x_z; the two robots planted after the tiling
+
+
+def _second_round_rows(c, reverse):
+    """(the period, the outside robots) as device rows: the first PERIOD robots of the pool - every kind of SR.KINDS 21 times - the
+    first X_Z_ROBOTS of them with x_z = 0, < 0 and NaN as test_flagged_robots sets it (every kind meets each of the three).  Forward:
+    the batch before the call, the records and the clock's steps; reverse: the phases the forward call left, the records before it,
+    the four cotangents and every accumulator."""
+    b = dict(c["b"], x=c["b"]["x"].copy())
+    b["x"][:X_Z_ROBOTS, 2] = np.array([0.0, -0.1, np.nan])[(np.arange(X_Z_ROBOTS) // 6) % 3]
+    rows = {k: b[k] for k in STATE_KEYS}
+    rows["swing_state"] = c["state"].view(np.uint8).reshape(257, -1)
+    if reverse:
+        rows.update(gait_phase=c["phases"], **{"cot_" + k: v for k, v in c["bars"].items()}, **c["ins"])
+    else:
+        rows.update(gait_phase=b["gait_phase"], gait_dt=c["dt"])
+    assert X_Z_ROBOTS % 18 == 0 and X_Z_ROBOTS < PERIOD <= min(OUTSIDE) and max(OUTSIDE) < 257
+    return {k: _cuda(v[:PERIOD]) for k, v in rows.items()}, {k: _cuda(v[list(OUTSIDE)]) for k, v in rows.items()}
+
+
+def _second_round_forward(ctl, c):
+    """swing_reference_kernel at n = 4096 x 64 + 65 = 262 209 robots: the grid is capped at 4096 one-wave workgroups, so workgroup 0
+    walks a full second round and workgroup 1 has one live lane and 63 tail lanes in its second.  The batch is the period of
+    _second_round_rows tiled on the device, with robots 262 149 and n - 1 replaced by two robots from outside the period.  swing_pos,
+    swing_vel and planned, each starting from its sentinel, and what the kernel writes in place - the advanced phases and the swing
+    records, bytewise - equal the n = 130 launch tiled (the two replaced robots: an n = 2 launch of theirs) bit for bit.  The period
+    holds robots on their first call, replanned on an edge, carrying and losing a trajectory and all in stance: replan bits of both
+    kinds, stance and swing legs, records with and without a trajectory."""
+    import torch
+
+    def launch(rows, m, over=False):
+        phase, state = rows["gait_phase"].clone(), rows["swing_state"].clone()
+        out = {"swing_pos": sentinel_tensor((m, 12), torch.float64), "swing_vel": sentinel_tensor((m, 12), torch.float64), "planned": sentinel_tensor((m,), torch.uint8)}
+        ctl.swing_reference_batch(dict({k: rows[k] for k in STATE_KEYS}, gait_phase=phase, swing_state=state, gait_dt=rows["gait_dt"]), want=tuple(out), out=out)
+        return dict(out, gait_phase=phase, swing_state=state)
+
+    period, outside = _second_round_rows(c, False)
+    small = second_round(launch, period, outside, in_place=("gait_phase", "swing_state"))
+    planned = small["planned"].cpu().numpy()
+    assert np.array_equal(planned, c["planned"][:PERIOD]) and (planned != 0).sum() > 40 and (planned == 0).sum() > 40
+    rec = small["swing_state"].cpu().numpy().reshape(-1).view(SR.STATE_DTYPE)
+    before = c["state"][:PERIOD]
+    assert (before["leg_state"][:, 0] < 0).any() and (before["leg_state"][:, 0] >= 0).any()  # first calls and later ones
+    assert (rec["leg_state"] == 0).any() and (rec["leg_state"] == 1).any() and (rec["has_traj"] == 0).any() and (rec["has_traj"] == 1).any()
+    assert ((before["has_traj"] == 1) & (rec["has_traj"] == 0)).any(), "a trajectory cleared by another leg's replan"
+    assert not torch.equal(small["gait_phase"], period["gait_phase"]) and not torch.equal(small["swing_state"], period["swing_state"])
+    torch.cuda.empty_cache()
+
+
+def _second_round_reverse(ctl, c):
+    """swing_reference_adjoint_kernel at the same n on the same tiled period, with the four cotangents and every `_in` accumulator
+    given (tiled too): every output and the flags against the n = 130 launch tiled, the two replaced robots against their n = 2 launch;
+    then once more at this n with every output written over its `_in` / `_next_` array: the bits of the first run.  The first
+    X_Z_ROBOTS robots are flagged exactly where they replan (NaN rows), no other robot is."""
+    import torch
+
+    def launch(rows, m, over=False):
+        take = (lambda t: t.clone()) if over else (lambda t: t)
+        cot = {k: take(rows["cot_" + k]) for k in SR.COTANGENTS}
+        acc = {k: take(rows[k]) for k in SR.INS}
+        if over:
+            out = dict({k[:-3]: t for k, t in acc.items()}, p_start_bar=cot["p_start"], p_final_bar=cot["p_final"], xdot_d_bar=sentinel_tensor((m, 3), torch.float64))
+        else:
+            out = {k: sentinel_tensor((m, SR.SIZES[k]), torch.float64) for k in SR.OUTPUTS}
+        out["flags"] = sentinel_tensor((m,), torch.int32)
+        ctl.swing_reference_adjoint_batch({k: rows[k] for k in STATE_KEYS + ("gait_phase",)}, rows["swing_state"], cot, want=SR.OUTPUTS + ("flags",), out=out, **acc)
+        return {k: v.reshape(m, -1) if v.dim() > 1 else v for k, v in out.items()}
+
+    small = second_round(launch, *_second_round_rows(c, True), over=True)
+    flags, plan = small["flags"].cpu().numpy(), c["planned"][:PERIOD].astype(np.int32)
+    assert np.array_equal(flags[:X_Z_ROBOTS], plan[:X_Z_ROBOTS]) and not flags[X_Z_ROBOTS:].any() and (flags != 0).sum() == X_Z_ROBOTS // 2
+    for k in SR.OUTPUTS:
+        got = small[k].cpu().numpy()
+        assert np.isnan(got[flags != 0]).all() and np.isfinite(got[flags == 0]).all(), k
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("kernel", ["forward", "reverse"])
+def test_second_round_of_the_grid_stride(q, ctl, reference, kernel):
+    """both kernels past their grid cap (SENSITIVITY_MAX_BLOCKS = 4096 workgroups of 64 robots): _second_round_forward, _second_round_reverse"""
+    assert UNPLANTED == (4096 * 64 + 5, SECOND_ROUND_N - 1)
+    {"forward": _second_round_forward, "reverse": _second_round_reverse}[kernel](ctl, reference)
 
 
 def test_refusals_launch_nothing(q, ctl, reference):

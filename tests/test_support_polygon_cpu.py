@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from tests import support_polygon_restatement as SP
-from tests.device_math_reference import EPS
+from tests.device_math_reference import DEFAULT_KIN, EPS, ODD_KIN
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = 24
@@ -45,22 +45,40 @@ def drawn():
 
 
 @pytest.mark.parametrize("world", [False, True])
-@pytest.mark.parametrize("kin", [False, True])
-def test_float64_agrees_with_50_digits(drawn, world, kin):
+@pytest.mark.parametrize("kin,model", [pytest.param(False, DEFAULT_KIN, id="False"), pytest.param(True, DEFAULT_KIN, id="True"),
+                                       pytest.param(True, ODD_KIN, id="odd")])
+def test_float64_agrees_with_50_digits(drawn, world, kin, model):
+    """the measurement behind SP.C_FWD / C_REV (the library's model, both input forms) and SP.C_FWD_ODD / C_REV_ODD (ODD_KIN, joint_q)"""
     b, sched, bar = drawn
     b = {k: v for k, v in b.items() if k != ("feet" if kin else "joint_q")}
-    f = SP.reference_np(b, sched, world)
-    ref, cond = SP.reference_mp(b, sched, world)
+    c_fwd, c_rev = (SP.C_FWD_ODD, SP.C_REV_ODD) if model is ODD_KIN else (SP.C_FWD, SP.C_REV)
+    f = SP.reference_np(b, sched, world, kin=model)
+    ref, cond = SP.reference_mp(b, sched, world, kin=model)
     assert not f["flags"].any() and not ref["flags"].any()
     r = SP.worst_ratio(f["com_xy"], ref["com_xy"], cond["com_xy"])
-    print(f"forward world={world} kin={kin}: {r:.3f} EPS x condition sum")
-    assert r <= SP.C_FWD
-    g, _ = SP.reference_adjoint_np(b, sched, bar, world)
-    gref, gcond, _ = SP.reference_adjoint_mp(b, sched, bar, world)
+    print(f"forward world={world} kin={kin} model={model.name}: {r:.3f} EPS x condition sum")
+    assert r <= c_fwd
+    g, _ = SP.reference_adjoint_np(b, sched, bar, world, kin=model)
+    gref, gcond, _ = SP.reference_adjoint_mp(b, sched, bar, world, kin=model)
     for k in SP.OUTPUTS:
         r = SP.worst_ratio(g[k], gref[k], gcond[k])
-        print(f"reverse {k} world={world} kin={kin}: {r:.3f} EPS x condition sum")
-        assert r <= SP.C_REV
+        print(f"reverse {k} world={world} kin={kin} model={model.name}: {r:.3f} EPS x condition sum")
+        assert r <= c_rev
+
+
+@pytest.mark.parametrize("world", [False, True])
+def test_the_odd_model_moves_every_robot(world):
+    """com_xy from joint_q at ODD_KIN against com_xy at the library's model, over the first 65 robots of the GPU tests' draw: every
+    robot moves by a millimetre or more (printed: 1.1e-3 ... 1.9e-2 m), more than a million times the device's bar (4 C_FWD_ODD EPS x
+    condition sum, below 1e-13 m) - a kernel that ignored the handle's model cannot pass the GPU tests at ODD_KIN"""
+    b, sched = SP.pool(257, seed=61, saturating=16)
+    b, sched = {k: v[:65] for k, v in b.items() if k != "feet"}, sched[:65]
+    odd, cond = SP.reference_mp(b, sched, world, kin=ODD_KIN)
+    plain = SP.reference_np(b, sched, world)
+    moved = np.abs(odd["com_xy"] - plain["com_xy"]).max(axis=1)
+    bar = 4.0 * SP.C_FWD_ODD * EPS * cond["com_xy"].max(axis=1)
+    print(f"world={world}: com_xy moves by {moved.min():.2e} ... {moved.max():.2e} m; the device's bar is at most {bar.max():.2e} m")
+    assert not odd["flags"].any() and (moved > 1e6 * bar).all()
 
 
 def test_affine_equivariance():
