@@ -297,6 +297,35 @@ def plant_step_autograd(ctl, state, grf_body, foot_world, dt):
     return _PlantStep.apply(ctl, float(dt), *tensors)
 
 
+def _step_outputs(n, dev, warm, active, torques):
+    """The tensors a rollout step's solve writes into, this step's own: grf_body, status, joint_tau with `torques`, and with `warm` its
+    working-set word - the next solve starts from it (detached: an int32), this one from `active`.  Returns (res, the solve's keyword
+    arguments, the word the next step starts from)."""
+    res = {"grf_body": torch.zeros((n, 12), dtype=torch.float64, device=dev), "status": torch.full((n,), -1, dtype=torch.int32, device=dev)}
+    if torques:
+        res["joint_tau"] = torch.zeros((n, 12), dtype=torch.float64, device=dev)
+    kwargs = dict(out=res)
+    if warm:
+        res["active_set"] = torch.zeros((n,), dtype=torch.int32, device=dev)
+        kwargs.update(warm=active, want_active_set=True)
+        active = res["active_set"]
+    return res, kwargs, active
+
+
+def _refuse(who, batch, table):
+    """ValueError for the first array of `table` (name -> why not) the batch carries"""
+    for k, why in table.items():
+        if batch.get(k) is not None:
+            raise ValueError(f"{who}: the batch carries {k} - {why}")
+
+
+def _require(who, batch, names):
+    """ValueError naming the arrays of `names` the batch lacks"""
+    missing = [k for k in names if batch.get(k) is None]
+    if missing:
+        raise ValueError(f"{who}: the batch lacks {missing}")
+
+
 def rollout_autograd(ctl, batch, foot_world, steps, dt, act_tol=1e-7, warm=True, params=None):
     """BalanceController.rollout_autograd (see there): `steps` times control_batch_autograd() then plant_step_autograd(), out of place.
     The gradient is the one on the active face of every solve along the way; memory grows with `steps`.  `params` goes to every
@@ -310,12 +339,8 @@ def rollout_autograd(ctl, batch, foot_world, steps, dt, act_tol=1e-7, warm=True,
     out, active = {}, None
     for _ in range(steps):
         kwargs = {}
-        if warm:  # the solve writes its working-set word into a tensor of this step's own; the next solve starts from it (detached: an int32)
-            n, dev = cur["x"].shape[0], cur["x"].device
-            res = {"grf_body": torch.zeros((n, 12), dtype=torch.float64, device=dev), "status": torch.full((n,), -1, dtype=torch.int32, device=dev),
-                   "active_set": torch.zeros((n,), dtype=torch.int32, device=dev)}
-            kwargs = dict(warm=active, out=res, want_active_set=True)
-            active = res["active_set"]
+        if warm:
+            _, kwargs, active = _step_outputs(cur["x"].shape[0], cur["x"].device, True, active, torques=False)
         grf, status = control_batch_autograd(ctl, cur, act_tol, params=params, **kwargs)
         Rwb, x, xdot, w, feet = plant_step_autograd(ctl, cur, grf, foot_world, dt)
         cur = dict(cur, Rwb=Rwb, x=x, xdot=xdot, w=w, feet=feet)
@@ -416,9 +441,7 @@ def swing_reference_autograd(ctl, batch, swing_state, p_start, p_final):
     for k in ("swing_pos", "swing_vel"):
         if batch.get(k) is not None:
             raise ValueError(f"swing_reference_autograd: the batch carries {k} - this call makes the references")
-    missing = [k for k in SWING_REFERENCE_DIFFERENTIABLE[:-2] + ("gait_phase",) if batch.get(k) is None]
-    if missing:
-        raise ValueError(f"swing_reference_autograd: the batch lacks {missing}")
+    _require("swing_reference_autograd", batch, SWING_REFERENCE_DIFFERENTIABLE[:-2] + ("gait_phase",))
     n = batch["x"].shape[0]
     for name, t in (("p_start", p_start), ("p_final", p_final)):
         if t is None or t.dtype != torch.float64 or t.numel() != 12 * n:
@@ -433,6 +456,37 @@ _ROLLOUT_GAIT_REFUSED = {"stance": "the gait clock makes the contact mask from g
                          "feet": "the tick reads joint_q (rollout_autograd() steps the bare rigid body on `feet`)"}
 
 
+_COMMANDER_DESIRED_REFUSED = {k: "in commander mode the desired state lives in command['state']" for k in ("Rwb_d", "x_d", "xdot_d", "w_d")}
+_ROLLOUT_GAIT_NEEDED = ("joint_q", "joint_qdot", "gait_phase", "swing_state")
+
+
+def _gait_clock(gait_dt, n, dev):
+    """the clock's step of a gait rollout as a float64 [n] tensor"""
+    if isinstance(gait_dt, torch.Tensor):
+        return gait_dt.detach().to(dtype=torch.float64, device=dev).contiguous()
+    return torch.full((n,), float(gait_dt), dtype=torch.float64, device=dev)
+
+
+def _gait_step(ctl, cur, desired, phase, duty, clock, record, p_start, p_final, warm, active, flags, dt, leg_inertia, act_tol, params, joint_gains):
+    """One step of the two gait rollouts behind whatever made `desired`, the desired-state arrays that take the place of the batch's own
+    for this step: swing_reference_autograd() with the clock advancing, tick_autograd() on its references and phases,
+    leg_plant_step_autograd() with those phases.  Returns (the next cur, the step's out, (phase, record, p_start, p_final, planned,
+    active) as the next step takes them)."""
+    n, dev = cur["x"].shape[0], cur["x"].device
+    phase = phase.clone()  # this step's own phases: advanced in place by the references' clock, then read by the tick and the plant
+    tracked = dict(cur, **desired)
+    ref_in = dict({k: tracked[k] for k in SWING_REFERENCE_DIFFERENTIABLE[:-2]}, gait_phase=phase, gait_dt=clock)
+    if duty is not None:
+        ref_in["gait_duty"] = duty
+    pos, vel, p_start, p_final, record, planned = swing_reference_autograd(ctl, ref_in, record, p_start, p_final)
+    _, kwargs, active = _step_outputs(n, dev, warm, active, torques=True)
+    tick_in = dict(tracked, gait_phase=phase, swing_pos=pos, swing_vel=vel)
+    tau, grf, status = tick_autograd(ctl, tick_in, act_tol, params=params, joint_gains=joint_gains, **kwargs)
+    new = leg_plant_step_autograd(ctl, cur, tau, dt, leg_inertia, gait_phase=phase, gait_duty=duty, flags=flags)
+    out = {"joint_tau": tau, "grf_body": grf, "status": status, "flags": flags}
+    return dict(cur, **dict(zip(LEG_PLANT_DIFFERENTIABLE[:-1], new))), out, (phase, record, p_start, p_final, planned, active)
+
+
 def rollout_gait_autograd(ctl, batch, steps, dt, leg_inertia, gait_dt, act_tol=1e-7, warm=True, params=None, joint_gains=None, lean=None):
     """BalanceController.rollout_gait_autograd (see there): `steps` times swing_reference_autograd() with the clock advancing,
     tick_autograd() on its references and phases, leg_plant_step_autograd() with those phases; the swing record threaded through.
@@ -440,21 +494,14 @@ def rollout_gait_autograd(ctl, batch, steps, dt, leg_inertia, gait_dt, act_tol=1
     lean = _lean("rollout_gait_autograd", lean, "replace")
     if lean is not None and batch.get("x_d") is None:
         raise ValueError("rollout_gait_autograd: lean needs batch['x_d'] (its z in replace mode, the base of the offset)")
-    for k, why in _ROLLOUT_GAIT_REFUSED.items():
-        if batch.get(k) is not None:
-            raise ValueError(f"rollout_gait_autograd: the batch carries {k} - {why}")
-    missing = [k for k in ("joint_q", "joint_qdot", "gait_phase", "swing_state") if batch.get(k) is None]
-    if missing:
-        raise ValueError(f"rollout_gait_autograd: the batch lacks {missing}")
+    _refuse("rollout_gait_autograd", batch, _ROLLOUT_GAIT_REFUSED)
+    _require("rollout_gait_autograd", batch, _ROLLOUT_GAIT_NEEDED)
     steps = int(steps)
     if steps < 0:
         raise ValueError("rollout_gait_autograd: steps must be >= 0")
     names = LEG_PLANT_DIFFERENTIABLE[:-1]
     n, dev = batch["x"].shape[0], batch["x"].device
-    if isinstance(gait_dt, torch.Tensor):
-        clock = gait_dt.detach().to(dtype=torch.float64, device=dev).contiguous()
-    else:
-        clock = torch.full((n,), float(gait_dt), dtype=torch.float64, device=dev)
+    clock = _gait_clock(gait_dt, n, dev)
     cur = {k: v for k, v in batch.items() if k not in ("swing_state", "gait_phase")}
     duty = batch.get("gait_duty")
     record, phase = batch["swing_state"].detach(), batch["gait_phase"].detach()
@@ -462,26 +509,9 @@ def rollout_gait_autograd(ctl, batch, steps, dt, leg_inertia, gait_dt, act_tol=1
     out, active, planned = {}, None, None
     flags = torch.zeros((n,), dtype=torch.int32, device=dev) if steps else None
     for _ in range(steps):
-        x_d = None if lean is None else _lean_x_d(ctl, lean, cur, phase, duty, batch["x_d"])
-        phase = phase.clone()  # this step's own phases: advanced in place by the references' clock, then read by the tick and the plant
-        ref_in = dict({k: cur[k] for k in SWING_REFERENCE_DIFFERENTIABLE[:-2]}, gait_phase=phase, gait_dt=clock)
-        if duty is not None:
-            ref_in["gait_duty"] = duty
-        pos, vel, p_start, p_final, record, planned = swing_reference_autograd(ctl, ref_in, record, p_start, p_final)
-        res = {"grf_body": torch.zeros((n, 12), dtype=torch.float64, device=dev), "status": torch.full((n,), -1, dtype=torch.int32, device=dev),
-               "joint_tau": torch.zeros((n, 12), dtype=torch.float64, device=dev)}
-        kwargs = dict(out=res)
-        if warm:  # this step's own working-set word; the next solve starts from it (detached: an int32)
-            res["active_set"] = torch.zeros((n,), dtype=torch.int32, device=dev)
-            kwargs.update(warm=active, want_active_set=True)
-            active = res["active_set"]
-        tick_in = dict(cur, gait_phase=phase, swing_pos=pos, swing_vel=vel)
-        if x_d is not None:
-            tick_in["x_d"] = x_d
-        tau, grf, status = tick_autograd(ctl, tick_in, act_tol, params=params, joint_gains=joint_gains, **kwargs)
-        new = leg_plant_step_autograd(ctl, cur, tau, dt, leg_inertia, gait_phase=phase, gait_duty=duty, flags=flags)
-        cur = dict(cur, **dict(zip(names, new)))
-        out = {"joint_tau": tau, "grf_body": grf, "status": status, "flags": flags}
+        desired = {} if lean is None else {"x_d": _lean_x_d(ctl, lean, cur, phase, duty, batch["x_d"])}
+        cur, out, (phase, record, p_start, p_final, planned, active) = _gait_step(
+            ctl, cur, desired, phase, duty, clock, record, p_start, p_final, warm, active, flags, dt, leg_inertia, act_tol, params, joint_gains)
     if warm and active is not None:
         out["active_set"] = active
     out.update(gait_phase=phase, swing_state=record, p_start=p_start, p_final=p_final)
@@ -542,9 +572,7 @@ def commander_step_autograd(ctl, batch, command, desired, Vb):
     """BalanceController.commander_step_autograd (see there): (Rwb_d, x_d, xdot_d, w_d, Vb', state', run, applied) of
     commander_step_batch() on a copy of command["state"] whose held command is `Vb` and whose desired state is `desired`,
     differentiable in COMMANDER_STEP_DIFFERENTIABLE."""
-    missing = [k for k in ("Rwb", "x") if batch.get(k) is None]
-    if missing:
-        raise ValueError(f"commander_step_autograd: the batch lacks {missing}")
+    _require("commander_step_autograd", batch, ("Rwb", "x"))
     if command.get("state") is None:
         raise ValueError("commander_step_autograd: command['state'] is required (new_commander_states)")
     n = batch["x"].shape[0]
@@ -568,15 +596,9 @@ def rollout_commander_autograd(ctl, batch, command, steps, dt, leg_inertia, gait
     the commander's x_d for the tick alone."""
     who = "rollout_commander_autograd"
     lean = _lean(who, lean, "offset")
-    for k, why in _ROLLOUT_GAIT_REFUSED.items():
-        if batch.get(k) is not None:
-            raise ValueError(f"{who}: the batch carries {k} - {why}")
-    for k in ("Rwb_d", "x_d", "xdot_d", "w_d"):
-        if batch.get(k) is not None:
-            raise ValueError(f"{who}: the batch carries {k} - in commander mode the desired state lives in command['state']")
-    missing = [k for k in ("joint_q", "joint_qdot", "gait_phase", "swing_state") if batch.get(k) is None]
-    if missing:
-        raise ValueError(f"{who}: the batch lacks {missing}")
+    _refuse(who, batch, _ROLLOUT_GAIT_REFUSED)
+    _refuse(who, batch, _COMMANDER_DESIRED_REFUSED)
+    _require(who, batch, _ROLLOUT_GAIT_NEEDED)
     steps = int(steps)
     if steps < 0:
         raise ValueError(f"{who}: steps must be >= 0")
@@ -597,10 +619,7 @@ def rollout_commander_autograd(ctl, batch, command, steps, dt, leg_inertia, gait
     if sequence and fresh is None:
         fresh = torch.ones((steps, n), dtype=torch.uint8, device=dev)
     scalars = {k: command[k] for k in ("stand_height", "stand_tol", "cmd_dt") if command.get(k) is not None}
-    if isinstance(gait_dt, torch.Tensor):
-        clock = gait_dt.detach().to(dtype=torch.float64, device=dev).contiguous()
-    else:
-        clock = torch.full((n,), float(gait_dt), dtype=torch.float64, device=dev)
+    clock = _gait_clock(gait_dt, n, dev)
     cur = {k: v for k, v in batch.items() if k not in ("swing_state", "gait_phase")}
     duty = batch.get("gait_duty")
     record, phase = batch["swing_state"].detach(), batch["gait_phase"].detach()
@@ -619,23 +638,9 @@ def rollout_commander_autograd(ctl, batch, command, steps, dt, leg_inertia, gait
         *desired, Vb, cstate, _run, applied = commander_step_autograd(ctl, cur, cmd, desired, Vb)
         # (the leaned value goes to the tick only: `desired` keeps the un-leaned integral, the lean never feeds back into twist tracking)
         x_d = desired[1] if lean is None else _lean_x_d(ctl, lean, cur, phase, duty, desired[1])
-        phase = phase.clone()  # this step's own phases: advanced in place by the references' clock, then read by the tick and the plant
-        ref_in = dict({name: cur[name] for name in SWING_REFERENCE_DIFFERENTIABLE[:-2] if name != "xdot_d"}, xdot_d=desired[2], gait_phase=phase, gait_dt=clock)
-        if duty is not None:
-            ref_in["gait_duty"] = duty
-        pos, vel, p_start, p_final, record, planned = swing_reference_autograd(ctl, ref_in, record, p_start, p_final)
-        res = {"grf_body": torch.zeros((n, 12), dtype=torch.float64, device=dev), "status": torch.full((n,), -1, dtype=torch.int32, device=dev),
-               "joint_tau": torch.zeros((n, 12), dtype=torch.float64, device=dev)}
-        kwargs = dict(out=res)
-        if warm:  # this step's own working-set word; the next solve starts from it (detached: an int32)
-            res["active_set"] = torch.zeros((n,), dtype=torch.int32, device=dev)
-            kwargs.update(warm=active, want_active_set=True)
-            active = res["active_set"]
-        tick_in = dict(cur, gait_phase=phase, swing_pos=pos, swing_vel=vel, Rwb_d=desired[0], x_d=x_d, xdot_d=desired[2], w_d=desired[3])
-        tau, grf, status = tick_autograd(ctl, tick_in, act_tol, params=params, joint_gains=joint_gains, **kwargs)
-        new = leg_plant_step_autograd(ctl, cur, tau, dt, leg_inertia, gait_phase=phase, gait_duty=duty, flags=flags)
-        cur = dict(cur, **dict(zip(names, new)))
-        out = {"joint_tau": tau, "grf_body": grf, "status": status, "flags": flags}
+        tracked = dict(Rwb_d=desired[0], x_d=x_d, xdot_d=desired[2], w_d=desired[3])
+        cur, out, (phase, record, p_start, p_final, planned, active) = _gait_step(
+            ctl, cur, tracked, phase, duty, clock, record, p_start, p_final, warm, active, flags, dt, leg_inertia, act_tol, params, joint_gains)
     if warm and active is not None:
         out["active_set"] = active
     out.update(gait_phase=phase, swing_state=record, p_start=p_start, p_final=p_final, cmd_state=cstate)
@@ -653,9 +658,7 @@ def rollout_tick_autograd(ctl, batch, steps, dt, leg_inertia, act_tol=1e-7, warm
     """BalanceController.rollout_tick_autograd (see there): `steps` times fused_tick_autograd() - tick_autograd() for a batch with
     swing_pos and swing_vel, both held over the rollout - then leg_plant_step_autograd(), out of place.  The gradient is the one on the active face of every solve, at every tick's clamp mask and off the plant's flagged legs;
     memory grows with `steps`."""
-    for k, why in _ROLLOUT_TICK_REFUSED.items():
-        if batch.get(k) is not None:
-            raise ValueError(f"rollout_tick_autograd: the batch carries {k} - {why}")
+    _refuse("rollout_tick_autograd", batch, _ROLLOUT_TICK_REFUSED)
     if batch.get("joint_q") is None or batch.get("joint_qdot") is None:
         raise ValueError("rollout_tick_autograd: the batch carries joint_q and joint_qdot (rollout_autograd() steps the bare rigid body)")
     swings = batch.get("swing_pos") is not None
@@ -672,13 +675,7 @@ def rollout_tick_autograd(ctl, batch, steps, dt, leg_inertia, act_tol=1e-7, warm
     flags = torch.zeros((n,), dtype=torch.int32, device=dev) if steps else None
     for _ in range(steps):
         # the tick, as rollout_tick(batch, None, ...) plans it: a control_batch() without swing references takes no joint_qdot
-        res = {"grf_body": torch.zeros((n, 12), dtype=torch.float64, device=dev), "status": torch.full((n,), -1, dtype=torch.int32, device=dev),
-               "joint_tau": torch.zeros((n, 12), dtype=torch.float64, device=dev)}
-        kwargs = dict(out=res)
-        if warm:  # this step's own working-set word; the next solve starts from it (detached: an int32)
-            res["active_set"] = torch.zeros((n,), dtype=torch.int32, device=dev)
-            kwargs.update(warm=active, want_active_set=True)
-            active = res["active_set"]
+        _, kwargs, active = _step_outputs(n, dev, warm, active, torques=True)
         if swings:  # the swing legs' PD torques read joint_qdot and the held references
             tau, grf, status = tick_autograd(ctl, cur, act_tol, params=params, **kwargs)
         else:
@@ -698,6 +695,37 @@ SUPPORT_POLYGON_DIFFERENTIABLE = ("feet", "joint_q", "Rwb", "x", "gait_phase", "
 _SUPPORT_POLYGON_BAR = {"feet": "feet_bar", "joint_q": "feet_bar", "Rwb": "Rwb_bar", "x": "x_bar", "gait_phase": "phase_bar", "schedule": "schedule_bar"}
 
 
+def _polygon_backward(ctx, names, bar, lead, adjoint):
+    """What _SupportPolygon.backward and _ComReference.backward share.  `names`: forward's tensor arguments; `bar`: name -> the reverse
+    pass's output that is its gradient; `lead`: the number of non-tensor arguments in front of them; adjoint(batch, schedule, want):
+    the reverse pass.  With joint_q a second launch carries feet_bar on; per-robot schedule_bar rows of a shared block are summed here."""
+    given = iter(ctx.saved_tensors)
+    inputs = {k: (next(given) if there else None) for k, there in zip(names, ctx.present)}
+    need = dict(zip(names, ctx.needs_input_grad[lead:]))
+    want = tuple(dict.fromkeys(bar[k] for k in names if need[k]))
+    if not want:
+        return (None,) * (lead + len(names))
+    batch = dict(ctx.rest, **{k: v for k, v in inputs.items() if v is not None and k not in ("schedule", "x_d")})
+    schedule = inputs["schedule"]
+    s = adjoint(batch, schedule, want)
+    grads = {k: s[bar[k]] for k in names if need[k] and k != "joint_q"}
+    if need["joint_q"]:  # J(q)^T feet_bar, leg by leg: the kinematics half of the fused tick's reverse pass (unmasked: every leg)
+        grads["joint_q"] = ctx.ctl.sensitivity_kinematics_batch({"joint_q": inputs["joint_q"]}, feet_bar=s["feet_bar"], want=("joint_q_bar",))["joint_q_bar"]
+    if need["schedule"] and schedule.dim() == 2 and bar["schedule"] == "schedule_bar":  # a shared block: the sum over the robots
+        grads["schedule"] = grads["schedule"].sum(0)
+    return (*(None,) * lead, *[grads[k].view_as(inputs[k]) if need[k] else None for k in names])
+
+
+def _polygon_tensors(batch, world):
+    """Of the batch of the two polygon calls: the tensors a gradient is produced for, in SUPPORT_POLYGON_DIFFERENTIABLE's order less
+    the schedule (None where the forward pass does not read one), and the batch detached - `feet` dropped where joint_q takes its place."""
+    kin = batch.get("joint_q") is not None
+    taken = {"feet": not kin, "joint_q": kin, "Rwb": bool(world), "x": bool(world), "gait_phase": True}
+    tensors = [batch.get(k) if taken[k] else None for k in SUPPORT_POLYGON_DIFFERENTIABLE[:-1]]
+    detached = {k: (v.detach() if isinstance(v, torch.Tensor) else v) for k, v in batch.items() if k != "feet" or not kin}
+    return tensors, detached
+
+
 class _SupportPolygon(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ctl, batch, world, *tensors):
@@ -712,22 +740,8 @@ class _SupportPolygon(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, com_bar):
-        names = SUPPORT_POLYGON_DIFFERENTIABLE
-        given = iter(ctx.saved_tensors)
-        inputs = {k: (next(given) if there else None) for k, there in zip(names, ctx.present)}
-        need = dict(zip(names, ctx.needs_input_grad[3:]))
-        want = tuple(dict.fromkeys(_SUPPORT_POLYGON_BAR[k] for k in names if need[k]))
-        if not want:
-            return (None,) * (3 + len(names))
-        batch = dict(ctx.rest, **{k: v for k, v in inputs.items() if v is not None and k != "schedule"})
-        ctl, schedule = ctx.ctl, inputs["schedule"]
-        s = ctl.support_polygon_adjoint_batch(batch, schedule, com_bar.contiguous(), world=ctx.world, want=want)
-        grads = {k: s[_SUPPORT_POLYGON_BAR[k]] for k in names if need[k] and k != "joint_q"}
-        if need["joint_q"]:  # J(q)^T feet_bar, leg by leg: the kinematics half of the fused tick's reverse pass (unmasked: every leg)
-            grads["joint_q"] = ctl.sensitivity_kinematics_batch({"joint_q": inputs["joint_q"]}, feet_bar=s["feet_bar"], want=("joint_q_bar",))["joint_q_bar"]
-        if need["schedule"] and schedule.dim() == 2:  # a shared block: the sum over the robots
-            grads["schedule"] = grads["schedule"].sum(0)
-        return (None, None, None, *[grads[k].view_as(inputs[k]) if need[k] else None for k in names])
+        return _polygon_backward(ctx, SUPPORT_POLYGON_DIFFERENTIABLE, _SUPPORT_POLYGON_BAR, 3, lambda batch, schedule, want:
+                                 ctx.ctl.support_polygon_adjoint_batch(batch, schedule, com_bar.contiguous(), world=ctx.world, want=want))
 
 
 def support_polygon_autograd(ctl, batch, schedule, world=False):
@@ -739,11 +753,8 @@ def support_polygon_autograd(ctl, batch, schedule, world=False):
         raise ValueError("support_polygon_autograd: world=True needs Rwb and x")
     if schedule is None or schedule.dtype != torch.float64:
         raise ValueError("support_polygon_autograd: schedule is a float64 [n,4,4] or [4,4] tensor")
-    kin = batch.get("joint_q") is not None
-    taken = {"feet": not kin, "joint_q": kin, "Rwb": bool(world), "x": bool(world), "gait_phase": True}
-    tensors = [batch.get(k) if taken[k] else None for k in SUPPORT_POLYGON_DIFFERENTIABLE[:-1]] + [schedule]
-    detached = {k: (v.detach() if isinstance(v, torch.Tensor) else v) for k, v in batch.items() if k != "feet" or not kin}
-    return _SupportPolygon.apply(ctl, detached, bool(world), *tensors)
+    tensors, detached = _polygon_tensors(batch, world)
+    return _SupportPolygon.apply(ctl, detached, bool(world), *tensors, schedule)
 
 
 # ------------------------------------------------------------------ the desired COM of a step from the polygon
@@ -765,22 +776,10 @@ class _ComReference(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, x_d_bar):
-        names = COM_REFERENCE_DIFFERENTIABLE
-        given = iter(ctx.saved_tensors)
-        inputs = {k: (next(given) if there else None) for k, there in zip(names, ctx.present)}
-        need = dict(zip(names, ctx.needs_input_grad[4:]))
-        schedule = inputs["schedule"]
-        bar = dict(_COM_REFERENCE_BAR, schedule="schedule_bar_sum" if schedule.dim() == 2 else "schedule_bar")  # a shared block: the kernel's sum
-        want = tuple(dict.fromkeys(bar[k] for k in names if need[k]))
-        if not want:
-            return (None,) * (4 + len(names))
-        batch = dict(ctx.rest, **{k: v for k, v in inputs.items() if v is not None and k not in ("schedule", "x_d")})
-        ctl = ctx.ctl
-        s = ctl.com_reference_adjoint_batch(batch, schedule, x_d_bar.contiguous(), ctx.mode, ctx.gain, want=want)
-        grads = {k: s[bar[k]] for k in names if need[k] and k != "joint_q"}
-        if need["joint_q"]:  # J(q)^T feet_bar, leg by leg: the kinematics half of the fused tick's reverse pass (unmasked: every leg)
-            grads["joint_q"] = ctl.sensitivity_kinematics_batch({"joint_q": inputs["joint_q"]}, feet_bar=s["feet_bar"], want=("joint_q_bar",))["joint_q_bar"]
-        return (None, None, None, None, *[grads[k].view_as(inputs[k]) if need[k] else None for k in names])
+        shared = ctx.saved_tensors[-1].dim() == 2  # a shared block: the kernel's sum
+        bar = dict(_COM_REFERENCE_BAR, schedule="schedule_bar_sum" if shared else "schedule_bar")
+        return _polygon_backward(ctx, COM_REFERENCE_DIFFERENTIABLE, bar, 4, lambda batch, schedule, want:
+                                 ctx.ctl.com_reference_adjoint_batch(batch, schedule, x_d_bar.contiguous(), ctx.mode, ctx.gain, want=want))
 
 
 def com_reference_autograd(ctl, batch, schedule, x_d, mode="replace", gain=1.0):
@@ -793,11 +792,8 @@ def com_reference_autograd(ctl, batch, schedule, x_d, mode="replace", gain=1.0):
         raise ValueError("com_reference_autograd: schedule is a float64 [n,4,4] or [4,4] tensor")
     if x_d is None or x_d.dtype != torch.float64 or x_d.dim() != 2 or x_d.shape[1] != 3:
         raise ValueError("com_reference_autograd: x_d is a float64 [n,3] tensor")
-    kin = batch.get("joint_q") is not None
-    taken = {"feet": not kin, "joint_q": kin, "Rwb": True, "x": True, "gait_phase": True}
-    tensors = [x_d] + [batch.get(k) if taken[k] else None for k in SUPPORT_POLYGON_DIFFERENTIABLE[:-1]] + [schedule]
-    detached = {k: (v.detach() if isinstance(v, torch.Tensor) else v) for k, v in batch.items() if k != "feet" or not kin}
-    return _ComReference.apply(ctl, detached, mode, float(gain), *tensors)
+    tensors, detached = _polygon_tensors(batch, True)
+    return _ComReference.apply(ctl, detached, mode, float(gain), x_d, *tensors, schedule)
 
 
 def _lean(who, lean, default_mode):

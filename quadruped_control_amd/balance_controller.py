@@ -78,6 +78,33 @@ def _outputs(who, table, want, out, n, dev, io, extra=()):
     return res
 
 
+def _record_tensor(name, t, n, itemsize, dev):
+    """`t` is a uint8 tensor holding n records of `itemsize` bytes on `dev`, or None.  Returns whether there is a tensor."""
+    import torch
+
+    return _check_tensor(name, t, n, itemsize, torch.uint8, dev, False, msg=f"{name}: need a contiguous uint8 tensor of n * {itemsize} bytes on the device")
+
+
+def _known_cotangents(who, cotangents, table, whose="call"):
+    """Refuses a cotangent on anything but the outputs of the forward call (`table`)."""
+    unknown = [k for k in cotangents if k not in table]
+    if unknown:
+        raise ValueError(f"{who}: unknown cotangent(s) {unknown}; the {whose}'s outputs are {tuple(table)}")
+
+
+def _rows_and_sum(want, name, shape):
+    """`want` split into the per-robot outputs and, if `name` - the one output summed over the batch - is asked for, its `extra` entry
+    of _outputs (its shape does not depend on n).  Returns (rows, extra)."""
+    return tuple(w for w in want if w != name), [(name, shape, "float64")] if name in want else []
+
+
+def _launched(plan):
+    """what every *_batch call is: its plan, launched once"""
+    launch, res = plan
+    launch()
+    return res
+
+
 class _RolloutPlans:
     """What rollout() and rollout_tick() share: the output tensors, the two working-set arrays a warm rollout ping-pongs between (a
     solve never reads the array it writes), the solves marshalled once - `plan(first, warm, out)` returns the launch of step 0
@@ -293,8 +320,7 @@ class BalanceController:
                 setattr(bi, name, t.data_ptr())
         ss = batch.get("swing_state")
         # torch.uint8 tensor of n * sizeof(qc_swing_state) bytes, updated in place
-        if _check_tensor("swing_state", ss, n, SWING_STATE_DTYPE.itemsize, torch.uint8, dev, False,
-                         msg="swing_state: need a contiguous uint8 tensor of n * 224 bytes on the device"):
+        if _record_tensor("swing_state", ss, n, SWING_STATE_DTYPE.itemsize, dev):
             bi.swing_state = ss.data_ptr()
         if out is None:
             # Allocated here: defined contents until the first launch has run (plan_batch launches nothing) - zero forces and
@@ -421,9 +447,7 @@ class BalanceController:
         records (new_commander_states, updated in place), twist=[n,6] float64 or None, fresh=[n] uint8 or None (1 = a command
         arrived for this robot), and optionally stand_height / stand_tol / cmd_dt).  Asynchronous on `stream`; returns the
         out dict of control_batch(..., want_torques=True)."""
-        launch, out = self.plan_tick(batch, command, warm, out, want_active_set, want_iterations, stream)
-        launch()
-        return out
+        return _launched(self.plan_tick(batch, command, warm, out, want_active_set, want_iterations, stream))
 
     # ------------------------------------------------------- closing the loop
     def _plant_arrays(self, io, state, grf_body, foot_world, feet=None):
@@ -505,9 +529,7 @@ class BalanceController:
         io = _lib.QcPlantAdjointIo()
         self._lib.qc_default_plant_adjoint(C.byref(io))
         n, dev = self._plant_arrays(io, state, grf_body, foot_world)
-        unknown = [k for k in cotangents if k not in _PLANT_COTANGENTS]
-        if unknown:
-            raise ValueError(f"plant_step_adjoint: unknown cotangent(s) {unknown}; the step's outputs are {tuple(_PLANT_COTANGENTS)}")
+        _known_cotangents("plant_step_adjoint", cotangents, _PLANT_COTANGENTS, "step")
         for name, t in cotangents.items():
             if _check_tensor(f"cotangents['{name}']", t, n, int(np.prod(_PLANT_COTANGENTS[name][0])), torch.float64, dev, False, "float64"):
                 setattr(io, name + "_next_bar", t.data_ptr())
@@ -526,9 +548,7 @@ class BalanceController:
         accumulated.  The step is recomputed from `state`; nothing of it is written.  No cotangent of mass, Ib or dt is produced.
         Asynchronous on `stream`, no synchronisation.  Returns the dict of device tensors; ValueError with the library's message for
         a call it refuses."""
-        launch, res = self.plan_plant_adjoint(state, grf_body, foot_world, dt, cotangents, want, out, stream)
-        launch()
-        return res
+        return _launched(self.plan_plant_adjoint(state, grf_body, foot_world, dt, cotangents, want, out, stream))
 
     def plant_step_autograd(self, state, grf_body, foot_world, dt):
         """plant_step() with a gradient, OUT OF PLACE: returns (Rwb', x', xdot', w', feet') as new tensors and leaves `state` as it
@@ -712,9 +732,7 @@ class BalanceController:
         for name, t, k, dtype, required in arrays:
             if _check_tensor(name, t, n, k, dtype, dev, required):
                 setattr(io, name, t.data_ptr() if n else None)
-        unknown = [k for k in cotangents if k not in _LEG_PLANT_COTANGENTS]
-        if unknown:
-            raise ValueError(f"leg_plant_step_adjoint: unknown cotangent(s) {unknown}; the step's outputs are {tuple(_LEG_PLANT_COTANGENTS)}")
+        _known_cotangents("leg_plant_step_adjoint", cotangents, _LEG_PLANT_COTANGENTS, "step")
         for name, t in cotangents.items():
             if _check_tensor(f"cotangents['{name}']", t, n, int(np.prod(_LEG_PLANT_COTANGENTS[name][0])), torch.float64, dev, False, "float64"):
                 setattr(io, name + "_next_bar", t.data_ptr())
@@ -741,10 +759,8 @@ class BalanceController:
         kinematic constants is produced, none through foot_world, and the contact mask is held.  Asynchronous on `stream`, no
         synchronisation.  Returns the dict of device tensors (with "flags" if given); ValueError with the library's message for a
         call it refuses."""
-        launch, res = self.plan_leg_plant_adjoint(state, joint_tau, dt, leg_inertia, cotangents, want, stance, gait_phase, gait_duty, cmd_state,
-                                                  out, flags, stream)
-        launch()
-        return res
+        return _launched(self.plan_leg_plant_adjoint(state, joint_tau, dt, leg_inertia, cotangents, want, stance, gait_phase, gait_duty, cmd_state,
+                                                     out, flags, stream))
 
     def leg_plant_step_autograd(self, state, joint_tau, dt, leg_inertia, stance=None, gait_phase=None, gait_duty=None, flags=None):
         """leg_plant_step() with a gradient, OUT OF PLACE: returns (Rwb', x', xdot', w', joint_q', joint_qdot') as new tensors and
@@ -779,17 +795,19 @@ class BalanceController:
         return rollout_tick_autograd(self, batch, steps, dt, leg_inertia, act_tol, warm, params)
 
     # ------------------------------------------------------ certifying a batch
-    def _readonly_batch(self, who, batch, fields, io, own):
-        """The batch of a call that only reads it, and the call's own input arrays: n from the first array that is there among
-        _IN_FIELDS and `own` ((name, tensor, k) entries, float64), a QcBatchIn filled from whatever `fields` ((name, k, torch dtype
-        name) entries) the batch holds, the arrays of `own` set in `io`.  What is required is the library's decision: it names what is
-        missing, from launch().  Returns (n, dev, bi)."""
+    def _readonly_batch(self, who, batch, fields, io, own, sizing=None, none="the batch holds no state array"):
+        """The batch of a call that only reads it, and the call's own input arrays: n from the first array that is there among `sizing`
+        (default: _IN_FIELDS of the batch and `own`; `none`: what the refusal says when none is), a QcBatchIn filled from whatever
+        `fields` ((name, k, torch dtype name) entries) the batch holds, the arrays of `own` ((name, tensor, k) entries, float64) set in
+        `io`.  What is required is the library's decision: it names what is missing, from launch().  Returns (n, dev, bi)."""
         import torch
 
         dev = torch.device("cuda", self.device)
-        sized = [t for t in [batch.get(k) for k, _ in _IN_FIELDS] + [t for _, t, _ in own] if t is not None]
+        if sizing is None:
+            sizing = [batch.get(k) for k, _ in _IN_FIELDS] + [t for _, t, _ in own]
+        sized = [t for t in sizing if t is not None]
         if not sized:
-            raise ValueError(f"{who}: the batch holds no state array")
+            raise ValueError(f"{who}: {none}")
         n = sized[0].shape[0]  # (a missing array is the library's refusal, not a KeyError here)
         bi = _lib.QcBatchIn()
         for name, k, dtype in fields:
@@ -801,19 +819,46 @@ class BalanceController:
                 setattr(io, name, t.data_ptr())
         return n, dev, bi
 
+    def _plan(self, name, who, io_type, default, batch, fields, own, table, want, out, stream, extra=(), scalars=None, sizing=None,
+              none="the batch holds no state array", status=None, command=None, need_state=True, records=(), marshal=None, aliases=(),
+              invalid=ValueError):
+        """What every plan_* of a call on a read-only batch is.  `name`: the entry point; `io_type`, `default`: its io record and the
+        qc_default_* that fills it; `batch`, `fields`, `own`, `sizing`, `none`: _readonly_batch's; `status`: the solve's int32 [n]
+        array, for the call that reads it; `command`, `need_state`: _marshal_command's, for a call that takes a command record;
+        `scalars`: io fields set from numbers; `records`: (name, tensor, itemsize) record tensors (_record_tensor) - the batch's
+        swing_state goes into the QcBatchIn, any other into the io field of its name; marshal(io, bi, n, dev): what else the call
+        marshals, returning the tensors it handed over; `table`, `want`, `out`, `extra`: _outputs'; `aliases`: (io field, output
+        name) pairs, io fields that point at an output.  Validates in that order and launches nothing.  Returns (launch, res);
+        launch holds on to every tensor named here, so none a launch reads can be forgotten."""
+        import torch
+
+        io = io_type()
+        getattr(self._lib, default)(C.byref(io))
+        n, dev, bi = self._readonly_batch(who, batch, fields, io, own, sizing, none)
+        if _check_tensor("status", status, n, None, torch.int32, dev, False):
+            io.status = status.data_ptr()
+        c = None if command is None else self._marshal_command(n, command, need_state)
+        for field, value in (scalars or {}).items():
+            setattr(io, field, float(value))
+        for field, t, itemsize in records:
+            if _record_tensor(field, t, n, itemsize, dev):
+                setattr(bi if field == "swing_state" else io, field, t.data_ptr())
+        marshalled = marshal(io, bi, n, dev) if marshal is not None else ()
+        res = _outputs(who, table, want, out, n, dev, io, extra)
+        for field, output in aliases:
+            setattr(io, field, res[output].data_ptr())
+        args = (n, C.byref(bi)) + (() if c is None else (C.byref(c),)) + (C.byref(io), self._stream_ptr(stream))
+        held = (batch, command, status, [t for _, t, _ in own], [t for _, t, _ in records], marshalled, res, bi, c, io)
+        return self._launcher(name, args, held, invalid), res
+
     def plan_certify(self, batch, grf_body, act_tol=1e-7, primal_tol=1e-7, stat_tol=1e-8, want=("primal", "stationarity"), summary=True,
                      out=None, stream=None):
         """certify_batch() marshalled once: returns (launch, out), `launch()` being one qc_certify_batch call (graph-capturable) on
         tensors that are read in place.  Planning launches nothing.  `out`: a dict of tensors to write into instead of new ones
         (every name in `want`, and "summary" if summary=True)."""
-        io = _lib.QcCertifyIo()
-        self._lib.qc_default_certify(C.byref(io))
-        n, dev, bi = self._readonly_batch("certify", batch, _READONLY_FIELDS, io, [("grf_body", grf_body, 12)])
-        io.act_tol, io.primal_tol, io.stat_tol = float(act_tol), float(primal_tol), float(stat_tol)
         extra = [("summary", (CERTIFY_SUMMARY_DTYPE.itemsize,), "uint8")] if summary else []
-        res = _outputs("certify", _CERTIFY_OUTPUTS, want, out, n, dev, io, extra)
-        args = (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
-        return self._launcher("qc_certify_batch", args, (batch, grf_body, res, bi, io)), res
+        return self._plan("qc_certify_batch", "certify", _lib.QcCertifyIo, "qc_default_certify", batch, _READONLY_FIELDS, [("grf_body", grf_body, 12)],
+                          _CERTIFY_OUTPUTS, want, out, stream, extra, dict(act_tol=act_tol, primal_tol=primal_tol, stat_tol=stat_tol), invalid=RuntimeError)
 
     def certify_batch(self, batch, grf_body, act_tol=1e-7, primal_tol=1e-7, stat_tol=1e-8, want=("primal", "stationarity"), summary=True,
                       out=None, stream=None):
@@ -823,22 +868,16 @@ class BalanceController:
         a uint8 tensor holding one qc_certify_summary record (certify_summary() reads it on the host).  The contact mask is
         batch["stance"], else the phase rule on batch["gait_phase"] as it is now, else all stance; gait_dt and the swing arrays are
         ignored, nothing of `batch` is written.  Asynchronous on `stream`, no synchronisation.  Returns the dict of device tensors."""
-        launch, res = self.plan_certify(batch, grf_body, act_tol, primal_tol, stat_tol, want, summary, out, stream)
-        launch()
-        return res
+        return _launched(self.plan_certify(batch, grf_body, act_tol, primal_tol, stat_tol, want, summary, out, stream))
 
     # ------------------------------------------------------ sensitivity of a solved batch
     def plan_sensitivity(self, batch, grf_body, grf_bar, want=("adjoint", "b_bar"), act_tol=1e-7, out=None, stream=None):
         """sensitivity_batch() marshalled once: returns (launch, out), `launch()` being one qc_sensitivity_batch call
         (graph-capturable) on tensors that are read in place.  Planning launches nothing.  `out`: a dict of tensors to write into
         instead of new ones (every name in `want`).  A call the library refuses raises ValueError with its message, from launch()."""
-        io = _lib.QcSensitivityIo()
-        self._lib.qc_default_sensitivity(C.byref(io))
-        n, dev, bi = self._readonly_batch("sensitivity", batch, _READONLY_FIELDS, io, [("grf_body", grf_body, 12), ("grf_bar", grf_bar, 12)])
-        io.act_tol = float(act_tol)
-        res = _outputs("sensitivity", _SENSITIVITY_OUTPUTS, want, out, n, dev, io)
-        args = (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
-        return self._launcher("qc_sensitivity_batch", args, (batch, grf_body, grf_bar, res, bi, io), ValueError), res
+        own = [("grf_body", grf_body, 12), ("grf_bar", grf_bar, 12)]
+        return self._plan("qc_sensitivity_batch", "sensitivity", _lib.QcSensitivityIo, "qc_default_sensitivity", batch, _READONLY_FIELDS, own,
+                          _SENSITIVITY_OUTPUTS, want, out, stream, scalars=dict(act_tol=act_tol))
 
     def sensitivity_batch(self, batch, grf_body, grf_bar, want=("adjoint", "b_bar"), act_tol=1e-7, out=None, stream=None):
         """The adjoint of the balance QP on the active face of `grf_body` [n,12] (as control_batch() wrote it) for the batch the
@@ -849,21 +888,15 @@ class BalanceController:
         their cotangents come from sensitivity_rotation_batch(), given this call's b_bar and feet_bar; the cotangents of the
         handle's parameters come from sensitivity_params_batch(), given this call's adjoint.  Nothing of `batch` is written.  Asynchronous on `stream`,
         no synchronisation.  Returns the dict of device tensors; ValueError with the library's message for a call it refuses."""
-        launch, res = self.plan_sensitivity(batch, grf_body, grf_bar, want, act_tol, out, stream)
-        launch()
-        return res
+        return _launched(self.plan_sensitivity(batch, grf_body, grf_bar, want, act_tol, out, stream))
 
     def plan_sensitivity_rotation(self, batch, grf_body, grf_bar, b_bar, feet_bar, want=("Rwb_bar", "Rwb_d_bar"), out=None, stream=None):
         """sensitivity_rotation_batch() marshalled once: returns (launch, out), `launch()` being one qc_sensitivity_rot_batch call
         (graph-capturable) on tensors that are read in place.  Planning launches nothing.  `out`: a dict of tensors to write into
         instead of new ones (every name in `want`).  A call the library refuses raises ValueError with its message, from launch()."""
-        io = _lib.QcSensitivityRotIo()
-        self._lib.qc_default_sensitivity_rot(C.byref(io))
         own = [("grf_body", grf_body, 12), ("grf_bar", grf_bar, 12), ("b_bar", b_bar, 6), ("feet_bar", feet_bar, 12)]
-        n, dev, bi = self._readonly_batch("sensitivity_rotation", batch, _STATE_FIELDS, io, own)  # (no contact mask: swing feet carry zeros)
-        res = _outputs("sensitivity_rotation", _SENSITIVITY_ROT_OUTPUTS, want, out, n, dev, io)
-        args = (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
-        return self._launcher("qc_sensitivity_rot_batch", args, (batch, grf_body, grf_bar, b_bar, feet_bar, res, bi, io), ValueError), res
+        return self._plan("qc_sensitivity_rot_batch", "sensitivity_rotation", _lib.QcSensitivityRotIo, "qc_default_sensitivity_rot", batch,
+                          _STATE_FIELDS, own, _SENSITIVITY_ROT_OUTPUTS, want, out, stream)  # (no contact mask: swing feet carry zeros)
 
     def sensitivity_rotation_batch(self, batch, grf_body, grf_bar, b_bar, feet_bar, want=("Rwb_bar", "Rwb_d_bar"), out=None, stream=None):
         """The cotangents of Rwb and Rwb_d that sensitivity_batch() leaves out (qc_sensitivity_rot_batch, include/qc_balance.h;
@@ -875,9 +908,7 @@ class BalanceController:
         holds, one-sided for robots with bit 0 of its flags, NaN for robots with bit 1.  Nothing of `batch` is written.
         Asynchronous on `stream`, no synchronisation.  Returns the dict of device tensors; ValueError with the library's message for
         a call it refuses."""
-        launch, res = self.plan_sensitivity_rotation(batch, grf_body, grf_bar, b_bar, feet_bar, want, out, stream)
-        launch()
-        return res
+        return _launched(self.plan_sensitivity_rotation(batch, grf_body, grf_bar, b_bar, feet_bar, want, out, stream))
 
     def parameter_tensor(self):
         """The handle's own parameters as a new float64 [211] tensor on its device, in PARAM_LAYOUT's order (the doubles of
@@ -892,19 +923,11 @@ class BalanceController:
         """sensitivity_params_batch() marshalled once: returns (launch, out), `launch()` being one qc_sensitivity_param_batch call
         (graph-capturable) on tensors that are read in place.  Planning launches nothing.  `out`: a dict of tensors to write into
         instead of new ones (every name in `want`).  A call the library refuses raises ValueError with its message, from launch()."""
-        io = _lib.QcSensitivityParamIo()
-        self._lib.qc_default_sensitivity_param(C.byref(io))
         own = [("grf_body", grf_body, 12), ("grf_bar", grf_bar, 12), ("adjoint", adjoint, 12)]
-        n, dev, bi = self._readonly_batch("sensitivity_params", batch, _READONLY_FIELDS, io, own)
-        io.act_tol = float(act_tol)
-        unknown = [w for w in want if w not in ("param_bar", "param_bar_rows")]
-        if unknown:
-            raise ValueError(f"sensitivity_params: unknown output(s) {unknown}; want is a subset of ('param_bar', 'param_bar_rows')")
-        rows = tuple(w for w in want if w == "param_bar_rows")
-        extra = [("param_bar", (_lib.PARAM_COUNT,), "float64")] if "param_bar" in want else []
-        res = _outputs("sensitivity_params", _SENSITIVITY_PARAM_OUTPUTS, rows, out, n, dev, io, extra)
-        args = (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
-        return self._launcher("qc_sensitivity_param_batch", args, (batch, grf_body, grf_bar, adjoint, res, bi, io), ValueError), res
+        rows, extra = _rows_and_sum(want, "param_bar", (_lib.PARAM_COUNT,))
+        table = dict(param_bar=None, **_SENSITIVITY_PARAM_OUTPUTS)  # (both names are known; only the rows are made per robot)
+        return self._plan("qc_sensitivity_param_batch", "sensitivity_params", _lib.QcSensitivityParamIo, "qc_default_sensitivity_param", batch,
+                          _READONLY_FIELDS, own, table, rows, out, stream, extra, dict(act_tol=act_tol))
 
     def sensitivity_params_batch(self, batch, grf_body, grf_bar, adjoint, want=("param_bar",), act_tol=1e-7, out=None, stream=None):
         """The cotangents of the handle's own parameters (qc_sensitivity_param_batch, include/qc_balance.h; INTEGRATION.md
@@ -920,9 +943,7 @@ class BalanceController:
         is NaN.  Nothing of `batch` is written.  Asynchronous on `stream`, no synchronisation.  For n = 0 nothing is launched and the
         outputs stay as they were (new ones: zeros).  Returns the dict of device tensors; ValueError with the library's message for
         a call it refuses."""
-        launch, res = self.plan_sensitivity_params(batch, grf_body, grf_bar, adjoint, want, act_tol, out, stream)
-        launch()
-        return res
+        return _launched(self.plan_sensitivity_params(batch, grf_body, grf_bar, adjoint, want, act_tol, out, stream))
 
     def plan_sensitivity_kinematics(self, batch, grf_body=None, status=None, joint_tau_bar=None, feet_bar=None, grf_bar_in=None,
                                     joint_q_bar_in=None, want=("joint_q_bar",), out=None, stream=None):
@@ -930,19 +951,10 @@ class BalanceController:
         (graph-capturable) on tensors that are read in place.  Planning launches nothing.  `out`: a dict of tensors to write into
         instead of new ones (every name in `want`) - out["grf_bar"] may be grf_bar_in and out["joint_q_bar"] joint_q_bar_in.  A call
         the library refuses raises ValueError with its message, from launch()."""
-        import torch
-
-        io = _lib.QcSensitivityKinIo()
-        self._lib.qc_default_sensitivity_kin(C.byref(io))
         own = [("grf_body", grf_body, 12), ("joint_tau_bar", joint_tau_bar, 12), ("feet_bar", feet_bar, 12), ("grf_bar_in", grf_bar_in, 12),
                ("joint_q_bar_in", joint_q_bar_in, 12)]
-        n, dev, bi = self._readonly_batch("sensitivity_kinematics", batch, _KINEMATICS_FIELDS, io, own)  # (no state array is read)
-        if _check_tensor("status", status, n, None, torch.int32, dev, False):
-            io.status = status.data_ptr()
-        res = _outputs("sensitivity_kinematics", _SENSITIVITY_KIN_OUTPUTS, want, out, n, dev, io)
-        args = (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
-        keep = (batch, grf_body, status, joint_tau_bar, feet_bar, grf_bar_in, joint_q_bar_in, res, bi, io)
-        return self._launcher("qc_sensitivity_kin_batch", args, keep, ValueError), res
+        return self._plan("qc_sensitivity_kin_batch", "sensitivity_kinematics", _lib.QcSensitivityKinIo, "qc_default_sensitivity_kin", batch,
+                          _KINEMATICS_FIELDS, own, _SENSITIVITY_KIN_OUTPUTS, want, out, stream, status=status)  # (no state array is read)
 
     def sensitivity_kinematics_batch(self, batch, grf_body=None, status=None, joint_tau_bar=None, feet_bar=None, grf_bar_in=None,
                                      joint_q_bar_in=None, want=("joint_q_bar",), out=None, stream=None):
@@ -958,9 +970,7 @@ class BalanceController:
         is unmasked.  Out of scope: the swing legs' PD torques (their joint_tau_bar is ignored), commander mode, the cotangents of
         the kinematic constants and the torque limits.  Nothing of `batch` is written.  Asynchronous on `stream`, no synchronisation.
         Returns the dict of device tensors; ValueError with the library's message for a call it refuses."""
-        launch, res = self.plan_sensitivity_kinematics(batch, grf_body, status, joint_tau_bar, feet_bar, grf_bar_in, joint_q_bar_in, want, out, stream)
-        launch()
-        return res
+        return _launched(self.plan_sensitivity_kinematics(batch, grf_body, status, joint_tau_bar, feet_bar, grf_bar_in, joint_q_bar_in, want, out, stream))
 
     def plan_sensitivity_swing(self, batch, joint_tau_bar, want=_SENSITIVITY_SWING_WANT, out=None, joint_q_bar_in=None, Rwb_bar_in=None,
                                x_bar_in=None, stream=None):
@@ -968,20 +978,10 @@ class BalanceController:
         (graph-capturable) on tensors that are read in place.  Planning launches nothing.  `out`: a dict of tensors to write into
         instead of new ones (every name in `want`) - out["joint_q_bar"] may be joint_q_bar_in, out["Rwb_bar"] Rwb_bar_in and
         out["x_bar"] x_bar_in.  A call the library refuses raises ValueError with its message, from launch()."""
-        import torch
-
-        io = _lib.QcSensitivitySwingIo()
-        self._lib.qc_default_sensitivity_swing(C.byref(io))
         own = [("joint_tau_bar", joint_tau_bar, 12), ("joint_q_bar_in", joint_q_bar_in, 12), ("Rwb_bar_in", Rwb_bar_in, 9), ("x_bar_in", x_bar_in, 3)]
-        n, dev, bi = self._readonly_batch("sensitivity_swing", batch, _SWING_FIELDS, io, own)
-        ss = batch.get("swing_state")  # (handed over so that the library names its refusal)
-        if _check_tensor("swing_state", ss, n, SWING_STATE_DTYPE.itemsize, torch.uint8, dev, False,
-                         msg="swing_state: need a contiguous uint8 tensor of n * 224 bytes on the device"):
-            bi.swing_state = ss.data_ptr()
-        res = _outputs("sensitivity_swing", _SENSITIVITY_SWING_OUTPUTS, want, out, n, dev, io)
-        args = (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
-        keep = (batch, joint_tau_bar, joint_q_bar_in, Rwb_bar_in, x_bar_in, res, bi, io)
-        return self._launcher("qc_sensitivity_swing_batch", args, keep, ValueError), res
+        return self._plan("qc_sensitivity_swing_batch", "sensitivity_swing", _lib.QcSensitivitySwingIo, "qc_default_sensitivity_swing", batch,
+                          _SWING_FIELDS, own, _SENSITIVITY_SWING_OUTPUTS, want, out, stream,
+                          records=[("swing_state", batch.get("swing_state"), SWING_STATE_DTYPE.itemsize)])  # (the library names its refusal)
 
     def sensitivity_swing_batch(self, batch, joint_tau_bar, want=_SENSITIVITY_SWING_WANT, out=None, joint_q_bar_in=None, Rwb_bar_in=None,
                                 x_bar_in=None, stream=None):
@@ -997,33 +997,17 @@ class BalanceController:
         finite, or at a singular J(q_ref) - NaN in its rows and in the robot's Rwb_bar and x_bar.  Nothing of `batch` is written.
         Asynchronous on `stream`, no synchronisation.  Returns the dict of device tensors; ValueError with the library's message for
         a call it refuses."""
-        launch, res = self.plan_sensitivity_swing(batch, joint_tau_bar, want, out, joint_q_bar_in, Rwb_bar_in, x_bar_in, stream)
-        launch()
-        return res
+        return _launched(self.plan_sensitivity_swing(batch, joint_tau_bar, want, out, joint_q_bar_in, Rwb_bar_in, x_bar_in, stream))
 
     # ------------------------------------------- the swing references as a launch of their own, and their reverse pass
-    def _swing_reference_batch(self, who, batch, io, own):
-        """_readonly_batch() for the two swing-reference calls, plus the batch's swing_state record."""
-        import torch
-
-        n, dev, bi = self._readonly_batch(who, batch, _SWING_REFERENCE_FIELDS, io, own)
-        ss = batch.get("swing_state")
-        if _check_tensor("swing_state", ss, n, SWING_STATE_DTYPE.itemsize, torch.uint8, dev, False,
-                         msg="swing_state: need a contiguous uint8 tensor of n * 224 bytes on the device"):
-            bi.swing_state = ss.data_ptr()
-        return n, dev, bi
-
     def plan_swing_reference(self, batch, want=("swing_pos", "swing_vel"), out=None, stream=None):
         """swing_reference_batch() marshalled once: returns (launch, out), `launch()` being one qc_swing_reference_batch call
         (graph-capturable) on tensors that are read and updated in place.  Planning launches nothing.  `out`: a dict of tensors to
         write into instead of new ones (every name in `want`).  A call the library refuses raises ValueError with its message, from
         launch()."""
-        io = _lib.QcSwingReferenceIo()
-        self._lib.qc_default_swing_reference(C.byref(io))
-        n, dev, bi = self._swing_reference_batch("swing_reference", batch, io, [])
-        res = _outputs("swing_reference", _SWING_REFERENCE_OUTPUTS, want, out, n, dev, io)
-        args = (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
-        return self._launcher("qc_swing_reference_batch", args, (batch, res, bi, io), ValueError), res
+        return self._plan("qc_swing_reference_batch", "swing_reference", _lib.QcSwingReferenceIo, "qc_default_swing_reference", batch,
+                          _SWING_REFERENCE_FIELDS, [], _SWING_REFERENCE_OUTPUTS, want, out, stream,
+                          records=[("swing_state", batch.get("swing_state"), SWING_STATE_DTYPE.itemsize)])  # (the library names its refusal)
 
     def swing_reference_batch(self, batch, want=("swing_pos", "swing_vel"), out=None, stream=None):
         """The front half of the tick as a launch of its own (qc_swing_reference_batch, include/qc_balance.h; INTEGRATION.md
@@ -1035,9 +1019,7 @@ class BalanceController:
         and "planned" uint8 [n] (bit l: leg l was replanned by this call).  control_batch() on the returned references and the phases
         this call left gives the tick's joint_tau, grf_body and status bit for bit.  Asynchronous on `stream`, no synchronisation.
         Returns the dict of device tensors; ValueError with the library's message for a call it refuses."""
-        launch, res = self.plan_swing_reference(batch, want, out, stream)
-        launch()
-        return res
+        return _launched(self.plan_swing_reference(batch, want, out, stream))
 
     def plan_swing_reference_adjoint(self, batch, state_before, cotangents, want=_SWING_REFERENCE_ADJOINT_WANT, out=None, Rwb_bar_in=None,
                                      x_bar_in=None, xdot_bar_in=None, w_bar_in=None, joint_q_bar_in=None, stream=None):
@@ -1046,24 +1028,14 @@ class BalanceController:
         a dict of tensors to write into instead of new ones (every name in `want`) - an output may be its `_in` tensor, and
         out["p_start_bar"] / out["p_final_bar"] may be cotangents["p_start"] / cotangents["p_final"].  A call the library refuses raises
         ValueError with its message, from launch()."""
-        import torch
-
-        io = _lib.QcSwingReferenceAdjointIo()
-        self._lib.qc_default_swing_reference_adjoint(C.byref(io))
-        unknown = [k for k in cotangents if k not in _SWING_REFERENCE_COTANGENTS]
-        if unknown:
-            raise ValueError(f"swing_reference_adjoint: unknown cotangent(s) {unknown}; the call's outputs are {tuple(_SWING_REFERENCE_COTANGENTS)}")
+        _known_cotangents("swing_reference_adjoint", cotangents, _SWING_REFERENCE_COTANGENTS)
         own = [(_SWING_REFERENCE_COTANGENTS[k], t, 12) for k, t in cotangents.items()]
         own += [("Rwb_bar_in", Rwb_bar_in, 9), ("x_bar_in", x_bar_in, 3), ("xdot_bar_in", xdot_bar_in, 3), ("w_bar_in", w_bar_in, 3),
                 ("joint_q_bar_in", joint_q_bar_in, 12)]
-        n, dev, bi = self._swing_reference_batch("swing_reference_adjoint", batch, io, own)
-        if _check_tensor("state_before", state_before, n, SWING_STATE_DTYPE.itemsize, torch.uint8, dev, False,
-                         msg="state_before: need a contiguous uint8 tensor of n * 224 bytes on the device"):
-            io.state_before = state_before.data_ptr()
-        res = _outputs("swing_reference_adjoint", _SWING_REFERENCE_ADJOINT_OUTPUTS, want, out, n, dev, io)
-        args = (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
-        keep = (batch, state_before, cotangents, Rwb_bar_in, x_bar_in, xdot_bar_in, w_bar_in, joint_q_bar_in, res, bi, io)
-        return self._launcher("qc_swing_reference_adjoint_batch", args, keep, ValueError), res
+        return self._plan("qc_swing_reference_adjoint_batch", "swing_reference_adjoint", _lib.QcSwingReferenceAdjointIo,
+                          "qc_default_swing_reference_adjoint", batch, _SWING_REFERENCE_FIELDS, own, _SWING_REFERENCE_ADJOINT_OUTPUTS, want, out, stream,
+                          records=[("swing_state", batch.get("swing_state"), SWING_STATE_DTYPE.itemsize),
+                                   ("state_before", state_before, SWING_STATE_DTYPE.itemsize)])
 
     def swing_reference_adjoint_batch(self, batch, state_before, cotangents, want=_SWING_REFERENCE_ADJOINT_WANT, out=None, Rwb_bar_in=None,
                                       x_bar_in=None, xdot_bar_in=None, w_bar_in=None, joint_q_bar_in=None, stream=None):
@@ -1078,10 +1050,8 @@ class BalanceController:
         in every row of the robot.  The clock and the contact mask are held: no cotangent of the phases.  Nothing of `batch` is written.
         Asynchronous on `stream`, no synchronisation.  Returns the dict of device tensors; ValueError with the library's message for a
         call it refuses."""
-        launch, res = self.plan_swing_reference_adjoint(batch, state_before, cotangents, want, out, Rwb_bar_in, x_bar_in, xdot_bar_in, w_bar_in,
-                                                        joint_q_bar_in, stream)
-        launch()
-        return res
+        return _launched(self.plan_swing_reference_adjoint(batch, state_before, cotangents, want, out, Rwb_bar_in, x_bar_in, xdot_bar_in, w_bar_in,
+                                                           joint_q_bar_in, stream))
 
     def swing_reference_autograd(self, batch, swing_state, p_start, p_final):
         """swing_reference_batch() with a gradient, OUT OF PLACE in the record: returns (swing_pos, swing_vel, p_start', p_final',
@@ -1097,46 +1067,37 @@ class BalanceController:
         return swing_reference_autograd(self, batch, swing_state, p_start, p_final)
 
     # ------------------------------------------- the virtual support polygon: the desired COM from the gait, and its reverse pass
-    def _support_polygon_batch(self, who, batch, schedule, world, io, own):
-        """The batch, the schedule and the mode of the two support-polygon calls: n from gait_phase (else feet, else joint_q), a
-        QcBatchIn from whatever of _SUPPORT_POLYGON_FIELDS the batch holds - and its swing_state, so that the library names its
-        refusal -, the float64 arrays of `own` ((name, tensor, k) entries) set in `io`.  Returns (n, dev, bi)."""
+    def _plan_polygon(self, name, who, io_type, default, batch, schedule, world, own, table, want, out, stream, extra=(), mode=None, gain=1.0,
+                      aliases=()):
+        """_plan for the polygon and COM-reference calls: n from gait_phase (else feet, else joint_q), the batch's swing_state handed
+        over unchecked so that the library names its refusal, the schedule and the mode - `world`, and the COM reference's `mode` and
+        `gain`."""
         import torch
 
-        dev = torch.device("cuda", self.device)
-        sized = [batch.get(k) for k in ("gait_phase", "feet", "joint_q") if batch.get(k) is not None]
-        if not sized:
-            raise ValueError(f"{who}: the batch holds neither gait_phase nor feet nor joint_q")
-        n = sized[0].shape[0]
-        bi = _lib.QcBatchIn()
-        for name, k, dtype in _SUPPORT_POLYGON_FIELDS:
-            t = batch.get(name)
-            if _check_tensor(name, t, n, k, getattr(torch, dtype), dev, False):
-                setattr(bi, name, t.data_ptr())
-        if batch.get("swing_state") is not None:
-            bi.swing_state = batch["swing_state"].data_ptr()
-        for name, t, k in own:
-            if _check_tensor(name, t, n, k, torch.float64, dev, False, "float64"):
-                setattr(io, name, t.data_ptr())
-        if schedule is not None:
-            shared = schedule.dim() == 2
-            if schedule.dtype != torch.float64 or not schedule.is_contiguous() or schedule.device != dev or \
-                    tuple(schedule.shape) != ((4, 4) if shared else (n, 4, 4)):
-                raise ValueError(f"schedule: need contiguous float64 [4,4] (shared) or [{n},4,4] on {dev}")
-            io.schedule, io.schedule_shared = schedule.data_ptr(), int(shared)
-        io.world = int(bool(world))
-        return n, dev, bi
+        def marshal(io, bi, n, dev):
+            if batch.get("swing_state") is not None:
+                bi.swing_state = batch["swing_state"].data_ptr()
+            if schedule is not None:
+                shared = schedule.dim() == 2
+                if schedule.dtype != torch.float64 or not schedule.is_contiguous() or schedule.device != dev or \
+                        tuple(schedule.shape) != ((4, 4) if shared else (n, 4, 4)):
+                    raise ValueError(f"schedule: need contiguous float64 [4,4] (shared) or [{n},4,4] on {dev}")
+                io.schedule, io.schedule_shared = schedule.data_ptr(), int(shared)
+            io.world = int(bool(world))
+            if mode is not None:
+                io.mode, io.gain = _lib.COM_MODES[mode], float(gain)
+            return batch.get("swing_state"), schedule
+
+        return self._plan(name, who, io_type, default, batch, _SUPPORT_POLYGON_FIELDS, own, table, want, out, stream, extra,
+                          sizing=[batch.get(k) for k in ("gait_phase", "feet", "joint_q")], none="the batch holds neither gait_phase nor feet nor joint_q",
+                          marshal=marshal, aliases=aliases)
 
     def plan_support_polygon(self, batch, schedule, world=False, want=("com_xy",), out=None, stream=None):
         """support_polygon_batch() marshalled once: returns (launch, out), `launch()` being one qc_support_polygon_batch call
         (graph-capturable) on tensors that are read in place.  Planning launches nothing.  `out`: a dict of tensors to write into
         instead of new ones (every name in `want`).  A call the library refuses raises ValueError with its message, from launch()."""
-        io = _lib.QcSupportPolygonIo()
-        self._lib.qc_default_support_polygon(C.byref(io))
-        n, dev, bi = self._support_polygon_batch("support_polygon", batch, schedule, world, io, [])
-        res = _outputs("support_polygon", _SUPPORT_POLYGON_OUTPUTS, want, out, n, dev, io)
-        args = (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
-        return self._launcher("qc_support_polygon_batch", args, (batch, schedule, res, bi, io), ValueError), res
+        return self._plan_polygon("qc_support_polygon_batch", "support_polygon", _lib.QcSupportPolygonIo, "qc_default_support_polygon", batch, schedule,
+                                  world, [], _SUPPORT_POLYGON_OUTPUTS, want, out, stream)
 
     def support_polygon_batch(self, batch, schedule, world=False, want=("com_xy",), out=None, stream=None):
         """The reference's virtual support polygon (SupportPolygon::position; qc_support_polygon_batch, include/qc_balance.h;
@@ -1149,9 +1110,7 @@ class BalanceController:
         `want`: any of "com_xy" [n,2], "weights" [n,4], "flags" int32 [n] (bit l: the denominator of leg l's virtual point is zero
         or not finite - the reference's 0/0, reproduced: com_xy is NaN).  Asynchronous on `stream`, no synchronisation.  Returns the
         dict of device tensors; ValueError with the library's message for a call it refuses."""
-        launch, res = self.plan_support_polygon(batch, schedule, world, want, out, stream)
-        launch()
-        return res
+        return _launched(self.plan_support_polygon(batch, schedule, world, want, out, stream))
 
     def plan_support_polygon_adjoint(self, batch, schedule, com_xy_bar, world=False, want=_SUPPORT_POLYGON_ADJOINT_WANT, out=None,
                                      feet_bar_in=None, Rwb_bar_in=None, x_bar_in=None, phase_bar_in=None, schedule_bar_in=None, stream=None):
@@ -1159,15 +1118,10 @@ class BalanceController:
         qc_support_polygon_adjoint_batch call (graph-capturable) on tensors that are read in place.  Planning launches nothing.
         `out`: a dict of tensors to write into instead of new ones (every name in `want`) - an output may be its `_in` tensor.  A
         call the library refuses raises ValueError with its message, from launch()."""
-        io = _lib.QcSupportPolygonAdjointIo()
-        self._lib.qc_default_support_polygon_adjoint(C.byref(io))
         own = [("com_xy_bar", com_xy_bar, 2), ("feet_bar_in", feet_bar_in, 12), ("Rwb_bar_in", Rwb_bar_in, 9), ("x_bar_in", x_bar_in, 3),
                ("phase_bar_in", phase_bar_in, 4), ("schedule_bar_in", schedule_bar_in, 16)]
-        n, dev, bi = self._support_polygon_batch("support_polygon_adjoint", batch, schedule, world, io, own)
-        res = _outputs("support_polygon_adjoint", _SUPPORT_POLYGON_ADJOINT_OUTPUTS, want, out, n, dev, io)
-        args = (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
-        keep = (batch, schedule, com_xy_bar, feet_bar_in, Rwb_bar_in, x_bar_in, phase_bar_in, schedule_bar_in, res, bi, io)
-        return self._launcher("qc_support_polygon_adjoint_batch", args, keep, ValueError), res
+        return self._plan_polygon("qc_support_polygon_adjoint_batch", "support_polygon_adjoint", _lib.QcSupportPolygonAdjointIo,
+                                  "qc_default_support_polygon_adjoint", batch, schedule, world, own, _SUPPORT_POLYGON_ADJOINT_OUTPUTS, want, out, stream)
 
     def support_polygon_adjoint_batch(self, batch, schedule, com_xy_bar, world=False, want=_SUPPORT_POLYGON_ADJOINT_WANT, out=None,
                                       feet_bar_in=None, Rwb_bar_in=None, x_bar_in=None, phase_bar_in=None, schedule_bar_in=None, stream=None):
@@ -1179,10 +1133,8 @@ class BalanceController:
         added to the outputs of those names; each may be the output's own tensor.  The contact mask is held.  A robot the forward
         rule flags gets NaN in every row.  Nothing of `batch` is written.  Asynchronous on `stream`, no synchronisation.  Returns the
         dict of device tensors; ValueError with the library's message for a call it refuses."""
-        launch, res = self.plan_support_polygon_adjoint(batch, schedule, com_xy_bar, world, want, out, feet_bar_in, Rwb_bar_in, x_bar_in,
-                                                        phase_bar_in, schedule_bar_in, stream)
-        launch()
-        return res
+        return _launched(self.plan_support_polygon_adjoint(batch, schedule, com_xy_bar, world, want, out, feet_bar_in, Rwb_bar_in, x_bar_in,
+                                                           phase_bar_in, schedule_bar_in, stream))
 
     def support_polygon_autograd(self, batch, schedule, world=False):
         """support_polygon_batch() with a gradient: returns com_xy [n,2], differentiable in batch["feet"] - or batch["joint_q"],
@@ -1195,27 +1147,16 @@ class BalanceController:
         return support_polygon_autograd(self, batch, schedule, world)
 
     # ------------------------------------------- the desired COM of a step from the polygon, and its reverse pass
-    def _com_reference_io(self, who, io, batch, schedule, mode, gain, own):
-        """What the two COM-reference calls share on top of _support_polygon_batch (world mode): the mode and the gain."""
-        if mode not in _lib.COM_MODES:
-            raise ValueError(f"{who}: mode is one of {tuple(_lib.COM_MODES)}, not {mode!r}")
-        n, dev, bi = self._support_polygon_batch(who, batch, schedule, True, io, own)
-        io.mode, io.gain = _lib.COM_MODES[mode], float(gain)
-        return n, dev, bi
-
     def plan_com_reference(self, batch, schedule, x_d, mode="replace", gain=1.0, want=("x_d",), out=None, stream=None):
         """com_reference_batch() marshalled once: returns (launch, out), `launch()` being one qc_com_reference_batch call
         (graph-capturable) on tensors that are read in place.  Planning launches nothing.  `out`: a dict of tensors to write into
         instead of new ones (every name in `want`; "x_d" is always made) - out["x_d"] may be `x_d` itself.  A call the library
         refuses raises ValueError with its message, from launch()."""
-        io = _lib.QcComReferenceIo()
-        self._lib.qc_default_com_reference(C.byref(io))
-        n, dev, bi = self._com_reference_io("com_reference", io, batch, schedule, mode, gain, [("x_d_in", x_d, 3)])
+        if mode not in _lib.COM_MODES:
+            raise ValueError(f"com_reference: mode is one of {tuple(_lib.COM_MODES)}, not {mode!r}")
         want = tuple(dict.fromkeys(("x_d",) + tuple(want)))
-        res = _outputs("com_reference", _COM_REFERENCE_OUTPUTS, want, out, n, dev, io)
-        io.x_d_out = res["x_d"].data_ptr()
-        args = (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
-        return self._launcher("qc_com_reference_batch", args, (batch, schedule, x_d, res, bi, io), ValueError), res
+        return self._plan_polygon("qc_com_reference_batch", "com_reference", _lib.QcComReferenceIo, "qc_default_com_reference", batch, schedule, True,
+                                  [("x_d_in", x_d, 3)], _COM_REFERENCE_OUTPUTS, want, out, stream, mode=mode, gain=gain, aliases=[("x_d_out", "x_d")])
 
     def com_reference_batch(self, batch, schedule, x_d, mode="replace", gain=1.0, want=("x_d",), out=None, stream=None):
         """The desired COM position of a step from the virtual support polygon (qc_com_reference_batch, include/qc_balance.h;
@@ -1226,9 +1167,7 @@ class BalanceController:
         x_d is leaned, not dragged to the feet.  `want`: "x_d" [n,3] (always), "com_xy" [n,2] (support_polygon_batch's, bit for bit),
         "flags" int32 [n]; a flagged robot (the reference's 0/0) gets NaN in x and y.  out["x_d"] may be `x_d`.  Asynchronous on
         `stream`, no synchronisation.  Returns the dict of device tensors; ValueError with the library's message for a call it refuses."""
-        launch, res = self.plan_com_reference(batch, schedule, x_d, mode, gain, want, out, stream)
-        launch()
-        return res
+        return _launched(self.plan_com_reference(batch, schedule, x_d, mode, gain, want, out, stream))
 
     def plan_com_reference_adjoint(self, batch, schedule, x_d_bar, mode="replace", gain=1.0, want=_COM_REFERENCE_ADJOINT_WANT, out=None,
                                    feet_bar_in=None, Rwb_bar_in=None, x_bar_in=None, phase_bar_in=None, schedule_bar_in=None, stream=None):
@@ -1236,17 +1175,14 @@ class BalanceController:
         call (graph-capturable; two kernels when "schedule_bar_sum" is asked for) on tensors that are read in place.  Planning
         launches nothing.  `out`: a dict of tensors to write into instead of new ones (every name in `want`) - an output may be its
         `_in` tensor, out["x_d_in_bar"] may be `x_d_bar`.  A call the library refuses raises ValueError with its message, from launch()."""
-        io = _lib.QcComReferenceAdjointIo()
-        self._lib.qc_default_com_reference_adjoint(C.byref(io))
+        if mode not in _lib.COM_MODES:
+            raise ValueError(f"com_reference_adjoint: mode is one of {tuple(_lib.COM_MODES)}, not {mode!r}")
         own = [("x_d_out_bar", x_d_bar, 3), ("feet_bar_in", feet_bar_in, 12), ("Rwb_bar_in", Rwb_bar_in, 9), ("x_bar_in", x_bar_in, 3),
                ("phase_bar_in", phase_bar_in, 4), ("schedule_bar_in", schedule_bar_in, 16)]
-        n, dev, bi = self._com_reference_io("com_reference_adjoint", io, batch, schedule, mode, gain, own)
-        rows = tuple(w for w in want if w != "schedule_bar_sum")
-        extra = [("schedule_bar_sum", (4, 4), "float64")] if "schedule_bar_sum" in want else []
-        res = _outputs("com_reference_adjoint", _COM_REFERENCE_ADJOINT_OUTPUTS, rows, out, n, dev, io, extra)
-        args = (n, C.byref(bi), C.byref(io), self._stream_ptr(stream))
-        keep = (batch, schedule, x_d_bar, feet_bar_in, Rwb_bar_in, x_bar_in, phase_bar_in, schedule_bar_in, res, bi, io)
-        return self._launcher("qc_com_reference_adjoint_batch", args, keep, ValueError), res
+        rows, extra = _rows_and_sum(want, "schedule_bar_sum", (4, 4))
+        return self._plan_polygon("qc_com_reference_adjoint_batch", "com_reference_adjoint", _lib.QcComReferenceAdjointIo,
+                                  "qc_default_com_reference_adjoint", batch, schedule, True, own, _COM_REFERENCE_ADJOINT_OUTPUTS, rows, out, stream, extra,
+                                  mode=mode, gain=gain)
 
     def com_reference_adjoint_batch(self, batch, schedule, x_d_bar, mode="replace", gain=1.0, want=_COM_REFERENCE_ADJOINT_WANT, out=None,
                                     feet_bar_in=None, Rwb_bar_in=None, x_bar_in=None, phase_bar_in=None, schedule_bar_in=None, stream=None):
@@ -1260,10 +1196,8 @@ class BalanceController:
         mask is held.  A robot the forward rule flags gets NaN in every row and makes the sum NaN.  Two calls that ask for the sum
         share a buffer of the handle: keep them on one stream.  Asynchronous on `stream`, no synchronisation.  Returns the dict of
         device tensors; ValueError with the library's message for a call it refuses."""
-        launch, res = self.plan_com_reference_adjoint(batch, schedule, x_d_bar, mode, gain, want, out, feet_bar_in, Rwb_bar_in, x_bar_in,
-                                                      phase_bar_in, schedule_bar_in, stream)
-        launch()
-        return res
+        return _launched(self.plan_com_reference_adjoint(batch, schedule, x_d_bar, mode, gain, want, out, feet_bar_in, Rwb_bar_in, x_bar_in,
+                                                         phase_bar_in, schedule_bar_in, stream))
 
     def com_reference_autograd(self, batch, schedule, x_d, mode="replace", gain=1.0):
         """com_reference_batch() with a gradient: returns x_d' [n,3], differentiable in `x_d`, batch["feet"] - or batch["joint_q"],
@@ -1302,13 +1236,8 @@ class BalanceController:
         (graph-capturable) on tensors that are read and updated in place.  Planning launches nothing.  `out`: a dict of tensors to
         write into instead of new ones (every name in `want`).  A call the library refuses raises ValueError with its message, from
         launch()."""
-        io = _lib.QcCommanderStepIo()
-        self._lib.qc_default_commander_step(C.byref(io))
-        n, dev, bi = self._readonly_batch("commander_step", batch, _COMMANDER_STEP_FIELDS, io, [])
-        c = self._marshal_command(n, command)
-        res = _outputs("commander_step", _COMMANDER_STEP_OUTPUTS, want, out, n, dev, io)
-        args = (n, C.byref(bi), C.byref(c), C.byref(io), self._stream_ptr(stream))
-        return self._launcher("qc_commander_step_batch", args, (batch, command, res, bi, c, io), ValueError), res
+        return self._plan("qc_commander_step_batch", "commander_step", _lib.QcCommanderStepIo, "qc_default_commander_step", batch,
+                          _COMMANDER_STEP_FIELDS, [], _COMMANDER_STEP_OUTPUTS, want, out, stream, command=command)
 
     def commander_step_batch(self, batch, command, want=_DESIRED, out=None, stream=None):
         """The commander step of the tick as a launch of its own (qc_commander_step_batch, include/qc_balance.h; INTEGRATION.md
@@ -1318,9 +1247,7 @@ class BalanceController:
         uint8 [n].  For robots that stand and run, control_batch() on those four and the batch's swing_state / gait_dt gives the
         tick's outputs and records bit for bit.  Asynchronous on `stream`, no synchronisation.  Returns the dict of device tensors;
         ValueError with the library's message for a call it refuses."""
-        launch, res = self.plan_commander_step(batch, command, want, out, stream)
-        launch()
-        return res
+        return _launched(self.plan_commander_step(batch, command, want, out, stream))
 
     def plan_commander_step_adjoint(self, batch, command, state_before, cotangents, want=_COMMANDER_STEP_ADJOINT_WANT, out=None, Rwb_bar_in=None,
                                     x_bar_in=None, stream=None):
@@ -1329,24 +1256,12 @@ class BalanceController:
         instead of new ones (every name in `want`) - an output may be its `_in` tensor, out["Vb_bar"] may be cotangents["Vb"], and the
         four `_prev_bar` may be the four desired-state cotangents.  A call the library refuses raises ValueError with its message, from
         launch()."""
-        import torch
-
-        io = _lib.QcCommanderStepAdjointIo()
-        self._lib.qc_default_commander_step_adjoint(C.byref(io))
-        unknown = [k for k in cotangents if k not in _COMMANDER_STEP_COTANGENTS]
-        if unknown:
-            raise ValueError(f"commander_step_adjoint: unknown cotangent(s) {unknown}; the call's outputs are {tuple(_COMMANDER_STEP_COTANGENTS)}")
+        _known_cotangents("commander_step_adjoint", cotangents, _COMMANDER_STEP_COTANGENTS)
         own = [_COMMANDER_STEP_COTANGENTS[k][:1] + (t,) + _COMMANDER_STEP_COTANGENTS[k][1:] for k, t in cotangents.items()]
         own += [("Rwb_bar_in", Rwb_bar_in, 9), ("x_bar_in", x_bar_in, 3)]
-        n, dev, bi = self._readonly_batch("commander_step_adjoint", batch, _COMMANDER_STEP_FIELDS, io, own)
-        c = self._marshal_command(n, command, need_state=False)
-        if _check_tensor("state_before", state_before, n, COMMANDER_STATE_DTYPE.itemsize, torch.uint8, dev, False,
-                         msg=f"state_before: need a contiguous uint8 tensor of n * {COMMANDER_STATE_DTYPE.itemsize} bytes on the device"):
-            io.state_before = state_before.data_ptr()
-        res = _outputs("commander_step_adjoint", _COMMANDER_STEP_ADJOINT_OUTPUTS, want, out, n, dev, io)
-        args = (n, C.byref(bi), C.byref(c), C.byref(io), self._stream_ptr(stream))
-        keep = (batch, command, state_before, cotangents, Rwb_bar_in, x_bar_in, res, bi, c, io)
-        return self._launcher("qc_commander_step_adjoint_batch", args, keep, ValueError), res
+        return self._plan("qc_commander_step_adjoint_batch", "commander_step_adjoint", _lib.QcCommanderStepAdjointIo,
+                          "qc_default_commander_step_adjoint", batch, _COMMANDER_STEP_FIELDS, own, _COMMANDER_STEP_ADJOINT_OUTPUTS, want, out, stream,
+                          command=command, need_state=False, records=[("state_before", state_before, COMMANDER_STATE_DTYPE.itemsize)])
 
     def commander_step_adjoint_batch(self, batch, command, state_before, cotangents, want=_COMMANDER_STEP_ADJOINT_WANT, out=None, Rwb_bar_in=None,
                                      x_bar_in=None, stream=None):
@@ -1360,9 +1275,7 @@ class BalanceController:
         used, so twist_bar[3:6] is not silently zero there.  flags bit 0: a command applied at gimbal lock (R00 = R10 = 0) - NaN in every
         row of the robot.  The latches and branch decisions are held.  Asynchronous on `stream`, no synchronisation.  Returns the dict
         of device tensors; ValueError with the library's message for a call it refuses."""
-        launch, res = self.plan_commander_step_adjoint(batch, command, state_before, cotangents, want, out, Rwb_bar_in, x_bar_in, stream)
-        launch()
-        return res
+        return _launched(self.plan_commander_step_adjoint(batch, command, state_before, cotangents, want, out, Rwb_bar_in, x_bar_in, stream))
 
     def commander_step_autograd(self, batch, command, desired, Vb):
         """commander_step_batch() with a gradient, OUT OF PLACE in the records: returns (Rwb_d, x_d, xdot_d, w_d, Vb', state', run,

@@ -2030,13 +2030,25 @@ static qc::BatchIn readonly_view(const qc_batch_in* in, bool mask) {
                      mask ? in->gait_phase : nullptr, mask ? in->gait_duty : nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 }
 
+// one launch of a kernel without dynamic LDS on a flat grid, checked
+template <class... P, class... A>
+static int launch_flat(void (*kernel)(P...), unsigned blocks, int block, void* stream, const A&... args) {
+  kernel<<<dim3(blocks), dim3(block), 0, (hipStream_t)stream>>>(args...);
+  QC_HIP(hipGetLastError());
+  return QC_OK;
+}
+
 // one launch of a `template <bool KIN>` per-robot kernel - `kin` where `bi` carries joint_q, `feet` where it does not -, checked
 template <class Args>
 static int launch_per_robot(void (*kin)(const qc::DevParams*, long, qc::BatchIn, Args), void (*feet)(const qc::DevParams*, long, qc::BatchIn, Args),
                             unsigned blocks, int block, const qc_handle* h, size_t n, const qc::BatchIn& bi, const Args& a, void* stream) {
-  (bi.joint_q ? kin : feet)<<<dim3(blocks), dim3(block), 0, (hipStream_t)stream>>>(h->d_params, (long)n, bi, a);
-  QC_HIP(hipGetLastError());
-  return QC_OK;
+  return launch_flat(bi.joint_q ? kin : feet, blocks, block, stream, h->d_params, (long)n, bi, a);
+}
+
+// the instantiation of a `template <bool, bool>` kernel that two flags of the call pick
+template <class Fn>
+static Fn pick2(bool first, bool second, Fn tt, Fn tf, Fn ft, Fn ff) {
+  return first ? (second ? tt : tf) : (second ? ft : ff);
 }
 
 extern "C" {
@@ -2120,37 +2132,28 @@ int qc_create_abi(const qc_params* p, int device, qc_handle** out, int abi_versi
   qc_handle* h = new (std::nothrow) qc_handle();
   if (!h) return fail(QC_ERR_INVALID, "qc_create: out of memory");
   h->device = device;
-  if (const int rc = qc::derive_params(p, h->dp, h->tune); rc != QC_OK) { delete h; return rc; }
+  // (from here on a failure goes through qc_destroy, which frees whatever is there - and, as a qc_create that succeeds does, leaves
+  // `device` the calling thread's current device)
+  if (const int rc = qc::derive_params(p, h->dp, h->tune); rc != QC_OK) { qc_destroy(h); return rc; }
   hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) != hipSuccess) { delete h; return fail(QC_ERR_HIP, "qc_create: hipGetDeviceProperties failed"); }
+  if (hipGetDeviceProperties(&prop, device) != hipSuccess) { qc_destroy(h); return fail(QC_ERR_HIP, "qc_create: hipGetDeviceProperties failed"); }
   h->cus = prop.multiProcessorCount;
   if (hipSetDevice(device) != hipSuccess || hipMalloc((void**)&h->d_params, sizeof(qc::DevParams)) != hipSuccess ||
       hipMemcpy(h->d_params, &h->dp, sizeof(qc::DevParams), hipMemcpyHostToDevice) != hipSuccess) {
-    if (h->d_params) (void)hipFree(h->d_params);
-    delete h;
+    qc_destroy(h);
     return fail(QC_ERR_HIP, "qc_create: could not upload the controller constants");
   }
-  // qc_certify_batch's partial buffer (224 KB), allocated here and not at the first certificate: that call may be inside a graph capture
-  if (hipMalloc((void**)&h->certify_parts, sizeof(qc::CertifySummary) * qc::CERTIFY_MAX_PARTIALS) != hipSuccess) {
-    (void)hipFree(h->d_params);
-    delete h;
-    return fail(QC_ERR_HIP, "qc_create: could not allocate the certificate's partial buffer");
-  }
-  // ... and qc_sensitivity_param_batch's (1.7 MB), for the same reason
-  if (hipMalloc((void**)&h->param_parts, sizeof(double) * qc::PARAM_COUNT * qc::SENSITIVITY_PARAM_MAX_BLOCKS) != hipSuccess) {
-    (void)hipFree(h->certify_parts);
-    (void)hipFree(h->d_params);
-    delete h;
-    return fail(QC_ERR_HIP, "qc_create: could not allocate the parameter cotangents' partial buffer");
-  }
-  // ... and qc_com_reference_adjoint_batch's (128 KB)
-  if (hipMalloc((void**)&h->com_parts, sizeof(double) * 16 * qc::COM_SUM_MAX_BLOCKS) != hipSuccess) {
-    (void)hipFree(h->param_parts);
-    (void)hipFree(h->certify_parts);
-    (void)hipFree(h->d_params);
-    delete h;
-    return fail(QC_ERR_HIP, "qc_create: could not allocate the schedule cotangent's partial buffer");
-  }
+  // The handle-owned partial buffers of qc_certify_batch (224 KB), qc_sensitivity_param_batch (1.7 MB) and
+  // qc_com_reference_adjoint_batch (128 KB), allocated here and not at the first call: that call may be inside a graph capture.
+  const struct { void** member; size_t bytes; const char* message; } parts[] = {
+      {(void**)&h->certify_parts, sizeof(qc::CertifySummary) * qc::CERTIFY_MAX_PARTIALS, "qc_create: could not allocate the certificate's partial buffer"},
+      {(void**)&h->param_parts, sizeof(double) * qc::PARAM_COUNT * qc::SENSITIVITY_PARAM_MAX_BLOCKS, "qc_create: could not allocate the parameter cotangents' partial buffer"},
+      {(void**)&h->com_parts, sizeof(double) * 16 * qc::COM_SUM_MAX_BLOCKS, "qc_create: could not allocate the schedule cotangent's partial buffer"}};
+  for (const auto& part : parts)
+    if (hipMalloc(part.member, part.bytes) != hipSuccess) {
+      qc_destroy(h);
+      return fail(QC_ERR_HIP, part.message);
+    }
   *out = h;
   return QC_OK;
 }
@@ -2249,9 +2252,7 @@ int qc_plant_step_batch(qc_handle* h, size_t n, const qc_plant_io* io, void* str
   if (const int rc = qc::plant_constants(h->dp.mass, h->dp.Ib, io, a); rc != QC_OK) return rc;
   QC_HIP(hipSetDevice(h->device));
   const unsigned blocks = (unsigned)((n + qc::PLANT_BLOCK - 1) / qc::PLANT_BLOCK);
-  qc::plant_step_kernel<<<dim3(blocks), dim3(qc::PLANT_BLOCK), 0, (hipStream_t)stream>>>((long)n, a);
-  QC_HIP(hipGetLastError());
-  return QC_OK;
+  return launch_flat(qc::plant_step_kernel, blocks, qc::PLANT_BLOCK, stream, (long)n, a);
 }
 
 void qc_default_plant_adjoint(qc_plant_adjoint_io* io) {
@@ -2265,9 +2266,7 @@ int qc_plant_step_adjoint_batch(qc_handle* h, size_t n, const qc_plant_adjoint_i
   if (const int rc = qc::plant_adjoint_constants(h->dp.mass, h->dp.Ib, io, a); rc != QC_OK) return rc;
   QC_HIP(hipSetDevice(h->device));
   const unsigned blocks = (unsigned)((n + qc::PLANT_BLOCK - 1) / qc::PLANT_BLOCK);
-  qc::plant_step_adjoint_kernel<<<dim3(blocks), dim3(qc::PLANT_BLOCK), 0, (hipStream_t)stream>>>((long)n, a);
-  QC_HIP(hipGetLastError());
-  return QC_OK;
+  return launch_flat(qc::plant_step_adjoint_kernel, blocks, qc::PLANT_BLOCK, stream, (long)n, a);
 }
 
 void qc_default_leg_plant(qc_leg_plant_io* io) {
@@ -2281,9 +2280,7 @@ int qc_leg_plant_step_batch(qc_handle* h, size_t n, const qc_leg_plant_io* io, v
   if (const int rc = qc::leg_plant_constants(h->dp.mass, h->dp.Ib, io, a); rc != QC_OK) return rc;
   QC_HIP(hipSetDevice(h->device));
   const unsigned blocks = (unsigned)((n + qc::LEG_PLANT_BLOCK - 1) / qc::LEG_PLANT_BLOCK);
-  qc::leg_plant_step_kernel<<<dim3(blocks), dim3(qc::LEG_PLANT_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, a);
-  QC_HIP(hipGetLastError());
-  return QC_OK;
+  return launch_flat(qc::leg_plant_step_kernel, blocks, qc::LEG_PLANT_BLOCK, stream, h->d_params, (long)n, a);
 }
 
 void qc_default_leg_plant_adjoint(qc_leg_plant_adjoint_io* io) {
@@ -2297,9 +2294,7 @@ int qc_leg_plant_step_adjoint_batch(qc_handle* h, size_t n, const qc_leg_plant_a
   if (const int rc = qc::leg_plant_adjoint_constants(h->dp.mass, h->dp.Ib, io, a); rc != QC_OK) return rc;
   QC_HIP(hipSetDevice(h->device));
   const unsigned blocks = (unsigned)((n + qc::LEG_PLANT_BLOCK - 1) / qc::LEG_PLANT_BLOCK);
-  qc::leg_plant_step_adjoint_kernel<<<dim3(blocks), dim3(qc::LEG_PLANT_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, a);
-  QC_HIP(hipGetLastError());
-  return QC_OK;
+  return launch_flat(qc::leg_plant_step_adjoint_kernel, blocks, qc::LEG_PLANT_BLOCK, stream, h->d_params, (long)n, a);
 }
 
 void qc_default_certify(qc_certify_io* io) {
@@ -2316,12 +2311,8 @@ int qc_certify_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_cer
                     io->active, io->flags, io->summary ? h->certify_parts : nullptr};
   const unsigned blocks = qc::certify_blocks(n);
   if (const int rc = launch_per_robot(qc::certify_kernel<true>, qc::certify_kernel<false>, blocks, qc::CERTIFY_BLOCK, h, n, readonly_view(in, true), a, stream); rc != QC_OK) return rc;
-  if (io->summary) {
-    qc::certify_summary_kernel<<<dim3(1), dim3(qc::CERTIFY_SUMMARY_BLOCK), 0, (hipStream_t)stream>>>(h->certify_parts, (int)blocks,
-                                                                                                    reinterpret_cast<qc::CertifySummary*>(io->summary));
-    QC_HIP(hipGetLastError());
-  }
-  return QC_OK;
+  if (!io->summary) return QC_OK;
+  return launch_flat(qc::certify_summary_kernel, 1, qc::CERTIFY_SUMMARY_BLOCK, stream, h->certify_parts, (int)blocks, reinterpret_cast<qc::CertifySummary*>(io->summary));
 }
 
 void qc_default_sensitivity(qc_sensitivity_io* io) {
@@ -2358,11 +2349,8 @@ int qc_sensitivity_param_batch(qc_handle* h, size_t n, const qc_batch_in* in, co
   qc::SensitivityParamArgs a{io->grf_body, io->grf_bar, io->adjoint, io->act_tol, io->param_bar_rows, io->param_bar ? h->param_parts : nullptr};
   const unsigned blocks = qc::sensitivity_param_blocks(n);
   if (const int rc = launch_per_robot(qc::sensitivity_param_kernel<true>, qc::sensitivity_param_kernel<false>, blocks, qc::SENSITIVITY_PARAM_BLOCK, h, n, readonly_view(in, true), a, stream); rc != QC_OK) return rc;
-  if (io->param_bar) {
-    qc::sensitivity_param_sum_kernel<<<dim3(1), dim3(qc::SENSITIVITY_PARAM_SUM_BLOCK), 0, (hipStream_t)stream>>>(h->param_parts, (int)blocks, io->param_bar);
-    QC_HIP(hipGetLastError());
-  }
-  return QC_OK;
+  if (!io->param_bar) return QC_OK;
+  return launch_flat(qc::sensitivity_param_sum_kernel, 1, qc::SENSITIVITY_PARAM_SUM_BLOCK, stream, h->param_parts, (int)blocks, io->param_bar);
 }
 
 void qc_default_sensitivity_kin(qc_sensitivity_kin_io* io) { (void)zeroed(io); }
@@ -2374,12 +2362,9 @@ int qc_sensitivity_kin_batch(qc_handle* h, size_t n, const qc_batch_in* in, cons
   const qc::SensitivityKinArgs a{in->joint_q, in->stance, in->gait_phase, in->gait_duty, io->grf_body, io->status, io->joint_tau_bar, io->feet_bar,
                                  io->grf_bar_in, io->joint_q_bar_in, io->grf_bar, io->joint_q_bar};
   const bool tau = io->joint_tau_bar != nullptr, fk = io->feet_bar != nullptr;
-  void (*const fn)(const qc::DevParams*, long, qc::SensitivityKinArgs) =
-      tau ? (fk ? qc::sensitivity_kin_kernel<true, true> : qc::sensitivity_kin_kernel<true, false>)
-          : (fk ? qc::sensitivity_kin_kernel<false, true> : qc::sensitivity_kin_kernel<false, false>);
-  fn<<<dim3(qc::sensitivity_kin_blocks(n)), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)(4 * n), a);
-  QC_HIP(hipGetLastError());
-  return QC_OK;
+  const auto fn = pick2(tau, fk, qc::sensitivity_kin_kernel<true, true>, qc::sensitivity_kin_kernel<true, false>, qc::sensitivity_kin_kernel<false, true>,
+                        qc::sensitivity_kin_kernel<false, false>);
+  return launch_flat(fn, qc::sensitivity_kin_blocks(n), qc::SENSITIVITY_BLOCK, stream, h->d_params, (long)(4 * n), a);
 }
 
 void qc_default_sensitivity_swing(qc_sensitivity_swing_io* io) { (void)zeroed(io); }
@@ -2392,12 +2377,9 @@ int qc_sensitivity_swing_batch(qc_handle* h, size_t n, const qc_batch_in* in, co
                                    io->joint_tau_bar, io->joint_q_bar_in, io->Rwb_bar_in, io->x_bar_in, io->swing_pos_bar, io->swing_vel_bar,
                                    io->joint_q_bar, io->joint_qdot_bar, io->gain_bar, io->Rwb_bar, io->x_bar, io->flags};
   const bool leg = io->swing_pos_bar || io->swing_vel_bar || io->joint_q_bar || io->joint_qdot_bar || io->gain_bar, body = io->Rwb_bar || io->x_bar;
-  void (*const fn)(const qc::DevParams*, long, qc::SensitivitySwingArgs) =
-      leg ? (body ? qc::sensitivity_swing_kernel<true, true> : qc::sensitivity_swing_kernel<true, false>)
-          : (body ? qc::sensitivity_swing_kernel<false, true> : qc::sensitivity_swing_kernel<false, false>);
-  fn<<<dim3(qc::sensitivity_swing_blocks(n)), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)(4 * n), a);
-  QC_HIP(hipGetLastError());
-  return QC_OK;
+  const auto fn = pick2(leg, body, qc::sensitivity_swing_kernel<true, true>, qc::sensitivity_swing_kernel<true, false>,
+                        qc::sensitivity_swing_kernel<false, true>, qc::sensitivity_swing_kernel<false, false>);
+  return launch_flat(fn, qc::sensitivity_swing_blocks(n), qc::SENSITIVITY_BLOCK, stream, h->d_params, (long)(4 * n), a);
 }
 
 void qc_default_swing_reference(qc_swing_reference_io* io) { (void)zeroed(io); }
@@ -2407,9 +2389,7 @@ int qc_swing_reference_batch(qc_handle* h, size_t n, const qc_batch_in* in, cons
   QC_HIP(hipSetDevice(h->device));
   const qc::SwingReferenceArgs a{in->Rwb, in->x, in->xdot, in->w, in->xdot_d, in->joint_q, in->gait_phase, in->stance, in->gait_duty, in->gait_dt,
                                  reinterpret_cast<qc::SwingState*>(in->swing_state), io->swing_pos, io->swing_vel, io->planned};
-  qc::swing_reference_kernel<<<dim3(qc::swing_reference_blocks(n)), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, a);
-  QC_HIP(hipGetLastError());
-  return QC_OK;
+  return launch_flat(qc::swing_reference_kernel, qc::swing_reference_blocks(n), qc::SENSITIVITY_BLOCK, stream, h->d_params, (long)n, a);
 }
 
 void qc_default_swing_reference_adjoint(qc_swing_reference_adjoint_io* io) { (void)zeroed(io); }
@@ -2423,9 +2403,7 @@ int qc_swing_reference_adjoint_batch(qc_handle* h, size_t n, const qc_batch_in* 
                                         io->p_start_next_bar, io->p_final_next_bar, io->Rwb_bar_in, io->x_bar_in, io->xdot_bar_in, io->w_bar_in,
                                         io->joint_q_bar_in, io->Rwb_bar, io->x_bar, io->xdot_bar, io->w_bar, io->xdot_d_bar, io->joint_q_bar,
                                         io->p_start_bar, io->p_final_bar, io->flags};
-  qc::swing_reference_adjoint_kernel<<<dim3(qc::swing_reference_blocks(n)), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, a);
-  QC_HIP(hipGetLastError());
-  return QC_OK;
+  return launch_flat(qc::swing_reference_adjoint_kernel, qc::swing_reference_blocks(n), qc::SENSITIVITY_BLOCK, stream, h->d_params, (long)n, a);
 }
 
 void qc_default_commander_step(qc_commander_step_io* io) { (void)zeroed(io); }
@@ -2435,9 +2413,7 @@ int qc_commander_step_batch(qc_handle* h, size_t n, const qc_batch_in* in, const
   QC_HIP(hipSetDevice(h->device));
   const qc::CommanderStepArgs a{in->Rwb, in->x, cmd->twist, cmd->fresh, reinterpret_cast<qc::CmdState*>(cmd->state), cmd->stand_height, cmd->stand_tol,
                                 cmd->cmd_dt, io->Rwb_d, io->x_d, io->xdot_d, io->w_d, io->run, io->applied};
-  qc::commander_step_kernel<<<dim3(qc::commander_step_blocks(n)), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>((long)n, a);
-  QC_HIP(hipGetLastError());
-  return QC_OK;
+  return launch_flat(qc::commander_step_kernel, qc::commander_step_blocks(n), qc::SENSITIVITY_BLOCK, stream, (long)n, a);
 }
 
 void qc_default_commander_step_adjoint(qc_commander_step_adjoint_io* io) { (void)zeroed(io); }
@@ -2451,9 +2427,7 @@ int qc_commander_step_adjoint_batch(qc_handle* h, size_t n, const qc_batch_in* i
                                        cmd->stand_tol, cmd->cmd_dt, io->Rwb_d_bar, io->x_d_bar, io->xdot_d_bar, io->w_d_bar, io->Vb_next_bar,
                                        io->Rwb_bar_in, io->x_bar_in, io->twist_bar, io->Vb_bar, io->Rwb_bar, io->x_bar, io->Rwb_d_prev_bar,
                                        io->x_d_prev_bar, io->xdot_d_prev_bar, io->w_d_prev_bar, io->flags};
-  qc::commander_step_adjoint_kernel<<<dim3(qc::commander_step_blocks(n)), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>((long)n, a);
-  QC_HIP(hipGetLastError());
-  return QC_OK;
+  return launch_flat(qc::commander_step_adjoint_kernel, qc::commander_step_blocks(n), qc::SENSITIVITY_BLOCK, stream, (long)n, a);
 }
 
 void qc_default_support_polygon(qc_support_polygon_io* io) { (void)zeroed(io); }
@@ -2462,12 +2436,8 @@ int qc_support_polygon_batch(qc_handle* h, size_t n, const qc_batch_in* in, cons
   if (const int rc = qc::check_support_polygon_args(h, n, in, io); rc != QC_OK || n == 0) return rc;
   QC_HIP(hipSetDevice(h->device));
   // (of `in`: the feet, the phases and the contact mask as it is now, the pose in world mode - nothing of it is written)
-  const bool world = io->world != 0;
-  const qc::SupportPolygonArgs a{in->feet, in->joint_q, in->gait_phase, in->stance, in->gait_duty, world ? in->Rwb : nullptr, world ? in->x : nullptr,
-                                 io->schedule, io->schedule_shared != 0, io->com_xy, io->weights, io->flags};
-  qc::support_polygon_kernel<<<dim3(qc::support_polygon_blocks(n)), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, a);
-  QC_HIP(hipGetLastError());
-  return QC_OK;
+  const qc::SupportPolygonArgs a{qc::support_in(in, io->schedule, io->schedule_shared, io->world != 0), io->com_xy, io->weights, io->flags};
+  return launch_flat(qc::support_polygon_kernel, qc::support_polygon_blocks(n), qc::SENSITIVITY_BLOCK, stream, h->d_params, (long)n, a);
 }
 
 void qc_default_support_polygon_adjoint(qc_support_polygon_adjoint_io* io) { (void)zeroed(io); }
@@ -2475,14 +2445,10 @@ void qc_default_support_polygon_adjoint(qc_support_polygon_adjoint_io* io) { (vo
 int qc_support_polygon_adjoint_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_support_polygon_adjoint_io* io, void* stream) {
   if (const int rc = qc::check_support_polygon_adjoint_args(h, n, in, io); rc != QC_OK || n == 0) return rc;
   QC_HIP(hipSetDevice(h->device));
-  const bool world = io->world != 0;
-  const qc::SupportPolygonAdjointArgs a{in->feet, in->joint_q, in->gait_phase, in->stance, in->gait_duty, world ? in->Rwb : nullptr, world ? in->x : nullptr,
-                                        io->schedule, io->schedule_shared != 0, io->com_xy_bar, io->feet_bar_in, io->Rwb_bar_in, io->x_bar_in,
-                                        io->phase_bar_in, io->schedule_bar_in, io->feet_bar, io->Rwb_bar, io->x_bar, io->phase_bar, io->schedule_bar,
-                                        io->flags};
-  qc::support_polygon_adjoint_kernel<<<dim3(qc::support_polygon_blocks(n)), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, a);
-  QC_HIP(hipGetLastError());
-  return QC_OK;
+  const qc::SupportPolygonAdjointArgs a{qc::support_in(in, io->schedule, io->schedule_shared, io->world != 0), io->com_xy_bar, io->feet_bar_in,
+                                        io->Rwb_bar_in, io->x_bar_in, io->phase_bar_in, io->schedule_bar_in, io->feet_bar, io->Rwb_bar, io->x_bar,
+                                        io->phase_bar, io->schedule_bar, io->flags};
+  return launch_flat(qc::support_polygon_adjoint_kernel, qc::support_polygon_blocks(n), qc::SENSITIVITY_BLOCK, stream, h->d_params, (long)n, a);
 }
 
 void qc_default_com_reference(qc_com_reference_io* io) {
@@ -2495,11 +2461,8 @@ int qc_com_reference_batch(qc_handle* h, size_t n, const qc_batch_in* in, const 
   if (const int rc = qc::check_com_reference_args(h, n, in, io); rc != QC_OK || n == 0) return rc;
   QC_HIP(hipSetDevice(h->device));
   // (of `in`: the feet, the phases and the contact mask as it is now, the pose - nothing of it is written)
-  const qc::ComReferenceArgs a{in->feet, in->joint_q, in->gait_phase, in->stance, in->gait_duty, in->Rwb, in->x, io->schedule, io->schedule_shared != 0,
-                               io->x_d_in, io->mode, io->gain, io->x_d_out, io->com_xy, io->flags};
-  qc::com_reference_kernel<<<dim3(qc::com_reference_blocks(n, false)), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, a);
-  QC_HIP(hipGetLastError());
-  return QC_OK;
+  const qc::ComReferenceArgs a{qc::support_in(in, io->schedule, io->schedule_shared, true), io->x_d_in, io->mode, io->gain, io->x_d_out, io->com_xy, io->flags};
+  return launch_flat(qc::com_reference_kernel, qc::com_reference_blocks(n, false), qc::SENSITIVITY_BLOCK, stream, h->d_params, (long)n, a);
 }
 
 void qc_default_com_reference_adjoint(qc_com_reference_adjoint_io* io) {
@@ -2512,20 +2475,16 @@ int qc_com_reference_adjoint_batch(qc_handle* h, size_t n, const qc_batch_in* in
   if (const int rc = qc::check_com_reference_adjoint_args(h, n, in, io); rc != QC_OK || n == 0) return rc;
   QC_HIP(hipSetDevice(h->device));
   const bool sum = io->schedule_bar_sum != nullptr;
-  const qc::ComReferenceAdjointArgs a{in->feet, in->joint_q, in->gait_phase, in->stance, in->gait_duty, in->Rwb, in->x, io->schedule,
-                                      io->schedule_shared != 0, io->mode, io->gain, io->x_d_out_bar, io->feet_bar_in, io->Rwb_bar_in, io->x_bar_in,
-                                      io->phase_bar_in, io->schedule_bar_in, io->x_d_in_bar, io->feet_bar, io->Rwb_bar, io->x_bar, io->phase_bar,
-                                      io->schedule_bar, sum ? h->com_parts : nullptr, io->flags};
+  const qc::SupportIn s = qc::support_in(in, io->schedule, io->schedule_shared, true);
+  const qc::ComReferenceAdjointArgs a{s.feet, s.joint_q, s.gait_phase, s.stance, s.gait_duty, s.Rwb, s.x, s.schedule, s.shared, io->mode, io->gain,
+                                      io->x_d_out_bar, io->feet_bar_in, io->Rwb_bar_in, io->x_bar_in, io->phase_bar_in, io->schedule_bar_in, io->x_d_in_bar,
+                                      io->feet_bar, io->Rwb_bar, io->x_bar, io->phase_bar, io->schedule_bar, sum ? h->com_parts : nullptr, io->flags};
   const unsigned blocks = qc::com_reference_blocks(n, sum);
   if (sum) {
-    qc::com_reference_adjoint_kernel<true><<<dim3(blocks), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, a);
-    QC_HIP(hipGetLastError());
-    qc::com_schedule_sum_kernel<<<dim3(1), dim3(qc::COM_SUM_FINISH_BLOCK), 0, (hipStream_t)stream>>>(h->com_parts, (int)blocks, io->schedule_bar_sum);
-  } else {
-    qc::com_reference_adjoint_kernel<false><<<dim3(blocks), dim3(qc::SENSITIVITY_BLOCK), 0, (hipStream_t)stream>>>(h->d_params, (long)n, a);
+    if (const int rc = launch_flat(qc::com_reference_adjoint_kernel<true>, blocks, qc::SENSITIVITY_BLOCK, stream, h->d_params, (long)n, a); rc != QC_OK) return rc;
+    return launch_flat(qc::com_schedule_sum_kernel, 1, qc::COM_SUM_FINISH_BLOCK, stream, h->com_parts, (int)blocks, io->schedule_bar_sum);
   }
-  QC_HIP(hipGetLastError());
-  return QC_OK;
+  return launch_flat(qc::com_reference_adjoint_kernel<false>, blocks, qc::SENSITIVITY_BLOCK, stream, h->d_params, (long)n, a);
 }
 
 // host-pointer variant.  Large batches: one device staging allocation, H2D copies, kernel, D2H copies, sync.

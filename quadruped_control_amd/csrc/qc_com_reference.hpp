@@ -44,13 +44,7 @@ namespace qc {
 
 constexpr int COM_REPLACE = 0, COM_OFFSET = 1;  // QC_COM_REPLACE, QC_COM_OFFSET
 
-struct ComReferenceArgs {
-  const double *feet, *joint_q, *gait_phase;  // as SupportPolygonArgs, always world mode
-  const uint8_t* stance;
-  const double* gait_duty;
-  const double *Rwb, *x;
-  const double* schedule;
-  int shared;
+struct ComReferenceArgs : SupportIn {  // (always world mode)
   const double* x_d_in;  // [n][3]
   int mode;
   double gain;
@@ -58,6 +52,8 @@ struct ComReferenceArgs {
   int32_t* flags;            // [n] optional
 };
 
+// (flat, not on SupportIn: its `mode` sits in the padding behind `shared`, and a base struct's padding is not reused - the base would move
+// every field behind it and with them the kernarg loads of both reverse kernels)
 struct ComReferenceAdjointArgs {
   const double *feet, *joint_q, *gait_phase;
   const uint8_t* stance;
@@ -73,6 +69,13 @@ struct ComReferenceAdjointArgs {
   double* partials;                                                                     // [gridDim.x][16]: the summing instantiation
   int32_t* flags;                                                                       // [n] optional OUT
 };
+
+#pragma GCC diagnostic push
+#pragma GCC diagnostic ignored "-Winvalid-offsetof"  // (a struct with a base is not standard-layout; the compilers this builds with lay it out as C would)
+static_assert(sizeof(ComReferenceArgs) == 120 && offsetof(ComReferenceArgs, x_d_in) == 72 && sizeof(ComReferenceAdjointArgs) == 192 &&
+                  offsetof(ComReferenceAdjointArgs, mode) == 68,
+              "SupportIn leads ComReferenceArgs; ComReferenceAdjointArgs keeps its nine fields and its layout");
+#pragma GCC diagnostic pop
 
 constexpr int COM_SUM_MAX_BLOCKS = 1024;  // grid cap of the summing instantiation = partials in the handle's buffer
 constexpr int COM_SUM_STRIDE = 17;        // a lane's 16 numbers in LDS, at an odd stride
@@ -125,9 +128,10 @@ __global__ __launch_bounds__(SENSITIVITY_BLOCK) void com_reference_kernel(const 
 }
 
 // The polygon's reverse pass of one robot from g = vb_l (a quarter of the cotangent on the mean of the four virtual points): the body
-// of support_polygon_adjoint_kernel, line by line, REPEATED here and not shared - factoring it out of that kernel changed the
-// kernel's instructions (profiles/com_reference.md) -, its world-mode branch alone.  Pb arrives holding what the centroid left there (zero in REPLACE mode) and the
-// five accumulators their `_in` rows.  Returns the forward rule's flags.
+// of support_polygon_adjoint_kernel, line by line, REPEATED here and not shared - one body for both changed the registers or the
+// instruction mix of one of the three kernels in each of the three variants tried (profiles/reference_fold.md) -, its world-mode
+// branch alone.  Pb arrives holding what the centroid left there (zero in REPLACE mode) and the five accumulators their `_in` rows.
+// Returns the forward rule's flags.
 QC_DEV int support_reverse(const SupportRobot& S, const double (&g)[2], double (&Pb)[4][2], double (&fb)[12], double (&Rb)[9],
                            double (&xb)[3], double (&pb)[4], double (&sb)[16]) {
   double wb[4] = {0.0, 0.0, 0.0, 0.0};

@@ -563,12 +563,20 @@ inline int check_leg_plant_args(const qc_handle* h, size_t n, const qc_leg_plant
   return check_plant_io(who, n, io, own, io->joint_q && io->joint_qdot && io->joint_tau, ": joint_q, joint_qdot and joint_tau are required", LEG_PLANT_BLOCK);
 }
 
-// the kernel's arguments: the body's constants (body_constants, under this entry point's name), the call's leg inertia and its arrays
-inline int leg_plant_constants(double mass, const double* Ib, const qc_leg_plant_io* io, LegPlantArgs& a) {
-  if (const int rc = body_constants("qc_leg_plant_step_batch", mass, Ib, io->dt, a); rc != QC_OK) return rc;
+// What LegPlantArgs and LegPlantAdjointArgs share: the body's constants (body_constants, under the entry point's name), the call's leg
+// inertia, the state, the torques and the contact inputs.
+template <class Io, class Args>
+int leg_plant_shared(const char* who, double mass, const double* Ib, const Io* io, Args& a) {
+  if (const int rc = body_constants(who, mass, Ib, io->dt, a); rc != QC_OK) return rc;
   for (int k = 0; k < 3; k++) a.leg_inertia[k] = io->leg_inertia[k];
   a.Rwb = io->Rwb; a.x = io->x; a.xdot = io->xdot; a.w = io->w; a.joint_q = io->joint_q; a.joint_qdot = io->joint_qdot; a.joint_tau = io->joint_tau;
   a.stance = io->stance; a.gait_phase = io->gait_phase; a.gait_duty = io->gait_duty; a.cmd_state = reinterpret_cast<const CmdState*>(io->cmd_state);
+  return QC_OK;
+}
+
+// the kernel's arguments: what the two leg-plant calls share (leg_plant_shared) and the step's two outputs
+inline int leg_plant_constants(double mass, const double* Ib, const qc_leg_plant_io* io, LegPlantArgs& a) {
+  if (const int rc = leg_plant_shared("qc_leg_plant_step_batch", mass, Ib, io, a); rc != QC_OK) return rc;
   a.foot_world = io->foot_world; a.flags = io->flags;
   return QC_OK;
 }
@@ -589,12 +597,9 @@ inline int check_leg_plant_adjoint_args(const qc_handle* h, size_t n, const qc_l
   return check_plant_io(who, n, io, own, io->joint_q && io->joint_qdot && io->joint_tau, ": joint_q, joint_qdot and joint_tau are required", LEG_PLANT_BLOCK);
 }
 
-// the kernel's arguments: the body's constants (body_constants, under this entry point's name), the call's leg inertia and its arrays
+// the kernel's arguments: what the two leg-plant calls share (leg_plant_shared), the cotangents and the outputs
 inline int leg_plant_adjoint_constants(double mass, const double* Ib, const qc_leg_plant_adjoint_io* io, LegPlantAdjointArgs& a) {
-  if (const int rc = body_constants("qc_leg_plant_step_adjoint_batch", mass, Ib, io->dt, a); rc != QC_OK) return rc;
-  for (int k = 0; k < 3; k++) a.leg_inertia[k] = io->leg_inertia[k];
-  a.Rwb = io->Rwb; a.x = io->x; a.xdot = io->xdot; a.w = io->w; a.joint_q = io->joint_q; a.joint_qdot = io->joint_qdot; a.joint_tau = io->joint_tau;
-  a.stance = io->stance; a.gait_phase = io->gait_phase; a.gait_duty = io->gait_duty; a.cmd_state = reinterpret_cast<const CmdState*>(io->cmd_state);
+  if (const int rc = leg_plant_shared("qc_leg_plant_step_adjoint_batch", mass, Ib, io, a); rc != QC_OK) return rc;
   a.Rwb_next_bar = io->Rwb_next_bar; a.x_next_bar = io->x_next_bar; a.xdot_next_bar = io->xdot_next_bar; a.w_next_bar = io->w_next_bar;
   a.joint_q_next_bar = io->joint_q_next_bar; a.joint_qdot_next_bar = io->joint_qdot_next_bar;
   a.Rwb_bar = io->Rwb_bar; a.x_bar = io->x_bar; a.xdot_bar = io->xdot_bar; a.w_bar = io->w_bar;
@@ -863,6 +868,13 @@ inline int check_com_reference_adjoint_args(const qc_handle* h, size_t n, const 
     own = ": no output requested (x_d_in_bar, feet_bar, Rwb_bar, x_bar, phase_bar, schedule_bar, schedule_bar_sum, flags are all NULL)";
   if (!own && n > 0 && !io->x_d_out_bar) own = ": x_d_out_bar is required";
   return check_com_reference_batch(who, n, in, own, io->schedule);
+}
+
+// what the polygon and COM kernels read of the batch (SupportIn): the feet, the phases and the contact mask as it is now, the pose in
+// world mode, the schedule - nothing of `in` is written
+inline SupportIn support_in(const qc_batch_in* in, const double* schedule, int32_t schedule_shared, bool world) {
+  return SupportIn{in->feet, in->joint_q, in->gait_phase, in->stance, in->gait_duty, world ? in->Rwb : nullptr, world ? in->x : nullptr, schedule,
+                   schedule_shared != 0};
 }
 
 // workgroups of the kernels for n robots: one wave each, capped - the reverse pass that sums at the partials of the handle's buffer

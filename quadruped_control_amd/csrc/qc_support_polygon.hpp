@@ -36,6 +36,8 @@
 // lanes (the index clamped, nothing stored) are qc_swing_reference.hpp's.  Both read every input of a robot before they write any of
 // its outputs, and a lane writes its own robot only: an output may be the same array as its `_in` input.
 #pragma once
+#include <cstddef>
+
 #include "qc_swing_reference.hpp"
 
 namespace qc {
@@ -46,7 +48,8 @@ constexpr int SUPPORT_PLUS[4] = {2, 0, 3, 1};   // RL: RR, FL: RL, RR: FR, FR: F
 // the order in which the reference's std::map<std::string, ...> visits the legs: "FL" < "FR" < "RL" < "RR"
 constexpr int SUPPORT_SUM_ORDER[4] = {1, 3, 0, 2};
 
-struct SupportPolygonArgs {
+// what the polygon and COM kernels read of a robot: the base of their four argument structs (as BodyConst is of the plant's)
+struct SupportIn {
   const double *feet, *joint_q;  // [n][4][3]: joint_q if given, else feet
   const double* gait_phase;      // [n][4]
   const uint8_t* stance;         // [n][4] or NULL: the phase rule
@@ -54,22 +57,27 @@ struct SupportPolygonArgs {
   const double *Rwb, *x;         // [n][9], [n][3]: world mode, else NULL
   const double* schedule;        // [n][4][4], or [4][4] if shared
   int shared;
+};
+
+struct SupportPolygonArgs : SupportIn {
   double *com_xy, *weights;      // [n][2], [n][4] optional OUT
   int32_t* flags;                // [n] optional OUT
 };
 
-struct SupportPolygonAdjointArgs {
-  const double *feet, *joint_q, *gait_phase;
-  const uint8_t* stance;
-  const double* gait_duty;
-  const double *Rwb, *x;
-  const double* schedule;
-  int shared;
+struct SupportPolygonAdjointArgs : SupportIn {
   const double* com_xy_bar;                                                               // [n][2]
   const double *feet_bar_in, *Rwb_bar_in, *x_bar_in, *phase_bar_in, *schedule_bar_in;     // optional
   double *feet_bar, *Rwb_bar, *x_bar, *phase_bar, *schedule_bar;                          // optional OUT
   int32_t* flags;                                                                         // [n] optional OUT
 };
+
+// (a derived struct's own fields start behind the base's padded size: the layout is the one the flat structs had)
+#pragma GCC diagnostic push
+#pragma GCC diagnostic ignored "-Winvalid-offsetof"  // (a struct with a base is not standard-layout; the compilers this builds with lay it out as C would)
+static_assert(sizeof(SupportIn) == 72 && sizeof(SupportPolygonArgs) == 96 && offsetof(SupportPolygonArgs, com_xy) == 72 &&
+                  sizeof(SupportPolygonAdjointArgs) == 168 && offsetof(SupportPolygonAdjointArgs, com_xy_bar) == 72,
+              "SupportIn leads the polygon's argument structs");
+#pragma GCC diagnostic pop
 
 }  // namespace qc
 

@@ -204,6 +204,56 @@ def test_outputs_over_their_inputs(ctl, reference):
     assert np.array_equal(x_d.cpu().numpy(), fwd["x_d"])
 
 
+FLAGGED_AT = 5  # the lane of the 0/0 robot in _replace_pool
+
+
+def _replace_pool(c, shared):
+    """the first 65 robots of the draw with the 0/0 robot of test_a_flagged_robot planted at FLAGGED_AT (three swing legs whose widths
+    are 0: per robot its own block, shared a block whose swing widths are 0 for every robot); asserted to flag under the phase rule's
+    mask and to hold stance and swing legs on every leg"""
+    b = {k: v.copy() for k, v in c["b"].items()}
+    b["gait_phase"][FLAGGED_AT] = [0.2, 0.75, 0.75, 0.75]
+    if shared:
+        sched = c["shared"].copy()
+        sched[:, 2:] = 0.0
+    else:
+        sched = c["sched"][:65].copy()
+        sched[FLAGGED_AT] = 0.0
+    mask = np.array([[SP.in_stance(float(p), SP.TROT_DUTY) for p in row] for row in b["gait_phase"][:65]])
+    assert mask[FLAGGED_AT].tolist() == [True, False, False, False] and mask.any(axis=0).all() and (~mask).any(axis=0).all()
+    return b, sched
+
+
+@pytest.mark.parametrize("n", (1, 65))
+def test_replace_mode_is_the_world_polygons_reverse_pass(ctl, reference, n):
+    """com_reference_adjoint_batch(mode="replace") on x_d_bar = (a, b, c) against support_polygon_adjoint_batch(world=True) on com_xy_bar =
+    (a, b), the same batch and schedule: feet_bar, Rwb_bar, x_bar, phase_bar, schedule_bar and flags equal bit for bit, NaNs at the same
+    places, and x_d_in_bar = (0, 0, c) - NaN for a flagged robot, the kernel's documented rule ("a flagged robot gets NaN in every output
+    row, x_d_in_bar's included", qc_com_reference.hpp) - both input forms, shared and per-robot schedule, with and without
+    the five `_in` accumulators; n = 65 is one full wave and one tail robot.  The two kernels hold the same lines twice: this is what
+    sharing them has to keep."""
+    import torch
+
+    bar = _cuda(reference["bar"][:n])
+    for form in ("feet", "joint_q"):
+        for shared in (False, True):
+            b, sched = _replace_pool(reference, shared)
+            dev, s = {k: _cuda(v) for k, v in _batch(b, form, n).items()}, _cuda(sched if shared else sched[:n])
+            for ins in (False, True):
+                acc = {k: _cuda(v[:n]) for k, v in reference["ins"].items()} if ins else {}
+                com = ctl.com_reference_adjoint_batch(dev, s, bar, "replace", GAIN, want=ROWS, **acc)
+                pol = ctl.support_polygon_adjoint_batch(dev, s, bar[:, :2].contiguous(), world=True, want=SP.OUTPUTS + ("flags",), **acc)
+                torch.cuda.synchronize()
+                com, pol = ({k: v.cpu().numpy().reshape(n, -1) for k, v in r.items()} for r in (com, pol))
+                flagged = com["flags"][:, 0] != 0
+                assert n == 1 or (np.flatnonzero(flagged).tolist() == [FLAGGED_AT] and com["flags"][FLAGGED_AT, 0] == 1 << 3), (form, shared)
+                for k in SP.OUTPUTS + ("flags",):
+                    assert np.array_equal(com[k], pol[k], equal_nan=k != "flags"), (form, shared, ins, k)
+                    assert k == "flags" or (np.isnan(com[k]).all(axis=1) == flagged).all(), (form, shared, ins, k)
+                want = reference["bar"][:n] * [0.0, 0.0, 1.0]
+                assert np.array_equal(com["x_d_in_bar"][~flagged], want[~flagged]) and np.isnan(com["x_d_in_bar"][flagged]).all()
+
+
 # ------------------------------------------------------------------ the second round of the grid stride
 ZERO_AT, OUTSIDE = 77, (200, 201)  # the period's 0/0 robot; the two robots of the draw that are planted after the tiling
 BATCH_KEYS = ("joint_q", "gait_phase", "Rwb", "x")
