@@ -31,4 +31,8 @@ def __getattr__(name):
         from . import autograd as _ag
 
         return getattr(_ag, name)
+    if name == "tangent":  # forward mode: q.tangent.tangent_batch(ctl, ...), q.tangent.jacobian_batch(ctl, ...)
+        import importlib
+
+        return importlib.import_module(".tangent", __name__)
     raise AttributeError(name)

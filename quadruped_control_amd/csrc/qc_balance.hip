@@ -2328,6 +2328,19 @@ int qc_sensitivity_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc
   return launch_per_robot(qc::sensitivity_kernel<true>, qc::sensitivity_kernel<false>, qc::sensitivity_blocks(n), qc::SENSITIVITY_BLOCK, h, n, readonly_view(in, true), a, stream);
 }
 
+void qc_default_tangent(qc_tangent_io* io) {
+  if (!zeroed(io)) return;
+  io->act_tol = 1e-7;  // qc_default_sensitivity's
+  io->n_dir = 1;
+}
+
+int qc_tangent_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_tangent_io* io, void* stream) {
+  if (const int rc = qc::check_tangent_args(h, n, in, io); rc != QC_OK || n == 0) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  return launch_per_robot(qc::tangent_kernel<true>, qc::tangent_kernel<false>, qc::tangent_blocks(n), qc::TANGENT_BLOCK, h, n, readonly_view(in, true),
+                          qc::tangent_constants(io), stream);
+}
+
 void qc_default_sensitivity_rot(qc_sensitivity_rot_io* io) { (void)zeroed(io); }
 
 int qc_sensitivity_rot_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_rot_io* io, void* stream) {

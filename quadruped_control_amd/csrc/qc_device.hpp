@@ -1322,6 +1322,31 @@ QC_DEV bool ldlt_solve(double (&M)[N * (N + 1) / 2], double (&x)[N]) {
   return ok;
 }
 
+// The substitution half of ldlt_solve against the factor it leaves in M (unit L below the diagonal, 1 / d_k on it):
+// x <- M^-1 x for a further right-hand side, the same three sweeps in the same order - x comes out as ldlt_solve would have
+// returned it for that right-hand side.
+template <int N>
+QC_DEV void ldlt_apply(const double (&M)[N * (N + 1) / 2], double (&x)[N]) {
+#define QC_LI(r, c) ((r) * ((r) + 1) / 2 + (c))
+#pragma unroll
+  for (int k = 1; k < N; k++) {
+    double t = x[k];
+#pragma unroll
+    for (int m = 0; m < k; m++) t = __builtin_fma(-M[QC_LI(k, m)], x[m], t);
+    x[k] = t;
+  }
+#pragma unroll
+  for (int k = 0; k < N; k++) x[k] *= M[QC_LI(k, k)];
+#pragma unroll
+  for (int k = N - 2; k >= 0; k--) {
+    double t = x[k];
+#pragma unroll
+    for (int m = k + 1; m < N; m++) t = __builtin_fma(-M[QC_LI(m, k)], x[m], t);
+    x[k] = t;
+  }
+#undef QC_LI
+}
+
 // -------------------------------------------------------------- EQP, diagonal W
 // Equality-constrained subproblem on the current face, 6-dimensional form.
 // With f = T y + p (T,p from the cube states), diagonal W and u = A f - b:

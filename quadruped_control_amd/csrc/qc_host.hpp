@@ -8,6 +8,7 @@
 #include <utility>
 
 #include "../../include/qc_balance.h"
+#include "../../include/qc_tangent.h"
 #include "qc_device.hpp"
 #include "qc_plant.hpp"
 #include "qc_plant_adjoint.hpp"
@@ -23,6 +24,7 @@
 #include "qc_commander.hpp"
 #include "qc_support_polygon.hpp"
 #include "qc_com_reference.hpp"
+#include "qc_tangent.hpp"
 
 namespace qc {
 
@@ -879,5 +881,30 @@ inline SupportIn support_in(const qc_batch_in* in, const double* schedule, int32
 
 // workgroups of the kernels for n robots: one wave each, capped - the reverse pass that sums at the partials of the handle's buffer
 inline unsigned com_reference_blocks(size_t n, bool sum) { return capped_blocks(n, SENSITIVITY_BLOCK, sum ? COM_SUM_MAX_BLOCKS : SENSITIVITY_MAX_BLOCKS); }
+
+// ---------------------------------------------------------------- qc_tangent_batch
+// The argument check of the forward mode: what is wrong with the call itself (message prefix "qc_tangent_batch:").
+inline int check_tangent_args(const qc_handle* h, size_t n, const qc_batch_in* in, const qc_tangent_io* io) {
+  const char* who = "qc_tangent_batch";
+  if (const int rc = check_io(who, h && in, io, "qc_tangent_io", "qc_default_tangent"); rc != QC_OK) return rc;
+  const char* own = nullptr;
+  if (!std::isfinite(io->act_tol) || !(io->act_tol >= 0.0)) own = ": act_tol must be finite and >= 0";
+  else if (io->n_dir == 0) own = ": n_dir must be >= 1";
+  else if (!io->grf_tan && !io->b_tan) own = ": no output requested (grf_tan and b_tan are both NULL)";
+  else if (!io->x_tan && !io->xdot_tan && !io->w_tan && !io->x_d_tan && !io->xdot_d_tan && !io->w_d_tan && !io->Rwb_rot_tan && !io->Rwb_d_rot_tan &&
+           !io->feet_tan && !io->joint_q_tan)
+    own = ": no tangent given (x_tan, xdot_tan, w_tan, x_d_tan, xdot_d_tan, w_d_tan, Rwb_rot_tan, Rwb_d_rot_tan, feet_tan, joint_q_tan are all NULL)";
+  else if (io->joint_q_tan && !in->joint_q) own = ": joint_q_tan needs joint_q";
+  return check_readonly_batch(who, n, in, own, io->grf_body != nullptr, ": grf_body is required", TANGENT_BLOCK);
+}
+
+// the kernel's arguments: the record's scalars and arrays
+inline TangentArgs tangent_constants(const qc_tangent_io* io) {
+  return TangentArgs{io->grf_body, io->act_tol, (long)io->n_dir, io->x_tan, io->xdot_tan, io->w_tan, io->x_d_tan, io->xdot_d_tan, io->w_d_tan,
+                     io->Rwb_rot_tan, io->Rwb_d_rot_tan, io->feet_tan, io->joint_q_tan, io->grf_tan, io->b_tan, io->flags};
+}
+
+// workgroups of tangent_kernel for n robots: one wave each, capped (a grid cap of its own)
+inline unsigned tangent_blocks(size_t n) { return capped_blocks(n, TANGENT_BLOCK, TANGENT_MAX_BLOCKS); }
 
 }  // namespace qc
