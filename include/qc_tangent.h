@@ -31,8 +31,11 @@
  *
  * OUT OF SCOPE: entrywise (nine-number) rotation tangents - the rotations move along the left tangents above only; tangents of
  * the handle's parameters (mu, fzmin, fzmax, the weights, the gains, mass, Ib, the kinematic model); tangents through the J^T
- * torque map, the plants and the swing pipeline; weak activity (a row whose multiplier is about 0 is on the face like any other);
- * commander mode (the desired state must be in `in`); a jvp on the torch.autograd.Functions of the Python package. */
+ * torque map, the leg plant and the swing pipeline; weak activity (a row whose multiplier is about 0 is on the face like any other);
+ * commander mode (the desired state must be in `in`); a jvp on the torch.autograd.Functions of the Python package.
+ *
+ * The rigid-body plant step has its forward mode below, qc_plant_step_tangent_batch: with it the two calls chain, step after step,
+ * into the tangent of a closed-loop rollout. */
 #ifndef QC_TANGENT_H
 #define QC_TANGENT_H
 
@@ -64,6 +67,49 @@ void qc_default_tangent(qc_tangent_io* io);
  * joint_q_tan without in->joint_q, a missing grf_body, a missing state array (Rwb, Rwb_d, x, xdot, w, x_d, xdot_d, w_d), neither
  * feet nor joint_q, or n beyond one launch. */
 int qc_tangent_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_tangent_io* io, void* stream);
+
+/* qc_plant_step_tangent_batch - forward mode of qc_plant_step_batch: K tangents on the inputs of one plant step pushed through it,
+ * in one launch.  Given the state BEFORE the step, the forces and the feet the step read (nothing is saved by the forward step; it
+ * is recomputed), per direction, in the notation of qc_plant_step_batch (h = Iw w, c = tau - w x h, delta the world-frame left
+ * tangent of Rwb, as above; dg_l = grf_tan_l, dp_l = foot_world_tan_l):
+ *   df_l  = delta x f_l - Rwb dg_l,   dr_l = dp_l - dx,   da = (sum df_l) / m,   dtau = sum (dr_l x f_l + r_l x df_l)
+ *   dh    = delta x h - Iw (delta x w) + Iw dw,   dc = dtau - dw x h - w x dh,   dwdot = Iw^-1 (dc - delta x c) + delta x wdot
+ *   dxdot' = dxdot + dt da,   dx' = dx + dt dxdot',   dw' = dw + dt dwdot
+ *   delta' = Jl(phi) dt dw' + Exp(phi) delta,  phi = dt w',  Jl = I + B K + C K^2,  K = hat(phi),  B = (1 - cos theta) / theta^2,
+ *            C = (theta - sin theta) / theta^3: series in theta^2 below theta^2 = 1, the quotients from it on; at theta = 0 exactly
+ *            the smooth limit (Jl = I), as qc_plant_step_adjoint_batch differentiates it
+ *   dfeet'_l = Rwb'^T (dp_l - dx' - delta' x d_l),   d_l = foot_world_l - x'.
+ * <cotangents of the step's outputs, these tangents> equals <qc_plant_step_adjoint_batch's cotangents, the input tangents>, with the
+ * entrywise Rwb_bar paired with [delta]x Rwb and Rwb_next_bar with [delta']x Rwb'.
+ *
+ * There are no tangents of mass, Ib or dt.  Non-finite inputs propagate as NaN; nothing is clamped.  A (robot, direction) pair
+ * reads all its inputs before it writes any output and touches only its own rows, so every output may BE the input tangent of its
+ * layout - x_next_tan over x_tan, Rwb_rot_next_tan over Rwb_rot_tan, feet_next_tan over grf_tan or foot_world_tan - and a rollout
+ * carries one set of tangent buffers.  The state, force and feet inputs are never written.  All pointers are device pointers.
+ *
+ * OUT OF SCOPE: the leg plant (qc_leg_plant_step_batch); tangents of mass, Ib and dt; entrywise rotation tangents. */
+typedef struct qc_plant_tangent_io {
+  size_t struct_size;            /* = sizeof(qc_plant_tangent_io); checked                                            */
+  const double *Rwb;             /* [n][9] the state BEFORE the step                                                  */
+  const double *x, *xdot, *w;    /* [n][3]                                                                            */
+  const double *grf_body, *foot_world;  /* [n][4][3] as the step read them                                            */
+  double dt;                     /* finite, > 0                                                                       */
+  size_t n_dir;                  /* K >= 1 directions per launch                                                      */
+  /* tangents, direction-major as in qc_tangent_io; NULL = zero, at least one given                                   */
+  const double *Rwb_rot_tan, *x_tan, *xdot_tan, *w_tan;   /* [K][n][3]                                                */
+  const double *grf_tan;         /* [K][n][4][3] what qc_tangent_batch wrote                                          */
+  const double *foot_world_tan;  /* [K][n][4][3]                                                                      */
+  /* outputs, each optional, at least one given                                                                       */
+  double *Rwb_rot_next_tan, *x_next_tan, *xdot_next_tan, *w_next_tan;  /* [K][n][3]                                   */
+  double *feet_next_tan;         /* [K][n][4][3] the tangent of qc_plant_io.feet: the next solve's feet_tan           */
+} qc_plant_tangent_io;
+/* struct_size set, pointers NULL, dt = 1/300, n_dir = 1. */
+void qc_default_plant_tangent(qc_plant_tangent_io* io);
+/* Asynchronous on `stream`, no host synchronisation (graph-capturable); n == 0 launches nothing and returns QC_OK.
+ * QC_ERR_INVALID (message starting with "qc_plant_step_tangent_batch:", nothing launched) for a null handle or `io`, a wrong
+ * struct_size, a dt that is not finite and > 0, n_dir == 0, no tangent given at all, no output requested at all, a missing state,
+ * force or feet array, a handle whose mass or Ib qc_plant_step_batch refuses, or n * n_dir beyond one launch. */
+int qc_plant_step_tangent_batch(qc_handle* h, size_t n, const qc_plant_tangent_io* io, void* stream);
 
 #ifdef __cplusplus
 }

@@ -2341,6 +2341,20 @@ int qc_tangent_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_tan
                           qc::tangent_constants(io), stream);
 }
 
+void qc_default_plant_tangent(qc_plant_tangent_io* io) {
+  if (!zeroed(io)) return;
+  io->dt = 1.0 / 300.0;  // qc_default_plant's
+  io->n_dir = 1;
+}
+
+int qc_plant_step_tangent_batch(qc_handle* h, size_t n, const qc_plant_tangent_io* io, void* stream) {
+  if (const int rc = qc::check_plant_tangent_args(h, n, io); rc != QC_OK || n == 0) return rc;
+  qc::PlantTangentArgs a;
+  if (const int rc = qc::plant_tangent_constants(h->dp.mass, h->dp.Ib, io, a); rc != QC_OK) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  return launch_flat(qc::plant_step_tangent_kernel, qc::plant_tangent_blocks(n, io->n_dir), qc::PLANT_TANGENT_BLOCK, stream, (long)n, a);
+}
+
 void qc_default_sensitivity_rot(qc_sensitivity_rot_io* io) { (void)zeroed(io); }
 
 int qc_sensitivity_rot_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_rot_io* io, void* stream) {

@@ -25,6 +25,7 @@
 #include "qc_support_polygon.hpp"
 #include "qc_com_reference.hpp"
 #include "qc_tangent.hpp"
+#include "qc_plant_tangent.hpp"
 
 namespace qc {
 
@@ -906,5 +907,38 @@ inline TangentArgs tangent_constants(const qc_tangent_io* io) {
 
 // workgroups of tangent_kernel for n robots: one wave each, capped (a grid cap of its own)
 inline unsigned tangent_blocks(size_t n) { return capped_blocks(n, TANGENT_BLOCK, TANGENT_MAX_BLOCKS); }
+
+// ---------------------------------------------------------------- qc_plant_step_tangent_batch
+// What is wrong with the call itself (message prefix "qc_plant_step_tangent_batch:"); the handle's mass and Ib are judged by
+// plant_tangent_constants, through the plant's own checks.  One lane per (robot, direction): the pairs, not the robots, must fit a launch.
+inline int check_plant_tangent_args(const qc_handle* h, size_t n, const qc_plant_tangent_io* io) {
+  const char* who = "qc_plant_step_tangent_batch";
+  if (const int rc = check_io(who, h != nullptr, io, "qc_plant_tangent_io", "qc_default_plant_tangent"); rc != QC_OK) return rc;
+  const char* own = nullptr;
+  if (io->n_dir == 0) own = ": n_dir must be >= 1";
+  else if (!io->Rwb_rot_tan && !io->x_tan && !io->xdot_tan && !io->w_tan && !io->grf_tan && !io->foot_world_tan)
+    own = ": no tangent given (Rwb_rot_tan, x_tan, xdot_tan, w_tan, grf_tan, foot_world_tan are all NULL)";
+  else if (!io->Rwb_rot_next_tan && !io->x_next_tan && !io->xdot_next_tan && !io->w_next_tan && !io->feet_next_tan)
+    own = ": no output requested (Rwb_rot_next_tan, x_next_tan, xdot_next_tan, w_next_tan, feet_next_tan are all NULL)";
+  if (const int rc = check_plant_io(who, n, io, own, io->grf_body && io->foot_world, ": grf_body and foot_world are required", PLANT_TANGENT_BLOCK); rc != QC_OK || n == 0)
+    return rc;
+  if (io->n_dir > (size_t)0xFFFFFF * (size_t)PLANT_TANGENT_BLOCK / n) return fail(QC_ERR_INVALID, std::string(who) + ": n * n_dir is beyond one launch");
+  return QC_OK;
+}
+
+// the kernel's arguments: the body's constants (body_constants, under this entry point's name) and the call's arrays
+inline int plant_tangent_constants(double mass, const double* Ib, const qc_plant_tangent_io* io, PlantTangentArgs& a) {
+  if (const int rc = body_constants("qc_plant_step_tangent_batch", mass, Ib, io->dt, a); rc != QC_OK) return rc;
+  a.Rwb = io->Rwb; a.x = io->x; a.xdot = io->xdot; a.w = io->w; a.grf_body = io->grf_body; a.foot_world = io->foot_world;
+  a.n_dir = (long)io->n_dir;
+  a.Rwb_rot_tan = io->Rwb_rot_tan; a.x_tan = io->x_tan; a.xdot_tan = io->xdot_tan; a.w_tan = io->w_tan; a.grf_tan = io->grf_tan;
+  a.foot_world_tan = io->foot_world_tan;
+  a.Rwb_rot_next_tan = io->Rwb_rot_next_tan; a.x_next_tan = io->x_next_tan; a.xdot_next_tan = io->xdot_next_tan; a.w_next_tan = io->w_next_tan;
+  a.feet_next_tan = io->feet_next_tan;
+  return QC_OK;
+}
+
+// workgroups of plant_step_tangent_kernel for n robots and K directions: one wave of pairs each, capped (a grid cap of its own)
+inline unsigned plant_tangent_blocks(size_t n, size_t n_dir) { return capped_blocks(n * n_dir, PLANT_TANGENT_BLOCK, PLANT_TANGENT_MAX_BLOCKS); }
 
 }  // namespace qc

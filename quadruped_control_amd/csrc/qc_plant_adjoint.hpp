@@ -51,6 +51,9 @@ struct PlantAdjointArgs : BodyConst {
 #ifdef __HIPCC__
 namespace qc {
 
+// theta^2 below which the coefficients that cancel for a small angle are series (A1, B1 here; B, C of qc_plant_tangent.hpp)
+constexpr double SERIES_BELOW = 1.0;
+
 QC_DEV void load3_or_zero(const double* p, long idx, double (&v)[3]) {
   if (p) load3(p, idx, v);
   else v[0] = v[1] = v[2] = 0.0;
@@ -58,7 +61,7 @@ QC_DEV void load3_or_zero(const double* p, long idx, double (&v)[3]) {
 
 // A1 = (cos theta - A) / theta^2 and B1 = (A - 2 B) / theta^2 from th2 = theta^2, sh = sin(theta / 2) and the forward step's A and B
 QC_DEV void exp_coefficient_slopes(double th2, double sh, double A, double B, double* __restrict__ A1, double* __restrict__ B1) {
-  if (th2 < 1.0) {
+  if (th2 < SERIES_BELOW) {
     const double z = th2;
     // 2k / (2k+1)! and 2k / (2k+2)!, k = 9 ... 1, alternating
     double p = -1.4797143443923793e-16, q = -7.398571721961897e-18;  // -18 / 19!, -18 / 20!

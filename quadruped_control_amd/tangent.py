@@ -1,20 +1,34 @@
 """Forward mode of the balance QP (include/qc_tangent.h, csrc/qc_tangent.hpp): tangents of the inputs of a solved batch pushed
 through the QP on its active face, and the Jacobian d grf_body / d inputs as the tangent call on unit seeds.
 
-The functions take the controller as their first argument, as autograd.py's do.  The two symbols of the library are bound here, on
+The plant step's forward mode (qc_plant_step_tangent_batch, csrc/qc_plant_tangent.hpp) follows it: plant_step_tangent(), and the two
+chained step after step - rollout_tangent(), the forward-mode twin of rollout(), and rollout_transition(), the 12 x 12
+state-transition matrix of a closed-loop rollout.
+
+The functions take the controller as their first argument, as autograd.py's do.  The four symbols of the library are bound here, on
 the CDLL that _lib.load() returns, with this module's own ctypes record: _lib.EXPORTS and BalanceController are not touched."""
 from __future__ import annotations
 
 import ctypes as C
 
 from . import _lib
-from .balance_controller import _READONLY_FIELDS, _outputs
+from .balance_controller import _READONLY_FIELDS, _RolloutPlans, _outputs
 
 # name -> values per robot; the names are the record's fields
 TANGENTS = {"x_tan": 3, "xdot_tan": 3, "w_tan": 3, "x_d_tan": 3, "xdot_d_tan": 3, "w_d_tan": 3, "Rwb_rot_tan": 3, "Rwb_d_rot_tan": 3,
             "feet_tan": 12, "joint_q_tan": 12}
 _TANGENT_OUTPUTS = {"grf_tan": ((4, 3), "float64"), "b_tan": ((6,), "float64")}
 JACOBIAN_WRT = ("x", "xdot", "w", "x_d", "xdot_d", "w_d", "Rwb_rot", "Rwb_d_rot")  # jacobian_batch's default; "feet" and "joint_q" are allowed too
+# the plant step's forward mode (qc_plant_tangent_io): its input tangents and its outputs
+PLANT_TANGENTS = {"Rwb_rot_tan": 3, "x_tan": 3, "xdot_tan": 3, "w_tan": 3, "grf_tan": 12, "foot_world_tan": 12}
+_PLANT_TANGENT_OUTPUTS = {"Rwb_rot_next_tan": ((3,), "float64"), "x_next_tan": ((3,), "float64"), "xdot_next_tan": ((3,), "float64"),
+                          "w_next_tan": ((3,), "float64"), "feet_next_tan": ((4, 3), "float64")}
+PLANT_TANGENT_WANT = tuple(_PLANT_TANGENT_OUTPUTS)
+# rollout_tangent(): what `tangents` may hold - the start state's, step 0's feet_tan, and the held ones, applied at every step
+_ROLLOUT_STATE = ("Rwb_rot_tan", "x_tan", "xdot_tan", "w_tan")
+_ROLLOUT_HELD = ("x_d_tan", "xdot_d_tan", "w_d_tan", "Rwb_d_rot_tan")
+ROLLOUT_TANGENTS = {**{k: 3 for k in _ROLLOUT_STATE}, "feet_tan": 12, "foot_world_tan": 12, **{k: 3 for k in _ROLLOUT_HELD}}
+TRANSITION_COLUMNS = tuple((name, c) for name in ("Rwb_rot", "x", "xdot", "w") for c in range(3))  # rollout_transition's rows and columns
 
 
 class QcTangentIo(C.Structure):
@@ -22,42 +36,44 @@ class QcTangentIo(C.Structure):
                [(k, C.c_void_p) for k in tuple(TANGENTS) + ("grf_tan", "b_tan", "flags")]
 
 
+class QcPlantTangentIo(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t)] + [(k, C.c_void_p) for k in ("Rwb", "x", "xdot", "w", "grf_body", "foot_world")] + \
+               [("dt", C.c_double), ("n_dir", C.c_size_t)] + [(k, C.c_void_p) for k in tuple(PLANT_TANGENTS) + PLANT_TANGENT_WANT]
+
+
 _bound = None
 
 
 def _library():
-    """the library with this module's two symbols bound"""
+    """the library with this module's four symbols bound"""
     global _bound
     if _bound is None:
         lib = _lib.load()
-        for name in ("qc_default_tangent", "qc_tangent_batch"):
+        for name in ("qc_default_tangent", "qc_tangent_batch", "qc_default_plant_tangent", "qc_plant_step_tangent_batch"):
             if not hasattr(lib, name):
                 raise ImportError(f"{_lib.LIB_PATH} does not export {name}")
         lib.qc_default_tangent.argtypes = [C.POINTER(QcTangentIo)]
         lib.qc_default_tangent.restype = None
         lib.qc_tangent_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(_lib.QcBatchIn), C.POINTER(QcTangentIo), C.c_void_p]
         lib.qc_tangent_batch.restype = C.c_int
+        lib.qc_default_plant_tangent.argtypes = [C.POINTER(QcPlantTangentIo)]
+        lib.qc_default_plant_tangent.restype = None
+        lib.qc_plant_step_tangent_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcPlantTangentIo), C.c_void_p]
+        lib.qc_plant_step_tangent_batch.restype = C.c_int
         _bound = lib
     return _bound
 
 
-def plan_tangent(ctl, batch, grf_body, tangents, want=("grf_tan",), act_tol=1e-7, out=None, stream=None):
-    """tangent_batch() marshalled once: returns (launch, out, squeeze), `launch()` being one qc_tangent_batch call (graph-capturable)
-    on tensors that are read in place; `out` holds [K, n, ...] tensors and squeeze says whether the tangents came as [n, ...].
-    Planning launches nothing."""
+def _directions(tangents, table, n, dev, io=None):
+    """The tangents that are given (not None), validated against `table` (name -> values per robot): contiguous float64 on `dev`,
+    each [n, ...] (one direction, squeezed) or [K, n, ...], all agreeing.  Sets each pointer in `io`.  Returns (given, K, squeeze);
+    K is 1 when there is none (no tangent at all is the library's refusal)."""
     import torch
 
-    _library()
-    unknown = [k for k in tangents if k not in TANGENTS]
-    if unknown:
-        raise ValueError(f"tangent: unknown tangent(s) {unknown}; the tangents are {tuple(TANGENTS)}")
-    io = QcTangentIo()
-    ctl._lib.qc_default_tangent(C.byref(io))
-    n, dev, bi = ctl._readonly_batch("tangent", batch, _READONLY_FIELDS, io, [("grf_body", grf_body, 12)])
     given = {k: t for k, t in tangents.items() if t is not None}
     K, squeeze = None, False
     for k, t in given.items():
-        m = TANGENTS[k]
+        m = table[k]
         bad = ValueError(f"{k}: need contiguous float64 [{n},{m}] or [K,{n},{m}] on {dev}")
         if t.dtype != torch.float64 or not t.is_contiguous() or t.device != dev or t.dim() < 1 or t.numel() == 0:
             raise bad
@@ -70,8 +86,23 @@ def plan_tangent(ctl, batch, grf_body, tangents, want=("grf_tan",), act_tol=1e-7
             K, squeeze = lead, flat
         elif K != lead or squeeze != flat:
             raise ValueError(f"{k}: the tangents must agree on the number of directions and on the [n, ...] / [K, n, ...] form")
-        setattr(io, k, t.data_ptr())
-    K = 1 if K is None else K  # (no tangent at all is the library's refusal)
+        if io is not None:
+            setattr(io, k, t.data_ptr())
+    return given, (1 if K is None else K), squeeze
+
+
+def plan_tangent(ctl, batch, grf_body, tangents, want=("grf_tan",), act_tol=1e-7, out=None, stream=None):
+    """tangent_batch() marshalled once: returns (launch, out, squeeze), `launch()` being one qc_tangent_batch call (graph-capturable)
+    on tensors that are read in place; `out` holds [K, n, ...] tensors and squeeze says whether the tangents came as [n, ...].
+    Planning launches nothing."""
+    _library()
+    unknown = [k for k in tangents if k not in TANGENTS]
+    if unknown:
+        raise ValueError(f"tangent: unknown tangent(s) {unknown}; the tangents are {tuple(TANGENTS)}")
+    io = QcTangentIo()
+    ctl._lib.qc_default_tangent(C.byref(io))
+    n, dev, bi = ctl._readonly_batch("tangent", batch, _READONLY_FIELDS, io, [("grf_body", grf_body, 12)])
+    given, K, squeeze = _directions(tangents, TANGENTS, n, dev, io)
     io.n_dir = K
     io.act_tol = float(act_tol)
     wanted = tuple(w for w in want if w != "flags")
@@ -93,7 +124,7 @@ def tangent_batch(ctl, batch, grf_body, tangents, want=("grf_tan",), act_tol=1e-
     The reduced system is factorised once per robot and substituted K times in one launch.  Nothing of `batch` is written.
     Asynchronous on `stream`, no synchronisation.  Returns the dict of device tensors, [K, n, ...] - squeezed to [n, ...] where the
     tangents came that way; `out`: a dict of tensors with K * n rows to write into.  ValueError with the library's message for a
-    call it refuses.  Not covered: entrywise rotation tangents, tangents of the handle's parameters, of the torque map, the plants
+    call it refuses.  Not covered: entrywise rotation tangents, tangents of the handle's parameters, of the torque map, the leg plant
     and the swing pipeline."""
     launch, res, squeeze = plan_tangent(ctl, batch, grf_body, tangents, want, act_tol, out, stream)
     launch()
@@ -137,3 +168,163 @@ def jacobian_batch(ctl, batch, grf_body, wrt=JACOBIAN_WRT, act_tol=1e-7, chunk=N
         jac[:, :, c0:c0 + len(part)] = res["grf_tan"].reshape(len(part), n, 12).permute(1, 2, 0)
         flags = res["flags"]
     return dict(jac=jac, columns=cols, flags=flags)
+
+
+# ------------------------------------------------------------------ the plant step's forward mode and the closed loop
+def plan_plant_step_tangent(ctl, state, grf_body, foot_world, dt, tangents, want=PLANT_TANGENT_WANT, out=None, stream=None):
+    """plant_step_tangent() marshalled once: returns (launch, out, squeeze), `launch()` being one qc_plant_step_tangent_batch call
+    (graph-capturable) on tensors that are read in place; `out` holds [K, n, ...] tensors and squeeze says whether the tangents came
+    as [n, ...].  A tensor of `out` may be a tensor of `tangents` of the same layout (the aliasing contract of include/qc_tangent.h).
+    Planning launches nothing."""
+    _library()
+    unknown = [k for k in tangents if k not in PLANT_TANGENTS]
+    if unknown:
+        raise ValueError(f"plant_step_tangent: unknown tangent(s) {unknown}; the tangents are {tuple(PLANT_TANGENTS)}")
+    io = QcPlantTangentIo()
+    ctl._lib.qc_default_plant_tangent(C.byref(io))
+    n, dev = ctl._plant_arrays(io, state, grf_body, foot_world)
+    given, K, squeeze = _directions(tangents, PLANT_TANGENTS, n, dev, io)
+    io.n_dir = K
+    io.dt = float(dt)
+    res = _outputs("plant_step_tangent", _PLANT_TANGENT_OUTPUTS, tuple(want), out, K * n, dev, io)
+    res = {k: v.view((K, n) + _PLANT_TANGENT_OUTPUTS[k][0]) for k, v in res.items()}
+    launch = ctl._launcher("qc_plant_step_tangent_batch", (n, C.byref(io), ctl._stream_ptr(stream)), (state, grf_body, foot_world, given, res, io), ValueError)
+    return launch, res, squeeze
+
+
+def plant_step_tangent(ctl, state, grf_body, foot_world, dt, tangents, want=PLANT_TANGENT_WANT, out=None, stream=None):
+    """Forward mode of plant_step() (qc_plant_step_tangent_batch, include/qc_tangent.h; INTEGRATION.md "Forward mode: the plant step
+    and the closed loop").  `state`: the tensors Rwb [n,9], x, xdot, w [n,3] as they are BEFORE the step; `grf_body`, `foot_world`
+    [n,12] and `dt` as the step reads them.  `tangents`: a dict with any of "Rwb_rot_tan" (the world-frame left tangent,
+    Rwb <- exp([d]x) Rwb), "x_tan", "xdot_tan", "w_tan" ([n,3]), "grf_tan" (what tangent_batch() wrote) and "foot_world_tan" ([n,4,3]) -
+    each [n, ...] for one direction or [K, n, ...] for K, all agreeing on K; a missing one is zero, at least one given.  `want`: any of
+    "Rwb_rot_next_tan", "x_next_tan", "xdot_next_tan", "w_next_tan" [K,n,3] and "feet_next_tan" [K,n,4,3], the tangent of the `feet`
+    plant_step() writes.  The step is recomputed from `state`; nothing of it is written.  `out`: a dict of tensors with K * n rows
+    to write into - each may be the input tangent of its layout.  Asynchronous on `stream`, no synchronisation.  Returns the dict of
+    device tensors, squeezed to [n, ...] where the tangents came that way.  ValueError with the library's message for a call it
+    refuses.  Not covered: tangents of mass, Ib and dt, the leg plant."""
+    launch, res, squeeze = plan_plant_step_tangent(ctl, state, grf_body, foot_world, dt, tangents, want, out, stream)
+    launch()
+    return {k: (v[0] if squeeze else v) for k, v in res.items()}
+
+
+def rollout_tangent(ctl, batch, foot_world, steps, dt, tangents, act_tol=1e-7, warm=True, stream=None):
+    """The forward-mode twin of ctl.rollout(): `steps` times control_batch(), tangent_batch(), plant_step_tangent() (it reads the state
+    before the step) and plant_step(), everything planned once, on one stream and without a host round trip.  `batch` is advanced IN
+    PLACE and ends bit for bit where ctl.rollout() leaves it.  `tangents`: any of the start state's "Rwb_rot_tan", "x_tan",
+    "xdot_tan", "w_tan" [n,3], step 0's "feet_tan" [n,4,3] (body frame), and - held, applied at every step - "foot_world_tan" [n,4,3]
+    and the desired state's "x_d_tan", "xdot_d_tan", "w_d_tan", "Rwb_d_rot_tan"; each [n, ...] or [K, n, ...], all agreeing; none is
+    written.  Returns (state, res): `state` the tensors of `batch`, `res` the final "Rwb_rot_tan", "x_tan", "xdot_tan", "w_tan",
+    "feet_tan", the last solve's "grf_tan" ([K, n, ...], squeezed where the tangents came as [n, ...]) and "flags" int32 [n],
+    tangent_batch()'s flags OR-ed over the steps on the device.  The derivative is the one on the active face of every solve at
+    `act_tol`, as rollout_autograd()'s.  Tangent memory is one set of buffers whatever `steps` is."""
+    import contextlib
+
+    import torch
+
+    if batch.get("joint_q") is not None or batch.get("feet") is None:
+        raise ValueError("rollout: the plant is a single rigid body - the batch carries `feet`, not joint_q")
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError("rollout: steps must be >= 0")
+    unknown = [k for k in tangents if k not in ROLLOUT_TANGENTS]
+    if unknown:
+        raise ValueError(f"rollout_tangent: unknown tangent(s) {unknown}; the tangents are {tuple(ROLLOUT_TANGENTS)}")
+    n = batch["x"].shape[0]
+    dev = torch.device("cuda", ctl.device)
+    given, K, squeeze = _directions(tangents, ROLLOUT_TANGENTS, n, dev)
+    if not given:
+        raise ValueError("rollout_tangent: no tangent given")
+    on_stream = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+    with on_stream:
+        # one set of buffers: the state's tangents and feet_tan are advanced in place, grf_tan is rewritten by every step
+        buf = {k: (given[k].reshape((K, n) + ((4, 3) if m == 12 else (3,))).clone() if k in given else
+                   torch.zeros((K, n) + ((4, 3) if m == 12 else (3,)), dtype=torch.float64, device=dev))
+               for k, m in ROLLOUT_TANGENTS.items() if k in _ROLLOUT_STATE or k == "feet_tan"}
+        grf_tan = torch.zeros((K, n, 4, 3), dtype=torch.float64, device=dev)
+        flags, step_flags = (torch.zeros((n,), dtype=torch.int32, device=dev) for _ in range(2))
+    held = {k: given[k].reshape(K, n, 3) for k in _ROLLOUT_HELD if k in given}
+    fw_tan = given["foot_world_tan"].reshape(K, n, 4, 3) if "foot_world_tan" in given else None
+    state = {k: batch[k] for k in ("Rwb", "x", "xdot", "w")}
+    r = _RolloutPlans(ctl, "rollout_tangent", batch, n, warm, lambda first, w, o: ctl.plan_batch(batch, w, o, want_active_set=warm, stream=stream)[0],
+                      None, stream)
+    if steps > 0 and n > 0:
+        solve_tan, _, _ = plan_tangent(ctl, batch, r.out["grf_body"], dict(buf, **held), ("grf_tan", "flags"), act_tol,
+                                       {"grf_tan": grf_tan, "flags": step_flags}, stream)
+        plant_in = {k: buf[k] for k in _ROLLOUT_STATE}
+        plant_in["grf_tan"] = grf_tan
+        if fw_tan is not None:
+            plant_in["foot_world_tan"] = fw_tan
+        plant_out = {k[:-4] + "_next_tan": buf[k] for k in _ROLLOUT_STATE}
+        plant_out["feet_next_tan"] = buf["feet_tan"]
+        step_tan, _, _ = plan_plant_step_tangent(ctl, state, r.out["grf_body"], foot_world, dt, plant_in, PLANT_TANGENT_WANT, plant_out, stream)
+        step = ctl.plan_plant(state, r.out["grf_body"], foot_world, dt, batch["feet"], stream)
+        for k in range(steps):
+            r.solve(k)
+            solve_tan()
+            with on_stream:
+                flags.bitwise_or_(step_flags)
+            step_tan()
+            step()
+    res = dict(buf, grf_tan=grf_tan)
+    res = {k: (v[0] if squeeze else v) for k, v in res.items()}
+    res["flags"] = flags
+    return state, res
+
+
+def transition_seeds(batch, foot_world, columns=TRANSITION_COLUMNS):
+    """rollout_tangent()'s `tangents` for unit seeds on the start state: direction j moves coordinate columns[j] - (name, component)
+    with name in "Rwb_rot", "x", "xdot", "w" - by one, and step 0's feet_tan follows from the pinned feet,
+    Rwb^T (-dx - delta x (foot_world - x)).  [K, n, ...] device tensors."""
+    import torch
+
+    n, dev = batch["x"].shape[0], batch["x"].device
+    K = len(columns)
+    seeds = {k: torch.zeros((K, n, 3), dtype=torch.float64, device=dev) for k in _ROLLOUT_STATE}
+    for j, (name, comp) in enumerate(columns):
+        if name + "_tan" not in seeds:
+            raise ValueError(f"rollout_transition: unknown coordinate {name!r}; the coordinates are {tuple(k[:-4] for k in _ROLLOUT_STATE)}")
+        seeds[name + "_tan"][j, :, comp] = 1.0
+    R = batch["Rwb"].reshape(1, n, 1, 3, 3)
+    arm = (foot_world.reshape(n, 4, 3) - batch["x"].reshape(n, 1, 3)).unsqueeze(0)
+    delta, dx = seeds["Rwb_rot_tan"].unsqueeze(2), seeds["x_tan"].unsqueeze(2)
+    world = -dx - torch.cross(delta.expand(K, n, 4, 3), arm.expand(K, n, 4, 3), dim=-1)
+    seeds["feet_tan"] = (R.transpose(-1, -2) * world.unsqueeze(-2)).sum(-1).contiguous()  # Rwb^T world, elementwise: the same bits however the seeds are chunked
+    return seeds
+
+
+def rollout_transition(ctl, batch, foot_world, steps, dt, act_tol=1e-7, warm=True, chunk=None, stream=None):
+    """The 12 x 12 state-transition matrix of `steps` closed-loop steps in minimal coordinates (rotation tangent, x, xdot, w):
+    rollout_tangent() on the 12 unit seeds of the start state (transition_seeds), `chunk` seeds per rollout (None: all in one; the
+    start state is restored between the chunks).  `batch` is advanced in place, as by ctl.rollout().  Returns dict(phi [n,12,12] -
+    phi[:, r, c] = d (coordinate r after the steps) / d (coordinate c at the start), rows and columns in the order of `columns` -,
+    columns: the list of (name, component), flags int32 [n]: OR-ed over the steps and the chunks).  Column c equals rollout_tangent()
+    on seed c bit for bit, however the columns are chunked; steps = 0 gives the identity."""
+    import contextlib
+
+    import torch
+
+    cols = list(TRANSITION_COLUMNS)
+    n, dev = batch["x"].shape[0], batch["x"].device
+    size = len(cols) if chunk is None else int(chunk)
+    if size < 1:
+        raise ValueError("rollout_transition: chunk must be >= 1")
+    on_stream = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+    moved = ("Rwb", "x", "xdot", "w", "feet")
+    with on_stream:
+        phi = torch.empty((n, 12, 12), dtype=torch.float64, device=dev)
+        flags = torch.zeros((n,), dtype=torch.int32, device=dev)
+        start = {k: batch[k].clone() for k in moved} if size < len(cols) else None
+    for c0 in range(0, len(cols), size):
+        part = cols[c0:c0 + size]
+        with on_stream:
+            if c0 > 0:
+                for k in moved:
+                    batch[k].copy_(start[k])
+            seeds = transition_seeds(batch, foot_world, part)
+        _, res = rollout_tangent(ctl, batch, foot_world, steps, dt, seeds, act_tol, warm, stream)
+        with on_stream:
+            rows = torch.cat([res[k] for k in _ROLLOUT_STATE], dim=-1)  # [len(part), n, 12]
+            phi[:, :, c0:c0 + len(part)] = rows.permute(1, 2, 0)
+            flags.bitwise_or_(res["flags"])
+    return dict(phi=phi, columns=cols, flags=flags)
