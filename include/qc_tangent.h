@@ -1,5 +1,5 @@
 /* qc_tangent.h - forward mode of the balance QP: qc_tangent_batch pushes K tangents on the inputs of a solved batch through the
- * QP on its active face and returns the tangents of the forces.  A header beside qc_balance.h: the two functions live in the same
+ * QP on its active face and returns the tangents of the forces.  A header beside qc_balance.h: its functions live in the same
  * libqc_balance.so, QC_ABI_VERSION and the records of qc_balance.h are untouched.
  *
  * Per robot the solve minimises (A f - b)^T S (A f - b) + f^T W f over the world-frame forces f under the pyramid rows described
@@ -30,12 +30,14 @@
  * nothing is clamped.
  *
  * OUT OF SCOPE: entrywise (nine-number) rotation tangents - the rotations move along the left tangents above only; tangents of
- * the handle's parameters (mu, fzmin, fzmax, the weights, the gains, mass, Ib, the kinematic model); tangents through the J^T
- * torque map, the leg plant and the swing pipeline; weak activity (a row whose multiplier is about 0 is on the face like any other);
- * commander mode (the desired state must be in `in`); a jvp on the torch.autograd.Functions of the Python package.
+ * the handle's parameters (mu, fzmin, fzmax, the weights, the gains, mass, Ib, the kinematic model); tangents through the swing
+ * pipeline (the swing legs' PD torques, the planner's references, the gait clock); weak activity (a row whose multiplier is about 0
+ * is on the face like any other); commander mode (the desired state must be in `in`); a jvp on the torch.autograd.Functions of the
+ * Python package.
  *
  * The rigid-body plant step has its forward mode below, qc_plant_step_tangent_batch: with it the two calls chain, step after step,
- * into the tangent of a closed-loop rollout. */
+ * into the tangent of a closed-loop rollout.  The loop around the complete tick - joint_q -> FK -> QP -> clamped J^T -> joint_tau ->
+ * legged plant - chains four calls: qc_tangent_batch (joint_q_tan), qc_torque_tangent_batch, qc_leg_plant_step_tangent_batch, all below. */
 #ifndef QC_TANGENT_H
 #define QC_TANGENT_H
 
@@ -87,7 +89,8 @@ int qc_tangent_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_tan
  * layout - x_next_tan over x_tan, Rwb_rot_next_tan over Rwb_rot_tan, feet_next_tan over grf_tan or foot_world_tan - and a rollout
  * carries one set of tangent buffers.  The state, force and feet inputs are never written.  All pointers are device pointers.
  *
- * OUT OF SCOPE: the leg plant (qc_leg_plant_step_batch); tangents of mass, Ib and dt; entrywise rotation tangents. */
+ * OUT OF SCOPE: tangents of mass, Ib and dt; entrywise rotation tangents.  (The leg plant has its own call,
+ * qc_leg_plant_step_tangent_batch, below.) */
 typedef struct qc_plant_tangent_io {
   size_t struct_size;            /* = sizeof(qc_plant_tangent_io); checked                                            */
   const double *Rwb;             /* [n][9] the state BEFORE the step                                                  */
@@ -110,6 +113,90 @@ void qc_default_plant_tangent(qc_plant_tangent_io* io);
  * struct_size, a dt that is not finite and > 0, n_dir == 0, no tangent given at all, no output requested at all, a missing state,
  * force or feet array, a handle whose mass or Ib qc_plant_step_batch refuses, or n * n_dir beyond one launch. */
 int qc_plant_step_tangent_batch(qc_handle* h, size_t n, const qc_plant_tangent_io* io, void* stream);
+
+/* qc_torque_tangent_batch - forward mode of the clamped J^T torque map, the map qc_sensitivity_kin_batch transposes.  Per direction,
+ * robot and leg l, with q = joint_q_l, J the leg Jacobian, H_r = d^2 p_r / d q^2, g = grf_body_l, tau_raw = J^T g:
+ *   joint_tau_tan_l = m o ( J^T grf_tan_l + (sum_r g_r H_r) joint_q_tan_l )
+ * m is qc_sensitivity_kin_batch's mask: m_c = 1 where !(tau_raw_c < tau_min) && !(tau_raw_c > tau_max) (equality passes, a NaN passes
+ * and propagates), m = 0 for a swing leg and for a robot with status != 0; the contact mask is resolved as qc_certify_batch
+ * resolves it (in->stance, else the phase rule on in->gait_phase with in->gait_duty or the handle's duty, else all stance).  Of `in`
+ * only joint_q and the contact inputs are read; nothing is written.  <joint_tau_bar, joint_tau_tan> equals <grf_bar, grf_tan> +
+ * <joint_q_bar, joint_q_tan> of qc_sensitivity_kin_batch's torque half.
+ *
+ * joint_tau_tan may BE grf_tan or joint_q_tan: a (direction, robot, leg) reads all its inputs before it writes and touches only its
+ * own row.  Non-finite inputs propagate as NaN where m = 1; nothing is clamped.
+ *
+ * OUT OF SCOPE: with swing references the swing legs' PD torque gets tangent 0; there are no tangents of the kinematic constants or
+ * of tau_min / tau_max. */
+typedef struct qc_torque_tangent_io {
+  size_t struct_size;            /* = sizeof(qc_torque_tangent_io); checked                                           */
+  const double* grf_body;        /* [n][4][3] qc_batch_out.grf_body                                                   */
+  const int32_t* status;         /* [n] qc_batch_out.status                                                           */
+  size_t n_dir;                  /* K >= 1 directions per launch                                                      */
+  /* tangents, direction-major as in qc_tangent_io; NULL = zero, at least one given                                   */
+  const double* grf_tan;         /* [K][n][4][3] what qc_tangent_batch wrote                                          */
+  const double* joint_q_tan;     /* [K][n][12]                                                                        */
+  double* joint_tau_tan;         /* [K][n][12] required                                                               */
+} qc_torque_tangent_io;
+/* struct_size set, pointers NULL, n_dir = 1. */
+void qc_default_torque_tangent(qc_torque_tangent_io* io);
+/* Asynchronous on `stream`, no host synchronisation (graph-capturable); n == 0 launches nothing and returns QC_OK.
+ * QC_ERR_INVALID (message starting with "qc_torque_tangent_batch:", nothing launched) for a null handle, `in` or `io`, a wrong
+ * struct_size, n_dir == 0, no output (joint_tau_tan NULL), no tangent given at all, a missing grf_body or status, a missing
+ * in->joint_q, or 4 * n * n_dir beyond one launch. */
+int qc_torque_tangent_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_torque_tangent_io* io, void* stream);
+
+/* qc_leg_plant_step_tangent_batch - forward mode of qc_leg_plant_step_batch: K tangents on the inputs of one step of the legged plant
+ * pushed through it, in one launch.  Given the state BEFORE the step (Rwb, x, xdot, w, joint_q, joint_qdot), the torques, the contact
+ * inputs (resolved as the step resolves them, cmd_state included), dt and leg_inertia - nothing is saved by the forward step; it is
+ * recomputed - per direction, in the notation of qc_leg_plant_step_batch and its adjoint (delta the world-frame left tangent of Rwb,
+ * G(g) = sum_r g_r H_r):
+ *   stance leg    dp = J dq,  dg = J^-T (dtau - G(g) dq),  df = delta x f - Rwb dg,  dr = delta x r + Rwb dp,  dc = dx + dr
+ *   body          qc_plant_step_tangent_batch's block from (df_l, dr_l): da, dtau_body = sum (dr x f + r x df), dh, dc, dwdot, the
+ *                 semi-implicit Euler lines, delta' = Jl(phi) dt dw' + Exp(phi) delta (series / quotients / smooth limit as there)
+ *   stance leg, after the body has moved
+ *                 dp' = Rwb'^T (dc - dx' - delta' x (c - x')),  dqn = J(qn)^-1 dp',  dq' = dqn,  dqd' = (dqn - dq) / dt
+ *                 (wrap_PI has slope 1; the IK inverts the FK, so its derivative is the inverse Jacobian at the angles it returned)
+ *   swing leg     dqd' = dqd + dt dtau / leg_inertia,  dq' = dq + dt dqd'
+ * <cotangents of the step's outputs, these tangents> equals <qc_leg_plant_step_adjoint_batch's cotangents, the input tangents>, with
+ * the entrywise Rwb_bar paired with [delta]x Rwb and Rwb_next_bar with [delta']x Rwb'.
+ *
+ * `flags` carries the adjoint's bits under the adjoint's rules: bit l, J(q_l) of stance leg l is outside the closed-form band;
+ * bit 4 + l, leg l is out of reach or J(qn_l) is outside the band.  A robot with any bit set gets NaN in every output row of every
+ * direction.  Other non-finite inputs propagate as NaN; nothing is clamped.  A (robot, direction) pair reads all its inputs before
+ * it writes and touches only its own rows: each `_next_tan` may BE the input tangent of its layout, and joint_qdot_next_tan may also
+ * be joint_tau_tan.  The state and torque inputs are never written.  All pointers are device pointers.
+ *
+ * OUT OF SCOPE: tangents of mass, Ib, leg_inertia, dt and the kinematic constants; the contact mask is held; entrywise rotation
+ * tangents; a tangent of the optional foot_world output of the step. */
+typedef struct qc_leg_plant_tangent_io {
+  size_t struct_size;               /* = sizeof(qc_leg_plant_tangent_io); checked                                     */
+  const double *Rwb, *x, *xdot, *w; /* [n][9], [n][3] x 3: the state BEFORE the step                                  */
+  const double *joint_q, *joint_qdot; /* [n][4][3] before the step (joint_qdot's values are not read)                 */
+  const double* joint_tau;          /* [n][4][3] the torques the step read                                            */
+  const uint8_t* stance;            /* [n][4] optional: the contact inputs of the forward call                        */
+  const double* gait_phase;         /* [n][4] optional                                                                */
+  const double* gait_duty;          /* [n] optional                                                                   */
+  const qc_commander_state* cmd_state; /* [n] optional                                                                */
+  double leg_inertia[3];            /* kg m^2 (hip, thigh, calf), finite and > 0: the step's                          */
+  double dt;                        /* seconds, finite, > 0: the step's                                               */
+  size_t n_dir;                     /* K >= 1 directions per launch                                                   */
+  /* tangents, direction-major as in qc_tangent_io; NULL = zero, at least one given                                   */
+  const double *Rwb_rot_tan, *x_tan, *xdot_tan, *w_tan;            /* [K][n][3]                                       */
+  const double *joint_q_tan, *joint_qdot_tan, *joint_tau_tan;      /* [K][n][12]                                      */
+  /* outputs, each optional, at least one given (flags counts)                                                        */
+  double *Rwb_rot_next_tan, *x_next_tan, *xdot_next_tan, *w_next_tan;  /* [K][n][3]                                   */
+  double *joint_q_next_tan, *joint_qdot_next_tan;                      /* [K][n][12]                                  */
+  int32_t* flags;                   /* [n]: bit l singular J(q_l), bit 4 + l out of reach or singular J(qn_l)         */
+} qc_leg_plant_tangent_io;
+/* struct_size set, pointers NULL, dt = 1/300, n_dir = 1, leg_inertia = 0 (the caller must give the step's). */
+void qc_default_leg_plant_tangent(qc_leg_plant_tangent_io* io);
+/* Asynchronous on `stream`, no host synchronisation (graph-capturable); n == 0 launches nothing and returns QC_OK.
+ * QC_ERR_INVALID (message starting with "qc_leg_plant_step_tangent_batch:", nothing launched) for a null handle or `io`, a wrong
+ * struct_size, a dt or a leg_inertia entry that is not finite and > 0, n_dir == 0, no tangent given at all, no output requested at
+ * all, a missing Rwb, x, xdot, w, joint_q, joint_qdot or joint_tau, a handle whose mass or Ib qc_plant_step_batch refuses, or
+ * n * n_dir beyond one launch. */
+int qc_leg_plant_step_tangent_batch(qc_handle* h, size_t n, const qc_leg_plant_tangent_io* io, void* stream);
 
 #ifdef __cplusplus
 }

@@ -2355,6 +2355,33 @@ int qc_plant_step_tangent_batch(qc_handle* h, size_t n, const qc_plant_tangent_i
   return launch_flat(qc::plant_step_tangent_kernel, qc::plant_tangent_blocks(n, io->n_dir), qc::PLANT_TANGENT_BLOCK, stream, (long)n, a);
 }
 
+void qc_default_torque_tangent(qc_torque_tangent_io* io) {
+  if (!zeroed(io)) return;
+  io->n_dir = 1;
+}
+
+int qc_torque_tangent_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_torque_tangent_io* io, void* stream) {
+  if (const int rc = qc::check_torque_tangent_args(h, n, in, io); rc != QC_OK || n == 0) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  // (of `in`: joint_q and the contact mask as it is now - no state array, nothing that advances or plans)
+  return launch_flat(qc::torque_tangent_kernel, qc::torque_tangent_blocks(n, io->n_dir), qc::TORQUE_TANGENT_BLOCK, stream, h->d_params, (long)(4 * n),
+                     qc::torque_tangent_constants(in, io));
+}
+
+void qc_default_leg_plant_tangent(qc_leg_plant_tangent_io* io) {
+  if (!zeroed(io)) return;  // (leg_inertia 0, as qc_default_leg_plant leaves it)
+  io->dt = 1.0 / 300.0;  // qc_default_leg_plant's
+  io->n_dir = 1;
+}
+
+int qc_leg_plant_step_tangent_batch(qc_handle* h, size_t n, const qc_leg_plant_tangent_io* io, void* stream) {
+  if (const int rc = qc::check_leg_plant_tangent_args(h, n, io); rc != QC_OK || n == 0) return rc;
+  qc::LegPlantTangentArgs a;
+  if (const int rc = qc::leg_plant_tangent_constants(h->dp.mass, h->dp.Ib, io, a); rc != QC_OK) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  return launch_flat(qc::leg_plant_step_tangent_kernel, qc::leg_plant_tangent_blocks(n, io->n_dir), qc::LEG_PLANT_TANGENT_BLOCK, stream, h->d_params, (long)n, a);
+}
+
 void qc_default_sensitivity_rot(qc_sensitivity_rot_io* io) { (void)zeroed(io); }
 
 int qc_sensitivity_rot_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_rot_io* io, void* stream) {

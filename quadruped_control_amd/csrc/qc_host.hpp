@@ -26,6 +26,8 @@
 #include "qc_com_reference.hpp"
 #include "qc_tangent.hpp"
 #include "qc_plant_tangent.hpp"
+#include "qc_torque_tangent.hpp"
+#include "qc_leg_plant_tangent.hpp"
 
 namespace qc {
 
@@ -940,5 +942,68 @@ inline int plant_tangent_constants(double mass, const double* Ib, const qc_plant
 
 // workgroups of plant_step_tangent_kernel for n robots and K directions: one wave of pairs each, capped (a grid cap of its own)
 inline unsigned plant_tangent_blocks(size_t n, size_t n_dir) { return capped_blocks(n * n_dir, PLANT_TANGENT_BLOCK, PLANT_TANGENT_MAX_BLOCKS); }
+
+// ---------------------------------------------------------------- qc_torque_tangent_batch
+// What is wrong with the call itself (message prefix "qc_torque_tangent_batch:").  The kernel reads joint_q and the contact mask of
+// `in` and none of the state arrays: they are not asked for.  One lane per (direction, robot, leg): the rows must fit a launch.
+inline int check_torque_tangent_args(const qc_handle* h, size_t n, const qc_batch_in* in, const qc_torque_tangent_io* io) {
+  const char* who = "qc_torque_tangent_batch";
+  if (const int rc = check_io(who, h && in, io, "qc_torque_tangent_io", "qc_default_torque_tangent"); rc != QC_OK) return rc;
+  const auto bad = [who](const char* what) { return fail(QC_ERR_INVALID, std::string(who) + what); };
+  if (io->n_dir == 0) return bad(": n_dir must be >= 1");
+  if (!io->joint_tau_tan) return bad(": no output requested (joint_tau_tan is NULL)");
+  if (!io->grf_tan && !io->joint_q_tan) return bad(": no tangent given (grf_tan and joint_q_tan are both NULL)");
+  if (!io->grf_body || !io->status) return bad(": joint_tau_tan needs grf_body and status");
+  if (n == 0) return QC_OK;
+  if (!in->joint_q) return bad(": joint_q is required");
+  if (n > (size_t)0xFFFFFF * (size_t)TORQUE_TANGENT_BLOCK / 4 || io->n_dir > (size_t)0xFFFFFF * (size_t)TORQUE_TANGENT_BLOCK / (4 * n))
+    return bad(": 4 * n * n_dir is beyond one launch");
+  return QC_OK;
+}
+
+// the kernel's arguments: joint_q and the contact inputs of `in`, the record's arrays
+inline TorqueTangentArgs torque_tangent_constants(const qc_batch_in* in, const qc_torque_tangent_io* io) {
+  return TorqueTangentArgs{in->joint_q, in->stance, in->gait_phase, in->gait_duty, io->grf_body, io->status, (long)io->n_dir, io->grf_tan, io->joint_q_tan,
+                           io->joint_tau_tan};
+}
+
+// workgroups of torque_tangent_kernel for n robots and K directions: one wave of rows each, capped (a grid cap of its own)
+inline unsigned torque_tangent_blocks(size_t n, size_t n_dir) { return capped_blocks(4 * n * n_dir, TORQUE_TANGENT_BLOCK, TORQUE_TANGENT_MAX_BLOCKS); }
+
+// ---------------------------------------------------------------- qc_leg_plant_step_tangent_batch
+// What is wrong with the call itself (message prefix "qc_leg_plant_step_tangent_batch:"); the handle's mass and Ib are judged by
+// leg_plant_tangent_constants, through the plant's own checks.  One lane per (robot, direction): the pairs must fit a launch.
+inline int check_leg_plant_tangent_args(const qc_handle* h, size_t n, const qc_leg_plant_tangent_io* io) {
+  const char* who = "qc_leg_plant_step_tangent_batch";
+  if (const int rc = check_io(who, h != nullptr, io, "qc_leg_plant_tangent_io", "qc_default_leg_plant_tangent"); rc != QC_OK) return rc;
+  const char* own = nullptr;
+  if (io->n_dir == 0) own = ": n_dir must be >= 1";
+  else if (!io->Rwb_rot_tan && !io->x_tan && !io->xdot_tan && !io->w_tan && !io->joint_q_tan && !io->joint_qdot_tan && !io->joint_tau_tan)
+    own = ": no tangent given (Rwb_rot_tan, x_tan, xdot_tan, w_tan, joint_q_tan, joint_qdot_tan, joint_tau_tan are all NULL)";
+  else if (!io->Rwb_rot_next_tan && !io->x_next_tan && !io->xdot_next_tan && !io->w_next_tan && !io->joint_q_next_tan && !io->joint_qdot_next_tan && !io->flags)
+    own = ": no output requested (Rwb_rot_next_tan, x_next_tan, xdot_next_tan, w_next_tan, joint_q_next_tan, joint_qdot_next_tan, flags are all NULL)";
+  for (int k = 0; k < 3; k++)
+    if (!std::isfinite(io->leg_inertia[k]) || !(io->leg_inertia[k] > 0.0))
+      own = ": leg_inertia (hip, thigh, calf) must be finite and > 0; qc_default_leg_plant_tangent leaves it at 0, the caller gives the step's";
+  if (const int rc = check_plant_io(who, n, io, own, io->joint_q && io->joint_qdot && io->joint_tau, ": joint_q, joint_qdot and joint_tau are required", LEG_PLANT_TANGENT_BLOCK);
+      rc != QC_OK || n == 0)
+    return rc;
+  if (io->n_dir > (size_t)0xFFFFFF * (size_t)LEG_PLANT_TANGENT_BLOCK / n) return fail(QC_ERR_INVALID, std::string(who) + ": n * n_dir is beyond one launch");
+  return QC_OK;
+}
+
+// the kernel's arguments: what the leg-plant calls share (leg_plant_shared), the tangents and the outputs
+inline int leg_plant_tangent_constants(double mass, const double* Ib, const qc_leg_plant_tangent_io* io, LegPlantTangentArgs& a) {
+  if (const int rc = leg_plant_shared("qc_leg_plant_step_tangent_batch", mass, Ib, io, a); rc != QC_OK) return rc;
+  a.n_dir = (long)io->n_dir;
+  a.Rwb_rot_tan = io->Rwb_rot_tan; a.x_tan = io->x_tan; a.xdot_tan = io->xdot_tan; a.w_tan = io->w_tan;
+  a.joint_q_tan = io->joint_q_tan; a.joint_qdot_tan = io->joint_qdot_tan; a.joint_tau_tan = io->joint_tau_tan;
+  a.Rwb_rot_next_tan = io->Rwb_rot_next_tan; a.x_next_tan = io->x_next_tan; a.xdot_next_tan = io->xdot_next_tan; a.w_next_tan = io->w_next_tan;
+  a.joint_q_next_tan = io->joint_q_next_tan; a.joint_qdot_next_tan = io->joint_qdot_next_tan; a.flags = io->flags;
+  return QC_OK;
+}
+
+// workgroups of leg_plant_step_tangent_kernel for n robots and K directions: one wave of pairs each, capped (a grid cap of its own)
+inline unsigned leg_plant_tangent_blocks(size_t n, size_t n_dir) { return capped_blocks(n * n_dir, LEG_PLANT_TANGENT_BLOCK, LEG_PLANT_TANGENT_MAX_BLOCKS); }
 
 }  // namespace qc

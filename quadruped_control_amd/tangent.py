@@ -5,14 +5,24 @@ The plant step's forward mode (qc_plant_step_tangent_batch, csrc/qc_plant_tangen
 chained step after step - rollout_tangent(), the forward-mode twin of rollout(), and rollout_transition(), the 12 x 12
 state-transition matrix of a closed-loop rollout.
 
-The functions take the controller as their first argument, as autograd.py's do.  The four symbols of the library are bound here, on
-the CDLL that _lib.load() returns, with this module's own ctypes record: _lib.EXPORTS and BalanceController are not touched."""
+The loop around the complete tick has its forward mode too: torque_tangent() (qc_torque_tangent_batch, csrc/qc_torque_tangent.hpp),
+the clamped J^T torque map, and leg_plant_step_tangent() (qc_leg_plant_step_tangent_batch, csrc/qc_leg_plant_tangent.hpp), the legged
+plant; rollout_tick_tangent() chains them with tangent_batch() into the forward-mode twin of ctl.rollout_tick(batch, None, ...), and
+rollout_tick_transition() is its 36 x 36 state-transition matrix.
+
+The functions take the controller as their first argument, as autograd.py's do.  The symbols of the library are bound here, on
+the CDLL that _lib.load() returns, with this module's own ctypes records: _lib.EXPORTS and BalanceController are not touched.
+
+Not covered: the swing pipeline (swing references, the planner, the gait clock), commander mode, tangents of the handle's parameters,
+and a jvp on the torch.autograd.Functions of autograd.py."""
 from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
+
 from . import _lib
-from .balance_controller import _READONLY_FIELDS, _RolloutPlans, _outputs
+from .balance_controller import _KINEMATICS_FIELDS, _READONLY_FIELDS, COMMANDER_STATE_DTYPE, _check_tensor, _fill, _RolloutPlans, _outputs
 
 # name -> values per robot; the names are the record's fields
 TANGENTS = {"x_tan": 3, "xdot_tan": 3, "w_tan": 3, "x_d_tan": 3, "xdot_d_tan": 3, "w_d_tan": 3, "Rwb_rot_tan": 3, "Rwb_d_rot_tan": 3,
@@ -31,6 +41,33 @@ ROLLOUT_TANGENTS = {**{k: 3 for k in _ROLLOUT_STATE}, "feet_tan": 12, "foot_worl
 TRANSITION_COLUMNS = tuple((name, c) for name in ("Rwb_rot", "x", "xdot", "w") for c in range(3))  # rollout_transition's rows and columns
 
 
+# the torque map's forward mode (qc_torque_tangent_io) and the leg plant's (qc_leg_plant_tangent_io)
+TORQUE_TANGENTS = {"grf_tan": 12, "joint_q_tan": 12}
+_TORQUE_TANGENT_OUTPUTS = {"joint_tau_tan": ((4, 3), "float64")}
+LEG_PLANT_TANGENTS = {"Rwb_rot_tan": 3, "x_tan": 3, "xdot_tan": 3, "w_tan": 3, "joint_q_tan": 12, "joint_qdot_tan": 12, "joint_tau_tan": 12}
+_LEG_PLANT_TANGENT_OUTPUTS = {**{k: ((3,), "float64") for k in ("Rwb_rot_next_tan", "x_next_tan", "xdot_next_tan", "w_next_tan")},
+                              "joint_q_next_tan": ((4, 3), "float64"), "joint_qdot_next_tan": ((4, 3), "float64")}
+LEG_PLANT_TANGENT_WANT = tuple(_LEG_PLANT_TANGENT_OUTPUTS)
+# rollout_tick_tangent(): the start state's six tangents and the held ones; rollout_tick_transition()'s 36 coordinates
+_TICK_STATE = ("Rwb_rot_tan", "x_tan", "xdot_tan", "w_tan", "joint_q_tan", "joint_qdot_tan")
+ROLLOUT_TICK_TANGENTS = {**{k: LEG_PLANT_TANGENTS[k] for k in _TICK_STATE}, **{k: 3 for k in _ROLLOUT_HELD}}
+TICK_TRANSITION_COLUMNS = tuple((name, c) for name in ("Rwb_rot", "x", "xdot", "w") for c in range(3)) + \
+    tuple((name, c) for name in ("joint_q", "joint_qdot") for c in range(12))
+TICK_PLANT_FLAGS_SHIFT = 8  # rollout_tick_tangent()'s flags: tangent_batch()'s bits | the plant's bits << 8
+
+
+class QcTorqueTangentIo(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("grf_body", C.c_void_p), ("status", C.c_void_p), ("n_dir", C.c_size_t)] + \
+               [(k, C.c_void_p) for k in ("grf_tan", "joint_q_tan", "joint_tau_tan")]
+
+
+class QcLegPlantTangentIo(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t)] + \
+               [(k, C.c_void_p) for k in ("Rwb", "x", "xdot", "w", "joint_q", "joint_qdot", "joint_tau", "stance", "gait_phase", "gait_duty", "cmd_state")] + \
+               [("leg_inertia", C.c_double * 3), ("dt", C.c_double), ("n_dir", C.c_size_t)] + \
+               [(k, C.c_void_p) for k in tuple(LEG_PLANT_TANGENTS) + LEG_PLANT_TANGENT_WANT + ("flags",)]
+
+
 class QcTangentIo(C.Structure):
     _fields_ = [("struct_size", C.c_size_t), ("grf_body", C.c_void_p), ("act_tol", C.c_double), ("n_dir", C.c_size_t)] + \
                [(k, C.c_void_p) for k in tuple(TANGENTS) + ("grf_tan", "b_tan", "flags")]
@@ -45,11 +82,12 @@ _bound = None
 
 
 def _library():
-    """the library with this module's four symbols bound"""
+    """the library with this module's symbols bound"""
     global _bound
     if _bound is None:
         lib = _lib.load()
-        for name in ("qc_default_tangent", "qc_tangent_batch", "qc_default_plant_tangent", "qc_plant_step_tangent_batch"):
+        for name in ("qc_default_tangent", "qc_tangent_batch", "qc_default_plant_tangent", "qc_plant_step_tangent_batch", "qc_default_torque_tangent",
+                     "qc_torque_tangent_batch", "qc_default_leg_plant_tangent", "qc_leg_plant_step_tangent_batch"):
             if not hasattr(lib, name):
                 raise ImportError(f"{_lib.LIB_PATH} does not export {name}")
         lib.qc_default_tangent.argtypes = [C.POINTER(QcTangentIo)]
@@ -60,6 +98,14 @@ def _library():
         lib.qc_default_plant_tangent.restype = None
         lib.qc_plant_step_tangent_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcPlantTangentIo), C.c_void_p]
         lib.qc_plant_step_tangent_batch.restype = C.c_int
+        lib.qc_default_torque_tangent.argtypes = [C.POINTER(QcTorqueTangentIo)]
+        lib.qc_default_torque_tangent.restype = None
+        lib.qc_torque_tangent_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(_lib.QcBatchIn), C.POINTER(QcTorqueTangentIo), C.c_void_p]
+        lib.qc_torque_tangent_batch.restype = C.c_int
+        lib.qc_default_leg_plant_tangent.argtypes = [C.POINTER(QcLegPlantTangentIo)]
+        lib.qc_default_leg_plant_tangent.restype = None
+        lib.qc_leg_plant_step_tangent_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcLegPlantTangentIo), C.c_void_p]
+        lib.qc_leg_plant_step_tangent_batch.restype = C.c_int
         _bound = lib
     return _bound
 
@@ -124,8 +170,8 @@ def tangent_batch(ctl, batch, grf_body, tangents, want=("grf_tan",), act_tol=1e-
     The reduced system is factorised once per robot and substituted K times in one launch.  Nothing of `batch` is written.
     Asynchronous on `stream`, no synchronisation.  Returns the dict of device tensors, [K, n, ...] - squeezed to [n, ...] where the
     tangents came that way; `out`: a dict of tensors with K * n rows to write into.  ValueError with the library's message for a
-    call it refuses.  Not covered: entrywise rotation tangents, tangents of the handle's parameters, of the torque map, the leg plant
-    and the swing pipeline."""
+    call it refuses.  Not covered: entrywise rotation tangents, tangents of the handle's parameters and of the swing pipeline (the
+    torque map and the leg plant have their own calls, torque_tangent() and leg_plant_step_tangent())."""
     launch, res, squeeze = plan_tangent(ctl, batch, grf_body, tangents, want, act_tol, out, stream)
     launch()
     return {k: (v[0] if squeeze and k != "flags" else v) for k, v in res.items()}
@@ -202,7 +248,7 @@ def plant_step_tangent(ctl, state, grf_body, foot_world, dt, tangents, want=PLAN
     plant_step() writes.  The step is recomputed from `state`; nothing of it is written.  `out`: a dict of tensors with K * n rows
     to write into - each may be the input tangent of its layout.  Asynchronous on `stream`, no synchronisation.  Returns the dict of
     device tensors, squeezed to [n, ...] where the tangents came that way.  ValueError with the library's message for a call it
-    refuses.  Not covered: tangents of mass, Ib and dt, the leg plant."""
+    refuses.  Not covered: tangents of mass, Ib and dt (the leg plant: leg_plant_step_tangent())."""
     launch, res, squeeze = plan_plant_step_tangent(ctl, state, grf_body, foot_world, dt, tangents, want, out, stream)
     launch()
     return {k: (v[0] if squeeze else v) for k, v in res.items()}
@@ -325,6 +371,241 @@ def rollout_transition(ctl, batch, foot_world, steps, dt, act_tol=1e-7, warm=Tru
         _, res = rollout_tangent(ctl, batch, foot_world, steps, dt, seeds, act_tol, warm, stream)
         with on_stream:
             rows = torch.cat([res[k] for k in _ROLLOUT_STATE], dim=-1)  # [len(part), n, 12]
+            phi[:, :, c0:c0 + len(part)] = rows.permute(1, 2, 0)
+            flags.bitwise_or_(res["flags"])
+    return dict(phi=phi, columns=cols, flags=flags)
+
+
+# ------------------------------------------------------------------ forward mode around the tick: the torque map, the leg plant, the loop
+def plan_torque_tangent(ctl, batch, grf_body, status, tangents, out=None, stream=None):
+    """torque_tangent() marshalled once: returns (launch, out, squeeze), `launch()` being one qc_torque_tangent_batch call
+    (graph-capturable) on tensors that are read in place; `out` holds the [K, n, 4, 3] tensor and squeeze says whether the tangents
+    came as [n, ...].  out["joint_tau_tan"] may be a tensor of `tangents`.  Planning launches nothing."""
+    import torch
+
+    _library()
+    unknown = [k for k in tangents if k not in TORQUE_TANGENTS]
+    if unknown:
+        raise ValueError(f"torque_tangent: unknown tangent(s) {unknown}; the tangents are {tuple(TORQUE_TANGENTS)}")
+    io = QcTorqueTangentIo()
+    ctl._lib.qc_default_torque_tangent(C.byref(io))
+    sizing = [batch.get("joint_q"), grf_body, status] + [t for t in tangents.values() if t is not None and t.dim() == 2]
+    n, dev, bi = ctl._readonly_batch("torque_tangent", batch, _KINEMATICS_FIELDS, io, [("grf_body", grf_body, 12)], sizing,
+                                     "neither joint_q, grf_body nor status is there to size the call")
+    if _check_tensor("status", status, n, None, torch.int32, dev, False):
+        io.status = status.data_ptr()
+    given, K, squeeze = _directions(tangents, TORQUE_TANGENTS, n, dev, io)
+    io.n_dir = K
+    res = _outputs("torque_tangent", _TORQUE_TANGENT_OUTPUTS, ("joint_tau_tan",), out, K * n, dev, io)
+    res = {k: v.view((K, n) + _TORQUE_TANGENT_OUTPUTS[k][0]) for k, v in res.items()}
+    launch = ctl._launcher("qc_torque_tangent_batch", (n, C.byref(bi), C.byref(io), ctl._stream_ptr(stream)), (batch, grf_body, status, given, res, bi, io), ValueError)
+    return launch, res, squeeze
+
+
+def torque_tangent(ctl, batch, grf_body, status, tangents, out=None, stream=None):
+    """Forward mode of the clamped J^T torque map (qc_torque_tangent_batch, include/qc_tangent.h; INTEGRATION.md "Forward mode around
+    the tick"): joint_tau_tan = m o (J^T grf_tan + (sum_r g_r H_r) joint_q_tan), the map sensitivity_kinematics_batch() transposes.
+    `batch`: the one control_batch(want_torques=True) read - joint_q and the contact mask (stance, else the phase rule on gait_phase,
+    else all stance) are all that is read of it; `grf_body` [n,12] and `status` int32 [n] as the solve wrote them.  `tangents`: a dict
+    with "grf_tan" (what tangent_batch() wrote) and / or "joint_q_tan", each [n, ...] for one direction or [K, n, ...] for K, agreeing;
+    a missing one is zero, at least one given.  m is 1 where the forward torque passed through the clamp, 0 where it was clamped, for
+    swing legs and for robots with status != 0.  Returns dict(joint_tau_tan [K, n, 4, 3]), squeezed to [n, 4, 3] where the tangents
+    came that way; `out`: a dict with a tensor of K * n * 12 values to write into - it may be one of the tangents.  Nothing of
+    `batch` is written.  Asynchronous on `stream`, no synchronisation.  ValueError with the library's message for a call it refuses.
+    Not covered: the swing legs' PD torques (tangent 0), tangents of the kinematic constants and the torque limits."""
+    launch, res, squeeze = plan_torque_tangent(ctl, batch, grf_body, status, tangents, out, stream)
+    launch()
+    return {k: (v[0] if squeeze else v) for k, v in res.items()}
+
+
+def plan_leg_plant_step_tangent(ctl, state, joint_tau, dt, leg_inertia, tangents, stance=None, gait_phase=None, gait_duty=None, cmd_state=None,
+                                want=LEG_PLANT_TANGENT_WANT, out=None, stream=None):
+    """leg_plant_step_tangent() marshalled once: returns (launch, out, squeeze), `launch()` being one qc_leg_plant_step_tangent_batch
+    call (graph-capturable) on tensors that are read in place; `out` holds [K, n, ...] tensors (and "flags" int32 [n] where asked for)
+    and squeeze says whether the tangents came as [n, ...].  A tensor of `out` may be a tensor of `tangents` of the same layout (the
+    aliasing contract of include/qc_tangent.h).  Planning launches nothing."""
+    import torch
+
+    _library()
+    unknown = [k for k in tangents if k not in LEG_PLANT_TANGENTS]
+    if unknown:
+        raise ValueError(f"leg_plant_step_tangent: unknown tangent(s) {unknown}; the tangents are {tuple(LEG_PLANT_TANGENTS)}")
+    dev = torch.device("cuda", ctl.device)
+    n = state["x"].shape[0]
+    io = QcLegPlantTangentIo()
+    ctl._lib.qc_default_leg_plant_tangent(C.byref(io))
+    # (a missing state or torque array is the library's refusal, from launch())
+    arrays = [(k, state.get(k), m, torch.float64) for k, m in (("Rwb", 9), ("x", 3), ("xdot", 3), ("w", 3), ("joint_q", 12), ("joint_qdot", 12))]
+    arrays += [("joint_tau", joint_tau, 12, torch.float64), ("stance", stance, 4, torch.uint8), ("gait_phase", gait_phase, 4, torch.float64),
+               ("gait_duty", gait_duty, 1, torch.float64), ("cmd_state", cmd_state, COMMANDER_STATE_DTYPE.itemsize, torch.uint8)]
+    for name, t, k, dtype in arrays:
+        if _check_tensor(name, t, n, k, dtype, dev, False):
+            setattr(io, name, t.data_ptr() if n else None)
+    given, K, squeeze = _directions(tangents, LEG_PLANT_TANGENTS, n, dev, io)
+    io.n_dir = K
+    _fill(io.leg_inertia, np.broadcast_to(np.asarray(leg_inertia, dtype=np.float64), (3,)), 3, "leg_inertia")
+    io.dt = float(dt)
+    rows = tuple(w for w in want if w != "flags")
+    extra = [("flags", (n,), "int32")] if "flags" in want else []
+    res = _outputs("leg_plant_step_tangent", _LEG_PLANT_TANGENT_OUTPUTS, rows, out, K * n, dev, io, extra)
+    res = {k: (v if k == "flags" else v.view((K, n) + _LEG_PLANT_TANGENT_OUTPUTS[k][0])) for k, v in res.items()}
+    keep = (state, joint_tau, stance, gait_phase, gait_duty, cmd_state, given, res, io)
+    launch = ctl._launcher("qc_leg_plant_step_tangent_batch", (n, C.byref(io), ctl._stream_ptr(stream)), keep, ValueError)
+    return launch, res, squeeze
+
+
+def leg_plant_step_tangent(ctl, state, joint_tau, dt, leg_inertia, tangents, stance=None, gait_phase=None, gait_duty=None, cmd_state=None,
+                           want=LEG_PLANT_TANGENT_WANT, out=None, stream=None):
+    """Forward mode of ctl.leg_plant_step() (qc_leg_plant_step_tangent_batch, include/qc_tangent.h; INTEGRATION.md "Forward mode
+    around the tick").  `state`: the tensors Rwb [n,9], x, xdot, w [n,3], joint_q, joint_qdot [n,12] as they are BEFORE the step;
+    `joint_tau`, `dt`, `leg_inertia` and the contact inputs `stance` / `gait_phase` / `gait_duty` / `cmd_state` as the step reads them.
+    `tangents`: a dict with any of "Rwb_rot_tan" (the world-frame left tangent, Rwb <- exp([d]x) Rwb), "x_tan", "xdot_tan", "w_tan"
+    ([n,3]), "joint_q_tan", "joint_qdot_tan" and "joint_tau_tan" ([n,12] or [n,4,3]; the last is what torque_tangent() wrote) - each
+    [n, ...] for one direction or [K, n, ...] for K, all agreeing on K; a missing one is zero, at least one given.  `want`: any of
+    "Rwb_rot_next_tan", "x_next_tan", "xdot_next_tan", "w_next_tan" [K,n,3], "joint_q_next_tan", "joint_qdot_next_tan" [K,n,4,3] and
+    "flags" int32 [n] (bit l: J(q_l) of stance leg l singular, bit 4 + l: leg l out of reach or J singular after the step); a robot
+    with any bit set has NaN in every output row of every direction.  The step is recomputed from `state`; nothing of it is written.
+    `out`: a dict of tensors with K * n rows to write into - each may be the input tangent of its layout, joint_qdot_next_tan also
+    joint_tau_tan.  Asynchronous on `stream`, no synchronisation.  Returns the dict of device tensors, squeezed to [n, ...] where the
+    tangents came that way.  ValueError with the library's message for a call it refuses.  Not covered: tangents of mass, Ib,
+    leg_inertia, dt and the kinematic constants; the contact mask is held."""
+    launch, res, squeeze = plan_leg_plant_step_tangent(ctl, state, joint_tau, dt, leg_inertia, tangents, stance, gait_phase, gait_duty, cmd_state,
+                                                       want, out, stream)
+    launch()
+    return {k: (v[0] if squeeze and k != "flags" else v) for k, v in res.items()}
+
+
+def rollout_tick_tangent(ctl, batch, steps, dt, leg_inertia, tangents, act_tol=1e-7, warm=True, stream=None, command=None, lean=None):
+    """The forward-mode twin of ctl.rollout_tick(batch, None, ...): `steps` times control_batch(want_torques=True), tangent_batch()
+    (the state's tangents and joint_q_tan), torque_tangent(), leg_plant_step_tangent() (it reads the state before the step) and
+    leg_plant_step(), everything planned once, on one stream and without a host round trip.  `batch` is advanced IN PLACE and ends
+    bit for bit where ctl.rollout_tick() leaves it.  `tangents`: any of the start state's "Rwb_rot_tan", "x_tan", "xdot_tan", "w_tan"
+    [n,3], "joint_q_tan", "joint_qdot_tan" [n,12] and - held, applied at every step - the desired state's "x_d_tan", "xdot_d_tan",
+    "w_d_tan", "Rwb_d_rot_tan"; each [n, ...] or [K, n, ...], all agreeing; none is written.  A `stance` / `gait_phase` / `gait_duty`
+    contact mask is HELD over the rollout, as in rollout_tick_autograd().  Returns (state, res): `state` the six tensors of `batch`,
+    `res` the final six tangents under their input names, the last "grf_tan" and "joint_tau_tan" ([K, n, ...], squeezed where the
+    tangents came as [n, ...]) and "flags" int32 [n], OR-ed over the steps on the device: bits 0-1 are tangent_batch()'s (bit 0: a
+    one-sided face, bit 1: a bad pivot), bits 8-15 the plant's shifted left by 8 (bit 8 + l: J(q_l) singular, bit 12 + l: leg l out
+    of reach or J singular after the step).  The derivative is the one on the active face of every solve at `act_tol`, at every
+    tick's torque clamp mask and off the plant's flagged legs, as rollout_tick_autograd()'s.  Tangent memory is one set of buffers
+    whatever `steps` is.  ValueError for swing references (swing_state, swing_pos, swing_vel), gait_dt, `lean` and a `command`: the
+    swing pipeline, the gait clock and commander mode have no forward mode."""
+    import contextlib
+
+    import torch
+
+    who = "rollout_tick_tangent"
+    if command is not None:
+        raise ValueError(f"{who}: commander mode has no forward mode - command must be None (the desired state is held in the batch)")
+    if lean is not None:
+        raise ValueError(f"{who}: lean has no forward mode - lean must be None")
+    for name, why in (("swing_state", "the swing planner"), ("swing_pos", "the swing legs' PD torques"), ("swing_vel", "the swing legs' PD torques"),
+                      ("gait_dt", "the gait clock (the contact mask is held)")):
+        if batch.get(name) is not None:
+            raise ValueError(f"{who}: batch['{name}'] must be None - {why} has no forward mode")
+    if batch.get("joint_q") is None or batch.get("joint_qdot") is None:
+        raise ValueError(f"{who}: the batch carries joint_q and joint_qdot (rollout_tangent() steps the bare rigid body)")
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError(f"{who}: steps must be >= 0")
+    unknown = [k for k in tangents if k not in ROLLOUT_TICK_TANGENTS]
+    if unknown:
+        raise ValueError(f"{who}: unknown tangent(s) {unknown}; the tangents are {tuple(ROLLOUT_TICK_TANGENTS)}")
+    n = batch["x"].shape[0]
+    dev = torch.device("cuda", ctl.device)
+    given, K, squeeze = _directions(tangents, ROLLOUT_TICK_TANGENTS, n, dev)
+    if not given:
+        raise ValueError(f"{who}: no tangent given")
+    shape = lambda m: (K, n) + ((4, 3) if m == 12 else (3,))
+    on_stream = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+    with on_stream:
+        # one set of buffers: the state's tangents are advanced in place, grf_tan and joint_tau_tan are rewritten by every step
+        buf = {k: (given[k].reshape(shape(ROLLOUT_TICK_TANGENTS[k])).clone() if k in given else
+                   torch.zeros(shape(ROLLOUT_TICK_TANGENTS[k]), dtype=torch.float64, device=dev)) for k in _TICK_STATE}
+        grf_tan, tau_tan = (torch.zeros((K, n, 4, 3), dtype=torch.float64, device=dev) for _ in range(2))
+        flags, solve_flags, plant_flags = (torch.zeros((n,), dtype=torch.int32, device=dev) for _ in range(3))
+    held = {k: given[k].reshape(K, n, 3) for k in _ROLLOUT_HELD if k in given}
+    names = ("Rwb", "x", "xdot", "w", "joint_q", "joint_qdot")
+    state = {k: batch[k] for k in names}
+    tick_in = {k: v for k, v in batch.items() if k != "joint_qdot"}  # as rollout_tick(): a tick without swing references takes no joint_qdot
+    contact = {k: batch.get(k) for k in ("stance", "gait_phase", "gait_duty")}
+    r = _RolloutPlans(ctl, who, batch, n, warm, lambda first, w, o: ctl.plan_batch(tick_in, w, o, want_active_set=warm, want_torques=True, stream=stream)[0],
+                      None, stream, torques=True)
+    if steps > 0 and n > 0:
+        solve_in = {k: buf[k] for k in ("Rwb_rot_tan", "x_tan", "xdot_tan", "w_tan", "joint_q_tan")}
+        solve_tan, _, _ = plan_tangent(ctl, tick_in, r.out["grf_body"], dict(solve_in, **held), ("grf_tan", "flags"), act_tol,
+                                       {"grf_tan": grf_tan, "flags": solve_flags}, stream)
+        torque_tan, _, _ = plan_torque_tangent(ctl, tick_in, r.out["grf_body"], r.out["status"], {"grf_tan": grf_tan, "joint_q_tan": buf["joint_q_tan"]},
+                                               {"joint_tau_tan": tau_tan}, stream)
+        plant_out = {k[:-4] + "_next_tan": buf[k] for k in _TICK_STATE}
+        plant_out["flags"] = plant_flags
+        step_tan, _, _ = plan_leg_plant_step_tangent(ctl, state, r.out["joint_tau"], dt, leg_inertia, dict(buf, joint_tau_tan=tau_tan), want=tuple(plant_out),
+                                                     out=plant_out, stream=stream, **contact)
+        step = ctl.plan_leg_plant(state, r.out["joint_tau"], dt, leg_inertia, stream=stream, **contact)
+        for k in range(steps):
+            r.solve(k)
+            solve_tan()
+            torque_tan()
+            step_tan()
+            with on_stream:
+                flags.bitwise_or_(solve_flags.bitwise_or(plant_flags.bitwise_left_shift(TICK_PLANT_FLAGS_SHIFT)))
+            step()
+    res = dict(buf, grf_tan=grf_tan, joint_tau_tan=tau_tan)
+    res = {k: (v[0] if squeeze else v) for k, v in res.items()}
+    res["flags"] = flags
+    return state, res
+
+
+def tick_transition_seeds(n, dev, columns=TICK_TRANSITION_COLUMNS):
+    """rollout_tick_tangent()'s `tangents` for unit seeds on the start state: direction j moves coordinate columns[j] - (name, component)
+    with name in "Rwb_rot", "x", "xdot", "w" (3 components) or "joint_q", "joint_qdot" (12) - by one.  [K, n, m] device tensors; only
+    the coordinates that are seeded are returned."""
+    import torch
+
+    seeds = {}
+    for j, (name, comp) in enumerate(columns):
+        key = name + "_tan"
+        if key not in _TICK_STATE:
+            raise ValueError(f"rollout_tick_transition: unknown coordinate {name!r}; the coordinates are {tuple(k[:-4] for k in _TICK_STATE)}")
+        if key not in seeds:
+            seeds[key] = torch.zeros((len(columns), n, ROLLOUT_TICK_TANGENTS[key]), dtype=torch.float64, device=dev)
+        seeds[key][j, :, comp] = 1.0
+    return seeds
+
+
+def rollout_tick_transition(ctl, batch, steps, dt, leg_inertia, act_tol=1e-7, warm=True, chunk=None, stream=None):
+    """The 36 x 36 state-transition matrix of `steps` closed-loop steps around the tick in minimal coordinates - the rotation tangent,
+    x, xdot, w (3 each), joint_q[12], joint_qdot[12], in this order -: rollout_tick_tangent() on the 36 unit seeds of the start state
+    (tick_transition_seeds), `chunk` seeds per rollout (None: all in one; the start state is restored between the chunks).  `batch` is
+    advanced in place, as by ctl.rollout_tick().  Returns dict(phi [n,36,36] - phi[:, r, c] = d (coordinate r after the steps) / d
+    (coordinate c at the start), rows and columns in the order of `columns` -, columns: the list of (name, component), flags int32
+    [n]: rollout_tick_tangent()'s, OR-ed over the chunks).  Column c equals rollout_tick_tangent() on seed c bit for bit, however the
+    columns are chunked; steps = 0 gives the identity.  A stance leg's joint_qdot is not read by the step: those columns are 0."""
+    import contextlib
+
+    import torch
+
+    cols = list(TICK_TRANSITION_COLUMNS)
+    n, dev = batch["x"].shape[0], batch["x"].device
+    size = len(cols) if chunk is None else int(chunk)
+    if size < 1:
+        raise ValueError("rollout_tick_transition: chunk must be >= 1")
+    on_stream = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+    moved = ("Rwb", "x", "xdot", "w", "joint_q", "joint_qdot")
+    with on_stream:
+        phi = torch.empty((n, len(cols), len(cols)), dtype=torch.float64, device=dev)
+        flags = torch.zeros((n,), dtype=torch.int32, device=dev)
+        start = {k: batch[k].clone() for k in moved} if size < len(cols) else None
+    for c0 in range(0, len(cols), size):
+        part = cols[c0:c0 + size]
+        with on_stream:
+            if c0 > 0:
+                for k in moved:
+                    batch[k].copy_(start[k])
+            seeds = tick_transition_seeds(n, dev, part)
+        _, res = rollout_tick_tangent(ctl, batch, steps, dt, leg_inertia, seeds, act_tol, warm, stream)
+        with on_stream:
+            rows = torch.cat([res[k].reshape(len(part), n, -1) for k in _TICK_STATE], dim=-1)  # [len(part), n, 36]
             phi[:, :, c0:c0 + len(part)] = rows.permute(1, 2, 0)
             flags.bitwise_or_(res["flags"])
     return dict(phi=phi, columns=cols, flags=flags)
