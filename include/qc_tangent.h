@@ -37,7 +37,8 @@
  *
  * The rigid-body plant step has its forward mode below, qc_plant_step_tangent_batch: with it the two calls chain, step after step,
  * into the tangent of a closed-loop rollout.  The loop around the complete tick - joint_q -> FK -> QP -> clamped J^T -> joint_tau ->
- * legged plant - chains four calls: qc_tangent_batch (joint_q_tan), qc_torque_tangent_batch, qc_leg_plant_step_tangent_batch, all below. */
+ * legged plant - chains qc_tangent_batch (joint_q_tan), qc_torque_tangent_batch, for a batch with swing references
+ * qc_swing_torque_tangent_batch in place behind it, and qc_leg_plant_step_tangent_batch, all below. */
 #ifndef QC_TANGENT_H
 #define QC_TANGENT_H
 
@@ -126,8 +127,10 @@ int qc_plant_step_tangent_batch(qc_handle* h, size_t n, const qc_plant_tangent_i
  * joint_tau_tan may BE grf_tan or joint_q_tan: a (direction, robot, leg) reads all its inputs before it writes and touches only its
  * own row.  Non-finite inputs propagate as NaN where m = 1; nothing is clamped.
  *
- * OUT OF SCOPE: with swing references the swing legs' PD torque gets tangent 0; there are no tangents of the kinematic constants or
- * of tau_min / tau_max. */
+ * A swing leg's row is exactly 0: with swing references, qc_swing_torque_tangent_batch (below) called on the same buffer afterwards
+ * fills those rows, and joint_tau_tan is the tangent of the tick's complete joint_tau.
+ *
+ * OUT OF SCOPE: tangents of the kinematic constants and of tau_min / tau_max. */
 typedef struct qc_torque_tangent_io {
   size_t struct_size;            /* = sizeof(qc_torque_tangent_io); checked                                           */
   const double* grf_body;        /* [n][4][3] qc_batch_out.grf_body                                                   */
@@ -145,6 +148,53 @@ void qc_default_torque_tangent(qc_torque_tangent_io* io);
  * struct_size, n_dir == 0, no output (joint_tau_tan NULL), no tangent given at all, a missing grf_body or status, a missing
  * in->joint_q, or 4 * n * n_dir beyond one launch. */
 int qc_torque_tangent_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_torque_tangent_io* io, void* stream);
+
+/* qc_swing_torque_tangent_batch - forward mode of the swing legs' PD torques, the map qc_sensitivity_swing_batch transposes: K
+ * tangents per launch, chained IN PLACE behind qc_torque_tangent_batch.  Of `in` it reads exactly what qc_sensitivity_swing_batch
+ * reads - Rwb, x, joint_q, joint_qdot, swing_pos, swing_vel and the contact inputs resolved by that call's rule (in->stance, else the
+ * phase rule on in->gait_phase with in->gait_duty or the handle's duty, else all stance) -; nothing of `in` is written.  Per
+ * direction, robot and SWING leg, in the notation of qc_sensitivity_swing_batch (p_b = Rwb^T pos - x (sic), v_b = Rwb^T vel,
+ * q_ref = IK(p_b), qd = J(q_ref)^-1 v_b, H_r = d^2 FK_r / dq^2 at q_ref), delta the world-frame left tangent of Rwb:
+ *   dp_b   = Rwb^T (dpos - delta x pos) - dx
+ *   dv_b   = Rwb^T (dvel - delta x vel)
+ *   dq_ref = J(q_ref)^-1 dp_b                      (inside reach the IK inverts the FK)
+ *   dqd    = J(q_ref)^-1 (dv_b - B),  B_r = dq_ref^T H_r qd
+ *   dtau   = m o ( kp o (dq_ref - dq) + kd o (dqd - dqdot) ) + joint_tau_tan_in
+ * m is qc_sensitivity_swing_batch's mask: tau_raw from the forward pass's own function on the same inputs, m_c = 1 where
+ * !(tau_raw_c < tau_min) && !(tau_raw_c > tau_max) - the forward tick's mask bit for bit.  The wraps have slope 1; the QP's status
+ * plays no part, as in the tick.  A STANCE leg's row is joint_tau_tan_in, or 0 where that is NULL.  qc_torque_tangent_batch writes
+ * exact zeros in swing rows, so the two calls in that order on one buffer (joint_tau_tan = joint_tau_tan_in) give the tangent of the
+ * tick's complete joint_tau.
+ *
+ * `flags` follows the adjoint's rules: bit l, swing leg l's reference is out of reach, inside the inner limit, not finite, or at a
+ * det J(q_ref) outside the closed-form band.  A flagged leg's row is NaN in every direction, whatever the mask and joint_tau_tan_in;
+ * the other legs of that robot are unaffected.  Other non-finite inputs propagate as NaN; nothing else is clamped.
+ *
+ * <joint_tau_bar, dtau - joint_tau_tan_in> equals <swing_pos_bar, dpos> + <swing_vel_bar, dvel> + <joint_q_bar, dq> +
+ * <joint_qdot_bar, dqdot> + <x_bar, dx> + <Rwb_bar, [delta]x Rwb> with the cotangents of qc_sensitivity_swing_batch.
+ *
+ * joint_tau_tan may BE joint_tau_tan_in or any other [K][n][4][3] input tangent: a (direction, robot, leg) row reads all it needs
+ * before it writes and touches only its own row.  All pointers are device pointers.
+ *
+ * OUT OF SCOPE: tangents of the gains, of tau_min / tau_max and of the kinematic constants; the planner and the gait clock
+ * (qc_swing_reference_batch has no forward mode: swing_state and gait_dt are refused); commander mode. */
+typedef struct qc_swing_tangent_io {
+  size_t struct_size;            /* = sizeof(qc_swing_tangent_io); checked                                            */
+  size_t n_dir;                  /* K >= 1 directions per launch                                                      */
+  /* tangents, direction-major as in qc_tangent_io; NULL = zero, at least one given                                   */
+  const double *Rwb_rot_tan, *x_tan;   /* [K][n][3]; Rwb_rot_tan: the world-frame left tangent, Rwb <- exp([d]x) Rwb  */
+  const double *swing_pos_tan, *swing_vel_tan, *joint_q_tan, *joint_qdot_tan;  /* [K][n][4][3]                        */
+  const double *joint_tau_tan_in;      /* [K][n][4][3] added: what qc_torque_tangent_batch wrote                      */
+  double* joint_tau_tan;         /* [K][n][4][3] required unless flags is given                                       */
+  int32_t* flags;                /* [n] optional: bit l, swing leg l has no derivative                                */
+} qc_swing_tangent_io;
+/* struct_size set, pointers NULL, n_dir = 1. */
+void qc_default_swing_tangent(qc_swing_tangent_io* io);
+/* Asynchronous on `stream`, no host synchronisation (graph-capturable); n == 0 launches nothing and returns QC_OK.
+ * QC_ERR_INVALID (message starting with "qc_swing_torque_tangent_batch:", nothing launched) for a null handle, `in` or `io`, a wrong
+ * struct_size, n_dir == 0, no tangent given at all, no output (joint_tau_tan and flags both NULL), in->swing_state or in->gait_dt, a
+ * missing Rwb, x, joint_q, joint_qdot, swing_pos or swing_vel, or 4 * n * n_dir beyond one launch. */
+int qc_swing_torque_tangent_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_swing_tangent_io* io, void* stream);
 
 /* qc_leg_plant_step_tangent_batch - forward mode of qc_leg_plant_step_batch: K tangents on the inputs of one step of the legged plant
  * pushed through it, in one launch.  Given the state BEFORE the step (Rwb, x, xdot, w, joint_q, joint_qdot), the torques, the contact

@@ -2368,6 +2368,19 @@ int qc_torque_tangent_batch(qc_handle* h, size_t n, const qc_batch_in* in, const
                      qc::torque_tangent_constants(in, io));
 }
 
+void qc_default_swing_tangent(qc_swing_tangent_io* io) {
+  if (!zeroed(io)) return;
+  io->n_dir = 1;
+}
+
+int qc_swing_torque_tangent_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_swing_tangent_io* io, void* stream) {
+  if (const int rc = qc::check_swing_tangent_args(h, n, in, io); rc != QC_OK || n == 0) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  // (of `in`: the six arrays of the swing chain and the contact mask as it is now - nothing that advances or plans)
+  return launch_flat(qc::swing_tangent_kernel, qc::swing_tangent_blocks(n, qc::swing_tangent_dirs(io)), qc::SWING_TANGENT_BLOCK, stream, h->d_params,
+                     (long)(4 * n), qc::swing_tangent_constants(in, io));
+}
+
 void qc_default_leg_plant_tangent(qc_leg_plant_tangent_io* io) {
   if (!zeroed(io)) return;  // (leg_inertia 0, as qc_default_leg_plant leaves it)
   io->dt = 1.0 / 300.0;  // qc_default_leg_plant's

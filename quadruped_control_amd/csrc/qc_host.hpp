@@ -26,6 +26,7 @@
 #include "qc_com_reference.hpp"
 #include "qc_tangent.hpp"
 #include "qc_plant_tangent.hpp"
+#include "qc_swing_tangent.hpp"
 #include "qc_torque_tangent.hpp"
 #include "qc_leg_plant_tangent.hpp"
 
@@ -969,6 +970,41 @@ inline TorqueTangentArgs torque_tangent_constants(const qc_batch_in* in, const q
 
 // workgroups of torque_tangent_kernel for n robots and K directions: one wave of rows each, capped (a grid cap of its own)
 inline unsigned torque_tangent_blocks(size_t n, size_t n_dir) { return capped_blocks(4 * n * n_dir, TORQUE_TANGENT_BLOCK, TORQUE_TANGENT_MAX_BLOCKS); }
+
+// ---------------------------------------------------------------- qc_swing_torque_tangent_batch
+// What is wrong with the call itself (message prefix "qc_swing_torque_tangent_batch:").  The kernel reads the six arrays of `in` that
+// qc_sensitivity_swing_batch reads and the contact mask as it is now; what would plan or advance (swing_state, gait_dt) is refused.
+// One lane per (direction, robot, leg): the rows must fit a launch.
+inline int check_swing_tangent_args(const qc_handle* h, size_t n, const qc_batch_in* in, const qc_swing_tangent_io* io) {
+  const char* who = "qc_swing_torque_tangent_batch";
+  if (const int rc = check_io(who, h && in, io, "qc_swing_tangent_io", "qc_default_swing_tangent"); rc != QC_OK) return rc;
+  const auto bad = [who](const char* what) { return fail(QC_ERR_INVALID, std::string(who) + what); };
+  if (io->n_dir == 0) return bad(": n_dir must be >= 1");
+  if (!io->Rwb_rot_tan && !io->x_tan && !io->swing_pos_tan && !io->swing_vel_tan && !io->joint_q_tan && !io->joint_qdot_tan && !io->joint_tau_tan_in)
+    return bad(": no tangent given (Rwb_rot_tan, x_tan, swing_pos_tan, swing_vel_tan, joint_q_tan, joint_qdot_tan, joint_tau_tan_in are all NULL)");
+  if (!io->joint_tau_tan && !io->flags) return bad(": no output requested (joint_tau_tan and flags are both NULL)");
+  if (in->swing_state) return bad(": swing_state must be NULL (the planner's references have no forward mode: give swing_pos and swing_vel)");
+  if (in->gait_dt) return bad(": gait_dt must be NULL (the gait clock has no forward mode: the contact mask is read as it is now)");
+  if (n == 0) return QC_OK;
+  if (!in->Rwb || !in->x || !in->joint_q || !in->joint_qdot || !in->swing_pos || !in->swing_vel)
+    return bad(": Rwb, x, joint_q, joint_qdot, swing_pos and swing_vel are required");
+  if (n > (size_t)0xFFFFFF * (size_t)SWING_TANGENT_BLOCK / 4 || io->n_dir > (size_t)0xFFFFFF * (size_t)SWING_TANGENT_BLOCK / (4 * n))
+    return bad(": 4 * n * n_dir is beyond one launch");
+  return QC_OK;
+}
+
+// the directions the kernel walks: the flags come from the forward chain alone, so a call without joint_tau_tan walks one
+inline size_t swing_tangent_dirs(const qc_swing_tangent_io* io) { return io->joint_tau_tan ? io->n_dir : 1; }
+
+// the kernel's arguments: the six arrays and the contact inputs of `in`, the record's arrays
+inline SwingTangentArgs swing_tangent_constants(const qc_batch_in* in, const qc_swing_tangent_io* io) {
+  return SwingTangentArgs{in->Rwb, in->x, in->joint_q, in->joint_qdot, in->swing_pos, in->swing_vel, in->stance, in->gait_phase, in->gait_duty,
+                          (long)swing_tangent_dirs(io), io->Rwb_rot_tan, io->x_tan, io->swing_pos_tan, io->swing_vel_tan, io->joint_q_tan, io->joint_qdot_tan,
+                          io->joint_tau_tan_in, io->joint_tau_tan, io->flags};
+}
+
+// workgroups of swing_tangent_kernel for n robots and K directions: one wave of rows each, capped (a grid cap of its own)
+inline unsigned swing_tangent_blocks(size_t n, size_t n_dir) { return capped_blocks(4 * n * n_dir, SWING_TANGENT_BLOCK, SWING_TANGENT_MAX_BLOCKS); }
 
 // ---------------------------------------------------------------- qc_leg_plant_step_tangent_batch
 // What is wrong with the call itself (message prefix "qc_leg_plant_step_tangent_batch:"); the handle's mass and Ib are judged by

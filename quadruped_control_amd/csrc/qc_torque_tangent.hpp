@@ -6,7 +6,8 @@
 // m_c = 1 where !(tau_raw_c < tau_min) && !(tau_raw_c > tau_max) - equality passes, a NaN passes and propagates -, m = 0 for a swing
 // leg and for a robot with status != 0: exactly that kernel's mask, the contact mask resolved by its rule (stance bytes, else the
 // phase rule, else all stance).  A masked entry is exactly 0 whatever the tangents hold.
-// OUT OF SCOPE: the swing legs' PD torques (tangent 0), tangents of the kinematic constants and of tau_min / tau_max.
+// A swing leg's row is exactly 0: its PD torque has its own kernel (qc_swing_tangent.hpp), chained in place behind this one.
+// OUT OF SCOPE: tangents of the kinematic constants and of tau_min / tau_max.
 //
 // Kernel: one lane per (direction, robot, leg) ROW, the (robot, leg) row fastest - row j = k 4n + r is row j of a [K][n][4][3]
 // array -, as qc_sensitivity_kin.hpp is one lane per (robot, leg): a wave's loads of one direction are contiguous, and K multiplies

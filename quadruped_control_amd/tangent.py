@@ -10,10 +10,14 @@ the clamped J^T torque map, and leg_plant_step_tangent() (qc_leg_plant_step_tang
 plant; rollout_tick_tangent() chains them with tangent_batch() into the forward-mode twin of ctl.rollout_tick(batch, None, ...), and
 rollout_tick_transition() is its 36 x 36 state-transition matrix.
 
+A trot has its forward mode as well: swing_torque_tangent() (qc_swing_torque_tangent_batch, csrc/qc_swing_tangent.hpp), the swing legs'
+PD torques on references that are given, chained in place behind torque_tangent(); rollout_swing_tangent() is the forward-mode twin of
+ctl.rollout_tick(batch, None, ...) for a batch with swing_pos and swing_vel, rollout_swing_transition() its 36 x 36 matrix.
+
 The functions take the controller as their first argument, as autograd.py's do.  The symbols of the library are bound here, on
 the CDLL that _lib.load() returns, with this module's own ctypes records: _lib.EXPORTS and BalanceController are not touched.
 
-Not covered: the swing pipeline (swing references, the planner, the gait clock), commander mode, tangents of the handle's parameters,
+Not covered: the swing planner and the gait clock (swing_state, gait_dt), commander mode, tangents of the handle's parameters,
 and a jvp on the torch.autograd.Functions of autograd.py."""
 from __future__ import annotations
 
@@ -55,6 +59,19 @@ TICK_TRANSITION_COLUMNS = tuple((name, c) for name in ("Rwb_rot", "x", "xdot", "
     tuple((name, c) for name in ("joint_q", "joint_qdot") for c in range(12))
 TICK_PLANT_FLAGS_SHIFT = 8  # rollout_tick_tangent()'s flags: tangent_batch()'s bits | the plant's bits << 8
 
+# the swing legs' PD torques (qc_swing_tangent_io): the record's tangents in its order, and rollout_swing_tangent()'s - the tick's
+# and the two held references'
+SWING_TORQUE_TANGENTS = {"Rwb_rot_tan": 3, "x_tan": 3, "swing_pos_tan": 12, "swing_vel_tan": 12, "joint_q_tan": 12, "joint_qdot_tan": 12,
+                         "joint_tau_tan_in": 12}
+_SWING_TORQUE_TANGENT_OUTPUTS = {"joint_tau_tan": ((4, 3), "float64")}
+_SWING_HELD = ("swing_pos_tan", "swing_vel_tan")
+ROLLOUT_SWING_TANGENTS = {**ROLLOUT_TICK_TANGENTS, **{k: 12 for k in _SWING_HELD}}
+SWING_FLAGS_SHIFT = 16  # rollout_swing_tangent()'s flags: rollout_tick_tangent()'s word | swing_torque_tangent()'s bits << 16
+
+
+class QcSwingTangentIo(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("n_dir", C.c_size_t)] + [(k, C.c_void_p) for k in tuple(SWING_TORQUE_TANGENTS) + ("joint_tau_tan", "flags")]
+
 
 class QcTorqueTangentIo(C.Structure):
     _fields_ = [("struct_size", C.c_size_t), ("grf_body", C.c_void_p), ("status", C.c_void_p), ("n_dir", C.c_size_t)] + \
@@ -87,7 +104,8 @@ def _library():
     if _bound is None:
         lib = _lib.load()
         for name in ("qc_default_tangent", "qc_tangent_batch", "qc_default_plant_tangent", "qc_plant_step_tangent_batch", "qc_default_torque_tangent",
-                     "qc_torque_tangent_batch", "qc_default_leg_plant_tangent", "qc_leg_plant_step_tangent_batch"):
+                     "qc_torque_tangent_batch", "qc_default_leg_plant_tangent", "qc_leg_plant_step_tangent_batch", "qc_default_swing_tangent",
+                     "qc_swing_torque_tangent_batch"):
             if not hasattr(lib, name):
                 raise ImportError(f"{_lib.LIB_PATH} does not export {name}")
         lib.qc_default_tangent.argtypes = [C.POINTER(QcTangentIo)]
@@ -106,6 +124,10 @@ def _library():
         lib.qc_default_leg_plant_tangent.restype = None
         lib.qc_leg_plant_step_tangent_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(QcLegPlantTangentIo), C.c_void_p]
         lib.qc_leg_plant_step_tangent_batch.restype = C.c_int
+        lib.qc_default_swing_tangent.argtypes = [C.POINTER(QcSwingTangentIo)]
+        lib.qc_default_swing_tangent.restype = None
+        lib.qc_swing_torque_tangent_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(_lib.QcBatchIn), C.POINTER(QcSwingTangentIo), C.c_void_p]
+        lib.qc_swing_torque_tangent_batch.restype = C.c_int
         _bound = lib
     return _bound
 
@@ -490,10 +512,6 @@ def rollout_tick_tangent(ctl, batch, steps, dt, leg_inertia, tangents, act_tol=1
     tick's torque clamp mask and off the plant's flagged legs, as rollout_tick_autograd()'s.  Tangent memory is one set of buffers
     whatever `steps` is.  ValueError for swing references (swing_state, swing_pos, swing_vel), gait_dt, `lean` and a `command`: the
     swing pipeline, the gait clock and commander mode have no forward mode."""
-    import contextlib
-
-    import torch
-
     who = "rollout_tick_tangent"
     if command is not None:
         raise ValueError(f"{who}: commander mode has no forward mode - command must be None (the desired state is held in the batch)")
@@ -505,15 +523,27 @@ def rollout_tick_tangent(ctl, batch, steps, dt, leg_inertia, tangents, act_tol=1
             raise ValueError(f"{who}: batch['{name}'] must be None - {why} has no forward mode")
     if batch.get("joint_q") is None or batch.get("joint_qdot") is None:
         raise ValueError(f"{who}: the batch carries joint_q and joint_qdot (rollout_tangent() steps the bare rigid body)")
+    return _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, ROLLOUT_TICK_TANGENTS, act_tol, warm, stream, False)
+
+
+def _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, table, act_tol, warm, stream, swings):
+    """What rollout_tick_tangent() and rollout_swing_tangent() share, behind their own refusals: the tangents validated against `table`,
+    one set of buffers, every launch planned once, the step loop.  swings=False launches exactly what rollout_tick_tangent() always
+    did; swings=True hands the whole batch to the tick (joint_qdot and the two references with it, as ctl.rollout_tick() does) and
+    adds swing_torque_tangent() in place on joint_tau_tan behind torque_tangent(), its flags at SWING_FLAGS_SHIFT."""
+    import contextlib
+
+    import torch
+
     steps = int(steps)
     if steps < 0:
         raise ValueError(f"{who}: steps must be >= 0")
-    unknown = [k for k in tangents if k not in ROLLOUT_TICK_TANGENTS]
+    unknown = [k for k in tangents if k not in table]
     if unknown:
-        raise ValueError(f"{who}: unknown tangent(s) {unknown}; the tangents are {tuple(ROLLOUT_TICK_TANGENTS)}")
+        raise ValueError(f"{who}: unknown tangent(s) {unknown}; the tangents are {tuple(table)}")
     n = batch["x"].shape[0]
     dev = torch.device("cuda", ctl.device)
-    given, K, squeeze = _directions(tangents, ROLLOUT_TICK_TANGENTS, n, dev)
+    given, K, squeeze = _directions(tangents, table, n, dev)
     if not given:
         raise ValueError(f"{who}: no tangent given")
     shape = lambda m: (K, n) + ((4, 3) if m == 12 else (3,))
@@ -524,10 +554,12 @@ def rollout_tick_tangent(ctl, batch, steps, dt, leg_inertia, tangents, act_tol=1
                    torch.zeros(shape(ROLLOUT_TICK_TANGENTS[k]), dtype=torch.float64, device=dev)) for k in _TICK_STATE}
         grf_tan, tau_tan = (torch.zeros((K, n, 4, 3), dtype=torch.float64, device=dev) for _ in range(2))
         flags, solve_flags, plant_flags = (torch.zeros((n,), dtype=torch.int32, device=dev) for _ in range(3))
+        swing_flags = torch.zeros((n,), dtype=torch.int32, device=dev) if swings else None
     held = {k: given[k].reshape(K, n, 3) for k in _ROLLOUT_HELD if k in given}
     names = ("Rwb", "x", "xdot", "w", "joint_q", "joint_qdot")
     state = {k: batch[k] for k in names}
-    tick_in = {k: v for k, v in batch.items() if k != "joint_qdot"}  # as rollout_tick(): a tick without swing references takes no joint_qdot
+    # as rollout_tick(): a tick without swing references takes no joint_qdot
+    tick_in = batch if swings else {k: v for k, v in batch.items() if k != "joint_qdot"}
     contact = {k: batch.get(k) for k in ("stance", "gait_phase", "gait_duty")}
     r = _RolloutPlans(ctl, who, batch, n, warm, lambda first, w, o: ctl.plan_batch(tick_in, w, o, want_active_set=warm, want_torques=True, stream=stream)[0],
                       None, stream, torques=True)
@@ -537,6 +569,11 @@ def rollout_tick_tangent(ctl, batch, steps, dt, leg_inertia, tangents, act_tol=1
                                        {"grf_tan": grf_tan, "flags": solve_flags}, stream)
         torque_tan, _, _ = plan_torque_tangent(ctl, tick_in, r.out["grf_body"], r.out["status"], {"grf_tan": grf_tan, "joint_q_tan": buf["joint_q_tan"]},
                                                {"joint_tau_tan": tau_tan}, stream)
+        swing_tan = None
+        if swings:
+            swing_in = {k: buf[k] for k in ("Rwb_rot_tan", "x_tan", "joint_q_tan", "joint_qdot_tan")}
+            swing_in.update({k: given[k].reshape(K, n, 4, 3) for k in _SWING_HELD if k in given}, joint_tau_tan_in=tau_tan)
+            swing_tan, _, _ = plan_swing_torque_tangent(ctl, tick_in, swing_in, ("joint_tau_tan", "flags"), {"joint_tau_tan": tau_tan, "flags": swing_flags}, stream)
         plant_out = {k[:-4] + "_next_tan": buf[k] for k in _TICK_STATE}
         plant_out["flags"] = plant_flags
         step_tan, _, _ = plan_leg_plant_step_tangent(ctl, state, r.out["joint_tau"], dt, leg_inertia, dict(buf, joint_tau_tan=tau_tan), want=tuple(plant_out),
@@ -546,9 +583,13 @@ def rollout_tick_tangent(ctl, batch, steps, dt, leg_inertia, tangents, act_tol=1
             r.solve(k)
             solve_tan()
             torque_tan()
+            if swing_tan is not None:
+                swing_tan()
             step_tan()
             with on_stream:
                 flags.bitwise_or_(solve_flags.bitwise_or(plant_flags.bitwise_left_shift(TICK_PLANT_FLAGS_SHIFT)))
+                if swing_flags is not None:
+                    flags.bitwise_or_(swing_flags.bitwise_left_shift(SWING_FLAGS_SHIFT))
             step()
     res = dict(buf, grf_tan=grf_tan, joint_tau_tan=tau_tan)
     res = {k: (v[0] if squeeze else v) for k, v in res.items()}
@@ -581,6 +622,11 @@ def rollout_tick_transition(ctl, batch, steps, dt, leg_inertia, act_tol=1e-7, wa
     (coordinate c at the start), rows and columns in the order of `columns` -, columns: the list of (name, component), flags int32
     [n]: rollout_tick_tangent()'s, OR-ed over the chunks).  Column c equals rollout_tick_tangent() on seed c bit for bit, however the
     columns are chunked; steps = 0 gives the identity.  A stance leg's joint_qdot is not read by the step: those columns are 0."""
+    return _tick_transition("rollout_tick_transition", rollout_tick_tangent, ctl, batch, steps, dt, leg_inertia, act_tol, warm, chunk, stream)
+
+
+def _tick_transition(who, rollout, ctl, batch, steps, dt, leg_inertia, act_tol, warm, chunk, stream):
+    """rollout_tick_transition() and rollout_swing_transition(): `rollout` on the 36 unit seeds, `chunk` of them at a time"""
     import contextlib
 
     import torch
@@ -589,7 +635,7 @@ def rollout_tick_transition(ctl, batch, steps, dt, leg_inertia, act_tol=1e-7, wa
     n, dev = batch["x"].shape[0], batch["x"].device
     size = len(cols) if chunk is None else int(chunk)
     if size < 1:
-        raise ValueError("rollout_tick_transition: chunk must be >= 1")
+        raise ValueError(f"{who}: chunk must be >= 1")
     on_stream = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
     moved = ("Rwb", "x", "xdot", "w", "joint_q", "joint_qdot")
     with on_stream:
@@ -603,9 +649,107 @@ def rollout_tick_transition(ctl, batch, steps, dt, leg_inertia, act_tol=1e-7, wa
                 for k in moved:
                     batch[k].copy_(start[k])
             seeds = tick_transition_seeds(n, dev, part)
-        _, res = rollout_tick_tangent(ctl, batch, steps, dt, leg_inertia, seeds, act_tol, warm, stream)
+        _, res = rollout(ctl, batch, steps, dt, leg_inertia, seeds, act_tol, warm, stream)
         with on_stream:
             rows = torch.cat([res[k].reshape(len(part), n, -1) for k in _TICK_STATE], dim=-1)  # [len(part), n, 36]
             phi[:, :, c0:c0 + len(part)] = rows.permute(1, 2, 0)
             flags.bitwise_or_(res["flags"])
     return dict(phi=phi, columns=cols, flags=flags)
+
+
+# ------------------------------------------------------------------ forward mode through a trot: the swing legs' PD torques
+def plan_swing_torque_tangent(ctl, batch, tangents, want=("joint_tau_tan",), out=None, stream=None):
+    """swing_torque_tangent() marshalled once: returns (launch, out, squeeze), `launch()` being one qc_swing_torque_tangent_batch call
+    (graph-capturable) on tensors that are read in place; `out` holds the [K, n, 4, 3] tensor (and "flags" int32 [n] where asked for)
+    and squeeze says whether the tangents came as [n, ...].  out["joint_tau_tan"] may be tangents["joint_tau_tan_in"] or any other
+    [K, n, 4, 3] tangent (the aliasing contract of include/qc_tangent.h).  Planning launches nothing."""
+    from .balance_controller import _SWING_FIELDS, SWING_STATE_DTYPE, _record_tensor
+
+    _library()
+    unknown = [k for k in tangents if k not in SWING_TORQUE_TANGENTS]
+    if unknown:
+        raise ValueError(f"swing_torque_tangent: unknown tangent(s) {unknown}; the tangents are {tuple(SWING_TORQUE_TANGENTS)}")
+    io = QcSwingTangentIo()
+    ctl._lib.qc_default_swing_tangent(C.byref(io))
+    sizing = [batch.get(k) for k in ("x", "Rwb", "joint_q", "joint_qdot", "swing_pos", "swing_vel")] + [t for t in tangents.values() if t is not None and t.dim() == 2]
+    n, dev, bi = ctl._readonly_batch("swing_torque_tangent", batch, _SWING_FIELDS, io, [], sizing, "none of the arrays of the swing chain is there to size the call")
+    if _record_tensor("swing_state", batch.get("swing_state"), n, SWING_STATE_DTYPE.itemsize, dev):  # (the library names its refusal)
+        bi.swing_state = batch["swing_state"].data_ptr()
+    given, K, squeeze = _directions(tangents, SWING_TORQUE_TANGENTS, n, dev, io)
+    io.n_dir = K
+    rows = tuple(w for w in want if w != "flags")
+    extra = [("flags", (n,), "int32")] if "flags" in want else []
+    res = _outputs("swing_torque_tangent", _SWING_TORQUE_TANGENT_OUTPUTS, rows, out, K * n, dev, io, extra)
+    res = {k: (v if k == "flags" else v.view((K, n) + _SWING_TORQUE_TANGENT_OUTPUTS[k][0])) for k, v in res.items()}
+    launch = ctl._launcher("qc_swing_torque_tangent_batch", (n, C.byref(bi), C.byref(io), ctl._stream_ptr(stream)), (batch, given, res, bi, io), ValueError)
+    return launch, res, squeeze
+
+
+def swing_torque_tangent(ctl, batch, tangents, want=("joint_tau_tan",), out=None, stream=None):
+    """Forward mode of the swing legs' PD torques (qc_swing_torque_tangent_batch, include/qc_tangent.h; INTEGRATION.md "Forward mode:
+    tangents and the Jacobian"), the map ctl.sensitivity_swing_batch() transposes.  `batch`: the one control_batch(want_torques=True)
+    read, with swing_pos and swing_vel - Rwb, x, joint_q, joint_qdot, the two references and the contact mask (stance, else the phase
+    rule on gait_phase as it is now, else all stance) are all that is read of it; a batch with swing_state or gait_dt is refused.
+    `tangents`: a dict with any of "Rwb_rot_tan" (the world-frame left tangent, Rwb <- exp([d]x) Rwb), "x_tan" ([n,3]),
+    "swing_pos_tan", "swing_vel_tan", "joint_q_tan", "joint_qdot_tan" and "joint_tau_tan_in" ([n,12] or [n,4,3]; the last is added:
+    what torque_tangent() wrote) - each [n, ...] for one direction or [K, n, ...] for K, all agreeing on K; a missing one is zero, at
+    least one given.  `want`: "joint_tau_tan" [K,n,4,3] and / or "flags" int32 [n].  A swing leg's row is m o (kp o (dq_ref - dq) +
+    kd o (dqd - dqdot)) + joint_tau_tan_in, m the forward tick's clamp mask bit for bit, whatever the QP's status; a stance leg's row
+    is joint_tau_tan_in.  flags bit l: swing leg l's reference is out of reach, inside the inner limit, not finite, or at a singular
+    J(q_ref) - NaN in its row in every direction, the other legs untouched.  torque_tangent() writes exact zeros in swing rows: the
+    two calls in that order on one buffer (out["joint_tau_tan"] = tangents["joint_tau_tan_in"]) give the tangent of the tick's
+    complete joint_tau.  Returns the dict of device tensors, squeezed to [n, 4, 3] where the tangents came that way; `out`: a dict of
+    tensors to write into - joint_tau_tan may be any of the [K, n, 4, 3] tangents.  Nothing of `batch` is written.  Asynchronous on
+    `stream`, no synchronisation.  ValueError with the library's message for a call it refuses.  Not covered: tangents of the gains,
+    the torque limits and the kinematic constants; the planner and the gait clock."""
+    launch, res, squeeze = plan_swing_torque_tangent(ctl, batch, tangents, want, out, stream)
+    launch()
+    return {k: (v[0] if squeeze and k != "flags" else v) for k, v in res.items()}
+
+
+def _swing_rollout_refusals(who, batch, command, lean):
+    """what the rollouts through a trot refuse before anything is planned"""
+    if command is not None:
+        raise ValueError(f"{who}: commander mode has no forward mode - command must be None (the desired state is held in the batch)")
+    if lean is not None:
+        raise ValueError(f"{who}: lean has no forward mode - lean must be None")
+    for name, why in (("swing_state", "the swing planner"), ("gait_dt", "the gait clock (the contact mask is held)")):
+        if batch.get(name) is not None:
+            raise ValueError(f"{who}: batch['{name}'] must be None - {why} has no forward mode")
+    if batch.get("swing_pos") is None or batch.get("swing_vel") is None:
+        raise ValueError(f"{who}: the batch carries swing_pos and swing_vel, both (rollout_tick_tangent() differentiates a batch without swing references)")
+    if batch.get("joint_q") is None or batch.get("joint_qdot") is None:
+        raise ValueError(f"{who}: the batch carries joint_q and joint_qdot (rollout_tangent() steps the bare rigid body)")
+
+
+def rollout_swing_tangent(ctl, batch, steps, dt, leg_inertia, tangents, act_tol=1e-7, warm=True, stream=None, command=None, lean=None):
+    """The forward-mode twin of ctl.rollout_tick(batch, None, ...) for a batch that carries swing_pos AND swing_vel: forward mode
+    through a trot.  The two references and the `stance` / `gait_phase` / `gait_duty` contact mask are HELD over the rollout, exactly
+    as rollout_tick_autograd() holds them.  Per step: control_batch(want_torques=True), tangent_batch(), torque_tangent(),
+    swing_torque_tangent() in place on joint_tau_tan, leg_plant_step_tangent() (it reads the state before the step) and
+    leg_plant_step(), everything planned once, on one stream and without a host round trip.  `batch` is advanced IN PLACE and ends bit
+    for bit where ctl.rollout_tick() leaves it.  `tangents`: rollout_tick_tangent()'s - the start state's "Rwb_rot_tan", "x_tan",
+    "xdot_tan", "w_tan" [n,3], "joint_q_tan", "joint_qdot_tan" [n,12] and the held "x_d_tan", "xdot_d_tan", "w_d_tan", "Rwb_d_rot_tan" -
+    plus the held "swing_pos_tan" and "swing_vel_tan" [n,12], applied at every step; each [n, ...] or [K, n, ...], all agreeing; none is
+    written.  Returns (state, res) as rollout_tick_tangent() does.  res["flags"] int32 [n], OR-ed over the steps on the device, is
+    rollout_tick_tangent()'s word - bits 0-1 tangent_batch()'s, bits 8-15 the plant's shifted left by 8 - with swing_torque_tangent()'s
+    bits shifted left by SWING_FLAGS_SHIFT = 16: bit 16 + l, swing leg l's reference had no derivative at some step (its torque
+    tangent, and what follows from it, is NaN).  The derivative is the one on the active face of every solve at `act_tol` and at
+    every tick's clamp masks, as rollout_tick_autograd()'s.  Tangent memory is one set of buffers whatever `steps` is.  ValueError for
+    swing_state, gait_dt, a `command`, `lean`, and for a batch with only one of swing_pos / swing_vel (or neither): the planner, the
+    gait clock and commander mode have no forward mode."""
+    who = "rollout_swing_tangent"
+    _swing_rollout_refusals(who, batch, command, lean)
+    return _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, ROLLOUT_SWING_TANGENTS, act_tol, warm, stream, True)
+
+
+def rollout_swing_transition(ctl, batch, steps, dt, leg_inertia, act_tol=1e-7, warm=True, chunk=None, stream=None):
+    """The 36 x 36 state-transition matrix of `steps` closed-loop steps through a trot: rollout_swing_tangent() on the 36 unit seeds of
+    the start state (tick_transition_seeds), in rollout_tick_transition()'s column order and chunked the same way (the start state is
+    restored between the chunks; the references and the mask are held).  `batch` is advanced in place, as by ctl.rollout_tick().
+    Returns dict(phi [n,36,36], columns, flags int32 [n]: rollout_swing_tangent()'s, OR-ed over the chunks).  Column c equals
+    rollout_swing_tangent() on seed c bit for bit, however the columns are chunked; steps = 0 gives the identity.  ValueError as
+    rollout_swing_tangent()."""
+    who = "rollout_swing_transition"
+    _swing_rollout_refusals(who, batch, None, None)
+    return _tick_transition(who, rollout_swing_tangent, ctl, batch, steps, dt, leg_inertia, act_tol, warm, chunk, stream)
