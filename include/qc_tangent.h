@@ -31,14 +31,15 @@
  *
  * OUT OF SCOPE: entrywise (nine-number) rotation tangents - the rotations move along the left tangents above only; tangents of
  * the handle's parameters (mu, fzmin, fzmax, the weights, the gains, mass, Ib, the kinematic model); tangents through the swing
- * pipeline (the swing legs' PD torques, the planner's references, the gait clock); weak activity (a row whose multiplier is about 0
+ * pipeline (the swing legs' PD torques and the planner's references have their own calls below; the gait clock is held); weak activity (a row whose multiplier is about 0
  * is on the face like any other); commander mode (the desired state must be in `in`); a jvp on the torch.autograd.Functions of the
  * Python package.
  *
  * The rigid-body plant step has its forward mode below, qc_plant_step_tangent_batch: with it the two calls chain, step after step,
  * into the tangent of a closed-loop rollout.  The loop around the complete tick - joint_q -> FK -> QP -> clamped J^T -> joint_tau ->
  * legged plant - chains qc_tangent_batch (joint_q_tan), qc_torque_tangent_batch, for a batch with swing references
- * qc_swing_torque_tangent_batch in place behind it, and qc_leg_plant_step_tangent_batch, all below. */
+ * qc_swing_torque_tangent_batch in place behind it, and qc_leg_plant_step_tangent_batch, all below.  With swing_state the references
+ * themselves move: qc_swing_reference_tangent_batch, last in this header, is the forward mode of the planner and the trajectory. */
 #ifndef QC_TANGENT_H
 #define QC_TANGENT_H
 
@@ -176,8 +177,9 @@ int qc_torque_tangent_batch(qc_handle* h, size_t n, const qc_batch_in* in, const
  * joint_tau_tan may BE joint_tau_tan_in or any other [K][n][4][3] input tangent: a (direction, robot, leg) row reads all it needs
  * before it writes and touches only its own row.  All pointers are device pointers.
  *
- * OUT OF SCOPE: tangents of the gains, of tau_min / tau_max and of the kinematic constants; the planner and the gait clock
- * (qc_swing_reference_batch has no forward mode: swing_state and gait_dt are refused); commander mode. */
+ * OUT OF SCOPE: tangents of the gains, of tau_min / tau_max and of the kinematic constants; the planner and the gait clock in THIS
+ * call (swing_state and gait_dt are refused: qc_swing_reference_tangent_batch, below, gives swing_pos_tan / swing_vel_tan on the
+ * references qc_swing_reference_batch returned); commander mode. */
 typedef struct qc_swing_tangent_io {
   size_t struct_size;            /* = sizeof(qc_swing_tangent_io); checked                                            */
   size_t n_dir;                  /* K >= 1 directions per launch                                                      */
@@ -247,6 +249,64 @@ void qc_default_leg_plant_tangent(qc_leg_plant_tangent_io* io);
  * all, a missing Rwb, x, xdot, w, joint_q, joint_qdot or joint_tau, a handle whose mass or Ib qc_plant_step_batch refuses, or
  * n * n_dir beyond one launch. */
 int qc_leg_plant_step_tangent_batch(qc_handle* h, size_t n, const qc_leg_plant_tangent_io* io, void* stream);
+
+/* qc_swing_reference_tangent_batch - forward mode of qc_swing_reference_batch (qc_balance.h), the map qc_swing_reference_adjoint_batch
+ * transposes: the foothold planner and the sextic swing trajectory, K tangents per launch.  The contract of `in` is the adjoint's,
+ * unchanged: nothing is saved by the forward launch; pass the same `in` with gait_phase AS THE FORWARD CALL LEFT IT (gait_dt is
+ * refused: no clock is advanced here) and `state_before`, a copy of the qc_swing_state records from BEFORE the forward call.  The
+ * plan decision is recomputed from its leg_state / has_traj and the contact mask by the forward kernel's own device functions.  Of
+ * `in` it reads Rwb, x, xdot, w, joint_q, gait_phase - required - and the optional stance and gait_duty; `in` is never written.
+ *
+ * Per direction, robot and leg l, with p = FK(joint_q_l), r = Rwb p, half = t_stance / 2, k = planner_k, lip = sqrt(x_z / 9.81) / 2,
+ * hip = planner_hip[l] (the adjoint's symbols), delta the world-frame left tangent of Rwb, dq_l = joint_q_tan_l:
+ *   leg replanned:      dr  = delta x r + Rwb J(q_l) dq_l
+ *                       dps = dr + dx
+ *                       dpf = delta x (Rwb hip) + dx + (half + k + lip) dxdot - k dxdot_d + (0.25 / (9.81 sqrt(x_z / 9.81))) dx_z xdot
+ *                             + half (dw x r + w x dr),   dpf_z := 0 (the foothold's z is the constant 0)
+ *   leg NOT replanned:  dps = p_start_tan_l,  dpf = p_final_tan_l       (the record passed through)
+ *   swing leg with a trajectory after the call, (h, h') the sextic's basis functions and their derivatives at the leg's clamped
+ *   trajectory time (the loop the forward kernel and the adjoint share):
+ *                       swing_pos_tan_r = (h0 + m h2) dps_r + (h1 + m h2) dpf_r,  swing_vel_tan_r likewise with h'
+ *                       m = 1/2 for r = x, y and 0 for z (the centre's z is swing_height)
+ *   every other leg:    swing_pos_tan_l = swing_vel_tan_l = 0 exactly
+ *   p_start_next_tan_l = dps,  p_final_next_tan_l = dpf                 on the record after the call
+ * HELD: the clock, the contact mask and the plan decisions, as in the adjoint.  There is no tangent of the phase, of gait_dt, of the
+ * gait's periods, of swing_height, of planner_k or of the kinematic constants.
+ *
+ * `flags` bit l: leg l is replanned and x_z is not finite and > 0 (the adjoint's rule: the LIP square root has no derivative there).
+ * A robot with any bit set gets NaN in every output row of every direction.  Other non-finite inputs propagate; nothing is clamped.
+ *
+ * <swing_pos_bar, swing_pos_tan> + <swing_vel_bar, swing_vel_tan> + <p_start_next_bar, p_start_next_tan> + <p_final_next_bar,
+ * p_final_next_tan> equals <x_bar, dx> + <xdot_bar, dxdot> + <w_bar, dw> + <xdot_d_bar, dxdot_d> + <joint_q_bar, dq> + <p_start_bar,
+ * p_start_tan> + <p_final_bar, p_final_tan> + <Rwb_bar, [delta]x Rwb> with the outputs of qc_swing_reference_adjoint_batch (its `_in`
+ * arrays NULL): the entrywise Rwb_bar is paired with [delta]x Rwb, as for the other kernels of this header.
+ *
+ * A (direction, robot) pair reads every input before it writes and touches only its own rows: p_start_next_tan may BE p_start_tan,
+ * p_final_next_tan may BE p_final_tan, and swing_pos_tan / swing_vel_tan may be any [K][n][12] input tangent.  A rollout carries the
+ * record's two tangents in one pair of buffers.  All pointers are device pointers.  No buffer is kept on the handle.
+ *
+ * OUT OF SCOPE: tangents of the phase, of gait_dt, of the periods, of swing_height and of planner_k; the commander step and the com
+ * reference (qc_commander_step_batch, qc_com_reference_batch have no forward mode); parameter tangents. */
+typedef struct qc_swing_reference_tangent_io {
+  size_t struct_size;                         /* = sizeof(qc_swing_reference_tangent_io); checked                      */
+  const struct qc_swing_state* state_before;  /* [n] the records before the forward call; required                     */
+  size_t n_dir;                               /* K >= 1 directions per launch                                          */
+  /* tangents, direction-major as in qc_tangent_io; NULL = zero, at least one given                                   */
+  const double *Rwb_rot_tan, *x_tan, *xdot_tan, *w_tan, *xdot_d_tan;  /* [K][n][3]; Rwb_rot_tan: Rwb <- exp([d]x) Rwb  */
+  const double* joint_q_tan;                  /* [K][n][12]                                                            */
+  const double *p_start_tan, *p_final_tan;    /* [K][n][12] on the record before the call                              */
+  /* outputs, each optional, at least one given (flags counts)                                                        */
+  double *swing_pos_tan, *swing_vel_tan;      /* [K][n][4][3]                                                          */
+  double *p_start_next_tan, *p_final_next_tan;  /* [K][n][12] on the record after the call                             */
+  int32_t* flags;                             /* [n]: bit l - replanned leg l has no derivative                        */
+} qc_swing_reference_tangent_io;
+/* struct_size set, pointers NULL, n_dir = 1. */
+void qc_default_swing_reference_tangent(qc_swing_reference_tangent_io* io);
+/* Asynchronous on `stream`, no host synchronisation (graph-capturable); n == 0 launches nothing and returns QC_OK.
+ * QC_ERR_INVALID (message starting with "qc_swing_reference_tangent_batch:", nothing launched) for a null handle, `in` or `io`, a
+ * wrong struct_size, n_dir == 0, no tangent given at all, no output requested at all, a gait_dt, swing_pos or swing_vel in `in`,
+ * `feet` without joint_q, a missing state_before, a missing Rwb, x, xdot, w, joint_q or gait_phase, or n * n_dir beyond one launch. */
+int qc_swing_reference_tangent_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_swing_reference_tangent_io* io, void* stream);
 
 #ifdef __cplusplus
 }

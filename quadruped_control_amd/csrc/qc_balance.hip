@@ -2395,6 +2395,19 @@ int qc_leg_plant_step_tangent_batch(qc_handle* h, size_t n, const qc_leg_plant_t
   return launch_flat(qc::leg_plant_step_tangent_kernel, qc::leg_plant_tangent_blocks(n, io->n_dir), qc::LEG_PLANT_TANGENT_BLOCK, stream, h->d_params, (long)n, a);
 }
 
+void qc_default_swing_reference_tangent(qc_swing_reference_tangent_io* io) {
+  if (!zeroed(io)) return;
+  io->n_dir = 1;
+}
+
+int qc_swing_reference_tangent_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_swing_reference_tangent_io* io, void* stream) {
+  if (const int rc = qc::check_swing_reference_tangent_args(h, n, in, io); rc != QC_OK || n == 0) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  // (of `in`: the state, joint_q and the contact mask as the forward call left it - nothing of it is written)
+  return launch_flat(qc::swing_reference_tangent_kernel, qc::swing_reference_tangent_blocks(n, qc::swing_reference_tangent_dirs(io)),
+                     qc::SWING_REFERENCE_TANGENT_BLOCK, stream, h->d_params, (long)n, qc::swing_reference_tangent_constants(in, io));
+}
+
 void qc_default_sensitivity_rot(qc_sensitivity_rot_io* io) { (void)zeroed(io); }
 
 int qc_sensitivity_rot_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_rot_io* io, void* stream) {

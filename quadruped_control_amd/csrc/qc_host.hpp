@@ -29,6 +29,7 @@
 #include "qc_swing_tangent.hpp"
 #include "qc_torque_tangent.hpp"
 #include "qc_leg_plant_tangent.hpp"
+#include "qc_swing_reference_tangent.hpp"
 
 namespace qc {
 
@@ -1041,5 +1042,46 @@ inline int leg_plant_tangent_constants(double mass, const double* Ib, const qc_l
 
 // workgroups of leg_plant_step_tangent_kernel for n robots and K directions: one wave of pairs each, capped (a grid cap of its own)
 inline unsigned leg_plant_tangent_blocks(size_t n, size_t n_dir) { return capped_blocks(n * n_dir, LEG_PLANT_TANGENT_BLOCK, LEG_PLANT_TANGENT_MAX_BLOCKS); }
+
+// ---------------------------------------------------------------- qc_swing_reference_tangent_batch
+// What is wrong with the call itself (message prefix "qc_swing_reference_tangent_batch:").  The contract of `in` is
+// qc_swing_reference_adjoint_batch's: what that call refuses about `in` is refused here in its words.  One lane per (direction,
+// robot): the pairs must fit a launch.
+inline int check_swing_reference_tangent_args(const qc_handle* h, size_t n, const qc_batch_in* in, const qc_swing_reference_tangent_io* io) {
+  const char* who = "qc_swing_reference_tangent_batch";
+  if (const int rc = check_io(who, h && in, io, "qc_swing_reference_tangent_io", "qc_default_swing_reference_tangent"); rc != QC_OK) return rc;
+  const auto bad = [who](const char* what) { return fail(QC_ERR_INVALID, std::string(who) + what); };
+  if (io->n_dir == 0) return bad(": n_dir must be >= 1");
+  if (!io->Rwb_rot_tan && !io->x_tan && !io->xdot_tan && !io->w_tan && !io->xdot_d_tan && !io->joint_q_tan && !io->p_start_tan && !io->p_final_tan)
+    return bad(": no tangent given (Rwb_rot_tan, x_tan, xdot_tan, w_tan, xdot_d_tan, joint_q_tan, p_start_tan, p_final_tan are all NULL)");
+  if (!io->swing_pos_tan && !io->swing_vel_tan && !io->p_start_next_tan && !io->p_final_next_tan && !io->flags)
+    return bad(": no output requested (swing_pos_tan, swing_vel_tan, p_start_next_tan, p_final_next_tan, flags are all NULL)");
+  if (const int rc = check_swing_reference_batch(who, in); rc != QC_OK) return rc;
+  if (in->gait_dt) return bad(": gait_dt must be NULL (no clock is advanced here: gait_phase is read as the forward call left it)");
+  if (n == 0) return QC_OK;
+  if (!io->state_before) return bad(": state_before is required (the swing records from before the forward call)");
+  if (!in->Rwb || !in->x || !in->xdot || !in->w || !in->joint_q || !in->gait_phase) return bad(": Rwb, x, xdot, w, joint_q and gait_phase are required");
+  if (n > (size_t)0xFFFFFF * (size_t)SWING_REFERENCE_TANGENT_BLOCK || io->n_dir > (size_t)0xFFFFFF * (size_t)SWING_REFERENCE_TANGENT_BLOCK / n)
+    return bad(": n * n_dir is beyond one launch");
+  return QC_OK;
+}
+
+// the directions the kernel walks: the flags come from the held decisions alone, so a call that asks for nothing else walks one
+inline size_t swing_reference_tangent_dirs(const qc_swing_reference_tangent_io* io) {
+  return (io->swing_pos_tan || io->swing_vel_tan || io->p_start_next_tan || io->p_final_next_tan) ? io->n_dir : 1;
+}
+
+// the kernel's arguments: the arrays of `in` the adjoint reads, the record's arrays
+inline SwingReferenceTangentArgs swing_reference_tangent_constants(const qc_batch_in* in, const qc_swing_reference_tangent_io* io) {
+  return SwingReferenceTangentArgs{in->Rwb, in->x, in->xdot, in->w, in->joint_q, in->gait_phase, in->stance, in->gait_duty,
+                                   reinterpret_cast<const SwingState*>(io->state_before), (long)swing_reference_tangent_dirs(io), io->Rwb_rot_tan,
+                                   io->x_tan, io->xdot_tan, io->w_tan, io->xdot_d_tan, io->joint_q_tan, io->p_start_tan, io->p_final_tan,
+                                   io->swing_pos_tan, io->swing_vel_tan, io->p_start_next_tan, io->p_final_next_tan, io->flags};
+}
+
+// workgroups of swing_reference_tangent_kernel for n robots and K directions: one wave of pairs each, capped (a grid cap of its own)
+inline unsigned swing_reference_tangent_blocks(size_t n, size_t n_dir) {
+  return capped_blocks(n * n_dir, SWING_REFERENCE_TANGENT_BLOCK, SWING_REFERENCE_TANGENT_MAX_BLOCKS);
+}
 
 }  // namespace qc

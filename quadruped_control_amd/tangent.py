@@ -14,11 +14,16 @@ A trot has its forward mode as well: swing_torque_tangent() (qc_swing_torque_tan
 PD torques on references that are given, chained in place behind torque_tangent(); rollout_swing_tangent() is the forward-mode twin of
 ctl.rollout_tick(batch, None, ...) for a batch with swing_pos and swing_vel, rollout_swing_transition() its 36 x 36 matrix.
 
+The planner has its forward mode too: swing_reference_tangent() (qc_swing_reference_tangent_batch, csrc/qc_swing_reference_tangent.hpp),
+the foothold planner and the sextic swing trajectory at held plan decisions; rollout_gait_tangent() is the forward-mode twin of
+ctl.rollout_tick(batch, None, ...) for a batch with swing_state and a running clock - of rollout_gait_autograd() -, and
+rollout_gait_transition() its 60 x 60 matrix: the 36 coordinates of the tick and the record's p_start[12], p_final[12].
+
 The functions take the controller as their first argument, as autograd.py's do.  The symbols of the library are bound here, on
 the CDLL that _lib.load() returns, with this module's own ctypes records: _lib.EXPORTS and BalanceController are not touched.
 
-Not covered: the swing planner and the gait clock (swing_state, gait_dt), commander mode, tangents of the handle's parameters,
-and a jvp on the torch.autograd.Functions of autograd.py."""
+Not covered: tangents of the gait clock (the phases, the contact mask and the plan decisions are held), commander mode, the com
+reference (`lean`), tangents of the handle's parameters, and a jvp on the torch.autograd.Functions of autograd.py."""
 from __future__ import annotations
 
 import ctypes as C
@@ -68,6 +73,22 @@ _SWING_HELD = ("swing_pos_tan", "swing_vel_tan")
 ROLLOUT_SWING_TANGENTS = {**ROLLOUT_TICK_TANGENTS, **{k: 12 for k in _SWING_HELD}}
 SWING_FLAGS_SHIFT = 16  # rollout_swing_tangent()'s flags: rollout_tick_tangent()'s word | swing_torque_tangent()'s bits << 16
 
+# the planner and the swing trajectory (qc_swing_reference_tangent_io): the record's tangents and outputs in its order;
+# rollout_gait_tangent()'s tangents - the tick's and the two of the start record - and rollout_gait_transition()'s 60 coordinates
+SWING_REFERENCE_TANGENTS = {"Rwb_rot_tan": 3, "x_tan": 3, "xdot_tan": 3, "w_tan": 3, "xdot_d_tan": 3, "joint_q_tan": 12, "p_start_tan": 12, "p_final_tan": 12}
+_SWING_REFERENCE_TANGENT_OUTPUTS = {"swing_pos_tan": ((4, 3), "float64"), "swing_vel_tan": ((4, 3), "float64"),
+                                    "p_start_next_tan": ((12,), "float64"), "p_final_next_tan": ((12,), "float64")}
+SWING_REFERENCE_TANGENT_WANT = tuple(_SWING_REFERENCE_TANGENT_OUTPUTS)
+_GAIT_RECORD = ("p_start_tan", "p_final_tan")
+ROLLOUT_GAIT_TANGENTS = {**ROLLOUT_TICK_TANGENTS, **{k: 12 for k in _GAIT_RECORD}}
+GAIT_TRANSITION_COLUMNS = TICK_TRANSITION_COLUMNS + tuple((name, c) for name in ("p_start", "p_final") for c in range(12))
+REFERENCE_FLAGS_SHIFT = 20  # rollout_gait_tangent()'s flags: rollout_swing_tangent()'s word | swing_reference_tangent()'s bits << 20
+
+
+class QcSwingReferenceTangentIo(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("state_before", C.c_void_p), ("n_dir", C.c_size_t)] + \
+               [(k, C.c_void_p) for k in tuple(SWING_REFERENCE_TANGENTS) + SWING_REFERENCE_TANGENT_WANT + ("flags",)]
+
 
 class QcSwingTangentIo(C.Structure):
     _fields_ = [("struct_size", C.c_size_t), ("n_dir", C.c_size_t)] + [(k, C.c_void_p) for k in tuple(SWING_TORQUE_TANGENTS) + ("joint_tau_tan", "flags")]
@@ -105,7 +126,7 @@ def _library():
         lib = _lib.load()
         for name in ("qc_default_tangent", "qc_tangent_batch", "qc_default_plant_tangent", "qc_plant_step_tangent_batch", "qc_default_torque_tangent",
                      "qc_torque_tangent_batch", "qc_default_leg_plant_tangent", "qc_leg_plant_step_tangent_batch", "qc_default_swing_tangent",
-                     "qc_swing_torque_tangent_batch"):
+                     "qc_swing_torque_tangent_batch", "qc_default_swing_reference_tangent", "qc_swing_reference_tangent_batch"):
             if not hasattr(lib, name):
                 raise ImportError(f"{_lib.LIB_PATH} does not export {name}")
         lib.qc_default_tangent.argtypes = [C.POINTER(QcTangentIo)]
@@ -128,6 +149,10 @@ def _library():
         lib.qc_default_swing_tangent.restype = None
         lib.qc_swing_torque_tangent_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(_lib.QcBatchIn), C.POINTER(QcSwingTangentIo), C.c_void_p]
         lib.qc_swing_torque_tangent_batch.restype = C.c_int
+        lib.qc_default_swing_reference_tangent.argtypes = [C.POINTER(QcSwingReferenceTangentIo)]
+        lib.qc_default_swing_reference_tangent.restype = None
+        lib.qc_swing_reference_tangent_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(_lib.QcBatchIn), C.POINTER(QcSwingReferenceTangentIo), C.c_void_p]
+        lib.qc_swing_reference_tangent_batch.restype = C.c_int
         _bound = lib
     return _bound
 
@@ -526,11 +551,14 @@ def rollout_tick_tangent(ctl, batch, steps, dt, leg_inertia, tangents, act_tol=1
     return _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, ROLLOUT_TICK_TANGENTS, act_tol, warm, stream, False)
 
 
-def _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, table, act_tol, warm, stream, swings):
-    """What rollout_tick_tangent() and rollout_swing_tangent() share, behind their own refusals: the tangents validated against `table`,
-    one set of buffers, every launch planned once, the step loop.  swings=False launches exactly what rollout_tick_tangent() always
-    did; swings=True hands the whole batch to the tick (joint_qdot and the two references with it, as ctl.rollout_tick() does) and
-    adds swing_torque_tangent() in place on joint_tau_tan behind torque_tangent(), its flags at SWING_FLAGS_SHIFT."""
+def _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, table, act_tol, warm, stream, swings, clock=None):
+    """What rollout_tick_tangent(), rollout_swing_tangent() and rollout_gait_tangent() share, behind their own refusals: the tangents
+    validated against `table`, one set of buffers, every launch planned once, the step loop.  swings=False launches exactly what
+    rollout_tick_tangent() always did; swings=True hands the whole batch to the tick (joint_qdot and the two references with it, as
+    ctl.rollout_tick() does) and adds swing_torque_tangent() in place on joint_tau_tan behind torque_tangent(), its flags at
+    SWING_FLAGS_SHIFT.  `clock` (float64 [n], with swings=True): the references are made per step - a copy of the records,
+    swing_reference_batch() with `clock` as its gait_dt and swing_reference_tangent() in front of the tick, which reads the references
+    and the phases they left; the record's two tangents are carried in place, the flags land at REFERENCE_FLAGS_SHIFT."""
     import contextlib
 
     import torch
@@ -555,11 +583,20 @@ def _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, table,
         grf_tan, tau_tan = (torch.zeros((K, n, 4, 3), dtype=torch.float64, device=dev) for _ in range(2))
         flags, solve_flags, plant_flags = (torch.zeros((n,), dtype=torch.int32, device=dev) for _ in range(3))
         swing_flags = torch.zeros((n,), dtype=torch.int32, device=dev) if swings else None
+        if clock is not None:
+            # the record's tangents, advanced in place; the references and their tangents, rewritten by every step; the records before it
+            rec = {k: (given[k].reshape(K, n, 12).clone() if k in given else torch.zeros((K, n, 12), dtype=torch.float64, device=dev)) for k in _GAIT_RECORD}
+            pos_tan, vel_tan = (torch.zeros((K, n, 4, 3), dtype=torch.float64, device=dev) for _ in range(2))
+            pos, vel = (torch.zeros((n, 4, 3), dtype=torch.float64, device=dev) for _ in range(2))
+            ref_flags = torch.zeros((n,), dtype=torch.int32, device=dev)
+            before = torch.empty_like(batch["swing_state"])
     held = {k: given[k].reshape(K, n, 3) for k in _ROLLOUT_HELD if k in given}
     names = ("Rwb", "x", "xdot", "w", "joint_q", "joint_qdot")
     state = {k: batch[k] for k in names}
     # as rollout_tick(): a tick without swing references takes no joint_qdot
     tick_in = batch if swings else {k: v for k, v in batch.items() if k != "joint_qdot"}
+    if clock is not None:  # the tick of a gait step: on the references of this step and the phases they left, no planner and no clock
+        tick_in = dict({k: v for k, v in batch.items() if k != "swing_state"}, swing_pos=pos, swing_vel=vel)
     contact = {k: batch.get(k) for k in ("stance", "gait_phase", "gait_duty")}
     r = _RolloutPlans(ctl, who, batch, n, warm, lambda first, w, o: ctl.plan_batch(tick_in, w, o, want_active_set=warm, want_torques=True, stream=stream)[0],
                       None, stream, torques=True)
@@ -573,13 +610,31 @@ def _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, table,
         if swings:
             swing_in = {k: buf[k] for k in ("Rwb_rot_tan", "x_tan", "joint_q_tan", "joint_qdot_tan")}
             swing_in.update({k: given[k].reshape(K, n, 4, 3) for k in _SWING_HELD if k in given}, joint_tau_tan_in=tau_tan)
+            if clock is not None:
+                swing_in.update(swing_pos_tan=pos_tan, swing_vel_tan=vel_tan)
             swing_tan, _, _ = plan_swing_torque_tangent(ctl, tick_in, swing_in, ("joint_tau_tan", "flags"), {"joint_tau_tan": tau_tan, "flags": swing_flags}, stream)
         plant_out = {k[:-4] + "_next_tan": buf[k] for k in _TICK_STATE}
         plant_out["flags"] = plant_flags
         step_tan, _, _ = plan_leg_plant_step_tangent(ctl, state, r.out["joint_tau"], dt, leg_inertia, dict(buf, joint_tau_tan=tau_tan), want=tuple(plant_out),
                                                      out=plant_out, stream=stream, **contact)
         step = ctl.plan_leg_plant(state, r.out["joint_tau"], dt, leg_inertia, stream=stream, **contact)
+        reference = reference_tan = None
+        if clock is not None:
+            reads = {k: batch[k] for k in ("Rwb", "x", "xdot", "w", "xdot_d", "joint_q", "gait_phase", "gait_duty") if batch.get(k) is not None}
+            reference, _ = ctl.plan_swing_reference(dict(reads, swing_state=batch["swing_state"], gait_dt=clock), ("swing_pos", "swing_vel"),
+                                                    {"swing_pos": pos, "swing_vel": vel}, stream)
+            ref_in = dict({k: buf[k] for k in ("Rwb_rot_tan", "x_tan", "xdot_tan", "w_tan", "joint_q_tan")}, **rec)
+            if "xdot_d_tan" in held:
+                ref_in["xdot_d_tan"] = held["xdot_d_tan"]
+            ref_out = {"swing_pos_tan": pos_tan, "swing_vel_tan": vel_tan, "p_start_next_tan": rec["p_start_tan"], "p_final_next_tan": rec["p_final_tan"],
+                       "flags": ref_flags}
+            reference_tan, _, _ = plan_swing_reference_tangent(ctl, reads, before, ref_in, tuple(ref_out), ref_out, stream)
         for k in range(steps):
+            if reference is not None:
+                with on_stream:
+                    before.copy_(batch["swing_state"])
+                reference()
+                reference_tan()
             r.solve(k)
             solve_tan()
             torque_tan()
@@ -590,14 +645,18 @@ def _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, table,
                 flags.bitwise_or_(solve_flags.bitwise_or(plant_flags.bitwise_left_shift(TICK_PLANT_FLAGS_SHIFT)))
                 if swing_flags is not None:
                     flags.bitwise_or_(swing_flags.bitwise_left_shift(SWING_FLAGS_SHIFT))
+                if reference is not None:
+                    flags.bitwise_or_(ref_flags.bitwise_left_shift(REFERENCE_FLAGS_SHIFT))
             step()
     res = dict(buf, grf_tan=grf_tan, joint_tau_tan=tau_tan)
+    if clock is not None:
+        res.update(rec, swing_pos_tan=pos_tan, swing_vel_tan=vel_tan)
     res = {k: (v[0] if squeeze else v) for k, v in res.items()}
     res["flags"] = flags
     return state, res
 
 
-def tick_transition_seeds(n, dev, columns=TICK_TRANSITION_COLUMNS):
+def tick_transition_seeds(n, dev, columns=TICK_TRANSITION_COLUMNS, coordinates=_TICK_STATE):
     """rollout_tick_tangent()'s `tangents` for unit seeds on the start state: direction j moves coordinate columns[j] - (name, component)
     with name in "Rwb_rot", "x", "xdot", "w" (3 components) or "joint_q", "joint_qdot" (12) - by one.  [K, n, m] device tensors; only
     the coordinates that are seeded are returned."""
@@ -606,10 +665,10 @@ def tick_transition_seeds(n, dev, columns=TICK_TRANSITION_COLUMNS):
     seeds = {}
     for j, (name, comp) in enumerate(columns):
         key = name + "_tan"
-        if key not in _TICK_STATE:
-            raise ValueError(f"rollout_tick_transition: unknown coordinate {name!r}; the coordinates are {tuple(k[:-4] for k in _TICK_STATE)}")
+        if key not in coordinates:
+            raise ValueError(f"rollout_tick_transition: unknown coordinate {name!r}; the coordinates are {tuple(k[:-4] for k in coordinates)}")
         if key not in seeds:
-            seeds[key] = torch.zeros((len(columns), n, ROLLOUT_TICK_TANGENTS[key]), dtype=torch.float64, device=dev)
+            seeds[key] = torch.zeros((len(columns), n, ROLLOUT_GAIT_TANGENTS[key]), dtype=torch.float64, device=dev)
         seeds[key][j, :, comp] = 1.0
     return seeds
 
@@ -625,19 +684,22 @@ def rollout_tick_transition(ctl, batch, steps, dt, leg_inertia, act_tol=1e-7, wa
     return _tick_transition("rollout_tick_transition", rollout_tick_tangent, ctl, batch, steps, dt, leg_inertia, act_tol, warm, chunk, stream)
 
 
-def _tick_transition(who, rollout, ctl, batch, steps, dt, leg_inertia, act_tol, warm, chunk, stream):
-    """rollout_tick_transition() and rollout_swing_transition(): `rollout` on the 36 unit seeds, `chunk` of them at a time"""
+def _tick_transition(who, rollout, ctl, batch, steps, dt, leg_inertia, act_tol, warm, chunk, stream, columns=TICK_TRANSITION_COLUMNS,
+                     coordinates=_TICK_STATE, restored=()):
+    """rollout_tick_transition(), rollout_swing_transition() and rollout_gait_transition(): `rollout` on the unit seeds of `columns`
+    (over `coordinates`, the tangents that make a row), `chunk` of them at a time; `restored`: what the rollout advances in the batch
+    beside the six state arrays"""
     import contextlib
 
     import torch
 
-    cols = list(TICK_TRANSITION_COLUMNS)
+    cols = list(columns)
     n, dev = batch["x"].shape[0], batch["x"].device
     size = len(cols) if chunk is None else int(chunk)
     if size < 1:
         raise ValueError(f"{who}: chunk must be >= 1")
     on_stream = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
-    moved = ("Rwb", "x", "xdot", "w", "joint_q", "joint_qdot")
+    moved = ("Rwb", "x", "xdot", "w", "joint_q", "joint_qdot") + tuple(restored)
     with on_stream:
         phi = torch.empty((n, len(cols), len(cols)), dtype=torch.float64, device=dev)
         flags = torch.zeros((n,), dtype=torch.int32, device=dev)
@@ -648,10 +710,10 @@ def _tick_transition(who, rollout, ctl, batch, steps, dt, leg_inertia, act_tol, 
             if c0 > 0:
                 for k in moved:
                     batch[k].copy_(start[k])
-            seeds = tick_transition_seeds(n, dev, part)
+            seeds = tick_transition_seeds(n, dev, part, coordinates)
         _, res = rollout(ctl, batch, steps, dt, leg_inertia, seeds, act_tol, warm, stream)
         with on_stream:
-            rows = torch.cat([res[k].reshape(len(part), n, -1) for k in _TICK_STATE], dim=-1)  # [len(part), n, 36]
+            rows = torch.cat([res[k].reshape(len(part), n, -1) for k in coordinates], dim=-1)  # [len(part), n, 36] (60 through the planner)
             phi[:, :, c0:c0 + len(part)] = rows.permute(1, 2, 0)
             flags.bitwise_or_(res["flags"])
     return dict(phi=phi, columns=cols, flags=flags)
@@ -753,3 +815,135 @@ def rollout_swing_transition(ctl, batch, steps, dt, leg_inertia, act_tol=1e-7, w
     who = "rollout_swing_transition"
     _swing_rollout_refusals(who, batch, None, None)
     return _tick_transition(who, rollout_swing_tangent, ctl, batch, steps, dt, leg_inertia, act_tol, warm, chunk, stream)
+
+
+# ------------------------------------------------------------------ forward mode through the planner: the swing references
+def plan_swing_reference_tangent(ctl, batch, state_before, tangents, want=SWING_REFERENCE_TANGENT_WANT, out=None, stream=None):
+    """swing_reference_tangent() marshalled once: returns (launch, out, squeeze), `launch()` being one qc_swing_reference_tangent_batch
+    call (graph-capturable) on tensors that are read in place; `out` holds [K, n, ...] tensors (and "flags" int32 [n] where asked for)
+    and squeeze says whether the tangents came as [n, ...].  out["p_start_next_tan"] may be tangents["p_start_tan"],
+    out["p_final_next_tan"] tangents["p_final_tan"], and out["swing_pos_tan"] / out["swing_vel_tan"] any [K, n, 12] tangent (the aliasing
+    contract of include/qc_tangent.h).  Planning launches nothing."""
+    from .balance_controller import _SWING_REFERENCE_FIELDS, SWING_STATE_DTYPE, _record_tensor
+
+    _library()
+    unknown = [k for k in tangents if k not in SWING_REFERENCE_TANGENTS]
+    if unknown:
+        raise ValueError(f"swing_reference_tangent: unknown tangent(s) {unknown}; the tangents are {tuple(SWING_REFERENCE_TANGENTS)}")
+    io = QcSwingReferenceTangentIo()
+    ctl._lib.qc_default_swing_reference_tangent(C.byref(io))
+    sizing = [batch.get(k) for k in ("x", "Rwb", "xdot", "w", "joint_q", "gait_phase")] + [t for t in tangents.values() if t is not None and t.dim() == 2]
+    n, dev, bi = ctl._readonly_batch("swing_reference_tangent", batch, _SWING_REFERENCE_FIELDS, io, [], sizing,
+                                     "none of the arrays the planner reads is there to size the call")
+    if _record_tensor("swing_state", batch.get("swing_state"), n, SWING_STATE_DTYPE.itemsize, dev):  # (not read: the records come as state_before)
+        bi.swing_state = batch["swing_state"].data_ptr()
+    if _record_tensor("state_before", state_before, n, SWING_STATE_DTYPE.itemsize, dev):  # (a missing one is the library's refusal)
+        io.state_before = state_before.data_ptr()
+    given, K, squeeze = _directions(tangents, SWING_REFERENCE_TANGENTS, n, dev, io)
+    io.n_dir = K
+    rows = tuple(w for w in want if w != "flags")
+    extra = [("flags", (n,), "int32")] if "flags" in want else []
+    res = _outputs("swing_reference_tangent", _SWING_REFERENCE_TANGENT_OUTPUTS, rows, out, K * n, dev, io, extra)
+    res = {k: (v if k == "flags" else v.view((K, n) + _SWING_REFERENCE_TANGENT_OUTPUTS[k][0])) for k, v in res.items()}
+    launch = ctl._launcher("qc_swing_reference_tangent_batch", (n, C.byref(bi), C.byref(io), ctl._stream_ptr(stream)),
+                           (batch, state_before, given, res, bi, io), ValueError)
+    return launch, res, squeeze
+
+
+def swing_reference_tangent(ctl, batch, state_before, tangents, want=SWING_REFERENCE_TANGENT_WANT, out=None, stream=None):
+    """Forward mode of ctl.swing_reference_batch() (qc_swing_reference_tangent_batch, include/qc_tangent.h; INTEGRATION.md "Forward mode
+    through the planner"), the map ctl.swing_reference_adjoint_batch() transposes, under that call's contract: `batch` is the one the
+    forward call read, with gait_phase AS THAT CALL LEFT IT and without gait_dt - Rwb, x, xdot, w, joint_q, gait_phase and the optional
+    stance / gait_duty are all that is read of it -, `state_before` a copy of the swing_state tensor from BEFORE the forward call: the
+    plan decisions are recomputed from it and held, as are the clock and the contact mask.  `tangents`: a dict with any of
+    "Rwb_rot_tan" (the world-frame left tangent, Rwb <- exp([d]x) Rwb), "x_tan", "xdot_tan", "w_tan", "xdot_d_tan" ([n,3]),
+    "joint_q_tan" and, on the record before the call, "p_start_tan", "p_final_tan" ([n,12]) - each [n, ...] for one direction or
+    [K, n, ...] for K, all agreeing on K; a missing one is zero, at least one given.  `want`: any of "swing_pos_tan", "swing_vel_tan"
+    [K,n,4,3], "p_start_next_tan", "p_final_next_tan" [K,n,12] (on the record after the call) and "flags" int32 [n].  A replanned leg's
+    end points follow the state (the foothold's z has tangent 0), any other leg's pass the record's tangents through; a swing leg with
+    a trajectory after the call gets the sextic's linear map of the two, every other leg exact zeros.  flags bit l: leg l is replanned
+    at an x_z that is not finite and > 0 - NaN in every row of the robot, in every direction.  Returns the dict of device tensors,
+    squeezed to [n, ...] where the tangents came that way; `out`: a dict of tensors to write into (the aliasing contract:
+    plan_swing_reference_tangent()).  Nothing of `batch` or `state_before` is written.  Asynchronous on `stream`, no synchronisation.
+    ValueError with the library's message for a call it refuses.  Not covered: tangents of the phase, of gait_dt, of the gait's
+    periods, of swing_height, of planner_k and of the kinematic constants."""
+    launch, res, squeeze = plan_swing_reference_tangent(ctl, batch, state_before, tangents, want, out, stream)
+    launch()
+    return {k: (v[0] if squeeze and k != "flags" else v) for k, v in res.items()}
+
+
+_ROLLOUT_GAIT_REFUSED = {"stance": "the gait clock makes the contact mask from gait_phase", "swing_pos": "the references are made per step",
+                         "swing_vel": "the references are made per step", "gait_dt": "the clock's step is this call's gait_dt argument",
+                         "feet": "the tick reads joint_q (rollout_tangent() steps the bare rigid body on `feet`)"}
+_ROLLOUT_GAIT_NEEDED = ("joint_q", "joint_qdot", "gait_phase", "swing_state")
+
+
+def _gait_rollout_refusals(who, batch, lean):
+    """what the rollouts through the planner refuse before anything is planned"""
+    if lean is not None:
+        raise ValueError(f"{who}: lean has no forward mode - lean must be None (the com reference has no forward mode)")
+    for name, why in _ROLLOUT_GAIT_REFUSED.items():
+        if batch.get(name) is not None:
+            raise ValueError(f"{who}: batch['{name}'] must be None - {why}")
+    missing = [name for name in _ROLLOUT_GAIT_NEEDED if batch.get(name) is None]
+    if missing:
+        raise ValueError(f"{who}: the batch carries joint_q, joint_qdot, gait_phase and swing_state - missing {missing}")
+
+
+def _gait_clock(gait_dt, n, dev):
+    """the clock's step of a gait rollout as a float64 [n] tensor (a tensor is copied: the caller's is not kept)"""
+    import torch
+
+    if isinstance(gait_dt, torch.Tensor):
+        if gait_dt.numel() != n:
+            raise ValueError(f"gait_dt: a number or a tensor of {n} values")
+        return gait_dt.detach().to(dtype=torch.float64, device=dev).reshape(n).clone()
+    return torch.full((n,), float(gait_dt), dtype=torch.float64, device=dev)
+
+
+def rollout_gait_tangent(ctl, batch, steps, dt, leg_inertia, gait_dt, tangents, act_tol=1e-7, warm=True, stream=None, lean=None):
+    """The forward-mode twin of ctl.rollout_tick(batch, None, ...) for a batch with swing_state and a running clock - of
+    rollout_gait_autograd() -: forward mode through the planner.  Per step: a copy of the records, swing_reference_batch() with
+    `gait_dt` (a number or a float64 [n] tensor; the phases and the records advance IN PLACE), swing_reference_tangent() (the record's
+    two tangents in place, swing_pos_tan / swing_vel_tan written), control_batch(want_torques=True) on the returned references and
+    the phases left, tangent_batch(), torque_tangent(), swing_torque_tangent() in place on joint_tau_tan, leg_plant_step_tangent() (it
+    reads the state before the step) and leg_plant_step() with those same phases - everything planned once, on one stream and without
+    a host round trip.  `batch`, its gait_phase and its swing_state are advanced IN PLACE and end bit for bit where ctl.rollout_tick()
+    leaves them with a gait_dt of `dt`.  `tangents`: rollout_tick_tangent()'s - the start state's "Rwb_rot_tan", "x_tan", "xdot_tan",
+    "w_tan" [n,3], "joint_q_tan", "joint_qdot_tan" [n,12] and the held "x_d_tan", "xdot_d_tan" (it enters the planner too), "w_d_tan",
+    "Rwb_d_rot_tan" - plus "p_start_tan", "p_final_tan" [n,12] on the start record; each [n, ...] or [K, n, ...], all agreeing; none is
+    written.  The references' tangents are computed, not taken.  Returns (state, res) as rollout_swing_tangent() does; `res` adds the
+    final "p_start_tan", "p_final_tan" [K,n,12] and the last "swing_pos_tan", "swing_vel_tan" [K,n,4,3].  res["flags"] int32 [n], OR-ed
+    over the steps on the device, is rollout_swing_tangent()'s word with swing_reference_tangent()'s bits shifted left by
+    REFERENCE_FLAGS_SHIFT = 20: bit 20 + l, leg l was replanned at an x_z that is not finite and > 0 at some step.  The clock, the
+    contact mask and the plan decisions are held, as in rollout_gait_autograd(); the derivative is the one on the active face of
+    every solve at `act_tol` and at every tick's clamp masks.  Tangent memory is one set of buffers whatever `steps` is.  ValueError
+    for `lean` (the com reference has no forward mode), a `stance` mask, swing_pos / swing_vel, a gait_dt inside the batch, `feet`, and
+    a batch without joint_q, joint_qdot, gait_phase or swing_state."""
+    import torch
+
+    who = "rollout_gait_tangent"
+    _gait_rollout_refusals(who, batch, lean)
+    unknown = [k for k in tangents if k not in ROLLOUT_GAIT_TANGENTS]
+    if unknown:  # (swing_pos_tan / swing_vel_tan among them: the references' tangents are computed; refused before anything touches the device)
+        raise ValueError(f"{who}: unknown tangent(s) {unknown}; the tangents are {tuple(ROLLOUT_GAIT_TANGENTS)}")
+    clock = _gait_clock(gait_dt, batch["x"].shape[0], torch.device("cuda", ctl.device))
+    return _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, ROLLOUT_GAIT_TANGENTS, act_tol, warm, stream, True, clock)
+
+
+def rollout_gait_transition(ctl, batch, steps, dt, leg_inertia, gait_dt, act_tol=1e-7, warm=True, chunk=None, stream=None):
+    """The 60 x 60 state-transition matrix of `steps` closed-loop steps through the planner in minimal coordinates -
+    TICK_TRANSITION_COLUMNS (the rotation tangent, x, xdot, w, joint_q[12], joint_qdot[12]), then the record's p_start[12] and
+    p_final[12] -: rollout_gait_tangent() on the 60 unit seeds, `chunk` seeds per rollout (None: all in one; the state, the phases and
+    the records are restored between the chunks).  `batch`, its gait_phase and its swing_state are advanced in place, as by
+    rollout_gait_tangent().  Returns dict(phi [n,60,60], columns, flags int32 [n]: rollout_gait_tangent()'s, OR-ed over the chunks).
+    Column c equals rollout_gait_tangent() on seed c bit for bit, however the columns are chunked; steps = 0 gives the identity.
+    ValueError as rollout_gait_tangent()."""
+    who = "rollout_gait_transition"
+    _gait_rollout_refusals(who, batch, None)
+
+    def rollout(ctl, batch, steps, dt, leg_inertia, seeds, act_tol, warm, stream):
+        return rollout_gait_tangent(ctl, batch, steps, dt, leg_inertia, gait_dt, seeds, act_tol, warm, stream)
+
+    return _tick_transition(who, rollout, ctl, batch, steps, dt, leg_inertia, act_tol, warm, chunk, stream, GAIT_TRANSITION_COLUMNS,
+                            _TICK_STATE + _GAIT_RECORD, ("gait_phase", "swing_state"))
