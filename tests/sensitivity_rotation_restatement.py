@@ -77,6 +77,33 @@ def _quaternion_and_jacobian(m, case):
 
 def log_jacobian(Re):
     """(e [3], J [3, 9], case, qw) of the Eigen-convention log at the double matrix Re, on the branch it takes"""
+    e, do, dq, case, qw = _log_factors(Re)
+    return e, do @ dq, case, qw
+
+
+def log_jacobian_sum(Re):
+    """[3, 9]: the magnitude sum of J's own formation, J = (d out / d q) (d q / d m) with d out / d q_v = s I + q_v q_v^T (ds / dn) / n
+    and ds / dn = (2 |qw| / |q|^2 - angle / n) / n a difference of two terms of 2 / n each - every factor absolute, the difference a
+    sum.  However it is evaluated (here; in the device's reverse pass as sb (2 qw / |q|^2 - s) / n2 q_v, whose comment says so) the
+    second term keeps an ABSOLUTE rounding of EPS |s|, so the entries of J that are small by structure carry the rounding of the
+    large ones: a condition sum that is to cover a tangent along ONE axis takes this, not |J|."""
+    _, _, dq, _, qw = _log_factors(Re)
+    m = np.asarray(Re, float).reshape(3, 3)
+    q, _ = _quaternion_and_jacobian(m, DMR.eigen_case(m))
+    qv = np.abs(q[:3])
+    n = np.sqrt(qv @ qv)
+    ado = np.zeros((3, 4))
+    if n == 0.0:
+        ado[:, :3] = (2.0 / abs(qw)) * np.eye(3)
+    else:
+        w2 = n * n + qw * qw
+        angle = 2.0 * np.arctan2(n, abs(qw))
+        ado[:, :3] = (angle / n) * np.eye(3) + np.outer(qv, qv) * ((2.0 * abs(qw) / w2 / n + angle / (n * n)) / n)
+        ado[:, 3] = qv * (2.0 / w2)
+    return ado @ np.abs(dq)
+
+
+def _log_factors(Re):
     m = np.asarray(Re, float).reshape(3, 3)
     case = DMR.eigen_case(m)
     q, dq = _quaternion_and_jacobian(m, case)
@@ -91,11 +118,15 @@ def log_jacobian(Re):
         sg = -1.0 if qw < 0 else 1.0
         angle = 2.0 * np.arctan2(n, abs(qw))
         s = sg * angle / n
-        ds_dn = sg * (2.0 * abs(qw) / w2 / n - angle / (n * n))
+        # (the two terms are 2 / n each and cancel to O(n): in double the difference carries 6 EPS / n^2 of itself, 600 EPS at an error
+        # angle of 0.2 rad, which reaches the entries of J that are small by structure as an ABSOLUTE error of the size of EPS |J|max -
+        # far outside |J| |dRe| for a tangent along one axis.  Formed in long double, as device_math_reference's _ld routines are.)
+        nl, wl = np.longdouble(n), np.longdouble(abs(qw))
+        ds_dn = sg * float(2 * wl / (nl * nl + wl * wl) / nl - 2 * np.arctan2(nl, wl) / (nl * nl))
         e = qv * s
         do[:, :3] = s * np.eye(3) + np.outer(qv, qv) * (ds_dn / n)
         do[:, 3] = qv * (-2.0 / w2)
-    return e, do @ dq, case, qw
+    return e, do, dq, case, qw
 
 
 # ------------------------------------------------------------------ the four contributions, float64

@@ -29,6 +29,81 @@ def params(q, kind):
     return dict(P, W=1e-5 * (np.eye(12) + 0.05 * (M @ M.T) / 12.0), S=np.asarray(P["S"]) + 0.2 * (N @ N.T) / 6.0)  # dense S and W
 
 
+@functools.lru_cache(maxsize=None)
+def _odd_law(kind):
+    import quadruped_control_amd as q
+
+    P = params(q, kind)
+    rng = np.random.default_rng(77)
+    N = rng.normal(size=(3, 3))
+    kff = np.array([0.11, 0.23, 0.15, 0.31, 0.17, 0.29])
+    ratio = lambda k, r: np.asarray(P[k], float) * np.array(r)
+    odd = dict(P, mass=9.3, Ib=np.asarray(P["Ib"], float) + 0.004 * (N @ N.T) / 3.0, kff=kff, kp_p=ratio("kp_p", (0.8, 1.3, 1.0)),
+               kd_p=ratio("kd_p", (0.7, 1.0, 1.3)), kp_w=ratio("kp_w", (0.6, 1.0, 0.84)), kd_w=ratio("kd_w", (1.0, 0.64, 0.82)))
+    if kind == "uniform":  # (the uniform form asks for a diagonal S: six distinct weights; a dense S is the "dense" kind's)
+        odd["S"] = np.asarray(P["S"], float) * np.diag([0.9, 1.0, 1.1, 0.8, 1.2, 1.05])
+    Ib = odd["Ib"]
+    assert np.array_equal(Ib, Ib.T) and np.linalg.eigvalsh(Ib).min() > 0 and 1e-3 < np.abs(Ib[np.triu_indices(3, 1)]).min() < 1e-2, Ib
+    for k in ("kp_p", "kd_p", "kp_w", "kd_w"):
+        r = odd[k] / np.asarray(P[k], float)
+        assert len(set(odd[k])) == 3 and 0.6 <= r.min() and r.max() <= 1.3, (k, odd[k])
+    assert len(set(kff)) == 6 and 0.1 <= kff.min() and kff.max() <= 0.35, kff
+    assert all(odd[k] == P[k] for k in ("mu", "fzmin", "fzmax")) and odd["mass"] != P["mass"]
+    return odd
+
+
+def odd_law(kind="uniform"):
+    """params(q, kind) off the cheetah's control law, so that every index of the PD law b(state; gains) is visible: mass 9.3; Ib dense
+    symmetric positive definite (the cheetah's diagonal + 0.004 N N^T / 3: off-diagonals of a few 1e-3); kp_p, kd_p, kp_w, kd_w
+    three distinct values each, 0.6 ... 1.3 of the cheetah's; six distinct non-zero kff in 0.1 ... 0.35; for "uniform" six distinct
+    weights on the diagonal of S (qc_create keeps the uniform form only for a diagonal S, and the kernel name must stay FORMS[kind];
+    the "dense" kind carries a dense S).  mu, fzmin, fzmax as they were: the forces
+    inputs() places stay exactly on their faces.  Fixed seed, cached: callers copy before they write."""
+    return dict(_odd_law(kind))
+
+
+@functools.lru_cache(maxsize=None)
+def _odd_states(n, seed):
+    from scipy.spatial.transform import Rotation
+
+    r = np.random.default_rng(seed)
+    axis = r.normal(size=(n, 3))
+    axis /= np.linalg.norm(axis, axis=1, keepdims=True)
+    turn = Rotation.from_rotvec(axis * r.uniform(0.1, 0.6, (n, 1))).as_matrix()
+    return r.uniform(-0.3, 0.3, (n, 3)), r.uniform(-0.3, 0.3, (n, 3)), r.uniform(-0.2, 0.2, (n, 3)), turn
+
+
+def odd_states(b, seed):
+    """a copy of the batch `b` off config3's states: w_d and xdot_d uniform in (-0.3, 0.3)^3 (config3: w_d = (0, 0, +-0.05),
+    xdot_d[2] = 0), w moved by up to 0.2 per component, Rwb_d = a general-axis rotation of 0.1 ... 0.6 rad times Rwb.  Rwb itself is
+    untouched: the level robots carry the on-face forces of inputs().  Fixed by (n, seed); the draws are cached."""
+    n = b["x"].shape[0]
+    w_d, xdot_d, dw, turn = _odd_states(n, seed)
+    out = {k: v.copy() for k, v in b.items()}
+    out["w_d"], out["xdot_d"], out["w"] = w_d.copy(), xdot_d.copy(), np.ascontiguousarray(b["w"] + dw)
+    out["Rwb_d"] = np.ascontiguousarray((turn @ b["Rwb"].reshape(n, 3, 3)).reshape(n, 9))
+    return out
+
+
+def assert_tangent_close(got, ref, what, rows=None, c=None):
+    """qc_tangent_batch's outputs against tangent_restatement.tangent(): flags exactly, every entry of grf_tan and b_tan within
+    4 x c x EPS x its condition sum (c: tangent_restatement.C_TAN unless given); prints and returns the worst error / bar"""
+    from tests.tangent_restatement import C_TAN
+
+    c = C_TAN if c is None else c
+    rows = range(ref["flags"].shape[0]) if rows is None else rows
+    assert np.array_equal(got["flags"], ref["flags"]), what
+    worst = 0.0
+    rows = list(rows)
+    for name, sums in (("grf_tan", "grf_sum"), ("b_tan", "b_sum")):
+        err, bar = np.abs(got[name][:, rows] - ref[name][:, rows]), 4 * c * EPS * ref[sums][:, rows]
+        worst = max(worst, float((err / np.where(bar > 0, bar, 1.0))[bar > 0].max()) if (bar > 0).any() else 0.0)
+        bad = np.argwhere(~(err <= bar))
+        assert not len(bad), (what, name, bad[0].tolist(), float(err[tuple(bad[0])]), float(bar[tuple(bad[0])]))
+    print(what, "worst error / bar", worst)
+    return worst
+
+
 @pytest.fixture(scope="module")
 def ctls(q):
     """one handle per formulation, keyed as FORMS"""

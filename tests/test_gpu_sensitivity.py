@@ -153,19 +153,31 @@ def test_device_and_restatement_against_50_digits(solved):
             assert dev <= 8 * max(host, 8 * EPS), (kind, k, dev, host)
 
 
-def test_finite_differences_of_control_batch(q, ctls):
+@pytest.mark.parametrize("law", ["cheetah", "odd"])
+def test_finite_differences_of_control_batch(q, ctls, law):
     """<theta_bar, d> against control_batch itself at theta +- h d, 128 robots, race = 0, for a direction in the b-type inputs
     (exactly linear on a fixed face: h = 1e-3).  Kept: solved and the same want_active_set word at -h, 0, +h, flags 0.  Bar: the 6x6
     forms' forces carry an absolute error of eps (S / w) |b| ~ 1e-8 N at the reference's weights (csrc/qc_host.hpp), so the quotient
-    carries 1e-8 / h = 1e-5 on derivatives of |theta_bar| |d| ~ 5e3: 2e-9 relative; the bar is 1e-6 |theta_bar| |d|."""
+    carries 1e-8 / h = 1e-5 on derivatives of |theta_bar| |d| ~ 5e3: 2e-9 relative; the bar is 1e-6 |theta_bar| |d|.  law = "odd": the same h, bar and keep rule on a handle of the test's own at
+    solved_batch_support.odd_law with odd_states of the batch; there the kept share must be at least one half, and is printed."""
     import torch
     from quadruped_control_amd import workloads
 
-    ctl = ctls["uniform"]
+    ctl = ctls["uniform"] if law == "cheetah" else q.BalanceController.from_params(SB.odd_law(), device=0)
+    try:
+        _finite_differences(q, ctl, law, torch, workloads)
+    finally:
+        if law == "odd":
+            ctl.close()
+
+
+def _finite_differences(q, ctl, law, torch, workloads):
     ctl.set_tuning(race=0)
     n, h = 128, 1e-3
     b = dict(workloads.config3(n=n))
     b["stance"] = ((np.arange(n)[:, None] % 15 + 1 >> np.arange(4)[None, :]) & 1).astype(np.uint8)
+    if law == "odd":
+        b = SB.odd_states({k: np.ascontiguousarray(v) for k, v in b.items()}, 5)
     rng = np.random.default_rng(9)
     keys = ("x", "xdot", "w", "x_d", "xdot_d", "w_d")
     d = {k: rng.normal(0.0, 1.0, (n, 3)) for k in keys}
@@ -186,13 +198,13 @@ def test_finite_differences_of_control_batch(q, ctls):
     st = [o["status"].cpu().numpy() for o in (o0, op, om)]
     ws = [o["active_set"].cpu().numpy() for o in (o0, op, om)]
     keep = (st[0] == 0) & (st[1] == 0) & (st[2] == 0) & (ws[0] == ws[1]) & (ws[0] == ws[2]) & (s["flags"] == 0)
-    assert keep.mean() >= 0.75, keep.mean()
+    assert keep.mean() >= (0.75 if law == "cheetah" else 0.5), keep.mean()
     fd = (gbar * (op["grf_body"].cpu().numpy() - om["grf_body"].cpu().numpy())).sum(axis=1) / (2 * h)
     an = sum((s[k + "_bar"] * d[k]).sum(axis=1) for k in keys)
     scale = np.sqrt(sum((s[k + "_bar"] ** 2).sum(axis=1) for k in keys)) * np.sqrt(sum((d[k] ** 2).sum(axis=1) for k in keys))
     err = np.abs(fd - an)
-    print("kept", keep.mean(), "worst relative error", float((err[keep] / np.maximum(scale[keep], 1e-300)).max()))
-    assert (scale[keep] > 0).mean() > 0.9
+    print(law, "kept", keep.mean(), "worst relative error", float((err[keep] / np.maximum(scale[keep], 1e-300)).max()))
+    assert (scale[keep] > 0).mean() > (0.9 if law == "cheetah" else 0.75)  # (odd states keep more robots whose face is pinned throughout: 0.85 measured)
     assert np.all(err[keep] <= 1e-6 * scale[keep])
 
 

@@ -38,17 +38,7 @@ def _run(q, ctl, b, grf, tans, want=WANT_ALL, **kw):
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 
-def _assert_close(got, ref, what, rows=None):
-    rows = range(ref["flags"].shape[0]) if rows is None else rows
-    assert np.array_equal(got["flags"], ref["flags"]), what
-    worst = 0.0
-    rows = list(rows)
-    for name, sums in (("grf_tan", "grf_sum"), ("b_tan", "b_sum")):
-        err, bar = np.abs(got[name][:, rows] - ref[name][:, rows]), 4 * C_TAN * EPS * ref[sums][:, rows]
-        worst = max(worst, float((err / np.where(bar > 0, bar, 1.0))[bar > 0].max()) if (bar > 0).any() else 0.0)
-        bad = np.argwhere(~(err <= bar))
-        assert not len(bad), (what, name, bad[0].tolist(), float(err[tuple(bad[0])]), float(bar[tuple(bad[0])]))
-    print(what, "worst error / bar", worst)
+_assert_close = SB.assert_tangent_close  # (the comparator lives with the shared helpers: tests/test_gpu_odd_law.py uses it too)
 
 
 @pytest.mark.parametrize("n", SIZES)
@@ -231,21 +221,25 @@ def test_second_round_of_the_grid_stride(q, ctls, source):
     torch.cuda.empty_cache()
 
 
-def test_finite_differences_of_control_batch(q, ctls):
+@pytest.mark.parametrize("law", ["cheetah", "odd"])
+def test_finite_differences_of_control_batch(q, ctls, law):
     """<grf_bar, grf_tan> against control_batch itself at theta +- h d, for three random directions in the b-type inputs (exactly
     linear on a fixed face): the batch (128 robots of config 3, the 15 contact patterns in turn, race = 0), the keep rule (solved and
     the same want_active_set word at -h, 0, +h, flags 0), the step h = 1e-3 and the bar 1e-6 |theta_bar| |d| of
     tests/test_gpu_sensitivity.py's finite-difference test - with |theta_bar| the norm of sensitivity_batch's cotangents for the same
-    grf_bar, the scale that bar is stated in.  Kept share >= 0.75."""
+    grf_bar, the scale that bar is stated in.  Kept share >= 0.75.  law = "odd": the same h, bar and keep rule on a handle at
+    solved_batch_support.odd_law with odd_states of the batch; there the kept share must be at least one half, and is printed."""
     import torch
     from quadruped_control_amd import workloads
 
-    ctl = q.BalanceController.from_params(params(q, "uniform"), device=0)  # a handle of the test's own: race = 0 stays with it
+    ctl = q.BalanceController.from_params(params(q, "uniform") if law == "cheetah" else SB.odd_law(), device=0)  # a handle of the test's own: race = 0 stays with it
     try:
         ctl.set_tuning(race=0)
         n, h = 128, 1e-3
         b = dict(workloads.config3(n=n))
         b["stance"] = ((np.arange(n)[:, None] % 15 + 1 >> np.arange(4)[None, :]) & 1).astype(np.uint8)
+        if law == "odd":
+            b = SB.odd_states({k: np.ascontiguousarray(v) for k, v in b.items()}, 5)
         keys = ("x", "xdot", "w", "x_d", "xdot_d", "w_d")
         gbar = SB.gbar(9100, n)
         for trial in range(3):
@@ -269,13 +263,13 @@ def test_finite_differences_of_control_batch(q, ctls):
             st = [o["status"].cpu().numpy() for o in (o0, op, om)]
             ws = [o["active_set"].cpu().numpy() for o in (o0, op, om)]
             keep = (st[0] == 0) & (st[1] == 0) & (st[2] == 0) & (ws[0] == ws[1]) & (ws[0] == ws[2]) & (flags == 0)
-            assert keep.mean() >= 0.75, keep.mean()
+            assert keep.mean() >= (0.75 if law == "cheetah" else 0.5), keep.mean()
             fd = (gbar * (op["grf_body"].cpu().numpy() - om["grf_body"].cpu().numpy())).sum(axis=1) / (2 * h)
             an = (gbar * t["grf_tan"].cpu().numpy().reshape(n, 12)).sum(axis=1)
             scale = np.sqrt(sum((s[k + "_bar"] ** 2).sum(axis=1) for k in keys)) * np.sqrt(sum((d[k] ** 2).sum(axis=1) for k in keys))
             err = np.abs(fd - an)
-            print("direction", trial, "kept", keep.mean(), "worst relative error", float((err[keep] / np.maximum(scale[keep], 1e-300)).max()))
-            assert (scale[keep] > 0).mean() > 0.9
+            print(law, "direction", trial, "kept", keep.mean(), "worst relative error", float((err[keep] / np.maximum(scale[keep], 1e-300)).max()))
+            assert (scale[keep] > 0).mean() > (0.9 if law == "cheetah" else 0.75)  # (odd states keep more robots whose face is pinned throughout: 0.84 ... 0.85 measured)
             assert np.all(err[keep] <= 1e-6 * scale[keep])
     finally:
         ctl.close()

@@ -20,7 +20,9 @@ def test_restatement_against_50_digits():
     """The float64 restatement against tangent_mp on every eighth robot of the 130-robot placed-force batch, two directions each: from
     `feet` with every tangent but joint_q_tan, and from joint_q with every tangent.  The distance of every entry of grf_tan and b_tan
     is measured in EPS x its condition sum (tests/tangent_restatement.py); an entry whose condition sum is 0 is exact.  The worst is
-    the module's C_TAN (measured: grf_tan 0.52 / 0.66, b_tan 1.06; over ALL 65 robots of the n = 65 batch grf_tan stays below 0.53); the device's bar is 4 x it."""
+    the module's C_TAN (measured: grf_tan 0.52 / 0.66, b_tan 1.06); the device's bar is 4 x it.  This is the worst of a SAMPLE -
+    robots 0, 8, ... 128: over all 130 robots b_tan reaches 3.06, the module's C_TAN_ALL, which
+    tests/test_odd_law_cpu.py::test_tangent_restatement_against_50_digits_on_every_robot asserts."""
     from tests.kkt_certificate_restatement import distance
 
     P = q.cheetah_params(mu=0.6)
