@@ -32,14 +32,16 @@
  * OUT OF SCOPE: entrywise (nine-number) rotation tangents - the rotations move along the left tangents above only; tangents of
  * the handle's parameters (mu, fzmin, fzmax, the weights, the gains, mass, Ib, the kinematic model); tangents through the swing
  * pipeline (the swing legs' PD torques and the planner's references have their own calls below; the gait clock is held); weak activity (a row whose multiplier is about 0
- * is on the face like any other); commander mode (the desired state must be in `in`); a jvp on the torch.autograd.Functions of the
- * Python package.
+ * is on the face like any other); commander mode in THIS call (the desired state must be in `in`: qc_commander_step_tangent_batch,
+ * below, gives its tangents); a jvp on the torch.autograd.Functions of the Python package.
  *
  * The rigid-body plant step has its forward mode below, qc_plant_step_tangent_batch: with it the two calls chain, step after step,
  * into the tangent of a closed-loop rollout.  The loop around the complete tick - joint_q -> FK -> QP -> clamped J^T -> joint_tau ->
  * legged plant - chains qc_tangent_batch (joint_q_tan), qc_torque_tangent_batch, for a batch with swing references
  * qc_swing_torque_tangent_batch in place behind it, and qc_leg_plant_step_tangent_batch, all below.  With swing_state the references
- * themselves move: qc_swing_reference_tangent_batch, last in this header, is the forward mode of the planner and the trajectory. */
+ * themselves move: qc_swing_reference_tangent_batch is the forward mode of the planner and the trajectory.  The two stages a rollout
+ * is steered through close the header: qc_commander_step_tangent_batch (the twist command -> the desired state) and
+ * qc_com_reference_tangent_batch (the schedule of the lean -> x_d).  With them every differentiable stage has both modes. */
 #ifndef QC_TANGENT_H
 #define QC_TANGENT_H
 
@@ -179,7 +181,7 @@ int qc_torque_tangent_batch(qc_handle* h, size_t n, const qc_batch_in* in, const
  *
  * OUT OF SCOPE: tangents of the gains, of tau_min / tau_max and of the kinematic constants; the planner and the gait clock in THIS
  * call (swing_state and gait_dt are refused: qc_swing_reference_tangent_batch, below, gives swing_pos_tan / swing_vel_tan on the
- * references qc_swing_reference_batch returned); commander mode. */
+ * references qc_swing_reference_batch returned); commander mode (qc_commander_step_tangent_batch, below, is a call of its own). */
 typedef struct qc_swing_tangent_io {
   size_t struct_size;            /* = sizeof(qc_swing_tangent_io); checked                                            */
   size_t n_dir;                  /* K >= 1 directions per launch                                                      */
@@ -286,7 +288,8 @@ int qc_leg_plant_step_tangent_batch(qc_handle* h, size_t n, const qc_leg_plant_t
  * record's two tangents in one pair of buffers.  All pointers are device pointers.  No buffer is kept on the handle.
  *
  * OUT OF SCOPE: tangents of the phase, of gait_dt, of the periods, of swing_height and of planner_k; the commander step and the com
- * reference (qc_commander_step_batch, qc_com_reference_batch have no forward mode); parameter tangents. */
+ * reference in THIS call (their forward modes, qc_commander_step_tangent_batch and qc_com_reference_tangent_batch, are below);
+ * parameter tangents. */
 typedef struct qc_swing_reference_tangent_io {
   size_t struct_size;                         /* = sizeof(qc_swing_reference_tangent_io); checked                      */
   const struct qc_swing_state* state_before;  /* [n] the records before the forward call; required                     */
@@ -307,6 +310,125 @@ void qc_default_swing_reference_tangent(qc_swing_reference_tangent_io* io);
  * wrong struct_size, n_dir == 0, no tangent given at all, no output requested at all, a gait_dt, swing_pos or swing_vel in `in`,
  * `feet` without joint_q, a missing state_before, a missing Rwb, x, xdot, w, joint_q or gait_phase, or n * n_dir beyond one launch. */
 int qc_swing_reference_tangent_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_swing_reference_tangent_io* io, void* stream);
+
+/* qc_commander_step_tangent_batch - forward mode of qc_commander_step_batch (qc_balance.h), the map qc_commander_step_adjoint_batch
+ * transposes: from K tangents on the twist command, the held command, the pose and the record's desired state to the tangents of the
+ * desired state the QP and the planner are fed.  The contract is the adjoint's: nothing is saved by the forward launch; pass the same
+ * Rwb and x (`in`), twist, fresh and the three scalars (`cmd`; cmd->state is not read) and `state_before`, a copy of the records from
+ * BEFORE the forward call.  fresh / standing / running / pending / applied are recomputed as the forward kernel decides them and HELD.
+ *
+ * Per direction, in the symbols of qc_commander_step_adjoint_batch (v = vb[0:3], om = vb[3:6], d = cmd_dt om, Rb = Exp(d),
+ * t = cmd_dt Rb v, Y = Rz(yaw), (cy, sy) = (R00, R10) / h, u = v - x x om), delta = Rwb_rot_tan, dx = x_tan,
+ * dvb = fresh ? twist_tan : Vb_tan = (dv, dom):
+ *   always        Vb_next_tan = dvb
+ *   NOT applied   the four desired-state outputs are the four `_prev_` tangents, bit for bit; nothing else reaches them
+ *   applied       beta = Jl(d) cmd_dt dom                     (the left tangent of Rb)
+ *                 dt   = beta x t + cmd_dt Rb dv
+ *                 dpsi = (cy (delta_2 R00 - delta_0 R20) - sy (delta_1 R20 - delta_2 R10)) / h
+ *                 Rwb_d_rot_tan = dpsi e_z + Y beta
+ *                 x_d_tan = (dx_0 + g_0, dx_1 + g_1, 0),  g = dpsi e_z x (Y t) + Y dt      (the height is a constant)
+ *                 xdot_d_tan = Rwb^T (du - delta x u),  du = dv - dx x om - x x dom
+ *                 w_d_tan = Rwb^T (dom - delta x om)
+ * SMALL ANGLE, |d| < 1e-12, where the forward pass takes Rb = I: the SMOOTH function is differentiated, as the adjoint does - a
+ * yaw-rate tangent at zero rate is not silently zero.  Jl = I + B K + C K^2 by qc_plant_step_tangent_batch's coefficients: the series
+ * below |d|^2 = 1, the quotients from it on, Jl = I at |d| = 0.
+ *
+ * Rwb_d_rot_tan, x_d_tan, xdot_d_tan, w_d_tan are exactly what qc_tangent_batch and qc_swing_reference_tangent_batch take under those
+ * names (Rwb_d_rot_tan: the world-frame left tangent of Rwb_d).
+ *
+ * `flags` bit 0 is the adjoint's rule: a command is applied at the gimbal-lock branch (h == 0 or not finite below 1e300).  Every
+ * output row of that robot, in every direction, is NaN.  Other non-finite inputs propagate; nothing is clamped.  There are no tangents
+ * of stand_height, stand_tol or cmd_dt; the flags and latches are held.
+ *
+ * <G, [Rwb_d_rot_tan]x Rwb_d> + <a, x_d_tan> + <b, xdot_d_tan> + <c, w_d_tan> + <Vb_next_bar, Vb_next_tan> equals <twist_bar, twist_tan>
+ * + <Vb_bar, Vb_tan> + <Rwb_bar, [delta]x Rwb> + <x_bar, dx> + <Rwb_d_prev_bar, [Rwb_d_rot_prev_tan]x Rwb_d_prev> + <x_d_prev_bar,
+ * x_d_prev_tan> + <xdot_d_prev_bar, xdot_d_prev_tan> + <w_d_prev_bar, w_d_prev_tan> with the outputs of
+ * qc_commander_step_adjoint_batch (its `_in` arrays NULL; G = Rwb_d_bar, a = x_d_bar, b = xdot_d_bar, c = w_d_bar).
+ *
+ * A (direction, robot) pair reads every input before it writes and touches only its own rows: the four desired-state outputs may BE
+ * the four `_prev_` inputs and Vb_next_tan may BE Vb_tan - a rollout carries them in one set of buffers.  All pointers are device
+ * pointers.  No buffer is kept on the handle.
+ *
+ * OUT OF SCOPE: tangents of stand_height, stand_tol and cmd_dt; entrywise rotation tangents. */
+typedef struct qc_commander_step_tangent_io {
+  size_t struct_size;                             /* = sizeof(qc_commander_step_tangent_io); checked                   */
+  const struct qc_commander_state* state_before;  /* [n] the records before the forward call; required                 */
+  size_t n_dir;                                   /* K >= 1 directions per launch                                      */
+  /* tangents, direction-major as in qc_tangent_io; NULL = zero, at least one given                                   */
+  const double *twist_tan, *Vb_tan;               /* [K][n][6]; twist_tan only with cmd->twist                         */
+  const double *Rwb_rot_tan, *x_tan;              /* [K][n][3]; Rwb_rot_tan: Rwb <- exp([d]x) Rwb                      */
+  const double *Rwb_d_rot_prev_tan, *x_d_prev_tan, *xdot_d_prev_tan, *w_d_prev_tan;  /* [K][n][3] on the record before */
+  /* outputs, each optional, at least one given (flags counts)                                                        */
+  double *Rwb_d_rot_tan, *x_d_tan, *xdot_d_tan, *w_d_tan;  /* [K][n][3]                                                */
+  double* Vb_next_tan;                            /* [K][n][6] on the held command after the call                      */
+  int32_t* flags;                                 /* [n]: bit 0 - applied at gimbal lock, no derivative                */
+} qc_commander_step_tangent_io;
+/* struct_size set, pointers NULL, n_dir = 1. */
+void qc_default_commander_step_tangent(qc_commander_step_tangent_io* io);
+/* Asynchronous on `stream`, no host synchronisation (graph-capturable); n == 0 launches nothing and returns QC_OK.
+ * QC_ERR_INVALID (message starting with "qc_commander_step_tangent_batch:", nothing launched) for a null handle, `in`, `cmd` or `io`,
+ * a wrong struct_size of either record, n_dir == 0, no tangent given at all, no output requested at all, twist_tan without
+ * cmd->twist, `fresh` without `twist`, a stand_height, stand_tol (>= 0) or cmd_dt that is not finite, a missing state_before, Rwb or
+ * x, or n * n_dir beyond one launch. */
+int qc_commander_step_tangent_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_command_in* cmd,
+                                    const qc_commander_step_tangent_io* io, void* stream);
+
+/* qc_com_reference_tangent_batch - forward mode of qc_com_reference_batch (qc_balance.h), the map qc_com_reference_adjoint_batch
+ * transposes: the desired COM from the virtual support polygon, K tangents per launch.  It takes the same `in`, schedule,
+ * schedule_shared, mode and gain; nothing is saved by the forward launch.  The contact mask is HELD: a phase exactly on the stance /
+ * swing boundary gets the branch the forward pass took.
+ *
+ * Per direction, robot and leg l, with p_l the body-frame foot (`feet`, or the FK of joint_q), r_l = Rwb p_l, delta = Rwb_rot_tan,
+ * dx = x_tan, dphi = phase_tan, dsigma = schedule_tan, and a_i, d_i, e_i = exp(-a_i^2) / sqrt(pi), sgn those of
+ * qc_support_polygon_adjoint_batch:
+ *   dp_l = feet_tan_l + J(q_l) joint_q_tan_l                                         (as in qc_tangent_batch)
+ *   dP_l = (delta x r_l + Rwb dp_l + dx) in x and y
+ *   dw_l = sgn (e1 / d1 - e2 / d2) dphi_l - sum_i e_i a_i sqrt(2) / d_i dsigma_i     over the two widths the leg's branch reads
+ *   dzm = w dP + (1 - w) dP_m + (P - P_m) dw, dzp likewise;  with v = N / D: dv = (dN - v dD) / D, in the forward pass's own
+ *   summation order;  com_xy_tan = (((dv_FL + dv_FR) + dv_RL) + dv_RR) / 4
+ *   QC_COM_REPLACE   x_d_out_tan = (com_xy_tan, x_d_in_tan.z)
+ *   QC_COM_OFFSET    x_d_out_tan = x_d_in_tan + gain (com_xy_tan - (((dP_FL + dP_FR) + dP_RL) + dP_RR) / 4, 0)
+ * `gain` has no tangent.  With schedule_shared, schedule_tan is ONE [4][4] block per direction, [K][4][4].
+ *
+ * `flags` bit l: the forward rule, the reference's 0/0 at leg l's point.  A flagged robot gets NaN in every output row of every
+ * direction.  Other non-finite inputs propagate; nothing is clamped.
+ *
+ * <x_d_out_bar, x_d_out_tan> equals <x_d_in_bar, x_d_in_tan> + <feet_bar, dp> + <Rwb_bar, [delta]x Rwb> + <x_bar, dx> + <phase_bar,
+ * dphi> + <schedule_bar rows, dsigma> with the outputs of qc_com_reference_adjoint_batch (its `_in` arrays NULL); with a shared
+ * schedule_tan the last term is <schedule_bar_sum, dsigma> over the batch.  com_xy_tan in replace mode is the tangent of
+ * qc_support_polygon_batch's world-mode com_xy: there is no separate call for it.
+ *
+ * A (direction, robot) pair reads every input before it writes and touches only its own rows: x_d_out_tan may BE x_d_in_tan.  All
+ * pointers are device pointers.  No buffer is kept on the handle.
+ *
+ * OUT OF SCOPE: tangents of gain and of the phase through the clock; the body-frame polygon. */
+typedef struct qc_com_reference_tangent_io {
+  size_t struct_size;            /* = sizeof(qc_com_reference_tangent_io); checked                                    */
+  const double* schedule;        /* as the forward call's                                                             */
+  int32_t schedule_shared;
+  int32_t mode;
+  double gain;
+  size_t n_dir;                  /* K >= 1 directions per launch                                                      */
+  /* tangents, direction-major as in qc_tangent_io; NULL = zero, at least one given                                   */
+  const double* x_d_in_tan;      /* [K][n][3]                                                                         */
+  const double* feet_tan;        /* [K][n][4][3] body frame                                                           */
+  const double* joint_q_tan;     /* [K][n][12], only with in->joint_q                                                 */
+  const double *Rwb_rot_tan, *x_tan;  /* [K][n][3]                                                                    */
+  const double* phase_tan;       /* [K][n][4]                                                                         */
+  const double* schedule_tan;    /* [K][n][4][4], or [K][4][4] with schedule_shared                                   */
+  /* outputs, each optional, at least one given (flags counts)                                                        */
+  double* x_d_out_tan;           /* [K][n][3]; may be x_d_in_tan                                                      */
+  double* com_xy_tan;            /* [K][n][2] the polygon's own tangent                                               */
+  int32_t* flags;                /* [n]: bit l - leg l's point is 0/0, no derivative                                  */
+} qc_com_reference_tangent_io;
+/* struct_size set, mode = QC_COM_REPLACE, gain = 1, n_dir = 1, the rest zero. */
+void qc_default_com_reference_tangent(qc_com_reference_tangent_io* io);
+/* Asynchronous on `stream`, no host synchronisation (graph-capturable); n == 0 launches nothing and returns QC_OK.
+ * QC_ERR_INVALID (message starting with "qc_com_reference_tangent_batch:", nothing launched) for a null handle, `in` or `io`, a wrong
+ * struct_size, a gait_dt, swing_state, swing_pos or swing_vel in `in`, an unknown mode, a gain that is not finite, n_dir == 0, no
+ * tangent given at all, no output requested at all, joint_q_tan without in->joint_q, a missing schedule, gait_phase, feet / joint_q,
+ * Rwb or x, or n * n_dir beyond one launch. */
+int qc_com_reference_tangent_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_com_reference_tangent_io* io, void* stream);
 
 #ifdef __cplusplus
 }

@@ -2408,6 +2408,34 @@ int qc_swing_reference_tangent_batch(qc_handle* h, size_t n, const qc_batch_in* 
                      qc::SWING_REFERENCE_TANGENT_BLOCK, stream, h->d_params, (long)n, qc::swing_reference_tangent_constants(in, io));
 }
 
+void qc_default_commander_step_tangent(qc_commander_step_tangent_io* io) {
+  if (!zeroed(io)) return;
+  io->n_dir = 1;
+}
+
+int qc_commander_step_tangent_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_command_in* cmd, const qc_commander_step_tangent_io* io,
+                                    void* stream) {
+  if (const int rc = qc::check_commander_step_tangent_args(h, n, in, cmd, io); rc != QC_OK || n == 0) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  // (cmd->state is not read: the records are io->state_before)
+  return launch_flat(qc::commander_step_tangent_kernel, qc::command_tangent_blocks(n, qc::commander_step_tangent_dirs(io)), qc::COMMAND_TANGENT_BLOCK,
+                     stream, (long)n, qc::commander_step_tangent_constants(in, cmd, io));
+}
+
+void qc_default_com_reference_tangent(qc_com_reference_tangent_io* io) {
+  if (!zeroed(io)) return;
+  io->mode = QC_COM_REPLACE;
+  io->gain = 1.0;
+  io->n_dir = 1;
+}
+
+int qc_com_reference_tangent_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_com_reference_tangent_io* io, void* stream) {
+  if (const int rc = qc::check_com_reference_tangent_args(h, n, in, io); rc != QC_OK || n == 0) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  return launch_flat(qc::com_reference_tangent_kernel, qc::command_tangent_blocks(n, qc::com_reference_tangent_dirs(io)), qc::COMMAND_TANGENT_BLOCK,
+                     stream, h->d_params, (long)n, qc::com_reference_tangent_constants(in, io));
+}
+
 void qc_default_sensitivity_rot(qc_sensitivity_rot_io* io) { (void)zeroed(io); }
 
 int qc_sensitivity_rot_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_rot_io* io, void* stream) {

@@ -30,6 +30,7 @@
 #include "qc_torque_tangent.hpp"
 #include "qc_leg_plant_tangent.hpp"
 #include "qc_swing_reference_tangent.hpp"
+#include "qc_command_tangent.hpp"
 
 namespace qc {
 
@@ -1082,6 +1083,95 @@ inline SwingReferenceTangentArgs swing_reference_tangent_constants(const qc_batc
 // workgroups of swing_reference_tangent_kernel for n robots and K directions: one wave of pairs each, capped (a grid cap of its own)
 inline unsigned swing_reference_tangent_blocks(size_t n, size_t n_dir) {
   return capped_blocks(n * n_dir, SWING_REFERENCE_TANGENT_BLOCK, SWING_REFERENCE_TANGENT_MAX_BLOCKS);
+}
+
+// ---------------------------------------------------------------- qc_commander_step_tangent_batch
+// What is wrong with the call itself (message prefix "qc_commander_step_tangent_batch:").  The contract of `in` and `cmd` is
+// qc_commander_step_adjoint_batch's: what that call refuses about them is refused here in its words, but for the launch bound - one
+// lane per (direction, robot): the pairs must fit a launch.
+inline int check_commander_step_tangent_args(const qc_handle* h, size_t n, const qc_batch_in* in, const qc_command_in* cmd,
+                                             const qc_commander_step_tangent_io* io) {
+  const char* who = "qc_commander_step_tangent_batch";
+  if (const int rc = check_io(who, h && in && io, cmd, "qc_command_in", "qc_default_command"); rc != QC_OK) return rc;
+  if (const int rc = check_io(who, true, io, "qc_commander_step_tangent_io", "qc_default_commander_step_tangent"); rc != QC_OK) return rc;
+  const char* own = nullptr;
+  if (io->n_dir == 0) own = ": n_dir must be >= 1";
+  else if (!io->twist_tan && !io->Vb_tan && !io->Rwb_rot_tan && !io->x_tan && !io->Rwb_d_rot_prev_tan && !io->x_d_prev_tan && !io->xdot_d_prev_tan &&
+           !io->w_d_prev_tan)
+    own = ": no tangent given (twist_tan, Vb_tan, Rwb_rot_tan, x_tan, Rwb_d_rot_prev_tan, x_d_prev_tan, xdot_d_prev_tan, w_d_prev_tan are all NULL)";
+  else if (!io->Rwb_d_rot_tan && !io->x_d_tan && !io->xdot_d_tan && !io->w_d_tan && !io->Vb_next_tan && !io->flags)
+    own = ": no output requested (Rwb_d_rot_tan, x_d_tan, xdot_d_tan, w_d_tan, Vb_next_tan, flags are all NULL)";
+  else if (io->twist_tan && !cmd->twist)
+    own = ": twist_tan needs qc_command_in.twist";
+  if (const int rc = check_commander_step_batch(who, n, in, cmd, own, io->state_before != nullptr,
+                                                ": state_before is required (the commander records from before the forward call)");
+      rc != QC_OK || n == 0)
+    return rc;
+  static_assert(COMMAND_TANGENT_BLOCK == SENSITIVITY_BLOCK, "n itself was bounded by the shared check");
+  if (io->n_dir > (size_t)0xFFFFFF * (size_t)COMMAND_TANGENT_BLOCK / n)
+    return fail(QC_ERR_INVALID, std::string(who) + ": n * n_dir is beyond one launch");
+  return QC_OK;
+}
+
+// the directions the kernel walks: the flags come from the held decisions alone, so a call that asks for nothing else walks one
+inline size_t commander_step_tangent_dirs(const qc_commander_step_tangent_io* io) {
+  return (io->Rwb_d_rot_tan || io->x_d_tan || io->xdot_d_tan || io->w_d_tan || io->Vb_next_tan) ? io->n_dir : 1;
+}
+
+// the kernel's arguments: what the adjoint reads of `in` and `cmd`, the record's arrays
+inline CommanderStepTangentArgs commander_step_tangent_constants(const qc_batch_in* in, const qc_command_in* cmd, const qc_commander_step_tangent_io* io) {
+  return CommanderStepTangentArgs{in->Rwb, in->x, cmd->twist, cmd->fresh, reinterpret_cast<const CmdState*>(io->state_before), cmd->stand_height,
+                                  cmd->stand_tol, cmd->cmd_dt, (long)commander_step_tangent_dirs(io), io->twist_tan, io->Vb_tan, io->Rwb_rot_tan,
+                                  io->x_tan, io->Rwb_d_rot_prev_tan, io->x_d_prev_tan, io->xdot_d_prev_tan, io->w_d_prev_tan, io->Rwb_d_rot_tan,
+                                  io->x_d_tan, io->xdot_d_tan, io->w_d_tan, io->Vb_next_tan, io->flags};
+}
+
+// workgroups of the two kernels of qc_command_tangent.hpp for n robots and K directions: one wave of pairs each, capped
+inline unsigned command_tangent_blocks(size_t n, size_t n_dir) { return capped_blocks(n * n_dir, COMMAND_TANGENT_BLOCK, COMMAND_TANGENT_MAX_BLOCKS); }
+
+// ---------------------------------------------------------------- qc_com_reference_tangent_batch
+// What is wrong with the call itself (message prefix "qc_com_reference_tangent_batch:"): qc_com_reference_adjoint_batch's refusals
+// about `in`, the mode, the gain and the schedule in its words, the tangent's own about its arrays in their place, and the launch bound
+// on the pairs.
+inline int check_com_reference_tangent_args(const qc_handle* h, size_t n, const qc_batch_in* in, const qc_com_reference_tangent_io* io) {
+  const char* who = "qc_com_reference_tangent_batch";
+  if (const int rc = check_io(who, h && in, io, "qc_com_reference_tangent_io", "qc_default_com_reference_tangent"); rc != QC_OK) return rc;
+  const char* own = check_com_mode(io->mode, io->gain);
+  if (own) {
+  } else if (io->n_dir == 0) own = ": n_dir must be >= 1";
+  else if (!io->x_d_in_tan && !io->feet_tan && !io->joint_q_tan && !io->Rwb_rot_tan && !io->x_tan && !io->phase_tan && !io->schedule_tan)
+    own = ": no tangent given (x_d_in_tan, feet_tan, joint_q_tan, Rwb_rot_tan, x_tan, phase_tan, schedule_tan are all NULL)";
+  else if (!io->x_d_out_tan && !io->com_xy_tan && !io->flags)
+    own = ": no output requested (x_d_out_tan, com_xy_tan, flags are all NULL)";
+  else if (io->joint_q_tan && !in->joint_q)
+    own = ": joint_q_tan needs in->joint_q";
+  if (const int rc = check_com_reference_batch(who, n, in, own, io->schedule); rc != QC_OK || n == 0) return rc;
+  static_assert(COMMAND_TANGENT_BLOCK == SENSITIVITY_BLOCK, "n itself was bounded by the shared check");
+  if (io->n_dir > (size_t)0xFFFFFF * (size_t)COMMAND_TANGENT_BLOCK / n)
+    return fail(QC_ERR_INVALID, std::string(who) + ": n * n_dir is beyond one launch");
+  return QC_OK;
+}
+
+inline size_t com_reference_tangent_dirs(const qc_com_reference_tangent_io* io) { return (io->x_d_out_tan || io->com_xy_tan) ? io->n_dir : 1; }
+
+// the kernel's arguments: SupportIn as the forward call packs it (world mode), the tangents
+inline ComReferenceTangentArgs com_reference_tangent_constants(const qc_batch_in* in, const qc_com_reference_tangent_io* io) {
+  ComReferenceTangentArgs a{};
+  static_cast<SupportIn&>(a) = support_in(in, io->schedule, io->schedule_shared, true);
+  a.mode = io->mode;
+  a.gain = io->gain;
+  a.n_dir = (long)com_reference_tangent_dirs(io);
+  a.x_d_in_tan = io->x_d_in_tan;
+  a.feet_tan = io->feet_tan;
+  a.joint_q_tan = io->joint_q_tan;
+  a.Rwb_rot_tan = io->Rwb_rot_tan;
+  a.x_tan = io->x_tan;
+  a.phase_tan = io->phase_tan;
+  a.schedule_tan = io->schedule_tan;
+  a.x_d_out_tan = io->x_d_out_tan;
+  a.com_xy_tan = io->com_xy_tan;
+  a.flags = io->flags;
+  return a;
 }
 
 }  // namespace qc

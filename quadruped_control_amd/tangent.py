@@ -22,8 +22,17 @@ rollout_gait_transition() its 60 x 60 matrix: the 36 coordinates of the tick and
 The functions take the controller as their first argument, as autograd.py's do.  The symbols of the library are bound here, on
 the CDLL that _lib.load() returns, with this module's own ctypes records: _lib.EXPORTS and BalanceController are not touched.
 
-Not covered: tangents of the gait clock (the phases, the contact mask and the plan decisions are held), commander mode, the com
-reference (`lean`), tangents of the handle's parameters, and a jvp on the torch.autograd.Functions of autograd.py."""
+The two stages a rollout is steered through have theirs: commander_step_tangent() (qc_commander_step_tangent_batch) - the twist
+command, the held command, the pose and the record's desired state to the desired state the QP and the planner are fed - and
+com_reference_tangent() (qc_com_reference_tangent_batch) - the feet, the pose, the phases and the schedule of the lean to x_d; both in
+csrc/qc_command_tangent.hpp.
+
+rollout_commander_tangent() - the forward-mode twin of ctl.rollout_tick(batch, command, ...) and of
+rollout_commander_autograd() - and rollout_lean_tangent() - that of ctl.rollout_tick(batch, None, ..., lean=...) and of
+rollout_gait_autograd(lean=...) - chain them in front of rollout_gait_tangent()'s step.
+
+Not covered: tangents of the gait clock (the phases, the contact mask and the plan decisions are held), tangents of the handle's
+parameters, and a jvp on the torch.autograd.Functions of autograd.py."""
 from __future__ import annotations
 
 import ctypes as C
@@ -84,6 +93,25 @@ ROLLOUT_GAIT_TANGENTS = {**ROLLOUT_TICK_TANGENTS, **{k: 12 for k in _GAIT_RECORD
 GAIT_TRANSITION_COLUMNS = TICK_TRANSITION_COLUMNS + tuple((name, c) for name in ("p_start", "p_final") for c in range(12))
 REFERENCE_FLAGS_SHIFT = 20  # rollout_gait_tangent()'s flags: rollout_swing_tangent()'s word | swing_reference_tangent()'s bits << 20
 
+# the commander step (qc_commander_step_tangent_io) and the com reference (qc_com_reference_tangent_io): the records' tangents and
+# outputs in their order
+COMMANDER_STEP_TANGENTS = {"twist_tan": 6, "Vb_tan": 6, "Rwb_rot_tan": 3, "x_tan": 3, "Rwb_d_rot_prev_tan": 3, "x_d_prev_tan": 3, "xdot_d_prev_tan": 3,
+                           "w_d_prev_tan": 3}
+_COMMANDER_STEP_TANGENT_OUTPUTS = {**{k: ((3,), "float64") for k in ("Rwb_d_rot_tan", "x_d_tan", "xdot_d_tan", "w_d_tan")}, "Vb_next_tan": ((6,), "float64")}
+COMMANDER_STEP_TANGENT_WANT = tuple(_COMMANDER_STEP_TANGENT_OUTPUTS)
+COM_REFERENCE_TANGENTS = {"x_d_in_tan": 3, "feet_tan": 12, "joint_q_tan": 12, "Rwb_rot_tan": 3, "x_tan": 3, "phase_tan": 4, "schedule_tan": 16}
+_COM_REFERENCE_TANGENT_OUTPUTS = {"x_d_out_tan": ((3,), "float64"), "com_xy_tan": ((2,), "float64")}
+
+
+class QcCommanderStepTangentIo(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("state_before", C.c_void_p), ("n_dir", C.c_size_t)] + \
+               [(k, C.c_void_p) for k in tuple(COMMANDER_STEP_TANGENTS) + COMMANDER_STEP_TANGENT_WANT + ("flags",)]
+
+
+class QcComReferenceTangentIo(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("schedule", C.c_void_p), ("schedule_shared", C.c_int32), ("mode", C.c_int32), ("gain", C.c_double),
+                ("n_dir", C.c_size_t)] + [(k, C.c_void_p) for k in tuple(COM_REFERENCE_TANGENTS) + tuple(_COM_REFERENCE_TANGENT_OUTPUTS) + ("flags",)]
+
 
 class QcSwingReferenceTangentIo(C.Structure):
     _fields_ = [("struct_size", C.c_size_t), ("state_before", C.c_void_p), ("n_dir", C.c_size_t)] + \
@@ -126,7 +154,9 @@ def _library():
         lib = _lib.load()
         for name in ("qc_default_tangent", "qc_tangent_batch", "qc_default_plant_tangent", "qc_plant_step_tangent_batch", "qc_default_torque_tangent",
                      "qc_torque_tangent_batch", "qc_default_leg_plant_tangent", "qc_leg_plant_step_tangent_batch", "qc_default_swing_tangent",
-                     "qc_swing_torque_tangent_batch", "qc_default_swing_reference_tangent", "qc_swing_reference_tangent_batch"):
+                     "qc_swing_torque_tangent_batch", "qc_default_swing_reference_tangent", "qc_swing_reference_tangent_batch",
+                     "qc_default_commander_step_tangent", "qc_commander_step_tangent_batch", "qc_default_com_reference_tangent",
+                     "qc_com_reference_tangent_batch"):
             if not hasattr(lib, name):
                 raise ImportError(f"{_lib.LIB_PATH} does not export {name}")
         lib.qc_default_tangent.argtypes = [C.POINTER(QcTangentIo)]
@@ -153,6 +183,15 @@ def _library():
         lib.qc_default_swing_reference_tangent.restype = None
         lib.qc_swing_reference_tangent_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(_lib.QcBatchIn), C.POINTER(QcSwingReferenceTangentIo), C.c_void_p]
         lib.qc_swing_reference_tangent_batch.restype = C.c_int
+        lib.qc_default_commander_step_tangent.argtypes = [C.POINTER(QcCommanderStepTangentIo)]
+        lib.qc_default_commander_step_tangent.restype = None
+        lib.qc_commander_step_tangent_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(_lib.QcBatchIn), C.POINTER(_lib.QcCommandIn),
+                                                        C.POINTER(QcCommanderStepTangentIo), C.c_void_p]
+        lib.qc_commander_step_tangent_batch.restype = C.c_int
+        lib.qc_default_com_reference_tangent.argtypes = [C.POINTER(QcComReferenceTangentIo)]
+        lib.qc_default_com_reference_tangent.restype = None
+        lib.qc_com_reference_tangent_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(_lib.QcBatchIn), C.POINTER(QcComReferenceTangentIo), C.c_void_p]
+        lib.qc_com_reference_tangent_batch.restype = C.c_int
         _bound = lib
     return _bound
 
@@ -535,8 +574,9 @@ def rollout_tick_tangent(ctl, batch, steps, dt, leg_inertia, tangents, act_tol=1
     one-sided face, bit 1: a bad pivot), bits 8-15 the plant's shifted left by 8 (bit 8 + l: J(q_l) singular, bit 12 + l: leg l out
     of reach or J singular after the step).  The derivative is the one on the active face of every solve at `act_tol`, at every
     tick's torque clamp mask and off the plant's flagged legs, as rollout_tick_autograd()'s.  Tangent memory is one set of buffers
-    whatever `steps` is.  ValueError for swing references (swing_state, swing_pos, swing_vel), gait_dt, `lean` and a `command`: the
-    swing pipeline, the gait clock and commander mode have no forward mode."""
+    whatever `steps` is.  ValueError for swing references (swing_state, swing_pos, swing_vel), gait_dt, `lean` and a `command` - in THIS
+    rollout: rollout_swing_tangent() and rollout_gait_tangent() take the swing pipeline, rollout_commander_tangent() a `command` and
+    rollout_lean_tangent() a `lean`."""
     who = "rollout_tick_tangent"
     if command is not None:
         raise ValueError(f"{who}: commander mode has no forward mode - command must be None (the desired state is held in the batch)")
@@ -551,14 +591,20 @@ def rollout_tick_tangent(ctl, batch, steps, dt, leg_inertia, tangents, act_tol=1
     return _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, ROLLOUT_TICK_TANGENTS, act_tol, warm, stream, False)
 
 
-def _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, table, act_tol, warm, stream, swings, clock=None):
+def _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, table, act_tol, warm, stream, swings, clock=None, hook=None, lead=None):
     """What rollout_tick_tangent(), rollout_swing_tangent() and rollout_gait_tangent() share, behind their own refusals: the tangents
     validated against `table`, one set of buffers, every launch planned once, the step loop.  swings=False launches exactly what
     rollout_tick_tangent() always did; swings=True hands the whole batch to the tick (joint_qdot and the two references with it, as
     ctl.rollout_tick() does) and adds swing_torque_tangent() in place on joint_tau_tan behind torque_tangent(), its flags at
     SWING_FLAGS_SHIFT.  `clock` (float64 [n], with swings=True): the references are made per step - a copy of the records,
     swing_reference_batch() with `clock` as its gait_dt and swing_reference_tangent() in front of the tick, which reads the references
-    and the phases they left; the record's two tangents are carried in place, the flags land at REFERENCE_FLAGS_SHIFT."""
+    and the phases they left; the record's two tangents are carried in place, the flags land at REFERENCE_FLAGS_SHIFT.
+    `hook` (rollout_commander_tangent(), rollout_lean_tangent()): hook(ctl, who, batch, n, K, dev, buf, given, stream) is called once,
+    behind the buffers, and returns an object whose step(k) is launched in front of every step - it rewrites the desired state the tick
+    reads (`desired`: name -> tensor, laid over the batch) and the desired-state tangent buffers (`held`: name -> [K,n,3], in place of
+    the held ones) -, whose flags(word) ORs its own bits into the rollout's word after the step's launches and whose `res` joins the
+    result; the tangents the hook takes itself are not in `tangents`, `lead` = (K, squeeze) is their form.  Without a hook nothing here
+    launches, reads or allocates anything it did not before."""
     import contextlib
 
     import torch
@@ -572,7 +618,11 @@ def _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, table,
     n = batch["x"].shape[0]
     dev = torch.device("cuda", ctl.device)
     given, K, squeeze = _directions(tangents, table, n, dev)
-    if not given:
+    if lead is not None:
+        if given and (K, squeeze) != tuple(lead):
+            raise ValueError(f"{who}: the tangents must agree on the number of directions and on the [n, ...] / [K, n, ...] form")
+        K, squeeze = lead
+    elif not given:
         raise ValueError(f"{who}: no tangent given")
     shape = lambda m: (K, n) + ((4, 3) if m == 12 else (3,))
     on_stream = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
@@ -590,7 +640,11 @@ def _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, table,
             pos, vel = (torch.zeros((n, 4, 3), dtype=torch.float64, device=dev) for _ in range(2))
             ref_flags = torch.zeros((n,), dtype=torch.int32, device=dev)
             before = torch.empty_like(batch["swing_state"])
+    h = hook(ctl, who, batch, n, K, dev, buf, given, stream) if hook is not None else None
     held = {k: given[k].reshape(K, n, 3) for k in _ROLLOUT_HELD if k in given}
+    if h is not None:  # the desired state of a step is made by the hook: its arrays over the batch's, its tangent buffers over the held ones
+        held = dict(held, **h.held)
+        batch = dict(batch, **h.desired)
     names = ("Rwb", "x", "xdot", "w", "joint_q", "joint_qdot")
     state = {k: batch[k] for k in names}
     # as rollout_tick(): a tick without swing references takes no joint_qdot
@@ -630,6 +684,8 @@ def _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, table,
                        "flags": ref_flags}
             reference_tan, _, _ = plan_swing_reference_tangent(ctl, reads, before, ref_in, tuple(ref_out), ref_out, stream)
         for k in range(steps):
+            if h is not None:
+                h.step(k)
             if reference is not None:
                 with on_stream:
                     before.copy_(batch["swing_state"])
@@ -647,10 +703,14 @@ def _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, table,
                     flags.bitwise_or_(swing_flags.bitwise_left_shift(SWING_FLAGS_SHIFT))
                 if reference is not None:
                     flags.bitwise_or_(ref_flags.bitwise_left_shift(REFERENCE_FLAGS_SHIFT))
+                if h is not None:
+                    h.flags(flags)
             step()
     res = dict(buf, grf_tan=grf_tan, joint_tau_tan=tau_tan)
     if clock is not None:
         res.update(rec, swing_pos_tan=pos_tan, swing_vel_tan=vel_tan)
+    if h is not None:
+        res.update(h.res)
     res = {k: (v[0] if squeeze else v) for k, v in res.items()}
     res["flags"] = flags
     return state, res
@@ -798,8 +858,8 @@ def rollout_swing_tangent(ctl, batch, steps, dt, leg_inertia, tangents, act_tol=
     bits shifted left by SWING_FLAGS_SHIFT = 16: bit 16 + l, swing leg l's reference had no derivative at some step (its torque
     tangent, and what follows from it, is NaN).  The derivative is the one on the active face of every solve at `act_tol` and at
     every tick's clamp masks, as rollout_tick_autograd()'s.  Tangent memory is one set of buffers whatever `steps` is.  ValueError for
-    swing_state, gait_dt, a `command`, `lean`, and for a batch with only one of swing_pos / swing_vel (or neither): the planner, the
-    gait clock and commander mode have no forward mode."""
+    swing_state, gait_dt, a `command`, `lean`, and for a batch with only one of swing_pos / swing_vel (or neither) - in THIS rollout:
+    rollout_gait_tangent() takes the planner, rollout_commander_tangent() a `command` and rollout_lean_tangent() a `lean`."""
     who = "rollout_swing_tangent"
     _swing_rollout_refusals(who, batch, command, lean)
     return _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, ROLLOUT_SWING_TANGENTS, act_tol, warm, stream, True)
@@ -918,8 +978,8 @@ def rollout_gait_tangent(ctl, batch, steps, dt, leg_inertia, gait_dt, tangents, 
     REFERENCE_FLAGS_SHIFT = 20: bit 20 + l, leg l was replanned at an x_z that is not finite and > 0 at some step.  The clock, the
     contact mask and the plan decisions are held, as in rollout_gait_autograd(); the derivative is the one on the active face of
     every solve at `act_tol` and at every tick's clamp masks.  Tangent memory is one set of buffers whatever `steps` is.  ValueError
-    for `lean` (the com reference has no forward mode), a `stance` mask, swing_pos / swing_vel, a gait_dt inside the batch, `feet`, and
-    a batch without joint_q, joint_qdot, gait_phase or swing_state."""
+    for `lean` (rollout_lean_tangent() is this rollout with the lean; rollout_commander_tangent() takes a `command`), a `stance` mask,
+    swing_pos / swing_vel, a gait_dt inside the batch, `feet`, and a batch without joint_q, joint_qdot, gait_phase or swing_state."""
     import torch
 
     who = "rollout_gait_tangent"
@@ -947,3 +1007,373 @@ def rollout_gait_transition(ctl, batch, steps, dt, leg_inertia, gait_dt, act_tol
 
     return _tick_transition(who, rollout, ctl, batch, steps, dt, leg_inertia, act_tol, warm, chunk, stream, GAIT_TRANSITION_COLUMNS,
                             _TICK_STATE + _GAIT_RECORD, ("gait_phase", "swing_state"))
+
+
+# ------------------------------------------------------------------ forward mode through the command and the lean
+def plan_commander_step_tangent(ctl, batch, command, state_before, tangents, want=COMMANDER_STEP_TANGENT_WANT, out=None, stream=None):
+    """commander_step_tangent() marshalled once: returns (launch, out, squeeze), `launch()` being one qc_commander_step_tangent_batch
+    call (graph-capturable) on tensors that are read in place; `out` holds [K, n, ...] tensors (and "flags" int32 [n] where asked for)
+    and squeeze says whether the tangents came as [n, ...].  The four desired-state outputs may be the four `_prev_` tangents and
+    out["Vb_next_tan"] may be tangents["Vb_tan"] (the aliasing contract of include/qc_tangent.h).  Planning launches nothing."""
+    from .balance_controller import _COMMANDER_STEP_FIELDS, _record_tensor
+
+    _library()
+    unknown = [k for k in tangents if k not in COMMANDER_STEP_TANGENTS]
+    if unknown:
+        raise ValueError(f"commander_step_tangent: unknown tangent(s) {unknown}; the tangents are {tuple(COMMANDER_STEP_TANGENTS)}")
+    io = QcCommanderStepTangentIo()
+    ctl._lib.qc_default_commander_step_tangent(C.byref(io))
+    sizing = [batch.get("x"), batch.get("Rwb")] + [t for t in tangents.values() if t is not None and t.dim() == 2]
+    n, dev, bi = ctl._readonly_batch("commander_step_tangent", batch, _COMMANDER_STEP_FIELDS, io, [], sizing, "neither x nor Rwb is there to size the call")
+    c = ctl._marshal_command(n, command, False)  # (the records it reads are state_before)
+    if _record_tensor("state_before", state_before, n, COMMANDER_STATE_DTYPE.itemsize, dev):  # (a missing one is the library's refusal)
+        io.state_before = state_before.data_ptr()
+    given, K, squeeze = _directions(tangents, COMMANDER_STEP_TANGENTS, n, dev, io)
+    io.n_dir = K
+    rows = tuple(w for w in want if w != "flags")
+    extra = [("flags", (n,), "int32")] if "flags" in want else []
+    res = _outputs("commander_step_tangent", _COMMANDER_STEP_TANGENT_OUTPUTS, rows, out, K * n, dev, io, extra)
+    res = {k: (v if k == "flags" else v.view((K, n) + _COMMANDER_STEP_TANGENT_OUTPUTS[k][0])) for k, v in res.items()}
+    launch = ctl._launcher("qc_commander_step_tangent_batch", (n, C.byref(bi), C.byref(c), C.byref(io), ctl._stream_ptr(stream)),
+                           (batch, command, state_before, given, res, bi, c, io), ValueError)
+    return launch, res, squeeze
+
+
+def commander_step_tangent(ctl, batch, command, state_before, tangents, want=COMMANDER_STEP_TANGENT_WANT, out=None, stream=None):
+    """Forward mode of ctl.commander_step_batch() (qc_commander_step_tangent_batch, include/qc_tangent.h; INTEGRATION.md "Forward mode
+    through the command and the lean"), the map ctl.commander_step_adjoint_batch() transposes, under that call's contract: `batch`: Rwb
+    and x as the forward call read them; `command`: its twist, fresh and scalars (its records are not read); `state_before`: a copy of
+    the record tensor from BEFORE the forward call - the latches and branch decisions are recomputed from it and held.  `tangents`: a
+    dict with any of "twist_tan", "Vb_tan" [n,6] (the command that arrives, the command that is held: `fresh` says which one a robot
+    reads), "Rwb_rot_tan" (the world-frame left tangent, Rwb <- exp([d]x) Rwb), "x_tan" and, on the record's desired state before the
+    call, "Rwb_d_rot_prev_tan", "x_d_prev_tan", "xdot_d_prev_tan", "w_d_prev_tan" ([n,3]) - each [n, ...] for one direction or
+    [K, n, ...] for K, all agreeing on K; a missing one is zero, at least one given.  `want`: any of "Rwb_d_rot_tan", "x_d_tan",
+    "xdot_d_tan", "w_d_tan" [K,n,3] - what tangent_batch() and swing_reference_tangent() take under those names -, "Vb_next_tan" [K,n,6]
+    and "flags" int32 [n].  A robot whose command is not applied passes the four `_prev_` tangents through bit for bit; where one is
+    applied with zero angular rate the smooth limit of the rotation's derivative is used, so a yaw-rate seed is not silently lost;
+    x_d_tan's z is exactly 0 there (the stand height is a constant).  flags bit 0: a command applied at gimbal lock - NaN in every row
+    of the robot, in every direction.  Returns the dict of device tensors, squeezed to [n, ...] where the tangents came that way; `out`:
+    a dict of tensors to write into (the aliasing contract: plan_commander_step_tangent()).  Nothing of `batch`, `command` or
+    `state_before` is written.  Asynchronous on `stream`, no synchronisation.  ValueError with the library's message for a call it
+    refuses.  Not covered: tangents of stand_height, stand_tol and cmd_dt."""
+    launch, res, squeeze = plan_commander_step_tangent(ctl, batch, command, state_before, tangents, want, out, stream)
+    launch()
+    return {k: (v[0] if squeeze and k != "flags" else v) for k, v in res.items()}
+
+
+def plan_com_reference_tangent(ctl, batch, schedule, x_d_in, tangents, mode="replace", gain=1.0, want=("x_d_out_tan",), out=None, stream=None):
+    """com_reference_tangent() marshalled once: returns (launch, out, squeeze), `launch()` being one qc_com_reference_tangent_batch
+    call (graph-capturable) on tensors that are read in place; `out` holds [K, n, ...] tensors (and "flags" int32 [n] where asked for)
+    and squeeze says whether the tangents came as [n, ...].  out["x_d_out_tan"] may be tangents["x_d_in_tan"].  `x_d_in` is not read by
+    the derivative (the map is affine in it) and not looked at; it is taken for the symmetry with com_reference_batch() and may be None.  Planning
+    launches nothing."""
+    import torch
+
+    from .balance_controller import _SUPPORT_POLYGON_FIELDS
+
+    _library()
+    if mode not in _lib.COM_MODES:
+        raise ValueError(f"com_reference_tangent: mode is one of {tuple(_lib.COM_MODES)}, not {mode!r}")
+    unknown = [k for k in tangents if k not in COM_REFERENCE_TANGENTS]
+    if unknown:
+        raise ValueError(f"com_reference_tangent: unknown tangent(s) {unknown}; the tangents are {tuple(COM_REFERENCE_TANGENTS)}")
+    io = QcComReferenceTangentIo()
+    ctl._lib.qc_default_com_reference_tangent(C.byref(io))
+    n, dev, bi = ctl._readonly_batch("com_reference_tangent", batch, _SUPPORT_POLYGON_FIELDS, io, [], [batch.get(k) for k in ("gait_phase", "feet", "joint_q")],
+                                     "the batch holds neither gait_phase nor feet nor joint_q")
+    if batch.get("swing_state") is not None:  # (handed over unchecked: the library names its refusal)
+        bi.swing_state = batch["swing_state"].data_ptr()
+    shared = False
+    if schedule is not None:
+        shared = schedule.dim() == 2
+        if schedule.dtype != torch.float64 or not schedule.is_contiguous() or schedule.device != dev or tuple(schedule.shape) != ((4, 4) if shared else (n, 4, 4)):
+            raise ValueError(f"schedule: need contiguous float64 [4,4] (shared) or [{n},4,4] on {dev}")
+        io.schedule, io.schedule_shared = schedule.data_ptr(), int(shared)
+    io.mode, io.gain = _lib.COM_MODES[mode], float(gain)
+    # a shared schedule's tangent is one [4,4] block per direction: [4,4] (squeezed) or [K,4,4]
+    rows = {k: t for k, t in tangents.items() if not (shared and k == "schedule_tan")}
+    given, K, squeeze = _directions(rows, COM_REFERENCE_TANGENTS, n, dev, io)
+    st = tangents.get("schedule_tan") if shared else None
+    if st is not None:
+        flat = st.dim() == 2
+        if st.dtype != torch.float64 or not st.is_contiguous() or st.device != dev or tuple(st.shape[-2:]) != (4, 4) or st.dim() not in (2, 3):
+            raise ValueError(f"schedule_tan: with a shared schedule, need contiguous float64 [4,4] or [K,4,4] on {dev}")
+        lead = 1 if flat else st.shape[0]
+        if given and (lead != K or flat != squeeze):
+            raise ValueError("schedule_tan: the tangents must agree on the number of directions and on the squeezed / [K, ...] form")
+        K, squeeze = lead, flat
+        io.schedule_tan = st.data_ptr()
+        given = dict(given, schedule_tan=st)
+    io.n_dir = K
+    names = tuple(w for w in want if w != "flags")
+    extra = [("flags", (n,), "int32")] if "flags" in want else []
+    res = _outputs("com_reference_tangent", _COM_REFERENCE_TANGENT_OUTPUTS, names, out, K * n, dev, io, extra)
+    res = {k: (v if k == "flags" else v.view((K, n) + _COM_REFERENCE_TANGENT_OUTPUTS[k][0])) for k, v in res.items()}
+    launch = ctl._launcher("qc_com_reference_tangent_batch", (n, C.byref(bi), C.byref(io), ctl._stream_ptr(stream)),
+                           (batch, schedule, x_d_in, given, res, bi, io), ValueError)
+    return launch, res, squeeze
+
+
+def com_reference_tangent(ctl, batch, schedule, x_d_in, tangents, mode="replace", gain=1.0, want=("x_d_out_tan",), out=None, stream=None):
+    """Forward mode of ctl.com_reference_batch() (qc_com_reference_tangent_batch, include/qc_tangent.h; INTEGRATION.md "Forward mode
+    through the command and the lean"), the map ctl.com_reference_adjoint_batch() transposes.  `batch`, `schedule`, `mode`, `gain`: the
+    forward call's - nothing was saved; the contact mask is held.  `tangents`: a dict with any of "x_d_in_tan" [n,3], "feet_tan" [n,4,3]
+    (body frame), "joint_q_tan" [n,12] (only for a batch with joint_q; added through the leg Jacobian), "Rwb_rot_tan" (the world-frame
+    left tangent), "x_tan" [n,3], "phase_tan" [n,4] and "schedule_tan" - [n,4,4], or with a shared [4,4] schedule ONE block per
+    direction, [4,4] / [K,4,4] - each [n, ...] for one direction or [K, n, ...] for K, all agreeing; a missing one is zero, at least one
+    given.  `want`: any of "x_d_out_tan" [K,n,3] - replace: (com_xy_tan, x_d_in_tan.z); offset: x_d_in_tan + gain (com_xy_tan - the
+    centroid's tangent, 0) -, "com_xy_tan" [K,n,2] (the polygon's own tangent: support_polygon_batch(world=True)'s) and "flags" int32
+    [n] (bit l: the reference's 0/0 at leg l's point - NaN in every row of the robot, in every direction).  Returns the dict of device
+    tensors, squeezed where the tangents came that way; `out`: a dict of tensors to write into - x_d_out_tan may be x_d_in_tan.
+    Nothing of `batch` is written.  Asynchronous on `stream`, no synchronisation.  ValueError with the library's message for a call it
+    refuses.  Not covered: a tangent of `gain`, and of the phase through the clock."""
+    launch, res, squeeze = plan_com_reference_tangent(ctl, batch, schedule, x_d_in, tangents, mode, gain, want, out, stream)
+    launch()
+    return {k: (v[0] if squeeze and k != "flags" else v) for k, v in res.items()}
+
+
+# ------------------------------------------------------------------ the rollouts through the command and the lean
+COMMANDER_FLAGS_SHIFT = 24  # rollout_commander_tangent()'s flags: rollout_gait_tangent()'s word | commander_step_tangent()'s bit << 24
+LEAN_FLAGS_SHIFT = 25       # ... | com_reference_tangent()'s four bits << 25 (rollout_lean_tangent() too)
+_COMMANDER_CARRIED = {"Rwb_d_rot_tan": "Rwb_d_rot_prev_tan", "x_d_tan": "x_d_prev_tan", "xdot_d_tan": "xdot_d_prev_tan", "w_d_tan": "w_d_prev_tan"}
+ROLLOUT_LEAN_TANGENTS = {**ROLLOUT_GAIT_TANGENTS, "schedule_tan": 16}
+ROLLOUT_COMMANDER_TANGENTS = {**ROLLOUT_GAIT_TANGENTS, "twist_tan": 6, "Vb_tan": 6, "schedule_tan": 16}
+
+
+def _lead_tangent(who, name, t, inner, n, dev):
+    """A tangent the hooks take themselves - `inner`: its shape for one direction, e.g. (n, 6), (steps, n, 6) or (4, 4) - as
+    ([K, *inner] contiguous view, K, squeeze), or None."""
+    import torch
+
+    if t is None:
+        return None
+    inner = tuple(inner)
+    if t.dtype != torch.float64 or not t.is_contiguous() or t.device != dev or tuple(t.shape) not in (inner, tuple(t.shape[:1]) + inner):
+        raise ValueError(f"{who}: {name}: need contiguous float64 {list(inner)} or [K, {', '.join(str(v) for v in inner)}] on {dev}")
+    squeeze = tuple(t.shape) == inner
+    return t.reshape((-1,) + inner), (1 if squeeze else t.shape[0]), squeeze
+
+
+def _agree(who, leads):
+    """(K, squeeze) of the tangents a hook takes itself - `leads`: (view, K, squeeze) or None each -, which must agree, or None where
+    there is none: the step loop validates the others once, holds them to this form and refuses a call without any tangent"""
+    forms = {(K, squeeze) for _, K, squeeze in (v for v in leads if v is not None)}
+    if len(forms) > 1:
+        raise ValueError(f"{who}: the tangents must agree on the number of directions and on the squeezed / [K, ...] form")
+    return forms.pop() if forms else None
+
+
+class _LeanHook:
+    """the lean in front of a step: com_reference_batch() and com_reference_tangent() on the state and the phases as the step finds
+    them, before the clock advances.  `base` / `base_tan`: the x_d that is leaned and its tangent buffer (None: zero); the leaned x_d
+    goes to `x_d`, its tangent to a buffer of this hook that takes the place of the held x_d_tan."""
+
+    def __init__(self, ctl, who, batch, n, K, dev, buf, stream, lean, schedule_tan, base, base_tan, x_d):
+        import torch
+
+        schedule, mode, gain = lean
+        self.flag_word = torch.zeros((n,), dtype=torch.int32, device=dev)
+        self.x_d_tan = torch.zeros((K, n, 3), dtype=torch.float64, device=dev)
+        reads = {k: batch[k] for k in ("joint_q", "Rwb", "x", "gait_phase", "gait_duty") if batch.get(k) is not None}
+        self.forward = ctl.plan_com_reference(reads, schedule, base, mode, gain, out={"x_d": x_d}, stream=stream)[0]
+        tans = {"joint_q_tan": buf["joint_q_tan"].view(K, n, 12), "Rwb_rot_tan": buf["Rwb_rot_tan"], "x_tan": buf["x_tan"]}
+        if base_tan is not None:
+            tans["x_d_in_tan"] = base_tan
+        if schedule_tan is not None:
+            tans["schedule_tan"] = schedule_tan
+        self.tangent = plan_com_reference_tangent(ctl, reads, schedule, None, tans, mode, gain, ("x_d_out_tan", "flags"),
+                                                  {"x_d_out_tan": self.x_d_tan, "flags": self.flag_word}, stream)[0]
+
+    def step(self, k):
+        self.forward()
+        self.tangent()
+
+    def flags(self, word):
+        word.bitwise_or_(self.flag_word.bitwise_left_shift(LEAN_FLAGS_SHIFT))
+
+
+def _lean_arguments(who, lean, default_mode, tangents, n, dev):
+    """(schedule, mode, gain) of `lean` and the lead form of tangents["schedule_tan"]: [n,4,4] / [K,n,4,4], or with a shared [4,4]
+    schedule one block per direction, [4,4] / [K,4,4]"""
+    from .autograd import _lean
+
+    lean = _lean(who, lean, default_mode)
+    st = tangents.get("schedule_tan")
+    if lean is None:
+        if st is not None:
+            raise ValueError(f"{who}: schedule_tan needs lean")
+        return None, None
+    if lean[1] not in _lib.COM_MODES:
+        raise ValueError(f"{who}: lean's mode is one of {tuple(_lib.COM_MODES)}, not {lean[1]!r}")
+    shared = lean[0].dim() == 2
+    return lean, _lead_tangent(who, "schedule_tan", st, (4, 4) if shared else (n, 4, 4), n, dev)
+
+
+def rollout_lean_tangent(ctl, batch, steps, dt, leg_inertia, gait_dt, lean, tangents, act_tol=1e-7, warm=True, stream=None):
+    """The forward-mode twin of ctl.rollout_tick(batch, None, ..., lean=lean) for a batch with swing_state and a running clock - of
+    rollout_gait_autograd(lean=lean) -: rollout_gait_tangent()'s loop with com_reference_batch() and com_reference_tangent() in front of
+    each step, on the state and the phases as the step finds them (before the clock advances); the feet's tangent comes from the
+    carried joint_q_tan.  lean = dict(schedule=..., mode="replace", gain=1.0), as rollout_tick() takes it; batch["x_d"] is written IN
+    PLACE from a copy taken at entry, as rollout_tick() writes it.  `tangents`: rollout_gait_tangent()'s, plus "schedule_tan" - [n,4,4] /
+    [K,n,4,4], or with a shared [4,4] schedule ONE block per direction, [4,4] / [K,4,4]; a held "x_d_tan" is the tangent of the x_d that
+    is leaned.  The state, the phases and the records end bit for bit where rollout_tick(..., lean=lean) leaves them with a gait_dt of
+    `dt`.  Returns (state, res) as rollout_gait_tangent() does; `res` adds the last step's "x_d_tan" (the leaned x_d's tangent), and
+    res["flags"] carries com_reference_tangent()'s bits shifted left by LEAN_FLAGS_SHIFT = 25: bit 25 + l, leg l's point was the
+    reference's 0/0 at some step.  The contact mask of the polygon is held, as the clock is.  One set of tangent buffers whatever
+    `steps` is.  ValueError as rollout_gait_tangent(), and for a batch without x_d."""
+    import torch
+
+    who = "rollout_lean_tangent"
+    _gait_rollout_refusals(who, batch, None)
+    if lean is None:
+        raise ValueError(f"{who}: lean is required (rollout_gait_tangent() is this rollout without it)")
+    if batch.get("x_d") is None:
+        raise ValueError(f"{who}: lean needs batch['x_d'] (its z in replace mode, the base of the offset)")
+    unknown = [k for k in tangents if k not in ROLLOUT_LEAN_TANGENTS]
+    if unknown:
+        raise ValueError(f"{who}: unknown tangent(s) {unknown}; the tangents are {tuple(ROLLOUT_LEAN_TANGENTS)}")
+    n, dev = batch["x"].shape[0], torch.device("cuda", ctl.device)
+    lean, st = _lean_arguments(who, lean, "replace", tangents, n, dev)
+    rest = {k: v for k, v in tangents.items() if k != "schedule_tan"}
+    lead = _agree(who, [st])
+    clock = _gait_clock(gait_dt, n, dev)
+
+    def hook(ctl, who, batch, n, K, dev, buf, given, stream):
+        base_tan = given["x_d_tan"].reshape(K, n, 3) if "x_d_tan" in given else None
+        h = _LeanHook(ctl, who, batch, n, K, dev, buf, stream, lean, None if st is None else st[0], batch["x_d"].clone(), base_tan, batch["x_d"])
+        h.held, h.desired, h.res = {"x_d_tan": h.x_d_tan}, {}, {"x_d_tan": h.x_d_tan}
+        return h
+
+    return _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, rest, ROLLOUT_GAIT_TANGENTS, act_tol, warm, stream, True, clock, hook, lead)
+
+
+class _CommanderHook:
+    """the commander step in front of a step: a copy of the records, commander_step_batch() (the records advance in place),
+    commander_step_tangent() with the four desired-state tangents and Vb_tan carried in place, and - with `lean` - the lean of the
+    commander's x_d for the tick alone, on a buffer of its own."""
+
+    def __init__(self, ctl, who, batch, n, K, dev, buf, given, stream, command, steps, twist_tan, Vb_tan, lean, schedule_tan):
+        import contextlib
+
+        import torch
+
+        self.on_stream = (lambda: torch.cuda.stream(stream)) if stream is not None else contextlib.nullcontext
+        self.state = command["state"]
+        zeros = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
+        with self.on_stream():
+            self.before = torch.empty_like(self.state)
+            self.desired = {"Rwb_d": zeros(n, 9), "x_d": zeros(n, 3), "xdot_d": zeros(n, 3), "w_d": zeros(n, 3)}
+            self.held = {k: (given[k].reshape(K, n, 3).clone() if k in given else zeros(K, n, 3)) for k in _COMMANDER_CARRIED}
+            self.Vb_tan = Vb_tan.clone() if Vb_tan is not None else zeros(K, n, 6)
+            self.flag_word = torch.zeros((n,), dtype=torch.int32, device=dev)
+        twist, fresh = command.get("twist"), command.get("fresh")
+        scalars = {k: command[k] for k in ("stand_height", "stand_tol", "cmd_dt") if command.get(k) is not None}
+        sequence = twist is not None and twist.dim() == 3
+        if sequence:  # one command per step, fresh where it says (default: everywhere)
+            if fresh is None:
+                fresh = torch.ones((steps, n), dtype=torch.uint8, device=dev)
+            # direction-major per step: [K, steps, n, 6] -> [steps, K, n, 6]
+            per_step = None if twist_tan is None else twist_tan.permute(1, 0, 2, 3).contiguous()
+            variants = [(dict(scalars, twist=twist[k], fresh=fresh[k]), None if per_step is None else per_step[k]) for k in range(steps)]
+            self.pick = lambda k: k
+        else:  # rollout_tick()'s rule: `fresh` holds on step 0 only
+            first = dict(scalars, **({} if twist is None else {"twist": twist}), **({} if fresh is None else {"fresh": fresh}))
+            variants = [(first, twist_tan if twist is not None else None), (dict(scalars), None)]
+            self.pick = lambda k: 0 if k == 0 else 1
+        pose = {"Rwb": batch["Rwb"], "x": batch["x"]}
+        carried = dict({prev: self.held[k] for k, prev in _COMMANDER_CARRIED.items()}, Vb_tan=self.Vb_tan, Rwb_rot_tan=buf["Rwb_rot_tan"], x_tan=buf["x_tan"])
+        out = dict(self.held, Vb_next_tan=self.Vb_tan, flags=self.flag_word)
+        self.plans = []
+        for cmd, tw in variants:
+            forward = ctl.plan_commander_step(pose, dict(cmd, state=self.state), tuple(self.desired), self.desired, stream)[0]
+            tans = dict(carried, **({} if tw is None else {"twist_tan": tw}))
+            self.plans.append((forward, plan_commander_step_tangent(ctl, pose, cmd, self.before, tans, tuple(out), out, stream)[0]))
+        self.res = dict(self.held, Vb_tan=self.Vb_tan)
+        self.lean = None
+        if lean is not None:
+            with self.on_stream():
+                x_d = zeros(n, 3)
+            self.lean = _LeanHook(ctl, who, batch, n, K, dev, buf, stream, lean, schedule_tan, self.desired["x_d"], self.held["x_d_tan"], x_d)
+            # (the tick alone tracks the leaned value: the record and its tangent keep the un-leaned integral)
+            self.desired = dict(self.desired, x_d=x_d)
+            self.held = dict(self.held, x_d_tan=self.lean.x_d_tan)
+            self.res["x_d_lean_tan"] = self.lean.x_d_tan
+
+    def step(self, k):
+        with self.on_stream():
+            self.before.copy_(self.state)
+        forward, tangent = self.plans[self.pick(k)]
+        forward()
+        tangent()
+        if self.lean is not None:
+            self.lean.step(k)
+
+    def flags(self, word):
+        word.bitwise_or_(self.flag_word.bitwise_left_shift(COMMANDER_FLAGS_SHIFT))
+        if self.lean is not None:
+            self.lean.flags(word)
+
+
+def rollout_commander_tangent(ctl, batch, command, steps, dt, leg_inertia, gait_dt, tangents, act_tol=1e-7, warm=True, stream=None, lean=None):
+    """The forward-mode twin of ctl.rollout_tick(batch, command, ...) for robots that stand and run - of rollout_commander_autograd() -:
+    the sensitivity of a closed-loop gait rollout to the twist command.  Per step: a copy of the commander records,
+    commander_step_batch() (the records advance IN PLACE), commander_step_tangent() - the four desired-state tangents and Vb_tan carried
+    in place -, with `lean` com_reference_batch() and com_reference_tangent() on a separate x_d buffer for the tick alone (default
+    mode "offset"; the record keeps the un-leaned integral, as in the autograd twin), then rollout_gait_tangent()'s step with the
+    commander's desired state and its tangents in place of the held ones - xdot_d_tan enters the planner's tangent too.  `batch` as
+    rollout_commander_autograd() takes it: joint_q, joint_qdot, gait_phase, swing_state, no desired state of its own.  `command`:
+    tick_batch()'s dict; a single twist [n,6] is applied under rollout_tick()'s rule (`fresh` holds on step 0 only), a sequence
+    twist [steps,n,6] with an optional fresh [steps,n] step by step.  `tangents`: rollout_gait_tangent()'s start-state and record
+    tangents; "Rwb_d_rot_tan", "x_d_tan", "xdot_d_tan", "w_d_tan" are here the tangents of the START RECORD's desired state; plus
+    "twist_tan" - [n,6] / [K,n,6], for a sequence [steps,n,6] / [K,steps,n,6] -, "Vb_tan" [n,6] / [K,n,6] on the held command and, with
+    `lean`, "schedule_tan" as rollout_lean_tangent() takes it.  As rollout_commander_autograd(), this call reads the latches ONCE on the
+    host and refuses a batch in which not every robot stands and runs.  With lean = None the state, the phases, the swing records and
+    the commander records end bit for bit where ctl.rollout_tick(batch, command, ...) leaves them with a gait_dt of `dt`; with `lean`
+    they are the forward values of rollout_commander_autograd(lean=lean).  Returns (state, res) as rollout_gait_tangent() does; `res`
+    adds the record's final "Rwb_d_rot_tan", "x_d_tan", "xdot_d_tan", "w_d_tan" and "Vb_tan" (with `lean`: "x_d_lean_tan", the last
+    tick's), and res["flags"] carries commander_step_tangent()'s bit at COMMANDER_FLAGS_SHIFT = 24 (a command applied at gimbal lock at
+    some step) and com_reference_tangent()'s at LEAN_FLAGS_SHIFT = 25 ... 28.  K unit seeds on twist_tan give the Jacobian in the
+    command.  One set of tangent buffers whatever `steps` is; a command SEQUENCE is an input of `steps` commands, and with it the
+    planning grows with the horizon: one commander launch and one tangent launch are planned per step, and twist_tan is copied once into
+    per-step [K,n,6] blocks."""
+    import torch
+
+    from .autograd import _COMMANDER_DESIRED_REFUSED
+
+    who = "rollout_commander_tangent"
+    _gait_rollout_refusals(who, batch, None)
+    for name, why in _COMMANDER_DESIRED_REFUSED.items():
+        if batch.get(name) is not None:
+            raise ValueError(f"{who}: batch['{name}'] must be None - {why}")
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError(f"{who}: steps must be >= 0")
+    if command is None or command.get("state") is None:
+        raise ValueError(f"{who}: command['state'] is required (new_commander_states)")
+    unknown = [k for k in tangents if k not in ROLLOUT_COMMANDER_TANGENTS]
+    if unknown:
+        raise ValueError(f"{who}: unknown tangent(s) {unknown}; the tangents are {tuple(ROLLOUT_COMMANDER_TANGENTS)}")
+    n, dev = batch["x"].shape[0], torch.device("cuda", ctl.device)
+    # standing and gait_running are latched and never reset: read ONCE, here (the rollout's one host synchronisation)
+    latched = command["state"].view(torch.int32).view(n, -1)[:, :2].ne(0).all(dim=0).tolist()
+    if not all(latched):
+        raise ValueError(f"{who}: every robot must have standing and gait_running set (not all have {'standing' if not latched[0] else 'gait_running'}): "
+                         "until then the commander ignores the twist - the tangent is identically zero - and rollout_tick() runs the stand-up")
+    twist, fresh = command.get("twist"), command.get("fresh")
+    sequence = twist is not None and twist.dim() == 3
+    if sequence and (twist.shape[0] != steps or (fresh is not None and (fresh.dim() != 2 or fresh.shape[0] != steps))):
+        raise ValueError(f"{who}: a command sequence is twist [steps,n,6] with an optional fresh [steps,n]")
+    if tangents.get("twist_tan") is not None and twist is None:
+        raise ValueError(f"{who}: twist_tan needs command['twist']")
+    lean, st = _lean_arguments(who, lean, "offset", tangents, n, dev)
+    tw = _lead_tangent(who, "twist_tan", tangents.get("twist_tan"), (steps, n, 6) if sequence else (n, 6), n, dev)
+    vb = _lead_tangent(who, "Vb_tan", tangents.get("Vb_tan"), (n, 6), n, dev)
+    rest = {k: v for k, v in tangents.items() if k not in ("twist_tan", "Vb_tan", "schedule_tan")}
+    lead = _agree(who, [tw, vb, st])
+    clock = _gait_clock(gait_dt, n, dev)
+
+    def hook(ctl, who, batch, n, K, dev, buf, given, stream):
+        return _CommanderHook(ctl, who, batch, n, K, dev, buf, given, stream, command, steps, None if tw is None else tw[0], None if vb is None else vb[0],
+                              lean, None if st is None else st[0])
+
+    return _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, rest, ROLLOUT_GAIT_TANGENTS, act_tol, warm, stream, True, clock, hook, lead)
