@@ -173,13 +173,18 @@ struct Lane {
       const double ly = -(double)C.sy[i] * g[3 * i + 1];
       const double lz = (double)C.sz[i] * (P.mu * (lx + ly) - g[3 * i + 2]);
       const int c0 = 3 * (foot0 + i);
-      cand[3 * i + 0] = tag(C.sx[i] != 0 ? lx : QC_BIG, c0 + 0);
-      cand[3 * i + 1] = tag(C.sy[i] != 0 ? ly : QC_BIG, c0 + 1);
-      cand[3 * i + 2] = tag(C.sz[i] != 0 ? lz : QC_BIG, c0 + 2);
+      // an inactive face: +BIG's high word over whatever low word (one select, as step_cand).  `worst` is read past `opt` only
+      // when it is below the bar, which nothing with that high word is
+      const double vx = big_unless(C.sx[i] != 0, lx), vy = big_unless(C.sy[i] != 0, ly), vz = big_unless(C.sz[i] != 0, lz);
+      cand[3 * i + 0] = tag(vx, c0 + 0);
+      cand[3 * i + 1] = tag(vy, c0 + 1);
+      cand[3 * i + 2] = tag(vz, c0 + 2);
       if constexpr (RACE) {  // per-axis "this multiplier is negative" for the drop-all strategy (compares; the masks live in SGPRs)
-        neg[3 * i + 0] = (C.sx[i] != 0) & (lx < thr);
-        neg[3 * i + 1] = (C.sy[i] != 0) & (ly < thr);
-        neg[3 * i + 2] = (C.sz[i] != 0) & (lz < thr);
+        // on the selected value BEFORE its tag (the tag moves the low five bits): an active face's is its multiplier, an inactive
+        // face's about 1e300 and under no bar
+        neg[3 * i + 0] = vx < thr;
+        neg[3 * i + 1] = vy < thr;
+        neg[3 * i + 2] = vz < thr;
         if constexpr (FPL == 4) {
           // one lane per robot (the dense form's twin race): twelve lane masks = twelve SGPR pairs across the state update, next to a
           // kernel whose pointers already fill half of the SGPR file - they spill, and SGPR pairs that spill leave frame slots.
@@ -189,7 +194,9 @@ struct Lane {
         } else if constexpr (kPacked) {
           // packed state update (iterate): the answers as the release mask itself, both bits of every negative axis, at the
           // axis' place in the working-set word
-          negbits |= ((neg[3 * i + 0] ? 3u : 0u) | (neg[3 * i + 1] ? 12u : 0u) | (neg[3 * i + 2] ? 48u : 0u)) << (6 * (foot0 + i));
+          // (the three masks shifted to the foot's place: they do not change while the lane keeps its robot)
+          const uint32_t sh = 6u * (uint32_t)(foot0 + i);
+          negbits |= (neg[3 * i + 0] ? 3u << sh : 0u) | (neg[3 * i + 1] ? 12u << sh : 0u) | (neg[3 * i + 2] ? 48u << sh : 0u);
           neg[3 * i + 0] = neg[3 * i + 1] = neg[3 * i + 2] = false;
         }
       } else {
@@ -272,23 +279,27 @@ struct Lane {
     int bcode = -1;
     uint32_t alo = 0u;  // (kPacked: the low word of the smallest ratio - its face code)
     if constexpr (PHASE != FIRST) {
-      double cand[6 * FPL];
+      // e = f - f^ is the step's operand below, and the directions are its negation (a source modifier): -(f - f^) is f^ - f bit
+      // for bit, except that equal operands give -0 where the difference gives +0 - a zero direction, with which no face can
+      // block (nd > eps fails) and whose sign no slack sees.  The step itself must keep e: fma(beta, -0, f^) turns a f^ of -0
+      // into -0 where e = +0 gives +0.
+      double cand[5 * FPL], e[3 * FPL];
 #pragma unroll
       for (int i = 0; i < FPL; i++) {
         const double fx = f[3 * i], fy = f[3 * i + 1], fz = f[3 * i + 2];
-        const double dx = fh[3 * i] - fx, dy = fh[3 * i + 1] - fy, dz = fh[3 * i + 2] - fz;
+        e[3 * i] = fx - fh[3 * i]; e[3 * i + 1] = fy - fh[3 * i + 1]; e[3 * i + 2] = fz - fh[3 * i + 2];
+        const double dx = -e[3 * i], dy = -e[3 * i + 1], dz = -e[3 * i + 2];
         const double m = P.mu * fz, md = P.mu * dz;
         const bool zf = C.sz[i] == 0, xf = C.sx[i] == 0, yf = C.sy[i] == 0;
         const int c0 = 6 * (foot0 + i);
-        cand[6 * i + 0] = step_cand(xf, m + fx, -dx - md, c0 + 0);     // X-
-        cand[6 * i + 1] = step_cand(xf, m - fx, dx - md, c0 + 1);      // X+
-        cand[6 * i + 2] = step_cand(yf, m + fy, -dy - md, c0 + 2);     // Y-
-        cand[6 * i + 3] = step_cand(yf, m - fy, dy - md, c0 + 3);      // Y+
-        cand[6 * i + 4] = step_cand(zf, fz - lo(P, i), -dz, c0 + 4);   // Z-
-        cand[6 * i + 5] = step_cand(zf, hi(P, i) - fz, dz, c0 + 5);    // Z+
+        cand[5 * i + 0] = step_cand(xf, m + fx, -dx - md, c0 + 0);     // X-
+        cand[5 * i + 1] = step_cand(xf, m - fx, dx - md, c0 + 1);      // X+  (both X faces can block at once: mu dz < -|dx|)
+        cand[5 * i + 2] = step_cand(yf, m + fy, -dy - md, c0 + 2);     // Y-
+        cand[5 * i + 3] = step_cand(yf, m - fy, dy - md, c0 + 3);      // Y+
+        cand[5 * i + 4] = step_cand_z(zf, fz, dz, lo(P, i), hi(P, i), c0 + 4);  // Z- (code c0 + 4) or Z+ (c0 + 5)
       }
 #pragma unroll
-      for (int w = 6 * FPL; w > 1; w = (w + 1) / 2)
+      for (int w = 5 * FPL; w > 1; w = (w + 1) / 2)
 #pragma unroll
         for (int k = 0; k < w / 2; k++) cand[k] = min_nn(cand[k], cand[k + (w + 1) / 2]);
       const double amin = group_min<G, S>(cand[0]);
@@ -299,7 +310,7 @@ struct Lane {
       // (branch-free; a blocking ratio that the approximate reciprocal rounds up to 1 is clamped too)
       const double beta = 1.0 - min_nn(max_nn(amin, 0.0), 1.0);
 #pragma unroll
-      for (int k = 0; k < 3 * FPL; k++) f[k] = fresh ? fc[k] : __builtin_fma(beta, f[k] - fh[k], fh[k]);
+      for (int k = 0; k < 3 * FPL; k++) f[k] = fresh ? fc[k] : __builtin_fma(beta, e[k], fh[k]);
     } else {
 #pragma unroll
       for (int k = 0; k < 3 * FPL; k++) f[k] = fc[k];

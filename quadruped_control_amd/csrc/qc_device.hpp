@@ -1256,7 +1256,9 @@ QC_DEV bool clamp_foot(double mu, double lo, double hi, int wx, int wy, int wz, 
 // tree yields arg-min and min together, without compare/select chains.
 QC_DEV double tag(double v, int code) {
   const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  return __longlong_as_double((long long)((b & ~31ull) | (unsigned long long)code));
+  // (on the low word alone, as step_cand: the 64-bit OR with a sign-extended int costs an OR on the high word too; codes are 0 ... 31)
+  const unsigned lo = ((unsigned)b & ~31u) | (unsigned)code;
+  return __longlong_as_double((long long)((b & 0xFFFFFFFF00000000ull) | lo));
 }
 QC_DEV int tag_code(double v) { return (int)(__double_as_longlong(v) & 31ll); }
 
@@ -1273,6 +1275,22 @@ QC_DEV double step_cand(bool free_face, double slack, double nd, int code) {
   const unsigned hi = can ? (unsigned)(b >> 32) : 0x7E37E43Cu;  // high word of 1e300
   const unsigned lo = ((unsigned)b & ~31u) | (unsigned)code;
   return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+// The two Z faces of one foot as ONE candidate.  Their directions are -dz and dz, so at most one of them passes nd > eps: the face
+// dz points at (upper for dz > 0) gets its slack and nd = |dz| (a source modifier) - the very operand bits the blocking face of the
+// pair sent to v_rcp_f64 and the multiply - and its code, c4 + 1 for the upper face; the other face of the pair was +BIG.  A
+// candidate that cannot block (dz = +-0, tiny, NaN: `dz > 0` is false and |dz| fails nd > eps as both faces did) has +BIG's high
+// word, and nobody reads the low word of a ratio that does not block.
+QC_DEV double step_cand_z(bool free_face, double fz, double dz, double lo, double hi, int c4) {
+  const bool up = dz > 0.0;
+  return step_cand(free_face, up ? hi - fz : fz - lo, __builtin_fabs(dz), up ? c4 + 1 : c4);
+}
+// v where `on`, otherwise a value with +BIG's high word (about 1e300 whatever its low word): one select, as in step_cand.  For
+// multipliers: the low word of an inactive face's candidate is read only if it wins the minimum, i.e. when no face is active.
+QC_DEV double big_unless(bool on, double v) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+  const unsigned hi = on ? (unsigned)(b >> 32) : 0x7E37E43Cu;
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | (unsigned)b));
 }
 
 // ------------------------------------------------------------ small SPD solve
