@@ -30,7 +30,8 @@
  * nothing is clamped.
  *
  * OUT OF SCOPE: entrywise (nine-number) rotation tangents - the rotations move along the left tangents above only; tangents of
- * the handle's parameters (mu, fzmin, fzmax, the weights, the gains, mass, Ib, the kinematic model); tangents through the swing
+ * the handle's parameters in THIS call (mu, fzmin, fzmax, the weights, the gains, mass, Ib: qc_param_tangent_batch, at the end of
+ * the header, adds them in place on grf_tan; the kinematic model has no tangent); tangents through the swing
  * pipeline (the swing legs' PD torques and the planner's references have their own calls below; the gait clock is held); weak activity (a row whose multiplier is about 0
  * is on the face like any other); commander mode in THIS call (the desired state must be in `in`: qc_commander_step_tangent_batch,
  * below, gives its tangents); a jvp on the torch.autograd.Functions of the Python package.
@@ -41,7 +42,8 @@
  * qc_swing_torque_tangent_batch in place behind it, and qc_leg_plant_step_tangent_batch, all below.  With swing_state the references
  * themselves move: qc_swing_reference_tangent_batch is the forward mode of the planner and the trajectory.  The two stages a rollout
  * is steered through close the header: qc_commander_step_tangent_batch (the twist command -> the desired state) and
- * qc_com_reference_tangent_batch (the schedule of the lean -> x_d).  With them every differentiable stage has both modes. */
+ * qc_com_reference_tangent_batch (the schedule of the lean -> x_d).  With them every differentiable stage has both modes in the
+ * state; qc_param_tangent_batch, the last call of the header, is the QP's forward mode in the handle's parameters. */
 #ifndef QC_TANGENT_H
 #define QC_TANGENT_H
 
@@ -289,7 +291,7 @@ int qc_leg_plant_step_tangent_batch(qc_handle* h, size_t n, const qc_leg_plant_t
  *
  * OUT OF SCOPE: tangents of the phase, of gait_dt, of the periods, of swing_height and of planner_k; the commander step and the com
  * reference in THIS call (their forward modes, qc_commander_step_tangent_batch and qc_com_reference_tangent_batch, are below);
- * parameter tangents. */
+ * tangents of the planner's own parameters. */
 typedef struct qc_swing_reference_tangent_io {
   size_t struct_size;                         /* = sizeof(qc_swing_reference_tangent_io); checked                      */
   const struct qc_swing_state* state_before;  /* [n] the records before the forward call; required                     */
@@ -429,6 +431,69 @@ void qc_default_com_reference_tangent(qc_com_reference_tangent_io* io);
  * tangent given at all, no output requested at all, joint_q_tan without in->joint_q, a missing schedule, gait_phase, feet / joint_q,
  * Rwb or x, or n * n_dir beyond one launch. */
 int qc_com_reference_tangent_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_com_reference_tangent_io* io, void* stream);
+
+/* qc_param_tangent_batch - forward mode of the balance QP in the handle's own PARAMETERS, the map qc_sensitivity_param_batch
+ * (qc_balance.h) transposes: K directions in the QC_PARAM_COUNT = 211 doubles of qc_params - mu, mass, fzmin, fzmax, Ib[9], S[36],
+ * W[144], kff[6], kp_p[3], kd_p[3], kp_w[3], kd_w[3], matrices entrywise and row-major - pushed through the QP on its active face.
+ * The handle holds ONE parameter set for the batch, so param_tan is SHARED by the batch: [K][211], not [K][n][211].  The call takes
+ * the SAME qc_batch_in the solve read and the forces; the face is exactly qc_tangent_batch's (qc_certify_batch's codes at act_tol; a
+ * code 3 on any axis of a foot pins that foot and sets bit 0 of `flags`), `in` is never written.
+ *
+ * In the notation of qc_sensitivity_param_batch - f the world forces, u = A f - b, v = S u, g = 2 (A^T v + W f),
+ * H = 2 (A^T S A + W), sx, sy in {-1, 0, +1} from the x / y codes 1 / 2 / 0 of a foot - per direction:
+ *   db     the forward derivative of the PD law in mass, kff, kp_p, kd_p, kp_w, kd_w and Ib, line by line as the library evaluates
+ *          it: db_lin = dmass (a - (0, 0, 9.81)) + mass da with da = dkp_p o (x_d - x) + dkd_p o (xdot_d - xdot) + (dkff0 xdot_d0,
+ *          dkff1 xdot_d1, dkff2 mass 9.81 + kff2 dmass 9.81) (mass enters three times); dal = dkp_w o e + dkd_w o (w_d - w) +
+ *          (dkff3 w_d0, dkff4 w_d1 + dkff5 w_d2, 0) (kff[5] acts on the second component, as the library has it);
+ *          db_ang = Iw dal + dIw al + w_d x (dIw w_d) with dIw = Rwb dIb Rwb^T
+ *   dg     = 2 (A^T dS u + dW f - A^T S db) at fixed f; dS and dW are taken entrywise AS GIVEN, not symmetrised - the caller owns
+ *          that, as with S_bar / W_bar
+ *   df0_l  the motion of foot l at fixed free coordinates: (sx, sy, 0) f_lz dmu with fz free; (sx (dmu f_lz + mu dfzmin),
+ *          sy (dmu f_lz + mu dfzmin), dfzmin) at a z code 1 (f_lz is fzmin there, to act_tol; the adjoint reads f_lz and so does
+ *          this); the same with fzmax at a z code 2; nothing for a swing foot or a foot with a code 3
+ *   dZ^T g on the z column of each foot with fz free: dmu (sx g_lx + sy g_ly)
+ *   (Z^T H Z) dy = -Z^T (H df0 + dg) - dZ^T g             (factorised once per robot, substituted K times)
+ *   df = df0 + Z dy,   grf_tan_l = -Rwb^T df_l (+ grf_tan_in),   b_tan = db (+ b_tan_in).
+ * <grf_bar, grf_tan_k - grf_tan_in_k> per robot equals <param_bar_rows' row, param_tan_k> with what qc_sensitivity_param_batch writes
+ * for that grf_bar.  With unit seeds the K outputs are K columns of d grf_body / d theta.
+ *
+ * This is the derivative of the CONTROLLER's use of mass and Ib (the wrench law), as the cotangent is; a plant that integrates the
+ * same body is another function of them.
+ *
+ * A pivot that is not positive and finite sets bit 1 of `flags`, and every grf_tan and b_tan of that robot is NaN in all K
+ * directions - a grf_tan_in does not rescue it.  A failed robot (all-zero forces), and a robot with no stance foot whose forces are
+ * zero, gets grf_tan = grf_tan_in + 0: grf_tan_in's numbers exactly (of its bits only the sign of a -0.0 may change), or exact
+ * zeros without one; b_tan is still db (+ b_tan_in).  Non-finite inputs propagate; nothing is clamped.
+ *
+ * grf_tan_in may BE grf_tan and b_tan_in may BE b_tan: a (direction, robot) pair reads its rows before it writes them and touches
+ * only its own.  qc_tangent_batch followed by this call with grf_tan_in = grf_tan on its buffer gives the tangent in the state and
+ * the parameters together: the sum of the two calls run apart, bit for bit (one IEEE addition of the two results).  param_tan must
+ * not overlap an output.  All pointers are device pointers.  No buffer is kept on the handle.
+ *
+ * OUT OF SCOPE: per-robot parameter directions; tangents of the kinematic model, of tau_min / tau_max, of the joint gains and of the
+ * plant's use of mass and Ib (qc_plant_step_tangent_batch and qc_leg_plant_step_tangent_batch hold them); symmetrised dS / dW;
+ * fusing this launch with qc_tangent_batch - it repeats that call's classification and factorisation (profiles/param_tangent.md
+ * has what that costs). */
+typedef struct qc_param_tangent_io {
+  size_t struct_size;            /* = sizeof(qc_param_tangent_io); checked                                            */
+  const double* grf_body;        /* [n][4][3] qc_batch_out.grf_body                                                   */
+  double act_tol;                /* as qc_sensitivity_io.act_tol: finite, >= 0                                        */
+  size_t n_dir;                  /* K >= 1 directions per launch                                                      */
+  const double* param_tan;       /* [K][QC_PARAM_COUNT], SHARED by the batch, qc_params' order, matrices entrywise     */
+  const double* grf_tan_in;      /* [K][n][4][3] optional: added; may BE grf_tan                                      */
+  const double* b_tan_in;        /* [K][n][6] optional: added; may BE b_tan                                           */
+  double* grf_tan;               /* [K][n][4][3] body frame                                                           */
+  double* b_tan;                 /* [K][n][6] optional                                                                */
+  int32_t* flags;                /* [n] optional: the bits of qc_sensitivity_io.flags                                 */
+} qc_param_tangent_io;
+/* struct_size set, pointers NULL, act_tol = 1e-7, n_dir = 1. */
+void qc_default_param_tangent(qc_param_tangent_io* io);
+/* Asynchronous on `stream`, no host synchronisation (graph-capturable); n == 0 launches nothing and returns QC_OK.
+ * QC_ERR_INVALID (message starting with "qc_param_tangent_batch:", nothing launched) for a null handle, `in` or `io`, a wrong
+ * struct_size, an act_tol that is not finite and >= 0, n_dir == 0, a missing param_tan, neither grf_tan nor b_tan requested,
+ * grf_tan_in without grf_tan, b_tan_in without b_tan, a missing grf_body, a missing state array (Rwb, Rwb_d, x, xdot, w, x_d, xdot_d,
+ * w_d), neither feet nor joint_q, or n beyond one launch. */
+int qc_param_tangent_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_param_tangent_io* io, void* stream);
 
 #ifdef __cplusplus
 }

@@ -2447,6 +2447,19 @@ int qc_com_reference_tangent_batch(qc_handle* h, size_t n, const qc_batch_in* in
                      stream, h->d_params, (long)n, qc::com_reference_tangent_constants(in, io));
 }
 
+void qc_default_param_tangent(qc_param_tangent_io* io) {
+  if (!zeroed(io)) return;
+  io->act_tol = 1e-7;  // qc_default_tangent's
+  io->n_dir = 1;
+}
+
+int qc_param_tangent_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_param_tangent_io* io, void* stream) {
+  if (const int rc = qc::check_param_tangent_args(h, n, in, io); rc != QC_OK || n == 0) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  return launch_per_robot(qc::param_tangent_kernel<true>, qc::param_tangent_kernel<false>, qc::param_tangent_blocks(n), qc::PARAM_TANGENT_BLOCK, h, n,
+                          readonly_view(in, true), qc::param_tangent_constants(io), stream);
+}
+
 void qc_default_sensitivity_rot(qc_sensitivity_rot_io* io) { (void)zeroed(io); }
 
 int qc_sensitivity_rot_batch(qc_handle* h, size_t n, const qc_batch_in* in, const qc_sensitivity_rot_io* io, void* stream) {

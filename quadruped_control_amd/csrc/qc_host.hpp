@@ -31,6 +31,7 @@
 #include "qc_leg_plant_tangent.hpp"
 #include "qc_swing_reference_tangent.hpp"
 #include "qc_command_tangent.hpp"
+#include "qc_param_tangent.hpp"
 
 namespace qc {
 
@@ -912,6 +913,30 @@ inline TangentArgs tangent_constants(const qc_tangent_io* io) {
 
 // workgroups of tangent_kernel for n robots: one wave each, capped (a grid cap of its own)
 inline unsigned tangent_blocks(size_t n) { return capped_blocks(n, TANGENT_BLOCK, TANGENT_MAX_BLOCKS); }
+
+// ---------------------------------------------------------------- qc_param_tangent_batch
+// The argument check of the forward mode in the parameters: what is wrong with the call itself (message prefix
+// "qc_param_tangent_batch:").  One lane per robot, whatever K is: the robots must fit a launch.
+inline int check_param_tangent_args(const qc_handle* h, size_t n, const qc_batch_in* in, const qc_param_tangent_io* io) {
+  const char* who = "qc_param_tangent_batch";
+  if (const int rc = check_io(who, h && in, io, "qc_param_tangent_io", "qc_default_param_tangent"); rc != QC_OK) return rc;
+  const char* own = nullptr;
+  if (!std::isfinite(io->act_tol) || !(io->act_tol >= 0.0)) own = ": act_tol must be finite and >= 0";
+  else if (io->n_dir == 0) own = ": n_dir must be >= 1";
+  else if (!io->param_tan) own = ": param_tan is required";
+  else if (!io->grf_tan && !io->b_tan) own = ": no output requested (grf_tan and b_tan are both NULL)";
+  else if (io->grf_tan_in && !io->grf_tan) own = ": grf_tan_in needs grf_tan";
+  else if (io->b_tan_in && !io->b_tan) own = ": b_tan_in needs b_tan";
+  return check_readonly_batch(who, n, in, own, io->grf_body != nullptr, ": grf_body is required", PARAM_TANGENT_BLOCK);
+}
+
+// the kernel's arguments: the record's scalars and arrays
+inline ParamTangentArgs param_tangent_constants(const qc_param_tangent_io* io) {
+  return ParamTangentArgs{io->grf_body, io->act_tol, (long)io->n_dir, io->param_tan, io->grf_tan_in, io->b_tan_in, io->grf_tan, io->b_tan, io->flags};
+}
+
+// workgroups of param_tangent_kernel for n robots: one wave each, capped (a grid cap of its own)
+inline unsigned param_tangent_blocks(size_t n) { return capped_blocks(n, PARAM_TANGENT_BLOCK, PARAM_TANGENT_MAX_BLOCKS); }
 
 // ---------------------------------------------------------------- qc_plant_step_tangent_batch
 // What is wrong with the call itself (message prefix "qc_plant_step_tangent_batch:"); the handle's mass and Ib are judged by

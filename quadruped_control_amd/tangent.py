@@ -31,8 +31,12 @@ rollout_commander_tangent() - the forward-mode twin of ctl.rollout_tick(batch, c
 rollout_commander_autograd() - and rollout_lean_tangent() - that of ctl.rollout_tick(batch, None, ..., lean=...) and of
 rollout_gait_autograd(lean=...) - chain them in front of rollout_gait_tangent()'s step.
 
-Not covered: tangents of the gait clock (the phases, the contact mask and the plan decisions are held), tangents of the handle's
-parameters, and a jvp on the torch.autograd.Functions of autograd.py."""
+The handle's own parameters have their forward mode too: param_tangent() (qc_param_tangent_batch, csrc/qc_param_tangent.hpp) pushes
+K directions in the 211 doubles of PARAM_LAYOUT through the QP - the transpose of autograd.py's params=theta -,
+param_jacobian_batch() is d grf_body / d theta on unit seeds, and every rollout here takes `params_tan`.
+
+Not covered: tangents of the gait clock (the phases, the contact mask and the plan decisions are held), tangents of the kinematic
+model, the joint gains and the plant's use of mass and Ib, and a jvp on the torch.autograd.Functions of autograd.py."""
 from __future__ import annotations
 
 import ctypes as C
@@ -139,6 +143,11 @@ class QcTangentIo(C.Structure):
                [(k, C.c_void_p) for k in tuple(TANGENTS) + ("grf_tan", "b_tan", "flags")]
 
 
+class QcParamTangentIo(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("grf_body", C.c_void_p), ("act_tol", C.c_double), ("n_dir", C.c_size_t)] + \
+               [(k, C.c_void_p) for k in ("param_tan", "grf_tan_in", "b_tan_in", "grf_tan", "b_tan", "flags")]
+
+
 class QcPlantTangentIo(C.Structure):
     _fields_ = [("struct_size", C.c_size_t)] + [(k, C.c_void_p) for k in ("Rwb", "x", "xdot", "w", "grf_body", "foot_world")] + \
                [("dt", C.c_double), ("n_dir", C.c_size_t)] + [(k, C.c_void_p) for k in tuple(PLANT_TANGENTS) + PLANT_TANGENT_WANT]
@@ -156,7 +165,7 @@ def _library():
                      "qc_torque_tangent_batch", "qc_default_leg_plant_tangent", "qc_leg_plant_step_tangent_batch", "qc_default_swing_tangent",
                      "qc_swing_torque_tangent_batch", "qc_default_swing_reference_tangent", "qc_swing_reference_tangent_batch",
                      "qc_default_commander_step_tangent", "qc_commander_step_tangent_batch", "qc_default_com_reference_tangent",
-                     "qc_com_reference_tangent_batch"):
+                     "qc_com_reference_tangent_batch", "qc_default_param_tangent", "qc_param_tangent_batch"):
             if not hasattr(lib, name):
                 raise ImportError(f"{_lib.LIB_PATH} does not export {name}")
         lib.qc_default_tangent.argtypes = [C.POINTER(QcTangentIo)]
@@ -192,6 +201,10 @@ def _library():
         lib.qc_default_com_reference_tangent.restype = None
         lib.qc_com_reference_tangent_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(_lib.QcBatchIn), C.POINTER(QcComReferenceTangentIo), C.c_void_p]
         lib.qc_com_reference_tangent_batch.restype = C.c_int
+        lib.qc_default_param_tangent.argtypes = [C.POINTER(QcParamTangentIo)]
+        lib.qc_default_param_tangent.restype = None
+        lib.qc_param_tangent_batch.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(_lib.QcBatchIn), C.POINTER(QcParamTangentIo), C.c_void_p]
+        lib.qc_param_tangent_batch.restype = C.c_int
         _bound = lib
     return _bound
 
@@ -302,6 +315,145 @@ def jacobian_batch(ctl, batch, grf_body, wrt=JACOBIAN_WRT, act_tol=1e-7, chunk=N
     return dict(jac=jac, columns=cols, flags=flags)
 
 
+# ------------------------------------------------------------------ forward mode in the handle's parameters
+PARAM_JACOBIAN_WRT = ("mu", "mass", "fzmin", "fzmax", "Ib", "kff", "kp_p", "kd_p", "kp_w", "kd_w")  # param_jacobian_batch's default: all groups but S and W
+
+
+def _param_directions(who, param_tan, dev):
+    """param_tan validated: contiguous float64 [211] (one direction, squeezed) or [K, 211] on `dev`.  Returns (K, squeeze)."""
+    import torch
+
+    if param_tan is None or param_tan.dtype != torch.float64 or not param_tan.is_contiguous() or param_tan.device != dev or param_tan.dim() not in (1, 2) or \
+            param_tan.shape[-1] != _lib.PARAM_COUNT or param_tan.numel() == 0:
+        raise ValueError(f"{who}: param_tan: need contiguous float64 [{_lib.PARAM_COUNT}] or [K,{_lib.PARAM_COUNT}] on {dev} (PARAM_LAYOUT's order)")
+    return (1, True) if param_tan.dim() == 1 else (param_tan.shape[0], False)
+
+
+def plan_param_tangent(ctl, batch, grf_body, param_tan, want=("grf_tan",), act_tol=1e-7, out=None, add_to=None, stream=None):
+    """param_tangent() marshalled once: returns (launch, out, squeeze), `launch()` being one qc_param_tangent_batch call
+    (graph-capturable) on tensors that are read in place; `out` holds [K, n, ...] tensors and squeeze says whether param_tan came as
+    [211].  Planning launches nothing."""
+    import torch
+
+    _library()
+    who = "param_tangent"
+    dev = torch.device("cuda", ctl.device)
+    K, squeeze = _param_directions(who, param_tan, dev)
+    io = QcParamTangentIo()
+    ctl._lib.qc_default_param_tangent(C.byref(io))
+    n, dev, bi = ctl._readonly_batch(who, batch, _READONLY_FIELDS, io, [("grf_body", grf_body, 12)])
+    io.param_tan = param_tan.data_ptr()
+    io.n_dir = K
+    io.act_tol = float(act_tol)
+    add_to = dict(add_to or {})
+    unknown = [k for k in add_to if k not in _TANGENT_OUTPUTS]
+    if unknown:
+        raise ValueError(f"{who}: add_to names {unknown}; it may hold {tuple(_TANGENT_OUTPUTS)}")
+    wanted = tuple(w for w in want if w != "flags")
+    missing = [k for k in add_to if k not in wanted]
+    if missing:
+        raise ValueError(f"{who}: add_to names {missing}, which `want` does not ask for")
+    if add_to:  # accumulated onto in place: the buffer is the input AND the output of its name
+        if out is not None and any(out.get(k) is not None for k in add_to):
+            raise ValueError(f"{who}: a buffer of add_to IS the output of its name - give it in add_to alone")
+        for k, t in add_to.items():
+            m = int(np.prod(_TANGENT_OUTPUTS[k][0]))
+            _check_tensor(k, t, K * n, m, torch.float64, dev, True, msg=f"add_to['{k}']: need contiguous float64 with {K * n * m} elements on {dev}")
+            setattr(io, k + "_in", t.data_ptr())
+        rest = {w: torch.zeros((K * n,) + _TANGENT_OUTPUTS[w][0], dtype=torch.float64, device=dev) for w in wanted if w not in add_to}
+        if "flags" in want:
+            rest["flags"] = torch.zeros((n,), dtype=torch.int32, device=dev)
+        out = dict(rest, **{k: v for k, v in (out or {}).items() if v is not None}, **add_to)
+    extra = [("flags", (n,), "int32")] if "flags" in want else []
+    res = _outputs(who, _TANGENT_OUTPUTS, wanted, out, K * n, dev, io, extra)
+    res = {k: (v if k == "flags" else v.view((K, n) + _TANGENT_OUTPUTS[k][0])) for k, v in res.items()}
+    launch = ctl._launcher("qc_param_tangent_batch", (n, C.byref(bi), C.byref(io), ctl._stream_ptr(stream)), (batch, grf_body, param_tan, res, bi, io), ValueError)
+    return launch, res, squeeze
+
+
+def param_tangent(ctl, batch, grf_body, param_tan, want=("grf_tan",), act_tol=1e-7, out=None, add_to=None, stream=None):
+    """Forward mode of the balance QP in the handle's own parameters, on the active face of `grf_body` [n,12] (as control_batch()
+    wrote it) for the batch the solve read (qc_param_tangent_batch, include/qc_tangent.h; INTEGRATION.md "Forward mode in the
+    parameters").  `param_tan`: a device tensor [211] (one direction, squeezed) or [K, 211] in PARAM_LAYOUT's order - mu, mass,
+    fzmin, fzmax, Ib, S, W, kff, kp_p, kd_p, kp_w, kd_w, matrices entrywise and row-major, NOT symmetrised (a direction in S or W
+    means something only where it is symmetric) - SHARED by the batch, as the handle's parameters are.  `want`: any of "grf_tan"
+    [K,n,4,3] (body frame), "b_tan" [K,n,6] and "flags" int32 [n] (tangent_batch()'s bits).  `add_to`: a dict with the "grf_tan" /
+    "b_tan" buffers ([K,n,...], as tangent_batch() wrote them) to accumulate onto IN PLACE - they are the outputs of their names; the
+    sum is the one IEEE addition of the two calls' results.  The transpose of sensitivity_params_batch(): <grf_bar, grf_tan_k> per
+    robot equals <param_bar_rows, param_tan_k>.  It repeats tangent_batch()'s factorisation (once per robot, substituted K times).
+    Nothing of `batch` is written.  Asynchronous on `stream`, no synchronisation.  Returns the dict of device tensors, [K, n, ...] -
+    squeezed to [n, ...] where param_tan came as [211].  ValueError with the library's message for a call it refuses.  Not covered:
+    per-robot directions, tangents of the kinematic model, of tau_min / tau_max, of the joint gains and of the plant's use of mass and
+    Ib."""
+    launch, res, squeeze = plan_param_tangent(ctl, batch, grf_body, param_tan, want, act_tol, out, add_to, stream)
+    launch()
+    return {k: (v[0] if squeeze and k != "flags" else v) for k, v in res.items()}
+
+
+def param_jacobian_columns(wrt=None):
+    """the columns of param_jacobian_batch(): the list of (group, index) - index a tuple into the group's shape; for "S" and "W" the
+    upper triangle (i, j), i <= j, row by row: the column of the symmetric pair"""
+    from .balance_controller import PARAM_LAYOUT
+
+    wrt = PARAM_JACOBIAN_WRT if wrt is None else tuple(wrt)
+    unknown = [w for w in wrt if w not in PARAM_LAYOUT]
+    if unknown:
+        raise ValueError(f"param_jacobian: unknown group(s) {unknown}; wrt is a subset of {tuple(PARAM_LAYOUT)}")
+    cols = []
+    for w in wrt:
+        shape = PARAM_LAYOUT[w][1]
+        if w in ("S", "W"):
+            cols += [(w, (i, j)) for i in range(shape[0]) for j in range(i, shape[1])]
+        else:
+            cols += [(w, tuple(int(v) for v in idx)) for idx in np.ndindex(*shape)]
+    return cols
+
+
+def param_jacobian_seeds(cols, dev):
+    """the unit seeds [len(cols), 211] of param_jacobian_columns()' columns, on `dev`: one 1 per column, and for an off-diagonal (i, j)
+    of "S" / "W" the symmetric pair E_ij + E_ji (E_ii on the diagonal)"""
+    import torch
+
+    from .balance_controller import PARAM_LAYOUT
+
+    seeds = np.zeros((len(cols), _lib.PARAM_COUNT))
+    for c, (group, idx) in enumerate(cols):
+        sl, shape = PARAM_LAYOUT[group]
+        E = np.zeros(shape if shape else (1,))
+        E[idx if shape else 0] = 1.0
+        if group in ("S", "W"):
+            E[idx[::-1]] = 1.0
+        seeds[c, sl] = E.reshape(-1)
+    return torch.from_numpy(seeds).to(dev)
+
+
+def param_jacobian_batch(ctl, batch, grf_body, wrt=None, chunk=None, act_tol=1e-7, stream=None):
+    """The Jacobian d grf_body / d theta of a solved batch on its active face, in the handle's own parameters: param_tangent() on unit
+    seeds, `chunk` directions per launch (None: all in one).  `wrt`: PARAM_LAYOUT groups (None: PARAM_JACOBIAN_WRT - every group but
+    "S" and "W").  A column of a vector or of Ib is the derivative in ONE entry; for "S" and "W" the seeds are the SYMMETRIC pairs
+    E_ij + E_ji, i <= j (E_ii on the diagonal) - the derivative along a matrix that stays symmetric, 21 columns for S and 78 for W.
+    Returns dict(jac [n, 12, C] - column c is d grf_body / d (columns[c]) -, columns: the list of (group, index), flags int32 [n]).
+    Column c equals param_tangent() on the seed of columns[c] bit for bit, however the columns are chunked.  ValueError as
+    param_tangent()."""
+    import torch
+
+    cols = param_jacobian_columns(wrt)
+    n, dev = grf_body.shape[0], grf_body.device
+    total = len(cols)
+    step = total if chunk is None else int(chunk)
+    if step < 1:
+        raise ValueError("param_jacobian: chunk must be >= 1")
+    seeds = param_jacobian_seeds(cols, dev)
+    jac = torch.empty((n, 12, total), dtype=torch.float64, device=dev)
+    flags = None
+    for c0 in range(0, total, step):
+        part = seeds[c0:c0 + step].contiguous()
+        res = param_tangent(ctl, batch, grf_body, part, want=("grf_tan", "flags"), act_tol=act_tol, stream=stream)
+        jac[:, :, c0:c0 + part.shape[0]] = res["grf_tan"].reshape(part.shape[0], n, 12).permute(1, 2, 0)
+        flags = res["flags"]
+    return dict(jac=jac, columns=cols, flags=flags)
+
+
 # ------------------------------------------------------------------ the plant step's forward mode and the closed loop
 def plan_plant_step_tangent(ctl, state, grf_body, foot_world, dt, tangents, want=PLANT_TANGENT_WANT, out=None, stream=None):
     """plant_step_tangent() marshalled once: returns (launch, out, squeeze), `launch()` being one qc_plant_step_tangent_batch call
@@ -340,7 +492,18 @@ def plant_step_tangent(ctl, state, grf_body, foot_world, dt, tangents, want=PLAN
     return {k: (v[0] if squeeze else v) for k, v in res.items()}
 
 
-def rollout_tangent(ctl, batch, foot_world, steps, dt, tangents, act_tol=1e-7, warm=True, stream=None):
+def _rollout_params_tan(who, params_tan, dev, given, K, squeeze):
+    """`params_tan` of a rollout (None, [211] or [K, 211]) against the form of the other tangents: returns (K, squeeze) - params_tan's
+    own where it is the only seed."""
+    if params_tan is None:
+        return K, squeeze
+    lead = _param_directions(who, params_tan, dev)
+    if given and lead != (K, squeeze):
+        raise ValueError(f"{who}: params_tan must agree with the tangents on the number of directions and on the squeezed / [K, ...] form")
+    return lead
+
+
+def rollout_tangent(ctl, batch, foot_world, steps, dt, tangents, act_tol=1e-7, warm=True, stream=None, params_tan=None):
     """The forward-mode twin of ctl.rollout(): `steps` times control_batch(), tangent_batch(), plant_step_tangent() (it reads the state
     before the step) and plant_step(), everything planned once, on one stream and without a host round trip.  `batch` is advanced IN
     PLACE and ends bit for bit where ctl.rollout() leaves it.  `tangents`: any of the start state's "Rwb_rot_tan", "x_tan",
@@ -349,7 +512,11 @@ def rollout_tangent(ctl, batch, foot_world, steps, dt, tangents, act_tol=1e-7, w
     written.  Returns (state, res): `state` the tensors of `batch`, `res` the final "Rwb_rot_tan", "x_tan", "xdot_tan", "w_tan",
     "feet_tan", the last solve's "grf_tan" ([K, n, ...], squeezed where the tangents came as [n, ...]) and "flags" int32 [n],
     tangent_batch()'s flags OR-ed over the steps on the device.  The derivative is the one on the active face of every solve at
-    `act_tol`, as rollout_autograd()'s.  Tangent memory is one set of buffers whatever `steps` is."""
+    `act_tol`, as rollout_autograd()'s.  Tangent memory is one set of buffers whatever `steps` is.
+    `params_tan` ([211] or [K, 211], PARAM_LAYOUT's order, agreeing with `tangents` on K): directions in the handle's parameters, held
+    over the rollout - every step launches param_tangent() in place on grf_tan behind tangent_batch() and ORs its flags into the same
+    word; it is a seed of its own (`tangents` may then be empty).  The plant's mass and Ib stay held, as in
+    rollout_autograd(params=...).  params_tan=None launches exactly what the rollout launched without the keyword."""
     import contextlib
 
     import torch
@@ -365,8 +532,9 @@ def rollout_tangent(ctl, batch, foot_world, steps, dt, tangents, act_tol=1e-7, w
     n = batch["x"].shape[0]
     dev = torch.device("cuda", ctl.device)
     given, K, squeeze = _directions(tangents, ROLLOUT_TANGENTS, n, dev)
-    if not given:
+    if not given and params_tan is None:
         raise ValueError("rollout_tangent: no tangent given")
+    K, squeeze = _rollout_params_tan("rollout_tangent", params_tan, dev, given, K, squeeze)
     on_stream = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
     with on_stream:
         # one set of buffers: the state's tangents and feet_tan are advanced in place, grf_tan is rewritten by every step
@@ -375,6 +543,7 @@ def rollout_tangent(ctl, batch, foot_world, steps, dt, tangents, act_tol=1e-7, w
                for k, m in ROLLOUT_TANGENTS.items() if k in _ROLLOUT_STATE or k == "feet_tan"}
         grf_tan = torch.zeros((K, n, 4, 3), dtype=torch.float64, device=dev)
         flags, step_flags = (torch.zeros((n,), dtype=torch.int32, device=dev) for _ in range(2))
+        param_flags = torch.zeros((n,), dtype=torch.int32, device=dev) if params_tan is not None else None
     held = {k: given[k].reshape(K, n, 3) for k in _ROLLOUT_HELD if k in given}
     fw_tan = given["foot_world_tan"].reshape(K, n, 4, 3) if "foot_world_tan" in given else None
     state = {k: batch[k] for k in ("Rwb", "x", "xdot", "w")}
@@ -383,6 +552,10 @@ def rollout_tangent(ctl, batch, foot_world, steps, dt, tangents, act_tol=1e-7, w
     if steps > 0 and n > 0:
         solve_tan, _, _ = plan_tangent(ctl, batch, r.out["grf_body"], dict(buf, **held), ("grf_tan", "flags"), act_tol,
                                        {"grf_tan": grf_tan, "flags": step_flags}, stream)
+        param_tan = None
+        if params_tan is not None:
+            param_tan, _, _ = plan_param_tangent(ctl, batch, r.out["grf_body"], params_tan, ("grf_tan", "flags"), act_tol, {"flags": param_flags},
+                                                 {"grf_tan": grf_tan}, stream)
         plant_in = {k: buf[k] for k in _ROLLOUT_STATE}
         plant_in["grf_tan"] = grf_tan
         if fw_tan is not None:
@@ -394,8 +567,12 @@ def rollout_tangent(ctl, batch, foot_world, steps, dt, tangents, act_tol=1e-7, w
         for k in range(steps):
             r.solve(k)
             solve_tan()
+            if param_tan is not None:
+                param_tan()
             with on_stream:
                 flags.bitwise_or_(step_flags)
+                if param_flags is not None:
+                    flags.bitwise_or_(param_flags)
             step_tan()
             step()
     res = dict(buf, grf_tan=grf_tan)
@@ -561,7 +738,7 @@ def leg_plant_step_tangent(ctl, state, joint_tau, dt, leg_inertia, tangents, sta
     return {k: (v[0] if squeeze and k != "flags" else v) for k, v in res.items()}
 
 
-def rollout_tick_tangent(ctl, batch, steps, dt, leg_inertia, tangents, act_tol=1e-7, warm=True, stream=None, command=None, lean=None):
+def rollout_tick_tangent(ctl, batch, steps, dt, leg_inertia, tangents, act_tol=1e-7, warm=True, stream=None, command=None, lean=None, params_tan=None):
     """The forward-mode twin of ctl.rollout_tick(batch, None, ...): `steps` times control_batch(want_torques=True), tangent_batch()
     (the state's tangents and joint_q_tan), torque_tangent(), leg_plant_step_tangent() (it reads the state before the step) and
     leg_plant_step(), everything planned once, on one stream and without a host round trip.  `batch` is advanced IN PLACE and ends
@@ -576,7 +753,9 @@ def rollout_tick_tangent(ctl, batch, steps, dt, leg_inertia, tangents, act_tol=1
     tick's torque clamp mask and off the plant's flagged legs, as rollout_tick_autograd()'s.  Tangent memory is one set of buffers
     whatever `steps` is.  ValueError for swing references (swing_state, swing_pos, swing_vel), gait_dt, `lean` and a `command` - in THIS
     rollout: rollout_swing_tangent() and rollout_gait_tangent() take the swing pipeline, rollout_commander_tangent() a `command` and
-    rollout_lean_tangent() a `lean`."""
+    rollout_lean_tangent() a `lean`.  `params_tan` ([211] or [K, 211], PARAM_LAYOUT's order): directions in the handle's parameters, held
+    over the rollout - param_tangent() in place on grf_tan behind tangent_batch() at every step, a seed of its own; the plant's mass
+    and Ib, the joint gains and the kinematic model stay held, as in rollout_tick_autograd(params=...)."""
     who = "rollout_tick_tangent"
     if command is not None:
         raise ValueError(f"{who}: commander mode has no forward mode - command must be None (the desired state is held in the batch)")
@@ -588,10 +767,11 @@ def rollout_tick_tangent(ctl, batch, steps, dt, leg_inertia, tangents, act_tol=1
             raise ValueError(f"{who}: batch['{name}'] must be None - {why} has no forward mode")
     if batch.get("joint_q") is None or batch.get("joint_qdot") is None:
         raise ValueError(f"{who}: the batch carries joint_q and joint_qdot (rollout_tangent() steps the bare rigid body)")
-    return _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, ROLLOUT_TICK_TANGENTS, act_tol, warm, stream, False)
+    return _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, ROLLOUT_TICK_TANGENTS, act_tol, warm, stream, False, params_tan=params_tan)
 
 
-def _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, table, act_tol, warm, stream, swings, clock=None, hook=None, lead=None):
+def _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, table, act_tol, warm, stream, swings, clock=None, hook=None, lead=None,
+                       params_tan=None):
     """What rollout_tick_tangent(), rollout_swing_tangent() and rollout_gait_tangent() share, behind their own refusals: the tangents
     validated against `table`, one set of buffers, every launch planned once, the step loop.  swings=False launches exactly what
     rollout_tick_tangent() always did; swings=True hands the whole batch to the tick (joint_qdot and the two references with it, as
@@ -604,7 +784,10 @@ def _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, table,
     reads (`desired`: name -> tensor, laid over the batch) and the desired-state tangent buffers (`held`: name -> [K,n,3], in place of
     the held ones) -, whose flags(word) ORs its own bits into the rollout's word after the step's launches and whose `res` joins the
     result; the tangents the hook takes itself are not in `tangents`, `lead` = (K, squeeze) is their form.  Without a hook nothing here
-    launches, reads or allocates anything it did not before."""
+    launches, reads or allocates anything it did not before.
+    `params_tan` ([211] or [K, 211], agreeing with the other tangents): directions in the handle's parameters, held over the rollout -
+    param_tangent() in place on grf_tan behind tangent_batch(), its flags OR-ed into the word's bits 0-1; a seed of its own.  The
+    plant's mass and Ib, the joint gains and the kinematic model stay held.  With None nothing is launched or allocated for it."""
     import contextlib
 
     import torch
@@ -622,8 +805,11 @@ def _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, table,
         if given and (K, squeeze) != tuple(lead):
             raise ValueError(f"{who}: the tangents must agree on the number of directions and on the [n, ...] / [K, n, ...] form")
         K, squeeze = lead
-    elif not given:
+        _rollout_params_tan(who, params_tan, dev, True, K, squeeze)
+    elif not given and params_tan is None:
         raise ValueError(f"{who}: no tangent given")
+    else:
+        K, squeeze = _rollout_params_tan(who, params_tan, dev, given, K, squeeze)
     shape = lambda m: (K, n) + ((4, 3) if m == 12 else (3,))
     on_stream = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
     with on_stream:
@@ -633,6 +819,7 @@ def _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, table,
         grf_tan, tau_tan = (torch.zeros((K, n, 4, 3), dtype=torch.float64, device=dev) for _ in range(2))
         flags, solve_flags, plant_flags = (torch.zeros((n,), dtype=torch.int32, device=dev) for _ in range(3))
         swing_flags = torch.zeros((n,), dtype=torch.int32, device=dev) if swings else None
+        param_flags = torch.zeros((n,), dtype=torch.int32, device=dev) if params_tan is not None else None
         if clock is not None:
             # the record's tangents, advanced in place; the references and their tangents, rewritten by every step; the records before it
             rec = {k: (given[k].reshape(K, n, 12).clone() if k in given else torch.zeros((K, n, 12), dtype=torch.float64, device=dev)) for k in _GAIT_RECORD}
@@ -658,6 +845,10 @@ def _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, table,
         solve_in = {k: buf[k] for k in ("Rwb_rot_tan", "x_tan", "xdot_tan", "w_tan", "joint_q_tan")}
         solve_tan, _, _ = plan_tangent(ctl, tick_in, r.out["grf_body"], dict(solve_in, **held), ("grf_tan", "flags"), act_tol,
                                        {"grf_tan": grf_tan, "flags": solve_flags}, stream)
+        param_tan = None
+        if params_tan is not None:
+            param_tan, _, _ = plan_param_tangent(ctl, tick_in, r.out["grf_body"], params_tan, ("grf_tan", "flags"), act_tol, {"flags": param_flags},
+                                                 {"grf_tan": grf_tan}, stream)
         torque_tan, _, _ = plan_torque_tangent(ctl, tick_in, r.out["grf_body"], r.out["status"], {"grf_tan": grf_tan, "joint_q_tan": buf["joint_q_tan"]},
                                                {"joint_tau_tan": tau_tan}, stream)
         swing_tan = None
@@ -693,12 +884,16 @@ def _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, table,
                 reference_tan()
             r.solve(k)
             solve_tan()
+            if param_tan is not None:
+                param_tan()
             torque_tan()
             if swing_tan is not None:
                 swing_tan()
             step_tan()
             with on_stream:
                 flags.bitwise_or_(solve_flags.bitwise_or(plant_flags.bitwise_left_shift(TICK_PLANT_FLAGS_SHIFT)))
+                if param_flags is not None:
+                    flags.bitwise_or_(param_flags)
                 if swing_flags is not None:
                     flags.bitwise_or_(swing_flags.bitwise_left_shift(SWING_FLAGS_SHIFT))
                 if reference is not None:
@@ -844,7 +1039,7 @@ def _swing_rollout_refusals(who, batch, command, lean):
         raise ValueError(f"{who}: the batch carries joint_q and joint_qdot (rollout_tangent() steps the bare rigid body)")
 
 
-def rollout_swing_tangent(ctl, batch, steps, dt, leg_inertia, tangents, act_tol=1e-7, warm=True, stream=None, command=None, lean=None):
+def rollout_swing_tangent(ctl, batch, steps, dt, leg_inertia, tangents, act_tol=1e-7, warm=True, stream=None, command=None, lean=None, params_tan=None):
     """The forward-mode twin of ctl.rollout_tick(batch, None, ...) for a batch that carries swing_pos AND swing_vel: forward mode
     through a trot.  The two references and the `stance` / `gait_phase` / `gait_duty` contact mask are HELD over the rollout, exactly
     as rollout_tick_autograd() holds them.  Per step: control_batch(want_torques=True), tangent_batch(), torque_tangent(),
@@ -859,10 +1054,11 @@ def rollout_swing_tangent(ctl, batch, steps, dt, leg_inertia, tangents, act_tol=
     tangent, and what follows from it, is NaN).  The derivative is the one on the active face of every solve at `act_tol` and at
     every tick's clamp masks, as rollout_tick_autograd()'s.  Tangent memory is one set of buffers whatever `steps` is.  ValueError for
     swing_state, gait_dt, a `command`, `lean`, and for a batch with only one of swing_pos / swing_vel (or neither) - in THIS rollout:
-    rollout_gait_tangent() takes the planner, rollout_commander_tangent() a `command` and rollout_lean_tangent() a `lean`."""
+    rollout_gait_tangent() takes the planner, rollout_commander_tangent() a `command` and rollout_lean_tangent() a `lean`.
+    `params_tan` ([211] or [K, 211]): directions in the handle's parameters, held over the rollout, as rollout_tick_tangent() takes them."""
     who = "rollout_swing_tangent"
     _swing_rollout_refusals(who, batch, command, lean)
-    return _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, ROLLOUT_SWING_TANGENTS, act_tol, warm, stream, True)
+    return _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, ROLLOUT_SWING_TANGENTS, act_tol, warm, stream, True, params_tan=params_tan)
 
 
 def rollout_swing_transition(ctl, batch, steps, dt, leg_inertia, act_tol=1e-7, warm=True, chunk=None, stream=None):
@@ -961,7 +1157,7 @@ def _gait_clock(gait_dt, n, dev):
     return torch.full((n,), float(gait_dt), dtype=torch.float64, device=dev)
 
 
-def rollout_gait_tangent(ctl, batch, steps, dt, leg_inertia, gait_dt, tangents, act_tol=1e-7, warm=True, stream=None, lean=None):
+def rollout_gait_tangent(ctl, batch, steps, dt, leg_inertia, gait_dt, tangents, act_tol=1e-7, warm=True, stream=None, lean=None, params_tan=None):
     """The forward-mode twin of ctl.rollout_tick(batch, None, ...) for a batch with swing_state and a running clock - of
     rollout_gait_autograd() -: forward mode through the planner.  Per step: a copy of the records, swing_reference_batch() with
     `gait_dt` (a number or a float64 [n] tensor; the phases and the records advance IN PLACE), swing_reference_tangent() (the record's
@@ -979,7 +1175,8 @@ def rollout_gait_tangent(ctl, batch, steps, dt, leg_inertia, gait_dt, tangents, 
     contact mask and the plan decisions are held, as in rollout_gait_autograd(); the derivative is the one on the active face of
     every solve at `act_tol` and at every tick's clamp masks.  Tangent memory is one set of buffers whatever `steps` is.  ValueError
     for `lean` (rollout_lean_tangent() is this rollout with the lean; rollout_commander_tangent() takes a `command`), a `stance` mask,
-    swing_pos / swing_vel, a gait_dt inside the batch, `feet`, and a batch without joint_q, joint_qdot, gait_phase or swing_state."""
+    swing_pos / swing_vel, a gait_dt inside the batch, `feet`, and a batch without joint_q, joint_qdot, gait_phase or swing_state.
+    `params_tan` ([211] or [K, 211]): directions in the handle's parameters, held over the rollout, as rollout_tick_tangent() takes them."""
     import torch
 
     who = "rollout_gait_tangent"
@@ -988,7 +1185,7 @@ def rollout_gait_tangent(ctl, batch, steps, dt, leg_inertia, gait_dt, tangents, 
     if unknown:  # (swing_pos_tan / swing_vel_tan among them: the references' tangents are computed; refused before anything touches the device)
         raise ValueError(f"{who}: unknown tangent(s) {unknown}; the tangents are {tuple(ROLLOUT_GAIT_TANGENTS)}")
     clock = _gait_clock(gait_dt, batch["x"].shape[0], torch.device("cuda", ctl.device))
-    return _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, ROLLOUT_GAIT_TANGENTS, act_tol, warm, stream, True, clock)
+    return _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, tangents, ROLLOUT_GAIT_TANGENTS, act_tol, warm, stream, True, clock, params_tan=params_tan)
 
 
 def rollout_gait_transition(ctl, batch, steps, dt, leg_inertia, gait_dt, act_tol=1e-7, warm=True, chunk=None, stream=None):
@@ -1209,7 +1406,7 @@ def _lean_arguments(who, lean, default_mode, tangents, n, dev):
     return lean, _lead_tangent(who, "schedule_tan", st, (4, 4) if shared else (n, 4, 4), n, dev)
 
 
-def rollout_lean_tangent(ctl, batch, steps, dt, leg_inertia, gait_dt, lean, tangents, act_tol=1e-7, warm=True, stream=None):
+def rollout_lean_tangent(ctl, batch, steps, dt, leg_inertia, gait_dt, lean, tangents, act_tol=1e-7, warm=True, stream=None, params_tan=None):
     """The forward-mode twin of ctl.rollout_tick(batch, None, ..., lean=lean) for a batch with swing_state and a running clock - of
     rollout_gait_autograd(lean=lean) -: rollout_gait_tangent()'s loop with com_reference_batch() and com_reference_tangent() in front of
     each step, on the state and the phases as the step finds them (before the clock advances); the feet's tangent comes from the
@@ -1220,7 +1417,8 @@ def rollout_lean_tangent(ctl, batch, steps, dt, leg_inertia, gait_dt, lean, tang
     `dt`.  Returns (state, res) as rollout_gait_tangent() does; `res` adds the last step's "x_d_tan" (the leaned x_d's tangent), and
     res["flags"] carries com_reference_tangent()'s bits shifted left by LEAN_FLAGS_SHIFT = 25: bit 25 + l, leg l's point was the
     reference's 0/0 at some step.  The contact mask of the polygon is held, as the clock is.  One set of tangent buffers whatever
-    `steps` is.  ValueError as rollout_gait_tangent(), and for a batch without x_d."""
+    `steps` is.  ValueError as rollout_gait_tangent(), and for a batch without x_d.
+    `params_tan` ([211] or [K, 211]): directions in the handle's parameters, held over the rollout, as rollout_tick_tangent() takes them."""
     import torch
 
     who = "rollout_lean_tangent"
@@ -1236,6 +1434,8 @@ def rollout_lean_tangent(ctl, batch, steps, dt, leg_inertia, gait_dt, lean, tang
     lean, st = _lean_arguments(who, lean, "replace", tangents, n, dev)
     rest = {k: v for k, v in tangents.items() if k != "schedule_tan"}
     lead = _agree(who, [st])
+    if lead is None and params_tan is not None and not any(v is not None for v in rest.values()):
+        lead = _param_directions(who, params_tan, dev)  # params_tan alone is a seed
     clock = _gait_clock(gait_dt, n, dev)
 
     def hook(ctl, who, batch, n, K, dev, buf, given, stream):
@@ -1244,7 +1444,7 @@ def rollout_lean_tangent(ctl, batch, steps, dt, leg_inertia, gait_dt, lean, tang
         h.held, h.desired, h.res = {"x_d_tan": h.x_d_tan}, {}, {"x_d_tan": h.x_d_tan}
         return h
 
-    return _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, rest, ROLLOUT_GAIT_TANGENTS, act_tol, warm, stream, True, clock, hook, lead)
+    return _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, rest, ROLLOUT_GAIT_TANGENTS, act_tol, warm, stream, True, clock, hook, lead, params_tan)
 
 
 class _CommanderHook:
@@ -1314,7 +1514,8 @@ class _CommanderHook:
             self.lean.flags(word)
 
 
-def rollout_commander_tangent(ctl, batch, command, steps, dt, leg_inertia, gait_dt, tangents, act_tol=1e-7, warm=True, stream=None, lean=None):
+def rollout_commander_tangent(ctl, batch, command, steps, dt, leg_inertia, gait_dt, tangents, act_tol=1e-7, warm=True, stream=None, lean=None,
+                              params_tan=None):
     """The forward-mode twin of ctl.rollout_tick(batch, command, ...) for robots that stand and run - of rollout_commander_autograd() -:
     the sensitivity of a closed-loop gait rollout to the twist command.  Per step: a copy of the commander records,
     commander_step_batch() (the records advance IN PLACE), commander_step_tangent() - the four desired-state tangents and Vb_tan carried
@@ -1335,7 +1536,8 @@ def rollout_commander_tangent(ctl, batch, command, steps, dt, leg_inertia, gait_
     some step) and com_reference_tangent()'s at LEAN_FLAGS_SHIFT = 25 ... 28.  K unit seeds on twist_tan give the Jacobian in the
     command.  One set of tangent buffers whatever `steps` is; a command SEQUENCE is an input of `steps` commands, and with it the
     planning grows with the horizon: one commander launch and one tangent launch are planned per step, and twist_tan is copied once into
-    per-step [K,n,6] blocks."""
+    per-step [K,n,6] blocks.
+    `params_tan` ([211] or [K, 211]): directions in the handle's parameters, held over the rollout, as rollout_tick_tangent() takes them."""
     import torch
 
     from .autograd import _COMMANDER_DESIRED_REFUSED
@@ -1370,10 +1572,12 @@ def rollout_commander_tangent(ctl, batch, command, steps, dt, leg_inertia, gait_
     vb = _lead_tangent(who, "Vb_tan", tangents.get("Vb_tan"), (n, 6), n, dev)
     rest = {k: v for k, v in tangents.items() if k not in ("twist_tan", "Vb_tan", "schedule_tan")}
     lead = _agree(who, [tw, vb, st])
+    if lead is None and params_tan is not None and not any(v is not None for v in rest.values()):
+        lead = _param_directions(who, params_tan, dev)  # params_tan alone is a seed
     clock = _gait_clock(gait_dt, n, dev)
 
     def hook(ctl, who, batch, n, K, dev, buf, given, stream):
         return _CommanderHook(ctl, who, batch, n, K, dev, buf, given, stream, command, steps, None if tw is None else tw[0], None if vb is None else vb[0],
                               lean, None if st is None else st[0])
 
-    return _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, rest, ROLLOUT_GAIT_TANGENTS, act_tol, warm, stream, True, clock, hook, lead)
+    return _tick_tangent_loop(ctl, who, batch, steps, dt, leg_inertia, rest, ROLLOUT_GAIT_TANGENTS, act_tol, warm, stream, True, clock, hook, lead, params_tan)
