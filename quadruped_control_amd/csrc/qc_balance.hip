@@ -1398,13 +1398,40 @@ __global__ __launch_bounds__(64, MIN_WAVES_PER_SIMD) void balance_kernel(const D
     eqp.setup(*QC_PARAMS_HERE(Pg), L.Wr, L.foot0);
     busy = busy && !probe;
     unsigned solved_mask = 0;  // RACE: strategies of this lane's robot that have reached the KKT point
+    // The lanes whose robot is still running, as the wave's lane mask (a scalar pair).  The loops below test it as the integer it
+    // is, and a recalculation takes its `live` from it for nothing (a lane mask is what a select reads).  Carried as a per-lane
+    // bool instead, `busy` went through a VGPR byte: written and compared after every recalculation for the ballot, masked and
+    // compared twice at the top of the next - and a loop whose test is a ballot (a convergent operation, which loop rotation does
+    // not duplicate) stays top-tested, so everything live past it (f, status and count, the working-set word, the race's mask)
+    // was copied at the header of every recalculation and the exit was a block of its own with mask merges at the latch.
+    // Racing kernels of the packed lanes (the 6x6 uniform form) only.  The 4-lane kernels without a race keep the per-lane flag:
+    // with the mask the uniform form's mode-2 kernel needs ten registers more and loses its third wave per SIMD.  So do the
+    // general and the dense form's racing kernels, which it costs 16 VGPRs and eight more registers parked in AGPRs.
+    constexpr bool MASKED = RACE > 1 && LaneT::kWord;
+    unsigned long long running = MASKED ? __builtin_amdgcn_ballot_w64(busy) : 0ull;
+    auto any_running = [&]() {
+      if constexpr (MASKED) return running != 0;
+      else return __builtin_amdgcn_ballot_w64(busy) != 0;
+    };
+    auto live_now = [&]() -> bool {
+      if constexpr (MASKED) return __builtin_amdgcn_inverse_ballot_w64(running);
+      else return busy;
+    };
     // the robot is finished as soon as one strategy has solved it; the others stop with it
-    auto after = [&](bool done) {
-      if constexpr (RACE > 1) {
+    auto after = [&](bool live, bool done) {
+      if constexpr (RACE > 1 && !MASKED) {
         const int mine = (busy & L.kkt) ? (1 << sid) : 0;
         const int m = race_or<ROB, RACE>(mine);
         solved_mask |= (unsigned)m;
         busy = busy & !done & (solved_mask == 0);
+      } else if constexpr (RACE > 1) {
+        const int mine = L.kkt ? (1 << sid) : 0;  // (kkt = live & solved: Lane::iterate)
+        const int m = race_or<ROB, RACE>(mine);
+        solved_mask |= (unsigned)m;
+        // live & !done & (solved_mask == 0) as ONE compare: what stops the robot, any non-zero value for a lane that stops by itself
+        unsigned stop = (live & !done) ? solved_mask : 1u;
+        asm volatile("" : "+v"(stop));  // (opaque: folded back into the three conditions it is a compare, a mask AND, a select and a second compare)
+        running = __builtin_amdgcn_ballot_w64(stop == 0u);
       } else {
         busy = busy & !done;
       }
@@ -1413,41 +1440,44 @@ __global__ __launch_bounds__(64, MIN_WAVES_PER_SIMD) void balance_kernel(const D
     // clamp steps: one for the racing lanes (their strategies take more in the MIXED recalculations below)
     const int first_steps = RACE > 1 ? 1 : clamp_steps_for<G>(*QC_PARAMS_HERE(Pg), warm);
 #pragma unroll 1
-    for (int k = 0; k < first_steps && (k == 0 || __builtin_amdgcn_ballot_w64(busy) != 0); k++) {
+    for (int k = 0; k < first_steps && (k == 0 || any_running()); k++) {
       if (k) QC_CLK(7, 2);
+      const bool live = live_now();
       bool done;
       if constexpr (RESIDENT) {
         pin_uconst(uc);
-        done = L.template iterate<LaneT::FIRST>(uc, eqp, busy, k == 0 && warm == nullptr);
+        done = L.template iterate<LaneT::FIRST>(uc, eqp, live, k == 0 && warm == nullptr);
       } else {
-        done = L.template iterate<LaneT::FIRST>(*QC_PARAMS_HERE(Pg), eqp, busy, k == 0 && warm == nullptr);
+        done = L.template iterate<LaneT::FIRST>(*QC_PARAMS_HERE(Pg), eqp, live, k == 0 && warm == nullptr);
       }
-      after(done);
+      after(live, done);
     }
     if constexpr (RACE > 1) {  // recalculations 2 and 3: clamp steps for the strategies that take them, ordinary steps for the others
 #pragma unroll 1
-      for (int it = 2; it <= 3 && __builtin_amdgcn_ballot_w64(busy) != 0; it++) {
+      for (int it = 2; it <= 3 && any_running(); it++) {
         QC_CLK(7, 2);
+        const bool live = live_now();
         bool done;
         if constexpr (RESIDENT) {
           pin_uconst(uc);
-          done = L.template iterate<LaneT::MIXED>(uc, eqp, busy);
+          done = L.template iterate<LaneT::MIXED>(uc, eqp, live);
         } else {
-          done = L.template iterate<LaneT::MIXED>(*QC_PARAMS_HERE(Pg), eqp, busy);
+          done = L.template iterate<LaneT::MIXED>(*QC_PARAMS_HERE(Pg), eqp, live);
         }
-        after(done);
+        after(live, done);
       }
     }
-    while (__builtin_amdgcn_ballot_w64(busy) != 0) {
+    while (any_running()) {
       QC_CLK(7, 2);
+      const bool live = live_now();
       bool done;
       if constexpr (RESIDENT) {
         pin_uconst(uc);
-        done = L.template iterate<LaneT::STEADY>(uc, eqp, busy);
+        done = L.template iterate<LaneT::STEADY>(uc, eqp, live);
       } else {
-        done = L.template iterate<LaneT::STEADY>(*QC_PARAMS_HERE(Pg), eqp, busy);
+        done = L.template iterate<LaneT::STEADY>(*QC_PARAMS_HERE(Pg), eqp, live);
       }
-      after(done);
+      after(live, done);
     }
     // RACE: the winner - the lowest-numbered strategy among those that solved the robot in the deciding
     // recalculation, or strategy 0 with whatever status it has if none did - parks the result (no race: slot = grp)
