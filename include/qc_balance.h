@@ -625,7 +625,8 @@ int qc_sensitivity_kin_batch(qc_handle* h, size_t n, const qc_batch_in* in, cons
  *   the semi-implicit Euler step, wdot = Rwb Ib^-1 Rwb^T (tau - w x (Rwb Ib Rwb^T w)) into Rwb_bar, w_bar and tau_bar, and
  *   tau = sum r_l x f_l, r_l = foot_world_l - x, f_l = -Rwb grf_body_l:  f_bar_l = fs_bar + tau_bar x r_l,  r_bar_l = f_l x tau_bar,
  *                                                 grf_bar_l = -Rwb^T f_bar_l,  Rwb_bar += -f_bar_l grf_body_l^T.
- * NOT produced: the cotangents of mass, Ib and dt.  Outputs are written, not accumulated.  Non-finite inputs propagate as NaN;
+ * NOT produced: the cotangents of mass, Ib and dt (of mass and Ib, and of an external wrench: qc_plant_step_model_adjoint_batch,
+ * include/qc_plant_model.h).  Outputs are written, not accumulated.  Non-finite inputs propagate as NaN;
  * nothing is clamped.  Each robot's inputs are all read before any of its outputs is written, and a robot touches its own rows
  * only: an output may be the SAME array as an input cotangent of the same layout (x_bar over x_next_bar, Rwb_bar over
  * Rwb_next_bar, foot_world_bar or grf_bar over feet_next_bar, ...), so backpropagation through time runs in place.  The six state

@@ -471,7 +471,8 @@ int qc_com_reference_tangent_batch(qc_handle* h, size_t n, const qc_batch_in* in
  * not overlap an output.  All pointers are device pointers.  No buffer is kept on the handle.
  *
  * OUT OF SCOPE: per-robot parameter directions; tangents of the kinematic model, of tau_min / tau_max, of the joint gains and of the
- * plant's use of mass and Ib (qc_plant_step_tangent_batch and qc_leg_plant_step_tangent_batch hold them); symmetrised dS / dW;
+ * plant's use of mass and Ib (qc_plant_step_tangent_batch and qc_leg_plant_step_tangent_batch hold them; the reverse mode in
+ * the plant's own mass and Ib is qc_plant_step_model_adjoint_batch, include/qc_plant_model.h); symmetrised dS / dW;
  * fusing this launch with qc_tangent_batch - it repeats that call's classification and factorisation (profiles/param_tangent.md
  * has what that costs). */
 typedef struct qc_param_tangent_io {

@@ -35,4 +35,8 @@ def __getattr__(name):
         import importlib
 
         return importlib.import_module(".tangent", __name__)
+    if name == "plant_model":  # a plant of its own: q.plant_model.plant_step(ctl, ..., model), q.plant_model.rollout(ctl, ..., model)
+        import importlib
+
+        return importlib.import_module(".plant_model", __name__)
     raise AttributeError(name)

@@ -509,6 +509,8 @@ class BalanceController:
                           certify_every, stream)
         step = self.plan_plant(state, r.out["grf_body"], foot_world, dt, batch["feet"], stream)
         history = [] if record_every else None
+        # (plant_model.rollout runs this method on a stand-in whose plan_plant is the model's: the step is planned ONCE, above, launched
+        # once per step in step order and nowhere else, and no attribute is set on self - its push schedule counts these launches)
         for k in range(steps):
             if history is not None and k % int(record_every) == 0:
                 history.append((k, {name: batch[name].clone() for name in ("Rwb", "x", "xdot", "w", "feet")}))
@@ -693,6 +695,8 @@ class BalanceController:
             # (of the batch: what the polygon reads - the library refuses the clock and the planner's record)
             reads = {name: batch[name] for name in ("joint_q", "Rwb", "x", "gait_phase", "stance", "gait_duty") if batch.get(name) is not None}
             lean_x_d = self.plan_com_reference(reads, schedule, batch["x_d"].clone(), mode, gain, out={"x_d": batch["x_d"]}, stream=stream)[0]
+        # (plant_model.rollout_tick runs this method on a stand-in whose plan_leg_plant is the model's: the step is planned ONCE, above,
+        # launched once per step in step order and nowhere else, and no attribute is set on self - its push schedule counts these launches)
         for k in range(steps):
             rec = None
             if history is not None and k % int(record_every) == 0:

@@ -17,6 +17,7 @@
 #include "qc_device.hpp"
 #include "qc_host.hpp"
 #include "qc_plant.hpp"
+#include "qc_plant_model.hpp"
 
 namespace qc {
 
@@ -2337,6 +2338,47 @@ int qc_leg_plant_step_adjoint_batch(qc_handle* h, size_t n, const qc_leg_plant_a
   const unsigned blocks = (unsigned)((n + qc::LEG_PLANT_BLOCK - 1) / qc::LEG_PLANT_BLOCK);
   return launch_flat(qc::leg_plant_step_adjoint_kernel, blocks, qc::LEG_PLANT_BLOCK, stream, h->d_params, (long)n, a);
 }
+
+void qc_default_plant_model(qc_plant_model* model) { (void)zeroed(model); }
+void qc_default_plant_model_bar(qc_plant_model_bar* bar) { (void)zeroed(bar); }
+
+// the instantiation <MASS, IB, WRENCH> of a model kernel for plant_model_variant()'s word (1 ... 7)
+#define QC_MODEL_KERNELS(kernel)                                                                                                      \
+  {nullptr, qc::kernel<true, false, false>, qc::kernel<false, true, false>, qc::kernel<true, true, false>, qc::kernel<false, false, true>, \
+   qc::kernel<true, false, true>, qc::kernel<false, true, true>, qc::kernel<true, true, true>}
+
+int qc_plant_step_model_batch(qc_handle* h, size_t n, const qc_plant_io* io, const qc_plant_model* model, void* stream) {
+  if (const int rc = qc::check_plant_model_args(h, n, io, model); rc != QC_OK || n == 0) return rc;
+  qc::PlantArgs a;
+  if (const int rc = qc::plant_model_constants(h->dp.mass, h->dp.Ib, io, model, a); rc != QC_OK) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  static void (*const kernels[8])(long, qc::PlantArgs, qc::PlantModelArgs) = QC_MODEL_KERNELS(plant_step_model_kernel);
+  const unsigned blocks = (unsigned)((n + qc::PLANT_BLOCK - 1) / qc::PLANT_BLOCK);
+  return launch_flat(kernels[qc::plant_model_variant(model)], blocks, qc::PLANT_BLOCK, stream, (long)n, a, qc::plant_model_args(model));
+}
+
+int qc_leg_plant_step_model_batch(qc_handle* h, size_t n, const qc_leg_plant_io* io, const qc_plant_model* model, void* stream) {
+  if (const int rc = qc::check_leg_plant_model_args(h, n, io, model); rc != QC_OK || n == 0) return rc;
+  qc::LegPlantArgs a;
+  if (const int rc = qc::leg_plant_model_constants(h->dp.mass, h->dp.Ib, io, model, a); rc != QC_OK) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  static void (*const kernels[8])(const qc::DevParams*, long, qc::LegPlantArgs, qc::PlantModelArgs) = QC_MODEL_KERNELS(leg_plant_step_model_kernel);
+  const unsigned blocks = (unsigned)((n + qc::LEG_PLANT_BLOCK - 1) / qc::LEG_PLANT_BLOCK);
+  return launch_flat(kernels[qc::plant_model_variant(model)], blocks, qc::LEG_PLANT_BLOCK, stream, h->d_params, (long)n, a, qc::plant_model_args(model));
+}
+
+int qc_plant_step_model_adjoint_batch(qc_handle* h, size_t n, const qc_plant_adjoint_io* io, const qc_plant_model* model,
+                                      const qc_plant_model_bar* bar, void* stream) {
+  if (const int rc = qc::check_plant_model_adjoint_args(h, n, io, model, bar); rc != QC_OK || n == 0) return rc;
+  qc::PlantAdjointArgs a;
+  if (const int rc = qc::plant_model_adjoint_constants(h->dp.mass, h->dp.Ib, io, model, a); rc != QC_OK) return rc;
+  QC_HIP(hipSetDevice(h->device));
+  static void (*const kernels[8])(long, qc::PlantAdjointArgs, qc::PlantModelArgs, qc::PlantModelBarArgs) = QC_MODEL_KERNELS(plant_step_model_adjoint_kernel);
+  const unsigned blocks = (unsigned)((n + qc::PLANT_BLOCK - 1) / qc::PLANT_BLOCK);
+  return launch_flat(kernels[qc::plant_model_variant(model)], blocks, qc::PLANT_BLOCK, stream, (long)n, a, qc::plant_model_args(model),
+                     qc::plant_model_bar_args(bar));
+}
+#undef QC_MODEL_KERNELS
 
 void qc_default_certify(qc_certify_io* io) {
   if (!zeroed(io)) return;

@@ -9,6 +9,7 @@
 
 #include "../../include/qc_balance.h"
 #include "../../include/qc_tangent.h"
+#include "../../include/qc_plant_model.h"
 #include "qc_device.hpp"
 #include "qc_plant.hpp"
 #include "qc_plant_adjoint.hpp"
@@ -32,6 +33,7 @@
 #include "qc_swing_reference_tangent.hpp"
 #include "qc_command_tangent.hpp"
 #include "qc_param_tangent.hpp"
+#include "qc_plant_model.hpp"
 
 namespace qc {
 
@@ -1197,6 +1199,101 @@ inline ComReferenceTangentArgs com_reference_tangent_constants(const qc_batch_in
   a.com_xy_tan = io->com_xy_tan;
   a.flags = io->flags;
   return a;
+}
+
+// ---------------------------------------------------------------- qc_plant_step_model_batch, qc_leg_plant_step_model_batch, qc_plant_step_model_adjoint_batch
+// What the three calls of include/qc_plant_model.h refuse about the model, after everything the base call refuses about its record:
+// no model, a model of another revision, and - for n > 0: n = 0 reads no array, of the model's either - a model that changes nothing
+// (`base`: the call to make instead).
+inline int check_plant_model(const char* who, const char* base, size_t n, const qc_plant_model* m) {
+  if (!m) return fail(QC_ERR_INVALID, std::string(who) + ": null argument");
+  if (const int rc = check_struct_size(who, "qc_plant_model", "qc_default_plant_model", m->struct_size, sizeof(qc_plant_model)); rc != QC_OK) return rc;
+  if (n > 0 && !m->mass && !m->Ib && !m->wrench_world)
+    return fail(QC_ERR_INVALID, std::string(who) + ": the model gives neither mass, Ib nor wrench_world - call " + base);
+  return QC_OK;
+}
+
+inline int check_plant_model_args(const qc_handle* h, size_t n, const qc_plant_io* io, const qc_plant_model* m) {
+  const char* who = "qc_plant_step_model_batch";
+  if (const int rc = check_io(who, h != nullptr, io, "qc_plant_io", "qc_default_plant"); rc != QC_OK) return rc;
+  if (const int rc = check_plant_io(who, n, io, nullptr, io->grf_body && io->foot_world, ": grf_body and foot_world are required", PLANT_BLOCK); rc != QC_OK) return rc;
+  return check_plant_model(who, "qc_plant_step_batch", n, m);
+}
+
+inline int check_leg_plant_model_args(const qc_handle* h, size_t n, const qc_leg_plant_io* io, const qc_plant_model* m) {
+  const char* who = "qc_leg_plant_step_model_batch";
+  if (const int rc = check_io(who, h != nullptr, io, "qc_leg_plant_io", "qc_default_leg_plant"); rc != QC_OK) return rc;
+  const char* own = nullptr;
+  for (int k = 0; k < 3; k++)
+    if (!std::isfinite(io->leg_inertia[k]) || !(io->leg_inertia[k] > 0.0))
+      own = ": leg_inertia (hip, thigh, calf) must be finite and > 0; qc_default_leg_plant leaves it at 0, the caller gives it";
+  if (const int rc = check_plant_io(who, n, io, own, io->joint_q && io->joint_qdot && io->joint_tau, ": joint_q, joint_qdot and joint_tau are required", LEG_PLANT_BLOCK);
+      rc != QC_OK)
+    return rc;
+  return check_plant_model(who, "qc_leg_plant_step_batch", n, m);
+}
+
+// (`bar` may be NULL; an output of either record will do)
+inline int check_plant_model_adjoint_args(const qc_handle* h, size_t n, const qc_plant_adjoint_io* io, const qc_plant_model* m, const qc_plant_model_bar* bar) {
+  const char* who = "qc_plant_step_model_adjoint_batch";
+  if (const int rc = check_io(who, h != nullptr, io, "qc_plant_adjoint_io", "qc_default_plant_adjoint"); rc != QC_OK) return rc;
+  if (bar)
+    if (const int rc = check_struct_size(who, "qc_plant_model_bar", "qc_default_plant_model_bar", bar->struct_size, sizeof(qc_plant_model_bar)); rc != QC_OK) return rc;
+  const char* own = nullptr;
+  if (!io->Rwb_next_bar && !io->x_next_bar && !io->xdot_next_bar && !io->w_next_bar && !io->feet_next_bar)
+    own = ": no input cotangent given (Rwb_next_bar, x_next_bar, xdot_next_bar, w_next_bar, feet_next_bar are all NULL)";
+  else if (!io->Rwb_bar && !io->x_bar && !io->xdot_bar && !io->w_bar && !io->grf_bar && !io->foot_world_bar &&
+           !(bar && (bar->wrench_bar || bar->mass_bar || bar->Ib_bar)))
+    own = ": no output requested (Rwb_bar, x_bar, xdot_bar, w_bar, grf_bar, foot_world_bar and the model's wrench_bar, mass_bar, Ib_bar are all NULL)";
+  if (const int rc = check_plant_io(who, n, io, own, io->grf_body && io->foot_world, ": grf_body and foot_world are required", PLANT_BLOCK); rc != QC_OK) return rc;
+  return check_plant_model(who, "qc_plant_step_adjoint_batch", n, m);
+}
+
+// The body's constants under a model: what the model supplies per robot is not asked of the handle (a placeholder - 1, the identity -
+// travels in its place and is never read by that instantiation); the rest is judged as body_constants judges it.
+inline int model_body_constants(const char* who, double mass, const double* Ib, double dt, const qc_plant_model* m, BodyConst& b) {
+  if (!m->mass && (!std::isfinite(mass) || !(mass > 0.0))) return fail(QC_ERR_INVALID, std::string(who) + ": the handle's mass is not finite and > 0");
+  b.mass = m->mass ? 1.0 : mass;
+  if (m->Ib) {
+    for (int k = 0; k < 9; k++) b.Ib[k] = b.Ib_inv[k] = (k % 4 == 0) ? 1.0 : 0.0;
+  } else {
+    if (const int rc = plant_inertia_inverse(Ib, b.Ib_inv, who); rc != QC_OK) return rc;
+    std::memcpy(b.Ib, Ib, sizeof(b.Ib));
+  }
+  b.g = PLANT_G;
+  b.dt = dt;
+  return QC_OK;
+}
+
+inline PlantModelArgs plant_model_args(const qc_plant_model* m) { return PlantModelArgs{m->mass, m->Ib, m->wrench_world, m->flags}; }
+inline PlantModelBarArgs plant_model_bar_args(const qc_plant_model_bar* bar) {
+  return bar ? PlantModelBarArgs{bar->wrench_bar, bar->mass_bar, bar->Ib_bar, bar->flags} : PlantModelBarArgs{nullptr, nullptr, nullptr, nullptr};
+}
+// which of the eight instantiations <MASS, IB, WRENCH> a model selects: bit 0 mass, bit 1 Ib, bit 2 wrench_world (0 is refused)
+inline int plant_model_variant(const qc_plant_model* m) { return (m->mass ? 1 : 0) | (m->Ib ? 2 : 0) | (m->wrench_world ? 4 : 0); }
+
+inline int plant_model_constants(double mass, const double* Ib, const qc_plant_io* io, const qc_plant_model* m, PlantArgs& a) {
+  if (const int rc = model_body_constants("qc_plant_step_model_batch", mass, Ib, io->dt, m, a); rc != QC_OK) return rc;
+  a.Rwb = io->Rwb; a.x = io->x; a.xdot = io->xdot; a.w = io->w; a.grf_body = io->grf_body; a.foot_world = io->foot_world; a.feet = io->feet;
+  return QC_OK;
+}
+
+inline int leg_plant_model_constants(double mass, const double* Ib, const qc_leg_plant_io* io, const qc_plant_model* m, LegPlantArgs& a) {
+  if (const int rc = model_body_constants("qc_leg_plant_step_model_batch", mass, Ib, io->dt, m, a); rc != QC_OK) return rc;
+  for (int k = 0; k < 3; k++) a.leg_inertia[k] = io->leg_inertia[k];
+  a.Rwb = io->Rwb; a.x = io->x; a.xdot = io->xdot; a.w = io->w; a.joint_q = io->joint_q; a.joint_qdot = io->joint_qdot; a.joint_tau = io->joint_tau;
+  a.stance = io->stance; a.gait_phase = io->gait_phase; a.gait_duty = io->gait_duty; a.cmd_state = reinterpret_cast<const CmdState*>(io->cmd_state);
+  a.foot_world = io->foot_world; a.flags = io->flags;
+  return QC_OK;
+}
+
+inline int plant_model_adjoint_constants(double mass, const double* Ib, const qc_plant_adjoint_io* io, const qc_plant_model* m, PlantAdjointArgs& a) {
+  if (const int rc = model_body_constants("qc_plant_step_model_adjoint_batch", mass, Ib, io->dt, m, a); rc != QC_OK) return rc;
+  a.Rwb = io->Rwb; a.x = io->x; a.xdot = io->xdot; a.w = io->w; a.grf_body = io->grf_body; a.foot_world = io->foot_world;
+  a.Rwb_next_bar = io->Rwb_next_bar; a.x_next_bar = io->x_next_bar; a.xdot_next_bar = io->xdot_next_bar; a.w_next_bar = io->w_next_bar;
+  a.feet_next_bar = io->feet_next_bar;
+  a.Rwb_bar = io->Rwb_bar; a.x_bar = io->x_bar; a.xdot_bar = io->xdot_bar; a.w_bar = io->w_bar; a.grf_bar = io->grf_bar; a.foot_world_bar = io->foot_world_bar;
+  return QC_OK;
 }
 
 }  // namespace qc
